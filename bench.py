@@ -10,6 +10,7 @@ different chunk. Flags of the headline: the reference's DisparityUtil.cpp:149,29
 withScale=false, 6.0); the (true, true) flags of FeatureMatchUtil.cpp:69 are reported beside it under "rot_scale".
 
   python bench.py --gpus N --steps K --warmup W         (N > 1 without a launcher: starts the N ranks itself)
+  python bench.py ... --dump-outputs DIR                 (also writes what the last timed step computed: dump_outputs)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -54,7 +55,13 @@ def parse():
                     help="diagnostic: keypoints listed cell by cell instead of in random order (LDS bank-conflict experiment, DESIGN.md 6)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg (profiling runs)")
     ap.add_argument("--no-extra", action="store_true", help="skip the rot+scale side measurement")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(every pair's result record, the survivors of a fixed sample of its pairs; rank 0's shard)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def spawn_ranks(args):
@@ -159,6 +166,40 @@ def timed_steps(ctx, wl, stream, steps, warmup, rot, scale, dist, first_chunk=0,
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     return wall, float(np.mean([a.elapsed_time(b) for a, b in ev]))
+
+
+DUMP_SEED = 0x6D5  # which pairs of the last step --dump-outputs writes in full
+DUMP_SAMPLE_PAIRS = 256
+DUMP_MATCH_BYTES = 48 << 20  # budget of the survivors' records (float32 x 4 per match; everything else is small)
+
+
+def dump_outputs(wl, pkg, chunk, out_dir):
+    """--dump-outputs: what the launch on `chunk` (the last timed step) handed its caller, as float arrays.
+    results.npy          float64 [pairs, 4]   every pair's gms_result: n_inliers, best_scale, best_rot, status
+    sample_pairs.npy     float64 [S, 4]       the sampled pairs: index in the step, frame_a, frame_b, survivors
+    sample_matches.npy   float32 [sum, 4]     their surviving gms_dmatch records in order: queryIdx, trainIdx, imgIdx, distance
+    The sample is a fixed, seeded choice of S pairs of the step, sized so that S x M records stay within DUMP_MATCH_BYTES."""
+    import torch
+    ch, n_kp = wl.chunks[chunk], wl.n_kp
+    res = ch["d_res"].cpu().numpy().view(pkg.RESULT_DTYPE).reshape(-1)
+    n_pairs = len(res)
+    n_sample = max(1, min(DUMP_SAMPLE_PAIRS, n_pairs, DUMP_MATCH_BYTES // (16 * n_kp)))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_pairs, n_sample, replace=False))
+    kept = res["n_inliers"][idx].astype(np.int64)
+    rows = np.concatenate([np.arange(j * n_kp, j * n_kp + k, dtype=np.int64) for j, k in zip(idx, kept)])
+    recs = ch["d_out"].index_select(0, torch.from_numpy(rows).to(ch["d_out"].device)).cpu().numpy()
+    recs = recs.view(np.uint8).reshape(-1).view(pkg.DMATCH_DTYPE)
+    pairs = ch["pairs"][idx]
+    arrays = {
+        "results": np.stack([res[f].astype(np.float64) for f in pkg.RESULT_DTYPE.names], axis=1),
+        "sample_pairs": np.stack([idx, pairs["frame_a"], pairs["frame_b"], kept], axis=1).astype(np.float64),
+        "sample_matches": np.stack([recs[f].astype(np.float32) for f in pkg.DMATCH_DTYPE.names], axis=1),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "step_chunk": chunk, "pairs": n_pairs, "sample_pairs": n_sample,
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 def opencv_on_box():
@@ -743,6 +784,9 @@ def main():
     variant = {"dealt": bool(ctx.query(1)), "matches_per_thread": ctx.query(3),  # which bit-identical instantiation the timed launches ran
                "touch_ahead": {"before_grid_type": ctx.query(6), "pairs_ahead": ctx.query(7)}, "first_round_stagger_us": ctx.query(8) / 100.0}
     value = wl.n_pairs * world * args.steps / wall_max
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything else launches on the chunks
+        dumped = dump_outputs(wl, pkg, (args.warmup + args.steps - 1) % n_res, args.dump_outputs)
 
     # ---- parity on every rank: the sampled pairs of every resident chunk, as the timed launches left them
     checked, bad = check_parity(wl, pkg, range(n_res), False, False)
@@ -785,6 +829,8 @@ def main():
                        "rule": f"every {distmod.PARITY_EVERY}th global pair of every resident chunk, on every rank, vs oracle/gms_ref.c"},
             "opencv_on_box": opencv_on_box(),
         }
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         tpath = os.path.join(ROOT, "profiles", "traffic.json")
         if os.path.exists(tpath):  # measured in a separate rocprofv3 --pmc run (tools/pmc_collect.sh), not in this one
             try:

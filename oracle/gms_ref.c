@@ -25,7 +25,7 @@
  *   - select_hypothesis (getInlierMask: loop nest and order, strict '>', the mask copy, the value returned):
  *     GMSMatcher::getInlierMask executed WHOLE with its eight calls of setScale / run re-pointed at a script player, every flag
  *     combination, eleven scripts -- ties, all zero, maximum first / last (refdll_select.npz);
- *   - the rotation-pattern table, the scale-ratio table and the 0.5 constant, byte for byte (when /root/reference exists);
+ *   - the rotation-pattern table, the scale-ratio table and the 0.5 constant, byte for byte (refdll_tables.npz);
  *   - END TO END (refdll_chain.npz): getInlierMask executed whole with those calls re-pointed at drivers that run the DLL's own
  *     pieces (setScale's head + initalizeNeighbors; per grid type assignMatchPairs, the verifyCellPairs body per cell, run's
  *     marking / counting tail), behind the DLL's normalizePoints -- on the inputs of all fourteen golden cases (BASELINE configs 1

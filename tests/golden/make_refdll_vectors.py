@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/refdll_*.npz (grid index, assign pairs, verify cells). refdll_grid_index.npz: (nx, ny) -> cell indices AS RETURNED BY THE REFERENCE'S OWN BINARY.
+"""Generates tests/golden/refdll_*.npz (grid index, assign pairs, verify cells, constant tables). refdll_grid_index.npz: (nx, ny) -> cell indices AS RETURNED BY THE REFERENCE'S OWN BINARY.
 
 refdll_runner.c maps SfM-GMS/bin/opencv_xfeatures2d452.dll and calls its GMSMatcher::getGridIndexLeft /
 getGridIndexRight (two leaf functions) on the inputs built here. Needs /root/reference; run in the build container:
@@ -224,6 +224,26 @@ def setscale_fixture():
     print("setscale fixture", out["ratios"].tolist(), out["left20x20"].tolist())
 
 
+TABLES = {  # name: (file offset in the DLL, bytes)
+    "rotation_patterns": (0x12DF20, 288),  # mRotationPatterns: .rdata VA 0x18012f520, 8 x 9 int32
+    "scale_ratios": (0x2C2C08, 40),        # mScaleRatios: .data VA 0x1802c5008, 5 double (slots 2, 3 filled at load time)
+    "half": (0x12C9C0, 8),                 # the 0.5 added before the fp64 floor of the shifted grids: VA 0x18012dfc0
+}
+
+
+def tables_fixture():
+    """The constant tables of the path, byte for byte as the DLL file holds them (refdll_tables.npz), with their file
+    offsets and the DLL's SHA-256: tests/test_oracle_pins.py compares the oracle's tables with these bytes."""
+    import hashlib
+    data = open(DLL, "rb").read()
+    out = {"dll_sha256": np.array(hashlib.sha256(data).hexdigest())}
+    for name, (off, n) in TABLES.items():
+        out[name] = np.frombuffer(data[off:off + n], dtype=np.uint8).copy()
+        out[name + "_offset"] = np.int64(off)
+    np.savez_compressed(os.path.join(HERE, "refdll_tables.npz"), **out)
+    print("tables fixture", {k: len(v) for k, v in out.items() if v.dtype == np.uint8})
+
+
 def _runner(tmp):
     exe = os.path.join(tmp, "refdll_runner")
     subprocess.check_call(["gcc", "-O1", "-o", exe, os.path.join(HERE, "refdll_runner.c")])
@@ -399,6 +419,7 @@ def main():
     mark_fixture()
     select_fixture()
     chain_fixture()
+    tables_fixture()
     print(len(pts), "points;", "left range", res[:, :4].min(), res[:, :4].max(), "; file",
           os.path.getsize(os.path.join(HERE, "refdll_grid_index.npz")), "bytes")
 

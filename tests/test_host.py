@@ -162,6 +162,55 @@ def test_bench_refuses_a_world_size_that_contradicts_gpus():
     assert res.returncode != 0 and "--gpus 4" in res.stderr
 
 
+def test_bench_refuses_zero_timed_steps():
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert res.returncode != 0 and "--steps" in res.stderr
+
+
+def test_bench_dump_outputs_writes_what_the_step_returned(pkg, tmp_path):
+    """bench.dump_outputs on a stand-in for a resident chunk (CPU tensors): every result record, the survivors of the seeded
+    sample in order, float32 / float64 only, within 64 MB at 10k matches per pair, the same files from run to run."""
+    import importlib
+    import torch
+    bench = importlib.import_module("bench")
+    d = importlib.import_module("sfm-gms_amd.dist")
+    n_pairs, n_kp = 300, 10000
+    rng = np.random.default_rng(5)
+    res = np.zeros(n_pairs, dtype=pkg.RESULT_DTYPE)
+    res["n_inliers"] = rng.integers(0, n_kp + 1, n_pairs)
+    res["n_inliers"][::7] = n_kp  # pairs that keep everything: the size bound holds for them too
+    res["best_rot"], res["best_scale"] = rng.integers(0, 8, n_pairs), rng.integers(0, 5, n_pairs)
+    out = np.zeros(n_pairs * n_kp, dtype=pkg.DMATCH_DTYPE)
+    out["queryIdx"], out["trainIdx"] = np.tile(np.arange(n_kp), n_pairs), rng.integers(0, n_kp, n_pairs * n_kp)
+    out["distance"] = rng.random(n_pairs * n_kp, dtype=np.float32)
+
+    class Wl:
+        chunks = [None, dict(pairs=d.pair_table(40, 100, 100 + n_pairs, n_kp),
+                             d_out=torch.from_numpy(out.view(np.int32).reshape(-1, 4).copy()),
+                             d_res=torch.from_numpy(res.view(np.int32).reshape(-1, 4).copy()))]
+    Wl.n_kp = n_kp
+
+    info = bench.dump_outputs(Wl, pkg, 1, str(tmp_path / "a"))
+    bench.dump_outputs(Wl, pkg, 1, str(tmp_path / "b"))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["results.npy", "sample_matches.npy", "sample_pairs.npy"] == sorted(os.listdir(tmp_path / "b"))
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) == info["bytes"] <= 64 << 20
+    for f in files:
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes()
+    assert np.array_equal(got["results"], np.stack([res[f] for f in pkg.RESULT_DTYPE.names], axis=1))
+    sp = got["sample_pairs"]
+    assert len(sp) == info["sample_pairs"] > 0 and np.all(np.diff(sp[:, 0]) > 0)
+    pt = Wl.chunks[1]["pairs"]
+    want = []
+    for j, fa, fb, k in sp.astype(np.int64):
+        assert (fa, fb, k) == (pt["frame_a"][j], pt["frame_b"][j], res["n_inliers"][j])
+        want.append(out[j * n_kp:j * n_kp + k])
+    want = np.concatenate(want)
+    assert np.array_equal(got["sample_matches"], np.stack([want[f].astype(np.float32) for f in pkg.DMATCH_DTYPE.names], axis=1))
+
+
 def test_vectorised_pair_indexing_and_match_synthesis(pkg):
     import importlib
     d = importlib.import_module("sfm-gms_amd.dist")

@@ -1,34 +1,32 @@
 """CPU: pins for the oracle's pieces. The reference holds no tests or golden vectors for this path
 (parity unpinned); what CAN be pinned is pinned here: the constant tables byte for byte
-against the reference's DLL (when /root/reference is present), and the arithmetic of each piece against
-hand-derived known answers taken from the DLL's disassembly."""
+against the reference's DLL (tests/golden/refdll_tables.npz, bytes cut out of the DLL file), and the arithmetic of each
+piece against hand-derived known answers taken from the DLL's disassembly."""
 import math
 import os
 import struct
 
 import numpy as np
-import pytest
 
-DLL = "/root/reference/SfM-GMS/bin/opencv_xfeatures2d452.dll"
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-@pytest.mark.skipif(not os.path.exists(DLL), reason="reference DLL not present on this box")
 def test_tables_match_reference_dll(oracle):
     import ctypes as C
     lib = oracle.load()
-    data = open(DLL, "rb").read()
+    z = np.load(os.path.join(GOLDEN, "refdll_tables.npz"))  # make_refdll_vectors.py: tables_fixture
+    assert (int(z["rotation_patterns_offset"]), int(z["scale_ratios_offset"]), int(z["half_offset"])) == (0x12DF20, 0x2C2C08, 0x12C9C0)
     # mRotationPatterns: .rdata VA 0x18012f520 -> file offset 0x12df20, 8 x 9 int32
-    rot = struct.unpack("<72i", data[0x12DF20:0x12DF20 + 288])
+    rot = struct.unpack("<72i", z["rotation_patterns"].tobytes())
     mine = (C.c_int * 72).in_dll(lib, "gms_ref_rotation_patterns")
     assert tuple(mine) == rot
     # mScaleRatios: .data VA 0x1802c5008 -> file offset 0x2c2c08; slots 2, 3 are filled by the static
     # initialiser (1/sqrt2, sqrt2), the others are literal
-    sc = struct.unpack("<5d", data[0x2C2C08:0x2C2C08 + 40])
+    sc = struct.unpack("<5d", z["scale_ratios"].tobytes())
     assert sc[0] == 1.0 and sc[1] == 0.5 and sc[4] == 2.0 and sc[2] == 0.0 and sc[3] == 0.0
     assert [lib.gms_ref_scale_ratio(i) for i in range(5)] == [1.0, 0.5, 1.0 / math.sqrt(2.0), math.sqrt(2.0), 2.0]
     # the 0.5 added before the fp64 floor of the shifted grids: VA 0x18012dfc0 -> file offset 0x12c9c0
-    assert struct.unpack("<d", data[0x12C9C0:0x12C9C8])[0] == 0.5
+    assert struct.unpack("<d", z["half"].tobytes())[0] == 0.5
 
 
 def test_rotation_patterns_are_rotations_of_the_ring(oracle):
