@@ -383,6 +383,26 @@ int gms_detect_batch_device(gms_ctx* ctx, const uint8_t* d_images, int n_images,
 int gms_describe_device(gms_ctx* ctx, const uint8_t* d_image, int width, int height, gms_keypoint* d_keypoints, int n,
                         void* d_workspace, size_t workspace_bytes, uint8_t* d_descriptors, int32_t* d_status);
 
+/* ---- LOGOS match filter -----------------------------------------------------------------------
+ * cv::xfeatures2d::matchLOGOS(keypoints1, keypoints2, nn1, nn2, matches1to2) (FeatureMatchUtil.cpp:86-131; DESIGN.md, LOGOS):
+ * candidates are the pairs (i, j) with nn1[i] == nn2[j]; a candidate survives if it has local support among the five nearest
+ * neighbours of i and of j, and its relative orientation lies within 0.1 rad of the peak of the supported candidates' histogram.
+ * Reads pt, size and angle of each keypoint. Output: (queryIdx = i, trainIdx = j, imgIdx = -1, distance = 0), i ascending, then j.
+ * Host pointers; synchronous; uses the current HIP device. out_cap: room in `out`. *n_out: the number of survivors -- also when
+ * that exceeds out_cap, in which case nothing is written and GMS_ERR_CAPACITY is returned. result may be NULL.
+ * Neighbours at equal distances are taken in the order the reference's (unstable) std::sort leaves them in, restated in
+ * logos_core.h. Frames of 1..5 keypoints use the neighbours there are (the reference reads past its list there). */
+typedef struct gms_logos_result {
+    int64_t n_candidates; /* pairs with equal labels                                   */
+    int64_t n_supported;  /* candidates with local support                             */
+    int64_t n_out;        /* survivors (the needed count on overflow)                  */
+    int32_t peak_bin;     /* 0..188, -1 when no candidate had support                  */
+    int32_t status;       /* GMS_OK or GMS_ERR_CAPACITY                                */
+} gms_logos_result;
+
+int gms_logos_match(const gms_keypoint* kp1, int n1, const gms_keypoint* kp2, int n2, const int32_t* nn1, const int32_t* nn2,
+                    gms_dmatch* out, int64_t out_cap, int64_t* n_out, gms_logos_result* result);
+
 const char* gms_error_string(int code);
 const char* gms_version(void);
 

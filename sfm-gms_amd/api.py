@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from .capi import load_library
-from .types import (DMATCH_DTYPE, KEYPOINT_DTYPE, PAIR_DTYPE, RESULT_DTYPE, GMS_OK, GmsError)
+from .types import (DMATCH_DTYPE, KEYPOINT_DTYPE, PAIR_DTYPE, RESULT_DTYPE, GMS_OK, GMS_ERR_CAPACITY, GmsError)
 
 
 def _as(arr, dtype, name):
@@ -278,3 +278,29 @@ def matchGMS(size1, size2, keypoints1, keypoints2, matches1to2, withRotation=Fal
         _default_ctx = GmsContext(0)
     return _default_ctx.match(size1, size2, keypoints1, keypoints2, matches1to2, withRotation, withScale,
                               thresholdFactor)
+
+
+def matchLOGOS(keypoints1, keypoints2, nn1, nn2):
+    """cv::xfeatures2d::matchLOGOS(keypoints1, keypoints2, nn1, nn2, matches1to2) (FeatureMatchUtil.cpp:86-131) on the GPU.
+
+    keypoints*: KEYPOINT_DTYPE arrays (pt, size and angle are read); nn*: the visual word of each keypoint (int32). Returns the
+    surviving DMATCH_DTYPE records (queryIdx, trainIdx, imgIdx -1, distance 0) in the reference's order."""
+    lib = load_library()
+    kp1 = _as(keypoints1, KEYPOINT_DTYPE, "keypoints1")
+    kp2 = _as(keypoints2, KEYPOINT_DTYPE, "keypoints2")
+    l1 = np.ascontiguousarray(nn1, dtype=np.int32)
+    l2 = np.ascontiguousarray(nn2, dtype=np.int32)
+    if l1.shape != (len(kp1),) or l2.shape != (len(kp2),):
+        raise ValueError("nn1 / nn2 must hold one label per keypoint")
+    # survivors rarely outnumber the larger frame: that first capacity avoids a second run in the common case
+    cap = max(len(kp1), len(kp2))
+    while True:
+        out = np.zeros(max(cap, 1), DMATCH_DTYPE)
+        n = C.c_int64(0)
+        rc = lib.gms_logos_match(kp1.ctypes.data, len(kp1), kp2.ctypes.data, len(kp2), l1.ctypes.data, l2.ctypes.data,
+                                 out.ctypes.data, cap, C.byref(n), None)
+        if rc == GMS_ERR_CAPACITY and n.value > cap:   # run again with room for what it reported
+            cap = n.value
+            continue
+        _check(rc, lib, "gms_logos_match")
+        return out[: n.value].copy()

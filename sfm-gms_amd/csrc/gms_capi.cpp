@@ -29,6 +29,10 @@ static_assert(sizeof(gms_pair_result) == 16, "gms_pair_result layout");
 static_assert(sizeof(gms_two_view) == 232 && sizeof(gms_camera) == 72, "two-view records");
 
 static thread_local int t_last_hip = 0;
+// for the other translation units of the library (logos_kernels.hip): what gms_last_hip_error() reports
+namespace gms {
+void record_hip_error(int e) { t_last_hip = e; }
+}
 #ifdef GMS_PHASE_TIMING
 static unsigned long long* g_diag = nullptr;
 extern "C" int gms_diag_set_buffer(void* d_buf) { g_diag = (unsigned long long*)d_buf; return 0; }

@@ -1,0 +1,172 @@
+"""CPU: the LOGOS match filter's restatement against the reference DLL, and the host build of its kernel arithmetic.
+
+tests/golden/refdll_logos.npz holds cv::xfeatures2d::matchLOGOS run whole out of the reference DLL (make_logos_vectors.py,
+logos_runner.c; logf / acosf of libm in place of the Windows CRT's -- the fixture's one residue). tests/logos_ref.py restates
+it in numpy; sfm-gms_amd/csrc/logos_core.h is what the kernels run per lane, compiled here for the host (tests/cpp/logos_host.cpp).
+"""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import logos_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIXTURE = os.path.join(ROOT, "tests", "golden", "refdll_logos.npz")
+
+
+def fixture_cases():
+    z = np.load(FIXTURE)
+    names = sorted(k[: -len("_matches")] for k in z.files if k.endswith("_matches"))
+    return z, names
+
+
+Z, NAMES = fixture_cases()
+
+
+def test_fixture_metadata():
+    assert len(str(Z["dll_sha256"])) == 64
+    # the case whose neighbour sets tie across the fifth place (the DLL's tie order is MSVC std::sort's)
+    assert "grid_ties_n600" in list(Z["tie_cases"]) and "detector_1080p" in list(Z["tie_cases"])
+    assert "random_n10000" in NAMES and "single_label_n200" in NAMES and "empty_both" in NAMES
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_restatement_reproduces_dll(name):
+    got = logos_ref.match(Z[name + "_kp1"], Z[name + "_kp2"], Z[name + "_nn1"], Z[name + "_nn2"])
+    want = Z[name + "_matches"]
+    assert got.dtype == np.int32 and got.tobytes() == want.astype(np.int32).tobytes()
+
+
+def test_fixture_has_real_peaks():
+    # the inlier cases keep most of their inliers, so the histogram peak is real
+    for name in ("rot30_s1.3", "rot_m115_s0.7", "rot57_s1.0"):
+        m = Z[name + "_matches"]
+        assert len(m) > 0.6 * len(Z[name + "_kp1"])
+        assert np.all(np.diff(m[:, 0]) >= 0)
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("logos") / "liblogos_host.so")
+    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wextra", "-Werror",
+                           "-I" + os.path.join(ROOT, "sfm-gms_amd", "csrc"), "-o", so, os.path.join(ROOT, "tests", "cpp", "logos_host.cpp")])
+    lib = C.CDLL(so)
+    vp = C.c_void_p
+    lib.logos_host_logf.argtypes = [vp, C.c_int, vp]
+    lib.logos_host_acosf.argtypes = [vp, C.c_int, vp]
+    lib.logos_host_support.argtypes = [vp] * 8 + [C.c_longlong, vp, vp]
+    lib.logos_host_sort_head.argtypes = [vp, vp, C.c_long, C.c_long]
+    return lib
+
+
+def _ulps(a, b):
+    ia = a.view(np.int32).astype(np.int64)
+    ib = b.view(np.int32).astype(np.int64)
+    return np.abs(ia - ib)
+
+
+def test_elementary_functions_close_to_libm(host):
+    rng = np.random.default_rng(5)
+    x = np.concatenate([rng.uniform(1e-3, 1e4, 200000), np.float32([1.0, 2.0, 0.5, 3.4e38, 1e-40])]).astype(np.float32)
+    y = np.zeros_like(x)
+    host.logos_host_logf(x.ctypes.data, len(x), y.ctypes.data)
+    want = np.log(x.astype(np.float64)).astype(np.float32)
+    assert _ulps(y, want).max() <= 1
+    assert (_ulps(y, want) > 0).mean() < 1e-4
+    c = np.concatenate([rng.uniform(-1, 1, 200000), np.float32([-1.0, 1.0, 0.0, 0.5, -0.5])]).astype(np.float32)
+    y = np.zeros_like(c)
+    host.logos_host_acosf(c.ctypes.data, len(c), y.ctypes.data)
+    want = np.arccos(c.astype(np.float64)).astype(np.float32)
+    assert _ulps(y, want).max() <= 1
+    assert (_ulps(y, want) > 0).mean() < 1e-4
+    z = np.float32([0.0, -1.0])
+    y = np.zeros_like(z)
+    host.logos_host_logf(z.ctypes.data, 2, y.ctypes.data)
+    assert y[0] == -np.inf and np.isnan(y[1])
+
+
+@pytest.mark.parametrize("name", [n for n in NAMES if not n.startswith("empty")])
+def test_core_header_agrees_with_restatement(host, name):
+    kp1, kp2 = Z[name + "_kp1"].astype(np.float32), Z[name + "_kp2"].astype(np.float32)
+    l1, l2 = Z[name + "_nn1"].astype(np.int32), Z[name + "_nn2"].astype(np.int32)
+    P1, P2 = logos_ref.points(kp1, l1), logos_ref.points(kp2, l2)
+    nb1 = logos_ref.neighbours(P1[0], P1[1])
+    nb2 = logos_ref.neighbours(P2[0], P2[1])
+    ci, cj = logos_ref.candidates(l1, l2)
+    if len(ci) > 400000:
+        sel = np.random.default_rng(0).choice(len(ci), 400000, replace=False)
+        sel.sort()
+        ci, cj = ci[sel], cj[sel]
+    want, want_o = logos_ref.local_support(P1, P2, nb1, nb2, ci, cj)
+    got = np.zeros(len(ci), np.int32)
+    got_o = np.zeros(len(ci), np.float32)
+    ci64, cj64 = np.ascontiguousarray(ci, np.int64), np.ascontiguousarray(cj, np.int64)
+    host.logos_host_support(kp1.ctypes.data, l1.ctypes.data, nb1.ctypes.data, kp2.ctypes.data, l2.ctypes.data, nb2.ctypes.data,
+                            ci64.ctypes.data, cj64.ctypes.data, len(ci), got.ctypes.data, got_o.ctypes.data)
+    assert got_o.tobytes() == want_o.tobytes()
+    assert np.array_equal(got, want), f"{np.count_nonzero(got != want)} of {len(ci)} candidate supports differ"
+
+
+def test_neighbour_tie_rule_lower_index_first():
+    # four points at equal distance from the origin point: the lower indices are taken first
+    x = np.float32([0, 1, 0, -1, 0, 2, 2, 3])
+    y = np.float32([0, 0, 1, 0, -1, 2, -2, 3])
+    nb = logos_ref.neighbours(x, y)
+    assert list(nb[0]) == [1, 2, 3, 4, 5]
+
+
+def test_tiny_frames_use_the_neighbours_there_are():
+    nb = logos_ref.neighbours(np.float32([0, 1, 5]), np.float32([0, 0, 0]))
+    assert list(nb[0]) == [1, 2, -1, -1, -1]
+    assert list(logos_ref.neighbours(np.float32([3]), np.float32([4]))[0]) == [-1] * 5
+
+
+SORTS = sorted(int(k.split("_")[1]) for k in Z.files if k.startswith("sort_") and k.endswith("_order"))
+
+
+@pytest.mark.parametrize("t", SORTS)
+def test_sort_restatement_reproduces_dll_sort(host, t):
+    """The DLL's std::sort over (distance, index) records with many equal distances: the first five places (the only ones the
+    neighbour selection reads), and the first 32, by logos_ref and by the host build of logos_core.h."""
+    d, want = Z[f"sort_{t}_d"], Z[f"sort_{t}_order"]
+    n = len(d)
+    for k in (5, min(n, 32)):
+        dl, il = [float(v) for v in d], list(range(n))
+        logos_ref.msvc_sort_head(dl, il, k)
+        assert il[:k] == list(want[:k])
+        dc, ic = d.astype(np.float32).copy(), np.arange(n, dtype=np.int32)
+        host.logos_host_sort_head(dc.ctypes.data, ic.ctypes.data, n, k)
+        assert list(ic[:k]) == list(want[:k])
+    # above 32 records the order is not the stable one: this is what makes the tie rule matter
+    if n > 32:
+        assert list(want[:5]) != list(np.argsort(d, kind="stable")[:5])
+
+
+def test_tie_cases_are_not_resolved_by_lower_index():
+    """On the integer-coordinate cases the lower-index rule picks other neighbours than the DLL's sort for some points."""
+    kp = Z["int_rot0.3_n800_kp2"]
+    x, y = kp[:, 0], kp[:, 1]
+    nb = logos_ref.neighbours(x, y)
+    d = (x[:, None] - x[None, :]) ** 2 + (y[:, None] - y[None, :]) ** 2
+    np.fill_diagonal(d, np.inf)
+    stable = np.argsort(d, axis=1, kind="stable")[:, :5]
+    assert any(set(nb[i]) != set(stable[i]) for i in range(len(x)))
+
+
+def test_histogram_edges_and_tied_peak_are_covered():
+    peaks = {}
+    for name in ("rot_near_pi_n1000", "rot_near_mpi_n1000", "tied_peak_n400", "random_n300"):
+        _, (nc, ns, peak) = logos_ref.match(Z[name + "_kp1"], Z[name + "_kp2"], Z[name + "_nn1"], Z[name + "_nn2"], detail=True)
+        peaks[name] = peak
+    # every relOri in the last bin: the circular smoothing gives bins 0 and 188 the same sum, the first maximum (bin 0, centre
+    # near -pi) wins, and the global test does not wrap around, so nothing survives -- in the DLL as here
+    assert peaks["rot_near_pi_n1000"] == 0 and len(Z["rot_near_pi_n1000_matches"]) == 0
+    assert peaks["rot_near_mpi_n1000"] == 0 and len(Z["rot_near_mpi_n1000_matches"]) == 1000
+    assert peaks["random_n300"] == -1          # no candidate had support
+    # tied_peak: the two groups' smoothed maxima are equal; the first (lower) bin -- relOri -1.0, the second group -- wins and
+    # only that group survives
+    m = Z["tied_peak_n400_matches"]
+    assert len(m) == 200 and np.all(m[:, 0] >= 200)
