@@ -11,13 +11,20 @@ withScale=false, 6.0); the (true, true) flags of FeatureMatchUtil.cpp:69 are rep
 
   python bench.py --gpus N --steps K --warmup W         (N > 1 without a launcher: starts the N ranks itself)
   python bench.py ... --dump-outputs DIR                 (also writes what the last timed step computed: dump_outputs)
+  python bench.py ... --full                             (also everything beyond the headline; see below)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
+A plain run does what the headline needs and nothing more: it sets up, warms up, times the K steps, writes
+--dump-outputs, and prints the line (the headline with its roofline from the timed launches' own events).
+--full adds, after the timed steps and the dump: the parity check, the committed PMC traffic profile, opencv_on_box and,
+on one rank, the CPU baseline (unless --no-cpu) and the side records (unless --no-extra): rot_scale, real_pixels,
+config4, descriptors_to_filtered_matches, descriptors_to_poses, pixels_to_keypoints.
+
 Pairs are independent: no collective on the data path ("scaling": "weak": pairs per GPU per step are
 fixed). The rendezvous (barrier around the timed region, MAX of the ranks' times, SUM of the parity counts) runs over
-gloo on CPU tensors -- the path needs no RCCL. Every rank checks every 997th global pair it filtered against the CPU
-oracle, outside the timed region; a mismatch makes the run exit non-zero.
+gloo on CPU tensors -- the path needs no RCCL. With --full every rank checks every 997th global pair it filtered against
+the CPU oracle, outside the timed region; a mismatch makes the run exit non-zero.
 """
 import argparse
 import importlib
@@ -53,8 +60,10 @@ def parse():
     ap.add_argument("--cpu-oversubscribe", action="store_true", help="also time one thread per CPU of the affinity mask, beyond the cgroup's quota")
     ap.add_argument("--spatial-order", action="store_true",
                     help="diagnostic: keypoints listed cell by cell instead of in random order (LDS bank-conflict experiment, DESIGN.md 6)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg (profiling runs)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the rot+scale side measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the parity check, the CPU baseline and the side measurements (off: the headline only)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg (profiling runs)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the side measurements (rot_scale and the records after it)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
                          "(every pair's result record, the survivors of a fixed sample of its pairs; rank 0's shard)")
@@ -788,11 +797,12 @@ def main():
     if args.dump_outputs and rank == 0:  # before anything else launches on the chunks
         dumped = dump_outputs(wl, pkg, (args.warmup + args.steps - 1) % n_res, args.dump_outputs)
 
-    # ---- parity on every rank: the sampled pairs of every resident chunk, as the timed launches left them
-    checked, bad = check_parity(wl, pkg, range(n_res), False, False)
-    checked_all, bad_all = distmod.sum_over_ranks([checked, bad], dist)
-
-    ok = bad_all == 0
+    # ---- --full: parity on every rank, the sampled pairs of every resident chunk, as the timed launches left them
+    ok = True
+    if args.full:
+        checked, bad = check_parity(wl, pkg, range(n_res), False, False)
+        checked_all, bad_all = distmod.sum_over_ranks([checked, bad], dist)
+        ok = bad_all == 0
     if rank == 0:
         n_kp = wl.n_kp
         kept = 0
@@ -825,14 +835,15 @@ def main():
             "frame_table_build_ms": wl.frame_table_build_ms,
             "frame_table_note": f"gms_normalize_device over {args.frames} frames x {n_kp} keypoints (normalizePoints + per-keypoint cell codes), "
                                 "once per sequence, outside the timed steps: every frame serves frames - 1 pairs",
-            "parity": {"pairs_checked": checked_all, "mismatches": bad_all, "bit_exact": ok,
-                       "rule": f"every {distmod.PARITY_EVERY}th global pair of every resident chunk, on every rank, vs oracle/gms_ref.c"},
-            "opencv_on_box": opencv_on_box(),
         }
+        if args.full:
+            line["parity"] = {"pairs_checked": checked_all, "mismatches": bad_all, "bit_exact": ok,
+                              "rule": f"every {distmod.PARITY_EVERY}th global pair of every resident chunk, on every rank, vs oracle/gms_ref.c"}
+            line["opencv_on_box"] = opencv_on_box()
         if dumped is not None:
             line["dump_outputs"] = dumped
         tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tpath):  # measured in a separate rocprofv3 --pmc run (tools/pmc_collect.sh), not in this one
+        if args.full and os.path.exists(tpath):  # measured in a separate rocprofv3 --pmc run (tools/pmc_collect.sh), not in this one
             try:
                 tj = json.load(open(tpath))
                 line["roofline"]["traffic_from_profiles"] = tj
@@ -843,10 +854,10 @@ def main():
                                                           "(tools/pmc_collect.sh), FETCH_SIZE x2 per MI355X_MICROARCH.md, bytes per launch of this kernel")
             except Exception:
                 pass
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             line["cpu_baseline"] = cpu_baseline(args, wl, pkg, False, False, budget_s=12.0)
             line["gpu_vs_cpu"] = value / line["cpu_baseline"]["value"]
-        if not args.no_extra and world == 1:
+        if args.full and not args.no_extra and world == 1:
             # the reference's SfM call-site flags on the head of the same chunks
             n_sub = min(wl.n_pairs, 2048)
             w2, k2 = timed_steps(ctx, wl, stream, 8, 2, True, True, None, n_pairs=n_sub)

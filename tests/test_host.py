@@ -167,6 +167,15 @@ def test_bench_refuses_zero_timed_steps():
     assert res.returncode != 0 and "--steps" in res.stderr
 
 
+def test_bench_full_is_off_by_default(monkeypatch):
+    import importlib
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse().full is True
+
+
 def test_bench_dump_outputs_writes_what_the_step_returned(pkg, tmp_path):
     """bench.dump_outputs on a stand-in for a resident chunk (CPU tensors): every result record, the survivors of the seeded
     sample in order, float32 / float64 only, within 64 MB at 10k matches per pair, the same files from run to run."""

@@ -11,7 +11,7 @@ libs = sys.argv[1:3]
 extra = sys.argv[3:]
 code = """
 import importlib, sys
-sys.path.insert(0, {root!r}); sys.argv = ['bench.py', '--no-cpu', '--no-extra'] + {extra!r}
+sys.path.insert(0, {root!r}); sys.argv = ['bench.py', '--full', '--no-cpu', '--no-extra'] + {extra!r}
 capi = importlib.import_module('sfm-gms_amd.capi'); capi.library_path = lambda: {lib!r}
 import bench; bench.main()
 """

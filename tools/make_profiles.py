@@ -13,7 +13,7 @@ src = os.path.join(ROOT, "gpurun_out", "prof")
 dst = os.path.join(ROOT, "profiles")
 os.makedirs(dst, exist_ok=True)
 
-for name, what in (("trace", "python3 bench.py --no-cpu --no-extra  (only the headline launches)"), ("trace_full", "python3 bench.py  (all legs)")):
+for name, what in (("trace", "python3 bench.py --no-cpu --no-extra  (only the headline launches)"), ("trace_full", "python3 bench.py --full  (all legs)")):
     rows = list(csv.DictReader(open(os.path.join(src, f"kernel_stats_{name}.csv"))))
     suffix = "" if name == "trace" else "_full"
     with open(os.path.join(dst, f"{tag}_kernel_stats{suffix}.csv"), "w") as f:
