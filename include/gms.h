@@ -397,11 +397,51 @@ typedef struct gms_logos_result {
     int64_t n_supported;  /* candidates with local support                             */
     int64_t n_out;        /* survivors (the needed count on overflow)                  */
     int32_t peak_bin;     /* 0..188, -1 when no candidate had support                  */
-    int32_t status;       /* GMS_OK or GMS_ERR_CAPACITY                                */
+    int32_t status;       /* GMS_OK or GMS_ERR_CAPACITY (batched path also: _DOMAIN, _BAD_ARG) */
 } gms_logos_result;
 
 int gms_logos_match(const gms_keypoint* kp1, int n1, const gms_keypoint* kp2, int n2, const int32_t* nn1, const int32_t* nn2,
                     gms_dmatch* out, int64_t out_cap, int64_t* n_out, gms_logos_result* result);
+
+/* ---- LOGOS on resident frames (throughput API) ----------------------------------------------------------------
+ * The same filter for many pairs of resident frames, with everything per frame worked out once. Device pointers on the context's
+ * device, stream-ordered on the context's stream; these calls neither allocate nor synchronise nor read anything back, so they can
+ * be captured into a hipGraph. Every buffer comes from the caller, sized by the two *_bytes functions.
+ *
+ * gms_logos_prepare_device: the frame table d_table (gms_logos_table_bytes(total_kp, n_frames, n_words) bytes, 16-byte aligned,
+ *   opaque) for the keypoints d_kp of n_frames frames (d_frame_off: n_frames + 1 offsets) and one word per keypoint, d_words,
+ *   in [0, n_words): the LOGOS point of each keypoint, its five nearest neighbours in its frame (ties at the fifth place in the
+ *   order of the reference's sort, as gms_logos_match), and per frame its keypoints sorted by word (stable) with bucket offsets.
+ *   A word outside [0, n_words) marks its frame: pairs that touch it get GMS_ERR_DOMAIN. The workspace holds the slices of the tie
+ *   pass: with fewer than gms_logos_workspace_bytes(largest frame, 0, 0) bytes, a frame whose ties do not fit is marked and its
+ *   pairs get GMS_ERR_BAD_ARG.
+ * gms_logos_filter_device: n_pairs pairs of the table's frames. For a gms_pair here, m is the pair's OUTPUT CAPACITY and match_off
+ *   where its survivors start in d_out; ranges must be disjoint, as for gms_filter_device. Survivors are written as gms_logos_match
+ *   writes them, (i, j, -1, 0), i then j ascending, byte for byte the same. d_logos_results gets one record per pair (as
+ *   gms_logos_match reports it); when the survivors do not fit in m nothing of the pair is written, its status is GMS_ERR_CAPACITY and
+ *   n_out the count needed. A frame index out of range or m < 0: GMS_ERR_BAD_ARG. d_pair_results (optional, NULL allowed) gets
+ *   gms_pair_result records {n_inliers = survivors written, -1, -1, status}, so that gms_two_view_batch_device and
+ *   gms_disparity_batch_device take the output as it is. The workspace needs gms_logos_workspace_bytes(0, n_pairs, largest query
+ *   frame) bytes; pairs whose queries do not fit in it get GMS_ERR_BAD_ARG.
+ * gms_logos_workspace_bytes(max_frame_kp, n_pairs, max_query_kp): enough for both calls.
+ * gms_logos_words_device: the visual word of each of total_desc descriptor rows: the index of its EXACT nearest row of d_dict
+ *   (n_words rows, 1 <= n_words <= 65535; lowest index on ties), where the reference's FLANN lookup is approximate.
+ *     GMS_DESC_L2_F32X128  fp32 rows of 128; squared distance accumulated in fp32 in flann::L2's order: per group of four
+ *                          dimensions ((d0*d0 + d1*d1) + d2*d2) + d3*d3, groups added to the running sum in order, no FMA. A NaN
+ *                          distance counts as +inf.
+ *     GMS_DESC_HAMMING256  rows of 32 bytes; popcount of the xor.
+ * gms_logos_host_batch: prepare + filter on host arrays, synchronous (the C++ shim's batch form); pairs / out / results as for
+ *   gms_logos_filter_device, in host memory. */
+int64_t gms_logos_table_bytes(int64_t total_kp, int n_frames, int n_words);
+size_t  gms_logos_workspace_bytes(int64_t max_frame_kp, int n_pairs, int64_t max_query_kp);
+int gms_logos_prepare_device(gms_ctx* ctx, const gms_keypoint* d_kp, const int64_t* d_frame_off, int n_frames, int64_t total_kp,
+                             const int32_t* d_words, int n_words, void* d_workspace, size_t ws_bytes, void* d_table);
+int gms_logos_filter_device(gms_ctx* ctx, const void* d_table, const gms_pair* d_pairs, int n_pairs, void* d_workspace, size_t ws_bytes,
+                            gms_dmatch* d_out, gms_logos_result* d_logos_results, gms_pair_result* d_pair_results);
+int gms_logos_words_device(gms_ctx* ctx, int desc_kind, const void* d_desc, int64_t total_desc, const void* d_dict, int n_words,
+                           int32_t* d_words);
+int gms_logos_host_batch(gms_ctx* ctx, const gms_keypoint* kp, const int64_t* frame_off, int n_frames, const int32_t* words, int n_words,
+                         const gms_pair* pairs, int n_pairs, gms_dmatch* out, gms_logos_result* results);
 
 const char* gms_error_string(int code);
 const char* gms_version(void);

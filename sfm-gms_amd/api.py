@@ -244,6 +244,25 @@ class GmsContext:
         _check(self._lib.gms_describe_device(self._h, d_image, int(width), int(height), d_kp, int(n), d_ws, int(ws_bytes), d_desc, d_status),
                self._lib, "gms_describe_device")
 
+    # -- LOGOS on resident frames (gms_logos_*; batch.LogosTable / logos_pairs / logos_words drive them) ---------------------------
+    def logos_table_bytes(self, total_kp, n_frames, n_words):
+        return int(self._lib.gms_logos_table_bytes(int(total_kp), int(n_frames), int(n_words)))
+
+    def logos_workspace_bytes(self, max_frame_kp, n_pairs, max_query_kp):
+        return int(self._lib.gms_logos_workspace_bytes(int(max_frame_kp), int(n_pairs), int(max_query_kp)))
+
+    def logos_prepare_device(self, d_kp, d_frame_off, n_frames, total_kp, d_words, n_words, d_ws, ws_bytes, d_table):
+        _check(self._lib.gms_logos_prepare_device(self._h, d_kp or None, d_frame_off, int(n_frames), int(total_kp), d_words or None,
+                                                  int(n_words), d_ws or None, int(ws_bytes), d_table), self._lib, "gms_logos_prepare_device")
+
+    def logos_filter_device(self, d_table, d_pairs, n_pairs, d_ws, ws_bytes, d_out, d_logos_results, d_pair_results=None):
+        _check(self._lib.gms_logos_filter_device(self._h, d_table, d_pairs, int(n_pairs), d_ws, int(ws_bytes), d_out, d_logos_results,
+                                                 d_pair_results or None), self._lib, "gms_logos_filter_device")
+
+    def logos_words_device(self, desc_kind, d_desc, total_desc, d_dict, n_words, d_words):
+        _check(self._lib.gms_logos_words_device(self._h, int(desc_kind), d_desc or None, int(total_desc), d_dict, int(n_words),
+                                                d_words or None), self._lib, "gms_logos_words_device")
+
     def selftest_five_point(self, x1, x2):
         """gms_selftest_five_point: x1, x2 [n_samples, 5, 2] normalised points -> list of [k, 3, 3] model arrays, one per sample."""
         x1 = np.asarray(x1, dtype=np.float64).reshape(-1, 5, 2)

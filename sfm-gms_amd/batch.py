@@ -9,7 +9,8 @@ import numpy as np
 import torch
 
 from .api import GmsContext
-from .types import DMATCH_DTYPE, KEYPOINT_DTYPE, PAIR_DTYPE, RESULT_DTYPE
+from .types import (DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_ERR_CAPACITY, KEYPOINT_DTYPE, LOGOS_RESULT_DTYPE, PAIR_DTYPE,
+                    RESULT_DTYPE)
 
 
 def _to_dev(arr, device):
@@ -154,3 +155,148 @@ def filter_pairs(ctx, frames, pairs, matches, withRotation=False, withScale=Fals
     res = d_res.cpu().numpy().view(RESULT_DTYPE)[:n_pairs]
     mask = d_mask.cpu().numpy()[:total_m] if want_mask else None
     return out, res, mask
+
+
+# ---- LOGOS on resident frames (gms_logos_*) --------------------------------------------------------------------------
+class LogosTable:
+    """The per-frame LOGOS table of a sequence (gms_logos_prepare_device): points, five nearest neighbours and word buckets of every
+    frame, worked out once for all the pairs the frames are matched in.
+
+    keypoints_per_frame: a list of KEYPOINT_DTYPE arrays, or a FrameTable whose resident keypoints are used. words_per_frame: one word
+    per keypoint in [0, n_words) -- a list of per-frame int arrays, or an int32 device tensor of all keypoints back to back (as
+    gms_logos_words_device leaves it). A frame with a word out of range is marked: its pairs come back with GMS_ERR_DOMAIN."""
+
+    def __init__(self, ctx, keypoints_per_frame, words_per_frame, n_words, device="cuda:0"):
+        self.ctx, self.n_words = ctx, int(n_words)
+        if isinstance(keypoints_per_frame, FrameTable):
+            ft = keypoints_per_frame
+            self.device, self.n_frames, self.frame_off_host, self.total = ft.device, ft.n_frames, ft.frame_off_host, ft.total
+            self.d_kp, self.d_frame_off = ft.d_kp, ft.d_frame_off
+        else:
+            self.device = torch.device(device)
+            self.n_frames = len(keypoints_per_frame)
+            counts = np.array([len(k) for k in keypoints_per_frame], dtype=np.int64)
+            self.frame_off_host = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            self.total = int(self.frame_off_host[-1])
+            kp_all = (np.concatenate([np.ascontiguousarray(k, dtype=KEYPOINT_DTYPE) for k in keypoints_per_frame])
+                      if self.total else np.zeros(0, dtype=KEYPOINT_DTYPE))
+            self.d_kp = _to_dev(kp_all, self.device) if self.total else torch.zeros(28, dtype=torch.uint8, device=self.device)
+            self.d_frame_off = torch.from_numpy(self.frame_off_host).to(self.device)
+        self.counts = np.diff(self.frame_off_host)
+        if torch.is_tensor(words_per_frame):
+            self.d_words = words_per_frame.to(self.device, torch.int32).contiguous()
+        else:
+            w = (np.concatenate([np.asarray(x, dtype=np.int64).reshape(-1) for x in words_per_frame]) if len(words_per_frame)
+                 else np.zeros(0, np.int64))
+            if len(w) != self.total:
+                raise ValueError("one word per keypoint")
+            w = np.clip(w, -1, 2**31 - 1).astype(np.int32)   # (out of range stays out of range)
+            self.d_words = torch.from_numpy(w).to(self.device) if self.total else torch.zeros(1, dtype=torch.int32, device=self.device)
+        if self.d_words.numel() < self.total:
+            raise ValueError("one word per keypoint")
+        self.max_kp = int(self.counts.max()) if self.n_frames else 0
+        self.d_table = torch.zeros(max(ctx.logos_table_bytes(self.total, self.n_frames, self.n_words), 16), dtype=torch.uint8,
+                                   device=self.device)
+        ws = ctx.logos_workspace_bytes(self.max_kp, 0, 0)
+        d_ws = torch.empty(max(ws, 16), dtype=torch.uint8, device=self.device)
+        torch.cuda.synchronize(self.device)
+        ctx.logos_prepare_device(self.d_kp.data_ptr(), self.d_frame_off.data_ptr(), self.n_frames, self.total, self.d_words.data_ptr(),
+                                 self.n_words, d_ws.data_ptr(), ws, self.d_table.data_ptr())
+        ctx.synchronize()
+
+    def filter_device(self, d_pairs, n_pairs, d_ws, ws_bytes, d_out, d_logos_results, d_pair_results=None):
+        """gms_logos_filter_device on this table (stream-ordered; capturable)."""
+        self.ctx.logos_filter_device(self.d_table.data_ptr(), d_pairs, n_pairs, d_ws, ws_bytes, d_out, d_logos_results, d_pair_results)
+
+
+def logos_pair_table(table, frame_pairs, capacity=None):
+    """PAIR_DTYPE records for (frame_a, frame_b) pairs: m = the output capacity (default max(n_a, n_b) per pair -- survivors rarely
+    outnumber the larger frame), match_off back to back."""
+    fp = np.asarray(frame_pairs, dtype=np.int64).reshape(-1, 2)
+    pairs = np.zeros(len(fp), dtype=PAIR_DTYPE)
+    pairs["frame_a"], pairs["frame_b"] = fp[:, 0], fp[:, 1]
+    if capacity is None:
+        cap = np.zeros(len(fp), np.int64)
+        for k in (0, 1):
+            ok = (fp[:, k] >= 0) & (fp[:, k] < table.n_frames)
+            cap[ok] = np.maximum(cap[ok], table.counts[fp[ok, k]])
+    else:
+        cap = np.broadcast_to(np.asarray(capacity, dtype=np.int64), (len(fp),))
+    pairs["m"] = cap
+    pairs["match_off"] = np.concatenate([[0], np.cumsum(cap)[:-1]]) if len(fp) else 0
+    return pairs
+
+
+def logos_filter(ctx, table, pairs):
+    """One gms_logos_filter_device run over PAIR_DTYPE `pairs` -> (out, logos_results, pair_results) as host arrays (out laid out by
+    match_off; pairs with GMS_ERR_CAPACITY wrote nothing)."""
+    dev = table.device
+    pairs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
+    n = len(pairs)
+    if n == 0:
+        return np.zeros(0, DMATCH_DTYPE), np.zeros(0, LOGOS_RESULT_DTYPE), np.zeros(0, RESULT_DTYPE)
+    total = int((pairs["match_off"] + np.maximum(pairs["m"], 0)).max())
+    ok = (pairs["frame_a"] >= 0) & (pairs["frame_a"] < table.n_frames)
+    max_q = int(table.counts[pairs["frame_a"][ok]].max()) if ok.any() else 0
+    ws = ctx.logos_workspace_bytes(0, n, max_q)
+    d_pairs = _to_dev(pairs, dev)
+    d_ws = torch.empty(ws, dtype=torch.uint8, device=dev)
+    d_out = torch.zeros(max(total, 1) * 16, dtype=torch.uint8, device=dev)
+    d_lres = torch.zeros(n * LOGOS_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    d_pres = torch.zeros(n * RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+    table.filter_device(d_pairs.data_ptr(), n, d_ws.data_ptr(), ws, d_out.data_ptr(), d_lres.data_ptr(), d_pres.data_ptr())
+    ctx.synchronize()
+    return (d_out.cpu().numpy().view(DMATCH_DTYPE)[:total], d_lres.cpu().numpy().view(LOGOS_RESULT_DTYPE).copy(),
+            d_pres.cpu().numpy().view(RESULT_DTYPE).copy())
+
+
+def logos_pairs(ctx, table, pairs, capacity=None):
+    """The survivors of every (frame_a, frame_b) pair of `pairs` on a LogosTable: (list of DMATCH_DTYPE arrays, LOGOS_RESULT_DTYPE
+    records). capacity: output room per pair (int or one per pair; default max(n_a, n_b)). Pairs that come back with
+    GMS_ERR_CAPACITY are run once more with the count they reported, as matchLOGOS does for one pair."""
+    recs = logos_pair_table(table, pairs, capacity)
+    out, lres, _ = logos_filter(ctx, table, recs)
+    over = np.nonzero(lres["status"] == GMS_ERR_CAPACITY)[0]
+    where = {p: (out, int(recs["match_off"][p])) for p in range(len(recs))}
+    if len(over):
+        again = recs[over].copy()
+        again["m"] = lres["n_out"][over]
+        again["match_off"] = np.concatenate([[0], np.cumsum(again["m"])[:-1]])
+        out2, lres2, _ = logos_filter(ctx, table, again)
+        lres[over] = lres2
+        where.update({int(p): (out2, int(again["match_off"][q])) for q, p in enumerate(over)})
+    got = []
+    for p in range(len(recs)):
+        arr, o = where[p]
+        k = int(lres["n_out"][p]) if lres["status"][p] == 0 else 0
+        got.append(arr[o:o + k].copy())
+    return got, lres
+
+
+def logos_words(ctx, descriptors_per_frame, dictionary, kind, device=None):
+    """gms_logos_words_device: the exact nearest dictionary row (lowest index on ties) of every descriptor row -- in place of the
+    reference's FLANN lookup (FeatureMatchUtil.cpp:86-131). descriptors_per_frame: a list of per-frame row arrays (or one array);
+    kind GMS_DESC_L2_F32X128: float32 [n, 128] rows, GMS_DESC_HAMMING256: uint8 [n, 32]. Returns int32 words per frame."""
+    dev = torch.device(device if device is not None else f"cuda:{ctx.device}")
+    kind = int(kind)
+    dt, width = (np.uint8, 32) if kind == GMS_DESC_HAMMING256 else (np.float32, 128)
+    single = not isinstance(descriptors_per_frame, (list, tuple))
+    frames = [descriptors_per_frame] if single else list(descriptors_per_frame)
+    rows = [np.ascontiguousarray(d, dtype=dt).reshape(-1, width) for d in frames]
+    counts = [len(r) for r in rows]
+    total = int(sum(counts))
+    dic = np.ascontiguousarray(dictionary, dtype=dt).reshape(-1, width)
+    words = np.zeros(0, np.int32)
+    if total:
+        d_desc = torch.from_numpy(np.concatenate(rows).view(np.uint8).reshape(-1)).to(dev)
+        d_dict = torch.from_numpy(dic.view(np.uint8).reshape(-1).copy()).to(dev)
+        d_words = torch.zeros(total, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        ctx.logos_words_device(kind, d_desc.data_ptr(), total, d_dict.data_ptr(), len(dic), d_words.data_ptr())
+        ctx.synchronize()
+        words = d_words.cpu().numpy()
+    elif not 1 <= len(dic) <= 65535:
+        raise ValueError("1 <= dictionary rows <= 65535")
+    out = np.split(words, np.cumsum(counts)[:-1]) if counts else []
+    return out[0] if single else out

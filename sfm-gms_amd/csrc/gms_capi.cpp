@@ -20,6 +20,7 @@
 
 #include "gms.h"
 #include "gms_kernels.h"
+#include "logos_batch.h"
 #include "twoview_core.h"
 
 static_assert(sizeof(gms_keypoint) == 28, "gms_keypoint must match cv::KeyPoint (stride 0x1c)");
@@ -1275,6 +1276,115 @@ int gms_describe_device(gms_ctx* c, const uint8_t* d_image, int width, int heigh
     std::lock_guard<std::mutex> lock(c->mu);
     GMS_HIP(hipSetDevice(c->device));
     GMS_HIP(gms::launch_describe(d_image, width, height, d_keypoints, n, d_workspace, d_descriptors, d_status, c->stream));
+    return GMS_OK;
+}
+
+// ---- LOGOS on resident frames (logos_batch_kernels.hip) ----------------------------------------------------------------------
+int64_t gms_logos_table_bytes(int64_t total_kp, int n_frames, int n_words)
+{
+    if (total_kp < 0 || n_frames < 0 || n_words < 1 || n_words > 65535) return 0;
+    return gms::logos::table_layout(total_kp, n_frames, n_words).total;
+}
+
+size_t gms_logos_workspace_bytes(int64_t max_frame_kp, int n_pairs, int64_t max_query_kp)
+{
+    if (max_frame_kp < 0 || n_pairs < 0 || max_query_kp < 0) return 0;
+    return (size_t)gms::logos::workspace_bytes(max_frame_kp, n_pairs, max_query_kp);
+}
+
+int gms_logos_prepare_device(gms_ctx* c, const gms_keypoint* d_kp, const int64_t* d_frame_off, int n_frames, int64_t total_kp,
+                             const int32_t* d_words, int n_words, void* d_workspace, size_t ws_bytes, void* d_table)
+{
+    if (!c || n_frames < 0 || total_kp < 0 || n_words < 1 || n_words > 65535 || !d_table || !d_frame_off) return GMS_ERR_BAD_ARG;
+    if (total_kp > 0 && (!d_kp || !d_words)) return GMS_ERR_BAD_ARG;
+    if (ws_bytes > 0 && !d_workspace) return GMS_ERR_BAD_ARG;
+    if (total_kp > INT32_MAX || (reinterpret_cast<uintptr_t>(d_table) & 15u)) return GMS_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(c->mu);
+    GMS_HIP(hipSetDevice(c->device));
+    GMS_HIP(gms::launch_logos_prepare(d_kp, d_frame_off, n_frames, total_kp, d_words, n_words, d_workspace, ws_bytes, d_table, c->n_cus,
+                                      c->stream));
+    return GMS_OK;
+}
+
+int gms_logos_filter_device(gms_ctx* c, const void* d_table, const gms_pair* d_pairs, int n_pairs, void* d_workspace, size_t ws_bytes,
+                            gms_dmatch* d_out, gms_logos_result* d_logos_results, gms_pair_result* d_pair_results)
+{
+    if (!c || n_pairs < 0) return GMS_ERR_BAD_ARG;
+    if (n_pairs == 0) return GMS_OK;
+    if (!d_table || !d_pairs || !d_workspace || !d_out || !d_logos_results) return GMS_ERR_BAD_ARG;
+    if ((int64_t)ws_bytes < gms::logos::filter_fixed_bytes(n_pairs) || (reinterpret_cast<uintptr_t>(d_workspace) & 15u)) return GMS_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(c->mu);
+    GMS_HIP(hipSetDevice(c->device));
+    GMS_HIP(gms::launch_logos_filter(d_table, d_pairs, n_pairs, d_workspace, ws_bytes, d_out, d_logos_results, d_pair_results, c->n_cus,
+                                     c->stream));
+    return GMS_OK;
+}
+
+int gms_logos_words_device(gms_ctx* c, int desc_kind, const void* d_desc, int64_t total_desc, const void* d_dict, int n_words,
+                           int32_t* d_words)
+{
+    if (!c || total_desc < 0 || n_words < 1 || n_words > 65535 || !d_dict) return GMS_ERR_BAD_ARG;
+    if (desc_kind != GMS_DESC_L2_F32X128 && desc_kind != GMS_DESC_HAMMING256) return GMS_ERR_BAD_ARG;
+    if (total_desc == 0) return GMS_OK;
+    if (!d_desc || !d_words) return GMS_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(c->mu);
+    GMS_HIP(hipSetDevice(c->device));
+    GMS_HIP(gms::launch_logos_words(desc_kind, d_desc, total_desc, d_dict, n_words, d_words, c->n_cus, c->stream));
+    return GMS_OK;
+}
+
+int gms_logos_host_batch(gms_ctx* c, const gms_keypoint* kp, const int64_t* frame_off, int n_frames, const int32_t* words, int n_words,
+                         const gms_pair* pairs, int n_pairs, gms_dmatch* out, gms_logos_result* results)
+{
+    if (!c || n_frames < 0 || n_pairs < 0 || n_words < 1 || n_words > 65535 || !frame_off) return GMS_ERR_BAD_ARG;
+    if (n_pairs == 0) return GMS_OK;
+    if (!pairs || !results) return GMS_ERR_BAD_ARG;
+    const int64_t total_kp = frame_off[n_frames];
+    if (total_kp < 0 || total_kp > INT32_MAX || (total_kp > 0 && (!kp || !words))) return GMS_ERR_BAD_ARG;
+    int64_t max_kp = 0, max_q = 0, out_len = 0;
+    for (int f = 0; f < n_frames; f++) {
+        if (frame_off[f + 1] < frame_off[f]) return GMS_ERR_BAD_ARG;
+        max_kp = std::max(max_kp, frame_off[f + 1] - frame_off[f]);
+    }
+    for (int p = 0; p < n_pairs; p++) {
+        const gms_pair& q = pairs[p];
+        if (q.frame_a >= 0 && q.frame_a < n_frames) max_q = std::max(max_q, frame_off[q.frame_a + 1] - frame_off[q.frame_a]);
+        if (q.m > 0 && q.match_off >= 0) out_len = std::max(out_len, q.match_off + (int64_t)q.m);
+    }
+    if (out_len > 0 && !out) return GMS_ERR_BAD_ARG;
+    const size_t table = (size_t)gms_logos_table_bytes(total_kp, n_frames, n_words);
+    const size_t ws = gms_logos_workspace_bytes(max_kp, n_pairs, max_q);
+    std::lock_guard<std::mutex> lock(c->mu);
+    GMS_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    // one block: keypoints | offsets | words | pairs | results | table | workspace | out, each 256-byte aligned
+    const size_t a = 256;
+    auto up = [&](size_t x) { return (x + a - 1) / a * a; };
+    const size_t o_kp = 0, o_off = up(o_kp + sizeof(gms_keypoint) * (size_t)total_kp), o_w = up(o_off + 8 * ((size_t)n_frames + 1));
+    const size_t o_pairs = up(o_w + 4 * (size_t)total_kp), o_res = up(o_pairs + sizeof(gms_pair) * (size_t)n_pairs);
+    const size_t o_tab = up(o_res + sizeof(gms_logos_result) * (size_t)n_pairs), o_ws = up(o_tab + table);
+    const size_t o_out = up(o_ws + ws), bytes = o_out + sizeof(gms_dmatch) * (size_t)out_len + 16;
+    void* blk = nullptr;
+    GMS_HIP(hipMalloc(&blk, bytes));
+    char* d = static_cast<char*>(blk);
+    hipError_t e = hipSuccess;
+    if (total_kp > 0) e = hipMemcpyAsync(d + o_kp, kp, sizeof(gms_keypoint) * (size_t)total_kp, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_off, frame_off, 8 * ((size_t)n_frames + 1), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && total_kp > 0) e = hipMemcpyAsync(d + o_w, words, 4 * (size_t)total_kp, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_pairs, pairs, sizeof(gms_pair) * (size_t)n_pairs, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = gms::launch_logos_prepare(reinterpret_cast<const gms_keypoint*>(d + o_kp), reinterpret_cast<const int64_t*>(d + o_off), n_frames,
+                                      total_kp, reinterpret_cast<const int32_t*>(d + o_w), n_words, d + o_ws, ws, d + o_tab, c->n_cus, st);
+    if (e == hipSuccess)
+        e = gms::launch_logos_filter(d + o_tab, reinterpret_cast<const gms_pair*>(d + o_pairs), n_pairs, d + o_ws, ws,
+                                     reinterpret_cast<gms_dmatch*>(d + o_out), reinterpret_cast<gms_logos_result*>(d + o_res), nullptr,
+                                     c->n_cus, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(results, d + o_res, sizeof(gms_logos_result) * (size_t)n_pairs, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && out_len > 0) e = hipMemcpyAsync(out, d + o_out, sizeof(gms_dmatch) * (size_t)out_len, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    else (void)hipStreamSynchronize(st);
+    (void)hipFree(blk);
+    GMS_HIP(e);
     return GMS_OK;
 }
 

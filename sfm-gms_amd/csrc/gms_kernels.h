@@ -135,6 +135,13 @@ hipError_t launch_detect(const uint8_t* d_images, int n_images, int w, int h, in
                          gms_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, hipStream_t stream);
 hipError_t launch_describe(const uint8_t* d_image, int w, int h, gms_keypoint* d_kp, int n, void* d_ws, uint8_t* d_desc, int32_t* d_status,
                            hipStream_t stream);
+// batched LOGOS (logos_batch_kernels.hip; layouts in logos_batch.h)
+hipError_t launch_logos_prepare(const gms_keypoint* d_kp, const int64_t* d_frame_off, int n_frames, int64_t total_kp, const int32_t* d_words,
+                                int n_words, void* d_ws, size_t ws_bytes, void* d_table, int n_cus, hipStream_t stream);
+hipError_t launch_logos_filter(const void* d_table, const gms_pair* d_pairs, int n_pairs, void* d_ws, size_t ws_bytes, gms_dmatch* d_out,
+                               gms_logos_result* d_lres, gms_pair_result* d_pres, int n_cus, hipStream_t stream);
+hipError_t launch_logos_words(int kind, const void* d_desc, int64_t total, const void* d_dict, int n_words, int32_t* d_words, int n_cus,
+                              hipStream_t stream);
 hipError_t launch_threshold(const int32_t* d_T, const int32_t* d_n, const int32_t* d_score, double factor,
                             int count, uint8_t* d_out, hipStream_t stream);
 

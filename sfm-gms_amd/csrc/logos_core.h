@@ -154,6 +154,33 @@ GMS_HD bool consistent(const Pt& p, const Pt& q, float rel_o, float rel_s, const
     return kThresh > intra_o && kThresh > intra_s && kThresh > inter_o && kThresh > inter_s;
 }
 
+// The same verdict as consistent(), from the same operations on the same operands, but the cheap intra tests come first and the
+// logf / acosf of the inter tests are only evaluated while the verdict is still open (the batched path's support test).
+GMS_HD bool consistent_early(const Pt& p, const Pt& q, float rel_o, float rel_s, const Pt& a, const Pt& b)
+{
+    const float n_rel_o = rel_ori(a.ori, b.ori);
+    const float n_rel_s = a.logscale - b.logscale;
+    if (!(kThresh > fabsf(rel_s - n_rel_s))) return false;
+    if (!(kThresh > angle_dist(rel_o, n_rel_o))) return false;
+    const float dx1 = p.x - a.x, dy1 = p.y - a.y;
+    const float dx2 = q.x - b.x, dy2 = q.y - b.y;
+    const float s1a = dy1 * dy1, s1b = dx1 * dx1;
+    const float n1 = sqrtf(s1a + s1b);
+    const float s2a = dy2 * dy2, s2b = dx2 * dx2;
+    const float n2 = sqrtf(s2a + s2b);
+    const float lsc = logf_(n1) - logf_(n2);
+    if (!(kThresh > fabsf(rel_s - lsc))) return false;
+    const float c1 = dy2 * dx1, c2 = dy1 * dx2;
+    const float cross = c1 - c2;
+    const float d1 = dy2 * dy1, d2 = dx2 * dx1, nn = n2 * n1;
+    const float dot = (d1 + d2) / nn;
+    float c = -1.0f > dot ? -1.0f : dot;
+    if (c > 1.0f) c = 1.0f;
+    const float sign = (float)((cross > 0.0f ? 1 : 0) - (0.0f > cross ? 1 : 0));
+    const float ang = acosf_(c) * sign;
+    return kThresh > angle_dist(rel_o, ang);
+}
+
 // Logos::estimateMatches: histogram bin of a supported candidate's relOri (floor by truncation and correction; out of range ->
 // last bin, as the DLL's unsigned compare does)
 GMS_HD int bin_of(float rel_o)

@@ -3,7 +3,12 @@
 //   cv::xfeatures2d::matchGMS(const Size&, const Size&, const std::vector<KeyPoint>&, const std::vector<KeyPoint>&,
 //                             const std::vector<DMatch>&, std::vector<DMatch>&, bool = false, bool = false, double = 6.0)
 //
-// (reference call sites: SfM-GMS/SfM-GMS/FeatureMatchUtil.cpp:69, DisparityUtil.cpp:149, :299).
+// (reference call sites: SfM-GMS/SfM-GMS/FeatureMatchUtil.cpp:69, DisparityUtil.cpp:149, :299), and likewise
+//
+//   cv::xfeatures2d::matchLOGOS(const std::vector<KeyPoint>&, const std::vector<KeyPoint>&, const std::vector<int>&,
+//                               const std::vector<int>&, std::vector<DMatch>&)
+//
+// (FeatureMatchUtil.cpp:86-131).
 // With OpenCV headers present the cv:: types are used directly (cv::KeyPoint and cv::DMatch are
 // layout-identical to gms_keypoint / gms_dmatch); without them the same-shaped PODs below stand in, so the
 // call sites compile unchanged apart from the namespace. Link with libgms_hip.so.
@@ -122,6 +127,102 @@ inline void matchGMSBatch(const std::vector<Size>& sizes, const std::vector<std:
             continue;
         }
         matchesGMS[p].assign(out_all.begin() + prs[p].match_off, out_all.begin() + prs[p].match_off + res[p].n_inliers);
+    }
+}
+
+static_assert(sizeof(int) == sizeof(int32_t), "visual words travel as int32");
+
+// Same arguments, same output as the reference: matches1to2 is cleared, then receives the survivors (queryIdx, trainIdx, imgIdx -1,
+// distance 0), queryIdx ascending, then trainIdx. nn1 / nn2 hold the visual word of each keypoint. Throws where the reference has
+// undefined behaviour or no GPU is available; there is no CPU fallback.
+inline void matchLOGOS(const std::vector<KeyPoint>& keypoints1, const std::vector<KeyPoint>& keypoints2, const std::vector<int>& nn1,
+                       const std::vector<int>& nn2, std::vector<DMatch>& matches1to2)
+{
+    if (nn1.size() != keypoints1.size() || nn2.size() != keypoints2.size())
+        throw std::invalid_argument("mi355::matchLOGOS: one label per keypoint");
+    // survivors rarely outnumber the larger frame; on overflow the call reports the count it needs and runs once more with it
+    int64_t cap = (int64_t)std::max<size_t>(std::max(keypoints1.size(), keypoints2.size()), 1);
+    for (int attempt = 0;; ++attempt) {
+        std::vector<DMatch> out((size_t)cap);
+        int64_t n = 0;
+        const int rc = gms_logos_match(reinterpret_cast<const gms_keypoint*>(keypoints1.data()), (int)keypoints1.size(),
+                                       reinterpret_cast<const gms_keypoint*>(keypoints2.data()), (int)keypoints2.size(),
+                                       reinterpret_cast<const int32_t*>(nn1.data()), reinterpret_cast<const int32_t*>(nn2.data()),
+                                       reinterpret_cast<gms_dmatch*>(out.data()), cap, &n, nullptr);
+        if (rc == GMS_ERR_CAPACITY && attempt == 0 && n > cap) {
+            cap = n;
+            continue;
+        }
+        if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::matchLOGOS: ") + gms_error_string(rc));
+        out.resize((size_t)n);
+        matches1to2.swap(out);
+        return;
+    }
+}
+
+// The LOGOS filter for a whole sequence in one call, on a context (gms_logos_host_batch): keypoints[f] / words[f] describe frame f
+// (words in [0, n_words)), pair p filters frames pairs[p].first (query side) and pairs[p].second; matches1to2[p] receives what
+// matchLOGOS would. Each frame's neighbours and word buckets are worked out once for all its pairs. Pairs the library refuses (a word
+// out of range: GMS_ERR_DOMAIN) come back empty with ok[p] = false (if given).
+inline void matchLOGOSBatch(const std::vector<std::vector<KeyPoint>>& keypoints, const std::vector<std::vector<int>>& words, int n_words,
+                            const std::vector<std::pair<int, int>>& pairs, std::vector<std::vector<DMatch>>& matches1to2,
+                            std::vector<bool>* ok = nullptr)
+{
+    if (keypoints.size() != words.size()) throw std::invalid_argument("mi355::matchLOGOSBatch: one word list per frame");
+    static gms_ctx* ctx = nullptr;  // one context per process, created on first use
+    static int ctx_rc = GMS_OK;
+    static std::once_flag ctx_once;
+    std::call_once(ctx_once, [] { ctx_rc = gms_ctx_create(0, &ctx); });
+    if (ctx_rc != GMS_OK || !ctx) throw std::runtime_error(std::string("mi355::matchLOGOSBatch: ") + gms_error_string(ctx_rc));
+    const size_t nf = keypoints.size();
+    std::vector<int64_t> frame_off(nf + 1, 0);
+    for (size_t f = 0; f < nf; ++f) {
+        if (words[f].size() != keypoints[f].size()) throw std::invalid_argument("mi355::matchLOGOSBatch: one word per keypoint");
+        frame_off[f + 1] = frame_off[f] + (int64_t)keypoints[f].size();
+    }
+    std::vector<KeyPoint> kp_all((size_t)frame_off.back());
+    std::vector<int32_t> w_all((size_t)frame_off.back());
+    for (size_t f = 0; f < nf; ++f) {
+        std::copy(keypoints[f].begin(), keypoints[f].end(), kp_all.begin() + frame_off[f]);
+        std::copy(words[f].begin(), words[f].end(), w_all.begin() + frame_off[f]);
+    }
+    std::vector<int64_t> cap(pairs.size());
+    for (size_t p = 0; p < pairs.size(); ++p) {
+        const int a = pairs[p].first, b = pairs[p].second;
+        if (a < 0 || b < 0 || (size_t)a >= nf || (size_t)b >= nf) throw std::invalid_argument("mi355::matchLOGOSBatch: frame index");
+        cap[p] = std::max(keypoints[a].size(), keypoints[b].size());
+    }
+    std::vector<gms_pair> prs(pairs.size());
+    std::vector<gms_logos_result> res(pairs.size());
+    std::vector<DMatch> out_all;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        int64_t total = 0;
+        for (size_t p = 0; p < pairs.size(); ++p) {
+            prs[p] = gms_pair{pairs[p].first, pairs[p].second, (int32_t)cap[p], 0, total};
+            total += cap[p];
+        }
+        out_all.assign((size_t)total, DMatch());
+        const int rc = gms_logos_host_batch(ctx, reinterpret_cast<const gms_keypoint*>(kp_all.data()), frame_off.data(), (int)nf,
+                                            w_all.data(), n_words, prs.data(), (int)prs.size(),
+                                            reinterpret_cast<gms_dmatch*>(out_all.data()), res.data());
+        if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::matchLOGOSBatch: ") + gms_error_string(rc));
+        bool again = false;
+        for (size_t p = 0; p < pairs.size(); ++p)
+            if (res[p].status == GMS_ERR_CAPACITY) {
+                if (res[p].n_out > INT32_MAX) throw std::runtime_error("mi355::matchLOGOSBatch: too many survivors");
+                cap[p] = res[p].n_out;
+                again = true;
+            }
+        if (!again) break;
+    }
+    matches1to2.assign(pairs.size(), std::vector<DMatch>());
+    if (ok) ok->assign(pairs.size(), true);
+    for (size_t p = 0; p < pairs.size(); ++p) {
+        if (res[p].status != GMS_OK) {
+            if (ok) (*ok)[p] = false;
+            continue;
+        }
+        matches1to2[p].assign(out_all.begin() + prs[p].match_off, out_all.begin() + prs[p].match_off + res[p].n_out);
     }
 }
 

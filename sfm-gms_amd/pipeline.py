@@ -4,21 +4,33 @@
     descriptors --gms_bfmatch_device--> putative matches --gms_filter_device--> survivors
         --gms_two_view_batch_device--> essential matrix, pose, triangulated points, reprojection error   (with a camera)
 
+method="logos" runs the reference's SIFT_matchLOGOS flow instead (FeatureMatchUtil.cpp:86-131):
+
+    descriptors --gms_logos_words_device--> visual words --gms_logos_prepare_device / gms_logos_filter_device--> survivors
+        --gms_two_view_batch_device--> ...                                                                  (with a camera)
+
 torch here is device memory only; every stage is a call into csrc/libgms_hip.so. Used by tools/gms_filter_file.py and the tests."""
 import numpy as np
 import torch
 
-from .batch import DescriptorTable, FrameTable, _to_dev
-from .types import DMATCH_DTYPE, PAIR_DTYPE, RESULT_DTYPE, TWO_VIEW_DTYPE, make_camera
+from .batch import DescriptorTable, FrameTable, LogosTable, _to_dev
+from .types import (DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_ERR_CAPACITY, LOGOS_RESULT_DTYPE, PAIR_DTYPE, RESULT_DTYPE, TWO_VIEW_DTYPE,
+                    make_camera)
 
 
 def run_dataset(ctx, ds, withRotation=False, withScale=False, thresholdFactor=6.0, match=None, camera=None, dist=None, prob=0.7,
-                ransac_threshold=1.0, max_iters=1000, device="cuda:0"):
+                ransac_threshold=1.0, max_iters=1000, device="cuda:0", method="gms", dictionary=None, logos_capacity=None):
     """(prob, ransac_threshold: findEssentialMat's confidence and threshold as the flow this function restates passes them -- SfMUtil.cpp:39:
     RANSAC, 0.7, 1.0 -- not OpenCV's own default of 0.999, which gms_find_essential_batch_device's Python mirror keeps.)
     ds: io.Dataset. match=None: brute-force match when the file carries descriptors and no matches. camera = (fx, fy, cx, cy)
     switches the two-view stage on. Returns a dict of host arrays: pairs, matches (the putative ones), out, results, and with a camera
-    two_view (TWO_VIEW_DTYPE per pair), coords1, coords2, mask, points3d -- all per-match arrays laid out by match_off."""
+    two_view (TWO_VIEW_DTYPE per pair), coords1, coords2, mask, points3d -- all per-match arrays laid out by match_off.
+    method="logos": the LOGOS flow on the file's descriptors and pairs (frame_a, frame_b; their m / match_off are not used) with the
+    caller's `dictionary` (rows like the descriptors); see _run_logos."""
+    if method == "logos":
+        return _run_logos(ctx, ds, dictionary, logos_capacity, camera, dist, prob, ransac_threshold, max_iters, device)
+    if method != "gms":
+        raise ValueError(f"unknown method {method!r}")
     frames = FrameTable(ctx, ds.frames, ds.sizes, device=device)
     dev = frames.device
     pairs = np.ascontiguousarray(ds.pairs, dtype=PAIR_DTYPE).copy()
@@ -67,5 +79,83 @@ def run_dataset(ctx, ds, withRotation=False, withScale=False, thresholdFactor=6.
                    points3d=d_p3.cpu().numpy().reshape(-1, 3)[:total_m])
     ctx.synchronize()
     out.update(matches=d_matches.cpu().numpy().view(DMATCH_DTYPE)[:total_m], out=d_out.cpu().numpy().view(DMATCH_DTYPE)[:total_m],
+               results=d_res.cpu().numpy().view(RESULT_DTYPE)[:n_pairs])
+    return out
+
+
+def _run_logos(ctx, ds, dictionary, capacity, camera, dist, prob, ransac_threshold, max_iters, device):
+    """descriptors -> words (the exact nearest dictionary row) -> one LOGOS table for all frames -> every pair in one filter run ->
+    two-view with a camera. Pair p gets room for `capacity` survivors (default: the larger of its two frames); pairs that overflow
+    are reported with the count they need, and the batch is run once more with that room. Returns what run_dataset returns
+    (`matches` empty: LOGOS has no putative matches), plus words (per keypoint) and logos_results (LOGOS_RESULT_DTYPE per pair);
+    `results` are gms_pair_result records, `pairs` the table the survivors are laid out by."""
+    if ds.descriptors is None or dictionary is None:
+        raise ValueError("method='logos' needs the dataset's descriptors and a dictionary")
+    frames = FrameTable(ctx, ds.frames, ds.sizes, device=device)
+    dev = frames.device
+    kind = int(ds.desc_kind)
+    dt, width = (np.uint8, 32) if kind == GMS_DESC_HAMMING256 else (np.float32, 128)
+    dic = np.ascontiguousarray(dictionary, dtype=dt).reshape(-1, width)
+    total_kp = frames.total
+    d_words = torch.zeros(max(total_kp, 1), dtype=torch.int32, device=dev)
+    if total_kp:
+        desc = np.concatenate([np.ascontiguousarray(d, dtype=dt).reshape(-1, width) for d in ds.descriptors])
+        if len(desc) != total_kp:
+            raise ValueError("one descriptor per keypoint")
+        d_desc = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(dev)
+        d_dict = torch.from_numpy(dic.view(np.uint8).reshape(-1).copy()).to(dev)
+        torch.cuda.synchronize(dev)
+        ctx.logos_words_device(kind, d_desc.data_ptr(), total_kp, d_dict.data_ptr(), len(dic), d_words.data_ptr())
+    table = LogosTable(ctx, frames, d_words, len(dic))
+    src = np.ascontiguousarray(ds.pairs, dtype=PAIR_DTYPE)
+    n_pairs = len(src)
+    counts = np.diff(frames.frame_off_host)
+    # a frame index out of range is the library's to report (GMS_ERR_BAD_ARG for that pair alone): it counts as an empty frame here
+    def frame_kp(f):
+        f = np.asarray(f, np.int64)
+        ok = (f >= 0) & (f < len(counts))
+        return np.where(ok, counts[np.clip(f, 0, max(len(counts) - 1, 0))] if len(counts) else 0, 0).astype(np.int64)
+
+    n_a, n_b = frame_kp(src["frame_a"]), frame_kp(src["frame_b"])
+    cap = np.maximum(n_a, n_b) if capacity is None else np.full(n_pairs, int(capacity), np.int64)
+    max_q = int(n_a.max()) if n_pairs else 0
+    ws = ctx.logos_workspace_bytes(0, n_pairs, max_q)
+    d_ws = torch.empty(max(ws, 16), dtype=torch.uint8, device=dev)
+    d_lres = torch.zeros(max(n_pairs, 1) * LOGOS_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    d_res = torch.zeros(max(n_pairs, 1) * RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    for attempt in range(2):
+        pairs = src.copy()
+        pairs["m"] = cap
+        pairs["match_off"] = np.concatenate([[0], np.cumsum(cap)[:-1]]) if n_pairs else 0
+        total_m = int(cap.sum())
+        d_pairs = _to_dev(pairs, dev) if n_pairs else torch.zeros(24, dtype=torch.uint8, device=dev)
+        d_out = torch.zeros(max(total_m, 1) * 16, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        if n_pairs:
+            table.filter_device(d_pairs.data_ptr(), n_pairs, d_ws.data_ptr(), ws, d_out.data_ptr(), d_lres.data_ptr(), d_res.data_ptr())
+        ctx.synchronize()
+        lres = d_lres.cpu().numpy().view(LOGOS_RESULT_DTYPE)[:n_pairs].copy()
+        over = lres["status"] == GMS_ERR_CAPACITY
+        if attempt or not over.any():
+            break
+        cap = np.where(over, lres["n_out"], cap).astype(np.int64)   # room for what the overflowing pairs reported
+    out = dict(pairs=pairs, logos_results=lres, words=d_words.cpu().numpy()[:total_kp])
+    max_m = int(cap.max()) if n_pairs else 0
+    if camera is not None:
+        cam = make_camera(camera, dist)
+        d_c1 = torch.zeros(max(total_m, 1) * 2, dtype=torch.float32, device=dev)
+        d_c2 = torch.zeros(max(total_m, 1) * 2, dtype=torch.float32, device=dev)
+        d_mask = torch.zeros(max(total_m, 1), dtype=torch.uint8, device=dev)
+        d_p3 = torch.zeros(max(total_m, 1) * 3, dtype=torch.float64, device=dev)
+        d_tv = torch.zeros(max(n_pairs, 1) * TWO_VIEW_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        ctx.two_view_batch_device(cam, frames.d_kp.data_ptr(), frames.d_frame_off.data_ptr(), frames.n_frames, d_pairs.data_ptr(), n_pairs,
+                                  max_m, d_out.data_ptr(), d_res.data_ptr(), d_c1.data_ptr(), d_c2.data_ptr(), d_mask.data_ptr(),
+                                  d_p3.data_ptr(), d_tv.data_ptr(), prob, ransac_threshold, max_iters)
+        ctx.synchronize()
+        out.update(two_view=d_tv.cpu().numpy().view(TWO_VIEW_DTYPE)[:n_pairs], coords1=d_c1.cpu().numpy().reshape(-1, 2)[:total_m],
+                   coords2=d_c2.cpu().numpy().reshape(-1, 2)[:total_m], mask=d_mask.cpu().numpy()[:total_m],
+                   points3d=d_p3.cpu().numpy().reshape(-1, 3)[:total_m])
+    out.update(matches=np.zeros(0, DMATCH_DTYPE), out=d_out.cpu().numpy().view(DMATCH_DTYPE)[:total_m],
                results=d_res.cpu().numpy().view(RESULT_DTYPE)[:n_pairs])
     return out

@@ -1,0 +1,71 @@
+// tests/test_cpp_logos_shim.py: mi355::matchLOGOS and mi355::matchLOGOSBatch (sfm-gms_amd/include/mi355_gms.hpp) on the cases of
+// an input file, printing per case the survivors' count and an FNV-1a checksum of their bytes, single calls first, then the batch.
+// Input (little-endian): int32 n_cases, then per case int32 n1, n2, float x, y, size, angle per keypoint of frame 1 then frame 2,
+// int32 words of frame 1 then frame 2. No arguments: prints usage and exits 2 (the CPU test links this without a device).
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "mi355_gms.hpp"
+
+static unsigned long long fnv(const std::vector<mi355::DMatch>& m)
+{
+    unsigned long long s = 1469598103934665603ull;
+    std::vector<uint32_t> w(m.size() * 4);
+    if (!m.empty()) std::memcpy(w.data(), m.data(), w.size() * 4);
+    for (uint32_t v : w) s = (s ^ v) * 1099511628211ull;
+    return s;
+}
+
+int main(int argc, char** argv)
+{
+    if (argc < 2) {
+        std::fprintf(stderr, "usage: logos_shim_main CASES.bin\n");
+        return 2;
+    }
+    FILE* f = std::fopen(argv[1], "rb");
+    if (!f) return 2;
+    int32_t n_cases = 0;
+    if (std::fread(&n_cases, 4, 1, f) != 1) return 2;
+    std::vector<std::vector<mi355::KeyPoint>> kps;
+    std::vector<std::vector<int>> words;
+    for (int c = 0; c < 2 * n_cases; c += 2) {
+        int32_t n[2];
+        if (std::fread(n, 4, 2, f) != 2) return 2;
+        for (int k = 0; k < 2; ++k) {
+            std::vector<float> a((size_t)n[k] * 4);
+            if (n[k] && std::fread(a.data(), 4, a.size(), f) != a.size()) return 2;
+            std::vector<mi355::KeyPoint> kp((size_t)n[k]);
+            for (int i = 0; i < n[k]; ++i) {
+                kp[i].pt.x = a[4 * i];
+                kp[i].pt.y = a[4 * i + 1];
+                kp[i].size = a[4 * i + 2];
+                kp[i].angle = a[4 * i + 3];
+            }
+            kps.push_back(kp);
+        }
+        for (int k = 0; k < 2; ++k) {
+            std::vector<int> w((size_t)n[k]);
+            if (n[k] && std::fread(w.data(), 4, w.size(), f) != w.size()) return 2;
+            words.push_back(w);
+        }
+    }
+    std::fclose(f);
+    try {
+        std::vector<std::pair<int, int>> pairs;
+        for (int c = 0; c < n_cases; ++c) {
+            std::vector<mi355::DMatch> m;
+            mi355::matchLOGOS(kps[2 * c], kps[2 * c + 1], words[2 * c], words[2 * c + 1], m);
+            std::printf("%zu %llu\n", m.size(), fnv(m));
+            pairs.push_back({2 * c, 2 * c + 1});
+        }
+        std::vector<std::vector<mi355::DMatch>> out;
+        std::vector<bool> ok;
+        mi355::matchLOGOSBatch(kps, words, 50, pairs, out, &ok);
+        for (int c = 0; c < n_cases; ++c) std::printf("%zu %llu %d\n", out[c].size(), fnv(out[c]), ok[c] ? 1 : 0);
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        return 3;
+    }
+    return 0;
+}

@@ -3,10 +3,14 @@
 
     python tools/gms_filter_file.py seq.gmsf [--rot] [--scale] [--thr 6.0] [--match] [--camera fx fy cx cy] [--dist k1 k2 p1 p2 k3]
                                              [--prob 0.7] [--ransac-threshold 1.0] [--out result.npz]
+                                             [--logos DICT.npy [--logos-capacity N]]
 
 The file is read by the library's C reader (gms_dataset_read); with descriptors and no matches in it (or --match) the putative
 matches come from gms_bfmatch_device (FeatureMatchUtil.cpp:66-68), then gms_filter_device (matchGMS, FeatureMatchUtil.cpp:69), and
 with --camera the two-view stage of structureFromMotion (SfMUtil.cpp:25-82: findEssentialMat, recoverPose, undistort + triangulate).
+--logos DICT.npy runs the reference's SIFT_matchLOGOS flow instead (FeatureMatchUtil.cpp:86-131): the file's descriptors get their
+visual words from the dictionary (its rows like the descriptors: [k, 128] float32 or [k, 32] uint8), then LOGOS filters every pair of
+the file (gms_logos_filter_device), then the two-view stage as above.
 Prints one JSON line; --out keeps every array (numpy .npz)."""
 import argparse
 import importlib
@@ -32,18 +36,27 @@ def main():
     ap.add_argument("--prob", type=float, default=0.7, help="findEssentialMat's confidence (SfMUtil.cpp:39 passes 0.7)")
     ap.add_argument("--ransac-threshold", type=float, default=1.0)
     ap.add_argument("--out")
+    ap.add_argument("--logos", metavar="DICT.npy", help="LOGOS with this visual-word dictionary instead of GMS")
+    ap.add_argument("--logos-capacity", type=int, help="survivors per pair before a rerun (default: the larger frame)")
     a = ap.parse_args()
     pkg = importlib.import_module("sfm-gms_amd")
     io = importlib.import_module("sfm-gms_amd.io")
     pipeline = importlib.import_module("sfm-gms_amd.pipeline")
     ds = io.load_c(a.path)
     with pkg.GmsContext(0) as ctx:
-        r = pipeline.run_dataset(ctx, ds, a.rot, a.scale, a.thr, match=True if a.match else None, camera=a.camera, dist=a.dist,
-                                 prob=a.prob, ransac_threshold=a.ransac_threshold)
+        if a.logos:
+            r = pipeline.run_dataset(ctx, ds, camera=a.camera, dist=a.dist, prob=a.prob, ransac_threshold=a.ransac_threshold,
+                                     method="logos", dictionary=np.load(a.logos), logos_capacity=a.logos_capacity)
+        else:
+            r = pipeline.run_dataset(ctx, ds, a.rot, a.scale, a.thr, match=True if a.match else None, camera=a.camera, dist=a.dist,
+                                     prob=a.prob, ransac_threshold=a.ransac_threshold)
     res = r["results"]
     line = {"file": a.path, "frames": len(ds.frames), "pairs": len(res), "matches": int(r["pairs"]["m"].sum()),
             "kept": int(res["n_inliers"][res["status"] == 0].sum()), "failed_pairs": int((res["status"] != 0).sum()),
             "flags": [a.rot, a.scale, a.thr]}
+    if a.logos:
+        lr = r["logos_results"]
+        line.update(method="logos", matches=None, candidates=int(lr["n_candidates"].sum()), supported=int(lr["n_supported"].sum()))
     if "two_view" in r:
         tv = r["two_view"]
         ok = tv["status"] == 0
