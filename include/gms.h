@@ -213,6 +213,51 @@ int gms_bfmatch_device(gms_ctx* ctx, int desc_kind, const void* d_desc, const vo
                        const int64_t* d_frame_off, int n_frames, const gms_pair* d_pairs, int n_pairs, int max_query,
                        gms_dmatch* d_matches);
 
+/* ---- bruteForceMatch: cross-check, sort and ratio prune (FeatureMatchUtil.cpp:20-31) --------------------------
+ * What the reference's DEFAULT_SIFT method and its SIFT_matchBF baseline run:
+ *     BFMatcher(normType, crossCheck = true).match(desc1, desc2, matches); std::sort(matches);
+ *     while (front.distance * coef < back.distance) pop_back;  while (size > max_size) pop_back;     (coef 4.0, max_size 500)
+ * for n_pairs pairs of the resident descriptor table of gms_bfmatch_device (same d_desc / d_prepared / d_frame_off / desc_kind).
+ * Cross-check is OpenCV's one-sided rule, not a mutual-nearest test: every row i of frame_b takes its first nearest row tidx[i] of
+ * frame_a, and query row q keeps, among the i with tidx[i] == q, the one of smallest distance (lowest i on ties). The candidates,
+ * (q, t = that i, imgIdx = 0, distance) in ascending q, are sorted by distance in the order MSVC's std::sort leaves them (unstable;
+ * restated in bf_select_core.h) and the first K = min(max_size, #{d : !((double)d_min * coef < (double)d)}) are the survivors.
+ * cross_check = 0: the candidates are the plain forward matches of gms_bfmatch_device (the reference's match() helper, :38-50).
+ * imgIdx is 0 (the matcher's convention; OpenCV's split of trainIdx above 2^18 train rows is not reproduced).
+ *
+ * gms_bf_select_device: for a gms_pair here, m is the pair's OUTPUT CAPACITY and match_off where its survivors start in d_out (ranges
+ *   disjoint). max_rows bounds both frames of every pair (a pair with a larger frame gets GMS_ERR_BAD_ARG); the matcher's grid is
+ *   sized by it. d_bf_results gets one record per pair. K > m: nothing of the pair is written, status GMS_ERR_CAPACITY, n_out = K.
+ *   An empty frame: no survivors, GMS_ERR_DOMAIN (the reference calls front() on an empty vector). A frame index out of range,
+ *   m < 0, or more matcher rows than total_backward_rows over the pairs before it: GMS_ERR_BAD_ARG. d_pair_results (optional)
+ *   gets {n_inliers = survivors written, -1, -1, status} for gms_two_view_batch_device / gms_disparity_batch_device.
+ *   coef < 1 or not finite, max_size < 0, a bad kind or pointer, or too small a workspace: GMS_ERR_BAD_ARG for the call, nothing run.
+ *   Stream-ordered on the context's stream; no allocation, no synchronisation (graph-capturable).
+ * gms_bf_select_workspace_bytes(n_pairs, max_rows, total_backward_rows): the workspace (256-byte aligned pointer), where
+ *   total_backward_rows >= the sum over pairs of n(frame_b) with cross-check, of n(frame_a) without.
+ * gms_bf_match_select: the same for ONE pair on host rows (desc1: n1 query rows, desc2: n2 train rows), synchronous, on the current
+ *   HIP device; out_cap: room in out; *n_out: K, also when it exceeds out_cap (GMS_ERR_CAPACITY, nothing written). Byte-identical to
+ *   the batched call for that pair. result may be NULL. */
+typedef struct gms_bf_result {
+    int64_t n_candidates; /* cross-check survivors (forward matches without cross-check)         */
+    int64_t n_ratio;      /* candidates with !(d_min * coef < d)                                 */
+    int64_t n_out;        /* K = min(max_size, n_ratio): survivors (the needed count on overflow) */
+    float   d_min;        /* smallest candidate distance; 0 when there is none                   */
+    int32_t status;       /* GMS_OK, _DOMAIN, _CAPACITY or _BAD_ARG                               */
+} gms_bf_result;
+
+size_t gms_bf_select_workspace_bytes(int n_pairs, int max_rows, int64_t total_backward_rows);
+int gms_bf_select_device(gms_ctx* ctx, int desc_kind, const void* d_desc, const void* d_prepared, int64_t total_desc,
+                         const int64_t* d_frame_off, int n_frames, const gms_pair* d_pairs, int n_pairs, int max_rows, int cross_check,
+                         double distance_coef, int max_size, void* d_ws, size_t ws_bytes, gms_dmatch* d_out, gms_bf_result* d_bf_results,
+                         gms_pair_result* d_pair_results);
+int gms_bf_match_select(int desc_kind, const void* desc1, int n1, const void* desc2, int n2, int cross_check, double distance_coef,
+                        int max_size, gms_dmatch* out, int64_t out_cap, int64_t* n_out, gms_bf_result* result);
+/* gms_bf_select_host_batch: prepare + select on host arrays, synchronous (the C++ shim's batch form): desc holds frame_off[n_frames]
+ * rows; pairs / out / results as for gms_bf_select_device, in host memory. */
+int gms_bf_select_host_batch(gms_ctx* ctx, int desc_kind, const void* desc, const int64_t* frame_off, int n_frames, const gms_pair* pairs,
+                             int n_pairs, int cross_check, double distance_coef, int max_size, gms_dmatch* out, gms_bf_result* results);
+
 /* ---- consumers of the filtered matches --------------------------------------------------------------------
  * Both read the survivors of ONE pair where gms_filter_device left them (d_matches = d_out + match_off, *d_n_matches =
  * d_results[i].n_inliers, max_matches >= that count, e.g. the pair's m) and the two frames' ORIGINAL keypoints (pixel

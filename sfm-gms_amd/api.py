@@ -12,7 +12,8 @@ import ctypes as C
 import numpy as np
 
 from .capi import load_library
-from .types import (DMATCH_DTYPE, KEYPOINT_DTYPE, PAIR_DTYPE, RESULT_DTYPE, GMS_OK, GMS_ERR_CAPACITY, GmsError)
+from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_DESC_HAMMING256, KEYPOINT_DTYPE, PAIR_DTYPE, RESULT_DTYPE, GMS_OK, GMS_ERR_CAPACITY,
+                    GmsError)
 
 
 def _as(arr, dtype, name):
@@ -166,6 +167,17 @@ class GmsContext:
         _check(self._lib.gms_bfmatch_device(self._h, int(desc_kind), d_desc, d_prepared or None, int(total_desc), d_frame_off,
                                             int(n_frames), d_pairs, int(n_pairs), int(max_query), d_matches),
                self._lib, "gms_bfmatch_device")
+
+    # -- bruteForceMatch: cross-check, sort and ratio prune behind the matcher (FeatureMatchUtil.cpp:20-31) ----------------
+    def bf_select_workspace_bytes(self, n_pairs, max_rows, total_backward_rows):
+        return int(self._lib.gms_bf_select_workspace_bytes(int(n_pairs), int(max_rows), int(total_backward_rows)))
+
+    def bf_select_device(self, desc_kind, d_desc, d_prepared, total_desc, d_frame_off, n_frames, d_pairs, n_pairs, max_rows, cross_check,
+                         distance_coef, max_size, d_ws, ws_bytes, d_out, d_bf_results, d_pair_results=None):
+        _check(self._lib.gms_bf_select_device(self._h, int(desc_kind), d_desc or None, d_prepared or None, int(total_desc), d_frame_off,
+                                              int(n_frames), d_pairs, int(n_pairs), int(max_rows), int(bool(cross_check)),
+                                              float(distance_coef), int(max_size), d_ws, int(ws_bytes), d_out, d_bf_results,
+                                              d_pair_results or None), self._lib, "gms_bf_select_device")
 
     # -- consumers of the filtered matches (DisparityUtil.cpp:179-201, SfMUtil.cpp:25-35) -------------------------------
     def disparity_device(self, d_kp1, n1, d_kp2, n2, d_matches, d_n_matches, max_matches, width, height, d_gt, disp_ratio,
@@ -323,3 +335,28 @@ def matchLOGOS(keypoints1, keypoints2, nn1, nn2):
             continue
         _check(rc, lib, "gms_logos_match")
         return out[: n.value].copy()
+
+
+def bruteForceMatch(desc1, desc2, kind, cross_check=True, distance_coef=4.0, max_size=500, detail=False):
+    """The reference's bruteForceMatch (FeatureMatchUtil.cpp:20-31) on the GPU: BFMatcher(norm, crossCheck).match(desc1, desc2),
+    std::sort by distance (MSVC's order among equal distances), then the survivors within distance_coef * d_min, at most max_size.
+
+    desc1 / desc2: query / train rows -- uint8 [n, 32] for GMS_DESC_HAMMING256, float32 [n, 128] for GMS_DESC_L2_F32X128.
+    cross_check=False: the reference's match() helper (no cross-check, same sort and prune). Returns DMATCH_DTYPE records
+    (queryIdx, trainIdx, imgIdx 0, distance); with detail=True also the BF_RESULT_DTYPE record. An empty frame raises GmsError
+    (GMS_ERR_DOMAIN): the reference reads front() of an empty vector there."""
+    lib = load_library()
+    kind = int(kind)
+    dt, width = (np.uint8, 32) if kind == GMS_DESC_HAMMING256 else (np.float32, 128)
+    d1 = np.ascontiguousarray(desc1, dtype=dt).reshape(-1, width)
+    d2 = np.ascontiguousarray(desc2, dtype=dt).reshape(-1, width)
+    cap = min(int(max_size), len(d1)) if max_size >= 0 else 0
+    out = np.zeros(max(cap, 1), DMATCH_DTYPE)
+    n = C.c_int64(0)
+    res = np.zeros(1, BF_RESULT_DTYPE)
+    rc = lib.gms_bf_match_select(kind, d1.ctypes.data if len(d1) else None, len(d1), d2.ctypes.data if len(d2) else None, len(d2),
+                                 int(bool(cross_check)), float(distance_coef), int(max_size), out.ctypes.data, cap, C.byref(n),
+                                 res.ctypes.data)
+    _check(rc, lib, "gms_bf_match_select")
+    got = out[: n.value].copy()
+    return (got, res[0]) if detail else got

@@ -9,8 +9,8 @@ import numpy as np
 import torch
 
 from .api import GmsContext
-from .types import (DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_ERR_CAPACITY, KEYPOINT_DTYPE, LOGOS_RESULT_DTYPE, PAIR_DTYPE,
-                    RESULT_DTYPE)
+from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_ERR_CAPACITY, KEYPOINT_DTYPE, LOGOS_RESULT_DTYPE,
+                    PAIR_DTYPE, RESULT_DTYPE)
 
 
 def _to_dev(arr, device):
@@ -69,6 +69,94 @@ class DescriptorTable:
         f = self.frames
         self.ctx.bfmatch_device(self.kind, self.d_desc.data_ptr(), self.d_prep.data_ptr() if use_prepared else None, f.total,
                                 f.d_frame_off.data_ptr(), f.n_frames, d_pairs, n_pairs, max_query, d_matches)
+
+
+class BfSelect:
+    """Device buffers of one gms_bf_select_device batch over a DescriptorTable: the pair table, workspace, output and result
+    records, sized once, so that run() can be replayed (or captured into a graph) on the same pairs."""
+
+    def __init__(self, ctx, descs, recs, cross_check=True, distance_coef=4.0, max_size=500, use_prepared=True):
+        f = descs.frames
+        self.ctx, self.descs, self.recs = ctx, descs, np.ascontiguousarray(recs, dtype=PAIR_DTYPE)
+        self.cross_check, self.distance_coef, self.max_size, self.use_prepared = bool(cross_check), float(distance_coef), int(max_size), use_prepared
+        sizes = np.diff(f.frame_off_host)
+        a, b = self.recs["frame_a"], self.recs["frame_b"]
+        ok = (a >= 0) & (a < f.n_frames) & (b >= 0) & (b < f.n_frames)
+        na, nb = np.where(ok, sizes[np.clip(a, 0, max(f.n_frames - 1, 0))] if f.n_frames else 0, 0), \
+            np.where(ok, sizes[np.clip(b, 0, max(f.n_frames - 1, 0))] if f.n_frames else 0, 0)
+        self.max_rows = int(max(na.max(initial=0), nb.max(initial=0)))
+        self.total_back = int((nb if self.cross_check else na).sum())
+        n = len(self.recs)
+        dev = f.device
+        self.ws_bytes = ctx.bf_select_workspace_bytes(n, self.max_rows, self.total_back)
+        self.d_ws = torch.zeros(max(self.ws_bytes, 256), dtype=torch.uint8, device=dev)
+        self.d_pairs = _to_dev(self.recs, dev) if n else torch.zeros(24, dtype=torch.uint8, device=dev)
+        total = int((self.recs["match_off"] + np.maximum(self.recs["m"], 0)).max()) if n else 0
+        self.out_len = total
+        self.d_out = torch.zeros(max(total, 1) * 16, dtype=torch.uint8, device=dev)
+        self.d_res = torch.zeros(max(n, 1) * 32, dtype=torch.uint8, device=dev)
+        self.d_pres = torch.zeros(max(n, 1) * 16, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+
+    def run(self):
+        f, d = self.descs.frames, self.descs
+        self.ctx.bf_select_device(d.kind, d.d_desc.data_ptr(), d.d_prep.data_ptr() if self.use_prepared else None, f.total,
+                                  f.d_frame_off.data_ptr(), f.n_frames, self.d_pairs.data_ptr(), len(self.recs), self.max_rows,
+                                  self.cross_check, self.distance_coef, self.max_size, self.d_ws.data_ptr(), self.ws_bytes,
+                                  self.d_out.data_ptr(), self.d_res.data_ptr(), self.d_pres.data_ptr())
+
+    def results(self):
+        """(output DMATCH_DTYPE array laid out by match_off, BF_RESULT_DTYPE records, RESULT_DTYPE records) on the host."""
+        n = len(self.recs)
+        out = self.d_out.cpu().numpy().view(DMATCH_DTYPE)[: self.out_len].copy()
+        return out, self.d_res.cpu().numpy().view(BF_RESULT_DTYPE)[:n].copy(), self.d_pres.cpu().numpy().view(RESULT_DTYPE)[:n].copy()
+
+
+def bf_select_table(descs, frame_pairs, capacity=None, max_size=500):
+    """PAIR_DTYPE records for (frame_a, frame_b) pairs; m: output room per pair (int or one per pair; default min(max_size, n_a),
+    which K never exceeds), match_off: the running sum."""
+    fp = np.asarray(frame_pairs, dtype=np.int64).reshape(-1, 2)
+    sizes = np.diff(descs.frames.frame_off_host)
+    recs = np.zeros(len(fp), PAIR_DTYPE)
+    recs["frame_a"], recs["frame_b"] = fp[:, 0], fp[:, 1]
+    if capacity is None:
+        ok = (fp[:, 0] >= 0) & (fp[:, 0] < len(sizes))
+        na = np.where(ok, sizes[np.clip(fp[:, 0], 0, max(len(sizes) - 1, 0))] if len(sizes) else 0, 0)
+        cap = np.minimum(na, max(int(max_size), 0))
+    else:
+        cap = np.broadcast_to(np.asarray(capacity, dtype=np.int64), (len(fp),))
+    recs["m"] = cap
+    recs["match_off"] = np.concatenate([[0], np.cumsum(np.maximum(cap, 0))[:-1]]) if len(fp) else []
+    return recs
+
+
+def bf_select_pairs(ctx, descs, frame_pairs, cross_check=True, distance_coef=4.0, max_size=500, capacity=None, use_prepared=True):
+    """The reference's bruteForceMatch (FeatureMatchUtil.cpp:20-31) for every (frame_a, frame_b) pair of a DescriptorTable: (list of
+    DMATCH_DTYPE survivor arrays, BF_RESULT_DTYPE records). Pairs that come back with GMS_ERR_CAPACITY are run once more with the
+    count they reported."""
+    recs = bf_select_table(descs, frame_pairs, capacity, max_size)
+    run = BfSelect(ctx, descs, recs, cross_check, distance_coef, max_size, use_prepared)
+    run.run()
+    ctx.synchronize()
+    out, res, _ = run.results()
+    over = np.nonzero(res["status"] == GMS_ERR_CAPACITY)[0]
+    where = {p: (out, int(recs["match_off"][p])) for p in range(len(recs))}
+    if len(over):
+        again = recs[over].copy()
+        again["m"] = res["n_out"][over]
+        again["match_off"] = np.concatenate([[0], np.cumsum(again["m"])[:-1]])
+        run2 = BfSelect(ctx, descs, again, cross_check, distance_coef, max_size, use_prepared)
+        run2.run()
+        ctx.synchronize()
+        out2, res2, _ = run2.results()
+        res[over] = res2
+        where.update({int(p): (out2, int(again["match_off"][q])) for q, p in enumerate(over)})
+    got = []
+    for p in range(len(recs)):
+        arr, o = where[p]
+        k = int(res["n_out"][p]) if res["status"][p] == 0 else 0
+        got.append(arr[o:o + k].copy())
+    return got, res
 
 
 def detect_images(ctx, images, threshold=20, max_keypoints=10000, device=None):

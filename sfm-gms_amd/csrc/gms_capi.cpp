@@ -1094,6 +1094,147 @@ int gms_bfmatch_device(gms_ctx* c, int desc_kind, const void* d_desc, const void
     return GMS_OK;
 }
 
+size_t gms_bf_select_workspace_bytes(int n_pairs, int max_rows, int64_t total_backward_rows)
+{
+    if (n_pairs < 0 || max_rows < 0 || max_rows > (1 << 22) || total_backward_rows < 0) return 0;
+    return gms::bf_select_ws_bytes(n_pairs, max_rows, total_backward_rows);
+}
+
+static bool bf_select_args_ok(int desc_kind, int cross_check, double coef, int max_size)
+{
+    return (desc_kind == GMS_DESC_HAMMING256 || desc_kind == GMS_DESC_L2_F32X128) && (cross_check == 0 || cross_check == 1) &&
+           std::isfinite(coef) && coef >= 1.0 && max_size >= 0;
+}
+
+int gms_bf_select_device(gms_ctx* c, int desc_kind, const void* d_desc, const void* d_prepared, int64_t total_desc,
+                         const int64_t* d_frame_off, int n_frames, const gms_pair* d_pairs, int n_pairs, int max_rows, int cross_check,
+                         double distance_coef, int max_size, void* d_ws, size_t ws_bytes, gms_dmatch* d_out, gms_bf_result* d_bf_results,
+                         gms_pair_result* d_pair_results)
+{
+    if (!c || n_frames < 0 || n_pairs < 0 || max_rows < 0 || max_rows > (1 << 22) || total_desc < 0) return GMS_ERR_BAD_ARG;
+    if (!bf_select_args_ok(desc_kind, cross_check, distance_coef, max_size)) return GMS_ERR_BAD_ARG;
+    if (n_pairs == 0) return GMS_OK;
+    if (!d_frame_off || !d_pairs || !d_ws || !d_out || !d_bf_results || (total_desc > 0 && !d_desc)) return GMS_ERR_BAD_ARG;
+    if (desc_kind == GMS_DESC_L2_F32X128 && total_desc > 0 && !d_prepared) return GMS_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(d_ws) & 255u) return GMS_ERR_BAD_ARG;
+    // the workspace's size fixes how many matcher rows it holds (total_backward_rows of gms_bf_select_workspace_bytes)
+    const size_t fixed = gms::bf_select_ws_bytes(n_pairs, max_rows, 0);
+    if (ws_bytes < fixed) return GMS_ERR_BAD_ARG;
+    const int64_t total_back = (int64_t)((ws_bytes - fixed) / 256) * 16;  // whole 256-byte blocks, as the layout aligns them
+    std::lock_guard<std::mutex> lock(c->mu);
+    GMS_HIP(hipSetDevice(c->device));
+    GMS_HIP(gms::launch_bf_select(desc_kind, d_desc, d_prepared, total_desc, d_frame_off, n_frames, d_pairs, n_pairs, max_rows, total_back,
+                                  cross_check, distance_coef, max_size, d_ws, d_out, d_bf_results, d_pair_results, c->stream));
+    return GMS_OK;
+}
+
+int gms_bf_match_select(int desc_kind, const void* desc1, int n1, const void* desc2, int n2, int cross_check, double distance_coef,
+                        int max_size, gms_dmatch* out, int64_t out_cap, int64_t* n_out, gms_bf_result* result)
+{
+    if (n_out) *n_out = 0;
+    if (result) *result = gms_bf_result{0, 0, 0, 0.0f, GMS_OK};
+    if (n1 < 0 || n2 < 0 || n1 > (1 << 22) || n2 > (1 << 22) || out_cap < 0 || out_cap > INT32_MAX || !n_out) return GMS_ERR_BAD_ARG;
+    if (!bf_select_args_ok(desc_kind, cross_check, distance_coef, max_size)) return GMS_ERR_BAD_ARG;
+    if ((n1 > 0 && !desc1) || (n2 > 0 && !desc2) || (out_cap > 0 && !out)) return GMS_ERR_BAD_ARG;
+    const size_t row = desc_kind == GMS_DESC_HAMMING256 ? 32 : 512;
+    const int64_t total = (int64_t)n1 + n2;
+    const int max_rows = std::max(n1, n2);
+    const int64_t back_rows = cross_check ? n2 : n1;
+    const size_t a = 256;
+    auto up = [&](size_t x) { return (x + a - 1) / a * a; };
+    const size_t prep = (size_t)gms::bf_prepared_bytes(desc_kind, total, 2);
+    const size_t ws = gms::bf_select_ws_bytes(1, max_rows, back_rows);
+    // one block: rows | frame offsets | pair | result | prepared tables | workspace | out
+    const size_t o_desc = 0, o_off = up(row * (size_t)total + 16), o_pair = up(o_off + 3 * 8), o_res = up(o_pair + sizeof(gms_pair));
+    const size_t o_prep = up(o_res + sizeof(gms_bf_result)), o_ws = up(o_prep + prep + 16), o_out = up(o_ws + ws);
+    const size_t bytes = o_out + sizeof(gms_dmatch) * (size_t)out_cap + 16;
+    void* blk = nullptr;
+    GMS_HIP(hipMalloc(&blk, bytes));
+    char* d = static_cast<char*>(blk);
+    const int64_t off[3] = {0, n1, total};
+    const gms_pair pr{0, 1, (int32_t)out_cap, 0, 0};
+    hipStream_t st = nullptr;
+    hipError_t e = hipSuccess;
+    if (n1 > 0) e = hipMemcpyAsync(d + o_desc, desc1, row * (size_t)n1, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && n2 > 0) e = hipMemcpyAsync(d + o_desc + row * (size_t)n1, desc2, row * (size_t)n2, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_off, off, sizeof(off), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_pair, &pr, sizeof(pr), hipMemcpyHostToDevice, st);
+    const int64_t* d_off = reinterpret_cast<const int64_t*>(d + o_off);
+    if (e == hipSuccess && total > 0) e = gms::launch_bf_prepare(desc_kind, d + o_desc, d_off, 2, total, d + o_prep, st);
+    if (e == hipSuccess)
+        e = gms::launch_bf_select(desc_kind, d + o_desc, d + o_prep, total, d_off, 2, reinterpret_cast<const gms_pair*>(d + o_pair), 1,
+                                  max_rows, back_rows, cross_check, distance_coef, max_size, d + o_ws, reinterpret_cast<gms_dmatch*>(d + o_out),
+                                  reinterpret_cast<gms_bf_result*>(d + o_res), nullptr, st);
+    gms_bf_result r{0, 0, 0, 0.0f, GMS_OK};
+    if (e == hipSuccess) e = hipMemcpyAsync(&r, d + o_res, sizeof(r), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && r.status == GMS_OK && r.n_out > 0)
+        e = hipMemcpy(out, d + o_out, sizeof(gms_dmatch) * (size_t)r.n_out, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) (void)hipStreamSynchronize(st);
+    (void)hipFree(blk);
+    GMS_HIP(e);
+    *n_out = r.n_out;
+    if (result) *result = r;
+    return r.status;
+}
+
+int gms_bf_select_host_batch(gms_ctx* c, int desc_kind, const void* desc, const int64_t* frame_off, int n_frames, const gms_pair* pairs,
+                             int n_pairs, int cross_check, double distance_coef, int max_size, gms_dmatch* out, gms_bf_result* results)
+{
+    if (!c || n_frames < 0 || n_pairs < 0 || !frame_off) return GMS_ERR_BAD_ARG;
+    if (!bf_select_args_ok(desc_kind, cross_check, distance_coef, max_size)) return GMS_ERR_BAD_ARG;
+    if (n_pairs == 0) return GMS_OK;
+    if (!pairs || !results) return GMS_ERR_BAD_ARG;
+    const int64_t total = frame_off[n_frames];
+    if (total < 0 || (total > 0 && !desc)) return GMS_ERR_BAD_ARG;
+    int64_t max_rows = 0, back = 0, out_len = 0;
+    for (int f = 0; f < n_frames; f++) {
+        if (frame_off[f + 1] < frame_off[f]) return GMS_ERR_BAD_ARG;
+    }
+    for (int p = 0; p < n_pairs; p++) {
+        const gms_pair& q = pairs[p];
+        if (q.frame_a < 0 || q.frame_a >= n_frames || q.frame_b < 0 || q.frame_b >= n_frames) continue;  // reported per pair
+        const int64_t na = frame_off[q.frame_a + 1] - frame_off[q.frame_a], nb = frame_off[q.frame_b + 1] - frame_off[q.frame_b];
+        max_rows = std::max(max_rows, std::max(na, nb));
+        back += cross_check ? nb : na;
+        if (q.m > 0 && q.match_off >= 0) out_len = std::max(out_len, q.match_off + (int64_t)q.m);
+    }
+    if (max_rows > (1 << 22)) return GMS_ERR_CAPACITY;
+    if (out_len > 0 && !out) return GMS_ERR_BAD_ARG;
+    const size_t row = desc_kind == GMS_DESC_HAMMING256 ? 32 : 512;
+    const size_t prep = (size_t)gms::bf_prepared_bytes(desc_kind, total, n_frames);
+    const size_t ws = gms::bf_select_ws_bytes(n_pairs, max_rows, back);
+    std::lock_guard<std::mutex> lock(c->mu);
+    GMS_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    // one block: rows | offsets | pairs | results | prepared tables | workspace | out, each 256-byte aligned
+    const size_t a = 256;
+    auto up = [&](size_t x) { return (x + a - 1) / a * a; };
+    const size_t o_desc = 0, o_off = up(row * (size_t)total + 16), o_pairs = up(o_off + 8 * ((size_t)n_frames + 1));
+    const size_t o_res = up(o_pairs + sizeof(gms_pair) * (size_t)n_pairs), o_prep = up(o_res + sizeof(gms_bf_result) * (size_t)n_pairs);
+    const size_t o_ws = up(o_prep + prep + 16), o_out = up(o_ws + ws), bytes = o_out + sizeof(gms_dmatch) * (size_t)out_len + 16;
+    void* blk = nullptr;
+    GMS_HIP(hipMalloc(&blk, bytes));
+    char* d = static_cast<char*>(blk);
+    const int64_t* d_off = reinterpret_cast<const int64_t*>(d + o_off);
+    hipError_t e = hipSuccess;
+    if (total > 0) e = hipMemcpyAsync(d + o_desc, desc, row * (size_t)total, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_off, frame_off, 8 * ((size_t)n_frames + 1), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_pairs, pairs, sizeof(gms_pair) * (size_t)n_pairs, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && total > 0) e = gms::launch_bf_prepare(desc_kind, d + o_desc, d_off, n_frames, total, d + o_prep, st);
+    if (e == hipSuccess)
+        e = gms::launch_bf_select(desc_kind, d + o_desc, d + o_prep, total, d_off, n_frames, reinterpret_cast<const gms_pair*>(d + o_pairs),
+                                  n_pairs, (int)max_rows, back, cross_check, distance_coef, max_size, d + o_ws,
+                                  reinterpret_cast<gms_dmatch*>(d + o_out), reinterpret_cast<gms_bf_result*>(d + o_res), nullptr, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(results, d + o_res, sizeof(gms_bf_result) * (size_t)n_pairs, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && out_len > 0) e = hipMemcpyAsync(out, d + o_out, sizeof(gms_dmatch) * (size_t)out_len, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    else (void)hipStreamSynchronize(st);
+    (void)hipFree(blk);
+    GMS_HIP(e);
+    return GMS_OK;
+}
+
 int gms_disparity_device(gms_ctx* c, const gms_keypoint* d_kp1, int n1, const gms_keypoint* d_kp2, int n2,
                          const gms_dmatch* d_matches, const int32_t* d_n_matches, int max_matches, int width, int height,
                          const uint8_t* d_gt, int disp_ratio, uint8_t* d_disparity, uint32_t* d_work, gms_disparity_stats* d_stats)

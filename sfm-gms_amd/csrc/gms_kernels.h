@@ -101,6 +101,11 @@ hipError_t launch_bf_prepare(int kind, const void* d_desc, const int64_t* d_fram
                              hipStream_t stream);
 hipError_t launch_bf_match(int kind, const void* d_desc, const void* d_prep, int64_t total, const int64_t* d_frame_off, int n_frames,
                            const gms_pair* d_pairs, int n_pairs, int max_query, gms_dmatch* d_matches, hipStream_t stream);
+// bruteForceMatch: cross-check merge, ratio prune and MSVC sort prefix behind the matcher (bf_select_kernels.hip)
+size_t     bf_select_ws_bytes(int n_pairs, int64_t max_rows, int64_t total_back);
+hipError_t launch_bf_select(int kind, const void* d_desc, const void* d_prep, int64_t total, const int64_t* d_frame_off, int n_frames,
+                            const gms_pair* d_pairs, int n_pairs, int max_rows, int64_t total_back, int cross, double coef, int max_size,
+                            void* d_ws, gms_dmatch* d_out, gms_bf_result* d_res, gms_pair_result* d_pres, hipStream_t stream);
 // consumers of the filtered matches (consumer_kernels.hip)
 hipError_t launch_disparity(const gms_keypoint* d_kp1, int n1, const gms_keypoint* d_kp2, int n2, const gms_dmatch* d_matches,
                             const int32_t* d_n_matches, int max_matches, int w, int h, const uint8_t* d_gt, int disp_ratio,

@@ -18,6 +18,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -215,6 +216,92 @@ inline void matchLOGOSBatch(const std::vector<std::vector<KeyPoint>>& keypoints,
             }
         if (!again) break;
     }
+    matches1to2.assign(pairs.size(), std::vector<DMatch>());
+    if (ok) ok->assign(pairs.size(), true);
+    for (size_t p = 0; p < pairs.size(); ++p) {
+        if (res[p].status != GMS_OK) {
+            if (ok) (*ok)[p] = false;
+            continue;
+        }
+        matches1to2[p].assign(out_all.begin() + prs[p].match_off, out_all.begin() + prs[p].match_off + res[p].n_out);
+    }
+}
+
+// The reference's bruteForceMatch (FeatureMatchUtil.cpp:20-31): BFMatcher(norm, crossCheck).match(desc1, desc2), std::sort by
+// distance (MSVC's order among equal distances), then the matches within distance_coef times the smallest distance, at most
+// max_size. The shim has no cv::Mat: descriptors come as flat row-major vectors -- 128 floats per row (SIFT, NORM_L2) or 32 bytes
+// per row (ORB, NORM_HAMMING). matches receives (queryIdx, trainIdx, imgIdx 0, distance). An empty frame throws (the reference reads
+// front() of an empty vector there).
+namespace detail {
+inline void bf_match(int kind, const void* d1, size_t n1, const void* d2, size_t n2, std::vector<DMatch>& matches, bool cross_check,
+                     double distance_coef, int max_size)
+{
+    const int64_t cap = (int64_t)std::max<size_t>(std::min<size_t>(n1, (size_t)std::max(max_size, 0)), 1);
+    std::vector<DMatch> out((size_t)cap);
+    int64_t n = 0;
+    const int rc = gms_bf_match_select(kind, n1 ? d1 : nullptr, (int)n1, n2 ? d2 : nullptr, (int)n2, cross_check ? 1 : 0, distance_coef,
+                                       max_size, reinterpret_cast<gms_dmatch*>(out.data()), cap, &n, nullptr);
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::bruteForceMatch: ") + gms_error_string(rc));
+    out.resize((size_t)n);
+    matches.swap(out);
+}
+}  // namespace detail
+
+inline void bruteForceMatch(const std::vector<float>& desc1, const std::vector<float>& desc2, std::vector<DMatch>& matches,
+                            bool cross_check = true, double distance_coef = 4.0, int max_size = 500)
+{
+    if (desc1.size() % 128 || desc2.size() % 128) throw std::invalid_argument("mi355::bruteForceMatch: rows of 128 floats");
+    detail::bf_match(GMS_DESC_L2_F32X128, desc1.data(), desc1.size() / 128, desc2.data(), desc2.size() / 128, matches, cross_check,
+                     distance_coef, max_size);
+}
+
+inline void bruteForceMatch(const std::vector<uint8_t>& desc1, const std::vector<uint8_t>& desc2, std::vector<DMatch>& matches,
+                            bool cross_check = true, double distance_coef = 4.0, int max_size = 500)
+{
+    if (desc1.size() % 32 || desc2.size() % 32) throw std::invalid_argument("mi355::bruteForceMatch: rows of 32 bytes");
+    detail::bf_match(GMS_DESC_HAMMING256, desc1.data(), desc1.size() / 32, desc2.data(), desc2.size() / 32, matches, cross_check,
+                     distance_coef, max_size);
+}
+
+// bruteForceMatch for a whole sequence in one call, on a context (gms_bf_select_host_batch): descriptors[f] holds frame f's rows
+// (flat, T = float: 128 per row; T = uint8_t: 32 per row), pair p matches frames pairs[p].first (query) and pairs[p].second;
+// matches1to2[p] receives what bruteForceMatch would. Pairs the library refuses (an empty frame) come back empty with ok[p] = false.
+template <typename T>
+inline void bruteForceMatchBatch(const std::vector<std::vector<T>>& descriptors, const std::vector<std::pair<int, int>>& pairs,
+                                 std::vector<std::vector<DMatch>>& matches1to2, bool cross_check = true, double distance_coef = 4.0,
+                                 int max_size = 500, std::vector<bool>* ok = nullptr)
+{
+    static_assert(std::is_same<T, float>::value || std::is_same<T, uint8_t>::value, "rows of float (SIFT) or uint8_t (ORB)");
+    const int kind = std::is_same<T, float>::value ? GMS_DESC_L2_F32X128 : GMS_DESC_HAMMING256;
+    const size_t width = std::is_same<T, float>::value ? 128 : 32;
+    static gms_ctx* ctx = nullptr;  // one context per process, created on first use
+    static int ctx_rc = GMS_OK;
+    static std::once_flag ctx_once;
+    std::call_once(ctx_once, [] { ctx_rc = gms_ctx_create(0, &ctx); });
+    if (ctx_rc != GMS_OK || !ctx) throw std::runtime_error(std::string("mi355::bruteForceMatchBatch: ") + gms_error_string(ctx_rc));
+    const size_t nf = descriptors.size();
+    std::vector<int64_t> frame_off(nf + 1, 0);
+    for (size_t f = 0; f < nf; ++f) {
+        if (descriptors[f].size() % width) throw std::invalid_argument("mi355::bruteForceMatchBatch: whole rows per frame");
+        frame_off[f + 1] = frame_off[f] + (int64_t)(descriptors[f].size() / width);
+    }
+    std::vector<T> all((size_t)frame_off.back() * width);
+    for (size_t f = 0; f < nf; ++f) std::copy(descriptors[f].begin(), descriptors[f].end(), all.begin() + frame_off[f] * (int64_t)width);
+    std::vector<gms_pair> prs(pairs.size());
+    int64_t total = 0;
+    for (size_t p = 0; p < pairs.size(); ++p) {
+        const int a = pairs[p].first, b = pairs[p].second;
+        if (a < 0 || b < 0 || (size_t)a >= nf || (size_t)b >= nf) throw std::invalid_argument("mi355::bruteForceMatchBatch: frame index");
+        const int64_t cap = std::min<int64_t>(frame_off[a + 1] - frame_off[a], std::max(max_size, 0));  // K never exceeds it
+        prs[p] = gms_pair{a, b, (int32_t)cap, 0, total};
+        total += cap;
+    }
+    std::vector<DMatch> out_all((size_t)std::max<int64_t>(total, 1));
+    std::vector<gms_bf_result> res(pairs.size());
+    const int rc = gms_bf_select_host_batch(ctx, kind, all.empty() ? nullptr : all.data(), frame_off.data(), (int)nf, prs.data(),
+                                            (int)prs.size(), cross_check ? 1 : 0, distance_coef, max_size,
+                                            reinterpret_cast<gms_dmatch*>(out_all.data()), res.data());
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::bruteForceMatchBatch: ") + gms_error_string(rc));
     matches1to2.assign(pairs.size(), std::vector<DMatch>());
     if (ok) ok->assign(pairs.size(), true);
     for (size_t p = 0; p < pairs.size(); ++p) {

@@ -9,24 +9,34 @@ method="logos" runs the reference's SIFT_matchLOGOS flow instead (FeatureMatchUt
     descriptors --gms_logos_words_device--> visual words --gms_logos_prepare_device / gms_logos_filter_device--> survivors
         --gms_two_view_batch_device--> ...                                                                  (with a camera)
 
+method="bf" runs the reference's DEFAULT_SIFT flow (bruteForceMatch, FeatureMatchUtil.cpp:20-31; its SIFT_matchBF baseline):
+
+    descriptors --gms_bf_select_device (matcher, cross-check, sort, ratio prune)--> survivors
+        --gms_two_view_batch_device--> ...                                                                  (with a camera)
+
 torch here is device memory only; every stage is a call into csrc/libgms_hip.so. Used by tools/gms_filter_file.py and the tests."""
 import numpy as np
 import torch
 
-from .batch import DescriptorTable, FrameTable, LogosTable, _to_dev
+from .batch import BfSelect, DescriptorTable, FrameTable, LogosTable, _to_dev, bf_select_table
 from .types import (DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_ERR_CAPACITY, LOGOS_RESULT_DTYPE, PAIR_DTYPE, RESULT_DTYPE, TWO_VIEW_DTYPE,
                     make_camera)
 
 
 def run_dataset(ctx, ds, withRotation=False, withScale=False, thresholdFactor=6.0, match=None, camera=None, dist=None, prob=0.7,
-                ransac_threshold=1.0, max_iters=1000, device="cuda:0", method="gms", dictionary=None, logos_capacity=None):
+                ransac_threshold=1.0, max_iters=1000, device="cuda:0", method="gms", dictionary=None, logos_capacity=None,
+                cross_check=True, distance_coef=4.0, max_size=500):
     """(prob, ransac_threshold: findEssentialMat's confidence and threshold as the flow this function restates passes them -- SfMUtil.cpp:39:
     RANSAC, 0.7, 1.0 -- not OpenCV's own default of 0.999, which gms_find_essential_batch_device's Python mirror keeps.)
     ds: io.Dataset. match=None: brute-force match when the file carries descriptors and no matches. camera = (fx, fy, cx, cy)
     switches the two-view stage on. Returns a dict of host arrays: pairs, matches (the putative ones), out, results, and with a camera
     two_view (TWO_VIEW_DTYPE per pair), coords1, coords2, mask, points3d -- all per-match arrays laid out by match_off.
     method="logos": the LOGOS flow on the file's descriptors and pairs (frame_a, frame_b; their m / match_off are not used) with the
-    caller's `dictionary` (rows like the descriptors); see _run_logos."""
+    caller's `dictionary` (rows like the descriptors); see _run_logos.
+    method="bf": bruteForceMatch on the file's descriptors and pairs (cross_check, distance_coef, max_size as the reference's
+    4.0 / 500 by default); see _run_bf."""
+    if method == "bf":
+        return _run_bf(ctx, ds, cross_check, distance_coef, max_size, camera, dist, prob, ransac_threshold, max_iters, device)
     if method == "logos":
         return _run_logos(ctx, ds, dictionary, logos_capacity, camera, dist, prob, ransac_threshold, max_iters, device)
     if method != "gms":
@@ -158,4 +168,45 @@ def _run_logos(ctx, ds, dictionary, capacity, camera, dist, prob, ransac_thresho
                    points3d=d_p3.cpu().numpy().reshape(-1, 3)[:total_m])
     out.update(matches=np.zeros(0, DMATCH_DTYPE), out=d_out.cpu().numpy().view(DMATCH_DTYPE)[:total_m],
                results=d_res.cpu().numpy().view(RESULT_DTYPE)[:n_pairs])
+    return out
+
+
+def _run_bf(ctx, ds, cross_check, distance_coef, max_size, camera, dist, prob, ransac_threshold, max_iters, device):
+    """descriptors -> every pair's bruteForceMatch survivors in one gms_bf_select_device run -> two-view with a camera. Pair p gets
+    room for min(max_size, n(frame_a)) survivors, which its K never exceeds. Returns what run_dataset returns (`matches` empty: the
+    putative matches stay in the workspace), plus bf_results (BF_RESULT_DTYPE per pair); `results` are gms_pair_result records,
+    `pairs` the table the survivors are laid out by."""
+    if ds.descriptors is None:
+        raise ValueError("method='bf' needs the dataset's descriptors")
+    frames = FrameTable(ctx, ds.frames, ds.sizes, device=device)
+    dev = frames.device
+    descs = DescriptorTable(ctx, frames, ds.descriptors, ds.desc_kind)
+    src = np.ascontiguousarray(ds.pairs, dtype=PAIR_DTYPE)
+    n_pairs = len(src)
+    pairs = bf_select_table(descs, np.stack([src["frame_a"], src["frame_b"]], axis=1) if n_pairs else np.zeros((0, 2)),
+                            max_size=max_size)
+    run = BfSelect(ctx, descs, pairs, cross_check, distance_coef, max_size)
+    if n_pairs:
+        run.run()
+    ctx.synchronize()
+    total_m = run.out_len
+    max_m = int(pairs["m"].max()) if n_pairs else 0
+    out = dict(pairs=pairs)
+    if camera is not None:
+        cam = make_camera(camera, dist)
+        d_c1 = torch.zeros(max(total_m, 1) * 2, dtype=torch.float32, device=dev)
+        d_c2 = torch.zeros(max(total_m, 1) * 2, dtype=torch.float32, device=dev)
+        d_mask = torch.zeros(max(total_m, 1), dtype=torch.uint8, device=dev)
+        d_p3 = torch.zeros(max(total_m, 1) * 3, dtype=torch.float64, device=dev)
+        d_tv = torch.zeros(max(n_pairs, 1) * TWO_VIEW_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        ctx.two_view_batch_device(cam, frames.d_kp.data_ptr(), frames.d_frame_off.data_ptr(), frames.n_frames, run.d_pairs.data_ptr(),
+                                  n_pairs, max_m, run.d_out.data_ptr(), run.d_pres.data_ptr(), d_c1.data_ptr(), d_c2.data_ptr(),
+                                  d_mask.data_ptr(), d_p3.data_ptr(), d_tv.data_ptr(), prob, ransac_threshold, max_iters)
+        ctx.synchronize()
+        out.update(two_view=d_tv.cpu().numpy().view(TWO_VIEW_DTYPE)[:n_pairs], coords1=d_c1.cpu().numpy().reshape(-1, 2)[:total_m],
+                   coords2=d_c2.cpu().numpy().reshape(-1, 2)[:total_m], mask=d_mask.cpu().numpy()[:total_m],
+                   points3d=d_p3.cpu().numpy().reshape(-1, 3)[:total_m])
+    res_out, bf_res, pres = run.results()
+    out.update(matches=np.zeros(0, DMATCH_DTYPE), out=res_out[:total_m], results=pres, bf_results=bf_res)
     return out

@@ -15,6 +15,9 @@ assert PAIR_DTYPE.itemsize == 24 and RESULT_DTYPE.itemsize == 16
 # gms_logos_result (include/gms.h): one LOGOS pair's counts, peak bin and status
 LOGOS_RESULT_DTYPE = np.dtype([("n_candidates", "<i8"), ("n_supported", "<i8"), ("n_out", "<i8"), ("peak_bin", "<i4"), ("status", "<i4")])
 assert LOGOS_RESULT_DTYPE.itemsize == 32
+# gms_bf_result (include/gms.h): one bruteForceMatch pair's candidate count, count within the ratio, survivors, d_min and status
+BF_RESULT_DTYPE = np.dtype([("n_candidates", "<i8"), ("n_ratio", "<i8"), ("n_out", "<i8"), ("d_min", "<f4"), ("status", "<i4")])
+assert BF_RESULT_DTYPE.itemsize == 32
 
 GMS_OK, GMS_ERR_BAD_ARG, GMS_ERR_DOMAIN, GMS_ERR_HIP, GMS_ERR_NO_DEVICE, GMS_ERR_CAPACITY = 0, -1, -2, -3, -4, -5
 GMS_ERR_NOT_RESERVED, GMS_ERR_IO, GMS_ERR_NO_MODEL = -6, -7, -8

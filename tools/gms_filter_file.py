@@ -4,6 +4,7 @@
     python tools/gms_filter_file.py seq.gmsf [--rot] [--scale] [--thr 6.0] [--match] [--camera fx fy cx cy] [--dist k1 k2 p1 p2 k3]
                                              [--prob 0.7] [--ransac-threshold 1.0] [--out result.npz]
                                              [--logos DICT.npy [--logos-capacity N]]
+                                             [--bf [--bf-coef 4.0] [--bf-max 500] [--no-cross-check]]
 
 The file is read by the library's C reader (gms_dataset_read); with descriptors and no matches in it (or --match) the putative
 matches come from gms_bfmatch_device (FeatureMatchUtil.cpp:66-68), then gms_filter_device (matchGMS, FeatureMatchUtil.cpp:69), and
@@ -11,6 +12,9 @@ with --camera the two-view stage of structureFromMotion (SfMUtil.cpp:25-82: find
 --logos DICT.npy runs the reference's SIFT_matchLOGOS flow instead (FeatureMatchUtil.cpp:86-131): the file's descriptors get their
 visual words from the dictionary (its rows like the descriptors: [k, 128] float32 or [k, 32] uint8), then LOGOS filters every pair of
 the file (gms_logos_filter_device), then the two-view stage as above.
+--bf runs the reference's DEFAULT_SIFT flow (bruteForceMatch, FeatureMatchUtil.cpp:20-31): cross-checked brute-force matches of every
+pair, sorted by distance, kept within --bf-coef times the smallest distance and at most --bf-max (gms_bf_select_device), then the
+two-view stage as above; --no-cross-check for the reference's match() helper.
 Prints one JSON line; --out keeps every array (numpy .npz)."""
 import argparse
 import importlib
@@ -38,13 +42,20 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--logos", metavar="DICT.npy", help="LOGOS with this visual-word dictionary instead of GMS")
     ap.add_argument("--logos-capacity", type=int, help="survivors per pair before a rerun (default: the larger frame)")
+    ap.add_argument("--bf", action="store_true", help="bruteForceMatch (cross-check, sort, ratio prune) instead of GMS")
+    ap.add_argument("--bf-coef", type=float, default=4.0, help="kDistanceCoef: keep d <= coef * d_min")
+    ap.add_argument("--bf-max", type=int, default=500, help="kMaxMatchingSize: at most this many survivors per pair")
+    ap.add_argument("--no-cross-check", action="store_true", help="plain forward matches (the reference's match() helper)")
     a = ap.parse_args()
     pkg = importlib.import_module("sfm-gms_amd")
     io = importlib.import_module("sfm-gms_amd.io")
     pipeline = importlib.import_module("sfm-gms_amd.pipeline")
     ds = io.load_c(a.path)
     with pkg.GmsContext(0) as ctx:
-        if a.logos:
+        if a.bf:
+            r = pipeline.run_dataset(ctx, ds, camera=a.camera, dist=a.dist, prob=a.prob, ransac_threshold=a.ransac_threshold, method="bf",
+                                     cross_check=not a.no_cross_check, distance_coef=a.bf_coef, max_size=a.bf_max)
+        elif a.logos:
             r = pipeline.run_dataset(ctx, ds, camera=a.camera, dist=a.dist, prob=a.prob, ransac_threshold=a.ransac_threshold,
                                      method="logos", dictionary=np.load(a.logos), logos_capacity=a.logos_capacity)
         else:
@@ -54,7 +65,11 @@ def main():
     line = {"file": a.path, "frames": len(ds.frames), "pairs": len(res), "matches": int(r["pairs"]["m"].sum()),
             "kept": int(res["n_inliers"][res["status"] == 0].sum()), "failed_pairs": int((res["status"] != 0).sum()),
             "flags": [a.rot, a.scale, a.thr]}
-    if a.logos:
+    if a.bf:
+        br = r["bf_results"]
+        line.update(method="bf", matches=None, candidates=int(br["n_candidates"].sum()), within_ratio=int(br["n_ratio"].sum()),
+                    flags=[not a.no_cross_check, a.bf_coef, a.bf_max])
+    elif a.logos:
         lr = r["logos_results"]
         line.update(method="logos", matches=None, candidates=int(lr["n_candidates"].sum()), supported=int(lr["n_supported"].sum()))
     if "two_view" in r:
