@@ -488,6 +488,51 @@ int gms_logos_words_device(gms_ctx* ctx, int desc_kind, const void* d_desc, int6
 int gms_logos_host_batch(gms_ctx* ctx, const gms_keypoint* kp, const int64_t* frame_off, int n_frames, const int32_t* words, int n_words,
                          const gms_pair* pairs, int n_pairs, gms_dmatch* out, gms_logos_result* results);
 
+/* ---- StereoBM block matching: the reference's dense baseline (DisparityUtil.cpp:22-49) -------------------------------
+ *     StereoBM::create(16, 5); setNumDisparities(224); ...; compute(g1, g2, disparity);            CV_16S, 4 fractional bits
+ *     normalize(disparity, disparity, 0, 255, NORM_MINMAX, CV_8U); every 0 pixel -> 255
+ * OpenCV 4.5.2's integer path, restated (tests/stereo_bm_ref.py): XSOBEL pre-filter, blockSize^2 SADs for numDisparities disparities,
+ * texture and uniqueness tests, the subpixel step, the left-right check (validateDisparity, disp12_max_diff >= 0) and FILTERED =
+ * (min_disparity - 1) * 16 outside the valid ROI. Equal costs go to the largest disparity. Accepted (others: GMS_ERR_BAD_ARG):
+ * pre_filter_type XSOBEL, pre_filter_size odd in 5..255 (unused by XSOBEL), pre_filter_cap 1..63, block_size odd in 5..51,
+ * num_disparities a positive multiple of 16 up to 512, min_disparity >= -2047 with min_disparity + num_disparities <= 2048,
+ * texture_threshold >= 0, uniqueness_ratio 0..1000, speckle_window_size 0 (speckle_range is then unused), width 1..8192 and
+ * block_size < min(width, height).
+ * Images: 8-bit grey, row y of image i at d_left / d_right + (i * height + y) * pitch (pitch >= width). Maps: int16 [n][height][width];
+ * costs (optional): int32 [n][height][width], sad[best] where the winner-take-all step gave a disparity, -1 elsewhere. */
+#define GMS_STEREO_BM_PREFILTER_NORMALIZED_RESPONSE 0
+#define GMS_STEREO_BM_PREFILTER_XSOBEL              1
+#define GMS_STEREO_BM_MAX_WIDTH                  8192
+typedef struct gms_stereo_bm_params {
+    int32_t block_size;          /* SADWindowSize                          */
+    int32_t num_disparities;
+    int32_t min_disparity;
+    int32_t pre_filter_type;     /* GMS_STEREO_BM_PREFILTER_XSOBEL only    */
+    int32_t pre_filter_size;
+    int32_t pre_filter_cap;
+    int32_t texture_threshold;
+    int32_t uniqueness_ratio;
+    int32_t speckle_window_size; /* 0 only                                 */
+    int32_t speckle_range;
+    int32_t disp12_max_diff;     /* < 0: no left-right check               */
+} gms_stereo_bm_params;
+/* The reference's values (DisparityUtil.cpp:24-36): gms_stereo_bm_params p = GMS_STEREO_BM_PARAMS_REFERENCE; a NULL params pointer
+ * means the same. */
+#define GMS_STEREO_BM_PARAMS_REFERENCE {5, 224, -39, GMS_STEREO_BM_PREFILTER_XSOBEL, 5, 61, 507, 0, 0, 8, 1}
+
+/* gms_stereo_bm_workspace_bytes: the workspace of gms_stereo_bm_device (256-byte aligned pointer); 0 for arguments it rejects.
+ * gms_stereo_bm_device: n_pairs (up to 65535) pairs on the context's stream; no allocation, no synchronisation, no readback
+ *   (graph-capturable). d_cost may be NULL.
+ * gms_stereo_bm_normalize_device: the reference's 8-bit map of each of n int16 maps (d_out8: n * width * height bytes).
+ * gms_stereo_bm: ONE pair on host pointers, synchronous, on the current HIP device; disp16 / cost / disp8 (the reference's 8-bit map)
+ *   are each optional. */
+size_t gms_stereo_bm_workspace_bytes(int width, int height, int n_pairs, const gms_stereo_bm_params* params);
+int gms_stereo_bm_device(gms_ctx* ctx, const gms_stereo_bm_params* params, const uint8_t* d_left, const uint8_t* d_right, int n_pairs,
+                         int width, int height, int pitch, void* d_ws, size_t ws_bytes, int16_t* d_disp16, int32_t* d_cost);
+int gms_stereo_bm_normalize_device(gms_ctx* ctx, const int16_t* d_disp16, int n, int width, int height, uint8_t* d_out8);
+int gms_stereo_bm(const gms_stereo_bm_params* params, const uint8_t* left, const uint8_t* right, int width, int height, int pitch,
+                  int16_t* disp16, int32_t* cost, uint8_t* disp8);
+
 const char* gms_error_string(int code);
 const char* gms_version(void);
 

@@ -13,7 +13,7 @@ import numpy as np
 
 from .capi import load_library
 from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_DESC_HAMMING256, KEYPOINT_DTYPE, PAIR_DTYPE, RESULT_DTYPE, GMS_OK, GMS_ERR_CAPACITY,
-                    GmsError)
+                    GmsError, stereo_bm_params)
 
 
 def _as(arr, dtype, name):
@@ -275,6 +275,20 @@ class GmsContext:
         _check(self._lib.gms_logos_words_device(self._h, int(desc_kind), d_desc or None, int(total_desc), d_dict, int(n_words),
                                                 d_words or None), self._lib, "gms_logos_words_device")
 
+    # -- StereoBM block matching (DisparityUtil.cpp:22-49; batch.stereo_bm_batch drives these) ------------------------------------
+    def stereo_bm_workspace_bytes(self, width, height, n_pairs, params=None):
+        return int(self._lib.gms_stereo_bm_workspace_bytes(int(width), int(height), int(n_pairs), stereo_bm_params(params).ctypes.data))
+
+    def stereo_bm_device(self, params, d_left, d_right, n_pairs, width, height, pitch, d_ws, ws_bytes, d_disp16, d_cost=None):
+        """gms_stereo_bm_device; params: None (the reference's), a dict or a STEREO_BM_PARAMS_DTYPE record. Stream-ordered."""
+        rec = stereo_bm_params(params)
+        _check(self._lib.gms_stereo_bm_device(self._h, rec.ctypes.data, d_left, d_right, int(n_pairs), int(width), int(height), int(pitch),
+                                              d_ws, int(ws_bytes), d_disp16, d_cost or None), self._lib, "gms_stereo_bm_device")
+
+    def stereo_bm_normalize_device(self, d_disp16, n, width, height, d_out8):
+        _check(self._lib.gms_stereo_bm_normalize_device(self._h, d_disp16, int(n), int(width), int(height), d_out8), self._lib,
+               "gms_stereo_bm_normalize_device")
+
     def selftest_five_point(self, x1, x2):
         """gms_selftest_five_point: x1, x2 [n_samples, 5, 2] normalised points -> list of [k, 3, 3] model arrays, one per sample."""
         x1 = np.asarray(x1, dtype=np.float64).reshape(-1, 5, 2)
@@ -304,11 +318,7 @@ def matchGMS(size1, size2, keypoints1, keypoints2, matches1to2, withRotation=Fal
 
     size = (width, height) like cv::Size. Raises GmsError instead of the reference's undefined behaviour
     on out-of-domain input."""
-    global _default_ctx
-    if _default_ctx is None:
-        _default_ctx = GmsContext(0)
-    return _default_ctx.match(size1, size2, keypoints1, keypoints2, matches1to2, withRotation, withScale,
-                              thresholdFactor)
+    return default_context().match(size1, size2, keypoints1, keypoints2, matches1to2, withRotation, withScale, thresholdFactor)
 
 
 def matchLOGOS(keypoints1, keypoints2, nn1, nn2):
@@ -360,3 +370,43 @@ def bruteForceMatch(desc1, desc2, kind, cross_check=True, distance_coef=4.0, max
     _check(rc, lib, "gms_bf_match_select")
     got = out[: n.value].copy()
     return (got, res[0]) if detail else got
+
+
+def default_context():
+    """The process-wide context of device 0 that matchGMS uses, created on first use."""
+    global _default_ctx
+    if _default_ctx is None:
+        _default_ctx = GmsContext(0)
+    return _default_ctx
+
+
+def _stereo_bm(left, right, params, want16, want_cost, want8):
+    lib = load_library()
+    lt = np.ascontiguousarray(left, dtype=np.uint8)
+    rt = np.ascontiguousarray(right, dtype=np.uint8)
+    if lt.ndim != 2 or rt.shape != lt.shape:
+        raise ValueError("left and right: two 8-bit grey images [H, W] of one size")
+    h, w = lt.shape
+    rec = stereo_bm_params(params)
+    d16 = np.zeros((h, w), np.int16) if want16 else None
+    cost = np.zeros((h, w), np.int32) if want_cost else None
+    d8 = np.zeros((h, w), np.uint8) if want8 else None
+    rc = lib.gms_stereo_bm(rec.ctypes.data, lt.ctypes.data, rt.ctypes.data, w, h, w, None if d16 is None else d16.ctypes.data,
+                           None if cost is None else cost.ctypes.data, None if d8 is None else d8.ctypes.data)
+    _check(rc, lib, "gms_stereo_bm")
+    return d16, cost, d8
+
+
+def stereoBM(left, right, return_cost=False, **params):
+    """StereoBM::compute(left, right, disparity) of OpenCV 4.5.2 on the GPU (integer path; tests/stereo_bm_ref.py states it): the int16
+    map with 4 fractional bits, FILTERED = (min_disparity - 1) * 16. Parameters by keyword (block_size, num_disparities, min_disparity,
+    pre_filter_cap, texture_threshold, uniqueness_ratio, disp12_max_diff, ...; types.STEREO_BM_PARAMS_DTYPE), the reference's values
+    (DisparityUtil.cpp:24-36) by default. return_cost=True: also the int32 cost map (sad of the winner, -1 where there is none)."""
+    d16, cost, _ = _stereo_bm(left, right, params, True, return_cost, False)
+    return (d16, cost) if return_cost else d16
+
+
+def stereo_match(left, right, **params):
+    """The reference's stereo_match (DisparityUtil.cpp:22-49): StereoBM with its parameters, normalize(NORM_MINMAX, 0..255, CV_8U),
+    every 0 -> 255. Returns the uint8 map."""
+    return _stereo_bm(left, right, params, False, False, True)[2]

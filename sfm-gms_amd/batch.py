@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from .api import GmsContext
-from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_ERR_CAPACITY, KEYPOINT_DTYPE, LOGOS_RESULT_DTYPE,
+from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_ERR_CAPACITY, KEYPOINT_DTYPE, LOGOS_RESULT_DTYPE, stereo_bm_params,
                     PAIR_DTYPE, RESULT_DTYPE)
 
 
@@ -388,3 +388,56 @@ def logos_words(ctx, descriptors_per_frame, dictionary, kind, device=None):
         raise ValueError("1 <= dictionary rows <= 65535")
     out = np.split(words, np.cumsum(counts)[:-1]) if counts else []
     return out[0] if single else out
+
+
+class StereoBM:
+    """Device buffers of gms_stereo_bm_device for n pairs of one size: workspace, int16 maps, costs and 8-bit maps, sized once, so that
+    run() can be replayed (or captured into a graph) on new images in the same tensors."""
+
+    def __init__(self, ctx, n, width, height, params=None, device="cuda:0", with_cost=True):
+        self.ctx, self.n, self.width, self.height = ctx, int(n), int(width), int(height)
+        self.params = stereo_bm_params(params)
+        dev = torch.device(device)
+        self.ws_bytes = ctx.stereo_bm_workspace_bytes(width, height, n, self.params)
+        if self.ws_bytes == 0 and self.n > 0:
+            raise ValueError("StereoBM: parameters or image size rejected (include/gms.h)")
+        self.d_ws = torch.zeros(max(self.ws_bytes, 256), dtype=torch.uint8, device=dev)
+        self.d_disp = torch.zeros((max(self.n, 1), self.height, self.width), dtype=torch.int16, device=dev)
+        self.d_cost = torch.zeros((max(self.n, 1), self.height, self.width), dtype=torch.int32, device=dev) if with_cost else None
+        self.d_out8 = torch.zeros((max(self.n, 1), self.height, self.width), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+
+    def run(self, d_left, d_right, eight_bit=False):
+        """d_left / d_right: uint8 device tensors [n, height, width] (contiguous). Stream-ordered on the context's stream."""
+        for t in (d_left, d_right):
+            if t.dtype != torch.uint8 or tuple(t.shape) != (self.n, self.height, self.width) or not t.is_contiguous():
+                raise ValueError("left / right: contiguous uint8 device tensors [n, height, width]")
+        self.ctx.stereo_bm_device(self.params, d_left.data_ptr(), d_right.data_ptr(), self.n, self.width, self.height, self.width,
+                                  self.d_ws.data_ptr(), self.ws_bytes, self.d_disp.data_ptr(),
+                                  self.d_cost.data_ptr() if self.d_cost is not None else None)
+        if eight_bit:
+            self.ctx.stereo_bm_normalize_device(self.d_disp.data_ptr(), self.n, self.width, self.height, self.d_out8.data_ptr())
+
+
+def stereo_bm_batch(lefts, rights, params=None, ctx=None, return_cost=False, eight_bit=False):
+    """StereoBM::compute for n pairs in one gms_stereo_bm_device run. lefts / rights: uint8 [n, H, W] host arrays or device tensors.
+    Returns the int16 maps [n, H, W] (numpy for host input, device tensors for device input), then the int32 costs with
+    return_cost=True and the reference's 8-bit maps with eight_bit=True."""
+    from .api import default_context
+    ctx = ctx or default_context()
+    on_dev = isinstance(lefts, torch.Tensor)
+    if on_dev:
+        dl, dr = lefts.contiguous(), rights.contiguous()
+    else:
+        l, r = np.ascontiguousarray(lefts, dtype=np.uint8), np.ascontiguousarray(rights, dtype=np.uint8)
+        if l.ndim != 3 or r.shape != l.shape:
+            raise ValueError("lefts / rights: uint8 [n, H, W] of one shape")
+        dl, dr = torch.from_numpy(l).cuda(), torch.from_numpy(r).cuda()
+    n, h, w = dl.shape
+    run = StereoBM(ctx, n, w, h, params, dl.device, with_cost=return_cost)
+    run.run(dl, dr, eight_bit)
+    ctx.synchronize()
+    outs = [run.d_disp[:n]] + ([run.d_cost[:n]] if return_cost else []) + ([run.d_out8[:n]] if eight_bit else [])
+    if not on_dev:
+        outs = [o.cpu().numpy() for o in outs]
+    return outs[0] if len(outs) == 1 else tuple(outs)

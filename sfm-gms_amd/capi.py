@@ -16,7 +16,8 @@ EXPORTED_SYMBOLS = [
     "gms_detect_workspace_bytes", "gms_detect_batch_device", "gms_describe_device", "gms_logos_match",
     "gms_logos_table_bytes", "gms_logos_workspace_bytes", "gms_logos_prepare_device", "gms_logos_filter_device", "gms_logos_words_device",
     "gms_logos_host_batch", "gms_bf_select_workspace_bytes", "gms_bf_select_device", "gms_bf_match_select",
-    "gms_bf_select_host_batch",
+    "gms_bf_select_host_batch", "gms_stereo_bm_workspace_bytes", "gms_stereo_bm_device", "gms_stereo_bm_normalize_device",
+    "gms_stereo_bm",
 ]
 
 _lib = None
@@ -87,6 +88,10 @@ def load_library():
     lib.gms_bf_select_device.argtypes = [vp, i32, vp, vp, i64, vp, i32, vp, i32, i32, i32, dbl, i32, vp, C.c_size_t, vp, vp, vp]
     lib.gms_bf_match_select.argtypes = [i32, vp, i32, vp, i32, i32, dbl, i32, vp, i64, C.POINTER(i64), vp]
     lib.gms_bf_select_host_batch.argtypes = [vp, i32, vp, vp, i32, vp, i32, i32, dbl, i32, vp, vp]
+    lib.gms_stereo_bm_workspace_bytes.argtypes = [i32, i32, i32, vp]
+    lib.gms_stereo_bm_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, C.c_size_t, vp, vp]
+    lib.gms_stereo_bm_normalize_device.argtypes = [vp, vp, i32, i32, i32, vp]
+    lib.gms_stereo_bm.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     lib.gms_max_matches.argtypes = []
     lib.gms_last_hip_error.argtypes = []
     lib.gms_error_string.argtypes = [i32]
@@ -103,6 +108,7 @@ def load_library():
     lib.gms_logos_table_bytes.restype = i64
     lib.gms_logos_workspace_bytes.restype = C.c_size_t
     lib.gms_bf_select_workspace_bytes.restype = C.c_size_t
+    lib.gms_stereo_bm_workspace_bytes.restype = C.c_size_t
     lib.gms_dataset_free.restype = None
     lib.gms_frame_table_bytes.argtypes = [i64]
     lib.gms_frame_table_bytes.restype = i64

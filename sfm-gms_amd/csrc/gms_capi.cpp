@@ -21,6 +21,7 @@
 #include "gms.h"
 #include "gms_kernels.h"
 #include "logos_batch.h"
+#include "stereo_bm_core.h"
 #include "twoview_core.h"
 
 static_assert(sizeof(gms_keypoint) == 28, "gms_keypoint must match cv::KeyPoint (stride 0x1c)");
@@ -1228,6 +1229,78 @@ int gms_bf_select_host_batch(gms_ctx* c, int desc_kind, const void* desc, const 
                                   reinterpret_cast<gms_dmatch*>(d + o_out), reinterpret_cast<gms_bf_result*>(d + o_res), nullptr, st);
     if (e == hipSuccess) e = hipMemcpyAsync(results, d + o_res, sizeof(gms_bf_result) * (size_t)n_pairs, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && out_len > 0) e = hipMemcpyAsync(out, d + o_out, sizeof(gms_dmatch) * (size_t)out_len, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    else (void)hipStreamSynchronize(st);
+    (void)hipFree(blk);
+    GMS_HIP(e);
+    return GMS_OK;
+}
+
+// ---- StereoBM (stereo_bm_kernels.hip) ----------------------------------------------------------------------------
+static const gms_stereo_bm_params& sbm_params(const gms_stereo_bm_params* p)
+{
+    static const gms_stereo_bm_params ref = GMS_STEREO_BM_PARAMS_REFERENCE;
+    return p ? *p : ref;
+}
+
+size_t gms_stereo_bm_workspace_bytes(int width, int height, int n_pairs, const gms_stereo_bm_params* params)
+{
+    if (n_pairs < 0 || n_pairs > 65535 || !sbm::params_ok(sbm_params(params), width, height)) return 0;
+    return gms::stereo_bm_ws_bytes(n_pairs, width, height);
+}
+
+int gms_stereo_bm_device(gms_ctx* c, const gms_stereo_bm_params* params, const uint8_t* d_left, const uint8_t* d_right, int n_pairs,
+                         int width, int height, int pitch, void* d_ws, size_t ws_bytes, int16_t* d_disp16, int32_t* d_cost)
+{
+    const gms_stereo_bm_params& p = sbm_params(params);
+    if (!c || n_pairs < 0 || n_pairs > 65535 || !sbm::params_ok(p, width, height) || pitch < width) return GMS_ERR_BAD_ARG;
+    if (n_pairs == 0) return GMS_OK;
+    if (!d_left || !d_right || !d_ws || !d_disp16) return GMS_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_ws) & 255u) || (reinterpret_cast<uintptr_t>(d_disp16) & 1u) ||
+        (reinterpret_cast<uintptr_t>(d_cost) & 3u) || ws_bytes < gms::stereo_bm_ws_bytes(n_pairs, width, height))
+        return GMS_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(c->mu);
+    GMS_HIP(hipSetDevice(c->device));
+    GMS_HIP(gms::launch_stereo_bm(p, d_left, d_right, n_pairs, width, height, pitch, d_ws, d_disp16, d_cost, c->stream));
+    return GMS_OK;
+}
+
+int gms_stereo_bm_normalize_device(gms_ctx* c, const int16_t* d_disp16, int n, int width, int height, uint8_t* d_out8)
+{
+    if (!c || n < 0 || width <= 0 || height <= 0) return GMS_ERR_BAD_ARG;
+    if (n == 0) return GMS_OK;
+    if (!d_disp16 || !d_out8 || (reinterpret_cast<uintptr_t>(d_disp16) & 1u)) return GMS_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(c->mu);
+    GMS_HIP(hipSetDevice(c->device));
+    GMS_HIP(gms::launch_stereo_bm_normalize(d_disp16, n, width, height, d_out8, c->stream));
+    return GMS_OK;
+}
+
+int gms_stereo_bm(const gms_stereo_bm_params* params, const uint8_t* left, const uint8_t* right, int width, int height, int pitch,
+                  int16_t* disp16, int32_t* cost, uint8_t* disp8)
+{
+    const gms_stereo_bm_params& p = sbm_params(params);
+    if (!sbm::params_ok(p, width, height) || pitch < width || !left || !right) return GMS_ERR_BAD_ARG;
+    const size_t px = (size_t)width * (size_t)height, img = (size_t)pitch * (size_t)(height - 1) + (size_t)width;
+    const size_t a = 256;
+    auto up = [&](size_t x) { return (x + a - 1) / a * a; };
+    // one block: left | right (pitch as given) | workspace | int16 map | costs | 8-bit map
+    const size_t o_r = up(img), o_ws = up(o_r + img), o_d = o_ws + up(gms::stereo_bm_ws_bytes(1, width, height));
+    const size_t o_c = up(o_d + 2 * px), o_8 = up(o_c + 4 * px), bytes = o_8 + px;
+    void* blk = nullptr;
+    GMS_HIP(hipMalloc(&blk, bytes));
+    char* d = static_cast<char*>(blk);
+    hipStream_t st = nullptr;
+    int16_t* d_disp = reinterpret_cast<int16_t*>(d + o_d);
+    hipError_t e = hipMemcpyAsync(d, left, img, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_r, right, img, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = gms::launch_stereo_bm(p, reinterpret_cast<const uint8_t*>(d), reinterpret_cast<const uint8_t*>(d + o_r), 1, width, height,
+                                  pitch, d + o_ws, d_disp, cost ? reinterpret_cast<int32_t*>(d + o_c) : nullptr, st);
+    if (e == hipSuccess && disp8) e = gms::launch_stereo_bm_normalize(d_disp, 1, width, height, reinterpret_cast<uint8_t*>(d + o_8), st);
+    if (e == hipSuccess && disp16) e = hipMemcpyAsync(disp16, d_disp, 2 * px, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && cost) e = hipMemcpyAsync(cost, d + o_c, 4 * px, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && disp8) e = hipMemcpyAsync(disp8, d + o_8, px, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     else (void)hipStreamSynchronize(st);
     (void)hipFree(blk);

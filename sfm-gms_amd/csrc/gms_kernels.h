@@ -147,6 +147,11 @@ hipError_t launch_logos_filter(const void* d_table, const gms_pair* d_pairs, int
                                gms_logos_result* d_lres, gms_pair_result* d_pres, int n_cus, hipStream_t stream);
 hipError_t launch_logos_words(int kind, const void* d_desc, int64_t total, const void* d_dict, int n_words, int32_t* d_words, int n_cus,
                               hipStream_t stream);
+// StereoBM block matching (stereo_bm_kernels.hip; shared arithmetic in stereo_bm_core.h)
+size_t     stereo_bm_ws_bytes(int n, int W, int H);
+hipError_t launch_stereo_bm(const gms_stereo_bm_params& p, const uint8_t* d_left, const uint8_t* d_right, int n, int W, int H, int pitch,
+                            void* d_ws, int16_t* d_disp, int32_t* d_cost, hipStream_t stream);
+hipError_t launch_stereo_bm_normalize(const int16_t* d_disp, int n, int W, int H, uint8_t* d_out, hipStream_t stream);
 hipError_t launch_threshold(const int32_t* d_T, const int32_t* d_n, const int32_t* d_score, double factor,
                             int count, uint8_t* d_out, hipStream_t stream);
 

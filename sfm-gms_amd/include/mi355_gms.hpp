@@ -313,4 +313,46 @@ inline void bruteForceMatchBatch(const std::vector<std::vector<T>>& descriptors,
     }
 }
 
+// The reference's stereo_match (DisparityUtil.cpp:22-49): StereoBM with its parameters (GMS_STEREO_BM_PARAMS_REFERENCE), then
+// normalize(NORM_MINMAX, 0..255, CV_8U) and every 0 -> 255. The shim has no cv::Mat: images are flat row-major 8-bit grey vectors of
+// width * height bytes, and so is disparity8. stereoBM gives StereoBM::compute's int16 map (4 fractional bits) for any accepted
+// parameter set (include/gms.h). Both run one pair synchronously on the current HIP device (gms_stereo_bm).
+inline gms_stereo_bm_params stereo_bm_reference_params()
+{
+    const gms_stereo_bm_params p = GMS_STEREO_BM_PARAMS_REFERENCE;
+    return p;
+}
+
+namespace detail {
+inline void stereo_check(const std::vector<uint8_t>& left, const std::vector<uint8_t>& right, int width, int height)
+{
+    if (width <= 0 || height <= 0 || left.size() != (size_t)width * (size_t)height || right.size() != left.size())
+        throw std::invalid_argument("mi355::stereo_match: two width * height 8-bit images");
+}
+}  // namespace detail
+
+inline void stereoBM(const std::vector<uint8_t>& left, const std::vector<uint8_t>& right, int width, int height,
+                     const gms_stereo_bm_params& params, std::vector<int16_t>& disparity16)
+{
+    detail::stereo_check(left, right, width, height);
+    disparity16.assign((size_t)width * (size_t)height, 0);
+    const int rc = gms_stereo_bm(&params, left.data(), right.data(), width, height, width, disparity16.data(), nullptr, nullptr);
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::stereoBM: ") + gms_error_string(rc));
+}
+
+inline void stereo_match(const std::vector<uint8_t>& left, const std::vector<uint8_t>& right, int width, int height,
+                         const gms_stereo_bm_params& params, std::vector<uint8_t>& disparity8)
+{
+    detail::stereo_check(left, right, width, height);
+    disparity8.assign((size_t)width * (size_t)height, 0);
+    const int rc = gms_stereo_bm(&params, left.data(), right.data(), width, height, width, nullptr, nullptr, disparity8.data());
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::stereo_match: ") + gms_error_string(rc));
+}
+
+inline void stereo_match(const std::vector<uint8_t>& left, const std::vector<uint8_t>& right, int width, int height,
+                         std::vector<uint8_t>& disparity8)
+{
+    stereo_match(left, right, width, height, stereo_bm_reference_params(), disparity8);
+}
+
 }  // namespace mi355

@@ -19,6 +19,32 @@ assert LOGOS_RESULT_DTYPE.itemsize == 32
 BF_RESULT_DTYPE = np.dtype([("n_candidates", "<i8"), ("n_ratio", "<i8"), ("n_out", "<i8"), ("d_min", "<f4"), ("status", "<i4")])
 assert BF_RESULT_DTYPE.itemsize == 32
 
+# gms_stereo_bm_params (include/gms.h): StereoBM's parameters, eleven int32 in this order
+STEREO_BM_PARAMS_DTYPE = np.dtype([(n, "<i4") for n in (
+    "block_size", "num_disparities", "min_disparity", "pre_filter_type", "pre_filter_size", "pre_filter_cap", "texture_threshold",
+    "uniqueness_ratio", "speckle_window_size", "speckle_range", "disp12_max_diff")])
+assert STEREO_BM_PARAMS_DTYPE.itemsize == 44
+GMS_STEREO_BM_PREFILTER_NORMALIZED_RESPONSE, GMS_STEREO_BM_PREFILTER_XSOBEL = 0, 1
+# GMS_STEREO_BM_PARAMS_REFERENCE: the reference's StereoBM (DisparityUtil.cpp:24-36)
+STEREO_BM_REFERENCE = dict(block_size=5, num_disparities=224, min_disparity=-39, pre_filter_type=GMS_STEREO_BM_PREFILTER_XSOBEL,
+                           pre_filter_size=5, pre_filter_cap=61, texture_threshold=507, uniqueness_ratio=0, speckle_window_size=0,
+                           speckle_range=8, disp12_max_diff=1)
+
+
+def stereo_bm_params(params=None, **kw):
+    """A one-record STEREO_BM_PARAMS_DTYPE array: the reference's values, updated from params (a dict or a record) and keywords."""
+    rec = np.zeros(1, STEREO_BM_PARAMS_DTYPE)
+    vals = dict(STEREO_BM_REFERENCE)
+    if params is not None:
+        vals.update(params if isinstance(params, dict) else {n: int(np.asarray(params).reshape(-1)[0][n]) for n in STEREO_BM_PARAMS_DTYPE.names})
+    vals.update(kw)
+    for k, v in vals.items():
+        if k not in STEREO_BM_PARAMS_DTYPE.names:
+            raise TypeError(f"unknown StereoBM parameter {k!r}")
+        rec[k] = int(v)
+    return rec
+
+
 GMS_OK, GMS_ERR_BAD_ARG, GMS_ERR_DOMAIN, GMS_ERR_HIP, GMS_ERR_NO_DEVICE, GMS_ERR_CAPACITY = 0, -1, -2, -3, -4, -5
 GMS_ERR_NOT_RESERVED, GMS_ERR_IO, GMS_ERR_NO_MODEL = -6, -7, -8
 GMS_DETECT_BORDER = 16   # include/gms.h: keypoints of gms_detect_batch_device sit at least this far from every edge
