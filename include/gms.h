@@ -177,12 +177,17 @@ int gms_filter_device(gms_ctx* ctx, const float* d_pts, const int64_t* d_frame_o
 /* ---- host-pointer batch path -------------------------------------------------------------------
  * The throughput entry for callers that hold everything in host memory (a C++ caller of the reference looping over
  * image pairs: FeatureMatchUtil.cpp:66-69 once per pair): the frames' keypoints are uploaded and normalised once,
- * then the pair list is cut into chunks that travel through pinned staging buffers on two streams -- chunk k+1 is
- * uploaded while chunk k is filtered and chunk k-1 comes back. Synchronous: returns when out/results are complete.
- *   kp/frame_off/wh   keypoints of all frames back to back, n_frames+1 offsets, (w, h) per frame
+ * then the pair list is cut into chunks (at most 2^21 matches or 8192 pairs each; a larger pair is a chunk of its own) that
+ * travel through pinned staging buffers on three lanes, each with a stream of its own; chunk k rides lane k % 3, so that
+ * chunk k+1 is uploaded while chunk k is filtered and chunk k-1 comes back. Synchronous: returns when out/results are complete.
+ *   kp/frame_off/wh   keypoints of all frames back to back, n_frames+1 offsets, (w, h) per frame. frame_off[0] must be 0 and the
+ *                     offsets must never decrease (GMS_ERR_BAD_ARG before anything is copied or launched otherwise); kp must hold
+ *                     at least frame_off[n_frames] records -- the library cannot check that, it reads that many
  *   pairs/matches     as gms_filter_device, host memory; match_off indexes `matches` and `out` alike
  *   out               pair i's survivors verbatim at out[match_off .. match_off + results[i].n_inliers)
- * Returns GMS_OK, or the first error; pairs outside the parity domain are reported per pair in results[i].status. */
+ * Only those records of out are written: the rest of each pair's range, and whatever lies outside every pair's range, keep what
+ * they held; so do results[n_pairs ..]. Returns GMS_OK, or the first error; pairs outside the parity domain are reported per
+ * pair in results[i].status. */
 int gms_filter_host_batch(gms_ctx* ctx, const gms_keypoint* kp, const int64_t* frame_off, const int32_t* wh,
                           int n_frames, const gms_pair* pairs, int n_pairs, const gms_dmatch* matches,
                           int with_rotation, int with_scale, double threshold_factor,

@@ -96,7 +96,7 @@ class GmsContext:
         kept = out[: n_out.value].copy()
         return (kept, res[0]) if return_result else kept
 
-    # -- host-pointer batch path: many pairs per call, pinned staging and two streams inside the library ------------
+    # -- host-pointer batch path: many pairs per call, pinned staging and three lanes inside the library ----------
     def filter_host_batch(self, keypoints_per_frame, sizes, pairs, matches, withRotation=False, withScale=False,
                           thresholdFactor=6.0, out=None, results=None):
         """gms_filter_host_batch: `pairs` (PAIR_DTYPE) index `matches` (DMATCH_DTYPE) by match_off. Returns
@@ -107,9 +107,14 @@ class GmsContext:
         by its constructor."""
         if isinstance(keypoints_per_frame, tuple):
             kp, frame_off = keypoints_per_frame
-            kp = _as(kp, KEYPOINT_DTYPE, "keypoints") if len(kp) else np.zeros(1, dtype=KEYPOINT_DTYPE)
+            n_kp = len(kp)
+            kp = _as(kp, KEYPOINT_DTYPE, "keypoints") if n_kp else np.zeros(1, dtype=KEYPOINT_DTYPE)
             frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
-            n_frames = len(frame_off) - 1
+            n_frames = len(np.asarray(sizes).reshape(-1, 2))
+            # the library reads frame_off[-1] keypoints from kp: a prefix of a longer array is fine, running past its end is not
+            if (frame_off.shape != (n_frames + 1,) or frame_off[0] != 0 or (np.diff(frame_off) < 0).any()
+                    or frame_off[-1] > n_kp):
+                raise ValueError("frame_off: one offset per frame and one more, from 0, never decreasing, the last at most len(keypoints)")
         else:
             counts = np.array([len(k) for k in keypoints_per_frame], dtype=np.int64)
             frame_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)

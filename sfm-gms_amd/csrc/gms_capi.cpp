@@ -18,6 +18,7 @@
 #include <thread>
 #include <vector>
 
+#include "copy_pool.h"
 #include "gms.h"
 #include "gms_kernels.h"
 #include "logos_batch.h"
@@ -173,7 +174,6 @@ struct Lane {
     DevBuf din, dout;
     hipEvent_t ev_res = nullptr, ev_out = nullptr;  // gms_filter_host_batch: a chunk's results are on the host / its survivors are
 };
-namespace { class CopyPool; }
 
 struct gms_ctx {
     int device = 0;
@@ -211,7 +211,7 @@ struct gms_ctx {
     hipStream_t ws_stream = nullptr;
     bool ws_pending = false;
     Lane lane[3];     // one-shot calls use lane 0 (on the context's stream); gms_filter_host_batch rotates through all three
-    CopyPool* pool = nullptr;  // gms_filter_host_batch: the threads that stage its chunks (created with the first call)
+    gms::CopyPool* pool = nullptr;  // gms_filter_host_batch: the threads that stage its chunks (created with the first call)
     DevBuf tab_kp, tab_pts, tab_small;  // gms_filter_host_batch: the call's frame table
     int n_cus = 256;  // multiProcessorCount of the device
 };
@@ -450,125 +450,10 @@ int filter_launch(gms_ctx* c, hipStream_t st, const float* d_pts, const int64_t*
 // and coming back:                                            [ results (16 B each) | out (16 B each) ]
 size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
-// Host-side staging: the copies between the caller's (pageable) arrays and the pinned blocks the copy engines work from. One core
-// moves 25-35 GB/s here, four move 65-110 (tools/ubench/host_copy_rate.cpp), the copy engines 30-55 GB/s per direction: the copies of
-// a chunk are cut into parts of 1 MB that a PERSISTENT pool of threads (created with the context's first host batch, not per chunk)
-// takes from a shared counter; the calling thread works along.
-struct CopyJob {
-    void* dst;
-    const void* src;
-    size_t bytes;   // of dst
-    int pack_xy;    // 0: memcpy; 1: src = gms_keypoint records, dst = (pt.x, pt.y) float pairs, 8 bytes each (bytes % 8 == 0)
-};
-
-// (pt.x, pt.y) of n keypoints, 8 bytes each: all the filter reads of a cv::KeyPoint (DLL@0x1800485d4) and all that has to
-// cross PCIe. Pure data movement; the divide by the image size happens on the GPU (normalize_kernel).
-void pack_xy(const gms_keypoint* kp, size_t n, float* dst)
-{
-    for (size_t i = 0; i < n; ++i) {
-        dst[2 * i] = kp[i].x;
-        dst[2 * i + 1] = kp[i].y;
-    }
-}
-
-class CopyPool {
-public:
-    ~CopyPool() { shutdown(); }
-    void shutdown()
-    {
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            stop_ = true;
-        }
-        cv_work_.notify_all();
-        for (std::thread& t : threads_) t.join();
-        threads_.clear();
-        stop_ = false;
-    }
-    // Runs the jobs (disjoint destinations) and returns when every byte has landed.
-    void run(const std::vector<CopyJob>& jobs)
-    {
-        if (jobs.empty()) return;
-        starts_.resize(jobs.size() + 1);
-        starts_[0] = 0;
-        for (size_t i = 0; i < jobs.size(); ++i) starts_[i + 1] = starts_[i] + jobs[i].bytes;
-        const size_t total = starts_.back();
-        if (total == 0) return;
-        const unsigned n_parts = (unsigned)((total + kPart - 1) / kPart);
-        if (n_parts <= 1) {
-            part(jobs, 0);
-            return;
-        }
-        if (threads_.empty()) start();
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            jobs_ = &jobs;
-            n_parts_ = n_parts;
-            next_.store(0, std::memory_order_relaxed);
-            done_ = 0;
-            ++gen_;
-        }
-        cv_work_.notify_all();
-        unsigned mine = 0;
-        for (unsigned i; (i = next_.fetch_add(1, std::memory_order_relaxed)) < n_parts; ++mine) part(jobs, i);
-        std::unique_lock<std::mutex> lk(mu_);
-        done_ += mine;
-        cv_done_.wait(lk, [&] { return done_ == n_parts_; });
-        jobs_ = nullptr;
-    }
-
-private:
-    static constexpr size_t kPart = (size_t)1 << 20;
-    void start()
-    {
-        unsigned hw = std::thread::hardware_concurrency();
-        const unsigned n = std::min(hw ? hw : 4u, 8u) - 1;   // plus the calling thread
-        for (unsigned t = 0; t < n; ++t) threads_.emplace_back([this] { worker(); });
-    }
-    void worker()
-    {
-        uint64_t seen = 0;
-        for (;;) {
-            const std::vector<CopyJob>* jobs;
-            unsigned n_parts;
-            {
-                std::unique_lock<std::mutex> lk(mu_);
-                cv_work_.wait(lk, [&] { return stop_ || gen_ != seen; });
-                if (stop_) return;
-                seen = gen_;
-                jobs = jobs_;
-                n_parts = n_parts_;
-            }
-            if (!jobs) continue;
-            unsigned mine = 0;
-            for (unsigned i; (i = next_.fetch_add(1, std::memory_order_relaxed)) < n_parts; ++mine) part(*jobs, i);
-            std::lock_guard<std::mutex> lk(mu_);
-            done_ += mine;
-            if (done_ == n_parts_) cv_done_.notify_all();
-        }
-    }
-    // bytes [i, i + 1) * kPart of the concatenated destinations
-    void part(const std::vector<CopyJob>& jobs, unsigned i) const
-    {
-        const size_t lo = (size_t)i * kPart, hi = std::min(lo + kPart, starts_.back());
-        size_t j = (size_t)(std::upper_bound(starts_.begin(), starts_.end(), lo) - starts_.begin()) - 1;
-        for (; j < jobs.size() && starts_[j] < hi; ++j) {
-            const size_t a = std::max(lo, starts_[j]) - starts_[j], b = std::min(hi, starts_[j + 1]) - starts_[j];
-            if (a >= b) continue;
-            if (jobs[j].pack_xy) pack_xy((const gms_keypoint*)jobs[j].src + a / 8, (b - a) / 8, (float*)((char*)jobs[j].dst + a));
-            else std::memcpy((char*)jobs[j].dst + a, (const char*)jobs[j].src + a, b - a);
-        }
-    }
-    std::vector<std::thread> threads_;
-    std::vector<size_t> starts_;
-    std::mutex mu_;
-    std::condition_variable cv_work_, cv_done_;
-    const std::vector<CopyJob>* jobs_ = nullptr;
-    unsigned n_parts_ = 0, done_ = 0;
-    std::atomic<unsigned> next_{0};
-    uint64_t gen_ = 0;
-    bool stop_ = false;
-};
+// Host-side staging: copy_pool.h (CopyJob, pack_xy, CopyPool)
+using gms::CopyJob;
+using gms::CopyPool;
+using gms::pack_xy;
 
 }  // namespace
 
@@ -894,6 +779,10 @@ int gms_filter_host_batch(gms_ctx* c, const gms_keypoint* kp, const int64_t* fra
     if (!c || n_frames < 0 || n_pairs < 0) return GMS_ERR_BAD_ARG;
     if (n_pairs == 0) return GMS_OK;
     if (!frame_off || !wh || !pairs || !results || n_frames == 0) return GMS_ERR_BAD_ARG;
+    // the frame table starts at keypoint 0 and never decreases (whether kp holds frame_off[n_frames] records is the caller's word)
+    if (frame_off[0] != 0) return GMS_ERR_BAD_ARG;
+    for (int f = 0; f < n_frames; ++f)
+        if (frame_off[f + 1] < frame_off[f]) return GMS_ERR_BAD_ARG;
     const int64_t total_kp = frame_off[n_frames];
     if (total_kp < 0 || (total_kp > 0 && !kp)) return GMS_ERR_BAD_ARG;
     int max_m = 0;

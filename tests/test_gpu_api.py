@@ -207,6 +207,210 @@ def test_host_batch_mixed_sizes_and_a_bad_pair(ctx, pkg, oracle, synth):
     _same(pairs, out, res, wout, wres)
 
 
+# ---- gms_filter_host_batch over many chunks: lanes reused (chunk k rides lane k % 3), the tail iterations of a long list ------------
+_CHUNK_MATCHES, _CHUNK_PAIRS = 2 << 20, 8192   # the cut of gms_filter_host_batch (gms_capi.cpp: kChunkMatches, kChunkPairs)
+
+
+def _host_chunks(m):
+    """The chunks gms_filter_host_batch cuts a pair list into, by its rule: runs of consecutive pairs, at most _CHUNK_PAIRS pairs and
+    _CHUNK_MATCHES matches (a larger pair alone). [(first pair, pairs, matches)]."""
+    chunks, i, m = [], 0, [int(v) for v in m]
+    while i < len(m):
+        first, total = i, 0
+        while i < len(m) and i - first < _CHUNK_PAIRS and (i == first or total + m[i] <= _CHUNK_MATCHES):
+            total += m[i]
+            i += 1
+        chunks.append((first, i - first, total))
+    return chunks
+
+
+def _lay_out(pkg, ms, blocks, rng):
+    """Pair i's match block (a window of blocks[i % len(blocks)]) placed in a shuffled order in the match array."""
+    offs, off = np.zeros(len(ms), dtype=np.int64), 0
+    for i in rng.permutation(len(ms)):
+        offs[i] = off
+        off += ms[i]
+    matches = np.zeros(off, dtype=pkg.DMATCH_DTYPE)
+    for i, m in enumerate(ms):
+        b = blocks[i % len(blocks)]
+        s = int(rng.integers(0, len(b) - m + 1))
+        matches[offs[i]:offs[i] + m] = b[s:s + m]
+    return offs, matches
+
+
+def _fill(rng, total, lo=3000, hi=20000):
+    """Ragged pair sizes in [lo, hi] (a remainder above lo / 2) that add up to exactly `total`."""
+    ms = []
+    while total > hi + lo:
+        ms.append(int(rng.integers(lo, hi + 1)))
+        total -= ms[-1]
+    return ms + ([total // 2, total - total // 2] if total > hi else [total])
+
+
+@pytest.fixture(scope="module")
+def long_list(pkg, synth, oracle):
+    """Default flags, 1280 x 720 frames of 20 000 keypoints, about 12.6 M matches in seven chunks cut by match count. Pair 0 is empty
+    (it opens chunk 0), chunk 1 holds exactly _CHUNK_MATCHES (the inclusive edge of the cut), a pair of chunk 4 -- lane 1, second
+    use -- is outside the parity domain, the last chunk holds one small pair and the empty last pair; match blocks in shuffled
+    order (the host's overlap check sorts). The oracle's answer once for the module."""
+    size, n_kp, n_frames = (1280, 720), 20000, 8
+    frames = synth.make_sequence(61, n_frames, size=size, n_kp=n_kp)
+    rng = np.random.default_rng(61)
+    chunk_ms = [[0] + _fill(rng, _CHUNK_MATCHES - 5000),
+                [n_kp] + _fill(rng, _CHUNK_MATCHES - n_kp),
+                [n_kp] + [1, 2, 5] + _fill(rng, _CHUNK_MATCHES - n_kp - 8 - 777),
+                [n_kp] + _fill(rng, _CHUNK_MATCHES - n_kp - 3000),
+                [n_kp] + _fill(rng, _CHUNK_MATCHES - n_kp - 12000),
+                [n_kp] + _fill(rng, _CHUNK_MATCHES - n_kp - 20),
+                [37, 0]]
+    ms = [m for c in chunk_ms for m in c]
+    blocks = [synth.sequence_matches(6100 + j, n_kp, n_kp, 0.5) for j in range(5)]
+    offs, matches = _lay_out(pkg, ms, blocks, rng)
+    pairs = np.zeros(len(ms), dtype=pkg.PAIR_DTYPE)
+    for i, m in enumerate(ms):
+        a = i % (n_frames - 1)
+        pairs[i] = (a, min(a + 1 + (i // 7) % 2, n_frames - 1), m, 0, offs[i])
+    chunks = _host_chunks(pairs["m"])
+    bad = chunks[4][0] + 3
+    matches["trainIdx"][offs[bad] + 2] = 10 ** 6
+    foff = np.arange(n_frames + 1, dtype=np.int64) * n_kp
+    failed, wout, wres, _ = _oracle_batch(oracle, frames, [size] * n_frames, foff, pairs, matches, False, False)
+    return dict(frames=frames, size=size, foff=foff, pairs=pairs, matches=matches, chunks=chunks, bad=bad, failed=failed, wout=wout,
+                wres=wres)
+
+
+def test_host_batch_long_list_across_chunks(ctx, pkg, long_list):
+    L = long_list
+    pairs, chunks = L["pairs"], L["chunks"]
+    # the layout the test is about, by the library's own rule
+    assert len(chunks) == 7 and all(n < _CHUNK_PAIRS for _, n, _ in chunks)            # cut by match count, lanes 0 1 2 0 1 2 0
+    assert chunks[1][2] == _CHUNK_MATCHES                                                # the inclusive edge
+    assert pairs["m"][0] == 0 and pairs["m"][-1] == 0 and chunks[-1][1:] == (2, 37)
+    assert len(pairs) > 600 and len(L["matches"]) > 12_000_000 and (np.diff(pairs["match_off"]) < 0).any()
+    assert [i for i, (f, n, _) in enumerate(chunks) if f <= L["bad"] < f + n] == [4]
+    assert L["failed"] == 1 and np.flatnonzero(L["wres"]["status"]).tolist() == [L["bad"]] and L["wres"]["status"][L["bad"]] == -2
+    assert (L["wres"]["n_inliers"] > 0).sum() > 600
+    out, res = ctx.filter_host_batch(L["frames"], [L["size"]] * len(L["frames"]), pairs, L["matches"], False, False, 6.0)
+    _same(pairs, out, res, L["wout"], L["wres"])
+
+
+def _oracle_subset(oracle, frames, sizes, foff, pairs, matches, idx, rot, scale):
+    """The oracle on pairs[idx] alone (their match blocks gathered back to back): (failed, out, results, the blocks' offsets)."""
+    sel = pairs[idx].copy()
+    sel["match_off"] = np.concatenate([[0], np.cumsum(sel["m"])[:-1]])
+    m = np.concatenate([matches[o:o + k] for o, k in zip(pairs["match_off"][idx], pairs["m"][idx])])
+    failed, wout, wres, _ = _oracle_batch(oracle, frames, sizes, foff, sel, m, rot, scale)
+    return failed, wout, wres, sel["match_off"]
+
+
+def test_host_batch_pair_count_cut_with_rotation_and_scale(ctx, pkg, oracle, synth):
+    """More than 5 x 8192 pairs of a few dozen matches (every 64th pair 1000): six chunks cut by pair count, empty pairs that open
+    chunks 1 and 2, a pair outside the parity domain in chunk 4, rotation + scale hypotheses. Every pair against the device-resident
+    entry (one launch over the whole list, no chunks, no staging), and a thousand of them -- both sides of every chunk border,
+    the bad pair's neighbours, the tail, a spread sample -- against the oracle (all 42 k: minutes of CPU)."""
+    batch = importlib.import_module("sfm-gms_amd.batch")
+    size, n_kp, n_frames = (1280, 720), 3000, 6
+    frames = synth.make_sequence(62, n_frames, size=size, n_kp=n_kp)
+    rng = np.random.default_rng(62)
+    n_pairs = 5 * _CHUNK_PAIRS + 1234
+    ms = rng.integers(20, 81, n_pairs)
+    ms[::64] = 1000
+    ms[[_CHUNK_PAIRS, 2 * _CHUNK_PAIRS]] = 0
+    blocks = [synth.sequence_matches(6200 + j, n_kp, n_kp, 0.6) for j in range(7)]
+    offs, matches = _lay_out(pkg, ms, blocks, rng)
+    pairs = np.zeros(n_pairs, dtype=pkg.PAIR_DTYPE)
+    a = np.arange(n_pairs) % (n_frames - 1)
+    pairs["frame_a"], pairs["frame_b"], pairs["m"], pairs["match_off"] = a, a + 1, ms, offs
+    chunks = _host_chunks(ms)
+    assert len(chunks) == 6 and [n for _, n, _ in chunks] == [_CHUNK_PAIRS] * 5 + [1234]
+    assert all(t < _CHUNK_MATCHES for _, _, t in chunks) and 2_000_000 < len(matches) < 3_000_000
+    bad = 4 * _CHUNK_PAIRS + 100
+    matches["trainIdx"][offs[bad] + 1] = n_kp
+    out, res = ctx.filter_host_batch(frames, [size] * n_frames, pairs, matches, True, True, 6.0)
+    assert res["status"][bad] == -2 and (np.flatnonzero(res["status"]) == [bad]).all() and (res["n_inliers"] > 0).sum() > 20000
+
+    table = batch.FrameTable(ctx, frames, [size] * n_frames)
+    dout, dres, _ = batch.filter_pairs(ctx, table, pairs, matches, True, True, 6.0, want_mask=False)
+    _same(pairs, out, res, dout, dres)
+
+    near = [i for c in range(1, 6) for i in range(c * _CHUNK_PAIRS - 40, c * _CHUNK_PAIRS + 40)]
+    idx = np.unique(np.r_[near, np.arange(bad - 30, bad + 30), np.arange(n_pairs - 60, n_pairs), np.arange(0, n_pairs, 64)[::4],
+                          rng.choice(n_pairs, 300, replace=False)])
+    failed, wout, wres, woff = _oracle_subset(oracle, frames, [size] * n_frames, table.frame_off_host, pairs, matches, idx, True, True)
+    assert failed == 1 and len(idx) > 900
+    assert res[idx].tobytes() == wres.tobytes()
+    for j, i in enumerate(idx):
+        o, k = int(pairs["match_off"][i]), int(res["n_inliers"][i])
+        assert out[o:o + k].tobytes() == wout[woff[j]:woff[j] + k].tobytes(), i
+
+
+def test_host_batch_tuple_form_reuses_the_callers_arrays(ctx, pkg, oracle, synth, long_list):
+    """(kp_all, frame_off) three times into the same caller-owned out / results, prefilled with a sentinel record: the long list,
+    a short list of other matches with rotation + scale (on a prefix of the frame table), the long list again. Each call gives
+    the oracle's bytes; the first leaves every record it does not own -- behind each pair's survivors, beyond the pairs -- alone."""
+    L = long_list
+    frames, pairs, matches = L["frames"], L["pairs"], L["matches"]
+    kp_all, foff, n_frames = np.concatenate(frames), L["foff"], len(frames)
+    sentinel = np.zeros(1, dtype=pkg.DMATCH_DTYPE)
+    sentinel["queryIdx"], sentinel["trainIdx"], sentinel["imgIdx"], sentinel["distance"] = -7, -8, -9, -1.5
+    rsent = np.zeros(1, dtype=pkg.RESULT_DTYPE)
+    rsent["n_inliers"], rsent["best_scale"], rsent["best_rot"], rsent["status"] = -11, -12, -13, -14
+    out = np.repeat(sentinel, len(matches) + 1000)
+    results = np.repeat(rsent, len(pairs) + 50)
+
+    o, r = ctx.filter_host_batch((kp_all, foff), [L["size"]] * n_frames, pairs, matches, False, False, 6.0, out=out, results=results)
+    assert np.shares_memory(o, out) and np.shares_memory(r, results)
+    _same(pairs, out, results[:len(pairs)], L["wout"], L["wres"])
+    written = np.zeros(len(out), dtype=bool)
+    for off, k in zip(pairs["match_off"], results["n_inliers"][:len(pairs)]):
+        written[off:off + k] = True
+    rows = out.view(np.uint8).reshape(-1, 16)
+    assert (rows[~written] == np.frombuffer(sentinel.tobytes(), np.uint8)).all()
+    assert results[len(pairs):].tobytes() == np.repeat(rsent, 50).tobytes()
+
+    # a short list: two chunks, other matches, rotation + scale, the first five frames of the same table (a prefix: legal)
+    use, n_kp = 5, len(frames[0])
+    rng = np.random.default_rng(63)
+    ms2 = [int(v) for v in rng.integers(2000, n_kp + 1, 200)]
+    blocks = [synth.sequence_matches(6300 + j, n_kp, n_kp, 0.6) for j in range(3)]
+    offs2, matches2 = _lay_out(pkg, ms2, blocks, rng)
+    pairs2 = np.zeros(len(ms2), dtype=pkg.PAIR_DTYPE)
+    for i, m in enumerate(ms2):
+        pairs2[i] = (i % (use - 1), i % (use - 1) + 1, m, 0, offs2[i])
+    assert len(_host_chunks(ms2)) == 2
+    failed, wout2, wres2, _ = _oracle_batch(oracle, frames[:use], [L["size"]] * use, foff[:use + 1], pairs2, matches2, True, True)
+    assert failed == 0 and (wres2["n_inliers"] > 0).mean() > 0.9
+    ctx.filter_host_batch((kp_all, foff[:use + 1]), [L["size"]] * use, pairs2, matches2, True, True, 6.0, out=out, results=results)
+    _same(pairs2, out, results[:len(pairs2)], wout2, wres2)
+
+    ctx.filter_host_batch((kp_all, foff), [L["size"]] * n_frames, pairs, matches, False, False, 6.0, out=out, results=results)
+    _same(pairs, out, results[:len(pairs)], L["wout"], L["wres"])
+    assert results[len(pairs):].tobytes() == np.repeat(rsent, 50).tobytes()
+
+
+def test_host_batch_frame_off_is_validated(ctx, pkg, synth):
+    """The tuple form's frame table: ValueError for offsets that decrease, do not start at 0, run past the keypoints or miss a frame.
+    The C entry refuses the first two itself (GMS_ERR_BAD_ARG) before it copies or launches anything, results untouched."""
+    size = (640, 480)
+    frames, pairs, matches = _sequence(pkg, synth, 3, 500, 4, 64, size, ragged=False)
+    kp_all = np.concatenate(frames)
+    for foff in ([0, 600, 400, 1500], [5, 500, 1000, 1500], [0, 500, 1000, 1501], [0, 500, 1500], [0, 500, 1000, 1500, 1500]):
+        with pytest.raises(ValueError):
+            ctx.filter_host_batch((kp_all, np.array(foff)), [size] * 3, pairs, matches, False, False, 6.0)
+    out, res = ctx.filter_host_batch((kp_all, np.array([0, 500, 1000, 1500])), [size] * 3, pairs, matches, False, False, 6.0)
+    assert (res["status"] == 0).all() and res["n_inliers"].sum() > 0
+    lib = pkg.load_library()
+    wh = np.array([size] * 3, dtype=np.int32)
+    for foff in ([0, 600, 400, 1500], [5, 500, 1000, 1500]):
+        foff = np.array(foff, dtype=np.int64)
+        out = np.zeros(len(matches), dtype=pkg.DMATCH_DTYPE)
+        results = np.full(len(pairs) * 4, -5, dtype=np.int32).view(pkg.RESULT_DTYPE)
+        before = results.tobytes()
+        rc = lib.gms_filter_host_batch(ctx._h, kp_all.ctypes.data, foff.ctypes.data, wh.ctypes.data, 3, pairs.ctypes.data, len(pairs),
+                                       matches.ctypes.data, 0, 0, 6.0, out.ctypes.data, results.ctypes.data)
+        assert rc == -1 and results.tobytes() == before and not out.view(np.uint8).any()
+
+
 # ---- large batches filtered in slices of the workspace budget (GMS_BAND_WS_BYTES is read once per process) ----------------
 _SLICE_WORKER = r'''
 import importlib, sys

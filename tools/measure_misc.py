@@ -81,7 +81,7 @@ def main():
     gpu = timeit(lambda: ctx.match(c["size1"], c["size2"], c["kp1"], c["kp2"], c["matches"]), 3)
     cpu = timeit(lambda: gms_oracle.match(c["size1"], c["size2"], c["kp1"], c["kp2"], c["matches"]), 2)
     out["per_pixel_2594x1131_2.93M_default_flags"] = {"gpu_call_ms_incl_pcie": gpu * 1e3, "cpu_oracle_ms_1thread": cpu * 1e3}
-    # ---- the host-pointer batch entry (pinned staging, two streams): 2048 pairs x 10k matches from host memory
+    # ---- the host-pointer batch entry (pinned staging, three lanes): 2048 pairs x 10k matches from host memory
     size, n_frames, n_kp, n_pairs = (1920, 1080), 72, 10000, 2048
     frames = synth.make_sequence(1000, n_frames, size=size, n_kp=n_kp)
     pairs = dist.pair_table(n_frames, 0, n_pairs, n_kp)
