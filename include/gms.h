@@ -538,6 +538,61 @@ int gms_stereo_bm_normalize_device(gms_ctx* ctx, const int16_t* d_disp16, int n,
 int gms_stereo_bm(const gms_stereo_bm_params* params, const uint8_t* left, const uint8_t* right, int width, int height, int pitch,
                   int16_t* disp16, int32_t* cost, uint8_t* disp8);
 
+/* ---- Portrait mode: the image tail of the reference's createPortraitMode (DisparityUtil.cpp:317-412) -----------------
+ *     disparity 255 -> 0; threshold(60); dilate(3 x 3, 2 iterations, BORDER_REPLICATE); findContours(RETR_LIST, CHAIN_APPROX_NONE);
+ *     the 5 borders of largest |contourArea|, drawContours(FILLED); medianBlur(image, 15); the photograph's own pixels back where a
+ *     filled border covers them, except in the last three rows and columns
+ * restated in tests/portrait_ref.py (OpenCV parity is unpinned; the choices are in DESIGN.md §4.9). Borders: Suzuki-Abe, set pixels
+ * 8-connected, every outer and every hole border; ranked by the doubled shoelace area of the chain, equal areas by the raster order of
+ * the border's start pixel, outer before hole (this project's rule, not the reference's); fewer than num_contours borders = all of
+ * them. A border's fill is its chain and what the chain encloses, even-odd. The median is the exact (ksize^2 / 2)-th smallest per
+ * channel, border replicated.
+ * Accepted (others: GMS_ERR_BAD_ARG): threshold 0..255, dilate_iterations 0..8, num_contours 1..64, median_ksize odd in 3..31, width
+ * and height 1..8192 (smaller than the window is legal), n 1..65535.
+ * Images: 8-bit BGR, pixel (x, y) of image i at d_bgr + (i * height + y) * pitch_bgr + 3 x (pitch_bgr >= 3 width); disparity maps:
+ * 8-bit, 255 = no value, row y of map i at d_disparity + (i * height + y) * pitch_disp (pitch_disp >= width). Outputs are dense:
+ * d_out_bgr and d_blurred [n][height][width][3]; d_mask (the dilated mask, 0 / 255) and d_selected (255 where a chosen border's fill
+ * covers the pixel, else 0) [n][height][width]. */
+#define GMS_PORTRAIT_MAX_SIDE 8192
+#define GMS_PORTRAIT_STAGES   9
+typedef struct gms_portrait_params {
+    int32_t threshold;
+    int32_t dilate_iterations;
+    int32_t num_contours;
+    int32_t median_ksize;
+} gms_portrait_params;
+/* The reference's values (DisparityUtil.cpp:341, :351, :380, :394); a NULL params pointer means the same. */
+#define GMS_PORTRAIT_PARAMS_REFERENCE {60, 2, 5, 15}
+
+/* gms_portrait_workspace_bytes: the workspace of gms_portrait_device (256-byte aligned pointer); 0 for arguments it rejects. With
+ *   px = n * width * height and up(x) = x rounded up to 256: 4 up(px) + up(4 px) + up(8 px) + up(8 n height ((width + 1) / 2)) +
+ *   up(264 n) bytes (mask, neighbour codes, frame flags and selection, a byte each; labels, int32; even-odd toggles, one bit per
+ *   chosen border; one 64-bit rank key per border; the chosen borders).
+ * gms_portrait_device: n images on the context's stream; no allocation, no synchronisation, no readback (graph-capturable). d_mask,
+ *   d_selected and d_blurred may each be NULL; without d_blurred the blurred image never goes to memory on its own. Cost: every
+ *   border is walked by one lane, a dependent byte load per step, so the call's time grows with the longest chain; a ragged mask
+ *   that is one component can have a chain of the order of the pixel count (measured figures: DESIGN.md §4.9).
+ * gms_portrait_profile_device: a diagnostic, NOT capturable: the same launches with a device event between them, then a
+ *   synchronisation; stage_ms (host, GMS_PORTRAIT_STAGES floats) receives the time of each kernel in launch order: mask, init, merge,
+ *   flatten, area, select, trace, fill, median. tools/portrait_bench.py reads its per-kernel times here.
+ * gms_median_blur_device: medianBlur of n images of 1 or 3 interleaved channels; source and destination rows both `pitch` bytes
+ *   apart (pitch >= channels * width), image i at i * height * pitch. d_dst must not overlap d_src (tiles read their neighbours'
+ *   pixels while others write): overlapping ranges are GMS_ERR_BAD_ARG.
+ * gms_median_blur: ONE image on host pointers (dense rows), synchronous, on the current HIP device.
+ * gms_portrait: ONE image on host pointers (dense rows), synchronous, on the current HIP device; mask / selected / blurred optional. */
+size_t gms_portrait_workspace_bytes(int width, int height, int n, const gms_portrait_params* params);
+int gms_portrait_device(gms_ctx* ctx, const gms_portrait_params* params, const uint8_t* d_bgr, const uint8_t* d_disparity, int n,
+                        int width, int height, int pitch_bgr, int pitch_disp, void* d_ws, size_t ws_bytes, uint8_t* d_out_bgr,
+                        uint8_t* d_mask, uint8_t* d_selected, uint8_t* d_blurred);
+int gms_median_blur_device(gms_ctx* ctx, const uint8_t* d_src, int n, int width, int height, int channels, int pitch, int ksize,
+                           uint8_t* d_dst);
+int gms_portrait_profile_device(gms_ctx* ctx, const gms_portrait_params* params, const uint8_t* d_bgr, const uint8_t* d_disparity, int n,
+                                int width, int height, int pitch_bgr, int pitch_disp, void* d_ws, size_t ws_bytes, uint8_t* d_out_bgr,
+                                uint8_t* d_mask, uint8_t* d_selected, uint8_t* d_blurred, float* stage_ms);
+int gms_median_blur(const uint8_t* src, int width, int height, int channels, int ksize, uint8_t* dst);
+int gms_portrait(const gms_portrait_params* params, const uint8_t* bgr, const uint8_t* disparity, int width, int height,
+                 uint8_t* out_bgr, uint8_t* mask, uint8_t* selected, uint8_t* blurred);
+
 const char* gms_error_string(int code);
 const char* gms_version(void);
 

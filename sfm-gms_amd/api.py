@@ -13,7 +13,7 @@ import numpy as np
 
 from .capi import load_library
 from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_DESC_HAMMING256, KEYPOINT_DTYPE, PAIR_DTYPE, RESULT_DTYPE, GMS_OK, GMS_ERR_CAPACITY,
-                    GmsError, stereo_bm_params)
+                    GmsError, portrait_params, stereo_bm_params)
 
 
 def _as(arr, dtype, name):
@@ -294,6 +294,35 @@ class GmsContext:
         _check(self._lib.gms_stereo_bm_normalize_device(self._h, d_disp16, int(n), int(width), int(height), d_out8), self._lib,
                "gms_stereo_bm_normalize_device")
 
+    # -- portrait mode (DisparityUtil.cpp:317-412; batch.portrait_batch drives these) ---------------------------------------------
+    def portrait_workspace_bytes(self, width, height, n, params=None):
+        return int(self._lib.gms_portrait_workspace_bytes(int(width), int(height), int(n), portrait_params(params).ctypes.data))
+
+    def portrait_device(self, params, d_bgr, d_disparity, n, width, height, pitch_bgr, pitch_disp, d_ws, ws_bytes, d_out_bgr,
+                        d_mask=None, d_selected=None, d_blurred=None):
+        """gms_portrait_device; params: None (the reference's), a dict or a PORTRAIT_PARAMS_DTYPE record. Stream-ordered."""
+        rec = portrait_params(params)
+        _check(self._lib.gms_portrait_device(self._h, rec.ctypes.data, d_bgr, d_disparity, int(n), int(width), int(height),
+                                             int(pitch_bgr), int(pitch_disp), d_ws, int(ws_bytes), d_out_bgr, d_mask or None,
+                                             d_selected or None, d_blurred or None), self._lib, "gms_portrait_device")
+
+    PORTRAIT_STAGES = ("mask", "init", "merge", "flatten", "area", "select", "trace", "fill", "median")
+
+    def portrait_profile_device(self, params, d_bgr, d_disparity, n, width, height, pitch_bgr, pitch_disp, d_ws, ws_bytes, d_out_bgr,
+                                d_mask=None, d_selected=None, d_blurred=None):
+        """gms_portrait_profile_device (a diagnostic; synchronises): the time of each kernel in ms, in PORTRAIT_STAGES' order."""
+        rec = portrait_params(params)
+        ms = np.zeros(len(self.PORTRAIT_STAGES), np.float32)
+        _check(self._lib.gms_portrait_profile_device(self._h, rec.ctypes.data, d_bgr, d_disparity, int(n), int(width), int(height),
+                                                     int(pitch_bgr), int(pitch_disp), d_ws, int(ws_bytes), d_out_bgr, d_mask or None,
+                                                     d_selected or None, d_blurred or None, ms.ctypes.data), self._lib,
+               "gms_portrait_profile_device")
+        return ms
+
+    def median_blur_device(self, d_src, n, width, height, channels, pitch, ksize, d_dst):
+        _check(self._lib.gms_median_blur_device(self._h, d_src, int(n), int(width), int(height), int(channels), int(pitch), int(ksize),
+                                                d_dst), self._lib, "gms_median_blur_device")
+
     def selftest_five_point(self, x1, x2):
         """gms_selftest_five_point: x1, x2 [n_samples, 5, 2] normalised points -> list of [k, 3, 3] model arrays, one per sample."""
         x1 = np.asarray(x1, dtype=np.float64).reshape(-1, 5, 2)
@@ -415,3 +444,39 @@ def stereo_match(left, right, **params):
     """The reference's stereo_match (DisparityUtil.cpp:22-49): StereoBM with its parameters, normalize(NORM_MINMAX, 0..255, CV_8U),
     every 0 -> 255. Returns the uint8 map."""
     return _stereo_bm(left, right, params, False, False, True)[2]
+
+
+def portraitMode(image_bgr, disparity, detail=False, **params):
+    """The image tail of the reference's createPortraitMode (DisparityUtil.cpp:317-412) on the GPU: image_bgr uint8 [H, W, 3],
+    disparity uint8 [H, W] (255 = no value; what gms_disparity_device or stereo_match write) -> the portrait image uint8 [H, W, 3]:
+    the photograph where one of the num_contours largest borders of the thresholded, dilated map covers it, its median blur
+    elsewhere. Parameters by keyword (threshold, dilate_iterations, num_contours, median_ksize), the reference's 60, 2, 5, 15 by
+    default; tests/portrait_ref.py states every step. detail=True: (out, mask, selected, blurred)."""
+    lib = load_library()
+    img = np.ascontiguousarray(image_bgr, dtype=np.uint8)
+    disp = np.ascontiguousarray(disparity, dtype=np.uint8)
+    if img.ndim != 3 or img.shape[2] != 3 or disp.shape != img.shape[:2]:
+        raise ValueError("image_bgr: uint8 [H, W, 3]; disparity: uint8 [H, W] of the same size")
+    h, w = disp.shape
+    rec = portrait_params(params)
+    out = np.zeros((h, w, 3), np.uint8)
+    mask, sel, blur = (np.zeros((h, w), np.uint8), np.zeros((h, w), np.uint8), np.zeros((h, w, 3), np.uint8)) if detail else (None,) * 3
+    rc = lib.gms_portrait(rec.ctypes.data, img.ctypes.data, disp.ctypes.data, w, h, out.ctypes.data,
+                          None if mask is None else mask.ctypes.data, None if sel is None else sel.ctypes.data,
+                          None if blur is None else blur.ctypes.data)
+    _check(rc, lib, "gms_portrait")
+    return (out, mask, sel, blur) if detail else out
+
+
+def medianBlur(image, ksize):
+    """cv::medianBlur(image, ksize) on the GPU (gms_median_blur): image uint8 [H, W] or [H, W, 3], ksize odd in 3..31, border
+    replicated."""
+    lib = load_library()
+    img = np.ascontiguousarray(image, dtype=np.uint8)
+    if img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] not in (1, 3)) or img.size == 0:
+        raise ValueError("image: uint8 [H, W], [H, W, 1] or [H, W, 3]")
+    h, w = img.shape[:2]
+    out = np.zeros_like(img)
+    _check(lib.gms_median_blur(img.ctypes.data, w, h, 1 if img.ndim == 2 else img.shape[2], int(ksize), out.ctypes.data), lib,
+           "gms_median_blur")
+    return out

@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from .api import GmsContext
-from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_ERR_CAPACITY, KEYPOINT_DTYPE, LOGOS_RESULT_DTYPE, stereo_bm_params,
+from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_ERR_CAPACITY, KEYPOINT_DTYPE, LOGOS_RESULT_DTYPE, portrait_params, stereo_bm_params,
                     PAIR_DTYPE, RESULT_DTYPE)
 
 
@@ -438,6 +438,60 @@ def stereo_bm_batch(lefts, rights, params=None, ctx=None, return_cost=False, eig
     run.run(dl, dr, eight_bit)
     ctx.synchronize()
     outs = [run.d_disp[:n]] + ([run.d_cost[:n]] if return_cost else []) + ([run.d_out8[:n]] if eight_bit else [])
+    if not on_dev:
+        outs = [o.cpu().numpy() for o in outs]
+    return outs[0] if len(outs) == 1 else tuple(outs)
+
+
+class Portrait:
+    """Device buffers of gms_portrait_device for n images of one size: workspace, portrait images and (with detail) the dilated masks,
+    the selections and the blurred images, sized once, so that run() can be replayed (or captured into a graph) on new images in the
+    same tensors."""
+
+    def __init__(self, ctx, n, width, height, params=None, device="cuda:0", detail=True):
+        self.ctx, self.n, self.width, self.height = ctx, int(n), int(width), int(height)
+        self.params = portrait_params(params)
+        dev = torch.device(device)
+        self.ws_bytes = ctx.portrait_workspace_bytes(width, height, n, self.params)
+        if self.ws_bytes == 0:
+            raise ValueError("Portrait: parameters, image size or batch size rejected (include/gms.h)")
+        self.d_ws = torch.zeros(self.ws_bytes, dtype=torch.uint8, device=dev)
+        self.d_out = torch.zeros((self.n, self.height, self.width, 3), dtype=torch.uint8, device=dev)
+        self.d_mask = torch.zeros((self.n, self.height, self.width), dtype=torch.uint8, device=dev) if detail else None
+        self.d_selected = torch.zeros((self.n, self.height, self.width), dtype=torch.uint8, device=dev) if detail else None
+        self.d_blurred = torch.zeros((self.n, self.height, self.width, 3), dtype=torch.uint8, device=dev) if detail else None
+        torch.cuda.synchronize(dev)
+
+    def run(self, d_bgr, d_disparity):
+        """d_bgr: uint8 device tensor [n, height, width, 3]; d_disparity: [n, height, width] (both contiguous). Stream-ordered on the
+        context's stream."""
+        for t, shape in ((d_bgr, (self.n, self.height, self.width, 3)), (d_disparity, (self.n, self.height, self.width))):
+            if t.dtype != torch.uint8 or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("images [n, height, width, 3] and disparities [n, height, width]: contiguous uint8 device tensors")
+        opt = [t.data_ptr() if t is not None else None for t in (self.d_mask, self.d_selected, self.d_blurred)]
+        self.ctx.portrait_device(self.params, d_bgr.data_ptr(), d_disparity.data_ptr(), self.n, self.width, self.height, 3 * self.width,
+                                 self.width, self.d_ws.data_ptr(), self.ws_bytes, self.d_out.data_ptr(), *opt)
+
+
+def portrait_batch(images, disparities, params=None, ctx=None, detail=False):
+    """Portrait mode for n images in one gms_portrait_device run. images: uint8 [n, H, W, 3] (BGR); disparities: uint8 [n, H, W], 255 =
+    no value; host arrays or device tensors. Returns the portrait images [n, H, W, 3] (numpy for host input, device tensors for device
+    input); with detail=True (out, mask, selected, blurred)."""
+    from .api import default_context
+    ctx = ctx or default_context()
+    on_dev = isinstance(images, torch.Tensor)
+    if on_dev:
+        di, dd = images.contiguous(), disparities.contiguous()
+    else:
+        im, dp = np.ascontiguousarray(images, dtype=np.uint8), np.ascontiguousarray(disparities, dtype=np.uint8)
+        if im.ndim != 4 or im.shape[3] != 3 or dp.shape != im.shape[:3]:
+            raise ValueError("images: uint8 [n, H, W, 3]; disparities: uint8 [n, H, W]")
+        di, dd = torch.from_numpy(im).cuda(), torch.from_numpy(dp).cuda()
+    n, h, w = dd.shape
+    run = Portrait(ctx, n, w, h, params, di.device, detail=detail)
+    run.run(di, dd)
+    ctx.synchronize()
+    outs = [run.d_out] + ([run.d_mask, run.d_selected, run.d_blurred] if detail else [])
     if not on_dev:
         outs = [o.cpu().numpy() for o in outs]
     return outs[0] if len(outs) == 1 else tuple(outs)

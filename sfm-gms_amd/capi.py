@@ -17,7 +17,8 @@ EXPORTED_SYMBOLS = [
     "gms_logos_table_bytes", "gms_logos_workspace_bytes", "gms_logos_prepare_device", "gms_logos_filter_device", "gms_logos_words_device",
     "gms_logos_host_batch", "gms_bf_select_workspace_bytes", "gms_bf_select_device", "gms_bf_match_select",
     "gms_bf_select_host_batch", "gms_stereo_bm_workspace_bytes", "gms_stereo_bm_device", "gms_stereo_bm_normalize_device",
-    "gms_stereo_bm",
+    "gms_stereo_bm", "gms_portrait_workspace_bytes", "gms_portrait_device", "gms_median_blur_device", "gms_portrait",
+    "gms_portrait_profile_device", "gms_median_blur",
 ]
 
 _lib = None
@@ -92,6 +93,12 @@ def load_library():
     lib.gms_stereo_bm_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, C.c_size_t, vp, vp]
     lib.gms_stereo_bm_normalize_device.argtypes = [vp, vp, i32, i32, i32, vp]
     lib.gms_stereo_bm.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    lib.gms_portrait_workspace_bytes.argtypes = [i32, i32, i32, vp]
+    lib.gms_portrait_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp]
+    lib.gms_median_blur_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    lib.gms_portrait.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    lib.gms_portrait_profile_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    lib.gms_median_blur.argtypes = [vp, i32, i32, i32, i32, vp]
     lib.gms_max_matches.argtypes = []
     lib.gms_last_hip_error.argtypes = []
     lib.gms_error_string.argtypes = [i32]
@@ -109,6 +116,7 @@ def load_library():
     lib.gms_logos_workspace_bytes.restype = C.c_size_t
     lib.gms_bf_select_workspace_bytes.restype = C.c_size_t
     lib.gms_stereo_bm_workspace_bytes.restype = C.c_size_t
+    lib.gms_portrait_workspace_bytes.restype = C.c_size_t
     lib.gms_dataset_free.restype = None
     lib.gms_frame_table_bytes.argtypes = [i64]
     lib.gms_frame_table_bytes.restype = i64

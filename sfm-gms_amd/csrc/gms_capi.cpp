@@ -22,6 +22,7 @@
 #include "gms.h"
 #include "gms_kernels.h"
 #include "logos_batch.h"
+#include "portrait_core.h"
 #include "stereo_bm_core.h"
 #include "twoview_core.h"
 
@@ -1190,6 +1191,125 @@ int gms_stereo_bm(const gms_stereo_bm_params* params, const uint8_t* left, const
     if (e == hipSuccess && disp16) e = hipMemcpyAsync(disp16, d_disp, 2 * px, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && cost) e = hipMemcpyAsync(cost, d + o_c, 4 * px, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && disp8) e = hipMemcpyAsync(disp8, d + o_8, px, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    else (void)hipStreamSynchronize(st);
+    (void)hipFree(blk);
+    GMS_HIP(e);
+    return GMS_OK;
+}
+
+// ---- portrait mode (portrait_kernels.hip) --------------------------------------------------------------------------
+static const gms_portrait_params& pm_params(const gms_portrait_params* p)
+{
+    static const gms_portrait_params ref = GMS_PORTRAIT_PARAMS_REFERENCE;
+    return p ? *p : ref;
+}
+
+size_t gms_portrait_workspace_bytes(int width, int height, int n, const gms_portrait_params* params)
+{
+    if (n < 1 || n > 65535 || !pm::params_ok(pm_params(params), width, height)) return 0;
+    return gms::portrait_ws_bytes(n, width, height);
+}
+
+int gms_portrait_device(gms_ctx* c, const gms_portrait_params* params, const uint8_t* d_bgr, const uint8_t* d_disparity, int n, int width,
+                        int height, int pitch_bgr, int pitch_disp, void* d_ws, size_t ws_bytes, uint8_t* d_out_bgr, uint8_t* d_mask,
+                        uint8_t* d_selected, uint8_t* d_blurred)
+{
+    const gms_portrait_params& p = pm_params(params);
+    if (!c || n < 1 || n > 65535 || !pm::params_ok(p, width, height) || pitch_bgr < 3 * width || pitch_disp < width) return GMS_ERR_BAD_ARG;
+    if (!d_bgr || !d_disparity || !d_ws || !d_out_bgr || (reinterpret_cast<uintptr_t>(d_ws) & 255u) ||
+        ws_bytes < gms::portrait_ws_bytes(n, width, height))
+        return GMS_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(c->mu);
+    GMS_HIP(hipSetDevice(c->device));
+    GMS_HIP(gms::launch_portrait(p, d_bgr, d_disparity, n, width, height, pitch_bgr, pitch_disp, d_ws, d_out_bgr, d_mask, d_selected,
+                                 d_blurred, c->stream));
+    return GMS_OK;
+}
+
+int gms_portrait_profile_device(gms_ctx* c, const gms_portrait_params* params, const uint8_t* d_bgr, const uint8_t* d_disparity, int n,
+                                int width, int height, int pitch_bgr, int pitch_disp, void* d_ws, size_t ws_bytes, uint8_t* d_out_bgr,
+                                uint8_t* d_mask, uint8_t* d_selected, uint8_t* d_blurred, float* stage_ms)
+{
+    const gms_portrait_params& p = pm_params(params);
+    if (!c || !stage_ms || n < 1 || n > 65535 || !pm::params_ok(p, width, height) || pitch_bgr < 3 * width || pitch_disp < width)
+        return GMS_ERR_BAD_ARG;
+    if (!d_bgr || !d_disparity || !d_ws || !d_out_bgr || (reinterpret_cast<uintptr_t>(d_ws) & 255u) ||
+        ws_bytes < gms::portrait_ws_bytes(n, width, height))
+        return GMS_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(c->mu);
+    GMS_HIP(hipSetDevice(c->device));
+    hipEvent_t ev[GMS_PORTRAIT_STAGES + 1] = {};
+    hipError_t e = hipSuccess;
+    for (int i = 0; i <= GMS_PORTRAIT_STAGES && e == hipSuccess; i++) e = hipEventCreate(&ev[i]);
+    if (e == hipSuccess)
+        e = gms::launch_portrait(p, d_bgr, d_disparity, n, width, height, pitch_bgr, pitch_disp, d_ws, d_out_bgr, d_mask, d_selected,
+                                 d_blurred, c->stream, ev);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    for (int i = 0; i < GMS_PORTRAIT_STAGES && e == hipSuccess; i++) e = hipEventElapsedTime(&stage_ms[i], ev[i], ev[i + 1]);
+    for (int i = 0; i <= GMS_PORTRAIT_STAGES; i++)
+        if (ev[i]) (void)hipEventDestroy(ev[i]);
+    GMS_HIP(e);
+    return GMS_OK;
+}
+
+int gms_median_blur_device(gms_ctx* c, const uint8_t* d_src, int n, int width, int height, int channels, int pitch, int ksize,
+                           uint8_t* d_dst)
+{
+    if (!c || n < 1 || n > 65535 || !pm::median_ok(width, height, channels, ksize) || pitch < channels * width || !d_src || !d_dst)
+        return GMS_ERR_BAD_ARG;
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
+    const uintptr_t span = (uintptr_t)n * (uintptr_t)height * (uintptr_t)pitch;
+    if (s0 < d0 + span && d0 < s0 + span) return GMS_ERR_BAD_ARG;  // the destination may not overlap the source
+    std::lock_guard<std::mutex> lock(c->mu);
+    GMS_HIP(hipSetDevice(c->device));
+    GMS_HIP(gms::launch_median_blur(d_src, n, width, height, channels, pitch, ksize, d_dst, c->stream));
+    return GMS_OK;
+}
+
+int gms_median_blur(const uint8_t* src, int width, int height, int channels, int ksize, uint8_t* dst)
+{
+    if (!pm::median_ok(width, height, channels, ksize) || !src || !dst) return GMS_ERR_BAD_ARG;
+    const size_t bytes = (size_t)width * (size_t)height * (size_t)channels, o_dst = (bytes + 255) / 256 * 256;
+    void* blk = nullptr;
+    GMS_HIP(hipMalloc(&blk, o_dst + bytes));
+    uint8_t* d = static_cast<uint8_t*>(blk);
+    hipStream_t st = nullptr;
+    hipError_t e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = gms::launch_median_blur(d, 1, width, height, channels, width * channels, ksize, d + o_dst, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dst, d + o_dst, bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    else (void)hipStreamSynchronize(st);
+    (void)hipFree(blk);
+    GMS_HIP(e);
+    return GMS_OK;
+}
+
+int gms_portrait(const gms_portrait_params* params, const uint8_t* bgr, const uint8_t* disparity, int width, int height, uint8_t* out_bgr,
+                 uint8_t* mask, uint8_t* selected, uint8_t* blurred)
+{
+    const gms_portrait_params& p = pm_params(params);
+    if (!pm::params_ok(p, width, height) || !bgr || !disparity || !out_bgr) return GMS_ERR_BAD_ARG;
+    const size_t px = (size_t)width * (size_t)height;
+    const size_t a = 256;
+    auto up = [&](size_t x) { return (x + a - 1) / a * a; };
+    // one block: image | disparity | workspace | portrait | mask | selected | blurred
+    const size_t o_d = up(3 * px), o_ws = up(o_d + px), o_out = o_ws + up(gms::portrait_ws_bytes(1, width, height));
+    const size_t o_m = up(o_out + 3 * px), o_s = up(o_m + px), o_b = up(o_s + px), bytes = o_b + 3 * px;
+    void* blk = nullptr;
+    GMS_HIP(hipMalloc(&blk, bytes));
+    uint8_t* d = static_cast<uint8_t*>(blk);
+    hipStream_t st = nullptr;
+    hipError_t e = hipMemcpyAsync(d, bgr, 3 * px, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_d, disparity, px, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = gms::launch_portrait(p, d, d + o_d, 1, width, height, 3 * width, width, d + o_ws, d + o_out, mask ? d + o_m : nullptr,
+                                 selected ? d + o_s : nullptr, blurred ? d + o_b : nullptr, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_bgr, d + o_out, 3 * px, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && mask) e = hipMemcpyAsync(mask, d + o_m, px, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && selected) e = hipMemcpyAsync(selected, d + o_s, px, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && blurred) e = hipMemcpyAsync(blurred, d + o_b, 3 * px, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     else (void)hipStreamSynchronize(st);
     (void)hipFree(blk);

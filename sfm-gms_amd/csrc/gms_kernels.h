@@ -152,6 +152,13 @@ size_t     stereo_bm_ws_bytes(int n, int W, int H);
 hipError_t launch_stereo_bm(const gms_stereo_bm_params& p, const uint8_t* d_left, const uint8_t* d_right, int n, int W, int H, int pitch,
                             void* d_ws, int16_t* d_disp, int32_t* d_cost, hipStream_t stream);
 hipError_t launch_stereo_bm_normalize(const int16_t* d_disp, int n, int W, int H, uint8_t* d_out, hipStream_t stream);
+// portrait mode (portrait_kernels.hip; shared parts in portrait_core.h)
+size_t     portrait_ws_bytes(int n, int W, int H);
+hipError_t launch_portrait(const gms_portrait_params& p, const uint8_t* d_bgr, const uint8_t* d_disp, int n, int W, int H, int pitch_bgr,
+                           int pitch_disp, void* d_ws, uint8_t* d_out, uint8_t* d_mask, uint8_t* d_selected, uint8_t* d_blurred,
+                           hipStream_t stream, hipEvent_t* stage_events = nullptr);
+hipError_t launch_median_blur(const uint8_t* d_src, int n, int W, int H, int channels, int pitch, int ksize, uint8_t* d_dst,
+                              hipStream_t stream);
 hipError_t launch_threshold(const int32_t* d_T, const int32_t* d_n, const int32_t* d_score, double factor,
                             int count, uint8_t* d_out, hipStream_t stream);
 

@@ -355,4 +355,39 @@ inline void stereo_match(const std::vector<uint8_t>& left, const std::vector<uin
     stereo_match(left, right, width, height, stereo_bm_reference_params(), disparity8);
 }
 
+// The image tail of the reference's createPortraitMode (DisparityUtil.cpp:317-412): img = the photograph as flat row-major BGR bytes
+// (3 * width * height, cv::Mat's layout after imread), disparity = an 8-bit map with 255 = no value (what gms_disparity_device and
+// stereo_match write); out receives the portrait image in img's layout. medianBlur is cv::medianBlur for 1 or 3 interleaved channels
+// (ksize odd in 3..31). Both run one image synchronously on the current HIP device (gms_portrait, gms_median_blur).
+inline gms_portrait_params portrait_reference_params()
+{
+    const gms_portrait_params p = GMS_PORTRAIT_PARAMS_REFERENCE;
+    return p;
+}
+
+inline void createPortraitMode(const std::vector<uint8_t>& img, const std::vector<uint8_t>& disparity, int width, int height,
+                               const gms_portrait_params& params, std::vector<uint8_t>& out)
+{
+    if (width <= 0 || height <= 0 || disparity.size() != (size_t)width * (size_t)height || img.size() != 3 * disparity.size())
+        throw std::invalid_argument("mi355::createPortraitMode: a 3 * width * height BGR image and a width * height disparity map");
+    out.assign(img.size(), 0);
+    const int rc = gms_portrait(&params, img.data(), disparity.data(), width, height, out.data(), nullptr, nullptr, nullptr);
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::createPortraitMode: ") + gms_error_string(rc));
+}
+
+inline void createPortraitMode(const std::vector<uint8_t>& img, const std::vector<uint8_t>& disparity, int width, int height,
+                               std::vector<uint8_t>& out)
+{
+    createPortraitMode(img, disparity, width, height, portrait_reference_params(), out);
+}
+
+inline void medianBlur(const std::vector<uint8_t>& src, int width, int height, int channels, int ksize, std::vector<uint8_t>& dst)
+{
+    if (width <= 0 || height <= 0 || (channels != 1 && channels != 3) || src.size() != (size_t)width * (size_t)height * (size_t)channels)
+        throw std::invalid_argument("mi355::medianBlur: a width * height image of 1 or 3 interleaved channels");
+    dst.assign(src.size(), 0);
+    const int rc = gms_median_blur(src.data(), width, height, channels, ksize, dst.data());
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::medianBlur: ") + gms_error_string(rc));
+}
+
 }  // namespace mi355

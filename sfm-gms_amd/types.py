@@ -45,6 +45,27 @@ def stereo_bm_params(params=None, **kw):
     return rec
 
 
+# gms_portrait_params (include/gms.h): portrait mode's parameters, four int32 in this order; the reference's values
+# (DisparityUtil.cpp:341, :351, :380, :394)
+PORTRAIT_PARAMS_DTYPE = np.dtype([(n, "<i4") for n in ("threshold", "dilate_iterations", "num_contours", "median_ksize")])
+assert PORTRAIT_PARAMS_DTYPE.itemsize == 16
+PORTRAIT_REFERENCE = dict(threshold=60, dilate_iterations=2, num_contours=5, median_ksize=15)
+
+
+def portrait_params(params=None, **kw):
+    """A one-record PORTRAIT_PARAMS_DTYPE array: the reference's values, updated from params (a dict or a record) and keywords."""
+    rec = np.zeros(1, PORTRAIT_PARAMS_DTYPE)
+    vals = dict(PORTRAIT_REFERENCE)
+    if params is not None:
+        vals.update(params if isinstance(params, dict) else {n: int(np.asarray(params).reshape(-1)[0][n]) for n in PORTRAIT_PARAMS_DTYPE.names})
+    vals.update(kw)
+    for k, v in vals.items():
+        if k not in PORTRAIT_PARAMS_DTYPE.names:
+            raise TypeError(f"unknown portrait parameter {k!r}")
+        rec[k] = int(v)
+    return rec
+
+
 GMS_OK, GMS_ERR_BAD_ARG, GMS_ERR_DOMAIN, GMS_ERR_HIP, GMS_ERR_NO_DEVICE, GMS_ERR_CAPACITY = 0, -1, -2, -3, -4, -5
 GMS_ERR_NOT_RESERVED, GMS_ERR_IO, GMS_ERR_NO_MODEL = -6, -7, -8
 GMS_DETECT_BORDER = 16   # include/gms.h: keypoints of gms_detect_batch_device sit at least this far from every edge
