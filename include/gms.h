@@ -411,9 +411,12 @@ int         gms_max_matches(void);        /* largest m per pair this build accep
 int         gms_last_hip_error(void);     /* last hipError_t seen by this thread's calls           */
 /* ---- keypoint source ---------------------------------------------------------------------
  * Stands where the reference calls OpenCV's detectors (FeatureMatchUtil.cpp:9-12 SIFT::create(10000)->detectAndCompute;
- * DisparityUtil.cpp:108,123-138 ORB::create(), detectAndCompute / compute at every pixel). NOT cv::ORB: a single-scale FAST-9 +
- * steered-BRIEF detector of this library's own, in integer arithmetic (definition: DESIGN.md section 7b; CPU statement
- * oracle/detect_ref.c). Same records out: cv::KeyPoint {pt, size 31, angle = 11.25 * direction bin, response = FAST score, octave 0,
+ * DisparityUtil.cpp:108,123-138 ORB::create(), detectAndCompute / compute at every pixel). NOT cv::ORB: a FAST-9 + steered-BRIEF
+ * detector of this library's own, in integer arithmetic (definition: DESIGN.md section 7b; CPU statement oracle/detect_ref.c).
+ * What cv::ORB has and this has: FAST-9 corners, an intensity-centroid direction, 256 steered comparisons on a smoothed image and --
+ * through gms_detect_pyramid_batch_device below -- a scale pyramid with size and octave per keypoint. What it still has not: Harris
+ * ranking (the FAST score ranks), cv::ORB's learned pattern (the pattern is this library's own) and cv::resize's pyramid (the resize is
+ * this library's own). The functions of this block are the single-scale form. Same records out: cv::KeyPoint {pt, size 31, angle = 11.25 * direction bin, response = FAST score, octave 0,
  * class_id -1} and one 32-byte row per keypoint for NORM_HAMMING -- what gms_normalize_device / gms_bf_prepare_device take.
  * Images: 8-bit grey, row-major, pitch = width, n_images of one size back to back in device memory. Keypoints sit at least
  * GMS_DETECT_BORDER pixels from every edge. */
@@ -432,6 +435,39 @@ int gms_detect_batch_device(gms_ctx* ctx, const uint8_t* d_images, int n_images,
  * Workspace: gms_detect_workspace_bytes(width, height, 1, 0). */
 int gms_describe_device(gms_ctx* ctx, const uint8_t* d_image, int width, int height, gms_keypoint* d_keypoints, int n,
                         void* d_workspace, size_t workspace_bytes, uint8_t* d_descriptors, int32_t* d_status);
+
+/* ---- pyramid keypoint source (CPU statement tests/pyramid_ref.py) ------------------------------------
+ * The detector above on every level of an image pyramid, as SIFT::create / ORB::create search one: keypoints come back in level-0
+ * pixel coordinates with size and octave, so that matchGMS(withScale), matchLOGOS and a resized pair ("Change Scale", main.cpp:42-47)
+ * get a scale from the keypoint source.
+ *   levels   level 0 is the image; w_l = (5 w_{l-1} + 3) / 6, the same for h (a ratio of about 1.2, cv::ORB's). They end at n_levels
+ *            (1 .. GMS_PYRAMID_MAX_LEVELS) or before the first level the detector refuses (width or height <= 32).
+ *   resize   level l from level l - 1: bilinear with pixel centres aligned, 8-bit fixed-point weights, rounded to nearest, edges
+ *            clamped -- integer arithmetic, this library's own definition (not cv::resize's).
+ *   quotas   q_l = max_keypoints * w_l h_l / sum_j w_j h_j in 64-bit integers, the remainder to level 0. What a level does not use of
+ *            its quota is not handed to another level (cv::ORB does not either).
+ *   records  level 0 first, raster order inside a level. pt = ((x + 0.5) * f - 0.5) in fp32, each operation rounded once, with
+ *            f = (float)w_0 / (float)w_l for x and (float)h_0 / (float)h_l for y; size = 31 * (float)w_0 / (float)w_l; octave = l; angle,
+ *            response, class_id and the 32-byte row as the detector above gives them on the level's image.
+ * n_levels = 1 gives the bytes of gms_detect_batch_device. */
+#define GMS_PYRAMID_MAX_LEVELS 16
+/* Host: the sizes of the levels actually used -> widths[], heights[] (room for n_levels each). Returns their number (>= 1), or
+ * GMS_ERR_BAD_ARG (NULL, n_levels outside [1, 16], width/height outside (32, 65535]). */
+int gms_pyramid_level_sizes(int width, int height, int n_levels, int32_t* widths, int32_t* heights);
+size_t gms_detect_pyramid_workspace_bytes(int width, int height, int n_images, int max_keypoints, int n_levels);   /* 0: bad arguments */
+
+/* detectAndCompute over the pyramid for a batch: image i's keypoints at d_keypoints[i * max_keypoints ..], its rows at
+ * d_descriptors[(i * max_keypoints ..) * 32], d_counts[i] of them; d_level_counts[i * n_levels + l] come from level l (0 for a level
+ * that is not used). On the context's stream; allocates nothing, waits for nothing, so it can be captured into a graph.
+ * Errors: those of gms_detect_batch_device, and n_levels outside [1, GMS_PYRAMID_MAX_LEVELS]. */
+int gms_detect_pyramid_batch_device(gms_ctx* ctx, const uint8_t* d_images, int n_images, int width, int height, int threshold, int max_keypoints,
+                                    int n_levels, void* d_workspace, size_t workspace_bytes, gms_keypoint* d_keypoints, uint8_t* d_descriptors,
+                                    int32_t* d_counts, int32_t* d_level_counts);
+
+/* The level images alone: levels 1, 2, .. of the batch into d_levels, level after level, the n_images images of a level back to back
+ * (pitch = the level's width), nothing between them: n_images * sum_{l >= 1} w_l h_l bytes. levels_bytes: room in d_levels. */
+int gms_pyramid_build_device(gms_ctx* ctx, const uint8_t* d_images, int n_images, int width, int height, int n_levels, uint8_t* d_levels,
+                             size_t levels_bytes);
 
 /* ---- LOGOS match filter -----------------------------------------------------------------------
  * cv::xfeatures2d::matchLOGOS(keypoints1, keypoints2, nn1, nn2, matches1to2) (FeatureMatchUtil.cpp:86-131; DESIGN.md, LOGOS):

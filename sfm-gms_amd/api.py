@@ -261,6 +261,28 @@ class GmsContext:
         _check(self._lib.gms_describe_device(self._h, d_image, int(width), int(height), d_kp, int(n), d_ws, int(ws_bytes), d_desc, d_status),
                self._lib, "gms_describe_device")
 
+    # -- pyramid keypoint source (gms_detect_pyramid_*; batch.detect_images_pyramid / build_pyramid drive them) ---------------------
+    def pyramid_level_sizes(self, width, height, n_levels):
+        """[(w_l, h_l)] of the levels gms_detect_pyramid_batch_device uses for this image size (host arithmetic)."""
+        n_levels = int(n_levels)
+        ww, hh = np.zeros(max(n_levels, 1), np.int32), np.zeros(max(n_levels, 1), np.int32)
+        n = self._lib.gms_pyramid_level_sizes(int(width), int(height), n_levels, ww.ctypes.data, hh.ctypes.data)
+        _check(min(n, 0), self._lib, "gms_pyramid_level_sizes")
+        return [(int(ww[l]), int(hh[l])) for l in range(n)]
+
+    def detect_pyramid_workspace_bytes(self, width, height, n_images, max_keypoints, n_levels):
+        return int(self._lib.gms_detect_pyramid_workspace_bytes(int(width), int(height), int(n_images), int(max_keypoints), int(n_levels)))
+
+    def detect_pyramid_batch_device(self, d_images, n_images, width, height, threshold, max_keypoints, n_levels, d_ws, ws_bytes, d_kp, d_desc,
+                                    d_counts, d_level_counts):
+        _check(self._lib.gms_detect_pyramid_batch_device(self._h, d_images, int(n_images), int(width), int(height), int(threshold),
+                                                         int(max_keypoints), int(n_levels), d_ws, int(ws_bytes), d_kp, d_desc, d_counts,
+                                                         d_level_counts), self._lib, "gms_detect_pyramid_batch_device")
+
+    def pyramid_build_device(self, d_images, n_images, width, height, n_levels, d_levels, levels_bytes):
+        _check(self._lib.gms_pyramid_build_device(self._h, d_images, int(n_images), int(width), int(height), int(n_levels), d_levels,
+                                                  int(levels_bytes)), self._lib, "gms_pyramid_build_device")
+
     # -- LOGOS on resident frames (gms_logos_*; batch.LogosTable / logos_pairs / logos_words drive them) ---------------------------
     def logos_table_bytes(self, total_kp, n_frames, n_words):
         return int(self._lib.gms_logos_table_bytes(int(total_kp), int(n_frames), int(n_words)))

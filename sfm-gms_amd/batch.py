@@ -185,6 +185,78 @@ def detect_images(ctx, images, threshold=20, max_keypoints=10000, device=None):
     return [kp[i, : counts[i]].copy() for i in range(n)], [desc[i, : counts[i]].copy() for i in range(n)]
 
 
+def _image_stack(ctx, images, device):
+    dev = torch.device(device if device is not None else f"cuda:{ctx.device}")
+    imgs = images if torch.is_tensor(images) else torch.from_numpy(np.ascontiguousarray(images, dtype=np.uint8))
+    if imgs.dim() == 2:
+        imgs = imgs[None]
+    return dev, imgs.to(dev).contiguous()
+
+
+class DetectPyramid:
+    """Device buffers of one gms_detect_pyramid_batch_device batch (n images of w x h), sized once, so that run() can be repeated or
+    captured into a graph: workspace, keypoints, rows, counts and per-level counts."""
+
+    def __init__(self, ctx, n, w, h, threshold=20, max_keypoints=10000, n_levels=8, device=None):
+        self.ctx, self.n, self.w, self.h = ctx, int(n), int(w), int(h)
+        self.threshold, self.max_keypoints, self.n_levels = int(threshold), int(max_keypoints), int(n_levels)
+        dev = torch.device(device if device is not None else f"cuda:{ctx.device}")
+        self.ws_bytes = ctx.detect_pyramid_workspace_bytes(w, h, n, max_keypoints, n_levels)
+        if self.ws_bytes == 0:
+            raise ValueError("bad image size, keypoint count or number of levels")
+        self.d_ws = torch.zeros(self.ws_bytes, dtype=torch.uint8, device=dev)
+        self.d_kp = torch.zeros(max(self.n * self.max_keypoints, 1) * 28, dtype=torch.uint8, device=dev)
+        self.d_desc = torch.zeros(max(self.n * self.max_keypoints, 1) * 32, dtype=torch.uint8, device=dev)
+        self.d_counts = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        self.d_level_counts = torch.zeros(self.n * self.n_levels, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+
+    def run(self, d_images):
+        """Stream-ordered on the context's stream; d_images: uint8 device tensor [n, h, w], contiguous."""
+        self.ctx.detect_pyramid_batch_device(d_images.data_ptr(), self.n, self.w, self.h, self.threshold, self.max_keypoints, self.n_levels,
+                                             self.d_ws.data_ptr(), self.ws_bytes, self.d_kp.data_ptr(), self.d_desc.data_ptr(),
+                                             self.d_counts.data_ptr(), self.d_level_counts.data_ptr())
+
+    def results(self):
+        """(keypoints_per_image, rows_per_image, level_counts [n, n_levels]) on the host."""
+        n, m = self.n, self.max_keypoints
+        counts = self.d_counts.cpu().numpy()
+        kp = self.d_kp.cpu().numpy()[: n * m * 28].view(KEYPOINT_DTYPE).reshape(n, m)
+        desc = self.d_desc.cpu().numpy()[: n * m * 32].reshape(n, m, 32)
+        return ([kp[i, : counts[i]].copy() for i in range(n)], [desc[i, : counts[i]].copy() for i in range(n)],
+                self.d_level_counts.cpu().numpy().reshape(n, self.n_levels).copy())
+
+
+def detect_images_pyramid(ctx, images, threshold=20, max_keypoints=10000, n_levels=8, device=None):
+    """gms_detect_pyramid_batch_device on a stack of equally sized 8-bit grey images [n, H, W]: the detector of detect_images on every
+    level of an image pyramid (ratio about 1.2). Returns (keypoints_per_image, rows_per_image, level_counts [n, n_levels]) as host
+    arrays: KEYPOINT_DTYPE records in level-0 pixel coordinates with size and octave, level 0 first, raster order inside a level."""
+    dev, imgs = _image_stack(ctx, images, device)
+    n, h, w = imgs.shape
+    run = DetectPyramid(ctx, n, w, h, threshold, max_keypoints, n_levels, dev)
+    run.run(imgs)
+    ctx.synchronize()
+    return run.results()
+
+
+def build_pyramid(ctx, images, n_levels=8, device=None):
+    """gms_pyramid_build_device: the level images of a stack [n, H, W] -> a list over the levels of host arrays [n, h_l, w_l] (level 0:
+    the input itself)."""
+    dev, imgs = _image_stack(ctx, images, device)
+    n, h, w = imgs.shape
+    sizes = ctx.pyramid_level_sizes(w, h, n_levels)
+    nb = n * sum(wl * hl for wl, hl in sizes[1:])
+    d_levels = torch.zeros(max(nb, 1), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+    ctx.pyramid_build_device(imgs.data_ptr(), n, w, h, n_levels, d_levels.data_ptr(), nb)
+    ctx.synchronize()
+    flat, out, off = d_levels.cpu().numpy(), [imgs.cpu().numpy()], 0
+    for wl, hl in sizes[1:]:
+        out.append(flat[off:off + n * wl * hl].reshape(n, hl, wl).copy())
+        off += n * wl * hl
+    return out
+
+
 def describe_image(ctx, image, keypoints, device=None):
     """gms_describe_device: directions and 32-byte rows at the given integer keypoints of one image -> (status, keypoints, rows)."""
     dev = torch.device(device if device is not None else f"cuda:{ctx.device}")

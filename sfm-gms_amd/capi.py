@@ -19,6 +19,7 @@ EXPORTED_SYMBOLS = [
     "gms_bf_select_host_batch", "gms_stereo_bm_workspace_bytes", "gms_stereo_bm_device", "gms_stereo_bm_normalize_device",
     "gms_stereo_bm", "gms_portrait_workspace_bytes", "gms_portrait_device", "gms_median_blur_device", "gms_portrait",
     "gms_portrait_profile_device", "gms_median_blur",
+    "gms_pyramid_level_sizes", "gms_detect_pyramid_workspace_bytes", "gms_detect_pyramid_batch_device", "gms_pyramid_build_device",
 ]
 
 _lib = None
@@ -78,6 +79,10 @@ def load_library():
     lib.gms_detect_workspace_bytes.restype = C.c_size_t
     lib.gms_detect_batch_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, C.c_size_t, vp, vp, vp]
     lib.gms_describe_device.argtypes = [vp, vp, i32, i32, vp, i32, vp, C.c_size_t, vp, vp]
+    lib.gms_pyramid_level_sizes.argtypes = [i32, i32, i32, vp, vp]
+    lib.gms_detect_pyramid_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
+    lib.gms_detect_pyramid_batch_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp]
+    lib.gms_pyramid_build_device.argtypes = [vp, vp, i32, i32, i32, i32, vp, C.c_size_t]
     lib.gms_logos_match.argtypes = [vp, i32, vp, i32, vp, vp, vp, i64, C.POINTER(i64), vp]
     lib.gms_logos_table_bytes.argtypes = [i64, i32, i32]
     lib.gms_logos_workspace_bytes.argtypes = [i64, i32, i64]
@@ -117,6 +122,7 @@ def load_library():
     lib.gms_bf_select_workspace_bytes.restype = C.c_size_t
     lib.gms_stereo_bm_workspace_bytes.restype = C.c_size_t
     lib.gms_portrait_workspace_bytes.restype = C.c_size_t
+    lib.gms_detect_pyramid_workspace_bytes.restype = C.c_size_t
     lib.gms_dataset_free.restype = None
     lib.gms_frame_table_bytes.argtypes = [i64]
     lib.gms_frame_table_bytes.restype = i64

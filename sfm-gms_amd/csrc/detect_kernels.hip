@@ -24,6 +24,10 @@
 //   det_scan_kernel      exclusive scan of those over the rows.
 //   det_emit_kernel      per image row: survivors to their slots (x, y, score), raster order.
 //   det_describe_kernel  one wave per keypoint: moments by wave reduction, direction, 256 comparisons by four ballots.
+// The same detector over an image pyramid (launch_detect_pyramid) adds
+//   pyr_resize_kernel    a level from the level below it: integer bilinear, source rows through LDS, 4-byte loads and stores.
+//   det_describe_kernel  in its per-level form: records behind the earlier levels', pt mapped to level 0, size and octave set.
+//   pyr_clear_kernel     zeroes the levels' counts and histograms; pyr_counts_kernel: the per-image and per-level counts for the caller.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -272,13 +276,25 @@ det_emit_kernel(const uint8_t* __restrict__ cand, int w, int h, const int32_t* _
 }
 
 // ---- direction + descriptor: one wave per keypoint ---------------------------------------------------------------------------------------
-// FROM_LIST: keypoints come from det_emit_kernel's list (and the record is written here); otherwise from caller's records (compute()).
-template <bool FROM_LIST>
+// Where the keypoints come from and where the records go:
+//   kAtRecords   from the caller's records (compute()); only the angle is written.
+//   kFromList    from det_emit_kernel's list; record k of image img goes to slot img * max_keypoints + k.
+//   kFromLevel   the same list, of pyramid level `level` (max_keypoints = the level's quota): the record goes behind the earlier levels'
+//                survivors in the image's block of out_stride records, pt mapped to level 0, size and octave of the level.
+enum { kAtRecords = 0, kFromList = 1, kFromLevel = 2 };
+struct LevelOut {
+    const int32_t* level_counts;   // [level][image]: survivors of the levels (this level's row is `counts`)
+    int level, n_images, out_stride;
+    float fx, fy;                  // (float)w_0 / (float)w_level, (float)h_0 / (float)h_level
+};
+
+template <int MODE>
 __global__ void __launch_bounds__(256)
 det_describe_kernel(const uint8_t* __restrict__ images, const uint16_t* __restrict__ box, int w, int h, const uint32_t* __restrict__ list,
                     const int32_t* __restrict__ counts, int max_keypoints, gms_keypoint* __restrict__ kp, uint8_t* __restrict__ desc,
-                    int32_t* __restrict__ status)
+                    int32_t* __restrict__ status, LevelOut lo)
 {
+    constexpr bool FROM_LIST = MODE != kAtRecords;
     const int lane = (int)threadIdx.x & 63, img = (int)blockIdx.y;
     const int k = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
     const int n = counts != nullptr ? min(counts[img], max_keypoints) : max_keypoints;
@@ -286,7 +302,13 @@ det_describe_kernel(const uint8_t* __restrict__ images, const uint16_t* __restri
     const size_t plane = (size_t)w * h;
     const uint8_t* __restrict__ im = images + (size_t)img * plane;
     const uint16_t* __restrict__ bx = box + (size_t)img * plane;
-    gms_keypoint* rec = kp + (size_t)img * max_keypoints + k;
+    size_t slot = (size_t)img * max_keypoints + k;
+    if constexpr (MODE == kFromLevel) {
+        int before = 0;   // (the levels' counts sum to at most out_stride: the quotas do)
+        for (int j = 0; j < lo.level; ++j) before += lo.level_counts[(size_t)j * lo.n_images + img];
+        slot = (size_t)img * lo.out_stride + before + k;
+    }
+    gms_keypoint* rec = kp + slot;
     int x, y, sc = 0;
     if constexpr (FROM_LIST) {
         const uint32_t xy = list[((size_t)img * max_keypoints + k) * 2];
@@ -336,9 +358,14 @@ det_describe_kernel(const uint8_t* __restrict__ images, const uint16_t* __restri
         const int va = bx[(size_t)(y + ray) * w + (x + rax)], vb = bx[(size_t)(y + rby) * w + (x + rbx)];
         bits[j] = __ballot(va < vb);
     }
-    if (lane < 4) reinterpret_cast<uint64_t*>(desc + ((size_t)img * max_keypoints + k) * 32)[lane] = bits[lane & 3];
+    if (lane < 4) reinterpret_cast<uint64_t*>(desc + slot * 32)[lane] = bits[lane & 3];
     if (lane == 0) {
-        if constexpr (FROM_LIST) {
+        if constexpr (MODE == kFromLevel) {   // pixel centres aligned; every operation rounded once (-ffp-contract=off)
+            gms_keypoint r;
+            r.x = ((float)x + 0.5f) * lo.fx - 0.5f; r.y = ((float)y + 0.5f) * lo.fy - 0.5f; r.size = 31.0f * lo.fx;
+            r.angle = 11.25f * (float)bin; r.response = (float)sc; r.octave = lo.level; r.class_id = -1;
+            *rec = r;
+        } else if constexpr (MODE == kFromList) {
             gms_keypoint r;
             r.x = (float)x; r.y = (float)y; r.size = 31.0f; r.angle = 11.25f * (float)bin; r.response = (float)sc; r.octave = 0; r.class_id = -1;
             *rec = r;
@@ -346,6 +373,97 @@ det_describe_kernel(const uint8_t* __restrict__ images, const uint16_t* __restri
             rec->angle = 11.25f * (float)bin;
         }
     }
+}
+
+// ---- pyramid: a level from the level below it -----------------------------------------------------------------------------------------
+// Bilinear, pixel centres aligned, 8-bit fixed-point weights, all integer: for output column x
+//   X = floor((2x + 1) * w_src * 128 / w_dst) - 128 (>= 0 because w_src >= w_dst), x0 = X >> 8, ax = X & 255, x1 = min(x0 + 1, w_src - 1),
+// the same for rows, out = ((256 - ax)(256 - ay) p00 + ax (256 - ay) p01 + (256 - ax) ay p10 + ax ay p11 + 32768) >> 16.
+// A workgroup makes 64 x 16 output pixels, a thread four of one row as one aligned 4-byte store: rows of pitch = width start at any
+// address, so the tile of row y starts (address of the row's first pixel) & 3 pixels early and the bytes that fall outside the row at
+// its two ends are stored one by one. The source rows come through LDS with aligned 4-byte loads in the same way: a row is loaded
+// from the 4-byte boundary at or below its first pixel and remembered with that shift. The level rule keeps w_src / w_dst and
+// h_src / h_dst at or below 1.2 + 0.4 / 33, so the 67 columns a tile can touch span at most 83 source pixels (+ 3 of shift) and its 16
+// rows at most 21 source rows.
+constexpr int kRzCols = 64 + 3, kRzRows = 16, kRzSrcRows = 22, kRzPitch = 96;
+
+__global__ void __launch_bounds__(256)
+pyr_resize_kernel(const uint8_t* __restrict__ src, int ws, int hs, uint8_t* __restrict__ dst, int wd, int hd, size_t src_bytes)
+{
+    __shared__ uint32_t tile[kRzSrcRows][kRzPitch / 4];
+    __shared__ int col_x[kRzCols], row_y[kRzRows];
+    const int tid = (int)threadIdx.x;
+    const int xo0 = (int)blockIdx.x * 64 - 3, yo0 = (int)blockIdx.y * kRzRows;   // first output column / row this tile may hold
+    if (tid < kRzCols) {
+        const int x = min(max(xo0 + tid, 0), wd - 1);
+        col_x[tid] = (int)((uint64_t)(2 * x + 1) * (uint64_t)ws * 128u / (uint64_t)wd) - 128;
+    } else if (tid >= 128 && tid < 128 + kRzRows) {
+        const int y = min(yo0 + tid - 128, hd - 1);
+        row_y[tid - 128] = (int)((uint64_t)(2 * y + 1) * (uint64_t)hs * 128u / (uint64_t)hd) - 128;
+    }
+    __syncthreads();
+    const int xs0 = col_x[0] >> 8, ys0 = row_y[0] >> 8;
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(src), hi = lo + src_bytes;
+    const uintptr_t im = lo + (size_t)blockIdx.z * ws * hs;
+    for (int i = tid; i < kRzSrcRows * (kRzPitch / 4); i += 256) {
+        const int r = i / (kRzPitch / 4), j = i - r * (kRzPitch / 4);
+        const uintptr_t a = ((im + (size_t)min(ys0 + r, hs - 1) * ws + xs0) & ~(uintptr_t)3) + 4u * (unsigned)j;
+        uint32_t v = 0;
+        if (a >= lo && a + 4 <= hi) {
+            v = *reinterpret_cast<const uint32_t*>(a);
+        } else {   // the 4 bytes straddle an end of the batch: the ones inside it, one by one
+            for (int b = 0; b < 4; ++b)
+                if (a + b >= lo && a + b < hi) v |= (uint32_t)*reinterpret_cast<const uint8_t*>(a + b) << (8 * b);
+        }
+        tile[r][j] = v;
+    }
+    __syncthreads();
+    const int y = yo0 + (tid >> 4);
+    if (y >= hd) return;
+    uint8_t* __restrict__ out_row = dst + (size_t)blockIdx.z * wd * hd + (size_t)y * wd;
+    const int xf = (int)blockIdx.x * 64 + 4 * (tid & 15) - (int)(reinterpret_cast<uintptr_t>(out_row) & 3);   // out_row + xf is 4-byte aligned
+    const int Y = row_y[tid >> 4], y0 = Y >> 8, ay = Y & 255, y1 = min(y0 + 1, hs - 1);
+    const uint8_t* r0 = reinterpret_cast<const uint8_t*>(tile[y0 - ys0]);   // source pixel x of a row sits at byte x + o of its LDS row
+    const uint8_t* r1 = reinterpret_cast<const uint8_t*>(tile[y1 - ys0]);
+    const int o0 = (int)((im + (size_t)y0 * ws + xs0) & 3) - xs0, o1 = (int)((im + (size_t)y1 * ws + xs0) & 3) - xs0;
+    uint32_t packed = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int X = col_x[xf + q - xo0], x0 = X >> 8, ax = X & 255, x1 = min(x0 + 1, ws - 1);
+        const uint32_t top = (uint32_t)(256 - ax) * r0[o0 + x0] + (uint32_t)ax * r0[o0 + x1];
+        const uint32_t bot = (uint32_t)(256 - ax) * r1[o1 + x0] + (uint32_t)ax * r1[o1 + x1];
+        packed |= (((uint32_t)(256 - ay) * top + (uint32_t)ay * bot + 32768u) >> 16) << (8 * q);
+    }
+    if (xf >= 0 && xf + 3 < wd) {
+        *reinterpret_cast<uint32_t*>(out_row + xf) = packed;
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (xf + q >= 0 && xf + q < wd) out_row[xf + q] = (uint8_t)(packed >> (8 * q));
+    }
+}
+
+// zeroes the levels' counts and score histograms at the head of a call (a kernel, not a memset: the call is one chain of kernel launches,
+// which is what the other graph-captured batch calls of this library are)
+__global__ void __launch_bounds__(256)
+pyr_clear_kernel(uint32_t* __restrict__ words, size_t n_words)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n_words; i += (size_t)gridDim.x * 256) words[i] = 0;
+}
+
+// the caller's counts from the levels' [level][image] counts: counts[img] = the sum, level_counts[img][l] (0 for levels not used)
+__global__ void __launch_bounds__(256)
+pyr_counts_kernel(const int32_t* __restrict__ lvl, int n_images, int n_used, int n_levels, int32_t* __restrict__ counts, int32_t* __restrict__ level_counts)
+{
+    const int img = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (img >= n_images) return;
+    int sum = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        const int v = l < n_used ? lvl[(size_t)l * n_images + img] : 0;
+        level_counts[(size_t)img * n_levels + l] = v;
+        sum += v;
+    }
+    counts[img] = sum;
 }
 
 }  // namespace
@@ -381,15 +499,19 @@ DetWs carve(void* ws, int w, int h, int n_images, int max_keypoints)
     (void)max_keypoints;
     return d;
 }
-}  // namespace
 
-hipError_t launch_detect(const uint8_t* d_images, int n_images, int w, int h, int threshold, int max_keypoints, void* d_ws,
-                         gms_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, hipStream_t stream)
+// the detector on one set of equally sized images: the single-scale call (lo == nullptr; clears its histogram itself) or one level of the
+// pyramid (lo and the level's histogram, already cleared)
+hipError_t detect_level(const uint8_t* d_images, int n_images, int w, int h, int threshold, int max_keypoints, void* d_ws, gms_keypoint* d_kp,
+                        uint8_t* d_desc, int32_t* d_counts, const LevelOut* lo, uint32_t* level_hist, hipStream_t stream)
 {
-    if (n_images <= 0) return hipSuccess;
-    const DetWs ws = carve(d_ws, w, h, n_images, max_keypoints);
-    hipError_t e = hipMemsetAsync(ws.hist, 0, (size_t)n_images * 256 * 4, stream);
-    if (e != hipSuccess) return e;
+    DetWs ws = carve(d_ws, w, h, n_images, max_keypoints);
+    if (level_hist != nullptr) {
+        ws.hist = level_hist;
+    } else {
+        hipError_t e = hipMemsetAsync(ws.hist, 0, (size_t)n_images * 256 * 4, stream);
+        if (e != hipSuccess) return e;
+    }
     hipLaunchKernelGGL(det_maps_kernel, dim3((w + kTileW - 1) / kTileW, (h + kTileH - 1) / kTileH, n_images), dim3(256), 0, stream, d_images, w, h,
                        ws.score, ws.box);
     hipLaunchKernelGGL(det_nms_kernel, dim3((w + 63) / 64, (h + 3) / 4, n_images), dim3(256), 0, stream, ws.score, w, h, threshold, ws.cand, ws.hist);
@@ -397,10 +519,26 @@ hipError_t launch_detect(const uint8_t* d_images, int n_images, int w, int h, in
     hipLaunchKernelGGL(det_rows_kernel, dim3(h, n_images), dim3(64), 0, stream, ws.cand, w, h, ws.cut, ws.rows);
     hipLaunchKernelGGL(det_scan_kernel, dim3(n_images), dim3(1024), 0, stream, ws.rows, h);
     hipLaunchKernelGGL(det_emit_kernel, dim3(h, n_images), dim3(64), 0, stream, ws.cand, w, h, ws.cut, ws.rows, max_keypoints, ws.list);
-    if (max_keypoints > 0)
-        hipLaunchKernelGGL(det_describe_kernel<true>, dim3((max_keypoints + 3) / 4, n_images), dim3(256), 0, stream, d_images, ws.box, w, h, ws.list,
-                           d_counts, max_keypoints, d_kp, d_desc, (int32_t*)nullptr);
+    if (max_keypoints > 0) {
+        const dim3 grid((max_keypoints + 3) / 4, n_images);
+        if (lo != nullptr)
+            hipLaunchKernelGGL(det_describe_kernel<kFromLevel>, grid, dim3(256), 0, stream, d_images, ws.box, w, h, ws.list, d_counts, max_keypoints,
+                               d_kp, d_desc, (int32_t*)nullptr, *lo);
+        else
+            hipLaunchKernelGGL(det_describe_kernel<kFromList>, grid, dim3(256), 0, stream, d_images, ws.box, w, h, ws.list, d_counts, max_keypoints,
+                               d_kp, d_desc, (int32_t*)nullptr, LevelOut{});
+    }
     return hipGetLastError();
+}
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+}  // namespace
+
+hipError_t launch_detect(const uint8_t* d_images, int n_images, int w, int h, int threshold, int max_keypoints, void* d_ws,
+                         gms_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, hipStream_t stream)
+{
+    if (n_images <= 0) return hipSuccess;
+    return detect_level(d_images, n_images, w, h, threshold, max_keypoints, d_ws, d_kp, d_desc, d_counts, nullptr, nullptr, stream);
 }
 
 // compute(): directions and rows at the caller's keypoints of ONE image; *d_status = 1 when a keypoint is off the pixel grid or outside the
@@ -413,8 +551,106 @@ hipError_t launch_describe(const uint8_t* d_image, int w, int h, gms_keypoint* d
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(det_maps_kernel, dim3((w + kTileW - 1) / kTileW, (h + kTileH - 1) / kTileH, 1), dim3(256), 0, stream, d_image, w, h, ws.score, ws.box);
     if (n > 0)
-        hipLaunchKernelGGL(det_describe_kernel<false>, dim3((n + 3) / 4, 1), dim3(256), 0, stream, d_image, ws.box, w, h, (const uint32_t*)nullptr,
-                           (const int32_t*)nullptr, n, d_kp, d_desc, d_status);
+        hipLaunchKernelGGL(det_describe_kernel<kAtRecords>, dim3((n + 3) / 4, 1), dim3(256), 0, stream, d_image, ws.box, w, h, (const uint32_t*)nullptr,
+                           (const int32_t*)nullptr, n, d_kp, d_desc, d_status, LevelOut{});
+    return hipGetLastError();
+}
+
+// ---- the pyramid keypoint source --------------------------------------------------------------------------------
+// Level 0 is the image; w_l = (5 w_{l-1} + 3) / 6, the same for h; the levels end at n_levels or before the first one the detector
+// refuses (width or height <= 32). Returns the number of levels (0: level 0 itself is refused).
+int pyramid_level_sizes(int w, int h, int n_levels, int* widths, int* heights)
+{
+    int n = 0;
+    while (n < n_levels && n < kPyramidMaxLevels && w > 2 * kBorder && h > 2 * kBorder && w <= 65535 && h <= 65535) {
+        widths[n] = w; heights[n] = h;
+        ++n;
+        w = (5 * w + 3) / 6; h = (5 * h + 3) / 6;
+    }
+    return n;
+}
+
+// q_l = max_keypoints * area_l / (sum of the areas) in 64-bit integers; what the division leaves goes to level 0
+void pyramid_quotas(const int* widths, const int* heights, int n, int max_keypoints, int* quotas)
+{
+    int64_t total = 0, given = 0;
+    for (int l = 0; l < n; ++l) total += (int64_t)widths[l] * heights[l];
+    for (int l = 1; l < n; ++l) {
+        quotas[l] = (int)((int64_t)max_keypoints * widths[l] * heights[l] / total);
+        given += quotas[l];
+    }
+    if (n > 0) quotas[0] = (int)(max_keypoints - given);
+}
+
+// bytes of levels 1 .. n - 1 of n_images images, level after level, the images of a level back to back, nothing between them
+size_t pyramid_bytes(int w, int h, int n_images, int n_levels)
+{
+    int ww[kPyramidMaxLevels], hh[kPyramidMaxLevels];
+    const int n = pyramid_level_sizes(w, h, n_levels, ww, hh);
+    size_t b = 0;
+    for (int l = 1; l < n; ++l) b += (size_t)ww[l] * hh[l] * (size_t)(n_images > 0 ? n_images : 0);
+    return b;
+}
+
+hipError_t launch_pyramid_build(const uint8_t* d_images, int n_images, int w, int h, int n_levels, uint8_t* d_levels, hipStream_t stream)
+{
+    int ww[kPyramidMaxLevels], hh[kPyramidMaxLevels];
+    const int n = pyramid_level_sizes(w, h, n_levels, ww, hh);
+    if (n_images <= 0) return hipSuccess;
+    const uint8_t* src = d_images;
+    uint8_t* dst = d_levels;
+    for (int l = 1; l < n; ++l) {
+        const size_t src_bytes = (size_t)ww[l - 1] * hh[l - 1] * n_images;
+        hipLaunchKernelGGL(pyr_resize_kernel, dim3((ww[l] + 3 + 63) / 64, (hh[l] + kRzRows - 1) / kRzRows, n_images), dim3(256), 0, stream, src, ww[l - 1],
+                           hh[l - 1], dst, ww[l], hh[l], src_bytes);
+        src = dst;
+        dst += (size_t)ww[l] * hh[l] * n_images;
+    }
+    return hipGetLastError();
+}
+
+// bytes of the part of the workspace that every call zeroes first: the levels' counts, then their histograms
+static size_t pyramid_cleared_bytes(int n_images)
+{
+    return align256((size_t)kPyramidMaxLevels * n_images * 4) + (size_t)kPyramidMaxLevels * n_images * 256 * 4;
+}
+
+// workspace: level images 1 .. | [level][image] counts | [level][image] score histograms | the single-scale workspace of level 0 (every
+// level fits into it in its turn)
+size_t detect_pyramid_workspace_bytes(int w, int h, int n_images, int max_keypoints, int n_levels)
+{
+    const size_t single = detect_workspace_bytes(w, h, n_images, max_keypoints);
+    if (single == 0 || n_levels < 1 || n_levels > kPyramidMaxLevels) return 0;
+    return align256(pyramid_bytes(w, h, n_images, n_levels)) + pyramid_cleared_bytes(n_images) + single;
+}
+
+hipError_t launch_detect_pyramid(const uint8_t* d_images, int n_images, int w, int h, int threshold, int max_keypoints, int n_levels, void* d_ws,
+                                 gms_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, int32_t* d_level_counts, hipStream_t stream)
+{
+    if (n_images <= 0) return hipSuccess;
+    int ww[kPyramidMaxLevels], hh[kPyramidMaxLevels], quota[kPyramidMaxLevels];
+    const int n = pyramid_level_sizes(w, h, n_levels, ww, hh);
+    pyramid_quotas(ww, hh, n, max_keypoints, quota);
+    uint8_t* levels = reinterpret_cast<uint8_t*>(d_ws);
+    int32_t* lvl_counts = reinterpret_cast<int32_t*>(levels + align256(pyramid_bytes(w, h, n_images, n_levels)));
+    uint32_t* hists = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lvl_counts) + align256((size_t)kPyramidMaxLevels * n_images * 4));
+    void* det_ws = reinterpret_cast<char*>(lvl_counts) + pyramid_cleared_bytes(n_images);
+    const size_t clear_words = pyramid_cleared_bytes(n_images) / 4;   // (the counts too: a level with quota 0 is not run)
+    hipLaunchKernelGGL(pyr_clear_kernel, dim3((unsigned)((clear_words + 255) / 256 < 1024 ? (clear_words + 255) / 256 : 1024)), dim3(256), 0, stream,
+                       reinterpret_cast<uint32_t*>(lvl_counts), clear_words);
+    hipError_t e = launch_pyramid_build(d_images, n_images, w, h, n_levels, levels, stream);
+    if (e != hipSuccess) return e;
+    const uint8_t* img = d_images;
+    for (int l = 0; l < n; ++l) {
+        if (quota[l] > 0) {
+            const LevelOut lo = {lvl_counts, l, n_images, max_keypoints, (float)w / (float)ww[l], (float)h / (float)hh[l]};
+            e = detect_level(img, n_images, ww[l], hh[l], threshold, quota[l], det_ws, d_kp, d_desc, lvl_counts + (size_t)l * n_images, &lo,
+                             hists + (size_t)l * n_images * 256, stream);
+            if (e != hipSuccess) return e;
+        }
+        img = l == 0 ? levels : img + (size_t)ww[l] * hh[l] * n_images;
+    }
+    hipLaunchKernelGGL(pyr_counts_kernel, dim3((n_images + 255) / 256), dim3(256), 0, stream, lvl_counts, n_images, n, n_levels, d_counts, d_level_counts);
     return hipGetLastError();
 }
 

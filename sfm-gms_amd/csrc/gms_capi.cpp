@@ -1502,6 +1502,48 @@ int gms_describe_device(gms_ctx* c, const uint8_t* d_image, int width, int heigh
     return GMS_OK;
 }
 
+// ---- pyramid keypoint source (detect_kernels.hip) -------------------------------------------------------------------------------
+int gms_pyramid_level_sizes(int width, int height, int n_levels, int32_t* widths, int32_t* heights)
+{
+    if (n_levels < 1 || n_levels > GMS_PYRAMID_MAX_LEVELS || !detect_image_ok(width, height) || !widths || !heights) return GMS_ERR_BAD_ARG;
+    return gms::pyramid_level_sizes(width, height, n_levels, widths, heights);
+}
+
+size_t gms_detect_pyramid_workspace_bytes(int width, int height, int n_images, int max_keypoints, int n_levels)
+{
+    if (!detect_image_ok(width, height)) return 0;
+    return gms::detect_pyramid_workspace_bytes(width, height, n_images, max_keypoints, n_levels);
+}
+
+int gms_pyramid_build_device(gms_ctx* c, const uint8_t* d_images, int n_images, int width, int height, int n_levels, uint8_t* d_levels,
+                             size_t levels_bytes)
+{
+    if (!c || n_images < 0 || n_levels < 1 || n_levels > GMS_PYRAMID_MAX_LEVELS || !detect_image_ok(width, height)) return GMS_ERR_BAD_ARG;
+    if (n_images == 0) return GMS_OK;
+    const size_t need = gms::pyramid_bytes(width, height, n_images, n_levels);
+    if (!d_images || levels_bytes < need || (need > 0 && !d_levels)) return GMS_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(c->mu);
+    GMS_HIP(hipSetDevice(c->device));
+    GMS_HIP(gms::launch_pyramid_build(d_images, n_images, width, height, n_levels, d_levels, c->stream));
+    return GMS_OK;
+}
+
+int gms_detect_pyramid_batch_device(gms_ctx* c, const uint8_t* d_images, int n_images, int width, int height, int threshold, int max_keypoints,
+                                    int n_levels, void* d_workspace, size_t workspace_bytes, gms_keypoint* d_keypoints, uint8_t* d_descriptors,
+                                    int32_t* d_counts, int32_t* d_level_counts)
+{
+    if (!c || n_images < 0 || max_keypoints < 0 || threshold < 0 || threshold > 254 || !detect_image_ok(width, height)) return GMS_ERR_BAD_ARG;
+    if (n_levels < 1 || n_levels > GMS_PYRAMID_MAX_LEVELS) return GMS_ERR_BAD_ARG;
+    if (n_images == 0) return GMS_OK;
+    if (!d_images || !d_workspace || !d_counts || !d_level_counts || (max_keypoints > 0 && (!d_keypoints || !d_descriptors))) return GMS_ERR_BAD_ARG;
+    if (workspace_bytes < gms::detect_pyramid_workspace_bytes(width, height, n_images, max_keypoints, n_levels)) return GMS_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(c->mu);
+    GMS_HIP(hipSetDevice(c->device));
+    GMS_HIP(gms::launch_detect_pyramid(d_images, n_images, width, height, threshold, max_keypoints, n_levels, d_workspace, d_keypoints, d_descriptors,
+                                       d_counts, d_level_counts, c->stream));
+    return GMS_OK;
+}
+
 // ---- LOGOS on resident frames (logos_batch_kernels.hip) ----------------------------------------------------------------------
 int64_t gms_logos_table_bytes(int64_t total_kp, int n_frames, int n_words)
 {

@@ -140,6 +140,15 @@ hipError_t launch_detect(const uint8_t* d_images, int n_images, int w, int h, in
                          gms_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, hipStream_t stream);
 hipError_t launch_describe(const uint8_t* d_image, int w, int h, gms_keypoint* d_kp, int n, void* d_ws, uint8_t* d_desc, int32_t* d_status,
                            hipStream_t stream);
+// pyramid keypoint source (detect_kernels.hip): the same detector on every level of an image pyramid
+constexpr int kPyramidMaxLevels = 16;
+int        pyramid_level_sizes(int w, int h, int n_levels, int* widths, int* heights);
+void       pyramid_quotas(const int* widths, const int* heights, int n, int max_keypoints, int* quotas);
+size_t     pyramid_bytes(int w, int h, int n_images, int n_levels);
+size_t     detect_pyramid_workspace_bytes(int w, int h, int n_images, int max_keypoints, int n_levels);
+hipError_t launch_pyramid_build(const uint8_t* d_images, int n_images, int w, int h, int n_levels, uint8_t* d_levels, hipStream_t stream);
+hipError_t launch_detect_pyramid(const uint8_t* d_images, int n_images, int w, int h, int threshold, int max_keypoints, int n_levels, void* d_ws,
+                                 gms_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, int32_t* d_level_counts, hipStream_t stream);
 // batched LOGOS (logos_batch_kernels.hip; layouts in logos_batch.h)
 hipError_t launch_logos_prepare(const gms_keypoint* d_kp, const int64_t* d_frame_off, int n_frames, int64_t total_kp, const int32_t* d_words,
                                 int n_words, void* d_ws, size_t ws_bytes, void* d_table, int n_cus, hipStream_t stream);

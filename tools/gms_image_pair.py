@@ -5,7 +5,8 @@
     -> disparity map + RMS against a ground truth (gms_disparity_device).
 Input: an .npz with arrays left, right [H, W] uint8 and optionally gt (default: the committed 450 x 375 pair of the reference's
 SourceImages, tests/golden/image_stereo_pair_450x375.npz). Prints one JSON line; --out writes the survivors and the map as .npz.
-    python tools/gms_image_pair.py [pair.npz] [--dense] [--threshold 12] [--max-keypoints 10000] [--rotation] [--scale] [--ratio 4] [--check]
+    python tools/gms_image_pair.py [pair.npz] [--dense] [--pyramid N] [--threshold 12] [--max-keypoints 10000] [--rotation] [--scale] [--ratio 4] [--check]
+--pyramid N: keypoints from N levels of an image pyramid (gms_detect_pyramid_batch_device), with size and octave; without it the single-scale detector.
 --check runs the CPU statement (oracle/) beside it and compares every stage (test infrastructure; slow in --dense)."""
 import argparse
 import importlib
@@ -25,6 +26,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("pair", nargs="?", default=os.path.join(ROOT, "tests", "golden", "image_stereo_pair_450x375.npz"))
     ap.add_argument("--dense", action="store_true")
+    ap.add_argument("--pyramid", type=int, default=0, metavar="N")
     ap.add_argument("--threshold", type=int, default=12)
     ap.add_argument("--max-keypoints", type=int, default=10000)
     ap.add_argument("--rotation", action="store_true")
@@ -55,6 +57,8 @@ def main():
             assert st == 0
             kps.append(k)
             rows.append(r)
+    elif a.pyramid > 0:
+        kps, rows, level_counts = batch.detect_images_pyramid(ctx, np.stack([left, right]), a.threshold, a.max_keypoints, a.pyramid)
     else:
         kps, rows = batch.detect_images(ctx, np.stack([left, right]), a.threshold, a.max_keypoints)
     t["keypoints_ms"] = (time.perf_counter() - t0) * 1e3
@@ -91,6 +95,8 @@ def main():
             "status": int(res["status"][0]), "rms_pixels_compared": cnt,
             "disparity_rms": float(np.sqrt(float(stats["sum_sq"]) / cnt)) if cnt else None, "max_abs_error": int(stats["max_abs"]),
             "ms": {k: round(v, 3) for k, v in t.items()}, "note": "first-call times (allocation and module load included)"}
+    if a.pyramid > 0 and not a.dense:
+        line["mode"], line["keypoints_per_level"] = f"pyramid {a.pyramid}", level_counts.tolist()
     if a.check:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import gms_oracle as oracle
@@ -102,7 +108,12 @@ def main():
             ok["matches_sampled"] = bool((want_m["trainIdx"] == matches["trainIdx"][sample]).all() and (want_m["distance"] == matches["distance"][sample]).all()
                                          and (matches["queryIdx"] == np.arange(len(matches))).all() and (matches["imgIdx"] == 0).all())
         else:
-            want = [oracle.detect(img, a.threshold, a.max_keypoints) for img in (left, right)]
+            if a.pyramid > 0:
+                sys.path.insert(0, os.path.join(ROOT, "tests"))
+                import pyramid_ref
+                want = [pyramid_ref.detect(oracle, img, a.threshold, a.max_keypoints, a.pyramid) for img in (left, right)]
+            else:
+                want = [oracle.detect(img, a.threshold, a.max_keypoints) for img in (left, right)]
             ok["keypoints"] = all(want[i][0].tobytes() == kps[i].tobytes() and want[i][1].tobytes() == rows[i].tobytes() for i in range(2))
             ok["matches"] = oracle.bf_match(rows[0], rows[1], True).tobytes() == matches.tobytes()
         rc, wout, wmask, wres = oracle.match((w, h), (w, h), kps[0], kps[1], matches, a.rotation, a.scale, 6.0)
