@@ -529,6 +529,45 @@ int gms_logos_words_device(gms_ctx* ctx, int desc_kind, const void* d_desc, int6
 int gms_logos_host_batch(gms_ctx* ctx, const gms_keypoint* kp, const int64_t* frame_off, int n_frames, const int32_t* words, int n_words,
                          const gms_pair* pairs, int n_pairs, gms_dmatch* out, gms_logos_result* results);
 
+/* ---- Training the LOGOS dictionary ("Training the dictionary") -----------------------------------------------------
+ * The reference builds its dictionary with BOWKMeansTrainer(50 | 100).cluster(desc1) (FeatureMatchUtil.cpp:100-104). cv::kmeans
+ * seeds from a global RNG and sums in float, so its rows cannot be reproduced; the definition here is this library's own, and every
+ * order-dependent step of it is integer arithmetic: the result is, byte for byte, that of the numpy statement
+ * tests/logos_dict_ref.py, on every run. It is k-means with k-means++ seeding (three trials per centre), `attempts` restarts and at
+ * most `max_iters` assignments, on the distances of gms_logos_words_device.
+ *
+ * A training set is a run of descriptor rows: set s is rows [d_set_off[s], d_set_off[s + 1]) of d_desc (n_sets + 1 offsets within
+ * [0, total_rows], never decreasing). desc_kind: GMS_DESC_L2_F32X128 or GMS_DESC_HAMMING256. n_words 1..65535, attempts 1..16,
+ * max_iters 1..1000, n_sets 0..65535 (others: GMS_ERR_BAD_ARG for the call, nothing run). Per set:
+ *   d_dict     n_words rows per set, set after set; zero-filled for a set whose status is not GMS_OK.
+ *   d_results  one record per set. status: GMS_ERR_BAD_ARG for a set with fewer than n_words rows, more than 2^20 rows or unusable
+ *              offsets (negative, past total_rows, end before start, or a start before the end of an earlier set with usable
+ *              offsets: sets that run never overlap); GMS_ERR_DOMAIN for an L2 set with an element that is not finite or outside [-4096, 4096]. Such a set
+ *              does not disturb the others. attempt: the attempt with the smallest compactness (lowest index on ties), -1 on
+ *              failure; iterations: the assignments it ran; compactness: the sum of the integer weights of its last assignment
+ *              (a Hamming distance is its own weight, an L2 squared distance d weighs floor(d 2^8)); empty_clusters: dictionary
+ *              rows that no row of the set is nearest to.
+ *   d_labels   optional (NULL allowed), one int32 per row of d_desc: the word of every row of every set under its dictionary
+ *              (what gms_logos_words_device gives for it), -1 for the rows of a failed set; rows outside every set, and those of a set with unusable
+ *              offsets, are left alone.
+ * gms_logos_dict_train_device: stream-ordered on the context's stream; no allocation, synchronisation or read-back; capturable.
+ *   The workspace (16-byte aligned) needs gms_logos_dict_workspace_bytes(...) bytes for the same arguments; 0 means they are refused.
+ * gms_logos_dict_train: the same on host arrays, synchronous, on device 0. */
+typedef struct gms_logos_dict_result {
+    int32_t  status;
+    int32_t  attempt;
+    int32_t  iterations;
+    int32_t  empty_clusters;
+    uint64_t compactness;
+} gms_logos_dict_result;
+
+size_t gms_logos_dict_workspace_bytes(int desc_kind, int64_t total_rows, int n_sets, int n_words, int attempts, int max_iters);
+int gms_logos_dict_train_device(gms_ctx* ctx, int desc_kind, const void* d_desc, const int64_t* d_set_off, int n_sets, int64_t total_rows,
+                                int n_words, int attempts, int max_iters, uint64_t seed, void* d_workspace, size_t ws_bytes, void* d_dict,
+                                gms_logos_dict_result* d_results, int32_t* d_labels);
+int gms_logos_dict_train(int desc_kind, const void* desc, const int64_t* set_off, int n_sets, int n_words, int attempts, int max_iters,
+                         uint64_t seed, void* dict, gms_logos_dict_result* results, int32_t* labels);
+
 /* ---- StereoBM block matching: the reference's dense baseline (DisparityUtil.cpp:22-49) -------------------------------
  *     StereoBM::create(16, 5); setNumDisparities(224); ...; compute(g1, g2, disparity);            CV_16S, 4 fractional bits
  *     normalize(disparity, disparity, 0, 255, NORM_MINMAX, CV_8U); every 0 pixel -> 255

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from .capi import load_library
-from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_DESC_HAMMING256, KEYPOINT_DTYPE, PAIR_DTYPE, RESULT_DTYPE, GMS_OK, GMS_ERR_CAPACITY,
+from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128, LOGOS_DICT_RESULT_DTYPE, KEYPOINT_DTYPE, PAIR_DTYPE, RESULT_DTYPE, GMS_OK, GMS_ERR_CAPACITY,
                     GmsError, portrait_params, stereo_bm_params)
 
 
@@ -302,6 +302,18 @@ class GmsContext:
         _check(self._lib.gms_logos_words_device(self._h, int(desc_kind), d_desc or None, int(total_desc), d_dict, int(n_words),
                                                 d_words or None), self._lib, "gms_logos_words_device")
 
+    # -- LOGOS dictionary training (gms_logos_dict_*; batch.LogosDictionary / logos_dictionary drive them) ------------------------
+    def logos_dict_workspace_bytes(self, desc_kind, total_rows, n_sets, n_words, attempts, max_iters):
+        return int(self._lib.gms_logos_dict_workspace_bytes(int(desc_kind), int(total_rows), int(n_sets), int(n_words), int(attempts),
+                                                            int(max_iters)))
+
+    def logos_dict_train_device(self, desc_kind, d_desc, d_set_off, n_sets, total_rows, n_words, attempts, max_iters, seed, d_ws, ws_bytes,
+                                d_dict, d_results, d_labels=None):
+        _check(self._lib.gms_logos_dict_train_device(self._h, int(desc_kind), d_desc or None, d_set_off, int(n_sets), int(total_rows),
+                                                     int(n_words), int(attempts), int(max_iters), int(seed) & 0xFFFFFFFFFFFFFFFF, d_ws,
+                                                     int(ws_bytes), d_dict, d_results, d_labels or None),
+               self._lib, "gms_logos_dict_train_device")
+
     # -- StereoBM block matching (DisparityUtil.cpp:22-49; batch.stereo_bm_batch drives these) ------------------------------------
     def stereo_bm_workspace_bytes(self, width, height, n_pairs, params=None):
         return int(self._lib.gms_stereo_bm_workspace_bytes(int(width), int(height), int(n_pairs), stereo_bm_params(params).ctypes.data))
@@ -401,6 +413,41 @@ def matchLOGOS(keypoints1, keypoints2, nn1, nn2):
             continue
         _check(rc, lib, "gms_logos_match")
         return out[: n.value].copy()
+
+
+def logos_dict_args(kind, n_words, attempts, max_iters):
+    """The argument checks of the dictionary trainer, as include/gms.h states them -> (dtype, row width)."""
+    kind = int(kind)
+    if kind not in (GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128):
+        raise ValueError("kind: GMS_DESC_HAMMING256 or GMS_DESC_L2_F32X128")
+    if not 1 <= int(n_words) <= 65535:
+        raise ValueError("1 <= n_words <= 65535")
+    if not 1 <= int(attempts) <= 16 or not 1 <= int(max_iters) <= 1000:
+        raise ValueError("1 <= attempts <= 16 and 1 <= max_iters <= 1000")
+    return (np.uint8, 32) if kind == GMS_DESC_HAMMING256 else (np.float32, 128)
+
+
+def trainLogosDictionary(descriptors, kind, n_words=50, attempts=3, max_iters=100, seed=0, detail=False):
+    """The dictionary the reference gets from BOWKMeansTrainer(n_words).cluster(descriptors) (FeatureMatchUtil.cpp:100-104), trained
+    on the GPU (gms_logos_dict_train): k-means with k-means++ seeding, `attempts` restarts, at most `max_iters`
+    assignments. It is not OpenCV's dictionary (cv::kmeans draws from a global RNG and sums in float): the definition is this
+    library's own and gives the same bytes on every run for the same rows and seed.
+
+    descriptors: uint8 [n, 32] for GMS_DESC_HAMMING256, float32 [n, 128] for GMS_DESC_L2_F32X128 (finite, |x| <= 4096), n_words <= n
+    <= 2^20. Returns the dictionary [n_words, width]; with detail=True also the LOGOS_DICT_RESULT_DTYPE record and the word of every
+    row. Rows outside the domain or too few of them raise GmsError."""
+    dt, width = logos_dict_args(kind, n_words, attempts, max_iters)
+    lib = load_library()
+    rows = np.ascontiguousarray(descriptors, dtype=dt).reshape(-1, width)
+    off = np.array([0, len(rows)], np.int64)
+    dic = np.zeros((int(n_words), width), dt)
+    rec = np.zeros(1, LOGOS_DICT_RESULT_DTYPE)
+    labels = np.full(max(len(rows), 1), -1, np.int32)
+    rc = lib.gms_logos_dict_train(int(kind), rows.ctypes.data if len(rows) else None, off.ctypes.data, 1, int(n_words), int(attempts),
+                                  int(max_iters), int(seed) & 0xFFFFFFFFFFFFFFFF, dic.ctypes.data, rec.ctypes.data, labels.ctypes.data)
+    _check(rc, lib, "gms_logos_dict_train")
+    _check(int(rec[0]["status"]), lib, "gms_logos_dict_train (the training set)")
+    return (dic, rec[0], labels[: len(rows)]) if detail else dic
 
 
 def bruteForceMatch(desc1, desc2, kind, cross_check=True, distance_coef=4.0, max_size=500, detail=False):

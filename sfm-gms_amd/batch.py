@@ -8,8 +8,8 @@ for many pairs per launch with the per-frame keypoint tables kept in HBM.
 import numpy as np
 import torch
 
-from .api import GmsContext
-from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_ERR_CAPACITY, KEYPOINT_DTYPE, LOGOS_RESULT_DTYPE, portrait_params, stereo_bm_params,
+from .api import GmsContext, logos_dict_args
+from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_ERR_CAPACITY, KEYPOINT_DTYPE, LOGOS_DICT_RESULT_DTYPE, LOGOS_RESULT_DTYPE, portrait_params, stereo_bm_params,
                     PAIR_DTYPE, RESULT_DTYPE)
 
 
@@ -460,6 +460,74 @@ def logos_words(ctx, descriptors_per_frame, dictionary, kind, device=None):
         raise ValueError("1 <= dictionary rows <= 65535")
     out = np.split(words, np.cumsum(counts)[:-1]) if counts else []
     return out[0] if single else out
+
+
+class LogosDictionary:
+    """Device buffers of gms_logos_dict_train_device for up to max_sets training sets of max_rows descriptor rows in all: the rows, the
+    set offsets, workspace, dictionaries, records and labels, sized once, so that run() can be repeated -- or captured into a graph
+    and replayed -- on new rows put into the same tensors (d_desc, d_set_off). The arguments that size the launches (n_sets, the row
+    total, n_words, attempts, max_iters) are fixed here; the offsets are read on the device, so sets may change size between runs."""
+
+    def __init__(self, ctx, kind, n_sets, total_rows, n_words=50, attempts=3, max_iters=100, seed=0, device=None):
+        self.dtype, self.width = logos_dict_args(kind, n_words, attempts, max_iters)
+        self.ctx, self.kind, self.n_sets, self.total_rows = ctx, int(kind), int(n_sets), int(total_rows)
+        self.n_words, self.attempts, self.max_iters, self.seed = int(n_words), int(attempts), int(max_iters), int(seed)
+        dev = torch.device(device if device is not None else f"cuda:{ctx.device}")
+        self.device = dev
+        self.ws_bytes = ctx.logos_dict_workspace_bytes(self.kind, self.total_rows, self.n_sets, self.n_words, self.attempts, self.max_iters)
+        if self.ws_bytes == 0:
+            raise ValueError("LogosDictionary: arguments refused (include/gms.h)")
+        row_bytes = self.width * np.dtype(self.dtype).itemsize
+        self.d_desc = torch.zeros(max(self.total_rows, 1) * row_bytes, dtype=torch.uint8, device=dev)
+        self.d_set_off = torch.zeros(self.n_sets + 1, dtype=torch.int64, device=dev)
+        self.d_ws = torch.zeros(self.ws_bytes, dtype=torch.uint8, device=dev)
+        self.d_dict = torch.zeros(max(self.n_sets, 1) * self.n_words * row_bytes, dtype=torch.uint8, device=dev)
+        self.d_results = torch.zeros(max(self.n_sets, 1) * LOGOS_DICT_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.d_labels = torch.full((max(self.total_rows, 1),), -1, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+
+    def load(self, descriptor_sets):
+        """Copy the rows of `descriptor_sets` (a list of row arrays, n_sets of them, total_rows rows in all at most) and their offsets
+        into the device tensors (on the current torch stream)."""
+        rows = [np.ascontiguousarray(d, dtype=self.dtype).reshape(-1, self.width) for d in descriptor_sets]
+        if len(rows) != self.n_sets or sum(len(r) for r in rows) > self.total_rows:
+            raise ValueError("LogosDictionary.load: n_sets sets of at most total_rows rows in all")
+        off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+        if off[-1]:
+            flat = torch.from_numpy(np.concatenate(rows).view(np.uint8).reshape(-1))
+            self.d_desc[: flat.numel()].copy_(flat)
+        self.d_set_off.copy_(torch.from_numpy(off))
+        self.d_labels.fill_(-1)
+        return off
+
+    def run(self, with_labels=True):
+        """gms_logos_dict_train_device on the tensors as they are: stream-ordered on the context's stream, capturable."""
+        self.ctx.logos_dict_train_device(self.kind, self.d_desc.data_ptr(), self.d_set_off.data_ptr(), self.n_sets, self.total_rows,
+                                         self.n_words, self.attempts, self.max_iters, self.seed, self.d_ws.data_ptr(), self.ws_bytes,
+                                         self.d_dict.data_ptr(), self.d_results.data_ptr(), self.d_labels.data_ptr() if with_labels else None)
+
+    def results(self):
+        """(dictionaries [n_sets, n_words, width], LOGOS_DICT_RESULT_DTYPE records, labels per row) as host arrays."""
+        dic = self.d_dict.cpu().numpy().view(self.dtype).reshape(max(self.n_sets, 1), self.n_words, self.width)[: self.n_sets]
+        rec = self.d_results.cpu().numpy().view(LOGOS_DICT_RESULT_DTYPE)[: self.n_sets]
+        return dic.copy(), rec.copy(), self.d_labels.cpu().numpy()[: self.total_rows]
+
+
+def logos_dictionary(ctx, descriptor_sets, kind, n_words=50, attempts=3, max_iters=100, seed=0, device=None):
+    """One dictionary per training set, all sets in the same launches (gms_logos_dict_train_device). descriptor_sets: a
+    list of row arrays (or one array: one set). Returns (dictionaries [n_sets, n_words, width], LOGOS_DICT_RESULT_DTYPE records,
+    list of int32 labels per set); a set that fails its checks has status != 0 in its record, a zero dictionary and labels -1."""
+    single = not isinstance(descriptor_sets, (list, tuple))
+    sets = [descriptor_sets] if single else list(descriptor_sets)
+    dt, width = logos_dict_args(kind, n_words, attempts, max_iters)
+    total = sum(len(np.asarray(d).reshape(-1, width)) for d in sets)
+    job = LogosDictionary(ctx, kind, len(sets), total, n_words, attempts, max_iters, seed, device)
+    off = job.load(sets)
+    torch.cuda.synchronize(job.device)
+    job.run()
+    ctx.synchronize()
+    dic, rec, labels = job.results()
+    return dic, rec, [labels[off[s]:off[s + 1]] for s in range(len(sets))]
 
 
 class StereoBM:

@@ -20,6 +20,7 @@ EXPORTED_SYMBOLS = [
     "gms_stereo_bm", "gms_portrait_workspace_bytes", "gms_portrait_device", "gms_median_blur_device", "gms_portrait",
     "gms_portrait_profile_device", "gms_median_blur",
     "gms_pyramid_level_sizes", "gms_detect_pyramid_workspace_bytes", "gms_detect_pyramid_batch_device", "gms_pyramid_build_device",
+    "gms_logos_dict_workspace_bytes", "gms_logos_dict_train_device", "gms_logos_dict_train",
 ]
 
 _lib = None
@@ -90,6 +91,9 @@ def load_library():
     lib.gms_logos_filter_device.argtypes = [vp, vp, vp, i32, vp, C.c_size_t, vp, vp, vp]
     lib.gms_logos_words_device.argtypes = [vp, i32, vp, i64, vp, i32, vp]
     lib.gms_logos_host_batch.argtypes = [vp, vp, vp, i32, vp, i32, vp, i32, vp, vp]
+    lib.gms_logos_dict_workspace_bytes.argtypes = [i32, i64, i32, i32, i32, i32]
+    lib.gms_logos_dict_train_device.argtypes = [vp, i32, vp, vp, i32, i64, i32, i32, i32, C.c_uint64, vp, C.c_size_t, vp, vp, vp]
+    lib.gms_logos_dict_train.argtypes = [i32, vp, vp, i32, i32, i32, i32, C.c_uint64, vp, vp, vp]
     lib.gms_bf_select_workspace_bytes.argtypes = [i32, i32, i64]
     lib.gms_bf_select_device.argtypes = [vp, i32, vp, vp, i64, vp, i32, vp, i32, i32, i32, dbl, i32, vp, C.c_size_t, vp, vp, vp]
     lib.gms_bf_match_select.argtypes = [i32, vp, i32, vp, i32, i32, dbl, i32, vp, i64, C.POINTER(i64), vp]
@@ -119,6 +123,7 @@ def load_library():
     lib.gms_bf_prepared_bytes.restype = i64
     lib.gms_logos_table_bytes.restype = i64
     lib.gms_logos_workspace_bytes.restype = C.c_size_t
+    lib.gms_logos_dict_workspace_bytes.restype = C.c_size_t
     lib.gms_bf_select_workspace_bytes.restype = C.c_size_t
     lib.gms_stereo_bm_workspace_bytes.restype = C.c_size_t
     lib.gms_portrait_workspace_bytes.restype = C.c_size_t

@@ -22,6 +22,7 @@
 #include "gms.h"
 #include "gms_kernels.h"
 #include "logos_batch.h"
+#include "logos_dict_core.h"
 #include "portrait_core.h"
 #include "stereo_bm_core.h"
 #include "twoview_core.h"
@@ -1646,6 +1647,83 @@ int gms_logos_host_batch(gms_ctx* c, const gms_keypoint* kp, const int64_t* fram
                                      c->n_cus, st);
     if (e == hipSuccess) e = hipMemcpyAsync(results, d + o_res, sizeof(gms_logos_result) * (size_t)n_pairs, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && out_len > 0) e = hipMemcpyAsync(out, d + o_out, sizeof(gms_dmatch) * (size_t)out_len, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    else (void)hipStreamSynchronize(st);
+    (void)hipFree(blk);
+    GMS_HIP(e);
+    return GMS_OK;
+}
+
+// ---- LOGOS dictionary training (logos_dict_kernels.hip) --------------------------------------------------------------------------
+static bool logos_dict_params(int desc_kind, int64_t total_rows, int n_sets, int n_words, int attempts, int max_iters, uint64_t seed,
+                              gms::logos_dict::Params* p)
+{
+    p->kind = desc_kind;
+    p->n_sets = n_sets;
+    p->n_words = n_words;
+    p->attempts = attempts;
+    p->max_iters = max_iters;
+    p->row_bytes = desc_kind == GMS_DESC_HAMMING256 ? 32 : 512;
+    p->total_rows = total_rows;
+    p->seed = seed;
+    return (desc_kind == GMS_DESC_HAMMING256 || desc_kind == GMS_DESC_L2_F32X128) && gms::logos_dict::params_ok(*p);
+}
+
+size_t gms_logos_dict_workspace_bytes(int desc_kind, int64_t total_rows, int n_sets, int n_words, int attempts, int max_iters)
+{
+    gms::logos_dict::Params p;
+    if (!logos_dict_params(desc_kind, total_rows, n_sets, n_words, attempts, max_iters, 0, &p)) return 0;
+    return gms::logos_dict_ws_bytes(p);
+}
+
+int gms_logos_dict_train_device(gms_ctx* c, int desc_kind, const void* d_desc, const int64_t* d_set_off, int n_sets, int64_t total_rows,
+                                int n_words, int attempts, int max_iters, uint64_t seed, void* d_workspace, size_t ws_bytes, void* d_dict,
+                                gms_logos_dict_result* d_results, int32_t* d_labels)
+{
+    gms::logos_dict::Params p;
+    if (!c || !logos_dict_params(desc_kind, total_rows, n_sets, n_words, attempts, max_iters, seed, &p)) return GMS_ERR_BAD_ARG;
+    if (n_sets == 0) return GMS_OK;
+    if (!d_set_off || !d_workspace || !d_dict || !d_results || (total_rows > 0 && !d_desc)) return GMS_ERR_BAD_ARG;
+    if (ws_bytes < gms::logos_dict_ws_bytes(p) || (reinterpret_cast<uintptr_t>(d_workspace) & 15u)) return GMS_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(c->mu);
+    GMS_HIP(hipSetDevice(c->device));
+    GMS_HIP(gms::launch_logos_dict_train(p, d_desc, d_set_off, d_workspace, d_dict, d_results, d_labels, c->stream));
+    return GMS_OK;
+}
+
+int gms_logos_dict_train(int desc_kind, const void* desc, const int64_t* set_off, int n_sets, int n_words, int attempts, int max_iters,
+                         uint64_t seed, void* dict, gms_logos_dict_result* results, int32_t* labels)
+{
+    if (n_sets < 0 || !set_off) return GMS_ERR_BAD_ARG;
+    const int64_t total = set_off[n_sets];
+    gms::logos_dict::Params p;
+    if (!logos_dict_params(desc_kind, total, n_sets, n_words, attempts, max_iters, seed, &p)) return GMS_ERR_BAD_ARG;
+    if (n_sets == 0) return GMS_OK;
+    if (!dict || !results || (total > 0 && !desc)) return GMS_ERR_BAD_ARG;
+    const size_t a = 256;
+    auto up = [&](size_t x) { return (x + a - 1) / a * a; };
+    const size_t b_desc = (size_t)p.row_bytes * (size_t)total, b_off = 8 * ((size_t)n_sets + 1);
+    const size_t b_dict = (size_t)p.row_bytes * (size_t)n_words * (size_t)n_sets, b_res = sizeof(gms_logos_dict_result) * (size_t)n_sets;
+    const size_t b_lab = 4 * (size_t)total, ws = gms::logos_dict_ws_bytes(p);
+    // one block: rows | offsets | dictionaries | records | labels | workspace
+    const size_t o_desc = 0, o_off = up(o_desc + b_desc + 16), o_dict = up(o_off + b_off), o_res = up(o_dict + b_dict);
+    const size_t o_lab = up(o_res + b_res), o_ws = up(o_lab + b_lab + 16), bytes = o_ws + ws;
+    GMS_HIP(hipSetDevice(0));
+    void* blk = nullptr;
+    GMS_HIP(hipMalloc(&blk, bytes));
+    char* d = static_cast<char*>(blk);
+    hipStream_t st = nullptr;
+    hipError_t e = hipSuccess;
+    if (total > 0) e = hipMemcpyAsync(d + o_desc, desc, b_desc, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_off, set_off, b_off, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && labels && total > 0) e = hipMemcpyAsync(d + o_lab, labels, b_lab, hipMemcpyHostToDevice, st);  // rows outside every set keep theirs
+    if (e == hipSuccess)
+        e = gms::launch_logos_dict_train(p, d + o_desc, reinterpret_cast<const int64_t*>(d + o_off), d + o_ws, d + o_dict,
+                                         reinterpret_cast<gms_logos_dict_result*>(d + o_res), labels ? reinterpret_cast<int32_t*>(d + o_lab) : nullptr,
+                                         st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dict, d + o_dict, b_dict, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(results, d + o_res, b_res, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && labels && total > 0) e = hipMemcpyAsync(labels, d + o_lab, b_lab, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     else (void)hipStreamSynchronize(st);
     (void)hipFree(blk);

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "gms.h"
+#include "logos_dict_core.h"
 
 namespace gms {
 
@@ -156,6 +157,10 @@ hipError_t launch_logos_filter(const void* d_table, const gms_pair* d_pairs, int
                                gms_logos_result* d_lres, gms_pair_result* d_pres, int n_cus, hipStream_t stream);
 hipError_t launch_logos_words(int kind, const void* d_desc, int64_t total, const void* d_dict, int n_words, int32_t* d_words, int n_cus,
                               hipStream_t stream);
+// LOGOS dictionary training (logos_dict_kernels.hip; shared parts and the workspace layout in logos_dict_core.h)
+size_t     logos_dict_ws_bytes(const logos_dict::Params& p);
+hipError_t launch_logos_dict_train(const logos_dict::Params& p, const void* d_desc, const int64_t* d_set_off, void* d_ws, void* d_dict,
+                                   gms_logos_dict_result* d_results, int32_t* d_labels, hipStream_t stream);
 // StereoBM block matching (stereo_bm_kernels.hip; shared arithmetic in stereo_bm_core.h)
 size_t     stereo_bm_ws_bytes(int n, int W, int H);
 hipError_t launch_stereo_bm(const gms_stereo_bm_params& p, const uint8_t* d_left, const uint8_t* d_right, int n, int W, int H, int pitch,

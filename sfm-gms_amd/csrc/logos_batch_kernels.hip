@@ -15,6 +15,7 @@
 #include "gms_kernels.h"
 #include "logos_batch.h"
 #include "logos_core.h"
+#include "logos_words_dist.h"
 
 namespace {
 
@@ -611,34 +612,11 @@ __global__ void __launch_bounds__(kScanBlock) filter_scan_kernel(const gms_pair*
 // The exact nearest dictionary row of every descriptor row: lane l of a wave computes, alone and in the sequential
 // order of the definition, the distance of the wave's current row to word (tile + l); a wave-wide (distance, index) minimum and a
 // strict '<' across tiles leave the lowest index among equal distances. NaN distances count as +inf.
-constexpr int kWordTile = 64;
+using gms::logos::kWordTile;
+using gms::logos::l2_words_dist;
+using gms::logos::wave_argmin;
 constexpr int kRowsPerWave = 8;
 constexpr int kRowsPerBlock = kRowsPerWave * (kBlock / kWave);
-
-__device__ __forceinline__ void wave_argmin(float& d, int& w)
-{
-    for (int s = 1; s < kWave; s <<= 1) {
-        const float od = __shfl_xor(d, s);
-        const int ow = __shfl_xor(w, s);
-        if (od < d || (od == d && ow < w)) {
-            d = od;
-            w = ow;
-        }
-    }
-}
-
-__device__ __forceinline__ float l2_words_dist(const float* __restrict__ row, const float (*tile)[kWordTile], int lane)
-{
-    float acc = 0.0f;
-    for (int g = 0; g < 128; g += 4) {
-        const float d0 = row[g] - tile[g][lane], d1 = row[g + 1] - tile[g + 1][lane];
-        const float d2 = row[g + 2] - tile[g + 2][lane], d3 = row[g + 3] - tile[g + 3][lane];
-        const float s0 = d0 * d0, s1 = d1 * d1, s2 = d2 * d2, s3 = d3 * d3;
-        const float grp = ((s0 + s1) + s2) + s3;
-        acc = acc + grp;
-    }
-    return acc;
-}
 
 __global__ void __launch_bounds__(kBlock) words_l2_kernel(const float* __restrict__ desc, int64_t total, const float* __restrict__ dict,
                                                            int n_words, int32_t* __restrict__ out)

@@ -227,6 +227,49 @@ inline void matchLOGOSBatch(const std::vector<std::vector<KeyPoint>>& keypoints,
     }
 }
 
+// The dictionary the reference builds with BOWKMeansTrainer(n_words).cluster(desc1) (FeatureMatchUtil.cpp:100-104), trained on the
+// GPU (gms_logos_dict_train): k-means with k-means++ seeding, `attempts` restarts, at most `max_iters` assignments. Not OpenCV's
+// rows -- cv::kmeans draws from a global RNG and sums in float -- but the same bytes on every run for the same rows and seed. The
+// shim has no cv::Mat: descriptors are flat row-major vectors of 128 floats (finite, |x| <= 4096) or 32 bytes per row, and so is
+// the dictionary returned (n_words rows). labels (optional) gets the word of every row; result (optional) the record. Too few rows
+// (fewer than n_words) or rows outside the domain throw.
+namespace detail {
+inline void train_dict(int kind, const void* desc, size_t n, void* dict, int n_words, int attempts, int max_iters,
+                       uint64_t seed, std::vector<int>* labels, gms_logos_dict_result* result)
+{
+    const int64_t off[2] = {0, (int64_t)n};
+    std::vector<int32_t> lab(std::max<size_t>(n, 1), -1);
+    gms_logos_dict_result res{};
+    int rc = gms_logos_dict_train(kind, n ? desc : nullptr, off, 1, n_words, attempts, max_iters, seed, dict, &res, lab.data());
+    if (rc == GMS_OK) rc = res.status;
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::trainLogosDictionary: ") + gms_error_string(rc));
+    if (labels) labels->assign(lab.begin(), lab.begin() + (std::ptrdiff_t)n);
+    if (result) *result = res;
+}
+}  // namespace detail
+
+inline std::vector<float> trainLogosDictionary(const std::vector<float>& descriptors, int n_words = 50, int attempts = 3,
+                                               int max_iters = 100, uint64_t seed = 0, std::vector<int>* labels = nullptr,
+                                               gms_logos_dict_result* result = nullptr)
+{
+    if (descriptors.size() % 128 || n_words < 1) throw std::invalid_argument("mi355::trainLogosDictionary: rows of 128 floats, n_words >= 1");
+    std::vector<float> dict((size_t)n_words * 128);
+    detail::train_dict(GMS_DESC_L2_F32X128, descriptors.data(), descriptors.size() / 128, dict.data(), n_words, attempts, max_iters, seed,
+                       labels, result);
+    return dict;
+}
+
+inline std::vector<uint8_t> trainLogosDictionary(const std::vector<uint8_t>& descriptors, int n_words = 50, int attempts = 3,
+                                                 int max_iters = 100, uint64_t seed = 0, std::vector<int>* labels = nullptr,
+                                                 gms_logos_dict_result* result = nullptr)
+{
+    if (descriptors.size() % 32 || n_words < 1) throw std::invalid_argument("mi355::trainLogosDictionary: rows of 32 bytes, n_words >= 1");
+    std::vector<uint8_t> dict((size_t)n_words * 32);
+    detail::train_dict(GMS_DESC_HAMMING256, descriptors.data(), descriptors.size() / 32, dict.data(), n_words, attempts, max_iters, seed,
+                       labels, result);
+    return dict;
+}
+
 // The reference's bruteForceMatch (FeatureMatchUtil.cpp:20-31): BFMatcher(norm, crossCheck).match(desc1, desc2), std::sort by
 // distance (MSVC's order among equal distances), then the matches within distance_coef times the smallest distance, at most
 // max_size. The shim has no cv::Mat: descriptors come as flat row-major vectors -- 128 floats per row (SIFT, NORM_L2) or 32 bytes

@@ -18,27 +18,38 @@ torch here is device memory only; every stage is a call into csrc/libgms_hip.so.
 import numpy as np
 import torch
 
-from .batch import BfSelect, DescriptorTable, FrameTable, LogosTable, _to_dev, bf_select_table
+from .batch import BfSelect, DescriptorTable, FrameTable, LogosTable, _to_dev, bf_select_table, logos_dictionary
+from .api import logos_dict_args
 from .types import (DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_ERR_CAPACITY, LOGOS_RESULT_DTYPE, PAIR_DTYPE, RESULT_DTYPE, TWO_VIEW_DTYPE,
                     make_camera)
 
 
 def run_dataset(ctx, ds, withRotation=False, withScale=False, thresholdFactor=6.0, match=None, camera=None, dist=None, prob=0.7,
                 ransac_threshold=1.0, max_iters=1000, device="cuda:0", method="gms", dictionary=None, logos_capacity=None,
-                cross_check=True, distance_coef=4.0, max_size=500):
+                cross_check=True, distance_coef=4.0, max_size=500, train_dictionary=None):
     """(prob, ransac_threshold: findEssentialMat's confidence and threshold as the flow this function restates passes them -- SfMUtil.cpp:39:
     RANSAC, 0.7, 1.0 -- not OpenCV's own default of 0.999, which gms_find_essential_batch_device's Python mirror keeps.)
     ds: io.Dataset. match=None: brute-force match when the file carries descriptors and no matches. camera = (fx, fy, cx, cy)
     switches the two-view stage on. Returns a dict of host arrays: pairs, matches (the putative ones), out, results, and with a camera
     two_view (TWO_VIEW_DTYPE per pair), coords1, coords2, mask, points3d -- all per-match arrays laid out by match_off.
     method="logos": the LOGOS flow on the file's descriptors and pairs (frame_a, frame_b; their m / match_off are not used) with the
-    caller's `dictionary` (rows like the descriptors); see _run_logos.
+    caller's `dictionary` (rows like the descriptors); see _run_logos. Without one, train_dictionary=True or a dict of
+    dictionary_training_options trains it first on the file's descriptors (gms_logos_dict_train_device) -- by default on frame 0's,
+    as the reference clusters desc1 (FeatureMatchUtil.cpp:100-104); the result then also carries `dictionary` and
+    `dictionary_result`. A `dictionary` that is passed is used as it is and train_dictionary is then not read. With neither,
+    method="logos" raises.
     method="bf": bruteForceMatch on the file's descriptors and pairs (cross_check, distance_coef, max_size as the reference's
     4.0 / 500 by default); see _run_bf."""
     if method == "bf":
         return _run_bf(ctx, ds, cross_check, distance_coef, max_size, camera, dist, prob, ransac_threshold, max_iters, device)
     if method == "logos":
-        return _run_logos(ctx, ds, dictionary, logos_capacity, camera, dist, prob, ransac_threshold, max_iters, device)
+        trained = None
+        if dictionary is None and train_dictionary not in (None, False):
+            dictionary, trained = _train_dictionary(ctx, ds, dictionary_training_options(train_dictionary), device)
+        r = _run_logos(ctx, ds, dictionary, logos_capacity, camera, dist, prob, ransac_threshold, max_iters, device)
+        if trained is not None:
+            r.update(dictionary=dictionary, dictionary_result=trained)
+        return r
     if method != "gms":
         raise ValueError(f"unknown method {method!r}")
     frames = FrameTable(ctx, ds.frames, ds.sizes, device=device)
@@ -91,6 +102,36 @@ def run_dataset(ctx, ds, withRotation=False, withScale=False, thresholdFactor=6.
     out.update(matches=d_matches.cpu().numpy().view(DMATCH_DTYPE)[:total_m], out=d_out.cpu().numpy().view(DMATCH_DTYPE)[:total_m],
                results=d_res.cpu().numpy().view(RESULT_DTYPE)[:n_pairs])
     return out
+
+
+def dictionary_training_options(train_dictionary):
+    """run_dataset's train_dictionary= as a full dict: True, or a dict with any of rows ("first": frame 0's descriptors, as the
+    reference trains on desc1; "all": every frame's, as one set), n_words, attempts, max_iters, seed."""
+    opts = {"rows": "first", "n_words": 50, "attempts": 3, "max_iters": 100, "seed": 0}
+    if train_dictionary is not True:
+        given = dict(train_dictionary)
+        unknown = set(given) - set(opts)
+        if unknown:
+            raise ValueError(f"train_dictionary: unknown keys {sorted(unknown)}")
+        opts.update(given)
+    if opts["rows"] not in ("first", "all"):
+        raise ValueError("train_dictionary: rows is 'first' or 'all'")
+    return opts
+
+
+def _train_dictionary(ctx, ds, opts, device):
+    """-> (dictionary, its LOGOS_DICT_RESULT_DTYPE record), trained on the dataset's descriptors; a set outside the domain raises."""
+    if ds.descriptors is None or len(ds.descriptors) == 0:
+        raise ValueError("method='logos' needs the dataset's descriptors and a dictionary")
+    kind = int(ds.desc_kind)
+    dt, width = logos_dict_args(kind, opts["n_words"], opts["attempts"], opts["max_iters"])
+    rows = [np.ascontiguousarray(d, dtype=dt).reshape(-1, width) for d in ds.descriptors]
+    train = rows[0] if opts["rows"] == "first" else np.concatenate(rows)
+    dic, rec, _ = logos_dictionary(ctx, [train], kind, opts["n_words"], opts["attempts"], opts["max_iters"], opts["seed"], device)
+    if rec[0]["status"] != 0:
+        raise ValueError(f"train_dictionary: the training rows were refused (status {int(rec[0]['status'])}): at least n_words and at "
+                         "most 2^20 rows, L2 elements finite and within [-4096, 4096]")
+    return dic[0], rec[0]
 
 
 def _run_logos(ctx, ds, dictionary, capacity, camera, dist, prob, ransac_threshold, max_iters, device):

@@ -15,6 +15,10 @@ assert PAIR_DTYPE.itemsize == 24 and RESULT_DTYPE.itemsize == 16
 # gms_logos_result (include/gms.h): one LOGOS pair's counts, peak bin and status
 LOGOS_RESULT_DTYPE = np.dtype([("n_candidates", "<i8"), ("n_supported", "<i8"), ("n_out", "<i8"), ("peak_bin", "<i4"), ("status", "<i4")])
 assert LOGOS_RESULT_DTYPE.itemsize == 32
+# gms_logos_dict_result (include/gms.h): one training set's status, winning attempt, assignments run, empty words and compactness
+LOGOS_DICT_RESULT_DTYPE = np.dtype([("status", "<i4"), ("attempt", "<i4"), ("iterations", "<i4"), ("empty_clusters", "<i4"),
+                                    ("compactness", "<u8")])
+assert LOGOS_DICT_RESULT_DTYPE.itemsize == 24
 # gms_bf_result (include/gms.h): one bruteForceMatch pair's candidate count, count within the ratio, survivors, d_min and status
 BF_RESULT_DTYPE = np.dtype([("n_candidates", "<i8"), ("n_ratio", "<i8"), ("n_out", "<i8"), ("d_min", "<f4"), ("status", "<i4")])
 assert BF_RESULT_DTYPE.itemsize == 32
