@@ -18,6 +18,7 @@
 #include <thread>
 #include <vector>
 
+#include "block_layout.h"
 #include "copy_pool.h"
 #include "gms.h"
 #include "gms_kernels.h"
@@ -114,50 +115,33 @@ void right_grids(int rw[5], int rh[5])
     }
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t bytes)
-    {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes < 4096 ? 4096 : bytes + bytes / 4;
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
+inline hipError_t device_alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+inline hipError_t pinned_alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
 
-// page-locked host memory: what the copy engines read and write without a bounce through the runtime's own staging
-struct PinBuf {
+// A buffer that only grows: a request above the capacity frees the block and allocates one a quarter larger (at least kMin bytes).
+template <hipError_t (*Alloc)(void**, size_t), hipError_t (*Free)(void*), size_t kMin>
+struct GrowBuf {
     void* p = nullptr;
     size_t cap = 0;
     hipError_t reserve(size_t bytes)
     {
         if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes < 65536 ? 65536 : bytes + bytes / 4;
-        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
+        release();
+        const size_t want = bytes < kMin ? kMin : bytes + bytes / 4;
+        const hipError_t e = Alloc(&p, want);
         if (e == hipSuccess) cap = want;
         return e;
     }
     void release()
     {
-        if (p) (void)hipHostFree(p);
+        if (p) (void)Free(p);
         p = nullptr;
         cap = 0;
     }
 };
+using DevBuf = GrowBuf<device_alloc, hipFree, 4096>;
+// page-locked host memory: what the copy engines read and write without a bounce through the runtime's own staging
+using PinBuf = GrowBuf<pinned_alloc, hipHostFree, 65536>;
 
 // What one gms_filter_device call needs beyond its arguments.
 struct WsNeed {
@@ -457,6 +441,79 @@ using gms::CopyJob;
 using gms::CopyPool;
 using gms::pack_xy;
 
+bool desc_kind_ok(int kind) { return kind == GMS_DESC_HAMMING256 || kind == GMS_DESC_L2_F32X128; }
+size_t desc_row_bytes(int kind) { return kind == GMS_DESC_HAMMING256 ? 32 : 512; }
+
+// The body of an entry point that is one launch on the context's stream: launch() -> hipError_t, run with the context locked and
+// its device selected.
+template <class Launch>
+int on_ctx(gms_ctx* c, Launch&& launch)
+{
+    std::lock_guard<std::mutex> lock(c->mu);
+    GMS_HIP(hipSetDevice(c->device));
+    GMS_HIP(launch());
+    return GMS_OK;
+}
+
+// ---- the one-shot host entry points ------------------------------------------------------------------------------------
+// Such a call keeps everything it needs in one device block (gms::BlockLayout says where), allocated on the current device and
+// freed when the call returns. DevBlock owns the block and the call's sticky HIP error: once a step has failed the later ones
+// are skipped, and the block is freed only after the stream has been waited for -- also on failure and on an early return, so
+// that nothing in flight still uses it.
+class DevBlock {
+public:
+    DevBlock(const gms::BlockLayout& layout, hipStream_t stream) : st_(stream) { err_ = hipMalloc(&p_, layout.total()); }
+    ~DevBlock() { release(); }
+    DevBlock(const DevBlock&) = delete;
+    DevBlock& operator=(const DevBlock&) = delete;
+
+    template <class T = void>
+    T* at(size_t offset) const { return reinterpret_cast<T*>(static_cast<char*>(p_) + offset); }
+    bool ok() const { return err_ == hipSuccess; }
+    // the steps: launch(stream) -> hipError_t, and copies between host memory and a region
+    template <class Launch>
+    void run(Launch&& launch)
+    {
+        if (!ok()) return;
+        busy_ = true;
+        err_ = launch(st_);
+    }
+    void in(size_t offset, const void* src, size_t bytes) { run([&](hipStream_t st) { return hipMemcpyAsync(at(offset), src, bytes, hipMemcpyHostToDevice, st); }); }
+    void out(void* dst, size_t offset, size_t bytes) { run([&](hipStream_t st) { return hipMemcpyAsync(dst, at(offset), bytes, hipMemcpyDeviceToHost, st); }); }
+    // for a call that reads what it copied out before it goes on: wait for the steps so far / copy out and wait, in one blocking copy
+    void sync() { wait([&] { return hipStreamSynchronize(st_); }); }
+    void out_now(void* dst, size_t offset, size_t bytes) { wait([&] { return hipMemcpy(dst, at(offset), bytes, hipMemcpyDeviceToHost); }); }
+    // The end of the call: waits, frees the block, records the error for gms_last_hip_error() -> GMS_OK or GMS_ERR_HIP.
+    int finish()
+    {
+        release();
+        GMS_HIP(err_);
+        return GMS_OK;
+    }
+
+private:
+    template <class Wait>
+    void wait(Wait&& w)
+    {
+        if (ok()) err_ = w();
+        busy_ = !ok();
+    }
+    void release()
+    {
+        if (!p_) return;
+        if (busy_) {  // (also behind a failed step: earlier ones may still be running)
+            const hipError_t e = hipStreamSynchronize(st_);
+            if (ok()) err_ = e;
+        }
+        (void)hipFree(p_);
+        p_ = nullptr;
+    }
+    void* p_ = nullptr;
+    hipStream_t st_;
+    hipError_t err_;
+    bool busy_ = false;  // steps were enqueued since the stream was last waited for
+};
+
 }  // namespace
 
 extern "C" {
@@ -498,29 +555,29 @@ int gms_ctx_create(int device, gms_ctx** out_ctx)
     gms_ctx* c = new (std::nothrow) gms_ctx;
     if (!c) return GMS_ERR_BAD_ARG;
     c->device = device;
-    e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->lane[1].stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->lane[2].stream, hipStreamNonBlocking);
-    for (Lane& l : c->lane) {
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&l.ev_res, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&l.ev_out, hipEventDisableTiming);
-    }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ws_event, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->verdict_event, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&c->verdict, 64, hipHostMallocDefault);
-    if (e == hipSuccess) {
+    const int rc = [c] {  // (what a failed step leaves behind is destroyed below)
+        GMS_HIP(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+        GMS_HIP(hipStreamCreateWithFlags(&c->lane[1].stream, hipStreamNonBlocking));
+        GMS_HIP(hipStreamCreateWithFlags(&c->lane[2].stream, hipStreamNonBlocking));
+        for (Lane& l : c->lane) {
+            GMS_HIP(hipEventCreateWithFlags(&l.ev_res, hipEventDisableTiming));
+            GMS_HIP(hipEventCreateWithFlags(&l.ev_out, hipEventDisableTiming));
+        }
+        GMS_HIP(hipEventCreateWithFlags(&c->ws_event, hipEventDisableTiming));
+        GMS_HIP(hipEventCreateWithFlags(&c->verdict_event, hipEventDisableTiming));
+        GMS_HIP(hipHostMalloc((void**)&c->verdict, 64, hipHostMallocDefault));
         c->verdict[0] = 0;
         c->verdict[1] = 0x1D | (16 << 8);
         c->verdict[2] = 0;
-    }
-    if (e == hipSuccess) e = c->probe_stats.reserve(128);  // [0..13] probe counters (probe_verdict_kernel), [16..23] flag words of the pair-table check
-    if (e == hipSuccess) e = hipMemset(c->probe_stats.p, 0, 128);
-    if (e == hipSuccess) e = gms::init_filter_kernels();
-    if (e == hipSuccess) e = gms::init_band_kernels();
-    if (e == hipSuccess) e = gms::init_stream_kernels();
-    if (e == hipSuccess) e = gms::init_big_kernels();
-    if (e != hipSuccess) {
-        t_last_hip = (int)e;
+        GMS_HIP(c->probe_stats.reserve(128));  // [0..13] probe counters (probe_verdict_kernel), [16..23] flag words of the pair-table check
+        GMS_HIP(hipMemset(c->probe_stats.p, 0, 128));
+        GMS_HIP(gms::init_filter_kernels());
+        GMS_HIP(gms::init_band_kernels());
+        GMS_HIP(gms::init_stream_kernels());
+        GMS_HIP(gms::init_big_kernels());
+        return GMS_OK;
+    }();
+    if (rc != GMS_OK) {
         if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
         if (c->lane[1].stream) (void)hipStreamDestroy(c->lane[1].stream);
         if (c->lane[2].stream) (void)hipStreamDestroy(c->lane[2].stream);
@@ -533,7 +590,7 @@ int gms_ctx_create(int device, gms_ctx** out_ctx)
         if (c->verdict) (void)hipHostFree(c->verdict);
         c->probe_stats.release();
         delete c;
-        return GMS_ERR_HIP;
+        return rc;
     }
     c->stream = c->own_stream;
     hipDeviceProp_t prop;
@@ -652,10 +709,7 @@ int gms_normalize_device(gms_ctx* c, const gms_keypoint* d_kp, const int64_t* d_
     if (!c || n_frames < 0 || total_kp < 0) return GMS_ERR_BAD_ARG;
     if (total_kp == 0 || n_frames == 0) return GMS_OK;
     if (!d_kp || !d_frame_off || !d_wh || !d_pts) return GMS_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_normalize(d_kp, (int)sizeof(gms_keypoint), d_frame_off, d_wh, n_frames, total_kp, d_pts, c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] { return gms::launch_normalize(d_kp, (int)sizeof(gms_keypoint), d_frame_off, d_wh, n_frames, total_kp, d_pts, c->stream); });
 }
 
 int gms_filter_device(gms_ctx* c, const float* d_pts, const int64_t* d_frame_off, int n_frames,
@@ -960,13 +1014,10 @@ int gms_bf_prepare_device(gms_ctx* c, int desc_kind, const void* d_desc, const i
                           int64_t total_desc, void* d_prepared)
 {
     if (!c || n_frames < 0 || total_desc < 0) return GMS_ERR_BAD_ARG;
-    if (desc_kind != GMS_DESC_HAMMING256 && desc_kind != GMS_DESC_L2_F32X128) return GMS_ERR_BAD_ARG;
+    if (!desc_kind_ok(desc_kind)) return GMS_ERR_BAD_ARG;
     if (total_desc == 0 || n_frames == 0) return GMS_OK;
     if (!d_desc || !d_frame_off || !d_prepared) return GMS_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_bf_prepare(desc_kind, d_desc, d_frame_off, n_frames, total_desc, d_prepared, c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] { return gms::launch_bf_prepare(desc_kind, d_desc, d_frame_off, n_frames, total_desc, d_prepared, c->stream); });
 }
 
 int gms_bfmatch_device(gms_ctx* c, int desc_kind, const void* d_desc, const void* d_prepared, int64_t total_desc,
@@ -974,16 +1025,15 @@ int gms_bfmatch_device(gms_ctx* c, int desc_kind, const void* d_desc, const void
                        gms_dmatch* d_matches)
 {
     if (!c || n_frames < 0 || n_pairs < 0 || max_query < 0 || total_desc < 0) return GMS_ERR_BAD_ARG;
-    if (desc_kind != GMS_DESC_HAMMING256 && desc_kind != GMS_DESC_L2_F32X128) return GMS_ERR_BAD_ARG;
+    if (!desc_kind_ok(desc_kind)) return GMS_ERR_BAD_ARG;
     if (n_pairs == 0 || max_query == 0) return GMS_OK;
     if (!d_desc || !d_frame_off || !d_pairs || !d_matches) return GMS_ERR_BAD_ARG;
     if (desc_kind == GMS_DESC_L2_F32X128 && !d_prepared) return GMS_ERR_BAD_ARG;
     if (max_query > (1 << 22)) return GMS_ERR_CAPACITY;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_bf_match(desc_kind, d_desc, d_prepared, total_desc, d_frame_off, n_frames, d_pairs, n_pairs, max_query,
-                                 d_matches, c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] {
+        return gms::launch_bf_match(desc_kind, d_desc, d_prepared, total_desc, d_frame_off, n_frames, d_pairs, n_pairs, max_query, d_matches,
+                                    c->stream);
+    });
 }
 
 size_t gms_bf_select_workspace_bytes(int n_pairs, int max_rows, int64_t total_backward_rows)
@@ -994,7 +1044,7 @@ size_t gms_bf_select_workspace_bytes(int n_pairs, int max_rows, int64_t total_ba
 
 static bool bf_select_args_ok(int desc_kind, int cross_check, double coef, int max_size)
 {
-    return (desc_kind == GMS_DESC_HAMMING256 || desc_kind == GMS_DESC_L2_F32X128) && (cross_check == 0 || cross_check == 1) &&
+    return desc_kind_ok(desc_kind) && (cross_check == 0 || cross_check == 1) &&
            std::isfinite(coef) && coef >= 1.0 && max_size >= 0;
 }
 
@@ -1013,11 +1063,10 @@ int gms_bf_select_device(gms_ctx* c, int desc_kind, const void* d_desc, const vo
     const size_t fixed = gms::bf_select_ws_bytes(n_pairs, max_rows, 0);
     if (ws_bytes < fixed) return GMS_ERR_BAD_ARG;
     const int64_t total_back = (int64_t)((ws_bytes - fixed) / 256) * 16;  // whole 256-byte blocks, as the layout aligns them
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_bf_select(desc_kind, d_desc, d_prepared, total_desc, d_frame_off, n_frames, d_pairs, n_pairs, max_rows, total_back,
-                                  cross_check, distance_coef, max_size, d_ws, d_out, d_bf_results, d_pair_results, c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] {
+        return gms::launch_bf_select(desc_kind, d_desc, d_prepared, total_desc, d_frame_off, n_frames, d_pairs, n_pairs, max_rows, total_back,
+                                     cross_check, distance_coef, max_size, d_ws, d_out, d_bf_results, d_pair_results, c->stream);
+    });
 }
 
 int gms_bf_match_select(int desc_kind, const void* desc1, int n1, const void* desc2, int n2, int cross_check, double distance_coef,
@@ -1028,43 +1077,34 @@ int gms_bf_match_select(int desc_kind, const void* desc1, int n1, const void* de
     if (n1 < 0 || n2 < 0 || n1 > (1 << 22) || n2 > (1 << 22) || out_cap < 0 || out_cap > INT32_MAX || !n_out) return GMS_ERR_BAD_ARG;
     if (!bf_select_args_ok(desc_kind, cross_check, distance_coef, max_size)) return GMS_ERR_BAD_ARG;
     if ((n1 > 0 && !desc1) || (n2 > 0 && !desc2) || (out_cap > 0 && !out)) return GMS_ERR_BAD_ARG;
-    const size_t row = desc_kind == GMS_DESC_HAMMING256 ? 32 : 512;
+    const size_t row = desc_row_bytes(desc_kind);
     const int64_t total = (int64_t)n1 + n2;
     const int max_rows = std::max(n1, n2);
     const int64_t back_rows = cross_check ? n2 : n1;
-    const size_t a = 256;
-    auto up = [&](size_t x) { return (x + a - 1) / a * a; };
-    const size_t prep = (size_t)gms::bf_prepared_bytes(desc_kind, total, 2);
-    const size_t ws = gms::bf_select_ws_bytes(1, max_rows, back_rows);
-    // one block: rows | frame offsets | pair | result | prepared tables | workspace | out
-    const size_t o_desc = 0, o_off = up(row * (size_t)total + 16), o_pair = up(o_off + 3 * 8), o_res = up(o_pair + sizeof(gms_pair));
-    const size_t o_prep = up(o_res + sizeof(gms_bf_result)), o_ws = up(o_prep + prep + 16), o_out = up(o_ws + ws);
-    const size_t bytes = o_out + sizeof(gms_dmatch) * (size_t)out_cap + 16;
-    void* blk = nullptr;
-    GMS_HIP(hipMalloc(&blk, bytes));
-    char* d = static_cast<char*>(blk);
+    gms::BlockLayout lay;
+    const size_t o_desc = lay.add(row * (size_t)total, 16), o_off = lay.add(3 * 8), o_pair = lay.add(sizeof(gms_pair));
+    const size_t o_res = lay.add(sizeof(gms_bf_result)), o_prep = lay.add((size_t)gms::bf_prepared_bytes(desc_kind, total, 2), 16);
+    const size_t o_ws = lay.add(gms::bf_select_ws_bytes(1, max_rows, back_rows)), o_out = lay.add(sizeof(gms_dmatch) * (size_t)out_cap, 16);
+    DevBlock blk(lay, nullptr);
     const int64_t off[3] = {0, n1, total};
     const gms_pair pr{0, 1, (int32_t)out_cap, 0, 0};
-    hipStream_t st = nullptr;
-    hipError_t e = hipSuccess;
-    if (n1 > 0) e = hipMemcpyAsync(d + o_desc, desc1, row * (size_t)n1, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && n2 > 0) e = hipMemcpyAsync(d + o_desc + row * (size_t)n1, desc2, row * (size_t)n2, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + o_off, off, sizeof(off), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + o_pair, &pr, sizeof(pr), hipMemcpyHostToDevice, st);
-    const int64_t* d_off = reinterpret_cast<const int64_t*>(d + o_off);
-    if (e == hipSuccess && total > 0) e = gms::launch_bf_prepare(desc_kind, d + o_desc, d_off, 2, total, d + o_prep, st);
-    if (e == hipSuccess)
-        e = gms::launch_bf_select(desc_kind, d + o_desc, d + o_prep, total, d_off, 2, reinterpret_cast<const gms_pair*>(d + o_pair), 1,
-                                  max_rows, back_rows, cross_check, distance_coef, max_size, d + o_ws, reinterpret_cast<gms_dmatch*>(d + o_out),
-                                  reinterpret_cast<gms_bf_result*>(d + o_res), nullptr, st);
+    if (n1 > 0) blk.in(o_desc, desc1, row * (size_t)n1);
+    if (n2 > 0) blk.in(o_desc + row * (size_t)n1, desc2, row * (size_t)n2);
+    blk.in(o_off, off, sizeof(off));
+    blk.in(o_pair, &pr, sizeof(pr));
+    if (total > 0)
+        blk.run([&](hipStream_t st) { return gms::launch_bf_prepare(desc_kind, blk.at(o_desc), blk.at<int64_t>(o_off), 2, total, blk.at(o_prep), st); });
+    blk.run([&](hipStream_t st) {
+        return gms::launch_bf_select(desc_kind, blk.at(o_desc), blk.at(o_prep), total, blk.at<int64_t>(o_off), 2, blk.at<gms_pair>(o_pair), 1,
+                                     max_rows, back_rows, cross_check, distance_coef, max_size, blk.at(o_ws), blk.at<gms_dmatch>(o_out),
+                                     blk.at<gms_bf_result>(o_res), nullptr, st);
+    });
+    // the result record first, then exactly the matches it counts
     gms_bf_result r{0, 0, 0, 0.0f, GMS_OK};
-    if (e == hipSuccess) e = hipMemcpyAsync(&r, d + o_res, sizeof(r), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess && r.status == GMS_OK && r.n_out > 0)
-        e = hipMemcpy(out, d + o_out, sizeof(gms_dmatch) * (size_t)r.n_out, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) (void)hipStreamSynchronize(st);
-    (void)hipFree(blk);
-    GMS_HIP(e);
+    blk.out(&r, o_res, sizeof(r));
+    blk.sync();
+    if (blk.ok() && r.status == GMS_OK && r.n_out > 0) blk.out_now(out, o_out, sizeof(gms_dmatch) * (size_t)r.n_out);
+    GMS_TRY(blk.finish());
     *n_out = r.n_out;
     if (result) *result = r;
     return r.status;
@@ -1093,38 +1133,30 @@ int gms_bf_select_host_batch(gms_ctx* c, int desc_kind, const void* desc, const 
     }
     if (max_rows > (1 << 22)) return GMS_ERR_CAPACITY;
     if (out_len > 0 && !out) return GMS_ERR_BAD_ARG;
-    const size_t row = desc_kind == GMS_DESC_HAMMING256 ? 32 : 512;
-    const size_t prep = (size_t)gms::bf_prepared_bytes(desc_kind, total, n_frames);
-    const size_t ws = gms::bf_select_ws_bytes(n_pairs, max_rows, back);
+    const size_t row = desc_row_bytes(desc_kind), b_off = 8 * ((size_t)n_frames + 1), b_pairs = sizeof(gms_pair) * (size_t)n_pairs;
+    const size_t b_res = sizeof(gms_bf_result) * (size_t)n_pairs, b_out = sizeof(gms_dmatch) * (size_t)out_len;
+    gms::BlockLayout lay;
+    const size_t o_desc = lay.add(row * (size_t)total, 16), o_off = lay.add(b_off), o_pairs = lay.add(b_pairs), o_res = lay.add(b_res);
+    const size_t o_prep = lay.add((size_t)gms::bf_prepared_bytes(desc_kind, total, n_frames), 16);
+    const size_t o_ws = lay.add(gms::bf_select_ws_bytes(n_pairs, max_rows, back)), o_out = lay.add(b_out, 16);
     std::lock_guard<std::mutex> lock(c->mu);
     GMS_HIP(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    // one block: rows | offsets | pairs | results | prepared tables | workspace | out, each 256-byte aligned
-    const size_t a = 256;
-    auto up = [&](size_t x) { return (x + a - 1) / a * a; };
-    const size_t o_desc = 0, o_off = up(row * (size_t)total + 16), o_pairs = up(o_off + 8 * ((size_t)n_frames + 1));
-    const size_t o_res = up(o_pairs + sizeof(gms_pair) * (size_t)n_pairs), o_prep = up(o_res + sizeof(gms_bf_result) * (size_t)n_pairs);
-    const size_t o_ws = up(o_prep + prep + 16), o_out = up(o_ws + ws), bytes = o_out + sizeof(gms_dmatch) * (size_t)out_len + 16;
-    void* blk = nullptr;
-    GMS_HIP(hipMalloc(&blk, bytes));
-    char* d = static_cast<char*>(blk);
-    const int64_t* d_off = reinterpret_cast<const int64_t*>(d + o_off);
-    hipError_t e = hipSuccess;
-    if (total > 0) e = hipMemcpyAsync(d + o_desc, desc, row * (size_t)total, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + o_off, frame_off, 8 * ((size_t)n_frames + 1), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + o_pairs, pairs, sizeof(gms_pair) * (size_t)n_pairs, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && total > 0) e = gms::launch_bf_prepare(desc_kind, d + o_desc, d_off, n_frames, total, d + o_prep, st);
-    if (e == hipSuccess)
-        e = gms::launch_bf_select(desc_kind, d + o_desc, d + o_prep, total, d_off, n_frames, reinterpret_cast<const gms_pair*>(d + o_pairs),
-                                  n_pairs, (int)max_rows, back, cross_check, distance_coef, max_size, d + o_ws,
-                                  reinterpret_cast<gms_dmatch*>(d + o_out), reinterpret_cast<gms_bf_result*>(d + o_res), nullptr, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(results, d + o_res, sizeof(gms_bf_result) * (size_t)n_pairs, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out_len > 0) e = hipMemcpyAsync(out, d + o_out, sizeof(gms_dmatch) * (size_t)out_len, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    else (void)hipStreamSynchronize(st);
-    (void)hipFree(blk);
-    GMS_HIP(e);
-    return GMS_OK;
+    DevBlock blk(lay, c->stream);
+    if (total > 0) blk.in(o_desc, desc, row * (size_t)total);
+    blk.in(o_off, frame_off, b_off);
+    blk.in(o_pairs, pairs, b_pairs);
+    if (total > 0)
+        blk.run([&](hipStream_t st) {
+            return gms::launch_bf_prepare(desc_kind, blk.at(o_desc), blk.at<int64_t>(o_off), n_frames, total, blk.at(o_prep), st);
+        });
+    blk.run([&](hipStream_t st) {
+        return gms::launch_bf_select(desc_kind, blk.at(o_desc), blk.at(o_prep), total, blk.at<int64_t>(o_off), n_frames, blk.at<gms_pair>(o_pairs),
+                                     n_pairs, (int)max_rows, back, cross_check, distance_coef, max_size, blk.at(o_ws), blk.at<gms_dmatch>(o_out),
+                                     blk.at<gms_bf_result>(o_res), nullptr, st);
+    });
+    blk.out(results, o_res, b_res);
+    if (out_len > 0) blk.out(out, o_out, b_out);
+    return blk.finish();
 }
 
 // ---- StereoBM (stereo_bm_kernels.hip) ----------------------------------------------------------------------------
@@ -1150,10 +1182,7 @@ int gms_stereo_bm_device(gms_ctx* c, const gms_stereo_bm_params* params, const u
     if ((reinterpret_cast<uintptr_t>(d_ws) & 255u) || (reinterpret_cast<uintptr_t>(d_disp16) & 1u) ||
         (reinterpret_cast<uintptr_t>(d_cost) & 3u) || ws_bytes < gms::stereo_bm_ws_bytes(n_pairs, width, height))
         return GMS_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_stereo_bm(p, d_left, d_right, n_pairs, width, height, pitch, d_ws, d_disp16, d_cost, c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] { return gms::launch_stereo_bm(p, d_left, d_right, n_pairs, width, height, pitch, d_ws, d_disp16, d_cost, c->stream); });
 }
 
 int gms_stereo_bm_normalize_device(gms_ctx* c, const int16_t* d_disp16, int n, int width, int height, uint8_t* d_out8)
@@ -1161,10 +1190,7 @@ int gms_stereo_bm_normalize_device(gms_ctx* c, const int16_t* d_disp16, int n, i
     if (!c || n < 0 || width <= 0 || height <= 0) return GMS_ERR_BAD_ARG;
     if (n == 0) return GMS_OK;
     if (!d_disp16 || !d_out8 || (reinterpret_cast<uintptr_t>(d_disp16) & 1u)) return GMS_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_stereo_bm_normalize(d_disp16, n, width, height, d_out8, c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] { return gms::launch_stereo_bm_normalize(d_disp16, n, width, height, d_out8, c->stream); });
 }
 
 int gms_stereo_bm(const gms_stereo_bm_params* params, const uint8_t* left, const uint8_t* right, int width, int height, int pitch,
@@ -1173,30 +1199,21 @@ int gms_stereo_bm(const gms_stereo_bm_params* params, const uint8_t* left, const
     const gms_stereo_bm_params& p = sbm_params(params);
     if (!sbm::params_ok(p, width, height) || pitch < width || !left || !right) return GMS_ERR_BAD_ARG;
     const size_t px = (size_t)width * (size_t)height, img = (size_t)pitch * (size_t)(height - 1) + (size_t)width;
-    const size_t a = 256;
-    auto up = [&](size_t x) { return (x + a - 1) / a * a; };
-    // one block: left | right (pitch as given) | workspace | int16 map | costs | 8-bit map
-    const size_t o_r = up(img), o_ws = up(o_r + img), o_d = o_ws + up(gms::stereo_bm_ws_bytes(1, width, height));
-    const size_t o_c = up(o_d + 2 * px), o_8 = up(o_c + 4 * px), bytes = o_8 + px;
-    void* blk = nullptr;
-    GMS_HIP(hipMalloc(&blk, bytes));
-    char* d = static_cast<char*>(blk);
-    hipStream_t st = nullptr;
-    int16_t* d_disp = reinterpret_cast<int16_t*>(d + o_d);
-    hipError_t e = hipMemcpyAsync(d, left, img, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + o_r, right, img, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
-        e = gms::launch_stereo_bm(p, reinterpret_cast<const uint8_t*>(d), reinterpret_cast<const uint8_t*>(d + o_r), 1, width, height,
-                                  pitch, d + o_ws, d_disp, cost ? reinterpret_cast<int32_t*>(d + o_c) : nullptr, st);
-    if (e == hipSuccess && disp8) e = gms::launch_stereo_bm_normalize(d_disp, 1, width, height, reinterpret_cast<uint8_t*>(d + o_8), st);
-    if (e == hipSuccess && disp16) e = hipMemcpyAsync(disp16, d_disp, 2 * px, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && cost) e = hipMemcpyAsync(cost, d + o_c, 4 * px, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && disp8) e = hipMemcpyAsync(disp8, d + o_8, px, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    else (void)hipStreamSynchronize(st);
-    (void)hipFree(blk);
-    GMS_HIP(e);
-    return GMS_OK;
+    gms::BlockLayout lay;  // the images keep the caller's pitch
+    const size_t o_l = lay.add(img), o_r = lay.add(img), o_ws = lay.add(gms::stereo_bm_ws_bytes(1, width, height));
+    const size_t o_d = lay.add(2 * px), o_c = lay.add(4 * px), o_8 = lay.add(px);
+    DevBlock blk(lay, nullptr);
+    blk.in(o_l, left, img);
+    blk.in(o_r, right, img);
+    blk.run([&](hipStream_t st) {
+        return gms::launch_stereo_bm(p, blk.at<uint8_t>(o_l), blk.at<uint8_t>(o_r), 1, width, height, pitch, blk.at(o_ws), blk.at<int16_t>(o_d),
+                                     cost ? blk.at<int32_t>(o_c) : nullptr, st);
+    });
+    if (disp8) blk.run([&](hipStream_t st) { return gms::launch_stereo_bm_normalize(blk.at<int16_t>(o_d), 1, width, height, blk.at<uint8_t>(o_8), st); });
+    if (disp16) blk.out(disp16, o_d, 2 * px);
+    if (cost) blk.out(cost, o_c, 4 * px);
+    if (disp8) blk.out(disp8, o_8, px);
+    return blk.finish();
 }
 
 // ---- portrait mode (portrait_kernels.hip) --------------------------------------------------------------------------
@@ -1221,11 +1238,10 @@ int gms_portrait_device(gms_ctx* c, const gms_portrait_params* params, const uin
     if (!d_bgr || !d_disparity || !d_ws || !d_out_bgr || (reinterpret_cast<uintptr_t>(d_ws) & 255u) ||
         ws_bytes < gms::portrait_ws_bytes(n, width, height))
         return GMS_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_portrait(p, d_bgr, d_disparity, n, width, height, pitch_bgr, pitch_disp, d_ws, d_out_bgr, d_mask, d_selected,
-                                 d_blurred, c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] {
+        return gms::launch_portrait(p, d_bgr, d_disparity, n, width, height, pitch_bgr, pitch_disp, d_ws, d_out_bgr, d_mask, d_selected, d_blurred,
+                                    c->stream);
+    });
 }
 
 int gms_portrait_profile_device(gms_ctx* c, const gms_portrait_params* params, const uint8_t* d_bgr, const uint8_t* d_disparity, int n,
@@ -1263,28 +1279,22 @@ int gms_median_blur_device(gms_ctx* c, const uint8_t* d_src, int n, int width, i
     const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
     const uintptr_t span = (uintptr_t)n * (uintptr_t)height * (uintptr_t)pitch;
     if (s0 < d0 + span && d0 < s0 + span) return GMS_ERR_BAD_ARG;  // the destination may not overlap the source
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_median_blur(d_src, n, width, height, channels, pitch, ksize, d_dst, c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] { return gms::launch_median_blur(d_src, n, width, height, channels, pitch, ksize, d_dst, c->stream); });
 }
 
 int gms_median_blur(const uint8_t* src, int width, int height, int channels, int ksize, uint8_t* dst)
 {
     if (!pm::median_ok(width, height, channels, ksize) || !src || !dst) return GMS_ERR_BAD_ARG;
-    const size_t bytes = (size_t)width * (size_t)height * (size_t)channels, o_dst = (bytes + 255) / 256 * 256;
-    void* blk = nullptr;
-    GMS_HIP(hipMalloc(&blk, o_dst + bytes));
-    uint8_t* d = static_cast<uint8_t*>(blk);
-    hipStream_t st = nullptr;
-    hipError_t e = hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = gms::launch_median_blur(d, 1, width, height, channels, width * channels, ksize, d + o_dst, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dst, d + o_dst, bytes, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    else (void)hipStreamSynchronize(st);
-    (void)hipFree(blk);
-    GMS_HIP(e);
-    return GMS_OK;
+    const size_t bytes = (size_t)width * (size_t)height * (size_t)channels;
+    gms::BlockLayout lay;
+    const size_t o_src = lay.add(bytes), o_dst = lay.add(bytes);
+    DevBlock blk(lay, nullptr);
+    blk.in(o_src, src, bytes);
+    blk.run([&](hipStream_t st) {
+        return gms::launch_median_blur(blk.at<uint8_t>(o_src), 1, width, height, channels, width * channels, ksize, blk.at<uint8_t>(o_dst), st);
+    });
+    blk.out(dst, o_dst, bytes);
+    return blk.finish();
 }
 
 int gms_portrait(const gms_portrait_params* params, const uint8_t* bgr, const uint8_t* disparity, int width, int height, uint8_t* out_bgr,
@@ -1293,29 +1303,22 @@ int gms_portrait(const gms_portrait_params* params, const uint8_t* bgr, const ui
     const gms_portrait_params& p = pm_params(params);
     if (!pm::params_ok(p, width, height) || !bgr || !disparity || !out_bgr) return GMS_ERR_BAD_ARG;
     const size_t px = (size_t)width * (size_t)height;
-    const size_t a = 256;
-    auto up = [&](size_t x) { return (x + a - 1) / a * a; };
-    // one block: image | disparity | workspace | portrait | mask | selected | blurred
-    const size_t o_d = up(3 * px), o_ws = up(o_d + px), o_out = o_ws + up(gms::portrait_ws_bytes(1, width, height));
-    const size_t o_m = up(o_out + 3 * px), o_s = up(o_m + px), o_b = up(o_s + px), bytes = o_b + 3 * px;
-    void* blk = nullptr;
-    GMS_HIP(hipMalloc(&blk, bytes));
-    uint8_t* d = static_cast<uint8_t*>(blk);
-    hipStream_t st = nullptr;
-    hipError_t e = hipMemcpyAsync(d, bgr, 3 * px, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + o_d, disparity, px, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
-        e = gms::launch_portrait(p, d, d + o_d, 1, width, height, 3 * width, width, d + o_ws, d + o_out, mask ? d + o_m : nullptr,
-                                 selected ? d + o_s : nullptr, blurred ? d + o_b : nullptr, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_bgr, d + o_out, 3 * px, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && mask) e = hipMemcpyAsync(mask, d + o_m, px, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && selected) e = hipMemcpyAsync(selected, d + o_s, px, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && blurred) e = hipMemcpyAsync(blurred, d + o_b, 3 * px, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    else (void)hipStreamSynchronize(st);
-    (void)hipFree(blk);
-    GMS_HIP(e);
-    return GMS_OK;
+    gms::BlockLayout lay;
+    const size_t o_img = lay.add(3 * px), o_d = lay.add(px), o_ws = lay.add(gms::portrait_ws_bytes(1, width, height)), o_out = lay.add(3 * px);
+    const size_t o_m = lay.add(px), o_s = lay.add(px), o_b = lay.add(3 * px);
+    DevBlock blk(lay, nullptr);
+    blk.in(o_img, bgr, 3 * px);
+    blk.in(o_d, disparity, px);
+    blk.run([&](hipStream_t st) {
+        return gms::launch_portrait(p, blk.at<uint8_t>(o_img), blk.at<uint8_t>(o_d), 1, width, height, 3 * width, width, blk.at(o_ws),
+                                    blk.at<uint8_t>(o_out), mask ? blk.at<uint8_t>(o_m) : nullptr, selected ? blk.at<uint8_t>(o_s) : nullptr,
+                                    blurred ? blk.at<uint8_t>(o_b) : nullptr, st);
+    });
+    blk.out(out_bgr, o_out, 3 * px);
+    if (mask) blk.out(mask, o_m, px);
+    if (selected) blk.out(selected, o_s, px);
+    if (blurred) blk.out(blurred, o_b, 3 * px);
+    return blk.finish();
 }
 
 int gms_disparity_device(gms_ctx* c, const gms_keypoint* d_kp1, int n1, const gms_keypoint* d_kp2, int n2,
@@ -1326,11 +1329,10 @@ int gms_disparity_device(gms_ctx* c, const gms_keypoint* d_kp1, int n1, const gm
     if (!d_n_matches || !d_disparity || !d_work || !d_stats || (d_gt && disp_ratio == 0)) return GMS_ERR_BAD_ARG;
     if (max_matches > 0 && (!d_kp1 || !d_kp2 || !d_matches)) return GMS_ERR_BAD_ARG;
     if (max_matches >= (1 << 24)) return GMS_ERR_CAPACITY;  // the scatter key keeps the match index in 24 bits
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_disparity(d_kp1, n1, d_kp2, n2, d_matches, d_n_matches, max_matches, width, height, d_gt, disp_ratio,
-                                  d_disparity, d_work, d_stats, c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] {
+        return gms::launch_disparity(d_kp1, n1, d_kp2, n2, d_matches, d_n_matches, max_matches, width, height, d_gt, disp_ratio, d_disparity, d_work,
+                                     d_stats, c->stream);
+    });
 }
 
 int gms_gather_points_device(gms_ctx* c, const gms_keypoint* d_kp1, int n1, const gms_keypoint* d_kp2, int n2,
@@ -1339,11 +1341,9 @@ int gms_gather_points_device(gms_ctx* c, const gms_keypoint* d_kp1, int n1, cons
 {
     if (!c || n1 < 0 || n2 < 0 || max_matches < 0 || !d_n_matches || !d_status) return GMS_ERR_BAD_ARG;
     if (max_matches > 0 && (!d_kp1 || !d_kp2 || !d_matches || !d_coords1 || !d_coords2)) return GMS_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_gather_points(d_kp1, n1, d_kp2, n2, d_matches, d_n_matches, max_matches, d_coords1, d_coords2, d_status,
-                                      c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] {
+        return gms::launch_gather_points(d_kp1, n1, d_kp2, n2, d_matches, d_n_matches, max_matches, d_coords1, d_coords2, d_status, c->stream);
+    });
 }
 
 int gms_triangulate_device(gms_ctx* c, const double camera[4], const double dist[5], const double P1[12], const double P2[12],
@@ -1353,10 +1353,9 @@ int gms_triangulate_device(gms_ctx* c, const double camera[4], const double dist
     if (!c || !camera || !P1 || !P2 || !d_n_matches || !d_stats || max_matches < 0) return GMS_ERR_BAD_ARG;
     if (max_matches > 0 && (!d_coords1 || !d_coords2 || !d_points3d)) return GMS_ERR_BAD_ARG;
     if (camera[0] == 0.0 || camera[1] == 0.0) return GMS_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_triangulate(camera, dist, P1, P2, d_coords1, d_coords2, d_n_matches, max_matches, d_points3d, d_stats, c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] {
+        return gms::launch_triangulate(camera, dist, P1, P2, d_coords1, d_coords2, d_n_matches, max_matches, d_points3d, d_stats, c->stream);
+    });
 }
 
 int gms_recover_pose_device(gms_ctx* c, const double E[9], const double camera[4], const float* d_coords1, const float* d_coords2,
@@ -1395,11 +1394,10 @@ int gms_gather_points_batch_device(gms_ctx* c, const gms_keypoint* d_kp, const i
     if (n_pairs == 0) return GMS_OK;
     if (!d_frame_off || !d_pairs || !d_results || !d_tv) return GMS_ERR_BAD_ARG;
     if (max_m > 0 && (!d_kp || !d_filtered || !d_coords1 || !d_coords2)) return GMS_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_gather_batch(d_kp, d_frame_off, n_frames, d_pairs, n_pairs, max_m, d_filtered, d_results, d_coords1, d_coords2, d_tv,
-                                     c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] {
+        return gms::launch_gather_batch(d_kp, d_frame_off, n_frames, d_pairs, n_pairs, max_m, d_filtered, d_results, d_coords1, d_coords2, d_tv,
+                                        c->stream);
+    });
 }
 
 int gms_find_essential_batch_device(gms_ctx* c, const gms_camera* camera, double prob, double threshold, int max_iters, const gms_pair* d_pairs,
@@ -1409,10 +1407,9 @@ int gms_find_essential_batch_device(gms_ctx* c, const gms_camera* camera, double
     if (!(prob > 0.0 && prob < 1.0) || !(threshold > 0.0) || max_iters < 1) return GMS_ERR_BAD_ARG;  // (CV_Assert(confidence > 0 && confidence < 1))
     if (n_pairs == 0) return GMS_OK;
     if (!d_pairs || !d_coords1 || !d_coords2 || !d_mask || !d_tv) return GMS_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_find_essential_batch(*camera, prob, threshold, max_iters, d_pairs, n_pairs, d_coords1, d_coords2, d_mask, d_tv, c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] {
+        return gms::launch_find_essential_batch(*camera, prob, threshold, max_iters, d_pairs, n_pairs, d_coords1, d_coords2, d_mask, d_tv, c->stream);
+    });
 }
 
 int gms_recover_pose_batch_device(gms_ctx* c, const gms_camera* camera, int use_in_mask, const gms_pair* d_pairs, int n_pairs,
@@ -1421,10 +1418,9 @@ int gms_recover_pose_batch_device(gms_ctx* c, const gms_camera* camera, int use_
     if (!c || n_pairs < 0 || !camera_ok(camera)) return GMS_ERR_BAD_ARG;
     if (n_pairs == 0) return GMS_OK;
     if (!d_pairs || !d_coords1 || !d_coords2 || !d_mask || !d_tv) return GMS_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_recover_pose_batch(*camera, 50.0, use_in_mask ? 1 : 0, d_pairs, n_pairs, d_coords1, d_coords2, d_mask, d_tv, c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] {
+        return gms::launch_recover_pose_batch(*camera, 50.0, use_in_mask ? 1 : 0, d_pairs, n_pairs, d_coords1, d_coords2, d_mask, d_tv, c->stream);
+    });
 }
 
 int gms_triangulate_batch_device(gms_ctx* c, const gms_camera* camera, const gms_pair* d_pairs, int n_pairs, const float* d_coords1,
@@ -1433,10 +1429,9 @@ int gms_triangulate_batch_device(gms_ctx* c, const gms_camera* camera, const gms
     if (!c || n_pairs < 0 || !camera_ok(camera)) return GMS_ERR_BAD_ARG;
     if (n_pairs == 0) return GMS_OK;
     if (!d_pairs || !d_coords1 || !d_coords2 || !d_points3d || !d_tv) return GMS_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_triangulate_batch(*camera, d_pairs, n_pairs, d_coords1, d_coords2, d_mask, d_points3d, d_tv, c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] {
+        return gms::launch_triangulate_batch(*camera, d_pairs, n_pairs, d_coords1, d_coords2, d_mask, d_points3d, d_tv, c->stream);
+    });
 }
 
 int gms_two_view_batch_device(gms_ctx* c, const gms_camera* camera, double prob, double threshold, int max_iters, const gms_keypoint* d_kp,
@@ -1460,11 +1455,10 @@ int gms_disparity_batch_device(gms_ctx* c, const gms_keypoint* d_kp, const int64
     if (!d_frame_off || !d_wh || !d_pairs || !d_results || !d_disparity || !d_work || !d_stats || (d_gt && disp_ratio == 0)) return GMS_ERR_BAD_ARG;
     if (max_m > 0 && (!d_kp || !d_filtered)) return GMS_ERR_BAD_ARG;
     if (max_m >= (1 << 24)) return GMS_ERR_CAPACITY;  // the scatter key keeps the match index in 24 bits
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_disparity_batch(d_kp, d_frame_off, d_wh, n_frames, d_pairs, n_pairs, max_m, d_filtered, d_results, d_gt, gt_stride, disp_ratio,
-                                        d_disparity, map_stride, d_work, d_stats, c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] {
+        return gms::launch_disparity_batch(d_kp, d_frame_off, d_wh, n_frames, d_pairs, n_pairs, max_m, d_filtered, d_results, d_gt, gt_stride,
+                                           disp_ratio, d_disparity, map_stride, d_work, d_stats, c->stream);
+    });
 }
 
 size_t gms_detect_workspace_bytes(int width, int height, int n_images, int max_keypoints)
@@ -1484,11 +1478,10 @@ int gms_detect_batch_device(gms_ctx* c, const uint8_t* d_images, int n_images, i
     if (n_images == 0) return GMS_OK;
     if (!d_images || !d_workspace || !d_counts || (max_keypoints > 0 && (!d_keypoints || !d_descriptors))) return GMS_ERR_BAD_ARG;
     if (workspace_bytes < gms::detect_workspace_bytes(width, height, n_images, max_keypoints)) return GMS_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_detect(d_images, n_images, width, height, threshold, max_keypoints, d_workspace, d_keypoints, d_descriptors, d_counts,
-                               c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] {
+        return gms::launch_detect(d_images, n_images, width, height, threshold, max_keypoints, d_workspace, d_keypoints, d_descriptors, d_counts,
+                                  c->stream);
+    });
 }
 
 int gms_describe_device(gms_ctx* c, const uint8_t* d_image, int width, int height, gms_keypoint* d_keypoints, int n,
@@ -1497,10 +1490,7 @@ int gms_describe_device(gms_ctx* c, const uint8_t* d_image, int width, int heigh
     if (!c || n < 0 || !detect_image_ok(width, height) || !d_image || !d_workspace || !d_status) return GMS_ERR_BAD_ARG;
     if (n > 0 && (!d_keypoints || !d_descriptors)) return GMS_ERR_BAD_ARG;
     if (workspace_bytes < gms::detect_workspace_bytes(width, height, 1, 0)) return GMS_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_describe(d_image, width, height, d_keypoints, n, d_workspace, d_descriptors, d_status, c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] { return gms::launch_describe(d_image, width, height, d_keypoints, n, d_workspace, d_descriptors, d_status, c->stream); });
 }
 
 // ---- pyramid keypoint source (detect_kernels.hip) -------------------------------------------------------------------------------
@@ -1523,10 +1513,7 @@ int gms_pyramid_build_device(gms_ctx* c, const uint8_t* d_images, int n_images, 
     if (n_images == 0) return GMS_OK;
     const size_t need = gms::pyramid_bytes(width, height, n_images, n_levels);
     if (!d_images || levels_bytes < need || (need > 0 && !d_levels)) return GMS_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_pyramid_build(d_images, n_images, width, height, n_levels, d_levels, c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] { return gms::launch_pyramid_build(d_images, n_images, width, height, n_levels, d_levels, c->stream); });
 }
 
 int gms_detect_pyramid_batch_device(gms_ctx* c, const uint8_t* d_images, int n_images, int width, int height, int threshold, int max_keypoints,
@@ -1538,11 +1525,10 @@ int gms_detect_pyramid_batch_device(gms_ctx* c, const uint8_t* d_images, int n_i
     if (n_images == 0) return GMS_OK;
     if (!d_images || !d_workspace || !d_counts || !d_level_counts || (max_keypoints > 0 && (!d_keypoints || !d_descriptors))) return GMS_ERR_BAD_ARG;
     if (workspace_bytes < gms::detect_pyramid_workspace_bytes(width, height, n_images, max_keypoints, n_levels)) return GMS_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_detect_pyramid(d_images, n_images, width, height, threshold, max_keypoints, n_levels, d_workspace, d_keypoints, d_descriptors,
-                                       d_counts, d_level_counts, c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] {
+        return gms::launch_detect_pyramid(d_images, n_images, width, height, threshold, max_keypoints, n_levels, d_workspace, d_keypoints,
+                                          d_descriptors, d_counts, d_level_counts, c->stream);
+    });
 }
 
 // ---- LOGOS on resident frames (logos_batch_kernels.hip) ----------------------------------------------------------------------
@@ -1565,11 +1551,10 @@ int gms_logos_prepare_device(gms_ctx* c, const gms_keypoint* d_kp, const int64_t
     if (total_kp > 0 && (!d_kp || !d_words)) return GMS_ERR_BAD_ARG;
     if (ws_bytes > 0 && !d_workspace) return GMS_ERR_BAD_ARG;
     if (total_kp > INT32_MAX || (reinterpret_cast<uintptr_t>(d_table) & 15u)) return GMS_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_logos_prepare(d_kp, d_frame_off, n_frames, total_kp, d_words, n_words, d_workspace, ws_bytes, d_table, c->n_cus,
-                                      c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] {
+        return gms::launch_logos_prepare(d_kp, d_frame_off, n_frames, total_kp, d_words, n_words, d_workspace, ws_bytes, d_table, c->n_cus,
+                                         c->stream);
+    });
 }
 
 int gms_logos_filter_device(gms_ctx* c, const void* d_table, const gms_pair* d_pairs, int n_pairs, void* d_workspace, size_t ws_bytes,
@@ -1579,24 +1564,20 @@ int gms_logos_filter_device(gms_ctx* c, const void* d_table, const gms_pair* d_p
     if (n_pairs == 0) return GMS_OK;
     if (!d_table || !d_pairs || !d_workspace || !d_out || !d_logos_results) return GMS_ERR_BAD_ARG;
     if ((int64_t)ws_bytes < gms::logos::filter_fixed_bytes(n_pairs) || (reinterpret_cast<uintptr_t>(d_workspace) & 15u)) return GMS_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_logos_filter(d_table, d_pairs, n_pairs, d_workspace, ws_bytes, d_out, d_logos_results, d_pair_results, c->n_cus,
-                                     c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] {
+        return gms::launch_logos_filter(d_table, d_pairs, n_pairs, d_workspace, ws_bytes, d_out, d_logos_results, d_pair_results, c->n_cus,
+                                        c->stream);
+    });
 }
 
 int gms_logos_words_device(gms_ctx* c, int desc_kind, const void* d_desc, int64_t total_desc, const void* d_dict, int n_words,
                            int32_t* d_words)
 {
     if (!c || total_desc < 0 || n_words < 1 || n_words > 65535 || !d_dict) return GMS_ERR_BAD_ARG;
-    if (desc_kind != GMS_DESC_L2_F32X128 && desc_kind != GMS_DESC_HAMMING256) return GMS_ERR_BAD_ARG;
+    if (!desc_kind_ok(desc_kind)) return GMS_ERR_BAD_ARG;
     if (total_desc == 0) return GMS_OK;
     if (!d_desc || !d_words) return GMS_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_logos_words(desc_kind, d_desc, total_desc, d_dict, n_words, d_words, c->n_cus, c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] { return gms::launch_logos_words(desc_kind, d_desc, total_desc, d_dict, n_words, d_words, c->n_cus, c->stream); });
 }
 
 int gms_logos_host_batch(gms_ctx* c, const gms_keypoint* kp, const int64_t* frame_off, int n_frames, const int32_t* words, int n_words,
@@ -1620,38 +1601,30 @@ int gms_logos_host_batch(gms_ctx* c, const gms_keypoint* kp, const int64_t* fram
     if (out_len > 0 && !out) return GMS_ERR_BAD_ARG;
     const size_t table = (size_t)gms_logos_table_bytes(total_kp, n_frames, n_words);
     const size_t ws = gms_logos_workspace_bytes(max_kp, n_pairs, max_q);
+    const size_t b_kp = sizeof(gms_keypoint) * (size_t)total_kp, b_off = 8 * ((size_t)n_frames + 1), b_words = 4 * (size_t)total_kp;
+    const size_t b_pairs = sizeof(gms_pair) * (size_t)n_pairs, b_res = sizeof(gms_logos_result) * (size_t)n_pairs;
+    const size_t b_out = sizeof(gms_dmatch) * (size_t)out_len;
+    gms::BlockLayout lay;
+    const size_t o_kp = lay.add(b_kp), o_off = lay.add(b_off), o_w = lay.add(b_words), o_pairs = lay.add(b_pairs), o_res = lay.add(b_res);
+    const size_t o_tab = lay.add(table), o_ws = lay.add(ws), o_out = lay.add(b_out, 16);
     std::lock_guard<std::mutex> lock(c->mu);
     GMS_HIP(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    // one block: keypoints | offsets | words | pairs | results | table | workspace | out, each 256-byte aligned
-    const size_t a = 256;
-    auto up = [&](size_t x) { return (x + a - 1) / a * a; };
-    const size_t o_kp = 0, o_off = up(o_kp + sizeof(gms_keypoint) * (size_t)total_kp), o_w = up(o_off + 8 * ((size_t)n_frames + 1));
-    const size_t o_pairs = up(o_w + 4 * (size_t)total_kp), o_res = up(o_pairs + sizeof(gms_pair) * (size_t)n_pairs);
-    const size_t o_tab = up(o_res + sizeof(gms_logos_result) * (size_t)n_pairs), o_ws = up(o_tab + table);
-    const size_t o_out = up(o_ws + ws), bytes = o_out + sizeof(gms_dmatch) * (size_t)out_len + 16;
-    void* blk = nullptr;
-    GMS_HIP(hipMalloc(&blk, bytes));
-    char* d = static_cast<char*>(blk);
-    hipError_t e = hipSuccess;
-    if (total_kp > 0) e = hipMemcpyAsync(d + o_kp, kp, sizeof(gms_keypoint) * (size_t)total_kp, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + o_off, frame_off, 8 * ((size_t)n_frames + 1), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && total_kp > 0) e = hipMemcpyAsync(d + o_w, words, 4 * (size_t)total_kp, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + o_pairs, pairs, sizeof(gms_pair) * (size_t)n_pairs, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
-        e = gms::launch_logos_prepare(reinterpret_cast<const gms_keypoint*>(d + o_kp), reinterpret_cast<const int64_t*>(d + o_off), n_frames,
-                                      total_kp, reinterpret_cast<const int32_t*>(d + o_w), n_words, d + o_ws, ws, d + o_tab, c->n_cus, st);
-    if (e == hipSuccess)
-        e = gms::launch_logos_filter(d + o_tab, reinterpret_cast<const gms_pair*>(d + o_pairs), n_pairs, d + o_ws, ws,
-                                     reinterpret_cast<gms_dmatch*>(d + o_out), reinterpret_cast<gms_logos_result*>(d + o_res), nullptr,
-                                     c->n_cus, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(results, d + o_res, sizeof(gms_logos_result) * (size_t)n_pairs, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && out_len > 0) e = hipMemcpyAsync(out, d + o_out, sizeof(gms_dmatch) * (size_t)out_len, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    else (void)hipStreamSynchronize(st);
-    (void)hipFree(blk);
-    GMS_HIP(e);
-    return GMS_OK;
+    DevBlock blk(lay, c->stream);
+    if (total_kp > 0) blk.in(o_kp, kp, b_kp);
+    blk.in(o_off, frame_off, b_off);
+    if (total_kp > 0) blk.in(o_w, words, b_words);
+    blk.in(o_pairs, pairs, b_pairs);
+    blk.run([&](hipStream_t st) {
+        return gms::launch_logos_prepare(blk.at<gms_keypoint>(o_kp), blk.at<int64_t>(o_off), n_frames, total_kp, blk.at<int32_t>(o_w), n_words,
+                                         blk.at(o_ws), ws, blk.at(o_tab), c->n_cus, st);
+    });
+    blk.run([&](hipStream_t st) {
+        return gms::launch_logos_filter(blk.at(o_tab), blk.at<gms_pair>(o_pairs), n_pairs, blk.at(o_ws), ws, blk.at<gms_dmatch>(o_out),
+                                        blk.at<gms_logos_result>(o_res), nullptr, c->n_cus, st);
+    });
+    blk.out(results, o_res, b_res);
+    if (out_len > 0) blk.out(out, o_out, b_out);
+    return blk.finish();
 }
 
 // ---- LOGOS dictionary training (logos_dict_kernels.hip) --------------------------------------------------------------------------
@@ -1663,10 +1636,10 @@ static bool logos_dict_params(int desc_kind, int64_t total_rows, int n_sets, int
     p->n_words = n_words;
     p->attempts = attempts;
     p->max_iters = max_iters;
-    p->row_bytes = desc_kind == GMS_DESC_HAMMING256 ? 32 : 512;
+    p->row_bytes = (int)desc_row_bytes(desc_kind);
     p->total_rows = total_rows;
     p->seed = seed;
-    return (desc_kind == GMS_DESC_HAMMING256 || desc_kind == GMS_DESC_L2_F32X128) && gms::logos_dict::params_ok(*p);
+    return desc_kind_ok(desc_kind) && gms::logos_dict::params_ok(*p);
 }
 
 size_t gms_logos_dict_workspace_bytes(int desc_kind, int64_t total_rows, int n_sets, int n_words, int attempts, int max_iters)
@@ -1685,10 +1658,7 @@ int gms_logos_dict_train_device(gms_ctx* c, int desc_kind, const void* d_desc, c
     if (n_sets == 0) return GMS_OK;
     if (!d_set_off || !d_workspace || !d_dict || !d_results || (total_rows > 0 && !d_desc)) return GMS_ERR_BAD_ARG;
     if (ws_bytes < gms::logos_dict_ws_bytes(p) || (reinterpret_cast<uintptr_t>(d_workspace) & 15u)) return GMS_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
-    GMS_HIP(hipSetDevice(c->device));
-    GMS_HIP(gms::launch_logos_dict_train(p, d_desc, d_set_off, d_workspace, d_dict, d_results, d_labels, c->stream));
-    return GMS_OK;
+    return on_ctx(c, [&] { return gms::launch_logos_dict_train(p, d_desc, d_set_off, d_workspace, d_dict, d_results, d_labels, c->stream); });
 }
 
 int gms_logos_dict_train(int desc_kind, const void* desc, const int64_t* set_off, int n_sets, int n_words, int attempts, int max_iters,
@@ -1700,35 +1670,26 @@ int gms_logos_dict_train(int desc_kind, const void* desc, const int64_t* set_off
     if (!logos_dict_params(desc_kind, total, n_sets, n_words, attempts, max_iters, seed, &p)) return GMS_ERR_BAD_ARG;
     if (n_sets == 0) return GMS_OK;
     if (!dict || !results || (total > 0 && !desc)) return GMS_ERR_BAD_ARG;
-    const size_t a = 256;
-    auto up = [&](size_t x) { return (x + a - 1) / a * a; };
     const size_t b_desc = (size_t)p.row_bytes * (size_t)total, b_off = 8 * ((size_t)n_sets + 1);
     const size_t b_dict = (size_t)p.row_bytes * (size_t)n_words * (size_t)n_sets, b_res = sizeof(gms_logos_dict_result) * (size_t)n_sets;
-    const size_t b_lab = 4 * (size_t)total, ws = gms::logos_dict_ws_bytes(p);
-    // one block: rows | offsets | dictionaries | records | labels | workspace
-    const size_t o_desc = 0, o_off = up(o_desc + b_desc + 16), o_dict = up(o_off + b_off), o_res = up(o_dict + b_dict);
-    const size_t o_lab = up(o_res + b_res), o_ws = up(o_lab + b_lab + 16), bytes = o_ws + ws;
+    const size_t b_lab = 4 * (size_t)total;
+    gms::BlockLayout lay;
+    const size_t o_desc = lay.add(b_desc, 16), o_off = lay.add(b_off), o_dict = lay.add(b_dict), o_res = lay.add(b_res);
+    const size_t o_lab = lay.add(b_lab, 16), o_ws = lay.add(gms::logos_dict_ws_bytes(p));
     GMS_HIP(hipSetDevice(0));
-    void* blk = nullptr;
-    GMS_HIP(hipMalloc(&blk, bytes));
-    char* d = static_cast<char*>(blk);
-    hipStream_t st = nullptr;
-    hipError_t e = hipSuccess;
-    if (total > 0) e = hipMemcpyAsync(d + o_desc, desc, b_desc, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + o_off, set_off, b_off, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && labels && total > 0) e = hipMemcpyAsync(d + o_lab, labels, b_lab, hipMemcpyHostToDevice, st);  // rows outside every set keep theirs
-    if (e == hipSuccess)
-        e = gms::launch_logos_dict_train(p, d + o_desc, reinterpret_cast<const int64_t*>(d + o_off), d + o_ws, d + o_dict,
-                                         reinterpret_cast<gms_logos_dict_result*>(d + o_res), labels ? reinterpret_cast<int32_t*>(d + o_lab) : nullptr,
-                                         st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dict, d + o_dict, b_dict, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(results, d + o_res, b_res, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && labels && total > 0) e = hipMemcpyAsync(labels, d + o_lab, b_lab, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    else (void)hipStreamSynchronize(st);
-    (void)hipFree(blk);
-    GMS_HIP(e);
-    return GMS_OK;
+    DevBlock blk(lay, nullptr);
+    const bool with_labels = labels && total > 0;
+    if (total > 0) blk.in(o_desc, desc, b_desc);
+    blk.in(o_off, set_off, b_off);
+    if (with_labels) blk.in(o_lab, labels, b_lab);  // rows outside every set keep theirs
+    blk.run([&](hipStream_t st) {
+        return gms::launch_logos_dict_train(p, blk.at(o_desc), blk.at<int64_t>(o_off), blk.at(o_ws), blk.at(o_dict), blk.at<gms_logos_dict_result>(o_res),
+                                            labels ? blk.at<int32_t>(o_lab) : nullptr, st);
+    });
+    blk.out(dict, o_dict, b_dict);
+    blk.out(results, o_res, b_res);
+    if (with_labels) blk.out(labels, o_lab, b_lab);
+    return blk.finish();
 }
 
 int gms_selftest_five_point(gms_ctx* c, const double* pts, int n_samples, double* models, int32_t* counts)
