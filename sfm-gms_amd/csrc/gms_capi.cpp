@@ -186,7 +186,7 @@ struct gms_ctx {
     uint32_t overflow_seen = 0;
     int stream_penalty = 0;
     int opt_deal = -1, opt_probe = -1;  // gms_ctx_set_option: -1 = the library's own choice (and the environment switches), 0 / 1 = forced
-    // Scale hypotheses: the kernels can bound a scale's inlier count before evaluating it (gms_kernels.hip, PROBE) and skip the
+    // Scale hypotheses: the kernels can bound a scale's inlier count before evaluating it (gms_kernel_scales.hip, PROBE) and skip the
     // scale when it cannot win -- a gain when at least half of the probes let a scale skip, a loss otherwise. The kernels count
     // both in probe_stats (device); every sixteenth launch with scale hypotheses probes whatever the verdict and is followed by a
     // one-thread kernel that turns the counts into verdict[1], which the launches in between follow.

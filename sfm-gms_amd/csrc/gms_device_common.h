@@ -1,13 +1,43 @@
 // gms_device_common.h -- device helpers shared by every kernel file of the GMS filter (one definition each:
 // the hashed table's slot/bucket arithmetic, verifyCellPairs' threshold test, the rotation patterns, small
-// LDS/DPP idioms). Internal; included by the .hip files only.
+// LDS/DPP idioms, the phase stamps of the diagnostic build) and, at the end, the host-side list of the per-pair
+// kernels' template instantiations. Internal; included by the .hip files only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
+#include <type_traits>
+
 #include "gms_kernels.h"
 
 namespace gms {
+
+// Diagnostic build only (-DGMS_PHASE_TIMING, libgms_hip_diag.so): thread 0 of each workgroup sums the
+// shader-clock cycles between phase boundaries into p.diag[block][phase]. No stamp exists in the product build.
+#ifdef GMS_PHASE_TIMING
+#define GMS_STAMP_DECL unsigned long long ph_[16] = {0}; unsigned long long t_prev_ = __builtin_readcyclecounter();
+#define GMS_STAMP(k) do { unsigned long long t_ = __builtin_readcyclecounter(); ph_[k] += t_ - t_prev_; t_prev_ = t_; } while (0)
+#define GMS_STAMP_FLUSH_AT(idx_) do { if (tid == 0 && p.diag) { for (int k_ = 0; k_ < 16; ++k_) p.diag[(size_t)(idx_) * 16 + k_] = ph_[k_]; } } while (0)
+#define GMS_STAMP_FLUSH GMS_STAMP_FLUSH_AT(pair_idx)
+#ifdef GMS_STAMP_BY_SCALE   // scale-hypothesis kernels: one sum per (scale, probe / evaluation) instead of one per phase
+#define GMS_STAMP_IN(k)
+#define GMS_STAMP_SCALE(k) GMS_STAMP(k)
+#define GMS_STAMP_OUT(k, kscale) GMS_STAMP(kscale)
+#else
+#define GMS_STAMP_IN(k) GMS_STAMP(k)
+#define GMS_STAMP_SCALE(k)
+#define GMS_STAMP_OUT(k, kscale) GMS_STAMP(k)
+#endif
+#else
+#define GMS_STAMP_IN(k)
+#define GMS_STAMP_SCALE(k)
+#define GMS_STAMP_OUT(k, kscale)
+#define GMS_STAMP_DECL
+#define GMS_STAMP(k)
+#define GMS_STAMP_FLUSH
+#define GMS_STAMP_FLUSH_AT(idx_)
+#endif
 
 constexpr uint32_t kEmpty = 0xFFFFFFFFu;
 
@@ -44,7 +74,7 @@ __device__ __forceinline__ uint32_t* lds_at(uint32_t* base, uint32_t byte_off)
     return reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(base) + byte_off);
 }
 
-// ---- idioms of the byte-matrix kernels that count their instructions (dense_pair_plain in gms_kernels.hip, stream_plain_kernel in
+// ---- idioms of the byte-matrix kernels that count their instructions (dense_pair_plain in gms_kernel_dense.hip, stream_plain_kernel in
 //      gms_kernel_stream.hip): LDS by absolute byte offset (the dynamic segment of these kernels starts at 0, so no "+ base" per access),
 //      non-temporal record traffic, two instructions the compiler does not pick by itself
 // The match records are read once and the survivors written once: non-temporal, so that what the L2 keeps is the lines a
@@ -239,6 +269,54 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 15) + (uint32_t)__builtin_amdgcn_readlane((int)v, 31) +
            (uint32_t)__builtin_amdgcn_readlane((int)v, 47) + (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// Every pair of a batch costs about the same, so the workgroups of one dispatch round would all read their
+// match arrays at the same moment (an HBM burst, then a long quiet stretch) and stay in lockstep round after
+// round. The first round's workgroups start spread over p.stagger_ticks (ticks of the 100 MHz wall clock, so the
+// spread does not depend on the shader clock the chip happens to hold); the spread then persists.
+__device__ __forceinline__ void first_round_stagger(const FilterParams& p)
+{
+    if (p.stagger_ticks > 0 && blockIdx.x < (unsigned)p.stagger_blocks) {
+        // in workgroup order: workgroups are handed to the XCDs round-robin and in order, so CUs should come free in
+        // that same order or the next workgroup in line waits for "its" XCD while others sit idle
+        const long long until = (long long)wall_clock64() +
+                                (long long)blockIdx.x * (long long)p.stagger_ticks / (long long)p.stagger_blocks;
+        while ((long long)wall_clock64() < until) __builtin_amdgcn_s_sleep(32);
+    }
+}
+
+// ---- host side of the per-pair kernels (gms_kernel_hash.hip, gms_kernel_dense.hip, gms_kernel_scales.hip) ----------------------
+// Their template instantiations, spelled once: kpt = matches per thread of the 1024-thread workgroup (filter_pick_kpt), with and
+// without rotation hypotheses. f(std::integral_constant<int, KPT>, std::bool_constant<ROT>) is called for the one that is asked for.
+// (A 512-thread build with twice the matches per thread and twice the matches in flight was measured 27 % slower at 10k matches:
+// the kernels want waves, not registers.)
+template <class F>
+hipError_t dispatch_kpt_rot(int kpt, bool rot, F&& f)
+{
+    switch (kpt) {
+    case 4: return rot ? f(std::integral_constant<int, 4>{}, std::true_type{}) : f(std::integral_constant<int, 4>{}, std::false_type{});
+    case 10: return rot ? f(std::integral_constant<int, 10>{}, std::true_type{}) : f(std::integral_constant<int, 10>{}, std::false_type{});
+    case 16: return rot ? f(std::integral_constant<int, 16>{}, std::true_type{}) : f(std::integral_constant<int, 16>{}, std::false_type{});
+    default: return hipErrorInvalidValue;
+    }
+}
+// ... and for every one of them in turn, until one fails
+template <class F>
+hipError_t for_each_kpt_rot(F&& f)
+{
+    for (int kpt : {4, 10, 16})
+        for (bool rot : {false, true}) {
+            const hipError_t e = dispatch_kpt_rot(kpt, rot, f);
+            if (e != hipSuccess) return e;
+        }
+    return hipSuccess;
+}
+// a kernel may ask for the CU's whole LDS as its dynamic segment
+template <class K>
+hipError_t allow_full_lds(K* kernel)
+{
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
 }
 
 }  // namespace gms

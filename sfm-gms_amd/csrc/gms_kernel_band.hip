@@ -2,7 +2,7 @@
 // no scale hypotheses): BASELINE config 4 and the reference's dense one-keypoint-per-pixel disparity call
 // (DisparityUtil.cpp:123-149, W*H matches).
 //
-// The byte-matrix idea of gms_kernels.hip (dense_pair) with 16-bit counters: the 400 x 400 motion matrix is
+// The byte-matrix idea of gms_kernel_dense.hip (dense_pair_rot) with 16-bit counters: the 400 x 400 motion matrix is
 // 320 KB then, so the 20 left-grid rows are cut into three bands (7 + 7 + 6 rows). One workgroup owns one band of one
 // pair and keeps the band's rows plus one halo row on either side in LDS -- [header dword | 400 x u16] per left cell,
 // 145 KB for 9 rows -- so that every neighbour count verifyCellPairs needs for the band's own cells is local. A left
@@ -18,7 +18,7 @@
 //   band_compact_kernel  grid (16k-match tiles, pairs): order-preserving compaction of the DMatch records by the mask.
 // A pair with a left cell above 65 535 matches (a 16-bit entry could wrap) is flagged instead and left to the
 // HBM-slab kernel of gms_kernel_big.hip, which runs afterwards on flagged pairs only. Bit-exactness rules are the ones
-// of gms_kernels.hip (same float -> cell arithmetic, same threshold, same arg-max and tie rules).
+// of the per-pair kernels (overview: gms_kernels.hip; same float -> cell arithmetic, same threshold, same arg-max and tie rules).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -649,7 +649,7 @@ tile_filter_kernel(FilterParams p, TileGeom gm, const uint2* lists, const uint32
 #pragma unroll
         for (int k8 = 0; k8 < 8; ++k8) {  // k8-th outer neighbour = position k8 (k8 < 4) or k8 + 1
             const int u = (int)((0x45637210u >> (4 * k8)) & 15u);  // position -> ring index: {0,1,2,7,.,3,6,5,4}
-            // ring 0,1,2,5,8,7,6,3 clockwise; pattern rot sends ring index u to (u - rot) mod 8 (see gms_kernels.hip)
+            // ring 0,1,2,5,8,7,6,3 clockwise; pattern rot sends ring index u to (u - rot) mod 8 (see gms_device_common.h)
             const int q = (int)((0x36785210u >> ((((u - (tid & 7)) & 7)) << 2)) & 15u);
             const int dx = (int)((0x24924u >> (q << 1)) & 3u) - 1, dy = (int)((0x2a540u >> (q << 1)) & 3u) - 1;
             rot_pack |= (uint32_t)((dx + 1) | ((dy + 1) << 2)) << (4 * k8);

@@ -31,7 +31,7 @@ __device__ __forceinline__ uint32_t tload(const uint32_t* p) { return __hip_atom
 // code words: written and re-read by the same thread across phases and pairs; kept out of the L1 as well
 __device__ __forceinline__ void cstore(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// motion[l][r]++ and the running arg-max of the row, general walk (see region_insert_general in gms_kernels.hip)
+// motion[l][r]++ and the running arg-max of the row, general walk (see region_insert_general in gms_kernel_hash.h)
 __device__ void big_insert(uint32_t* tab, uint32_t d, uint32_t r)
 {
     const uint32_t nb = d & kDescNbMask, hb = d >> kDescShift;

@@ -1,5 +1,5 @@
 // gms_kernel_stream.hip -- pairs of 16 385 ... 65 536 matches (BASELINE config 4: 4K pairs, 50k features) under every flag
-// combination, on the BYTE matrix of gms_kernels.hip (dense_pair / dense_scales_pair): one 1024-thread workgroup per (pair, scale
+// combination, on the BYTE matrix of gms_kernel_dense.hip and gms_kernel_scales.hip (dense_pair_rot / dense_scales_pair): one 1024-thread workgroup per (pair, scale
 // hypothesis) keeps the scale's 400 x N_right motion matrix -- or a band of its left rows -- in the CU's LDS, one byte per entry.
 //
 // What a workgroup of the small-pair kernels keeps in registers (a code word per match) does not fit here, so the matches live in a
@@ -778,8 +778,8 @@ stream_compact_kernel(FilterParams p, StreamWs w, int mcap, int n_scales)
 }
 
 // ================================================================================================================================
-// No scale hypotheses (the default flags of DisparityUtil.cpp:149,299, or rotation alone): ONE workgroup per pair, dense_pair() of
-// gms_kernels.hip with the per-match code words in an L2-resident scratch array instead of registers -- the 400 x 400 byte matrix
+// No scale hypotheses (the default flags of DisparityUtil.cpp:149,299, or rotation alone): ONE workgroup per pair, dense_pair_rot() of
+// gms_kernel_dense.hip with the per-match code words in an L2-resident scratch array instead of registers -- the 400 x 400 byte matrix
 // fills the LDS, zeroed once per pair (every match takes its own increment back after each grid type), the row headers carry the
 // running arg-max under a grid-type tag. What is different at this size:
 //   * nLeft is 16 bits per cell, from a 32-bit half-cell histogram that lives in the matrix area before the matrix does;
@@ -942,7 +942,7 @@ stream_dense_kernel(FilterParams p, uint32_t* __restrict__ codes_ws, uint16_t* _
             }
             return;
         }
-        // ---- verifyCellPairs (dense_pair's: two lanes per cell without rotation, one lane per (cell, rotation) with)
+        // ---- verifyCellPairs (two lanes per cell without rotation; with rotation dense_pair_rot's: one lane per (cell, rotation))
         {
             constexpr int kItems = ROT ? kLeftN * 8 : kLeftN * 2;
             for (int item = tid; item < ((kItems + 63) & ~63); item += 1024) {
@@ -1018,7 +1018,7 @@ stream_dense_kernel(FilterParams p, uint32_t* __restrict__ codes_ws, uint16_t* _
                 const uint32_t l = ((cw[j] >> kDCellShiftS) & 0x1FFu) + (cw[j] & gx) + 20u * ((cw[j] >> 1) & gy);
                 const uint32_t e = (cw[j] >> kDEShiftS) & 0x1FFu, row = __umul24(l, kDRow);
                 const uint32_t x = smem[row >> 2] ^ (e << 8);  // < 256: the same right cell, x = the rotations that accept the cell
-                if (g < 3) bytes[row + e] = 0;                 // (every reader of the entry is past the barrier: see dense_pair)
+                if (g < 3) bytes[row + e] = 0;                 // (every reader of the entry is past the barrier: see dense_pair_rot)
                 if (x < 256u && ((cw[j] >> kDAccShiftS) | x) != (cw[j] >> kDAccShiftS)) codes[(k0 + j) * 1024 + tid] = cw[j] | (x << kDAccShiftS);
             }
         }
@@ -1110,7 +1110,7 @@ stream_dense_kernel(FilterParams p, uint32_t* __restrict__ codes_ws, uint16_t* _
 
 // ================================================================================================================================
 // The same size class under the DEFAULT flags (no rotation either: DisparityUtil.cpp:149,299 -- BASELINE config 4 as the reference's
-// disparity demo calls it): stream_plain_kernel = stream_dense_kernel<false> rebuilt the way dense_pair_plain (gms_kernels.hip) rebuilt
+// disparity demo calls it): stream_plain_kernel = stream_dense_kernel<false> rebuilt the way dense_pair_plain (gms_kernel_dense.hip) rebuilt
 // the register kernel -- entry-offset code words ([404 * cell + E : 18 | E : 9 | q and edge bits : 5]) in the scratch array, a per-lane
 // sink word instead of predication, LDS by absolute offset, the two-lane verification on base + s * 403 * d -- and with what the
 // streaming allows on top: the inlier flag of a match is one bit of two registers of its thread (a thread owns matches tid + 1024 k,
@@ -1121,7 +1121,7 @@ namespace {
 constexpr uint32_t kSPTrashOff = kDSMiscOff + 128u;         // [16] dwords: the sinks
 constexpr uint32_t kSPLdsBytes = kSPTrashOff + 64u;         // 162 592
 static_assert(kSPLdsBytes <= kLdsBytes, "stream-plain layout exceeds the LDS");
-constexpr uint32_t kSPEdgeX = 1u << 1, kSPEdgeY = 1u << 3;  // plain code word (as in gms_kernels.hip)
+constexpr uint32_t kSPEdgeX = 1u << 1, kSPEdgeY = 1u << 3;  // plain code word (as in gms_kernel_dense.hip)
 constexpr int kSPEShift = 5, kSPAtShift = 14, kSPTagShift = 20;
 }  // namespace
 

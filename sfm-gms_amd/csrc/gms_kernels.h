@@ -41,7 +41,7 @@ struct FilterParams {
     int with_rotation, with_scale;
     uint32_t* partial;          // scale hypotheses: per-pair records of the byte-matrix kernel (scales 0..3), or null
     const uint32_t* pair_flags; // large-pair kernel only: when set, it filters just the pairs whose flag word has bit 1 set
-    int dealt;                  // byte-matrix kernel: deal the matches to the lanes (inputs in spatial order; see dense_pair)
+    int dealt;                  // byte-matrix kernel: deal the matches to the lanes (inputs in spatial order; see dense_pair_rot in gms_kernel_dense.hip)
     int probe_scales;           // scale hypotheses: bit s set = bound scale s's inlier count first and skip the scale when it cannot win
     int probe_nibble;           // scale hypotheses: bit 3 / bit 4 = bound the 28 x 28 / 40 x 40 grid with four-bit entries first (half the bands of the byte probe)
     uint32_t* probe_stats;      // optional device counters: [0] scales probed, [1] scales the probe let skip
@@ -66,6 +66,13 @@ size_t     filter_lds_bytes(int kpt, uint32_t table_slots);
 hipError_t launch_normalize(const void* d_kp, int kp_stride_bytes, const int64_t* d_frame_off, const int32_t* d_wh,
                             int n_frames, int64_t total_kp, float* d_pts, hipStream_t stream);
 hipError_t launch_filter(const FilterParams& p, int kpt, int n_pairs, hipStream_t stream);
+// what launch_filter and init_filter_kernels dispatch to: the hashed kernel (gms_kernel_hash.hip), the byte-matrix kernel that
+// falls back to it per pair (gms_kernel_dense.hip), and the limits of launch_filter_scales' first kernel (gms_kernel_scales.hip)
+hipError_t launch_filter_hash(const FilterParams& p, int kpt, int n_pairs, size_t lds_bytes, hipStream_t stream);
+hipError_t launch_filter_dense(const FilterParams& p, int kpt, int n_pairs, size_t lds_bytes, hipStream_t stream);
+hipError_t init_hash_kernels();
+hipError_t init_dense_kernels();
+hipError_t init_scales_kernels();
 hipError_t launch_order_probe(const FilterParams& p, uint32_t* flag, hipStream_t stream);  // *flag: pinned host word
 hipError_t launch_probe_verdict(uint32_t* stats, uint32_t* flag, hipStream_t stream);      // FilterParams::probe_stats -> pinned host word
 // pair-table validation: ranges [match_off, match_off + m) must be disjoint; offenders get GMS_ERR_BAD_ARG in d_results (d_flag: a device word)
@@ -93,7 +100,7 @@ hipError_t init_stream_kernels();
 int        stream_max_matches();
 size_t     stream_ws_bytes_per_pair(const FilterParams& p, int mcap, bool need_mask);
 hipError_t launch_filter_stream(const FilterParams& p, int mcap, void* ws, const uint32_t** flags_out, hipStream_t stream);
-// the same size class without scale hypotheses: one workgroup per pair, dense_pair() with the code words streamed from an L2-resident array
+// the same size class without scale hypotheses: one workgroup per pair, the byte matrix of gms_kernel_dense.hip with the code words streamed from an L2-resident array
 size_t     stream_dense_ws_bytes_per_pair(int mcap);
 hipError_t launch_filter_stream_dense(const FilterParams& p, int mcap, void* ws, const uint32_t** flags_out, hipStream_t stream);
 // brute-force descriptor matcher (bf_kernels.hip)

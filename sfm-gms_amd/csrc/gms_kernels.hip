@@ -1,21 +1,25 @@
-// gms_kernels.hip -- hand-written HIP kernels for gfx950 (CDNA4): the GMS match filter.
+// gms_kernels.hip -- hand-written HIP kernels for gfx950 (CDNA4): the GMS match filter. Read this first: the overview of the
+// per-pair kernels (each form in a file of its own, named below), then the small kernels around them and the public launchers.
 //
 // What the reference does per pair (cv::xfeatures2d::matchGMS, opencv_xfeatures2d452.dll; SURVEY.md
 // section 8a) is a dense 400 x N_right int32 "motion" matrix that is zeroed, filled and scanned 4 times
 // per hypothesis. One 1024-thread workgroup owns one image pair and keeps the pair's whole state in
 // registers and in the CU's 160 KB LDS, in one of two forms:
 //
-//   filter_kernel_dense / dense_pair_plain(), dense_pair()   no scale hypotheses (right grid 20 x 20) and no left cell above 255
+//   filter_kernel_dense / dense_pair_plain(), dense_pair_rot()   [gms_kernel_dense.hip; layout and shared blocks: gms_kernel_dense.h]
+//               no scale hypotheses (right grid 20 x 20) and no left cell above 255
 //               matches: the 400 x 400 matrix itself, one BYTE per entry, fills the LDS; binning is one
 //               returning atomic per match, verification reads neighbour counts directly, the DMatch records
 //               stay in registers from load to copy-out. dense_pair_plain() is the default-flags body (the headline: written
 //               around its instruction count, touches the next workgroup's records ahead, non-temporal record traffic),
-//               dense_pair() the one with rotation hypotheses; both are described in front of them below. Pairs that
+//               dense_pair_rot() the one with rotation hypotheses; both are described in front of them there. Pairs that
 //               do not qualify are handed to hash_pair() by the same workgroup before anything is written.
-//   filter_kernel_dense_scales / dense_scales_pair()   scale hypotheses on the same byte matrix with a runtime row stride:
+//   filter_kernel_dense_scales / dense_scales_pair()   [gms_kernel_scales.hip]
+//               scale hypotheses on the same byte matrix with a runtime row stride:
 //               scales 0..3 evaluated (scale 1 first), every later one -- and scale 4 -- bounded first by a probe that bins
 //               without verifying and lets a scale skip when it cannot win; leaves a per-pair record for
-//   filter_kernel / hash_pair()          everything else (scale 4 when it has to be evaluated, crowded cells, the fallback of
+//   filter_kernel / hash_pair()          [gms_kernel_hash.hip; the body and its table helpers: gms_kernel_hash.h]
+//               everything else (scale 4 when it has to be evaluated, crowded cells, the fallback of
 //               both kernels above): the matrix has at most M non-zeros and is kept as a hash table --
 //
 //   code[KPT]   (registers) one dword per match: right cell of the current scale, half-cell index of the
@@ -46,153 +50,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <type_traits>
-
-#include "gms_device_common.h"
+#include "gms_kernel_dense.h"
 
 namespace gms {
-
-// Diagnostic build only (-DGMS_PHASE_TIMING, libgms_hip_diag.so): thread 0 of each workgroup sums the
-// shader-clock cycles between phase boundaries into p.diag[block][phase]. No stamp exists in the product build.
-#ifdef GMS_PHASE_TIMING
-#define GMS_STAMP_DECL unsigned long long ph_[16] = {0}; unsigned long long t_prev_ = __builtin_readcyclecounter();
-#define GMS_STAMP(k) do { unsigned long long t_ = __builtin_readcyclecounter(); ph_[k] += t_ - t_prev_; t_prev_ = t_; } while (0)
-#define GMS_STAMP_FLUSH_AT(idx_) do { if (tid == 0 && p.diag) { for (int k_ = 0; k_ < 16; ++k_) p.diag[(size_t)(idx_) * 16 + k_] = ph_[k_]; } } while (0)
-#define GMS_STAMP_FLUSH GMS_STAMP_FLUSH_AT(pair_idx)
-#ifdef GMS_STAMP_BY_SCALE   // scale-hypothesis kernels: one sum per (scale, probe / evaluation) instead of one per phase
-#define GMS_STAMP_IN(k)
-#define GMS_STAMP_SCALE(k) GMS_STAMP(k)
-#define GMS_STAMP_OUT(k, kscale) GMS_STAMP(kscale)
-#else
-#define GMS_STAMP_IN(k) GMS_STAMP(k)
-#define GMS_STAMP_SCALE(k)
-#define GMS_STAMP_OUT(k, kscale) GMS_STAMP(k)
-#endif
-#else
-#define GMS_STAMP_IN(k)
-#define GMS_STAMP_SCALE(k)
-#define GMS_STAMP_OUT(k, kscale)
-#define GMS_STAMP_DECL
-#define GMS_STAMP(k)
-#define GMS_STAMP_FLUSH
-#define GMS_STAMP_FLUSH_AT(idx_)
-#endif
-
-// byte offset (0, 4, 8, 12) of the slot of bucket v whose key is r (kr = r << 21), or -1
-__device__ __forceinline__ int bucket_find(const uint4& v, uint32_t kr)
-{
-    int o = -1;
-    o = ((v.w ^ kr) <= kSlotCountMask) ? 12 : o;
-    o = ((v.z ^ kr) <= kSlotCountMask) ? 8 : o;
-    o = ((v.y ^ kr) <= kSlotCountMask) ? 4 : o;
-    o = ((v.x ^ kr) <= kSlotCountMask) ? 0 : o;
-    return o;
-}
-__device__ __forceinline__ int bucket_first_empty(const uint4& v)
-{
-    int o = -1;
-    o = (v.w == kEmpty) ? 12 : o;
-    o = (v.z == kEmpty) ? 8 : o;
-    o = (v.y == kEmpty) ? 4 : o;
-    o = (v.x == kEmpty) ? 0 : o;
-    return o;
-}
-__device__ __forceinline__ uint32_t bucket_count(const uint4& v, uint32_t kr)
-{
-    uint32_t c = 0;
-    c = ((v.w ^ kr) <= kSlotCountMask) ? v.w : c;
-    c = ((v.z ^ kr) <= kSlotCountMask) ? v.z : c;
-    c = ((v.y ^ kr) <= kSlotCountMask) ? v.y : c;
-    c = ((v.x ^ kr) <= kSlotCountMask) ? v.x : c;
-    return c & kSlotCountMask;
-}
-
-// A region is one header bucket followed by nb data buckets; d = (header bucket << 16) | nb.
-// Header dword 0 is the running arg-max of the cell's row, kept inverted so that the table's 0xFFFFFFFF
-// fill means "nothing yet": ~((count << 11) | (2047 - right cell)), updated with atomicMin. The largest
-// key ever reached by a slot is its final one, so the minimum over all updates is the row's arg-max with
-// the lowest right cell winning ties -- the reference's ascending scan with strict '>'.
-__device__ __forceinline__ void header_update(uint32_t* tab, uint32_t d, uint32_t r, uint32_t count)
-{
-    atomicMin(lds_at(tab, (d >> 16) << 4), ~((count << 11) | (2047u - r)));
-}
-
-// motion[l][r]++, general form: walk the region from its hashed bucket.
-// Every lane terminates: the region always has an empty slot.
-__device__ __forceinline__ void region_insert_general(uint32_t* tab, uint32_t d, uint32_t r)
-{
-    const uint32_t nb = d & 0xFFFFu, first = (d >> 16) + 1u;
-    if (nb == 0) return;
-    const uint32_t kr = r << kSlotRShift;
-    uint32_t b = bucket_of(r, nb);
-    for (uint32_t guard = 0; guard < 8u * nb + 8u; ++guard) {
-        const uint32_t boff = (first + b) << 4;
-        const uint4 v = *reinterpret_cast<const uint4*>(lds_at(tab, boff));
-        const int f = bucket_find(v, kr);
-        if (f >= 0) {
-            const uint32_t old = atomicAdd(lds_at(tab, boff + (uint32_t)f), 1u);
-            header_update(tab, d, r, (old & kSlotCountMask) + 1u);
-            return;
-        }
-        const int e = bucket_first_empty(v);
-        if (e >= 0) {
-            const uint32_t prev = atomicCAS(lds_at(tab, boff + (uint32_t)e), kEmpty, kr | 1u);
-            if (prev == kEmpty) {
-                header_update(tab, d, r, 1u);
-                return;
-            }
-            continue;  // the slot went to somebody else (maybe to this very key): look at the bucket again
-        }
-        if (++b == nb) b = 0;
-    }
-}
-
-// motion[l][r], general form, starting one bucket after the hashed one (which was full without the key).
-__device__ __forceinline__ uint32_t region_lookup_general(const uint32_t* tab, uint32_t d, uint32_t r)
-{
-    const uint32_t nb = d & 0xFFFFu, first = (d >> 16) + 1u;
-    const uint32_t kr = r << kSlotRShift;
-    uint32_t b = bucket_of(r, nb);
-    for (uint32_t guard = 1; guard < nb; ++guard) {
-        if (++b == nb) b = 0;
-        const uint4 v = *reinterpret_cast<const uint4*>(tab + ((first + b) << 2));
-        if (bucket_find(v, kr) >= 0) return bucket_count(v, kr);
-        if (bucket_first_empty(v) >= 0) return 0;
-    }
-    return 0;
-}
 
 // ------------------------------------------------------------------------------------------------
 // normalizePoints (DLL@0x180048420): one thread per keypoint; frame found by binary search.
 // A -0.0 result is stored as +0.0 (adding +0.0f): every later use is floor(n * W), which is 0 for
 // both, and it lets the filter test "finite, non-negative" on the bit pattern alone.
 // ------------------------------------------------------------------------------------------------
-// dense code word
-                                                     // bits 0..4   q = (hx & 1) + 20 * (hy & 1)
-constexpr uint32_t kDNever = 1u << 5;                // bit 5       not binned under any grid type
-constexpr uint32_t kDEdgeX = 1u << 6;                // bit 6       hx == 39: x >= 20 under the x-shifted grid types
-constexpr uint32_t kDEdgeY = 1u << 7;                // bit 7       hy == 39
-constexpr int kDEShift = 8;                          // bits 8..16  E(r) = 403 - r, the byte's offset in its row
-constexpr uint32_t kDEMask = 0x1FFu;
-constexpr int kDAccShift = 17;                       // bits 17..24 inlier-under-rotation bits (one bit without rotation)
-constexpr int kDTagShift = 20;                       // arg-max key in a row header: grid type << 20 | (count - 1) << 11 | E(j)
-constexpr int kDCellShift = 18;                      // without rotation only, bits 18..26: the left cell under grid type 1
-                                                     // (with rotation it has a register of its own, as a row offset)
-
-// Besides the normalised point, everything about a keypoint that does not depend on the pair it is matched in is worked out
-// here, once per frame (a frame of a sequence is filtered against hundreds of others): two 16-bit codes per keypoint.
-//   lcode  the keypoint as a LEFT point: [q : 5 | x >= 20 under the x-shifted grid types : 1 | y likewise : 1 | cell under grid
-//          type 1 : 9] -- q and the edge bits are the low bits of the dense code word as they stand (kDEdgeX / kDEdgeY one place
-//          up). Cell values above the grid: kLCellNever (the point is binned under no grid type), kLCellBad (outside the parity
-//          domain: negative, non-finite or >= 2^20 after normalisation);
-//   rcode  the keypoint as a RIGHT point: E(r) = 403 - r of scale 0 (0 = outside the 20 x 20 grid); top bit: outside the domain;
-//   scode  the keypoint as a RIGHT point under scale hypotheses, 32 bits: [cell on the 20 x 20 grid : 9 | cell on the 28 x 28
-//          grid : 10 | low bit of the 40 x 40 cell's x, y : 2] -- the 10 x 10, 14 x 14 and 40 x 40 cells follow from these
-//          (fl(10 n) = fl(20 n) / 2, fl(14 n) = fl(28 n) / 2, fl(40 n) = 2 fl(20 n) + bit, exactly); kSCodeBad: outside the domain or
-//          outside one of the grids coordinate-wise (the reference has no bounds test there: such a pair takes the general path).
-constexpr uint32_t kLCellShift = 7, kLCellNever = 510u, kLCellBad = 511u;
-constexpr uint32_t kRCodeBad = 1u << 15;
-constexpr uint32_t kSCodeBad = 1u << 31;
 __device__ __forceinline__ void keypoint_codes(float2 n, uint16_t& lcode, uint16_t& rcode, uint32_t& scode)
 {
     const bool bad = max(__float_as_uint(n.x), __float_as_uint(n.y)) >= 0x49800000u;
@@ -249,1749 +115,6 @@ normalize_kernel(const char* __restrict__ kp, int kp_stride, const int64_t* __re
     }
 }
 
-// Every pair of a batch costs about the same, so the workgroups of one dispatch round would all read their
-// match arrays at the same moment (an HBM burst, then a long quiet stretch) and stay in lockstep round after
-// round. The first round's workgroups start spread over p.stagger_ticks (ticks of the 100 MHz wall clock, so the
-// spread does not depend on the shader clock the chip happens to hold); the spread then persists.
-__device__ __forceinline__ void first_round_stagger(const FilterParams& p)
-{
-    if (p.stagger_ticks > 0 && blockIdx.x < (unsigned)p.stagger_blocks) {
-        // in workgroup order: workgroups are handed to the XCDs round-robin and in order, so CUs should come free in
-        // that same order or the next workgroup in line waits for "its" XCD while others sit idle
-        const long long until = (long long)wall_clock64() +
-                                (long long)blockIdx.x * (long long)p.stagger_ticks / (long long)p.stagger_blocks;
-        while ((long long)wall_clock64() < until) __builtin_amdgcn_s_sleep(32);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// The filter: one 1024-thread workgroup per pair, KPT matches per thread held in registers.
-// The kernel is VALU-issue bound, so the per-match work is kept to a few instructions: the left cell of
-// a match under grid type g is never computed per match -- a per-pair table indexed by the match's
-// half-cell index gives the table region (insert) and the verified cell result (mark) with one LDS read.
-// ------------------------------------------------------------------------------------------------
-template <int KPT, bool ROT, int NT>
-__device__ __forceinline__ void hash_pair(const FilterParams& p, uint32_t* smem, const int pair_idx, const int tid)
-{
-    constexpr int kMcap = KPT * NT;
-    constexpr int kNRot = ROT ? 8 : 1;
-    // matches a thread keeps in flight through the LDS stages: 5 (4) with 128 registers per thread, 10 with 256
-    constexpr int kChunk = (NT <= 512 && KPT % 10 == 0) ? 10 : (KPT % 5 == 0) ? 5 : 4;
-    static_assert(KPT % kChunk == 0, "KPT must be a multiple of the chunk");
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-
-    // with scale hypotheses the byte-matrix kernel may have evaluated scales 0..2 already (see dense_scales_pair): its
-    // record holds the best hypothesis so far, and this kernel continues with scale 3. The record's four header words in one load,
-    // requested in front of the pair's record (one round trip for both: see load_pair).
-    const uint32_t* __restrict__ part = p.partial ? p.partial + (size_t)pair_idx * kPartialStrideDw : nullptr;
-    uint4 part_hdr = make_uint4(0u, 0u, 0u, 0u);
-    if (part != nullptr) part_hdr = *reinterpret_cast<const uint4*>(part);
-    const gms_pair pr = load_pair(p.pairs, pair_idx);
-    if (part != nullptr) asm volatile("" : "+v"(part_hdr.x), "+v"(part_hdr.y), "+v"(part_hdr.z), "+v"(part_hdr.w));
-    const uint32_t part0 = (uint32_t)uniform((int)part_hdr.x);  // workgroup-uniform: 0, or what the first kernel decided:
-    if (part0 == 6u) return;                                     //   6: everything, the survivors copied out as well (scales_copy_out)
-    const int m = pr.m;
-    const gms_dmatch* __restrict__ matches = p.matches + pr.match_off;
-
-    const uint32_t T = p.table_slots;              // multiple of 4
-    uint32_t* tab = smem;                          // per-left-cell regions of [r | count] slots
-    uint32_t* nfine = tab + T;                     // [1664] 40 x 40 half-cell histogram of the left points; later reused as
-    uint32_t* fres = nfine;                        //        per half-cell (j* << 8) | rotation bits that pass
-    uint32_t* nleft4 = nfine + kFineStride;        // [4][400] mNumberPointsInPerCellLeft per grid type
-    uint32_t* desc4 = nleft4 + 4 * kLeftN;         // [4][400] (header bucket << 16) | data buckets
-    uint32_t* fdesc4 = desc4 + 4 * kLeftN;         // [4][1664] the same, per half-cell: region of the cell it falls in
-    uint32_t* bestmask = fdesc4 + 4 * kFineStride; // kMcap / 32
-    uint32_t* chunk_base = bestmask + (kMcap >> 5);// kMcap / 64 + 1
-    uint32_t* misc = chunk_base + (kMcap >> 6) + 1;// [0..7] rotation counts, [8] error, [9] carry, [12..15] bucket
-                                                   // allocators, [16..] scan scratch
-    uint32_t* trash = reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(misc + 48) + 15) & ~uintptr_t(15));
-                                                   // [0..63] add/CAS sink per lane, [64..127] min sink per lane,
-                                                   // [128..131] an always-empty bucket (16-byte aligned)
-
-    if (tid < 48) misc[tid] = 0;
-    if (tid < 128) trash[tid] = 0;
-    if (tid >= 128 && tid < 132) trash[tid] = kEmpty;
-    const int scales_done = (int)(part0 & 15u);                  //   scales 0..3 (4) or all five (5: its probe bounded scale 4 out)
-    const bool probed4 = (part0 >> 4) != 0;                      //   "scale 4 was probed and cannot be bounded out"
-    const bool resumed = scales_done != 0;
-    for (int i = tid; i < (kMcap >> 5); i += NT) bestmask[i] = resumed ? part[kPartialHeaderDw + i] : 0u;
-    if (scales_done < (p.with_scale ? 5 : 1)) {  // (a pair whose scales are all decided goes straight to the copy-out and touches neither)
-        for (int i = tid; i < kFineStride; i += NT) nfine[i] = 0;
-        for (int i = tid; i < 4 * kFineStride; i += NT) fdesc4[i] = 0;
-    }
-
-    const bool bad_pair = m < 0 || m > kMcap || pr.frame_a < 0 || pr.frame_a >= p.n_frames ||
-                          pr.frame_b < 0 || pr.frame_b >= p.n_frames;
-    int64_t offA = 0, offB = 0;
-    int nA = 0, nB = 0;
-    if (!bad_pair) {  // (pair-uniform values into scalar registers: see uniform())
-        load_frame_ranges(p.frame_off, pr.frame_a, pr.frame_b, offA, nA, offB, nB);
-    }
-    const float2* __restrict__ ptsA = p.pts + offA;
-    const float2* __restrict__ ptsB = p.pts + offB;
-    const int mm = bad_pair ? 0 : m;
-    const int n_scales = p.with_scale ? 5 : 1;
-    const bool thr_fast = threshold_fast_ok(p.threshold_factor);
-    uint32_t best_count = resumed ? (uint32_t)uniform((int)part_hdr.y) : 0u;
-    int best_scale = resumed ? uniform((int)part_hdr.z) : -1, best_rot = resumed ? uniform((int)part_hdr.w) : -1;
-    GMS_STAMP_DECL
-    if (mm == 0 || nA <= 0 || nB <= 0) {  // workgroup-uniform: nothing to filter (or nothing valid to index)
-        if (tid == 0) {
-            gms_pair_result r;
-            r.n_inliers = 0;
-            r.best_scale = -1;
-            r.best_rot = -1;
-            r.status = (bad_pair || m > 0) ? GMS_ERR_DOMAIN : GMS_OK;
-            p.results[pair_idx] = r;
-        }
-        return;
-    }
-    __syncthreads();
-
-    if (scales_done < n_scales) {  // (workgroup-uniform; otherwise everything is decided and only the copy-out is left)
-    // ---- both sides of every match, scale 0: one 8-byte load of (queryIdx, trainIdx), two gathers.
-    //      Loads are unconditional on clamped indices (so that all of a thread's loads are in flight
-    //      together); validity is applied to the values afterwards.
-    uint32_t code[KPT];
-    {
-        // KPT <= 10: all of a thread's loads in flight together. KPT = 16: in two halves -- sixteen (queryIdx, trainIdx) pairs and
-        // sixteen points of either frame at once are 96 registers and spilled (200 bytes of scratch per lane).
-        constexpr int kLoad = KPT > 10 ? KPT / 2 : KPT;
-        // The train-side gather is 8 bytes from a random line per match: the vector memory pipe takes it one
-        // line at a time. When frame B's normalised points fit the (still unused) table area, copy them into LDS
-        // with coalesced loads while the match loads are in flight, and gather from LDS instead.
-        const bool stage_b = (uint32_t)nB * 2u <= T && nB <= 4 * mm;  // workgroup-uniform
-        float2* lds_b = reinterpret_cast<float2*>(tab);
-        const int wr = p.right_w[0];
-        const uint32_t nr = (uint32_t)(wr * p.right_h[0]);
-        const float fwr = (float)wr, fhr = (float)p.right_h[0];
-        bool any_bad = false;
-#pragma unroll
-        for (int k0 = 0; k0 < KPT; k0 += kLoad) {
-            int2 qt[kLoad];
-#pragma unroll
-            for (int k = 0; k < kLoad; ++k) {
-                const int i = min((k0 + k) * NT + tid, mm - 1);
-                qt[k] = *reinterpret_cast<const int2*>(&matches[i]);
-            }
-            if (k0 == 0 && stage_b) {
-                for (int j = tid; j < nB; j += NT) lds_b[j] = ptsB[j];
-                __syncthreads();
-            }
-#ifdef GMS_PHASE_TIMING
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            GMS_STAMP(4);  // bin: (queryIdx, trainIdx) loads landed, frame B staged
-#endif
-            float2 a[kLoad], b[kLoad];
-#pragma unroll
-            for (int k = 0; k < kLoad; ++k) a[k] = ptsA[min((uint32_t)qt[k].x, (uint32_t)(nA - 1))];
-            if (stage_b) {
-#pragma unroll
-                for (int k = 0; k < kLoad; ++k) b[k] = lds_b[min((uint32_t)qt[k].y, (uint32_t)(nB - 1))];
-            } else {
-#pragma unroll
-                for (int k = 0; k < kLoad; ++k) b[k] = ptsB[min((uint32_t)qt[k].y, (uint32_t)(nB - 1))];
-            }
-#ifdef GMS_PHASE_TIMING
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            GMS_STAMP(12);  // bin: gathers landed
-#endif
-#pragma unroll
-            for (int k = 0; k < kLoad; ++k) {
-                const bool live = (k0 + k) * NT + tid < mm;
-                // parity domain: indices in range; coordinates finite, non-negative, < 2^20 -- one unsigned
-                // compare on the bit patterns (negative, NaN and Inf patterns are all above 0x49800000 = 2^20;
-                // -0.0 was canonicalised away by normalize_kernel)
-                const uint32_t worst = max(max(__float_as_uint(a[k].x), __float_as_uint(a[k].y)),
-                                           max(__float_as_uint(b[k].x), __float_as_uint(b[k].y)));
-                const float fx = 20.0f * a[k].x, fy = 20.0f * a[k].y;   // mulss, rounded to fp32
-                // floor == truncation for non-negative values; 2f is exact
-                const uint32_t hx = (uint32_t)(int)(fx + fx), hy = (uint32_t)(int)(fy + fy);
-                // no bounds test in the reference: r = x + y * wr whatever x and y are. (Clamped to 16 bits so that the product fits the
-                // 24-bit multiplier -- unclamped the compiler builds a 64-bit multiply-add; a clamped value is far beyond the grid anyway.)
-                const uint32_t r = __umul24(min((uint32_t)(int)(fhr * b[k].y), 0xFFFFu), (uint32_t)wr) + min((uint32_t)(int)(fwr * b[k].x), 0xFFFFu);
-                const bool ok = (uint32_t)qt[k].x < (uint32_t)nA && (uint32_t)qt[k].y < (uint32_t)nB &&
-                                worst < 0x49800000u && r < nr;
-                // hx >= 40 or hy >= 40: x >= 20 or y >= 20 under every grid type, never binned
-                const uint32_t f = (live && ok && hx < 40u && hy < 40u) ? hy * kFineW + hx : kFineInvalid;
-                if (f != kFineInvalid) atomicAdd(&nfine[f], 1u);
-                any_bad |= live && !ok;
-                code[k0 + k] = ((live && ok) ? r : 0u) | (f << kFShift);
-            }
-        }
-        if (any_bad) misc[8] = 1;  // benign race: every writer stores 1
-    }
-    GMS_STAMP(13);    // bin: codes + half-cell histogram
-    __syncthreads();  // nfine complete
-    GMS_STAMP(0);     // bin: wait for the other waves
-
-    // ---- per grid type, once per pair: nLeft of every cell, its table region, and the half-cell view of it.
-    //      Regions may sit in the table in any order, so a cell simply takes the next free buckets from a
-    //      per-grid-type counter (misc[12 + g]); 1600 (grid type, cell) items over the workgroup.
-    for (int item = tid; item < 4 * kLeftN; item += NT) {
-        const int g = item / kLeftN, cell = item - g * kLeftN;
-        const int x = cell % kLeftW, y = cell / kLeftW;
-        const int hx0 = 2 * x - (g & 1), hy0 = 2 * y - (g >> 1);
-        uint32_t n = 0;
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 2; ++dx) {
-                const int hx = hx0 + dx, hy = hy0 + dy;
-                if (hx >= 0 && hy >= 0) n += nfine[hy * kFineW + hx];  // hx, hy <= 39 always
-            }
-        const uint32_t nb = region_buckets(n, p.region_shift);
-        uint32_t d = 0;
-        if (nb) d = (atomicAdd(&misc[12 + g], nb + 1u) << 16) | nb;  // header bucket + nb data buckets
-        nleft4[item] = n;
-        desc4[item] = d;
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 2; ++dx) {
-                const int hx = hx0 + dx, hy = hy0 + dy;
-                if (hx >= 0 && hy >= 0) fdesc4[g * kFineStride + hy * kFineW + hx] = d;
-            }
-    }
-    __syncthreads();
-    GMS_STAMP(1);  // region tables
-
-    // With rotation a thread always verifies the same rotation (item & 7 == tid & 7): where the rotation pattern sends each
-    // of the eight outer neighbours is worked out once, as (dx + 1) | (dy + 1) << 2 in four bits per neighbour.
-    uint32_t rot_pack = 0;
-    if (ROT) {
-#pragma unroll
-        for (int k8 = 0; k8 < 8; ++k8) {
-            const int k = k8 < 4 ? k8 : k8 + 1;
-            constexpr int kRingIndex[9] = {0, 1, 2, 7, -1, 3, 6, 5, 4};  // position -> ring index
-            const int q = rotated_position(tid & 7, kRingIndex[k]);
-            rot_pack |= (uint32_t)((position_dx(q) + 1) | ((position_dy(q) + 1) << 2)) << (4 * k8);
-        }
-    }
-    for (int s = scales_done; s < n_scales; ++s) {
-        const int wr = p.right_w[s], hr = p.right_h[s];
-
-        if (s > 0) {
-            // ---- getGridIndexRight again for this scale's right grid ------------------------------------------
-            const uint32_t nr = (uint32_t)(wr * hr);
-            const float fwr = (float)wr, fhr = (float)hr;
-            constexpr int kLoad = KPT > 10 ? KPT / 2 : KPT;  // (KPT = 16: in two halves, see above)
-            bool any_bad = false;
-#pragma unroll
-            for (int k0 = 0; k0 < KPT; k0 += kLoad) {
-                int t[kLoad];
-#pragma unroll
-                for (int k = 0; k < kLoad; ++k) t[k] = matches[min((k0 + k) * NT + tid, mm - 1)].trainIdx;
-                float2 b[kLoad];
-#pragma unroll
-                for (int k = 0; k < kLoad; ++k) b[k] = ptsB[min((uint32_t)t[k], (uint32_t)(nB - 1))];
-#pragma unroll
-                for (int k = 0; k < kLoad; ++k) {
-                    const uint32_t fpart = code[k0 + k] & (kFMask << kFShift);
-                    const bool had = fpart != (kFineInvalid << kFShift);  // valid at scale 0 (so indices and points are fine)
-                    const uint32_t r = __umul24(min((uint32_t)(int)(fhr * b[k].y), 0xFFFFu), (uint32_t)wr) + min((uint32_t)(int)(fwr * b[k].x), 0xFFFFu);
-                    const bool ok = r < nr;
-                    any_bad |= had && !ok;
-                    code[k0 + k] = (had && ok) ? (fpart | r) : (kFineInvalid << kFShift);
-                }
-            }
-            if (any_bad) misc[8] = 1;
-        }
-
-        // probe (see dense_scales_pair): pass 0 only bins and flags the matches that sit in their row's arg-max entry; when
-        // their number does not exceed the best count so far the scale is skipped, else pass 1 evaluates it as always
-        const bool probing = ((p.probe_scales >> s) & 1) != 0 && best_count > 0 && !(s == 4 && probed4);  // workgroup-uniform
-        bool skip_scale = false;
-        for (int pass = probing ? 0 : 1; pass < 2 && !skip_scale; ++pass) {
-        const bool probe = pass == 0;
-        for (int g = 0; g < 4; ++g) {
-            const uint32_t* nleft = nleft4 + g * kLeftN;
-            const uint32_t* desc = desc4 + g * kLeftN;
-            const uint32_t* fdesc = fdesc4 + g * kFineStride;
-
-            // ---- motion.setTo(0) (this also resets every region header to "no arg-max yet") ------------------
-            {
-                const uint4 e4 = make_uint4(kEmpty, kEmpty, kEmpty, kEmpty);
-                uint4* tab4 = reinterpret_cast<uint4*>(tab);
-                for (uint32_t i = tid; i < (T >> 2); i += NT) tab4[i] = e4;
-            }
-            __syncthreads();
-            GMS_STAMP(2);  // clear
-            // every wave is past the previous grid type's mark (it reads fres): reset it before verify writes
-            for (int i = tid; i < kFineStride; i += NT) fres[i] = kNoMatch;
-
-            // ---- assignMatchPairs: motion[l][r]++, kChunk matches in flight per thread. Written without
-            //      branches: every lane issues every atomic, and a lane the operation does not apply to is
-            //      pointed at its own trash dword instead (the scalar unit that all four SIMDs share, not the
-            //      LDS, is what divergent exec-mask handling would saturate here).
-            {
-                uint32_t pending = 0;
-                const uint32_t trash_add = (uint32_t)((trash - tab) + lane) << 2;        // never equals kEmpty
-                const uint32_t trash_min = (uint32_t)((trash - tab) + 64 + lane) << 2;
-                const uint32_t trash_bkt = (uint32_t)((trash - tab) + 128) << 2;          // one all-empty bucket
-#pragma unroll
-                for (int k0 = 0; k0 < KPT; k0 += kChunk) {
-                    uint32_t slot[kChunk];  // byte offset of the hashed bucket, then of the match's slot
-                    uint4 v[kChunk];
-                    uint32_t d[kChunk];     // region of the match's left cell under this grid type, 0 = not binned
-#pragma unroll
-                    for (int c = 0; c < kChunk; ++c) d[c] = fdesc[(code[k0 + c] >> kFShift) & kFMask];
-#pragma unroll
-                    for (int c = 0; c < kChunk; ++c) {
-                        const uint32_t nb = d[c] & 0xFFFFu;
-                        const uint32_t bo = ((d[c] >> 16) + 1u + bucket_of(code[k0 + c] & kRMask, nb)) << 4;
-                        slot[c] = nb ? bo : trash_bkt;
-                        v[c] = *reinterpret_cast<const uint4*>(lds_at(tab, slot[c]));
-                    }
-                    // round 1: "+1" where the bucket already holds the right cell, CAS into its first empty slot
-                    // where it does not. Slots of a bucket fill lowest-first, so the occupied slots are a prefix.
-                    // (A match that is not binned under this grid type was pointed at the trash bucket above and
-                    // simply plays there: nothing it does lands in the table, and d = 0 ends its general walk at once.)
-                    uint32_t o_add[kChunk], o_cas[kChunk];
-                    bool fnd[kChunk], put[kChunk], pend[kChunk];
-#pragma unroll
-                    for (int c = 0; c < kChunk; ++c) {
-                        const uint32_t kr = (code[k0 + c] & kRMask) << kSlotRShift;
-                        const int f = bucket_find(v[c], kr);
-                        const int e = bucket_first_empty(v[c]);
-                        fnd[c] = f >= 0;
-                        put[c] = f < 0 && e >= 0;
-                        pend[c] = f < 0 && e < 0;  // full bucket: leftovers
-                        slot[c] += (uint32_t)(f >= 0 ? f : (e & 12));
-                        o_add[c] = atomicAdd(lds_at(tab, fnd[c] ? slot[c] : trash_add), 1u);
-                        o_cas[c] = atomicCAS(lds_at(tab, put[c] ? slot[c] : trash_add), kEmpty, kr | 1u);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);  // all of the chunk's atomics are issued before any result is read
-                    // round 2: a lost CAS whose winner was the same right cell (common: the true matches of a
-                    // cell arrive together) becomes "+1" on that slot; any other winner sends us to the leftovers
-                    uint32_t o_again[kChunk];
-                    bool won[kChunk];
-#pragma unroll
-                    for (int c = 0; c < kChunk; ++c) {
-                        const uint32_t kr = (code[k0 + c] & kRMask) << kSlotRShift;
-                        won[c] = put[c] && o_cas[c] == kEmpty;
-                        const bool sm = put[c] && !won[c] && (o_cas[c] ^ kr) <= kSlotCountMask;
-                        pend[c] = pend[c] || (put[c] && !won[c] && !sm);
-                        o_again[c] = atomicAdd(lds_at(tab, sm ? slot[c] : trash_add), 1u);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    // the count this match produced, folded into the cell's running arg-max
-#pragma unroll
-                    for (int c = 0; c < kChunk; ++c) {
-                        const uint32_t count = fnd[c] ? (o_add[c] & kSlotCountMask) + 1u
-                                                      : (won[c] ? 1u : (o_again[c] & kSlotCountMask) + 1u);
-                        const uint32_t key = ~((count << 11) | (2047u - (code[k0 + c] & kRMask)));
-                        const uint32_t hdr = (d[c] >> 16) << 4;
-                        atomicMin(lds_at(tab, (pend[c] || (d[c] & 0xFFFFu) == 0) ? trash_min : hdr), key);
-                        pending |= pend[c] ? (1u << (k0 + c)) : 0u;
-                    }
-                }
-                GMS_STAMP(3);  // insert: first-probe rounds
-                // leftovers, one at a time through the general walk
-                while (pending) {
-                    const int k1 = __ffs(pending) - 1;
-                    pending &= pending - 1u;
-                    uint32_t cw = 0;
-#pragma unroll
-                    for (int k = 0; k < KPT; ++k) cw = (k == k1) ? code[k] : cw;
-                    region_insert_general(tab, fdesc[(cw >> kFShift) & kFMask], cw & kRMask);
-                }
-                GMS_STAMP(10);  // insert: leftovers
-            }
-            __syncthreads();
-            GMS_STAMP(11);  // insert: wait for the other waves
-            if (probe) {  // the region header holds ~((max count << 11) | (2047 - j*)): is this match's right cell j*?
-#pragma unroll
-                for (int k = 0; k < KPT; ++k) {
-                    const uint32_t d = fdesc[(code[k] >> kFShift) & kFMask];
-                    const uint32_t bi = ~tab[(d >> 16) << 2];
-                    if ((d & 0xFFFFu) != 0 && 2047u - (bi & kRMask) == (code[k] & kRMask)) code[k] |= 1u << kAccShift;
-                }
-                __syncthreads();  // the next grid type's clear overwrites the headers read here
-                continue;
-            }
-
-            // ---- verifyCellPairs. Without rotation: two lanes per left cell, four neighbour look-ups each, joined
-            //      by one DPP exchange. With rotation: one lane per (cell, rotation), eight look-ups in two rounds.
-            {
-                constexpr int kItems = ROT ? kLeftN * 8 : kLeftN * 2;
-                for (int item = tid; item < ((kItems + 63) & ~63); item += NT) {
-                    const bool live = item < kItems;
-                    const int i = live ? (ROT ? (item >> 3) : (item >> 1)) : 0;
-                    const int half = item & 1;  // !ROT only
-                    const uint32_t ni = live ? nleft[i] : 0u;
-                    if (__ballot(ni != 0) == 0ull) continue;  // none of this wave's cells has a match under this grid type
-                    const uint32_t di = desc[i];
-                    const uint32_t bi = ni ? ~tab[(di >> 16) << 2] : 0u;  // (max count << 11) | (2047 - j*)
-                    const int j = 2047 - (int)(bi & kRMask);
-                    const int jx = j % wr, jy = j / wr;
-                    const int ix = i % kLeftW, iy = i / kLeftW;
-                    // centre pair (k = 4): ll = i, rr = j*, whose count is the arg-max count
-                    uint32_t score = 0, tn = 0;  // tn = (sum of nLeft << 4) | numpair
-#pragma unroll
-                    for (int h = 0; h < (ROT ? 8 : 4); h += 4) {
-                        uint32_t dn[4], rq[4];
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) {
-                            int k;
-                            if (ROT) {
-                                const int k8 = h + c;
-                                k = k8 < 4 ? k8 : k8 + 1;
-                            } else {
-                                k = half ? c + 5 : c;  // lane 0: neighbours 0..3, lane 1: neighbours 5..8
-                            }
-                            int ldx, ldy, rdx, rdy;
-                            if (ROT) {
-                                ldx = (k % 3) - 1; ldy = (k / 3) - 1;  // k is a compile-time constant here
-                                rdx = (int)((rot_pack >> (4 * (h + c))) & 3u) - 1;
-                                rdy = (int)((rot_pack >> (4 * (h + c) + 2)) & 3u) - 1;
-                            } else {
-                                // k = c or c + 5, both compile-time: select by lane parity
-                                ldx = half ? ((c + 5) % 3) - 1 : (c % 3) - 1;
-                                ldy = half ? ((c + 5) / 3) - 1 : (c / 3) - 1;
-                                rdx = ldx; rdy = ldy;
-                            }
-                            const int lx = ix + ldx, ly = iy + ldy;
-                            const int rx = jx + rdx, ry = jy + rdy;
-                            // the left neighbour does not depend on j*: its two table reads go out together with the
-                            // header read instead of behind it
-                            const bool okl = ni != 0 && (uint32_t)lx < (uint32_t)kLeftW && (uint32_t)ly < (uint32_t)kLeftH;  // ll != -1
-                            const int ll = okl ? lx + ly * kLeftW : 0;
-                            const uint32_t nll = nleft[ll], dll = desc[ll];
-                            const bool okp = okl && (uint32_t)rx < (uint32_t)wr && (uint32_t)ry < (uint32_t)hr;             // rr != -1
-                            rq[c] = okp ? (uint32_t)(rx + ry * wr) : 0u;  // 0: matches no slot of the all-empty stand-in
-                            tn += okp ? ((nll << 4) | 1u) : 0u;
-                            dn[c] = okp ? dll : 0u;
-                        }
-                        uint4 v[4];
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) {
-                            const uint32_t nb = dn[c] & 0xFFFFu;
-                            v[c] = make_uint4(kEmpty, kEmpty, kEmpty, kEmpty);
-                            if (nb) v[c] = *reinterpret_cast<const uint4*>(tab + (((dn[c] >> 16) + 1u + bucket_of(rq[c], nb)) << 2));
-                        }
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) {
-                            const uint32_t kr = rq[c] << kSlotRShift;
-                            const uint32_t cnt = bucket_count(v[c], kr);  // 0 when the bucket does not hold the right cell
-                            score += cnt;
-                            // slots fill lowest-first: the bucket is full iff its last slot is taken. Full and
-                            // without the key: the key may sit further along the region
-                            if (cnt == 0 && v[c].w != kEmpty) score += region_lookup_general(tab, dn[c], rq[c]);
-                        }
-                    }
-                    if (!ROT) {
-                        score += dpp_xor1(score);
-                        tn += dpp_xor1(tn);
-                    }
-                    score += bi >> 11;
-                    tn += (ni << 4) | 1u;
-                    uint32_t pass = 0;
-                    if (ni != 0 && (ROT || half == 0)) {
-                        pass = threshold_rejects(tn >> 4, tn & 15u, score, p.threshold_factor, thr_fast) ? 0u : 1u;
-                    }
-                    uint32_t bits = pass;
-                    bool writer = ni != 0 && half == 0;
-                    if (ROT) {
-                        const unsigned long long bal = __ballot(pass);
-                        bits = (uint32_t)(bal >> (lane & 56)) & 0xFFu;
-                        writer = ni != 0 && (lane & 7) == 0;
-                    }
-                    if (writer) {
-                        // cellPairs[i] as every half-cell of cell i sees it
-                        const uint32_t cr = ((uint32_t)j << 8) | bits;
-                        const int hx0 = 2 * ix - (g & 1), hy0 = 2 * iy - (g >> 1);
-#pragma unroll
-                        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-                            for (int dx = 0; dx < 2; ++dx) {
-                                const int hx = hx0 + dx, hy = hy0 + dy;
-                                if (hx >= 0 && hy >= 0) fres[hy * kFineW + hx] = cr;
-                            }
-                    }
-                }
-            }
-            __syncthreads();
-            GMS_STAMP(5);  // verify
-
-            // ---- mark inliers: cellPairs[l] == r, all rotations at once ---------------------------------------
-            {
-                uint32_t cr[KPT];
-#pragma unroll
-                for (int k = 0; k < KPT; ++k) cr[k] = fres[(code[k] >> kFShift) & kFMask];
-#pragma unroll
-                for (int k = 0; k < KPT; ++k)
-                    if ((cr[k] >> 8) == (code[k] & kRMask)) code[k] |= cr[k] << kAccShift;
-            }
-            GMS_STAMP(6);  // mark
-        }
-        if (probe) {
-            uint32_t c0 = 0;
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) c0 += (uint32_t)__popcll(__ballot((code[k] >> kAccShift) & 1u));
-            if (lane == 0 && c0) atomicAdd(&misc[0], c0);
-            __syncthreads();
-            skip_scale = misc[0] <= best_count;
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) code[k] &= (1u << kAccShift) - 1u;
-            __syncthreads();
-            if (tid == 0) {
-                misc[0] = 0;
-                if (p.probe_stats != nullptr) atomicAdd(&p.probe_stats[2 * s + (skip_scale ? 1 : 0)], 1u);
-            }
-        }
-        }
-        if (skip_scale) continue;
-
-        // ---- run() return value for each rotation of this scale ---------------------------------------
-        {
-            uint32_t cnt[kNRot];
-#pragma unroll
-            for (int r = 0; r < kNRot; ++r) cnt[r] = 0;
-#pragma unroll
-            for (int k = 0; k < KPT; ++k)
-#pragma unroll
-                for (int r = 0; r < kNRot; ++r)
-                    cnt[r] += (uint32_t)__popcll(__ballot((code[k] >> (kAccShift + r)) & 1u));
-            if (lane == 0) {
-#pragma unroll
-                for (int r = 0; r < kNRot; ++r)
-                    if (cnt[r]) atomicAdd(&misc[r], cnt[r]);
-            }
-        }
-        __syncthreads();
-
-        // ---- getInlierMask: keep on strict '>' (scale outer, rotation inner) ---------------------------
-        int winner = -1;
-#pragma unroll
-        for (int r = 0; r < kNRot; ++r) {
-            const uint32_t c = misc[r];
-            if (c > best_count) {
-                best_count = c;
-                best_scale = s;
-                best_rot = r + 1;
-                winner = r;
-            }
-        }
-        if (winner >= 0) {
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) {
-                const unsigned long long b = __ballot((code[k] >> (kAccShift + winner)) & 1u);
-                if (lane == 0) {
-                    const int ch = k * (NT / 64) + wave;  // chunk of 64 consecutive matches
-                    bestmask[2 * ch] = (uint32_t)b;
-                    bestmask[2 * ch + 1] = (uint32_t)(b >> 32);
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < KPT; ++k) code[k] &= (1u << kAccShift) - 1u;
-        __syncthreads();
-        if (tid < 8) misc[tid] = 0;
-        GMS_STAMP(7);  // count + select
-    }
-    }
-    __syncthreads();
-
-    // ---- copy-out: surviving DMatch verbatim, in input order (DLL@0x180048340) -----------------------
-    const bool failed = misc[8] != 0;
-    const int n_chunks = (mm + 63) >> 6;
-    {
-        // exclusive scan of per-chunk popcounts; NT chunks per round, carry in misc[9]
-        uint32_t* wave_tot = misc + 16;
-        for (int base = 0; base < n_chunks; base += NT) {
-            const int c = base + tid;
-            const uint32_t v = (c < n_chunks && !failed) ? __popc(bestmask[2 * c]) + __popc(bestmask[2 * c + 1]) : 0u;
-            uint32_t incl = v;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t t = __shfl_up(incl, d);
-                if (lane >= d) incl += t;
-            }
-            if (lane == 63) wave_tot[wave] = incl;
-            __syncthreads();
-            uint32_t wave_off = misc[9];
-            for (int w = 0; w < wave; ++w) wave_off += wave_tot[w];
-            if (c < n_chunks) chunk_base[c] = wave_off + incl - v;
-            __syncthreads();
-            if (tid == NT - 1) misc[9] = wave_off + incl;
-            __syncthreads();
-        }
-    }
-    const uint32_t total = misc[9];
-    GMS_STAMP(8);  // out scan
-
-    gms_dmatch* __restrict__ out = p.out + pr.match_off;
-    uint8_t* mask_out = p.mask ? p.mask + pr.match_off : nullptr;
-    constexpr int kOut = KPT % 10 == 0 ? 10 : KPT % 8 == 0 ? 8 : kChunk;  // records requested together (nothing else is live here)
-    static_assert(KPT % kOut == 0, "whole rounds");
-#pragma unroll
-    for (int k0 = 0; k0 < KPT; k0 += kOut) {
-        uint32_t pos[kOut];
-        uint4 v[kOut];
-        uint32_t inm = 0;
-#pragma unroll
-        for (int c = 0; c < kOut; ++c) {
-            const int i = (k0 + c) * NT + tid;
-            const int ch = i >> 6;
-            pos[c] = 0;
-            bool in = false;
-            if (i < mm) {
-                const unsigned long long bits =
-                    failed ? 0ull : ((unsigned long long)bestmask[2 * ch] | ((unsigned long long)bestmask[2 * ch + 1] << 32));
-                in = (bits >> lane) & 1ull;
-                if (mask_out) mask_out[i] = in ? 1 : 0;
-                if (in) {
-                    inm |= 1u << c;
-                    pos[c] = chunk_base[ch] + (uint32_t)__popcll(bits & ((1ull << lane) - 1ull));
-                }
-            }
-            // the survivor's record -- requested UNCONDITIONALLY, the address selected (everybody else reads the pair's first record:
-            // one line): a load inside the branch is waited for inside the branch, one round trip per record, and this kernel
-            // reads the records from HBM (the byte-matrix kernel had them long ago)
-            v[c] = *reinterpret_cast<const uint4*>(&matches[in ? i : 0]);
-        }
-#pragma unroll
-        for (int c = 0; c < kOut; ++c) asm volatile("" : "+v"(v[c].x), "+v"(v[c].y), "+v"(v[c].z), "+v"(v[c].w));  // (all of the round's records before its first store)
-#pragma unroll
-        for (int c = 0; c < kOut; ++c)
-            if ((inm >> c) & 1u) *reinterpret_cast<uint4*>(&out[pos[c]]) = v[c];
-    }
-    GMS_STAMP(9);  // copy-out
-    GMS_STAMP_FLUSH_AT(pair_idx + (resumed ? p.n_pairs : 0));  // (behind the byte-matrix kernel's stamps of the same launch)
-    if (tid == 0) {
-        gms_pair_result r;
-        r.n_inliers = failed ? 0 : (int)total;
-        r.best_scale = failed ? -1 : best_scale;
-        r.best_rot = failed ? -1 : best_rot;
-        r.status = failed ? GMS_ERR_DOMAIN : GMS_OK;
-        p.results[pair_idx] = r;
-    }
-}
-
-template <int KPT, bool ROT, int NT>
-__global__ void __launch_bounds__(NT)
-filter_kernel(FilterParams p)
-{
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    first_round_stagger(p);
-    hash_pair<KPT, ROT, NT>(p, smem, (int)blockIdx.x, (int)threadIdx.x);
-}
-
-// ------------------------------------------------------------------------------------------------
-// The dense path: pairs whose motion matrix fits the LDS as BYTES.
-//
-// Without scale hypotheses the right grid is 20 x 20, so the reference's motion matrix is 400 x 400; an entry never
-// exceeds the number of matches of its left cell, so when no left cell (of any grid type) holds more than 255
-// matches the whole matrix fits the CU's LDS as one byte per entry -- 160 000 of the 163 840 bytes.
-// assignMatchPairs then is one returning LDS atomic per match (+1 on the entry's byte; the value it returns is the
-// count this match produced, folded into the row's running arg-max with one atomicMax) and verifyCellPairs reads
-// neighbour counts directly: no hashing, no bucket scans, no probe chains. The kernel is VALU-issue bound (16
-// cycles of a SIMD per instruction of the 16-wave workgroup), so the per-match work is cut to the bone:
-//   * a row is [header dword | 400 count bytes], the byte of right cell r at offset E(r) = 403 - r; the header
-//     holds the running arg-max ((count - 1) << 11) | E(j) while binning (max = highest count, then lowest right
-//     cell: the reference's ascending scan with strict '>') and cellPairs after verification;
-//   * per match, two registers: the row start of its left cell under grid type 1, and a code word with E(r), the
-//     half-cell parities q = (hx & 1) + 20 (hy & 1) and three "not binned under ..." bits. The left cell under grid
-//     type g is l1 + (q & M_g), M_g = gx + 20 gy, so the row start is one multiply-add away;
-//   * the matrix is zeroed once per pair; after each grid type every match takes its own increment back
-//     (one non-returning atomic) instead of 160 KB being cleared again.
-// Everything else has to live in the remaining 2.2 KB: the half-cell histogram and the current grid type's nLeft as
-// bytes, the rotation counters and a few sink dwords. The DMatch records stay in registers from the first load to
-// copy-out, so the match array is read exactly once.
-// A pair that does not qualify (a cell above 255 matches, any input outside the parity domain, scale hypotheses) is handed to hash_pair() by the same workgroup; results are identical.
-// ------------------------------------------------------------------------------------------------
-constexpr int kDenseRightW = 20, kDenseRightN = 400;            // right grid of scale 0: cvRound(20 * 1.0)
-constexpr uint32_t kDenseRow = 4u + kDenseRightN;               // header dword + one byte per right cell
-constexpr uint32_t kDenseBytes = kLeftN * kDenseRow;            // 161 600
-constexpr uint32_t kDenseFineOff = kDenseBytes;                 // [1600] bytes: half-cell histogram of the left points
-constexpr uint32_t kDenseNleftOff = kDenseFineOff + kFineN;     // [400] bytes: nLeft of every cell under the current grid type
-constexpr uint32_t kDenseMiscOff = kDenseNleftOff + kLeftN;     // [32] dwords: [0..7] rotation counts, [8] domain error,
-                                                                //   [9] carry, [11] not eligible, [16..31] scan scratch
-constexpr uint32_t kDenseTrashOff = kDenseMiscOff + 4u * 32u;   // [16] dwords: sinks
-constexpr uint32_t kDenseLdsBytes = kDenseTrashOff + 4u * 16u;  // 163 792
-static_assert(kDenseLdsBytes <= kLdsBytes, "dense layout exceeds the LDS");
-static_assert(kDenseBytes % 16 == 0 && kDenseRow % 4 == 0, "rows are dword aligned, the matrix is cleared in uint4s");
-
-// The threshold test of the byte-matrix path: T <= 9 * 255, score <= 9 * 255, n <= 9. For an integer factor up to 1023
-// (the reference's default is 6) T * factor^2 and score^2 * n are exact 32-bit integers; when they differ, they differ by
-// at least 1 in about 2^32, far more than the reference's three fp64 roundings can move thresh, so their order is the
-// reference's answer. Exact ties (and every other factor) take the fp64 route of threshold_rejects().
-__device__ __forceinline__ uint32_t dense_factor_sq(double factor)
-{
-    return (factor >= 1.0 && factor <= 1023.0 && factor == floor(factor)) ? (uint32_t)(factor * factor) : 0u;
-}
-__device__ __forceinline__ bool dense_threshold_rejects(uint32_t T, uint32_t n, uint32_t score, double factor, bool fast_ok, uint32_t f2i)
-{
-    if (f2i) {
-        const uint32_t a = __umul24(T, f2i), b = __umul24(__umul24(score, score), n);
-        if (a != b) return a > b;
-    }
-    return threshold_rejects(T, n, score, factor, fast_ok);
-}
-
-// mNumberPointsInPerCellLeft of cell (x, y) under the grid type shifted by (gx, gy) half cells, from the half-cell histogram --
-// which is laid out by cell: one dword per cell of grid type 1, its four half cells in the
-// four bytes (byte index (hx & 1) + 2 (hy & 1)) -- the index a left code word yields without arithmetic.
-__device__ __forceinline__ uint32_t dense_nleft_cm(const uint8_t* nfine8, int x, int y, int gx, int gy)
-{
-    const int hx0 = 2 * x - gx, hy0 = 2 * y - gy;
-    uint32_t n = 0;
-#pragma unroll
-    for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 2; ++dx) {
-            const int hx = max(hx0 + dx, 0), hy = max(hy0 + dy, 0);
-            const uint32_t v = nfine8[(((hy >> 1) * kLeftW + (hx >> 1)) << 2) + (hx & 1) + ((hy & 1) << 1)];
-            n += (hx0 + dx >= 0 && hy0 + dy >= 0) ? v : 0u;
-        }
-    return n;
-}
-
-// false (workgroup-uniform, nothing written to global memory): the pair has to take the general path
-template <int KPT, bool ROT, int NT, bool DEALT>
-__device__ __forceinline__ bool dense_pair(const FilterParams& p, uint32_t* smem, const int pair_idx, const int tid)
-{
-    // (since round 3 only instantiated with rotation hypotheses: the default flags run dense_pair_plain below; the ROT = false
-    //  branches are kept because they are the description the comments in front of this function follow)
-    constexpr int kMcap = KPT * NT;
-    constexpr int kNRot = ROT ? 8 : 1;
-    constexpr int kChunk = (KPT % 5 == 0) ? 5 : 4;
-    static_assert(KPT % kChunk == 0, "KPT must be a multiple of the chunk");
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    // Which match a lane's k-th record is. Normally a wave instruction takes 64 consecutive matches (k * NT + tid). Inputs in
-    // spatial order (a detector scanning rows, a per-pixel grid) make consecutive matches share their (left cell, right cell)
-    // entry, and 64 of them in one LDS atomic instruction serialise on one address (1.7x slower on cell-sorted keypoints, DESIGN.md
-    // section 6). When the context's recent launches looked like that (order_probe_kernel; the host picks this instantiation), the
-    // matches are DEALT instead: the wave's eight 8-lane groups take 8 consecutive matches (one 128-byte line of the match array) from eight places
-    // KPT * 128 matches apart. Loads stay whole lines either way; the copy-out below orders 8-match units, which both mappings are
-    // made of. Speed only: either mapping gives the same result.
-    constexpr int kUnitsPerBlock = KPT * (NT / 64);   // dealt: unit (g, k, wave) = g * this + k * 16 + wave for lane group g
-    constexpr bool dealt = DEALT;
-    // either way match k of a lane is base + k * stride: (tid, NT) in list order, (its group's first unit, 128) when dealt
-    const int m_base = dealt ? ((((lane >> 3) * kUnitsPerBlock + wave) << 3) | (lane & 7)) : tid;
-    const int m_stride = dealt ? (NT / 64) * 8 : NT;
-    auto match_of = [&](int k) -> int { return m_base + k * m_stride; };
-
-    int64_t total_kp;
-    const gms_pair pr = load_pair(p.pairs, pair_idx, p, total_kp);  // (and the frame table's header word)
-    const int m = pr.m;
-    if (p.with_scale || p.right_w[0] != kDenseRightW || p.right_h[0] != kDenseRightW || m <= 0 || m > kMcap ||
-        pr.frame_a < 0 || pr.frame_a >= p.n_frames || pr.frame_b < 0 || pr.frame_b >= p.n_frames)
-        return false;
-    int64_t offA, offB;
-    int nA, nB;
-    load_frame_ranges(p.frame_off, pr.frame_a, pr.frame_b, offA, nA, offB, nB);
-    if (nA <= 0 || nB <= 0) return false;
-    const gms_dmatch* __restrict__ matches = p.matches + pr.match_off;
-    // the frame table's code words (written by normalize_kernel behind the points): frame A's left codes, frame B's right codes
-    if (total_kp < 0 || offA + nA > total_kp || offB + nB > total_kp) return false;  // (workgroup-uniform) no header, or frames beyond the table
-    const uint16_t* __restrict__ lcodeA = reinterpret_cast<const uint16_t*>(p.pts + total_kp) + offA;
-    const uint16_t* __restrict__ rcodeB = reinterpret_cast<const uint16_t*>(p.pts + total_kp) + total_kp + offB;
-
-    const uint8_t* dense8 = reinterpret_cast<const uint8_t*>(smem);
-    uint32_t* nfine32 = smem + kDenseFineOff / 4;   // half-cell histogram: one dword per cell of grid type 1, a byte per half cell
-    const uint8_t* nfine8 = reinterpret_cast<const uint8_t*>(nfine32);
-    uint8_t* nleft8 = reinterpret_cast<uint8_t*>(smem) + kDenseNleftOff;
-    uint32_t* misc = smem + kDenseMiscOff / 4;
-    uint32_t* trash = smem + kDenseTrashOff / 4;
-
-    GMS_STAMP_DECL
-#ifdef GMS_PHASE_TIMING
-    ph_[14] = wall_clock64();  // absolute start of this workgroup (100 MHz), for the dispatch-phase histogram
-#endif
-    if (tid < 32) misc[tid] = 0;
-    if (tid < 16) trash[tid] = 0;
-    if (tid < kFineN / 4) nfine32[tid] = 0;
-
-    // ---- both frames' code words staged in the still unused matrix area (coalesced 16-byte loads from 16-byte aligned addresses:
-    //      a frame starts anywhere in the table, so the copy keeps the source's phase and look-ups add it), then the pair's DMatch
-    //      records, whole (they stay in registers until copy-out). Loads return in order: the staged codes are complete -- and the
-    //      barrier passed -- while the later records are still on their way.
-    const uint32_t phA = (uint32_t)(reinterpret_cast<uintptr_t>(lcodeA) >> 1) & 7u, phB = (uint32_t)(reinterpret_cast<uintptr_t>(rcodeB) >> 1) & 7u;
-    const uint32_t qA = (phA + (uint32_t)nA + 7u) >> 3, qB = (phB + (uint32_t)nB + 7u) >> 3;  // uint4s of either copy (8 codes each)
-    const bool staged = (qA + qB) * 16u <= kDenseBytes;  // workgroup-uniform: both fit (40 400 keypoints a frame, say)
-    const uint4* __restrict__ srcA = reinterpret_cast<const uint4*>(lcodeA - phA);
-    const uint4* __restrict__ srcB = reinterpret_cast<const uint4*>(rcodeB - phB);
-    constexpr int kStageRegs = 3;  // 48 KB of codes (12 288 keypoints a frame) through registers; larger frames finish in a plain loop
-    uint4 tb[kStageRegs];
-#pragma unroll
-    for (int i = 0; i < kStageRegs; ++i) {  // (unconditional: a pair too large to stage just reads a few code words it does not use)
-        const uint32_t j = min((uint32_t)(i * NT + tid), qA + qB - 1u);
-        const uint4* src = j < qA ? srcA + j : srcB + (j - qA);  // one load either way: select the address, not the data
-        tb[i] = *src;
-    }
-    // Up to 10 matches per thread the whole 16-byte records stay in registers until copy-out (the match array is read
-    // once); at 16 per thread that would be 64 registers of a 128-register budget, so there only (queryIdx, trainIdx)
-    // are loaded here and the survivors' records are read again at copy-out.
-    constexpr bool kKeepRec = KPT <= 10;
-    uint4 rec[kKeepRec ? KPT : 1];
-    uint2 qt[kKeepRec ? 1 : KPT];
-#pragma unroll
-    for (int k = 0; k < KPT; ++k) {
-        if (kKeepRec) rec[k] = *reinterpret_cast<const uint4*>(&matches[min(match_of(k), m - 1)]);
-        else qt[k] = *reinterpret_cast<const uint2*>(&matches[min(match_of(k), m - 1)]);
-    }
-    auto query_of = [&](int k) -> uint32_t { return kKeepRec ? rec[k].x : qt[k].x; };
-    auto train_of = [&](int k) -> uint32_t { return kKeepRec ? rec[k].y : qt[k].y; };
-    // motion.setTo(0) for the part of the matrix area that the staged codes do not occupy: now, while the loads are in flight
-    const uint32_t staged16 = staged ? qA + qB : 0u;
-    {
-        const uint4 z4 = make_uint4(0, 0, 0, 0);
-        uint4* d4 = reinterpret_cast<uint4*>(smem);
-        // (staged: the first kStageRegs * NT slots are written below, codes or zeros)
-        for (uint32_t i = (staged ? max(staged16, (uint32_t)(kStageRegs * NT)) : 0u) + tid; i < kDenseBytes / 16; i += NT) d4[i] = z4;
-    }
-    if (staged) {
-        // UNCONDITIONAL stores, the data selected: a store under a condition lets the compiler sink its load into the branch, behind
-        // the clear, with a wait of its own -- one round trip per register instead of all of them in flight from the top
-        static_assert((size_t)kStageRegs * NT * 16 <= kDenseBytes, "the register-staged slots lie inside the matrix area");
-        uint4* d4 = reinterpret_cast<uint4*>(smem);
-#pragma unroll
-        for (int i = 0; i < kStageRegs; ++i) {
-            const bool in = (uint32_t)(i * NT + tid) < qA + qB;
-            d4[i * NT + tid] = make_uint4(in ? tb[i].x : 0u, in ? tb[i].y : 0u, in ? tb[i].z : 0u, in ? tb[i].w : 0u);
-        }
-        for (uint32_t j = kStageRegs * NT + tid; j < qA + qB; j += NT) d4[j] = *(j < qA ? srcA + j : srcB + (j - qA));
-    }
-    const uint16_t* ldsA = reinterpret_cast<const uint16_t*>(smem) + phA;  // left code of frame A's keypoint q at ldsA[q]
-    const uint16_t* ldsB = reinterpret_cast<const uint16_t*>(smem + 4u * qA) + phB;  // right code of frame B's keypoint t at ldsB[t]
-    __syncthreads();
-#ifdef GMS_PHASE_TIMING
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    GMS_STAMP(4);  // bin: records landed, codes staged
-    ph_[15] = wall_clock64();
-#endif
-
-    // With rotation: row1 = byte offset of the left cell's row under grid type 1. Without, the cell rides in the code word
-    // (two more instructions per use, ten registers fewer -- this variant sits at the 128-register limit).
-    constexpr bool kPackCell = !ROT;
-    uint32_t code[KPT], row1[kPackCell ? 1 : KPT];
-    auto row_of = [&](int k, uint32_t cw, uint32_t q_mask) -> uint32_t {
-        if (kPackCell) return __umul24(((cw >> kDCellShift) & 0x1FFu) + (cw & q_mask), kDenseRow);
-        return __umul24(cw & q_mask, kDenseRow) + row1[k];
-    };
-    {
-        uint32_t ca[KPT], cb[KPT];
-        if (staged) {
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) ca[k] = ldsA[min(query_of(k), (uint32_t)(nA - 1))];
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) cb[k] = ldsB[min(train_of(k), (uint32_t)(nB - 1))];
-        } else {  // frames too large to stage: both gathers go to global memory
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) ca[k] = lcodeA[min(query_of(k), (uint32_t)(nA - 1))];
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) cb[k] = rcodeB[min(train_of(k), (uint32_t)(nB - 1))];
-        }
-#ifdef GMS_PHASE_TIMING
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        GMS_STAMP(12);  // bin: gathers landed
-#endif
-        bool any_bad = false, spill = false;
-#pragma unroll
-        for (int k = 0; k < KPT; ++k) {
-            const bool live = match_of(k) < m;
-            const uint32_t e0 = cb[k] & kDEMask;  // E(r) of getGridIndexRight on the 20 x 20 grid, 0 = outside it (no bounds test in the reference)
-            // parity domain: indices in range, both points inside it, the right cell inside its grid ('&', not '&&': no branches)
-            const uint32_t cell = ca[k] >> kLCellShift;  // under grid type 1; kLCellNever / kLCellBad above the grid
-            const bool ok = ((int)(query_of(k) < (uint32_t)nA) & (int)(train_of(k) < (uint32_t)nB) & (int)(cell != kLCellBad) & (int)((cb[k] & kRCodeBad) == 0u) & (int)(e0 != 0u)) != 0;
-            const bool binned = live & ok & (cell < kLCellNever);
-            // half-cell histogram: dword = the cell under grid type 1, byte = (hx & 1) + 2 (hy & 1); q = (hx & 1) + 20 (hy & 1)
-            const uint32_t sh = ((ca[k] & 1u) << 3) | ((ca[k] & 4u) << 2);
-            const uint32_t old = atomicAdd(binned ? &nfine32[cell] : &trash[lane & 7], 1u << sh);
-            spill |= binned & (((old >> sh) & 255u) == 255u);  // the byte wrapped: > 255 in one half cell
-            any_bad |= live & !ok;
-            // the dense code word: q as it stands, the edge bits one place up, E(r), and (without rotation) the cell
-            const uint32_t cw = (ca[k] & 31u) | ((ca[k] & 0x60u) << 1) | (e0 << kDEShift) | (kPackCell ? cell << kDCellShift : 0u);
-            code[k] = binned ? cw : kDNever;
-            if (!kPackCell) row1[k] = binned ? __umul24(cell, kDenseRow) : 0u;
-        }
-        if (any_bad) misc[8] = 1;   // benign races: every writer stores 1
-        if (spill) misc[13] = 1;  // (its own flag: misc[11] is written again while slower waves may still be reading this one)
-    }
-    GMS_STAMP(13);    // bin: codes + half-cell histogram
-    __syncthreads();  // histogram complete; every read of the staged frame is done
-    GMS_STAMP(0);     // bin: wait for the other waves
-
-    // ---- motion.setTo(0), once: from here on every grid type leaves the matrix as it found it. The row headers are
-    //      never reset either: a grid type's arg-max keys carry the type in their top bits, so they outrank
-    //      whatever the previous type left there (its cellPairs word, which is below 2^17).
-    {
-        const uint4 z4 = make_uint4(0, 0, 0, 0);
-        uint4* d4 = reinterpret_cast<uint4*>(smem);
-        for (uint32_t i = tid; i < staged16; i += NT) d4[i] = z4;  // the rest was cleared while the records were loading
-    }
-    __syncthreads();
-    GMS_STAMP(2);  // clear
-    if (misc[8] != 0) {    // an input outside the parity domain (workgroup-uniform; nothing has been written to global memory yet)
-        __syncthreads();   // everybody has read the flag before the general path reuses the LDS
-        return false;
-    }
-    const bool spilled = misc[13] != 0;  // a half cell above 255 matches: straight to the crowded mode below
-
-    const bool thr_fast = threshold_fast_ok(p.threshold_factor);
-    const uint32_t f2i = dense_factor_sq(p.threshold_factor);
-    uint32_t* nl32 = nfine32;  // crowded mode: nLeft as 16-bit counters, two buffers of 400 (one per parity of the grid type)
-    auto cell_of = [&](int k, uint32_t cw, uint32_t q_mask) -> uint32_t {
-        if (kPackCell) return ((cw >> kDCellShift) & 0x1FFu) + (cw & q_mask);
-        return (((__umul24(cw & q_mask, kDenseRow) + row1[k]) >> 2) * 649u) >> 16;  // row / 404 for rows below 400
-    };
-
-    // The four grid types. CROWDED = some left cell holds more than 255 matches: a matrix entry still only overflows its byte
-    // when ONE (left cell, right cell) pair collects more than 255, which crowded scenes rarely do -- so the same byte matrix
-    // is used, with nLeft counted per grid type into 16-bit counters (one more LDS atomic per match, over the then useless
-    // half-cell histogram) and every returned count checked. Returns 0 = done, 1 = a cell above 255 matches (run again
-    // CROWDED), 2 = a matrix entry at its limit (the general path takes the pair).
-    auto run_types = [&](auto crowded_c) -> int {
-    constexpr bool CROWDED = decltype(crowded_c)::value;
-    for (int g = 0; g < 4; ++g) {
-        const int gx = g & 1, gy = g >> 1;
-        const uint32_t q_mask = (uint32_t)(gx + 20 * gy);                                 // l = l1 + (q & q_mask)
-        const uint32_t out_mask = kDNever | (gx ? kDEdgeX : 0u) | (gy ? kDEdgeY : 0u);    // x >= 20 || y >= 20 -> -1 (DLL@0x180047d3d)
-        const uint32_t key_tag = (uint32_t)g << kDTagShift;
-        uint32_t* nl32cur = nl32 + (g & 1) * (kLeftN / 2);
-        const uint16_t* nl16cur = reinterpret_cast<const uint16_t*>(nl32cur);
-        if (!CROWDED && tid < kLeftN) {
-            // nLeft of this grid type, once per cell (read by verify, behind the next barrier); above 255 a row's entries
-            // are no longer guaranteed to fit their bytes
-            const uint32_t n = dense_nleft_cm(nfine8, tid % kLeftW, tid / kLeftW, gx, gy);
-            if (n > 255u) misc[11] = 1;
-            nleft8[tid] = (uint8_t)n;
-        }
-
-        // ---- assignMatchPairs: motion[l][r]++ on the byte; the count it produced goes into the row's arg-max
-#pragma unroll
-        for (int k0 = 0; k0 < KPT; k0 += kChunk) {
-            uint32_t old[kChunk], at[kChunk], row[kChunk];
-#pragma unroll
-            for (int c = 0; c < kChunk; ++c) {
-                const uint32_t cw = code[k0 + c];
-                row[c] = row_of(k0 + c, cw, q_mask);
-                at[c] = row[c] + ((cw >> kDEShift) & kDEMask);
-                old[c] = 0;
-                // shift counts are taken modulo 32: at << 3 selects the byte (at & 3)
-                if ((cw & out_mask) == 0) {
-                    old[c] = atomicAdd(lds_at(smem, at[c] & ~3u), 1u << ((at[c] << 3) & 31u));
-                    if (CROWDED) {
-                        const uint32_t l = cell_of(k0 + c, cw, q_mask);
-                        atomicAdd(&nl32cur[l >> 1], 1u << ((l & 1u) << 4));
-                    }
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);  // all of the chunk's atomics are issued before any result is read
-#pragma unroll
-            for (int c = 0; c < kChunk; ++c) {
-                const uint32_t cw = code[k0 + c];
-                const uint32_t before = (old[c] >> ((at[c] << 3) & 31u)) & 255u;  // <= 254, or ...
-                if (CROWDED && (cw & out_mask) == 0 && before == 255u) misc[12] = 1;  // ... the entry's byte has just wrapped
-                if ((cw & out_mask) == 0) atomicMax(lds_at(smem, row[c]), key_tag | (before << 11) | ((cw >> kDEShift) & kDEMask));
-            }
-        }
-        GMS_STAMP(3);  // insert
-        __syncthreads();
-        GMS_STAMP(11);  // insert: wait for the other waves
-        if (!CROWDED && misc[11] != 0) return 1;  // a cell above 255 matches under this grid type (workgroup-uniform)
-        if (CROWDED && misc[12] != 0) return 2;   // a (left cell, right cell) pair above 255 matches
-
-        // ---- verifyCellPairs. Without rotation: two lanes per left cell, four neighbours each, joined by one DPP
-        //      exchange; with rotation: one lane per (cell, rotation).
-        {
-            constexpr int kItems = ROT ? kLeftN * 8 : kLeftN * 2;
-            for (int item = tid; item < ((kItems + 63) & ~63); item += NT) {
-                const bool live = item < kItems;
-                const int i = live ? (ROT ? (item >> 3) : (item >> 1)) : 0;
-                const int rot = ROT ? (item & 7) : 0;
-                const int half = item & 1;  // !ROT only
-                const int ix = i % kLeftW, iy = i / kLeftW;
-                const uint32_t ni = live ? (CROWDED ? (uint32_t)nl16cur[i] : (uint32_t)nleft8[i]) : 0u;
-                if (__ballot(ni != 0) == 0ull) continue;  // none of this wave's cells has a match under this grid type
-                const uint32_t best = smem[i * (kDenseRow / 4)] & ((1u << kDTagShift) - 1u);  // ((max count - 1) << 11) | E(j*), lowest j* among maxima
-                const uint32_t ej = ni ? (best & kDEMask) : (uint32_t)(kDenseRightN + 3);
-                const int j = kDenseRightN + 3 - (int)ej;
-                const int jx = j % kDenseRightW, jy = j / kDenseRightW;
-                uint32_t score = 0, tn = 0;  // tn = (sum of nLeft << 4) | numpair
-#pragma unroll
-                for (int h = 0; h < (ROT ? 8 : 4); h += 4) {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        int ldx, ldy, rdx, rdy;
-                        if (ROT) {
-                            const int k8 = h + c;
-                            const int k = k8 < 4 ? k8 : k8 + 1;
-                            constexpr int kRingIndex[9] = {0, 1, 2, 7, -1, 3, 6, 5, 4};  // position -> ring index
-                            const int q = rotated_position(rot, kRingIndex[k]);
-                            ldx = (k % 3) - 1; ldy = (k / 3) - 1;
-                            rdx = position_dx(q); rdy = position_dy(q);
-                        } else {
-                            ldx = half ? ((c + 5) % 3) - 1 : (c % 3) - 1;  // lane 0: neighbours 0..3, lane 1: 5..8
-                            ldy = half ? ((c + 5) / 3) - 1 : (c / 3) - 1;
-                            rdx = ldx; rdy = ldy;
-                        }
-                        const int lx = ix + ldx, ly = iy + ldy;
-                        const int rx = jx + rdx, ry = jy + rdy;
-                        const bool okl = ni != 0 && (uint32_t)lx < (uint32_t)kLeftW && (uint32_t)ly < (uint32_t)kLeftH;  // ll != -1
-                        const bool okp = okl && (uint32_t)rx < (uint32_t)kDenseRightW && (uint32_t)ry < (uint32_t)kDenseRightW;  // rr != -1
-                        const uint32_t ll = okl ? (uint32_t)(lx + ly * kLeftW) : 0u;
-                        const uint32_t nll = CROWDED ? (uint32_t)nl16cur[ll] : (uint32_t)nleft8[ll];
-                        const uint32_t cnt = dense8[ll * kDenseRow + (okp ? (uint32_t)(kDenseRightN + 3 - (rx + ry * kDenseRightW)) : 4u)];
-                        score += okp ? cnt : 0u;
-                        tn += okp ? ((nll << 4) | 1u) : 0u;
-                    }
-                }
-                if (!ROT) {
-                    score += dpp_xor1(score);
-                    tn += dpp_xor1(tn);
-                }
-                score += (best >> 11) + 1u;  // centre pair (k = 4): ll = i, rr = j*, the arg-max count itself
-                tn += (ni << 4) | 1u;
-                uint32_t pass = 0;
-                if (ni != 0 && (ROT || half == 0))
-                    pass = (CROWDED ? threshold_rejects(tn >> 4, tn & 15u, score, p.threshold_factor, thr_fast)
-                                    : dense_threshold_rejects(tn >> 4, tn & 15u, score, p.threshold_factor, thr_fast, f2i)) ? 0u : 1u;
-                uint32_t bits = pass;
-                bool writer = ni != 0 && half == 0;
-                if (ROT) {
-                    const unsigned long long bal = __ballot(pass);
-                    bits = (uint32_t)(bal >> (lane & 56)) & 0xFFu;
-                    writer = ni != 0 && (lane & 7) == 0;
-                }
-                // every lane of the cell has read the header above (same wave, program order): it now holds cellPairs[i]
-                if (writer) smem[i * (kDenseRow / 4)] = (ej << 8) | bits;
-            }
-        }
-        __syncthreads();
-        GMS_STAMP(5);  // verify
-
-        // ---- mark inliers: cellPairs[l] == r, all rotations at once; and take this grid type's increments back
-        {
-            uint32_t cr[KPT];
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) {
-                const uint32_t cw = code[k];
-                const uint32_t row = row_of(k, cw, q_mask);
-                cr[k] = 0xFFFFFFFFu;
-                if ((cw & out_mask) == 0) {
-                    cr[k] = smem[row >> 2];
-                    if (g < 3) {
-                        const uint32_t at = row + ((cw >> kDEShift) & kDEMask);
-                        // every reader of the entry is past the barrier: all its matches store the same zero (a plain byte store,
-                        // no read-modify-write in the LDS)
-                        reinterpret_cast<uint8_t*>(smem)[at] = 0;
-                    }
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) {
-                const uint32_t x = cr[k] ^ (code[k] & (kDEMask << kDEShift));  // < 256: same right cell, x = rotation bits
-                if (x < 256u) code[k] |= x << kDAccShift;
-            }
-        }
-        if (CROWDED && tid < kLeftN / 2) nl32[((g + 1) & 1) * (kLeftN / 2) + tid] = 0;  // the next grid type's counters (last read two barriers ago)
-        __syncthreads();  // the next grid type writes the headers; after the last one the matrix area is reused below
-        GMS_STAMP(6);  // mark
-    }
-    return 0;
-    };
-
-    int status = 1;
-    if (!spilled) status = run_types(std::false_type{});
-    if (status == 1) {
-        // crowded: start over on a clean matrix (the abandoned grid type's bytes may have wrapped), no inlier bits yet
-        __syncthreads();
-        {
-            const uint4 z4 = make_uint4(0, 0, 0, 0);
-            uint4* d4 = reinterpret_cast<uint4*>(smem);
-            for (uint32_t i = tid; i < kDenseBytes / 16; i += NT) d4[i] = z4;
-            if (tid < kLeftN) nl32[tid] = 0;
-            if (tid == 0) misc[11] = 0;
-        }
-#pragma unroll
-        for (int k = 0; k < KPT; ++k) code[k] &= ~((kPackCell ? 1u : 0xFFu) << kDAccShift);  // (the packed cell sits right above the one bit)
-        __syncthreads();
-        status = run_types(std::true_type{});
-    }
-    if (status != 0) {
-        __syncthreads();  // everybody has read the flags before the general path reuses the LDS
-        return false;
-    }
-
-
-    // ---- run() return value per rotation and getInlierMask's strict '>' over the rotations (one scale). Without
-    //      rotation there is one hypothesis: it wins iff it keeps anything, which the scan below reports anyway.
-    int winner = 0;
-    if (ROT) {
-        uint32_t cnt[kNRot];
-#pragma unroll
-        for (int r = 0; r < kNRot; ++r) cnt[r] = 0;
-#pragma unroll
-        for (int k = 0; k < KPT; ++k)
-#pragma unroll
-            for (int r = 0; r < kNRot; ++r)
-                cnt[r] += (uint32_t)__popcll(__ballot((code[k] >> (kDAccShift + r)) & 1u));
-        if (lane == 0) {
-#pragma unroll
-            for (int r = 0; r < kNRot; ++r)
-                if (cnt[r]) atomicAdd(&misc[r], cnt[r]);
-        }
-        __syncthreads();
-        uint32_t best_count = 0;
-        winner = -1;
-#pragma unroll
-        for (int r = 0; r < kNRot; ++r) {
-            const uint32_t c = misc[r];
-            if (c > best_count) {
-                best_count = c;
-                winner = r;
-            }
-        }
-    }
-    GMS_STAMP(7);  // count + select
-
-    // ---- copy-out: surviving DMatch verbatim, in input order (DLL@0x180048340), from the registers.
-    constexpr int kWaves = NT / 64;
-    uint32_t* cnt_tab = smem;  // in the matrix area
-    unsigned long long keep[KPT];
-#pragma unroll
-    for (int k = 0; k < KPT; ++k) keep[k] = winner >= 0 ? __ballot((code[k] >> (kDAccShift + max(winner, 0))) & 1u) : 0ull;
-    gms_dmatch* __restrict__ out = p.out + pr.match_off;
-    uint8_t* mask_out = p.mask ? p.mask + pr.match_off : nullptr;
-    uint32_t total = 0;
-    if (!dealt) {
-        // A chunk is 64 consecutive matches = one wave's k-th record; chunk (k, wave) sits at position k * 16 + wave of the order.
-        // Every wave publishes its KPT popcounts, then scans all KPT * 16 of them itself (one barrier, no further exchange).
-        constexpr int kScanRegs = (KPT * kWaves + 63) / 64;
-#pragma unroll
-        for (int k = 0; k < KPT; ++k)
-            if (lane == 0) cnt_tab[k * kWaves + wave] = (uint32_t)__popcll(keep[k]);
-        __syncthreads();
-        uint32_t excl[kScanRegs];
-#pragma unroll
-        for (int v = 0; v < kScanRegs; ++v) {
-            const int idx = v * 64 + lane;
-            const uint32_t c = idx < KPT * kWaves ? cnt_tab[idx] : 0u;
-            uint32_t incl = c;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t t = __shfl_up(incl, d);
-                if (lane >= d) incl += t;
-            }
-            excl[v] = total + incl - c;
-            total += __shfl(incl, 63);
-        }
-        GMS_STAMP(8);  // out scan
-#pragma unroll
-        for (int k = 0; k < KPT; ++k) {
-            const int i = k * NT + tid;
-            const int ch = k * kWaves + wave;                      // wave-uniform
-            static_assert(64 % kWaves == 0, "a wave's chunk never straddles two scan registers");
-            const uint32_t base = __shfl(excl[(k * kWaves) >> 6], ch & 63);
-            if (i < m) {
-                const bool in = (keep[k] >> lane) & 1ull;
-                if (mask_out) mask_out[i] = in ? 1 : 0;
-                if (in) {
-                    const uint32_t pos = base + (uint32_t)__popcll(keep[k] & ((1ull << lane) - 1ull));
-                    *reinterpret_cast<uint4*>(&out[pos]) = kKeepRec ? rec[k] : *reinterpret_cast<const uint4*>(&matches[i]);
-                }
-            }
-        }
-    } else {
-        // Dealt matches: the order is that of the 8-match units (see match_of). Every 8-lane group publishes the popcount of its
-        // byte of the wave's ballot, the workgroup scans the KPT * 128 counts (two per thread, two more barriers), and a lane's slot
-        // is its unit's base plus its rank in the byte.
-        constexpr int kUnits = KPT * NT / 8;
-        static_assert(kUnits <= 2 * NT, "two scan entries per thread");
-        uint32_t* wave_tot = misc + 16;
-#pragma unroll
-        for (int k = 0; k < KPT; ++k)
-            if ((lane & 7) == 0) cnt_tab[match_of(k) >> 3] = (uint32_t)__popc((uint32_t)(keep[k] >> (lane & 56)) & 0xFFu);
-        __syncthreads();
-        {
-            const uint32_t c0 = 2 * tid < kUnits ? cnt_tab[2 * tid] : 0u, c1 = 2 * tid + 1 < kUnits ? cnt_tab[2 * tid + 1] : 0u;
-            uint32_t incl = c0 + c1;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t t = __shfl_up(incl, d);
-                if (lane >= d) incl += t;
-            }
-            if (lane == 63) wave_tot[wave] = incl;
-            __syncthreads();
-            uint32_t off = 0;
-#pragma unroll
-            for (int w = 0; w < kWaves; ++w) {
-                const uint32_t tw = wave_tot[w];
-                off += w < wave ? tw : 0u;
-                total += tw;
-            }
-            if (2 * tid < kUnits) cnt_tab[2 * tid] = off + incl - c0 - c1;
-            if (2 * tid + 1 < kUnits) cnt_tab[2 * tid + 1] = off + incl - c1;
-        }
-        __syncthreads();
-        GMS_STAMP(8);  // out scan
-#pragma unroll
-        for (int k = 0; k < KPT; ++k) {
-            const int i = match_of(k);
-            if (i < m) {
-                const uint32_t byte = (uint32_t)(keep[k] >> (lane & 56)) & 0xFFu;  // the unit's survivors
-                const bool in = (byte >> (lane & 7)) & 1u;
-                if (mask_out) mask_out[i] = in ? 1 : 0;
-                if (in) {
-                    const uint32_t pos = cnt_tab[i >> 3] + (uint32_t)__popc(byte & ((1u << (lane & 7)) - 1u));
-                    *reinterpret_cast<uint4*>(&out[pos]) = kKeepRec ? rec[k] : *reinterpret_cast<const uint4*>(&matches[i]);
-                }
-            }
-        }
-    }
-    GMS_STAMP(9);  // copy-out
-    GMS_STAMP_FLUSH;
-    if (tid == 0) {
-        gms_pair_result r;
-        r.n_inliers = (int)total;
-        r.best_scale = total ? 0 : -1;
-        r.best_rot = total ? winner + 1 : -1;
-        r.status = GMS_OK;
-        p.results[pair_idx] = r;
-    }
-    return true;
-}
-
-// ------------------------------------------------------------------------------------------------
-// dense_pair_plain: the byte-matrix path WITHOUT rotation hypotheses (the reference's default flags, DisparityUtil.cpp:149,299 --
-// the headline workload), rewritten in round 3 around the instruction count: the kernel is bound by vector-instruction issue
-// (DESIGN.md section 6), and dense_pair<ROT = false> spent 20 vector instructions per match and grid type on binning, 9 on
-// marking, 140 per cell on verification. Same matrix, same phases, same results; what changed:
-//   * the code word is [entry under grid type 1 = 404 * cell + E : 18 | E : 9 | q and the two edge bits : 5]: the entry under
-//     grid type g is one and + one shift + one multiply-add away, the row header is "entry - E";
-//   * nothing is predicated: a match that is not binned under the current grid type (never, or in the last half cell of a shifted
-//     axis) swaps its code word for the lane's SINK word -- an entry in the 64 spare bytes behind the matrix -- and runs the same
-//     instructions as everybody else (no exec masks, no branches around the LDS atomics);
-//   * LDS is addressed by absolute byte offsets (the dynamic segment starts at 0 in these kernels): no "+ base" per access;
-//   * the inlier flag of a match is one bit of a wave-wide mask in scalar registers (v_cmp writes it; the copy-out wants the
-//     ballot anyway), the row header after verification is E(j*) when the cell pair passes and 0 when it does not: marking is
-//     one compare;
-//   * verification: the eight neighbour pairs of a cell are base + s * 403 * d for d in {-21, -20, -19, -1} and s = +-1 (the two
-//     lanes of a cell), their validity three compares per axis; an invalid pair reads a byte that is always zero.
-// ------------------------------------------------------------------------------------------------
-// plain code word
-constexpr uint32_t kPEdgeX = 1u << 1, kPEdgeY = 1u << 3;  // in the gaps of q = (hx & 1) + 20 (hy & 1) (bits 0, 2, 4)
-constexpr int kPEShift = 5;                                // bits 5..13  E(r); 0 = the sink word (binned nowhere)
-constexpr int kPAtShift = 14;                              // bits 14..31 byte offset of the entry under grid type 1: 404 * cell + E
-static_assert(kDenseLdsBytes < (1u << 18), "an entry offset is 18 bits");
-// byte 3 of a row header is zero at all times (arg-max keys end at bit 21, cellPairs words at bit 8)
-constexpr uint32_t kPZeroByte = 3u;
-
-template <int KPT, int NT, bool DEALT>
-__device__ __forceinline__ bool dense_pair_plain(const FilterParams& p, uint32_t* smem, const int pair_idx, const int tid)
-{
-    constexpr int kMcap = KPT * NT;
-    constexpr int kChunk = (KPT % 5 == 0) ? 5 : 4;
-    static_assert(KPT % kChunk == 0, "KPT must be a multiple of the chunk");
-    static_assert(NT >= 2 * kLeftN, "verification: two lanes per left cell in one sweep");
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    constexpr int kUnitsPerBlock = KPT * (NT / 64);   // (lane mapping: see dense_pair)
-    constexpr bool dealt = DEALT;
-    const int m_base = dealt ? ((((lane >> 3) * kUnitsPerBlock + wave) << 3) | (lane & 7)) : tid;
-    const int m_stride = dealt ? (NT / 64) * 8 : NT;
-    auto match_of = [&](int k) -> int { return m_base + k * m_stride; };
-
-    // the absolute LDS offsets below assume the dynamic segment starts at 0 (no static LDS in the kernels that call this)
-    if ((uint32_t)(uintptr_t)((lds_u32_t*)smem) != 0u) return false;
-
-    int64_t total_kp;
-    const gms_pair pr = load_pair(p.pairs, pair_idx, p, total_kp);  // (and the frame table's header word)
-    const int m = pr.m;
-    if (p.with_scale || p.with_rotation || p.right_w[0] != kDenseRightW || p.right_h[0] != kDenseRightW || m <= 0 || m > kMcap ||
-        pr.frame_a < 0 || pr.frame_a >= p.n_frames || pr.frame_b < 0 || pr.frame_b >= p.n_frames)
-        return false;
-    // the frame ranges and, right behind them, the pair's DMatch records: the records do not depend on the ranges, so they travel
-    // beside them instead of a round trip later.
-    // The records of a thread's first kKeep matches stay in registers from here to the copy-out (all of them up to ten matches per
-    // thread; at sixteen the first twelve: 16 384 matches per pair 5.58 M pairs/s keeping none, 6.06 M keeping eight, 6.41 M twelve,
-    // 6.67 M fourteen -- with 8 bytes of scratch --, 6.21 M all sixteen with 36); the others are loaded as (queryIdx, trainIdx) alone and
-    // the survivors among them are read again at the end.
-    const FrameRangeWords fr_words = request_frame_ranges(p.frame_off, pr.frame_a, pr.frame_b);
-    const gms_dmatch* __restrict__ matches = p.matches + pr.match_off;
-    constexpr int kKeep = KPT <= 10 ? KPT : (DEALT ? 10 : 12);  // (the dealt instantiation has two registers less to spare)
-    uint4 rec[kKeep];
-    uint2 qt[KPT > kKeep ? KPT - kKeep : 1];
-#pragma unroll
-    for (int k = 0; k < KPT; ++k) {
-        if (k < kKeep) { const u32x4_t rv = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(&matches[min(match_of(k), m - 1)])); rec[k] = make_uint4(rv.x, rv.y, rv.z, rv.w); }
-        else qt[k - kKeep] = *reinterpret_cast<const uint2*>(&matches[min(match_of(k), m - 1)]);
-    }
-    int64_t offA, offB;
-    int nA, nB;
-    take_frame_ranges(fr_words, offA, nA, offB, nB);
-    if (nA <= 0 || nB <= 0) return false;
-    if (total_kp < 0 || offA + nA > total_kp || offB + nB > total_kp) return false;  // (workgroup-uniform) no header, or frames beyond the table
-    const uint16_t* __restrict__ lcodeA = reinterpret_cast<const uint16_t*>(p.pts + total_kp) + offA;
-    const uint16_t* __restrict__ rcodeB = reinterpret_cast<const uint16_t*>(p.pts + total_kp) + total_kp + offB;
-
-    uint32_t* nfine32 = smem + kDenseFineOff / 4;   // half-cell histogram: one dword per cell of grid type 1, a byte per half cell
-    const uint8_t* nfine8 = reinterpret_cast<const uint8_t*>(nfine32);
-    uint32_t* misc = smem + kDenseMiscOff / 4;
-    uint32_t* trash = smem + kDenseTrashOff / 4;
-
-    GMS_STAMP_DECL
-#ifdef GMS_PHASE_TIMING
-    ph_[14] = wall_clock64();
-#endif
-    if (tid < 32) misc[tid] = 0;
-    if (tid < 16) trash[tid] = 0;
-    if (tid < kFineN / 4) nfine32[tid] = 0;
-
-    // ---- staging: both frames' code words into the still unused matrix area, then the pair's DMatch records (see dense_pair)
-    const uint32_t phA = (uint32_t)(reinterpret_cast<uintptr_t>(lcodeA) >> 1) & 7u, phB = (uint32_t)(reinterpret_cast<uintptr_t>(rcodeB) >> 1) & 7u;
-    const uint32_t qA = (phA + (uint32_t)nA + 7u) >> 3, qB = (phB + (uint32_t)nB + 7u) >> 3;
-    const bool staged = (qA + qB) * 16u <= kDenseBytes;
-    const uint4* __restrict__ srcA = reinterpret_cast<const uint4*>(lcodeA - phA);
-    const uint4* __restrict__ srcB = reinterpret_cast<const uint4*>(rcodeB - phB);
-    constexpr int kStageRegs = 3;
-    uint4 tb[kStageRegs];
-#pragma unroll
-    for (int i = 0; i < kStageRegs; ++i) {
-        const uint32_t j = min((uint32_t)(i * NT + tid), qA + qB - 1u);
-        const uint4* src = j < qA ? srcA + j : srcB + (j - qA);
-        tb[i] = *src;
-    }
-    auto query_of = [&](int k) -> uint32_t { return k < kKeep ? rec[k < kKeep ? k : 0].x : qt[k < kKeep ? 0 : k - kKeep].x; };
-    auto train_of = [&](int k) -> uint32_t { return k < kKeep ? rec[k < kKeep ? k : 0].y : qt[k < kKeep ? 0 : k - kKeep].y; };
-    const uint32_t staged16 = staged ? qA + qB : 0u;
-    {
-        const uint4 z4 = make_uint4(0, 0, 0, 0);
-        uint4* d4 = reinterpret_cast<uint4*>(smem);
-        // (staged: the first kStageRegs * NT slots are written below, codes or zeros)
-        for (uint32_t i = (staged ? max(staged16, (uint32_t)(kStageRegs * NT)) : 0u) + tid; i < kDenseBytes / 16; i += NT) d4[i] = z4;
-    }
-    if (staged) {
-        // UNCONDITIONAL stores, the data selected: a store under a condition lets the compiler sink its load into the branch, behind
-        // the clear, with a wait of its own -- one round trip per register instead of all of them in flight from the top
-        static_assert((size_t)kStageRegs * NT * 16 <= kDenseBytes, "the register-staged slots lie inside the matrix area");
-        uint4* d4 = reinterpret_cast<uint4*>(smem);
-#pragma unroll
-        for (int i = 0; i < kStageRegs; ++i) {
-            const bool in = (uint32_t)(i * NT + tid) < qA + qB;
-            d4[i * NT + tid] = make_uint4(in ? tb[i].x : 0u, in ? tb[i].y : 0u, in ? tb[i].z : 0u, in ? tb[i].w : 0u);
-        }
-        for (uint32_t j = kStageRegs * NT + tid; j < qA + qB; j += NT) d4[j] = *(j < qA ? srcA + j : srcB + (j - qA));
-    }
-    const uint32_t ldsA = 2u * phA, ldsB = 16u * qA + 2u * phB;  // byte offsets: left code of frame A's keypoint q at ldsA + 2 q
-    __syncthreads();
-#ifdef GMS_PHASE_TIMING
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    GMS_STAMP(4);
-    ph_[15] = wall_clock64();
-#endif
-
-    // ---- code words + half-cell histogram
-    uint32_t code[KPT];
-    const uint32_t cw_sink = (kDenseTrashOff + 4u * (uint32_t)(lane & 15)) << kPAtShift;  // E = 0, q = 0, no edge bit
-    {
-        uint32_t ca[KPT], cb[KPT];
-        if (staged) {
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) ca[k] = ldsa_ld16(ldsA + 2u * min(query_of(k), (uint32_t)(nA - 1)));
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) cb[k] = ldsa_ld16(ldsB + 2u * min(train_of(k), (uint32_t)(nB - 1)));
-        } else {
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) ca[k] = lcodeA[min(query_of(k), (uint32_t)(nA - 1))];
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) cb[k] = rcodeB[min(train_of(k), (uint32_t)(nB - 1))];
-        }
-#ifdef GMS_PHASE_TIMING
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        GMS_STAMP(12);
-#endif
-        bool any_bad = false, spill = false;
-#pragma unroll
-        for (int k = 0; k < KPT; ++k) {
-            const bool live = match_of(k) < m;
-            const uint32_t e0 = cb[k] & kDEMask;
-            const uint32_t cell = ca[k] >> kLCellShift;
-            const bool ok = ((int)(query_of(k) < (uint32_t)nA) & (int)(train_of(k) < (uint32_t)nB) & (int)(cell != kLCellBad) & (int)((cb[k] & kRCodeBad) == 0u) & (int)(e0 != 0u)) != 0;
-            const bool binned = live & ok & (cell < kLCellNever);
-            const uint32_t sh = ((ca[k] & 1u) << 3) | ((ca[k] & 4u) << 2);
-            const uint32_t old = ldsa_add_rtn(binned ? kDenseFineOff + 4u * cell : kDenseTrashOff + 4u * (uint32_t)(lane & 7), 1u << sh);
-            spill |= binned & (((old >> sh) & 255u) == 255u);
-            any_bad |= live & !ok;
-            const uint32_t qe = (ca[k] & 21u) | ((ca[k] >> 4) & kPEdgeX) | ((ca[k] >> 3) & kPEdgeY);
-            const uint32_t at1 = __umul24(cell, kDenseRow) + e0;
-            code[k] = binned ? ((at1 << kPAtShift) | (e0 << kPEShift) | qe) : cw_sink;
-        }
-        if (any_bad) misc[8] = 1;
-        if (spill) misc[13] = 1;
-    }
-    GMS_STAMP(13);
-    __syncthreads();
-    GMS_STAMP(0);
-
-    // ---- motion.setTo(0), once (see dense_pair)
-    {
-        const uint4 z4 = make_uint4(0, 0, 0, 0);
-        uint4* d4 = reinterpret_cast<uint4*>(smem);
-        for (uint32_t i = tid; i < staged16; i += NT) d4[i] = z4;
-        // the sink dwords from here on: bit 31 set, and nothing below ever clears it (increments land in byte 0, arg-max keys end at
-        // bit 21, the undo stores a zero into byte 0) -- a sink is never equal to an E, so a sink word is nobody's inlier
-        if (tid < 16) trash[tid] = 0x80000000u;
-    }
-    __syncthreads();
-    GMS_STAMP(2);
-    if (misc[8] != 0) {
-        __syncthreads();
-        return false;
-    }
-    const bool spilled = misc[13] != 0;
-
-    const bool thr_fast = threshold_fast_ok(p.threshold_factor);
-    const uint32_t f2i = dense_factor_sq(p.threshold_factor);
-    uint32_t acc = 0;  // bit k: match k of this thread is an inlier under some grid type
-
-    // verification: lane pair of cell i = tid >> 1; the even lane takes the neighbour pairs at d = -21, -20, -19, -1 (positions 0..3 of
-    // the 3 x 3 block), the odd lane the mirrored ones (positions 8..5): s = +-1
-    const uint32_t vi = (uint32_t)tid >> 1;
-    const uint32_t viy = (vi * 3277u) >> 16, vix = vi - 20u * viy;  // vi / 20, vi % 20 for vi < 400 (and harmless above)
-    const bool vodd = (tid & 1) != 0;
-
-    // L2 prefetch for the workgroup that follows this one on the CU: workgroups are handed out in order, one per CU, so that is
-    // pair_idx + (number of CUs) -- on the same XCD (256 = 8 x 32)
-    const uint32_t* __restrict__ pf_base = nullptr;
-    uint32_t pf_lines = 0, pf_sink = 0, pf_sink2 = 0;
-    {
-        const int nxt = pair_idx + p.prefetch_ahead;
-        if (p.prefetch_ahead > 0 && nxt < p.n_pairs) {
-            const gms_pair pn = load_pair(p.pairs, nxt);
-            // (only what that pair's own workgroup will read as well: a pair it would refuse before reading -- frames out of range,
-            //  a negative offset -- is not touched either)
-            if (pn.m > 0 && pn.m <= kMcap && pn.match_off >= 0 && pn.frame_a >= 0 && pn.frame_a < p.n_frames && pn.frame_b >= 0 &&
-                pn.frame_b < p.n_frames) {
-                pf_base = reinterpret_cast<const uint32_t*>(p.matches + pn.match_off);
-                pf_lines = min(((uint32_t)pn.m * 16u + 127u) >> 7, 2u * NT);   // (the array's first line may start a little earlier: close enough)
-            }
-        }
-    }
-
-    auto run_types = [&](auto crowded_c) -> int {
-    constexpr bool CROWDED = decltype(crowded_c)::value;
-    for (int g = 0; g < 4; ++g) {
-        const int gx = g & 1, gy = g >> 1;
-        const uint32_t q_mask = (uint32_t)(gx + 20 * gy);                               // entry = entry1 + 404 * (q & q_mask)
-        const uint32_t x_mask = (gx ? kPEdgeX : 0u) | (gy ? kPEdgeY : 0u);              // x >= 20 || y >= 20 -> -1 (DLL@0x180047d3d)
-        const uint32_t key_tag = (uint32_t)g << kDTagShift;
-        const uint32_t nl_cur = kDenseFineOff + (uint32_t)(g & 1) * (kLeftN * 2u);      // crowded: 16-bit nLeft counters, two buffers
-        if (!CROWDED && g == p.prefetch_type && pf_lines) {
-            // touch the match records of the pair this CU's NEXT workgroup will filter (one dword per 128-byte line): they are in the
-            // XCD's L2 when that workgroup asks for them. Late on purpose -- one grid type before the end -- so that only a few
-            // CUs' worth of lines sit in the 4 MB at any time (touched at the start of a pair they are evicted before use).
-            // (two independent loads, consumed only before the copy-out: nothing waits for them here)
-            if ((uint32_t)tid < pf_lines) pf_sink = pf_base[32u * (uint32_t)tid];
-            if ((uint32_t)tid + NT < pf_lines) pf_sink2 = pf_base[32u * ((uint32_t)tid + NT)];
-        }
-        if (!CROWDED && tid < kLeftN) {
-            const uint32_t n = dense_nleft_cm(nfine8, tid % kLeftW, tid / kLeftW, gx, gy);
-            if (n > 255u) misc[11] = 1;
-            ldsa_st8(kDenseNleftOff + (uint32_t)tid, n);
-        }
-
-        // ---- assignMatchPairs
-        uint32_t ae[KPT];  // [E : 9 | entry : 18] of every match under this grid type (a sink's own for the matches it does not bin)
-#pragma unroll
-        for (int k0 = 0; k0 < KPT; k0 += kChunk) {
-            uint32_t old[kChunk], at[kChunk], cg[kChunk], sh[kChunk];
-#pragma unroll
-            for (int c = 0; c < kChunk; ++c) {
-                const uint32_t cw = code[k0 + c];
-                cg[c] = (cw & x_mask) ? cw_sink : cw;
-                at[c] = mad24_vsv(cg[c] & q_mask, kDenseRow, cg[c] >> kPAtShift);
-                sh[c] = at[c] << 3;  // (shifts and bit-field extracts read its low five bits: 8 * (entry & 3))
-                asm("" : "+v"(sh[c]));
-                old[c] = ldsa_add_rtn(at[c] & ~3u, 1u << (sh[c] & 31u));
-                if (CROWDED) {
-                    const uint32_t l = (((at[c] - ((cg[c] >> kPEShift) & kDEMask)) >> 2) * 649u) >> 16;  // row / 404 (the sink: 405)
-                    ldsa_add(nl_cur + 4u * (l >> 1), 1u << ((l & 1u) << 4));
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);  // all of the chunk's atomics are issued before any result is read
-#pragma unroll
-            for (int c = 0; c < kChunk; ++c) {
-                const uint32_t e = (cg[c] >> kPEShift) & kDEMask;
-                const uint32_t before = __builtin_amdgcn_ubfe(old[c], sh[c], 8);  // <= 254, or ...
-                if (CROWDED && e != 0u && before == 255u) misc[12] = 1;                // ... the entry's byte has just wrapped
-                ldsa_max(at[c] - e, key_tag | (before << 11) | e);
-                asm("v_lshl_or_b32 %0, %1, 18, %2" : "=v"(ae[k0 + c]) : "v"(e), "v"(at[c]));  // (opaque: the compiler cannot know that an entry is 18 bits)
-            }
-        }
-        GMS_STAMP(3);
-        __syncthreads();
-        GMS_STAMP(11);
-        if (!CROWDED && misc[11] != 0) return 1;
-        if (CROWDED && misc[12] != 0) return 2;
-
-        // ---- verifyCellPairs
-        if (tid < 2 * kLeftN) {
-            // (everything that does not depend on j* is read at once: the cell's nLeft, its header, the four neighbours' nLeft)
-            const int s1 = vodd ? -1 : 1;
-            const uint32_t nlb = (CROWDED ? nl_cur + 2u * vi : kDenseNleftOff + vi);
-            const uint32_t hdr = vi * kDenseRow;
-            const uint32_t ni = CROWDED ? ldsa_ld16(nlb) : ldsa_ld8(nlb);
-            const uint32_t hdr_word = ldsa_ld32(hdr);
-            uint32_t nl4[4];
-            {
-                constexpr int kD[4] = {-21, -20, -19, -1};
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const uint32_t na = nlb + (uint32_t)((CROWDED ? 2 : 1) * s1 * kD[c]);
-                    nl4[c] = CROWDED ? ldsa_ld16(na) : ldsa_ld8(na);
-                }
-            }
-            if (__ballot(ni != 0) != 0ull) {
-                const uint32_t best = hdr_word & ((1u << kDTagShift) - 1u);  // ((max count - 1) << 11) | E(j*), lowest j* among maxima
-                const uint32_t ej = ni ? (best & kDEMask) : (uint32_t)(kDenseRightN + 3);
-                const uint32_t j = (uint32_t)(kDenseRightN + 3) - ej;
-                const uint32_t jy = (j * 3277u) >> 16, jx = j - 20u * jy;
-                const uint32_t lo = vodd ? 19u : 0u, hi = 19u - lo;
-                const bool okA = (vix != lo) & (jx != lo);   // one step against s along x stays inside both grids
-                const bool okB = (vix != hi) & (jx != hi);   // one step with s along x
-                const bool okC = (viy != lo) & (jy != lo);   // one step against s along y
-                const int s403 = vodd ? -403 : 403;
-                const uint32_t base = hdr + ej;
-                uint32_t score = 0, tn = 0;  // tn = (sum of nLeft << 4) | numpair
-                auto side = [&](int c, int d, bool valid) {
-                    const uint32_t a = valid ? base + (uint32_t)(s403 * d) : kPZeroByte;
-                    score += ldsa_ld8(a);
-                    tn += valid ? ((nl4[c] << 4) | 1u) : 0u;
-                };
-                side(0, -21, okA & okC);
-                side(1, -20, okC);
-                side(2, -19, okB & okC);
-                side(3, -1, okA);
-                score += dpp_xor1(score);
-                tn += dpp_xor1(tn);
-                score += (best >> 11) + 1u;  // centre pair: ll = i, rr = j*, the arg-max count itself
-                tn += (ni << 4) | 1u;
-                if (ni != 0 && !vodd) {
-                    const bool rej = CROWDED ? threshold_rejects(tn >> 4, tn & 15u, score, p.threshold_factor, thr_fast)
-                                             : dense_threshold_rejects(tn >> 4, tn & 15u, score, p.threshold_factor, thr_fast, f2i);
-                    ldsa_st32(hdr, rej ? 0u : ej);  // cellPairs[i] as E(j*), 0 = none
-                }
-            }
-        }
-        __syncthreads();
-        GMS_STAMP(5);
-
-        // ---- mark inliers (cellPairs[l] == r) and take this grid type's increments back (plain zero bytes: see dense_pair)
-        uint32_t cur = 0;
-#pragma unroll
-        for (int k = 0; k < KPT; ++k) {
-            const uint32_t at = ae[k] & 0x3FFFFu, e = ae[k] >> 18;
-            const uint32_t cr = ldsa_ld32(at - e);  // (a sink's own dword: never equal to its E = 0)
-            ldsa_st8(at, 0u);                       // (after the last grid type as well: the area is free then)
-            cur = shift_in_equal(cur, cr, e);       // match k ends up in bit KPT - 1 - k
-        }
-        acc |= cur;
-        if (CROWDED && tid < kLeftN / 2) ldsa_st32(kDenseFineOff + (uint32_t)((g + 1) & 1) * (kLeftN * 2u) + 4u * (uint32_t)tid, 0u);
-        __syncthreads();
-        GMS_STAMP(6);
-    }
-    return 0;
-    };
-
-    int status = 1;
-    if (!spilled) status = run_types(std::false_type{});
-    if (status == 1) {
-        // crowded: start over on a clean matrix (the abandoned grid type's bytes may have wrapped), no inlier bits yet
-        __syncthreads();
-        {
-            const uint4 z4 = make_uint4(0, 0, 0, 0);
-            uint4* d4 = reinterpret_cast<uint4*>(smem);
-            for (uint32_t i = tid; i < kDenseBytes / 16; i += NT) d4[i] = z4;
-            if (tid < kLeftN) nfine32[tid] = 0;
-            if (tid == 0) misc[11] = 0;
-        }
-        acc = 0;
-        if (tid < 16) trash[tid] = 0x80000000u;
-        __syncthreads();
-        status = run_types(std::true_type{});
-    }
-    if (status != 0) {
-        __syncthreads();
-        return false;
-    }
-    GMS_STAMP(7);
-    if (p.prefetch_type == 4 && pf_lines) {  // (diagnostic setting: as late as possible)
-        if ((uint32_t)tid < pf_lines) pf_sink = pf_base[32u * (uint32_t)tid];
-        if ((uint32_t)tid + NT < pf_lines) pf_sink2 = pf_base[32u * ((uint32_t)tid + NT)];
-    }
-    // (never true: keeps the prefetch loads alive; they landed long ago, and no copy-out store has been issued yet)
-    if (p.prefetch_type != 4 && (pf_sink ^ pf_sink2) == 0x9E3779B9u && p.n_pairs < 0) trash[0] = pf_sink;
-
-    // ---- copy-out: surviving DMatch verbatim, in input order (DLL@0x180048340), from the registers (see dense_pair)
-    constexpr int kWaves = NT / 64;
-    uint32_t* cnt_tab = smem;
-    unsigned long long keep[KPT];
-#pragma unroll
-    for (int k = 0; k < KPT; ++k) keep[k] = __ballot((acc >> (KPT - 1 - k)) & 1u);
-    gms_dmatch* __restrict__ out = p.out + pr.match_off;
-    uint8_t* mask_out = p.mask ? p.mask + pr.match_off : nullptr;
-    uint32_t total = 0;
-    if (!dealt) {
-        uint32_t row_base[KPT];
-
-        // A chunk is 64 consecutive matches = one wave's k-th record; chunk (k, wave) sits at position k * 16 + wave of the order, so the
-        // sixteen chunks of one k are one 16-lane DPP row of the published counts: a row-wise scan on the vector ALU (four DPP adds
-        // per register, no LDS round trips), the rows' totals added up in scalar registers.
-        constexpr int kScanRegs = (KPT * kWaves + 63) / 64;
-        static_assert(kWaves == 16, "one DPP row per k");
-#pragma unroll
-        for (int k = 0; k < KPT; ++k)
-            if (lane == 0) cnt_tab[k * kWaves + wave] = (uint32_t)__popcll(keep[k]);
-        __syncthreads();
-        uint32_t excl[kScanRegs];
-#pragma unroll
-        for (int v = 0; v < kScanRegs; ++v) {
-            const int idx = v * 64 + lane;
-            const uint32_t c = idx < KPT * kWaves ? cnt_tab[idx] : 0u;
-            uint32_t incl = c;
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xF, 0xF, true);  // row_shr:1, zeros shifted in
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xF, 0xF, true);
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xF, 0xF, true);
-            incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xF, 0xF, true);
-            excl[v] = incl - c;  // within its row
-            (void)idx;
-            // totals of this register's rows, in order (scalar)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int k = v * 4 + r;
-                if (k < KPT) {
-                    row_base[k] = total;
-                    total += (uint32_t)__builtin_amdgcn_readlane((int)incl, r * 16 + 15);
-                }
-            }
-        }
-        GMS_STAMP(8);
-        const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-        // The records that were not kept in registers (KPT above kKeep) are read again, two at a time: requested together, the survivor's
-        // own or -- address selected -- the pair's first, and pinned before the stores (a load inside the survivor's branch is waited for
-        // there, one round trip per record).
-        auto put = [&](int k, const uint4& rv) {
-            const int i = k * NT + tid;
-            const uint32_t base = row_base[k] + (uint32_t)__builtin_amdgcn_readlane((int)excl[k >> 2], (k & 3) * 16 + wave_s);
-            if (i < m) {
-                const bool in = (keep[k] >> lane) & 1ull;
-                if (mask_out) mask_out[i] = in ? 1 : 0;
-                if (in) {
-                    const uint32_t pos = base + (uint32_t)__popcll(keep[k] & ((1ull << lane) - 1ull));
-                    __builtin_nontemporal_store(u32x4_t{rv.x, rv.y, rv.z, rv.w}, reinterpret_cast<u32x4_t*>(&out[pos]));
-                }
-            }
-        };
-#pragma unroll
-        for (int k = 0; k < kKeep; ++k) put(k, rec[k]);  // (their registers are free for the records read again)
-        constexpr int kBatch = 2;
-#pragma unroll
-        for (int k0 = kKeep; k0 < KPT; k0 += kBatch) {
-            uint4 again[kBatch];
-#pragma unroll
-            for (int j = 0; j < kBatch; ++j) {
-                const int k = k0 + j < KPT ? k0 + j : KPT - 1, i = k * NT + tid;
-                again[j] = *reinterpret_cast<const uint4*>(&matches[(i < m && ((keep[k] >> lane) & 1ull)) ? i : 0]);
-            }
-#pragma unroll
-            for (int j = 0; j < kBatch; ++j) asm volatile("" : "+v"(again[j].x), "+v"(again[j].y), "+v"(again[j].z), "+v"(again[j].w));
-#pragma unroll
-            for (int j = 0; j < kBatch; ++j)
-                if (k0 + j < KPT) put(k0 + j, again[j]);
-        }
-    } else {
-        constexpr int kUnits = KPT * NT / 8;
-        static_assert(kUnits <= 2 * NT, "two scan entries per thread");
-        uint32_t* wave_tot = misc + 16;
-#pragma unroll
-        for (int k = 0; k < KPT; ++k)
-            if ((lane & 7) == 0) cnt_tab[match_of(k) >> 3] = (uint32_t)__popc((uint32_t)(keep[k] >> (lane & 56)) & 0xFFu);
-        __syncthreads();
-        {
-            const uint32_t c0 = 2 * tid < kUnits ? cnt_tab[2 * tid] : 0u, c1 = 2 * tid + 1 < kUnits ? cnt_tab[2 * tid + 1] : 0u;
-            uint32_t incl = c0 + c1;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t t = __shfl_up(incl, d);
-                if (lane >= d) incl += t;
-            }
-            if (lane == 63) wave_tot[wave] = incl;
-            __syncthreads();
-            uint32_t off = 0;
-#pragma unroll
-            for (int w = 0; w < kWaves; ++w) {
-                const uint32_t tw = wave_tot[w];
-                off += w < wave ? tw : 0u;
-                total += tw;
-            }
-            if (2 * tid < kUnits) cnt_tab[2 * tid] = off + incl - c0 - c1;
-            if (2 * tid + 1 < kUnits) cnt_tab[2 * tid + 1] = off + incl - c1;
-        }
-        __syncthreads();
-        GMS_STAMP(8);
-        auto put = [&](int k, const uint4& rv) {
-            const int i = match_of(k);
-            if (i < m) {
-                const uint32_t byte = (uint32_t)(keep[k] >> (lane & 56)) & 0xFFu;
-                const bool in = (byte >> (lane & 7)) & 1u;
-                if (mask_out) mask_out[i] = in ? 1 : 0;
-                if (in) {
-                    const uint32_t pos = cnt_tab[i >> 3] + (uint32_t)__popc(byte & ((1u << (lane & 7)) - 1u));
-                    __builtin_nontemporal_store(u32x4_t{rv.x, rv.y, rv.z, rv.w}, reinterpret_cast<u32x4_t*>(&out[pos]));
-                }
-            }
-        };
-#pragma unroll
-        for (int k = 0; k < kKeep; ++k) put(k, rec[k]);
-        constexpr int kBatch = 2;  // (see the list-order branch)
-#pragma unroll
-        for (int k0 = kKeep; k0 < KPT; k0 += kBatch) {
-            uint4 again[kBatch];
-#pragma unroll
-            for (int j = 0; j < kBatch; ++j) {
-                const int k = k0 + j < KPT ? k0 + j : KPT - 1, i = match_of(k);
-                const bool in = i < m && (((uint32_t)(keep[k] >> (lane & 56)) >> (lane & 7)) & 1u) != 0u;
-                again[j] = *reinterpret_cast<const uint4*>(&matches[in ? i : 0]);
-            }
-#pragma unroll
-            for (int j = 0; j < kBatch; ++j) asm volatile("" : "+v"(again[j].x), "+v"(again[j].y), "+v"(again[j].z), "+v"(again[j].w));
-#pragma unroll
-            for (int j = 0; j < kBatch; ++j)
-                if (k0 + j < KPT) put(k0 + j, again[j]);
-        }
-    }
-    GMS_STAMP(9);
-    GMS_STAMP_FLUSH;
-    if (p.prefetch_type == 4 && (pf_sink ^ pf_sink2) == 0x9E3779B9u && p.n_pairs < 0) trash[0] = pf_sink;
-    if (tid == 0) {
-        gms_pair_result r;
-        r.n_inliers = (int)total;
-        r.best_scale = total ? 0 : -1;
-        r.best_rot = total ? 1 : -1;
-        r.status = GMS_OK;
-        p.results[pair_idx] = r;
-    }
-    return true;
-}
-
-template <int KPT, bool ROT, int NT, bool DEALT>
-__global__ void __launch_bounds__(NT)
-filter_kernel_dense(FilterParams p)
-{
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    first_round_stagger(p);
-    bool done;
-    if constexpr (ROT) done = dense_pair<KPT, true, NT, DEALT>(p, smem, (int)blockIdx.x, (int)threadIdx.x);
-    else done = dense_pair_plain<KPT, NT, DEALT>(p, smem, (int)blockIdx.x, (int)threadIdx.x);
-    if (!done) hash_pair<KPT, ROT, NT>(p, smem, (int)blockIdx.x, (int)threadIdx.x);
-}
-
 // Are a batch's matches in spatial order? One small workgroup, launched now and then behind a byte-matrix launch (gms_capi.cpp):
 // sixteen waves look at 64 consecutive matches in the middle of sixteen pairs spread over the batch and count neighbours in the list
 // whose left points share the cell of grid type 1 (random order: 1 in 400; a row-scanning detector or a per-pixel grid: most of them).
@@ -2025,735 +148,6 @@ order_probe_kernel(FilterParams p, uint32_t* __restrict__ flag)
     }
     __syncthreads();
     if (tid == 0 && s_seen != 0) *flag = 4u * s_same > s_seen ? 1u : 0u;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Scale hypotheses on the byte matrix (dense_scales_pair): the right grids of scales 0, 1 and 2 are 20 x 20,
-// 10 x 10 and 14 x 14, so their motion matrices (400 x 400, 400 x 100, 400 x 196 bytes) fit the LDS like the default
-// case; scale 3 (28 x 28: 400 rows of 788 bytes) fits in three bands of left rows; scale 4 (40 x 40: 1604-byte rows) would
-// need seven. With scale hypotheses a launch therefore runs two kernels: this one evaluates scales 0..3 (all rotations),
-// bounds scale 4 (the probe below, four halo-free bands) and leaves the best hypothesis so far -- count, (scale, rotation),
-// the inlier bit of every match -- in a per-pair workspace record together with what is decided; filter_kernel then picks
-// the record up, evaluates scale 4 on the hashed path unless the probe bounded it out, and selects and copies out as always
-// (getInlierMask's order is scale-outer, rotation-inner with strict '>', so "best of 0..3, then 4" is the same comparison
-// sequence). A pair this kernel cannot take (a cell above 255 matches, inputs outside the parity domain) gets an empty record
-// and the hashed path evaluates all five scales.
-// Everything is dense_pair() with a runtime row stride; the records are not kept (nothing is copied out here).
-// ------------------------------------------------------------------------------------------------
-
-// The copy-out of a pair whose five scale hypotheses are all decided in the byte-matrix kernel (the probe bounded scale 4 out): the
-// survivors in input order, the result record, the optional mask -- what the hashed kernel would otherwise start a workgroup for, read
-// the pair's record and 160 KB of DMatch records from HBM for, 100 us after this kernel had them. NOT inlined on purpose: a body of its
-// own register allocation, so that nothing here is live through the scale passes (round 3's inlined attempt paid for itself in spills).
-// A unit is eight consecutive matches = the byte of a ballot that an eight-lane group holds, in either lane mapping.
-template <int KPT, int NT>
-__device__ __noinline__ void scales_copy_out(const gms_pair* pairs, const gms_dmatch* all_matches, gms_dmatch* all_out, uint8_t* all_mask,
-                                             gms_pair_result* results, uint32_t* smem, int pair_idx, uint32_t bestbits, int dealt,
-                                             uint32_t best_count, int best_scale, int best_rot)
-{
-    constexpr int kUnits = KPT * NT / 8, kWaves = NT / 64;
-    static_assert(kUnits <= 2 * NT, "two scan entries per thread");
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const gms_pair pr = load_pair(pairs, pair_idx);
-    const int m = pr.m;
-    const gms_dmatch* __restrict__ matches = all_matches + pr.match_off;
-    gms_dmatch* __restrict__ out = all_out + pr.match_off;
-    uint32_t* cnt = smem;              // [kUnits] survivors per unit, then in front of it
-    uint32_t* wtot = smem + kUnits;    // [kWaves]
-    const int ubase = dealt ? (lane >> 3) * (KPT * kWaves) + wave : (tid >> 3);
-    const int ustep = dealt ? kWaves : NT / 8;
-    __syncthreads();  // (the matrix area is free)
-    uint32_t ranks[(KPT + 7) / 8] = {};  // four bits per match: survivors before it in its unit
-#pragma unroll
-    for (int k = 0; k < KPT; ++k) {
-        const unsigned long long bal = __ballot((bestbits >> k) & 1u);
-        const uint32_t byte = (uint32_t)(bal >> (lane & 56)) & 0xFFu;
-        if ((lane & 7) == 0) cnt[ubase + k * ustep] = (uint32_t)__popc(byte);
-        ranks[k >> 3] |= (uint32_t)__popc(byte & ((1u << (lane & 7)) - 1u)) << ((k & 7) * 4);
-    }
-    __syncthreads();
-    {   // exclusive scan over the units, two per thread
-        const uint32_t a = 2 * tid < kUnits ? cnt[2 * tid] : 0u, b = 2 * tid + 1 < kUnits ? cnt[2 * tid + 1] : 0u;
-        uint32_t incl = a + b;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
-            if (lane >= d) incl += up;
-        }
-        if (lane == 63) wtot[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0;
-        for (int w = 0; w < wave; ++w) before += wtot[w];
-        const uint32_t excl = before + incl - (a + b);
-        if (2 * tid < kUnits) cnt[2 * tid] = excl;
-        if (2 * tid + 1 < kUnits) cnt[2 * tid + 1] = excl + a;
-    }
-    __syncthreads();
-    // the survivors' records: a round of them requested together, every lane from an address (its own record or the pair's first),
-    // pinned before the stores
-    constexpr int kRound = KPT % 10 == 0 ? 10 : KPT % 8 == 0 ? 8 : 4;
-    static_assert(KPT % kRound == 0, "whole rounds");
-#pragma unroll
-    for (int k0 = 0; k0 < KPT; k0 += kRound) {
-        uint4 rec[kRound];
-#pragma unroll
-        for (int c = 0; c < kRound; ++c) {
-            const int k = k0 + c, i = ((ubase + k * ustep) << 3) | (lane & 7);
-            rec[c] = *reinterpret_cast<const uint4*>(&matches[(((bestbits >> k) & 1u) && i < m) ? i : 0]);
-        }
-#pragma unroll
-        for (int c = 0; c < kRound; ++c) asm volatile("" : "+v"(rec[c].x), "+v"(rec[c].y), "+v"(rec[c].z), "+v"(rec[c].w));
-#pragma unroll
-        for (int c = 0; c < kRound; ++c) {
-            const int k = k0 + c, u = ubase + k * ustep, i = (u << 3) | (lane & 7);
-            const bool in = ((bestbits >> k) & 1u) && i < m;
-            if (all_mask && i < m) all_mask[pr.match_off + i] = in ? 1 : 0;
-            if (in) {
-                const uint32_t pos = cnt[u] + ((ranks[k >> 3] >> ((k & 7) * 4)) & 15u);
-                __builtin_nontemporal_store(u32x4_t{rec[c].x, rec[c].y, rec[c].z, rec[c].w}, reinterpret_cast<u32x4_t*>(&out[pos]));
-            }
-        }
-    }
-    if (tid == 0) {
-        gms_pair_result r;
-        r.n_inliers = (int)best_count;
-        r.best_scale = best_scale;
-        r.best_rot = best_rot;
-        r.status = GMS_OK;
-        results[pair_idx] = r;
-    }
-}
-
-template <int KPT, bool ROT, int NT>
-__device__ __forceinline__ bool dense_scales_pair(const FilterParams& p, uint32_t* smem, const int pair_idx, const int tid,
-                                                  uint32_t* __restrict__ part)
-{
-    constexpr int kMcap = KPT * NT;
-    constexpr int kNRot = ROT ? 8 : 1;
-    constexpr int kChunk = (KPT % 5 == 0) ? 5 : 4;
-    static_assert(KPT % kChunk == 0, "KPT must be a multiple of the chunk");
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    // Lane mapping (see dense_pair): in list order a wave instruction holds 64 consecutive matches; DEALT (a run-time choice here: it
-    // only moves the loads and the record's bits) gives the wave's eight 8-lane groups eight consecutive matches each from places
-    // KPT * 128 matches apart -- a detector that emits keypoints row by row puts consecutive matches into the same cells, and 64 of
-    // them in one LDS atomic instruction serialise on a handful of entries.
-    const bool dealt = p.dealt != 0;
-    const int m_base = dealt ? ((((lane >> 3) * (KPT * (NT / 64)) + wave) << 3) | (lane & 7)) : tid;
-    const int m_stride = dealt ? (NT / 64) * 8 : NT;
-    auto match_of = [&](int k) -> int { return m_base + k * m_stride; };
-
-    int64_t total_kp;
-    const gms_pair pr = load_pair(p.pairs, pair_idx, p, total_kp);  // (and the frame table's header word)
-    const int m = pr.m;
-    if (!p.with_scale || m <= 0 || m > kMcap || pr.frame_a < 0 || pr.frame_a >= p.n_frames || pr.frame_b < 0 ||
-        pr.frame_b >= p.n_frames)
-        return false;
-    if (p.right_w[0] != 20 || p.right_h[0] != 20 || p.right_w[1] != 10 || p.right_h[1] != 10 || p.right_w[2] != 14 ||
-        p.right_h[2] != 14 || p.right_w[3] != 28 || p.right_h[3] != 28)
-        return false;
-    constexpr uint32_t kSEMask = 0x3FFu;   // E(r) = nr + 3 - r needs 10 bits at 28 x 28 right cells (bits 8..17 of the code word)
-    constexpr int kSAccShift = 18;         // rotation bits 18..25
-    constexpr int kSProbeBit = 26;         // PROBE: "sits in its row's arg-max entry under some grid type"
-    const int64_t offA = p.frame_off[pr.frame_a], offB = p.frame_off[pr.frame_b];
-    const int nA = (int)(p.frame_off[pr.frame_a + 1] - offA), nB = (int)(p.frame_off[pr.frame_b + 1] - offB);
-    if (nA <= 0 || nB <= 0) return false;
-    const gms_dmatch* __restrict__ matches = p.matches + pr.match_off;
-    // the frame table's code words (normalize_kernel): frame A's left codes (16 bits), frame B's scale codes (32 bits)
-    if (total_kp < 0 || offA + nA > total_kp || offB + nB > total_kp) return false;  // (workgroup-uniform) no header, or frames beyond the table
-    const uint16_t* __restrict__ lcodeA = reinterpret_cast<const uint16_t*>(p.pts + total_kp) + offA;
-    const uint32_t* __restrict__ scodeB = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint16_t*>(p.pts + total_kp) + 2 * total_kp) + offB;
-
-    const uint8_t* dense8 = reinterpret_cast<const uint8_t*>(smem);
-    uint32_t* nfine32 = smem + kDenseFineOff / 4;   // half-cell histogram: one dword per cell of grid type 1, a byte per half cell (as in dense_pair)
-    const uint8_t* nfine8 = reinterpret_cast<const uint8_t*>(nfine32);
-    uint8_t* nleft8 = reinterpret_cast<uint8_t*>(smem) + kDenseNleftOff;
-    uint32_t* misc = smem + kDenseMiscOff / 4;
-    uint32_t* trash = smem + kDenseTrashOff / 4;
-
-    GMS_STAMP_DECL
-    if (tid < 32) misc[tid] = 0;
-    if (tid < 16) trash[tid] = 0;
-    if (tid < kFineN / 4) nfine32[tid] = 0;
-
-    // ---- both frames' codes staged in the still unused matrix area, then the pair's (queryIdx, trainIdx) (see dense_pair)
-    const uint32_t phA = (uint32_t)(reinterpret_cast<uintptr_t>(lcodeA) >> 1) & 7u, phB = (uint32_t)(reinterpret_cast<uintptr_t>(scodeB) >> 2) & 3u;
-    const uint32_t qA = (phA + (uint32_t)nA + 7u) >> 3, qB = (phB + (uint32_t)nB + 3u) >> 2;  // uint4s of either copy
-    const bool staged = (qA + qB) * 16u <= kDenseBytes;  // workgroup-uniform
-    const uint4* __restrict__ srcA = reinterpret_cast<const uint4*>(lcodeA - phA);
-    const uint4* __restrict__ srcB = reinterpret_cast<const uint4*>(scodeB - phB);
-    constexpr int kStageRegs = 4;  // 64 KB of codes (10 900 keypoints a frame) through registers; larger frames finish in a plain loop
-    uint4 tb[kStageRegs];
-#pragma unroll
-    for (int i = 0; i < kStageRegs; ++i) {  // (unconditional: a pair too large to stage just reads a few code words it does not use)
-        const uint32_t j = min((uint32_t)(i * NT + tid), qA + qB - 1u);
-        const uint4* src = j < qA ? srcA + j : srcB + (j - qA);
-        tb[i] = *src;
-    }
-    uint2 qt[KPT];
-#pragma unroll
-    for (int k = 0; k < KPT; ++k) qt[k] = *reinterpret_cast<const uint2*>(&matches[min(match_of(k), m - 1)]);
-    const uint32_t staged16 = staged ? qA + qB : 0u;
-    {
-        const uint4 z4 = make_uint4(0, 0, 0, 0);
-        uint4* d4 = reinterpret_cast<uint4*>(smem);
-        // (staged: the first kStageRegs * NT slots are written below, codes or zeros)
-        for (uint32_t i = (staged ? max(staged16, (uint32_t)(kStageRegs * NT)) : 0u) + tid; i < kDenseBytes / 16; i += NT) d4[i] = z4;
-    }
-    if (staged) {
-        // UNCONDITIONAL stores, the data selected: a store under a condition lets the compiler sink its load into the branch, behind
-        // the clear, with a wait of its own -- one round trip per register instead of all of them in flight from the top
-        static_assert((size_t)kStageRegs * NT * 16 <= kDenseBytes, "the register-staged slots lie inside the matrix area");
-        uint4* d4 = reinterpret_cast<uint4*>(smem);
-#pragma unroll
-        for (int i = 0; i < kStageRegs; ++i) {
-            const bool in = (uint32_t)(i * NT + tid) < qA + qB;
-            d4[i * NT + tid] = make_uint4(in ? tb[i].x : 0u, in ? tb[i].y : 0u, in ? tb[i].z : 0u, in ? tb[i].w : 0u);
-        }
-        for (uint32_t j = kStageRegs * NT + tid; j < qA + qB; j += NT) d4[j] = *(j < qA ? srcA + j : srcB + (j - qA));
-    }
-    const uint16_t* ldsA = reinterpret_cast<const uint16_t*>(smem) + phA;  // left code of frame A's keypoint q at ldsA[q]
-    const uint32_t* ldsB = smem + 4u * qA + phB;                           // scale code of frame B's keypoint t at ldsB[t]
-    __syncthreads();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-
-    GMS_STAMP_OUT(4, 10);  // indices landed, codes staged
-    // code word as in dense_pair (E = E(r) of the current scale, 10 bits); aux = left cell under grid type 1 : 9 | right cell on the
-    // 20 x 20 grid : 9 | on the 28 x 28 grid : 10 | low bit of the 40 x 40 cell's x, y : 2 (the scale code as it stands, 9 bits up)
-    uint32_t code[KPT], aux[KPT];
-    {
-        uint32_t ca[KPT], cb[KPT];
-        if (staged) {
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) ca[k] = ldsA[min(qt[k].x, (uint32_t)(nA - 1))];
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) cb[k] = ldsB[min(qt[k].y, (uint32_t)(nB - 1))];
-        } else {
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) ca[k] = lcodeA[min(qt[k].x, (uint32_t)(nA - 1))];
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) cb[k] = scodeB[min(qt[k].y, (uint32_t)(nB - 1))];
-        }
-        bool any_bad = false, spill = false;
-#pragma unroll
-        for (int k = 0; k < KPT; ++k) {
-            const bool live = match_of(k) < m;
-            const uint32_t cell = ca[k] >> kLCellShift;  // under grid type 1; kLCellNever / kLCellBad above the grid
-            const bool ok = ((int)(qt[k].x < (uint32_t)nA) & (int)(qt[k].y < (uint32_t)nB) & (int)(cell != kLCellBad) & (int)((cb[k] & kSCodeBad) == 0u)) != 0;
-            const bool binned = live & ok & (cell < kLCellNever);
-            const uint32_t sh = ((ca[k] & 1u) << 3) | ((ca[k] & 4u) << 2);  // byte (hx & 1) + 2 (hy & 1) of the cell's dword
-            const uint32_t old = atomicAdd(binned ? &nfine32[cell] : &trash[lane & 7], 1u << sh);
-            spill |= binned & (((old >> sh) & 255u) == 255u);
-            any_bad |= live & !ok;
-            const uint32_t r0 = cb[k] & 0x1FFu;
-            code[k] = binned ? ((ca[k] & 31u) | ((ca[k] & 0x60u) << 1) | ((403u - r0) << kDEShift)) : kDNever;
-            aux[k] = binned ? (cell | ((cb[k] & 0x1FFFFFu) << 9)) : 0u;
-        }
-        if (any_bad) misc[8] = 1;
-        if (spill) misc[13] = 1;  // (not misc[11]: that one is written again while slower waves may still be reading this)
-    }
-    __syncthreads();
-    {
-        const uint4 z4 = make_uint4(0, 0, 0, 0);
-        uint4* d4 = reinterpret_cast<uint4*>(smem);
-        for (uint32_t i = tid; i < staged16; i += NT) d4[i] = z4;
-        // the sink dwords (see dense_pair_plain): the binning and marking loops below run unpredicated, a match that is not binned in
-        // the current pass works on its lane's sink instead. Bit 31 is never cleared (increments land in byte 0, keys end below it).
-        if (tid < 16) trash[tid] = 0x80000000u;
-        if (tid == 0) misc[15] = 0xFFFFFFFFu;  // "no header": what a match reads in the marking pass when the grid type leaves it out (E = 2047: equal to no E -- a never-binned match carries E = 0 --, and no rotation bits)
-        if (tid == 0) misc[14] = 0x7FFu;       // the same for probes, whose nibble form also tests the low 20 bits for the "dirty row" key
-    }
-    __syncthreads();
-    if (misc[8] != 0) {  // an input outside the parity domain (workgroup-uniform)
-        __syncthreads();
-        return false;
-    }
-    const bool spilled = misc[13] != 0;  // a half cell above 255 matches: crowded from the start (see dense_pair)
-    uint32_t* nl32 = nfine32;            // crowded mode: nLeft as 16-bit counters, two buffers of 400
-    const uint32_t sink_at = kDenseTrashOff + 4u * (uint32_t)(lane & 15), none_at = kDenseMiscOff + 4u * 15u, none_probe_at = kDenseMiscOff + 4u * 14u;
-
-    const bool thr_fast = threshold_fast_ok(p.threshold_factor);
-    const uint32_t f2i = dense_factor_sq(p.threshold_factor);
-    uint32_t best_count = 0, bestbits = 0;
-    int best_scale = -1, best_rot = -1;
-
-    // One scale hypothesis. BANDED (scale 3, 28 x 28 right cells: 400 rows of 788 bytes do not fit): the left grid's rows
-    // are taken 8 at a time, each band with one halo row on either side in LDS (at most 10 rows = 157 600 bytes); per
-    // grid type a band bins the matches of the rows it holds, verifies and marks its own rows' cells and takes every
-    // increment back before the next band. (Probes band differently: no halo, as many rows as fit; scale 4 only exists as a probe.)
-    // With rotation a lane verifies two of the eight rotations of its cell (four lanes per cell: sub = item & 3 picks rotations
-    // 2 sub, 2 sub + 1; the left side of the nine neighbour pairs is shared by the two). Where a rotation pattern sends the
-    // eight outer neighbours is a compile-time word (rotation_pack): the lane selects its two at the point of use.
-
-    // PROBE: an upper bound of the scale's inlier count instead of the count itself. A match can only be an inlier of a
-    // (scale, rotation) hypothesis if, under some grid type, its right cell IS the arg-max of its left cell's row -- whatever the
-    // rotation, whatever verifyCellPairs says about the cell. So: bin as always, flag the matches that sit in their row's arg-max
-    // entry, take the increments back, no verify; when the number of flagged matches does not exceed the best count so far, none of
-    // the scale's eight rotations can replace the best hypothesis (getInlierMask keeps on strict '>') and the scale is skipped.
-    // Costs about 45 % of the scale when it does not help, saves the other 55 % when it does.
-
-    // returns 0 = done, 1 = a cell above 255 matches (everything is run again CROWDED), 2 = a matrix entry at its limit,
-    // 3 = PROBE only: the scale cannot win
-    auto run_scale = [&](auto banded_c, auto crowded_c, auto probe_c, auto nib_c, const int s) -> int {
-        constexpr bool BANDED = decltype(banded_c)::value;
-        constexpr bool CROWDED = decltype(crowded_c)::value;
-        constexpr bool PROBE = decltype(probe_c)::value;
-        // NIB (probes of the two fine grids only): one NIBBLE per entry -- rows half as long, so scale 3's matrix fits whole (400 rows
-        // of 396 bytes: a probe in four passes instead of eight) and scale 4's in two bands of ten rows (eight passes instead of
-        // sixteen). A probe is an upper bound, so an entry that passes 15 need not stop anything: the add that sees 15 come back (its
-        // carry has spoilt the neighbour entry of the same row, never another row: rows are dword-aligned) marks the ROW dirty --
-        // the largest key the pass can hold -- and every match of a dirty row counts as a possible inlier: a superset of the exact
-        // probe's set, a few matches larger where a row overflowed.
-        constexpr bool NIB = decltype(nib_c)::value;
-        static_assert(!NIB || (PROBE && !CROWDED), "nibble entries: probes of uncrowded pairs only");
-        const uint32_t wr = (uint32_t)p.right_w[s], nr = wr * wr;
-        const uint32_t stride = 4u + (NIB ? nr >> 1 : nr);   // header dword + one byte (nibble) per right cell
-        const uint32_t e_top = NIB ? nr + 7u : nr + 3u;       // E(r) = e_top - r: the entry's byte (nibble) offset in its row
-        const uint32_t wr_magic = 65535u / wr + 1u;      // j / wr == (j * magic) >> 16 for j * wr < 65536
-        // scale 4 (probe only): E(r) up to 1603 takes 11 bits and reaches into the rotation bits, which a probe does not use
-        const uint32_t emask = (PROBE && s == 4) ? 0x7FFu : kSEMask;
-        {   // the code words' E(r) for this scale (scale 0 too: it is not the first one evaluated)
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) {
-                uint32_t r;
-                if (s == 0) {
-                    r = (aux[k] >> 9) & 0x1FFu;
-                } else if (s == 3) {
-                    r = (aux[k] >> 18) & 0x3FFu;
-                } else if (s == 4) {  // double the 20 x 20 cell's coordinates and add the stored low bits: fl(40 n) = 2 fl(20 n) + bit
-                    const uint32_t c20 = (aux[k] >> 9) & 0x1FFu, cy = (c20 * 3277u) >> 16, cx = c20 - cy * 20u;
-                    r = (2u * cy + ((aux[k] >> 29) & 1u)) * 40u + 2u * cx + ((aux[k] >> 28) & 1u);
-                } else {  // halve the finer grid's cell coordinates: 20 -> 10 (s == 1), 28 -> 14 (s == 2)
-                    const uint32_t fine = s == 1 ? (aux[k] >> 9) & 0x1FFu : (aux[k] >> 18) & 0x3FFu, wf = s == 1 ? 20u : 28u;
-                    const uint32_t fy = (fine * (s == 1 ? 3277u : 2341u)) >> 16, fx = fine - fy * wf;  // fine / wf for fine < 784
-                    r = (fy >> 1) * (wf >> 1) + (fx >> 1);
-                }
-                if (!(code[k] & kDNever)) code[k] = (code[k] & ~(emask << kDEShift)) | ((e_top - r) << kDEShift);
-            }
-        }
-        int status = 0;
-        for (int g = 0; g < 4; ++g) {
-            const int gx = g & 1, gy = g >> 1;
-            const uint32_t q_mask = (uint32_t)(gx + 20 * gy);
-            const uint32_t out_mask = kDNever | (gx ? kDEdgeX : 0u) | (gy ? kDEdgeY : 0u);
-            uint32_t* nl32cur = nl32 + (g & 1) * (kLeftN / 2);
-            const uint16_t* nl16cur = reinterpret_cast<const uint16_t*>(nl32cur);
-            if (!CROWDED && tid < kLeftN) {
-                const uint32_t n = dense_nleft_cm(nfine8, tid % kLeftW, tid / kLeftW, gx, gy);
-                if (n > 255u) misc[11] = 1;
-                nleft8[tid] = (uint8_t)n;
-            }
-            if (CROWDED && !PROBE) {  // nLeft of this grid type by counting (read by verify, behind the first barrier below)
-#pragma unroll
-                for (int k = 0; k < KPT; ++k) {
-                    const uint32_t cw = code[k];
-                    const uint32_t l = (aux[k] & 0x1FFu) + (cw & q_mask);
-                    if ((cw & out_mask) == 0) atomicAdd(&nl32cur[l >> 1], 1u << ((l & 1u) << 4));
-                }
-            }
-            // bands: 8 own rows + a halo row on either side (verify reads the neighbour rows); a probe needs no neighbours, so its
-            // bands are as many whole rows as fit: 10 at 28 x 28 right cells, 5 at 40 x 40
-            const int band_rows = PROBE ? (s == 4 && !NIB ? 5 : 10) : 8, halo = PROBE ? 0 : 1;
-            const int n_bands = BANDED ? (kLeftH + band_rows - 1) / band_rows : 1;
-            for (int band = 0; band < n_bands; ++band) {
-                const int lo = BANDED ? band * band_rows : 0, hi = BANDED ? min(lo + band_rows, kLeftH) : kLeftH;      // own rows
-                const int blo = BANDED ? max(lo - halo, 0) : 0, bhi = BANDED ? min(hi + halo, kLeftH) : kLeftH;        // rows held
-                const uint32_t cell0 = (uint32_t)(blo * kLeftW), n_held = (uint32_t)((bhi - blo) * kLeftW);
-                const uint32_t own0 = (uint32_t)(lo * kLeftW), n_own = (uint32_t)((hi - lo) * kLeftW);
-                // arg-max keys carry (grid type, band) in their top bits: every binning pass outranks what the previous one
-                // left in the headers (a cellPairs word, below 2^19), so headers are never reset inside a scale
-                const uint32_t key_tag = (uint32_t)(BANDED ? g * n_bands + band : g) << kDTagShift;
-
-                // ---- assignMatchPairs
-#pragma unroll
-                for (int k0 = 0; k0 < KPT; k0 += kChunk) {
-                    // Whole matrix in LDS (scales 0..2): unpredicated, a match the grid type leaves out works on its lane's sink (see
-                    // dense_pair_plain). Banded (scales 3, 4): most matches are outside the band -- those are skipped, not sunk.
-                    uint32_t old[kChunk], at[kChunk], row[kChunk], ee[kChunk];
-                    bool in[kChunk];
-#pragma unroll
-                    for (int c = 0; c < kChunk; ++c) {
-                        const uint32_t cw = code[k0 + c];
-                        const uint32_t l = (aux[k0 + c] & 0x1FFu) + (cw & q_mask) - cell0;
-                        in[c] = (cw & out_mask) == 0 && (!BANDED || l < n_held);
-                        // at[c]: the entry's bit offset in its dword (bytes: 8 (E & 3); nibbles: 4 (E & 7)); rows are dword-aligned
-                        if constexpr (BANDED) {
-                            row[c] = __umul24(l, stride);
-                            ee[c] = (cw >> kDEShift) & emask;
-                            at[c] = NIB ? (ee[c] & 7u) << 2 : (ee[c] & 3u) << 3;
-                            old[c] = 0;
-                            if (in[c]) old[c] = ldsa_add_rtn(row[c] + (NIB ? (ee[c] >> 3) << 2 : ee[c] & ~3u), 1u << at[c]);
-                        } else {
-                            row[c] = in[c] ? __umul24(l, stride) : sink_at;  // (not binned under this grid type: the lane's sink, E = 0)
-                            ee[c] = in[c] ? ((cw >> kDEShift) & emask) : 0u;
-                            at[c] = NIB ? (ee[c] & 7u) << 2 : (ee[c] & 3u) << 3;
-                            old[c] = ldsa_add_rtn(row[c] + (NIB ? (ee[c] >> 3) << 2 : ee[c] & ~3u), 1u << at[c]);
-                        }
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int c = 0; c < kChunk; ++c) {
-                        const uint32_t before = __builtin_amdgcn_ubfe(old[c], at[c], NIB ? 4 : 8);
-                        if (CROWDED && in[c] && before == 255u) misc[12] = 1;  // the entry's byte has just wrapped
-                        // (nibbles: the entry has just wrapped -> the row is dirty: the largest key of this pass, no later one replaces it)
-                        const uint32_t key = (NIB && before == 15u) ? 0xFFFFFu : (before << 11) | ee[c];
-                        if (!BANDED || in[c]) ldsa_max(row[c], key_tag | key);
-                    }
-                }
-                GMS_STAMP_IN(3);  // insert
-                __syncthreads();
-                GMS_STAMP_IN(11);  // insert: wait for the other waves
-                if (!CROWDED && misc[11] != 0) {  // a cell above 255 matches (workgroup-uniform; nothing has been written out)
-                    status = 1;
-                    break;
-                }
-                if (CROWDED && misc[12] != 0) {  // a (left cell, right cell) pair above 255 matches
-                    status = 2;
-                    break;
-                }
-
-                // ---- verifyCellPairs for the cells of the own rows. Without rotation: two lanes per left cell, four of the eight outer
-                //      neighbour pairs each. With rotation: four lanes per cell, two of the eight rotations each over all eight pairs
-                //      (the left side of a pair is shared by the lane's rotations; 1600 items instead of 3200).
-                if constexpr (!PROBE) {
-                    constexpr int kNR = ROT ? 2 : 1;             // rotations per lane
-                    constexpr int kLanesPerCell = ROT ? 4 : 2, kCellShift = ROT ? 2 : 1;
-                    const int n_items = (int)n_own * kLanesPerCell;
-                    for (int item = tid; item < ((n_items + 63) & ~63); item += NT) {
-                        const bool live = item < n_items;
-                        const int i = (int)own0 + (live ? (item >> kCellShift) : 0);
-                        const int sub = item & (kLanesPerCell - 1);
-                        const int half = item & 1;  // !ROT only
-                        const int ix = i % kLeftW, iy = i / kLeftW;
-                        const uint32_t ni = live ? (CROWDED ? (uint32_t)nl16cur[i] : (uint32_t)nleft8[i]) : 0u;
-                        if (__ballot(ni != 0) == 0ull) continue;  // none of this wave's cells has a match under this grid type
-                        const uint32_t hdr = ((uint32_t)i - cell0) * (stride >> 2);
-                        const uint32_t best = smem[hdr] & ((1u << kDTagShift) - 1u);
-                        const uint32_t ej = ni ? (best & 0x7FFu) : nr + 3u;
-                        const uint32_t j = nr + 3u - ej;
-                        const int jy = (int)((j * wr_magic) >> 16), jx = (int)j - jy * (int)wr;
-                        uint32_t score[kNR], tn[kNR];  // tn = (sum of nLeft << 4) | numpair
-                        uint32_t rpack[kNR];           // where the lane's rotations send the eight outer neighbours (rotation_pack)
-#pragma unroll
-                        for (int jr = 0; jr < kNR; ++jr) {
-                            score[jr] = tn[jr] = 0;
-                            rpack[jr] = sub == 0 ? rotation_pack(jr) : sub == 1 ? rotation_pack(2 + jr) : sub == 2 ? rotation_pack(4 + jr) : rotation_pack(6 + jr);
-                        }
-#pragma unroll
-                        for (int c = 0; c < (ROT ? 8 : 4); ++c) {
-                            int ldx, ldy;
-                            if (ROT) {
-                                const int k = c < 4 ? c : c + 1;
-                                ldx = (k % 3) - 1; ldy = (k / 3) - 1;
-                            } else {
-                                ldx = half ? ((c + 5) % 3) - 1 : (c % 3) - 1;
-                                ldy = half ? ((c + 5) / 3) - 1 : (c / 3) - 1;
-                            }
-                            const int lx = ix + ldx, ly = iy + ldy;
-                            const bool okl = ni != 0 && (uint32_t)lx < (uint32_t)kLeftW && (uint32_t)ly < (uint32_t)kLeftH;
-                            const uint32_t ll = okl ? (uint32_t)(lx + ly * kLeftW) : (uint32_t)i;  // within one row of an own row: held
-                            const uint32_t nll = CROWDED ? (uint32_t)nl16cur[ll] : (uint32_t)nleft8[ll];
-                            const uint32_t rowb = (ll - cell0) * stride;
-#pragma unroll
-                            for (int jr = 0; jr < kNR; ++jr) {
-                                int rdx = ldx, rdy = ldy;
-                                if (ROT) {
-                                    rdx = (int)((rpack[jr] >> (4 * c)) & 3u) - 1;
-                                    rdy = (int)((rpack[jr] >> (4 * c + 2)) & 3u) - 1;
-                                }
-                                const int rx = jx + rdx, ry = jy + rdy;
-                                const bool okp = okl && (uint32_t)rx < wr && (uint32_t)ry < wr;
-                                const uint32_t cnt = dense8[rowb + (okp ? nr + 3u - (uint32_t)(rx + ry * (int)wr) : 4u)];
-                                score[jr] += okp ? cnt : 0u;
-                                tn[jr] += okp ? ((nll << 4) | 1u) : 0u;
-                            }
-                        }
-                        uint32_t bits = 0;
-                        if (!ROT) {
-                            score[0] += dpp_xor1(score[0]);
-                            tn[0] += dpp_xor1(tn[0]);
-                        }
-#pragma unroll
-                        for (int jr = 0; jr < kNR; ++jr) {
-                            const uint32_t sc = score[jr] + (best >> 11) + 1u, t = tn[jr] + ((ni << 4) | 1u);
-                            uint32_t pass = 0;
-                            if (ni != 0 && (ROT || half == 0))
-                                pass = (CROWDED ? threshold_rejects(t >> 4, t & 15u, sc, p.threshold_factor, thr_fast)
-                                                : dense_threshold_rejects(t >> 4, t & 15u, sc, p.threshold_factor, thr_fast, f2i)) ? 0u : 1u;
-                            bits |= pass << jr;
-                        }
-                        if (ROT) {  // the cell's four lanes hold rotations (0,1) (2,3) (4,5) (6,7): gather the quad's bit pairs (DPP quad_perm broadcasts)
-                            const uint32_t b0 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bits, 0x00, 0xF, 0xF, false);
-                            const uint32_t b1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bits, 0x55, 0xF, 0xF, false);
-                            const uint32_t b2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bits, 0xAA, 0xF, 0xF, false);
-                            const uint32_t b3 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bits, 0xFF, 0xF, 0xF, false);
-                            bits = b0 | (b1 << 2) | (b2 << 4) | (b3 << 6);
-                        }
-                        if (ni != 0 && sub == 0) smem[hdr] = (ej << 8) | bits;
-                    }
-                    __syncthreads();
-                }
-                GMS_STAMP_IN(5);  // verify
-
-                // ---- mark the matches of the own rows; every increment of the rows held is taken back
-                {
-                    if (CROWDED && !PROBE && tid < kLeftN / 2) nl32[((g + 1) & 1) * (kLeftN / 2) + tid] = 0;  // the next grid type's counters (idle now; a barrier follows)
-                    uint32_t cr[KPT];
-#pragma unroll
-                    for (int k = 0; k < KPT; ++k) {
-                        const uint32_t cw = code[k];
-                        const uint32_t l = (aux[k] & 0x1FFu) + (cw & q_mask);
-                        const bool in = (cw & out_mask) == 0 && (!BANDED || l - cell0 < n_held);
-                        // the undo is a zero BYTE over the entry: with nibbles that clears the neighbour entry too -- every entry that was
-                        // touched is cleared by somebody, nobody reads entries in this phase, all writers store the same value
-                        const uint32_t ebyte = NIB ? ((cw >> kDEShift) & emask) >> 1 : (cw >> kDEShift) & emask;
-                        if constexpr (BANDED) {
-                            const uint32_t row = __umul24(l - cell0, stride);
-                            cr[k] = PROBE ? 0x7FFu : 0xFFFFFFFFu;  // "no header" (reads as E = 2047; a probe also tests the low 20 bits for "dirty")
-                            if (in) {
-                                if (l - own0 < n_own) cr[k] = ldsa_ld32(row);
-                                ldsa_st8(row + ebyte, 0u);  // (every reader of the entry is past the barrier: see dense_pair)
-                            }
-                        } else {
-                            const uint32_t row = in ? __umul24(l - cell0, stride) : sink_at;
-                            const uint32_t at = row + (in ? ebyte : 0u);
-                            cr[k] = ldsa_ld32(in ? row : (PROBE ? none_probe_at : none_at));
-                            ldsa_st8(at, 0u);
-                        }
-                    }
-#pragma unroll
-                    for (int k = 0; k < KPT; ++k) {
-                        if constexpr (PROBE) {  // the header still holds the arg-max key: [tag | count - 1 | E(j*)]; (a row not owned reads as E = 2047)
-                            if ((cr[k] & 0x7FFu) == ((code[k] >> kDEShift) & emask) || (NIB && (cr[k] & 0xFFFFFu) == 0xFFFFFu)) code[k] |= 1u << kSProbeBit;
-                        } else {
-                            const uint32_t x = cr[k] ^ (code[k] & (kSEMask << kDEShift));
-                            if (x < 256u) code[k] |= x << kSAccShift;
-                        }
-                    }
-                }
-                __syncthreads();
-                GMS_STAMP_IN(6);  // mark
-            }
-            if (status != 0) break;
-        }
-        if (status != 0) return status;
-        // the next scale lays its rows out differently: no header of this one may survive as a count byte
-        for (uint32_t c = tid; c < (uint32_t)kLeftN; c += NT)
-            if (!BANDED || c < (uint32_t)((PROBE ? (s == 4 && !NIB ? 5 : 10) : 10) * kLeftW)) smem[c * (stride >> 2)] = 0;
-
-        if constexpr (PROBE) {  // ---- how many matches could be inliers at this scale at all
-            uint32_t c0 = 0;
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) c0 += (uint32_t)__popcll(__ballot((code[k] >> kSProbeBit) & 1u));
-            if (lane == 0 && c0) atomicAdd(&misc[0], c0);
-            __syncthreads();  // count complete; headers zeroed
-            const uint32_t bound = misc[0];
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) code[k] &= ~(1u << kSProbeBit);
-            __syncthreads();
-            if (tid < 8) misc[tid] = 0;
-            // (a scale that comes BEFORE the best one in the reference's order would also win a tie)
-            const bool can_win = bound > best_count || (bound == best_count && s < best_scale);
-            if (tid == 0 && p.probe_stats != nullptr) atomicAdd(&p.probe_stats[(NIB ? 4 + 2 * s : 2 * s) + (can_win ? 0 : 1)], 1u);  // (nibble probes of scales 3, 4: words 10..13)
-            GMS_STAMP_IN(7);
-            return can_win ? 0 : 3;
-        }
-        // ---- run() return value per rotation of this scale, getInlierMask's strict '>'
-        if constexpr (ROT) {
-            // a thread's eight counts (at most KPT each) as byte fields of two registers: the four low rotation bits of a match times
-            // 0x204081 put bit i at position 8 i (v_mul_u32_u24 + v_and instead of eight ballots per match); widened to 16-bit fields
-            // for the wave's sum (row scans on the DPP path + four v_readlane), one LDS atomic per register and wave
-            uint32_t a0 = 0, a1 = 0;
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) {
-                const uint32_t b = code[k] >> kSAccShift;
-                a0 += __umul24(b & 15u, 0x204081u) & 0x01010101u;
-                a1 += __umul24((b >> 4) & 15u, 0x204081u) & 0x01010101u;
-            }
-            const uint32_t w0 = wave_sum(a0 & 0x00FF00FFu), w1 = wave_sum((a0 >> 8) & 0x00FF00FFu);    // rotations (0, 2), (1, 3)
-            const uint32_t w2 = wave_sum(a1 & 0x00FF00FFu), w3 = wave_sum((a1 >> 8) & 0x00FF00FFu);    // rotations (4, 6), (5, 7)
-            if (lane == 0) {
-                if (w0) atomicAdd(&misc[0], w0);
-                if (w1) atomicAdd(&misc[1], w1);
-                if (w2) atomicAdd(&misc[2], w2);
-                if (w3) atomicAdd(&misc[3], w3);
-            }
-        } else {
-            uint32_t c0 = 0;
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) c0 += (uint32_t)__popcll(__ballot((code[k] >> kSAccShift) & 1u));
-            if (lane == 0 && c0) atomicAdd(&misc[0], c0);
-        }
-        __syncthreads();  // counts complete; headers zeroed
-        // getInlierMask walks scale-outer, rotation-inner and keeps on strict '>': the first hypothesis with the largest count wins.
-        // Scale 1 is evaluated before scale 0 here (below), so a count that TIES the best replaces it when this scale comes
-        // before the best one's.
-        int winner = -1;
-#pragma unroll
-        for (int r = 0; r < kNRot; ++r) {
-            const uint32_t c = ROT ? (misc[(r >> 2) * 2 + (r & 1)] >> ((r & 2) << 3)) & 0xFFFFu : misc[0];
-            if (c > best_count || (c == best_count && c != 0 && s < best_scale)) {
-                best_count = c;
-                best_scale = s;
-                best_rot = r + 1;
-                winner = r;
-            }
-        }
-        if (winner >= 0) {  // the best hypothesis' inliers: one bit per match of the thread (a register -- scale 0's matrix fills the LDS)
-            bestbits = 0;
-#pragma unroll
-            for (int k = 0; k < KPT; ++k) bestbits |= ((code[k] >> (kSAccShift + winner)) & 1u) << k;
-        }
-#pragma unroll
-        for (int k = 0; k < KPT; ++k) code[k] &= ~(0xFFu << kSAccShift);
-        __syncthreads();
-        if (tid < 8) misc[tid] = 0;
-        GMS_STAMP_IN(7);  // count + select
-        return 0;
-    };
-
-    // one scale: the probe first where the launch asks for it and there is a best count to beat
-    auto eval_scale = [&](auto banded_c, auto crowded_c, const int s) -> int {
-        if (((p.probe_scales >> s) & 1) != 0 && best_count > 0) {
-            constexpr bool kCrowded = decltype(crowded_c)::value;
-            if constexpr (!kCrowded) {
-                if (s == 3 && (p.probe_nibble & 8) != 0) {  // the cheap bound first: nibble entries, the whole matrix at once
-                    const int pn = run_scale(std::false_type{}, crowded_c, std::true_type{}, std::true_type{}, s);
-                    GMS_STAMP_SCALE(5 + s);
-                    if (pn == 3) return 0;
-                    if (pn != 0) return pn;
-                }
-            }
-            const int pr = run_scale(banded_c, crowded_c, std::true_type{}, std::false_type{}, s);
-            GMS_STAMP_SCALE(5 + s);
-            if (pr != 0) return pr == 3 ? 0 : pr;
-        }
-        const int ev = run_scale(banded_c, crowded_c, std::false_type{}, std::false_type{}, s);
-        GMS_STAMP_SCALE(s);
-        return ev;
-    };
-    // Order: scale 1 first (the 10 x 10 grid collects at least as many matches per cell pair as the 20 x 20 one and usually has the
-    // largest count), then 0, 2, 3: whichever comes first sets the count the probes of the others are measured against, so with the
-    // usual winner first scale 0 can be bounded out as well.
-    int status = spilled ? 1 : 0;
-    bool crowded_mode = false;
-    for (int i = 0; i < 3 && status == 0; ++i) status = eval_scale(std::false_type{}, std::false_type{}, i == 0 ? 1 : (i == 1 ? 0 : 2));
-    if (status == 0) status = eval_scale(std::true_type{}, std::false_type{}, 3);
-    if (status == 1) {
-        crowded_mode = true;
-        // crowded (dense_pair has the same mode): everything again on a clean matrix, nLeft counted into 16-bit counters and
-        // every returned entry count checked; the cell populations do not depend on the scale, so this shows at the first scale
-        __syncthreads();
-        {
-            const uint4 z4 = make_uint4(0, 0, 0, 0);
-            uint4* d4 = reinterpret_cast<uint4*>(smem);
-            for (uint32_t i = tid; i < kDenseBytes / 16; i += NT) d4[i] = z4;
-            if (tid < kLeftN) nl32[tid] = 0;
-            if (tid < 8) misc[tid] = 0;
-        }
-#pragma unroll
-        for (int k = 0; k < KPT; ++k) code[k] &= ~(0xFFu << kSAccShift);
-        best_count = bestbits = 0;
-        best_scale = best_rot = -1;
-        __syncthreads();
-        status = 0;
-        for (int i = 0; i < 3 && status == 0; ++i) status = eval_scale(std::false_type{}, std::true_type{}, i == 0 ? 1 : (i == 1 ? 0 : 2));
-        if (status == 0) status = eval_scale(std::true_type{}, std::true_type{}, 3);
-    }
-    // Scale 4 (40 x 40: 400 rows of 1604 bytes) is the hashed kernel's to evaluate -- but its probe runs here, on four bands of the
-    // byte matrix: when it bounds the scale out, the record says all five scales are decided and the hashed kernel only copies out;
-    // when it does not, the record says so and the hashed kernel does not probe again.
-    uint32_t decided = 4u;
-    if (status == 0 && ((p.probe_scales >> 4) & 1) != 0 && best_count > 0 && p.right_w[4] == 40 && p.right_h[4] == 40) {
-        int pr = 0;
-        if (crowded_mode) {
-            pr = run_scale(std::true_type{}, std::true_type{}, std::true_type{}, std::false_type{}, 4);
-        } else {
-            // the cheap bound first (nibble entries: two bands instead of four); when it cannot bound the scale out, the exact one
-            if ((p.probe_nibble & 16) != 0) pr = run_scale(std::true_type{}, std::false_type{}, std::true_type{}, std::true_type{}, 4);
-            if ((p.probe_nibble & 16) == 0 || pr == 0) pr = run_scale(std::true_type{}, std::false_type{}, std::true_type{}, std::false_type{}, 4);
-        }
-        GMS_STAMP_SCALE(9);
-        if (pr == 3) decided = 5u;
-        else if (pr == 0) decided = 4u | 16u;
-        else status = pr;
-    }
-    if (status != 0) {
-        __syncthreads();
-        return false;
-    }
-    __syncthreads();
-    if (decided == 5u) {  // (workgroup-uniform) nothing is left for the hashed kernel but the copy-out: done here, its workgroup returns at once
-        if (tid == 0) part[0] = 6u;
-        scales_copy_out<KPT, NT>(p.pairs, p.matches, p.out, p.mask, p.results, smem, pair_idx, bestbits, dealt ? 1 : 0, best_count, best_scale, best_rot);
-        GMS_STAMP_OUT(9, 11);
-        GMS_STAMP_FLUSH;
-        return true;
-    }
-    // the record the hashed kernel continues from: scales 0..3 (or all five) are decided
-    if (tid == 0) {
-        part[0] = decided;
-        part[1] = best_count;
-        part[2] = (uint32_t)best_scale;
-        part[3] = (uint32_t)best_rot;
-    }
-    // the inlier bit of every match, as a bit mask over the list (bit i & 31 of dword i >> 5). List order: slot k of a wave is one chunk of
-    // 64 consecutive matches = one ballot. Dealt: an 8-lane group holds eight consecutive matches = one byte of the mask.
-    if (dealt) {
-        uint8_t* mask8 = reinterpret_cast<uint8_t*>(part + kPartialHeaderDw);
-        // (the lane's first match worked out again from a thread index the compiler cannot connect with the one above: kept alive
-        //  from the loads to here, it would cost a register through every scale)
-        int t2 = (int)threadIdx.x;
-        asm volatile("" : "+v"(t2));
-        const int l2 = t2 & 63, base2 = (((l2 >> 3) * (KPT * (NT / 64)) + (t2 >> 6)) << 3) | (l2 & 7);
-#pragma unroll
-        for (int k = 0; k < KPT; ++k) {
-            const unsigned long long bsel = __ballot((bestbits >> k) & 1u);
-            if ((l2 & 7) == 0) mask8[(base2 + k * (NT / 64) * 8) >> 3] = (uint8_t)(bsel >> l2);
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < KPT; ++k) {
-            const unsigned long long bsel = __ballot((bestbits >> k) & 1u);
-            if (lane == 0) {
-                const int ch = k * (NT / 64) + wave;
-                part[kPartialHeaderDw + 2 * ch] = (uint32_t)bsel;
-                part[kPartialHeaderDw + 2 * ch + 1] = (uint32_t)(bsel >> 32);
-            }
-        }
-    }
-    GMS_STAMP_OUT(9, 11);  // record written
-    GMS_STAMP_FLUSH;
-    return true;
-}
-
-template <int KPT, bool ROT, int NT>
-__global__ void __launch_bounds__(NT)
-filter_kernel_dense_scales(FilterParams p)
-{
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    first_round_stagger(p);
-    uint32_t* part = p.partial + (size_t)blockIdx.x * kPartialStrideDw;
-    if (!dense_scales_pair<KPT, ROT, NT>(p, smem, (int)blockIdx.x, (int)threadIdx.x, part)) {
-        if (threadIdx.x == 0) part[0] = 0u;  // the hashed kernel evaluates all five scales
-    }
-}
-
-// Test hook: the threshold comparison in device fp64 -- and, where the operands are in its range, the byte-matrix
-// path's integer form of it, which must agree (a disagreement is reported as 2).
-__global__ void threshold_kernel(const int32_t* T, const int32_t* n, const int32_t* score, double factor,
-                                 int count, uint8_t* out)
-{
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) {
-        const uint32_t t = (uint32_t)T[i], nn = (uint32_t)n[i], sc = (uint32_t)score[i];
-        const bool general = threshold_rejects(t, nn, sc, factor, threshold_fast_ok(factor));
-        uint8_t r = general ? 1 : 0;
-        if (t <= 9u * 255u && sc <= 9u * 255u && nn >= 1u && nn <= 9u &&
-            dense_threshold_rejects(t, nn, sc, factor, threshold_fast_ok(factor), dense_factor_sq(factor)) != general)
-            r = 2;
-        out[i] = r;
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2928,95 +322,24 @@ hipError_t launch_normalize(const void* d_kp, int kp_stride_bytes, const int64_t
     return hipGetLastError();
 }
 
-template <int KPT, bool ROT, int NT>
-static hipError_t launch_filter_t(const FilterParams& p, int n_pairs, size_t lds_bytes, hipStream_t stream)
-{
-    if (p.dense) {
-        const size_t lds = lds_bytes > kDenseLdsBytes ? lds_bytes : (size_t)kDenseLdsBytes;
-        if (p.dealt) hipLaunchKernelGGL((filter_kernel_dense<KPT, ROT, NT, true>), dim3((unsigned)n_pairs), dim3(NT), lds, stream, p);
-        else hipLaunchKernelGGL((filter_kernel_dense<KPT, ROT, NT, false>), dim3((unsigned)n_pairs), dim3(NT), lds, stream, p);
-    } else {
-        hipLaunchKernelGGL((filter_kernel<KPT, ROT, NT>), dim3((unsigned)n_pairs), dim3(NT), lds_bytes, stream, p);
-    }
-    return hipGetLastError();
-}
-
-template <int KPT, bool ROT, int NT>
-static hipError_t allow_full_lds_t()
-{
-    const void* fns[] = {reinterpret_cast<const void*>(filter_kernel<KPT, ROT, NT>),
-                         reinterpret_cast<const void*>(filter_kernel_dense<KPT, ROT, NT, false>),
-                         reinterpret_cast<const void*>(filter_kernel_dense<KPT, ROT, NT, true>),
-                         reinterpret_cast<const void*>(filter_kernel_dense_scales<KPT, ROT, NT>)};
-    for (const void* fn : fns) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-// Once per context (device), before the first launch: every kernel here may ask for the CU's whole LDS. Done up front so
+// Once per context (device), before the first launch: every per-pair kernel may ask for the CU's whole LDS. Done up front so
 // that a launch is nothing but a launch (stream capture of gms_filter_device sees no attribute call).
 hipError_t init_filter_kernels()
 {
-    hipError_t e = allow_full_lds_t<4, false, 1024>();
-    if (e == hipSuccess) e = allow_full_lds_t<4, true, 1024>();
-    if (e == hipSuccess) e = allow_full_lds_t<10, false, 1024>();
-    if (e == hipSuccess) e = allow_full_lds_t<10, true, 1024>();
-    if (e == hipSuccess) e = allow_full_lds_t<16, false, 1024>();
-    if (e == hipSuccess) e = allow_full_lds_t<16, true, 1024>();
+    hipError_t e = init_hash_kernels();
+    if (e == hipSuccess) e = init_dense_kernels();
+    if (e == hipSuccess) e = init_scales_kernels();
     return e;
 }
 
-// kpt = matches per thread of the 1024-thread workgroup. (A 512-thread build with twice the matches per thread and
-// twice the matches in flight was measured 27 % slower at 10k matches: the kernel wants waves, not registers.)
+// kpt = matches per thread of the 1024-thread workgroup (filter_pick_kpt).
 // p.dense selects the kernel that tries the byte-matrix path first (only meaningful without scale hypotheses).
 hipError_t launch_filter(const FilterParams& p, int kpt, int n_pairs, hipStream_t stream)
 {
     if (n_pairs <= 0) return hipSuccess;
     const size_t lds = filter_lds_bytes(kpt, p.table_slots);
-    const bool rot = p.with_rotation != 0;
-    switch (kpt) {
-    case 4: return rot ? launch_filter_t<4, true, 1024>(p, n_pairs, lds, stream) : launch_filter_t<4, false, 1024>(p, n_pairs, lds, stream);
-    case 10: return rot ? launch_filter_t<10, true, 1024>(p, n_pairs, lds, stream) : launch_filter_t<10, false, 1024>(p, n_pairs, lds, stream);
-    case 16: return rot ? launch_filter_t<16, true, 1024>(p, n_pairs, lds, stream) : launch_filter_t<16, false, 1024>(p, n_pairs, lds, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-template <int KPT, bool ROT, int NT>
-static hipError_t launch_dense_scales_t(const FilterParams& p, int n_pairs, hipStream_t stream)
-{
-    hipLaunchKernelGGL((filter_kernel_dense_scales<KPT, ROT, NT>), dim3((unsigned)n_pairs), dim3(NT), kDenseLdsBytes, stream, p);
-    return hipGetLastError();
-}
-
-// Scale hypotheses: scales 0..2 on the byte matrix (records in p.partial), then the hashed kernel for scales 3 and 4 and
-// for everything the first kernel could not take. p.partial: n_pairs * kPartialStrideDw dwords.
-hipError_t launch_filter_scales(const FilterParams& p, int kpt, int n_pairs, hipStream_t stream)
-{
-    if (n_pairs <= 0) return hipSuccess;
-    const bool rot = p.with_rotation != 0;
-    hipError_t e = hipErrorInvalidValue;
-    switch (kpt) {
-    case 4: e = rot ? launch_dense_scales_t<4, true, 1024>(p, n_pairs, stream) : launch_dense_scales_t<4, false, 1024>(p, n_pairs, stream); break;
-    case 10: e = rot ? launch_dense_scales_t<10, true, 1024>(p, n_pairs, stream) : launch_dense_scales_t<10, false, 1024>(p, n_pairs, stream); break;
-    case 16: e = rot ? launch_dense_scales_t<16, true, 1024>(p, n_pairs, stream) : launch_dense_scales_t<16, false, 1024>(p, n_pairs, stream); break;
-    default: break;
-    }
-    if (e != hipSuccess) return e;
-    FilterParams q = p;
-    q.dense = 0;
-    return launch_filter(q, kpt, n_pairs, stream);
-}
-
-hipError_t launch_threshold(const int32_t* d_T, const int32_t* d_n, const int32_t* d_score, double factor,
-                            int count, uint8_t* d_out, hipStream_t stream)
-{
-    if (count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(threshold_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, d_T, d_n, d_score,
-                       factor, count, d_out);
-    return hipGetLastError();
+    return p.dense ? launch_filter_dense(p, kpt, n_pairs, lds, stream) : launch_filter_hash(p, kpt, n_pairs, lds, stream);
 }
 
 }  // namespace gms
+

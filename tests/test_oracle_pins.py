@@ -41,7 +41,7 @@ def test_rotation_patterns_are_rotations_of_the_ring(oracle):
 
 
 def test_rotation_patterns_arithmetic_form(oracle):
-    """The closed form the HIP kernel uses instead of the table (gms_kernels.hip: rotated_position)."""
+    """The closed form the HIP kernel uses instead of the table (gms_device_common.h: rotated_position)."""
     import ctypes as C
     pat = np.array((C.c_int * 72).in_dll(oracle.load(), "gms_ref_rotation_patterns")).reshape(8, 9)
     ring_index = [0, 1, 2, 7, -1, 3, 6, 5, 4]
