@@ -12,8 +12,8 @@ import ctypes as C
 import numpy as np
 
 from .capi import load_library
-from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128, LOGOS_DICT_RESULT_DTYPE, KEYPOINT_DTYPE, PAIR_DTYPE, RESULT_DTYPE, GMS_OK, GMS_ERR_CAPACITY,
-                    GmsError, portrait_params, stereo_bm_params)
+from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, LOGOS_DICT_RESULT_DTYPE, KEYPOINT_DTYPE, PAIR_DTYPE, RESULT_DTYPE, GMS_OK, GMS_ERR_CAPACITY,
+                    GmsError, concat_frames, desc_layout, portrait_params, stereo_bm_params)
 
 
 def _as(arr, dtype, name):
@@ -116,11 +116,9 @@ class GmsContext:
                     or frame_off[-1] > n_kp):
                 raise ValueError("frame_off: one offset per frame and one more, from 0, never decreasing, the last at most len(keypoints)")
         else:
-            counts = np.array([len(k) for k in keypoints_per_frame], dtype=np.int64)
-            frame_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-            kp = (np.concatenate([_as(k, KEYPOINT_DTYPE, "keypoints") for k in keypoints_per_frame])
-                  if frame_off[-1] else np.zeros(1, dtype=KEYPOINT_DTYPE))
-            n_frames = len(counts)
+            kp, frame_off = concat_frames([_as(k, KEYPOINT_DTYPE, "keypoints") for k in keypoints_per_frame])
+            kp = kp if len(kp) else np.zeros(1, dtype=KEYPOINT_DTYPE)
+            n_frames = len(frame_off) - 1
         wh = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32).reshape(-1, 2))
         if wh.shape[0] != n_frames:
             raise ValueError("one (width, height) per frame")
@@ -417,14 +415,12 @@ def matchLOGOS(keypoints1, keypoints2, nn1, nn2):
 
 def logos_dict_args(kind, n_words, attempts, max_iters):
     """The argument checks of the dictionary trainer, as include/gms.h states them -> (dtype, row width)."""
-    kind = int(kind)
-    if kind not in (GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128):
-        raise ValueError("kind: GMS_DESC_HAMMING256 or GMS_DESC_L2_F32X128")
+    layout = desc_layout(kind)
     if not 1 <= int(n_words) <= 65535:
         raise ValueError("1 <= n_words <= 65535")
     if not 1 <= int(attempts) <= 16 or not 1 <= int(max_iters) <= 1000:
         raise ValueError("1 <= attempts <= 16 and 1 <= max_iters <= 1000")
-    return (np.uint8, 32) if kind == GMS_DESC_HAMMING256 else (np.float32, 128)
+    return layout
 
 
 def trainLogosDictionary(descriptors, kind, n_words=50, attempts=3, max_iters=100, seed=0, detail=False):
@@ -460,7 +456,7 @@ def bruteForceMatch(desc1, desc2, kind, cross_check=True, distance_coef=4.0, max
     (GMS_ERR_DOMAIN): the reference reads front() of an empty vector there."""
     lib = load_library()
     kind = int(kind)
-    dt, width = (np.uint8, 32) if kind == GMS_DESC_HAMMING256 else (np.float32, 128)
+    dt, width = desc_layout(kind)
     d1 = np.ascontiguousarray(desc1, dtype=dt).reshape(-1, width)
     d2 = np.ascontiguousarray(desc2, dtype=dt).reshape(-1, width)
     cap = min(int(max_size), len(d1)) if max_size >= 0 else 0

@@ -9,13 +9,59 @@ import numpy as np
 import torch
 
 from .api import GmsContext, logos_dict_args
-from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_ERR_CAPACITY, KEYPOINT_DTYPE, LOGOS_DICT_RESULT_DTYPE, LOGOS_RESULT_DTYPE, portrait_params, stereo_bm_params,
-                    PAIR_DTYPE, RESULT_DTYPE)
+from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_ERR_CAPACITY, KEYPOINT_DTYPE, LOGOS_DICT_RESULT_DTYPE, LOGOS_RESULT_DTYPE, PAIR_DTYPE,
+                    RESULT_DTYPE, concat_frames, desc_layout, portrait_params, stereo_bm_params)
 
 
 def _to_dev(arr, device):
     a = np.ascontiguousarray(arr)
     return torch.from_numpy(a.view(np.uint8).reshape(-1)).to(device)
+
+
+def _device(ctx, device):
+    return torch.device(device if device is not None else f"cuda:{ctx.device}")
+
+
+def frame_counts(counts, idx):
+    """counts[idx] for every frame index of idx; 0 for an index out of range, also when there are no frames."""
+    counts, idx = np.asarray(counts, dtype=np.int64), np.asarray(idx, dtype=np.int64)
+    return np.append(counts, 0)[np.where((idx >= 0) & (idx < len(counts)), idx, len(counts))]
+
+
+def pair_table(frame_pairs, capacity):
+    """PAIR_DTYPE records for (frame_a, frame_b) pairs: m = capacity (an int or one per pair), match_off = the running sum of the
+    max(m, 0) before each pair, so that the pairs' ranges lie back to back."""
+    fp = np.asarray(frame_pairs, dtype=np.int64).reshape(-1, 2)
+    recs = np.zeros(len(fp), PAIR_DTYPE)
+    cap = np.broadcast_to(np.asarray(capacity, dtype=np.int64), (len(fp),))
+    room = np.maximum(cap, 0)
+    recs["frame_a"], recs["frame_b"], recs["m"], recs["match_off"] = fp[:, 0], fp[:, 1], cap, np.cumsum(room) - room
+    return recs
+
+
+def frame_pairs_of(recs):
+    """The (frame_a, frame_b) columns of PAIR_DTYPE records, as pair_table takes them."""
+    return np.stack([recs["frame_a"], recs["frame_b"]], axis=1)
+
+
+def _survivors(out, recs, res):
+    return [out[o:o + (k if st == 0 else 0)].copy()
+            for o, k, st in zip(recs["match_off"].tolist(), res["n_out"].tolist(), res["status"].tolist())]
+
+
+def run_with_retry(recs, run):
+    """run(PAIR_DTYPE records) -> (output laid out by match_off, result records with n_out and status). Pairs that come back with
+    GMS_ERR_CAPACITY are run once more, together, with the count they reported as their room: (list of per-pair survivor arrays,
+    result records with those of the second run merged in). A pair whose status is not 0 in the end has no survivors."""
+    out, res = run(recs)
+    got = _survivors(out, recs, res)
+    over = np.nonzero(res["status"] == GMS_ERR_CAPACITY)[0]
+    if len(over):
+        again = pair_table(frame_pairs_of(recs[over]), res["n_out"][over])
+        out2, res[over] = run(again)
+        for p, kept in zip(over, _survivors(out2, again, res[over])):
+            got[p] = kept
+    return got, res
 
 
 class FrameTable:
@@ -25,11 +71,8 @@ class FrameTable:
         self.ctx = ctx
         self.device = torch.device(device)
         self.n_frames = len(keypoints_per_frame)
-        counts = np.array([len(k) for k in keypoints_per_frame], dtype=np.int64)
-        self.frame_off_host = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        kp_all, self.frame_off_host = concat_frames(keypoints_per_frame)
         self.total = int(self.frame_off_host[-1])
-        kp_all = (np.concatenate([np.ascontiguousarray(k, dtype=KEYPOINT_DTYPE) for k in keypoints_per_frame])
-                  if self.total else np.zeros(0, dtype=KEYPOINT_DTYPE))
         wh = np.asarray(sizes, dtype=np.int32).reshape(-1, 2)
         assert wh.shape[0] == self.n_frames
         self.d_kp = _to_dev(kp_all, self.device)
@@ -50,7 +93,7 @@ class DescriptorTable:
 
     def __init__(self, ctx, frames, descriptors_per_frame, kind):
         self.ctx, self.kind, self.frames = ctx, int(kind), frames
-        dt, width = (np.uint8, 32) if self.kind == 0 else (np.float32, 128)
+        dt, width = desc_layout(self.kind)
         rows = [np.ascontiguousarray(d, dtype=dt).reshape(-1, width) for d in descriptors_per_frame]
         assert [len(r) for r in rows] == list(np.diff(frames.frame_off_host)), "one descriptor per keypoint"
         self.host = np.concatenate(rows) if frames.total else np.zeros((0, width), dtype=dt)
@@ -81,9 +124,8 @@ class BfSelect:
         self.cross_check, self.distance_coef, self.max_size, self.use_prepared = bool(cross_check), float(distance_coef), int(max_size), use_prepared
         sizes = np.diff(f.frame_off_host)
         a, b = self.recs["frame_a"], self.recs["frame_b"]
-        ok = (a >= 0) & (a < f.n_frames) & (b >= 0) & (b < f.n_frames)
-        na, nb = np.where(ok, sizes[np.clip(a, 0, max(f.n_frames - 1, 0))] if f.n_frames else 0, 0), \
-            np.where(ok, sizes[np.clip(b, 0, max(f.n_frames - 1, 0))] if f.n_frames else 0, 0)
+        ok = (a >= 0) & (a < f.n_frames) & (b >= 0) & (b < f.n_frames)   # a pair with one bad index sizes nothing
+        na, nb = np.where(ok, frame_counts(sizes, a), 0), np.where(ok, frame_counts(sizes, b), 0)
         self.max_rows = int(max(na.max(initial=0), nb.max(initial=0)))
         self.total_back = int((nb if self.cross_check else na).sum())
         n = len(self.recs)
@@ -116,57 +158,44 @@ def bf_select_table(descs, frame_pairs, capacity=None, max_size=500):
     """PAIR_DTYPE records for (frame_a, frame_b) pairs; m: output room per pair (int or one per pair; default min(max_size, n_a),
     which K never exceeds), match_off: the running sum."""
     fp = np.asarray(frame_pairs, dtype=np.int64).reshape(-1, 2)
-    sizes = np.diff(descs.frames.frame_off_host)
-    recs = np.zeros(len(fp), PAIR_DTYPE)
-    recs["frame_a"], recs["frame_b"] = fp[:, 0], fp[:, 1]
     if capacity is None:
-        ok = (fp[:, 0] >= 0) & (fp[:, 0] < len(sizes))
-        na = np.where(ok, sizes[np.clip(fp[:, 0], 0, max(len(sizes) - 1, 0))] if len(sizes) else 0, 0)
-        cap = np.minimum(na, max(int(max_size), 0))
-    else:
-        cap = np.broadcast_to(np.asarray(capacity, dtype=np.int64), (len(fp),))
-    recs["m"] = cap
-    recs["match_off"] = np.concatenate([[0], np.cumsum(np.maximum(cap, 0))[:-1]]) if len(fp) else []
-    return recs
+        capacity = np.minimum(frame_counts(np.diff(descs.frames.frame_off_host), fp[:, 0]), max(int(max_size), 0))
+    return pair_table(fp, capacity)
 
 
 def bf_select_pairs(ctx, descs, frame_pairs, cross_check=True, distance_coef=4.0, max_size=500, capacity=None, use_prepared=True):
     """The reference's bruteForceMatch (FeatureMatchUtil.cpp:20-31) for every (frame_a, frame_b) pair of a DescriptorTable: (list of
     DMATCH_DTYPE survivor arrays, BF_RESULT_DTYPE records). Pairs that come back with GMS_ERR_CAPACITY are run once more with the
     count they reported."""
-    recs = bf_select_table(descs, frame_pairs, capacity, max_size)
-    run = BfSelect(ctx, descs, recs, cross_check, distance_coef, max_size, use_prepared)
-    run.run()
-    ctx.synchronize()
-    out, res, _ = run.results()
-    over = np.nonzero(res["status"] == GMS_ERR_CAPACITY)[0]
-    where = {p: (out, int(recs["match_off"][p])) for p in range(len(recs))}
-    if len(over):
-        again = recs[over].copy()
-        again["m"] = res["n_out"][over]
-        again["match_off"] = np.concatenate([[0], np.cumsum(again["m"])[:-1]])
-        run2 = BfSelect(ctx, descs, again, cross_check, distance_coef, max_size, use_prepared)
-        run2.run()
+    def run(recs):
+        job = BfSelect(ctx, descs, recs, cross_check, distance_coef, max_size, use_prepared)
+        job.run()
         ctx.synchronize()
-        out2, res2, _ = run2.results()
-        res[over] = res2
-        where.update({int(p): (out2, int(again["match_off"][q])) for q, p in enumerate(over)})
-    got = []
-    for p in range(len(recs)):
-        arr, o = where[p]
-        k = int(res["n_out"][p]) if res["status"][p] == 0 else 0
-        got.append(arr[o:o + k].copy())
-    return got, res
+        return job.results()[:2]
+
+    return run_with_retry(bf_select_table(descs, frame_pairs, capacity, max_size), run)
+
+
+def _image_stack(ctx, images, device):
+    dev = _device(ctx, device)
+    imgs = images if torch.is_tensor(images) else torch.from_numpy(np.ascontiguousarray(images, dtype=np.uint8))
+    if imgs.dim() == 2:
+        imgs = imgs[None]
+    return dev, imgs.to(dev).contiguous()
+
+
+def _detected(d_kp, d_desc, d_counts, n, max_keypoints):
+    """(keypoints_per_image, rows_per_image) on the host from a detector's [n, max_keypoints] record and row buffers and its counts."""
+    counts = d_counts.cpu().numpy()
+    kp = d_kp.cpu().numpy()[: n * max_keypoints * 28].view(KEYPOINT_DTYPE).reshape(n, max_keypoints)
+    desc = d_desc.cpu().numpy()[: n * max_keypoints * 32].reshape(n, max_keypoints, 32)
+    return [kp[i, : counts[i]].copy() for i in range(n)], [desc[i, : counts[i]].copy() for i in range(n)]
 
 
 def detect_images(ctx, images, threshold=20, max_keypoints=10000, device=None):
     """gms_detect_batch_device on a stack of equally sized 8-bit grey images [n, H, W] (host array or device tensor): returns
     (keypoints_per_image, rows_per_image) as host arrays -- KEYPOINT_DTYPE records in raster order and uint8 [n_i, 32] rows."""
-    dev = torch.device(device if device is not None else f"cuda:{ctx.device}")
-    imgs = images if torch.is_tensor(images) else torch.from_numpy(np.ascontiguousarray(images, dtype=np.uint8))
-    if imgs.dim() == 2:
-        imgs = imgs[None]
-    imgs = imgs.to(dev).contiguous()
+    dev, imgs = _image_stack(ctx, images, device)
     n, h, w = imgs.shape
     nb = ctx.detect_workspace_bytes(w, h, n, max_keypoints)
     if nb == 0:
@@ -179,18 +208,7 @@ def detect_images(ctx, images, threshold=20, max_keypoints=10000, device=None):
     ctx.detect_batch_device(imgs.data_ptr(), n, w, h, threshold, max_keypoints, d_ws.data_ptr(), nb, d_kp.data_ptr(), d_desc.data_ptr(),
                             d_counts.data_ptr())
     ctx.synchronize()
-    counts = d_counts.cpu().numpy()
-    kp = d_kp.cpu().numpy()[: n * max_keypoints * 28].view(KEYPOINT_DTYPE).reshape(n, max_keypoints)
-    desc = d_desc.cpu().numpy()[: n * max_keypoints * 32].reshape(n, max_keypoints, 32)
-    return [kp[i, : counts[i]].copy() for i in range(n)], [desc[i, : counts[i]].copy() for i in range(n)]
-
-
-def _image_stack(ctx, images, device):
-    dev = torch.device(device if device is not None else f"cuda:{ctx.device}")
-    imgs = images if torch.is_tensor(images) else torch.from_numpy(np.ascontiguousarray(images, dtype=np.uint8))
-    if imgs.dim() == 2:
-        imgs = imgs[None]
-    return dev, imgs.to(dev).contiguous()
+    return _detected(d_kp, d_desc, d_counts, n, max_keypoints)
 
 
 class DetectPyramid:
@@ -200,7 +218,7 @@ class DetectPyramid:
     def __init__(self, ctx, n, w, h, threshold=20, max_keypoints=10000, n_levels=8, device=None):
         self.ctx, self.n, self.w, self.h = ctx, int(n), int(w), int(h)
         self.threshold, self.max_keypoints, self.n_levels = int(threshold), int(max_keypoints), int(n_levels)
-        dev = torch.device(device if device is not None else f"cuda:{ctx.device}")
+        dev = _device(ctx, device)
         self.ws_bytes = ctx.detect_pyramid_workspace_bytes(w, h, n, max_keypoints, n_levels)
         if self.ws_bytes == 0:
             raise ValueError("bad image size, keypoint count or number of levels")
@@ -219,12 +237,8 @@ class DetectPyramid:
 
     def results(self):
         """(keypoints_per_image, rows_per_image, level_counts [n, n_levels]) on the host."""
-        n, m = self.n, self.max_keypoints
-        counts = self.d_counts.cpu().numpy()
-        kp = self.d_kp.cpu().numpy()[: n * m * 28].view(KEYPOINT_DTYPE).reshape(n, m)
-        desc = self.d_desc.cpu().numpy()[: n * m * 32].reshape(n, m, 32)
-        return ([kp[i, : counts[i]].copy() for i in range(n)], [desc[i, : counts[i]].copy() for i in range(n)],
-                self.d_level_counts.cpu().numpy().reshape(n, self.n_levels).copy())
+        return (*_detected(self.d_kp, self.d_desc, self.d_counts, self.n, self.max_keypoints),
+                self.d_level_counts.cpu().numpy().reshape(self.n, self.n_levels).copy())
 
 
 def detect_images_pyramid(ctx, images, threshold=20, max_keypoints=10000, n_levels=8, device=None):
@@ -259,7 +273,7 @@ def build_pyramid(ctx, images, n_levels=8, device=None):
 
 def describe_image(ctx, image, keypoints, device=None):
     """gms_describe_device: directions and 32-byte rows at the given integer keypoints of one image -> (status, keypoints, rows)."""
-    dev = torch.device(device if device is not None else f"cuda:{ctx.device}")
+    dev = _device(ctx, device)
     img = torch.from_numpy(np.ascontiguousarray(image, dtype=np.uint8)).to(dev)
     h, w = img.shape
     kp = np.ascontiguousarray(keypoints, dtype=KEYPOINT_DTYPE)
@@ -335,11 +349,8 @@ class LogosTable:
         else:
             self.device = torch.device(device)
             self.n_frames = len(keypoints_per_frame)
-            counts = np.array([len(k) for k in keypoints_per_frame], dtype=np.int64)
-            self.frame_off_host = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            kp_all, self.frame_off_host = concat_frames(keypoints_per_frame)
             self.total = int(self.frame_off_host[-1])
-            kp_all = (np.concatenate([np.ascontiguousarray(k, dtype=KEYPOINT_DTYPE) for k in keypoints_per_frame])
-                      if self.total else np.zeros(0, dtype=KEYPOINT_DTYPE))
             self.d_kp = _to_dev(kp_all, self.device) if self.total else torch.zeros(28, dtype=torch.uint8, device=self.device)
             self.d_frame_off = torch.from_numpy(self.frame_off_host).to(self.device)
         self.counts = np.diff(self.frame_off_host)
@@ -373,74 +384,78 @@ def logos_pair_table(table, frame_pairs, capacity=None):
     """PAIR_DTYPE records for (frame_a, frame_b) pairs: m = the output capacity (default max(n_a, n_b) per pair -- survivors rarely
     outnumber the larger frame), match_off back to back."""
     fp = np.asarray(frame_pairs, dtype=np.int64).reshape(-1, 2)
-    pairs = np.zeros(len(fp), dtype=PAIR_DTYPE)
-    pairs["frame_a"], pairs["frame_b"] = fp[:, 0], fp[:, 1]
     if capacity is None:
-        cap = np.zeros(len(fp), np.int64)
-        for k in (0, 1):
-            ok = (fp[:, k] >= 0) & (fp[:, k] < table.n_frames)
-            cap[ok] = np.maximum(cap[ok], table.counts[fp[ok, k]])
-    else:
-        cap = np.broadcast_to(np.asarray(capacity, dtype=np.int64), (len(fp),))
-    pairs["m"] = cap
-    pairs["match_off"] = np.concatenate([[0], np.cumsum(cap)[:-1]]) if len(fp) else 0
-    return pairs
+        capacity = np.maximum(frame_counts(table.counts, fp[:, 0]), frame_counts(table.counts, fp[:, 1]))
+    return pair_table(fp, capacity)
+
+
+class LogosFilter:
+    """Device buffers of one gms_logos_filter_device batch over a LogosTable: the pair table, workspace, output and both kinds of result
+    records, sized once, so that run() can be replayed on the same pairs. A frame index out of range is the library's to report
+    (GMS_ERR_BAD_ARG for that pair alone): it counts as an empty frame here."""
+
+    def __init__(self, ctx, table, pairs):
+        self.ctx, self.table, self.pairs = ctx, table, np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
+        n, dev = len(self.pairs), table.device
+        self.out_len = int((self.pairs["match_off"] + np.maximum(self.pairs["m"], 0)).max()) if n else 0
+        max_q = int(frame_counts(table.counts, self.pairs["frame_a"]).max()) if n else 0
+        self.ws_bytes = ctx.logos_workspace_bytes(0, n, max_q)
+        self.d_pairs = _to_dev(self.pairs, dev) if n else torch.zeros(24, dtype=torch.uint8, device=dev)
+        self.d_ws = torch.empty(max(self.ws_bytes, 16), dtype=torch.uint8, device=dev)
+        self.d_out = torch.zeros(max(self.out_len, 1) * 16, dtype=torch.uint8, device=dev)
+        self.d_lres = torch.zeros(max(n, 1) * LOGOS_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.d_pres = torch.zeros(max(n, 1) * RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+
+    def run(self):
+        self.table.filter_device(self.d_pairs.data_ptr(), len(self.pairs), self.d_ws.data_ptr(), self.ws_bytes, self.d_out.data_ptr(),
+                                 self.d_lres.data_ptr(), self.d_pres.data_ptr())
+
+    def logos_results(self):
+        return self.d_lres.cpu().numpy().view(LOGOS_RESULT_DTYPE)[: len(self.pairs)].copy()
+
+    def results(self):
+        """(output DMATCH_DTYPE array laid out by match_off, LOGOS_RESULT_DTYPE records, RESULT_DTYPE records) on the host."""
+        return (self.d_out.cpu().numpy().view(DMATCH_DTYPE)[: self.out_len], self.logos_results(),
+                self.d_pres.cpu().numpy().view(RESULT_DTYPE)[: len(self.pairs)].copy())
 
 
 def logos_filter(ctx, table, pairs):
     """One gms_logos_filter_device run over PAIR_DTYPE `pairs` -> (out, logos_results, pair_results) as host arrays (out laid out by
     match_off; pairs with GMS_ERR_CAPACITY wrote nothing)."""
-    dev = table.device
-    pairs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
-    n = len(pairs)
-    if n == 0:
+    if len(pairs) == 0:
         return np.zeros(0, DMATCH_DTYPE), np.zeros(0, LOGOS_RESULT_DTYPE), np.zeros(0, RESULT_DTYPE)
-    total = int((pairs["match_off"] + np.maximum(pairs["m"], 0)).max())
-    ok = (pairs["frame_a"] >= 0) & (pairs["frame_a"] < table.n_frames)
-    max_q = int(table.counts[pairs["frame_a"][ok]].max()) if ok.any() else 0
-    ws = ctx.logos_workspace_bytes(0, n, max_q)
-    d_pairs = _to_dev(pairs, dev)
-    d_ws = torch.empty(ws, dtype=torch.uint8, device=dev)
-    d_out = torch.zeros(max(total, 1) * 16, dtype=torch.uint8, device=dev)
-    d_lres = torch.zeros(n * LOGOS_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    d_pres = torch.zeros(n * RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    torch.cuda.synchronize(dev)
-    table.filter_device(d_pairs.data_ptr(), n, d_ws.data_ptr(), ws, d_out.data_ptr(), d_lres.data_ptr(), d_pres.data_ptr())
+    job = LogosFilter(ctx, table, pairs)
+    job.run()
     ctx.synchronize()
-    return (d_out.cpu().numpy().view(DMATCH_DTYPE)[:total], d_lres.cpu().numpy().view(LOGOS_RESULT_DTYPE).copy(),
-            d_pres.cpu().numpy().view(RESULT_DTYPE).copy())
+    return job.results()
 
 
 def logos_pairs(ctx, table, pairs, capacity=None):
     """The survivors of every (frame_a, frame_b) pair of `pairs` on a LogosTable: (list of DMATCH_DTYPE arrays, LOGOS_RESULT_DTYPE
     records). capacity: output room per pair (int or one per pair; default max(n_a, n_b)). Pairs that come back with
     GMS_ERR_CAPACITY are run once more with the count they reported, as matchLOGOS does for one pair."""
-    recs = logos_pair_table(table, pairs, capacity)
-    out, lres, _ = logos_filter(ctx, table, recs)
-    over = np.nonzero(lres["status"] == GMS_ERR_CAPACITY)[0]
-    where = {p: (out, int(recs["match_off"][p])) for p in range(len(recs))}
-    if len(over):
-        again = recs[over].copy()
-        again["m"] = lres["n_out"][over]
-        again["match_off"] = np.concatenate([[0], np.cumsum(again["m"])[:-1]])
-        out2, lres2, _ = logos_filter(ctx, table, again)
-        lres[over] = lres2
-        where.update({int(p): (out2, int(again["match_off"][q])) for q, p in enumerate(over)})
-    got = []
-    for p in range(len(recs)):
-        arr, o = where[p]
-        k = int(lres["n_out"][p]) if lres["status"][p] == 0 else 0
-        got.append(arr[o:o + k].copy())
-    return got, lres
+    return run_with_retry(logos_pair_table(table, pairs, capacity), lambda recs: logos_filter(ctx, table, recs)[:2])
+
+
+def _words_device(ctx, kind, rows, dic, dev):
+    """gms_logos_words_device on host rows and a host dictionary -> (int32 device tensor of one word per row, the device inputs).
+    Stream-ordered on the context's stream and not waited for: the caller holds on to the inputs until it has synchronised."""
+    d_desc = torch.from_numpy(rows.view(np.uint8).reshape(-1)).to(dev)
+    d_dict = torch.from_numpy(dic.view(np.uint8).reshape(-1).copy()).to(dev)
+    d_words = torch.zeros(len(rows), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)
+    ctx.logos_words_device(kind, d_desc.data_ptr(), len(rows), d_dict.data_ptr(), len(dic), d_words.data_ptr())
+    return d_words, (d_desc, d_dict)
 
 
 def logos_words(ctx, descriptors_per_frame, dictionary, kind, device=None):
     """gms_logos_words_device: the exact nearest dictionary row (lowest index on ties) of every descriptor row -- in place of the
     reference's FLANN lookup (FeatureMatchUtil.cpp:86-131). descriptors_per_frame: a list of per-frame row arrays (or one array);
     kind GMS_DESC_L2_F32X128: float32 [n, 128] rows, GMS_DESC_HAMMING256: uint8 [n, 32]. Returns int32 words per frame."""
-    dev = torch.device(device if device is not None else f"cuda:{ctx.device}")
+    dev = _device(ctx, device)
     kind = int(kind)
-    dt, width = (np.uint8, 32) if kind == GMS_DESC_HAMMING256 else (np.float32, 128)
+    dt, width = desc_layout(kind)
     single = not isinstance(descriptors_per_frame, (list, tuple))
     frames = [descriptors_per_frame] if single else list(descriptors_per_frame)
     rows = [np.ascontiguousarray(d, dtype=dt).reshape(-1, width) for d in frames]
@@ -449,11 +464,7 @@ def logos_words(ctx, descriptors_per_frame, dictionary, kind, device=None):
     dic = np.ascontiguousarray(dictionary, dtype=dt).reshape(-1, width)
     words = np.zeros(0, np.int32)
     if total:
-        d_desc = torch.from_numpy(np.concatenate(rows).view(np.uint8).reshape(-1)).to(dev)
-        d_dict = torch.from_numpy(dic.view(np.uint8).reshape(-1).copy()).to(dev)
-        d_words = torch.zeros(total, dtype=torch.int32, device=dev)
-        torch.cuda.synchronize(dev)
-        ctx.logos_words_device(kind, d_desc.data_ptr(), total, d_dict.data_ptr(), len(dic), d_words.data_ptr())
+        d_words, held = _words_device(ctx, kind, np.concatenate(rows), dic, dev)
         ctx.synchronize()
         words = d_words.cpu().numpy()
     elif not 1 <= len(dic) <= 65535:
@@ -472,7 +483,7 @@ class LogosDictionary:
         self.dtype, self.width = logos_dict_args(kind, n_words, attempts, max_iters)
         self.ctx, self.kind, self.n_sets, self.total_rows = ctx, int(kind), int(n_sets), int(total_rows)
         self.n_words, self.attempts, self.max_iters, self.seed = int(n_words), int(attempts), int(max_iters), int(seed)
-        dev = torch.device(device if device is not None else f"cuda:{ctx.device}")
+        dev = _device(ctx, device)
         self.device = dev
         self.ws_bytes = ctx.logos_dict_workspace_bytes(self.kind, self.total_rows, self.n_sets, self.n_words, self.attempts, self.max_iters)
         if self.ws_bytes == 0:

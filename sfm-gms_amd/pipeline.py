@@ -18,10 +18,30 @@ torch here is device memory only; every stage is a call into csrc/libgms_hip.so.
 import numpy as np
 import torch
 
-from .batch import BfSelect, DescriptorTable, FrameTable, LogosTable, _to_dev, bf_select_table, logos_dictionary
+from .batch import (BfSelect, DescriptorTable, FrameTable, LogosFilter, LogosTable, _to_dev, _words_device, bf_select_table, frame_counts,
+                    frame_pairs_of, logos_dictionary, pair_table)
 from .api import logos_dict_args
-from .types import (DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_ERR_CAPACITY, LOGOS_RESULT_DTYPE, PAIR_DTYPE, RESULT_DTYPE, TWO_VIEW_DTYPE,
-                    make_camera)
+from .types import DMATCH_DTYPE, GMS_ERR_CAPACITY, PAIR_DTYPE, RESULT_DTYPE, TWO_VIEW_DTYPE, desc_layout, make_camera
+
+
+def _two_view(ctx, frames, d_pairs, n_pairs, max_m, total_m, d_out, d_res, camera, dist, prob, ransac_threshold, max_iters):
+    """gms_two_view_batch_device on the survivors d_out and their gms_pair_result records d_res, laid out by the pair table d_pairs ->
+    the two-view part of run_dataset's result: two_view, coords1, coords2, mask, points3d as host arrays."""
+    dev = frames.device
+    cam = make_camera(camera, dist)
+    d_c1 = torch.zeros(max(total_m, 1) * 2, dtype=torch.float32, device=dev)
+    d_c2 = torch.zeros(max(total_m, 1) * 2, dtype=torch.float32, device=dev)
+    d_mask = torch.zeros(max(total_m, 1), dtype=torch.uint8, device=dev)
+    d_p3 = torch.zeros(max(total_m, 1) * 3, dtype=torch.float64, device=dev)
+    d_tv = torch.zeros(max(n_pairs, 1) * TWO_VIEW_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+    ctx.two_view_batch_device(cam, frames.d_kp.data_ptr(), frames.d_frame_off.data_ptr(), frames.n_frames, d_pairs.data_ptr(), n_pairs,
+                              max_m, d_out.data_ptr(), d_res.data_ptr(), d_c1.data_ptr(), d_c2.data_ptr(), d_mask.data_ptr(),
+                              d_p3.data_ptr(), d_tv.data_ptr(), prob, ransac_threshold, max_iters)
+    ctx.synchronize()
+    return dict(two_view=d_tv.cpu().numpy().view(TWO_VIEW_DTYPE)[:n_pairs], coords1=d_c1.cpu().numpy().reshape(-1, 2)[:total_m],
+                coords2=d_c2.cpu().numpy().reshape(-1, 2)[:total_m], mask=d_mask.cpu().numpy()[:total_m],
+                points3d=d_p3.cpu().numpy().reshape(-1, 3)[:total_m])
 
 
 def run_dataset(ctx, ds, withRotation=False, withScale=False, thresholdFactor=6.0, match=None, camera=None, dist=None, prob=0.7,
@@ -62,8 +82,8 @@ def run_dataset(ctx, ds, withRotation=False, withScale=False, thresholdFactor=6.
         if ds.descriptors is None:
             raise ValueError("the dataset carries no descriptors to match")
         # BFMatcher::match without cross-check: one match per keypoint of the query frame (FeatureMatchUtil.cpp:66-68)
-        pairs["m"] = counts[pairs["frame_a"]] if n_pairs else 0
-        pairs["match_off"] = np.concatenate([[0], np.cumsum(pairs["m"][:-1])]) if n_pairs else 0
+        table = pair_table(frame_pairs_of(pairs), counts[pairs["frame_a"]] if n_pairs else 0)
+        pairs["m"], pairs["match_off"] = table["m"], table["match_off"]
     total_m = int((pairs["match_off"] + pairs["m"]).max()) if n_pairs else 0
     max_m = int(pairs["m"].max()) if n_pairs else 0
     d_pairs = _to_dev(pairs, dev) if n_pairs else torch.zeros(24, dtype=torch.uint8, device=dev)
@@ -84,20 +104,7 @@ def run_dataset(ctx, ds, withRotation=False, withScale=False, thresholdFactor=6.
                       d_matches.data_ptr(), d_out.data_ptr(), d_res.data_ptr(), None, withRotation, withScale, thresholdFactor)
     out = dict(pairs=pairs)
     if camera is not None:
-        cam = make_camera(camera, dist)
-        d_c1 = torch.zeros(max(total_m, 1) * 2, dtype=torch.float32, device=dev)
-        d_c2 = torch.zeros(max(total_m, 1) * 2, dtype=torch.float32, device=dev)
-        d_mask = torch.zeros(max(total_m, 1), dtype=torch.uint8, device=dev)
-        d_p3 = torch.zeros(max(total_m, 1) * 3, dtype=torch.float64, device=dev)
-        d_tv = torch.zeros(max(n_pairs, 1) * TWO_VIEW_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        torch.cuda.synchronize(dev)
-        ctx.two_view_batch_device(cam, frames.d_kp.data_ptr(), frames.d_frame_off.data_ptr(), frames.n_frames, d_pairs.data_ptr(), n_pairs,
-                                  max_m, d_out.data_ptr(), d_res.data_ptr(), d_c1.data_ptr(), d_c2.data_ptr(), d_mask.data_ptr(),
-                                  d_p3.data_ptr(), d_tv.data_ptr(), prob, ransac_threshold, max_iters)
-        ctx.synchronize()
-        out.update(two_view=d_tv.cpu().numpy().view(TWO_VIEW_DTYPE)[:n_pairs], coords1=d_c1.cpu().numpy().reshape(-1, 2)[:total_m],
-                   coords2=d_c2.cpu().numpy().reshape(-1, 2)[:total_m], mask=d_mask.cpu().numpy()[:total_m],
-                   points3d=d_p3.cpu().numpy().reshape(-1, 3)[:total_m])
+        out.update(_two_view(ctx, frames, d_pairs, n_pairs, max_m, total_m, d_out, d_res, camera, dist, prob, ransac_threshold, max_iters))
     ctx.synchronize()
     out.update(matches=d_matches.cpu().numpy().view(DMATCH_DTYPE)[:total_m], out=d_out.cpu().numpy().view(DMATCH_DTYPE)[:total_m],
                results=d_res.cpu().numpy().view(RESULT_DTYPE)[:n_pairs])
@@ -145,70 +152,40 @@ def _run_logos(ctx, ds, dictionary, capacity, camera, dist, prob, ransac_thresho
     frames = FrameTable(ctx, ds.frames, ds.sizes, device=device)
     dev = frames.device
     kind = int(ds.desc_kind)
-    dt, width = (np.uint8, 32) if kind == GMS_DESC_HAMMING256 else (np.float32, 128)
+    dt, width = desc_layout(kind)
     dic = np.ascontiguousarray(dictionary, dtype=dt).reshape(-1, width)
     total_kp = frames.total
-    d_words = torch.zeros(max(total_kp, 1), dtype=torch.int32, device=dev)
     if total_kp:
         desc = np.concatenate([np.ascontiguousarray(d, dtype=dt).reshape(-1, width) for d in ds.descriptors])
         if len(desc) != total_kp:
             raise ValueError("one descriptor per keypoint")
-        d_desc = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(dev)
-        d_dict = torch.from_numpy(dic.view(np.uint8).reshape(-1).copy()).to(dev)
-        torch.cuda.synchronize(dev)
-        ctx.logos_words_device(kind, d_desc.data_ptr(), total_kp, d_dict.data_ptr(), len(dic), d_words.data_ptr())
+        d_words, held = _words_device(ctx, kind, desc, dic, dev)   # (held: the launch's inputs, alive until this function returns)
+    else:
+        d_words = torch.zeros(1, dtype=torch.int32, device=dev)
     table = LogosTable(ctx, frames, d_words, len(dic))
-    src = np.ascontiguousarray(ds.pairs, dtype=PAIR_DTYPE)
+    src = frame_pairs_of(np.ascontiguousarray(ds.pairs, dtype=PAIR_DTYPE))
     n_pairs = len(src)
     counts = np.diff(frames.frame_off_host)
-    # a frame index out of range is the library's to report (GMS_ERR_BAD_ARG for that pair alone): it counts as an empty frame here
-    def frame_kp(f):
-        f = np.asarray(f, np.int64)
-        ok = (f >= 0) & (f < len(counts))
-        return np.where(ok, counts[np.clip(f, 0, max(len(counts) - 1, 0))] if len(counts) else 0, 0).astype(np.int64)
-
-    n_a, n_b = frame_kp(src["frame_a"]), frame_kp(src["frame_b"])
-    cap = np.maximum(n_a, n_b) if capacity is None else np.full(n_pairs, int(capacity), np.int64)
-    max_q = int(n_a.max()) if n_pairs else 0
-    ws = ctx.logos_workspace_bytes(0, n_pairs, max_q)
-    d_ws = torch.empty(max(ws, 16), dtype=torch.uint8, device=dev)
-    d_lres = torch.zeros(max(n_pairs, 1) * LOGOS_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    d_res = torch.zeros(max(n_pairs, 1) * RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    cap = (np.maximum(frame_counts(counts, src[:, 0]), frame_counts(counts, src[:, 1])) if capacity is None
+           else np.full(n_pairs, int(capacity), np.int64))
     for attempt in range(2):
-        pairs = src.copy()
-        pairs["m"] = cap
-        pairs["match_off"] = np.concatenate([[0], np.cumsum(cap)[:-1]]) if n_pairs else 0
-        total_m = int(cap.sum())
-        d_pairs = _to_dev(pairs, dev) if n_pairs else torch.zeros(24, dtype=torch.uint8, device=dev)
-        d_out = torch.zeros(max(total_m, 1) * 16, dtype=torch.uint8, device=dev)
-        torch.cuda.synchronize(dev)
+        pairs = pair_table(src, cap)
+        job = LogosFilter(ctx, table, pairs)
         if n_pairs:
-            table.filter_device(d_pairs.data_ptr(), n_pairs, d_ws.data_ptr(), ws, d_out.data_ptr(), d_lres.data_ptr(), d_res.data_ptr())
+            job.run()
         ctx.synchronize()
-        lres = d_lres.cpu().numpy().view(LOGOS_RESULT_DTYPE)[:n_pairs].copy()
+        lres = job.logos_results()
         over = lres["status"] == GMS_ERR_CAPACITY
         if attempt or not over.any():
             break
         cap = np.where(over, lres["n_out"], cap).astype(np.int64)   # room for what the overflowing pairs reported
+    total_m = job.out_len
     out = dict(pairs=pairs, logos_results=lres, words=d_words.cpu().numpy()[:total_kp])
-    max_m = int(cap.max()) if n_pairs else 0
     if camera is not None:
-        cam = make_camera(camera, dist)
-        d_c1 = torch.zeros(max(total_m, 1) * 2, dtype=torch.float32, device=dev)
-        d_c2 = torch.zeros(max(total_m, 1) * 2, dtype=torch.float32, device=dev)
-        d_mask = torch.zeros(max(total_m, 1), dtype=torch.uint8, device=dev)
-        d_p3 = torch.zeros(max(total_m, 1) * 3, dtype=torch.float64, device=dev)
-        d_tv = torch.zeros(max(n_pairs, 1) * TWO_VIEW_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        torch.cuda.synchronize(dev)
-        ctx.two_view_batch_device(cam, frames.d_kp.data_ptr(), frames.d_frame_off.data_ptr(), frames.n_frames, d_pairs.data_ptr(), n_pairs,
-                                  max_m, d_out.data_ptr(), d_res.data_ptr(), d_c1.data_ptr(), d_c2.data_ptr(), d_mask.data_ptr(),
-                                  d_p3.data_ptr(), d_tv.data_ptr(), prob, ransac_threshold, max_iters)
-        ctx.synchronize()
-        out.update(two_view=d_tv.cpu().numpy().view(TWO_VIEW_DTYPE)[:n_pairs], coords1=d_c1.cpu().numpy().reshape(-1, 2)[:total_m],
-                   coords2=d_c2.cpu().numpy().reshape(-1, 2)[:total_m], mask=d_mask.cpu().numpy()[:total_m],
-                   points3d=d_p3.cpu().numpy().reshape(-1, 3)[:total_m])
-    out.update(matches=np.zeros(0, DMATCH_DTYPE), out=d_out.cpu().numpy().view(DMATCH_DTYPE)[:total_m],
-               results=d_res.cpu().numpy().view(RESULT_DTYPE)[:n_pairs])
+        out.update(_two_view(ctx, frames, job.d_pairs, n_pairs, int(cap.max()) if n_pairs else 0, total_m, job.d_out, job.d_pres, camera,
+                             dist, prob, ransac_threshold, max_iters))
+    res_out, _, pres = job.results()
+    out.update(matches=np.zeros(0, DMATCH_DTYPE), out=res_out, results=pres)
     return out
 
 
@@ -220,12 +197,10 @@ def _run_bf(ctx, ds, cross_check, distance_coef, max_size, camera, dist, prob, r
     if ds.descriptors is None:
         raise ValueError("method='bf' needs the dataset's descriptors")
     frames = FrameTable(ctx, ds.frames, ds.sizes, device=device)
-    dev = frames.device
     descs = DescriptorTable(ctx, frames, ds.descriptors, ds.desc_kind)
     src = np.ascontiguousarray(ds.pairs, dtype=PAIR_DTYPE)
     n_pairs = len(src)
-    pairs = bf_select_table(descs, np.stack([src["frame_a"], src["frame_b"]], axis=1) if n_pairs else np.zeros((0, 2)),
-                            max_size=max_size)
+    pairs = bf_select_table(descs, frame_pairs_of(src), max_size=max_size)
     run = BfSelect(ctx, descs, pairs, cross_check, distance_coef, max_size)
     if n_pairs:
         run.run()
@@ -234,20 +209,8 @@ def _run_bf(ctx, ds, cross_check, distance_coef, max_size, camera, dist, prob, r
     max_m = int(pairs["m"].max()) if n_pairs else 0
     out = dict(pairs=pairs)
     if camera is not None:
-        cam = make_camera(camera, dist)
-        d_c1 = torch.zeros(max(total_m, 1) * 2, dtype=torch.float32, device=dev)
-        d_c2 = torch.zeros(max(total_m, 1) * 2, dtype=torch.float32, device=dev)
-        d_mask = torch.zeros(max(total_m, 1), dtype=torch.uint8, device=dev)
-        d_p3 = torch.zeros(max(total_m, 1) * 3, dtype=torch.float64, device=dev)
-        d_tv = torch.zeros(max(n_pairs, 1) * TWO_VIEW_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        torch.cuda.synchronize(dev)
-        ctx.two_view_batch_device(cam, frames.d_kp.data_ptr(), frames.d_frame_off.data_ptr(), frames.n_frames, run.d_pairs.data_ptr(),
-                                  n_pairs, max_m, run.d_out.data_ptr(), run.d_pres.data_ptr(), d_c1.data_ptr(), d_c2.data_ptr(),
-                                  d_mask.data_ptr(), d_p3.data_ptr(), d_tv.data_ptr(), prob, ransac_threshold, max_iters)
-        ctx.synchronize()
-        out.update(two_view=d_tv.cpu().numpy().view(TWO_VIEW_DTYPE)[:n_pairs], coords1=d_c1.cpu().numpy().reshape(-1, 2)[:total_m],
-                   coords2=d_c2.cpu().numpy().reshape(-1, 2)[:total_m], mask=d_mask.cpu().numpy()[:total_m],
-                   points3d=d_p3.cpu().numpy().reshape(-1, 3)[:total_m])
+        out.update(_two_view(ctx, frames, run.d_pairs, n_pairs, max_m, total_m, run.d_out, run.d_pres, camera, dist, prob,
+                             ransac_threshold, max_iters))
     res_out, bf_res, pres = run.results()
     out.update(matches=np.zeros(0, DMATCH_DTYPE), out=res_out[:total_m], results=pres, bf_results=bf_res)
     return out

@@ -83,6 +83,21 @@ class GmsError(RuntimeError):
 # descriptor kinds of the brute-force matcher (include/gms.h)
 GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128 = 0, 1
 
+
+def desc_layout(kind):
+    """(row dtype, row width) of a descriptor kind: uint8 x 32 (ORB) or float32 x 128 (SIFT)."""
+    if int(kind) not in (GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128):
+        raise ValueError("kind: GMS_DESC_HAMMING256 or GMS_DESC_L2_F32X128")
+    return (np.uint8, 32) if int(kind) == GMS_DESC_HAMMING256 else (np.float32, 128)
+
+
+def concat_frames(keypoints_per_frame):
+    """Per-frame KEYPOINT_DTYPE arrays -> (all keypoints back to back, frame_off int64 [n_frames + 1])."""
+    frame_off = np.concatenate([[0], np.cumsum([len(k) for k in keypoints_per_frame])]).astype(np.int64)
+    kp = (np.concatenate([np.ascontiguousarray(k, dtype=KEYPOINT_DTYPE) for k in keypoints_per_frame])
+          if frame_off[-1] else np.zeros(0, dtype=KEYPOINT_DTYPE))
+    return kp, frame_off
+
 # gms_disparity_stats (include/gms.h)
 DISPARITY_STATS_DTYPE = np.dtype([("count", "<i8"), ("sum_sq", "<i8"), ("max_abs", "<i4"), ("status", "<i4")])
 assert DISPARITY_STATS_DTYPE.itemsize == 24

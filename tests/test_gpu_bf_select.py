@@ -157,6 +157,23 @@ def test_empty_bad_and_overflow(ctx, pkg):
     assert res2["status"].tolist() == [0, -1]
 
 
+def test_pairs_short_of_room_are_run_again(ctx, pkg):
+    """bf_select_pairs with room that two of three pairs exceed: those two are run a second time with the count they reported, and
+    every pair's survivors and record equal those of the call with the default room, and the restatement's."""
+    batch = _batch()
+    rng = np.random.default_rng(29)
+    rows = [_rows(0, n, rng) for n in (40, 70, 33)]
+    descs = _tables(ctx, pkg, rows, 0)
+    fp = [(0, 1), (1, 2), (2, 0)]
+    first, res1 = batch.bf_select_pairs(ctx, descs, fp)
+    n_out = [int(k) for k in res1["n_out"]]
+    assert n_out[1] >= 1 and n_out[2] > 1   # (so that the room below is short for pairs 1 and 2)
+    second, res2 = batch.bf_select_pairs(ctx, descs, fp, capacity=[n_out[0], n_out[1] - 1, 1])
+    assert [a.tobytes() for a in second] == [a.tobytes() for a in first]
+    assert res2.tobytes() == res1.tobytes()
+    _check(second, res2, rows, fp, 0, True, 4.0, 500, {})
+
+
 # ---- 3. more than 1024 pairs ----------------------------------------------------------------------------------------------------
 def test_more_than_1024_pairs(ctx, pkg):
     batch = _batch()

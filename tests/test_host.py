@@ -2,6 +2,7 @@
 path fails loudly without a GPU, PODs have the reference's layout, sharding tiles the pair list, the
 synthetic recipe is deterministic, and the N>1 driver logic works under gloo with world_size 2."""
 import ctypes as C
+import importlib
 import os
 import re
 import subprocess
@@ -24,6 +25,66 @@ def test_header_symbols_are_exported(pkg):
     assert b"gfx950" in lib.gms_version()
     assert lib.gms_max_matches() >= 10000
     assert lib.gms_error_string(-2).decode().startswith("input outside")
+
+
+_C_CLASSES = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "size_t": C.c_size_t,
+              "double": C.c_double, "void": None}
+
+
+def _c_class(decl, name, is_return=False):
+    """The ctypes class a C parameter or return declaration stands for: "pointer" for a pointer or array, else the scalar's."""
+    if "*" in decl or "[" in decl:
+        return "pointer"
+    words = [w for w in re.findall(r"[A-Za-z_]\w*", decl) if w != "const"]
+    if not is_return and len(words) == 2:
+        words = words[:1]   # (the parameter's name)
+    assert len(words) == 1 and words[0] in _C_CLASSES, f"{name}: cannot read {decl!r}"
+    return _C_CLASSES[words[0]]
+
+
+def _ctypes_class(t):
+    return "pointer" if t in (C.c_void_p, C.c_char_p) or (isinstance(t, type) and issubclass(t, C._Pointer)) else t
+
+
+def test_signature_table_matches_the_header(pkg):
+    """Every prototype of include/gms.h against capi.SIGNATURES: the return type and the class of each parameter (pointer, int, int64,
+    uint64, size_t, double). A prototype the parser cannot read fails."""
+    capi = importlib.import_module("sfm-gms_amd.capi")
+    hdr = open(os.path.join(ROOT, "include", "gms.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = re.sub(r"^\s*#.*$", "", hdr, flags=re.M)                       # preprocessor lines
+    hdr = re.sub(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;", "", hdr, flags=re.S)   # struct bodies hold no prototypes
+    seen = {}
+    for stmt in hdr.split(";"):
+        if "gms_" not in stmt or "(" not in stmt:
+            continue
+        m = re.fullmatch(r"\s*([\w\s\*]+?)\b(gms_[a-z_0-9]+)\s*\((.*)\)\s*", stmt, flags=re.S)
+        assert m, f"cannot read the prototype {' '.join(stmt.split())!r}"
+        ret, name, params = m.groups()
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        seen[name] = (_c_class(ret, name, is_return=True), [_c_class(p, name) for p in params])
+    assert sorted(seen) == sorted(capi.SIGNATURES) == sorted(pkg.EXPORTED_SYMBOLS)
+    for name, (ret, params) in seen.items():
+        restype, argtypes = capi.SIGNATURES[name]
+        assert _ctypes_class(restype) == ret, f"{name}: returns {restype}, the header says {ret}"
+        assert [_ctypes_class(t) for t in argtypes] == params, f"{name}: {argtypes} against the header's {params}"
+    lib = pkg.load_library()
+    for name, (restype, argtypes) in capi.SIGNATURES.items():            # and the table is what the loaded library carries
+        assert getattr(lib, name).restype is restype and list(getattr(lib, name).argtypes) == argtypes, name
+
+
+def test_detect_workspace_size_is_not_truncated(pkg):
+    """gms_detect_workspace_bytes returns size_t: 300 images of 1920 x 1080 need more than 2^31 bytes (host arithmetic, no device).
+    The size restates detect_kernels.hip: detect_workspace_bytes."""
+    lib = pkg.load_library()
+    w, h, n, max_kp = 1920, 1080, 300, 10000
+    up = lambda b: (b + 255) & ~255
+    plane = w * h
+    want = up(plane * n) * 2 + up(plane * n * 2) + n * 256 * 4 + n * 16 + up(n * h * 8) + up(n * max_kp * 8)
+    got = lib.gms_detect_workspace_bytes(w, h, n, max_kp)
+    assert got > 2**31
+    assert got == want
+    assert lib.gms_detect_pyramid_workspace_bytes(w, h, n, max_kp, 1) >= got
 
 
 def test_pod_layouts_match_reference_strides(pkg):
