@@ -30,9 +30,7 @@ constexpr int kSelWaves = kSelBlock / 64;
 constexpr int kPlanBlock = 1024;
 constexpr int kLdsRecs = 10240;  // 80 KiB: 8 bytes per slot, or per sort record (float d + int32 ix); two workgroups per CU
 
-constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// the workspace: matcher pair table | matcher output | per pair, stride max_rows: (q, t) / slots (u64), d (f32), ix (i32)
+// the workspace's typed pointers (its regions: BfSelectLayout in ws_layout.h); per pair, stride max_rows: (q, t) / slots, d, ix
 struct SelWs {
     gms_pair* pairs2;
     gms_dmatch* back;
@@ -40,24 +38,6 @@ struct SelWs {
     float* cd;
     int32_t* cix;
 };
-
-__host__ __device__ inline SelWs sel_ws(void* base, int n_pairs, int64_t max_rows, int64_t total_back)
-{
-    char* b = static_cast<char*>(base);
-    SelWs w;
-    size_t o = 0;
-    w.pairs2 = reinterpret_cast<gms_pair*>(b + o);
-    o += align256(sizeof(gms_pair) * (size_t)n_pairs);
-    w.back = reinterpret_cast<gms_dmatch*>(b + o);
-    o += align256(sizeof(gms_dmatch) * (size_t)total_back);
-    const size_t rows = (size_t)n_pairs * (size_t)max_rows;
-    w.qt = reinterpret_cast<uint64_t*>(b + o);
-    o += align256(8 * rows);
-    w.cd = reinterpret_cast<float*>(b + o);
-    o += align256(4 * rows);
-    w.cix = reinterpret_cast<int32_t*>(b + o);
-    return w;
-}
 
 struct PairCheck {
     int64_t offA, offB;
@@ -293,19 +273,16 @@ bf_select_kernel(const gms_pair* __restrict__ pairs, const int64_t* __restrict__
 
 }  // namespace
 
-size_t bf_select_ws_bytes(int n_pairs, int64_t max_rows, int64_t total_back)
-{
-    const size_t rows = (size_t)n_pairs * (size_t)max_rows;
-    return align256(sizeof(gms_pair) * (size_t)n_pairs) + align256(sizeof(gms_dmatch) * (size_t)total_back) + align256(8 * rows) +
-           align256(4 * rows) + align256(4 * rows);
-}
+size_t bf_select_ws_bytes(int n_pairs, int64_t max_rows, int64_t total_back) { return bf_select_layout(n_pairs, max_rows, total_back).total; }
 
 hipError_t launch_bf_select(int kind, const void* d_desc, const void* d_prep, int64_t total, const int64_t* d_frame_off, int n_frames,
                             const gms_pair* d_pairs, int n_pairs, int max_rows, int64_t total_back, int cross, double coef, int max_size,
                             void* d_ws, gms_dmatch* d_out, gms_bf_result* d_res, gms_pair_result* d_pres, hipStream_t stream)
 {
     if (n_pairs <= 0) return hipSuccess;
-    const SelWs ws = sel_ws(d_ws, n_pairs, max_rows, total_back);
+    const BfSelectLayout L = bf_select_layout(n_pairs, max_rows, total_back);
+    const SelWs ws = {ws_ptr<gms_pair>(d_ws, L.pairs2), ws_ptr<gms_dmatch>(d_ws, L.back), ws_ptr<uint64_t>(d_ws, L.qt), ws_ptr<float>(d_ws, L.cd),
+                      ws_ptr<int32_t>(d_ws, L.cix)};
     hipLaunchKernelGGL(bf_sel_plan_kernel, dim3(1), dim3(kPlanBlock), 0, stream, d_pairs, n_pairs, d_frame_off, n_frames, max_rows,
                        cross, total_back, ws.pairs2);
     hipError_t e = hipGetLastError();

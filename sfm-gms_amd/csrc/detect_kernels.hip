@@ -36,7 +36,6 @@
 namespace gms {
 namespace {
 
-constexpr int kBorder = 16;
 constexpr int kBins = 32;
 constexpr int kTests = 256;
 constexpr int kTileW = 64, kTileH = 16, kHalo = 3;
@@ -468,36 +467,19 @@ pyr_counts_kernel(const int32_t* __restrict__ lvl, int n_images, int n_used, int
 
 }  // namespace
 
-// workspace of a batch: score | candidates | box sums | histogram | cut | row counts | list
 size_t detect_workspace_bytes(int w, int h, int n_images, int max_keypoints)
 {
     if (w <= 0 || h <= 0 || n_images <= 0 || max_keypoints < 0) return 0;
-    const size_t plane = (size_t)w * h;
-    size_t b = 0;
-    b += ((plane * n_images + 255) & ~(size_t)255) * 2;        // score, candidates
-    b += (plane * n_images * 2 + 255) & ~(size_t)255;           // box sums
-    b += (size_t)n_images * 256 * 4 + (size_t)n_images * 16;    // histogram, cut
-    b += ((size_t)n_images * h * 8 + 255) & ~(size_t)255;       // row counts
-    b += ((size_t)n_images * max_keypoints * 8 + 255) & ~(size_t)255;   // list
-    return b;
+    return detect_layout(w, h, n_images, max_keypoints).total;
 }
 
 namespace {
-struct DetWs { uint8_t* score; uint8_t* cand; uint16_t* box; uint32_t* hist; int32_t* cut; uint32_t* rows; uint32_t* list; };
+struct DetWs { uint8_t* score; uint8_t* cand; uint16_t* box; uint32_t* hist; int32_t* cut; uint32_t* rows; uint32_t* list; size_t hist_bytes; };
 DetWs carve(void* ws, int w, int h, int n_images, int max_keypoints)
 {
-    const size_t plane = (size_t)w * h, a = (plane * n_images + 255) & ~(size_t)255;
-    char* p = reinterpret_cast<char*>(ws);
-    DetWs d;
-    d.score = reinterpret_cast<uint8_t*>(p); p += a;
-    d.cand = reinterpret_cast<uint8_t*>(p); p += a;
-    d.box = reinterpret_cast<uint16_t*>(p); p += (plane * n_images * 2 + 255) & ~(size_t)255;
-    d.hist = reinterpret_cast<uint32_t*>(p); p += (size_t)n_images * 256 * 4;
-    d.cut = reinterpret_cast<int32_t*>(p); p += (size_t)n_images * 16;
-    d.rows = reinterpret_cast<uint32_t*>(p); p += ((size_t)n_images * h * 8 + 255) & ~(size_t)255;
-    d.list = reinterpret_cast<uint32_t*>(p);
-    (void)max_keypoints;
-    return d;
+    const DetectLayout L = detect_layout(w, h, n_images, max_keypoints);
+    return {ws_ptr<uint8_t>(ws, L.score), ws_ptr<uint8_t>(ws, L.cand), ws_ptr<uint16_t>(ws, L.box), ws_ptr<uint32_t>(ws, L.hist),
+            ws_ptr<int32_t>(ws, L.cut), ws_ptr<uint32_t>(ws, L.rows), ws_ptr<uint32_t>(ws, L.list), L.cut - L.hist};
 }
 
 // the detector on one set of equally sized images: the single-scale call (lo == nullptr; clears its histogram itself) or one level of the
@@ -509,7 +491,7 @@ hipError_t detect_level(const uint8_t* d_images, int n_images, int w, int h, int
     if (level_hist != nullptr) {
         ws.hist = level_hist;
     } else {
-        hipError_t e = hipMemsetAsync(ws.hist, 0, (size_t)n_images * 256 * 4, stream);
+        hipError_t e = hipMemsetAsync(ws.hist, 0, ws.hist_bytes, stream);
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(det_maps_kernel, dim3((w + kTileW - 1) / kTileW, (h + kTileH - 1) / kTileH, n_images), dim3(256), 0, stream, d_images, w, h,
@@ -530,8 +512,6 @@ hipError_t detect_level(const uint8_t* d_images, int n_images, int w, int h, int
     }
     return hipGetLastError();
 }
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 }  // namespace
 
 hipError_t launch_detect(const uint8_t* d_images, int n_images, int w, int h, int threshold, int max_keypoints, void* d_ws,
@@ -557,19 +537,7 @@ hipError_t launch_describe(const uint8_t* d_image, int w, int h, gms_keypoint* d
 }
 
 // ---- the pyramid keypoint source --------------------------------------------------------------------------------
-// Level 0 is the image; w_l = (5 w_{l-1} + 3) / 6, the same for h; the levels end at n_levels or before the first one the detector
-// refuses (width or height <= 32). Returns the number of levels (0: level 0 itself is refused).
-int pyramid_level_sizes(int w, int h, int n_levels, int* widths, int* heights)
-{
-    int n = 0;
-    while (n < n_levels && n < kPyramidMaxLevels && w > 2 * kBorder && h > 2 * kBorder && w <= 65535 && h <= 65535) {
-        widths[n] = w; heights[n] = h;
-        ++n;
-        w = (5 * w + 3) / 6; h = (5 * h + 3) / 6;
-    }
-    return n;
-}
-
+// (the levels' sizes, pyramid_level_sizes, are part of the workspace's layout: ws_layout.h)
 // q_l = max_keypoints * area_l / (sum of the areas) in 64-bit integers; what the division leaves goes to level 0
 void pyramid_quotas(const int* widths, const int* heights, int n, int max_keypoints, int* quotas)
 {
@@ -580,16 +548,6 @@ void pyramid_quotas(const int* widths, const int* heights, int n, int max_keypoi
         given += quotas[l];
     }
     if (n > 0) quotas[0] = (int)(max_keypoints - given);
-}
-
-// bytes of levels 1 .. n - 1 of n_images images, level after level, the images of a level back to back, nothing between them
-size_t pyramid_bytes(int w, int h, int n_images, int n_levels)
-{
-    int ww[kPyramidMaxLevels], hh[kPyramidMaxLevels];
-    const int n = pyramid_level_sizes(w, h, n_levels, ww, hh);
-    size_t b = 0;
-    for (int l = 1; l < n; ++l) b += (size_t)ww[l] * hh[l] * (size_t)(n_images > 0 ? n_images : 0);
-    return b;
 }
 
 hipError_t launch_pyramid_build(const uint8_t* d_images, int n_images, int w, int h, int n_levels, uint8_t* d_levels, hipStream_t stream)
@@ -609,19 +567,10 @@ hipError_t launch_pyramid_build(const uint8_t* d_images, int n_images, int w, in
     return hipGetLastError();
 }
 
-// bytes of the part of the workspace that every call zeroes first: the levels' counts, then their histograms
-static size_t pyramid_cleared_bytes(int n_images)
-{
-    return align256((size_t)kPyramidMaxLevels * n_images * 4) + (size_t)kPyramidMaxLevels * n_images * 256 * 4;
-}
-
-// workspace: level images 1 .. | [level][image] counts | [level][image] score histograms | the single-scale workspace of level 0 (every
-// level fits into it in its turn)
 size_t detect_pyramid_workspace_bytes(int w, int h, int n_images, int max_keypoints, int n_levels)
 {
-    const size_t single = detect_workspace_bytes(w, h, n_images, max_keypoints);
-    if (single == 0 || n_levels < 1 || n_levels > kPyramidMaxLevels) return 0;
-    return align256(pyramid_bytes(w, h, n_images, n_levels)) + pyramid_cleared_bytes(n_images) + single;
+    if (detect_workspace_bytes(w, h, n_images, max_keypoints) == 0 || n_levels < 1 || n_levels > kPyramidMaxLevels) return 0;
+    return pyramid_layout(w, h, n_images, max_keypoints, n_levels).total;
 }
 
 hipError_t launch_detect_pyramid(const uint8_t* d_images, int n_images, int w, int h, int threshold, int max_keypoints, int n_levels, void* d_ws,
@@ -631,11 +580,12 @@ hipError_t launch_detect_pyramid(const uint8_t* d_images, int n_images, int w, i
     int ww[kPyramidMaxLevels], hh[kPyramidMaxLevels], quota[kPyramidMaxLevels];
     const int n = pyramid_level_sizes(w, h, n_levels, ww, hh);
     pyramid_quotas(ww, hh, n, max_keypoints, quota);
-    uint8_t* levels = reinterpret_cast<uint8_t*>(d_ws);
-    int32_t* lvl_counts = reinterpret_cast<int32_t*>(levels + align256(pyramid_bytes(w, h, n_images, n_levels)));
-    uint32_t* hists = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lvl_counts) + align256((size_t)kPyramidMaxLevels * n_images * 4));
-    void* det_ws = reinterpret_cast<char*>(lvl_counts) + pyramid_cleared_bytes(n_images);
-    const size_t clear_words = pyramid_cleared_bytes(n_images) / 4;   // (the counts too: a level with quota 0 is not run)
+    const PyramidLayout L = pyramid_layout(w, h, n_images, max_keypoints, n_levels);
+    uint8_t* levels = ws_ptr<uint8_t>(d_ws, L.levels);
+    int32_t* lvl_counts = ws_ptr<int32_t>(d_ws, L.counts);
+    uint32_t* hists = ws_ptr<uint32_t>(d_ws, L.hists);
+    void* det_ws = ws_ptr<char>(d_ws, L.detect);
+    const size_t clear_words = (L.detect - L.counts) / 4;
     hipLaunchKernelGGL(pyr_clear_kernel, dim3((unsigned)((clear_words + 255) / 256 < 1024 ? (clear_words + 255) / 256 : 1024)), dim3(256), 0, stream,
                        reinterpret_cast<uint32_t*>(lvl_counts), clear_words);
     hipError_t e = launch_pyramid_build(d_images, n_images, w, h, n_levels, levels, stream);

@@ -454,7 +454,6 @@ struct TileGeom {
     int tiles_y, tiles_x;
     uint32_t row_bytes; // 4 + 2 * nr
 };
-constexpr int kMaxTiles = 32;
 constexpr uint32_t kTileMatrixBytes = 144u * 1024u;
 constexpr uint32_t kTileNleftOff = kTileMatrixBytes;                 // [400] u32
 constexpr uint32_t kTileFineOff = kTileNleftOff + 4u * kLeftN;       // [1600] u32
@@ -816,23 +815,17 @@ hipError_t init_band_kernels()  // once per context: see init_filter_kernels
     return hipSuccess;
 }
 
-size_t band_ws_bytes_per_pair(int mcap, bool need_mask)
-{
-    return (size_t)mcap * 24 + (size_t)kFineN * 4 + 16 + (need_mask ? (size_t)mcap : 0);
-}
+size_t band_ws_bytes_per_pair(int mcap, bool need_mask) { return band_bytes_per_pair((size_t)mcap, need_mask); }
 
-// ws layout for n pairs: lists [n][3][mcap] uint2 | nfine [n][1600] u32 | list_len [n][3] u32 | flags [n] u32 |
-//                        mask [n][mcap] u8 (if p.mask is null)
 hipError_t launch_filter_band(const FilterParams& p, int mcap, void* ws, const uint32_t** flags_out, hipStream_t stream)
 {
     const int n = p.n_pairs;
     if (n <= 0) return hipSuccess;
-    uint2* lists = reinterpret_cast<uint2*>(ws);
-    uint32_t* nfine = reinterpret_cast<uint32_t*>(lists + (size_t)n * 3 * mcap);
-    uint32_t* list_len = nfine + (size_t)n * kFineN;
-    uint32_t* flags = list_len + (size_t)n * 3;
-    uint8_t* mask_ws = reinterpret_cast<uint8_t*>(flags + n);
-    hipError_t e = hipMemsetAsync(nfine, 0, ((size_t)n * kFineN + (size_t)n * 4) * 4, stream);
+    const BandLayout L = band_layout((size_t)n, (size_t)mcap, p.mask == nullptr);
+    uint2* lists = ws_ptr<uint2>(ws, L.lists);
+    uint32_t *nfine = ws_ptr<uint32_t>(ws, L.nfine), *list_len = ws_ptr<uint32_t>(ws, L.list_len), *flags = ws_ptr<uint32_t>(ws, L.flags);
+    uint8_t* mask_ws = ws_ptr<uint8_t>(ws, L.mask);
+    hipError_t e = hipMemsetAsync(nfine, 0, L.mask - L.nfine, stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(band_codes_kernel, dim3((unsigned)((mcap + 4095) / 4096), (unsigned)n), dim3(1024), 0, stream, p, lists,
                        list_len, nfine, flags, mask_ws, mcap);
@@ -892,11 +885,9 @@ size_t tile_ws_bytes_per_pair(const FilterParams& p, int mcap, bool need_mask)
         const TileGeom g = tile_geom(p, s);
         max_tiles = g.tiles_y * g.tiles_x > max_tiles ? g.tiles_y * g.tiles_x : max_tiles;
     }
-    return (size_t)max_tiles * mcap * 8 + (size_t)kFineN * 4 + kMaxTiles * 4 + 32 + 4 + 32 + (size_t)mcap + (need_mask ? (size_t)mcap : 0) + 64;
+    return tile_bytes_per_pair((size_t)max_tiles, (size_t)mcap, need_mask);
 }
 
-// ws layout for n pairs: lists [n][tiles][mcap] uint2 | nfine [n][1600] | list_len [n][32] | cnt [n][8] | flags [n] |
-//                        state [2][n][4] | rotmask [n][mcap] u8 | bestmask [n][mcap] u8 (if p.mask is null)
 hipError_t launch_filter_tiles(const FilterParams& p, int mcap, void* ws, const uint32_t** flags_out, hipStream_t stream)
 {
     const int n = p.n_pairs;
@@ -908,15 +899,12 @@ hipError_t launch_filter_tiles(const FilterParams& p, int mcap, void* ws, const 
         if (g.tiles_y * g.tiles_x > kMaxTiles || g.own_r < 1 || g.own_c < 1) return hipErrorInvalidValue;
         max_tiles = g.tiles_y * g.tiles_x > max_tiles ? g.tiles_y * g.tiles_x : max_tiles;
     }
-    uint2* lists = reinterpret_cast<uint2*>(ws);
-    uint32_t* nfine = reinterpret_cast<uint32_t*>(lists + (size_t)n * max_tiles * mcap);
-    uint32_t* list_len = nfine + (size_t)n * kFineN;
-    uint32_t* cnt = list_len + (size_t)n * kMaxTiles;
-    uint32_t* flags = cnt + (size_t)n * 8;
-    uint32_t* state = flags + n;  // two arrays of n x 4, used alternately
-    uint8_t* rotmask = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(state + (size_t)n * 8) + 15) & ~(uintptr_t)15);  // read 16 bytes at a time
-    uint8_t* bestmask = rotmask + (size_t)n * mcap;
-    hipError_t e = hipMemsetAsync(flags, 0, (size_t)n * 9 * 4, stream);  // flags + both states
+    const TileLayout L = tile_layout((size_t)n, (size_t)max_tiles, (size_t)mcap, p.mask == nullptr);
+    uint2* lists = ws_ptr<uint2>(ws, L.lists);
+    uint32_t *nfine = ws_ptr<uint32_t>(ws, L.nfine), *list_len = ws_ptr<uint32_t>(ws, L.list_len), *cnt = ws_ptr<uint32_t>(ws, L.cnt);
+    uint32_t *flags = ws_ptr<uint32_t>(ws, L.flags), *state = ws_ptr<uint32_t>(ws, L.state);
+    uint8_t *rotmask = ws_ptr<uint8_t>(ws, L.rotmask), *bestmask = ws_ptr<uint8_t>(ws, L.bestmask);
+    hipError_t e = hipMemsetAsync(flags, 0, L.state_end - L.flags, stream);
     if (e != hipSuccess) return e;
     if (p.mask == nullptr) {
         e = hipMemsetAsync(bestmask, 0, (size_t)n * mcap, stream);
@@ -926,7 +914,7 @@ hipError_t launch_filter_tiles(const FilterParams& p, int mcap, void* ws, const 
     for (int s = 0; s < n_scales; ++s) {
         const TileGeom g = tile_geom(p, s);
         const int n_tiles = g.tiles_y * g.tiles_x;
-        e = hipMemsetAsync(nfine, 0, ((size_t)n * kFineN + (size_t)n * kMaxTiles + (size_t)n * 8) * 4, stream);  // histogram, list lengths, counts
+        e = hipMemsetAsync(nfine, 0, L.flags - L.nfine, stream);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(tile_codes_kernel, dim3((unsigned)((mcap + 4095) / 4096), (unsigned)n), dim3(1024), 0, stream, p, g, lists,
                            list_len, nfine, flags, rotmask, mcap);

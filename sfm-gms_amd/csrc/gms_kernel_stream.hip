@@ -50,7 +50,6 @@
 #endif
 
 namespace gms {
-static size_t align16s(size_t x) { return (x + 15) & ~(size_t)15; }
 namespace {
 
 constexpr int kSMaxMatches = 1 << 16;                      // (an entry holds 26 bits of original index; beyond 65 536 matches the 16-bit band / tile kernels are the better fit: entries above 255 get likely)
@@ -71,9 +70,8 @@ constexpr int kSItemsScales = 4 * (7 + 3 + 1);             // (scale, grid type,
                                                            // 14 x 14 grids ride on the 20 x 20 and 28 x 28 items)
 constexpr int kSRowBuckets = 41;                           // 40 half rows of the left grid (2 x row of grid type 1 + the y parity) + "binned under no grid type":
                                                            // the rows a band holds under ANY grid type are a range of half rows
-constexpr int kSRowWords = 192;                            // per pair: [h] matches per bucket; [64 + h] fill cursors; [128 + h] first entry of bucket h
 constexpr int kSMarkTile = 8192;                           // matches per workgroup of the marking / compacting kernels
-constexpr int kSTilesMax = kSMaxMatches / kSMarkTile;      // 8
+static_assert(kSTilesMax == kSMaxMatches / kSMarkTile, "ws_layout.h holds the tiles of a pair");
 
 struct StreamWs {
     uint2* entries;      // [n][mcap], sorted by left row
@@ -1474,21 +1472,18 @@ static bool stream_plain_on()
     return on;
 }
 
-size_t stream_dense_ws_bytes_per_pair(int mcap) { return (size_t)mcap * 4 + 4 * (size_t)kLeftN * 2 + 4 + 64; }
+size_t stream_dense_ws_bytes_per_pair(int mcap) { return stream_dense_bytes_per_pair((size_t)mcap); }
 
-// ws layout for n pairs: codes [n][mcap] u32 | nleft [n][4][400] u16 | flags [n]; *flags_out marks the pairs left to launch_filter_big (bit 1)
+// *flags_out marks the pairs left to launch_filter_big (bit 1)
 hipError_t launch_filter_stream_dense(const FilterParams& p, int mcap, void* ws, const uint32_t** flags_out, hipStream_t stream)
 {
     const int n = p.n_pairs;
     if (n <= 0) return hipSuccess;
     if (p.right_w[0] != 20 || p.right_h[0] != 20 || p.with_scale) return hipErrorInvalidValue;
-    char* q = reinterpret_cast<char*>(ws);
-    uint32_t* codes = reinterpret_cast<uint32_t*>(q);
-    q += align16s((size_t)n * mcap * 4);
-    uint16_t* nleft = reinterpret_cast<uint16_t*>(q);
-    q += align16s((size_t)n * 4 * kLeftN * 2);
-    uint32_t* flags = reinterpret_cast<uint32_t*>(q);
-    hipError_t e = hipMemsetAsync(flags, 0, (size_t)n * 4, stream);
+    const StreamDenseLayout L = stream_dense_layout((size_t)n, (size_t)mcap);
+    uint32_t *codes = ws_ptr<uint32_t>(ws, L.codes), *flags = ws_ptr<uint32_t>(ws, L.flags);
+    uint16_t* nleft = ws_ptr<uint16_t>(ws, L.nleft);
+    hipError_t e = hipMemsetAsync(flags, 0, L.total - L.flags, stream);
     if (e != hipSuccess) return e;
     if (p.with_rotation) hipLaunchKernelGGL(stream_dense_kernel<true>, dim3((unsigned)n), dim3(1024), kDSLdsBytes, stream, p, codes, nleft, flags, mcap);
     else if (stream_plain_on()) hipLaunchKernelGGL(stream_plain_kernel, dim3((unsigned)n), dim3(1024), kSPLdsBytes, stream, p, codes, nleft, flags, mcap);
@@ -1515,13 +1510,10 @@ int stream_max_matches() { return kSMaxMatches; }
 
 size_t stream_ws_bytes_per_pair(const FilterParams& p, int mcap, bool)
 {
-    const size_t n_scales = p.with_scale ? 5 : 1;
-    return (size_t)mcap * 16 + (size_t)kFineN * 4 + (size_t)kSRowWords * 4 + 4 * (size_t)kLeftN * 2 + 5 * 8 * 4 + (size_t)kSTilesMax * 5 * 8 * 4 + 4 +
-           4 * n_scales * (size_t)kLeftN * 4 + 128;  // (+ the alignment of the arrays of a slice)
+    return stream_bytes_per_pair((size_t)mcap, p.with_scale ? 5 : 1);
 }
 
-// ws layout for n pairs: entries | codes | nfine | row_cnt | counts | flags | tile_cnt | tables | nleft; *flags_out marks the pairs left
-// to launch_filter_big (bit 1)
+// *flags_out marks the pairs left to launch_filter_big (bit 1)
 hipError_t launch_filter_stream(const FilterParams& p, int mcap, void* ws, const uint32_t** flags_out, hipStream_t stream)
 {
     const int n = p.n_pairs;
@@ -1530,28 +1522,11 @@ hipError_t launch_filter_stream(const FilterParams& p, int mcap, void* ws, const
     static const int kGrid[5] = {20, 10, 14, 28, 40};  // the right grids the kernels are written for (setScale, DLL@0x180048c10)
     for (int s = 0; s < n_scales; ++s)
         if (p.right_w[s] != kGrid[s] || p.right_h[s] != kGrid[s]) return hipErrorInvalidValue;
-    StreamWs w;
-    char* q = reinterpret_cast<char*>(ws);
-    w.entries = reinterpret_cast<uint2*>(q);
-    q += align16s((size_t)n * mcap * 8);
-    w.codes = reinterpret_cast<uint2*>(q);
-    q += align16s((size_t)n * mcap * 8);
-    char* zero_from = q;  // the histograms, counters and flags start at zero (tables and tile counts do not need to: every word has one writer)
-    w.nfine = reinterpret_cast<uint32_t*>(q);
-    q += (size_t)n * kFineN * 4;
-    w.row_cnt = reinterpret_cast<uint32_t*>(q);
-    q += (size_t)n * kSRowWords * 4;
-    w.counts = reinterpret_cast<uint32_t*>(q);
-    q += (size_t)n * 5 * 8 * 4;
-    w.flags = reinterpret_cast<uint32_t*>(q);
-    q += align16s((size_t)n * 4);
-    char* zero_to = q;
-    w.tile_cnt = reinterpret_cast<uint32_t*>(q);
-    q += (size_t)n * kSTilesMax * 5 * 8 * 4;
-    w.tables = reinterpret_cast<uint32_t*>(q);
-    q += align16s((size_t)n * n_scales * 4 * kLeftN * 4);
-    w.nleft = reinterpret_cast<uint16_t*>(q);
-    hipError_t e = hipMemsetAsync(zero_from, 0, (size_t)(zero_to - zero_from), stream);
+    const StreamLayout L = stream_layout((size_t)n, (size_t)mcap, (size_t)n_scales);
+    const StreamWs w = {ws_ptr<uint2>(ws, L.entries),   ws_ptr<uint2>(ws, L.codes),     ws_ptr<uint32_t>(ws, L.nfine),
+                        ws_ptr<uint32_t>(ws, L.row_cnt), ws_ptr<uint16_t>(ws, L.nleft),  ws_ptr<uint32_t>(ws, L.counts),
+                        ws_ptr<uint32_t>(ws, L.tile_cnt), ws_ptr<uint32_t>(ws, L.flags), ws_ptr<uint32_t>(ws, L.tables)};
+    hipError_t e = hipMemsetAsync(w.nfine, 0, L.tile_cnt - L.nfine, stream);
     if (e != hipSuccess) return e;
     const dim3 ig((unsigned)((mcap + 4095) / 4096), (unsigned)n);
     hipLaunchKernelGGL(stream_index_kernel<0>, ig, dim3(1024), 0, stream, p, w, mcap);

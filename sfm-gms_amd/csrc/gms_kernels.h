@@ -6,11 +6,10 @@
 
 #include "gms.h"
 #include "logos_dict_core.h"
+#include "ws_layout.h"
 
 namespace gms {
 
-constexpr int kLeftW = 20, kLeftH = 20, kLeftN = 400;  // DLL@0x180046ac6: fixed 20 x 20 left grid
-constexpr int kFineW = 40, kFineN = 1600;                  // half-cell grid: carries all four grid types
 constexpr int kThreads = 1024;                         // one 16-wave workgroup per image pair
 constexpr size_t kLdsBytes = 160 * 1024;               // gfx950 LDS per CU (and per workgroup)
 // record handed from filter_kernel_dense_scales to filter_kernel: state, best count, best scale, best rotation, then one
@@ -148,11 +147,8 @@ hipError_t launch_detect(const uint8_t* d_images, int n_images, int w, int h, in
                          gms_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, hipStream_t stream);
 hipError_t launch_describe(const uint8_t* d_image, int w, int h, gms_keypoint* d_kp, int n, void* d_ws, uint8_t* d_desc, int32_t* d_status,
                            hipStream_t stream);
-// pyramid keypoint source (detect_kernels.hip): the same detector on every level of an image pyramid
-constexpr int kPyramidMaxLevels = 16;
-int        pyramid_level_sizes(int w, int h, int n_levels, int* widths, int* heights);
+// pyramid keypoint source (detect_kernels.hip): the same detector on every level of an image pyramid (level sizes: ws_layout.h)
 void       pyramid_quotas(const int* widths, const int* heights, int n, int max_keypoints, int* quotas);
-size_t     pyramid_bytes(int w, int h, int n_images, int n_levels);
 size_t     detect_pyramid_workspace_bytes(int w, int h, int n_images, int max_keypoints, int n_levels);
 hipError_t launch_pyramid_build(const uint8_t* d_images, int n_images, int w, int h, int n_levels, uint8_t* d_levels, hipStream_t stream);
 hipError_t launch_detect_pyramid(const uint8_t* d_images, int n_images, int w, int h, int threshold, int max_keypoints, int n_levels, void* d_ws,

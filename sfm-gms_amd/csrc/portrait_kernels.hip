@@ -31,39 +31,13 @@ namespace {
 constexpr int kTX = 64, kTY = 16, kBlock = 256;
 constexpr int kSelBlock = 1024;
 
-constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// the workspace: mask | neighbour codes | frame flags | selected, one byte per pixel each; labels, int32 per pixel; toggles, 64 bits
-// per pixel; the borders' rank keys, 64 bits each, pm_key_cap per image; per image [0] chosen count, [1..64] chosen roots, [65] borders
+// the workspace's typed pointers (its regions: PortraitLayout in ws_layout.h)
 struct PmWs {
     uint8_t *mask, *nb, *flag, *sel;
     int32_t* label;
     unsigned long long *tog, *keys;
     int32_t* chosen;
 };
-constexpr int kChosenStride = 2 + pm::kMaxContours;
-
-// Two pixels side by side are never both the root of a border, so a row holds at most (W + 1) / 2 of them. With equal values the two
-// are one component. Otherwise one is a hole's first pixel: the pixel above it is set (a zero there would be an earlier pixel of the
-// hole), and that pixel is 8-connected to the set pixel on either side of the hole's first pixel, so the set neighbour is not its
-// component's first pixel. tests/test_portrait_ref.py checks the bound on random masks.
-inline size_t pm_key_cap(int W, int H) { return (size_t)H * (size_t)((W + 1) / 2); }
-
-inline PmWs pm_ws(void* base, int n, int W, int H)
-{
-    char* b = static_cast<char*>(base);
-    const size_t px = (size_t)n * (size_t)W * (size_t)H;
-    PmWs w;
-    w.mask = reinterpret_cast<uint8_t*>(b);
-    w.nb = w.mask + align256(px);
-    w.flag = w.nb + align256(px);
-    w.sel = w.flag + align256(px);
-    w.label = reinterpret_cast<int32_t*>(w.sel + align256(px));
-    w.tog = reinterpret_cast<unsigned long long*>(w.label + align256(4 * px) / 4);
-    w.keys = w.tog + align256(8 * px) / 8;
-    w.chosen = reinterpret_cast<int32_t*>(w.keys + align256(8 * (size_t)n * pm_key_cap(W, H)) / 8);
-    return w;
-}
 
 __global__ void __launch_bounds__(kBlock)
 pm_mask_kernel(const uint8_t* __restrict__ disp, int64_t img_stride, int pitch, int W, int H, int threshold, int it,
@@ -371,12 +345,7 @@ hipError_t launch_median(const MedianArgs& a, int n, int channels, hipStream_t s
 
 }  // namespace
 
-size_t portrait_ws_bytes(int n, int W, int H)
-{
-    const size_t px = (size_t)n * (size_t)W * (size_t)H;
-    return 4 * align256(px) + align256(4 * px) + align256(8 * px) + align256(8 * (size_t)n * pm_key_cap(W, H)) +
-           align256((size_t)n * kChosenStride * 4);
-}
+size_t portrait_ws_bytes(int n, int W, int H) { return portrait_layout(n, W, H).total; }
 
 hipError_t launch_median_blur(const uint8_t* d_src, int n, int W, int H, int channels, int pitch, int ksize, uint8_t* d_dst,
                               hipStream_t stream)
@@ -391,7 +360,10 @@ hipError_t launch_portrait(const gms_portrait_params& p, const uint8_t* d_bgr, c
                            hipStream_t stream, hipEvent_t* ev)
 {
     if (n <= 0) return hipSuccess;
-    const PmWs ws = pm_ws(d_ws, n, W, H);
+    const PortraitLayout L = portrait_layout(n, W, H);
+    const PmWs ws = {ws_ptr<uint8_t>(d_ws, L.mask), ws_ptr<uint8_t>(d_ws, L.nb), ws_ptr<uint8_t>(d_ws, L.flag), ws_ptr<uint8_t>(d_ws, L.sel),
+                     ws_ptr<int32_t>(d_ws, L.label), ws_ptr<unsigned long long>(d_ws, L.tog), ws_ptr<unsigned long long>(d_ws, L.keys),
+                     ws_ptr<int32_t>(d_ws, L.chosen)};
     const int cap = (int)pm_key_cap(W, H);
     int stage = 0;
     // ev (diagnostic, NULL in production): GMS_PORTRAIT_STAGES + 1 events, one before the first launch and one after each

@@ -27,21 +27,6 @@ constexpr int kValBlock = 256;
 constexpr int kNormBlock = 1024;
 constexpr int kMaxW = GMS_STEREO_BM_MAX_WIDTH;
 
-constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// the workspace: pre-filtered images [n][2][H][W] (left, right) | costs of the winner-take-all step [n][H][W]
-struct SbmWs {
-    uint8_t* pre;
-    int32_t* cost;
-};
-
-inline SbmWs sbm_ws(void* base, int n, int W, int H)
-{
-    char* b = static_cast<char*>(base);
-    const size_t px = (size_t)n * (size_t)W * (size_t)H;
-    return SbmWs{reinterpret_cast<uint8_t*>(b), reinterpret_cast<int32_t*>(b + align256(2 * px))};
-}
-
 __global__ void __launch_bounds__(kPfBlock)
 sbm_prefilter_kernel(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right, int64_t pair_stride, int pitch, int W, int H,
                      int cap, uint8_t* __restrict__ pre)
@@ -308,31 +293,29 @@ hipError_t launch_match(const MatchArgs& a, int n, hipStream_t stream)
 
 }  // namespace
 
-size_t stereo_bm_ws_bytes(int n, int W, int H)
-{
-    const size_t px = (size_t)n * (size_t)W * (size_t)H;
-    return align256(2 * px) + align256(4 * px);
-}
+size_t stereo_bm_ws_bytes(int n, int W, int H) { return stereo_bm_layout(n, W, H).total; }
 
 hipError_t launch_stereo_bm(const gms_stereo_bm_params& p, const uint8_t* d_left, const uint8_t* d_right, int n, int W, int H, int pitch,
                             void* d_ws, int16_t* d_disp, int32_t* d_cost, hipStream_t stream)
 {
     if (n <= 0) return hipSuccess;
     const sbm::Geometry g = sbm::geometry(p, W);
-    const SbmWs ws = sbm_ws(d_ws, n, W, H);
+    const StereoBmLayout L = stereo_bm_layout(n, W, H);
+    uint8_t* pre = ws_ptr<uint8_t>(d_ws, L.pre);
+    int32_t* cost = ws_ptr<int32_t>(d_ws, L.cost);
     if (!g.none) {
         hipLaunchKernelGGL(sbm_prefilter_kernel, dim3((uint32_t)((W + kPfX - 1) / kPfX), (uint32_t)((H + kPfY - 1) / kPfY), (uint32_t)(2 * n)),
-                           dim3(kPfBlock), 0, stream, d_left, d_right, (int64_t)pitch * H, pitch, W, H, p.pre_filter_cap, ws.pre);
+                           dim3(kPfBlock), 0, stream, d_left, d_right, (int64_t)pitch * H, pitch, W, H, p.pre_filter_cap, pre);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        MatchArgs a{ws.pre, d_disp, ws.cost, W, H, p.num_disparities, p.min_disparity, g.w2, p.pre_filter_cap, p.texture_threshold,
+        MatchArgs a{pre, d_disp, cost, W, H, p.num_disparities, p.min_disparity, g.w2, p.pre_filter_cap, p.texture_threshold,
                     p.uniqueness_ratio, g.lofs, g.rofs, g.wx, g.filtered};
         const int nd = p.num_disparities;
         e = nd <= 64 ? launch_match<1>(a, n, stream) : nd <= 128 ? launch_match<2>(a, n, stream)
             : nd <= 256 ? launch_match<4>(a, n, stream) : launch_match<8>(a, n, stream);
         if (e != hipSuccess) return e;
     }
-    ValArgs v{d_disp, ws.cost, d_cost, W, H, g.w2, g.lofs, g.wx, g.none, g.filtered, p.disp12_max_diff, g.minX1, g.maxX1, g.roi_x0, g.roi_x1};
+    ValArgs v{d_disp, cost, d_cost, W, H, g.w2, g.lofs, g.wx, g.none, g.filtered, p.disp12_max_diff, g.minX1, g.maxX1, g.roi_x0, g.roi_x1};
     hipLaunchKernelGGL(sbm_validate_kernel, dim3((uint32_t)H, (uint32_t)n), dim3(kValBlock), 0, stream, v);
     return hipGetLastError();
 }

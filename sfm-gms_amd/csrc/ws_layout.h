@@ -1,0 +1,258 @@
+// ws_layout.h -- the device workspaces the launchers work in: for each one, ONE list of its regions in order, which gives both the
+// workspace's size (`total`) and the offset of every region. The size functions return the total; the launchers take every pointer
+// they hand to a kernel, and every span they clear, from the same struct. Offsets count from the workspace's start, which is 256-byte
+// aligned (the C ABI refuses other caller workspaces; the context's own come from hipMalloc).
+//
+// Plain arithmetic and no HIP header, so that a host compiler builds it alone: tests/cpp/ws_layout_check.cpp sweeps every layout
+// here for order, overlap, alignment and size.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "gms.h"
+#include "portrait_core.h"
+
+namespace gms {
+
+constexpr int kLeftW = 20, kLeftH = 20, kLeftN = 400;  // DLL@0x180046ac6: fixed 20 x 20 left grid
+constexpr int kFineW = 40, kFineN = 1600;                  // half-cell grid: carries all four grid types
+
+constexpr size_t round_up(size_t x, size_t a) { return (x + a - 1) & ~(a - 1); }  // a: a power of two
+
+template <typename T>
+T* ws_ptr(void* ws, size_t offset) { return reinterpret_cast<T*>(static_cast<char*>(ws) + offset); }
+
+// Hands out the consecutive regions of a workspace, in call order, and keeps count of the bytes that only round something up.
+struct WsCursor {
+    size_t end = 0, padding = 0;
+    // the offset of a new region of `bytes` bytes whose length is rounded up to a multiple of `pad`
+    size_t take(size_t bytes, size_t pad = 1)
+    {
+        const size_t at = end;
+        end += round_up(bytes, pad);
+        padding += round_up(bytes, pad) - bytes;
+        return at;
+    }
+    // the next region starts on a multiple of `a`
+    void align(size_t a)
+    {
+        padding += round_up(end, a) - end;
+        end = round_up(end, a);
+    }
+};
+
+// ---- the keypoint source (detect_kernels.hip) ---------------------------------------------------------------------------------------
+struct DetectLayout {
+    size_t score;  // uint8 [n][h][w]
+    size_t cand;   // uint8 [n][h][w]
+    size_t box;    // uint16 [n][h][w]: box sums
+    size_t hist;   // uint32 [n][256]: score histogram
+    size_t cut;    // int32 [n][4]. The single-scale call zeroes [hist, cut) first
+    size_t rows;   // [n][h], 8 bytes each: row counts
+    size_t list;   // [n][max_keypoints], 8 bytes each
+    size_t total;
+};
+inline DetectLayout detect_layout(int w, int h, int n_images, int max_keypoints)
+{
+    const size_t n = (size_t)n_images, plane = (size_t)w * h;
+    WsCursor c;
+    return {c.take(plane * n, 256), c.take(plane * n, 256), c.take(plane * n * 2, 256), c.take(n * 256 * 4), c.take(n * 16),
+            c.take(n * h * 8, 256), c.take(n * max_keypoints * 8, 256), c.end};
+}
+
+// The pyramid: level 0 is the image; w_l = (5 w_{l-1} + 3) / 6, the same for h; the levels end at n_levels or before the first one the
+// detector refuses (width or height <= 32). Returns the number of levels (0: level 0 itself is refused).
+constexpr int kPyramidMaxLevels = 16;
+constexpr int kBorder = 16;  // the detector keeps this far from the image's edge
+inline int pyramid_level_sizes(int w, int h, int n_levels, int* widths, int* heights)
+{
+    int n = 0;
+    while (n < n_levels && n < kPyramidMaxLevels && w > 2 * kBorder && h > 2 * kBorder && w <= 65535 && h <= 65535) {
+        widths[n] = w; heights[n] = h;
+        ++n;
+        w = (5 * w + 3) / 6; h = (5 * h + 3) / 6;
+    }
+    return n;
+}
+// bytes of levels 1 .. n - 1 of n_images images, level after level, the images of a level back to back, nothing between them
+inline size_t pyramid_bytes(int w, int h, int n_images, int n_levels)
+{
+    int ww[kPyramidMaxLevels], hh[kPyramidMaxLevels];
+    const int n = pyramid_level_sizes(w, h, n_levels, ww, hh);
+    size_t b = 0;
+    for (int l = 1; l < n; ++l) b += (size_t)ww[l] * hh[l] * (size_t)(n_images > 0 ? n_images : 0);
+    return b;
+}
+// Every call zeroes [counts, detect) first (the counts too: a level with quota 0 is not run).
+struct PyramidLayout {
+    size_t levels;  // uint8: the level images 1 .., pyramid_bytes of them
+    size_t counts;  // int32 [kPyramidMaxLevels][n]: keypoints per level and image
+    size_t hists;   // uint32 [kPyramidMaxLevels][n][256]: the levels' score histograms
+    size_t detect;  // the single-scale workspace of level 0: every level fits into it in its turn
+    size_t total;
+};
+inline PyramidLayout pyramid_layout(int w, int h, int n_images, int max_keypoints, int n_levels)
+{
+    const size_t n = (size_t)n_images;
+    WsCursor c;
+    return {c.take(pyramid_bytes(w, h, n_images, n_levels), 256), c.take(kPyramidMaxLevels * n * 4, 256), c.take(kPyramidMaxLevels * n * 256 * 4),
+            c.end, c.end + detect_layout(w, h, n_images, max_keypoints).total};
+}
+
+// ---- large pairs, per slice of n pairs of the context's own workspace (gms_kernel_band.hip, gms_kernel_stream.hip) ------------------
+// plan_workspace sizes a slice as n * bytes per pair: the regions of one pair, plus a slack that covers what the layout of n pairs
+// rounds up (`padding`; every round-up here is to 16 bytes, so it adds less than 16).
+constexpr size_t kAlignPadMax = 15;
+
+// default flags: three-band lists
+struct BandLayout {
+    size_t lists;     // uint2 [n][3][mcap]
+    size_t nfine;     // uint32 [n][1600]: half-cell histogram. Every launch zeroes [nfine, mask) first
+    size_t list_len;  // uint32 [n][3]
+    size_t flags;     // uint32 [n]
+    size_t mask;      // uint8 [n][mcap], when the caller gives no mask
+    size_t total, padding;
+};
+inline BandLayout band_layout(size_t n, size_t mcap, bool need_mask)
+{
+    WsCursor c;
+    return {c.take(n * 3 * mcap * 8), c.take(n * kFineN * 4), c.take(n * 3 * 4), c.take(n * 4), c.take(need_mask ? n * mcap : 0), c.end, c.padding};
+}
+inline size_t band_bytes_per_pair(size_t mcap, bool need_mask) { return band_layout(1, mcap, need_mask).total; }  // (nothing is rounded)
+
+// rotation / scale hypotheses: tiled lists; max_tiles = the most tiles of any scale's TileGeom
+constexpr int kMaxTiles = 32;
+struct TileLayout {
+    size_t lists;     // uint2 [n][max_tiles][mcap]
+    size_t nfine;     // uint32 [n][1600]. Every scale zeroes [nfine, flags) first: histogram, list lengths, counts
+    size_t list_len;  // uint32 [n][kMaxTiles]
+    size_t cnt;       // uint32 [n][8]: inliers per rotation
+    size_t flags;     // uint32 [n]. Every launch zeroes [flags, state_end) first: the flags and both states
+    size_t state;     // uint32 [2][n][4], the two used alternately
+    size_t state_end;
+    size_t rotmask;   // uint8 [n][mcap], on a 16-byte boundary: read 16 bytes at a time
+    size_t bestmask;  // uint8 [n][mcap], when the caller gives no mask
+    size_t total, padding;
+};
+inline TileLayout tile_layout(size_t n, size_t max_tiles, size_t mcap, bool need_mask)
+{
+    WsCursor c;
+    const size_t lists = c.take(n * max_tiles * mcap * 8), nfine = c.take(n * kFineN * 4), list_len = c.take(n * kMaxTiles * 4), cnt = c.take(n * 8 * 4),
+                 flags = c.take(n * 4), state = c.take(2 * n * 4 * 4), state_end = c.end;
+    c.align(16);
+    return {lists, nfine, list_len, cnt, flags, state, state_end, c.take(n * mcap), c.take(need_mask ? n * mcap : 0), c.end, c.padding};
+}
+constexpr size_t kTileSlack = 64;
+static_assert(kTileSlack >= 1 * kAlignPadMax, "the slack covers the tile layout's one round-up");
+inline size_t tile_bytes_per_pair(size_t max_tiles, size_t mcap, bool need_mask)
+{
+    const TileLayout one = tile_layout(1, max_tiles, mcap, need_mask);
+    return one.total - one.padding + kTileSlack;
+}
+
+// pairs up to 65 536 matches, every flag combination: the streamed byte matrix
+constexpr int kSRowWords = 192;  // per pair: [h] matches per bucket; [64 + h] fill cursors; [128 + h] first entry of bucket h
+constexpr int kSTilesMax = 8;    // tiles of the marking / compacting kernels per pair
+// Every launch zeroes [nfine, tile_cnt) first: the histograms, counters and flags start at zero (tables and tile counts need not:
+// every word has one writer).
+struct StreamLayout {
+    size_t entries;   // uint2 [n][mcap], sorted by left row
+    size_t codes;     // uint2 [n][mcap], the same words in the matches' original order
+    size_t nfine;     // uint32 [n][1600]: half-cell histogram
+    size_t row_cnt;   // uint32 [n][kSRowWords]
+    size_t counts;    // uint32 [n][5][8]
+    size_t flags;     // uint32 [n]
+    size_t tile_cnt;  // uint32 [n][kSTilesMax][5][8]
+    size_t tables;    // uint32 [n][scales][4][400]
+    size_t nleft;     // uint16 [n][4][400]
+    size_t total, padding;
+};
+inline StreamLayout stream_layout(size_t n, size_t mcap, size_t n_scales)
+{
+    WsCursor c;  // (the regions rounded to 16 keep every region of a slice 16-byte aligned)
+    return {c.take(n * mcap * 8, 16), c.take(n * mcap * 8, 16), c.take(n * kFineN * 4), c.take(n * kSRowWords * 4), c.take(n * 5 * 8 * 4),
+            c.take(n * 4, 16), c.take(n * kSTilesMax * 5 * 8 * 4), c.take(n * n_scales * 4 * kLeftN * 4, 16), c.take(n * 4 * kLeftN * 2), c.end,
+            c.padding};
+}
+constexpr size_t kStreamSlack = 128;
+static_assert(kStreamSlack >= 4 * kAlignPadMax, "the slack covers the stream layout's four round-ups");
+inline size_t stream_bytes_per_pair(size_t mcap, size_t n_scales)
+{
+    const StreamLayout one = stream_layout(1, mcap, n_scales);
+    return one.total - one.padding + kStreamSlack;
+}
+
+// the same size class without scale hypotheses: one workgroup per pair
+struct StreamDenseLayout {
+    size_t codes;  // uint32 [n][mcap]
+    size_t nleft;  // uint16 [n][4][400]
+    size_t flags;  // uint32 [n], zeroed by every launch
+    size_t total, padding;
+};
+inline StreamDenseLayout stream_dense_layout(size_t n, size_t mcap)
+{
+    WsCursor c;
+    return {c.take(n * mcap * 4, 16), c.take(n * 4 * kLeftN * 2, 16), c.take(n * 4), c.end, c.padding};
+}
+constexpr size_t kStreamDenseSlack = 64;
+static_assert(kStreamDenseSlack >= 2 * kAlignPadMax, "the slack covers the dense stream layout's two round-ups");
+inline size_t stream_dense_bytes_per_pair(size_t mcap)
+{
+    const StreamDenseLayout one = stream_dense_layout(1, mcap);
+    return one.total - one.padding + kStreamDenseSlack;
+}
+
+// ---- StereoBM (stereo_bm_kernels.hip) -----------------------------------------------------------------------------------------------
+struct StereoBmLayout {
+    size_t pre;   // uint8 [n][2][H][W]: the pre-filtered images (left, right)
+    size_t cost;  // int32 [n][H][W]: costs of the winner-take-all step
+    size_t total;
+};
+inline StereoBmLayout stereo_bm_layout(int n, int W, int H)
+{
+    const size_t px = (size_t)n * (size_t)W * (size_t)H;
+    WsCursor c;
+    return {c.take(2 * px, 256), c.take(4 * px, 256), c.end};
+}
+
+// ---- portrait mode (portrait_kernels.hip) -------------------------------------------------------------------------------------------
+// Two pixels side by side are never both the root of a border, so a row holds at most (W + 1) / 2 of them. With equal values the two
+// are one component. Otherwise one is a hole's first pixel: the pixel above it is set (a zero there would be an earlier pixel of the
+// hole), and that pixel is 8-connected to the set pixel on either side of the hole's first pixel, so the set neighbour is not its
+// component's first pixel. tests/test_portrait_ref.py checks the bound on random masks.
+inline size_t pm_key_cap(int W, int H) { return (size_t)H * (size_t)((W + 1) / 2); }
+constexpr int kChosenStride = 2 + pm::kMaxContours;
+struct PortraitLayout {
+    size_t mask, nb, flag, sel;  // uint8 [n][H][W] each: mask, neighbour codes, frame flags, selected
+    size_t label;                // int32 [n][H][W]
+    size_t tog;                  // uint64 [n][H][W]: toggles
+    size_t keys;                 // uint64 [n][pm_key_cap]: the borders' rank keys
+    size_t chosen;               // int32 [n][kChosenStride]: [0] chosen count, [1..64] chosen roots, [65] borders
+    size_t total;
+};
+inline PortraitLayout portrait_layout(int n, int W, int H)
+{
+    const size_t px = (size_t)n * (size_t)W * (size_t)H;
+    WsCursor c;
+    return {c.take(px, 256), c.take(px, 256), c.take(px, 256), c.take(px, 256), c.take(4 * px, 256), c.take(8 * px, 256),
+            c.take(8 * (size_t)n * pm_key_cap(W, H), 256), c.take((size_t)n * kChosenStride * 4, 256), c.end};
+}
+
+// ---- bruteForceMatch's selection (bf_select_kernels.hip) ----------------------------------------------------------------------------
+struct BfSelectLayout {
+    size_t pairs2;  // gms_pair [n_pairs]: the matcher's pair table
+    size_t back;    // gms_dmatch [total_back]: the matcher's output
+    size_t qt;      // uint64 [n_pairs][max_rows]: (q, t) / slots
+    size_t cd;      // float [n_pairs][max_rows]: d
+    size_t cix;     // int32 [n_pairs][max_rows]: ix
+    size_t total;
+};
+inline BfSelectLayout bf_select_layout(int n_pairs, int64_t max_rows, int64_t total_back)
+{
+    const size_t rows = (size_t)n_pairs * (size_t)max_rows;
+    WsCursor c;
+    return {c.take(sizeof(gms_pair) * (size_t)n_pairs, 256), c.take(sizeof(gms_dmatch) * (size_t)total_back, 256), c.take(8 * rows, 256),
+            c.take(4 * rows, 256), c.take(4 * rows, 256), c.end};
+}
+
+}  // namespace gms

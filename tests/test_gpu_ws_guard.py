@@ -1,0 +1,170 @@
+"""-m gpu: the six entry points that work in a caller's workspace -- detect, describe, detect-pyramid, stereo_bm, portrait and
+bf_select `_device` -- given EXACTLY gms_*_workspace_bytes: the workspace is the 256-byte aligned start of a buffer filled with
+0x5A that is 4096 bytes longer. The result equals what the entry point's own test expects (the same CPU statements), and the 4096
+bytes behind the workspace still hold 0x5A: a layout (sfm-gms_amd/csrc/ws_layout.h) whose total is smaller than what its launcher
+walks would write there. Three images or pairs with sides just above each entry point's minimum, so that no region's size is a
+multiple of its alignment."""
+import importlib
+
+import numpy as np
+import pytest
+
+import bf_select_ref
+import portrait_ref
+import pyramid_ref
+import stereo_bm_ref
+
+pytestmark = pytest.mark.gpu
+GUARD, FILL = 4096, 0x5A
+W, H, MAX_KP = 35, 33, 7
+
+
+def _batch():
+    return importlib.import_module("sfm-gms_amd.batch")
+
+
+class Guarded:
+    """A workspace of exactly `ws_bytes` in front of GUARD bytes that nothing may touch."""
+
+    def __init__(self, ws_bytes):
+        import torch
+        assert ws_bytes > 0
+        self.buf = torch.full((ws_bytes + GUARD,), FILL, dtype=torch.uint8, device="cuda:0")
+        assert self.buf.data_ptr() % 256 == 0
+        self.ws, self.ws_bytes = self.buf[:ws_bytes], ws_bytes
+        torch.cuda.synchronize()
+
+    def check(self):
+        assert bool((self.buf[self.ws_bytes:] == FILL).all()), "the entry point wrote behind its workspace"
+
+
+# 35 x 33 is the smallest image the detector accepts (three pixels can hold a keypoint, and the pyramid has no second level); 47 x 41
+# is the smallest whose second level (39 x 34) it accepts too
+SIZES = [(35, 33), (47, 41)]
+
+
+def _images(w, h):
+    return np.random.default_rng(2).integers(0, 256, (3, h, w), dtype=np.uint8)   # noise: every image has a keypoint at both sizes
+
+
+@pytest.mark.parametrize("W,H", SIZES)
+def test_detect(ctx, oracle, W, H):
+    import torch
+    imgs = _images(W, H)
+    g = Guarded(ctx.detect_workspace_bytes(W, H, 3, MAX_KP))
+    d_imgs = torch.from_numpy(imgs).cuda()
+    d_kp = torch.zeros(3 * MAX_KP * 28, dtype=torch.uint8, device="cuda:0")
+    d_desc = torch.zeros(3 * MAX_KP * 32, dtype=torch.uint8, device="cuda:0")
+    d_counts = torch.zeros(3, dtype=torch.int32, device="cuda:0")
+    torch.cuda.synchronize()
+    ctx.detect_batch_device(d_imgs.data_ptr(), 3, W, H, 10, MAX_KP, g.ws.data_ptr(), g.ws_bytes, d_kp.data_ptr(), d_desc.data_ptr(), d_counts.data_ptr())
+    ctx.synchronize()
+    kps, rows = _batch()._detected(d_kp, d_desc, d_counts, 3, MAX_KP)
+    for i in range(3):
+        want_kp, want_rows = oracle.detect(imgs[i], 10, MAX_KP)
+        assert kps[i].tobytes() == want_kp.tobytes() and rows[i].tobytes() == want_rows.tobytes(), i
+    assert all(len(k) > 0 for k in kps)
+    g.check()
+
+
+def test_describe(ctx, pkg, oracle):
+    import torch
+    img = _images(W, H)[0]
+    b = pkg.GMS_DETECT_BORDER
+    xs, ys = np.meshgrid(np.arange(b, W - b), np.arange(b, H - b), indexing="ij")
+    kp = np.zeros(xs.size, dtype=pkg.KEYPOINT_DTYPE)
+    kp["x"], kp["y"], kp["size"] = xs.ravel(), ys.ravel(), 1.0
+    g = Guarded(ctx.detect_workspace_bytes(W, H, 1, 0))
+    d_img = torch.from_numpy(img).cuda()
+    d_kp = torch.from_numpy(kp.view(np.uint8)).cuda()
+    d_desc = torch.zeros(len(kp) * 32, dtype=torch.uint8, device="cuda:0")
+    d_status = torch.zeros(1, dtype=torch.int32, device="cuda:0")
+    torch.cuda.synchronize()
+    ctx.describe_device(d_img.data_ptr(), W, H, d_kp.data_ptr(), len(kp), g.ws.data_ptr(), g.ws_bytes, d_desc.data_ptr(), d_status.data_ptr())
+    ctx.synchronize()
+    rc, want_kp, want_rows = oracle.describe(img, kp)
+    assert int(d_status.item()) == 0 and rc == len(kp) > 0
+    assert d_kp.cpu().numpy().tobytes() == want_kp.tobytes() and d_desc.cpu().numpy().tobytes() == want_rows.tobytes()
+    g.check()
+
+
+@pytest.mark.parametrize("w,h", SIZES)
+def test_detect_pyramid(ctx, oracle, w, h):
+    import torch
+    n_levels = 2
+    imgs = _images(w, h)
+    assert len(pyramid_ref.level_sizes(w, h, n_levels)) == (2 if w > 35 else 1)
+    run = _batch().DetectPyramid(ctx, 3, w, h, 10, MAX_KP, n_levels)
+    g = Guarded(run.ws_bytes)
+    run.d_ws = g.ws
+    run.run(torch.from_numpy(imgs).cuda())
+    ctx.synchronize()
+    kps, rows, lc = run.results()
+    for i in range(3):
+        want_kp, want_rows, want_lc = pyramid_ref.detect(oracle, imgs[i], 10, MAX_KP, n_levels)
+        assert lc[i].tolist() == want_lc.tolist()
+        assert kps[i].tobytes() == want_kp.tobytes() and rows[i].tobytes() == want_rows.tobytes(), i
+    assert (lc.sum(axis=0)[:1 if w == 35 else 2] > 0).all()   # every level that exists gave keypoints
+    g.check()
+
+
+def test_stereo_bm(ctx):
+    import torch
+    rng = np.random.default_rng(4)
+    kw = dict(block_size=5, num_disparities=16, min_disparity=0, pre_filter_cap=61, texture_threshold=0, uniqueness_ratio=0, disp12_max_diff=1)
+    base = rng.integers(0, 256, (3, H, W + 8), dtype=np.uint8)
+    lefts, rights = np.ascontiguousarray(base[:, :, 8:]), np.ascontiguousarray(base[:, :, 5:W + 5])
+    run = _batch().StereoBM(ctx, 3, W, H, kw)
+    g = Guarded(run.ws_bytes)
+    run.d_ws = g.ws
+    run.run(torch.from_numpy(lefts).cuda(), torch.from_numpy(rights).cuda())
+    ctx.synchronize()
+    for i in range(3):
+        want_d, want_c = stereo_bm_ref.stereo_bm(lefts[i], rights[i], **kw)
+        assert run.d_disp[i].cpu().numpy().tobytes() == want_d.tobytes() and run.d_cost[i].cpu().numpy().tobytes() == want_c.tobytes(), i
+    g.check()
+
+
+def test_portrait(ctx):
+    import torch
+    rng = np.random.default_rng(5)
+    kw = dict(threshold=60, dilate_iterations=1, num_contours=5, median_ksize=7)
+    a = rng.random((3, H, W))
+    a = (a + np.roll(a, 1, 1) + np.roll(a, 1, 2) + np.roll(a, -1, 1) + np.roll(a, -1, 2)) / 5
+    disparity = np.where(a > 0.5, rng.integers(61, 255, a.shape), rng.integers(0, 61, a.shape)).astype(np.uint8)
+    imgs = rng.integers(0, 256, (3, H, W, 3), dtype=np.uint8)
+    run = _batch().Portrait(ctx, 3, W, H, kw)
+    g = Guarded(run.ws_bytes)
+    run.d_ws = g.ws
+    run.run(torch.from_numpy(imgs).cuda(), torch.from_numpy(disparity).cuda())
+    ctx.synchronize()
+    for i in range(3):
+        want = portrait_ref.portrait(imgs[i], disparity[i], **kw)
+        assert not portrait_ref.cut_is_tied(want["info"]["contours"], W, kw["num_contours"]), "the statement's condition on its inputs"
+        for name, got in (("out", run.d_out), ("mask", run.d_mask), ("selected", run.d_selected), ("blurred", run.d_blurred)):
+            assert got[i].cpu().numpy().tobytes() == want[name].tobytes(), (i, name)
+    g.check()
+
+
+@pytest.mark.parametrize("cross", [True, False])
+def test_bf_select(ctx, pkg, cross):
+    batch = _batch()
+    rng = np.random.default_rng(6)
+    rows = [rng.integers(0, 256, (37, 32), dtype=np.uint8) for _ in range(4)]
+    frames = batch.FrameTable(ctx, [np.zeros(37, pkg.KEYPOINT_DTYPE) for _ in rows], [(640, 480)] * 4)
+    descs = batch.DescriptorTable(ctx, frames, rows, 0)
+    fp = [(0, 1), (1, 2), (3, 0)]
+    job = batch.BfSelect(ctx, descs, batch.bf_select_table(descs, fp), cross)
+    g = Guarded(job.ws_bytes)
+    job.d_ws = g.ws
+    job.run()
+    ctx.synchronize()
+    out, res, _ = job.results()
+    for k, (a, b) in enumerate(fp):
+        q, t, d = bf_select_ref.candidates(rows[a], rows[b], True, cross)
+        want, n_ratio, dm = bf_select_ref.select(q, t, d, 4.0, 500)
+        off = int(job.recs["match_off"][k])
+        assert int(res["status"][k]) == 0 and int(res["n_out"][k]) == len(want) > 0
+        assert out[off:off + len(want)].tobytes() == want.tobytes(), (a, b)
+        assert (int(res["n_candidates"][k]), int(res["n_ratio"][k]), res["d_min"][k]) == (len(d), n_ratio, dm)
+    g.check()
