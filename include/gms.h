@@ -469,6 +469,30 @@ int gms_detect_pyramid_batch_device(gms_ctx* ctx, const uint8_t* d_images, int n
 int gms_pyramid_build_device(gms_ctx* ctx, const uint8_t* d_images, int n_images, int width, int height, int n_levels, uint8_t* d_levels,
                              size_t levels_bytes);
 
+/* ---- gradient descriptor: SIFT-format rows from the pyramid keypoint source (CPU statement
+ * tests/grad_desc_ref.py) -------------------------------------------------------------------------------------------------------
+ * Where the reference gets keypoints it gets 128-float SIFT rows with them (FeatureMatchUtil.cpp:9-12, DisparityUtil.cpp:101-133). These
+ * calls make rows of that structure and format at the detector's keypoints: 4 x 4 cells x 8 orientations of weighted gradient
+ * magnitude on the keypoint's own pyramid level, in the frame of its direction, normalised, clipped at 0.2, normalised again and
+ * scaled by 512: 128 fp32 values per keypoint, each an integer 0..255 -- what gms_bf_prepare_device(GMS_DESC_L2_F32X128) sends to its
+ * exact int8 path. NOT cv::SIFT: this library's own definition in integer arithmetic (no DoG detector, no equality with OpenCV's rows),
+ * so the rows are the same bytes on every run and equal the CPU statement.
+ *
+ * gms_detect_pyramid_grad_batch_device: gms_detect_pyramid_batch_device with one output more. Keypoints, 32-byte rows, counts and level
+ * counts are the bytes that call writes; image i's 128-float rows go to d_rows128[(i * max_keypoints ..) * 128] (8-byte aligned), in the
+ * keypoints' order. n_levels = 1 is the single-scale form. Same stream rule (nothing allocated, nothing waited for: can be captured) and
+ * same errors; the workspace has its own size function. */
+size_t gms_detect_pyramid_grad_workspace_bytes(int width, int height, int n_images, int max_keypoints, int n_levels);   /* 0: bad arguments */
+int gms_detect_pyramid_grad_batch_device(gms_ctx* ctx, const uint8_t* d_images, int n_images, int width, int height, int threshold,
+                                         int max_keypoints, int n_levels, void* d_workspace, size_t workspace_bytes, gms_keypoint* d_keypoints,
+                                         uint8_t* d_descriptors, int32_t* d_counts, int32_t* d_level_counts, float* d_rows128);
+
+/* Feature2D::compute with these rows on ONE image, the counterpart of gms_describe_device: direction (written to angle) and the
+ * 128-float row at each of the caller's n keypoints, on the image itself (level 0). The same status rule: a keypoint off the integer
+ * pixel grid or inside the border sets *d_status = 1 and keeps its row. Workspace: gms_detect_workspace_bytes(width, height, 1, 0). */
+int gms_describe_grad_device(gms_ctx* ctx, const uint8_t* d_image, int width, int height, gms_keypoint* d_keypoints, int n,
+                             void* d_workspace, size_t workspace_bytes, float* d_rows128, int32_t* d_status);
+
 /* ---- LOGOS match filter -----------------------------------------------------------------------
  * cv::xfeatures2d::matchLOGOS(keypoints1, keypoints2, nn1, nn2, matches1to2) (FeatureMatchUtil.cpp:86-131; DESIGN.md, LOGOS):
  * candidates are the pairs (i, j) with nn1[i] == nn2[j]; a candidate survives if it has local support among the five nearest

@@ -281,6 +281,20 @@ class GmsContext:
         _check(self._lib.gms_pyramid_build_device(self._h, d_images, int(n_images), int(width), int(height), int(n_levels), d_levels,
                                                   int(levels_bytes)), self._lib, "gms_pyramid_build_device")
 
+    # -- gradient descriptor: 128-float rows at the detector's keypoints (batch.detect_images_pyramid / describe_image drive them) -----
+    def detect_pyramid_grad_workspace_bytes(self, width, height, n_images, max_keypoints, n_levels):
+        return int(self._lib.gms_detect_pyramid_grad_workspace_bytes(int(width), int(height), int(n_images), int(max_keypoints), int(n_levels)))
+
+    def detect_pyramid_grad_batch_device(self, d_images, n_images, width, height, threshold, max_keypoints, n_levels, d_ws, ws_bytes, d_kp,
+                                         d_desc, d_counts, d_level_counts, d_rows128):
+        _check(self._lib.gms_detect_pyramid_grad_batch_device(self._h, d_images, int(n_images), int(width), int(height), int(threshold),
+                                                              int(max_keypoints), int(n_levels), d_ws, int(ws_bytes), d_kp, d_desc, d_counts,
+                                                              d_level_counts, d_rows128), self._lib, "gms_detect_pyramid_grad_batch_device")
+
+    def describe_grad_device(self, d_image, width, height, d_kp, n, d_ws, ws_bytes, d_rows128, d_status):
+        _check(self._lib.gms_describe_grad_device(self._h, d_image, int(width), int(height), d_kp, int(n), d_ws, int(ws_bytes), d_rows128,
+                                                  d_status), self._lib, "gms_describe_grad_device")
+
     # -- LOGOS on resident frames (gms_logos_*; batch.LogosTable / logos_pairs / logos_words drive them) ---------------------------
     def logos_table_bytes(self, total_kp, n_frames, n_words):
         return int(self._lib.gms_logos_table_bytes(int(total_kp), int(n_frames), int(n_words)))

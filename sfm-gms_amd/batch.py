@@ -211,15 +211,22 @@ def detect_images(ctx, images, threshold=20, max_keypoints=10000, device=None):
     return _detected(d_kp, d_desc, d_counts, n, max_keypoints)
 
 
+DESCRIPTORS = ("brief", "grad", "both")
+
+
 class DetectPyramid:
     """Device buffers of one gms_detect_pyramid_batch_device batch (n images of w x h), sized once, so that run() can be repeated or
-    captured into a graph: workspace, keypoints, rows, counts and per-level counts."""
+    captured into a graph: workspace, keypoints, rows, counts and per-level counts. descriptor: "brief" (the 32-byte rows), "grad" or
+    "both" (gms_detect_pyramid_grad_batch_device: the 128-float gradient rows as well, in d_rows128)."""
 
-    def __init__(self, ctx, n, w, h, threshold=20, max_keypoints=10000, n_levels=8, device=None):
-        self.ctx, self.n, self.w, self.h = ctx, int(n), int(w), int(h)
+    def __init__(self, ctx, n, w, h, threshold=20, max_keypoints=10000, n_levels=8, device=None, descriptor="brief"):
+        if descriptor not in DESCRIPTORS:
+            raise ValueError(f"descriptor must be one of {DESCRIPTORS}")
+        self.ctx, self.n, self.w, self.h, self.descriptor = ctx, int(n), int(w), int(h), descriptor
         self.threshold, self.max_keypoints, self.n_levels = int(threshold), int(max_keypoints), int(n_levels)
         dev = _device(ctx, device)
-        self.ws_bytes = ctx.detect_pyramid_workspace_bytes(w, h, n, max_keypoints, n_levels)
+        size = ctx.detect_pyramid_workspace_bytes if descriptor == "brief" else ctx.detect_pyramid_grad_workspace_bytes
+        self.ws_bytes = size(w, h, n, max_keypoints, n_levels)
         if self.ws_bytes == 0:
             raise ValueError("bad image size, keypoint count or number of levels")
         self.d_ws = torch.zeros(self.ws_bytes, dtype=torch.uint8, device=dev)
@@ -227,27 +234,39 @@ class DetectPyramid:
         self.d_desc = torch.zeros(max(self.n * self.max_keypoints, 1) * 32, dtype=torch.uint8, device=dev)
         self.d_counts = torch.zeros(self.n, dtype=torch.int32, device=dev)
         self.d_level_counts = torch.zeros(self.n * self.n_levels, dtype=torch.int32, device=dev)
+        self.d_rows128 = None if descriptor == "brief" else torch.zeros(max(self.n * self.max_keypoints, 1) * 128, dtype=torch.float32, device=dev)
         torch.cuda.synchronize(dev)
 
     def run(self, d_images):
         """Stream-ordered on the context's stream; d_images: uint8 device tensor [n, h, w], contiguous."""
-        self.ctx.detect_pyramid_batch_device(d_images.data_ptr(), self.n, self.w, self.h, self.threshold, self.max_keypoints, self.n_levels,
-                                             self.d_ws.data_ptr(), self.ws_bytes, self.d_kp.data_ptr(), self.d_desc.data_ptr(),
-                                             self.d_counts.data_ptr(), self.d_level_counts.data_ptr())
+        args = (d_images.data_ptr(), self.n, self.w, self.h, self.threshold, self.max_keypoints, self.n_levels, self.d_ws.data_ptr(), self.ws_bytes,
+                self.d_kp.data_ptr(), self.d_desc.data_ptr(), self.d_counts.data_ptr(), self.d_level_counts.data_ptr())
+        if self.d_rows128 is None:
+            self.ctx.detect_pyramid_batch_device(*args)
+        else:
+            self.ctx.detect_pyramid_grad_batch_device(*args, self.d_rows128.data_ptr())
 
     def results(self):
-        """(keypoints_per_image, rows_per_image, level_counts [n, n_levels]) on the host."""
-        return (*_detected(self.d_kp, self.d_desc, self.d_counts, self.n, self.max_keypoints),
-                self.d_level_counts.cpu().numpy().reshape(self.n, self.n_levels).copy())
+        """On the host: (keypoints_per_image, rows_per_image, level_counts [n, n_levels]); rows_per_image are the uint8 [n_i, 32] rows for
+        "brief" and the float32 [n_i, 128] rows for "grad"; "both" gives (keypoints, rows32, rows128, level_counts)."""
+        kps, rows32 = _detected(self.d_kp, self.d_desc, self.d_counts, self.n, self.max_keypoints)
+        level_counts = self.d_level_counts.cpu().numpy().reshape(self.n, self.n_levels).copy()
+        if self.d_rows128 is None:
+            return kps, rows32, level_counts
+        grad = self.d_rows128.cpu().numpy()[: self.n * self.max_keypoints * 128].reshape(self.n, self.max_keypoints, 128)
+        rows128 = [grad[i, : len(kps[i])].copy() for i in range(self.n)]
+        return (kps, rows128, level_counts) if self.descriptor == "grad" else (kps, rows32, rows128, level_counts)
 
 
-def detect_images_pyramid(ctx, images, threshold=20, max_keypoints=10000, n_levels=8, device=None):
+def detect_images_pyramid(ctx, images, threshold=20, max_keypoints=10000, n_levels=8, device=None, descriptor="brief"):
     """gms_detect_pyramid_batch_device on a stack of equally sized 8-bit grey images [n, H, W]: the detector of detect_images on every
     level of an image pyramid (ratio about 1.2). Returns (keypoints_per_image, rows_per_image, level_counts [n, n_levels]) as host
-    arrays: KEYPOINT_DTYPE records in level-0 pixel coordinates with size and octave, level 0 first, raster order inside a level."""
+    arrays: KEYPOINT_DTYPE records in level-0 pixel coordinates with size and octave, level 0 first, raster order inside a level.
+    descriptor="grad": rows_per_image are the float32 [n_i, 128] gradient rows (for GMS_DESC_L2_F32X128); "both": (keypoints, 32-byte
+    rows, 128-float rows, level_counts)."""
     dev, imgs = _image_stack(ctx, images, device)
     n, h, w = imgs.shape
-    run = DetectPyramid(ctx, n, w, h, threshold, max_keypoints, n_levels, dev)
+    run = DetectPyramid(ctx, n, w, h, threshold, max_keypoints, n_levels, dev, descriptor)
     run.run(imgs)
     ctx.synchronize()
     return run.results()
@@ -271,8 +290,12 @@ def build_pyramid(ctx, images, n_levels=8, device=None):
     return out
 
 
-def describe_image(ctx, image, keypoints, device=None):
-    """gms_describe_device: directions and 32-byte rows at the given integer keypoints of one image -> (status, keypoints, rows)."""
+def describe_image(ctx, image, keypoints, device=None, descriptor="brief", fill=0):
+    """gms_describe_device: directions and 32-byte rows at the given integer keypoints of one image -> (status, keypoints, rows).
+    descriptor="grad": gms_describe_grad_device, float32 [n, 128] rows. fill: what the rows hold before the call (a refused keypoint's
+    row keeps it)."""
+    if descriptor not in ("brief", "grad"):
+        raise ValueError('descriptor must be "brief" or "grad"')
     dev = _device(ctx, device)
     img = torch.from_numpy(np.ascontiguousarray(image, dtype=np.uint8)).to(dev)
     h, w = img.shape
@@ -282,13 +305,16 @@ def describe_image(ctx, image, keypoints, device=None):
         raise ValueError("bad image size")
     d_ws = torch.zeros(nb, dtype=torch.uint8, device=dev)
     d_kp = _to_dev(kp, dev) if len(kp) else torch.zeros(28, dtype=torch.uint8, device=dev)
-    d_desc = torch.zeros(max(len(kp), 1) * 32, dtype=torch.uint8, device=dev)
+    grad = descriptor == "grad"
+    width = 128 if grad else 32
+    d_desc = torch.full((max(len(kp), 1) * width,), fill, dtype=torch.float32 if grad else torch.uint8, device=dev)
     d_status = torch.zeros(1, dtype=torch.int32, device=dev)
     torch.cuda.synchronize(dev)
-    ctx.describe_device(img.data_ptr(), w, h, d_kp.data_ptr(), len(kp), d_ws.data_ptr(), nb, d_desc.data_ptr(), d_status.data_ptr())
+    call = ctx.describe_grad_device if grad else ctx.describe_device
+    call(img.data_ptr(), w, h, d_kp.data_ptr(), len(kp), d_ws.data_ptr(), nb, d_desc.data_ptr(), d_status.data_ptr())
     ctx.synchronize()
     out_kp = d_kp.cpu().numpy()[: len(kp) * 28].view(KEYPOINT_DTYPE).copy() if len(kp) else kp
-    return int(d_status.item()), out_kp, d_desc.cpu().numpy()[: len(kp) * 32].reshape(-1, 32)
+    return int(d_status.item()), out_kp, d_desc.cpu().numpy()[: len(kp) * width].reshape(-1, width)
 
 
 def match_pairs(ctx, descs, pairs, use_prepared=True):

@@ -27,6 +27,7 @@
 // The same detector over an image pyramid (launch_detect_pyramid) adds
 //   pyr_resize_kernel    a level from the level below it: integer bilinear, source rows through LDS, 4-byte loads and stores.
 //   det_describe_kernel  in its per-level form: records behind the earlier levels', pt mapped to level 0, size and octave set.
+//   (with d_rows128: grad_desc_kernels.hip's kernel behind every level's describe kernel -- DESIGN.md section 4.7c)
 //   pyr_clear_kernel     zeroes the levels' counts and histograms; pyr_counts_kernel: the per-image and per-level counts for the caller.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -521,6 +522,16 @@ hipError_t launch_detect(const uint8_t* d_images, int n_images, int w, int h, in
     return detect_level(d_images, n_images, w, h, threshold, max_keypoints, d_ws, d_kp, d_desc, d_counts, nullptr, nullptr, stream);
 }
 
+// FAST scores and box sums of a batch alone, into a detect_layout workspace (what the gradient descriptor's compute() starts from)
+hipError_t launch_detect_maps(const uint8_t* d_images, int n_images, int w, int h, void* d_ws, hipStream_t stream)
+{
+    if (n_images <= 0) return hipSuccess;
+    const DetWs ws = carve(d_ws, w, h, n_images, 0);
+    hipLaunchKernelGGL(det_maps_kernel, dim3((w + kTileW - 1) / kTileW, (h + kTileH - 1) / kTileH, n_images), dim3(256), 0, stream, d_images, w, h,
+                       ws.score, ws.box);
+    return hipGetLastError();
+}
+
 // compute(): directions and rows at the caller's keypoints of ONE image; *d_status = 1 when a keypoint is off the pixel grid or outside the
 // keypoint region (its row is left alone)
 hipError_t launch_describe(const uint8_t* d_image, int w, int h, gms_keypoint* d_kp, int n, void* d_ws, uint8_t* d_desc, int32_t* d_status,
@@ -574,7 +585,7 @@ size_t detect_pyramid_workspace_bytes(int w, int h, int n_images, int max_keypoi
 }
 
 hipError_t launch_detect_pyramid(const uint8_t* d_images, int n_images, int w, int h, int threshold, int max_keypoints, int n_levels, void* d_ws,
-                                 gms_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, int32_t* d_level_counts, hipStream_t stream)
+                                 gms_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, int32_t* d_level_counts, hipStream_t stream, float* d_rows128)
 {
     if (n_images <= 0) return hipSuccess;
     int ww[kPyramidMaxLevels], hh[kPyramidMaxLevels], quota[kPyramidMaxLevels];
@@ -597,6 +608,10 @@ hipError_t launch_detect_pyramid(const uint8_t* d_images, int n_images, int w, i
             e = detect_level(img, n_images, ww[l], hh[l], threshold, quota[l], det_ws, d_kp, d_desc, lvl_counts + (size_t)l * n_images, &lo,
                              hists + (size_t)l * n_images * 256, stream);
             if (e != hipSuccess) return e;
+            if (d_rows128 != nullptr) {   // while the level's box sums and list are still in the workspace
+                e = launch_grad_level(n_images, ww[l], hh[l], quota[l], det_ws, lvl_counts, l, max_keypoints, d_kp, d_rows128, stream);
+                if (e != hipSuccess) return e;
+            }
         }
         img = l == 0 ? levels : img + (size_t)ww[l] * hh[l] * n_images;
     }

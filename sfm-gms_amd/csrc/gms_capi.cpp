@@ -1531,6 +1531,40 @@ int gms_detect_pyramid_batch_device(gms_ctx* c, const uint8_t* d_images, int n_i
     });
 }
 
+// ---- gradient descriptor (grad_desc_kernels.hip) ---------------------------------------------------------------------------------
+size_t gms_detect_pyramid_grad_workspace_bytes(int width, int height, int n_images, int max_keypoints, int n_levels)
+{
+    if (!detect_image_ok(width, height)) return 0;
+    return gms::detect_pyramid_grad_workspace_bytes(width, height, n_images, max_keypoints, n_levels);
+}
+
+static bool rows128_ok(const float* d_rows128) { return d_rows128 && reinterpret_cast<uintptr_t>(d_rows128) % 8 == 0; }  // stored two floats at a time
+
+int gms_detect_pyramid_grad_batch_device(gms_ctx* c, const uint8_t* d_images, int n_images, int width, int height, int threshold, int max_keypoints,
+                                         int n_levels, void* d_workspace, size_t workspace_bytes, gms_keypoint* d_keypoints, uint8_t* d_descriptors,
+                                         int32_t* d_counts, int32_t* d_level_counts, float* d_rows128)
+{
+    if (!c || n_images < 0 || max_keypoints < 0 || threshold < 0 || threshold > 254 || !detect_image_ok(width, height)) return GMS_ERR_BAD_ARG;
+    if (n_levels < 1 || n_levels > GMS_PYRAMID_MAX_LEVELS) return GMS_ERR_BAD_ARG;
+    if (n_images == 0) return GMS_OK;
+    if (!d_images || !d_workspace || !d_counts || !d_level_counts) return GMS_ERR_BAD_ARG;
+    if (max_keypoints > 0 && (!d_keypoints || !d_descriptors || !rows128_ok(d_rows128))) return GMS_ERR_BAD_ARG;
+    if (workspace_bytes < gms::detect_pyramid_grad_workspace_bytes(width, height, n_images, max_keypoints, n_levels)) return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] {
+        return gms::launch_detect_pyramid(d_images, n_images, width, height, threshold, max_keypoints, n_levels, d_workspace, d_keypoints,
+                                          d_descriptors, d_counts, d_level_counts, c->stream, max_keypoints > 0 ? d_rows128 : nullptr);
+    });
+}
+
+int gms_describe_grad_device(gms_ctx* c, const uint8_t* d_image, int width, int height, gms_keypoint* d_keypoints, int n, void* d_workspace,
+                             size_t workspace_bytes, float* d_rows128, int32_t* d_status)
+{
+    if (!c || n < 0 || !detect_image_ok(width, height) || !d_image || !d_workspace || !d_status) return GMS_ERR_BAD_ARG;
+    if (n > 0 && (!d_keypoints || !rows128_ok(d_rows128))) return GMS_ERR_BAD_ARG;
+    if (workspace_bytes < gms::detect_workspace_bytes(width, height, 1, 0)) return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] { return gms::launch_describe_grad(d_image, width, height, d_keypoints, n, d_workspace, d_rows128, d_status, c->stream); });
+}
+
 // ---- LOGOS on resident frames (logos_batch_kernels.hip) ----------------------------------------------------------------------
 int64_t gms_logos_table_bytes(int64_t total_kp, int n_frames, int n_words)
 {

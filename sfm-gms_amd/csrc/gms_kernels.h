@@ -152,7 +152,15 @@ void       pyramid_quotas(const int* widths, const int* heights, int n, int max_
 size_t     detect_pyramid_workspace_bytes(int w, int h, int n_images, int max_keypoints, int n_levels);
 hipError_t launch_pyramid_build(const uint8_t* d_images, int n_images, int w, int h, int n_levels, uint8_t* d_levels, hipStream_t stream);
 hipError_t launch_detect_pyramid(const uint8_t* d_images, int n_images, int w, int h, int threshold, int max_keypoints, int n_levels, void* d_ws,
-                                 gms_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, int32_t* d_level_counts, hipStream_t stream);
+                                 gms_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, int32_t* d_level_counts, hipStream_t stream,
+                                 float* d_rows128 = nullptr);   // d_rows128: the gradient descriptor's rows as well
+hipError_t launch_detect_maps(const uint8_t* d_images, int n_images, int w, int h, void* d_ws, hipStream_t stream);
+// gradient descriptor (grad_desc_kernels.hip; arithmetic in grad_desc_core.h): 128-float rows at the detector's keypoints
+size_t     detect_pyramid_grad_workspace_bytes(int w, int h, int n_images, int max_keypoints, int n_levels);
+hipError_t launch_grad_level(int n_images, int w, int h, int quota, void* d_det_ws, const int32_t* d_level_counts, int level, int out_stride,
+                             gms_keypoint* d_kp, float* d_rows128, hipStream_t stream);
+hipError_t launch_describe_grad(const uint8_t* d_image, int w, int h, gms_keypoint* d_kp, int n, void* d_ws, float* d_rows128, int32_t* d_status,
+                                hipStream_t stream);
 // batched LOGOS (logos_batch_kernels.hip; layouts in logos_batch.h)
 hipError_t launch_logos_prepare(const gms_keypoint* d_kp, const int64_t* d_frame_off, int n_frames, int64_t total_kp, const int32_t* d_words,
                                 int n_words, void* d_ws, size_t ws_bytes, void* d_table, int n_cus, hipStream_t stream);

@@ -99,6 +99,15 @@ inline PyramidLayout pyramid_layout(int w, int h, int n_images, int max_keypoint
             c.end, c.end + detect_layout(w, h, n_images, max_keypoints).total};
 }
 
+// The pyramid call that also writes the gradient descriptor's rows (grad_desc_kernels.hip): the descriptor kernel runs behind each
+// level's describe kernel and reads what that level left -- the box sums and the list in `detect`, the direction in the keypoint
+// record -- so it needs no region of its own: the pyramid's regions, under the names its launcher uses.
+using PyramidGradLayout = PyramidLayout;
+inline PyramidGradLayout pyramid_grad_layout(int w, int h, int n_images, int max_keypoints, int n_levels)
+{
+    return pyramid_layout(w, h, n_images, max_keypoints, n_levels);
+}
+
 // ---- large pairs, per slice of n pairs of the context's own workspace (gms_kernel_band.hip, gms_kernel_stream.hip) ------------------
 // plan_workspace sizes a slice as n * bytes per pair: the regions of one pair, plus a slack that covers what the layout of n pairs
 // rounds up (`padding`; every round-up here is to 16 bytes, so it adds less than 16).

@@ -1,0 +1,213 @@
+"""-m gpu: the gradient descriptor (gms_detect_pyramid_grad_batch_device / gms_describe_grad_device) against its numpy
+statement tests/grad_desc_ref.py, byte for byte; what the pyramid call writes beside the rows against the existing call; captured into a
+graph; in front of the L2 matcher and bruteForceMatch's selection; and how many exact nearest neighbours are right on a photograph
+and its 0.6 x copy, against the 32-byte rows on the same keypoints."""
+import importlib
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import bf_select_ref  # noqa: E402
+import grad_desc_ref  # noqa: E402
+import pyramid_ref  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
+STEREO = os.path.join(GOLDEN, "image_stereo_pair_450x375.npz")
+MAIN = os.path.join(GOLDEN, "image_main_scenario_1080p.npz")
+
+
+def _batch():
+    return importlib.import_module("sfm-gms_amd.batch")
+
+
+def _check(ctx, oracle, imgs, threshold, max_kp, n_levels):
+    """"grad" and "both" against the statement, and against what detect_images_pyramid returns without the option."""
+    batch = _batch()
+    base_kp, base_rows, base_lc = batch.detect_images_pyramid(ctx, imgs, threshold, max_kp, n_levels)
+    kps, rows32, rows128, lc = batch.detect_images_pyramid(ctx, imgs, threshold, max_kp, n_levels, descriptor="both")
+    g_kps, g_rows128, g_lc = batch.detect_images_pyramid(ctx, imgs, threshold, max_kp, n_levels, descriptor="grad")
+    assert lc.tobytes() == base_lc.tobytes() == g_lc.tobytes()
+    for i, img in enumerate(imgs):
+        want_kp, want_rows32, want_lc, want_rows128 = grad_desc_ref.detect(oracle, img, threshold, max_kp, n_levels)
+        assert lc[i].tolist() == want_lc.tolist()
+        assert kps[i].tobytes() == base_kp[i].tobytes() == want_kp.tobytes() == g_kps[i].tobytes(), i
+        assert rows32[i].tobytes() == base_rows[i].tobytes() == want_rows32.tobytes(), i
+        assert rows128[i].dtype == np.float32 and rows128[i].shape == (len(want_kp), 128)
+        assert rows128[i].tobytes() == want_rows128.tobytes(), i
+        assert g_rows128[i].tobytes() == want_rows128.tobytes(), i
+    return kps, rows128, lc
+
+
+@pytest.mark.parametrize("threshold,max_kp,n_levels", [(20, 10000, 8), (8, 700, 8), (20, 5, 8), (20, 1, 8), (12, 3000, 1)])
+def test_stereo_pair_equals_statement(ctx, oracle, threshold, max_kp, n_levels):
+    z = np.load(STEREO)
+    kps, rows128, lc = _check(ctx, oracle, np.stack([z["left"], z["right"]]), threshold, max_kp, n_levels)
+    if (threshold, max_kp, n_levels) == (20, 10000, 8):
+        assert (lc > 0).all() and rows128[0].any()
+
+
+@pytest.mark.parametrize("w,h", [(33, 33), (97, 65), (1030, 50)])
+def test_odd_sizes_three_images(ctx, oracle, w, h):
+    """Noise, two grey levels, sparse dots; max_keypoints of 1, 5 and 37 put the counts on and off multiples of the four keypoints of a
+    workgroup; the flat image has no keypoint."""
+    rng = np.random.default_rng(w * 1000 + h)
+    noise = rng.integers(0, 256, (h, w), dtype=np.uint8)
+    blocks = (np.kron(rng.integers(0, 2, ((h + 3) // 4, (w + 3) // 4)), np.ones((4, 4), dtype=np.int64))[:h, :w] * 90 + 60).astype(np.uint8)
+    sparse = np.full((h, w), 40, dtype=np.uint8)
+    sparse[rng.integers(0, h, 60), rng.integers(0, w, 60)] = 200
+    flat = np.full((h, w), 77, dtype=np.uint8)
+    for threshold, max_kp, n_levels in ((10, 37, 8), (0, 5, 16), (10, 1, 2)):
+        _check(ctx, oracle, np.stack([noise, blocks, sparse]), threshold, max_kp, n_levels)
+        kps, _, _ = _check(ctx, oracle, np.stack([noise, flat, blocks]), threshold, max_kp, n_levels)
+        assert len(kps[1]) == 0 and (w == 33 or len(kps[0]) > 0)
+
+
+def test_describe_image_at_every_pixel(ctx, oracle):
+    batch = _batch()
+    img = np.random.default_rng(6448).integers(0, 256, (48, 64), dtype=np.uint8)
+    ys, xs = np.mgrid[0:48, 0:64]
+    kp = np.zeros(48 * 64 + 1, dtype=oracle.KEYPOINT_DTYPE)
+    kp["x"][:-1], kp["y"][:-1] = xs.ravel(), ys.ravel()
+    kp["x"][-1], kp["y"][-1] = 30.5, 20.0                       # off the grid
+    kp["angle"] = -1.0
+    want_status, want_kp, want_rows = grad_desc_ref.describe(img, kp)
+    status, got_kp, got_rows = batch.describe_image(ctx, img, kp, descriptor="grad", fill=-7.0)
+    refused = np.isnan(want_rows[:, 0])
+    assert want_status == 1 and status == 1 and refused.sum() == 48 * 64 + 1 - 32 * 16
+    assert got_kp.tobytes() == want_kp.tobytes()
+    assert (got_rows[refused] == -7.0).all()
+    assert got_rows[~refused].tobytes() == want_rows[~refused].tobytes()
+    inner = kp[~refused]
+    status, got_kp, got_rows = batch.describe_image(ctx, img, inner, descriptor="grad")
+    assert status == 0 and got_rows.tobytes() == want_rows[~refused].tobytes() and got_kp.tobytes() == want_kp[~refused].tobytes()
+    _, brief_kp, _ = batch.describe_image(ctx, img, inner)       # the same directions as the existing call
+    assert brief_kp.tobytes() == got_kp.tobytes()
+
+
+def test_graph_replay_on_new_pixels(ctx, oracle):
+    import torch
+    batch = _batch()
+    z = np.load(STEREO)
+    first, second = np.stack([z["left"], z["right"]]), np.stack([z["right"][::-1].copy(), z["left"][:, ::-1].copy()])
+    h, w = z["left"].shape
+    want = {id(imgs): [grad_desc_ref.detect(oracle, img, 12, 600, 8) for img in imgs] for imgs in (first, second)}
+    d_imgs = torch.from_numpy(first).cuda()
+    run = batch.DetectPyramid(ctx, 2, w, h, 12, 600, 8, descriptor="both")
+    stream = torch.cuda.Stream()
+    ctx.set_stream(stream.cuda_stream)
+    g = torch.cuda.CUDAGraph()
+    try:
+        with torch.cuda.stream(stream):
+            run.run(d_imgs)                                   # warm-up
+        stream.synchronize()
+        with torch.cuda.graph(g, stream=stream):
+            run.run(d_imgs)
+        for imgs in (second, first):
+            d_imgs.copy_(torch.from_numpy(imgs))
+            for t in (run.d_kp, run.d_desc, run.d_counts, run.d_level_counts, run.d_rows128):
+                t.zero_()
+            torch.cuda.synchronize()
+            g.replay()
+            torch.cuda.synchronize()
+            kps, rows32, rows128, lc = run.results()
+            for i in range(2):
+                want_kp, want_rows32, want_lc, want_rows128 = want[id(imgs)][i]
+                assert kps[i].tobytes() == want_kp.tobytes() and rows32[i].tobytes() == want_rows32.tobytes()
+                assert lc[i].tolist() == want_lc.tolist() and rows128[i].tobytes() == want_rows128.tobytes() and rows128[i].any()
+    finally:
+        ctx.set_stream(None)
+        torch.cuda.synchronize()
+        g.reset()
+
+
+def test_rows_into_the_l2_matcher_and_the_selection(ctx, pkg, oracle):
+    batch = _batch()
+    z = np.load(STEREO)
+    kps, rows, _ = batch.detect_images_pyramid(ctx, np.stack([z["left"], z["right"]]), 12, 1500, 8, descriptor="grad")
+    assert min(len(k) for k in kps) > 500
+    h, w = z["left"].shape
+    table = batch.FrameTable(ctx, kps, [(w, h), (w, h)])
+    dt = batch.DescriptorTable(ctx, table, rows, pkg.GMS_DESC_L2_F32X128)
+    pairs = np.zeros(1, dtype=pkg.PAIR_DTYPE)
+    pairs[0] = (0, 1, len(kps[0]), 0, 0)
+    matches = batch.match_pairs(ctx, dt, pairs)
+    assert matches.tobytes() == oracle.bf_match(rows[0], rows[1], False).tobytes()
+    out, res = batch.bf_select_pairs(ctx, dt, [(0, 1)], True, 4.0, 500)
+    want, n_cand, n_ratio, _ = bf_select_ref.bf_match_select(rows[0], rows[1], False, True, 4.0, 500)
+    assert res["status"][0] == 0 and len(out[0]) == len(want) > 0 and out[0].tobytes() == want.tobytes()
+
+
+def test_argument_checks(ctx, pkg):
+    import torch
+    d = torch.zeros(1 << 22, dtype=torch.uint8, device="cuda:0")
+    p = d.data_ptr()
+    nb = ctx.detect_pyramid_grad_workspace_bytes(100, 100, 1, 10, 8)
+    assert 0 < nb <= 1 << 22 and nb >= ctx.detect_pyramid_workspace_bytes(100, 100, 1, 10, 8)
+    out = [torch.zeros(1024, dtype=torch.uint8, device="cuda:0") for _ in range(4)]     # keypoints, rows, counts, level counts
+    rows128 = torch.zeros(10 * 128, dtype=torch.float32, device="cuda:0")
+    img = torch.zeros(100 * 100, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    outs = [t.data_ptr() for t in out]
+    ctx.detect_pyramid_grad_batch_device(img.data_ptr(), 1, 100, 100, 20, 10, 8, p, nb, *outs, rows128.data_ptr())   # exactly enough
+    ctx.synchronize()
+    with pytest.raises(pkg.GmsError):
+        ctx.detect_pyramid_grad_batch_device(p, 1, 100, 100, 20, 10, 8, p, nb - 1, p, p, p, p, p)       # workspace one byte short
+    for n_levels in (0, 17):
+        with pytest.raises(pkg.GmsError):
+            ctx.detect_pyramid_grad_batch_device(p, 1, 100, 100, 20, 10, n_levels, p, 1 << 22, p, p, p, p, p)
+        assert ctx.detect_pyramid_grad_workspace_bytes(100, 100, 1, 10, n_levels) == 0
+    for bad in range(5):                                                                                  # each output pointer NULL in turn
+        ptrs = [p] * 5
+        ptrs[bad] = None
+        with pytest.raises(pkg.GmsError):
+            ctx.detect_pyramid_grad_batch_device(p, 1, 100, 100, 20, 10, 8, p, 1 << 22, *ptrs)
+    with pytest.raises(pkg.GmsError):
+        ctx.detect_pyramid_grad_batch_device(None, 1, 100, 100, 20, 10, 8, p, 1 << 22, p, p, p, p, p)    # no images
+    with pytest.raises(pkg.GmsError):
+        ctx.detect_pyramid_grad_batch_device(p, 1, 100, 100, 20, 10, 8, None, 1 << 22, p, p, p, p, p)    # no workspace
+    with pytest.raises(pkg.GmsError):
+        ctx.detect_pyramid_grad_batch_device(p, 1, 100, 100, 20, 10, 8, p, 1 << 22, p, p, p, p, p + 4)   # rows not 8-byte aligned
+    with pytest.raises(pkg.GmsError):
+        ctx.detect_pyramid_grad_batch_device(p, 1, 32, 100, 20, 10, 8, p, 1 << 22, p, p, p, p, p)        # no room for a keypoint
+    ctx.detect_pyramid_grad_batch_device(p, 0, 100, 100, 20, 10, 8, None, 0, None, None, None, None, None)   # nothing to do
+    ws = ctx.detect_workspace_bytes(100, 100, 1, 0)
+    for args in ((None, 100, 100, p, 4, p, ws, p, p), (p, 100, 100, None, 4, p, ws, p, p), (p, 100, 100, p, 4, None, ws, p, p),
+                 (p, 100, 100, p, 4, p, ws - 1, p, p), (p, 100, 100, p, 4, p, ws, None, p), (p, 100, 100, p, 4, p, ws, p, None),
+                 (p, 32, 100, p, 4, p, ws, p, p), (p, 100, 100, p, -1, p, ws, p, p)):
+        with pytest.raises(pkg.GmsError):
+            ctx.describe_grad_device(*args)
+    with pytest.raises(ValueError):
+        _batch().DetectPyramid(ctx, 1, 100, 100, descriptor="sift")
+
+
+def test_nearest_neighbours_on_a_shrunk_copy(ctx, oracle):
+    """1080p left against its 0.6 x copy, the 4000 pyramid keypoints of test_pipeline_on_a_shrunk_copy: the exact nearest neighbour of
+    every left row among the right rows, counted as correct within 3 pixels of where the shrink puts the left keypoint -- for the
+    128-float rows under L2 and for the 32-byte rows under Hamming on the same keypoints. The L2 count must reach 0.8 of the Hamming
+    count. Measured from the statement on the CPU (the GPU rows are those bytes): Hamming 860, L2 979."""
+    batch = _batch()
+    left = np.load(MAIN)["left"]
+    h, w = left.shape
+    wr, hr = 1152, 648
+    right = pyramid_ref.resize(left, wr, hr)
+    kps, rows32, rows128 = [], [], []
+    for img in (left, right):
+        k, r32, r128, _ = batch.detect_images_pyramid(ctx, img, 20, 4000, 8, descriptor="both")
+        want = grad_desc_ref.detect(oracle, img, 20, 4000, 8)
+        assert k[0].tobytes() == want[0].tobytes() and r32[0].tobytes() == want[1].tobytes() and r128[0].tobytes() == want[3].tobytes()
+        kps.append(k[0]); rows32.append(r32[0]); rows128.append(r128[0])
+    sx, sy = wr / w, hr / h
+
+    def correct(m):
+        q, t = kps[0][m["queryIdx"]], kps[1][m["trainIdx"]]
+        ex, ey = (q["x"] + 0.5) * sx - 0.5, (q["y"] + 0.5) * sy - 0.5
+        return int((np.hypot(t["x"] - ex, t["y"] - ey) <= 3.0).sum())
+
+    n_hamming = correct(oracle.bf_match(rows32[0], rows32[1], True))
+    n_l2 = correct(oracle.bf_match(rows128[0], rows128[1], False))
+    print(f"\n0.6 x: {len(kps[0])}/{len(kps[1])} keypoints; correct nearest neighbours: Hamming {n_hamming}, L2 {n_l2}")
+    assert n_hamming > 0 and n_l2 >= 0.8 * n_hamming

@@ -7,6 +7,8 @@ Input: an .npz with arrays left, right [H, W] uint8 and optionally gt (default: 
 SourceImages, tests/golden/image_stereo_pair_450x375.npz). Prints one JSON line; --out writes the survivors and the map as .npz.
     python tools/gms_image_pair.py [pair.npz] [--dense] [--pyramid N] [--threshold 12] [--max-keypoints 10000] [--rotation] [--scale] [--ratio 4] [--check]
 --pyramid N: keypoints from N levels of an image pyramid (gms_detect_pyramid_batch_device), with size and octave; without it the single-scale detector.
+--descriptor grad: the 128-float gradient rows (gms_detect_pyramid_grad_batch_device, one level without --pyramid; --dense:
+gms_describe_grad_device) under NORM_L2 instead of the 32-byte rows under NORM_HAMMING.
 --check runs the CPU statement (oracle/) beside it and compares every stage (test infrastructure; slow in --dense)."""
 import argparse
 import importlib
@@ -27,6 +29,7 @@ def main():
     ap.add_argument("pair", nargs="?", default=os.path.join(ROOT, "tests", "golden", "image_stereo_pair_450x375.npz"))
     ap.add_argument("--dense", action="store_true")
     ap.add_argument("--pyramid", type=int, default=0, metavar="N")
+    ap.add_argument("--descriptor", choices=("brief", "grad"), default="brief")
     ap.add_argument("--threshold", type=int, default=12)
     ap.add_argument("--max-keypoints", type=int, default=10000)
     ap.add_argument("--rotation", action="store_true")
@@ -44,6 +47,7 @@ def main():
     h, w = left.shape
     assert right.shape == (h, w), "images of one size (as a stereo pair)"
     ctx = pkg.GmsContext(0)
+    grad = a.descriptor == "grad"
     t = {}
     t0 = time.perf_counter()
     if a.dense:
@@ -53,17 +57,18 @@ def main():
         grid["x"], grid["y"], grid["size"] = xs.ravel(), ys.ravel(), 1.0
         kps, rows = [], []
         for img in (left, right):
-            st, k, r = batch.describe_image(ctx, img, grid)
+            st, k, r = batch.describe_image(ctx, img, grid, descriptor=a.descriptor)
             assert st == 0
             kps.append(k)
             rows.append(r)
-    elif a.pyramid > 0:
-        kps, rows, level_counts = batch.detect_images_pyramid(ctx, np.stack([left, right]), a.threshold, a.max_keypoints, a.pyramid)
+    elif a.pyramid > 0 or grad:
+        kps, rows, level_counts = batch.detect_images_pyramid(ctx, np.stack([left, right]), a.threshold, a.max_keypoints, max(a.pyramid, 1),
+                                                              descriptor=a.descriptor)
     else:
         kps, rows = batch.detect_images(ctx, np.stack([left, right]), a.threshold, a.max_keypoints)
     t["keypoints_ms"] = (time.perf_counter() - t0) * 1e3
     table = batch.FrameTable(ctx, kps, [(w, h)] * 2)
-    dt = batch.DescriptorTable(ctx, table, rows, pkg.GMS_DESC_HAMMING256)
+    dt = batch.DescriptorTable(ctx, table, rows, pkg.GMS_DESC_L2_F32X128 if grad else pkg.GMS_DESC_HAMMING256)
     pairs = np.zeros(1, dtype=pkg.PAIR_DTYPE)
     pairs[0] = (0, 1, len(kps[0]), 0, 0)
     t0 = time.perf_counter()
@@ -95,27 +100,36 @@ def main():
             "status": int(res["status"][0]), "rms_pixels_compared": cnt,
             "disparity_rms": float(np.sqrt(float(stats["sum_sq"]) / cnt)) if cnt else None, "max_abs_error": int(stats["max_abs"]),
             "ms": {k: round(v, 3) for k, v in t.items()}, "note": "first-call times (allocation and module load included)"}
+    line["descriptor"] = a.descriptor
     if a.pyramid > 0 and not a.dense:
         line["mode"], line["keypoints_per_level"] = f"pyramid {a.pyramid}", level_counts.tolist()
     if a.check:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
         import gms_oracle as oracle
         ok = {}
         if a.dense:
-            ok["keypoints"] = all(oracle.describe(img, grid)[2].tobytes() == rows[i].tobytes() for i, img in enumerate((left, right)))
+            if grad:
+                import grad_desc_ref
+                ok["keypoints"] = all(grad_desc_ref.describe(img, grid)[2].tobytes() == rows[i].tobytes() for i, img in enumerate((left, right)))
+            else:
+                ok["keypoints"] = all(oracle.describe(img, grid)[2].tobytes() == rows[i].tobytes() for i, img in enumerate((left, right)))
             sample = np.arange(0, len(kps[0]), max(len(kps[0]) // 400, 1))
-            want_m = oracle.bf_match(rows[0][sample], rows[1], True)
+            want_m = oracle.bf_match(rows[0][sample], rows[1], not grad)
             ok["matches_sampled"] = bool((want_m["trainIdx"] == matches["trainIdx"][sample]).all() and (want_m["distance"] == matches["distance"][sample]).all()
                                          and (matches["queryIdx"] == np.arange(len(matches))).all() and (matches["imgIdx"] == 0).all())
         else:
-            if a.pyramid > 0:
-                sys.path.insert(0, os.path.join(ROOT, "tests"))
+            if grad:
+                import grad_desc_ref
+                want = [grad_desc_ref.detect(oracle, img, a.threshold, a.max_keypoints, max(a.pyramid, 1)) for img in (left, right)]
+                want = [(k, r128) for k, _, _, r128 in want]
+            elif a.pyramid > 0:
                 import pyramid_ref
                 want = [pyramid_ref.detect(oracle, img, a.threshold, a.max_keypoints, a.pyramid) for img in (left, right)]
             else:
                 want = [oracle.detect(img, a.threshold, a.max_keypoints) for img in (left, right)]
             ok["keypoints"] = all(want[i][0].tobytes() == kps[i].tobytes() and want[i][1].tobytes() == rows[i].tobytes() for i in range(2))
-            ok["matches"] = oracle.bf_match(rows[0], rows[1], True).tobytes() == matches.tobytes()
+            ok["matches"] = oracle.bf_match(rows[0], rows[1], not grad).tobytes() == matches.tobytes()
         rc, wout, wmask, wres = oracle.match((w, h), (w, h), kps[0], kps[1], matches, a.rotation, a.scale, 6.0)
         ok["filter"] = rc == 0 and wout.tobytes() == out[:n].tobytes()
         rc, wdisp, wcnt, wssq, wmx, wrms = oracle.disparity(kps[0], kps[1], wout, w, h, gt, a.ratio)
