@@ -75,7 +75,7 @@ __device__ __forceinline__ uint32_t* lds_at(uint32_t* base, uint32_t byte_off)
 }
 
 // ---- idioms of the byte-matrix kernels that count their instructions (dense_pair_plain in gms_kernel_dense.hip, stream_plain_kernel in
-//      gms_kernel_stream.hip): LDS by absolute byte offset (the dynamic segment of these kernels starts at 0, so no "+ base" per access),
+//      gms_kernel_stream_plain.hip): LDS by absolute byte offset (the dynamic segment of these kernels starts at 0, so no "+ base" per access),
 //      non-temporal record traffic, two instructions the compiler does not pick by itself
 // The match records are read once and the survivors written once: non-temporal, so that what the L2 keeps is the lines a
 // workgroup touches ahead for its successor (below) -- with plain loads and stores a good part of those is evicted before use.

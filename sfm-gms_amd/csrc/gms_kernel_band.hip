@@ -22,7 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gms_device_common.h"
+#include "gms_large_common.h"
 
 namespace gms {
 namespace {
@@ -41,9 +41,6 @@ static_assert(kMatrixBytes % 16 == 0, "the band matrix is cleared in uint4s");
 // code word: E' = 400 - r (1..400; higher = lower right cell) : 9 | hx : 6 | hy : 6 | binned : 1
 constexpr int kHxShift = 9, kHyShift = 15;
 constexpr uint32_t kBinned = 1u << 21;
-
-constexpr uint32_t kFlagDomain = 1u;    // an input outside the parity domain: the pair fails as a whole
-constexpr uint32_t kFlagGeneral = 2u;   // a left cell above 65 535 matches: gms_kernel_big.hip takes the pair
 
 __device__ __forceinline__ void band_rows(int band, int& lo, int& hi)  // own rows [lo, hi)
 {
@@ -103,8 +100,9 @@ band_codes_kernel(FilterParams p, uint2* lists, uint32_t* list_len, uint32_t* nf
     }
     const int base = blockIdx.x * 4096;
     if (base >= m) return;  // workgroup-uniform
-    const int64_t offA = p.frame_off[pr.frame_a], offB = p.frame_off[pr.frame_b];
-    const int nA = (int)(p.frame_off[pr.frame_a + 1] - offA), nB = (int)(p.frame_off[pr.frame_b + 1] - offB);
+    int64_t offA, offB;
+    int nA, nB;
+    pair_frame_ranges(p, pr, offA, nA, offB, nB);
     if (nA <= 0 || nB <= 0) {  // matches, but nothing valid to index
         if (blockIdx.x == 0 && tid == 0) atomicOr(&flags[pi], kFlagDomain);
         return;
@@ -126,7 +124,7 @@ band_codes_kernel(FilterParams p, uint2* lists, uint32_t* list_len, uint32_t* nf
         a[k] = ptsA[min(qt[k].x, (uint32_t)(nA - 1))];
         b[k] = ptsB[min(qt[k].y, (uint32_t)(nB - 1))];
     }
-    bool any_bad = false;
+    bool any_bad = false;  // (the per-match steps below have a twin in tile_codes_kernel: as one function they change both kernels' code)
     uint32_t cw[4], rank[4][3];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -401,22 +399,10 @@ band_compact_kernel(FilterParams p, const uint32_t* flags, uint8_t* mask_ws, con
             before_total += wave_before[w];
         }
         pos += before_total;
-        const unsigned long long lt = (1ull << lane) - 1ull;
-        // the wave's records, eight loads in flight at a time (requested unconditionally and pinned before the stores: a load that
-        // only a conditional store uses is sunk into the branch by the compiler and waited for there, one round trip per record)
+        // the wave's records, eight loads in flight at a time
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            uint4 rec[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) rec[j] = *reinterpret_cast<const uint4*>(&matches[min(wbase + (h * 8 + j) * 64 + lane, m - 1)]);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(rec[j].x), "+v"(rec[j].y), "+v"(rec[j].z), "+v"(rec[j].w));
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                if (mb[h * 8 + j]) *reinterpret_cast<uint4*>(&out[pos + (uint32_t)__popcll(bal[h * 8 + j] & lt)]) = rec[j];
-                pos += (uint32_t)__popcll(bal[h * 8 + j]);
-            }
-        }
+        for (int h = 0; h < 2; ++h)
+            pos = copy_out_wave<8>(matches, out, wbase + h * 8 * 64, m, lane, bal + h * 8, [&](int j) { return mb[h * 8 + j] != 0; }, pos);
         total = before_total + tile_total;
     } else if (failed && m > 0 && m <= mcap && p.mask) {
         uint8_t* mask = p.mask + pr.match_off;  // a failed pair keeps nothing
@@ -491,8 +477,9 @@ tile_codes_kernel(FilterParams p, TileGeom gm, uint2* lists, uint32_t* list_len,
     }
     const int base = blockIdx.x * 4096;
     if (base >= m) return;  // workgroup-uniform
-    const int64_t offA = p.frame_off[pr.frame_a], offB = p.frame_off[pr.frame_b];
-    const int nA = (int)(p.frame_off[pr.frame_a + 1] - offA), nB = (int)(p.frame_off[pr.frame_b + 1] - offB);
+    int64_t offA, offB;
+    int nA, nB;
+    pair_frame_ranges(p, pr, offA, nA, offB, nB);
     if (nA <= 0 || nB <= 0) {
         if (blockIdx.x == 0 && tid == 0) atomicOr(&flags[pi], kFlagDomain);
         return;
@@ -515,7 +502,7 @@ tile_codes_kernel(FilterParams p, TileGeom gm, uint2* lists, uint32_t* list_len,
         b[k] = ptsB[min(qt[k].y, (uint32_t)(nB - 1))];
     }
     const float fwr = (float)gm.wr;
-    bool any_bad = false;
+    bool any_bad = false;  // (the per-match steps below are band_codes_kernel's, with this scale's right grid)
     uint32_t cw[4], rank[4][4], tile_of[4][4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {

@@ -13,7 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gms_device_common.h"
+#include "gms_large_common.h"
 
 namespace gms {
 namespace {
@@ -107,7 +107,7 @@ filter_kernel_big(FilterParams p, uint32_t* ws, size_t ws_stride, int mcap, uint
     uint32_t* chunk_base = bestmask + (mcap >> 5);                          // mcap / 64 + 1
 
     for (int pi = blockIdx.x; pi < p.n_pairs; pi += gridDim.x) {
-        if (p.pair_flags && !(p.pair_flags[pi] & 2u)) continue;  // the band kernels (gms_kernel_band.hip) did this pair
+        if (p.pair_flags && !(p.pair_flags[pi] & kFlagGeneral)) continue;  // the band kernels (gms_kernel_band.hip) did this pair
         const gms_pair pr = p.pairs[pi];
         const int m = pr.m;
         const gms_dmatch* __restrict__ matches = p.matches + pr.match_off;
@@ -121,7 +121,7 @@ filter_kernel_big(FilterParams p, uint32_t* ws, size_t ws_stride, int mcap, uint
                               pr.frame_b < 0 || pr.frame_b >= p.n_frames;
         int64_t offA = 0, offB = 0;
         int nA = 0, nB = 0;
-        if (!bad_pair) {
+        if (!bad_pair) {  // (pair_frame_ranges of gms_large_common.h, spelled out: the call changes this kernel's schedule)
             offA = p.frame_off[pr.frame_a];
             offB = p.frame_off[pr.frame_b];
             nA = (int)(p.frame_off[pr.frame_a + 1] - offA);

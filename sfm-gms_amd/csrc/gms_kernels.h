@@ -99,7 +99,7 @@ hipError_t init_stream_kernels();
 int        stream_max_matches();
 size_t     stream_ws_bytes_per_pair(const FilterParams& p, int mcap, bool need_mask);
 hipError_t launch_filter_stream(const FilterParams& p, int mcap, void* ws, const uint32_t** flags_out, hipStream_t stream);
-// the same size class without scale hypotheses: one workgroup per pair, the byte matrix of gms_kernel_dense.hip with the code words streamed from an L2-resident array
+// the same size class without scale hypotheses (gms_kernel_stream.hip; the default flags: gms_kernel_stream_plain.hip): one workgroup per pair, the byte matrix of gms_kernel_dense.hip with the code words streamed from an L2-resident array
 size_t     stream_dense_ws_bytes_per_pair(int mcap);
 hipError_t launch_filter_stream_dense(const FilterParams& p, int mcap, void* ws, const uint32_t** flags_out, hipStream_t stream);
 // brute-force descriptor matcher (bf_kernels.hip)
