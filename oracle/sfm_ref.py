@@ -182,6 +182,13 @@ def canonical_sign(E):
     return -E if E.reshape(-1)[k] < 0 else E
 
 
+# What five_point may return: after the polish, a candidate of unit Frobenius norm whose largest absolute constraint value (det E and the
+# nine entries of 2 E E^T E - tr(E E^T) E) exceeds this is dropped -- on degenerate samples (collinear points, no translation) the
+# polish can stall at a matrix that is no essential matrix, down to rank one, which every correspondence then "fits". The value and
+# the measurements behind it: DESIGN.md section 4.6; tv::kValidityGate of twoview_core.h is the same number.
+VALIDITY_GATE = 1e-13
+
+
 def _constraints(E):
     G = E @ E.T
     return np.concatenate([[np.linalg.det(E)], (2.0 * G @ E - np.trace(G) * E).reshape(-1)])
@@ -279,7 +286,10 @@ def five_point(x1, x2):
         if abs(v[2]) < 1e-10:          # (v is a unit vector)
             continue
         Em = _polish(basis, (v[0] / v[2], v[1] / v[2], z))
-        out.append(canonical_sign(Em / np.linalg.norm(Em)))
+        Em = Em / np.linalg.norm(Em)
+        if not np.abs(_constraints(Em)).max() <= VALIDITY_GATE:   # the polish stalled away from the constraint set: not an essential matrix
+            continue
+        out.append(canonical_sign(Em))
     return sorted(out, key=lambda m: tuple(m.reshape(-1)))
 
 

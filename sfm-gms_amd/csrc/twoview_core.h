@@ -579,8 +579,28 @@ GMS_HD void polish_solution(const Mem& basis, double& x, double& y, double& z)
     }
 }
 
+// What makes a candidate an essential matrix: the largest absolute value among the ten constraints (det E and the nine entries of
+// 2 E E^T E - tr(E E^T) E) of a unit-norm E. Polished solutions of well-posed samples sit at rounding level (<= 3.4e-16 measured);
+// on degenerate samples (collinear points, no translation, a plane) the polish can stall anywhere up to a rank-one matrix, which every
+// correspondence "fits". five_point drops a candidate above the gate; the tests' numpy restatement applies the same number
+// (sfm_ref.VALIDITY_GATE) and DESIGN.md section 4.6 has the measurements it was chosen from.
+constexpr double kValidityGate = 1e-13;
+
+GMS_HD double constraint_residual(const double* E)
+{
+    double G[9];  // E E^T
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) G[3 * a + b] = E[3 * a] * E[3 * b] + E[3 * a + 1] * E[3 * b + 1] + E[3 * a + 2] * E[3 * b + 2];
+    const double tr = G[0] + G[4] + G[8];
+    double worst = fabs(E[0] * (E[4] * E[8] - E[5] * E[7]) - E[1] * (E[3] * E[8] - E[5] * E[6]) + E[2] * (E[3] * E[7] - E[4] * E[6]));
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b)
+            worst = fmax(worst, fabs(2.0 * (G[3 * a] * E[b] + G[3 * a + 1] * E[3 + b] + G[3 * a + 2] * E[6 + b]) - tr * E[3 * a + b]));
+    return worst;
+}
+
 // Everything of one sample: models[9 * k] receives the k-th essential matrix (row-major, unit Frobenius norm, largest entry
-// positive, x2^T E x1 = 0); returns their number (0..10). The order of a sample's models decides RANSAC ties and must not depend on
+// positive, x2^T E x1 = 0, constraints within kValidityGate); returns their number (0..10). The order of a sample's models decides RANSAC ties and must not depend on
 // the null-space basis (the roots z do): ascending in E[0], then E[1], ...
 template <class Mem, class MemOut>
 GMS_HD int five_point(const double x1[5], const double y1[5], const double x2[5], const double y2[5], FivePointMem<Mem>& m, MemOut& models)
@@ -694,6 +714,7 @@ GMS_UNROLL
         if (!(n2 > 0.0) || !isfinite(n2)) continue;
         const double inv = 1.0 / sqrt(n2);
         for (int k = 0; k < 9; ++k) e[k] *= inv;
+        if (!(constraint_residual(e) <= kValidityGate)) continue;  // the polish stalled away from the constraint set
         canonical_sign(e);
         // insertion into the ordered list
         int pos = count;

@@ -44,6 +44,26 @@ void tvh_errors(const double* E, const double* x1, const double* x2, int n, floa
     for (int i = 0; i < n; ++i) err[i] = sampson_error(E, x1[2 * i], x1[2 * i + 1], x2[2 * i], x2[2 * i + 1]);
 }
 
+// recoverPose's cheirality votes of n correspondences (x1, x2: [n][2] normalised points; P: the four [R | +-t], [4][12]): bits[i] =
+// pose_votes, one[4 * i + h] = pose_vote_one for hypothesis h
+void tvh_pose_votes(const double* P, double dist_thresh, const double* x1, const double* x2, int n, uint8_t* bits, uint8_t* one)
+{
+    double Ph[4][12];
+    std::memcpy(Ph, P, sizeof Ph);
+    for (int i = 0; i < n; ++i) {
+        bits[i] = (uint8_t)pose_votes(Ph, dist_thresh, x1[2 * i], x1[2 * i + 1], x2[2 * i], x2[2 * i + 1]);
+        for (int h = 0; h < 4; ++h) one[4 * i + h] = pose_vote_one(Ph, h, dist_thresh, x1[2 * i], x1[2 * i + 1], x2[2 * i], x2[2 * i + 1]) ? 1 : 0;
+    }
+}
+
+void tvh_dlt_point(const double* Pa, const double* Pb, const double* x1, const double* x2, double* X) { dlt_point(Pa, Pb, x1[0], x1[1], x2[0], x2[1], X); }
+
+void tvh_undistort(const double* cam /* fx, fy, cx, cy, k1, k2, p1, p2, k3 */, const double* uv, int n, double* xy)
+{
+    const Camera c{cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7], cam[8]};
+    for (int i = 0; i < n; ++i) undistort_point(c, uv[2 * i], uv[2 * i + 1], xy[2 * i], xy[2 * i + 1]);
+}
+
 // find_essential_kernel's control flow on the host: uv in pixels (float), camera = fx, fy, cx, cy. Returns the inlier count.
 int tvh_find_essential(const float* uv1, const float* uv2, int n, const double* camera, double prob, double threshold, int max_iters,
                        double* E_out, uint8_t* mask, int* iters_out)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import sfm_ref
+import twoview_scenes as scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -28,6 +29,9 @@ def tvh(tmp_path_factory):
     lib.tvh_decompose.argtypes = [vp] * 4
     lib.tvh_errors.argtypes = [vp, vp, vp, C.c_int, vp]
     lib.tvh_find_essential.argtypes = [vp, vp, C.c_int, vp, C.c_double, C.c_double, C.c_int, vp, vp, vp]
+    lib.tvh_pose_votes.argtypes = [vp, C.c_double, vp, vp, C.c_int, vp, vp]
+    lib.tvh_dlt_point.argtypes = [vp] * 5
+    lib.tvh_undistort.argtypes = [vp, vp, C.c_int, vp]
     return lib
 
 
@@ -45,9 +49,11 @@ def _five(lib, x1, x2):
 
 
 def test_five_point_solver_against_the_restatement(tvh):
-    """1500 minimal samples -- exact two-view geometry, noisy, and unrelated points: the same number of models, the same matrices (both
-    sides polish every solution on the constraints themselves, so they meet at rounding level), in the same order. A sample in a few
-    thousand is near-degenerate (coinciding roots) and the two root finders part ways on it: at most 0.3 % may."""
+    """1500 minimal samples -- exact two-view geometry, noisy, and unrelated points: the same number of models, the same matrices, in the
+    same order. Both sides polish every solution on the constraints themselves and drop what the polish leaves above the validity gate
+    (largest constraint value of the unit-norm E <= 1e-13), so every model either side returns IS an essential matrix to that level --
+    on any input, test_every_model_is_an_essential_matrix -- and on well-posed samples the two sides meet at rounding level. A sample
+    in a few thousand is near-degenerate (coinciding roots) and the two root finders part ways on it: at most 0.3 % may."""
     rng = np.random.default_rng(2)
     diffs, off, exact_hit = [], 0, 0
     for trial in range(1500):
@@ -156,3 +162,143 @@ def test_ransac_loop_against_the_restatement(tvh, seed, n, outliers, prob):
         assert np.abs(Eh.reshape(3, 3) - E).max() < 1e-9
         if outliers <= 0.5 and n > 50:     # the estimate is the scene's geometry: most true correspondences are inliers, few wrong ones are
             assert mask[~wrong].mean() > 0.8 and mask[wrong].mean() < 0.1 and np.abs(E - Et).max() < 0.05
+
+
+# ---- the solver on degenerate samples, RANSAC on other motions, the cheirality votes, the DLT ------------------------------------------------
+def test_every_model_is_an_essential_matrix(tvh):
+    """300 seeded minimal samples of each of nine families -- the four well-posed ones and points collinear in one image, in both, no
+    translation, a planar scene, a correspondence twice in the sample: every model the host core returns and every model the restatement
+    returns has its largest constraint value (det E, 2 E E^T E - tr(E E^T) E of the unit-norm E) within the gate and singular values
+    (s, s, 0) within twoview_scenes.SPREAD_BOUND. On the well-posed families the two sides agree within 1e-9 on all but 0.3 % of the
+    samples (1 of 1200 measured); on the degenerate ones they legitimately return different (valid) sets."""
+    def solve(fam):
+        x1, x2 = scenes.minimal_samples(fam)
+        return [_five(tvh, a, b) for a, b in zip(x1, x2)]
+    seen = scenes.compare_solver_on_families(solve, live=True)
+    assert seen["planar"] > 1000        # (a plane is degenerate for the geometry, not for the solver: it still returns models)
+
+
+def _host_ransac(tvh, uv1, uv2, camera, prob, threshold, max_iters):
+    n = len(uv1)
+    Eh, mh, ith, cam = np.zeros(9), np.zeros(max(n, 1), dtype=np.uint8), C.c_int(0), np.array(camera)
+    good = tvh.tvh_find_essential(np.ascontiguousarray(uv1).ctypes.data, np.ascontiguousarray(uv2).ctypes.data, n, cam.ctypes.data, prob,
+                                  threshold, max_iters, Eh.ctypes.data, mh.ctypes.data, C.byref(ith))
+    return Eh.reshape(3, 3), mh[:n], good, ith.value
+
+
+@pytest.mark.parametrize("name", list(scenes.RANSAC_CASES))
+def test_ransac_on_other_motions_sizes_and_parameters(tvh, name):
+    """The host control flow against sfm_ref.find_essential_mat away from the one scene of the tests above: forward, backward, rolled,
+    widely yawed and vertical motion, a planar scene, integer pixels, repeated correspondences, a vanishing and a zero baseline; n around
+    the multiples of the kernels' workgroup sizes; max_iters around the multiples of their round sizes (12, 16); other thresholds and
+    cameras. Same iteration count, same mask, E within 1e-9."""
+    _, camera, prob, threshold, max_iters = scenes.RANSAC_CASES[name]
+    uv1, uv2 = scenes.case_scene(name)
+    E, mask, it = scenes.restatement_ransac(name)
+    scenes.assert_record_is_the_restatement(name)       # (what the GPU tests compare with)
+    Eh, mh, good, ith = _host_ransac(tvh, uv1, uv2, camera, prob, threshold, max_iters)
+    assert ith == it and good == int(mask.sum()) and np.array_equal(mh, mask), (ith, it, good, int(mask.sum()))
+    if E is None:
+        assert good == 0 and not Eh.any()
+    else:
+        assert np.abs(Eh - E).max() < 1e-9
+        scenes.assert_valid_model(Eh, name)
+
+
+@pytest.mark.parametrize("name", list(scenes.DEGENERATE_CASES))
+def test_ransac_on_degenerate_scenes_keeps_its_properties(tvh, name):
+    """Every point of one image (of both) on a line: no essential matrix explains such a pair and the two implementations part ways,
+    so each is held to what any answer must satisfy -- no model, or a valid essential matrix whose Sampson test IS the mask, the count
+    the mask's sum, iterations within the bound. Before the validity gate the core ended these inputs with a rank-one matrix and every
+    point an "inlier" (300 of 300)."""
+    _, camera, prob, threshold, max_iters = scenes.DEGENERATE_CASES[name]
+    uv1, uv2 = scenes.case_scene(name)
+    Eh, mh, good, ith = _host_ransac(tvh, uv1, uv2, camera, prob, threshold, max_iters)
+    scenes.assert_ransac_properties(name, Eh, mh, good, ith)
+    E, mask, it = scenes.restatement_ransac(name)
+    scenes.assert_ransac_properties(name, E, mask, int(mask.sum()), it)
+
+
+def _host_poses(tvh, E):
+    R1, R2, t = np.zeros(9), np.zeros(9), np.zeros(3)
+    assert tvh.tvh_decompose(np.ascontiguousarray(E).ctypes.data, R1.ctypes.data, R2.ctypes.data, t.ctypes.data) == 1
+    R1, R2 = R1.reshape(3, 3), R2.reshape(3, 3)
+    return [(R1, t), (R2, t), (R1, -t), (R2, -t)]
+
+
+def test_votes_for_each_of_the_four_hypotheses(tvh):
+    """Six random E; for each of its four (R, t) a scene of 600 noisy correspondences in front of both cameras of THAT hypothesis: the
+    restatement's recover_pose votes 600 of 600 for it, the host pose_votes' bit of the same pose (the core and numpy label R1 / R2 and
+    +-t differently: poses are compared, not indices) equals the restatement's mask of every hypothesis on every point, and
+    pose_vote_one equals pose_votes' bit -- including the two (R, -t) hypotheses, which pose_votes derives from (X, -w)."""
+    rng = np.random.default_rng(17)
+    fx, fy, cx, cy = scenes.BASE_CAMERA
+    points = 0
+    for _ in range(6):
+        E = scenes.random_essential(rng)
+        core = _host_poses(tvh, E)
+        P = np.ascontiguousarray([np.hstack([R, t.reshape(3, 1)]).reshape(12) for R, t in core])
+        for h in range(4):
+            uv1, uv2, R, t = scenes.hypothesis_scene(rng, E, h)
+            Rr, tr, good, mask = sfm_ref.recover_pose(E, uv1, uv2, scenes.BASE_CAMERA)
+            assert good == 600 and (mask == 255).all() and np.abs(Rr - R).max() < 1e-12 and np.abs(tr - t).max() < 1e-12
+            masks, poses = scenes.hypothesis_masks(E, uv1, uv2)
+            assert np.array_equal(masks[h], mask != 0) and sorted(m.sum() for m in masks)[-2] < 600      # a unique maximum
+            x1 = np.ascontiguousarray(np.stack([(uv1[:, 0].astype(np.float64) - cx) / fx, (uv1[:, 1].astype(np.float64) - cy) / fy], axis=1))
+            x2 = np.ascontiguousarray(np.stack([(uv2[:, 0].astype(np.float64) - cx) / fx, (uv2[:, 1].astype(np.float64) - cy) / fy], axis=1))
+            bits, one = np.zeros(600, dtype=np.uint8), np.zeros((600, 4), dtype=np.uint8)
+            tvh.tvh_pose_votes(P.ctypes.data, 50.0, x1.ctypes.data, x2.ctypes.data, 600, bits.ctypes.data, one.ctypes.data)
+            for hn, (Rn, tn) in enumerate(poses):      # numpy's hypothesis hn is the core's hypothesis hc
+                hc = [k for k, (Rc, tc) in enumerate(core) if np.abs(Rc - Rn).max() < 1e-9 and np.abs(tc - tn).max() < 1e-9]
+                assert len(hc) == 1
+                assert np.array_equal((bits >> hc[0]) & 1, masks[hn].astype(np.uint8)), (h, hn)
+                assert np.array_equal(one[:, hc[0]], (bits >> hc[0]) & 1), (h, hn)
+            points += 600
+    assert points == 14400
+
+
+def test_dlt_point_against_a_50_digit_eigenvector(tvh):
+    """tv::dlt_point (Jacobi on A^T A) against the eigenvector of the smallest eigenvalue of A^T A worked out with 50 digits (mpmath),
+    for depth-to-baseline ratios 5 .. 5e4 with 2e-4 of noise on the normalised points. The allowance is 100 x the error numpy's SVD
+    of the same A makes against the same 50-digit vector, computed here (measured: dlt_point <= 3.3e-16, numpy <= 6.7e-15)."""
+    import mpmath as mp
+    mp.mp.dps = 50
+    rng = np.random.default_rng(23)
+    worst, worst_np = 0.0, 0.0
+    for ratio in (5.0, 50.0, 500.0, 5e3, 5e4):
+        for _ in range(4):
+            R, t = scenes.rot(rng.uniform(-0.2, 0.2, 3)), rng.normal(size=3)
+            t /= np.linalg.norm(t)
+            X = np.array([rng.uniform(-0.3, 0.3) * ratio, rng.uniform(-0.2, 0.2) * ratio, ratio])
+            Xc = R @ X + t
+            x1 = np.ascontiguousarray(X[:2] / X[2] + rng.normal(0, 2e-4, 2))
+            x2 = np.ascontiguousarray(Xc[:2] / Xc[2] + rng.normal(0, 2e-4, 2))
+            Pa = np.ascontiguousarray(np.hstack([np.eye(3), np.zeros((3, 1))]))
+            Pb = np.ascontiguousarray(np.hstack([R, t.reshape(3, 1)]))
+            got = np.zeros(4)
+            tvh.tvh_dlt_point(Pa.ctypes.data, Pb.ctypes.data, x1.ctypes.data, x2.ctypes.data, got.ctypes.data)
+            A = np.stack([x1[0] * Pa[2] - Pa[0], x1[1] * Pa[2] - Pa[1], x2[0] * Pb[2] - Pb[0], x2[1] * Pb[2] - Pb[1]])
+            Am = mp.matrix(A.tolist())
+            ev, vecs = mp.eigsy(Am.T * Am)
+            k = min(range(4), key=lambda i: ev[i])
+            exact = np.array([float(vecs[i, k]) for i in range(4)])
+            exact /= np.linalg.norm(exact)
+            err = lambda v: min(np.abs(v / np.linalg.norm(v) - exact).max(), np.abs(v / np.linalg.norm(v) + exact).max())
+            worst, worst_np = max(worst, err(got)), max(worst_np, err(np.linalg.svd(A)[2][3]))
+            assert abs(np.linalg.norm(got) - 1) < 1e-14
+    print(f"dlt_point: worst error {worst:.3g}, numpy SVD {worst_np:.3g}")
+    assert worst_np > 0 and worst <= 100 * worst_np
+
+
+def test_undistort_point_against_the_restatement(tvh):
+    """tv::undistort_point (cv::undistortPoints' five fixed-point iterations) against sfm_ref.undistort_points, with and without
+    distortion: the same operations in the same order on both sides, fp-contraction off -- a few ulps of values below 1 (1e-15)."""
+    rng = np.random.default_rng(29)
+    uv = np.ascontiguousarray(np.stack([rng.uniform(0, 1920, 500), rng.uniform(0, 1080, 500)], axis=1))
+    for dist in ((0.0, 0.0, 0.0, 0.0, 0.0), (-0.12, 0.05, 0.001, -0.0007, 0.01), (0.0, 0.0, 0.002, 0.0, 0.0)):
+        cam, got = np.array(scenes.BASE_CAMERA + dist), np.zeros((500, 2))
+        tvh.tvh_undistort(cam.ctypes.data, uv.ctypes.data, 500, got.ctypes.data)
+        want = sfm_ref.undistort_points(uv, scenes.BASE_CAMERA, dist)
+        assert np.abs(got - want).max() <= 1e-15, dist
+        if any(dist):
+            assert np.abs(want - sfm_ref.undistort_points(uv, scenes.BASE_CAMERA)).max() > 1e-4
