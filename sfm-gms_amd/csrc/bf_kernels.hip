@@ -230,8 +230,11 @@ constexpr int kHamChunk = 32768;                 // Hamming: train rows whose in
 // L2, the exact search of a 32-row block, eight queries per wave: the eight lanes of a group (lane >> 3) hold the 16-byte pieces
 // (lane & 7) of the group's query and walk the 32 rows of the group's OWN block, so a group's load is one whole 128-byte row.
 // With the query side as nb = ~b' (the B operand of the matrix pass): d^2 = w(a) + 2 a'.nb + [nb.nb + 2 sum nb]; four elements per
-// v_dot4_i32_i8, the eight pieces added up with three DPP adds (the full sum lands in lanes 4..7 of the group, which all keep the
-// same running minimum). Returns (d^2 << 5 | row inside the block) of the block's first nearest row -- valid in lanes 4..7.
+// v_dot4_i32_i8, the eight pieces added up with three DPP adds: two inside the quads, then the group's other quad through
+// row_half_mirror, so that EVERY lane of the group ends with the full sum. Returns (d^2 << 5 | row inside the block) of the block's
+// first nearest row, the same value in all eight lanes: the caller's comparisons are then one decision per group, and the block a
+// group loads from next (`blk`, kept per lane) never differs between its lanes. (With row_shr:4 as the last add only lanes 4..7
+// held d^2; lanes 0..3 compared partial sums, took other blocks, and the group's next "row" came from two blocks.)
 __device__ __forceinline__ int dot16(const uint4& a, const uint4& b)
 {
     int d = __builtin_amdgcn_sdot4((int)a.x, (int)b.x, 0, false);
@@ -257,7 +260,7 @@ __device__ __forceinline__ uint32_t l2_block_key(const uint4* __restrict__ rows,
         int d2 = 2 * dot16(y, nb) + query_part;
         d2 += __builtin_amdgcn_update_dpp(0, d2, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
         d2 += __builtin_amdgcn_update_dpp(0, d2, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]: every lane of a quad has the quad's sum
-        d2 += __builtin_amdgcn_update_dpp(0, d2, 0x114, 0xF, 0xF, true);   // row_shr:4: lanes 4..7 add the quad before them
+        d2 += __builtin_amdgcn_update_dpp(0, d2, 0x141, 0xF, 0xF, true);   // row_half_mirror (lane 7 - piece): the other quad's sum
         d2 += w;
         key = min(key, row < nB ? ((uint32_t)d2 << 5) | (uint32_t)r : 0xFFFFFFFFu);   // d^2 <= 128 * 255^2 < 2^23
     }
@@ -558,6 +561,7 @@ bf_mfma_kernel(const uint4* __restrict__ rows, const uint32_t* __restrict__ norm
             uint32_t key;
             if (__ballot(hsel == 2) == 0ull) key = l2_block_key<16>(rows, norms, nb, query_part, f.offB, f.nB, blk, piece, hsel);
             else key = l2_block_key<32>(rows, norms, nb, query_part, f.offB, f.nB, blk, piece, 0);
+            // key and blk are group-uniform after every step below (l2_block_key returns one value per group)
             if (__ballot(nt == 1) != 0ull) {   // some group's minimal P was seen in a second block (a group without one repeats its own)
                 const int b = nt == 1 ? blk2 : blk;
                 const uint32_t k2 = l2_block_key<32>(rows, norms, nb, query_part, f.offB, f.nB, b, piece, 0);

@@ -5,6 +5,8 @@ import importlib
 import numpy as np
 import pytest
 
+import bf_ties_ref
+
 pytestmark = pytest.mark.gpu
 
 
@@ -136,6 +138,59 @@ def test_l2_distances_one_apart_in_different_tiles(ctx, pkg, oracle, synth):
     assert (got["trainIdx"][:n_q] == want_rows).all()
 
 
+def _report_l2(got, want, classes, label):
+    """Print, before anything is asserted, how the rows that differ from the oracle differ."""
+    bad = np.nonzero((got["trainIdx"] != want["trainIdx"]) | (got["distance"] != want["distance"]))[0]
+    same_block = int((got["trainIdx"][bad] // 32 == want["trainIdx"][bad] // 32).sum())
+    smaller = int((got["distance"][bad] < want["distance"][bad]).sum())
+    print(f"{label}: {len(bad)} of {len(want)} rows differ from the oracle; {same_block} in the oracle's block, {smaller} with a smaller "
+          f"distance; their classes nt = 0 / 1 / >= 2: {np.bincount(np.minimum(classes.nt[bad], 2), minlength=3).tolist()}")
+
+
+def test_l2_repeated_rows_mix_tie_classes(ctx, pkg, oracle, synth):
+    """Train frames drawn with replacement from a pool of distinct rows: a query's minimal P turns up in one, two or many 32-row
+    blocks, and the three classes sit side by side in the eight-query iterations of the final search -- the situation in which
+    that search once loaded a group's row from two blocks. The reverse pairs put the repeated rows on
+    the query side."""
+    descs = bf_ties_ref.repeated_rows_frames()
+    counts = [len(d) for d in descs]
+    ab = [(0, 1), (2, 3), (1, 0), (3, 2)]
+    classes = [bf_ties_ref.tie_classes(descs[a], descs[b]) for a, b in ab]
+    for c in classes[:2]:       # on the CPU, before anything is compared
+        mixed, groups = bf_ties_ref.mixed_groups(c)
+        assert 2 * mixed >= groups, (mixed, groups)
+    batch, table, dt = _tables(ctx, pkg, synth, descs, pkg.GMS_DESC_L2_F32X128)
+    pairs = _pairs(pkg, counts, ab)
+    got = batch.match_pairs(ctx, dt, pairs)
+    for p, c in zip(pairs, classes):
+        o = int(p["match_off"])
+        want = oracle.bf_match(descs[p["frame_a"]], descs[p["frame_b"]], False)
+        _report_l2(got[o:o + len(want)], want, c, f"repeated rows, pair {int(p['frame_a'])} -> {int(p['frame_b'])}")
+    _check(oracle, descs, pairs, got, False)
+
+
+def test_l2_constructed_group_of_eight(ctx, pkg, oracle, synth):
+    """Every aligned group of eight queries holds one query whose nearest row stands in three blocks, one with three candidate
+    blocks of which the third is one below, and six with two blocks that share P (bf_ties_ref.constructed_groups_of_eight): the
+    blocks over both staging buffers, the rows over both lane halves, the winners known by construction."""
+    query, train, roles, places, want_rows = bf_ties_ref.constructed_groups_of_eight()
+    c = bf_ties_ref.tie_classes(query, train)
+    for i, (role, spot) in enumerate(zip(roles, places)):
+        if role in ("copies", "third_below"):
+            assert c.nt[i] >= 2 and c.blk[i] == spot[0][0], (i, role)
+        else:
+            assert (c.nt[i], c.blk[i], c.blk2[i]) == (1, spot[0][0], spot[1][0]), (i, role)
+        assert c.hsel[i] == (spot[0][1] >> 2) & 1
+    assert bf_ties_ref.mixed_groups(c) == (len(query) // 8, len(query) // 8)
+    descs = [query, train]
+    batch, table, dt = _tables(ctx, pkg, synth, descs, pkg.GMS_DESC_L2_F32X128)
+    pairs = _pairs(pkg, [len(query), len(train)], [(0, 1)])
+    got = batch.match_pairs(ctx, dt, pairs)
+    _report_l2(got[:len(query)], oracle.bf_match(query, train, False), c, "constructed groups of eight")
+    _check(oracle, descs, pairs, got, False)
+    assert (got["trainIdx"][:len(query)] == want_rows).all()
+
+
 def test_l2_general_floats_take_the_reference_loop(ctx, pkg, oracle, synth):
     rng = np.random.default_rng(5)
     sift = synth.sequence_descriptors(23, 2, 800, "sift")
@@ -156,6 +211,114 @@ def test_l2_10k_sift_config2(ctx, pkg, oracle, synth):
     got = batch.match_pairs(ctx, dt, pairs)
     _check(oracle, descs, pairs, got, False)
     assert (got[:10000]["trainIdx"] == np.arange(10000)).mean() > 0.95
+
+
+# ---- record edges of gms_bfmatch_device (include/gms.h; oracle/bf_ref.c), through every kernel form ---------------------------------
+def _plain_tables(ctx, pkg, descs, kind):
+    batch = importlib.import_module("sfm-gms_amd.batch")
+    table = batch.FrameTable(ctx, [np.zeros(len(d), pkg.KEYPOINT_DTYPE) for d in descs], [(640, 480)] * len(descs))
+    return batch, table, batch.DescriptorTable(ctx, table, descs, kind)
+
+
+@pytest.mark.parametrize("form", bf_ties_ref.MIXED_FORMS)
+def test_mixed_records_in_one_launch(ctx, pkg, oracle, form):
+    """One launch over records of every kind (bf_ties_ref.mixed_records) into a buffer of 0xAB bytes: a train frame of 0 rows gives
+    {i, -1, 0, FLT_MAX}; a query frame of 0 rows, m = 0 and an invalid record (frame_a = -1, frame_b = n_frames, m = -1) write
+    nothing; m below n(frame_a) writes exactly m records, m above is clamped; a frame against itself finds itself, the lower index
+    among equal rows; and every byte outside those ranges is untouched."""
+    import torch
+    hamming, use_prepared = form.startswith("hamming"), "valu" not in form
+    descs = bf_ties_ref.mixed_record_frames(form)
+    counts, n_frames = [len(d) for d in descs], len(descs)
+    # the vector-ALU kernel keeps four rows per lane from 1024 workgroups on: 64 x 20 records of one 1024-row tile each
+    recs = bf_ties_ref.mixed_records(64 if form == "hamming_valu4" else 1)
+    max_query = max(counts)
+    pairs = np.zeros(len(recs), dtype=pkg.PAIR_DTYPE)
+    off = 3
+    for i, (a, b, m) in enumerate(recs):
+        pairs[i] = (a, b, m, 0, off)
+        off += min(max(m, 0), max_query) + 3                 # three records of room that nobody owns after every range
+    want = np.full(off * 16, 0xAB, dtype=np.uint8).view(pkg.DMATCH_DTYPE)
+    cache, written = {}, {}
+    for i, (a, b, m) in enumerate(recs):
+        if not (0 <= a < n_frames and 0 <= b < n_frames and m >= 0):
+            continue
+        if (a, b) not in cache:
+            cache[(a, b)] = oracle.bf_match(descs[a], descs[b], hamming)
+        k, o = min(m, counts[a]), int(pairs["match_off"][i])
+        want[o:o + k] = cache[(a, b)][:k]
+        written[i] = k
+    assert sorted(set(written.values())) == [0, 1, 7, 129, 255, 256, 257, 300, 513, 700]
+    batch, table, dt = _plain_tables(ctx, pkg, descs, pkg.GMS_DESC_HAMMING256 if hamming else pkg.GMS_DESC_L2_F32X128)
+    d_pairs = batch._to_dev(pairs, table.device)
+    d_matches = torch.full((off * 16,), 0xAB, dtype=torch.uint8, device=table.device)
+    torch.cuda.synchronize()
+    dt.match_device(d_pairs.data_ptr(), len(pairs), max_query, d_matches.data_ptr(), use_prepared)
+    ctx.synchronize()
+    got = d_matches.cpu().numpy().view(pkg.DMATCH_DTYPE)
+    for i, (a, b, m) in enumerate(recs[:20]):                 # what the oracle's answers must look like, record by record
+        o, k = int(pairs["match_off"][i]), written.get(i, 0)
+        r = got[o:o + k]
+        assert (r["queryIdx"] == np.arange(k)).all() and (r["imgIdx"] == 0).all(), (i, a, b, m)
+        if k and counts[b] == 0:
+            assert (r["trainIdx"] == -1).all() and (r["distance"] == np.float32(3.402823466e+38)).all()
+        if k and a == b:
+            first = np.array([np.nonzero((descs[a] == row).all(axis=1))[0][0] for row in descs[a][:k]])
+            assert (r["trainIdx"] == first).all() and (r["distance"] == 0).all()
+            assert (first == np.arange(k)).all() == (a == 0)  # frame 2 repeats its rows, frame 0 does not
+    assert got.tobytes() == want.tobytes()
+
+
+def test_hamming_four_rows_per_lane_at_small_sizes(ctx, pkg, oracle, synth):
+    """bf_hamming_kernel<4> (taken from 1024 workgroups on) on frames far below its 1024-row tile and just above it: 1024 pairs."""
+    rng = np.random.default_rng(45)
+    counts = [1, 2, 63, 64, 65, 255, 257, 1025]
+    descs = [rng.integers(0, 256, (n, 32), dtype=np.uint8) for n in counts]
+    descs[7][1000:1025] = descs[5][:25]          # exact hits in the second tile's rows, and repeated train rows
+    descs[6][200:225] = descs[5][:25]
+    distinct = [(a, b) for a in range(len(counts)) for b in range(len(counts))]
+    pairs = _pairs(pkg, counts, distinct * 16)
+    assert len(pairs) >= 1024
+    batch, table, dt = _tables(ctx, pkg, synth, descs, pkg.GMS_DESC_HAMMING256)
+    got = batch.match_pairs(ctx, dt, pairs, use_prepared=False)
+    _check(oracle, descs, pairs[:len(distinct)], got, True)
+    once = sum(counts) * len(counts)
+    assert len(got) == 16 * once
+    assert all(got[k * once:(k + 1) * once].tobytes() == got[:once].tobytes() for k in range(1, 16))
+    assert got.tobytes() == batch.match_pairs(ctx, dt, pairs).tobytes()      # the matrix-core kernel, the whole array
+
+
+def test_hamming_extreme_rows_on_the_fp4_path(ctx, pkg, oracle, synth):
+    """Rows of all zeros, all ones, one bit and 255 bits and exact complements (bf_ties_ref.hamming_extreme_frames): distances 0, 1,
+    255 and 256, accumulators down to -256 plus the row's fraction, at the first and last rows of blocks and of frames, with ties
+    between the lane halves of a block and between blocks."""
+    descs = bf_ties_ref.hamming_extreme_frames()
+    counts = [len(d) for d in descs]
+    batch, table, dt = _tables(ctx, pkg, synth, descs, pkg.GMS_DESC_HAMMING256)
+    pairs = _pairs(pkg, counts, [(a, b) for a in range(len(counts)) for b in range(len(counts))])
+    for use_prepared in (True, False):
+        got = batch.match_pairs(ctx, dt, pairs, use_prepared)
+        _check(oracle, descs, pairs, got, True)
+        assert {0.0, 1.0, 255.0, 256.0} <= set(got["distance"].tolist())
+    x_in_y = got[int(pairs["match_off"][1]):][:counts[0]]                     # frame 0 -> frame 1
+    assert x_in_y["trainIdx"][[5, 6, 7]].tolist() == [3, 36, 45] and (x_in_y["distance"][[5, 6, 7]] == 0).all()
+
+
+def test_l2_values_at_the_edge_of_the_integer_test(ctx, pkg, oracle, synth):
+    """One element of 255.5, 256, -1, 1e20, NaN or +inf -- the last of a frame's last row or the first of its first -- flags that
+    frame and no other (-0.0 and 255.0 are legal), its pairs take the loop kernel, and every pair is the oracle's byte for byte:
+    rows with NaN or an overflowing square never win and, as queries, find nothing."""
+    descs, flagged = bf_ties_ref.l2_edge_frames()
+    counts = [len(d) for d in descs]
+    batch, table, dt = _tables(ctx, pkg, synth, descs, pkg.GMS_DESC_L2_F32X128)
+    # the prepared block: [total][128] int8 | [total] int32 | [n_frames] u32 flags (bf_prepared_bytes)
+    flags = dt.d_prep.cpu().numpy()[table.total * 132:][:4 * len(descs)].view(np.uint32)
+    assert (flags != 0).tolist() == flagged
+    pairs = _pairs(pkg, counts, bf_ties_ref.l2_edge_pairs(len(descs)))
+    got = batch.match_pairs(ctx, dt, pairs)
+    _check(oracle, descs, pairs, got, False)
+    last = got[int(pairs["match_off"][-2]):][:counts[-1]]                     # the all-NaN frame against itself
+    assert (last["trainIdx"] == -1).all() and (last["distance"] == np.float32(3.402823466e+38)).all()
 
 
 @pytest.mark.parametrize("kind", ["orb", "sift"])

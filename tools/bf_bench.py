@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Diagnostic: throughput of the brute-force matcher (gms_bfmatch_device) on 10k x 10k frames, and of matcher + GMS filter
-back to back. Run on the GPU box: python tools/bf_bench.py [orb|sift] [pairs]"""
+back to back. Run on the GPU box: python tools/bf_bench.py [orb|sift] [pairs] [timed repeats, default 3]"""
 import importlib
 import json
 import os
@@ -21,6 +21,7 @@ kind = sys.argv[1] if len(sys.argv) > 1 else "orb"
 use_prepared = "valu" not in kind
 kind = kind.replace("-valu", "")
 n_pairs = int(sys.argv[2]) if len(sys.argv) > 2 else 256
+reps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
 n_kp, size = 10000, (1920, 1080)
 n_frames = 32
 while n_frames * (n_frames - 1) // 2 < n_pairs:
@@ -53,7 +54,6 @@ for with_filter in (False, True):
     run(with_filter)
     ctx.synchronize()
     t0 = time.perf_counter()
-    reps = 3
     for _ in range(reps):
         run(with_filter)
     ctx.synchronize()
