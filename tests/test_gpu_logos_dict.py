@@ -1,12 +1,15 @@
 """GPU: the LOGOS dictionary trainer (gms_logos_dict_train_device / gms_logos_dict_train, DESIGN.md §6b "Training the dictionary")
-against the numpy statement tests/logos_dict_ref.py, byte for byte: dictionaries, records and labels."""
+against the numpy statement tests/logos_dict_ref.py, byte for byte: dictionaries, records and labels. The tests named test_case_*
+run the inputs of tests/logos_dict_cases.py, which tests/test_logos_dict_ref.py shows to leave the first pass of each kernel loop."""
 import importlib
 import os
 
 import numpy as np
 import pytest
 
+import logos_dict_cases as cases
 import logos_dict_ref as ref
+from logos_dict_cases import clustered_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -16,20 +19,6 @@ HAMMING, L2 = ref.HAMMING, ref.L2
 
 def _batch():
     return importlib.import_module("sfm-gms_amd.batch")
-
-
-def clustered_rows(kind, n, seed, n_centres=12):
-    """Rows around a few centres (so that k-means has something to find), with repeats among them."""
-    rng = np.random.default_rng(seed)
-    which = rng.integers(0, n_centres, n)
-    if kind == L2:
-        centres = rng.uniform(0.0, 200.0, (n_centres, 128)).astype(np.float32)
-        rows = np.rint(centres[which] + rng.normal(0.0, 12.0, (n, 128))).astype(np.float32)    # SIFT-like: small integers
-        rows[n // 2:] += rng.uniform(-0.5, 0.5, (n - n // 2, 128)).astype(np.float32)          # and rows that are not
-        return np.clip(rows, -4096.0, 4096.0).astype(np.float32)
-    centres = rng.integers(0, 256, (n_centres, 32), dtype=np.uint8)
-    flips = (rng.random((n, 256)) < 0.12)
-    return centres[which] ^ np.packbits(flips, axis=1)
 
 
 def check_against_statement(ctx, sets, kind, n_words, attempts=3, max_iters=100, seed=0):
@@ -215,3 +204,87 @@ def test_unusable_offsets_fail_their_set_alone(ctx, kind):
     assert want_rec["status"].tolist() == [0, ref.GMS_ERR_BAD_ARG, ref.GMS_ERR_BAD_ARG, ref.GMS_ERR_BAD_ARG]
     first = ref.train(rows, [0, 500, 0, 500, 1200], kind, 8, 2, 12, 6)[1]["status"].tolist()
     assert first == [0, ref.GMS_ERR_BAD_ARG, ref.GMS_ERR_BAD_ARG, 0]
+
+
+# ---- tests/logos_dict_cases.py: past one scan pass, one tile, 256 sets ----------------------------------------------------------------
+def check_case(ctx, name, kind, *key):
+    """The GPU on a case's inputs against the statement's answer (computed once per session) -> (dictionaries, records, labels)."""
+    sets, args = cases.inputs(name, kind, *key)
+    dic, rec, labels = _batch().logos_dictionary(ctx, sets, kind, **args)
+    labels = np.concatenate(labels)
+    want_dic, want_rec, want_labels = cases.expected(name, kind, *key)
+    for s in np.flatnonzero((rec != want_rec) | (dic != want_dic).any(axis=(1, 2)))[:10]:
+        print(f"set {s}: n={len(sets[s])} got {rec[s]} want {want_rec[s]}")
+    print(f"{len(sets)} sets, {len(labels)} rows: {int((labels != want_labels).sum())} labels differ; first records {rec[:4]}")
+    assert rec.tobytes() == want_rec.tobytes()
+    assert dic.tobytes() == want_dic.tobytes()
+    assert labels.tobytes() == want_labels.tobytes()
+    return dic, rec, labels
+
+
+@pytest.mark.parametrize("kind", [HAMMING, L2])
+def test_case_long_sets_scan_several_chunks_per_thread(ctx, kind):
+    """Sets of 256, 257 and 514 chunks behind a short one: seed_pick_kernel's scan with one, two and three chunks per thread, its
+    bisection over hundreds of entries, update_kernel over hundreds of passes."""
+    dic, rec, _ = check_case(ctx, "long_sets", kind)
+    assert (rec["status"] == 0).all() and (rec["iterations"] >= 2).all()
+
+
+def test_case_max_rows_set_and_one_row_more(ctx):
+    """Hamming: 2^20 rows (4096 chunks, 16 per thread of the scan) train; 2^20 + 1 rows are refused."""
+    dic, rec, labels = check_case(ctx, "max_rows", HAMMING)
+    assert rec["status"].tolist() == [0, ref.GMS_ERR_BAD_ARG] and rec["iterations"][0] == 2
+    assert dic[0].any() and not dic[1].any() and (labels[:1 << 20] >= 0).all() and (labels[1 << 20:] == -1).all()
+
+
+@pytest.mark.parametrize("kind", [HAMMING, L2])
+def test_case_zero_weight_runs_make_the_prefix_flat(ctx, kind):
+    """Five distinct rows in long runs, six words: chunks without weight in front, behind and in runs of over a hundred; three
+    candidates with equal potentials; the last centre drawn with no weight left."""
+    dic, rec, _ = check_case(ctx, "zero_weight_runs", kind)
+    assert rec["status"].tolist() == [0] and rec["compactness"].tolist() == [0] and rec["empty_clusters"].tolist() == [1]
+
+
+@pytest.mark.parametrize("kind,n_words", [(HAMMING, 512), (HAMMING, 513), (HAMMING, 1030), (L2, 129)])
+def test_case_many_words_fill_more_than_one_tile(ctx, kind, n_words):
+    """One full tile, one word more, three tiles: labels of the later tiles, and rows equally near to words of two tiles."""
+    dic, rec, labels = check_case(ctx, "many_words", kind, n_words)
+    assert rec["status"].tolist() == [0] and labels.max() >= min(n_words - 1, 1024)
+
+
+@pytest.mark.parametrize("kind", [HAMMING, L2])
+def test_case_many_sets_more_than_one_pass_of_the_plan(ctx, kind):
+    """300 sets: plan_kernel's strided loop past its first pass, locate() over 301 entries, failed sets at both ends and at 255 / 256."""
+    sets, args = cases.many_sets(kind)
+    dic, rec, labels = check_case(ctx, "many_sets", kind)
+    assert rec["status"].tolist() == cases.many_sets_statuses(kind).tolist()
+    off = cases.flat(sets, kind)[1]
+    for s in np.flatnonzero(rec["status"] != 0):
+        assert not dic[s].any() and (labels[off[s]:off[s + 1]] == -1).all()
+    set_of_row = np.repeat(np.arange(len(sets)), np.diff(off))
+    assert (labels[rec["status"][set_of_row] == 0] >= 0).all()
+
+
+def test_case_l2_domain_edge_has_the_largest_sums(ctx):
+    """Rows at the corners of [-4096, 4096]^128: weights near 2^41, a compactness above 2^47, sums of q near 2^32 per row."""
+    dic, rec, _ = check_case(ctx, "l2_domain_edge", L2)
+    assert rec["status"].tolist() == [0] and int(rec["compactness"][0]) > 2 ** 47
+    for x in cases.just_outside_the_domain():
+        d, r, lab = _batch().logos_dictionary(ctx, [x], L2, 8, 1, 2)
+        assert r["status"].tolist() == [ref.GMS_ERR_DOMAIN] and not d.any() and (lab[0] == -1).all()
+
+
+def test_case_l2_rounding_ties_are_rounded_to_even(ctx):
+    """Elements of the form (k + 0.5) 2^-20: the statement's bytes come out only with ties to even (the CPU test shows that rounding
+    half away from zero gives other bytes on this input)."""
+    dic, rec, _ = check_case(ctx, "l2_rounding_ties", L2)
+    assert rec["status"].tolist() == [0] and rec["iterations"][0] >= 2
+
+
+@pytest.mark.parametrize("kind", [HAMMING, L2])
+@pytest.mark.parametrize("corner", ["one_iteration", "sixteen_attempts", "rows_equal_words", "rows_equal_words_with_repeats"])
+def test_case_launch_corners(ctx, kind, corner):
+    dic, rec, _ = check_case(ctx, "launch_corners", kind, corner)
+    assert (rec["status"] == 0).all()
+    if corner == "one_iteration":
+        assert (rec["iterations"] == 1).all()

@@ -1,15 +1,18 @@
-"""-m gpu: the six entry points that work in a caller's workspace -- detect, describe, detect-pyramid, stereo_bm, portrait and
-bf_select `_device` -- given EXACTLY gms_*_workspace_bytes: the workspace is the 256-byte aligned start of a buffer filled with
+"""-m gpu: the seven entry points that work in a caller's workspace -- detect, describe, detect-pyramid, stereo_bm, portrait,
+bf_select and logos_dict_train `_device` -- given EXACTLY gms_*_workspace_bytes: the workspace is the 256-byte aligned start of a buffer filled with
 0x5A that is 4096 bytes longer. The result equals what the entry point's own test expects (the same CPU statements), and the 4096
 bytes behind the workspace still hold 0x5A: a layout (sfm-gms_amd/csrc/ws_layout.h) whose total is smaller than what its launcher
 walks would write there. Three images or pairs with sides just above each entry point's minimum, so that no region's size is a
-multiple of its alignment."""
+multiple of its alignment. The dictionary trainer (sets of 257, 5 and 300 rows) gets guards behind its three outputs as well, and
+since the fill is not zero it also shows that no kernel of it relies on a clean workspace."""
 import importlib
 
 import numpy as np
 import pytest
 
 import bf_select_ref
+import logos_dict_cases
+import logos_dict_ref
 import portrait_ref
 import pyramid_ref
 import stereo_bm_ref
@@ -168,3 +171,39 @@ def test_bf_select(ctx, pkg, cross):
         assert out[off:off + len(want)].tobytes() == want.tobytes(), (a, b)
         assert (int(res["n_candidates"][k]), int(res["n_ratio"][k]), res["d_min"][k]) == (len(d), n_ratio, dm)
     g.check()
+
+
+@pytest.mark.parametrize("kind", [logos_dict_ref.HAMMING, logos_dict_ref.L2])
+def test_logos_dict_train(ctx, kind):
+    import torch
+    sets, args = logos_dict_cases.workspace_guard_sets(kind)
+    rows, off = logos_dict_cases.flat(sets, kind)
+    # three rows in front of the first set and five behind the last belong to no set
+    lead, total = 3, len(rows) + 8
+    all_rows = np.concatenate([rows[:lead], rows, rows[:total - lead - len(rows)]])
+    off = off + lead
+    row_bytes = all_rows[0].nbytes
+    g = Guarded(ctx.logos_dict_workspace_bytes(kind, total, 3, args["n_words"], args["attempts"], args["max_iters"]))
+    g_dict, g_res = Guarded(3 * args["n_words"] * row_bytes), Guarded(3 * logos_dict_ref.DICT_RESULT_DTYPE.itemsize)
+    g_labels = Guarded(4 * total)
+    d_rows = torch.from_numpy(all_rows.view(np.uint8).reshape(-1)).cuda()
+    d_off = torch.from_numpy(off).cuda()
+    torch.cuda.synchronize()
+    ctx.logos_dict_train_device(kind, d_rows.data_ptr(), d_off.data_ptr(), 3, total, args["n_words"], args["attempts"], args["max_iters"],
+                                args["seed"], g.ws.data_ptr(), g.ws_bytes, g_dict.ws.data_ptr(), g_res.ws.data_ptr(), g_labels.ws.data_ptr())
+    ctx.synchronize()
+    want_dic, want_rec, want_labels = logos_dict_ref.train(all_rows, off, kind, **args)
+    # the statement's answer does not depend on where the sets lie among the rows
+    same = logos_dict_cases.expected("workspace_guard", kind)
+    assert want_dic.tobytes() == same[0].tobytes() and want_rec.tobytes() == same[1].tobytes()
+    rec = g_res.ws.cpu().numpy().view(logos_dict_ref.DICT_RESULT_DTYPE)
+    labels = g_labels.ws.cpu().numpy().view(np.int32)
+    print(rec, want_rec)
+    assert rec.tobytes() == want_rec.tobytes() and rec["status"].tolist() == [0, logos_dict_ref.GMS_ERR_BAD_ARG, 0]
+    assert g_dict.ws.cpu().numpy().tobytes() == want_dic.tobytes()
+    in_a_set = np.zeros(total, bool)
+    in_a_set[off[0]:off[-1]] = True
+    assert labels[in_a_set].tobytes() == want_labels[in_a_set].tobytes() and (want_labels[~in_a_set] == -1).all()
+    assert (labels[~in_a_set] == np.frombuffer(bytes([FILL] * 4), np.int32)[0]).all(), "labels of rows that belong to no set were written"
+    for guard in (g, g_dict, g_res, g_labels):
+        guard.check()

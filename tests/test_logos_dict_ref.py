@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import logos_dict_cases as cases
 import logos_dict_ref as ref
 import logos_words_ref
 
@@ -280,3 +281,205 @@ def test_python_layer_checks_its_arguments_first(pkg):
         pipeline.dictionary_training_options({"rows": "second"})
     assert pipeline.dictionary_training_options(True) == {"rows": "first", "n_words": 50, "attempts": 3, "max_iters": 100, "seed": 0}
     assert pipeline.dictionary_training_options({"n_words": 100, "rows": "all"})["n_words"] == 100
+
+
+# ---- the cases of tests/logos_dict_cases.py reach the regimes they are named for ----------------------------------------------------
+# The GPU is held to the statement's bytes on these inputs in tests/test_gpu_logos_dict.py; here the statement's own trace shows
+# that each input makes the kernels leave the first pass of the loop it is there for.
+def seeding_traces(rows, kind, args, set_index):
+    """Per attempt: (the centres' rows, the trace of seed_centres)."""
+    out = []
+    for a in range(args["attempts"]):
+        trace = []
+        chosen = ref.seed_centres(rows, kind, args["n_words"], args["seed"], set_index, a, trace=trace)
+        out.append((chosen, trace))
+    return out
+
+
+def assert_candidates_spread(rows, kind, args, set_index, min_chunks):
+    cands = np.array([c for _, trace in seeding_traces(rows, kind, args, set_index) for t in trace for c in t["candidates"]])
+    chunks = np.unique(cands // cases.CHUNK)
+    print(f"set {set_index}: {len(rows)} rows, {cases.n_chunks(len(rows))} chunks; {len(cands)} candidates in {len(chunks)} chunks, "
+          f"{int((cands >= len(rows) // 2).sum())} in the upper half, {int((cands >= cases.last_chunk(len(rows))).sum())} in the last chunk")
+    assert len(chunks) >= min_chunks
+    assert (cands >= len(rows) // 2).any()
+    assert (cands >= cases.last_chunk(len(rows))).any()
+
+
+@pytest.mark.parametrize("kind", [HAMMING, L2])
+def test_case_long_sets_scan_several_chunks_per_thread(kind):
+    sets, args = cases.long_sets(kind)
+    assert [len(s) for s in sets] == [300, 65536, 65537, 131329] and (args["n_words"], args["attempts"], args["max_iters"]) == (4, 2, 3)
+    # 256 chunks: the most with one chunk per thread of the scan; 257 and 514: two and three per thread. No long set starts at chunk 0.
+    assert [cases.n_chunks(len(s)) for s in sets] == [2, 256, 257, 514]
+    assert [-(-cases.n_chunks(len(s)) // 256) for s in sets] == [1, 1, 2, 3]
+    assert [len(s) - cases.last_chunk(len(s)) for s in sets[1:]] == [256, 1, 1]
+    for s in range(1, 4):
+        assert ref.set_status(sets[s], kind, args["n_words"]) == 0
+        assert_candidates_spread(sets[s], kind, args, s, 8)
+
+
+def test_case_max_rows_set_and_one_row_more():
+    sets, args = cases.max_rows_sets()
+    assert [len(s) for s in sets] == [1 << 20, (1 << 20) + 1] and (args["n_words"], args["attempts"], args["max_iters"]) == (3, 1, 2)
+    assert cases.n_chunks(len(sets[0])) == 4096      # 16 chunks per thread of the scan
+    assert ref.set_status(sets[0], HAMMING, 3) == 0 and ref.set_status(sets[1], HAMMING, 3) == ref.GMS_ERR_BAD_ARG
+    # two centres are drawn, three trials each, one attempt: six candidates in all, so six distinct chunks is the most there can be
+    assert_candidates_spread(sets[0], HAMMING, args, 0, 6)
+
+
+def longest_zero_run(sums):
+    best = run = 0
+    for v in sums:
+        run = run + 1 if v == 0 else 0
+        best = max(best, run)
+    return best
+
+
+@pytest.mark.parametrize("kind", [HAMMING, L2])
+def test_case_zero_weight_runs_make_the_prefix_flat(kind):
+    sets, args = cases.zero_weight_runs(kind)
+    rows = sets[0]
+    assert len(rows) == 67513 and len(np.unique(rows, axis=0)) == 5 < args["n_words"] == 6
+    assert (args["attempts"], args["max_iters"]) == (2, 3)
+    seen = {"flat run": False, "chunk 0 empty": False, "last chunk empty": False, "equal potentials": False}
+    for a, (chosen, trace) in enumerate(seeding_traces(rows, kind, args, 0)):
+        w = None
+        for t in trace:
+            c = t["centre"]
+            wc = ref.weights(ref.distances(rows, rows[chosen[c - 1]:chosen[c - 1] + 1], kind)[:, 0], kind)
+            w = wc if w is None else np.minimum(w, wc)
+            sums = np.add.reduceat(w, np.arange(0, len(rows), cases.CHUNK))
+            assert int(sums.sum(dtype=np.uint64)) == t["total"]
+            print(f"centre {c}: total {t['total']}, {int((sums == 0).sum())} of {len(sums)} chunks empty, longest run {longest_zero_run(sums)}, "
+                  f"candidates {t['candidates']} potentials {t['potentials']} kept {t['kept']}")
+            if t["total"] > 0:
+                seen["flat run"] |= longest_zero_run(sums) >= 100
+                seen["chunk 0 empty"] |= sums[0] == 0
+                seen["last chunk empty"] |= sums[-1] == 0
+            if len(set(t["potentials"])) == 1:
+                seen["equal potentials"] = True
+                assert t["kept"] == 0
+        assert trace[-1]["centre"] == 5 and trace[-1]["total"] == 0      # the last centre: mulhi64(u, n) on a long set
+        assert trace[-1]["candidates"] == [ref.mulhi64(ref.draw(args["seed"], 0, a, 5, k), len(rows)) for k in range(3)]
+    assert all(seen.values()), seen
+
+
+@pytest.mark.parametrize("kind,n_words", [(HAMMING, 512), (HAMMING, 513), (HAMMING, 1030), (L2, 129)])
+def test_case_many_words_fill_more_than_one_tile(kind, n_words):
+    sets, args = cases.many_words(kind, n_words)
+    assert len(sets[0]) == (1100 if kind == HAMMING else 400) and (args["attempts"], args["max_iters"]) == (1, 3)
+    dic, rec, labels = (v[0] if i != 2 else v for i, v in enumerate(cases.expected("many_words", kind, n_words)))
+    assert rec["status"] == 0
+    tiles = cases.tiles_at_minimum(sets[0], dic, kind)
+    print(f"{n_words} words: record {rec}, highest label {labels.max()}, {int((tiles >= 2).sum())} rows nearest to words of two tiles")
+    if n_words == 512:      # exactly one full tile: its last word is used, and there is no second tile to tie with
+        assert labels.max() == 511
+        return
+    assert labels.max() >= (128 if kind == L2 else 512)
+    if n_words == 1030:
+        assert labels.max() >= 1024
+    # such a row's label is the first word at the minimum, which lies in the earlier tile: "lowest index wins" across tiles
+    assert (tiles >= 2).any()
+
+
+@pytest.mark.parametrize("kind", [HAMMING, L2])
+def test_case_many_sets_more_than_one_pass_of_the_plan(kind):
+    sets, args = cases.many_sets(kind)
+    assert len(sets) == 300 and all(len(s) == 3 if k in cases.TOO_FEW else 6 <= len(s) <= 14 for k, s in enumerate(sets))
+    assert (args["n_words"], args["attempts"], args["max_iters"]) == (4, 2, 5)
+    dic, rec, labels = cases.expected("many_sets", kind)
+    assert rec["status"].tolist() == cases.many_sets_statuses(kind).tolist()
+    assert rec["status"][[0, 255, 256, 299]].tolist() == [ref.GMS_ERR_BAD_ARG] * 4
+    assert rec["status"][257] == (ref.GMS_ERR_DOMAIN if kind == L2 else 0) and int((rec["status"] != 0).sum()) == (5 if kind == L2 else 4)
+    off = cases.flat(sets, kind)[1]
+    for s in np.flatnonzero(rec["status"] != 0):
+        assert not dic[s].any() and (labels[off[s]:off[s + 1]] == -1).all() and rec["attempt"][s] == -1
+    for s in (1, 254, 258, 298):      # the neighbours of the failed sets are what they are alone
+        alone = ref.train_set(sets[s], kind, set_index=s, **args)
+        assert dic[s].tobytes() == alone[0].tobytes() and rec[s].tobytes() == alone[1].tobytes()
+        assert labels[off[s]:off[s + 1]].tobytes() == alone[2].tobytes()
+
+
+def test_case_l2_domain_edge_has_the_largest_sums():
+    sets, args = cases.l2_domain_edge()
+    rows = sets[0]
+    assert len(rows) == 600 and (args["n_words"], args["attempts"], args["max_iters"]) == (8, 2, 6)
+    assert (rows == 4096.0).any() and (rows == -4096.0).any() and np.abs(rows).max() == 4096.0
+    corners = np.delete(rows, np.arange(0, 600, 7), axis=0)
+    assert (np.abs(corners) == 4096.0).all() and (np.abs(rows[::7]) < 4096.0).any()
+    dic, rec, labels = cases.expected("l2_domain_edge", L2)
+    print(f"record {rec[0]}: compactness 2^{np.log2(float(rec[0]['compactness'])):.2f}")
+    assert rec[0]["status"] == 0 and int(rec[0]["compactness"]) > 2 ** 47
+    for x in cases.just_outside_the_domain():
+        assert np.abs(x).max() > 4096.0 and np.float32(np.abs(x).max()) == np.nextafter(np.float32(4096.0), np.float32(np.inf))
+        assert ref.set_status(x, L2, 8) == ref.GMS_ERR_DOMAIN
+
+
+def test_case_l2_rounding_ties_tell_ties_to_even_from_half_away(monkeypatch):
+    sets, args, blob = cases.l2_rounding_ties()
+    rows = sets[0]
+    scaled = rows.astype(np.float64) * 1048576.0
+    ties = np.abs(scaled - np.floor(scaled)) == 0.5
+    tie_rows = ties.all(axis=1)
+    # the ordinary rows have elements that are no ties (of those with |x| >= 4 every other float is one: the spacing there is 2^-21)
+    assert tie_rows.sum() == len(rows) - 2 * len(cases.TIE_BLOB_SIZES) and (~ties[~tie_rows]).sum() > 128
+    assert (scaled[ties] > 0).any() and (scaled[ties] < 0).any()
+    even = np.floor(scaled[ties]) % 2 == 0          # k + 0.5 with k even: rint rounds down; with k odd: up
+    assert even.any() and (~even).any()
+    dic, rec, labels = cases.expected("l2_rounding_ties", L2)
+    assert rec[0]["status"] == 0 and rec[0]["empty_clusters"] == 0 and rec[0]["iterations"] >= 2      # an update ran
+    counts = np.bincount(labels[:len(rows)], minlength=args["n_words"])
+    assert sorted(counts.tolist()) == cases.TIE_BLOB_SIZES          # one cluster per blob: odd and even member counts
+    assert all(len(set(labels[blob == b])) == 1 for b in range(len(counts)))
+
+    def half_away(x):
+        v = np.asarray(x, np.float32).astype(np.float64) * 1048576.0
+        return (np.sign(v) * np.floor(np.abs(v) + 0.5)).astype(np.int64)
+
+    assert half_away(np.float32(1.5 * 2.0 ** -20)) == 2 and half_away(np.float32(2.5 * 2.0 ** -20)) == 3 and half_away(np.float32(-0.5 * 2.0 ** -20)) == -1
+    monkeypatch.setattr(ref, "quantise", half_away)
+    other = ref.train_set(rows, L2, **args)
+    assert other[2].tobytes() == labels.tobytes() and other[0].tobytes() != dic[0].tobytes()
+    differ = (other[0] != dic[0]).any(axis=1)
+    print(f"half away from zero changes {int((other[0] != dic[0]).sum())} elements, in the clusters of {counts[differ].tolist()} rows")
+    assert (counts[differ] % 2 == 0).any() and (counts[differ] % 2 == 1).any()
+
+
+@pytest.mark.parametrize("kind", [HAMMING, L2])
+def test_case_launch_corners(kind):
+    corners = cases.launch_corners(kind)
+    # one assignment, no update: the labels are those of the seed centres
+    sets, args = corners["one_iteration"]
+    assert args["max_iters"] == 1
+    for s, rows in enumerate(sets):
+        dic, rec, labels, runs = ref.train_set(rows, kind, set_index=s, detail=True, **args)
+        win = runs[rec["attempt"]]
+        assert rec["status"] == 0 and rec["iterations"] == 1 and dic.tobytes() == rows[win["seed_rows"]].tobytes()
+        assert labels.tobytes() == ref.assign(rows, rows[win["seed_rows"]], kind)[0].tobytes()
+        assert rec["compactness"] == win["seed_compactness"]
+    sets, args = corners["sixteen_attempts"]
+    assert args["attempts"] == 16
+    for s, rows in enumerate(sets):
+        dic, rec, labels, runs = ref.train_set(rows, kind, set_index=s, detail=True, **args)
+        comps = [r["compactness"] for r in runs]
+        assert len(runs) == 16 and len(set(comps)) > 1 and rec["attempt"] == comps.index(min(comps))
+    sets, args = corners["rows_equal_words"]
+    assert len(sets[0]) == args["n_words"] == len(np.unique(sets[0], axis=0))
+    dic, rec, labels = ref.train_set(sets[0], kind, set_index=0, **args)
+    assert rec["status"] == 0 and rec["compactness"] == 0 and rec["empty_clusters"] == 0 and sorted(labels.tolist()) == list(range(9))
+    sets, args = corners["rows_equal_words_with_repeats"]
+    assert len(sets[0]) == args["n_words"] == 9 and len(np.unique(sets[0], axis=0)) == 6
+    dic, rec, labels, runs = ref.train_set(sets[0], kind, set_index=0, detail=True, **args)
+    assert rec["status"] == 0 and rec["compactness"] == 0 and rec["empty_clusters"] == 3
+    trace = []
+    ref.seed_centres(sets[0], kind, 9, args["seed"], 0, 0, trace=trace)
+    assert [t["total"] for t in trace[-3:]] == [0, 0, 0] and trace[-4]["total"] > 0      # the last three centres: nothing left to weigh
+
+
+@pytest.mark.parametrize("kind", [HAMMING, L2])
+def test_case_workspace_guard_sets(kind):
+    sets, args = cases.workspace_guard_sets(kind)
+    assert [len(s) for s in sets] == [257, 5, 300] and args["n_words"] == 7
+    dic, rec, labels = cases.expected("workspace_guard", kind)
+    assert rec["status"].tolist() == [0, ref.GMS_ERR_BAD_ARG, 0] and (rec["iterations"][[0, 2]] >= 2).all()      # updates ran
