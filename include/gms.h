@@ -493,6 +493,30 @@ int gms_detect_pyramid_grad_batch_device(gms_ctx* ctx, const uint8_t* d_images, 
 int gms_describe_grad_device(gms_ctx* ctx, const uint8_t* d_image, int width, int height, gms_keypoint* d_keypoints, int n,
                              void* d_workspace, size_t workspace_bytes, float* d_rows128, int32_t* d_status);
 
+/* ---- from photographs to the tables ---------------------------------------------------------------------
+ * The reference hands BGR Mats to every entry point (main.cpp:21-75) and gets one keypoint vector per image back from
+ * detectAndCompute; the detector above takes grey planes and leaves [n, max_keypoints] blocks, the tables (gms_normalize_device,
+ * gms_bf_prepare_device, gms_logos_prepare_device, gms_two_view_batch_device) take all frames back to back with an offset per frame.
+ * These two calls stand between them, so that neither pixels nor keypoints nor rows pass through the host. Both run on the context's
+ * stream, allocate nothing and wait for nothing, so they can be captured into a graph.
+ *
+ * gms_bgr_to_gray_device: n_images of height x width x 3 bytes, B, G, R interleaved (a CV_8UC3 Mat without padding), back to back ->
+ * n_images grey planes, pitch = width, back to back: grey = (299 R + 587 G + 114 B + 500) / 1000 in integer arithmetic (the weights of
+ * cv::cvtColor's BGR2GRAY; not its fixed-point rounding). Either buffer may start at any byte address.
+ * Errors: GMS_ERR_BAD_ARG (NULL, n_images < 0, width/height outside (0, 65535]). */
+int gms_bgr_to_gray_device(gms_ctx* ctx, const uint8_t* d_bgr, int n_images, int width, int height, uint8_t* d_gray);
+
+/* gms_detect_pack_device: the detector's blocks -> frames back to back. d_frame_off[0] = 0, d_frame_off[i + 1] = d_frame_off[i] +
+ * min(d_counts[i], max_keypoints) (a negative count counts as 0); record and row j of image i go from slot i * max_keypoints + j of
+ * the blocks to slot d_frame_off[i] + j of d_keypoints / d_rows32 / d_rows128, in their order. d_rows32_blocks with d_rows32, and
+ * d_rows128_blocks with d_rows128, may be NULL together (rows the detector did not make). The outputs have room for n_images *
+ * max_keypoints slots; what lies behind slot d_frame_off[n_images] is left as it was. d_frame_off: n_images + 1 values.
+ * Errors: GMS_ERR_BAD_ARG (NULL, n_images outside [1, 65535], max_keypoints < 0, a row pointer without its partner, a pointer that
+ * is not 4-byte aligned). 16-byte aligned buffers are moved with 16-byte accesses. */
+int gms_detect_pack_device(gms_ctx* ctx, const gms_keypoint* d_keypoint_blocks, const uint8_t* d_rows32_blocks, const float* d_rows128_blocks,
+                           const int32_t* d_counts, int n_images, int max_keypoints, gms_keypoint* d_keypoints, uint8_t* d_rows32,
+                           float* d_rows128, int64_t* d_frame_off);
+
 /* ---- LOGOS match filter -----------------------------------------------------------------------
  * cv::xfeatures2d::matchLOGOS(keypoints1, keypoints2, nn1, nn2, matches1to2) (FeatureMatchUtil.cpp:86-131; DESIGN.md, LOGOS):
  * candidates are the pairs (i, j) with nn1[i] == nn2[j]; a candidate survives if it has local support among the five nearest

@@ -295,6 +295,17 @@ class GmsContext:
         _check(self._lib.gms_describe_grad_device(self._h, d_image, int(width), int(height), d_kp, int(n), d_ws, int(ws_bytes), d_rows128,
                                                   d_status), self._lib, "gms_describe_grad_device")
 
+    # -- from photographs to the tables (gms_bgr_to_gray_device / gms_detect_pack_device; batch.tables_from_detector drives them) ---
+    def bgr_to_gray_device(self, d_bgr, n_images, width, height, d_gray):
+        _check(self._lib.gms_bgr_to_gray_device(self._h, d_bgr or None, int(n_images), int(width), int(height), d_gray or None), self._lib,
+               "gms_bgr_to_gray_device")
+
+    def detect_pack_device(self, d_kp_blocks, d_rows32_blocks, d_rows128_blocks, d_counts, n_images, max_keypoints, d_kp, d_rows32, d_rows128,
+                           d_frame_off):
+        _check(self._lib.gms_detect_pack_device(self._h, d_kp_blocks or None, d_rows32_blocks or None, d_rows128_blocks or None, d_counts or None,
+                                                int(n_images), int(max_keypoints), d_kp or None, d_rows32 or None, d_rows128 or None,
+                                                d_frame_off or None), self._lib, "gms_detect_pack_device")
+
     # -- LOGOS on resident frames (gms_logos_*; batch.LogosTable / logos_pairs / logos_words drive them) ---------------------------
     def logos_table_bytes(self, total_kp, n_frames, n_words):
         return int(self._lib.gms_logos_table_bytes(int(total_kp), int(n_frames), int(n_words)))
@@ -483,6 +494,49 @@ def bruteForceMatch(desc1, desc2, kind, cross_check=True, distance_coef=4.0, max
     _check(rc, lib, "gms_bf_match_select")
     got = out[: n.value].copy()
     return (got, res[0]) if detail else got
+
+
+def structureFromMotion(img1, img2, camera, dist=None, method="logos", ctx=None, **params):
+    """The reference's structureFromMotion(imgL, imgR, cameraMatrix, distCoeffs, points3D, ..., algo) (SfMUtil.cpp:4-83, called at
+    main.cpp:71-75) on two photographs of one size, [H, W] grey or [H, W, 3] BGR, 8-bit, host arrays or device tensors: keypoints and
+    rows of both, the method's matches, findEssentialMat(RANSAC, 0.7, 1.0), recoverPose, undistortPoints and triangulation, all on
+    the GPU (pipeline.run_images; keypoints and rows do not pass through the host on the way).
+
+    method  "bf"     algo 1, bruteForceMatch (cross-check, sort, ratio prune; FeatureMatchUtil.cpp:20-31)
+            "gms"    algo 2, nearest neighbour then matchGMS(true, true) (FeatureMatchUtil.cpp:66-69)
+            "logos"  algo 3, matchLOGOS on 50 visual words trained on image 1's rows (FeatureMatchUtil.cpp:101-102); what main.cpp:74 passes
+    camera = (fx, fy, cx, cy), dist = (k1, k2, p1, p2, k3) or None. params: run_images' keywords (threshold, max_keypoints, n_levels,
+    descriptor, thresholdFactor, prob, ransac_threshold, cross_check, distance_coef, max_size, dictionary, train_dictionary, ...).
+    The keypoints and rows are this library's own, not SIFT's.
+
+    Returns a dict: points3D float64 [k, 3] (the inliers' points, in their order), R [3, 3], t [3], E [3, 3], matches (the method's
+    surviving DMATCH_DTYPE records), mask (uint8 per surviving match: 0 = not an inlier of the pose), keypoints1, keypoints2
+    (KEYPOINT_DTYPE), two_view (the pair's TWO_VIEW_DTYPE record: counts, iterations, reprojection sums) and detail (run_images'
+    record, with `tables`: the resident FrameTable and DescriptorTable). A pair without a pose raises GmsError with the two-view status."""
+    from . import pipeline
+    if method not in pipeline.METHODS:
+        raise ValueError(f"unknown method {method!r}")
+    shapes = [tuple(im.shape) for im in (img1, img2)]
+    if len(shapes[0]) not in (2, 3) or (len(shapes[0]) == 3 and shapes[0][2] != 3):
+        raise ValueError("img1 / img2: [H, W] grey or [H, W, 3] BGR")
+    if shapes[0] != shapes[1]:
+        raise ValueError("img1 and img2: one size and one channel count")
+    opts = dict(params)
+    if method == "gms":
+        opts.setdefault("withRotation", True)
+        opts.setdefault("withScale", True)
+    if method == "logos" and opts.get("dictionary") is None:
+        opts.setdefault("train_dictionary", True)
+    r = pipeline.run_images(ctx or default_context(), [img1, img2], camera, dist, method=method, pairs=[(0, 1)], keep_tables=True, **opts)
+    frames = r["tables"][0]
+    tv, off, k = r["two_view"][0], int(r["pairs"]["match_off"][0]), int(r["results"]["n_inliers"][0])
+    if int(r["results"]["status"][0]) != GMS_OK or int(tv["status"]) != GMS_OK:
+        raise GmsError(int(r["results"]["status"][0]) or int(tv["status"]), "structureFromMotion: no pose for this pair")
+    kp = frames.d_kp.cpu().numpy()[: frames.total * KEYPOINT_DTYPE.itemsize].view(KEYPOINT_DTYPE)
+    f = frames.frame_off_host
+    return dict(points3D=r["points3d"][off:off + int(tv["n_triangulated"])].copy(), R=tv["R"].copy(), t=tv["t"].copy(), E=tv["E"].copy(),
+                matches=r["out"][off:off + k].copy(), mask=r["mask"][off:off + k].copy(), keypoints1=kp[f[0]:f[1]].copy(),
+                keypoints2=kp[f[1]:f[2]].copy(), two_view=tv, detail=r)
 
 
 def default_context():

@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from .api import GmsContext, logos_dict_args
-from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_ERR_CAPACITY, KEYPOINT_DTYPE, LOGOS_DICT_RESULT_DTYPE, LOGOS_RESULT_DTYPE, PAIR_DTYPE,
+from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128, GMS_ERR_CAPACITY, KEYPOINT_DTYPE, LOGOS_DICT_RESULT_DTYPE, LOGOS_RESULT_DTYPE, PAIR_DTYPE,
                     RESULT_DTYPE, concat_frames, desc_layout, portrait_params, stereo_bm_params)
 
 
@@ -85,6 +85,27 @@ class FrameTable:
                              self.n_frames, self.total, self.d_pts.data_ptr())
         ctx.synchronize()
 
+    @classmethod
+    def from_device(cls, ctx, d_kp, d_frame_off, sizes):
+        """The table of keypoints that are on the device already: d_kp a tensor of KEYPOINT_DTYPE records, all frames back to back,
+        d_frame_off int64 [n_frames + 1] (what gms_detect_pack_device leaves). The offsets are read back -- the one readback: they size
+        d_pts and are frame_off_host -- the keypoints are not. Waits for the context's stream first (the offsets come from it)."""
+        self = cls.__new__(cls)
+        self.ctx, self.device = ctx, d_kp.device
+        ctx.synchronize()
+        self.frame_off_host = d_frame_off.cpu().numpy().astype(np.int64)
+        self.n_frames, self.total = len(self.frame_off_host) - 1, int(self.frame_off_host[-1])
+        wh = np.asarray(sizes, dtype=np.int32).reshape(-1, 2)
+        assert wh.shape[0] == self.n_frames
+        self.d_kp, self.d_frame_off = d_kp, d_frame_off
+        self.d_wh = torch.from_numpy(wh.reshape(-1).copy()).to(self.device)
+        self.d_pts = torch.zeros(ctx.frame_table_bytes(self.total) // 4, dtype=torch.float32, device=self.device)
+        torch.cuda.synchronize(self.device)
+        ctx.normalize_device(self.d_kp.data_ptr(), self.d_frame_off.data_ptr(), self.d_wh.data_ptr(), self.n_frames, self.total,
+                             self.d_pts.data_ptr())
+        ctx.synchronize()
+        return self
+
 
 class DescriptorTable:
     """Descriptors of all frames of a sequence, resident on the GPU beside a FrameTable (descriptor i of a frame belongs to
@@ -105,6 +126,26 @@ class DescriptorTable:
         ctx.bf_prepare_device(self.kind, self.d_desc.data_ptr(), frames.d_frame_off.data_ptr(), frames.n_frames, frames.total,
                               self.d_prep.data_ptr())
         ctx.synchronize()
+
+    @classmethod
+    def from_device(cls, frames, d_rows, kind):
+        """The table of rows that are on the device already: d_rows a tensor of frames.total rows (or more: the head is used), row i
+        belonging to keypoint i of `frames`. Nothing is read back; `host` is None."""
+        self = cls.__new__(cls)
+        self.ctx, self.kind, self.frames, self.host = frames.ctx, int(kind), frames, None
+        dt, width = desc_layout(self.kind)
+        self.d_desc = d_rows.contiguous().view(torch.uint8).reshape(-1)
+        if self.d_desc.numel() < frames.total * width * np.dtype(dt).itemsize:
+            raise ValueError("one descriptor per keypoint")
+        if self.d_desc.numel() == 0:
+            self.d_desc = torch.zeros(16, dtype=torch.uint8, device=frames.device)
+        nbytes = self.ctx.bf_prepared_bytes(self.kind, frames.total, frames.n_frames)
+        self.d_prep = torch.zeros(max(nbytes, 16), dtype=torch.uint8, device=frames.device)
+        torch.cuda.synchronize(frames.device)
+        self.ctx.bf_prepare_device(self.kind, self.d_desc.data_ptr(), frames.d_frame_off.data_ptr(), frames.n_frames, frames.total,
+                                   self.d_prep.data_ptr())
+        self.ctx.synchronize()
+        return self
 
     def match_device(self, d_pairs, n_pairs, max_query, d_matches, use_prepared=True):
         """gms_bfmatch_device: one match per query row of every pair, written at the pair's match_off (stream-ordered).
@@ -270,6 +311,47 @@ def detect_images_pyramid(ctx, images, threshold=20, max_keypoints=10000, n_leve
     run.run(imgs)
     ctx.synchronize()
     return run.results()
+
+
+def bgr_to_gray(ctx, d_bgr):
+    """gms_bgr_to_gray_device on a uint8 device tensor [n, H, W, 3] (B, G, R; contiguous) -> the grey planes, a device tensor
+    [n, H, W]: (299 R + 587 G + 114 B + 500) // 1000. Stream-ordered on the context's stream."""
+    n, h, w, _ = d_bgr.shape
+    d_gray = torch.zeros((n, h, w), dtype=torch.uint8, device=d_bgr.device)
+    torch.cuda.synchronize(d_bgr.device)
+    ctx.bgr_to_gray_device(d_bgr.data_ptr(), n, w, h, d_gray.data_ptr())
+    return d_gray
+
+
+def pack_detector(run):
+    """gms_detect_pack_device on a DetectPyramid that has run: (d_kp, d_rows32, d_rows128, d_frame_off) -- the images' records and rows
+    back to back in tensors with room for n * max_keypoints of them, and the int64 [n + 1] offsets; d_rows128 is None for "brief".
+    Stream-ordered on the context's stream; nothing is read back."""
+    dev, slots = run.d_kp.device, max(run.n * run.max_keypoints, 1)
+    d_kp = torch.zeros(slots * 28, dtype=torch.uint8, device=dev)
+    d_rows32 = torch.zeros(slots * 32, dtype=torch.uint8, device=dev)
+    d_rows128 = None if run.d_rows128 is None else torch.zeros(slots * 128, dtype=torch.float32, device=dev)
+    d_frame_off = torch.zeros(run.n + 1, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize(dev)
+    run.ctx.detect_pack_device(run.d_kp.data_ptr(), run.d_desc.data_ptr(), None if d_rows128 is None else run.d_rows128.data_ptr(),
+                               run.d_counts.data_ptr(), run.n, run.max_keypoints, d_kp.data_ptr(), d_rows32.data_ptr(),
+                               None if d_rows128 is None else d_rows128.data_ptr(), d_frame_off.data_ptr())
+    return d_kp, d_rows32, d_rows128, d_frame_off
+
+
+def tables_from_detector(run, sizes=None, kind=None):
+    """(FrameTable, DescriptorTable) of a DetectPyramid that has run, without its keypoints or rows passing through the host: the
+    blocks are packed on the device (gms_detect_pack_device), the n + 1 offsets are read back, the tables are built on the packed
+    tensors. sizes: one (width, height) per image (default: the detector's). kind: GMS_DESC_HAMMING256 (the 32-byte rows) or
+    GMS_DESC_L2_F32X128 (the gradient rows; the detector must have made them); default: L2 where there are gradient rows."""
+    if kind is None:
+        kind = GMS_DESC_HAMMING256 if run.d_rows128 is None else GMS_DESC_L2_F32X128
+    desc_layout(kind)
+    if int(kind) == GMS_DESC_L2_F32X128 and run.d_rows128 is None:
+        raise ValueError('GMS_DESC_L2_F32X128 needs a detector with descriptor="grad" or "both"')
+    d_kp, d_rows32, d_rows128, d_frame_off = pack_detector(run)
+    frames = FrameTable.from_device(run.ctx, d_kp, d_frame_off, [(run.w, run.h)] * run.n if sizes is None else sizes)
+    return frames, DescriptorTable.from_device(frames, d_rows32 if int(kind) == GMS_DESC_HAMMING256 else d_rows128, kind)
 
 
 def build_pyramid(ctx, images, n_levels=8, device=None):

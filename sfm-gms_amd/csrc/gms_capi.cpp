@@ -1565,6 +1565,32 @@ int gms_describe_grad_device(gms_ctx* c, const uint8_t* d_image, int width, int 
     return on_ctx(c, [&] { return gms::launch_describe_grad(d_image, width, height, d_keypoints, n, d_workspace, d_rows128, d_status, c->stream); });
 }
 
+// ---- from photographs to the tables (ingest_kernels.hip) ----------------------------------------------------------------------------
+int gms_bgr_to_gray_device(gms_ctx* c, const uint8_t* d_bgr, int n_images, int width, int height, uint8_t* d_gray)
+{
+    if (!c || n_images < 0 || width <= 0 || height <= 0 || width > 65535 || height > 65535) return GMS_ERR_BAD_ARG;
+    if (n_images == 0) return GMS_OK;
+    if (!d_bgr || !d_gray) return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] { return gms::launch_bgr_to_gray(d_bgr, n_images, width, height, d_gray, c->stream); });
+}
+
+int gms_detect_pack_device(gms_ctx* c, const gms_keypoint* d_keypoint_blocks, const uint8_t* d_rows32_blocks, const float* d_rows128_blocks,
+                           const int32_t* d_counts, int n_images, int max_keypoints, gms_keypoint* d_keypoints, uint8_t* d_rows32,
+                           float* d_rows128, int64_t* d_frame_off)
+{
+    if (!c || n_images < 1 || n_images > 65535 || max_keypoints < 0 || !d_counts || !d_frame_off) return GMS_ERR_BAD_ARG;
+    if ((d_rows32_blocks == nullptr) != (d_rows32 == nullptr) || (d_rows128_blocks == nullptr) != (d_rows128 == nullptr)) return GMS_ERR_BAD_ARG;
+    if (max_keypoints > 0 && (!d_keypoint_blocks || !d_keypoints)) return GMS_ERR_BAD_ARG;
+    for (const void* p : {(const void*)d_keypoint_blocks, (const void*)d_rows32_blocks, (const void*)d_rows128_blocks, (const void*)d_counts,
+                          (const void*)d_keypoints, (const void*)d_rows32, (const void*)d_rows128})
+        if (reinterpret_cast<uintptr_t>(p) & 3u) return GMS_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(d_frame_off) & 7u) return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] {
+        return gms::launch_detect_pack(d_keypoint_blocks, d_rows32_blocks, d_rows128_blocks, d_counts, n_images, max_keypoints, d_keypoints, d_rows32,
+                                       d_rows128, d_frame_off, c->stream);
+    });
+}
+
 // ---- LOGOS on resident frames (logos_batch_kernels.hip) ----------------------------------------------------------------------
 int64_t gms_logos_table_bytes(int64_t total_kp, int n_frames, int n_words)
 {

@@ -161,6 +161,11 @@ hipError_t launch_grad_level(int n_images, int w, int h, int quota, void* d_det_
                              gms_keypoint* d_kp, float* d_rows128, hipStream_t stream);
 hipError_t launch_describe_grad(const uint8_t* d_image, int w, int h, gms_keypoint* d_kp, int n, void* d_ws, float* d_rows128, int32_t* d_status,
                                 hipStream_t stream);
+// from photographs to the tables (ingest_kernels.hip): BGR -> grey planes; the detector's blocks -> frames back to back
+hipError_t launch_bgr_to_gray(const uint8_t* d_bgr, int n, int w, int h, uint8_t* d_gray, hipStream_t stream);
+hipError_t launch_detect_pack(const gms_keypoint* d_kp_blocks, const uint8_t* d_rows32_blocks, const float* d_rows128_blocks, const int32_t* d_counts,
+                              int n, int max_keypoints, gms_keypoint* d_kp, uint8_t* d_rows32, float* d_rows128, int64_t* d_frame_off,
+                              hipStream_t stream);
 // batched LOGOS (logos_batch_kernels.hip; layouts in logos_batch.h)
 hipError_t launch_logos_prepare(const gms_keypoint* d_kp, const int64_t* d_frame_off, int n_frames, int64_t total_kp, const int32_t* d_words,
                                 int n_words, void* d_ws, size_t ws_bytes, void* d_table, int n_cus, hipStream_t stream);

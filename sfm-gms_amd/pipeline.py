@@ -14,14 +14,21 @@ method="bf" runs the reference's DEFAULT_SIFT flow (bruteForceMatch, FeatureMatc
     descriptors --gms_bf_select_device (matcher, cross-check, sort, ratio prune)--> survivors
         --gms_two_view_batch_device--> ...                                                                  (with a camera)
 
-torch here is device memory only; every stage is a call into csrc/libgms_hip.so. Used by tools/gms_filter_file.py and the tests."""
+run_images is the same three flows from pixels: grey or BGR images --gms_bgr_to_gray_device--> grey planes
+    --gms_detect_pyramid_(grad_)batch_device--> keypoints and rows --gms_detect_pack_device--> the resident tables --> the stages above.
+
+torch here is device memory only; every stage is a call into csrc/libgms_hip.so. Used by tools/gms_filter_file.py, tools/gms_sfm_pair.py
+and the tests."""
 import numpy as np
 import torch
 
-from .batch import (BfSelect, DescriptorTable, FrameTable, LogosFilter, LogosTable, _to_dev, _words_device, bf_select_table, frame_counts,
-                    frame_pairs_of, logos_dictionary, pair_table)
+from .batch import (BfSelect, DescriptorTable, DetectPyramid, FrameTable, LogosDictionary, LogosFilter, LogosTable, _device, _to_dev,
+                    bf_select_table, bgr_to_gray, frame_counts, frame_pairs_of, logos_dictionary, pair_table, tables_from_detector)
 from .api import logos_dict_args
-from .types import DMATCH_DTYPE, GMS_ERR_CAPACITY, PAIR_DTYPE, RESULT_DTYPE, TWO_VIEW_DTYPE, desc_layout, make_camera
+from .types import (DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128, GMS_ERR_CAPACITY, PAIR_DTYPE, RESULT_DTYPE, TWO_VIEW_DTYPE,
+                    desc_layout, make_camera)
+
+METHODS = ("gms", "bf", "logos")
 
 
 def _two_view(ctx, frames, d_pairs, n_pairs, max_m, total_m, d_out, d_res, camera, dist, prob, ransac_threshold, max_iters):
@@ -59,41 +66,64 @@ def run_dataset(ctx, ds, withRotation=False, withScale=False, thresholdFactor=6.
     `dictionary_result`. A `dictionary` that is passed is used as it is and train_dictionary is then not read. With neither,
     method="logos" raises.
     method="bf": bruteForceMatch on the file's descriptors and pairs (cross_check, distance_coef, max_size as the reference's
-    4.0 / 500 by default); see _run_bf."""
+    4.0 / 500 by default); see _run_bf.
+    The stages themselves work on resident tables (_run_gms, _run_bf, _run_logos): run_images feeds them from pixels."""
+    tail = (camera, dist, prob, ransac_threshold, max_iters)
     if method == "bf":
-        return _run_bf(ctx, ds, cross_check, distance_coef, max_size, camera, dist, prob, ransac_threshold, max_iters, device)
+        if ds.descriptors is None:
+            raise ValueError("method='bf' needs the dataset's descriptors")
+        frames = FrameTable(ctx, ds.frames, ds.sizes, device=device)
+        descs = DescriptorTable(ctx, frames, ds.descriptors, ds.desc_kind)
+        return _run_bf(ctx, descs, ds.pairs, cross_check, distance_coef, max_size, *tail)
     if method == "logos":
         trained = None
         if dictionary is None and train_dictionary not in (None, False):
             dictionary, trained = _train_dictionary(ctx, ds, dictionary_training_options(train_dictionary), device)
-        r = _run_logos(ctx, ds, dictionary, logos_capacity, camera, dist, prob, ransac_threshold, max_iters, device)
+        if ds.descriptors is None or dictionary is None:
+            raise ValueError("method='logos' needs the dataset's descriptors and a dictionary")
+        frames = FrameTable(ctx, ds.frames, ds.sizes, device=device)
+        kind = int(ds.desc_kind)
+        dt, width = desc_layout(kind)
+        d_desc = None
+        if frames.total:
+            desc = np.concatenate([np.ascontiguousarray(d, dtype=dt).reshape(-1, width) for d in ds.descriptors])
+            if len(desc) != frames.total:
+                raise ValueError("one descriptor per keypoint")
+            d_desc = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(frames.device)
+        r = _run_logos(ctx, frames, d_desc, kind, ds.pairs, dictionary, logos_capacity, *tail)
         if trained is not None:
             r.update(dictionary=dictionary, dictionary_result=trained)
         return r
     if method != "gms":
         raise ValueError(f"unknown method {method!r}")
     frames = FrameTable(ctx, ds.frames, ds.sizes, device=device)
+    do_match = (ds.descriptors is not None and len(ds.matches) == 0) if match is None else bool(match)
+    if do_match and ds.descriptors is None:
+        raise ValueError("the dataset carries no descriptors to match")
+    descs = DescriptorTable(ctx, frames, ds.descriptors, ds.desc_kind) if do_match else None
+    return _run_gms(ctx, frames, descs, ds.pairs, ds.matches, withRotation, withScale, thresholdFactor, *tail)
+
+
+def _run_gms(ctx, frames, descs, src_pairs, matches, withRotation, withScale, thresholdFactor, camera, dist, prob, ransac_threshold, max_iters):
+    """The GMS flow on resident tables: putative matches (descs: a DescriptorTable, whose matcher gives every keypoint of frame_a one
+    match -- BFMatcher::match without cross-check, FeatureMatchUtil.cpp:66-68; descs None: the host array `matches`, laid out by the
+    pairs' match_off) -> gms_filter_device -> two-view with a camera. Returns run_dataset's record."""
     dev = frames.device
-    pairs = np.ascontiguousarray(ds.pairs, dtype=PAIR_DTYPE).copy()
+    pairs = np.ascontiguousarray(src_pairs, dtype=PAIR_DTYPE).copy()
     n_pairs = len(pairs)
     counts = np.diff(frames.frame_off_host)
-    do_match = (ds.descriptors is not None and len(ds.matches) == 0) if match is None else bool(match)
-    if do_match:
-        if ds.descriptors is None:
-            raise ValueError("the dataset carries no descriptors to match")
-        # BFMatcher::match without cross-check: one match per keypoint of the query frame (FeatureMatchUtil.cpp:66-68)
+    if descs is not None:
         table = pair_table(frame_pairs_of(pairs), counts[pairs["frame_a"]] if n_pairs else 0)
         pairs["m"], pairs["match_off"] = table["m"], table["match_off"]
     total_m = int((pairs["match_off"] + pairs["m"]).max()) if n_pairs else 0
     max_m = int(pairs["m"].max()) if n_pairs else 0
     d_pairs = _to_dev(pairs, dev) if n_pairs else torch.zeros(24, dtype=torch.uint8, device=dev)
-    if do_match:
-        descs = DescriptorTable(ctx, frames, ds.descriptors, ds.desc_kind)
+    if descs is not None:
         d_matches = torch.zeros(max(total_m, 1) * 16, dtype=torch.uint8, device=dev)
         torch.cuda.synchronize(dev)
         descs.match_device(d_pairs.data_ptr(), n_pairs, max_m, d_matches.data_ptr())
     else:
-        m_host = np.ascontiguousarray(ds.matches, dtype=DMATCH_DTYPE)
+        m_host = np.ascontiguousarray(matches, dtype=DMATCH_DTYPE)
         if total_m > len(m_host):
             raise ValueError("a pair's match range lies outside the dataset's match array")
         d_matches = _to_dev(m_host, dev) if len(m_host) else torch.zeros(16, dtype=torch.uint8, device=dev)
@@ -109,6 +139,93 @@ def run_dataset(ctx, ds, withRotation=False, withScale=False, thresholdFactor=6.
     out.update(matches=d_matches.cpu().numpy().view(DMATCH_DTYPE)[:total_m], out=d_out.cpu().numpy().view(DMATCH_DTYPE)[:total_m],
                results=d_res.cpu().numpy().view(RESULT_DTYPE)[:n_pairs])
     return out
+
+
+def image_stack(images):
+    """The argument checks of run_images, before anything is launched: `images` a host array or device tensor [n, H, W] (grey) or
+    [n, H, W, 3] (B, G, R), or a list of equally sized [H, W] / [H, W, 3] images -> (uint8 array or tensor, is_bgr). Raises ValueError."""
+    if isinstance(images, (list, tuple)):
+        if len(images) == 0 or len({tuple(im.shape) for im in images}) != 1:
+            raise ValueError("images: at least one image, all of one size and one channel count")
+        images = torch.stack(list(images)) if torch.is_tensor(images[0]) else np.stack([np.asarray(im) for im in images])
+    elif not torch.is_tensor(images):
+        images = np.asarray(images)
+    if images.ndim not in (3, 4) or (images.ndim == 4 and images.shape[3] != 3) or 0 in tuple(images.shape):
+        raise ValueError("images: [n, H, W] grey or [n, H, W, 3] BGR")
+    if images.dtype != (torch.uint8 if torch.is_tensor(images) else np.uint8):
+        raise ValueError("images: 8-bit")
+    return images, images.ndim == 4
+
+
+def _train_dictionary_device(ctx, descs, opts):
+    """_train_dictionary on a resident DescriptorTable: the rows go from tensor to tensor, the dictionary stays on the device for the
+    word lookup -> (dictionary as a device tensor, as a host array for the record, its LOGOS_DICT_RESULT_DTYPE record)."""
+    frames, kind = descs.frames, descs.kind
+    dt, width = logos_dict_args(kind, opts["n_words"], opts["attempts"], opts["max_iters"])
+    n_rows = int(frames.frame_off_host[1]) if opts["rows"] == "first" else frames.total
+    if n_rows == 0:
+        raise ValueError("method='logos' needs descriptors to train a dictionary on")
+    job = LogosDictionary(ctx, kind, 1, n_rows, opts["n_words"], opts["attempts"], opts["max_iters"], opts["seed"], frames.device)
+    nbytes = n_rows * width * np.dtype(dt).itemsize
+    job.d_desc[:nbytes].copy_(descs.d_desc[:nbytes])
+    job.d_set_off.copy_(torch.tensor([0, n_rows], dtype=torch.int64))
+    torch.cuda.synchronize(frames.device)
+    job.run()
+    ctx.synchronize()
+    dic, rec, _ = job.results()
+    if rec[0]["status"] != 0:
+        raise ValueError(f"train_dictionary: the training rows were refused (status {int(rec[0]['status'])}): at least n_words and at "
+                         "most 2^20 rows, L2 elements finite and within [-4096, 4096]")
+    return job.d_dict, dic[0], rec[0]
+
+
+def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, threshold=20, max_keypoints=10000, n_levels=8,
+               descriptor="grad", withRotation=False, withScale=False, thresholdFactor=6.0, prob=0.7, ransac_threshold=1.0, max_iters=1000,
+               device=None, dictionary=None, logos_capacity=None, cross_check=True, distance_coef=4.0, max_size=500, train_dictionary=None,
+               keep_tables=False):
+    """run_dataset from pixels. images: [n, H, W] grey or [n, H, W, 3] BGR, 8-bit, a host array or a device tensor (or a list of equally
+    sized images). BGR goes through gms_bgr_to_gray_device; the pyramid keypoint source (threshold, max_keypoints, n_levels;
+    descriptor "grad" / "both": the 128-float rows under NORM_L2, "brief": the 32-byte rows under NORM_HAMMING) leaves its blocks on the
+    device, gms_detect_pack_device puts them back to back, and the tables are built there: between the pixels and the results only the
+    n + 1 frame offsets (and the status records the stages already read) come back. pairs: (frame_a, frame_b) rows or PAIR_DTYPE
+    records; default every a < b. The other arguments and the returned records are run_dataset's (the matcher always runs: there are
+    no matches to bring); keep_tables=True adds `tables` = (FrameTable, DescriptorTable), the resident keypoints and rows."""
+    if method not in METHODS:
+        raise ValueError(f"unknown method {method!r}")
+    if descriptor not in ("brief", "grad", "both"):
+        raise ValueError('descriptor: "brief", "grad" or "both"')
+    images, is_bgr = image_stack(images)
+    n, h, w = images.shape[:3]
+    if pairs is None:
+        pairs = [(a, b) for a in range(n) for b in range(a + 1, n)]
+    src = np.asarray(pairs)
+    src = src if src.dtype == PAIR_DTYPE else pair_table(np.asarray(pairs, dtype=np.int64).reshape(-1, 2), 0)
+    dev = _device(ctx, device)
+    d_images = (images if torch.is_tensor(images) else torch.from_numpy(np.ascontiguousarray(images))).to(dev).contiguous()
+    detector = DetectPyramid(ctx, n, w, h, threshold, max_keypoints, n_levels, dev, descriptor)   # (refuses a bad size before any launch)
+    if is_bgr:
+        d_images = bgr_to_gray(ctx, d_images)
+    torch.cuda.synchronize(dev)
+    detector.run(d_images)
+    kind = GMS_DESC_HAMMING256 if descriptor == "brief" else GMS_DESC_L2_F32X128
+    frames, descs = tables_from_detector(detector, [(w, h)] * n, kind)
+    tail = (camera, dist, prob, ransac_threshold, max_iters)
+    if method == "bf":
+        r = _run_bf(ctx, descs, src, cross_check, distance_coef, max_size, *tail)
+    elif method == "logos":
+        trained = None
+        if dictionary is None and train_dictionary not in (None, False):
+            dictionary, dic_host, trained = _train_dictionary_device(ctx, descs, dictionary_training_options(train_dictionary))
+        if dictionary is None:
+            raise ValueError("method='logos' needs a dictionary, or train_dictionary")
+        r = _run_logos(ctx, frames, descs.d_desc, kind, src, dictionary, logos_capacity, *tail)
+        if trained is not None:
+            r.update(dictionary=dic_host, dictionary_result=trained)
+    else:
+        r = _run_gms(ctx, frames, descs, src, None, withRotation, withScale, thresholdFactor, *tail)
+    if keep_tables:
+        r.update(tables=(frames, descs))
+    return r
 
 
 def dictionary_training_options(train_dictionary):
@@ -141,29 +258,33 @@ def _train_dictionary(ctx, ds, opts, device):
     return dic[0], rec[0]
 
 
-def _run_logos(ctx, ds, dictionary, capacity, camera, dist, prob, ransac_threshold, max_iters, device):
-    """descriptors -> words (the exact nearest dictionary row) -> one LOGOS table for all frames -> every pair in one filter run ->
-    two-view with a camera. Pair p gets room for `capacity` survivors (default: the larger of its two frames); pairs that overflow
-    are reported with the count they need, and the batch is run once more with that room. Returns what run_dataset returns
-    (`matches` empty: LOGOS has no putative matches), plus words (per keypoint) and logos_results (LOGOS_RESULT_DTYPE per pair);
-    `results` are gms_pair_result records, `pairs` the table the survivors are laid out by."""
-    if ds.descriptors is None or dictionary is None:
-        raise ValueError("method='logos' needs the dataset's descriptors and a dictionary")
-    frames = FrameTable(ctx, ds.frames, ds.sizes, device=device)
+def _run_logos(ctx, frames, d_desc, kind, src_pairs, dictionary, capacity, camera, dist, prob, ransac_threshold, max_iters):
+    """The LOGOS flow on resident tables: the rows d_desc (a device tensor, row i of keypoint i of `frames`; None without keypoints)
+    -> words (the exact nearest row of `dictionary`, a host array or a device tensor of rows like the descriptors) -> one LOGOS table
+    for all frames -> every pair in one filter run -> two-view with a camera. Pair p gets room for `capacity` survivors (default: the
+    larger of its two frames); pairs that overflow are reported with the count they need, and the batch is run once more with that
+    room. Returns what run_dataset returns (`matches` empty: LOGOS has no putative matches), plus words (per keypoint) and
+    logos_results (LOGOS_RESULT_DTYPE per pair); `results` are gms_pair_result records, `pairs` the table the survivors are laid out
+    by."""
     dev = frames.device
-    kind = int(ds.desc_kind)
     dt, width = desc_layout(kind)
-    dic = np.ascontiguousarray(dictionary, dtype=dt).reshape(-1, width)
+    if torch.is_tensor(dictionary):
+        d_dict = dictionary.contiguous().view(torch.uint8).reshape(-1)
+        n_words = d_dict.numel() // (width * np.dtype(dt).itemsize)
+    else:
+        dic = np.ascontiguousarray(dictionary, dtype=dt).reshape(-1, width)
+        d_dict, n_words = torch.from_numpy(dic.view(np.uint8).reshape(-1).copy()).to(dev), len(dic)
     total_kp = frames.total
     if total_kp:
-        desc = np.concatenate([np.ascontiguousarray(d, dtype=dt).reshape(-1, width) for d in ds.descriptors])
-        if len(desc) != total_kp:
+        if d_desc is None or d_desc.numel() * d_desc.element_size() < total_kp * width * np.dtype(dt).itemsize:
             raise ValueError("one descriptor per keypoint")
-        d_words, held = _words_device(ctx, kind, desc, dic, dev)   # (held: the launch's inputs, alive until this function returns)
+        d_words = torch.zeros(total_kp, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        ctx.logos_words_device(kind, d_desc.data_ptr(), total_kp, d_dict.data_ptr(), n_words, d_words.data_ptr())
     else:
         d_words = torch.zeros(1, dtype=torch.int32, device=dev)
-    table = LogosTable(ctx, frames, d_words, len(dic))
-    src = frame_pairs_of(np.ascontiguousarray(ds.pairs, dtype=PAIR_DTYPE))
+    table = LogosTable(ctx, frames, d_words, n_words)
+    src = frame_pairs_of(np.ascontiguousarray(src_pairs, dtype=PAIR_DTYPE))
     n_pairs = len(src)
     counts = np.diff(frames.frame_off_host)
     cap = (np.maximum(frame_counts(counts, src[:, 0]), frame_counts(counts, src[:, 1])) if capacity is None
@@ -189,16 +310,13 @@ def _run_logos(ctx, ds, dictionary, capacity, camera, dist, prob, ransac_thresho
     return out
 
 
-def _run_bf(ctx, ds, cross_check, distance_coef, max_size, camera, dist, prob, ransac_threshold, max_iters, device):
-    """descriptors -> every pair's bruteForceMatch survivors in one gms_bf_select_device run -> two-view with a camera. Pair p gets
-    room for min(max_size, n(frame_a)) survivors, which its K never exceeds. Returns what run_dataset returns (`matches` empty: the
-    putative matches stay in the workspace), plus bf_results (BF_RESULT_DTYPE per pair); `results` are gms_pair_result records,
-    `pairs` the table the survivors are laid out by."""
-    if ds.descriptors is None:
-        raise ValueError("method='bf' needs the dataset's descriptors")
-    frames = FrameTable(ctx, ds.frames, ds.sizes, device=device)
-    descs = DescriptorTable(ctx, frames, ds.descriptors, ds.desc_kind)
-    src = np.ascontiguousarray(ds.pairs, dtype=PAIR_DTYPE)
+def _run_bf(ctx, descs, src_pairs, cross_check, distance_coef, max_size, camera, dist, prob, ransac_threshold, max_iters):
+    """The bruteForceMatch flow on a resident DescriptorTable: every pair's survivors in one gms_bf_select_device run -> two-view with
+    a camera. Pair p gets room for min(max_size, n(frame_a)) survivors, which its K never exceeds. Returns what run_dataset returns
+    (`matches` empty: the putative matches stay in the workspace), plus bf_results (BF_RESULT_DTYPE per pair); `results` are
+    gms_pair_result records, `pairs` the table the survivors are laid out by."""
+    frames = descs.frames
+    src = np.ascontiguousarray(src_pairs, dtype=PAIR_DTYPE)
     n_pairs = len(src)
     pairs = bf_select_table(descs, frame_pairs_of(src), max_size=max_size)
     run = BfSelect(ctx, descs, pairs, cross_check, distance_coef, max_size)
