@@ -10,7 +10,8 @@ getValidDisparityROI), stated for every accepted parameter set. No OpenCV is at 
 that release's published source, not checked against it.
 
 Two forms that must agree: stereo_bm_loop, a literal per-pixel loop for small images, and stereo_bm, a vectorised one (window sums
-from cumulative sums) for the 450 x 375 fixture. Both return (disp int16 [H, W], cost int32 [H, W]); the cost of a pixel is
+from cumulative sums) for the 450 x 375 fixture, made of pieces (window_costs, decisions, raw_maps, lr_sources, validate, roi_fill) that
+tests/stereo_bm_cases.py counts with. Both return (disp int16 [H, W], cost int32 [H, W]); the cost of a pixel is
 sad[mind] wherever the winner-take-all step gave it a disparity (before the left-right check and the ROI fill), -1 elsewhere.
 gms_stereo_bm_device returns the same two arrays.
 """
@@ -193,20 +194,32 @@ def validate_loop(disp, cost, p):
                 disp[y, x] = inv
 
 
-def validate(disp, cost, p):
-    """validateDisparity, vectorised over all rows: per target (y, x2) the strictly lowest cost, the lowest x on ties."""
-    H, W = disp.shape
-    nd, md, maxdiff = p["num_disparities"], p["min_disparity"], p["disp12_max_diff"] * 16
+def lr_sources(disp, cost, p):
+    """The sources of validateDisparity's first pass on the raw map: (ys, x, d, c, x2), one entry per pixel of its column range that has
+    a disparity -- its row, column, disparity, cost and the target column x - ((d + 8) >> 4) it votes for. None when the range is empty."""
+    W = disp.shape[1]
+    nd, md = p["num_disparities"], p["min_disparity"]
     inv = (md - 1) * 16
     minX1, maxX1 = max(md + nd, 0), W + min(md, 0)
     if maxX1 <= minX1:
-        return
+        return None
     sub = disp[:, minX1:maxX1].astype(np.int64)
     ys, xs = np.nonzero(sub != inv)
     d = sub[ys, xs]
     x = xs + minX1
     c = cost[ys, x].astype(np.int64)
-    x2 = x - ((d + 8) >> 4)
+    return ys, x, d, c, x - ((d + 8) >> 4)
+
+
+def validate(disp, cost, p):
+    """validateDisparity, vectorised over all rows: per target (y, x2) the strictly lowest cost, the lowest x on ties."""
+    H, W = disp.shape
+    md, maxdiff = p["min_disparity"], p["disp12_max_diff"] * 16
+    inv = (md - 1) * 16
+    src = lr_sources(disp, cost, p)
+    if src is None:
+        return
+    ys, x, d, c, x2 = src
     g = ys * W + x2
     order = np.lexsort((x, c, g))
     first = np.ones(len(order), bool)
@@ -283,17 +296,13 @@ def stereo_bm_loop(left, right, **kw):
     return disp, cost
 
 
-def stereo_bm(left, right, **kw):
-    """Vectorised form: (disp int16, cost int32), equal to stereo_bm_loop."""
-    p, left, right, H, W = _prepare(left, right, kw)
-    nd, md, cap, bs = p["num_disparities"], p["min_disparity"], p["pre_filter_cap"], p["block_size"]
+def window_costs(left, right, p):
+    """The cost volume of the computed region, by cumulative sums: (sad int64 [nd, ny, wx], tex int64 [ny, wx]) for the rows
+    [w2, H - w2) and the output columns lofs + [0, wx), wx = min(width1, W - lofs)."""
+    H, W = left.shape
+    nd, cap, bs = p["num_disparities"], p["pre_filter_cap"], p["block_size"]
     w2 = bs // 2
-    inv = filtered_value(p)
-    disp = np.full((H, W), inv, np.int16)
-    cost = np.full((H, W), -1, np.int32)
-    lofs, rofs, width1, none = ranges(p, W)
-    if none:
-        return disp, cost
+    lofs, rofs, width1, _ = ranges(p, W)
     wx = min(width1, W - lofs)
     L = prefilter_xsobel(left, cap).astype(np.int32)
     R = prefilter_xsobel(right, cap).astype(np.int32)
@@ -311,26 +320,62 @@ def stereo_bm(left, right, **kw):
     sad = np.empty((nd, ny, wx), np.int64)
     for k in range(nd):
         sad[k] = vsum(np.abs(Lw - R[:, cr + k]).sum(axis=2))
+    return sad, tex
+
+
+def decisions(sad, tex, p):
+    """decide over the whole cost volume: a dict of [ny, wx] arrays -- mind and minsad (the winner), tex_ok and uniq_ok (the two rules;
+    a pixel is accepted when both hold), den (the subpixel step's denominator) and disp (the raw disparity of an accepted pixel)."""
+    nd, md = p["num_disparities"], p["min_disparity"]
+    ny, wx = tex.shape
     mind = np.argmin(sad, axis=0)                                  # the first strict minimum: the lowest k
     yy, xx = np.meshgrid(np.arange(ny), np.arange(wx), indexing="ij")
     minsad = sad[mind, yy, xx]
-    ok = tex >= p["texture_threshold"]
+    tex_ok = tex >= p["texture_threshold"]
+    uniq_ok = np.ones_like(tex_ok)
     ur = p["uniqueness_ratio"]
     if ur > 0:
         thresh = minsad + (minsad * ur) // 100
         far = np.abs(np.arange(nd)[:, None, None] - mind[None]) > 1
-        ok &= ~np.any(far & (sad <= thresh[None]), axis=0)
+        uniq_ok = ~np.any(far & (sad <= thresh[None]), axis=0)
     pp = sad[np.where(mind + 1 < nd, mind + 1, nd - 2), yy, xx]
     nn = sad[np.where(mind >= 1, mind - 1, 1), yy, xx]
     den = pp + nn - 2 * minsad + np.abs(pp - nn)
     num = (pp - nn) * 256
     frac = np.where(den != 0, np.sign(num) * (np.abs(num) // np.where(den != 0, den, 1)), 0)
     dv = ((nd - mind - 1 + md) * 256 + frac + 15) >> 4
-    disp[w2:H - w2, lofs:lofs + wx] = np.where(ok, dv, inv)
-    cost[w2:H - w2, lofs:lofs + wx] = np.where(ok, minsad, -1)
+    return dict(mind=mind, minsad=minsad, tex_ok=tex_ok, uniq_ok=uniq_ok, den=den, disp=dv)
+
+
+def raw_maps(left, right, p):
+    """findStereoCorrespondenceBM's output before the left-right check and the ROI fill: (disp int16, cost int32, the decisions; None
+    when nothing is computed)."""
+    H, W = left.shape
+    w2 = p["block_size"] // 2
+    disp = np.full((H, W), filtered_value(p), np.int16)
+    cost = np.full((H, W), -1, np.int32)
+    lofs, _, _, none = ranges(p, W)
+    if none:
+        return disp, cost, None
+    sad, tex = window_costs(left, right, p)
+    dec = decisions(sad, tex, p)
+    dec["sad"] = sad
+    ok = dec["tex_ok"] & dec["uniq_ok"]
+    wx = tex.shape[1]
+    disp[w2:H - w2, lofs:lofs + wx] = np.where(ok, dec["disp"], filtered_value(p))
+    cost[w2:H - w2, lofs:lofs + wx] = np.where(ok, dec["minsad"], -1)
+    return disp, cost, dec
+
+
+def stereo_bm(left, right, **kw):
+    """Vectorised form: (disp int16, cost int32), equal to stereo_bm_loop."""
+    p, left, right, H, W = _prepare(left, right, kw)
+    disp, cost, dec = raw_maps(left, right, p)
+    if dec is None:
+        return disp, cost
     if p["disp12_max_diff"] >= 0:
         validate(disp, cost, p)
-    roi_fill(disp, p, lofs)
+    roi_fill(disp, p, ranges(p, W)[0])
     return disp, cost
 
 

@@ -1,12 +1,14 @@
 """-m gpu: StereoBM block matching (gms_stereo_bm_device, gms_stereo_bm, gms_stereo_bm_normalize_device) -- the int16
 map and the cost byte for byte against the CPU statement tests/stereo_bm_ref.py on the reference's pair and over a seeded parameter
-sweep, a batch against the one-shot calls, the reference's 8-bit map, graph replay and rejected parameters."""
+sweep, a batch against the one-shot calls, the reference's 8-bit map, graph replay and rejected parameters; and on the named edge cases
+of tests/stereo_bm_cases.py (cost ties, rule cut-offs, winners at both ends, the size limits), whose content the CPU suite asserts."""
 import importlib
 import os
 
 import numpy as np
 import pytest
 
+import stereo_bm_cases as C
 import stereo_bm_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -134,3 +136,104 @@ def test_bad_params_rejected_before_launch(ctx, pkg):
     with pytest.raises(types.GmsError) as e:
         pkg.stereoBM(np.zeros((40, 8193), np.uint8), np.zeros((40, 8193), np.uint8))
     assert e.value.code == -1
+
+
+# ---- the named edge cases (tests/stereo_bm_cases.py) ------------------------------------------------------------------------------
+def _assert_same(got, want, what):
+    """Byte for byte, and on a mismatch the first differing pixel."""
+    assert got.shape == want.shape and got.dtype == want.dtype, what
+    if got.tobytes() != want.tobytes():
+        ys, xs = np.nonzero(got != want)
+        y, x = int(ys[0]), int(xs[0])
+        raise AssertionError(f"{what}: {len(ys)} of {got.size} pixels differ, the first at (y, x) = ({y}, {x}): got {got[y, x]}, want {want[y, x]}")
+
+
+@pytest.mark.parametrize("name", C.NAMES)
+def test_edge_cases_equal_statement(pkg, name):
+    left, right, kw = C.case(name)
+    want_d, want_c = C.expected(name)
+    got_d, got_c = pkg.stereoBM(left, right, return_cost=True, **kw)
+    _assert_same(got_c, want_c, (name, "cost"))
+    _assert_same(got_d, want_d, (name, "disparity"))
+
+
+@pytest.mark.parametrize("name", ["const_uniq", "stripes64"])
+def test_edge_cases_eight_bit(pkg, name):
+    left, right, kw = C.case(name)
+    want = R.normalize_u8(C.expected(name)[0])
+    if name == "const_uniq":
+        assert (want == 255).all()      # an all-FILTERED map: max == min, scale 0, every 0 -> 255
+    _assert_same(pkg.stereo_match(left, right, **kw), want, name)
+    assert want.tobytes() == R.stereo_match(left, right, **kw).tobytes()
+
+
+@pytest.mark.parametrize("nd", sorted(C.ENDS))
+def test_edge_cases_in_one_batch(ctx, pkg, nd):
+    """Winners at opposite ends of the range side by side in blockIdx.z."""
+    batch = _batch()
+    names = [f"end_last_{nd}", f"end_first_{nd}"]
+    pairs = [C.case(n) for n in names]
+    kw = pairs[0][2]
+    assert pairs[1][2] == kw
+    d, c, d8 = batch.stereo_bm_batch(np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs]), kw, ctx, return_cost=True, eight_bit=True)
+    for i, name in enumerate(names):
+        want_d, want_c = C.expected(name)
+        _assert_same(c[i], want_c, (name, "cost"))
+        _assert_same(d[i], want_d, (name, "disparity"))
+        _assert_same(d8[i], R.normalize_u8(want_d), (name, "8-bit"))
+        one_d, one_c = pkg.stereoBM(pairs[i][0], pairs[i][1], return_cost=True, **kw)
+        assert one_d.tobytes() == d[i].tobytes() and one_c.tobytes() == c[i].tobytes()
+        assert pkg.stereo_match(pairs[i][0], pairs[i][1], **kw).tobytes() == d8[i].tobytes()
+
+
+def test_padded_pitch(ctx):
+    """pitch > width through gms_stereo_bm_device: the statement's bytes, with and without the cost map, whatever the padding holds."""
+    import torch
+    left, right, kw = C.case("half_flat")
+    H, W = left.shape
+    pad = 37
+    want = [C.expected("half_flat"), R.stereo_bm(right, left, **kw)]
+    rng = np.random.default_rng(3)
+    rows_l = rng.integers(0, 256, (2, H, W + pad)).astype(np.uint8)
+    rows_r = rng.integers(0, 256, (2, H, W + pad)).astype(np.uint8)
+    rows_l[:, :, W::5] = 255
+    rows_l[0, :, :W], rows_r[0, :, :W] = left, right
+    rows_l[1, :, :W], rows_r[1, :, :W] = right, left
+    d_l, d_r = torch.from_numpy(rows_l).cuda(), torch.from_numpy(rows_r).cuda()
+    ws_bytes = ctx.stereo_bm_workspace_bytes(W, H, 2, kw)
+    ws = torch.zeros(ws_bytes, dtype=torch.uint8, device="cuda")
+    for with_cost in (True, False):
+        d_disp = torch.zeros((2, H, W), dtype=torch.int16, device="cuda")
+        d_cost = torch.zeros((2, H, W), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        ctx.stereo_bm_device(kw, d_l.data_ptr(), d_r.data_ptr(), 2, W, H, W + pad, ws.data_ptr(), ws_bytes, d_disp.data_ptr(),
+                             d_cost.data_ptr() if with_cost else None)
+        ctx.synchronize()
+        for i in range(2):
+            _assert_same(d_disp[i].cpu().numpy(), want[i][0], ("pitch", with_cost, i, "disparity"))
+            if with_cost:
+                _assert_same(d_cost[i].cpu().numpy(), want[i][1], ("pitch", i, "cost"))
+        assert with_cost or not bool(d_cost.any())      # no cost map asked for: none written
+
+
+@pytest.mark.parametrize("name", ["widest", "largest_lds"])
+def test_workspace_exact(ctx, name):
+    """A workspace of exactly gms_stereo_bm_workspace_bytes with 256 guard bytes behind it, at the two size limits."""
+    import torch
+    GUARD, FILL = 256, 0xA5
+    left, right, kw = C.case(name)
+    H, W = left.shape
+    ws_bytes = ctx.stereo_bm_workspace_bytes(W, H, 1, kw)
+    assert ws_bytes > 0
+    buf = torch.full((ws_bytes + GUARD,), FILL, dtype=torch.uint8, device="cuda")
+    assert buf.data_ptr() % 256 == 0
+    d_l, d_r = torch.from_numpy(left.copy()).cuda(), torch.from_numpy(right.copy()).cuda()
+    d_disp = torch.zeros((H, W), dtype=torch.int16, device="cuda")
+    d_cost = torch.zeros((H, W), dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    ctx.stereo_bm_device(kw, d_l.data_ptr(), d_r.data_ptr(), 1, W, H, W, buf.data_ptr(), ws_bytes, d_disp.data_ptr(), d_cost.data_ptr())
+    ctx.synchronize()
+    assert bool((buf[ws_bytes:] == FILL).all()), "the entry point wrote behind its workspace"
+    want_d, want_c = C.expected(name)
+    _assert_same(d_cost.cpu().numpy(), want_c, (name, "cost"))
+    _assert_same(d_disp.cpu().numpy(), want_d, (name, "disparity"))

@@ -1,10 +1,12 @@
 """CPU: the StereoBM statement (tests/stereo_bm_ref.py) -- hand-worked cases for each rule, the literal loop against
-the vectorised form over a parameter sweep, and the reference's parameters on its own 450 x 375 pair against the ground truth."""
+the vectorised form over a parameter sweep, the reference's parameters on its own 450 x 375 pair against the ground truth, and the
+named edge cases of tests/stereo_bm_cases.py: each contains what it is named for, by the statement's own census."""
 import os
 
 import numpy as np
 import pytest
 
+import stereo_bm_cases as C
 import stereo_bm_ref as R
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "image_stereo_pair_450x375.npz")
@@ -161,3 +163,63 @@ def test_normalize_rules():
     assert out[1, 0] == 255
     flat = R.normalize_u8(np.full((2, 2), 7, np.int16))     # max == min: scale 0, everything 0 -> 255
     assert (flat == 255).all()
+
+
+# ---- the named edge cases (tests/stereo_bm_cases.py) ------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", C.NAMES)
+def test_cases_contain_what_they_are_for(name):
+    """Conditions on the inputs, met by the statement alone: a case that stopped containing its rule would let the GPU test pass for
+    nothing. A floor that fails for a new seed means another seed, not another floor."""
+    left, right, kw = C.case(name)
+    n = C.census(left, right, **kw)
+    print(name, left.shape, n)
+    assert n["computed"] > 0
+    if name in ("const", "stripes8", "stripes64"):
+        assert n["tied_across_slots"] == n["tied"] == n["computed"]
+    if name in ("const_uniq", "stripes8_uniq"):
+        assert n["uniqueness_cut"] == n["computed"] and n["valid"] == 0
+    if name == "const_tex":
+        assert n["texture_cut"] == n["computed"] and n["valid"] == 0
+    if name == "const":
+        assert n["denominator_zero"] >= 1000 and n["winner_first"] == n["computed"]
+    if name == "stripes64":
+        assert n["lr_contended"] >= 100 and n["lr_removed"] >= 100
+    if name in ("stripes64_noise", "stripes64_noise2"):
+        assert n["uniqueness_cut"] >= 500 and n["accepted"] >= 500
+    if name == "stripes64_noise2":
+        cost = C.expected(name)[1]
+        assert cost[cost >= 0].min() > 0      # no exact match: every uniqueness threshold is above 0
+    if name == "half_flat":
+        assert 0.2 * n["computed"] <= n["texture_cut"] <= 0.6 * n["computed"] and n["accepted"] > 0
+    if name.startswith("end_last"):
+        assert n["winner_last"] >= 0.9 * n["accepted"] > 0
+    if name.startswith("end_first"):
+        assert n["winner_first"] >= 0.9 * n["accepted"] > 0
+    if name in ("cap1", "widest") or name.startswith("largest_lds"):
+        assert n["valid"] >= 300
+    assert n["valid"] == int((C.expected(name)[0] != R.filtered_value(R.make_params(**kw))).sum())   # the census walks stereo_bm's path
+
+
+def test_cases_reach_the_size_limits():
+    left, _, kw = C.case("widest")
+    assert left.shape[1] == R.MAX_WIDTH
+    for name, lofs, rofs in (("largest_lds", 511, 0), ("largest_lds_rofs", 11, 0), ("largest_lds_rofs9", 0, 9)):
+        left, _, kw = C.case(name)
+        p = R.make_params(**kw)
+        assert (p["block_size"], p["num_disparities"]) == (51, 512) and R.ranges(p, left.shape[1])[:2] == (lofs, rofs)
+        assert left.shape[0] - 2 * (p["block_size"] // 2) <= 32     # one band: its LDS rows are the image's 60, not 32 + 50
+    for nd, kpl, dead in ((80, 2, 48), (128, 2, 0), (256, 4, 0), (272, 8, 240)):
+        assert C.case(f"end_last_{nd}")[2]["num_disparities"] == nd and (64 * kpl - nd, nd > 64 * kpl // 2) == (dead, True)
+
+
+@pytest.mark.parametrize("name", C.CUT_DOWN)
+def test_loop_equals_vectorised_on_cut_down_cases(name):
+    left, right, kw = C.cut_down(name)
+    n = C.census(left, right, **kw)
+    if name in ("const", "const_uniq", "stripes8", "stripes64"):
+        assert n["tied"] == n["computed"] > 0
+    if name == "stripes64":
+        assert n["lr_contended"] >= 20 and n["lr_removed"] >= 20    # validate_loop and validate on equal costs
+    a = R.stereo_bm_loop(left, right, **kw)
+    b = R.stereo_bm(left, right, **kw)
+    assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
