@@ -716,6 +716,34 @@ int gms_median_blur(const uint8_t* src, int width, int height, int channels, int
 int gms_portrait(const gms_portrait_params* params, const uint8_t* bgr, const uint8_t* disparity, int width, int height,
                  uint8_t* out_bgr, uint8_t* mask, uint8_t* selected, uint8_t* blurred);
 
+/* ---- cv::resize and cv::warpAffine, the reference main()'s image transforms (main.cpp:36, :44, :114-120) -------------
+ * 8-bit images of 1 or 3 interleaved channels. Both are OpenCV 4.5.2's 8-bit INTER_LINEAR paths restated as integer arithmetic in
+ * tests/warp_ref.py and csrc/warp_core.h (parity with an OpenCV build is unpinned; DESIGN.md §4.11 has the statement):
+ *   resize: 11-bit column and row weights from float32 fractions; when both axes halve exactly, the 2 x 2 mean (a+b+c+d+2)>>2.
+ *   warpAffine: the FORWARD 2 x 3 matrix (source -> destination, row-major doubles), inverted as OpenCV inverts it; source positions
+ *     with 5 fractional bits; BORDER_CONSTANT 0: a tap outside the source is 0; every destination pixel is written. Non-finite
+ *     entries, or ones whose positions overflow int32, are outside the domain: the result is then unspecified, but nothing outside
+ *     the source is read.
+ * Accepted (others: GMS_ERR_BAD_ARG): channels 1 or 3; every side 1..GMS_WARP_MAX_SIDE; n 1..65535; src_pitch >= channels * src_width,
+ * dst_pitch >= channels * dst_width; the destination range must not overlap the source range; n_matrices 1 or n.
+ * Pixel (x, y) of image i at d_src + (i * src_height + y) * src_pitch + channels * x; the destination likewise. Bytes between a row's
+ * end and the next row are not written.
+ * gms_resize_device / gms_warp_affine_device: n images on the context's stream; no allocation, no synchronisation, no readback, no
+ *   workspace (graph-capturable). d_M: device doubles [n_matrices][6], read by the kernel: a captured graph follows new matrices.
+ * gms_rotation_matrix_2d: getRotationMatrix2D on the host (the centre is rounded to float32 first); M receives 6 doubles.
+ * gms_resize, gms_warp_affine, gms_img_rotate: ONE image on host pointers (dense rows; M on the host), synchronous, on the current HIP
+ *   device. gms_img_rotate is the reference's img_rotate: the rotation about (width / 2., height / 2.), scale 1, same size. */
+#define GMS_WARP_MAX_SIDE 8192
+int gms_resize_device(gms_ctx* ctx, const uint8_t* d_src, int n, int src_width, int src_height, int channels, int src_pitch,
+                      uint8_t* d_dst, int dst_width, int dst_height, int dst_pitch);
+int gms_warp_affine_device(gms_ctx* ctx, const uint8_t* d_src, int n, int src_width, int src_height, int channels, int src_pitch,
+                           const double* d_M, int n_matrices, uint8_t* d_dst, int dst_width, int dst_height, int dst_pitch);
+int gms_rotation_matrix_2d(double center_x, double center_y, double angle, double scale, double* M);
+int gms_resize(const uint8_t* src, int src_width, int src_height, int channels, uint8_t* dst, int dst_width, int dst_height);
+int gms_warp_affine(const uint8_t* src, int src_width, int src_height, int channels, const double* M, uint8_t* dst, int dst_width,
+                    int dst_height);
+int gms_img_rotate(const uint8_t* src, int width, int height, int channels, double angle, uint8_t* dst);
+
 const char* gms_error_string(int code);
 const char* gms_version(void);
 

@@ -380,6 +380,20 @@ class GmsContext:
         _check(self._lib.gms_median_blur_device(self._h, d_src, int(n), int(width), int(height), int(channels), int(pitch), int(ksize),
                                                 d_dst), self._lib, "gms_median_blur_device")
 
+    # -- resize and warpAffine (main.cpp:36, :44, :114-120; batch.Warp drives these) ---------------------------------------------------
+    def resize_device(self, d_src, n, src_width, src_height, channels, src_pitch, d_dst, dst_width, dst_height, dst_pitch):
+        """gms_resize_device (cv::resize, INTER_LINEAR) on raw device pointers. Stream-ordered."""
+        _check(self._lib.gms_resize_device(self._h, d_src, int(n), int(src_width), int(src_height), int(channels), int(src_pitch), d_dst,
+                                           int(dst_width), int(dst_height), int(dst_pitch)), self._lib, "gms_resize_device")
+
+    def warp_affine_device(self, d_src, n, src_width, src_height, channels, src_pitch, d_M, n_matrices, d_dst, dst_width, dst_height,
+                           dst_pitch):
+        """gms_warp_affine_device (cv::warpAffine, INTER_LINEAR, BORDER_CONSTANT 0); d_M: device doubles [n_matrices][6], the forward
+        matrices, read when the kernel runs. Stream-ordered."""
+        _check(self._lib.gms_warp_affine_device(self._h, d_src, int(n), int(src_width), int(src_height), int(channels), int(src_pitch),
+                                                d_M, int(n_matrices), d_dst, int(dst_width), int(dst_height), int(dst_pitch)), self._lib,
+               "gms_warp_affine_device")
+
     def selftest_five_point(self, x1, x2):
         """gms_selftest_five_point: x1, x2 [n_samples, 5, 2] normalised points -> list of [k, 3, 3] model arrays, one per sample."""
         x1 = np.asarray(x1, dtype=np.float64).reshape(-1, 5, 2)
@@ -613,3 +627,61 @@ def medianBlur(image, ksize):
     _check(lib.gms_median_blur(img.ctypes.data, w, h, 1 if img.ndim == 2 else img.shape[2], int(ksize), out.ctypes.data), lib,
            "gms_median_blur")
     return out
+
+
+def _host_image(image, who):
+    img = np.ascontiguousarray(image, dtype=np.uint8)
+    if img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] not in (1, 3)) or img.size == 0:
+        raise ValueError(f"{who}: uint8 [H, W], [H, W, 1] or [H, W, 3]")
+    return img, img.shape[1], img.shape[0], 1 if img.ndim == 2 else img.shape[2]
+
+
+def _is_tensor(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def getRotationMatrix2D(center, angle, scale):
+    """cv::getRotationMatrix2D on the host (gms_rotation_matrix_2d): the forward 2 x 3 matrix, float64; the centre is rounded to
+    float32 first, as OpenCV's Point2f does."""
+    lib = load_library()
+    M = np.zeros((2, 3), np.float64)
+    _check(lib.gms_rotation_matrix_2d(float(center[0]), float(center[1]), float(angle), float(scale), M.ctypes.data), lib,
+           "gms_rotation_matrix_2d")
+    return M
+
+
+def resize(image, dsize):
+    """cv::resize(image, dsize, INTER_LINEAR) on the GPU: image uint8 [H, W] or [H, W, 3], dsize = (width, height). A host array gives
+    a host array (gms_resize); a device tensor gives a device tensor (batch.resize_images). tests/warp_ref.py states every step."""
+    if _is_tensor(image):
+        from .batch import resize_images
+        return resize_images(image[None], dsize)[0]
+    lib = load_library()
+    img, w, h, c = _host_image(image, "image")
+    out = np.zeros((int(dsize[1]), int(dsize[0])) + img.shape[2:], np.uint8)
+    _check(lib.gms_resize(img.ctypes.data, w, h, c, out.ctypes.data, int(dsize[0]), int(dsize[1])), lib, "gms_resize")
+    return out
+
+
+def warpAffine(image, M, dsize):
+    """cv::warpAffine(image, M, dsize, INTER_LINEAR, BORDER_CONSTANT 0) on the GPU: M the forward 2 x 3 matrix, dsize = (width,
+    height). Host array -> host array (gms_warp_affine); device tensor -> device tensor (batch.warp_affine_images)."""
+    M = np.ascontiguousarray(M, dtype=np.float64)
+    if M.size != 6:
+        raise ValueError("M: a 2 x 3 matrix")
+    if _is_tensor(image):
+        from .batch import warp_affine_images
+        return warp_affine_images(image[None], M.reshape(1, 6), dsize)[0]
+    lib = load_library()
+    img, w, h, c = _host_image(image, "image")
+    out = np.zeros((int(dsize[1]), int(dsize[0])) + img.shape[2:], np.uint8)
+    _check(lib.gms_warp_affine(img.ctypes.data, w, h, c, M.ctypes.data, out.ctypes.data, int(dsize[0]), int(dsize[1])), lib,
+           "gms_warp_affine")
+    return out
+
+
+def imgRotate(image, angle):
+    """The reference's img_rotate (main.cpp:114-120): warpAffine by getRotationMatrix2D((w / 2., h / 2.), angle, 1) into the same
+    size. 180 degrees is NOT image[::-1, ::-1]: it is that flip moved by one pixel, behind a black first row and column."""
+    h, w = image.shape[:2]
+    return warpAffine(image, getRotationMatrix2D((w / 2., h / 2.), angle, 1.0), (w, h))

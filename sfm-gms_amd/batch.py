@@ -754,3 +754,80 @@ def portrait_batch(images, disparities, params=None, ctx=None, detail=False):
     if not on_dev:
         outs = [o.cpu().numpy() for o in outs]
     return outs[0] if len(outs) == 1 else tuple(outs)
+
+
+class Warp:
+    """Device buffers of gms_resize_device / gms_warp_affine_device for n images of one size and channel count (1: [n, H, W]; 3:
+    [n, H, W, 3]): the destination d_dst and, for warpAffine, the forward matrices d_M [n_matrices, 6] (n_matrices 1: one for all
+    images, or n), sized once, so that the calls can be repeated or captured into a graph. The kernel reads d_M when it runs: a
+    captured graph follows set_matrices()."""
+
+    def __init__(self, ctx, n, src_size, dst_size, channels=1, n_matrices=1, device=None):
+        self.ctx, self.n, self.channels, self.n_matrices = ctx, int(n), int(channels), int(n_matrices)
+        (self.sw, self.sh), (self.dw, self.dh) = (int(v) for v in src_size), (int(v) for v in dst_size)
+        if self.channels not in (1, 3) or self.n < 1 or min(self.sw, self.sh, self.dw, self.dh) < 1 or self.n_matrices not in (1, self.n):
+            raise ValueError("Warp: channels 1 or 3, n >= 1, positive sizes, n_matrices 1 or n")
+        dev = _device(ctx, device)
+        tail = () if self.channels == 1 else (3,)
+        self.src_shape = (self.n, self.sh, self.sw) + tail
+        self.d_dst = torch.zeros((self.n, self.dh, self.dw) + tail, dtype=torch.uint8, device=dev)
+        self.d_M = torch.zeros((self.n_matrices, 6), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+
+    def set_matrices(self, M):
+        """Forward 2 x 3 matrices, [n_matrices, 6] or [n_matrices, 2, 3] on the host -> d_M (a copy on torch's current stream)."""
+        m = np.ascontiguousarray(M, dtype=np.float64).reshape(self.n_matrices, 6)
+        self.d_M.copy_(torch.from_numpy(m))
+
+    def _src(self, d_src):
+        if d_src.dtype != torch.uint8 or tuple(d_src.shape) != self.src_shape or not d_src.is_contiguous():
+            raise ValueError(f"images: a contiguous uint8 device tensor {self.src_shape}")
+        return d_src.data_ptr(), self.n, self.sw, self.sh, self.channels, self.sw * self.channels
+
+    def resize(self, d_src):
+        """gms_resize_device into d_dst. Stream-ordered on the context's stream."""
+        self.ctx.resize_device(*self._src(d_src), self.d_dst.data_ptr(), self.dw, self.dh, self.dw * self.channels)
+        return self.d_dst
+
+    def warp_affine(self, d_src):
+        """gms_warp_affine_device by d_M into d_dst. Stream-ordered on the context's stream."""
+        self.ctx.warp_affine_device(*self._src(d_src), self.d_M.data_ptr(), self.n_matrices, self.d_dst.data_ptr(), self.dw, self.dh,
+                                    self.dw * self.channels)
+        return self.d_dst
+
+
+def _warp_stack(images):
+    """-> (device tensor [n, H, W] or [n, H, W, 3], contiguous; whether the caller gave a device tensor)."""
+    on_dev = torch.is_tensor(images)
+    d = images if on_dev else torch.from_numpy(np.ascontiguousarray(images, dtype=np.uint8))
+    if d.dtype != torch.uint8 or d.dim() not in (3, 4) or (d.dim() == 4 and d.shape[3] != 3) or d.numel() == 0:
+        raise ValueError("images: uint8 [n, H, W] or [n, H, W, 3]")
+    return (d if on_dev else d.cuda()).contiguous(), on_dev
+
+
+def resize_images(images, dsize, ctx=None):
+    """cv::resize(INTER_LINEAR) of n images in one gms_resize_device run. images: uint8 [n, H, W] or [n, H, W, 3], a host array or a
+    device tensor; dsize = (width, height). Returns the same kind."""
+    from .api import default_context
+    ctx = ctx or default_context()
+    d, on_dev = _warp_stack(images)
+    run = Warp(ctx, d.shape[0], (d.shape[2], d.shape[1]), dsize, 1 if d.dim() == 3 else 3, device=d.device)
+    run.resize(d)
+    ctx.synchronize()
+    return run.d_dst if on_dev else run.d_dst.cpu().numpy()
+
+
+def warp_affine_images(images, M, dsize, ctx=None):
+    """cv::warpAffine(INTER_LINEAR, BORDER_CONSTANT 0) of n images in one gms_warp_affine_device run. M: forward matrices, one ([6],
+    [2, 3], [1, 6]) for all images or one per image ([n, 6], [n, 2, 3]); dsize = (width, height). Returns what it was given: host
+    array or device tensor."""
+    from .api import default_context
+    ctx = ctx or default_context()
+    d, on_dev = _warp_stack(images)
+    m = np.ascontiguousarray(M, dtype=np.float64).reshape(-1, 6)
+    run = Warp(ctx, d.shape[0], (d.shape[2], d.shape[1]), dsize, 1 if d.dim() == 3 else 3, n_matrices=len(m), device=d.device)
+    run.set_matrices(m)
+    torch.cuda.synchronize(d.device)
+    run.warp_affine(d)
+    ctx.synchronize()
+    return run.d_dst if on_dev else run.d_dst.cpu().numpy()

@@ -68,6 +68,12 @@ SIGNATURES = {
     "gms_portrait": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp]),
     "gms_portrait_profile_device": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp, vp, vp, vp, vp]),
     "gms_median_blur": (i32, [vp, i32, i32, i32, i32, vp]),
+    "gms_resize_device": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, i32]),
+    "gms_warp_affine_device": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32]),
+    "gms_rotation_matrix_2d": (i32, [dbl, dbl, dbl, dbl, vp]),
+    "gms_resize": (i32, [vp, i32, i32, i32, vp, i32, i32]),
+    "gms_warp_affine": (i32, [vp, i32, i32, i32, vp, vp, i32, i32]),
+    "gms_img_rotate": (i32, [vp, i32, i32, i32, dbl, vp]),
     "gms_pyramid_level_sizes": (i32, [i32, i32, i32, vp, vp]),
     "gms_detect_pyramid_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
     "gms_detect_pyramid_batch_device": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp, vp, vp, vp]),

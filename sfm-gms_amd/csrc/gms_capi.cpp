@@ -27,6 +27,7 @@
 #include "portrait_core.h"
 #include "stereo_bm_core.h"
 #include "twoview_core.h"
+#include "warp_core.h"
 
 static_assert(sizeof(gms_keypoint) == 28, "gms_keypoint must match cv::KeyPoint (stride 0x1c)");
 static_assert(sizeof(gms_dmatch) == 16, "gms_dmatch must match cv::DMatch (stride 0x10)");
@@ -1319,6 +1320,81 @@ int gms_portrait(const gms_portrait_params* params, const uint8_t* bgr, const ui
     if (selected) blk.out(selected, o_s, px);
     if (blurred) blk.out(blurred, o_b, 3 * px);
     return blk.finish();
+}
+
+// ---- resize and warpAffine (warp_kernels.hip) ----------------------------------------------------------------------
+static bool warp_ranges_ok(const uint8_t* d_src, int n, int sh, int src_pitch, const uint8_t* d_dst, int dh, int dst_pitch)
+{
+    if (!d_src || !d_dst) return false;
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
+    const uintptr_t s_span = (uintptr_t)n * (uintptr_t)sh * (uintptr_t)src_pitch, d_span = (uintptr_t)n * (uintptr_t)dh * (uintptr_t)dst_pitch;
+    return !(s0 < d0 + d_span && d0 < s0 + s_span);  // the destination may not overlap the source
+}
+
+int gms_resize_device(gms_ctx* c, const uint8_t* d_src, int n, int sw, int sh, int channels, int src_pitch, uint8_t* d_dst, int dw, int dh,
+                      int dst_pitch)
+{
+    if (!c || !warp::args_ok(n, sw, sh, channels, src_pitch, dw, dh, dst_pitch) || !warp_ranges_ok(d_src, n, sh, src_pitch, d_dst, dh, dst_pitch))
+        return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] { return gms::launch_resize(d_src, n, sw, sh, channels, src_pitch, d_dst, dw, dh, dst_pitch, c->stream); });
+}
+
+int gms_warp_affine_device(gms_ctx* c, const uint8_t* d_src, int n, int sw, int sh, int channels, int src_pitch, const double* d_M,
+                           int n_matrices, uint8_t* d_dst, int dw, int dh, int dst_pitch)
+{
+    if (!c || !d_M || (n_matrices != 1 && n_matrices != n) || !warp::args_ok(n, sw, sh, channels, src_pitch, dw, dh, dst_pitch) ||
+        !warp_ranges_ok(d_src, n, sh, src_pitch, d_dst, dh, dst_pitch))
+        return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] {
+        return gms::launch_warp_affine(d_src, n, sw, sh, channels, src_pitch, d_M, n_matrices, d_dst, dw, dh, dst_pitch, c->stream);
+    });
+}
+
+int gms_rotation_matrix_2d(double center_x, double center_y, double angle, double scale, double* M)
+{
+    if (!M) return GMS_ERR_BAD_ARG;
+    warp::rotation_matrix_2d(center_x, center_y, angle, scale, M);
+    return GMS_OK;
+}
+
+int gms_resize(const uint8_t* src, int sw, int sh, int channels, uint8_t* dst, int dw, int dh)
+{
+    if (!src || !dst || !warp::args_ok(1, sw, sh, channels, (long long)channels * sw, dw, dh, (long long)channels * dw)) return GMS_ERR_BAD_ARG;
+    const size_t s_bytes = (size_t)sw * (size_t)sh * (size_t)channels, d_bytes = (size_t)dw * (size_t)dh * (size_t)channels;
+    gms::BlockLayout lay;
+    const size_t o_src = lay.add(s_bytes), o_dst = lay.add(d_bytes);
+    DevBlock blk(lay, nullptr);
+    blk.in(o_src, src, s_bytes);
+    blk.run([&](hipStream_t st) {
+        return gms::launch_resize(blk.at<uint8_t>(o_src), 1, sw, sh, channels, sw * channels, blk.at<uint8_t>(o_dst), dw, dh, dw * channels, st);
+    });
+    blk.out(dst, o_dst, d_bytes);
+    return blk.finish();
+}
+
+int gms_warp_affine(const uint8_t* src, int sw, int sh, int channels, const double* M, uint8_t* dst, int dw, int dh)
+{
+    if (!src || !dst || !M || !warp::args_ok(1, sw, sh, channels, (long long)channels * sw, dw, dh, (long long)channels * dw))
+        return GMS_ERR_BAD_ARG;
+    const size_t s_bytes = (size_t)sw * (size_t)sh * (size_t)channels, d_bytes = (size_t)dw * (size_t)dh * (size_t)channels;
+    gms::BlockLayout lay;
+    const size_t o_src = lay.add(s_bytes), o_M = lay.add(6 * sizeof(double)), o_dst = lay.add(d_bytes);
+    DevBlock blk(lay, nullptr);
+    blk.in(o_src, src, s_bytes);
+    blk.in(o_M, M, 6 * sizeof(double));
+    blk.run([&](hipStream_t st) {
+        return gms::launch_warp_affine(blk.at<uint8_t>(o_src), 1, sw, sh, channels, sw * channels, blk.at<double>(o_M), 1, blk.at<uint8_t>(o_dst),
+                                       dw, dh, dw * channels, st);
+    });
+    blk.out(dst, o_dst, d_bytes);
+    return blk.finish();
+}
+
+int gms_img_rotate(const uint8_t* src, int width, int height, int channels, double angle, uint8_t* dst)
+{
+    double M[6];
+    warp::rotation_matrix_2d(width / 2., height / 2., angle, 1.0, M);
+    return gms_warp_affine(src, width, height, channels, M, dst, width, height);
 }
 
 int gms_disparity_device(gms_ctx* c, const gms_keypoint* d_kp1, int n1, const gms_keypoint* d_kp2, int n2,

@@ -189,6 +189,11 @@ hipError_t launch_portrait(const gms_portrait_params& p, const uint8_t* d_bgr, c
                            hipStream_t stream, hipEvent_t* stage_events = nullptr);
 hipError_t launch_median_blur(const uint8_t* d_src, int n, int W, int H, int channels, int pitch, int ksize, uint8_t* d_dst,
                               hipStream_t stream);
+// resize and warpAffine (warp_kernels.hip; arithmetic in warp_core.h): no workspace
+hipError_t launch_resize(const uint8_t* d_src, int n, int sw, int sh, int channels, int src_pitch, uint8_t* d_dst, int dw, int dh,
+                         int dst_pitch, hipStream_t stream);
+hipError_t launch_warp_affine(const uint8_t* d_src, int n, int sw, int sh, int channels, int src_pitch, const double* d_M, int n_matrices,
+                              uint8_t* d_dst, int dw, int dh, int dst_pitch, hipStream_t stream);
 hipError_t launch_threshold(const int32_t* d_T, const int32_t* d_n, const int32_t* d_score, double factor,
                             int count, uint8_t* d_out, hipStream_t stream);
 

@@ -14,6 +14,7 @@
 // call sites compile unchanged apart from the namespace. Link with libgms_hip.so.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <mutex>
 #include <stdexcept>
@@ -431,6 +432,51 @@ inline void medianBlur(const std::vector<uint8_t>& src, int width, int height, i
     dst.assign(src.size(), 0);
     const int rc = gms_median_blur(src.data(), width, height, channels, ksize, dst.data());
     if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::medianBlur: ") + gms_error_string(rc));
+}
+
+// The image transforms of the reference's main() (main.cpp:36, :44, :114-120) on flat row-major 8-bit images of 1 or 3 interleaved
+// channels: cv::resize (INTER_LINEAR), cv::warpAffine (INTER_LINEAR, BORDER_CONSTANT 0; M = the forward 2 x 3 matrix, 6 doubles
+// row-major) and img_rotate (the rotation by `angle` degrees about (width / 2., height / 2.), same size). Each runs one image
+// synchronously on the current HIP device (gms_resize, gms_warp_affine, gms_img_rotate).
+inline void warp_check_image(const char* who, const std::vector<uint8_t>& src, int width, int height, int channels)
+{
+    if (width <= 0 || height <= 0 || (channels != 1 && channels != 3) || src.size() != (size_t)width * (size_t)height * (size_t)channels)
+        throw std::invalid_argument(std::string(who) + ": a width * height image of 1 or 3 interleaved channels");
+}
+
+inline void resize(const std::vector<uint8_t>& src, int width, int height, int channels, int dst_width, int dst_height,
+                   std::vector<uint8_t>& dst)
+{
+    warp_check_image("mi355::resize", src, width, height, channels);
+    if (dst_width <= 0 || dst_height <= 0) throw std::invalid_argument("mi355::resize: a positive destination size");
+    dst.assign((size_t)dst_width * (size_t)dst_height * (size_t)channels, 0);
+    const int rc = gms_resize(src.data(), width, height, channels, dst.data(), dst_width, dst_height);
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::resize: ") + gms_error_string(rc));
+}
+
+inline std::array<double, 6> getRotationMatrix2D(double center_x, double center_y, double angle, double scale)
+{
+    std::array<double, 6> M;
+    gms_rotation_matrix_2d(center_x, center_y, angle, scale, M.data());
+    return M;
+}
+
+inline void warpAffine(const std::vector<uint8_t>& src, int width, int height, int channels, const std::array<double, 6>& M, int dst_width,
+                       int dst_height, std::vector<uint8_t>& dst)
+{
+    warp_check_image("mi355::warpAffine", src, width, height, channels);
+    if (dst_width <= 0 || dst_height <= 0) throw std::invalid_argument("mi355::warpAffine: a positive destination size");
+    dst.assign((size_t)dst_width * (size_t)dst_height * (size_t)channels, 0);
+    const int rc = gms_warp_affine(src.data(), width, height, channels, M.data(), dst.data(), dst_width, dst_height);
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::warpAffine: ") + gms_error_string(rc));
+}
+
+inline void img_rotate(const std::vector<uint8_t>& src, int width, int height, int channels, double angle, std::vector<uint8_t>& dst)
+{
+    warp_check_image("mi355::img_rotate", src, width, height, channels);
+    dst.assign(src.size(), 0);
+    const int rc = gms_img_rotate(src.data(), width, height, channels, angle, dst.data());
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::img_rotate: ") + gms_error_string(rc));
 }
 
 }  // namespace mi355

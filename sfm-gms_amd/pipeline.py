@@ -19,12 +19,14 @@ run_images is the same three flows from pixels: grey or BGR images --gms_bgr_to_
 
 torch here is device memory only; every stage is a call into csrc/libgms_hip.so. Used by tools/gms_filter_file.py, tools/gms_sfm_pair.py
 and the tests."""
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
-from .batch import (BfSelect, DescriptorTable, DetectPyramid, FrameTable, LogosDictionary, LogosFilter, LogosTable, _device, _to_dev,
+from .batch import (BfSelect, DescriptorTable, DetectPyramid, FrameTable, LogosDictionary, LogosFilter, LogosTable, Warp, _device, _to_dev,
                     bf_select_table, bgr_to_gray, frame_counts, frame_pairs_of, logos_dictionary, pair_table, tables_from_detector)
-from .api import logos_dict_args
+from .api import getRotationMatrix2D, logos_dict_args
 from .types import (DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128, GMS_ERR_CAPACITY, PAIR_DTYPE, RESULT_DTYPE, TWO_VIEW_DTYPE,
                     desc_layout, make_camera)
 
@@ -226,6 +228,75 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
     if keep_tables:
         r.update(tables=(frames, descs))
     return r
+
+
+MAIN_SCENARIOS = ("normal", "rotated", "resized")   # frame 0 = the left image; frames 1, 2, 3 = the right image of each scenario
+
+
+def run_main_scenarios(ctx, img1, img2, resize_to=(1000, 1000), angle=180, threshold=20, max_keypoints=10000, n_levels=8,
+                       descriptor="grad", thresholdFactor=6.0, cross_check=True, distance_coef=4.0, max_size=500, camera=None, dist=None,
+                       prob=0.7, ransac_threshold=1.0, max_iters=1000, device=None):
+    """The three feature-match scenarios of the reference's main() (main.cpp:28-47) from its two photographs: the pair as it is, the
+    right image turned by `angle` degrees (img_rotate: getRotationMatrix2D + warpAffine) and the right image resized to `resize_to` =
+    (width, height) (cv::resize). img1, img2: equally sized [H, W] grey or [H, W, 3] BGR images, host arrays or device tensors.
+    The right image is transformed on the device (gms_warp_affine_device, gms_resize_device; BGR is transformed as BGR and then goes
+    through gms_bgr_to_gray_device, as the reference transforms what imread gave it); one detector runs over left, right and the
+    turned image, a second over the resized one; gms_detect_pack_device puts all four frames back to back, and ONE FrameTable /
+    DescriptorTable with each frame's own size is built there -- between the pixels and the results only the 5 frame offsets (and the
+    status records the stages read) come back. Each scenario then runs its pair (0, k) with method="bf" (bruteForceMatch) and with
+    method="gms" at withRotation = withScale = True (FeatureMatchUtil.cpp:69). detector and stage arguments: run_images'.
+    Returns {"images": {"rotated", "resized"} (the transformed right images, of the kind that came in), "tables": (FrameTable,
+    DescriptorTable), "sizes": the four (width, height), and per scenario name {"bf": record, "gms": record}, run_dataset's records}."""
+    if descriptor not in ("brief", "grad", "both"):
+        raise ValueError('descriptor: "brief", "grad" or "both"')
+    pair, is_bgr = image_stack([img1, img2])
+    on_dev = torch.is_tensor(pair)
+    h, w = pair.shape[1:3]
+    rw, rh = int(resize_to[0]), int(resize_to[1])
+    dev = _device(ctx, device)
+    d_pair = (pair if on_dev else torch.from_numpy(np.ascontiguousarray(pair))).to(dev).contiguous()
+    ch = 3 if is_bgr else 1
+    # (both detectors refuse a bad size before anything is launched)
+    det3 = DetectPyramid(ctx, 3, w, h, threshold, max_keypoints, n_levels, dev, descriptor)
+    det1 = DetectPyramid(ctx, 1, rw, rh, threshold, max_keypoints, n_levels, dev, descriptor)
+    turn = Warp(ctx, 1, (w, h), (w, h), ch, 1, dev)
+    shrink = Warp(ctx, 1, (w, h), (rw, rh), ch, 1, dev)
+    turn.set_matrices(getRotationMatrix2D((w / 2., h / 2.), angle, 1.0))
+    torch.cuda.synchronize(dev)
+    d_right = d_pair[1:2]
+    turn.warp_affine(d_right)
+    shrink.resize(d_right)
+    ctx.synchronize()
+    d_three = torch.cat([d_pair, turn.d_dst])
+    d_small = shrink.d_dst
+    if is_bgr:
+        d_three, d_small = bgr_to_gray(ctx, d_three), bgr_to_gray(ctx, d_small)
+    # the two detectors write their blocks into one [4][max_keypoints] set, so that one pack run lays the four frames back to back
+    slots = max(4 * det3.max_keypoints, 1)
+    joint = SimpleNamespace(ctx=ctx, n=4, max_keypoints=det3.max_keypoints, w=w, h=h,
+                            d_kp=torch.zeros(slots * 28, dtype=torch.uint8, device=dev),
+                            d_desc=torch.zeros(slots * 32, dtype=torch.uint8, device=dev),
+                            d_counts=torch.zeros(4, dtype=torch.int32, device=dev),
+                            d_rows128=None if descriptor == "brief" else torch.zeros(slots * 128, dtype=torch.float32, device=dev))
+    cut = 3 * det3.max_keypoints
+    for det, lo, hi, c0, c1 in ((det3, 0, cut, 0, 3), (det1, cut, slots, 3, 4)):
+        det.d_kp, det.d_desc, det.d_counts = joint.d_kp[lo * 28:hi * 28], joint.d_desc[lo * 32:hi * 32], joint.d_counts[c0:c1]
+        if joint.d_rows128 is not None:
+            det.d_rows128 = joint.d_rows128[lo * 128:hi * 128]
+    torch.cuda.synchronize(dev)
+    det3.run(d_three.contiguous())
+    det1.run(d_small.contiguous())
+    sizes = [(w, h)] * 3 + [(rw, rh)]
+    kind = GMS_DESC_HAMMING256 if descriptor == "brief" else GMS_DESC_L2_F32X128
+    frames, descs = tables_from_detector(joint, sizes, kind)
+    tail = (camera, dist, prob, ransac_threshold, max_iters)
+    images = {"rotated": turn.d_dst[0], "resized": shrink.d_dst[0]}
+    out = {"images": images if on_dev else {k: v.cpu().numpy() for k, v in images.items()}, "tables": (frames, descs), "sizes": sizes}
+    for k, name in enumerate(MAIN_SCENARIOS, start=1):
+        src = pair_table(np.array([[0, k]], dtype=np.int64), 0)
+        out[name] = {"bf": _run_bf(ctx, descs, src, cross_check, distance_coef, max_size, *tail),
+                     "gms": _run_gms(ctx, frames, descs, src, None, True, True, thresholdFactor, *tail)}
+    return out
 
 
 def dictionary_training_options(train_dictionary):
