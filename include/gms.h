@@ -744,6 +744,52 @@ int gms_warp_affine(const uint8_t* src, int src_width, int src_height, int chann
                     int dst_height);
 int gms_img_rotate(const uint8_t* src, int width, int height, int channels, double angle, uint8_t* dst);
 
+/* ---- camera calibration from chessboard photographs (main.cpp:53-68, CalibrationUtil.cpp:3-53) ---------------------
+ * The corner finder is THIS LIBRARY'S OWN definition, not OpenCV's quad-based findChessboardCorners; cornerSubPix restates OpenCV
+ * 4.5.2's algorithm in fp64; calibrateCamera follows its structure. Parity with an OpenCV build is unpinned. tests/calib_ref.py states
+ * every step in numpy and csrc/calib_core.h holds the arithmetic.
+ *   candidates: B = 5 x 5 box sum of the image, S = 5 x 5 box sum of B; with d = 4, sxx = S(x+d,y) + S(x-d,y) - 2 S, syy likewise along
+ *     y, sxy = S(x+d,y+d) + S(x-d,y-d) - S(x+d,y-d) - S(x-d,y+d); R = max(0, sxy^2 - 4 sxx syy) >> 10 (64-bit products; R < 2^29), and
+ *     R = 0 closer than GMS_DETECT_BORDER to an edge. A peak: R > 0, greater than every 17 x 17 neighbour earlier in raster order and
+ *     not smaller than any later one. Per image the max_candidates peaks of largest R (ties cut and ordered in raster order), written
+ *     in descending R, then raster order. Exact, whatever ties.
+ * gms_chess_candidates_device: n (1..65535) equally sized grey images (sides 1..GMS_WARP_MAX_SIDE), pitch = width, back to back, on
+ *   the context's stream; no allocation, no synchronisation, no readback (graph-capturable). d_workspace: 256-byte aligned,
+ *   gms_chess_candidates_workspace_bytes (0 for arguments that are refused). d_out: [n][max_candidates] records, image i's first
+ *   d_counts[i] are written, the others are left as they were. max_candidates 1..GMS_CHESS_MAX_CANDIDATES.
+ * gms_corner_subpix_device: cv::cornerSubPix(win (5, 5), zeroZone (-1, -1), MAX_ITER + EPS (max_iter, eps)) on n_corners corners
+ *   d_corners [n_corners][2] doubles (x, y), refined in place; corner i lies in image d_image_of[i] (NULL: all in image 0; an index
+ *   outside 0..n_images-1 leaves the corner and reports status 2). d_status (may be NULL) [n_corners]: 0 refined; 1 the start kept, as the
+ *   result moved more than win; 2 the start kept, as the 13 x 13 patch of samples left the image (OpenCV replicates the border there;
+ *   this library refuses); 3 stopped on a singular system. win must be 5 (the committed mask), max_iter >= 1, eps >= 0.
+ * gms_find_chessboard_corners: ONE grey image on host pointers (dense rows), synchronous, on the current HIP device: the nx * ny
+ *   strongest candidates ordered onto the board of nx points per row and ny rows (nx != ny, both >= 2, nx * ny <= 4096). *found = 1 and
+ *   corners [nx * ny][2] floats in findChessboardCorners' order (row by row; of the two half turns the one whose first point is smaller
+ *   in (y, x); never mirrored), or *found = 0 (fewer candidates, or they do not lie on such a grid within a quarter cell).
+ * gms_order_chessboard: the ordering alone, on the host, no GPU work: points [nx * ny][2] doubles (the first nx * ny candidates of an
+ *   image) -> *found and ordered [nx * ny][2], by the same rule.
+ * gms_corner_subpix: the same one image and corners [n][2] doubles on host pointers; a start whose patch leaves the image is
+ *   GMS_ERR_BAD_ARG, and nothing is changed.
+ * gms_calibrate_camera: host fp64, no GPU work (540 points and 69 parameters: not a kernel). n_views views; view v has counts[v] (>= 4)
+ *   points: object_points [total][3] and image_points [total][2] doubles, the views back to back. Out: K [9] row-major, dist [5]
+ *   (k1, k2, p1, p2, k3: OpenCV's flags = 0), rvecs and tvecs [n_views][3], *rms. GMS_ERR_DOMAIN: a view's points give no homography. */
+#define GMS_CHESS_MAX_CANDIDATES 4096
+typedef struct gms_chess_candidate {
+    int32_t x, y;
+    uint32_t response;
+} gms_chess_candidate;
+size_t gms_chess_candidates_workspace_bytes(int width, int height, int n_images);
+int gms_chess_candidates_device(gms_ctx* ctx, const uint8_t* d_images, int n_images, int width, int height, int max_candidates,
+                                void* d_workspace, size_t workspace_bytes, gms_chess_candidate* d_out, int32_t* d_counts);
+int gms_corner_subpix_device(gms_ctx* ctx, const uint8_t* d_images, int n_images, int width, int height, const int32_t* d_image_of,
+                             double* d_corners, int n_corners, int win, int max_iter, double eps, int32_t* d_status);
+int gms_find_chessboard_corners(const uint8_t* image, int width, int height, int nx, int ny, int* found, float* corners);
+int gms_order_chessboard(const double* points, int nx, int ny, int* found, double* ordered);
+int gms_corner_subpix(const uint8_t* image, int width, int height, double* corners, int n_corners, int win, int max_iter, double eps,
+                      int32_t* status);
+int gms_calibrate_camera(const double* object_points, const double* image_points, const int32_t* counts, int n_views, int width,
+                         int height, double* K, double* dist, double* rvecs, double* tvecs, double* rms);
+
 const char* gms_error_string(int code);
 const char* gms_version(void);
 

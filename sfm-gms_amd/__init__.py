@@ -15,6 +15,8 @@ from .types import (KEYPOINT_DTYPE, DMATCH_DTYPE, PAIR_DTYPE, RESULT_DTYPE, LOGO
 from .capi import load_library, library_path, EXPORTED_SYMBOLS  # noqa: F401
 from .api import matchGMS, matchLOGOS, trainLogosDictionary, bruteForceMatch, stereoBM, stereo_match, portraitMode, medianBlur, structureFromMotion, GmsContext  # noqa: F401
 from .api import resize, warpAffine, getRotationMatrix2D, imgRotate  # noqa: F401
+from .api import findChessboardCorners, cornerSubPix, calibrateCamera, addChessboardPoints, chessboardObjectPoints  # noqa: F401
+from .types import CHESS_CANDIDATE_DTYPE  # noqa: F401
 from .sharding import all_pairs_count, pair_from_index, shard_range  # noqa: F401
 
 __all__ = [
@@ -22,5 +24,6 @@ __all__ = [
     "load_library", "library_path", "EXPORTED_SYMBOLS", "matchGMS", "matchLOGOS", "trainLogosDictionary", "LOGOS_DICT_RESULT_DTYPE", "bruteForceMatch", "stereoBM", "stereo_match",
     "STEREO_BM_PARAMS_DTYPE", "stereo_bm_params", "GmsContext",
     "portraitMode", "medianBlur", "structureFromMotion", "resize", "warpAffine", "getRotationMatrix2D", "imgRotate", "PORTRAIT_PARAMS_DTYPE", "portrait_params",
+    "findChessboardCorners", "cornerSubPix", "calibrateCamera", "addChessboardPoints", "chessboardObjectPoints", "CHESS_CANDIDATE_DTYPE",
     "all_pairs_count", "pair_from_index", "shard_range", "GMS_DESC_HAMMING256", "GMS_DESC_L2_F32X128", "GMS_DETECT_BORDER",
 ]

@@ -394,6 +394,25 @@ class GmsContext:
                                                 d_M, int(n_matrices), d_dst, int(dst_width), int(dst_height), int(dst_pitch)), self._lib,
                "gms_warp_affine_device")
 
+    # -- chessboard corner candidates and cornerSubPix (batch.ChessCorners drives these) ---------------------------------
+    def chess_candidates_workspace_bytes(self, width, height, n_images):
+        return int(self._lib.gms_chess_candidates_workspace_bytes(int(width), int(height), int(n_images)))
+
+    def chess_candidates_device(self, d_images, n_images, width, height, max_candidates, d_ws, ws_bytes, d_out, d_counts):
+        """gms_chess_candidates_device on raw device pointers: d_out [n][max_candidates] CHESS_CANDIDATE_DTYPE, d_counts int32 [n].
+        Stream-ordered."""
+        _check(self._lib.gms_chess_candidates_device(self._h, d_images or None, int(n_images), int(width), int(height), int(max_candidates),
+                                                     d_ws or None, int(ws_bytes), d_out or None, d_counts or None), self._lib,
+               "gms_chess_candidates_device")
+
+    def corner_subpix_device(self, d_images, n_images, width, height, d_image_of, d_corners, n_corners, win=5, max_iter=30, eps=0.1,
+                             d_status=None):
+        """gms_corner_subpix_device: d_corners float64 [n_corners, 2] refined in place; d_image_of int32 [n_corners] or None (image 0).
+        Stream-ordered."""
+        _check(self._lib.gms_corner_subpix_device(self._h, d_images or None, int(n_images), int(width), int(height), d_image_of or None,
+                                                  d_corners or None, int(n_corners), int(win), int(max_iter), float(eps), d_status or None),
+               self._lib, "gms_corner_subpix_device")
+
     def selftest_five_point(self, x1, x2):
         """gms_selftest_five_point: x1, x2 [n_samples, 5, 2] normalised points -> list of [k, 3, 3] model arrays, one per sample."""
         x1 = np.asarray(x1, dtype=np.float64).reshape(-1, 5, 2)
@@ -685,3 +704,79 @@ def imgRotate(image, angle):
     size. 180 degrees is NOT image[::-1, ::-1]: it is that flip moved by one pixel, behind a black first row and column."""
     h, w = image.shape[:2]
     return warpAffine(image, getRotationMatrix2D((w / 2., h / 2.), angle, 1.0), (w, h))
+
+
+def _grey_host(image, who):
+    img = np.ascontiguousarray(image, dtype=np.uint8)
+    if img.ndim != 2 or img.size == 0:
+        raise ValueError(f"{who}: an 8-bit grey image [H, W]")
+    return img
+
+
+def findChessboardCorners(image, patternSize):
+    """(found, corners) for a grey image [H, W] and patternSize = (nx points per row, ny rows), nx != ny: the library's own finder
+    (NOT OpenCV's quad-based one): the nx * ny strongest saddle-response peaks (gms_chess_candidates_device's), ordered
+    onto the board. corners: float32 [nx * ny, 2] in findChessboardCorners' order (row by row; of the two half turns the one whose
+    first point is smaller in (y, x); never mirrored), or None. tests/calib_ref.py states every step."""
+    lib = load_library()
+    img = _grey_host(image, "image")
+    nx, ny = int(patternSize[0]), int(patternSize[1])
+    found = C.c_int(0)
+    corners = np.zeros((max(nx * ny, 1), 2), np.float32)
+    _check(lib.gms_find_chessboard_corners(img.ctypes.data, img.shape[1], img.shape[0], nx, ny, C.byref(found), corners.ctypes.data), lib,
+           "gms_find_chessboard_corners")
+    return (True, corners) if found.value else (False, None)
+
+
+def cornerSubPix(image, corners, win=(5, 5), criteria=(30, 0.1), return_status=False):
+    """cv::cornerSubPix(image, corners, win, (-1, -1), TermCriteria(MAX_ITER + EPS, *criteria)) on the GPU, OpenCV 4.5.2's algorithm
+    in fp64 (gms_corner_subpix): corners [n, 2] -> float64 [n, 2]. win must be (5, 5). A start whose 13 x 13 patch of samples leaves
+    the image is refused (GmsError, bad argument). return_status: also the int32 status per corner (include/gms.h)."""
+    lib = load_library()
+    img = _grey_host(image, "image")
+    if tuple(int(v) for v in win) != (5, 5):
+        raise ValueError("win: (5, 5), the window whose mask is committed")
+    pts = np.array(corners, dtype=np.float64).reshape(-1, 2)
+    status = np.zeros(max(len(pts), 1), np.int32)
+    _check(lib.gms_corner_subpix(img.ctypes.data, img.shape[1], img.shape[0], pts.ctypes.data, len(pts), 5, int(criteria[0]), float(criteria[1]),
+                                 status.ctypes.data), lib, "gms_corner_subpix")
+    return (pts, status[:len(pts)]) if return_status else pts
+
+
+def calibrateCamera(object_points, image_points, image_size):
+    """cv::calibrateCamera(objectPoints, imagePoints, imageSize, K, dist, rvecs, tvecs) with flags = 0, on the host in fp64
+    (gms_calibrate_camera; 540 points and 69 parameters are no work for a GPU): object_points, image_points: one [m, 3] / [m, 2] array
+    per view; image_size = (width, height). Returns (rms, K [3, 3], dist [5] = (k1, k2, p1, p2, k3), rvecs [n, 3], tvecs [n, 3])."""
+    lib = load_library()
+    obj = [np.asarray(o, dtype=np.float64).reshape(-1, 3) for o in object_points]
+    img = [np.asarray(i, dtype=np.float64).reshape(-1, 2) for i in image_points]
+    if len(obj) == 0 or len(obj) != len(img) or any(len(o) != len(i) for o, i in zip(obj, img)):
+        raise ValueError("object_points, image_points: one array per view, of equal lengths")
+    counts = np.array([len(o) for o in obj], np.int32)
+    o, i = np.ascontiguousarray(np.concatenate(obj)), np.ascontiguousarray(np.concatenate(img))
+    n = len(obj)
+    K, dist, rv, tv, rms = np.zeros((3, 3)), np.zeros(5), np.zeros((n, 3)), np.zeros((n, 3)), C.c_double(0)
+    _check(lib.gms_calibrate_camera(o.ctypes.data, i.ctypes.data, counts.ctypes.data, n, int(image_size[0]), int(image_size[1]), K.ctypes.data,
+                                    dist.ctypes.data, rv.ctypes.data, tv.ctypes.data, C.byref(rms)), lib, "gms_calibrate_camera")
+    return float(rms.value), K, dist, rv, tv
+
+
+def chessboardObjectPoints(board_size):
+    """The reference's object points (CalibrationUtil.cpp:13-17): point i * nx + j is (i, j, 0)."""
+    nx, ny = int(board_size[0]), int(board_size[1])
+    i, j = np.mgrid[0:ny, 0:nx]
+    return np.stack([i.ravel(), j.ravel(), np.zeros(nx * ny)], 1).astype(np.float64)
+
+
+def addChessboardPoints(images, board_size):
+    """The reference's addChessboardPoints (CalibrationUtil.cpp:3-53): findChessboardCorners, then cornerSubPix((5, 5), (-1, -1),
+    (30, 0.1)), per grey image; images where the board is not found are skipped. Returns (successes, object_points, image_points):
+    one [nx * ny, 3] and one [nx * ny, 2] float64 array per success."""
+    obj, img = [], []
+    for im in images:
+        found, corners = findChessboardCorners(im, board_size)
+        if not found:
+            continue
+        img.append(cornerSubPix(im, corners, (5, 5), (30, 0.1)))
+        obj.append(chessboardObjectPoints(board_size))
+    return len(img), obj, img

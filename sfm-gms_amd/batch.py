@@ -831,3 +831,52 @@ def warp_affine_images(images, M, dsize, ctx=None):
     run.warp_affine(d)
     ctx.synchronize()
     return run.d_dst if on_dev else run.d_dst.cpu().numpy()
+
+
+class ChessCorners:
+    """Device buffers of gms_chess_candidates_device for n grey images of one size: the workspace, the candidate records
+    [n, max_candidates] and the counts [n], sized once, so that run() can be repeated or captured into a graph on new pixels in the
+    same tensor. candidates() reads the records back (the only readback of the corner search)."""
+
+    def __init__(self, ctx, n, width, height, max_candidates=256, device=None):
+        self.ctx, self.n, self.width, self.height, self.max_candidates = ctx, int(n), int(width), int(height), int(max_candidates)
+        self.ws_bytes = ctx.chess_candidates_workspace_bytes(width, height, n)
+        if self.ws_bytes == 0 or not 1 <= self.max_candidates <= 4096:
+            raise ValueError("ChessCorners: image size, batch size or max_candidates rejected (include/gms.h)")
+        dev = _device(ctx, device)
+        self.d_ws = torch.zeros(self.ws_bytes, dtype=torch.uint8, device=dev)
+        self.d_out = torch.zeros(self.n * self.max_candidates * 12, dtype=torch.uint8, device=dev)
+        self.d_counts = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+
+    def run(self, d_images):
+        """gms_chess_candidates_device on a contiguous uint8 device tensor [n, H, W]. Stream-ordered on the context's stream."""
+        if d_images.dtype != torch.uint8 or tuple(d_images.shape) != (self.n, self.height, self.width) or not d_images.is_contiguous():
+            raise ValueError(f"images: a contiguous uint8 device tensor {(self.n, self.height, self.width)}")
+        self.ctx.chess_candidates_device(d_images.data_ptr(), self.n, self.width, self.height, self.max_candidates, self.d_ws.data_ptr(),
+                                         self.ws_bytes, self.d_out.data_ptr(), self.d_counts.data_ptr())
+
+    def candidates(self):
+        """Waits for the context's stream -> one CHESS_CANDIDATE_DTYPE array per image (its first counts[i] records)."""
+        from .types import CHESS_CANDIDATE_DTYPE
+        self.ctx.synchronize()
+        counts = self.d_counts.cpu().numpy()
+        recs = self.d_out.cpu().numpy().view(CHESS_CANDIDATE_DTYPE).reshape(self.n, self.max_candidates)
+        return [recs[i, :int(counts[i])].copy() for i in range(self.n)]
+
+
+def corner_subpix_images(ctx, d_images, image_of, corners, max_iter=30, eps=0.1):
+    """gms_corner_subpix_device: corners float64 [m, 2] (host) of images d_images[image_of[k]] -> (refined [m, 2], status [m]) on the
+    host; the images stay on the device."""
+    n, h, w = d_images.shape
+    pts = np.ascontiguousarray(corners, dtype=np.float64).reshape(-1, 2)
+    if len(pts) == 0:
+        return pts, np.zeros(0, np.int32)
+    dev = d_images.device
+    d_pts = torch.from_numpy(pts).to(dev)
+    d_of = torch.from_numpy(np.ascontiguousarray(image_of, dtype=np.int32)).to(dev)
+    d_status = torch.zeros(len(pts), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)
+    ctx.corner_subpix_device(d_images.data_ptr(), n, w, h, d_of.data_ptr(), d_pts.data_ptr(), len(pts), 5, max_iter, eps, d_status.data_ptr())
+    ctx.synchronize()
+    return d_pts.cpu().numpy(), d_status.cpu().numpy()

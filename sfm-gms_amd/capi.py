@@ -74,6 +74,13 @@ SIGNATURES = {
     "gms_resize": (i32, [vp, i32, i32, i32, vp, i32, i32]),
     "gms_warp_affine": (i32, [vp, i32, i32, i32, vp, vp, i32, i32]),
     "gms_img_rotate": (i32, [vp, i32, i32, i32, dbl, vp]),
+    "gms_chess_candidates_workspace_bytes": (sz, [i32, i32, i32]),
+    "gms_chess_candidates_device": (i32, [vp, vp, i32, i32, i32, i32, vp, sz, vp, vp]),
+    "gms_corner_subpix_device": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, dbl, vp]),
+    "gms_find_chessboard_corners": (i32, [vp, i32, i32, i32, i32, vp, vp]),
+    "gms_order_chessboard": (i32, [vp, i32, i32, vp, vp]),
+    "gms_corner_subpix": (i32, [vp, i32, i32, vp, i32, i32, i32, dbl, vp]),
+    "gms_calibrate_camera": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "gms_pyramid_level_sizes": (i32, [i32, i32, i32, vp, vp]),
     "gms_detect_pyramid_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
     "gms_detect_pyramid_batch_device": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp, vp, vp, vp]),

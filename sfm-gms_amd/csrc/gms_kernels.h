@@ -194,6 +194,12 @@ hipError_t launch_resize(const uint8_t* d_src, int n, int sw, int sh, int channe
                          int dst_pitch, hipStream_t stream);
 hipError_t launch_warp_affine(const uint8_t* d_src, int n, int sw, int sh, int channels, int src_pitch, const double* d_M, int n_matrices,
                               uint8_t* d_dst, int dw, int dh, int dst_pitch, hipStream_t stream);
+// chessboard corner candidates and cornerSubPix (calib_kernels.hip; arithmetic in calib_core.h; workspace: ws_layout.h ChessLayout)
+size_t     chess_candidates_ws_bytes(int n, int w, int h);
+hipError_t launch_chess_candidates(const uint8_t* d_images, int n, int w, int h, int max_candidates, void* d_ws,
+                                   gms_chess_candidate* d_out, int32_t* d_counts, hipStream_t stream);
+hipError_t launch_corner_subpix(const uint8_t* d_images, int n_images, int w, int h, const int32_t* d_image_of, double* d_corners,
+                                int n_corners, int max_iter, double eps, int32_t* d_status, hipStream_t stream);
 hipError_t launch_threshold(const int32_t* d_T, const int32_t* d_n, const int32_t* d_score, double factor,
                             int count, uint8_t* d_out, hipStream_t stream);
 

@@ -9,6 +9,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "calib_core.h"
 #include "gms.h"
 #include "portrait_core.h"
 
@@ -245,6 +246,21 @@ inline PortraitLayout portrait_layout(int n, int W, int H)
     WsCursor c;
     return {c.take(px, 256), c.take(px, 256), c.take(px, 256), c.take(px, 256), c.take(4 * px, 256), c.take(8 * px, 256),
             c.take(8 * (size_t)n * pm_key_cap(W, H), 256), c.take((size_t)n * kChosenStride * 4, 256), c.end};
+}
+
+// ---- chessboard corner candidates (calib_kernels.hip) -------------------------------------------------------------------------------
+// Every call zeroes n_list first.
+struct ChessLayout {
+    size_t R;       // uint32 [n][h][w]: the response
+    size_t list;    // uint64 [n][calib::peak_capacity(w, h)]: the peaks' rank keys, in no fixed order
+    size_t n_list;  // uint32 [n]: peaks per image
+    size_t total;
+};
+inline ChessLayout chess_layout(int n, int w, int h)
+{
+    const size_t px = (size_t)n * (size_t)w * (size_t)h;
+    WsCursor c;
+    return {c.take(4 * px, 256), c.take(8 * (size_t)n * (size_t)calib::peak_capacity(w, h), 256), c.take(4 * (size_t)n, 256), c.end};
 }
 
 // ---- bruteForceMatch's selection (bf_select_kernels.hip) ----------------------------------------------------------------------------

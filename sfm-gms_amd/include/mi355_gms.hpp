@@ -479,4 +479,97 @@ inline void img_rotate(const std::vector<uint8_t>& src, int width, int height, i
     if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::img_rotate: ") + gms_error_string(rc));
 }
 
+// ---- camera calibration from chessboard photographs (main.cpp:53-68, CalibrationUtil.cpp:3-53) --------------------------
+// The library's own corner finder (NOT OpenCV's quad-based one), OpenCV 4.5.2's cornerSubPix in fp64, and calibrateCamera with
+// flags = 0, on flat 8-bit grey images (dense rows). Points are doubles, so that nothing is rounded between the steps.
+struct ImagePoint { double x = 0, y = 0; };
+struct ObjectPoint { double x = 0, y = 0, z = 0; };
+struct CameraCalibration {
+    std::array<double, 9> K{};       // row-major
+    std::array<double, 5> dist{};    // k1, k2, p1, p2, k3
+    std::vector<std::array<double, 3>> rvecs, tvecs;
+    double rms = 0;
+};
+
+inline void calib_check_image(const char* who, const std::vector<uint8_t>& grey, int width, int height)
+{
+    if (width <= 0 || height <= 0 || grey.size() != (size_t)width * (size_t)height)
+        throw std::invalid_argument(std::string(who) + ": width * height grey bytes");
+}
+
+// findChessboardCorners(image, Size(nx, ny), corners): true and nx * ny corners in its order (row by row), or false
+inline bool findChessboardCorners(const std::vector<uint8_t>& grey, int width, int height, const Size& patternSize, std::vector<ImagePoint>& corners)
+{
+    calib_check_image("mi355::findChessboardCorners", grey, width, height);
+    const long long n = (long long)patternSize.width * patternSize.height;
+    if (patternSize.width < 2 || patternSize.height < 2 || n > GMS_CHESS_MAX_CANDIDATES)
+        throw std::invalid_argument("mi355::findChessboardCorners: a pattern of at least 2 x 2 and at most 4096 points");
+    std::vector<float> pts((size_t)(2 * n));
+    int found = 0;
+    const int rc = gms_find_chessboard_corners(grey.data(), width, height, patternSize.width, patternSize.height, &found, pts.data());
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::findChessboardCorners: ") + gms_error_string(rc));
+    corners.clear();
+    if (found)
+        for (long long i = 0; i < n; ++i) corners.push_back({pts[(size_t)(2 * i)], pts[(size_t)(2 * i + 1)]});
+    return found != 0;
+}
+
+// cornerSubPix(image, corners, Size(5, 5), Size(-1, -1), TermCriteria(MAX_ITER + EPS, max_iter, eps)), in place
+inline void cornerSubPix(const std::vector<uint8_t>& grey, int width, int height, std::vector<ImagePoint>& corners, const Size& win = Size(5, 5),
+                         int max_iter = 30, double eps = 0.1)
+{
+    calib_check_image("mi355::cornerSubPix", grey, width, height);
+    if (win.width != 5 || win.height != 5) throw std::invalid_argument("mi355::cornerSubPix: win (5, 5)");
+    static_assert(sizeof(ImagePoint) == 2 * sizeof(double), "ImagePoint is two doubles");
+    const int rc = gms_corner_subpix(grey.data(), width, height, corners.empty() ? nullptr : &corners[0].x, (int)corners.size(), 5, max_iter, eps, nullptr);
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::cornerSubPix: ") + gms_error_string(rc));
+}
+
+// calibrateCamera(objectPoints, imagePoints, imageSize, K, dist, rvecs, tvecs) with flags = 0; the RMS reprojection error is .rms
+inline CameraCalibration calibrateCamera(const std::vector<std::vector<ObjectPoint>>& objectPoints, const std::vector<std::vector<ImagePoint>>& imagePoints,
+                                         const Size& imageSize)
+{
+    if (objectPoints.empty() || objectPoints.size() != imagePoints.size()) throw std::invalid_argument("mi355::calibrateCamera: one point set per view");
+    static_assert(sizeof(ObjectPoint) == 3 * sizeof(double), "ObjectPoint is three doubles");
+    std::vector<double> obj, img;
+    std::vector<int32_t> counts;
+    for (size_t v = 0; v < objectPoints.size(); ++v) {
+        if (objectPoints[v].size() != imagePoints[v].size()) throw std::invalid_argument("mi355::calibrateCamera: as many image as object points");
+        counts.push_back((int32_t)objectPoints[v].size());
+        for (const ObjectPoint& o : objectPoints[v]) obj.insert(obj.end(), {o.x, o.y, o.z});
+        for (const ImagePoint& i : imagePoints[v]) img.insert(img.end(), {i.x, i.y});
+    }
+    CameraCalibration c;
+    const size_t n = counts.size();
+    std::vector<double> rv(3 * n), tv(3 * n);
+    const int rc = gms_calibrate_camera(obj.data(), img.data(), counts.data(), (int)n, imageSize.width, imageSize.height, c.K.data(), c.dist.data(),
+                                        rv.data(), tv.data(), &c.rms);
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::calibrateCamera: ") + gms_error_string(rc));
+    for (size_t v = 0; v < n; ++v) {
+        c.rvecs.push_back({rv[3 * v], rv[3 * v + 1], rv[3 * v + 2]});
+        c.tvecs.push_back({tv[3 * v], tv[3 * v + 1], tv[3 * v + 2]});
+    }
+    return c;
+}
+
+// The reference's addChessboardPoints (CalibrationUtil.cpp:3-53) on equally sized grey images: per image findChessboardCorners, then
+// cornerSubPix((5, 5), (-1, -1), (30, 0.1)); images without a board are skipped; object point i * nx + j is (i, j, 0). Returns the successes.
+inline int addChessboardPoints(const std::vector<std::vector<uint8_t>>& images, int width, int height, const Size& boardSize,
+                               std::vector<std::vector<ObjectPoint>>& objPtr, std::vector<std::vector<ImagePoint>>& imgPtr)
+{
+    std::vector<ObjectPoint> objectCorners;
+    for (int i = 0; i < boardSize.height; ++i)
+        for (int j = 0; j < boardSize.width; ++j) objectCorners.push_back({(double)i, (double)j, 0.0});
+    int successes = 0;
+    for (const std::vector<uint8_t>& image : images) {
+        std::vector<ImagePoint> corners;
+        if (!findChessboardCorners(image, width, height, boardSize, corners)) continue;
+        cornerSubPix(image, width, height, corners, Size(5, 5), 30, 0.1);
+        imgPtr.push_back(corners);
+        objPtr.push_back(objectCorners);
+        ++successes;
+    }
+    return successes;
+}
+
 }  // namespace mi355

@@ -299,6 +299,57 @@ def run_main_scenarios(ctx, img1, img2, resize_to=(1000, 1000), angle=180, thres
     return out
 
 
+def calibrate_images(ctx, images, board_size=(6, 9), max_candidates=256, device=None):
+    """The reference's calibration (main.cpp:53-68): addChessboardPoints over the images, then calibrateCamera. images: [n, H, W] grey
+    or [n, H, W, 3] BGR (through gms_bgr_to_gray_device), 8-bit, a host array, a device tensor or a list of equally sized images.
+    ONE gms_chess_candidates_device launch covers all images and only the candidate records are read back; the boards are ordered on
+    the host (gms_order_chessboard, the rule gms_find_chessboard_corners applies, here on the records); ONE
+    gms_corner_subpix_device launch refines every found board's corners on the resident images; gms_calibrate_camera runs on the
+    host. Images without a board are skipped, as the reference skips them.
+    Returns {"found": bool [n], "successes", "image_points": [successes, nx * ny, 2], "object_points", "K", "dist", "rvecs", "tvecs",
+    "rms", "camera": (fx, fy, cx, cy), "candidates": per image}; K and the rest are None when no board was found."""
+    from .api import calibrateCamera, chessboardObjectPoints
+    from .batch import ChessCorners, corner_subpix_images
+    from .capi import load_library
+    import ctypes as C
+    stack, is_bgr = image_stack(images)
+    dev = _device(ctx, device)
+    d = (stack if torch.is_tensor(stack) else torch.from_numpy(np.ascontiguousarray(stack))).to(dev).contiguous()
+    if is_bgr:
+        d = bgr_to_gray(ctx, d)
+    n, h, w = d.shape
+    nx, ny = int(board_size[0]), int(board_size[1])
+    if nx == ny or nx < 2 or ny < 2 or nx * ny > max_candidates:
+        raise ValueError("board_size: (nx, ny) with nx != ny, both at least 2, nx * ny <= max_candidates")
+    run = ChessCorners(ctx, n, w, h, max_candidates, dev)
+    run.run(d)
+    cands = run.candidates()
+    lib = load_library()
+    found, starts = np.zeros(n, bool), []
+    for i, c in enumerate(cands):
+        if len(c) < nx * ny:
+            continue
+        pts = np.ascontiguousarray(np.stack([c["x"][:nx * ny], c["y"][:nx * ny]], 1), dtype=np.float64)
+        out = np.zeros_like(pts)
+        ok = C.c_int(0)
+        if lib.gms_order_chessboard(pts.ctypes.data, nx, ny, C.byref(ok), out.ctypes.data) != 0:
+            raise ValueError("gms_order_chessboard: bad argument")
+        if ok.value:
+            found[i] = True
+            starts.append(out)
+    r = {"found": found, "successes": int(found.sum()), "candidates": cands, "image_points": np.zeros((0, nx * ny, 2)), "object_points": [],
+         "K": None, "dist": None, "rvecs": None, "tvecs": None, "rms": None, "camera": None}
+    if not starts:
+        return r
+    image_of = np.repeat(np.nonzero(found)[0], nx * ny)
+    refined, status = corner_subpix_images(ctx, d, image_of, np.concatenate(starts))
+    r["image_points"], r["subpix_status"] = refined.reshape(-1, nx * ny, 2), status.reshape(-1, nx * ny)
+    r["object_points"] = [chessboardObjectPoints((nx, ny))] * len(starts)
+    r["rms"], r["K"], r["dist"], r["rvecs"], r["tvecs"] = calibrateCamera(r["object_points"], list(r["image_points"]), (w, h))
+    r["camera"] = (float(r["K"][0, 0]), float(r["K"][1, 1]), float(r["K"][0, 2]), float(r["K"][1, 2]))
+    return r
+
+
 def dictionary_training_options(train_dictionary):
     """run_dataset's train_dictionary= as a full dict: True, or a dict with any of rows ("first": frame 0's descriptors, as the
     reference trains on desc1; "all": every frame's, as one set), n_words, attempts, max_iters, seed."""

@@ -121,3 +121,8 @@ def make_camera(camera, dist=None):
     if dist is not None:
         c["k1"], c["k2"], c["p1"], c["p2"], c["k3"] = dist
     return c
+
+
+# gms_chess_candidate (include/gms.h): a chessboard corner candidate
+CHESS_CANDIDATE_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("response", "<u4")])
+assert CHESS_CANDIDATE_DTYPE.itemsize == 12
