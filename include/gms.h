@@ -475,7 +475,8 @@ int gms_pyramid_build_device(gms_ctx* ctx, const uint8_t* d_images, int n_images
  * calls make rows of that structure and format at the detector's keypoints: 4 x 4 cells x 8 orientations of weighted gradient
  * magnitude on the keypoint's own pyramid level, in the frame of its direction, normalised, clipped at 0.2, normalised again and
  * scaled by 512: 128 fp32 values per keypoint, each an integer 0..255 -- what gms_bf_prepare_device(GMS_DESC_L2_F32X128) sends to its
- * exact int8 path. NOT cv::SIFT: this library's own definition in integer arithmetic (no DoG detector, no equality with OpenCV's rows),
+ * exact int8 path. NOT cv::SIFT: this library's own definition in integer arithmetic (no equality with OpenCV's rows; the DoG detector for them is
+ * gms_detect_dog_batch_device below),
  * so the rows are the same bytes on every run and equal the CPU statement.
  *
  * gms_detect_pyramid_grad_batch_device: gms_detect_pyramid_batch_device with one output more. Keypoints, 32-byte rows, counts and level
@@ -492,6 +493,30 @@ int gms_detect_pyramid_grad_batch_device(gms_ctx* ctx, const uint8_t* d_images, 
  * pixel grid or inside the border sets *d_status = 1 and keeps its row. Workspace: gms_detect_workspace_bytes(width, height, 1, 0). */
 int gms_describe_grad_device(gms_ctx* ctx, const uint8_t* d_image, int width, int height, gms_keypoint* d_keypoints, int n,
                              void* d_workspace, size_t workspace_bytes, float* d_rows128, int32_t* d_status);
+
+/* ---- difference-of-Gaussians (DoG) detector on the pyramid (CPU statement tests/dog_ref.py) ----------------
+ * The reference's keypoints are SIFT's: DoG blobs (FeatureMatchUtil.cpp:9-12, DisparityUtil.cpp:101-120,232). This call puts a DoG
+ * detector in the place of the FAST-9 corner detector of gms_detect_pyramid_(grad_)batch_device: a corner is found on every level on
+ * which it still is a corner, a DoG extremum picks the level on which the structure has its size -- the `size` that matchGMS(withScale)
+ * and LOGOS read. On every pyramid level: four integer Gaussian blurs (sigma 1.217 .. 2.103, taps that sum to 4096), three layers
+ * D_k = B_{k+1} - B_k in 1/256 grey level, a candidate where |D_1| > contrast, D_1 is strictly above or strictly below its 26 neighbours
+ * and the Hessian of D_1 passes SIFT's edge test (r = 10); score = clamp(|D_1| >> 4, 1, 255). Selection (strongest q_l per level, equal
+ * scores in raster order), records (pt in level-0 coordinates, size = 31 f, octave = level, angle = the centroid direction, response =
+ * score), 32-byte rows and 128-float rows are those of the calls above, unchanged. All integer: the same bytes on every run, equal to
+ * the CPU statement. NOT cv::SIFT: no sub-pixel or sub-scale refinement; one layer per level, so a blob is usually reported on two
+ * neighbouring levels; the direction is the intensity centroid's, not a gradient histogram's.
+ *
+ * contrast in [0, GMS_DOG_MAX_CONTRAST], in 1/256 grey level (128 = half a grey level). d_rows128 may be NULL (no 128-float rows; else
+ * 8-byte aligned). Everything else -- outputs, stream rule (nothing allocated, nothing waited for: can be captured), errors -- as
+ * gms_detect_pyramid_grad_batch_device. */
+#define GMS_DOG_MAX_CONTRAST 65535
+size_t gms_detect_dog_workspace_bytes(int width, int height, int n_images, int max_keypoints, int n_levels);   /* 0: bad arguments */
+int gms_detect_dog_batch_device(gms_ctx* ctx, const uint8_t* d_images, int n_images, int width, int height, int contrast, int max_keypoints,
+                                int n_levels, void* d_workspace, size_t workspace_bytes, gms_keypoint* d_keypoints, uint8_t* d_descriptors,
+                                int32_t* d_counts, int32_t* d_level_counts, float* d_rows128 /* may be NULL */);
+/* The candidate planes alone, single level: d_cand[n_images][height][width] = the score (1..255) where the image has a DoG candidate,
+ * else 0 -- before any selection. */
+int gms_dog_candidates_device(gms_ctx* ctx, const uint8_t* d_images, int n_images, int width, int height, int contrast, uint8_t* d_cand);
 
 /* ---- from photographs to the tables ---------------------------------------------------------------------
  * The reference hands BGR Mats to every entry point (main.cpp:21-75) and gets one keypoint vector per image back from

@@ -253,20 +253,29 @@ def detect_images(ctx, images, threshold=20, max_keypoints=10000, device=None):
 
 
 DESCRIPTORS = ("brief", "grad", "both")
+DETECTORS = ("fast", "dog")
 
 
 class DetectPyramid:
     """Device buffers of one gms_detect_pyramid_batch_device batch (n images of w x h), sized once, so that run() can be repeated or
     captured into a graph: workspace, keypoints, rows, counts and per-level counts. descriptor: "brief" (the 32-byte rows), "grad" or
-    "both" (gms_detect_pyramid_grad_batch_device: the 128-float gradient rows as well, in d_rows128)."""
+    "both" (gms_detect_pyramid_grad_batch_device: the 128-float gradient rows as well, in d_rows128). detector: "fast" (the FAST-9
+    corners of those two calls; `contrast` is not read) or "dog" (gms_detect_dog_batch_device: difference-of-Gaussians blobs with
+    |D| > contrast, in 1/256 grey level; `threshold` is not read). Everything behind the candidates is the same for both."""
 
-    def __init__(self, ctx, n, w, h, threshold=20, max_keypoints=10000, n_levels=8, device=None, descriptor="brief"):
+    def __init__(self, ctx, n, w, h, threshold=20, max_keypoints=10000, n_levels=8, device=None, descriptor="brief", detector="fast",
+                 contrast=128):
         if descriptor not in DESCRIPTORS:
             raise ValueError(f"descriptor must be one of {DESCRIPTORS}")
-        self.ctx, self.n, self.w, self.h, self.descriptor = ctx, int(n), int(w), int(h), descriptor
-        self.threshold, self.max_keypoints, self.n_levels = int(threshold), int(max_keypoints), int(n_levels)
+        if detector not in DETECTORS:
+            raise ValueError(f"detector must be one of {DETECTORS}")
+        self.ctx, self.n, self.w, self.h, self.descriptor, self.detector = ctx, int(n), int(w), int(h), descriptor, detector
+        self.threshold, self.max_keypoints, self.n_levels, self.contrast = int(threshold), int(max_keypoints), int(n_levels), int(contrast)
         dev = _device(ctx, device)
-        size = ctx.detect_pyramid_workspace_bytes if descriptor == "brief" else ctx.detect_pyramid_grad_workspace_bytes
+        if detector == "dog":
+            size = ctx.detect_dog_workspace_bytes
+        else:
+            size = ctx.detect_pyramid_workspace_bytes if descriptor == "brief" else ctx.detect_pyramid_grad_workspace_bytes
         self.ws_bytes = size(w, h, n, max_keypoints, n_levels)
         if self.ws_bytes == 0:
             raise ValueError("bad image size, keypoint count or number of levels")
@@ -280,9 +289,12 @@ class DetectPyramid:
 
     def run(self, d_images):
         """Stream-ordered on the context's stream; d_images: uint8 device tensor [n, h, w], contiguous."""
-        args = (d_images.data_ptr(), self.n, self.w, self.h, self.threshold, self.max_keypoints, self.n_levels, self.d_ws.data_ptr(), self.ws_bytes,
+        strength = self.contrast if self.detector == "dog" else self.threshold
+        args = (d_images.data_ptr(), self.n, self.w, self.h, strength, self.max_keypoints, self.n_levels, self.d_ws.data_ptr(), self.ws_bytes,
                 self.d_kp.data_ptr(), self.d_desc.data_ptr(), self.d_counts.data_ptr(), self.d_level_counts.data_ptr())
-        if self.d_rows128 is None:
+        if self.detector == "dog":
+            self.ctx.detect_dog_batch_device(*args, None if self.d_rows128 is None else self.d_rows128.data_ptr())
+        elif self.d_rows128 is None:
             self.ctx.detect_pyramid_batch_device(*args)
         else:
             self.ctx.detect_pyramid_grad_batch_device(*args, self.d_rows128.data_ptr())
@@ -299,18 +311,32 @@ class DetectPyramid:
         return (kps, rows128, level_counts) if self.descriptor == "grad" else (kps, rows32, rows128, level_counts)
 
 
-def detect_images_pyramid(ctx, images, threshold=20, max_keypoints=10000, n_levels=8, device=None, descriptor="brief"):
+def detect_images_pyramid(ctx, images, threshold=20, max_keypoints=10000, n_levels=8, device=None, descriptor="brief", detector="fast",
+                          contrast=128):
     """gms_detect_pyramid_batch_device on a stack of equally sized 8-bit grey images [n, H, W]: the detector of detect_images on every
     level of an image pyramid (ratio about 1.2). Returns (keypoints_per_image, rows_per_image, level_counts [n, n_levels]) as host
     arrays: KEYPOINT_DTYPE records in level-0 pixel coordinates with size and octave, level 0 first, raster order inside a level.
     descriptor="grad": rows_per_image are the float32 [n_i, 128] gradient rows (for GMS_DESC_L2_F32X128); "both": (keypoints, 32-byte
-    rows, 128-float rows, level_counts)."""
+    rows, 128-float rows, level_counts). detector="dog": the keypoints are difference-of-Gaussians blobs (gms_detect_dog_batch_device,
+    `contrast` in 1/256 grey level in the place of `threshold`); the outputs have the same form."""
     dev, imgs = _image_stack(ctx, images, device)
     n, h, w = imgs.shape
-    run = DetectPyramid(ctx, n, w, h, threshold, max_keypoints, n_levels, dev, descriptor)
+    run = DetectPyramid(ctx, n, w, h, threshold, max_keypoints, n_levels, dev, descriptor, detector, contrast)
     run.run(imgs)
     ctx.synchronize()
     return run.results()
+
+
+def dog_candidates(ctx, images, contrast=128, device=None):
+    """gms_dog_candidates_device on a stack of equally sized 8-bit grey images [n, H, W]: the DoG detector's candidate planes on the
+    images themselves (one level, before any selection) as a host array uint8 [n, H, W] -- the score 1..255 at a candidate, else 0."""
+    dev, imgs = _image_stack(ctx, images, device)
+    n, h, w = imgs.shape
+    d_cand = torch.zeros((n, h, w), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+    ctx.dog_candidates_device(imgs.data_ptr(), n, w, h, contrast, d_cand.data_ptr())
+    ctx.synchronize()
+    return d_cand.cpu().numpy()
 
 
 def bgr_to_gray(ctx, d_bgr):

@@ -28,6 +28,7 @@
 //   pyr_resize_kernel    a level from the level below it: integer bilinear, source rows through LDS, 4-byte loads and stores.
 //   det_describe_kernel  in its per-level form: records behind the earlier levels', pt mapped to level 0, size and octave set.
 //   (with d_rows128: grad_desc_kernels.hip's kernel behind every level's describe kernel -- DESIGN.md section 4.7c)
+//   (with dog_contrast >= 0: dog_kernels.hip's dog_maps_kernel in the place of det_maps_kernel + det_nms_kernel -- DESIGN.md section 4.7d)
 //   pyr_clear_kernel     zeroes the levels' counts and histograms; pyr_counts_kernel: the per-image and per-level counts for the caller.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -484,9 +485,10 @@ DetWs carve(void* ws, int w, int h, int n_images, int max_keypoints)
 }
 
 // the detector on one set of equally sized images: the single-scale call (lo == nullptr; clears its histogram itself) or one level of the
-// pyramid (lo and the level's histogram, already cleared)
+// pyramid (lo and the level's histogram, already cleared). dog_contrast >= 0: the candidates are the DoG detector's (dog_kernels.hip,
+// DESIGN.md section 4.7d) and `threshold` is not read; what follows the candidate plane is the same.
 hipError_t detect_level(const uint8_t* d_images, int n_images, int w, int h, int threshold, int max_keypoints, void* d_ws, gms_keypoint* d_kp,
-                        uint8_t* d_desc, int32_t* d_counts, const LevelOut* lo, uint32_t* level_hist, hipStream_t stream)
+                        uint8_t* d_desc, int32_t* d_counts, const LevelOut* lo, uint32_t* level_hist, hipStream_t stream, int dog_contrast = -1)
 {
     DetWs ws = carve(d_ws, w, h, n_images, max_keypoints);
     if (level_hist != nullptr) {
@@ -495,9 +497,14 @@ hipError_t detect_level(const uint8_t* d_images, int n_images, int w, int h, int
         hipError_t e = hipMemsetAsync(ws.hist, 0, ws.hist_bytes, stream);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(det_maps_kernel, dim3((w + kTileW - 1) / kTileW, (h + kTileH - 1) / kTileH, n_images), dim3(256), 0, stream, d_images, w, h,
-                       ws.score, ws.box);
-    hipLaunchKernelGGL(det_nms_kernel, dim3((w + 63) / 64, (h + 3) / 4, n_images), dim3(256), 0, stream, ws.score, w, h, threshold, ws.cand, ws.hist);
+    if (dog_contrast >= 0) {
+        hipError_t e = launch_dog_maps(d_images, n_images, w, h, dog_contrast, ws.cand, ws.box, ws.hist, stream);
+        if (e != hipSuccess) return e;
+    } else {
+        hipLaunchKernelGGL(det_maps_kernel, dim3((w + kTileW - 1) / kTileW, (h + kTileH - 1) / kTileH, n_images), dim3(256), 0, stream, d_images, w, h,
+                           ws.score, ws.box);
+        hipLaunchKernelGGL(det_nms_kernel, dim3((w + 63) / 64, (h + 3) / 4, n_images), dim3(256), 0, stream, ws.score, w, h, threshold, ws.cand, ws.hist);
+    }
     hipLaunchKernelGGL(det_cut_kernel, dim3(n_images), dim3(256), 0, stream, ws.hist, max_keypoints, ws.cut, d_counts);
     hipLaunchKernelGGL(det_rows_kernel, dim3(h, n_images), dim3(64), 0, stream, ws.cand, w, h, ws.cut, ws.rows);
     hipLaunchKernelGGL(det_scan_kernel, dim3(n_images), dim3(1024), 0, stream, ws.rows, h);
@@ -585,7 +592,8 @@ size_t detect_pyramid_workspace_bytes(int w, int h, int n_images, int max_keypoi
 }
 
 hipError_t launch_detect_pyramid(const uint8_t* d_images, int n_images, int w, int h, int threshold, int max_keypoints, int n_levels, void* d_ws,
-                                 gms_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, int32_t* d_level_counts, hipStream_t stream, float* d_rows128)
+                                 gms_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, int32_t* d_level_counts, hipStream_t stream, float* d_rows128,
+                                 int dog_contrast)
 {
     if (n_images <= 0) return hipSuccess;
     int ww[kPyramidMaxLevels], hh[kPyramidMaxLevels], quota[kPyramidMaxLevels];
@@ -606,7 +614,7 @@ hipError_t launch_detect_pyramid(const uint8_t* d_images, int n_images, int w, i
         if (quota[l] > 0) {
             const LevelOut lo = {lvl_counts, l, n_images, max_keypoints, (float)w / (float)ww[l], (float)h / (float)hh[l]};
             e = detect_level(img, n_images, ww[l], hh[l], threshold, quota[l], det_ws, d_kp, d_desc, lvl_counts + (size_t)l * n_images, &lo,
-                             hists + (size_t)l * n_images * 256, stream);
+                             hists + (size_t)l * n_images * 256, stream, dog_contrast);
             if (e != hipSuccess) return e;
             if (d_rows128 != nullptr) {   // while the level's box sums and list are still in the workspace
                 e = launch_grad_level(n_images, ww[l], hh[l], quota[l], det_ws, lvl_counts, l, max_keypoints, d_kp, d_rows128, stream);

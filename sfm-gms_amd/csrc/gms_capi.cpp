@@ -1775,6 +1775,38 @@ int gms_describe_grad_device(gms_ctx* c, const uint8_t* d_image, int width, int 
     return on_ctx(c, [&] { return gms::launch_describe_grad(d_image, width, height, d_keypoints, n, d_workspace, d_rows128, d_status, c->stream); });
 }
 
+// ---- difference-of-Gaussians detector (dog_kernels.hip) ---------------------------------------------------------------------------
+size_t gms_detect_dog_workspace_bytes(int width, int height, int n_images, int max_keypoints, int n_levels)
+{
+    if (!detect_image_ok(width, height)) return 0;
+    return gms::detect_pyramid_grad_workspace_bytes(width, height, n_images, max_keypoints, n_levels);   // the kernel is fused: no region of its own
+}
+
+int gms_detect_dog_batch_device(gms_ctx* c, const uint8_t* d_images, int n_images, int width, int height, int contrast, int max_keypoints,
+                                int n_levels, void* d_workspace, size_t workspace_bytes, gms_keypoint* d_keypoints, uint8_t* d_descriptors,
+                                int32_t* d_counts, int32_t* d_level_counts, float* d_rows128)
+{
+    if (!c || n_images < 0 || max_keypoints < 0 || contrast < 0 || contrast > GMS_DOG_MAX_CONTRAST || !detect_image_ok(width, height)) return GMS_ERR_BAD_ARG;
+    if (n_levels < 1 || n_levels > GMS_PYRAMID_MAX_LEVELS) return GMS_ERR_BAD_ARG;
+    if (n_images == 0) return GMS_OK;
+    if (!d_images || !d_workspace || !d_counts || !d_level_counts) return GMS_ERR_BAD_ARG;
+    if (max_keypoints > 0 && (!d_keypoints || !d_descriptors)) return GMS_ERR_BAD_ARG;
+    if (d_rows128 && reinterpret_cast<uintptr_t>(d_rows128) % 8 != 0) return GMS_ERR_BAD_ARG;
+    if (workspace_bytes < gms_detect_dog_workspace_bytes(width, height, n_images, max_keypoints, n_levels)) return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] {
+        return gms::launch_detect_pyramid(d_images, n_images, width, height, 0, max_keypoints, n_levels, d_workspace, d_keypoints, d_descriptors,
+                                          d_counts, d_level_counts, c->stream, max_keypoints > 0 ? d_rows128 : nullptr, contrast);
+    });
+}
+
+int gms_dog_candidates_device(gms_ctx* c, const uint8_t* d_images, int n_images, int width, int height, int contrast, uint8_t* d_cand)
+{
+    if (!c || n_images < 0 || contrast < 0 || contrast > GMS_DOG_MAX_CONTRAST || !detect_image_ok(width, height)) return GMS_ERR_BAD_ARG;
+    if (n_images == 0) return GMS_OK;
+    if (!d_images || !d_cand) return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] { return gms::launch_dog_maps(d_images, n_images, width, height, contrast, d_cand, nullptr, nullptr, c->stream); });
+}
+
 // ---- from photographs to the tables (ingest_kernels.hip) ----------------------------------------------------------------------------
 int gms_bgr_to_gray_device(gms_ctx* c, const uint8_t* d_bgr, int n_images, int width, int height, uint8_t* d_gray)
 {

@@ -1,0 +1,294 @@
+"""-m gpu: the difference-of-Gaussians detector (gms_detect_dog_batch_device / gms_dog_candidates_device) against
+its numpy statement tests/dog_ref.py, byte for byte: candidate planes on every pixel, the whole call (keypoints, 32-byte rows, 128-float
+rows, counts, level counts), the descriptor kinds against each other, detector="fast" against the call without the argument, captured
+into a graph, in front of the pipeline, and how many exact nearest neighbours are right on a photograph and its 0.6 x copy against the
+FAST source's count."""
+import functools
+import importlib
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import dog_ref  # noqa: E402
+import grad_desc_ref  # noqa: E402
+import pyramid_ref  # noqa: E402
+from test_dog_ref import small_images  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
+STEREO = os.path.join(GOLDEN, "image_stereo_pair_450x375.npz")
+MAIN = os.path.join(GOLDEN, "image_main_scenario_1080p.npz")
+SIZES = [(33, 33), (97, 65), (64, 48), (130, 200), (641, 479), (1030, 50)]     # (width, height)
+CONTRASTS = (0, 128, 2000, 65535)
+
+
+def _batch():
+    return importlib.import_module("sfm-gms_amd.batch")
+
+
+@functools.lru_cache(maxsize=None)
+def _stereo():
+    z = np.load(STEREO)
+    return np.stack([z["left"], z["right"]])
+
+
+def _images(key):
+    return _stereo() if key == "stereo" else small_images(*key)
+
+
+@functools.lru_cache(maxsize=None)
+def _planes(key, contrast):
+    """The statement's candidate planes of all 16 levels per image of a batch: what the parameter sets of one contrast share."""
+    return [dog_ref.level_candidates(img, contrast, 16) for img in _images(key)]
+
+
+@functools.lru_cache(maxsize=None)
+def _want(key, contrast, max_kp, n_levels):
+    """The statement's output per image of a batch, computed once: key = "stereo" or a (width, height) of small_images."""
+    import gms_oracle
+    gms_oracle.load()
+    return [dog_ref.detect(gms_oracle, img, contrast, max_kp, n_levels, planes) for img, planes in zip(_images(key), _planes(key, contrast))]
+
+
+# ---- candidate planes, every pixel -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("w,h", SIZES)
+def test_candidate_planes_on_every_pixel(ctx, w, h):
+    """Five images per size (noise, 4 x 4 blocks of 60 / 150 and of 20 / 220, sparse dots, flat) at four contrasts. (33, 33) has one legal
+    pixel, (97, 65) a region that crosses a 64-wide tile edge, (1030, 50) is one tile row and a part of a second high, (641, 479) and
+    (130, 200) are no multiple of the tile in either direction."""
+    imgs = small_images(w, h)
+    want = {c: np.stack([dog_ref.candidates(img, c) for img in imgs]) for c in CONTRASTS}
+    # what the statement alone must show, so that equal planes mean something
+    n = {c: [int(np.count_nonzero(p)) for p in want[c]] for c in CONTRASTS}
+    assert sum(n[65535]) == 0 and all(n[c][4] == 0 for c in CONTRASTS)             # contrast 65535; the flat image
+    if (w, h) == (33, 33):
+        assert sum(sum(v) for v in n.values()) == 0
+    if w >= 97 and h >= 50:                                                         # (97, 65) and larger
+        assert all(n[c][i] > 0 for c in (0, 128) for i in (0, 1, 2)), n
+        assert (want[128][2] == 255).any()                                          # the 20 / 220 blocks saturate the score
+    print(f"\n{w} x {h}: candidates per image at contrast 0 {n[0]}, 128 {n[128]}, 2000 {n[2000]}; scores of 255 in the 20 / 220 blocks: "
+          f"{int((want[128][2] == 255).sum())}")
+    for c in CONTRASTS:
+        got = _batch().dog_candidates(ctx, imgs, c)
+        assert got.dtype == np.uint8 and got.shape == want[c].shape
+        bad = np.argwhere(got != want[c])
+        assert len(bad) == 0, f"contrast {c}: {len(bad)} wrong pixels, the first (image, y, x) = {bad[0].tolist()}: " \
+                              f"got {got[tuple(bad[0])]}, want {want[c][tuple(bad[0])]}"
+
+
+# ---- the whole call ----------------------------------------------------------------------------------------------------------------------
+def _check(ctx, imgs, want, contrast, max_kp, n_levels):
+    """"both", "grad" and "brief" against the statement and against each other."""
+    batch = _batch()
+    kw = dict(detector="dog", contrast=contrast)
+    kps, rows32, rows128, lc = batch.detect_images_pyramid(ctx, imgs, 20, max_kp, n_levels, descriptor="both", **kw)
+    g_kps, g_rows128, g_lc = batch.detect_images_pyramid(ctx, imgs, 250, max_kp, n_levels, descriptor="grad", **kw)      # (threshold is not read)
+    b_kps, b_rows32, b_lc = batch.detect_images_pyramid(ctx, imgs, 0, max_kp, n_levels, descriptor="brief", **kw)
+    assert lc.tobytes() == g_lc.tobytes() == b_lc.tobytes() and lc.shape == (len(imgs), n_levels)
+    for i in range(len(imgs)):
+        want_kp, want_rows32, want_lc, want_rows128 = want[i]
+        assert lc[i].tolist() == want_lc.tolist(), i
+        assert len(kps[i]) == len(want_kp) == want_lc.sum()
+        assert kps[i].tobytes() == want_kp.tobytes() == g_kps[i].tobytes() == b_kps[i].tobytes(), i
+        assert rows32[i].tobytes() == want_rows32.tobytes() == b_rows32[i].tobytes(), i
+        assert rows128[i].dtype == np.float32 and rows128[i].shape == (len(want_kp), 128)
+        assert rows128[i].tobytes() == want_rows128.tobytes() == g_rows128[i].tobytes(), i
+    return kps, lc
+
+
+@pytest.mark.parametrize("contrast,max_kp,n_levels", [(128, 10000, 8), (128, 700, 8), (0, 4000, 5), (128, 5, 8), (128, 1, 8), (512, 300, 1),
+                                                      (128, 2500, 16)])
+def test_stereo_pair_equals_statement(ctx, contrast, max_kp, n_levels):
+    imgs = _stereo()
+    want = _want("stereo", contrast, max_kp, n_levels)
+    kps, lc = _check(ctx, imgs, want, contrast, max_kp, n_levels)
+    if (contrast, max_kp, n_levels) == (128, 10000, 8):
+        assert (lc > 0).all() and len(kps[0]) > 1000               # every level reports blobs; nothing is cut
+    if (contrast, max_kp, n_levels) == (128, 700, 8):              # the quotas cut, and at least one cut falls inside a run of equal scores
+        levels = pyramid_ref.build(imgs[0], n_levels)
+        quotas = pyramid_ref.quotas([(l.shape[1], l.shape[0]) for l in levels], max_kp)
+        assert any(dog_ref.cut_has_tie(dog_ref.candidates(l, contrast), q) for l, q in zip(levels, quotas))
+        assert lc[0].tolist() == quotas
+    if n_levels == 16:
+        assert (lc[:, len(pyramid_ref.level_sizes(450, 375, 16)):] == 0).all()
+
+
+@pytest.mark.parametrize("w,h", SIZES)
+def test_odd_sizes_five_images(ctx, w, h):
+    """max_keypoints of 1, 5 and 37 put the counts on and off multiples of the four keypoints of a describe workgroup; the flat image
+    has no keypoint."""
+    imgs = small_images(w, h)
+    for contrast, max_kp, n_levels in ((128, 37, 8), (0, 5, 16), (128, 1, 2)):
+        kps, _ = _check(ctx, imgs, _want((w, h), contrast, max_kp, n_levels), contrast, max_kp, n_levels)
+        assert len(kps[4]) == 0 and (w < 97 or len(kps[1]) > 0)
+
+
+def test_one_1080p_image_equals_statement(ctx, oracle):
+    left = np.load(MAIN)["left"]
+    want = dog_ref.detect(oracle, left, 128, 4000, 8)
+    kps, lc = _check(ctx, left[None], [want], 128, 4000, 8)
+    assert len(kps[0]) == 4000 and (lc > 0).all()
+
+
+def test_fast_is_the_call_without_the_argument(ctx):
+    batch = _batch()
+    imgs = _stereo()
+    base = batch.detect_images_pyramid(ctx, imgs, 12, 900, 8, descriptor="both")
+    fast = batch.detect_images_pyramid(ctx, imgs, 12, 900, 8, descriptor="both", detector="fast", contrast=7)       # (contrast is not read)
+    dog = batch.detect_images_pyramid(ctx, imgs, 12, 900, 8, descriptor="both", detector="dog")
+    for a, b in zip(base[:3], fast[:3]):
+        assert all(x.tobytes() == y.tobytes() for x, y in zip(a, b))
+    assert base[3].tobytes() == fast[3].tobytes()
+    assert dog[0][0].tobytes() != base[0][0].tobytes()                                                                # another point set
+
+
+def test_graph_replay_on_new_pixels(ctx):
+    import torch
+    batch = _batch()
+    first = _stereo()
+    second = np.stack([first[1][::-1].copy(), first[0][:, ::-1].copy()])
+    import gms_oracle
+    gms_oracle.load()
+    want = {0: _want("stereo", 128, 600, 8), 1: [dog_ref.detect(gms_oracle, img, 128, 600, 8) for img in second]}
+    h, w = first[0].shape
+    d_imgs = torch.from_numpy(first).cuda()
+    run = batch.DetectPyramid(ctx, 2, w, h, 20, 600, 8, descriptor="both", detector="dog", contrast=128)
+    stream = torch.cuda.Stream()
+    ctx.set_stream(stream.cuda_stream)
+    g = torch.cuda.CUDAGraph()
+    try:
+        with torch.cuda.stream(stream):
+            run.run(d_imgs)                                   # warm-up
+        stream.synchronize()
+        with torch.cuda.graph(g, stream=stream):
+            run.run(d_imgs)
+        for which, imgs in ((1, second), (0, first)):
+            d_imgs.copy_(torch.from_numpy(imgs))
+            for t in (run.d_kp, run.d_desc, run.d_counts, run.d_level_counts, run.d_rows128):
+                t.zero_()
+            torch.cuda.synchronize()
+            g.replay()
+            torch.cuda.synchronize()
+            kps, rows32, rows128, lc = run.results()
+            for i in range(2):
+                want_kp, want_rows32, want_lc, want_rows128 = want[which][i]
+                assert kps[i].tobytes() == want_kp.tobytes() and rows32[i].tobytes() == want_rows32.tobytes()
+                assert lc[i].tolist() == want_lc.tolist() and rows128[i].tobytes() == want_rows128.tobytes() and rows128[i].any()
+    finally:
+        ctx.set_stream(None)
+        torch.cuda.synchronize()
+        g.reset()
+
+
+def test_argument_checks(ctx, pkg):
+    import torch
+    d = torch.zeros(1 << 22, dtype=torch.uint8, device="cuda:0")
+    p = d.data_ptr()
+    nb = ctx.detect_dog_workspace_bytes(100, 100, 1, 10, 8)
+    assert 0 < nb <= 1 << 22 and nb == ctx.detect_pyramid_grad_workspace_bytes(100, 100, 1, 10, 8)        # the kernel is fused: no region of its own
+    out = [torch.zeros(1024, dtype=torch.uint8, device="cuda:0") for _ in range(4)]     # keypoints, rows, counts, level counts
+    rows128 = torch.zeros(10 * 128, dtype=torch.float32, device="cuda:0")
+    img = torch.zeros(100 * 100, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    outs = [t.data_ptr() for t in out]
+    ctx.detect_dog_batch_device(img.data_ptr(), 1, 100, 100, 128, 10, 8, p, nb, *outs, rows128.data_ptr())   # exactly enough
+    ctx.detect_dog_batch_device(img.data_ptr(), 1, 100, 100, 128, 10, 8, p, nb, *outs, None)                 # no 128-float rows
+    ctx.synchronize()
+    with pytest.raises(pkg.GmsError):
+        ctx.detect_dog_batch_device(p, 1, 100, 100, 128, 10, 8, p, nb - 1, p, p, p, p, p)           # workspace one byte short
+    for n_levels in (0, 17):
+        with pytest.raises(pkg.GmsError):
+            ctx.detect_dog_batch_device(p, 1, 100, 100, 128, 10, n_levels, p, 1 << 22, p, p, p, p, p)
+        assert ctx.detect_dog_workspace_bytes(100, 100, 1, 10, n_levels) == 0
+    for contrast in (-1, 65536):
+        with pytest.raises(pkg.GmsError):
+            ctx.detect_dog_batch_device(p, 1, 100, 100, contrast, 10, 8, p, 1 << 22, p, p, p, p, p)
+        with pytest.raises(pkg.GmsError):
+            ctx.dog_candidates_device(p, 1, 100, 100, contrast, p)
+    for contrast in (0, 65535):
+        ctx.detect_dog_batch_device(img.data_ptr(), 1, 100, 100, contrast, 10, 8, p, nb, *outs, rows128.data_ptr())
+    ctx.synchronize()
+    for bad in range(4):                                                                             # each required output NULL in turn
+        ptrs = [p] * 5
+        ptrs[bad] = None
+        with pytest.raises(pkg.GmsError):
+            ctx.detect_dog_batch_device(p, 1, 100, 100, 128, 10, 8, p, 1 << 22, *ptrs)
+    with pytest.raises(pkg.GmsError):
+        ctx.detect_dog_batch_device(None, 1, 100, 100, 128, 10, 8, p, 1 << 22, p, p, p, p, p)       # no images
+    with pytest.raises(pkg.GmsError):
+        ctx.detect_dog_batch_device(p, 1, 100, 100, 128, 10, 8, None, 1 << 22, p, p, p, p, p)       # no workspace
+    with pytest.raises(pkg.GmsError):
+        ctx.detect_dog_batch_device(p, 1, 100, 100, 128, 10, 8, p, 1 << 22, p, p, p, p, p + 4)      # rows not 8-byte aligned
+    with pytest.raises(pkg.GmsError):
+        ctx.detect_dog_batch_device(p, 1, 32, 100, 128, 10, 8, p, 1 << 22, p, p, p, p, p)           # no room for a keypoint
+    ctx.detect_dog_batch_device(p, 0, 100, 100, 128, 10, 8, None, 0, None, None, None, None, None)   # nothing to do
+    for args in ((None, 1, 100, 100, 128, p), (p, 1, 100, 100, 128, None), (p, 1, 100, 32, 128, p), (p, -1, 100, 100, 128, p)):
+        with pytest.raises(pkg.GmsError):
+            ctx.dog_candidates_device(*args)
+    ctx.dog_candidates_device(p, 0, 100, 100, 128, None)
+    with pytest.raises(ValueError):
+        _batch().DetectPyramid(ctx, 1, 100, 100, detector="sift")
+    with pytest.raises(ValueError):
+        _batch().detect_images_pyramid(ctx, np.zeros((1, 100, 100), np.uint8), detector="DoG")
+
+
+# ---- in front of the pipeline -----------------------------------------------------------------------------------------------------------
+def test_tables_and_run_images_on_the_stereo_pair(ctx, pkg, oracle):
+    import torch
+    batch = _batch()
+    types = importlib.import_module("sfm-gms_amd.types")
+    pipeline = importlib.import_module("sfm-gms_amd.pipeline")
+    imgs = _stereo()
+    want = _want("stereo", 128, 2500, 8)
+    want_kp, want_off = types.concat_frames([w[0] for w in want])
+    want_rows = np.concatenate([w[3] for w in want])
+    run = batch.DetectPyramid(ctx, 2, 450, 375, 20, 2500, 8, descriptor="grad", detector="dog", contrast=128)
+    run.run(torch.from_numpy(imgs).cuda())
+    d_kp, d_rows32, d_rows128, d_off = batch.pack_detector(run)                     # unchanged on a DoG run
+    frames, descs = batch.tables_from_detector(run, [(450, 375)] * 2)
+    ctx.synchronize()
+    assert d_off.cpu().numpy().tolist() == want_off.tolist() and d_kp.cpu().numpy()[: len(want_kp) * 28].tobytes() == want_kp.tobytes()
+    assert d_rows32.cpu().numpy()[: len(want_kp) * 32].tobytes() == np.concatenate([w[1] for w in want]).tobytes()
+    assert np.array_equal(frames.frame_off_host, want_off) and frames.total == len(want_kp) > 1000
+    assert frames.d_kp.cpu().numpy()[: frames.total * 28].tobytes() == want_kp.tobytes()
+    assert descs.d_desc.cpu().numpy()[: want_rows.nbytes].tobytes() == want_rows.tobytes()
+    got = pipeline.run_images(ctx, imgs, pairs=[(0, 1)], max_keypoints=2500, n_levels=8, descriptor="grad", method="gms", withRotation=True,
+                              withScale=True, detector="dog", contrast=128)
+    matches = oracle.bf_match(want[0][3], want[1][3], False)
+    rc, out, _, res = oracle.match((450, 375), (450, 375), want[0][0], want[1][0], matches, True, True, 6.0)
+    k = int(got["results"]["n_inliers"][0])
+    assert rc == 0 and got["matches"].tobytes() == matches.tobytes()
+    assert k == len(out) > 50 and got["out"][:k].tobytes() == out.tobytes() and got["results"][0].tobytes() == res.tobytes()
+
+
+# ---- quality ----------------------------------------------------------------------------------------------------------------------------
+def test_nearest_neighbours_on_a_shrunk_copy(ctx, oracle):
+    """The 1080p-against-0.6 x case of test_gpu_grad_desc.py::test_nearest_neighbours_on_a_shrunk_copy with detector="dog", contrast 128,
+    4000 keypoints: the exact L2 nearest neighbour of every left 128-float row among the right rows, correct within 3 pixels of where
+    the shrink puts the left keypoint. The DoG count must reach 0.8 of the FAST source's L2 count on the same pair, computed here in
+    the same way (the margin that test uses between row kinds). Measured from the statements on the CPU (the GPU's rows are those
+    bytes): DoG 4000 / 2435 keypoints, 1060 correct; FAST 1350 / 1214 keypoints, 979 correct."""
+    batch = _batch()
+    left = np.load(MAIN)["left"]
+    h, w = left.shape
+    wr, hr = 1152, 648
+    right = pyramid_ref.resize(left, wr, hr)
+    sx, sy = wr / w, hr / h
+
+    def count(**kw):
+        kps, rows = [], []
+        for img in (left, right):
+            k, r128, _ = batch.detect_images_pyramid(ctx, img, 20, 4000, 8, descriptor="grad", **kw)
+            kps.append(k[0]); rows.append(r128[0])
+        m = oracle.bf_match(rows[0], rows[1], False)
+        q, t = kps[0][m["queryIdx"]], kps[1][m["trainIdx"]]
+        ex, ey = (q["x"] + 0.5) * sx - 0.5, (q["y"] + 0.5) * sy - 0.5
+        return int((np.hypot(t["x"] - ex, t["y"] - ey) <= 3.0).sum()), [len(k) for k in kps]
+
+    n_dog, kp_dog = count(detector="dog", contrast=128)
+    n_fast, kp_fast = count()
+    print(f"\n0.6 x, correct L2 nearest neighbours: DoG {n_dog} of {kp_dog[0]} / {kp_dog[1]} keypoints, FAST {n_fast} of {kp_fast[0]} / {kp_fast[1]}")
+    assert n_fast > 0 and n_dog >= 0.8 * n_fast

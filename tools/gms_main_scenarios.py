@@ -3,7 +3,7 @@
 (pipeline.run_main_scenarios): the pair as it is, the right image turned (img_rotate) and the right image resized (cv::resize), each
 matched by bruteForceMatch and by matchGMS(withRotation, withScale).
 
-    python tools/gms_main_scenarios.py [pair.npz] [--resize 1000x1000] [--angle 180] [--keypoints 10000] [--threshold 20] [--check]
+    python tools/gms_main_scenarios.py [pair.npz] [--resize 1000x1000] [--angle 180] [--keypoints 10000] [--threshold 20] [--detector fast|dog] [--contrast 128] [--check]
 
 pair.npz holds `left` and `right`, equally sized [H, W] or [H, W, 3] (default: tests/golden/image_main_scenario_1080p.npz). Prints the
 scenario table, one JSON line per scenario and method. --check compares the transformed images with tests/warp_ref.py."""
@@ -27,6 +27,8 @@ def main():
     ap.add_argument("--angle", type=float, default=180.0)
     ap.add_argument("--keypoints", type=int, default=10000)
     ap.add_argument("--threshold", type=int, default=20)
+    ap.add_argument("--detector", choices=("fast", "dog"), default="fast")
+    ap.add_argument("--contrast", type=int, default=128)
     ap.add_argument("--check", action="store_true")
     a = ap.parse_args()
     z = np.load(a.pair)
@@ -36,7 +38,8 @@ def main():
     pipeline = importlib.import_module("sfm-gms_amd.pipeline")
     ctx = pkg.GmsContext(0)
     t0 = time.perf_counter()
-    r = pipeline.run_main_scenarios(ctx, left, right, resize_to=resize_to, angle=a.angle, threshold=a.threshold, max_keypoints=a.keypoints)
+    r = pipeline.run_main_scenarios(ctx, left, right, resize_to=resize_to, angle=a.angle, threshold=a.threshold, max_keypoints=a.keypoints,
+                                    detector=a.detector, contrast=a.contrast)
     ms = (time.perf_counter() - t0) * 1e3
     counts = np.diff(r["tables"][0].frame_off_host).tolist()
     for k, name in enumerate(pipeline.MAIN_SCENARIOS, start=1):
