@@ -503,7 +503,7 @@ int gms_describe_grad_device(gms_ctx* ctx, const uint8_t* d_image, int width, in
  * and the Hessian of D_1 passes SIFT's edge test (r = 10); score = clamp(|D_1| >> 4, 1, 255). Selection (strongest q_l per level, equal
  * scores in raster order), records (pt in level-0 coordinates, size = 31 f, octave = level, angle = the centroid direction, response =
  * score), 32-byte rows and 128-float rows are those of the calls above, unchanged. All integer: the same bytes on every run, equal to
- * the CPU statement. NOT cv::SIFT: no sub-pixel or sub-scale refinement; one layer per level, so a blob is usually reported on two
+ * the CPU statement. NOT cv::SIFT: no sub-pixel or sub-scale refinement (gms_detect_dog_refined_batch_device below has one step of it); one layer per level, so a blob is usually reported on two
  * neighbouring levels; the direction is the intensity centroid's, not a gradient histogram's.
  *
  * contrast in [0, GMS_DOG_MAX_CONTRAST], in 1/256 grey level (128 = half a grey level). d_rows128 may be NULL (no 128-float rows; else
@@ -517,6 +517,23 @@ int gms_detect_dog_batch_device(gms_ctx* ctx, const uint8_t* d_images, int n_ima
 /* The candidate planes alone, single level: d_cand[n_images][height][width] = the score (1..255) where the image has a DoG candidate,
  * else 0 -- before any selection. */
 int gms_dog_candidates_device(gms_ctx* ctx, const uint8_t* d_images, int n_images, int width, int height, int contrast, uint8_t* d_cand);
+
+/* The same detector with one refinement step (CPU statement tests/dog_refine_ref.py): after selection -- same
+ * candidates, same quotas, same order -- every keypoint is moved to 1/16 pixel of its level by the Newton step -H^-1 g on D_1 and to
+ * 1/16 layer by the parabola through D_0, D_1, D_2, all in int64 with floor divisions; an offset beyond half a pixel is clamped to
+ * it (SIFT re-centres and refits; this does not). With ox, oy, os the offsets in sixteenths (-8 .. 8), fx = width / level width:
+ *   x = ((x_level + ox / 16) + 0.5) * fx - 0.5, y likewise, size = (31 * fx) * 1.2^(os / 16) (17 fp32 constants),
+ * each operation rounded once in fp32. angle, response, octave, class_id, the 32-byte rows, the 128-float rows, counts and level
+ * counts are the bytes gms_detect_dog_batch_device writes; a keypoint whose three offsets are zero has that call's record.
+ * Arguments, checks, outputs and stream rule (nothing allocated, nothing waited for: can be captured) as gms_detect_dog_batch_device;
+ * the workspace is larger by one uint16 plane of offsets per image. */
+size_t gms_detect_dog_refined_workspace_bytes(int width, int height, int n_images, int max_keypoints, int n_levels);   /* 0: bad arguments */
+int gms_detect_dog_refined_batch_device(gms_ctx* ctx, const uint8_t* d_images, int n_images, int width, int height, int contrast,
+                                        int max_keypoints, int n_levels, void* d_workspace, size_t workspace_bytes, gms_keypoint* d_keypoints,
+                                        uint8_t* d_descriptors, int32_t* d_counts, int32_t* d_level_counts, float* d_rows128 /* may be NULL */);
+/* The offset planes alone, single level, the counterpart of gms_dog_candidates_device: d_codes[n_images][height][width] =
+ * 1 + (ox + 8) + 17 (oy + 8) + 289 (os + 8) where the image has a DoG candidate, else 0. */
+int gms_dog_offsets_device(gms_ctx* ctx, const uint8_t* d_images, int n_images, int width, int height, int contrast, uint16_t* d_codes);
 
 /* ---- from photographs to the tables ---------------------------------------------------------------------
  * The reference hands BGR Mats to every entry point (main.cpp:21-75) and gets one keypoint vector per image back from

@@ -309,6 +309,20 @@ class GmsContext:
         _check(self._lib.gms_dog_candidates_device(self._h, d_images, int(n_images), int(width), int(height), int(contrast), d_cand),
                self._lib, "gms_dog_candidates_device")
 
+    # -- ... with its keypoints refined to 1/16 pixel and 1/16 layer (batch.detect_images_pyramid(refine=True) / dog_offsets drive them) --
+    def detect_dog_refined_workspace_bytes(self, width, height, n_images, max_keypoints, n_levels):
+        return int(self._lib.gms_detect_dog_refined_workspace_bytes(int(width), int(height), int(n_images), int(max_keypoints), int(n_levels)))
+
+    def detect_dog_refined_batch_device(self, d_images, n_images, width, height, contrast, max_keypoints, n_levels, d_ws, ws_bytes, d_kp, d_desc,
+                                        d_counts, d_level_counts, d_rows128):
+        _check(self._lib.gms_detect_dog_refined_batch_device(self._h, d_images, int(n_images), int(width), int(height), int(contrast),
+                                                             int(max_keypoints), int(n_levels), d_ws, int(ws_bytes), d_kp, d_desc, d_counts,
+                                                             d_level_counts, d_rows128), self._lib, "gms_detect_dog_refined_batch_device")
+
+    def dog_offsets_device(self, d_images, n_images, width, height, contrast, d_codes):
+        _check(self._lib.gms_dog_offsets_device(self._h, d_images, int(n_images), int(width), int(height), int(contrast), d_codes),
+               self._lib, "gms_dog_offsets_device")
+
     # -- from photographs to the tables (gms_bgr_to_gray_device / gms_detect_pack_device; batch.tables_from_detector drives them) ---
     def bgr_to_gray_device(self, d_bgr, n_images, width, height, d_gray):
         _check(self._lib.gms_bgr_to_gray_device(self._h, d_bgr or None, int(n_images), int(width), int(height), d_gray or None), self._lib,
@@ -553,8 +567,9 @@ def structureFromMotion(img1, img2, camera, dist=None, method="logos", ctx=None,
             "gms"    algo 2, nearest neighbour then matchGMS(true, true) (FeatureMatchUtil.cpp:66-69)
             "logos"  algo 3, matchLOGOS on 50 visual words trained on image 1's rows (FeatureMatchUtil.cpp:101-102); what main.cpp:74 passes
     camera = (fx, fy, cx, cy), dist = (k1, k2, p1, p2, k3) or None. params: run_images' keywords (threshold, max_keypoints, n_levels,
-    detector, contrast, descriptor, thresholdFactor, prob, ransac_threshold, cross_check, distance_coef, max_size, dictionary, train_dictionary, ...).
-    The keypoints and rows are this library's own (detector="dog": 4.7d), not SIFT's.
+    detector, contrast, refine, descriptor, thresholdFactor, prob, ransac_threshold, cross_check, distance_coef, max_size, dictionary, train_dictionary, ...).
+    The keypoints and rows are this library's own (detector="dog", and refine=True
+    for its sub-pixel position and sub-level size: 4.7d), not SIFT's.
 
     Returns a dict: points3D float64 [k, 3] (the inliers' points, in their order), R [3, 3], t [3], E [3, 3], matches (the method's
     surviving DMATCH_DTYPE records), mask (uint8 per surviving match: 0 = not an inlier of the pose), keypoints1, keypoints2

@@ -261,19 +261,24 @@ class DetectPyramid:
     captured into a graph: workspace, keypoints, rows, counts and per-level counts. descriptor: "brief" (the 32-byte rows), "grad" or
     "both" (gms_detect_pyramid_grad_batch_device: the 128-float gradient rows as well, in d_rows128). detector: "fast" (the FAST-9
     corners of those two calls; `contrast` is not read) or "dog" (gms_detect_dog_batch_device: difference-of-Gaussians blobs with
-    |D| > contrast, in 1/256 grey level; `threshold` is not read). Everything behind the candidates is the same for both."""
+    |D| > contrast, in 1/256 grey level; `threshold` is not read). Everything behind the candidates is the same for both.
+    refine=True (detector "dog" only; gms_detect_dog_refined_batch_device): x, y and size of every record are refined to 1/16 pixel
+    and 1/16 layer; nothing else of the output changes."""
 
     def __init__(self, ctx, n, w, h, threshold=20, max_keypoints=10000, n_levels=8, device=None, descriptor="brief", detector="fast",
-                 contrast=128):
+                 contrast=128, refine=False):
         if descriptor not in DESCRIPTORS:
             raise ValueError(f"descriptor must be one of {DESCRIPTORS}")
         if detector not in DETECTORS:
             raise ValueError(f"detector must be one of {DETECTORS}")
+        if refine and detector != "dog":
+            raise ValueError('refine=True needs detector="dog"')
+        self.refine = bool(refine)
         self.ctx, self.n, self.w, self.h, self.descriptor, self.detector = ctx, int(n), int(w), int(h), descriptor, detector
         self.threshold, self.max_keypoints, self.n_levels, self.contrast = int(threshold), int(max_keypoints), int(n_levels), int(contrast)
         dev = _device(ctx, device)
         if detector == "dog":
-            size = ctx.detect_dog_workspace_bytes
+            size = ctx.detect_dog_refined_workspace_bytes if self.refine else ctx.detect_dog_workspace_bytes
         else:
             size = ctx.detect_pyramid_workspace_bytes if descriptor == "brief" else ctx.detect_pyramid_grad_workspace_bytes
         self.ws_bytes = size(w, h, n, max_keypoints, n_levels)
@@ -293,7 +298,8 @@ class DetectPyramid:
         args = (d_images.data_ptr(), self.n, self.w, self.h, strength, self.max_keypoints, self.n_levels, self.d_ws.data_ptr(), self.ws_bytes,
                 self.d_kp.data_ptr(), self.d_desc.data_ptr(), self.d_counts.data_ptr(), self.d_level_counts.data_ptr())
         if self.detector == "dog":
-            self.ctx.detect_dog_batch_device(*args, None if self.d_rows128 is None else self.d_rows128.data_ptr())
+            call = self.ctx.detect_dog_refined_batch_device if self.refine else self.ctx.detect_dog_batch_device
+            call(*args, None if self.d_rows128 is None else self.d_rows128.data_ptr())
         elif self.d_rows128 is None:
             self.ctx.detect_pyramid_batch_device(*args)
         else:
@@ -312,16 +318,17 @@ class DetectPyramid:
 
 
 def detect_images_pyramid(ctx, images, threshold=20, max_keypoints=10000, n_levels=8, device=None, descriptor="brief", detector="fast",
-                          contrast=128):
+                          contrast=128, refine=False):
     """gms_detect_pyramid_batch_device on a stack of equally sized 8-bit grey images [n, H, W]: the detector of detect_images on every
     level of an image pyramid (ratio about 1.2). Returns (keypoints_per_image, rows_per_image, level_counts [n, n_levels]) as host
     arrays: KEYPOINT_DTYPE records in level-0 pixel coordinates with size and octave, level 0 first, raster order inside a level.
     descriptor="grad": rows_per_image are the float32 [n_i, 128] gradient rows (for GMS_DESC_L2_F32X128); "both": (keypoints, 32-byte
     rows, 128-float rows, level_counts). detector="dog": the keypoints are difference-of-Gaussians blobs (gms_detect_dog_batch_device,
-    `contrast` in 1/256 grey level in the place of `threshold`); the outputs have the same form."""
+    `contrast` in 1/256 grey level in the place of `threshold`); the outputs have the same form. refine=True (with "dog"):
+    gms_detect_dog_refined_batch_device, the same records with x, y and size refined."""
     dev, imgs = _image_stack(ctx, images, device)
     n, h, w = imgs.shape
-    run = DetectPyramid(ctx, n, w, h, threshold, max_keypoints, n_levels, dev, descriptor, detector, contrast)
+    run = DetectPyramid(ctx, n, w, h, threshold, max_keypoints, n_levels, dev, descriptor, detector, contrast, refine)
     run.run(imgs)
     ctx.synchronize()
     return run.results()
@@ -337,6 +344,19 @@ def dog_candidates(ctx, images, contrast=128, device=None):
     ctx.dog_candidates_device(imgs.data_ptr(), n, w, h, contrast, d_cand.data_ptr())
     ctx.synchronize()
     return d_cand.cpu().numpy()
+
+
+def dog_offsets(ctx, images, contrast=128, device=None):
+    """gms_dog_offsets_device on a stack of equally sized 8-bit grey images [n, H, W]: the refinement's code planes on the images
+    themselves (one level) as a host array uint16 [n, H, W] -- 1 + (ox + 8) + 17 (oy + 8) + 289 (os + 8) at a candidate of
+    dog_candidates, the offsets in 1/16 pixel and 1/16 layer, else 0."""
+    dev, imgs = _image_stack(ctx, images, device)
+    n, h, w = imgs.shape
+    d_codes = torch.zeros((n, h, w), dtype=torch.int16, device=dev)
+    torch.cuda.synchronize(dev)
+    ctx.dog_offsets_device(imgs.data_ptr(), n, w, h, contrast, d_codes.data_ptr())
+    ctx.synchronize()
+    return d_codes.cpu().numpy().view(np.uint16)
 
 
 def bgr_to_gray(ctx, d_bgr):

@@ -91,6 +91,9 @@ SIGNATURES = {
     "gms_detect_dog_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
     "gms_detect_dog_batch_device": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp, vp, vp, vp, vp]),
     "gms_dog_candidates_device": (i32, [vp, vp, i32, i32, i32, i32, vp]),
+    "gms_detect_dog_refined_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "gms_detect_dog_refined_batch_device": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp, vp, vp, vp, vp]),
+    "gms_dog_offsets_device": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "gms_bgr_to_gray_device": (i32, [vp, vp, i32, i32, i32, vp]),
     "gms_detect_pack_device": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
     "gms_logos_dict_workspace_bytes": (sz, [i32, i64, i32, i32, i32, i32]),

@@ -28,11 +28,13 @@
 //   pyr_resize_kernel    a level from the level below it: integer bilinear, source rows through LDS, 4-byte loads and stores.
 //   det_describe_kernel  in its per-level form: records behind the earlier levels', pt mapped to level 0, size and octave set.
 //   (with d_rows128: grad_desc_kernels.hip's kernel behind every level's describe kernel -- DESIGN.md section 4.7c)
-//   (with dog_contrast >= 0: dog_kernels.hip's dog_maps_kernel in the place of det_maps_kernel + det_nms_kernel -- DESIGN.md section 4.7d)
+//   (with dog_contrast >= 0: dog_kernels.hip's dog_maps_kernel in the place of det_maps_kernel + det_nms_kernel -- DESIGN.md section 4.7d;
+//    with refine: its form that stores the refinement's codes, and det_describe_kernel's form that reads them)
 //   pyr_clear_kernel     zeroes the levels' counts and histograms; pyr_counts_kernel: the per-image and per-level counts for the caller.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dog_core.h"
 #include "gms_kernels.h"
 
 namespace gms {
@@ -282,11 +284,15 @@ det_emit_kernel(const uint8_t* __restrict__ cand, int w, int h, const int32_t* _
 //   kFromList    from det_emit_kernel's list; record k of image img goes to slot img * max_keypoints + k.
 //   kFromLevel   the same list, of pyramid level `level` (max_keypoints = the level's quota): the record goes behind the earlier levels'
 //                survivors in the image's block of out_stride records, pt mapped to level 0, size and octave of the level.
-enum { kAtRecords = 0, kFromList = 1, kFromLevel = 2 };
+//   kFromLevelRefined   kFromLevel behind the DoG detector's refining form: x, y and size of the record are moved by the offsets that
+//                dog_maps_kernel<true> left in `codes` at the keypoint's pixel. Direction, response and
+//                the row are those of the integer pixel.
+enum { kAtRecords = 0, kFromList = 1, kFromLevel = 2, kFromLevelRefined = 3 };
 struct LevelOut {
     const int32_t* level_counts;   // [level][image]: survivors of the levels (this level's row is `counts`)
     int level, n_images, out_stride;
     float fx, fy;                  // (float)w_0 / (float)w_level, (float)h_0 / (float)h_level
+    const uint16_t* codes;         // kFromLevelRefined: the level's plane of dog_core.h's refinement codes, [image][h][w]
 };
 
 template <int MODE>
@@ -304,7 +310,7 @@ det_describe_kernel(const uint8_t* __restrict__ images, const uint16_t* __restri
     const uint8_t* __restrict__ im = images + (size_t)img * plane;
     const uint16_t* __restrict__ bx = box + (size_t)img * plane;
     size_t slot = (size_t)img * max_keypoints + k;
-    if constexpr (MODE == kFromLevel) {
+    if constexpr (MODE == kFromLevel || MODE == kFromLevelRefined) {
         int before = 0;   // (the levels' counts sum to at most out_stride: the quotas do)
         for (int j = 0; j < lo.level; ++j) before += lo.level_counts[(size_t)j * lo.n_images + img];
         slot = (size_t)img * lo.out_stride + before + k;
@@ -361,7 +367,13 @@ det_describe_kernel(const uint8_t* __restrict__ images, const uint16_t* __restri
     }
     if (lane < 4) reinterpret_cast<uint64_t*>(desc + slot * 32)[lane] = bits[lane & 3];
     if (lane == 0) {
-        if constexpr (MODE == kFromLevel) {   // pixel centres aligned; every operation rounded once (-ffp-contract=off)
+        if constexpr (MODE == kFromLevelRefined) {   // (the code is non-zero: the list holds candidates only)
+            const dog::Offsets o = dog::offsets_of((int)lo.codes[(size_t)img * plane + (size_t)y * w + x]);
+            gms_keypoint r;
+            r.x = dog::refined_coord(x, o.ox, lo.fx); r.y = dog::refined_coord(y, o.oy, lo.fy); r.size = dog::refined_size(o.os, lo.fx);
+            r.angle = 11.25f * (float)bin; r.response = (float)sc; r.octave = lo.level; r.class_id = -1;
+            *rec = r;
+        } else if constexpr (MODE == kFromLevel) {   // pixel centres aligned; every operation rounded once (-ffp-contract=off)
             gms_keypoint r;
             r.x = ((float)x + 0.5f) * lo.fx - 0.5f; r.y = ((float)y + 0.5f) * lo.fy - 0.5f; r.size = 31.0f * lo.fx;
             r.angle = 11.25f * (float)bin; r.response = (float)sc; r.octave = lo.level; r.class_id = -1;
@@ -488,7 +500,8 @@ DetWs carve(void* ws, int w, int h, int n_images, int max_keypoints)
 // pyramid (lo and the level's histogram, already cleared). dog_contrast >= 0: the candidates are the DoG detector's (dog_kernels.hip,
 // DESIGN.md section 4.7d) and `threshold` is not read; what follows the candidate plane is the same.
 hipError_t detect_level(const uint8_t* d_images, int n_images, int w, int h, int threshold, int max_keypoints, void* d_ws, gms_keypoint* d_kp,
-                        uint8_t* d_desc, int32_t* d_counts, const LevelOut* lo, uint32_t* level_hist, hipStream_t stream, int dog_contrast = -1)
+                        uint8_t* d_desc, int32_t* d_counts, const LevelOut* lo, uint32_t* level_hist, hipStream_t stream, int dog_contrast = -1,
+                        uint16_t* d_codes = nullptr)   // d_codes (with lo and dog_contrast >= 0): the records are refined through this plane
 {
     DetWs ws = carve(d_ws, w, h, n_images, max_keypoints);
     if (level_hist != nullptr) {
@@ -498,7 +511,8 @@ hipError_t detect_level(const uint8_t* d_images, int n_images, int w, int h, int
         if (e != hipSuccess) return e;
     }
     if (dog_contrast >= 0) {
-        hipError_t e = launch_dog_maps(d_images, n_images, w, h, dog_contrast, ws.cand, ws.box, ws.hist, stream);
+        hipError_t e = d_codes != nullptr ? launch_dog_maps_refine(d_images, n_images, w, h, dog_contrast, ws.cand, ws.box, ws.hist, d_codes, stream)
+                                          : launch_dog_maps(d_images, n_images, w, h, dog_contrast, ws.cand, ws.box, ws.hist, stream);
         if (e != hipSuccess) return e;
     } else {
         hipLaunchKernelGGL(det_maps_kernel, dim3((w + kTileW - 1) / kTileW, (h + kTileH - 1) / kTileH, n_images), dim3(256), 0, stream, d_images, w, h,
@@ -511,7 +525,10 @@ hipError_t detect_level(const uint8_t* d_images, int n_images, int w, int h, int
     hipLaunchKernelGGL(det_emit_kernel, dim3(h, n_images), dim3(64), 0, stream, ws.cand, w, h, ws.cut, ws.rows, max_keypoints, ws.list);
     if (max_keypoints > 0) {
         const dim3 grid((max_keypoints + 3) / 4, n_images);
-        if (lo != nullptr)
+        if (lo != nullptr && d_codes != nullptr)
+            hipLaunchKernelGGL(det_describe_kernel<kFromLevelRefined>, grid, dim3(256), 0, stream, d_images, ws.box, w, h, ws.list, d_counts,
+                               max_keypoints, d_kp, d_desc, (int32_t*)nullptr, *lo);
+        else if (lo != nullptr)
             hipLaunchKernelGGL(det_describe_kernel<kFromLevel>, grid, dim3(256), 0, stream, d_images, ws.box, w, h, ws.list, d_counts, max_keypoints,
                                d_kp, d_desc, (int32_t*)nullptr, *lo);
         else
@@ -591,9 +608,15 @@ size_t detect_pyramid_workspace_bytes(int w, int h, int n_images, int max_keypoi
     return pyramid_layout(w, h, n_images, max_keypoints, n_levels).total;
 }
 
+size_t detect_pyramid_refined_workspace_bytes(int w, int h, int n_images, int max_keypoints, int n_levels)
+{
+    if (detect_pyramid_workspace_bytes(w, h, n_images, max_keypoints, n_levels) == 0) return 0;
+    return pyramid_refined_layout(w, h, n_images, max_keypoints, n_levels).total;
+}
+
 hipError_t launch_detect_pyramid(const uint8_t* d_images, int n_images, int w, int h, int threshold, int max_keypoints, int n_levels, void* d_ws,
                                  gms_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, int32_t* d_level_counts, hipStream_t stream, float* d_rows128,
-                                 int dog_contrast)
+                                 int dog_contrast, bool refine)
 {
     if (n_images <= 0) return hipSuccess;
     int ww[kPyramidMaxLevels], hh[kPyramidMaxLevels], quota[kPyramidMaxLevels];
@@ -604,6 +627,7 @@ hipError_t launch_detect_pyramid(const uint8_t* d_images, int n_images, int w, i
     int32_t* lvl_counts = ws_ptr<int32_t>(d_ws, L.counts);
     uint32_t* hists = ws_ptr<uint32_t>(d_ws, L.hists);
     void* det_ws = ws_ptr<char>(d_ws, L.detect);
+    uint16_t* codes = refine ? ws_ptr<uint16_t>(d_ws, pyramid_refined_layout(w, h, n_images, max_keypoints, n_levels).codes) : nullptr;
     const size_t clear_words = (L.detect - L.counts) / 4;
     hipLaunchKernelGGL(pyr_clear_kernel, dim3((unsigned)((clear_words + 255) / 256 < 1024 ? (clear_words + 255) / 256 : 1024)), dim3(256), 0, stream,
                        reinterpret_cast<uint32_t*>(lvl_counts), clear_words);
@@ -612,9 +636,9 @@ hipError_t launch_detect_pyramid(const uint8_t* d_images, int n_images, int w, i
     const uint8_t* img = d_images;
     for (int l = 0; l < n; ++l) {
         if (quota[l] > 0) {
-            const LevelOut lo = {lvl_counts, l, n_images, max_keypoints, (float)w / (float)ww[l], (float)h / (float)hh[l]};
+            const LevelOut lo = {lvl_counts, l, n_images, max_keypoints, (float)w / (float)ww[l], (float)h / (float)hh[l], codes};
             e = detect_level(img, n_images, ww[l], hh[l], threshold, quota[l], det_ws, d_kp, d_desc, lvl_counts + (size_t)l * n_images, &lo,
-                             hists + (size_t)l * n_images * 256, stream, dog_contrast);
+                             hists + (size_t)l * n_images * 256, stream, dog_contrast, codes);
             if (e != hipSuccess) return e;
             if (d_rows128 != nullptr) {   // while the level's box sums and list are still in the workspace
                 e = launch_grad_level(n_images, ww[l], hh[l], quota[l], det_ws, lvl_counts, l, max_keypoints, d_kp, d_rows128, stream);

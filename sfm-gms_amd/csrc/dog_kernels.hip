@@ -15,6 +15,8 @@
 //            come from 12 dword loads of pixels (six row sums per column, shared by the two rows). Sub-dword LDS loads cost the
 //            cycles of a dword load, and the kernel is bound by its LDS instructions, so everything is read as dwords.
 //     hist   scores counted in LDS, one global atomic per bin that the tile touched.
+//   dog_maps_kernel<true>   the same, and at every candidate the code of dog_core.h's refine (offsets in 1/16 pixel and 1/16 layer) as a
+//            2-byte store into a plane of its own: the layers are in registers at that point.
 //   LDS: 2 688 (pixels) + 17 408 (H) + 9 792 (B) + 1 024 (histogram) = 30 912 bytes: five workgroups per CU.
 //   HBM: 1 byte in, 3 bytes out per pixel (+ the halo re-reads, which the L2 serves).
 #include <hip/hip_runtime.h>
@@ -62,9 +64,13 @@ __device__ __forceinline__ void col_pass(const uint16_t* __restrict__ src, uint1
     *reinterpret_cast<uint64_t*>(dst) = packed;
 }
 
+// kRefine: the code of dog::refine at every candidate goes to `codes` as well, from the layers the candidate rule has just read. A
+// level's describe kernel reads a code only where the candidate plane is non-zero, so nothing else is stored; with cand == nullptr
+// (the code planes alone) every pixel is stored, 0 where there is no candidate, and no candidate plane.
+template <bool kRefine>
 __global__ void __launch_bounds__(256)
 dog_maps_kernel(const uint8_t* __restrict__ images, int w, int h, int contrast, uint8_t* __restrict__ cand, uint16_t* __restrict__ box,
-                uint32_t* __restrict__ hist)
+                uint32_t* __restrict__ hist, uint16_t* __restrict__ codes)
 {
     __shared__ __attribute__((aligned(16))) uint32_t pix[kPixH][kPixW / 4];
     __shared__ __attribute__((aligned(16))) uint16_t H[dog::kBlurs][kHRows][kPlaneW];
@@ -159,7 +165,13 @@ dog_maps_kernel(const uint8_t* __restrict__ images, int w, int h, int contrast, 
             if (x >= kBorder && x < w - kBorder && y >= kBorder && y < h - kBorder)
                 sc = dog::candidate(contrast, [&](int k, int dx, int dy) { return d[k][oy + 1 + dy][ox + 1 + dx]; });
             const size_t at = (size_t)blockIdx.z * plane + (size_t)y * w + x;
-            cand[at] = (uint8_t)sc;
+            if constexpr (kRefine) {
+                if (sc)
+                    codes[at] = (uint16_t)dog::refine([&](int k, int dx, int dy) { return d[k][oy + 1 + dy][ox + 1 + dx]; }).code();
+                else if (cand == nullptr)
+                    codes[at] = 0;
+            }
+            if (!kRefine || cand != nullptr) cand[at] = (uint8_t)sc;
             if (sc) atomicAdd(&lh[sc], 1u);
             const int bs = (x >= 2 && x < w - 2 && y >= 2 && y < h - 2) ? rs[ox][oy] + rs[ox][oy + 1] + rs[ox][oy + 2] + rs[ox][oy + 3] + rs[ox][oy + 4] : 0;
             if (box != nullptr) box[at] = (uint16_t)bs;
@@ -176,8 +188,18 @@ hipError_t launch_dog_maps(const uint8_t* d_images, int n_images, int w, int h, 
                            hipStream_t stream)
 {
     if (n_images <= 0) return hipSuccess;
-    hipLaunchKernelGGL(dog_maps_kernel, dim3((w + kTileW - 1) / kTileW, (h + kTileH - 1) / kTileH, n_images), dim3(256), 0, stream, d_images, w, h,
-                       contrast, d_cand, d_box, d_hist);
+    hipLaunchKernelGGL(dog_maps_kernel<false>, dim3((w + kTileW - 1) / kTileW, (h + kTileH - 1) / kTileH, n_images), dim3(256), 0, stream, d_images, w, h,
+                       contrast, d_cand, d_box, d_hist, (uint16_t*)nullptr);
+    return hipGetLastError();
+}
+
+// the same with the refinement's code plane: where d_cand is non-zero, or (d_cand == nullptr: the code planes alone) on every pixel
+hipError_t launch_dog_maps_refine(const uint8_t* d_images, int n_images, int w, int h, int contrast, uint8_t* d_cand, uint16_t* d_box, uint32_t* d_hist,
+                                  uint16_t* d_codes, hipStream_t stream)
+{
+    if (n_images <= 0) return hipSuccess;
+    hipLaunchKernelGGL(dog_maps_kernel<true>, dim3((w + kTileW - 1) / kTileW, (h + kTileH - 1) / kTileH, n_images), dim3(256), 0, stream, d_images, w, h,
+                       contrast, d_cand, d_box, d_hist, d_codes);
     return hipGetLastError();
 }
 

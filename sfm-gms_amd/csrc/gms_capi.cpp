@@ -1799,6 +1799,37 @@ int gms_detect_dog_batch_device(gms_ctx* c, const uint8_t* d_images, int n_image
     });
 }
 
+size_t gms_detect_dog_refined_workspace_bytes(int width, int height, int n_images, int max_keypoints, int n_levels)
+{
+    if (!detect_image_ok(width, height)) return 0;
+    return gms::detect_pyramid_refined_workspace_bytes(width, height, n_images, max_keypoints, n_levels);   // + the plane of refinement codes
+}
+
+int gms_detect_dog_refined_batch_device(gms_ctx* c, const uint8_t* d_images, int n_images, int width, int height, int contrast, int max_keypoints,
+                                        int n_levels, void* d_workspace, size_t workspace_bytes, gms_keypoint* d_keypoints, uint8_t* d_descriptors,
+                                        int32_t* d_counts, int32_t* d_level_counts, float* d_rows128)
+{
+    if (!c || n_images < 0 || max_keypoints < 0 || contrast < 0 || contrast > GMS_DOG_MAX_CONTRAST || !detect_image_ok(width, height)) return GMS_ERR_BAD_ARG;
+    if (n_levels < 1 || n_levels > GMS_PYRAMID_MAX_LEVELS) return GMS_ERR_BAD_ARG;
+    if (n_images == 0) return GMS_OK;
+    if (!d_images || !d_workspace || !d_counts || !d_level_counts) return GMS_ERR_BAD_ARG;
+    if (max_keypoints > 0 && (!d_keypoints || !d_descriptors)) return GMS_ERR_BAD_ARG;
+    if (d_rows128 && reinterpret_cast<uintptr_t>(d_rows128) % 8 != 0) return GMS_ERR_BAD_ARG;
+    if (workspace_bytes < gms_detect_dog_refined_workspace_bytes(width, height, n_images, max_keypoints, n_levels)) return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] {
+        return gms::launch_detect_pyramid(d_images, n_images, width, height, 0, max_keypoints, n_levels, d_workspace, d_keypoints, d_descriptors,
+                                          d_counts, d_level_counts, c->stream, max_keypoints > 0 ? d_rows128 : nullptr, contrast, true);
+    });
+}
+
+int gms_dog_offsets_device(gms_ctx* c, const uint8_t* d_images, int n_images, int width, int height, int contrast, uint16_t* d_codes)
+{
+    if (!c || n_images < 0 || contrast < 0 || contrast > GMS_DOG_MAX_CONTRAST || !detect_image_ok(width, height)) return GMS_ERR_BAD_ARG;
+    if (n_images == 0) return GMS_OK;
+    if (!d_images || !d_codes || reinterpret_cast<uintptr_t>(d_codes) % 2 != 0) return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] { return gms::launch_dog_maps_refine(d_images, n_images, width, height, contrast, nullptr, nullptr, nullptr, d_codes, c->stream); });
+}
+
 int gms_dog_candidates_device(gms_ctx* c, const uint8_t* d_images, int n_images, int width, int height, int contrast, uint8_t* d_cand)
 {
     if (!c || n_images < 0 || contrast < 0 || contrast > GMS_DOG_MAX_CONTRAST || !detect_image_ok(width, height)) return GMS_ERR_BAD_ARG;

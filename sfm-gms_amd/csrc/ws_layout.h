@@ -109,6 +109,22 @@ inline PyramidGradLayout pyramid_grad_layout(int w, int h, int n_images, int max
     return pyramid_layout(w, h, n_images, max_keypoints, n_levels);
 }
 
+// The DoG call with refinement (dog_kernels.hip, detect_kernels.hip): the pyramid's regions, unchanged, and behind them the plane of
+// refinement codes that a level's candidate kernel leaves for its describe kernel. Never cleared: a code is read only where the
+// level's candidate plane is non-zero, and the kernel that wrote that plane wrote the code.
+struct PyramidRefinedLayout {
+    PyramidLayout pyramid;
+    size_t codes;  // uint16 [n][h][w] of level 0: every level fits into it in its turn
+    size_t total;
+};
+inline PyramidRefinedLayout pyramid_refined_layout(int w, int h, int n_images, int max_keypoints, int n_levels)
+{
+    const PyramidLayout P = pyramid_layout(w, h, n_images, max_keypoints, n_levels);
+    WsCursor c;
+    c.take(P.total, 256);
+    return {P, c.take((size_t)w * h * (size_t)n_images * 2, 256), c.end};
+}
+
 // ---- large pairs, per slice of n pairs of the context's own workspace (gms_kernel_band.hip, gms_kernel_stream.hip) ------------------
 // plan_workspace sizes a slice as n * bytes per pair: the regions of one pair, plus a slack that covers what the layout of n pairs
 // rounds up (`padding`; every round-up here is to 16 bytes, so it adds less than 16).

@@ -184,10 +184,11 @@ def _train_dictionary_device(ctx, descs, opts):
 def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, threshold=20, max_keypoints=10000, n_levels=8,
                descriptor="grad", withRotation=False, withScale=False, thresholdFactor=6.0, prob=0.7, ransac_threshold=1.0, max_iters=1000,
                device=None, dictionary=None, logos_capacity=None, cross_check=True, distance_coef=4.0, max_size=500, train_dictionary=None,
-               keep_tables=False, detector="fast", contrast=128):
+               keep_tables=False, detector="fast", contrast=128, refine=False):
     """run_dataset from pixels. images: [n, H, W] grey or [n, H, W, 3] BGR, 8-bit, a host array or a device tensor (or a list of equally
     sized images). BGR goes through gms_bgr_to_gray_device; the pyramid keypoint source (threshold, max_keypoints, n_levels; detector
-    "fast", or "dog" with `contrast` in the place of `threshold`: gms_detect_dog_batch_device; descriptor "grad" / "both": the 128-float rows under NORM_L2, "brief": the 32-byte rows under NORM_HAMMING) leaves its blocks on the
+    "fast", or "dog" with `contrast` in the place of `threshold`: gms_detect_dog_batch_device, with refine=True
+    gms_detect_dog_refined_batch_device; descriptor "grad" / "both": the 128-float rows under NORM_L2, "brief": the 32-byte rows under NORM_HAMMING) leaves its blocks on the
     device, gms_detect_pack_device puts them back to back, and the tables are built there: between the pixels and the results only the
     n + 1 frame offsets (and the status records the stages already read) come back. pairs: (frame_a, frame_b) rows or PAIR_DTYPE
     records; default every a < b. The other arguments and the returned records are run_dataset's (the matcher always runs: there are
@@ -204,7 +205,7 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
     src = src if src.dtype == PAIR_DTYPE else pair_table(np.asarray(pairs, dtype=np.int64).reshape(-1, 2), 0)
     dev = _device(ctx, device)
     d_images = (images if torch.is_tensor(images) else torch.from_numpy(np.ascontiguousarray(images))).to(dev).contiguous()
-    source = DetectPyramid(ctx, n, w, h, threshold, max_keypoints, n_levels, dev, descriptor, detector, contrast)   # (refuses a bad size before any launch)
+    source = DetectPyramid(ctx, n, w, h, threshold, max_keypoints, n_levels, dev, descriptor, detector, contrast, refine)   # (refuses a bad size before any launch)
     if is_bgr:
         d_images = bgr_to_gray(ctx, d_images)
     torch.cuda.synchronize(dev)
@@ -235,7 +236,7 @@ MAIN_SCENARIOS = ("normal", "rotated", "resized")   # frame 0 = the left image; 
 
 def run_main_scenarios(ctx, img1, img2, resize_to=(1000, 1000), angle=180, threshold=20, max_keypoints=10000, n_levels=8,
                        descriptor="grad", thresholdFactor=6.0, cross_check=True, distance_coef=4.0, max_size=500, camera=None, dist=None,
-                       prob=0.7, ransac_threshold=1.0, max_iters=1000, device=None, detector="fast", contrast=128):
+                       prob=0.7, ransac_threshold=1.0, max_iters=1000, device=None, detector="fast", contrast=128, refine=False):
     """The three feature-match scenarios of the reference's main() (main.cpp:28-47) from its two photographs: the pair as it is, the
     right image turned by `angle` degrees (img_rotate: getRotationMatrix2D + warpAffine) and the right image resized to `resize_to` =
     (width, height) (cv::resize). img1, img2: equally sized [H, W] grey or [H, W, 3] BGR images, host arrays or device tensors.
@@ -244,7 +245,7 @@ def run_main_scenarios(ctx, img1, img2, resize_to=(1000, 1000), angle=180, thres
     turned image, a second over the resized one; gms_detect_pack_device puts all four frames back to back, and ONE FrameTable /
     DescriptorTable with each frame's own size is built there -- between the pixels and the results only the 5 frame offsets (and the
     status records the stages read) come back. Each scenario then runs its pair (0, k) with method="bf" (bruteForceMatch) and with
-    method="gms" at withRotation = withScale = True (FeatureMatchUtil.cpp:69). detector and stage arguments: run_images'.
+    method="gms" at withRotation = withScale = True (FeatureMatchUtil.cpp:69). detector, refine and stage arguments: run_images'.
     Returns {"images": {"rotated", "resized"} (the transformed right images, of the kind that came in), "tables": (FrameTable,
     DescriptorTable), "sizes": the four (width, height), and per scenario name {"bf": record, "gms": record}, run_dataset's records}."""
     if descriptor not in ("brief", "grad", "both"):
@@ -257,8 +258,8 @@ def run_main_scenarios(ctx, img1, img2, resize_to=(1000, 1000), angle=180, thres
     d_pair = (pair if on_dev else torch.from_numpy(np.ascontiguousarray(pair))).to(dev).contiguous()
     ch = 3 if is_bgr else 1
     # (both detectors refuse a bad size before anything is launched)
-    det3 = DetectPyramid(ctx, 3, w, h, threshold, max_keypoints, n_levels, dev, descriptor, detector, contrast)
-    det1 = DetectPyramid(ctx, 1, rw, rh, threshold, max_keypoints, n_levels, dev, descriptor, detector, contrast)
+    det3 = DetectPyramid(ctx, 3, w, h, threshold, max_keypoints, n_levels, dev, descriptor, detector, contrast, refine)
+    det1 = DetectPyramid(ctx, 1, rw, rh, threshold, max_keypoints, n_levels, dev, descriptor, detector, contrast, refine)
     turn = Warp(ctx, 1, (w, h), (w, h), ch, 1, dev)
     shrink = Warp(ctx, 1, (w, h), (rw, rh), ch, 1, dev)
     turn.set_matrices(getRotationMatrix2D((w / 2., h / 2.), angle, 1.0))

@@ -5,7 +5,7 @@
     -> disparity map + RMS against a ground truth (gms_disparity_device).
 Input: an .npz with arrays left, right [H, W] uint8 and optionally gt (default: the committed 450 x 375 pair of the reference's
 SourceImages, tests/golden/image_stereo_pair_450x375.npz). Prints one JSON line; --out writes the survivors and the map as .npz.
-    python tools/gms_image_pair.py [pair.npz] [--dense] [--pyramid N] [--threshold 12] [--detector fast|dog] [--contrast 128] [--max-keypoints 10000] [--rotation] [--scale] [--ratio 4] [--check]
+    python tools/gms_image_pair.py [pair.npz] [--dense] [--pyramid N] [--threshold 12] [--detector fast|dog] [--contrast 128] [--refine] [--max-keypoints 10000] [--rotation] [--scale] [--ratio 4] [--check]
 --pyramid N: keypoints from N levels of an image pyramid (gms_detect_pyramid_batch_device), with size and octave; without it the single-scale detector.
 --descriptor grad: the 128-float gradient rows (gms_detect_pyramid_grad_batch_device, one level without --pyramid; --dense:
 gms_describe_grad_device) under NORM_L2 instead of the 32-byte rows under NORM_HAMMING.
@@ -33,6 +33,7 @@ def main():
     ap.add_argument("--threshold", type=int, default=12)
     ap.add_argument("--detector", choices=("fast", "dog"), default="fast", help="dog: difference-of-Gaussians keypoints on the pyramid (DESIGN.md 4.7d)")
     ap.add_argument("--contrast", type=int, default=128, help="the DoG detector's contrast in 1/256 grey level, in the place of --threshold")
+    ap.add_argument("--refine", action="store_true", help="with --detector dog: keypoints refined to 1/16 pixel and 1/16 layer")
     ap.add_argument("--max-keypoints", type=int, default=10000)
     ap.add_argument("--rotation", action="store_true")
     ap.add_argument("--scale", action="store_true")
@@ -53,6 +54,8 @@ def main():
     dog = a.detector == "dog"
     if dog and a.dense:
         ap.error("--dense describes every pixel: there is no detector to choose")
+    if a.refine and not dog:
+        ap.error("--refine needs --detector dog")
     t = {}
     t0 = time.perf_counter()
     if a.dense:
@@ -68,7 +71,7 @@ def main():
             rows.append(r)
     elif a.pyramid > 0 or grad or dog:
         kps, rows, level_counts = batch.detect_images_pyramid(ctx, np.stack([left, right]), a.threshold, a.max_keypoints, max(a.pyramid, 1),
-                                                              descriptor=a.descriptor, detector=a.detector, contrast=a.contrast)
+                                                              descriptor=a.descriptor, detector=a.detector, contrast=a.contrast, refine=a.refine)
     else:
         kps, rows = batch.detect_images(ctx, np.stack([left, right]), a.threshold, a.max_keypoints)
     t["keypoints_ms"] = (time.perf_counter() - t0) * 1e3
@@ -125,8 +128,8 @@ def main():
                                          and (matches["queryIdx"] == np.arange(len(matches))).all() and (matches["imgIdx"] == 0).all())
         else:
             if dog:
-                import dog_ref
-                want = [dog_ref.detect(oracle, img, a.contrast, a.max_keypoints, max(a.pyramid, 1)) for img in (left, right)]
+                import dog_refine_ref
+                want = [dog_refine_ref.detect(oracle, img, a.contrast, a.max_keypoints, max(a.pyramid, 1), refine=a.refine) for img in (left, right)]
                 want = [(k, r128 if grad else r32) for k, r32, _, r128 in want]
             elif grad:
                 import grad_desc_ref

@@ -3,7 +3,7 @@
 (pipeline.run_main_scenarios): the pair as it is, the right image turned (img_rotate) and the right image resized (cv::resize), each
 matched by bruteForceMatch and by matchGMS(withRotation, withScale).
 
-    python tools/gms_main_scenarios.py [pair.npz] [--resize 1000x1000] [--angle 180] [--keypoints 10000] [--threshold 20] [--detector fast|dog] [--contrast 128] [--check]
+    python tools/gms_main_scenarios.py [pair.npz] [--resize 1000x1000] [--angle 180] [--keypoints 10000] [--threshold 20] [--detector fast|dog] [--contrast 128] [--refine] [--check]
 
 pair.npz holds `left` and `right`, equally sized [H, W] or [H, W, 3] (default: tests/golden/image_main_scenario_1080p.npz). Prints the
 scenario table, one JSON line per scenario and method. --check compares the transformed images with tests/warp_ref.py."""
@@ -29,8 +29,11 @@ def main():
     ap.add_argument("--threshold", type=int, default=20)
     ap.add_argument("--detector", choices=("fast", "dog"), default="fast")
     ap.add_argument("--contrast", type=int, default=128)
+    ap.add_argument("--refine", action="store_true", help="with --detector dog: keypoints refined to 1/16 pixel and 1/16 layer")
     ap.add_argument("--check", action="store_true")
     a = ap.parse_args()
+    if a.refine and a.detector != "dog":
+        ap.error("--refine needs --detector dog")
     z = np.load(a.pair)
     left, right = np.ascontiguousarray(z["left"]), np.ascontiguousarray(z["right"])
     resize_to = tuple(int(v) for v in a.resize.lower().split("x"))
@@ -39,7 +42,7 @@ def main():
     ctx = pkg.GmsContext(0)
     t0 = time.perf_counter()
     r = pipeline.run_main_scenarios(ctx, left, right, resize_to=resize_to, angle=a.angle, threshold=a.threshold, max_keypoints=a.keypoints,
-                                    detector=a.detector, contrast=a.contrast)
+                                    detector=a.detector, contrast=a.contrast, refine=a.refine)
     ms = (time.perf_counter() - t0) * 1e3
     counts = np.diff(r["tables"][0].frame_off_host).tolist()
     for k, name in enumerate(pipeline.MAIN_SCENARIOS, start=1):

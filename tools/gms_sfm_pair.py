@@ -3,15 +3,15 @@
 (structureFromMotion in sfm-gms_amd/api.py -> pipeline.run_images): pixels -> keypoints and rows -> the method's matches ->
 findEssentialMat(RANSAC, 0.7, 1.0) -> recoverPose -> undistort + triangulate. Prints one JSON line: pose, point count, reprojection RMS.
 
-    python tools/gms_sfm_pair.py [pair.npz] [--method gms|bf|logos] [--max-keypoints 10000] [--threshold 20] [--levels 8] [--detector fast|dog] [--contrast 128] [--bgr] [--check] [--camera camera.npz] [--out x.npz]
+    python tools/gms_sfm_pair.py [pair.npz] [--method gms|bf|logos] [--max-keypoints 10000] [--threshold 20] [--levels 8] [--detector fast|dog] [--contrast 128] [--refine] [--bgr] [--check] [--camera camera.npz] [--out x.npz]
 
 pair.npz: arrays left, right ([H, W] grey or [H, W, 3] BGR, uint8) and camera = (fx, fy, cx, cy), optionally dist = (k1, k2, p1, p2, k3);
 default: the committed pair of the reference's SourceImages, tests/golden/image_sfm_pair_1008x756.npz (its camera is stated, not
 calibrated). --camera: a file with camera (and optionally dist), as tools/gms_calibrate.py --out writes it, in place of the pair's own:
 the committed calibration photographs have the pair's scale, so their calibration applies to it. --bgr: hand the grey images over
 as three equal channels (the BGR entry, gms_bgr_to_gray_device). --detector dog: difference-of-Gaussians keypoints with
---contrast in 1/256 grey level in the place of --threshold. --check (method gms): runs the CPU statements (tests/sfm_images_ref.py; with
---detector dog tests/dog_ref.py's detector in front of them) beside it and compares every stage; test infrastructure, about ten seconds."""
+--contrast in 1/256 grey level in the place of --threshold; --refine: its keypoints refined to 1/16 pixel and 1/16 layer. --check (method gms): runs the CPU statements (tests/sfm_images_ref.py; with
+--detector dog tests/dog_ref.py's detector, with --refine tests/dog_refine_ref.py's, in front of them) beside it and compares every stage; test infrastructure, about ten seconds."""
 import argparse
 import importlib
 import json
@@ -34,11 +34,14 @@ def main():
     ap.add_argument("--levels", type=int, default=8)
     ap.add_argument("--detector", choices=("fast", "dog"), default="fast")
     ap.add_argument("--contrast", type=int, default=128)
+    ap.add_argument("--refine", action="store_true")
     ap.add_argument("--bgr", action="store_true")
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--camera")
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.refine and a.detector != "dog":
+        ap.error("--refine needs --detector dog")
     pkg = importlib.import_module("sfm-gms_amd")
     z = np.load(a.pair)
     left, right = np.ascontiguousarray(z["left"], dtype=np.uint8), np.ascontiguousarray(z["right"], dtype=np.uint8)
@@ -49,7 +52,7 @@ def main():
         camera = tuple(float(v) for v in zc["camera"])
         dist = tuple(float(v) for v in zc["dist"]) if "dist" in zc.files else None
     imgs = [np.ascontiguousarray(np.stack([im] * 3, axis=2)) for im in (left, right)] if a.bgr and left.ndim == 2 else [left, right]
-    kw = dict(method=a.method, max_keypoints=a.max_keypoints, threshold=a.threshold, n_levels=a.levels, detector=a.detector, contrast=a.contrast)
+    kw = dict(method=a.method, max_keypoints=a.max_keypoints, threshold=a.threshold, n_levels=a.levels, detector=a.detector, contrast=a.contrast, refine=a.refine)
     t0 = time.perf_counter()
     r = pkg.structureFromMotion(*imgs, camera, dist, **kw)
     ms = (time.perf_counter() - t0) * 1e3
@@ -58,7 +61,7 @@ def main():
     rms = float(np.sqrt((tv["sum_sq_err1"] + tv["sum_sq_err2"]) / (2 * max(n_pose, 1))) * (camera[0] + camera[1]) / 2)
     line = {"image": [int(left.shape[1]), int(left.shape[0])], "input": "bgr" if imgs[0].ndim == 3 else "grey", "method": a.method,
             "camera": [round(v, 4) for v in camera], "dist": None if dist is None else [round(v, 6) for v in dist],
-            "detector": a.detector, "max_keypoints": a.max_keypoints, "keypoints": [len(r["keypoints1"]), len(r["keypoints2"])], "survivors": len(r["matches"]),
+            "detector": a.detector, "refine": a.refine, "max_keypoints": a.max_keypoints, "keypoints": [len(r["keypoints1"]), len(r["keypoints2"])], "survivors": len(r["matches"]),
             "ransac_inliers": int(tv["n_ransac"]), "ransac_iterations": int(tv["ransac_iters"]), "after_recover_pose": int(tv["n_pose"]),
             "points": len(r["points3D"]), "behind_a_camera": int(tv["n_behind"]), "reprojection_rms_px": round(rms, 4),
             "t": [round(float(v), 4) for v in r["t"]], "R": [[round(float(v), 5) for v in row] for row in r["R"]],
@@ -72,8 +75,8 @@ def main():
         import gms_oracle as oracle
         import sfm_images_ref
         if a.detector == "dog":
-            import dog_ref
-            c = dog_ref.sfm_chain(oracle, left, right, camera, a.contrast, a.max_keypoints, a.levels)
+            import dog_refine_ref
+            c = dog_refine_ref.sfm_chain(oracle, left, right, camera, a.contrast, a.max_keypoints, a.levels, refine=a.refine)
         else:
             c = sfm_images_ref.chain(oracle, left, right, camera, a.max_keypoints, a.threshold, a.levels)
         ref = c["two_view"]
