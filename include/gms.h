@@ -703,6 +703,39 @@ int gms_stereo_bm_normalize_device(gms_ctx* ctx, const int16_t* d_disp16, int n,
 int gms_stereo_bm(const gms_stereo_bm_params* params, const uint8_t* left, const uint8_t* right, int width, int height, int pitch,
                   int16_t* disp16, int32_t* cost, uint8_t* disp8);
 
+/* ---- Semi-global matching on StereoBM's costs (tests/stereo_sgm_ref.py states it) ---------------------------------
+ * The library's own definition, NOT cv::StereoSGBM: no Birchfield-Tomasi cost, no OpenCV source restated. The matching cost
+ * C[y][x][k] is StereoBM's window SAD after its XSOBEL pre-filter, over the region StereoBM computes (rows [w2, H - w2), its output
+ * columns), k meaning disparity num_disparities - 1 + min_disparity - k. Along each of n_paths directions (dy, dx) = (0,1), (0,-1),
+ * (1,0), (-1,0), then (1,1), (1,-1), (-1,1), (-1,-1), a pixel whose predecessor (y - dy, x - dx) lies outside the region has L = C, every
+ * other pixel L[k] = C[k] + min(Lp[k], Lp[k-1] + p1, Lp[k+1] + p1, m + p2) - m with m = min Lp (terms with k +- 1 outside the range left
+ * out). S is the sum of L over the paths. StereoBM's rules then run on S in place of its SADs: the winner (the lowest k on ties), the
+ * texture rule on StereoBM's texture sum, the uniqueness rule, the subpixel step, the left-right check and the ROI fill. Outputs as
+ * gms_stereo_bm_device's: int16 maps with 4 fractional bits, FILTERED = (min_disparity - 1) * 16; costs S[winner], -1 elsewhere.
+ * With p1 = p2 = 0 and uniqueness_ratio = 0 the map is StereoBM's and the cost n_paths times StereoBM's.
+ * Accepted (others: GMS_ERR_BAD_ARG): what gms_stereo_bm_device accepts for bm, 0 <= p1 <= p2, n_paths 4 or 8, and
+ * n_paths * (block_size^2 * 2 * pre_filter_cap + p2) <= 65535 (every path cost and their sum fit 16 unsigned bits). */
+typedef struct gms_stereo_sgm_params {
+    gms_stereo_bm_params bm;
+    int32_t p1;                  /* penalty of a disparity step of one      */
+    int32_t p2;                  /* penalty of a larger step                */
+    int32_t n_paths;             /* 4 or 8                                  */
+} gms_stereo_sgm_params;
+/* The reference's StereoBM values, p1 = 8 * block_size^2, p2 = 32 * block_size^2, eight paths; a NULL params pointer means the same. */
+#define GMS_STEREO_SGM_PARAMS_REFERENCE {GMS_STEREO_BM_PARAMS_REFERENCE, 200, 800, 8}
+
+/* gms_stereo_sgm_workspace_bytes: the workspace of gms_stereo_sgm_device (256-byte aligned pointer): StereoBM's regions, the texture
+ *   sums and the two 16-bit volumes C and S, 4 * num_disparities bytes per pixel of the region; 0 for arguments it rejects and for a
+ *   size beyond size_t.
+ * gms_stereo_sgm_device: n_pairs (up to 65535) pairs on the context's stream, arguments as gms_stereo_bm_device's; no allocation, no
+ *   synchronisation, no readback (graph-capturable). d_cost may be NULL. gms_stereo_bm_normalize_device gives the 8-bit maps.
+ * gms_stereo_sgm: ONE pair on host pointers, synchronous, on the current HIP device; disp16 / cost / disp8 are each optional. */
+size_t gms_stereo_sgm_workspace_bytes(int width, int height, int n_pairs, const gms_stereo_sgm_params* params);
+int gms_stereo_sgm_device(gms_ctx* ctx, const gms_stereo_sgm_params* params, const uint8_t* d_left, const uint8_t* d_right, int n_pairs,
+                          int width, int height, int pitch, void* d_ws, size_t ws_bytes, int16_t* d_disp16, int32_t* d_cost);
+int gms_stereo_sgm(const gms_stereo_sgm_params* params, const uint8_t* left, const uint8_t* right, int width, int height, int pitch,
+                   int16_t* disp16, int32_t* cost, uint8_t* disp8);
+
 /* ---- Portrait mode: the image tail of the reference's createPortraitMode (DisparityUtil.cpp:317-412) -----------------
  *     disparity 255 -> 0; threshold(60); dilate(3 x 3, 2 iterations, BORDER_REPLICATE); findContours(RETR_LIST, CHAIN_APPROX_NONE);
  *     the 5 borders of largest |contourArea|, drawContours(FILLED); medianBlur(image, 15); the photograph's own pixels back where a

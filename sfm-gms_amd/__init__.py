@@ -11,9 +11,10 @@ The directory name has a dash (it is fixed by the project layout), so load it wi
 """
 from .types import (KEYPOINT_DTYPE, DMATCH_DTYPE, PAIR_DTYPE, RESULT_DTYPE, LOGOS_RESULT_DTYPE, LOGOS_DICT_RESULT_DTYPE, BF_RESULT_DTYPE, GmsError,  # noqa: F401
                     GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128, GMS_DETECT_BORDER, STEREO_BM_PARAMS_DTYPE, stereo_bm_params,
+                    STEREO_SGM_PARAMS_DTYPE, stereo_sgm_params,
                     PORTRAIT_PARAMS_DTYPE, portrait_params)
 from .capi import load_library, library_path, EXPORTED_SYMBOLS  # noqa: F401
-from .api import matchGMS, matchLOGOS, trainLogosDictionary, bruteForceMatch, stereoBM, stereo_match, portraitMode, medianBlur, structureFromMotion, GmsContext  # noqa: F401
+from .api import matchGMS, matchLOGOS, trainLogosDictionary, bruteForceMatch, stereoBM, stereo_match, stereoSGM, stereo_match_sgm, portraitMode, medianBlur, structureFromMotion, GmsContext  # noqa: F401
 from .api import resize, warpAffine, getRotationMatrix2D, imgRotate  # noqa: F401
 from .api import findChessboardCorners, cornerSubPix, calibrateCamera, addChessboardPoints, chessboardObjectPoints  # noqa: F401
 from .types import CHESS_CANDIDATE_DTYPE  # noqa: F401
@@ -23,6 +24,7 @@ __all__ = [
     "KEYPOINT_DTYPE", "DMATCH_DTYPE", "PAIR_DTYPE", "RESULT_DTYPE", "LOGOS_RESULT_DTYPE", "BF_RESULT_DTYPE", "GmsError",
     "load_library", "library_path", "EXPORTED_SYMBOLS", "matchGMS", "matchLOGOS", "trainLogosDictionary", "LOGOS_DICT_RESULT_DTYPE", "bruteForceMatch", "stereoBM", "stereo_match",
     "STEREO_BM_PARAMS_DTYPE", "stereo_bm_params", "GmsContext",
+    "stereoSGM", "stereo_match_sgm", "STEREO_SGM_PARAMS_DTYPE", "stereo_sgm_params",
     "portraitMode", "medianBlur", "structureFromMotion", "resize", "warpAffine", "getRotationMatrix2D", "imgRotate", "PORTRAIT_PARAMS_DTYPE", "portrait_params",
     "findChessboardCorners", "cornerSubPix", "calibrateCamera", "addChessboardPoints", "chessboardObjectPoints", "CHESS_CANDIDATE_DTYPE",
     "all_pairs_count", "pair_from_index", "shard_range", "GMS_DESC_HAMMING256", "GMS_DESC_L2_F32X128", "GMS_DETECT_BORDER",

@@ -13,7 +13,7 @@ import numpy as np
 
 from .capi import load_library
 from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, LOGOS_DICT_RESULT_DTYPE, KEYPOINT_DTYPE, PAIR_DTYPE, RESULT_DTYPE, GMS_OK, GMS_ERR_CAPACITY,
-                    GmsError, concat_frames, desc_layout, portrait_params, stereo_bm_params)
+                    GmsError, concat_frames, desc_layout, portrait_params, stereo_bm_params, stereo_sgm_params)
 
 
 def _as(arr, dtype, name):
@@ -375,6 +375,16 @@ class GmsContext:
         _check(self._lib.gms_stereo_bm_device(self._h, rec.ctypes.data, d_left, d_right, int(n_pairs), int(width), int(height), int(pitch),
                                               d_ws, int(ws_bytes), d_disp16, d_cost or None), self._lib, "gms_stereo_bm_device")
 
+    # -- semi-global matching on StereoBM's costs (batch.stereo_sgm_batch drives these) --------------------------
+    def stereo_sgm_workspace_bytes(self, width, height, n_pairs, params=None):
+        return int(self._lib.gms_stereo_sgm_workspace_bytes(int(width), int(height), int(n_pairs), stereo_sgm_params(params).ctypes.data))
+
+    def stereo_sgm_device(self, params, d_left, d_right, n_pairs, width, height, pitch, d_ws, ws_bytes, d_disp16, d_cost=None):
+        """gms_stereo_sgm_device; params: None (the reference's), a dict or a STEREO_SGM_PARAMS_DTYPE record. Stream-ordered."""
+        rec = stereo_sgm_params(params)
+        _check(self._lib.gms_stereo_sgm_device(self._h, rec.ctypes.data, d_left, d_right, int(n_pairs), int(width), int(height), int(pitch),
+                                               d_ws, int(ws_bytes), d_disp16, d_cost or None), self._lib, "gms_stereo_sgm_device")
+
     def stereo_bm_normalize_device(self, d_disp16, n, width, height, d_out8):
         _check(self._lib.gms_stereo_bm_normalize_device(self._h, d_disp16, int(n), int(width), int(height), d_out8), self._lib,
                "gms_stereo_bm_normalize_device")
@@ -609,21 +619,25 @@ def default_context():
     return _default_ctx
 
 
-def _stereo_bm(left, right, params, want16, want_cost, want8):
+def _stereo_one_shot(entry, make_params, left, right, params, want16, want_cost, want8):
     lib = load_library()
     lt = np.ascontiguousarray(left, dtype=np.uint8)
     rt = np.ascontiguousarray(right, dtype=np.uint8)
     if lt.ndim != 2 or rt.shape != lt.shape:
         raise ValueError("left and right: two 8-bit grey images [H, W] of one size")
     h, w = lt.shape
-    rec = stereo_bm_params(params)
+    rec = make_params(params)
     d16 = np.zeros((h, w), np.int16) if want16 else None
     cost = np.zeros((h, w), np.int32) if want_cost else None
     d8 = np.zeros((h, w), np.uint8) if want8 else None
-    rc = lib.gms_stereo_bm(rec.ctypes.data, lt.ctypes.data, rt.ctypes.data, w, h, w, None if d16 is None else d16.ctypes.data,
-                           None if cost is None else cost.ctypes.data, None if d8 is None else d8.ctypes.data)
-    _check(rc, lib, "gms_stereo_bm")
+    rc = getattr(lib, entry)(rec.ctypes.data, lt.ctypes.data, rt.ctypes.data, w, h, w, None if d16 is None else d16.ctypes.data,
+                             None if cost is None else cost.ctypes.data, None if d8 is None else d8.ctypes.data)
+    _check(rc, lib, entry)
     return d16, cost, d8
+
+
+def _stereo_bm(left, right, params, want16, want_cost, want8):
+    return _stereo_one_shot("gms_stereo_bm", stereo_bm_params, left, right, params, want16, want_cost, want8)
 
 
 def stereoBM(left, right, return_cost=False, **params):
@@ -639,6 +653,36 @@ def stereo_match(left, right, **params):
     """The reference's stereo_match (DisparityUtil.cpp:22-49): StereoBM with its parameters, normalize(NORM_MINMAX, 0..255, CV_8U),
     every 0 -> 255. Returns the uint8 map."""
     return _stereo_bm(left, right, params, False, False, True)[2]
+
+
+def _stereo_sgm(left, right, params, want_cost, want8):
+    """One pair: host arrays through gms_stereo_sgm, device tensors (torch, [H, W]) through a batch of one on the default context.
+    Returns (int16 map, cost or None, 8-bit map or None), arrays for arrays and tensors for tensors."""
+    if hasattr(left, "data_ptr"):
+        from .batch import stereo_sgm_batch
+        if left.dim() != 2 or right.shape != left.shape:
+            raise ValueError("left and right: two 8-bit grey images [H, W] of one size")
+        outs = stereo_sgm_batch(left[None], right[None], params, None, return_cost=want_cost, eight_bit=want8)
+        outs = list(outs) if isinstance(outs, tuple) else [outs]
+        return outs[0][0], (outs[1][0] if want_cost else None), (outs[-1][0] if want8 else None)
+    return _stereo_one_shot("gms_stereo_sgm", stereo_sgm_params, left, right, params, True, want_cost, want8)
+
+
+def stereoSGM(left, right, return_cost=False, p1=None, p2=None, n_paths=8, **bm_params):
+    """Semi-global matching on StereoBM's costs (tests/stereo_sgm_ref.py states it) -- the library's own definition,
+    not cv::StereoSGBM: StereoBM's window SADs, aggregated along n_paths (4 or 8) directions with the penalties p1 (a disparity step of
+    one; default 8 block_size^2) and p2 (a larger step; default 32 block_size^2), then StereoBM's decision rules on the sums. left /
+    right: uint8 [H, W] host arrays or device tensors. Returns the int16 map with 4 fractional bits, FILTERED = (min_disparity - 1) * 16;
+    return_cost=True: also the int32 cost map (the winner's sum, -1 where there is none). bm_params: StereoBM's parameters by keyword
+    (types.STEREO_SGM_PARAMS_DTYPE), the reference's values by default. p1 = p2 = 0 with uniqueness_ratio = 0 gives stereoBM's map."""
+    d16, cost, _ = _stereo_sgm(left, right, dict(bm_params, p1=p1, p2=p2, n_paths=n_paths), return_cost, False)
+    return (d16, cost) if return_cost else d16
+
+
+def stereo_match_sgm(left, right, **params):
+    """stereo_match with semi-global matching in StereoBM's place: normalize(NORM_MINMAX, 0..255, CV_8U), every 0 -> 255. Returns the
+    uint8 map."""
+    return _stereo_sgm(left, right, params, False, True)[2]
 
 
 def portraitMode(image_bgr, disparity, detail=False, **params):

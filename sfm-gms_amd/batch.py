@@ -10,7 +10,7 @@ import torch
 
 from .api import GmsContext, logos_dict_args
 from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128, GMS_ERR_CAPACITY, KEYPOINT_DTYPE, LOGOS_DICT_RESULT_DTYPE, LOGOS_RESULT_DTYPE, PAIR_DTYPE,
-                    RESULT_DTYPE, concat_frames, desc_layout, portrait_params, stereo_bm_params)
+                    RESULT_DTYPE, concat_frames, desc_layout, portrait_params, stereo_bm_params, stereo_sgm_params)
 
 
 def _to_dev(arr, device):
@@ -698,14 +698,22 @@ def logos_dictionary(ctx, descriptor_sets, kind, n_words=50, attempts=3, max_ite
 class StereoBM:
     """Device buffers of gms_stereo_bm_device for n pairs of one size: workspace, int16 maps, costs and 8-bit maps, sized once, so that
     run() can be replayed (or captured into a graph) on new images in the same tensors."""
+    NAME = "StereoBM"
+    make_params = staticmethod(stereo_bm_params)
+
+    def _workspace_bytes(self):
+        return self.ctx.stereo_bm_workspace_bytes(self.width, self.height, self.n, self.params)
+
+    def _device_call(self, *args):
+        self.ctx.stereo_bm_device(*args)
 
     def __init__(self, ctx, n, width, height, params=None, device="cuda:0", with_cost=True):
         self.ctx, self.n, self.width, self.height = ctx, int(n), int(width), int(height)
-        self.params = stereo_bm_params(params)
+        self.params = self.make_params(params)
         dev = torch.device(device)
-        self.ws_bytes = ctx.stereo_bm_workspace_bytes(width, height, n, self.params)
+        self.ws_bytes = self._workspace_bytes()
         if self.ws_bytes == 0 and self.n > 0:
-            raise ValueError("StereoBM: parameters or image size rejected (include/gms.h)")
+            raise ValueError(f"{self.NAME}: parameters or image size rejected (include/gms.h)")
         self.d_ws = torch.zeros(max(self.ws_bytes, 256), dtype=torch.uint8, device=dev)
         self.d_disp = torch.zeros((max(self.n, 1), self.height, self.width), dtype=torch.int16, device=dev)
         self.d_cost = torch.zeros((max(self.n, 1), self.height, self.width), dtype=torch.int32, device=dev) if with_cost else None
@@ -717,17 +725,27 @@ class StereoBM:
         for t in (d_left, d_right):
             if t.dtype != torch.uint8 or tuple(t.shape) != (self.n, self.height, self.width) or not t.is_contiguous():
                 raise ValueError("left / right: contiguous uint8 device tensors [n, height, width]")
-        self.ctx.stereo_bm_device(self.params, d_left.data_ptr(), d_right.data_ptr(), self.n, self.width, self.height, self.width,
-                                  self.d_ws.data_ptr(), self.ws_bytes, self.d_disp.data_ptr(),
-                                  self.d_cost.data_ptr() if self.d_cost is not None else None)
+        self._device_call(self.params, d_left.data_ptr(), d_right.data_ptr(), self.n, self.width, self.height, self.width,
+                          self.d_ws.data_ptr(), self.ws_bytes, self.d_disp.data_ptr(),
+                          self.d_cost.data_ptr() if self.d_cost is not None else None)
         if eight_bit:
             self.ctx.stereo_bm_normalize_device(self.d_disp.data_ptr(), self.n, self.width, self.height, self.d_out8.data_ptr())
 
 
-def stereo_bm_batch(lefts, rights, params=None, ctx=None, return_cost=False, eight_bit=False):
-    """StereoBM::compute for n pairs in one gms_stereo_bm_device run. lefts / rights: uint8 [n, H, W] host arrays or device tensors.
-    Returns the int16 maps [n, H, W] (numpy for host input, device tensors for device input), then the int32 costs with
-    return_cost=True and the reference's 8-bit maps with eight_bit=True."""
+class StereoSGM(StereoBM):
+    """The same buffers for gms_stereo_sgm_device (semi-global matching on StereoBM's costs): the workspace also holds
+    the two cost volumes, 4 * num_disparities bytes per pixel of the computed region."""
+    NAME = "StereoSGM"
+    make_params = staticmethod(stereo_sgm_params)
+
+    def _workspace_bytes(self):
+        return self.ctx.stereo_sgm_workspace_bytes(self.width, self.height, self.n, self.params)
+
+    def _device_call(self, *args):
+        self.ctx.stereo_sgm_device(*args)
+
+
+def _stereo_batch(cls, lefts, rights, params, ctx, return_cost, eight_bit):
     from .api import default_context
     ctx = ctx or default_context()
     on_dev = isinstance(lefts, torch.Tensor)
@@ -739,13 +757,26 @@ def stereo_bm_batch(lefts, rights, params=None, ctx=None, return_cost=False, eig
             raise ValueError("lefts / rights: uint8 [n, H, W] of one shape")
         dl, dr = torch.from_numpy(l).cuda(), torch.from_numpy(r).cuda()
     n, h, w = dl.shape
-    run = StereoBM(ctx, n, w, h, params, dl.device, with_cost=return_cost)
+    run = cls(ctx, n, w, h, params, dl.device, with_cost=return_cost)
     run.run(dl, dr, eight_bit)
     ctx.synchronize()
     outs = [run.d_disp[:n]] + ([run.d_cost[:n]] if return_cost else []) + ([run.d_out8[:n]] if eight_bit else [])
     if not on_dev:
         outs = [o.cpu().numpy() for o in outs]
     return outs[0] if len(outs) == 1 else tuple(outs)
+
+
+def stereo_bm_batch(lefts, rights, params=None, ctx=None, return_cost=False, eight_bit=False):
+    """StereoBM::compute for n pairs in one gms_stereo_bm_device run. lefts / rights: uint8 [n, H, W] host arrays or device tensors.
+    Returns the int16 maps [n, H, W] (numpy for host input, device tensors for device input), then the int32 costs with
+    return_cost=True and the reference's 8-bit maps with eight_bit=True."""
+    return _stereo_batch(StereoBM, lefts, rights, params, ctx, return_cost, eight_bit)
+
+
+def stereo_sgm_batch(lefts, rights, params=None, ctx=None, return_cost=False, eight_bit=False):
+    """Semi-global matching for n pairs in one gms_stereo_sgm_device run: arguments and results as stereo_bm_batch's; params may also
+    hold p1, p2 and n_paths (types.stereo_sgm_params)."""
+    return _stereo_batch(StereoSGM, lefts, rights, params, ctx, return_cost, eight_bit)
 
 
 class Portrait:

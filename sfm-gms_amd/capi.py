@@ -62,6 +62,9 @@ SIGNATURES = {
     "gms_stereo_bm_device": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp]),
     "gms_stereo_bm_normalize_device": (i32, [vp, vp, i32, i32, i32, vp]),
     "gms_stereo_bm": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "gms_stereo_sgm_workspace_bytes": (sz, [i32, i32, i32, vp]),
+    "gms_stereo_sgm_device": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp]),
+    "gms_stereo_sgm": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "gms_portrait_workspace_bytes": (sz, [i32, i32, i32, vp]),
     "gms_portrait_device": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp, vp, vp, vp]),
     "gms_median_blur_device": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),

@@ -26,6 +26,7 @@
 #include "logos_dict_core.h"
 #include "portrait_core.h"
 #include "stereo_bm_core.h"
+#include "stereo_sgm_core.h"
 #include "twoview_core.h"
 #include "warp_core.h"
 #include "calib_core.h"
@@ -1210,6 +1211,58 @@ int gms_stereo_bm(const gms_stereo_bm_params* params, const uint8_t* left, const
     blk.run([&](hipStream_t st) {
         return gms::launch_stereo_bm(p, blk.at<uint8_t>(o_l), blk.at<uint8_t>(o_r), 1, width, height, pitch, blk.at(o_ws), blk.at<int16_t>(o_d),
                                      cost ? blk.at<int32_t>(o_c) : nullptr, st);
+    });
+    if (disp8) blk.run([&](hipStream_t st) { return gms::launch_stereo_bm_normalize(blk.at<int16_t>(o_d), 1, width, height, blk.at<uint8_t>(o_8), st); });
+    if (disp16) blk.out(disp16, o_d, 2 * px);
+    if (cost) blk.out(cost, o_c, 4 * px);
+    if (disp8) blk.out(disp8, o_8, px);
+    return blk.finish();
+}
+
+// ---- semi-global matching (stereo_sgm_kernels.hip) ------------------------------------------------------------------
+static const gms_stereo_sgm_params& sgm_params(const gms_stereo_sgm_params* p)
+{
+    static const gms_stereo_sgm_params ref = GMS_STEREO_SGM_PARAMS_REFERENCE;
+    return p ? *p : ref;
+}
+
+size_t gms_stereo_sgm_workspace_bytes(int width, int height, int n_pairs, const gms_stereo_sgm_params* params)
+{
+    if (n_pairs < 0 || n_pairs > 65535 || !sgm::params_ok(sgm_params(params), width, height)) return 0;
+    return gms::stereo_sgm_ws_bytes(sgm_params(params), n_pairs, width, height);
+}
+
+int gms_stereo_sgm_device(gms_ctx* c, const gms_stereo_sgm_params* params, const uint8_t* d_left, const uint8_t* d_right, int n_pairs,
+                          int width, int height, int pitch, void* d_ws, size_t ws_bytes, int16_t* d_disp16, int32_t* d_cost)
+{
+    const gms_stereo_sgm_params& p = sgm_params(params);
+    if (!c || n_pairs < 0 || n_pairs > 65535 || !sgm::params_ok(p, width, height) || pitch < width) return GMS_ERR_BAD_ARG;
+    if (n_pairs == 0) return GMS_OK;
+    if (!d_left || !d_right || !d_ws || !d_disp16) return GMS_ERR_BAD_ARG;
+    const size_t need = gms::stereo_sgm_ws_bytes(p, n_pairs, width, height);
+    if ((reinterpret_cast<uintptr_t>(d_ws) & 255u) || (reinterpret_cast<uintptr_t>(d_disp16) & 1u) ||
+        (reinterpret_cast<uintptr_t>(d_cost) & 3u) || need == 0 || ws_bytes < need)
+        return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] { return gms::launch_stereo_sgm(p, d_left, d_right, n_pairs, width, height, pitch, d_ws, d_disp16, d_cost, c->stream); });
+}
+
+int gms_stereo_sgm(const gms_stereo_sgm_params* params, const uint8_t* left, const uint8_t* right, int width, int height, int pitch,
+                   int16_t* disp16, int32_t* cost, uint8_t* disp8)
+{
+    const gms_stereo_sgm_params& p = sgm_params(params);
+    if (!sgm::params_ok(p, width, height) || pitch < width || !left || !right) return GMS_ERR_BAD_ARG;
+    const size_t ws = gms::stereo_sgm_ws_bytes(p, 1, width, height);
+    if (ws == 0) return GMS_ERR_BAD_ARG;
+    const size_t px = (size_t)width * (size_t)height, img = (size_t)pitch * (size_t)(height - 1) + (size_t)width;
+    gms::BlockLayout lay;  // the images keep the caller's pitch
+    const size_t o_l = lay.add(img), o_r = lay.add(img), o_ws = lay.add(ws);
+    const size_t o_d = lay.add(2 * px), o_c = lay.add(4 * px), o_8 = lay.add(px);
+    DevBlock blk(lay, nullptr);
+    blk.in(o_l, left, img);
+    blk.in(o_r, right, img);
+    blk.run([&](hipStream_t st) {
+        return gms::launch_stereo_sgm(p, blk.at<uint8_t>(o_l), blk.at<uint8_t>(o_r), 1, width, height, pitch, blk.at(o_ws), blk.at<int16_t>(o_d),
+                                      cost ? blk.at<int32_t>(o_c) : nullptr, st);
     });
     if (disp8) blk.run([&](hipStream_t st) { return gms::launch_stereo_bm_normalize(blk.at<int16_t>(o_d), 1, width, height, blk.at<uint8_t>(o_8), st); });
     if (disp16) blk.out(disp16, o_d, 2 * px);

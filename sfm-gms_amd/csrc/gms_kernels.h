@@ -192,6 +192,14 @@ size_t     stereo_bm_ws_bytes(int n, int W, int H);
 hipError_t launch_stereo_bm(const gms_stereo_bm_params& p, const uint8_t* d_left, const uint8_t* d_right, int n, int W, int H, int pitch,
                             void* d_ws, int16_t* d_disp, int32_t* d_cost, hipStream_t stream);
 hipError_t launch_stereo_bm_normalize(const int16_t* d_disp, int n, int W, int H, uint8_t* d_out, hipStream_t stream);
+hipError_t launch_stereo_bm_prefilter(const gms_stereo_bm_params& p, const uint8_t* d_left, const uint8_t* d_right, int n, int W, int H,
+                                      int pitch, uint8_t* pre, hipStream_t stream);
+hipError_t launch_stereo_bm_validate(const gms_stereo_bm_params& p, int n, int W, int H, int16_t* d_disp, const int32_t* wcost,
+                                     int32_t* d_cost, hipStream_t stream);
+// semi-global matching on StereoBM's costs (stereo_sgm_kernels.hip; shared arithmetic in stereo_sgm_core.h); 0 bytes: beyond size_t
+size_t     stereo_sgm_ws_bytes(const gms_stereo_sgm_params& p, int n, int W, int H);
+hipError_t launch_stereo_sgm(const gms_stereo_sgm_params& p, const uint8_t* d_left, const uint8_t* d_right, int n, int W, int H, int pitch,
+                             void* d_ws, int16_t* d_disp, int32_t* d_cost, hipStream_t stream);
 // portrait mode (portrait_kernels.hip; shared parts in portrait_core.h)
 size_t     portrait_ws_bytes(int n, int W, int H);
 hipError_t launch_portrait(const gms_portrait_params& p, const uint8_t* d_bgr, const uint8_t* d_disp, int n, int W, int H, int pitch_bgr,

@@ -10,6 +10,8 @@
 //                          cost volume goes to HBM. The raw map goes to d_disp16, the costs to the workspace.
 //   sbm_validate_kernel    one workgroup per row: validateDisparity (a 64-bit LDS atomicMin of cost << 32 | x per target column), the
 //                          ROI fill, the final int16 row and the cost row.
+// launch_stereo_bm_prefilter and launch_stereo_bm_validate launch the first and the last alone: stereo_sgm_kernels.hip runs them
+// around its own kernels.
 // gms_stereo_bm_normalize_device: sbm_normalize_kernel, one workgroup per map (min / max, then NORM_MINMAX to 8 bits, 0 -> 255).
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -295,6 +297,23 @@ hipError_t launch_match(const MatchArgs& a, int n, hipStream_t stream)
 
 size_t stereo_bm_ws_bytes(int n, int W, int H) { return stereo_bm_layout(n, W, H).total; }
 
+hipError_t launch_stereo_bm_prefilter(const gms_stereo_bm_params& p, const uint8_t* d_left, const uint8_t* d_right, int n, int W, int H,
+                                      int pitch, uint8_t* pre, hipStream_t stream)
+{
+    hipLaunchKernelGGL(sbm_prefilter_kernel, dim3((uint32_t)((W + kPfX - 1) / kPfX), (uint32_t)((H + kPfY - 1) / kPfY), (uint32_t)(2 * n)),
+                       dim3(kPfBlock), 0, stream, d_left, d_right, (int64_t)pitch * H, pitch, W, H, p.pre_filter_cap, pre);
+    return hipGetLastError();
+}
+
+hipError_t launch_stereo_bm_validate(const gms_stereo_bm_params& p, int n, int W, int H, int16_t* d_disp, const int32_t* wcost,
+                                     int32_t* d_cost, hipStream_t stream)
+{
+    const sbm::Geometry g = sbm::geometry(p, W);
+    ValArgs v{d_disp, wcost, d_cost, W, H, g.w2, g.lofs, g.wx, g.none, g.filtered, p.disp12_max_diff, g.minX1, g.maxX1, g.roi_x0, g.roi_x1};
+    hipLaunchKernelGGL(sbm_validate_kernel, dim3((uint32_t)H, (uint32_t)n), dim3(kValBlock), 0, stream, v);
+    return hipGetLastError();
+}
+
 hipError_t launch_stereo_bm(const gms_stereo_bm_params& p, const uint8_t* d_left, const uint8_t* d_right, int n, int W, int H, int pitch,
                             void* d_ws, int16_t* d_disp, int32_t* d_cost, hipStream_t stream)
 {
@@ -304,9 +323,7 @@ hipError_t launch_stereo_bm(const gms_stereo_bm_params& p, const uint8_t* d_left
     uint8_t* pre = ws_ptr<uint8_t>(d_ws, L.pre);
     int32_t* cost = ws_ptr<int32_t>(d_ws, L.cost);
     if (!g.none) {
-        hipLaunchKernelGGL(sbm_prefilter_kernel, dim3((uint32_t)((W + kPfX - 1) / kPfX), (uint32_t)((H + kPfY - 1) / kPfY), (uint32_t)(2 * n)),
-                           dim3(kPfBlock), 0, stream, d_left, d_right, (int64_t)pitch * H, pitch, W, H, p.pre_filter_cap, pre);
-        hipError_t e = hipGetLastError();
+        hipError_t e = launch_stereo_bm_prefilter(p, d_left, d_right, n, W, H, pitch, pre, stream);
         if (e != hipSuccess) return e;
         MatchArgs a{pre, d_disp, cost, W, H, p.num_disparities, p.min_disparity, g.w2, p.pre_filter_cap, p.texture_threshold,
                     p.uniqueness_ratio, g.lofs, g.rofs, g.wx, g.filtered};
@@ -315,9 +332,7 @@ hipError_t launch_stereo_bm(const gms_stereo_bm_params& p, const uint8_t* d_left
             : nd <= 256 ? launch_match<4>(a, n, stream) : launch_match<8>(a, n, stream);
         if (e != hipSuccess) return e;
     }
-    ValArgs v{d_disp, cost, d_cost, W, H, g.w2, g.lofs, g.wx, g.none, g.filtered, p.disp12_max_diff, g.minX1, g.maxX1, g.roi_x0, g.roi_x1};
-    hipLaunchKernelGGL(sbm_validate_kernel, dim3((uint32_t)H, (uint32_t)n), dim3(kValBlock), 0, stream, v);
-    return hipGetLastError();
+    return launch_stereo_bm_validate(p, n, W, H, d_disp, cost, d_cost, stream);
 }
 
 hipError_t launch_stereo_bm_normalize(const int16_t* d_disp, int n, int W, int H, uint8_t* d_out, hipStream_t stream)

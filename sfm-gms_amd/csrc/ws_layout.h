@@ -241,6 +241,28 @@ inline StereoBmLayout stereo_bm_layout(int n, int W, int H)
     return {c.take(2 * px, 256), c.take(4 * px, 256), c.end};
 }
 
+// ---- semi-global matching (stereo_sgm_kernels.hip) ----------------------------------------------------------------------------------
+// ny x wx: the region StereoBM computes (rows [w2, H - w2), wx output columns; 0 x 0 when it computes nothing). The volumes take
+// 4 nd bytes per pixel of the region. total = 0: more than 2^50 pixels, so that no sum below can wrap.
+struct StereoSgmLayout {
+    StereoBmLayout bm;  // StereoBM's regions, unchanged: pre, and cost as the winner's S for the left-right check
+    size_t tex;         // int32 [n][ny][wx]: StereoBM's texture sums
+    size_t C;           // uint16 [n][ny][wx][nd]: the matching costs
+    size_t S;           // uint16 [n][ny][wx][nd]: the sum of the path costs. The first direction's launch writes it, the others add
+    size_t total;
+};
+inline StereoSgmLayout stereo_sgm_layout(int n, int W, int H, int ny, int wx, int nd)
+{
+    const StereoBmLayout B = stereo_bm_layout(n, W, H);
+    const size_t px = (size_t)n * (size_t)ny * (size_t)wx;  // n <= 65535, ny <= H < 2^31, wx <= 8192: below 2^60, no wrap in 64 bits
+    const bool fits = sizeof(size_t) >= 8 && px <= (SIZE_MAX >> 14) && B.total <= (SIZE_MAX >> 2);
+    const size_t vol = fits ? 2 * (size_t)nd * px : 0;      // nd <= 512: at most 2^10 px < 2^60
+    WsCursor c;
+    c.take(B.total, 256);
+    const size_t tex = c.take(4 * px, 256), C = c.take(vol, 256), S = c.take(vol, 256);
+    return {B, tex, C, S, fits ? c.end : 0};
+}
+
 // ---- portrait mode (portrait_kernels.hip) -------------------------------------------------------------------------------------------
 // Two pixels side by side are never both the root of a border, so a row holds at most (W + 1) / 2 of them. With equal values the two
 // are one component. Otherwise one is a hole's first pixel: the pixel above it is set (a zero there would be an earlier pixel of the

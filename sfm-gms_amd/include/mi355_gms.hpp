@@ -399,6 +399,39 @@ inline void stereo_match(const std::vector<uint8_t>& left, const std::vector<uin
     stereo_match(left, right, width, height, stereo_bm_reference_params(), disparity8);
 }
 
+// Semi-global matching on StereoBM's costs (include/gms.h) -- the library's own definition, not cv::StereoSGBM.
+// stereoSGM gives the int16 map (4 fractional bits), stereo_match_sgm the 8-bit map in stereo_match's form (normalised, 0 -> 255);
+// images and maps as above. Both run one pair synchronously on the current HIP device (gms_stereo_sgm).
+inline gms_stereo_sgm_params stereo_sgm_reference_params()
+{
+    const gms_stereo_sgm_params p = GMS_STEREO_SGM_PARAMS_REFERENCE;
+    return p;
+}
+
+inline void stereoSGM(const std::vector<uint8_t>& left, const std::vector<uint8_t>& right, int width, int height,
+                      const gms_stereo_sgm_params& params, std::vector<int16_t>& disparity16)
+{
+    detail::stereo_check(left, right, width, height);
+    disparity16.assign((size_t)width * (size_t)height, 0);
+    const int rc = gms_stereo_sgm(&params, left.data(), right.data(), width, height, width, disparity16.data(), nullptr, nullptr);
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::stereoSGM: ") + gms_error_string(rc));
+}
+
+inline void stereo_match_sgm(const std::vector<uint8_t>& left, const std::vector<uint8_t>& right, int width, int height,
+                             const gms_stereo_sgm_params& params, std::vector<uint8_t>& disparity8)
+{
+    detail::stereo_check(left, right, width, height);
+    disparity8.assign((size_t)width * (size_t)height, 0);
+    const int rc = gms_stereo_sgm(&params, left.data(), right.data(), width, height, width, nullptr, nullptr, disparity8.data());
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::stereo_match_sgm: ") + gms_error_string(rc));
+}
+
+inline void stereo_match_sgm(const std::vector<uint8_t>& left, const std::vector<uint8_t>& right, int width, int height,
+                             std::vector<uint8_t>& disparity8)
+{
+    stereo_match_sgm(left, right, width, height, stereo_sgm_reference_params(), disparity8);
+}
+
 // The image tail of the reference's createPortraitMode (DisparityUtil.cpp:317-412): img = the photograph as flat row-major BGR bytes
 // (3 * width * height, cv::Mat's layout after imread), disparity = an 8-bit map with 255 = no value (what gms_disparity_device and
 // stereo_match write); out receives the portrait image in img's layout. medianBlur is cv::medianBlur for 1 or 3 interleaved channels

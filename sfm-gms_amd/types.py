@@ -49,6 +49,29 @@ def stereo_bm_params(params=None, **kw):
     return rec
 
 
+# gms_stereo_sgm_params (include/gms.h): StereoBM's eleven, then p1, p2, n_paths
+STEREO_SGM_PARAMS_DTYPE = np.dtype([(n, "<i4") for n in STEREO_BM_PARAMS_DTYPE.names + ("p1", "p2", "n_paths")])
+assert STEREO_SGM_PARAMS_DTYPE.itemsize == 56
+
+
+def stereo_sgm_params(params=None, **kw):
+    """A one-record STEREO_SGM_PARAMS_DTYPE array: the reference's StereoBM values, eight paths, p1 = 8 block_size^2 and
+    p2 = 32 block_size^2 unless given (None means the default), updated from params (a dict or a record) and keywords."""
+    vals = {}
+    if params is not None:
+        vals.update(params if isinstance(params, dict) else {n: int(np.asarray(params).reshape(-1)[0][n]) for n in STEREO_SGM_PARAMS_DTYPE.names})
+    vals.update(kw)
+    own = {k: vals.pop(k, None) for k in ("p1", "p2", "n_paths")}
+    rec = np.zeros(1, STEREO_SGM_PARAMS_DTYPE)
+    bm = stereo_bm_params(vals)
+    for n in STEREO_BM_PARAMS_DTYPE.names:
+        rec[n] = bm[n]
+    bs2 = int(bm["block_size"][0]) ** 2
+    rec["p1"] = 8 * bs2 if own["p1"] is None else int(own["p1"])
+    rec["p2"] = 32 * bs2 if own["p2"] is None else int(own["p2"])
+    rec["n_paths"] = 8 if own["n_paths"] is None else int(own["n_paths"])
+    return rec
+
 # gms_portrait_params (include/gms.h): portrait mode's parameters, four int32 in this order; the reference's values
 # (DisparityUtil.cpp:341, :351, :380, :394)
 PORTRAIT_PARAMS_DTYPE = np.dtype([(n, "<i4") for n in ("threshold", "dilate_iterations", "num_contours", "median_ksize")])

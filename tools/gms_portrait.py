@@ -7,6 +7,7 @@
 
 pair.npz holds left_bgr [H, W, 3] and right_grey [H, W] (default: the committed reduced robot pair, tests/golden/image_portrait_robot.npz).
 --disparity bm       the project's stereo_match map of the pair (StereoBM with the reference's parameters, normalised, 0 -> 255)
+--disparity sgm      the same form from semi-global matching on StereoBM's costs (stereo_match_sgm)
 --disparity matches  detector -> matcher -> matchGMS -> gms_disparity_device (tools/gms_image_pair.py, run as a child process); 255 = no match,
                      which is the map createPortraitMode itself starts from. There is no SIFT here, so the keypoints are the project's own.
 --disparity FILE.npy any uint8 [H, W] map, 255 = no value
@@ -56,6 +57,8 @@ def main():
     pkg = importlib.import_module("sfm-gms_amd")
     if a.disparity == "bm":
         disparity = pkg.stereo_match(left, right)
+    elif a.disparity == "sgm":
+        disparity = pkg.stereo_match_sgm(left, right)
     elif a.disparity != "matches":
         disparity = np.ascontiguousarray(np.load(a.disparity), dtype=np.uint8)
     kw = dict(threshold=a.threshold, dilate_iterations=a.dilate, num_contours=a.contours, median_ksize=a.ksize)
