@@ -1,6 +1,8 @@
 """Inputs of the semi-global matching tests: every disparity count at which the kernels' lane layout changes, the
-shortest paths, regions whose diagonals start on each edge, exact ties of the summed cost across lanes, sums in the upper half of the
-unsigned 16-bit range, the penalty extremes, and StereoBM's rules (uniqueness, left-right check, minimum disparity) on the sums.
+shortest paths, block sizes 7, 9, 21 and 51 across the cost kernel's tile and band seams, its largest LDS request, disparity ranges
+wholly below 0, sloped winners at both ends of the range, a partial texture cut, regions whose diagonals start on each edge, exact
+ties of the summed cost across lanes, sums in the upper half of the unsigned 16-bit range, the penalty extremes, and StereoBM's rules
+(uniqueness, left-right check, minimum disparity) on the sums.
 case(name) returns (left, right, params); expected(name) the statement's (disp, cost), computed once; census(left, right, **params)
 counts on the statement's own pieces what a case is named for. tests/test_stereo_sgm_ref.py asserts FLOORS from the census on the
 CPU, and tests/test_gpu_stereo_sgm.py holds the GPU to the statement's bytes on the same inputs.
@@ -17,7 +19,9 @@ import stereo_bm_ref as B
 import stereo_sgm_ref as R
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "image_stereo_pair_450x375.npz")
-ND_SWEEP = (16, 48, 64, 80, 272, 512)    # part of a wave; one full set of lanes; a partly filled last register slot; the most
+# part of a wave; one full set of cost lanes; a partly filled last register slot; every lane of the path and decision kernels active at
+# the run lengths 2 and 4 (128, 256); the first count of run length 8; the most
+ND_SWEEP = (16, 48, 64, 80, 128, 256, 272, 512)
 
 
 def _smooth(name, h, w):
@@ -66,6 +70,30 @@ def _lr(maxdiff):
     return left, right, dict(num_disparities=32, min_disparity=0, texture_threshold=0, disp12_max_diff=maxdiff)
 
 
+def _block(name, bs, ny, wx, nd=16, shifts=(2, 9), **kw):
+    """A two-shift pair whose computed region is ny x wx with nd disparities from 0 and block size bs. The texture threshold is the
+    reference's, unless given."""
+    left, right = _two_shifts(name, ny + bs - 1, wx + nd - 1, *shifts)
+    return left, right, dict(num_disparities=nd, min_disparity=0, block_size=bs, **kw)
+
+
+def _negative(name, h, w, nd, md, s_top, s_bottom):
+    """A range at or below 0: the right image is the left shifted the other way, np.roll(left, +s), so the true disparities are -s_top
+    and -s_bottom."""
+    left, right = _two_shifts(name, h, w, -s_top, -s_bottom)
+    return left, right, dict(num_disparities=nd, min_disparity=md, texture_threshold=0)
+
+
+def _ends():
+    left, right = _two_shifts("ends", 44, 75, 0, 15)
+    return left, right, dict(num_disparities=16, min_disparity=0, texture_threshold=0, uniqueness_ratio=0)
+
+
+def _bs51_nd512(**kw):
+    left, right = _two_shifts("bs51_nd512", 60, 583, 0, 400)
+    return left, right, dict(num_disparities=512, min_disparity=0, block_size=51, texture_threshold=0, p1=200, **kw)
+
+
 BUILDERS = {
     # the shortest paths: two rows (H = block_size + 1), and one column (wx = 1)
     "two_rows": lambda: _region("two_rows", 2, 45),
@@ -98,6 +126,25 @@ BUILDERS = {
     "md_positive": lambda: _md(5),
     # GMS_STEREO_BM_MAX_WIDTH: the longest horizontal paths, the shortest vertical ones
     "widest": lambda: _bm_case("widest"),
+    # block sizes past 5 in the cost kernel. A region of 33 x 65 (34 x 66) is one row (two) into the second 32-row band and one column
+    # (two) into the second 64-column tile: 8 (49 * 122 + 1568) = 60 368; 8 (81 * 62 + 2592) = 60 912 (cap 61 is rejected at block 9)
+    "bs7_seams": lambda: _block("bs7_seams", 7, 33, 65),
+    "bs9_seams": lambda: _block("bs9_seams", 9, 33, 65, pre_filter_cap=31),
+    "bs21": lambda: _block("bs21", 21, 20, 89, nd=32, shifts=(3, 25), pre_filter_cap=3, p1=100, p2=1000),
+    "bs51_seams": lambda: _block("bs51_seams", 51, 34, 66, pre_filter_cap=1, texture_threshold=0, p1=200, p2=2000),
+    # the cost kernel's largest LDS request, (32 + 50) (128 + 100 + 511) = 60 598 bytes, with the last accepted p2 of 8 and of 4 paths:
+    # 8 (2601 * 2 + 2989) = 65 528, 4 (2601 * 6 + 777) = 65 532
+    "bs51_nd512": lambda: _bs51_nd512(pre_filter_cap=1, p2=2989),
+    "bs51_nd512_four": lambda: _bs51_nd512(pre_filter_cap=3, p2=777, n_paths=4),
+    # ranges wholly below 0 (rofs = -(nd - 1 + md) > 0, lofs = 0: the region starts at column 0), and nd - 1 + md = 0: both offsets 0
+    "rofs_5": lambda: _negative("rofs_5", 30, 90, 16, -20, 6, 18),
+    "rofs_1": lambda: _negative("rofs_1", 30, 110, 32, -32, 4, 27),
+    "offsets_zero": lambda: _negative("offsets_zero", 30, 110, 32, -31, 2, 26),
+    # winners at k = nd - 1 (disparity 0, the upper half) and at k = 0 (disparity 15) whose one neighbour differs from them: the subpixel
+    # step's mirrored neighbour decides the map
+    "ends": _ends,
+    # StereoBM's case: the texture rule cuts the flat part and leaves the rest
+    "half_flat": lambda: _bm_case("half_flat"),
 }
 for _n in ND_SWEEP:
     BUILDERS[f"nd_{_n}"] = functools.partial(_nd, _n)
@@ -169,6 +216,10 @@ def census(left, right, **kw):
                winners_high=int((accepted & (mind >= nd // 2)).sum()),
                last_lane_wins=int((accepted & (lane[mind] == lane[-1])).sum()),
                moved_by_paths=int((mind != dec["C"].argmin(axis=2)).sum()),
+               lofs=B.ranges(p, W)[0], rofs=B.ranges(p, W)[1],
+               texture_cut=int((~dec["tex_ok"]).sum()),
+               winner_first_sloped=int((accepted & (mind == 0) & (S[:, :, 1] != S[:, :, 0])).sum()),
+               winner_last_sloped=int((accepted & (mind == nd - 1) & (S[:, :, nd - 2] != S[:, :, nd - 1])).sum()),
                lr_removed=0)
     if p["disp12_max_diff"] >= 0:
         checked = disp.copy()
@@ -204,9 +255,22 @@ FLOORS = {
     "md_zero": dict(winners_low=1, winners_high=1),
     "md_positive": dict(winners_low=1, winners_high=1),
     "widest": dict(wx=("==", B.MAX_WIDTH - 15), accepted=1000),
+    "bs7_seams": dict(ny=("==", 33), wx=("==", 65), winners_low=100, winners_high=100, upper_half_share=0.3),
+    "bs9_seams": dict(ny=("==", 33), wx=("==", 65), winners_low=100, winners_high=100),
+    "bs21": dict(ny=("==", 20), wx=("==", 89), winners_low=100, winners_high=100),
+    "bs51_seams": dict(ny=("==", 34), wx=("==", 66), winners_low=100, winners_high=100),
+    "bs51_nd512": dict(ny=("==", 10), wx=("==", 72), upper_half_share=0.5, winners_low=20, winners_high=20, winner_last_sloped=20),
+    "bs51_nd512_four": dict(ny=("==", 10), wx=("==", 72), upper_half_share=0.5, winners_low=20, winners_high=20, winner_last_sloped=20),
+    "rofs_5": dict(rofs=("==", 5), lofs=("==", 0), ny=("==", 26), wx=("==", 70), winners_low=100, winners_high=100),
+    "rofs_1": dict(rofs=("==", 1), lofs=("==", 0), winners_low=100, winners_high=100),
+    "offsets_zero": dict(rofs=("==", 0), lofs=("==", 0), winners_low=100, winners_high=100),
+    "ends": dict(winner_first_sloped=200, winner_last_sloped=200),
+    "half_flat": dict(texture_cut=500, accepted=500),
 }
 for _n in ND_SWEEP:
     FLOORS[f"nd_{_n}"] = dict(winners_low=1, winners_high=1, last_lane_wins=1 if _n > 16 else 0)
+for _n in (128, 256):      # every lane active: lane 63 owns the winner, next to a value that differs from it
+    FLOORS[f"nd_{_n}"].update(last_lane_wins=50, winner_last_sloped=5)
 
 
 def check_floors(name, got):

@@ -1,8 +1,8 @@
 """-m gpu: semi-global matching on StereoBM's costs (gms_stereo_sgm_device, gms_stereo_sgm) -- the int16 map and the
 cost byte for byte against the CPU statement tests/stereo_sgm_ref.py: the committed pair with 8 and 4 paths, the named cases of
-tests/stereo_sgm_cases.py (whose content the CPU suite asserts), batches, a padded pitch, an exact workspace with guard bytes, zero
-penalties against gms_stereo_bm_device on the device, graph replay, the one-shot calls on host arrays and device tensors, and rejected
-parameters. On a difference a test names the first differing pixel."""
+tests/stereo_sgm_cases.py (whose content the CPU suite asserts), batches, a padded pitch (two pairs at block size 5, three at 9), an
+exact workspace with guard bytes, zero penalties against gms_stereo_bm_device on the device, graph replay, the one-shot calls on host
+arrays and device tensors, and rejected parameters. On a difference a test names the first differing pixel."""
 import importlib
 
 import numpy as np
@@ -46,7 +46,7 @@ def test_named_cases_equal_statement(pkg, name):
     _assert_same(got_d, want_d, (name, "disparity"))
 
 
-@pytest.mark.parametrize("name", ["const", "lr_0"])
+@pytest.mark.parametrize("name", ["const", "lr_0", "rofs_5"])
 def test_eight_bit_map(pkg, name):
     left, right, kw = C.case(name)
     want = B.normalize_u8(C.expected(name)[0])
@@ -98,7 +98,36 @@ def test_padded_pitch(ctx):
         assert with_cost or not bool(d_cost.any())      # no cost map asked for: none written
 
 
-@pytest.mark.parametrize("name", ["widest", "nd_512", "diag_tall"])
+def test_three_pairs_at_block_9_with_padded_pitch(ctx):
+    """bs9_seams' parameters through gms_stereo_sgm_device with n = 3 and pitch = W + 37: the case, the case with left and right
+    exchanged, and the case upside down, side by side in the cost kernel's blockIdx.z over random padding."""
+    import torch
+    left, right, kw = C.case("bs9_seams")
+    H, W = left.shape
+    pad = 37
+    pairs = [(left, right), (right, left), (np.ascontiguousarray(left[::-1]), np.ascontiguousarray(right[::-1]))]
+    want = [C.expected("bs9_seams")] + [R.stereo_sgm(l, r, **kw) for l, r in pairs[1:]]
+    assert len({w[0].tobytes() for w in want}) == 3
+    rng = np.random.default_rng(9)
+    rows_l = rng.integers(0, 256, (3, H, W + pad)).astype(np.uint8)
+    rows_r = rng.integers(0, 256, (3, H, W + pad)).astype(np.uint8)
+    for i, (l, r) in enumerate(pairs):
+        rows_l[i, :, :W], rows_r[i, :, :W] = l, r
+    d_l, d_r = torch.from_numpy(rows_l).cuda(), torch.from_numpy(rows_r).cuda()
+    ws_bytes = ctx.stereo_sgm_workspace_bytes(W, H, 3, kw)
+    assert ws_bytes > 0
+    ws = torch.zeros(ws_bytes, dtype=torch.uint8, device="cuda")
+    d_disp = torch.zeros((3, H, W), dtype=torch.int16, device="cuda")
+    d_cost = torch.zeros((3, H, W), dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    ctx.stereo_sgm_device(kw, d_l.data_ptr(), d_r.data_ptr(), 3, W, H, W + pad, ws.data_ptr(), ws_bytes, d_disp.data_ptr(), d_cost.data_ptr())
+    ctx.synchronize()
+    for i in range(3):
+        _assert_same(d_cost[i].cpu().numpy(), want[i][1], ("block 9", i, "cost"))
+        _assert_same(d_disp[i].cpu().numpy(), want[i][0], ("block 9", i, "disparity"))
+
+
+@pytest.mark.parametrize("name", ["widest", "nd_512", "diag_tall", "bs51_nd512", "rofs_5"])
 def test_workspace_exact(ctx, name):
     """A workspace of exactly gms_stereo_sgm_workspace_bytes with 256 guard bytes behind it, filled with a pattern before the run."""
     import torch
@@ -121,7 +150,8 @@ def test_workspace_exact(ctx, name):
     _assert_same(d_disp.cpu().numpy(), want_d, (name, "disparity"))
 
 
-@pytest.mark.parametrize("name,n_paths", [("diag_wide", 8), ("md_positive", 4), ("stripes64", 8)])
+@pytest.mark.parametrize("name,n_paths", [("diag_wide", 8), ("md_positive", 4), ("stripes64", 8), ("bs7_seams", 8), ("bs21", 8), ("rofs_5", 4),
+                                          ("bs51_nd512_four", 4)])
 def test_zero_penalties_equal_stereo_bm_on_the_device(ctx, name, n_paths):
     """p1 = p2 = 0, uniqueness_ratio = 0: gms_stereo_bm_device's map byte for byte, and n_paths times its cost."""
     left, right, kw = C.case(name)
@@ -196,6 +226,21 @@ def test_bad_params_rejected_before_launch(ctx, pkg):
         assert e.value.code == -1, kw
         assert ctx.stereo_sgm_workspace_bytes(64, 40, 1, kw) == 0, kw
     assert ctx.stereo_sgm_workspace_bytes(64, 40, 1, dict(pre_filter_cap=63, p2=5041)) > 0
+    # block 9 with the default cap and penalties: 8 (81 * 122 + 2592) is past 65535; with cap 31 it is 60 912
+    with pytest.raises(types.GmsError) as e:
+        pkg.stereoSGM(img, img, block_size=9)
+    assert e.value.code == -1
+    assert ctx.stereo_sgm_workspace_bytes(64, 40, 1, dict(block_size=9)) == 0
+    assert ctx.stereo_sgm_workspace_bytes(64, 40, 1, dict(block_size=9, pre_filter_cap=31)) > 0
+    # block 51 at cap 1 with 8 paths: 8 (2601 * 2 + 2989) = 65 528 is the last accepted p2
+    tall = np.zeros((60, 64), np.uint8)
+    at = dict(block_size=51, pre_filter_cap=1, p1=200, p2=2989)
+    assert ctx.stereo_sgm_workspace_bytes(64, 60, 1, at) > 0
+    assert pkg.stereoSGM(tall, tall, **at).shape == tall.shape
+    with pytest.raises(types.GmsError) as e:
+        pkg.stereoSGM(tall, tall, **dict(at, p2=2990))
+    assert e.value.code == -1
+    assert ctx.stereo_sgm_workspace_bytes(64, 60, 1, dict(at, p2=2990)) == 0
     assert ctx.stereo_sgm_workspace_bytes(8192, 2 ** 31 - 1, 65535) == 0          # beyond size_t
     d = torch.zeros(64 * 40 * 2, dtype=torch.uint8, device="cuda")
     ws = torch.zeros(ctx.stereo_sgm_workspace_bytes(64, 40, 1), dtype=torch.uint8, device="cuda")

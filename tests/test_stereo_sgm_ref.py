@@ -79,7 +79,7 @@ def test_hand_worked_path():
 
 
 # ---- the two forms and the host build ---------------------------------------------------------------------------------------------
-# nd, md, block_size, cap, texture, uniqueness, disp12, p1, p2, n_paths
+# nd, md, block_size, cap, texture, uniqueness, disp12, p1, p2, n_paths[, the true disparity of the pair: -3 where not given]
 SWEEP = [
     (16, 0, 5, 61, 0, 0, 1, None, None, 8),
     (16, -4, 5, 61, 0, 0, 1, None, None, 4),
@@ -88,21 +88,26 @@ SWEEP = [
     (32, -20, 5, 63, 507, 0, 2, 5041, 5041, 8),
     (16, 0, 9, 7, 0, 5, 1, 7, 900, 4),
     (16, 0, 5, 61, 0, 0, 1, 0, 0, 8),
+    (16, -20, 5, 61, 0, 0, 1, None, None, 8, -12),   # md <= -nd: rofs = 5, lofs = 0
+    (16, -15, 5, 61, 0, 0, 1, None, None, 8, -7),    # md = -(nd - 1): both offsets 0
 ]
 
 
-def _sweep_pair(h, w, seed):
+def _sweep_pair(h, w, seed, disparity=-3):
+    """right[x] = left[x + disparity] plus noise, cut from one wider image: `disparity` is at most 0."""
     rng = np.random.default_rng(seed)
-    left = cases._smooth(f"sweep{seed}", h, w + 8)
-    right = np.clip(left[:, 8 - 3:w + 8 - 3].astype(np.int32) + rng.integers(-3, 4, (h, w)), 0, 255).astype(np.uint8)
-    return np.ascontiguousarray(left[:, 8:]), right
+    m = max(8, -disparity)
+    left = cases._smooth(f"sweep{seed}", h, w + m)
+    right = np.clip(left[:, m + disparity:w + m + disparity].astype(np.int32) + rng.integers(-3, 4, (h, w)), 0, 255).astype(np.uint8)
+    return np.ascontiguousarray(left[:, m:]), right
 
 
 @pytest.mark.parametrize("shape", [(19, 44), (20, 45)])
 @pytest.mark.parametrize("case", range(len(SWEEP)))
 def test_loop_vectorised_and_host_agree(host, shape, case):
-    nd, md, bs, cap, tex, ur, dmd, p1, p2, n_paths = SWEEP[case]
-    left, right = _sweep_pair(*shape, seed=case)
+    nd, md, bs, cap, tex, ur, dmd, p1, p2, n_paths, *true = SWEEP[case]
+    left, right = _sweep_pair(*shape, case, *true)
+    assert not true or md <= true[0] < md + nd
     kw = dict(num_disparities=nd, min_disparity=md, block_size=bs, pre_filter_cap=cap, texture_threshold=tex, uniqueness_ratio=ur,
               disp12_max_diff=dmd, p1=p1, p2=p2, n_paths=n_paths)
     want = R.stereo_sgm_loop(left, right, **kw)
@@ -110,9 +115,12 @@ def test_loop_vectorised_and_host_agree(host, shape, case):
         assert got[0].dtype == np.int16 and got[1].dtype == np.int32
         assert (got[0] == want[0]).all() and (got[1] == want[1]).all(), kw
     assert (want[0] != B.filtered_value(R.make_params(**kw))).any() or tex == 507, kw
+    lofs, rofs = B.ranges(R.make_params(**kw), shape[1])[:2]
+    assert (lofs, rofs) == (max(nd - 1 + md, 0), max(-(nd - 1 + md), 0))
 
 
-@pytest.mark.parametrize("name", ["diag_wide", "diag_tall", "two_rows", "one_column", "unsigned_range", "stripes8", "nd_80"])
+@pytest.mark.parametrize("name", ["diag_wide", "diag_tall", "two_rows", "one_column", "unsigned_range", "stripes8", "nd_80", "bs7_seams",
+                                  "rofs_5", "offsets_zero", "ends", "bs51_seams"])
 def test_host_build_on_named_cases(host, name):
     left, right, kw = cases.case(name)
     got = _host_maps(host, left, right, **kw)
@@ -130,7 +138,7 @@ def test_sanitizer_run_of_the_stand_alone_program(tmp_path):
 
 # ---- properties -------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n_paths", [4, 8])
-@pytest.mark.parametrize("name", ["diag_wide", "md_negative", "stripes8", "lr_0"])
+@pytest.mark.parametrize("name", ["diag_wide", "md_negative", "stripes8", "lr_0", "rofs_5", "bs7_seams", "bs21"])
 def test_zero_penalties_reproduce_stereo_bm(name, n_paths):
     left, right, kw = cases.case(name)
     kw = {k: v for k, v in kw.items() if k in B.PARAM_NAMES}
