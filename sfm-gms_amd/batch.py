@@ -254,6 +254,11 @@ def detect_images(ctx, images, threshold=20, max_keypoints=10000, device=None):
 
 DESCRIPTORS = ("brief", "grad", "both")
 DETECTORS = ("fast", "dog")
+# (detector, refine, 128-float rows) -> the stem of the Context's <stem>_workspace_bytes and <stem>_batch_device; every entry point
+# but detect_pyramid_batch_device ends with d_rows128 (None to the DoG calls: no such rows)
+_PYRAMID_CALLS = {("fast", False, False): "detect_pyramid", ("fast", False, True): "detect_pyramid_grad",
+                  ("dog", False, False): "detect_dog", ("dog", False, True): "detect_dog",
+                  ("dog", True, False): "detect_dog_refined", ("dog", True, True): "detect_dog_refined"}
 
 
 class DetectPyramid:
@@ -277,11 +282,9 @@ class DetectPyramid:
         self.ctx, self.n, self.w, self.h, self.descriptor, self.detector = ctx, int(n), int(w), int(h), descriptor, detector
         self.threshold, self.max_keypoints, self.n_levels, self.contrast = int(threshold), int(max_keypoints), int(n_levels), int(contrast)
         dev = _device(ctx, device)
-        if detector == "dog":
-            size = ctx.detect_dog_refined_workspace_bytes if self.refine else ctx.detect_dog_workspace_bytes
-        else:
-            size = ctx.detect_pyramid_workspace_bytes if descriptor == "brief" else ctx.detect_pyramid_grad_workspace_bytes
-        self.ws_bytes = size(w, h, n, max_keypoints, n_levels)
+        stem = _PYRAMID_CALLS[detector, self.refine, descriptor != "brief"]
+        self._call, self._takes_rows128 = getattr(ctx, stem + "_batch_device"), stem != "detect_pyramid"
+        self.ws_bytes = getattr(ctx, stem + "_workspace_bytes")(w, h, n, max_keypoints, n_levels)
         if self.ws_bytes == 0:
             raise ValueError("bad image size, keypoint count or number of levels")
         self.d_ws = torch.zeros(self.ws_bytes, dtype=torch.uint8, device=dev)
@@ -297,13 +300,9 @@ class DetectPyramid:
         strength = self.contrast if self.detector == "dog" else self.threshold
         args = (d_images.data_ptr(), self.n, self.w, self.h, strength, self.max_keypoints, self.n_levels, self.d_ws.data_ptr(), self.ws_bytes,
                 self.d_kp.data_ptr(), self.d_desc.data_ptr(), self.d_counts.data_ptr(), self.d_level_counts.data_ptr())
-        if self.detector == "dog":
-            call = self.ctx.detect_dog_refined_batch_device if self.refine else self.ctx.detect_dog_batch_device
-            call(*args, None if self.d_rows128 is None else self.d_rows128.data_ptr())
-        elif self.d_rows128 is None:
-            self.ctx.detect_pyramid_batch_device(*args)
-        else:
-            self.ctx.detect_pyramid_grad_batch_device(*args, self.d_rows128.data_ptr())
+        if self._takes_rows128:
+            args += (None if self.d_rows128 is None else self.d_rows128.data_ptr(),)
+        self._call(*args)
 
     def results(self):
         """On the host: (keypoints_per_image, rows_per_image, level_counts [n, n_levels]); rows_per_image are the uint8 [n_i, 32] rows for

@@ -292,7 +292,8 @@ struct LevelOut {
     const int32_t* level_counts;   // [level][image]: survivors of the levels (this level's row is `counts`)
     int level, n_images, out_stride;
     float fx, fy;                  // (float)w_0 / (float)w_level, (float)h_0 / (float)h_level
-    const uint16_t* codes;         // kFromLevelRefined: the level's plane of dog_core.h's refinement codes, [image][h][w]
+    uint16_t* codes;               // kFromLevelRefined: the level's plane of dog_core.h's refinement codes, [image][h][w] (detect_level has
+                                   // dog_maps_kernel<true> write it; the describe kernel only reads it)
 };
 
 template <int MODE>
@@ -496,12 +497,18 @@ DetWs carve(void* ws, int w, int h, int n_images, int max_keypoints)
             ws_ptr<int32_t>(ws, L.cut), ws_ptr<uint32_t>(ws, L.rows), ws_ptr<uint32_t>(ws, L.list), L.cut - L.hist};
 }
 
-// the detector on one set of equally sized images: the single-scale call (lo == nullptr; clears its histogram itself) or one level of the
-// pyramid (lo and the level's histogram, already cleared). dog_contrast >= 0: the candidates are the DoG detector's (dog_kernels.hip,
-// DESIGN.md section 4.7d) and `threshold` is not read; what follows the candidate plane is the same.
-hipError_t detect_level(const uint8_t* d_images, int n_images, int w, int h, int threshold, int max_keypoints, void* d_ws, gms_keypoint* d_kp,
-                        uint8_t* d_desc, int32_t* d_counts, const LevelOut* lo, uint32_t* level_hist, hipStream_t stream, int dog_contrast = -1,
-                        uint16_t* d_codes = nullptr)   // d_codes (with lo and dog_contrast >= 0): the records are refined through this plane
+// FAST scores and box sums of a batch
+void launch_maps(const uint8_t* d_images, int n_images, int w, int h, const DetWs& ws, hipStream_t stream)
+{
+    hipLaunchKernelGGL(det_maps_kernel, dim3((w + kTileW - 1) / kTileW, (h + kTileH - 1) / kTileH, n_images), dim3(256), 0, stream, d_images, w, h,
+                       ws.score, ws.box);
+}
+
+// the detector on one set of equally sized images: the single-scale call (lo == nullptr; clears its histogram itself; never refined) or one
+// level of the pyramid (lo and the level's histogram, already cleared; refined records go through lo->codes). With the DoG detector the
+// candidates are dog_kernels.hip's; what follows the candidate plane is the same.
+hipError_t detect_level(const PyramidRun& run, const uint8_t* d_images, int n_images, int w, int h, int max_keypoints, void* d_ws, gms_keypoint* d_kp,
+                        uint8_t* d_desc, int32_t* d_counts, const LevelOut* lo, uint32_t* level_hist, hipStream_t stream)
 {
     DetWs ws = carve(d_ws, w, h, n_images, max_keypoints);
     if (level_hist != nullptr) {
@@ -510,14 +517,13 @@ hipError_t detect_level(const uint8_t* d_images, int n_images, int w, int h, int
         hipError_t e = hipMemsetAsync(ws.hist, 0, ws.hist_bytes, stream);
         if (e != hipSuccess) return e;
     }
-    if (dog_contrast >= 0) {
-        hipError_t e = d_codes != nullptr ? launch_dog_maps_refine(d_images, n_images, w, h, dog_contrast, ws.cand, ws.box, ws.hist, d_codes, stream)
-                                          : launch_dog_maps(d_images, n_images, w, h, dog_contrast, ws.cand, ws.box, ws.hist, stream);
+    const bool refined = run.refined && lo != nullptr;
+    if (run.detector == PyramidRun::kDog) {
+        hipError_t e = launch_dog_maps(d_images, n_images, w, h, run.strength, ws.cand, ws.box, ws.hist, refined ? lo->codes : nullptr, stream);
         if (e != hipSuccess) return e;
     } else {
-        hipLaunchKernelGGL(det_maps_kernel, dim3((w + kTileW - 1) / kTileW, (h + kTileH - 1) / kTileH, n_images), dim3(256), 0, stream, d_images, w, h,
-                           ws.score, ws.box);
-        hipLaunchKernelGGL(det_nms_kernel, dim3((w + 63) / 64, (h + 3) / 4, n_images), dim3(256), 0, stream, ws.score, w, h, threshold, ws.cand, ws.hist);
+        launch_maps(d_images, n_images, w, h, ws, stream);
+        hipLaunchKernelGGL(det_nms_kernel, dim3((w + 63) / 64, (h + 3) / 4, n_images), dim3(256), 0, stream, ws.score, w, h, run.strength, ws.cand, ws.hist);
     }
     hipLaunchKernelGGL(det_cut_kernel, dim3(n_images), dim3(256), 0, stream, ws.hist, max_keypoints, ws.cut, d_counts);
     hipLaunchKernelGGL(det_rows_kernel, dim3(h, n_images), dim3(64), 0, stream, ws.cand, w, h, ws.cut, ws.rows);
@@ -525,7 +531,7 @@ hipError_t detect_level(const uint8_t* d_images, int n_images, int w, int h, int
     hipLaunchKernelGGL(det_emit_kernel, dim3(h, n_images), dim3(64), 0, stream, ws.cand, w, h, ws.cut, ws.rows, max_keypoints, ws.list);
     if (max_keypoints > 0) {
         const dim3 grid((max_keypoints + 3) / 4, n_images);
-        if (lo != nullptr && d_codes != nullptr)
+        if (refined)
             hipLaunchKernelGGL(det_describe_kernel<kFromLevelRefined>, grid, dim3(256), 0, stream, d_images, ws.box, w, h, ws.list, d_counts,
                                max_keypoints, d_kp, d_desc, (int32_t*)nullptr, *lo);
         else if (lo != nullptr)
@@ -543,16 +549,15 @@ hipError_t launch_detect(const uint8_t* d_images, int n_images, int w, int h, in
                          gms_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, hipStream_t stream)
 {
     if (n_images <= 0) return hipSuccess;
-    return detect_level(d_images, n_images, w, h, threshold, max_keypoints, d_ws, d_kp, d_desc, d_counts, nullptr, nullptr, stream);
+    return detect_level({PyramidRun::kFast, threshold, false}, d_images, n_images, w, h, max_keypoints, d_ws, d_kp, d_desc, d_counts, nullptr, nullptr,
+                        stream);
 }
 
 // FAST scores and box sums of a batch alone, into a detect_layout workspace (what the gradient descriptor's compute() starts from)
 hipError_t launch_detect_maps(const uint8_t* d_images, int n_images, int w, int h, void* d_ws, hipStream_t stream)
 {
     if (n_images <= 0) return hipSuccess;
-    const DetWs ws = carve(d_ws, w, h, n_images, 0);
-    hipLaunchKernelGGL(det_maps_kernel, dim3((w + kTileW - 1) / kTileW, (h + kTileH - 1) / kTileH, n_images), dim3(256), 0, stream, d_images, w, h,
-                       ws.score, ws.box);
+    launch_maps(d_images, n_images, w, h, carve(d_ws, w, h, n_images, 0), stream);
     return hipGetLastError();
 }
 
@@ -564,7 +569,7 @@ hipError_t launch_describe(const uint8_t* d_image, int w, int h, gms_keypoint* d
     const DetWs ws = carve(d_ws, w, h, 1, 0);
     hipError_t e = hipMemsetAsync(d_status, 0, 4, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(det_maps_kernel, dim3((w + kTileW - 1) / kTileW, (h + kTileH - 1) / kTileH, 1), dim3(256), 0, stream, d_image, w, h, ws.score, ws.box);
+    launch_maps(d_image, 1, w, h, ws, stream);
     if (n > 0)
         hipLaunchKernelGGL(det_describe_kernel<kAtRecords>, dim3((n + 3) / 4, 1), dim3(256), 0, stream, d_image, ws.box, w, h, (const uint32_t*)nullptr,
                            (const int32_t*)nullptr, n, d_kp, d_desc, d_status, LevelOut{});
@@ -602,32 +607,25 @@ hipError_t launch_pyramid_build(const uint8_t* d_images, int n_images, int w, in
     return hipGetLastError();
 }
 
-size_t detect_pyramid_workspace_bytes(int w, int h, int n_images, int max_keypoints, int n_levels)
+size_t detect_pyramid_workspace_bytes(int w, int h, int n_images, int max_keypoints, int n_levels, bool refined)
 {
     if (detect_workspace_bytes(w, h, n_images, max_keypoints) == 0 || n_levels < 1 || n_levels > kPyramidMaxLevels) return 0;
-    return pyramid_layout(w, h, n_images, max_keypoints, n_levels).total;
+    return pyramid_layout(w, h, n_images, max_keypoints, n_levels, refined).total;
 }
 
-size_t detect_pyramid_refined_workspace_bytes(int w, int h, int n_images, int max_keypoints, int n_levels)
-{
-    if (detect_pyramid_workspace_bytes(w, h, n_images, max_keypoints, n_levels) == 0) return 0;
-    return pyramid_refined_layout(w, h, n_images, max_keypoints, n_levels).total;
-}
-
-hipError_t launch_detect_pyramid(const uint8_t* d_images, int n_images, int w, int h, int threshold, int max_keypoints, int n_levels, void* d_ws,
-                                 gms_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, int32_t* d_level_counts, hipStream_t stream, float* d_rows128,
-                                 int dog_contrast, bool refine)
+hipError_t launch_detect_pyramid(const PyramidRun& run, const uint8_t* d_images, int n_images, int w, int h, int max_keypoints, int n_levels, void* d_ws,
+                                 gms_keypoint* d_kp, uint8_t* d_desc, float* d_rows128, int32_t* d_counts, int32_t* d_level_counts, hipStream_t stream)
 {
     if (n_images <= 0) return hipSuccess;
     int ww[kPyramidMaxLevels], hh[kPyramidMaxLevels], quota[kPyramidMaxLevels];
     const int n = pyramid_level_sizes(w, h, n_levels, ww, hh);
     pyramid_quotas(ww, hh, n, max_keypoints, quota);
-    const PyramidLayout L = pyramid_layout(w, h, n_images, max_keypoints, n_levels);
+    const PyramidLayout L = pyramid_layout(w, h, n_images, max_keypoints, n_levels, run.refined);
     uint8_t* levels = ws_ptr<uint8_t>(d_ws, L.levels);
     int32_t* lvl_counts = ws_ptr<int32_t>(d_ws, L.counts);
     uint32_t* hists = ws_ptr<uint32_t>(d_ws, L.hists);
     void* det_ws = ws_ptr<char>(d_ws, L.detect);
-    uint16_t* codes = refine ? ws_ptr<uint16_t>(d_ws, pyramid_refined_layout(w, h, n_images, max_keypoints, n_levels).codes) : nullptr;
+    uint16_t* codes = run.refined ? ws_ptr<uint16_t>(d_ws, L.codes) : nullptr;
     const size_t clear_words = (L.detect - L.counts) / 4;
     hipLaunchKernelGGL(pyr_clear_kernel, dim3((unsigned)((clear_words + 255) / 256 < 1024 ? (clear_words + 255) / 256 : 1024)), dim3(256), 0, stream,
                        reinterpret_cast<uint32_t*>(lvl_counts), clear_words);
@@ -637,8 +635,8 @@ hipError_t launch_detect_pyramid(const uint8_t* d_images, int n_images, int w, i
     for (int l = 0; l < n; ++l) {
         if (quota[l] > 0) {
             const LevelOut lo = {lvl_counts, l, n_images, max_keypoints, (float)w / (float)ww[l], (float)h / (float)hh[l], codes};
-            e = detect_level(img, n_images, ww[l], hh[l], threshold, quota[l], det_ws, d_kp, d_desc, lvl_counts + (size_t)l * n_images, &lo,
-                             hists + (size_t)l * n_images * 256, stream, dog_contrast, codes);
+            e = detect_level(run, img, n_images, ww[l], hh[l], quota[l], det_ws, d_kp, d_desc, lvl_counts + (size_t)l * n_images, &lo,
+                             hists + (size_t)l * n_images * 256, stream);
             if (e != hipSuccess) return e;
             if (d_rows128 != nullptr) {   // while the level's box sums and list are still in the workspace
                 e = launch_grad_level(n_images, ww[l], hh[l], quota[l], det_ws, lvl_counts, l, max_keypoints, d_kp, d_rows128, stream);

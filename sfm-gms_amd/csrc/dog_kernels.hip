@@ -183,23 +183,17 @@ dog_maps_kernel(const uint8_t* __restrict__ images, int w, int h, int contrast, 
 
 }  // namespace
 
-// candidate plane and, unless nullptr, box sums and score histogram of n_images images of one size: what detect_level's later kernels read
+// candidate plane and, unless nullptr, box sums and score histogram of n_images images of one size: what detect_level's later kernels read.
+// d_codes != nullptr: the refinement's code plane as well, where d_cand is non-zero, or (d_cand == nullptr: the code planes alone) on every pixel
 hipError_t launch_dog_maps(const uint8_t* d_images, int n_images, int w, int h, int contrast, uint8_t* d_cand, uint16_t* d_box, uint32_t* d_hist,
-                           hipStream_t stream)
+                           uint16_t* d_codes, hipStream_t stream)
 {
     if (n_images <= 0) return hipSuccess;
-    hipLaunchKernelGGL(dog_maps_kernel<false>, dim3((w + kTileW - 1) / kTileW, (h + kTileH - 1) / kTileH, n_images), dim3(256), 0, stream, d_images, w, h,
-                       contrast, d_cand, d_box, d_hist, (uint16_t*)nullptr);
-    return hipGetLastError();
-}
-
-// the same with the refinement's code plane: where d_cand is non-zero, or (d_cand == nullptr: the code planes alone) on every pixel
-hipError_t launch_dog_maps_refine(const uint8_t* d_images, int n_images, int w, int h, int contrast, uint8_t* d_cand, uint16_t* d_box, uint32_t* d_hist,
-                                  uint16_t* d_codes, hipStream_t stream)
-{
-    if (n_images <= 0) return hipSuccess;
-    hipLaunchKernelGGL(dog_maps_kernel<true>, dim3((w + kTileW - 1) / kTileW, (h + kTileH - 1) / kTileH, n_images), dim3(256), 0, stream, d_images, w, h,
-                       contrast, d_cand, d_box, d_hist, d_codes);
+    const dim3 grid((w + kTileW - 1) / kTileW, (h + kTileH - 1) / kTileH, n_images);
+    if (d_codes == nullptr)
+        hipLaunchKernelGGL(dog_maps_kernel<false>, grid, dim3(256), 0, stream, d_images, w, h, contrast, d_cand, d_box, d_hist, d_codes);
+    else
+        hipLaunchKernelGGL(dog_maps_kernel<true>, grid, dim3(256), 0, stream, d_images, w, h, contrast, d_cand, d_box, d_hist, d_codes);
     return hipGetLastError();
 }
 

@@ -1763,12 +1763,6 @@ int gms_pyramid_level_sizes(int width, int height, int n_levels, int32_t* widths
     return gms::pyramid_level_sizes(width, height, n_levels, widths, heights);
 }
 
-size_t gms_detect_pyramid_workspace_bytes(int width, int height, int n_images, int max_keypoints, int n_levels)
-{
-    if (!detect_image_ok(width, height)) return 0;
-    return gms::detect_pyramid_workspace_bytes(width, height, n_images, max_keypoints, n_levels);
-}
-
 int gms_pyramid_build_device(gms_ctx* c, const uint8_t* d_images, int n_images, int width, int height, int n_levels, uint8_t* d_levels,
                              size_t levels_bytes)
 {
@@ -1779,44 +1773,64 @@ int gms_pyramid_build_device(gms_ctx* c, const uint8_t* d_images, int n_images, 
     return on_ctx(c, [&] { return gms::launch_pyramid_build(d_images, n_images, width, height, n_levels, d_levels, c->stream); });
 }
 
+// what the batch calls of the keypoint source check first: the context, the counts, the detector's strength and the image size
+static bool detect_scalars_ok(const gms_ctx* c, int n_images, int width, int height, int strength, int max_strength)
+{
+    return c && n_images >= 0 && strength >= 0 && strength <= max_strength && detect_image_ok(width, height);
+}
+
+static bool misaligned8(const float* p) { return reinterpret_cast<uintptr_t>(p) % 8 != 0; }   // the 128-float rows are stored two floats at a time
+static bool rows128_ok(const float* d_rows128) { return d_rows128 && !misaligned8(d_rows128); }
+
+static size_t pyramid_workspace_bytes(int width, int height, int n_images, int max_keypoints, int n_levels, bool refined)
+{
+    return detect_image_ok(width, height) ? gms::detect_pyramid_workspace_bytes(width, height, n_images, max_keypoints, n_levels, refined) : 0;
+}
+
+// The four pyramid calls. max_strength: the bound of run.strength. rows128_bad: the caller's own rule for d_rows128 refuses it (looked at
+// behind the early return of an empty batch, like every pointer).
+static int detect_pyramid(gms_ctx* c, const gms::PyramidRun& run, int max_strength, const uint8_t* d_images, int n_images, int width, int height,
+                          int max_keypoints, int n_levels, void* d_workspace, size_t workspace_bytes, gms_keypoint* d_keypoints,
+                          uint8_t* d_descriptors, int32_t* d_counts, int32_t* d_level_counts, float* d_rows128, bool rows128_bad)
+{
+    if (!detect_scalars_ok(c, n_images, width, height, run.strength, max_strength) || max_keypoints < 0) return GMS_ERR_BAD_ARG;
+    if (n_levels < 1 || n_levels > GMS_PYRAMID_MAX_LEVELS) return GMS_ERR_BAD_ARG;
+    if (n_images == 0) return GMS_OK;
+    if (!d_images || !d_workspace || !d_counts || !d_level_counts || rows128_bad) return GMS_ERR_BAD_ARG;
+    if (max_keypoints > 0 && (!d_keypoints || !d_descriptors)) return GMS_ERR_BAD_ARG;
+    if (workspace_bytes < pyramid_workspace_bytes(width, height, n_images, max_keypoints, n_levels, run.refined)) return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] {
+        return gms::launch_detect_pyramid(run, d_images, n_images, width, height, max_keypoints, n_levels, d_workspace, d_keypoints, d_descriptors,
+                                          max_keypoints > 0 ? d_rows128 : nullptr, d_counts, d_level_counts, c->stream);
+    });
+}
+
+size_t gms_detect_pyramid_workspace_bytes(int width, int height, int n_images, int max_keypoints, int n_levels)
+{
+    return pyramid_workspace_bytes(width, height, n_images, max_keypoints, n_levels, false);
+}
+
 int gms_detect_pyramid_batch_device(gms_ctx* c, const uint8_t* d_images, int n_images, int width, int height, int threshold, int max_keypoints,
                                     int n_levels, void* d_workspace, size_t workspace_bytes, gms_keypoint* d_keypoints, uint8_t* d_descriptors,
                                     int32_t* d_counts, int32_t* d_level_counts)
 {
-    if (!c || n_images < 0 || max_keypoints < 0 || threshold < 0 || threshold > 254 || !detect_image_ok(width, height)) return GMS_ERR_BAD_ARG;
-    if (n_levels < 1 || n_levels > GMS_PYRAMID_MAX_LEVELS) return GMS_ERR_BAD_ARG;
-    if (n_images == 0) return GMS_OK;
-    if (!d_images || !d_workspace || !d_counts || !d_level_counts || (max_keypoints > 0 && (!d_keypoints || !d_descriptors))) return GMS_ERR_BAD_ARG;
-    if (workspace_bytes < gms::detect_pyramid_workspace_bytes(width, height, n_images, max_keypoints, n_levels)) return GMS_ERR_BAD_ARG;
-    return on_ctx(c, [&] {
-        return gms::launch_detect_pyramid(d_images, n_images, width, height, threshold, max_keypoints, n_levels, d_workspace, d_keypoints,
-                                          d_descriptors, d_counts, d_level_counts, c->stream);
-    });
+    return detect_pyramid(c, {gms::PyramidRun::kFast, threshold, false}, 254, d_images, n_images, width, height, max_keypoints, n_levels, d_workspace,
+                          workspace_bytes, d_keypoints, d_descriptors, d_counts, d_level_counts, nullptr, false);
 }
 
-// ---- gradient descriptor (grad_desc_kernels.hip) ---------------------------------------------------------------------------------
+// ---- gradient descriptor (grad_desc_kernels.hip): fused into the pyramid call, no workspace region of its own ----------------------
 size_t gms_detect_pyramid_grad_workspace_bytes(int width, int height, int n_images, int max_keypoints, int n_levels)
 {
-    if (!detect_image_ok(width, height)) return 0;
-    return gms::detect_pyramid_grad_workspace_bytes(width, height, n_images, max_keypoints, n_levels);
+    return pyramid_workspace_bytes(width, height, n_images, max_keypoints, n_levels, false);
 }
-
-static bool rows128_ok(const float* d_rows128) { return d_rows128 && reinterpret_cast<uintptr_t>(d_rows128) % 8 == 0; }  // stored two floats at a time
 
 int gms_detect_pyramid_grad_batch_device(gms_ctx* c, const uint8_t* d_images, int n_images, int width, int height, int threshold, int max_keypoints,
                                          int n_levels, void* d_workspace, size_t workspace_bytes, gms_keypoint* d_keypoints, uint8_t* d_descriptors,
                                          int32_t* d_counts, int32_t* d_level_counts, float* d_rows128)
 {
-    if (!c || n_images < 0 || max_keypoints < 0 || threshold < 0 || threshold > 254 || !detect_image_ok(width, height)) return GMS_ERR_BAD_ARG;
-    if (n_levels < 1 || n_levels > GMS_PYRAMID_MAX_LEVELS) return GMS_ERR_BAD_ARG;
-    if (n_images == 0) return GMS_OK;
-    if (!d_images || !d_workspace || !d_counts || !d_level_counts) return GMS_ERR_BAD_ARG;
-    if (max_keypoints > 0 && (!d_keypoints || !d_descriptors || !rows128_ok(d_rows128))) return GMS_ERR_BAD_ARG;
-    if (workspace_bytes < gms::detect_pyramid_grad_workspace_bytes(width, height, n_images, max_keypoints, n_levels)) return GMS_ERR_BAD_ARG;
-    return on_ctx(c, [&] {
-        return gms::launch_detect_pyramid(d_images, n_images, width, height, threshold, max_keypoints, n_levels, d_workspace, d_keypoints,
-                                          d_descriptors, d_counts, d_level_counts, c->stream, max_keypoints > 0 ? d_rows128 : nullptr);
-    });
+    const bool rows128_bad = max_keypoints > 0 && !rows128_ok(d_rows128);   // required, but only where a row can be written
+    return detect_pyramid(c, {gms::PyramidRun::kFast, threshold, false}, 254, d_images, n_images, width, height, max_keypoints, n_levels, d_workspace,
+                          workspace_bytes, d_keypoints, d_descriptors, d_counts, d_level_counts, d_rows128, rows128_bad);
 }
 
 int gms_describe_grad_device(gms_ctx* c, const uint8_t* d_image, int width, int height, gms_keypoint* d_keypoints, int n, void* d_workspace,
@@ -1828,67 +1842,47 @@ int gms_describe_grad_device(gms_ctx* c, const uint8_t* d_image, int width, int 
     return on_ctx(c, [&] { return gms::launch_describe_grad(d_image, width, height, d_keypoints, n, d_workspace, d_rows128, d_status, c->stream); });
 }
 
-// ---- difference-of-Gaussians detector (dog_kernels.hip) ---------------------------------------------------------------------------
+// ---- difference-of-Gaussians detector (dog_kernels.hip): d_rows128 is optional, but never misaligned -------------------------------
 size_t gms_detect_dog_workspace_bytes(int width, int height, int n_images, int max_keypoints, int n_levels)
 {
-    if (!detect_image_ok(width, height)) return 0;
-    return gms::detect_pyramid_grad_workspace_bytes(width, height, n_images, max_keypoints, n_levels);   // the kernel is fused: no region of its own
+    return pyramid_workspace_bytes(width, height, n_images, max_keypoints, n_levels, false);   // the kernel is fused: no region of its own
 }
 
 int gms_detect_dog_batch_device(gms_ctx* c, const uint8_t* d_images, int n_images, int width, int height, int contrast, int max_keypoints,
                                 int n_levels, void* d_workspace, size_t workspace_bytes, gms_keypoint* d_keypoints, uint8_t* d_descriptors,
                                 int32_t* d_counts, int32_t* d_level_counts, float* d_rows128)
 {
-    if (!c || n_images < 0 || max_keypoints < 0 || contrast < 0 || contrast > GMS_DOG_MAX_CONTRAST || !detect_image_ok(width, height)) return GMS_ERR_BAD_ARG;
-    if (n_levels < 1 || n_levels > GMS_PYRAMID_MAX_LEVELS) return GMS_ERR_BAD_ARG;
-    if (n_images == 0) return GMS_OK;
-    if (!d_images || !d_workspace || !d_counts || !d_level_counts) return GMS_ERR_BAD_ARG;
-    if (max_keypoints > 0 && (!d_keypoints || !d_descriptors)) return GMS_ERR_BAD_ARG;
-    if (d_rows128 && reinterpret_cast<uintptr_t>(d_rows128) % 8 != 0) return GMS_ERR_BAD_ARG;
-    if (workspace_bytes < gms_detect_dog_workspace_bytes(width, height, n_images, max_keypoints, n_levels)) return GMS_ERR_BAD_ARG;
-    return on_ctx(c, [&] {
-        return gms::launch_detect_pyramid(d_images, n_images, width, height, 0, max_keypoints, n_levels, d_workspace, d_keypoints, d_descriptors,
-                                          d_counts, d_level_counts, c->stream, max_keypoints > 0 ? d_rows128 : nullptr, contrast);
-    });
+    return detect_pyramid(c, {gms::PyramidRun::kDog, contrast, false}, GMS_DOG_MAX_CONTRAST, d_images, n_images, width, height, max_keypoints, n_levels,
+                          d_workspace, workspace_bytes, d_keypoints, d_descriptors, d_counts, d_level_counts, d_rows128, misaligned8(d_rows128));
 }
 
 size_t gms_detect_dog_refined_workspace_bytes(int width, int height, int n_images, int max_keypoints, int n_levels)
 {
-    if (!detect_image_ok(width, height)) return 0;
-    return gms::detect_pyramid_refined_workspace_bytes(width, height, n_images, max_keypoints, n_levels);   // + the plane of refinement codes
+    return pyramid_workspace_bytes(width, height, n_images, max_keypoints, n_levels, true);   // + the plane of refinement codes
 }
 
 int gms_detect_dog_refined_batch_device(gms_ctx* c, const uint8_t* d_images, int n_images, int width, int height, int contrast, int max_keypoints,
                                         int n_levels, void* d_workspace, size_t workspace_bytes, gms_keypoint* d_keypoints, uint8_t* d_descriptors,
                                         int32_t* d_counts, int32_t* d_level_counts, float* d_rows128)
 {
-    if (!c || n_images < 0 || max_keypoints < 0 || contrast < 0 || contrast > GMS_DOG_MAX_CONTRAST || !detect_image_ok(width, height)) return GMS_ERR_BAD_ARG;
-    if (n_levels < 1 || n_levels > GMS_PYRAMID_MAX_LEVELS) return GMS_ERR_BAD_ARG;
-    if (n_images == 0) return GMS_OK;
-    if (!d_images || !d_workspace || !d_counts || !d_level_counts) return GMS_ERR_BAD_ARG;
-    if (max_keypoints > 0 && (!d_keypoints || !d_descriptors)) return GMS_ERR_BAD_ARG;
-    if (d_rows128 && reinterpret_cast<uintptr_t>(d_rows128) % 8 != 0) return GMS_ERR_BAD_ARG;
-    if (workspace_bytes < gms_detect_dog_refined_workspace_bytes(width, height, n_images, max_keypoints, n_levels)) return GMS_ERR_BAD_ARG;
-    return on_ctx(c, [&] {
-        return gms::launch_detect_pyramid(d_images, n_images, width, height, 0, max_keypoints, n_levels, d_workspace, d_keypoints, d_descriptors,
-                                          d_counts, d_level_counts, c->stream, max_keypoints > 0 ? d_rows128 : nullptr, contrast, true);
-    });
+    return detect_pyramid(c, {gms::PyramidRun::kDog, contrast, true}, GMS_DOG_MAX_CONTRAST, d_images, n_images, width, height, max_keypoints, n_levels,
+                          d_workspace, workspace_bytes, d_keypoints, d_descriptors, d_counts, d_level_counts, d_rows128, misaligned8(d_rows128));
 }
 
 int gms_dog_offsets_device(gms_ctx* c, const uint8_t* d_images, int n_images, int width, int height, int contrast, uint16_t* d_codes)
 {
-    if (!c || n_images < 0 || contrast < 0 || contrast > GMS_DOG_MAX_CONTRAST || !detect_image_ok(width, height)) return GMS_ERR_BAD_ARG;
+    if (!detect_scalars_ok(c, n_images, width, height, contrast, GMS_DOG_MAX_CONTRAST)) return GMS_ERR_BAD_ARG;
     if (n_images == 0) return GMS_OK;
     if (!d_images || !d_codes || reinterpret_cast<uintptr_t>(d_codes) % 2 != 0) return GMS_ERR_BAD_ARG;
-    return on_ctx(c, [&] { return gms::launch_dog_maps_refine(d_images, n_images, width, height, contrast, nullptr, nullptr, nullptr, d_codes, c->stream); });
+    return on_ctx(c, [&] { return gms::launch_dog_maps(d_images, n_images, width, height, contrast, nullptr, nullptr, nullptr, d_codes, c->stream); });
 }
 
 int gms_dog_candidates_device(gms_ctx* c, const uint8_t* d_images, int n_images, int width, int height, int contrast, uint8_t* d_cand)
 {
-    if (!c || n_images < 0 || contrast < 0 || contrast > GMS_DOG_MAX_CONTRAST || !detect_image_ok(width, height)) return GMS_ERR_BAD_ARG;
+    if (!detect_scalars_ok(c, n_images, width, height, contrast, GMS_DOG_MAX_CONTRAST)) return GMS_ERR_BAD_ARG;
     if (n_images == 0) return GMS_OK;
     if (!d_images || !d_cand) return GMS_ERR_BAD_ARG;
-    return on_ctx(c, [&] { return gms::launch_dog_maps(d_images, n_images, width, height, contrast, d_cand, nullptr, nullptr, c->stream); });
+    return on_ctx(c, [&] { return gms::launch_dog_maps(d_images, n_images, width, height, contrast, d_cand, nullptr, nullptr, nullptr, c->stream); });
 }
 
 // ---- from photographs to the tables (ingest_kernels.hip) ----------------------------------------------------------------------------

@@ -149,28 +149,29 @@ hipError_t launch_describe(const uint8_t* d_image, int w, int h, gms_keypoint* d
                            hipStream_t stream);
 // pyramid keypoint source (detect_kernels.hip): the same detector on every level of an image pyramid (level sizes: ws_layout.h)
 void       pyramid_quotas(const int* widths, const int* heights, int n, int max_keypoints, int* quotas);
-size_t     detect_pyramid_workspace_bytes(int w, int h, int n_images, int max_keypoints, int n_levels);
+// what a pyramid run does: the detector, its strength (the FAST threshold or the DoG contrast: dog_kernels.hip) and
+// whether the records are refined to 1/16 pixel and 1/16 layer (DoG only; the workspace then ends with the plane of refinement codes)
+struct PyramidRun {
+    enum Detector { kFast, kDog } detector;
+    int strength;
+    bool refined;
+};
+size_t     detect_pyramid_workspace_bytes(int w, int h, int n_images, int max_keypoints, int n_levels, bool refined);
 hipError_t launch_pyramid_build(const uint8_t* d_images, int n_images, int w, int h, int n_levels, uint8_t* d_levels, hipStream_t stream);
-hipError_t launch_detect_pyramid(const uint8_t* d_images, int n_images, int w, int h, int threshold, int max_keypoints, int n_levels, void* d_ws,
-                                 gms_keypoint* d_kp, uint8_t* d_desc, int32_t* d_counts, int32_t* d_level_counts, hipStream_t stream,
-                                 float* d_rows128 = nullptr,    // d_rows128: the gradient descriptor's rows as well
-                                 int dog_contrast = -1,         // >= 0: the DoG detector's candidates in the FAST detector's place
-                                 bool refine = false);          // with them: records refined to 1/16 pixel and 1/16 layer; the workspace below
-size_t     detect_pyramid_refined_workspace_bytes(int w, int h, int n_images, int max_keypoints, int n_levels);
+// d_rows128: the gradient descriptor's rows as well, or nullptr
+hipError_t launch_detect_pyramid(const PyramidRun& run, const uint8_t* d_images, int n_images, int w, int h, int max_keypoints, int n_levels, void* d_ws,
+                                 gms_keypoint* d_kp, uint8_t* d_desc, float* d_rows128, int32_t* d_counts, int32_t* d_level_counts, hipStream_t stream);
 hipError_t launch_detect_maps(const uint8_t* d_images, int n_images, int w, int h, void* d_ws, hipStream_t stream);
 // gradient descriptor (grad_desc_kernels.hip; arithmetic in grad_desc_core.h): 128-float rows at the detector's keypoints
-size_t     detect_pyramid_grad_workspace_bytes(int w, int h, int n_images, int max_keypoints, int n_levels);
 hipError_t launch_grad_level(int n_images, int w, int h, int quota, void* d_det_ws, const int32_t* d_level_counts, int level, int out_stride,
                              gms_keypoint* d_kp, float* d_rows128, hipStream_t stream);
 hipError_t launch_describe_grad(const uint8_t* d_image, int w, int h, gms_keypoint* d_kp, int n, void* d_ws, float* d_rows128, int32_t* d_status,
                                 hipStream_t stream);
 // difference-of-Gaussians detector (dog_kernels.hip; arithmetic in dog_core.h): the candidate plane, box sums and score histogram
-// (d_box and d_hist may be nullptr) that a level's selection and describe kernels read
+// (d_box and d_hist may be nullptr) that a level's selection and describe kernels read. d_codes != nullptr: dog_core.h's refinement
+// codes (uint16) as well, where d_cand is non-zero; then d_cand == nullptr: on every pixel (0: no candidate), no candidate plane
 hipError_t launch_dog_maps(const uint8_t* d_images, int n_images, int w, int h, int contrast, uint8_t* d_cand, uint16_t* d_box, uint32_t* d_hist,
-                           hipStream_t stream);
-// ... and dog_core.h's refinement codes (uint16) where d_cand is non-zero; d_cand == nullptr: on every pixel (0: no candidate), no candidate plane
-hipError_t launch_dog_maps_refine(const uint8_t* d_images, int n_images, int w, int h, int contrast, uint8_t* d_cand, uint16_t* d_box, uint32_t* d_hist,
-                                  uint16_t* d_codes, hipStream_t stream);
+                           uint16_t* d_codes, hipStream_t stream);
 // from photographs to the tables (ingest_kernels.hip): BGR -> grey planes; the detector's blocks -> frames back to back
 hipError_t launch_bgr_to_gray(const uint8_t* d_bgr, int n, int w, int h, uint8_t* d_gray, hipStream_t stream);
 hipError_t launch_detect_pack(const gms_keypoint* d_kp_blocks, const uint8_t* d_rows32_blocks, const float* d_rows128_blocks, const int32_t* d_counts,

@@ -105,12 +105,8 @@ grad_describe_kernel(const uint8_t* __restrict__ images, const uint16_t* __restr
 
 }  // namespace
 
-size_t detect_pyramid_grad_workspace_bytes(int w, int h, int n_images, int max_keypoints, int n_levels)
-{
-    if (detect_pyramid_workspace_bytes(w, h, n_images, max_keypoints, n_levels) == 0) return 0;
-    return pyramid_grad_layout(w, h, n_images, max_keypoints, n_levels).total;
-}
-
+// The pyramid call that also writes these rows needs no workspace region of its own: this kernel runs behind each level's describe kernel
+// and reads what that level left -- the box sums and the list in the level's detect_layout, the direction in the keypoint record.
 // the rows of one pyramid level's keypoints, after detect_level has run on that level in `d_det_ws` (detect_layout of the level)
 hipError_t launch_grad_level(int n_images, int w, int h, int quota, void* d_det_ws, const int32_t* d_level_counts, int level, int out_stride,
                              gms_keypoint* d_kp, float* d_rows128, hipStream_t stream)

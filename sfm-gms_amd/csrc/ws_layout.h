@@ -3,8 +3,9 @@
 // they hand to a kernel, and every span they clear, from the same struct. Offsets count from the workspace's start, which is 256-byte
 // aligned (the C ABI refuses other caller workspaces; the context's own come from hipMalloc).
 //
-// Plain arithmetic and no HIP header, so that a host compiler builds it alone: tests/cpp/ws_layout_check.cpp sweeps every layout
-// here for order, overlap, alignment and size.
+// Plain arithmetic and no HIP header, so that a host compiler builds it alone: tests/cpp/ws_layout_check.cpp sweeps the layouts of
+// the keypoint source (both forms of the pyramid's), the large pairs, StereoBM, portrait mode and bruteForceMatch's selection for order,
+// overlap, alignment and size.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -85,44 +86,26 @@ inline size_t pyramid_bytes(int w, int h, int n_images, int n_levels)
     return b;
 }
 // Every call zeroes [counts, detect) first (the counts too: a level with quota 0 is not run).
+// `refined` (the DoG call with refinement; dog_kernels.hip, detect_kernels.hip) adds, behind the other regions, the plane of refinement
+// codes that a level's candidate kernel leaves for its describe kernel. Never cleared: a code is read only where the level's candidate
+// plane is non-zero, and the kernel that wrote that plane wrote the code. Not refined: `codes` is empty and `total` ends at `detect`'s end.
 struct PyramidLayout {
     size_t levels;  // uint8: the level images 1 .., pyramid_bytes of them
     size_t counts;  // int32 [kPyramidMaxLevels][n]: keypoints per level and image
     size_t hists;   // uint32 [kPyramidMaxLevels][n][256]: the levels' score histograms
     size_t detect;  // the single-scale workspace of level 0: every level fits into it in its turn
+    size_t codes;   // refined only: uint16 [n][h][w] of level 0, on a 256-byte boundary: every level fits into it in its turn
     size_t total;
 };
-inline PyramidLayout pyramid_layout(int w, int h, int n_images, int max_keypoints, int n_levels)
+inline PyramidLayout pyramid_layout(int w, int h, int n_images, int max_keypoints, int n_levels, bool refined)
 {
     const size_t n = (size_t)n_images;
     WsCursor c;
-    return {c.take(pyramid_bytes(w, h, n_images, n_levels), 256), c.take(kPyramidMaxLevels * n * 4, 256), c.take(kPyramidMaxLevels * n * 256 * 4),
-            c.end, c.end + detect_layout(w, h, n_images, max_keypoints).total};
-}
-
-// The pyramid call that also writes the gradient descriptor's rows (grad_desc_kernels.hip): the descriptor kernel runs behind each
-// level's describe kernel and reads what that level left -- the box sums and the list in `detect`, the direction in the keypoint
-// record -- so it needs no region of its own: the pyramid's regions, under the names its launcher uses.
-using PyramidGradLayout = PyramidLayout;
-inline PyramidGradLayout pyramid_grad_layout(int w, int h, int n_images, int max_keypoints, int n_levels)
-{
-    return pyramid_layout(w, h, n_images, max_keypoints, n_levels);
-}
-
-// The DoG call with refinement (dog_kernels.hip, detect_kernels.hip): the pyramid's regions, unchanged, and behind them the plane of
-// refinement codes that a level's candidate kernel leaves for its describe kernel. Never cleared: a code is read only where the
-// level's candidate plane is non-zero, and the kernel that wrote that plane wrote the code.
-struct PyramidRefinedLayout {
-    PyramidLayout pyramid;
-    size_t codes;  // uint16 [n][h][w] of level 0: every level fits into it in its turn
-    size_t total;
-};
-inline PyramidRefinedLayout pyramid_refined_layout(int w, int h, int n_images, int max_keypoints, int n_levels)
-{
-    const PyramidLayout P = pyramid_layout(w, h, n_images, max_keypoints, n_levels);
-    WsCursor c;
-    c.take(P.total, 256);
-    return {P, c.take((size_t)w * h * (size_t)n_images * 2, 256), c.end};
+    const size_t levels = c.take(pyramid_bytes(w, h, n_images, n_levels), 256), counts = c.take(kPyramidMaxLevels * n * 4, 256),
+                 hists = c.take(kPyramidMaxLevels * n * 256 * 4), detect = c.take(detect_layout(w, h, n_images, max_keypoints).total);
+    if (!refined) return {levels, counts, hists, detect, c.end, c.end};
+    c.align(256);
+    return {levels, counts, hists, detect, c.take((size_t)w * h * n * 2, 256), c.end};
 }
 
 // ---- large pairs, per slice of n pairs of the context's own workspace (gms_kernel_band.hip, gms_kernel_stream.hip) ------------------

@@ -1,4 +1,4 @@
-// ws_layout_check.cpp -- CPU check of the nine workspace layouts of sfm-gms_amd/csrc/ws_layout.h. tests/test_ws_layout.py builds it
+// ws_layout_check.cpp -- CPU check of nine workspace layouts of sfm-gms_amd/csrc/ws_layout.h (all but SGM's and the chessboard's; the pyramid's in both its forms). tests/test_ws_layout.py builds it
 // with g++ (plain and under the address / undefined-behaviour sanitizers) and runs it.
 //
 // Every layout is swept over n in {1, 2, 3, 63, 64, 255, 257} and its other arguments' awkward values (below). For each case:
@@ -90,11 +90,22 @@ void check_detect(int w, int h, int n, int maxkp, int levels)
     check_regions(what, {{"score", d.score, px, 256}, {"cand", d.cand, px, 256}, {"box", d.box, 2 * px, 256}, {"hist", d.hist, N * 256 * 4, 256},
                          {"cut", d.cut, N * 16, 256}, {"rows", d.rows, N * h * 8, 16}, {"list", d.list, N * maxkp * 8, 16}}, d.total, 256);
     expect(what, "the cleared histogram", d.cut - d.hist, N * 256 * 4);
-    const PyramidLayout p = pyramid_layout(w, h, n, maxkp, levels);
+    const PyramidLayout p = pyramid_layout(w, h, n, maxkp, levels, false);
     what = fmt("pyramid %lld x %lld, %lld images, %lld keypoints, %lld levels", w, h, n, maxkp, levels);
     check_regions(what, {{"levels", p.levels, level_bytes(w, h, n, levels), 256}, {"counts", p.counts, 16 * N * 4, 256},
-                         {"hists", p.hists, 16 * N * 256 * 4, 256}, {"detect", p.detect, d.total, 256}}, p.total, 256);
+                         {"hists", p.hists, 16 * N * 256 * 4, 256}, {"detect", p.detect, d.total, 256}, {"codes", p.codes, 0, 1}}, p.total, 256);
     expect(what, "the cleared span", p.detect - p.counts, round_up(16 * N * 4, 256) + 16 * N * 256 * 4);
+    expect(what, "the total", p.total, p.detect + d.total);   // what it was before the refined form shared the struct
+    expect(what, "the empty code plane", p.codes, p.total);
+    // the refined form: the same regions at the same offsets, then the plane of refinement codes (2 w h n bytes) on a 256-byte boundary
+    const PyramidLayout r = pyramid_layout(w, h, n, maxkp, levels, true);
+    what = fmt("refined pyramid %lld x %lld, %lld images, %lld keypoints, %lld levels", w, h, n, maxkp, levels);
+    check_regions(what, {{"levels", r.levels, level_bytes(w, h, n, levels), 256}, {"counts", r.counts, 16 * N * 4, 256},
+                         {"hists", r.hists, 16 * N * 256 * 4, 256}, {"detect", r.detect, d.total, 256}, {"codes", r.codes, 2 * px, 256}}, r.total, 256);
+    expect(what, "the cleared span", r.detect - r.counts, round_up(16 * N * 4, 256) + 16 * N * 256 * 4);
+    expect(what, "the unrefined regions", (size_t)(r.levels == p.levels && r.counts == p.counts && r.hists == p.hists && r.detect == p.detect), 1);
+    expect(what, "the code plane", r.codes, round_up(p.total, 256));
+    expect(what, "the total", r.total, round_up(p.total, 256) + round_up(2 * px, 256));
 }
 
 void check_images(int w, int h, int n)
@@ -175,7 +186,8 @@ int check_fixture(const char* path)
         const std::string id = name;
         size_t got = 0;
         if (id == "detect" && k == 5) got = detect_layout((int)a[0], (int)a[1], (int)a[2], (int)a[3]).total;
-        else if (id == "pyramid" && k == 6) got = pyramid_layout((int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)a[4]).total;
+        else if (id == "pyramid" && k == 6) got = pyramid_layout((int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)a[4], false).total;
+        else if (id == "refined" && k == 6) got = pyramid_layout((int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)a[4], true).total;
         else if (id == "stereo" && k == 4) got = stereo_bm_layout((int)a[2], (int)a[0], (int)a[1]).total;
         else if (id == "portrait" && k == 4) got = portrait_layout((int)a[2], (int)a[0], (int)a[1]).total;
         else if (id == "bfsel" && k == 4) got = bf_select_layout((int)a[0], a[1], a[2]).total;

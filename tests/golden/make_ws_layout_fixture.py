@@ -1,4 +1,4 @@
-"""Generator of tests/golden/ws_layout_sizes.txt: the sizes the built library gives for its device workspaces -- the five public
+"""Generator of tests/golden/ws_layout_sizes.txt: the sizes the built library gives for its device workspaces -- six public
 gms_*_workspace_bytes functions (the zero of a refused input included) and the four internal per-pair figures that plan_workspace
 divides its budget by -- over a few hundred argument tuples, one text line each: `<name> <arguments ...> <bytes>`.
 
@@ -7,7 +7,9 @@ includes the library's internal header) against sfm-gms_amd/csrc/libgms_hip.so, 
 file. It reads nothing but this repository's own library.
 
 The committed fixture was recorded at commit 063d3a7, whose size functions were hand-written sums apart from the launchers' pointer
-walks; tests/test_ws_layout.py holds the layouts of ws_layout.h to it. Regenerating it from a later library must not change a line.
+walks; tests/test_ws_layout.py holds the layouts of ws_layout.h to it. Its `refined` lines (gms_detect_dog_refined_workspace_bytes on the
+tuples of the `pyramid` lines, appended at the end) were recorded at commit e96d1ca, the last one whose refined layout was a struct
+of its own beside the pyramid's. Regenerating it from a later library must not change a line.
 
 usage (after the library is built): python tests/golden/make_ws_layout_fixture.py
 """

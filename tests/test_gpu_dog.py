@@ -223,6 +223,8 @@ def test_argument_checks(ctx, pkg):
     with pytest.raises(pkg.GmsError):
         ctx.detect_dog_batch_device(p, 1, 100, 100, 128, 10, 8, p, 1 << 22, p, p, p, p, p + 4)      # rows not 8-byte aligned
     with pytest.raises(pkg.GmsError):
+        ctx.detect_dog_batch_device(img.data_ptr(), 1, 100, 100, 128, 0, 8, p, nb, *outs, p + 4)    # ... with no keypoints to write either
+    with pytest.raises(pkg.GmsError):
         ctx.detect_dog_batch_device(p, 1, 32, 100, 128, 10, 8, p, 1 << 22, p, p, p, p, p)           # no room for a keypoint
     ctx.detect_dog_batch_device(p, 0, 100, 100, 128, 10, 8, None, 0, None, None, None, None, None)   # nothing to do
     for args in ((None, 1, 100, 100, 128, p), (p, 1, 100, 100, 128, None), (p, 1, 100, 32, 128, p), (p, -1, 100, 100, 128, p)):

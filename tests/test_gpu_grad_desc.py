@@ -171,6 +171,8 @@ def test_argument_checks(ctx, pkg):
         ctx.detect_pyramid_grad_batch_device(p, 1, 100, 100, 20, 10, 8, None, 1 << 22, p, p, p, p, p)    # no workspace
     with pytest.raises(pkg.GmsError):
         ctx.detect_pyramid_grad_batch_device(p, 1, 100, 100, 20, 10, 8, p, 1 << 22, p, p, p, p, p + 4)   # rows not 8-byte aligned
+    ctx.detect_pyramid_grad_batch_device(img.data_ptr(), 1, 100, 100, 20, 0, 8, p, nb, *outs, p + 4)    # ... which no keypoints never look at
+    ctx.synchronize()
     with pytest.raises(pkg.GmsError):
         ctx.detect_pyramid_grad_batch_device(p, 1, 32, 100, 20, 10, 8, p, 1 << 22, p, p, p, p, p)        # no room for a keypoint
     ctx.detect_pyramid_grad_batch_device(p, 0, 100, 100, 20, 10, 8, None, 0, None, None, None, None, None)   # nothing to do

@@ -1,5 +1,5 @@
-"""-m gpu: the seven entry points that work in a caller's workspace -- detect, describe, detect-pyramid, stereo_bm, portrait,
-bf_select and logos_dict_train `_device` -- given EXACTLY gms_*_workspace_bytes: the workspace is the 256-byte aligned start of a buffer filled with
+"""-m gpu: the seven entry points that work in a caller's workspace -- detect, describe, detect-pyramid (and, of its three other
+forms, the refined DoG one, whose workspace is the largest), stereo_bm, portrait, bf_select and logos_dict_train `_device` -- given EXACTLY gms_*_workspace_bytes: the workspace is the 256-byte aligned start of a buffer filled with
 0x5A that is 4096 bytes longer. The result equals what the entry point's own test expects (the same CPU statements), and the 4096
 bytes behind the workspace still hold 0x5A: a layout (sfm-gms_amd/csrc/ws_layout.h) whose total is smaller than what its launcher
 walks would write there. Three images or pairs with sides just above each entry point's minimum, so that no region's size is a
@@ -91,22 +91,54 @@ def test_describe(ctx, pkg, oracle):
     g.check()
 
 
-@pytest.mark.parametrize("w,h", SIZES)
-def test_detect_pyramid(ctx, oracle, w, h):
+def _blob_images(w, h):
+    """The DoG detector finds nothing in the three keypoint pixels of a 35 x 33 noise image (no contrast helps: its CPU statement finds
+    no candidate there at contrast 0). So its case gets the same noise at an eighth of the amplitude under one blob per image at the
+    centre column - 1, + 0, + 1 of the centre row: integer taps of a Gaussian of sigma about 1.75, a blob of the detector's middle
+    layer, which survives on both levels at 47 x 41."""
+    taps = np.array([3, 16, 69, 216, 486, 792, 932, 792, 486, 216, 69, 16, 3], dtype=np.int64)
+    blob = np.outer(taps, taps) * 200 // (932 * 932)
+    imgs = (_images(w, h) >> 3).astype(np.int64)
+    for i in range(3):
+        cx, cy = w // 2 + i - 1, h // 2
+        imgs[i, cy - 6:cy + 7, cx - 6:cx + 7] += blob
+    return imgs.astype(np.uint8)
+
+
+# (the ids of the FAST cases are what they were before the DoG cases came)
+@pytest.mark.parametrize("w,h,dog", [(*s, False) for s in SIZES] + [(*s, True) for s in SIZES],
+                         ids=[f"{w}-{h}" for w, h in SIZES] + [f"dog-refined-{w}-{h}" for w, h in SIZES])
+def test_detect_pyramid(ctx, oracle, w, h, dog):
+    """dog: the refined DoG call with both kinds of rows, whose workspace ends with the plane of refinement codes. This file has no CPU
+    statement of that detector, so the guarded run is compared byte for byte with an unguarded run of the same arguments."""
     import torch
     n_levels = 2
-    imgs = _images(w, h)
+    imgs = _blob_images(w, h) if dog else _images(w, h)
     assert len(pyramid_ref.level_sizes(w, h, n_levels)) == (2 if w > 35 else 1)
-    run = _batch().DetectPyramid(ctx, 3, w, h, 10, MAX_KP, n_levels)
+    kw = dict(descriptor="both", detector="dog", contrast=128, refine=True) if dog else {}
+    run = _batch().DetectPyramid(ctx, 3, w, h, 10, MAX_KP, n_levels, **kw)
     g = Guarded(run.ws_bytes)
     run.d_ws = g.ws
-    run.run(torch.from_numpy(imgs).cuda())
+    d_imgs = torch.from_numpy(imgs).cuda()
+    run.run(d_imgs)
     ctx.synchronize()
-    kps, rows, lc = run.results()
-    for i in range(3):
-        want_kp, want_rows, want_lc = pyramid_ref.detect(oracle, imgs[i], 10, MAX_KP, n_levels)
-        assert lc[i].tolist() == want_lc.tolist()
-        assert kps[i].tobytes() == want_kp.tobytes() and rows[i].tobytes() == want_rows.tobytes(), i
+    if dog:
+        assert run.ws_bytes == ctx.detect_dog_refined_workspace_bytes(w, h, 3, MAX_KP, n_levels)
+        kps, rows, rows128, lc = run.results()
+        plain = _batch().DetectPyramid(ctx, 3, w, h, 10, MAX_KP, n_levels, **kw)
+        plain.run(d_imgs)
+        ctx.synchronize()
+        want_kps, want_rows, want_rows128, want_lc = plain.results()
+        assert lc.tobytes() == want_lc.tobytes()
+        for i in range(3):
+            assert kps[i].tobytes() == want_kps[i].tobytes() and rows[i].tobytes() == want_rows[i].tobytes(), i
+            assert rows128[i].tobytes() == want_rows128[i].tobytes() and len(kps[i]) > 0, i
+    else:
+        kps, rows, lc = run.results()
+        for i in range(3):
+            want_kp, want_rows, want_lc = pyramid_ref.detect(oracle, imgs[i], 10, MAX_KP, n_levels)
+            assert lc[i].tolist() == want_lc.tolist()
+            assert kps[i].tobytes() == want_kp.tobytes() and rows[i].tobytes() == want_rows.tobytes(), i
     assert (lc.sum(axis=0)[:1 if w == 35 else 2] > 0).all()   # every level that exists gave keypoints
     g.check()
 
