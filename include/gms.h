@@ -385,6 +385,76 @@ int gms_disparity_batch_device(gms_ctx* ctx, const gms_keypoint* d_kp, const int
                                const gms_pair_result* d_results, const uint8_t* d_gt, int64_t gt_stride, int disp_ratio,
                                uint8_t* d_disparity, int64_t map_stride, uint32_t* d_work, gms_disparity_stats* d_stats);
 
+/* ---- many views into one frame (the library's own step behind the batched two-view stage) -----------------------
+ * Every pair of gms_two_view_batch_device has its own frame (camera frame_a) and its own unit (|t| = 1). This stage joins the pairs
+ * of a spanning forest out of a root frame: per pair a scale from the scene points it shares with the pair it hangs on, per frame
+ * a pose [R | t] in the root's frame and the first pair's unit, every pair's points in that frame, and the tracks the surviving
+ * matches chain keypoints into, as one cloud. The inputs are exactly what the two-view stage leaves on the device: d_frame_off,
+ * d_pairs, the survivors d_filtered, d_mask, d_points3d (pair i's points at match_off + rank, rank = non-zero mask bytes before the
+ * match) and d_tv. tests/sfm_register_ref.py is the definition in numpy.
+ *
+ * gms_sfm_plan (host, pure arithmetic): walks the pairs in order with registered = {root}. Pair i registers frame_b when frame_a is
+ *   registered and frame_b is not; its link is the pair that registered frame_a (role 1: the shared frame is that pair's frame_b),
+ *   or for frame_a = root the first registering pair out of the root (role 0; that pair has link -1). depth = the link's + 1.
+ *   Every other pair (reverse direction, both frames registered -- loop closure is not done --, neither registered) has
+ *   registers = 0 and ends as GMS_SFM_SKIPPED. A frame index or root out of range: GMS_ERR_BAD_ARG.
+ * gms_sfm_register_device: d_plan is the plan of the same pairs, in device memory. Pair i is ok when it registers, its two-view status
+ *   is GMS_OK with n_triangulated > 0 and, with a link j, pair j is ok and n_links >= min_links; otherwise GMS_ERR_NO_MODEL, and the
+ *   pairs that hang on it fail the same way. A link: a match of pair i (non-zero mask) whose queryIdx is named by a non-zero-mask
+ *   match of pair j (through its queryIdx for role 0, its trainIdx for role 1; the lowest such match counts), with both points finite
+ *   and z > 0 (pair j's point for role 1 as R_j p + t_j); n_links counts them, r is the lower median of |X| / |Y| over them, S the
+ *   product of r along the links (1 without). Views: G_root = [I | 0], G_b = [R_i G_a.R | R_i G_a.t + S_i t_i]. d_points_world
+ *   (3 doubles per match slot, as d_points3d) = G_a.R^T (S_i p - G_a.t), 0 in every slot that holds no point of an ok pair; d_track
+ *   (int32 per match slot): the point's track, -1 without one. Both are written for every slot below total_matches. A track is a connected component of the edges (frame_off[a] + queryIdx, frame_off[b] +
+ *   trainIdx) of the ok pairs' non-zero-mask matches; its id is its least global keypoint index. The cloud has one entry per track
+ *   in ascending id, the first cloud_cap of them: d_cloud (3 doubles: the world point of the track's estimate of lowest (pair,
+ *   rank)), d_cloud_id, d_cloud_obs (keypoints), d_cloud_est (estimates), d_cloud_spread (largest distance from that point to
+ *   another estimate of the track; a distance that is not a number does not count). Matches that index outside their frames are ignored. Integers are exact; doubles agree with the
+ *   numpy statement to rounding. root out of range, min_links < 1, a null pointer, total_kp >= 2^31 - 1, a workspace that is not
+ *   256-byte aligned or too small: GMS_ERR_BAD_ARG, nothing run. Stream-ordered on the context's stream; no allocation, no
+ *   synchronisation, no readback (graph-capturable).
+ * gms_sfm_register_workspace_bytes: the workspace for n_pairs pairs over total_kp keypoints and total_matches match slots (0: refused).
+ * gms_sfm_register: plan + the device call on host arrays, synchronous, on the current HIP device; the outputs cover every match
+ *   slot below max(match_off + m) and cloud_cap entries (what the device call leaves untouched is 0). */
+#define GMS_SFM_SKIPPED 1   /* gms_sfm_pair_reg.status of a pair the plan does not use */
+typedef struct gms_sfm_plan_entry {
+    int32_t registers;  /* 1: the pair registers its frame_b                     */
+    int32_t link;       /* the pair it takes its scale from; -1: none            */
+    int32_t role;       /* 0: the shared frame is the link's frame_a, 1: frame_b */
+    int32_t depth;      /* links between the pair and one without a link         */
+} gms_sfm_plan_entry;
+typedef struct gms_sfm_view {
+    double  R[9], t[3];  /* x_camera = R x_world + t; zeros when not registered  */
+    int32_t registered;  /* 1: the root, or registered by an ok pair             */
+    int32_t pair;        /* the pair that registered the frame; -1: none         */
+} gms_sfm_view;
+typedef struct gms_sfm_pair_reg {
+    double  r, S;        /* the pair's scale against its link (0 when not measured) and the cumulative scale (0 when not ok) */
+    int32_t n_links;     /* valid links (0 when either pair has no two-view result)                                           */
+    int32_t depth, link, role;  /* the plan's                                                                                 */
+    int32_t status;      /* GMS_OK, GMS_SFM_SKIPPED or GMS_ERR_NO_MODEL                                                      */
+    int32_t reserved;
+} gms_sfm_pair_reg;
+typedef struct gms_sfm_summary {
+    int64_t n_tracks;      /* tracks (also when more than cloud_cap)                */
+    int64_t n_points;      /* estimates: points of ok pairs that belong to a track  */
+    int64_t n_multi;       /* tracks that hold two keypoints of one frame (kept)    */
+    int32_t n_registered;  /* registered frames, the root included                  */
+    int32_t n_ok_pairs;
+} gms_sfm_summary;
+int gms_sfm_plan(const gms_pair* pairs, int n_pairs, int n_frames, int root, gms_sfm_plan_entry* plan);
+size_t gms_sfm_register_workspace_bytes(int n_frames, int n_pairs, int64_t total_kp, int64_t total_matches);
+int gms_sfm_register_device(gms_ctx* ctx, const int64_t* d_frame_off, int n_frames, int64_t total_kp, const gms_pair* d_pairs,
+                            const gms_sfm_plan_entry* d_plan, int n_pairs, int max_m, int64_t total_matches, const gms_dmatch* d_filtered,
+                            const uint8_t* d_mask, const double* d_points3d, const gms_two_view* d_tv, int root, int min_links,
+                            void* d_ws, size_t ws_bytes, gms_sfm_view* d_views, gms_sfm_pair_reg* d_reg, double* d_points_world,
+                            int32_t* d_track, int64_t cloud_cap, double* d_cloud, int32_t* d_cloud_id, int32_t* d_cloud_obs,
+                            int32_t* d_cloud_est, double* d_cloud_spread, gms_sfm_summary* d_summary);
+int gms_sfm_register(const int64_t* frame_off, int n_frames, const gms_pair* pairs, int n_pairs, const gms_dmatch* filtered,
+                     const uint8_t* mask, const double* points3d, const gms_two_view* tv, int root, int min_links, gms_sfm_view* views,
+                     gms_sfm_pair_reg* reg, double* points_world, int32_t* track, int64_t cloud_cap, double* cloud, int32_t* cloud_id,
+                     int32_t* cloud_obs, int32_t* cloud_est, double* cloud_spread, gms_sfm_summary* summary);
+
 /* ---- ingest format -----------------------------------------------------------------------------------------
  * The reference keeps detector and matcher output in process (std::vector<cv::KeyPoint>, cv::Mat descriptors,
  * std::vector<cv::DMatch>: FeatureMatchUtil.cpp:9-12,58-68; DisparityUtil.cpp:108,137-143) and has no on-disk form. One

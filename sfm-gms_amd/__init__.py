@@ -18,6 +18,8 @@ from .api import matchGMS, matchLOGOS, trainLogosDictionary, bruteForceMatch, st
 from .api import resize, warpAffine, getRotationMatrix2D, imgRotate  # noqa: F401
 from .api import findChessboardCorners, cornerSubPix, calibrateCamera, addChessboardPoints, chessboardObjectPoints  # noqa: F401
 from .types import CHESS_CANDIDATE_DTYPE  # noqa: F401
+from .api import structureFromMotionMulti, registerViews, sfm_plan  # noqa: F401
+from .types import SFM_PLAN_DTYPE, SFM_VIEW_DTYPE, SFM_PAIR_REG_DTYPE, SFM_SUMMARY_DTYPE, GMS_SFM_SKIPPED  # noqa: F401
 from .sharding import all_pairs_count, pair_from_index, shard_range  # noqa: F401
 
 __all__ = [
@@ -27,5 +29,7 @@ __all__ = [
     "stereoSGM", "stereo_match_sgm", "STEREO_SGM_PARAMS_DTYPE", "stereo_sgm_params",
     "portraitMode", "medianBlur", "structureFromMotion", "resize", "warpAffine", "getRotationMatrix2D", "imgRotate", "PORTRAIT_PARAMS_DTYPE", "portrait_params",
     "findChessboardCorners", "cornerSubPix", "calibrateCamera", "addChessboardPoints", "chessboardObjectPoints", "CHESS_CANDIDATE_DTYPE",
+    "structureFromMotionMulti", "registerViews", "sfm_plan", "SFM_PLAN_DTYPE", "SFM_VIEW_DTYPE", "SFM_PAIR_REG_DTYPE", "SFM_SUMMARY_DTYPE",
+    "GMS_SFM_SKIPPED",
     "all_pairs_count", "pair_from_index", "shard_range", "GMS_DESC_HAMMING256", "GMS_DESC_L2_F32X128", "GMS_DETECT_BORDER",
 ]

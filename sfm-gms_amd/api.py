@@ -13,7 +13,8 @@ import numpy as np
 
 from .capi import load_library
 from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, LOGOS_DICT_RESULT_DTYPE, KEYPOINT_DTYPE, PAIR_DTYPE, RESULT_DTYPE, GMS_OK, GMS_ERR_CAPACITY,
-                    GmsError, concat_frames, desc_layout, portrait_params, stereo_bm_params, stereo_sgm_params)
+                    GmsError, SFM_PAIR_REG_DTYPE, SFM_PLAN_DTYPE, SFM_SUMMARY_DTYPE, SFM_VIEW_DTYPE, TWO_VIEW_DTYPE, concat_frames, desc_layout,
+                    portrait_params, stereo_bm_params, stereo_sgm_params)
 
 
 def _as(arr, dtype, name):
@@ -247,6 +248,20 @@ class GmsContext:
         _check(self._lib.gms_disparity_batch_device(self._h, d_kp, d_frame_off, d_wh, int(n_frames), d_pairs, int(n_pairs), int(max_m),
                                                     d_filtered, d_results, d_gt or None, int(gt_stride), int(disp_ratio), d_disparity,
                                                     int(map_stride), d_work, d_stats), self._lib, "gms_disparity_batch_device")
+
+    # -- many views into one frame (include/gms.h) -------------------------------------------------------------------
+    def sfm_register_workspace_bytes(self, n_frames, n_pairs, total_kp, total_matches):
+        return int(self._lib.gms_sfm_register_workspace_bytes(int(n_frames), int(n_pairs), int(total_kp), int(total_matches)))
+
+    def sfm_register_device(self, d_frame_off, n_frames, total_kp, d_pairs, d_plan, n_pairs, max_m, total_matches, d_filtered, d_mask,
+                            d_points3d, d_tv, root, min_links, d_ws, ws_bytes, d_views, d_reg, d_points_world, d_track, cloud_cap, d_cloud,
+                            d_cloud_id, d_cloud_obs, d_cloud_est, d_cloud_spread, d_summary):
+        """gms_sfm_register_device on the pairs, survivors, mask, points and records gms_two_view_batch_device left; d_plan: sfm_plan's
+        records in device memory. Stream-ordered, capturable."""
+        _check(self._lib.gms_sfm_register_device(self._h, d_frame_off, int(n_frames), int(total_kp), d_pairs, d_plan, int(n_pairs), int(max_m),
+                                                 int(total_matches), d_filtered, d_mask, d_points3d, d_tv, int(root), int(min_links), d_ws,
+                                                 int(ws_bytes), d_views, d_reg, d_points_world, d_track, int(cloud_cap), d_cloud, d_cloud_id,
+                                                 d_cloud_obs, d_cloud_est, d_cloud_spread, d_summary), self._lib, "gms_sfm_register_device")
 
     def detect_workspace_bytes(self, width, height, n_images, max_keypoints):
         return int(self._lib.gms_detect_workspace_bytes(int(width), int(height), int(n_images), int(max_keypoints)))
@@ -609,6 +624,93 @@ def structureFromMotion(img1, img2, camera, dist=None, method="logos", ctx=None,
     return dict(points3D=r["points3d"][off:off + int(tv["n_triangulated"])].copy(), R=tv["R"].copy(), t=tv["t"].copy(), E=tv["E"].copy(),
                 matches=r["out"][off:off + k].copy(), mask=r["mask"][off:off + k].copy(), keypoints1=kp[f[0]:f[1]].copy(),
                 keypoints2=kp[f[1]:f[2]].copy(), two_view=tv, detail=r)
+
+
+def sfm_plan(pairs, n_frames, root=0):
+    """gms_sfm_plan (host arithmetic, no device): which pairs of the list register a frame out of `root`, in list order, and which
+    pair each takes its scale from. pairs: PAIR_DTYPE records or (frame_a, frame_b) rows -> SFM_PLAN_DTYPE [n]. A frame index or root
+    out of range raises GmsError(GMS_ERR_BAD_ARG)."""
+    recs = _pair_records(pairs)
+    plan = np.zeros(len(recs), SFM_PLAN_DTYPE)
+    lib = load_library()
+    _check(lib.gms_sfm_plan(recs.ctypes.data, len(recs), int(n_frames), int(root), plan.ctypes.data), lib, "gms_sfm_plan")
+    return plan
+
+
+def _pair_records(pairs):
+    a = np.asarray(pairs)
+    if a.dtype == PAIR_DTYPE:
+        return np.ascontiguousarray(a)
+    fp = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    recs = np.zeros(len(fp), PAIR_DTYPE)
+    recs["frame_a"], recs["frame_b"] = fp[:, 0], fp[:, 1]
+    return recs
+
+
+def sfm_outputs(n_frames, n_pairs, total_matches, cloud_cap):
+    """Zeroed host arrays for the outputs of gms_sfm_register, in the order the C call takes them."""
+    return dict(views=np.zeros(n_frames, SFM_VIEW_DTYPE), registration=np.zeros(n_pairs, SFM_PAIR_REG_DTYPE),
+                points_world=np.zeros((total_matches, 3)), track=np.zeros(total_matches, np.int32), cloud=np.zeros((cloud_cap, 3)),
+                cloud_id=np.zeros(cloud_cap, np.int32), cloud_obs=np.zeros(cloud_cap, np.int32), cloud_est=np.zeros(cloud_cap, np.int32),
+                cloud_spread=np.zeros(cloud_cap), summary=np.zeros(1, SFM_SUMMARY_DTYPE))
+
+
+def sfm_trim(out):
+    """The cloud arrays of a registration cut to the tracks they hold (the summary's n_tracks, at most their capacity)."""
+    n = min(int(out["summary"]["n_tracks"][0]), len(out["cloud_id"]))
+    for k in ("cloud", "cloud_id", "cloud_obs", "cloud_est", "cloud_spread"):
+        out[k] = out[k][:n]
+    return out
+
+
+def registerViews(frame_off, pairs, matches, mask, points3d, two_view, root=0, min_links=8, cloud_cap=None):
+    """gms_sfm_register, the one-shot on host arrays (synchronous, on the current device): the two-view results of many pairs --
+    frame_off int64 [n_frames + 1], pairs PAIR_DTYPE, and matches (DMATCH_DTYPE), mask (uint8), points3d ([.., 3] float64) laid out by
+    the pairs' match_off, two_view TWO_VIEW_DTYPE per pair: pipeline.run_dataset's arrays -- joined into the frame of `root`. Returns
+    dict(plan, views SFM_VIEW_DTYPE per frame, registration SFM_PAIR_REG_DTYPE per pair, points_world, track, cloud, cloud_id,
+    cloud_obs, cloud_est, cloud_spread, summary). Loop closure, bundle adjustment and re-triangulation are not done."""
+    frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
+    recs = _as(pairs, PAIR_DTYPE, "pairs")
+    n_frames, n = len(frame_off) - 1, len(recs)
+    total = int((recs["match_off"] + np.maximum(recs["m"], 0)).max()) if n else 0
+    m = _as(matches, DMATCH_DTYPE, "matches")
+    mk, pts = np.ascontiguousarray(mask, dtype=np.uint8), np.ascontiguousarray(points3d, dtype=np.float64).reshape(-1, 3)
+    tv = _as(two_view, TWO_VIEW_DTYPE, "two_view")
+    if min(len(m), len(mk), len(pts)) < total or len(tv) != n:
+        raise ValueError("matches, mask and points3d cover every pair's match range; one two_view record per pair")
+    cap = max(int(frame_off[-1]) // 2, 0) if cloud_cap is None else int(cloud_cap)
+    out = sfm_outputs(n_frames, n, total, max(cap, 0))   # (a negative capacity is the C call's to refuse)
+    lib = load_library()
+    _check(lib.gms_sfm_register(frame_off.ctypes.data, n_frames, recs.ctypes.data, n, m.ctypes.data, mk.ctypes.data, pts.ctypes.data,
+                                tv.ctypes.data, int(root), int(min_links), *(out[k].ctypes.data for k in ("views", "registration",
+                                "points_world", "track")), cap, *(out[k].ctypes.data for k in ("cloud", "cloud_id", "cloud_obs",
+                                "cloud_est", "cloud_spread", "summary"))), lib, "gms_sfm_register")
+    out["plan"] = sfm_plan(recs, n_frames, root)
+    return sfm_trim(out)
+
+
+def structureFromMotionMulti(images, camera, dist=None, method="gms", pairs=None, root=0, min_links=8, ctx=None, **params):
+    """structureFromMotion for a sequence: n photographs of one size (a list, or [n, H, W] / [n, H, W, 3]) -> every pair's two-view result
+    and the registration that joins them into the frame of image `root` (pipeline.run_images(..., register=True)). pairs: (frame_a,
+    frame_b) rows, default the chain (i, i + 1); they are walked in order, a pair registers frame_b when frame_a is registered.
+    method, camera, dist and params as structureFromMotion (method="gms" runs matchGMS(true, true)). Returns run_images' dict:
+    two_view, points3d, ... per pair, and views, registration, points_world, track, cloud, cloud_obs, cloud_est, cloud_spread, summary.
+    A pair without a pose does not raise here: its registration status says so, and the frames behind it stay unregistered."""
+    from . import pipeline
+    if method not in pipeline.METHODS:
+        raise ValueError(f"unknown method {method!r}")
+    stack, _ = pipeline.image_stack(images)
+    n = stack.shape[0]
+    if pairs is None:
+        pairs = [(i, i + 1) for i in range(n - 1)]
+    opts = dict(params)
+    if method == "gms":
+        opts.setdefault("withRotation", True)
+        opts.setdefault("withScale", True)
+    if method == "logos" and opts.get("dictionary") is None:
+        opts.setdefault("train_dictionary", True)
+    return pipeline.run_images(ctx or default_context(), stack, camera, dist, method=method, pairs=pairs, register=True, root=root,
+                               min_links=min_links, **opts)
 
 
 def default_context():

@@ -956,3 +956,112 @@ def corner_subpix_images(ctx, d_images, image_of, corners, max_iter=30, eps=0.1)
     ctx.corner_subpix_device(d_images.data_ptr(), n, w, h, d_of.data_ptr(), d_pts.data_ptr(), len(pts), 5, max_iter, eps, d_status.data_ptr())
     ctx.synchronize()
     return d_pts.cpu().numpy(), d_status.cpu().numpy()
+
+
+class SfmRegister:
+    """Device buffers of one gms_sfm_register_device call over a fixed pair list: the frame offsets, the pair table, its plan
+    (api.sfm_plan, computed here on the host from the pair list), the workspace and every output, sized once, so that run() can be
+    repeated or captured into a graph. The inputs -- survivors, mask, points and two-view records, as gms_two_view_batch_device
+    leaves them -- are either the caller's device tensors, handed to run(), or the object's own (load() copies host arrays into them;
+    run() without arguments reads them). frame_off: int64 [n_frames + 1] on the host; pairs: PAIR_DTYPE records."""
+
+    def __init__(self, ctx, frame_off, pairs, root=0, min_links=8, cloud_cap=None, device=None, d_frame_off=None, d_pairs=None):
+        from .api import sfm_plan
+        from .types import SFM_PAIR_REG_DTYPE, SFM_SUMMARY_DTYPE, SFM_VIEW_DTYPE, TWO_VIEW_DTYPE
+        self.ctx, self.root, self.min_links = ctx, int(root), int(min_links)
+        self.frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
+        self.recs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
+        self.n_frames, self.n_pairs, self.total_kp = len(self.frame_off) - 1, len(self.recs), int(self.frame_off[-1])
+        if not 0 <= self.root < self.n_frames or self.min_links < 1:
+            raise ValueError("SfmRegister: root is a frame index, min_links at least 1")
+        self.plan = sfm_plan(self.recs, self.n_frames, self.root)   # (refuses a frame index out of range)
+        n = self.n_pairs
+        self.total_m = int((self.recs["match_off"] + np.maximum(self.recs["m"], 0)).max()) if n else 0
+        self.max_m = int(self.recs["m"].max()) if n else 0
+        self.cloud_cap = max(self.total_kp // 2, 0) if cloud_cap is None else int(cloud_cap)
+        self.ws_bytes = ctx.sfm_register_workspace_bytes(self.n_frames, n, self.total_kp, self.total_m)
+        if self.ws_bytes == 0:
+            raise ValueError("SfmRegister: sizes rejected (include/gms.h)")
+        dev = _device(ctx, device)
+        self.device = dev
+        self.d_frame_off = d_frame_off if d_frame_off is not None else torch.from_numpy(self.frame_off).to(dev)
+        self.d_pairs = d_pairs if d_pairs is not None else (_to_dev(self.recs, dev) if n else torch.zeros(24, dtype=torch.uint8, device=dev))
+        self.d_plan = _to_dev(self.plan, dev) if n else torch.zeros(16, dtype=torch.uint8, device=dev)
+        self.d_ws = torch.zeros(self.ws_bytes, dtype=torch.uint8, device=dev)
+        m, cap = max(self.total_m, 1), max(self.cloud_cap, 1)
+        self.d_views = torch.zeros(self.n_frames * SFM_VIEW_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.d_reg = torch.zeros(max(n, 1) * SFM_PAIR_REG_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.d_world = torch.zeros(m * 3, dtype=torch.float64, device=dev)
+        self.d_track = torch.zeros(m, dtype=torch.int32, device=dev)
+        self.d_cloud = torch.zeros(cap * 3, dtype=torch.float64, device=dev)
+        self.d_cloud_id, self.d_cloud_obs, self.d_cloud_est = (torch.zeros(cap, dtype=torch.int32, device=dev) for _ in range(3))
+        self.d_cloud_spread = torch.zeros(cap, dtype=torch.float64, device=dev)
+        self.d_summary = torch.zeros(SFM_SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self._own = None
+        self._tv_bytes = TWO_VIEW_DTYPE.itemsize
+        torch.cuda.synchronize(dev)
+
+    def _own_inputs(self):
+        if self._own is None:
+            m, n, dev = max(self.total_m, 1), max(self.n_pairs, 1), self.device
+            self._own = (torch.zeros(m * 16, dtype=torch.uint8, device=dev), torch.zeros(m, dtype=torch.uint8, device=dev),
+                         torch.zeros(m * 3, dtype=torch.float64, device=dev), torch.zeros(n * self._tv_bytes, dtype=torch.uint8, device=dev))
+        return self._own
+
+    def load(self, matches, mask, points3d, two_view):
+        """Host arrays (run_dataset's out, mask, points3d, two_view) into the object's own input tensors (same tensors every time: a
+        captured run() reads what the latest load() left)."""
+        from .types import TWO_VIEW_DTYPE
+        d_m, d_mask, d_pts, d_tv = self._own_inputs()
+        m = np.ascontiguousarray(matches, dtype=DMATCH_DTYPE)
+        mk = np.ascontiguousarray(mask, dtype=np.uint8)
+        pts = np.ascontiguousarray(points3d, dtype=np.float64).reshape(-1, 3)
+        tv = np.ascontiguousarray(two_view, dtype=TWO_VIEW_DTYPE)
+        if min(len(m), len(mk), len(pts)) < self.total_m or len(tv) != self.n_pairs:
+            raise ValueError("matches, mask and points3d cover every pair's match range; one two_view record per pair")
+        if self.total_m:
+            d_m[:self.total_m * 16].copy_(torch.from_numpy(m[:self.total_m].view(np.uint8).reshape(-1)))
+            d_mask[:self.total_m].copy_(torch.from_numpy(mk[:self.total_m]))
+            d_pts[:self.total_m * 3].copy_(torch.from_numpy(pts[:self.total_m].reshape(-1)))
+        if self.n_pairs:
+            d_tv[:self.n_pairs * self._tv_bytes].copy_(torch.from_numpy(tv.view(np.uint8).reshape(-1)))
+
+    def run(self, d_matches=None, d_mask=None, d_points3d=None, d_tv=None):
+        """gms_sfm_register_device, stream-ordered on the context's stream; no allocation, no synchronisation, no readback."""
+        given = (d_matches, d_mask, d_points3d, d_tv)
+        if any(t is None for t in given):
+            if not all(t is None for t in given):
+                raise ValueError("run: all four input tensors, or none (the object's own)")
+            given = self._own_inputs()
+        d_matches, d_mask, d_points3d, d_tv = given
+        self.ctx.sfm_register_device(self.d_frame_off.data_ptr(), self.n_frames, self.total_kp, self.d_pairs.data_ptr(), self.d_plan.data_ptr(),
+                                     self.n_pairs, self.max_m, self.total_m, d_matches.data_ptr(), d_mask.data_ptr(), d_points3d.data_ptr(),
+                                     d_tv.data_ptr(), self.root, self.min_links, self.d_ws.data_ptr(), self.ws_bytes, self.d_views.data_ptr(),
+                                     self.d_reg.data_ptr(), self.d_world.data_ptr(), self.d_track.data_ptr(), self.cloud_cap,
+                                     self.d_cloud.data_ptr(), self.d_cloud_id.data_ptr(), self.d_cloud_obs.data_ptr(),
+                                     self.d_cloud_est.data_ptr(), self.d_cloud_spread.data_ptr(), self.d_summary.data_ptr())
+
+    def results(self, trim=True):
+        """Waits for the context's stream -> dict(plan, views, registration, points_world, track, cloud, cloud_id, cloud_obs, cloud_est,
+        cloud_spread, summary) on the host; trim: the cloud arrays cut to the tracks they hold."""
+        from .api import sfm_trim
+        from .types import SFM_PAIR_REG_DTYPE, SFM_SUMMARY_DTYPE, SFM_VIEW_DTYPE
+        self.ctx.synchronize()
+        m, cap = self.total_m, self.cloud_cap
+        out = dict(plan=self.plan.copy(), views=self.d_views.cpu().numpy().view(SFM_VIEW_DTYPE).copy(),
+                   registration=self.d_reg.cpu().numpy().view(SFM_PAIR_REG_DTYPE)[:self.n_pairs].copy(),
+                   points_world=self.d_world.cpu().numpy().reshape(-1, 3)[:m].copy(), track=self.d_track.cpu().numpy()[:m].copy(),
+                   cloud=self.d_cloud.cpu().numpy().reshape(-1, 3)[:cap].copy(), cloud_id=self.d_cloud_id.cpu().numpy()[:cap].copy(),
+                   cloud_obs=self.d_cloud_obs.cpu().numpy()[:cap].copy(), cloud_est=self.d_cloud_est.cpu().numpy()[:cap].copy(),
+                   cloud_spread=self.d_cloud_spread.cpu().numpy()[:cap].copy(), summary=self.d_summary.cpu().numpy().view(SFM_SUMMARY_DTYPE).copy())
+        return sfm_trim(out) if trim else out
+
+
+def register_pairs(ctx, frame_off, pairs, matches, mask, points3d, two_view, root=0, min_links=8, cloud_cap=None, device=None):
+    """The convenience call: host arrays of many pairs' two-view results (run_dataset's pairs, out, mask, points3d, two_view and the
+    frames' offsets) -> SfmRegister.results() after one gms_sfm_register_device run."""
+    job = SfmRegister(ctx, frame_off, pairs, root, min_links, cloud_cap, device)
+    job.load(matches, mask, points3d, two_view)
+    torch.cuda.synchronize(job.device)
+    job.run()
+    return job.results()

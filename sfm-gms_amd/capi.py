@@ -35,6 +35,11 @@ SIGNATURES = {
     "gms_triangulate_batch_device": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, vp]),
     "gms_two_view_batch_device": (i32, [vp, vp, dbl, dbl, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "gms_disparity_batch_device": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, i64, i32, vp, i64, vp, vp]),
+    "gms_sfm_plan": (i32, [vp, i32, i32, i32, vp]),
+    "gms_sfm_register_workspace_bytes": (sz, [i32, i32, i64, i64]),
+    "gms_sfm_register_device": (i32, [vp, vp, i32, i64, vp, vp, i32, i32, i64, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp, vp, vp, i64, vp, vp, vp,
+                                      vp, vp, vp]),
+    "gms_sfm_register": (i32, [vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]),
     "gms_dataset_write": (i32, [cstr, vp]),
     "gms_dataset_read": (i32, [cstr, vp]),
     "gms_dataset_free": (None, [vp]),

@@ -26,6 +26,7 @@
 #include "logos_dict_core.h"
 #include "portrait_core.h"
 #include "stereo_bm_core.h"
+#include "sfm_register_core.h"
 #include "stereo_sgm_core.h"
 #include "twoview_core.h"
 #include "warp_core.h"
@@ -1722,6 +1723,116 @@ int gms_disparity_batch_device(gms_ctx* c, const gms_keypoint* d_kp, const int64
         return gms::launch_disparity_batch(d_kp, d_frame_off, d_wh, n_frames, d_pairs, n_pairs, max_m, d_filtered, d_results, d_gt, gt_stride,
                                            disp_ratio, d_disparity, map_stride, d_work, d_stats, c->stream);
     });
+}
+
+// ---- many views into one frame (sfm_register_kernels.hip; the plan and the arithmetic are sfm_register_core.h) ----------------------
+int gms_sfm_plan(const gms_pair* pairs, int n_pairs, int n_frames, int root, gms_sfm_plan_entry* plan)
+{
+    if (n_pairs < 0 || n_frames < 1 || (n_pairs > 0 && (!pairs || !plan))) return GMS_ERR_BAD_ARG;
+    std::vector<int32_t> reg_by((size_t)n_frames);
+    return sfr::plan(pairs, n_pairs, n_frames, root, reg_by.data(), plan) ? GMS_OK : GMS_ERR_BAD_ARG;
+}
+
+static bool sfm_register_sizes_ok(int n_frames, int n_pairs, int64_t total_kp, int64_t total_matches)
+{
+    return n_frames >= 1 && n_pairs >= 0 && total_kp >= 0 && total_kp < INT32_MAX && total_matches >= 0 && total_matches < ((int64_t)1 << 40);
+}
+
+size_t gms_sfm_register_workspace_bytes(int n_frames, int n_pairs, int64_t total_kp, int64_t total_matches)
+{
+    if (!sfm_register_sizes_ok(n_frames, n_pairs, total_kp, total_matches)) return 0;
+    return gms::sfm_register_ws_bytes(n_pairs, total_kp, total_matches);
+}
+
+int gms_sfm_register_device(gms_ctx* c, const int64_t* d_frame_off, int n_frames, int64_t total_kp, const gms_pair* d_pairs,
+                            const gms_sfm_plan_entry* d_plan, int n_pairs, int max_m, int64_t total_matches, const gms_dmatch* d_filtered,
+                            const uint8_t* d_mask, const double* d_points3d, const gms_two_view* d_tv, int root, int min_links, void* d_ws,
+                            size_t ws_bytes, gms_sfm_view* d_views, gms_sfm_pair_reg* d_reg, double* d_points_world, int32_t* d_track,
+                            int64_t cloud_cap, double* d_cloud, int32_t* d_cloud_id, int32_t* d_cloud_obs, int32_t* d_cloud_est,
+                            double* d_cloud_spread, gms_sfm_summary* d_summary)
+{
+    if (!c || !sfm_register_sizes_ok(n_frames, n_pairs, total_kp, total_matches) || max_m < 0 || max_m >= (1 << 24)) return GMS_ERR_BAD_ARG;
+    if (root < 0 || root >= n_frames || min_links < 1 || cloud_cap < 0) return GMS_ERR_BAD_ARG;
+    if (!d_frame_off || !d_ws || !d_views || !d_summary) return GMS_ERR_BAD_ARG;
+    if (n_pairs > 0 && (!d_pairs || !d_plan || !d_tv || !d_reg)) return GMS_ERR_BAD_ARG;
+    if (total_matches > 0 && (!d_filtered || !d_mask || !d_points3d || !d_points_world || !d_track)) return GMS_ERR_BAD_ARG;
+    if (cloud_cap > 0 && (!d_cloud || !d_cloud_id || !d_cloud_obs || !d_cloud_est || !d_cloud_spread)) return GMS_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_ws) & 255u) || ws_bytes < gms::sfm_register_ws_bytes(n_pairs, total_kp, total_matches)) return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] {
+        return gms::launch_sfm_register(d_frame_off, n_frames, total_kp, d_pairs, d_plan, n_pairs, max_m, total_matches, d_filtered, d_mask,
+                                        d_points3d, d_tv, root, min_links, d_ws, d_views, d_reg, d_points_world, d_track, cloud_cap, d_cloud,
+                                        d_cloud_id, d_cloud_obs, d_cloud_est, d_cloud_spread, d_summary, c->stream);
+    });
+}
+
+int gms_sfm_register(const int64_t* frame_off, int n_frames, const gms_pair* pairs, int n_pairs, const gms_dmatch* filtered,
+                     const uint8_t* mask, const double* points3d, const gms_two_view* tv, int root, int min_links, gms_sfm_view* views,
+                     gms_sfm_pair_reg* reg, double* points_world, int32_t* track, int64_t cloud_cap, double* cloud, int32_t* cloud_id,
+                     int32_t* cloud_obs, int32_t* cloud_est, double* cloud_spread, gms_sfm_summary* summary)
+{
+    if (n_frames < 1 || n_pairs < 0 || !frame_off || !views || !summary || root < 0 || root >= n_frames || min_links < 1 || cloud_cap < 0)
+        return GMS_ERR_BAD_ARG;
+    if (n_pairs > 0 && (!pairs || !tv || !reg)) return GMS_ERR_BAD_ARG;
+    if (cloud_cap > 0 && (!cloud || !cloud_id || !cloud_obs || !cloud_est || !cloud_spread)) return GMS_ERR_BAD_ARG;
+    for (int f = 0; f < n_frames; f++)
+        if (frame_off[f] < 0 || frame_off[f + 1] < frame_off[f]) return GMS_ERR_BAD_ARG;
+    std::vector<gms_sfm_plan_entry> plan((size_t)n_pairs);
+    GMS_TRY(gms_sfm_plan(pairs, n_pairs, n_frames, root, plan.data()));
+    int64_t total_m = 0;
+    int max_m = 0;
+    for (int p = 0; p < n_pairs; p++) {
+        if (pairs[p].m < 0 || pairs[p].match_off < 0) return GMS_ERR_BAD_ARG;
+        total_m = std::max(total_m, pairs[p].match_off + (int64_t)pairs[p].m);
+        max_m = std::max(max_m, pairs[p].m);
+    }
+    const int64_t total_kp = frame_off[n_frames];
+    if (!sfm_register_sizes_ok(n_frames, n_pairs, total_kp, total_m) || max_m >= (1 << 24)) return GMS_ERR_BAD_ARG;
+    if (total_m > 0 && (!filtered || !mask || !points3d || !points_world || !track)) return GMS_ERR_BAD_ARG;
+    const size_t M = (size_t)total_m, P = (size_t)n_pairs, Cc = (size_t)cloud_cap;
+    gms::BlockLayout lay;
+    const size_t o_off = lay.add(8 * ((size_t)n_frames + 1)), o_pairs = lay.add(sizeof(gms_pair) * P), o_plan = lay.add(sizeof(gms_sfm_plan_entry) * P);
+    const size_t o_m = lay.add(sizeof(gms_dmatch) * M), o_mask = lay.add(M), o_pts = lay.add(24 * M), o_tv = lay.add(sizeof(gms_two_view) * P);
+    const size_t o_ws = lay.add(gms::sfm_register_ws_bytes(n_pairs, total_kp, total_m));
+    // the outputs, back to back: cleared as one span
+    const size_t o_views = lay.add(sizeof(gms_sfm_view) * (size_t)n_frames), o_reg = lay.add(sizeof(gms_sfm_pair_reg) * P), o_world = lay.add(24 * M);
+    const size_t o_track = lay.add(4 * M), o_cloud = lay.add(24 * Cc), o_id = lay.add(4 * Cc), o_obs = lay.add(4 * Cc), o_est = lay.add(4 * Cc);
+    const size_t o_spread = lay.add(8 * Cc), o_sum = lay.add(sizeof(gms_sfm_summary));
+    DevBlock blk(lay, nullptr);
+    blk.in(o_off, frame_off, 8 * ((size_t)n_frames + 1));
+    if (P) {
+        blk.in(o_pairs, pairs, sizeof(gms_pair) * P);
+        blk.in(o_plan, plan.data(), sizeof(gms_sfm_plan_entry) * P);
+        blk.in(o_tv, tv, sizeof(gms_two_view) * P);
+    }
+    if (M) {
+        blk.in(o_m, filtered, sizeof(gms_dmatch) * M);
+        blk.in(o_mask, mask, M);
+        blk.in(o_pts, points3d, 24 * M);
+    }
+    blk.run([&](hipStream_t st) { return hipMemsetAsync(blk.at(o_views), 0, lay.total() - o_views, st); });
+    blk.run([&](hipStream_t st) {
+        return gms::launch_sfm_register(blk.at<int64_t>(o_off), n_frames, total_kp, blk.at<gms_pair>(o_pairs), blk.at<gms_sfm_plan_entry>(o_plan),
+                                        n_pairs, max_m, total_m, blk.at<gms_dmatch>(o_m), blk.at<uint8_t>(o_mask), blk.at<double>(o_pts),
+                                        blk.at<gms_two_view>(o_tv), root, min_links, blk.at(o_ws), blk.at<gms_sfm_view>(o_views),
+                                        blk.at<gms_sfm_pair_reg>(o_reg), blk.at<double>(o_world), blk.at<int32_t>(o_track), cloud_cap,
+                                        blk.at<double>(o_cloud), blk.at<int32_t>(o_id), blk.at<int32_t>(o_obs), blk.at<int32_t>(o_est),
+                                        blk.at<double>(o_spread), blk.at<gms_sfm_summary>(o_sum), st);
+    });
+    blk.out(views, o_views, sizeof(gms_sfm_view) * (size_t)n_frames);
+    if (P) blk.out(reg, o_reg, sizeof(gms_sfm_pair_reg) * P);
+    if (M) {
+        blk.out(points_world, o_world, 24 * M);
+        blk.out(track, o_track, 4 * M);
+    }
+    if (Cc) {
+        blk.out(cloud, o_cloud, 24 * Cc);
+        blk.out(cloud_id, o_id, 4 * Cc);
+        blk.out(cloud_obs, o_obs, 4 * Cc);
+        blk.out(cloud_est, o_est, 4 * Cc);
+        blk.out(cloud_spread, o_spread, 8 * Cc);
+    }
+    blk.out(summary, o_sum, sizeof(gms_sfm_summary));
+    return blk.finish();
 }
 
 size_t gms_detect_workspace_bytes(int width, int height, int n_images, int max_keypoints)

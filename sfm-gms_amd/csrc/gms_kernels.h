@@ -197,6 +197,14 @@ hipError_t launch_stereo_bm_prefilter(const gms_stereo_bm_params& p, const uint8
                                       int pitch, uint8_t* pre, hipStream_t stream);
 hipError_t launch_stereo_bm_validate(const gms_stereo_bm_params& p, int n, int W, int H, int16_t* d_disp, const int32_t* wcost,
                                      int32_t* d_cost, hipStream_t stream);
+// many two-view results into one frame (sfm_register_kernels.hip; shared arithmetic in sfm_register_core.h)
+size_t     sfm_register_ws_bytes(int n_pairs, int64_t total_kp, int64_t total_m);
+hipError_t launch_sfm_register(const int64_t* d_frame_off, int n_frames, int64_t total_kp, const gms_pair* d_pairs,
+                               const gms_sfm_plan_entry* d_plan, int n_pairs, int max_m, int64_t total_m, const gms_dmatch* d_filtered,
+                               const uint8_t* d_mask, const double* d_points3d, const gms_two_view* d_tv, int root, int min_links,
+                               void* d_ws, gms_sfm_view* d_views, gms_sfm_pair_reg* d_reg, double* d_world, int32_t* d_track,
+                               int64_t cloud_cap, double* d_cloud, int32_t* d_cloud_id, int32_t* d_cloud_obs, int32_t* d_cloud_est,
+                               double* d_cloud_spread, gms_sfm_summary* d_summary, hipStream_t stream);
 // semi-global matching on StereoBM's costs (stereo_sgm_kernels.hip; shared arithmetic in stereo_sgm_core.h); 0 bytes: beyond size_t
 size_t     stereo_sgm_ws_bytes(const gms_stereo_sgm_params& p, int n, int W, int H);
 hipError_t launch_stereo_sgm(const gms_stereo_sgm_params& p, const uint8_t* d_left, const uint8_t* d_right, int n, int W, int H, int pitch,

@@ -301,4 +301,40 @@ inline BfSelectLayout bf_select_layout(int n_pairs, int64_t max_rows, int64_t to
             c.take(4 * rows, 256), c.take(4 * rows, 256), c.end};
 }
 
+// ---- registering many views (sfm_register_kernels.hip) ------------------------------------------------------------------------------
+// K global keypoints, M match slots, P pairs. Every call writes every word it later reads: nothing is carried from call to call.
+constexpr int kSfrScanTile = 4096;  // keypoints per workgroup of the ordered compaction
+inline size_t sfr_hash_slots(size_t total_kp)  // a power of two of at least 2 K: a probe always meets an empty slot
+{
+    size_t s = 64;
+    while (s < 2 * total_kp) s <<= 1;
+    return s;
+}
+struct SfmRegisterLayout {
+    size_t rank;     // int32 [M]: non-zero mask bytes before the match, within its pair
+    size_t rho;      // uint64 [M]: the pair's valid link ratios, as bit patterns, packed at its match_off
+    size_t slot;     // int32 [K]: per keypoint of a registered frame, the lowest match of the registering pair that names it
+    size_t parent;   // int32 [K]: union-find; after the flatten kernel the track id
+    size_t member;   // int32 [K]: 1 when the keypoint is an end of an edge
+    size_t obs;      // uint32 [K]: per root, its keypoints
+    size_t est;      // uint32 [K]: per root, its estimates
+    size_t multi;    // uint32 [K]: per root, 1 when two of its keypoints share a frame
+    size_t repkey;  // uint64 [K]: per root, the least (pair << 32 | rank) of its estimates
+    size_t spread;   // uint64 [K]: per root, the bit pattern of the largest distance
+    size_t hash;     // uint64 [sfr_hash_slots(K)]: (root, frame) keys seen
+    size_t tiles;    // int32 [ceil(K / kSfrScanTile) + 1]: roots per tile, then their exclusive prefix
+    size_t npts;     // int32 [P]: non-zero mask bytes of the pair
+    size_t ok;       // int32 [P]
+    size_t total;
+};
+inline SfmRegisterLayout sfm_register_layout(int n_pairs, int64_t total_kp, int64_t total_matches)
+{
+    const size_t K = (size_t)total_kp, M = (size_t)total_matches, P = (size_t)n_pairs;
+    WsCursor c;
+    return {c.take(4 * M, 256), c.take(8 * M, 256), c.take(4 * K, 256), c.take(4 * K, 256), c.take(4 * K, 256), c.take(4 * K, 256),
+            c.take(4 * K, 256), c.take(4 * K, 256), c.take(8 * K, 256), c.take(8 * K, 256),
+            c.take(8 * sfr_hash_slots(K), 256), c.take(4 * ((K + kSfrScanTile - 1) / kSfrScanTile + 1), 256), c.take(4 * P, 256),
+            c.take(4 * P, 256), c.end};
+}
+
 }  // namespace gms

@@ -432,6 +432,55 @@ inline void stereo_match_sgm(const std::vector<uint8_t>& left, const std::vector
     stereo_match_sgm(left, right, width, height, stereo_sgm_reference_params(), disparity8);
 }
 
+// Many two-view results into one frame (include/gms.h) -- the library's own step behind the batched two-view stage.
+// frame_off: n_frames + 1 keypoint offsets; pairs, matches, mask, points3d (3 doubles per match slot) and two_view as the stage leaves
+// them, laid out by the pairs' match_off. Runs synchronously on the current HIP device (gms_sfm_register). The cloud arrays are cut to
+// the tracks they hold. Loop closure, bundle adjustment and re-triangulation over more than two views are not done.
+struct Registration {
+    std::vector<gms_sfm_view> views;            // one per frame
+    std::vector<gms_sfm_pair_reg> pairs;        // one per pair
+    std::vector<double> points_world;           // 3 per match slot; 0 where a slot holds no point
+    std::vector<int32_t> track;                 // per match slot; -1 without a track
+    std::vector<double> cloud, cloud_spread;    // 3 per track; 1 per track
+    std::vector<int32_t> cloud_id, cloud_obs, cloud_est;
+    gms_sfm_summary summary;
+};
+
+inline Registration registerViews(const std::vector<int64_t>& frame_off, const std::vector<gms_pair>& pairs, const std::vector<gms_dmatch>& matches,
+                                  const std::vector<uint8_t>& mask, const std::vector<double>& points3d, const std::vector<gms_two_view>& two_view,
+                                  int root = 0, int min_links = 8)
+{
+    size_t total = 0;
+    for (const gms_pair& p : pairs)
+        if (p.m > 0 && p.match_off >= 0) total = std::max(total, (size_t)p.match_off + (size_t)p.m);
+    if (frame_off.size() < 2 || two_view.size() != pairs.size() || matches.size() < total || mask.size() < total || points3d.size() < 3 * total)
+        throw std::invalid_argument("mi355::registerViews: offsets of at least one frame, one two-view record per pair, arrays that cover every pair's match range");
+    const int n_frames = (int)frame_off.size() - 1;
+    const size_t cap = frame_off.back() > 0 ? (size_t)frame_off.back() / 2 : 0;
+    Registration r;
+    r.views.resize((size_t)n_frames);
+    r.pairs.resize(pairs.size());
+    r.points_world.assign(3 * total, 0.0);
+    r.track.assign(total, -1);
+    r.cloud.assign(3 * cap, 0.0);
+    r.cloud_spread.assign(cap, 0.0);
+    r.cloud_id.assign(cap, 0);
+    r.cloud_obs.assign(cap, 0);
+    r.cloud_est.assign(cap, 0);
+    const int rc = gms_sfm_register(frame_off.data(), n_frames, pairs.data(), (int)pairs.size(), matches.data(), mask.data(), points3d.data(),
+                                    two_view.data(), root, min_links, r.views.data(), r.pairs.data(), r.points_world.data(), r.track.data(),
+                                    (int64_t)cap, r.cloud.data(), r.cloud_id.data(), r.cloud_obs.data(), r.cloud_est.data(),
+                                    r.cloud_spread.data(), &r.summary);
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::registerViews: ") + gms_error_string(rc));
+    const size_t n = std::min(cap, (size_t)r.summary.n_tracks);
+    r.cloud.resize(3 * n);
+    r.cloud_spread.resize(n);
+    r.cloud_id.resize(n);
+    r.cloud_obs.resize(n);
+    r.cloud_est.resize(n);
+    return r;
+}
+
 // The image tail of the reference's createPortraitMode (DisparityUtil.cpp:317-412): img = the photograph as flat row-major BGR bytes
 // (3 * width * height, cv::Mat's layout after imread), disparity = an 8-bit map with 255 = no value (what gms_disparity_device and
 // stereo_match write); out receives the portrait image in img's layout. medianBlur is cv::medianBlur for 1 or 3 interleaved channels

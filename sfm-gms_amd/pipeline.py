@@ -24,7 +24,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from .batch import (BfSelect, DescriptorTable, DetectPyramid, FrameTable, LogosDictionary, LogosFilter, LogosTable, Warp, _device, _to_dev,
+from .batch import (BfSelect, DescriptorTable, DetectPyramid, FrameTable, LogosDictionary, LogosFilter, LogosTable, SfmRegister, Warp, _device, _to_dev,
                     bf_select_table, bgr_to_gray, frame_counts, frame_pairs_of, logos_dictionary, pair_table, tables_from_detector)
 from .api import getRotationMatrix2D, logos_dict_args
 from .types import (DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128, GMS_ERR_CAPACITY, PAIR_DTYPE, RESULT_DTYPE, TWO_VIEW_DTYPE,
@@ -33,9 +33,12 @@ from .types import (DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128, GMS_
 METHODS = ("gms", "bf", "logos")
 
 
-def _two_view(ctx, frames, d_pairs, n_pairs, max_m, total_m, d_out, d_res, camera, dist, prob, ransac_threshold, max_iters):
+def _two_view(ctx, frames, d_pairs, n_pairs, max_m, total_m, d_out, d_res, camera, dist, prob, ransac_threshold, max_iters, pairs=None,
+              reg=None):
     """gms_two_view_batch_device on the survivors d_out and their gms_pair_result records d_res, laid out by the pair table d_pairs ->
-    the two-view part of run_dataset's result: two_view, coords1, coords2, mask, points3d as host arrays."""
+    the two-view part of run_dataset's result: two_view, coords1, coords2, mask, points3d as host arrays. reg = (root, min_links)
+    (with `pairs`, the host copy of the pair table): gms_sfm_register_device then joins the pairs on the tensors the stage left, in
+    stream order behind it -> also SfmRegister.results()'s arrays (the plan as `register_plan`)."""
     dev = frames.device
     cam = make_camera(camera, dist)
     d_c1 = torch.zeros(max(total_m, 1) * 2, dtype=torch.float32, device=dev)
@@ -47,15 +50,21 @@ def _two_view(ctx, frames, d_pairs, n_pairs, max_m, total_m, d_out, d_res, camer
     ctx.two_view_batch_device(cam, frames.d_kp.data_ptr(), frames.d_frame_off.data_ptr(), frames.n_frames, d_pairs.data_ptr(), n_pairs,
                               max_m, d_out.data_ptr(), d_res.data_ptr(), d_c1.data_ptr(), d_c2.data_ptr(), d_mask.data_ptr(),
                               d_p3.data_ptr(), d_tv.data_ptr(), prob, ransac_threshold, max_iters)
+    joined = {}
+    if reg is not None:
+        job = SfmRegister(ctx, frames.frame_off_host, pairs, reg[0], reg[1], device=dev, d_frame_off=frames.d_frame_off, d_pairs=d_pairs)
+        job.run(d_out, d_mask, d_p3, d_tv)
+        joined = job.results()
+        joined["register_plan"] = joined.pop("plan")
     ctx.synchronize()
-    return dict(two_view=d_tv.cpu().numpy().view(TWO_VIEW_DTYPE)[:n_pairs], coords1=d_c1.cpu().numpy().reshape(-1, 2)[:total_m],
+    return dict(joined, two_view=d_tv.cpu().numpy().view(TWO_VIEW_DTYPE)[:n_pairs], coords1=d_c1.cpu().numpy().reshape(-1, 2)[:total_m],
                 coords2=d_c2.cpu().numpy().reshape(-1, 2)[:total_m], mask=d_mask.cpu().numpy()[:total_m],
                 points3d=d_p3.cpu().numpy().reshape(-1, 3)[:total_m])
 
 
 def run_dataset(ctx, ds, withRotation=False, withScale=False, thresholdFactor=6.0, match=None, camera=None, dist=None, prob=0.7,
                 ransac_threshold=1.0, max_iters=1000, device="cuda:0", method="gms", dictionary=None, logos_capacity=None,
-                cross_check=True, distance_coef=4.0, max_size=500, train_dictionary=None):
+                cross_check=True, distance_coef=4.0, max_size=500, train_dictionary=None, register=False, root=0, min_links=8):
     """(prob, ransac_threshold: findEssentialMat's confidence and threshold as the flow this function restates passes them -- SfMUtil.cpp:39:
     RANSAC, 0.7, 1.0 -- not OpenCV's own default of 0.999, which gms_find_essential_batch_device's Python mirror keeps.)
     ds: io.Dataset. match=None: brute-force match when the file carries descriptors and no matches. camera = (fx, fy, cx, cy)
@@ -69,8 +78,12 @@ def run_dataset(ctx, ds, withRotation=False, withScale=False, thresholdFactor=6.
     method="logos" raises.
     method="bf": bruteForceMatch on the file's descriptors and pairs (cross_check, distance_coef, max_size as the reference's
     4.0 / 500 by default); see _run_bf.
+    register=True (needs a camera): the pairs are then joined into the frame of `root` behind the two-view stage, on the device
+    (gms_sfm_register_device): the pairs are walked in order, a pair registers frame_b when frame_a is registered, and a
+    pair with fewer than min_links scene points shared with the pair it hangs on fails. Adds views, registration, points_world, track,
+    cloud, cloud_id, cloud_obs, cloud_est, cloud_spread, summary and register_plan. register=False returns the dict without them.
     The stages themselves work on resident tables (_run_gms, _run_bf, _run_logos): run_images feeds them from pixels."""
-    tail = (camera, dist, prob, ransac_threshold, max_iters)
+    tail = (camera, dist, prob, ransac_threshold, max_iters, _register_args(register, root, min_links, camera))
     if method == "bf":
         if ds.descriptors is None:
             raise ValueError("method='bf' needs the dataset's descriptors")
@@ -106,7 +119,8 @@ def run_dataset(ctx, ds, withRotation=False, withScale=False, thresholdFactor=6.
     return _run_gms(ctx, frames, descs, ds.pairs, ds.matches, withRotation, withScale, thresholdFactor, *tail)
 
 
-def _run_gms(ctx, frames, descs, src_pairs, matches, withRotation, withScale, thresholdFactor, camera, dist, prob, ransac_threshold, max_iters):
+def _run_gms(ctx, frames, descs, src_pairs, matches, withRotation, withScale, thresholdFactor, camera, dist, prob, ransac_threshold, max_iters,
+             reg=None):
     """The GMS flow on resident tables: putative matches (descs: a DescriptorTable, whose matcher gives every keypoint of frame_a one
     match -- BFMatcher::match without cross-check, FeatureMatchUtil.cpp:66-68; descs None: the host array `matches`, laid out by the
     pairs' match_off) -> gms_filter_device -> two-view with a camera. Returns run_dataset's record."""
@@ -136,11 +150,23 @@ def _run_gms(ctx, frames, descs, src_pairs, matches, withRotation, withScale, th
                       d_matches.data_ptr(), d_out.data_ptr(), d_res.data_ptr(), None, withRotation, withScale, thresholdFactor)
     out = dict(pairs=pairs)
     if camera is not None:
-        out.update(_two_view(ctx, frames, d_pairs, n_pairs, max_m, total_m, d_out, d_res, camera, dist, prob, ransac_threshold, max_iters))
+        out.update(_two_view(ctx, frames, d_pairs, n_pairs, max_m, total_m, d_out, d_res, camera, dist, prob, ransac_threshold, max_iters,
+                             pairs, reg))
     ctx.synchronize()
     out.update(matches=d_matches.cpu().numpy().view(DMATCH_DTYPE)[:total_m], out=d_out.cpu().numpy().view(DMATCH_DTYPE)[:total_m],
                results=d_res.cpu().numpy().view(RESULT_DTYPE)[:n_pairs])
     return out
+
+
+def _register_args(register, root, min_links, camera):
+    """run_dataset's register / root / min_links -> None or (root, min_links), checked before anything is launched."""
+    if not register:
+        return None
+    if camera is None:
+        raise ValueError("register=True needs a camera: it joins the two-view results")
+    if int(min_links) < 1 or int(root) < 0:
+        raise ValueError("root: a frame index; min_links: at least 1")
+    return int(root), int(min_links)
 
 
 def image_stack(images):
@@ -184,7 +210,7 @@ def _train_dictionary_device(ctx, descs, opts):
 def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, threshold=20, max_keypoints=10000, n_levels=8,
                descriptor="grad", withRotation=False, withScale=False, thresholdFactor=6.0, prob=0.7, ransac_threshold=1.0, max_iters=1000,
                device=None, dictionary=None, logos_capacity=None, cross_check=True, distance_coef=4.0, max_size=500, train_dictionary=None,
-               keep_tables=False, detector="fast", contrast=128, refine=False):
+               keep_tables=False, detector="fast", contrast=128, refine=False, register=False, root=0, min_links=8):
     """run_dataset from pixels. images: [n, H, W] grey or [n, H, W, 3] BGR, 8-bit, a host array or a device tensor (or a list of equally
     sized images). BGR goes through gms_bgr_to_gray_device; the pyramid keypoint source (threshold, max_keypoints, n_levels; detector
     "fast", or "dog" with `contrast` in the place of `threshold`: gms_detect_dog_batch_device, with refine=True
@@ -192,13 +218,17 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
     device, gms_detect_pack_device puts them back to back, and the tables are built there: between the pixels and the results only the
     n + 1 frame offsets (and the status records the stages already read) come back. pairs: (frame_a, frame_b) rows or PAIR_DTYPE
     records; default every a < b. The other arguments and the returned records are run_dataset's (the matcher always runs: there are
-    no matches to bring); keep_tables=True adds `tables` = (FrameTable, DescriptorTable), the resident keypoints and rows."""
+    no matches to bring); keep_tables=True adds `tables` = (FrameTable, DescriptorTable), the resident keypoints and rows.
+    register, root, min_links: run_dataset's."""
     if method not in METHODS:
         raise ValueError(f"unknown method {method!r}")
     if descriptor not in ("brief", "grad", "both"):
         raise ValueError('descriptor: "brief", "grad" or "both"')
     images, is_bgr = image_stack(images)
     n, h, w = images.shape[:3]
+    reg = _register_args(register, root, min_links, camera)
+    if reg is not None and not 0 <= reg[0] < n:
+        raise ValueError("root: a frame index")
     if pairs is None:
         pairs = [(a, b) for a in range(n) for b in range(a + 1, n)]
     src = np.asarray(pairs)
@@ -212,7 +242,7 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
     source.run(d_images)
     kind = GMS_DESC_HAMMING256 if descriptor == "brief" else GMS_DESC_L2_F32X128
     frames, descs = tables_from_detector(source, [(w, h)] * n, kind)
-    tail = (camera, dist, prob, ransac_threshold, max_iters)
+    tail = (camera, dist, prob, ransac_threshold, max_iters, reg)
     if method == "bf":
         r = _run_bf(ctx, descs, src, cross_check, distance_coef, max_size, *tail)
     elif method == "logos":
@@ -381,7 +411,7 @@ def _train_dictionary(ctx, ds, opts, device):
     return dic[0], rec[0]
 
 
-def _run_logos(ctx, frames, d_desc, kind, src_pairs, dictionary, capacity, camera, dist, prob, ransac_threshold, max_iters):
+def _run_logos(ctx, frames, d_desc, kind, src_pairs, dictionary, capacity, camera, dist, prob, ransac_threshold, max_iters, reg=None):
     """The LOGOS flow on resident tables: the rows d_desc (a device tensor, row i of keypoint i of `frames`; None without keypoints)
     -> words (the exact nearest row of `dictionary`, a host array or a device tensor of rows like the descriptors) -> one LOGOS table
     for all frames -> every pair in one filter run -> two-view with a camera. Pair p gets room for `capacity` survivors (default: the
@@ -427,13 +457,13 @@ def _run_logos(ctx, frames, d_desc, kind, src_pairs, dictionary, capacity, camer
     out = dict(pairs=pairs, logos_results=lres, words=d_words.cpu().numpy()[:total_kp])
     if camera is not None:
         out.update(_two_view(ctx, frames, job.d_pairs, n_pairs, int(cap.max()) if n_pairs else 0, total_m, job.d_out, job.d_pres, camera,
-                             dist, prob, ransac_threshold, max_iters))
+                             dist, prob, ransac_threshold, max_iters, pairs, reg))
     res_out, _, pres = job.results()
     out.update(matches=np.zeros(0, DMATCH_DTYPE), out=res_out, results=pres)
     return out
 
 
-def _run_bf(ctx, descs, src_pairs, cross_check, distance_coef, max_size, camera, dist, prob, ransac_threshold, max_iters):
+def _run_bf(ctx, descs, src_pairs, cross_check, distance_coef, max_size, camera, dist, prob, ransac_threshold, max_iters, reg=None):
     """The bruteForceMatch flow on a resident DescriptorTable: every pair's survivors in one gms_bf_select_device run -> two-view with
     a camera. Pair p gets room for min(max_size, n(frame_a)) survivors, which its K never exceeds. Returns what run_dataset returns
     (`matches` empty: the putative matches stay in the workspace), plus bf_results (BF_RESULT_DTYPE per pair); `results` are
@@ -451,7 +481,7 @@ def _run_bf(ctx, descs, src_pairs, cross_check, distance_coef, max_size, camera,
     out = dict(pairs=pairs)
     if camera is not None:
         out.update(_two_view(ctx, frames, run.d_pairs, n_pairs, max_m, total_m, run.d_out, run.d_pres, camera, dist, prob,
-                             ransac_threshold, max_iters))
+                             ransac_threshold, max_iters, pairs, reg))
     res_out, bf_res, pres = run.results()
     out.update(matches=np.zeros(0, DMATCH_DTYPE), out=res_out[:total_m], results=pres, bf_results=bf_res)
     return out

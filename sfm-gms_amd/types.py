@@ -136,6 +136,16 @@ TWO_VIEW_DTYPE = np.dtype([("E", "<f8", (3, 3)), ("R", "<f8", (3, 3)), ("t", "<f
                            ("n_pose", "<i4"), ("pose_which", "<i4"), ("n_triangulated", "<i4"), ("status", "<i4"), ("reserved", "<i4")])
 assert CAMERA_DTYPE.itemsize == 72 and TWO_VIEW_DTYPE.itemsize == 232
 
+# gms_sfm_plan_entry / gms_sfm_view / gms_sfm_pair_reg / gms_sfm_summary (include/gms.h): many views into one frame
+GMS_SFM_SKIPPED = 1
+SFM_PLAN_DTYPE = np.dtype([("registers", "<i4"), ("link", "<i4"), ("role", "<i4"), ("depth", "<i4")])
+SFM_VIEW_DTYPE = np.dtype([("R", "<f8", (3, 3)), ("t", "<f8", (3,)), ("registered", "<i4"), ("pair", "<i4")])
+SFM_PAIR_REG_DTYPE = np.dtype([("r", "<f8"), ("S", "<f8"), ("n_links", "<i4"), ("depth", "<i4"), ("link", "<i4"), ("role", "<i4"),
+                               ("status", "<i4"), ("reserved", "<i4")])
+SFM_SUMMARY_DTYPE = np.dtype([("n_tracks", "<i8"), ("n_points", "<i8"), ("n_multi", "<i8"), ("n_registered", "<i4"), ("n_ok_pairs", "<i4")])
+assert SFM_PLAN_DTYPE.itemsize == 16 and SFM_VIEW_DTYPE.itemsize == 104 and SFM_PAIR_REG_DTYPE.itemsize == 40
+assert SFM_SUMMARY_DTYPE.itemsize == 32
+
 
 def make_camera(camera, dist=None):
     """(fx, fy, cx, cy) and (k1, k2, p1, p2, k3) or None -> a CAMERA_DTYPE record (cameraMatrix / distCoeffs of SfMUtil.cpp:4)."""

@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""A sequence of photographs to poses, tracks and one cloud, every stage on the GPU (structureFromMotionMulti in sfm-gms_amd/api.py ->
+pipeline.run_images(register=True): per pair the two-view stage, then gms_sfm_register_device joins the pairs).
+Prints one JSON line: per pair n_links, r, S and status; per view the camera centre; tracks by length; the median spread.
+
+    python tools/gms_sfm_sequence.py [images.npz] [--method gms|bf|logos] [--pairs chain|star|all] [--root 0] [--min-links 8] [--max-keypoints 2000] [--ply out.ply] [--check]
+
+images.npz: arrays images ([n, H, W] grey or [n, H, W, 3] BGR, uint8) and camera = (fx, fy, cx, cy), optionally dist. Default: views
+1, 2, 3, 4 of the reference's SourceImages scene from the two committed fixtures (tests/golden/image_sfm_pair_1008x756.npz holds views 1
+and 4, image_sfm_more_1008x756.npz views 2 and 3), with the pair's stated camera. --pairs: chain (i, i + 1); star (root, i); all:
+every a < b in order (the pairs that close a loop are skipped by the plan). --ply: the cloud as an ASCII PLY file (x, y, z, and the
+track's keypoint count as `obs`). --check: feeds the GPU's own two-view records to the numpy statement (tests/sfm_register_ref.py)
+and compares: integers exactly, doubles to 1e-9; test infrastructure."""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def default_images():
+    a, b = np.load(os.path.join(GOLDEN, "image_sfm_pair_1008x756.npz")), np.load(os.path.join(GOLDEN, "image_sfm_more_1008x756.npz"))
+    return np.stack([a["left"], b["second"], b["third"], a["right"]]), tuple(float(v) for v in a["camera"]), None
+
+
+def pair_list(kind, n, root):
+    if kind == "chain":
+        return [(i, i + 1) for i in range(n - 1)]
+    if kind == "star":
+        return [(root, i) for i in range(n) if i != root]
+    return [(a, b) for a in range(n) for b in range(a + 1, n)]
+
+
+def write_ply(path, cloud, obs):
+    keep = np.isfinite(cloud).all(1)
+    with open(path, "w") as f:
+        f.write(f"ply\nformat ascii 1.0\nelement vertex {int(keep.sum())}\nproperty double x\nproperty double y\nproperty double z\nproperty int obs\nend_header\n")
+        for p, o in zip(cloud[keep], obs[keep]):
+            f.write(f"{p[0]:.9g} {p[1]:.9g} {p[2]:.9g} {int(o)}\n")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("images", nargs="?")
+    ap.add_argument("--method", choices=("gms", "bf", "logos"), default="gms")
+    ap.add_argument("--pairs", choices=("chain", "star", "all"), default="chain")
+    ap.add_argument("--root", type=int, default=0)
+    ap.add_argument("--min-links", type=int, default=8)
+    ap.add_argument("--max-keypoints", type=int, default=2000)
+    ap.add_argument("--ply")
+    ap.add_argument("--check", action="store_true")
+    a = ap.parse_args()
+    if a.images:
+        z = np.load(a.images)
+        images, camera = np.ascontiguousarray(z["images"], dtype=np.uint8), tuple(float(v) for v in z["camera"])
+        dist = tuple(float(v) for v in z["dist"]) if "dist" in z.files else None
+    else:
+        images, camera, dist = default_images()
+    n = len(images)
+    if not 0 <= a.root < n:
+        ap.error("--root: a frame index")
+    pairs = pair_list(a.pairs, n, a.root)
+    pkg = importlib.import_module("sfm-gms_amd")
+    r = pkg.structureFromMotionMulti(images, camera, dist, method=a.method, pairs=pairs, root=a.root, min_links=a.min_links,
+                                     max_keypoints=a.max_keypoints, keep_tables=True)
+    reg, views, tv = r["registration"], r["views"], r["two_view"]
+    centres = [None if not v["registered"] else [round(float(x), 5) for x in -v["R"].T @ v["t"]] for v in views]
+    obs, spread, cloud = r["cloud_obs"], r["cloud_spread"], r["cloud"]
+    depth = cloud[:, 2][np.isfinite(cloud[:, 2])]
+    many = spread[r["cloud_est"] > 1]
+    line = {"images": [int(n), int(images.shape[2]), int(images.shape[1])], "method": a.method, "pairs": a.pairs, "root": a.root,
+            "min_links": a.min_links, "max_keypoints": a.max_keypoints, "keypoints": np.diff(r["tables"][0].frame_off_host).tolist(),
+            "per_pair": [{"pair": [int(p["frame_a"]), int(p["frame_b"])], "survivors": int(t["n_points"]), "points": int(t["n_triangulated"]),
+                          "two_view_status": int(t["status"]), "status": int(g["status"]), "n_links": int(g["n_links"]),
+                          "r": round(float(g["r"]), 6), "S": round(float(g["S"]), 6)} for p, t, g in zip(r["pairs"], tv, reg)],
+            "camera_centres": centres, "registered": int(r["summary"]["n_registered"][0]), "ok_pairs": int(r["summary"]["n_ok_pairs"][0]),
+            "tracks": int(r["summary"]["n_tracks"][0]), "estimates": int(r["summary"]["n_points"][0]),
+            "tracks_with_two_keypoints_of_a_frame": int(r["summary"]["n_multi"][0]),
+            "tracks_by_keypoints": {str(k): int(c) for k, c in enumerate(np.bincount(obs, minlength=3)) if k >= 2 and c},
+            "median_depth": None if not len(depth) else round(float(np.median(depth)), 5),
+            "median_spread": None if not len(many) else round(float(np.median(many)), 6),
+            "median_spread_over_median_depth": None if not len(many) or not len(depth) else round(float(np.median(many) / np.median(depth)), 6)}
+    ok = True
+    if a.check:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import sfm_register_ref as ref
+        want = ref.register(r["tables"][0].frame_off_host, r["pairs"], r["out"], r["mask"], r["points3d"], tv, a.root, a.min_links)
+
+        def near(x, y, size=0.0):
+            x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+            fin = np.isfinite(x) & np.isfinite(y)
+            same = (x[~fin] == y[~fin]) | (np.isnan(x[~fin]) & np.isnan(y[~fin]))
+            return bool(x.shape == y.shape and same.all() and (np.abs(x[fin] - y[fin]) <= 1e-9 * np.maximum(np.maximum(np.abs(x[fin]), np.abs(y[fin])), size)).all())
+        fin = want["cloud"][np.isfinite(want["cloud"])]
+        chk = {"plan": r["register_plan"].tobytes() == want["plan"].tobytes(),
+               "pair_integers": all(np.array_equal(reg[f], want["registration"][f]) for f in ("n_links", "depth", "link", "role", "status")),
+               "scales_1e-9": near(reg["r"], want["registration"]["r"]) and near(reg["S"], want["registration"]["S"]),
+               "views_1e-9": near(views["R"], want["views"]["R"], 1.0) and near(views["t"], want["views"]["t"], 1.0)
+               and np.array_equal(views["registered"], want["views"]["registered"]),
+               "points_1e-9": near(r["points_world"], want["points_world"][:len(r["points_world"])], 1.0),
+               "tracks": bool(np.array_equal(r["track"], want["track"][:len(r["track"])])),
+               "cloud": bool(np.array_equal(r["cloud_id"], want["cloud_id"]) and np.array_equal(obs, want["cloud_obs"])
+                             and np.array_equal(r["cloud_est"], want["cloud_est"]) and near(cloud, want["cloud"], 1.0)
+                             and near(spread, want["cloud_spread"], 1.0 + (np.abs(fin).max() if fin.size else 0.0))),
+               "summary": r["summary"].tobytes() == want["summary"].tobytes()}
+        line["check_vs_statement"] = {k: bool(v) for k, v in chk.items()}
+        ok = all(chk.values())
+    if a.ply:
+        write_ply(a.ply, cloud, obs)
+    print(json.dumps(line))
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
