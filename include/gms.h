@@ -455,6 +455,60 @@ int gms_sfm_register(const int64_t* frame_off, int n_frames, const gms_pair* pai
                      gms_sfm_pair_reg* reg, double* points_world, int32_t* track, int64_t cloud_cap, double* cloud, int32_t* cloud_id,
                      int32_t* cloud_obs, int32_t* cloud_est, double* cloud_spread, gms_sfm_summary* summary);
 
+/* ---- bundle adjustment behind the registration (the library's own; tests/sfm_ba_ref.py is the definition) --------
+ * Refines the registered views and the cloud over all the keypoints a track chains together. Inputs: the keypoints, d_frame_off,
+ * d_pairs, the survivors d_filtered and d_mask as the two-view stage took and left them, and d_views, d_reg, d_track, d_cloud,
+ * d_cloud_id and d_reg_summary as gms_sfm_register_device left them (cloud_cap: the capacity of that call).
+ *   Observations: a keypoint belongs to cloud entry c when a match of an ok pair (d_reg status GMS_OK) with a non-zero mask byte and
+ *   both indices inside their frames names it and d_track at the match's slot (match_off + rank) is d_cloud_id[c], c below
+ *   min(n_tracks, cloud_cap). Its measurement is cv::undistortPoints of its pt. A track with two keypoints of one frame, or with fewer
+ *   than two observations, is excluded whole: its point comes back unchanged. Sums over a track's or a frame's observations run in
+ *   ascending global keypoint index or in a tree fixed by the counts; no floating-point atomics: the same bytes run after run.
+ *   retriangulate: X = (sum (I - d d^T))^-1 sum (I - d d^T) c over a track's rays first; taken when finite and in front of every
+ *   camera that sees the track, otherwise the cloud's point stays (status 3). Residual r = f (pi(R X + t) - (u, v)), f = (fx + fy) / 2,
+ *   inactive at z <= 0 or a non-finite camera point; Huber weights at huber_px (0: none). Parameters: (omega, tau) of every registered
+ *   frame but the root (R <- exp([omega]x) R, t <- t + tau) and every used track's point. Levenberg-Marquardt with lambda diag
+ *   damping, points eliminated, the reduced camera system by conjugate gradients preconditioned with its 6 x 6 diagonal blocks,
+ *   Schur-implicit, at most n_cg iterations, done at r.z <= cg_tol^2 r0.z0. A step is accepted when the Huber cost falls and no
+ *   observation turns inactive (lambda <- max(lambda / 10, 1e-12)), else dropped (lambda <- 10 lambda); done when an accepted step
+ *   lowers the cost by no more than ftol cost. n_iters outer iterations are always launched (flags on the device turn the rest into
+ *   no-ops). At the end (n_iters > 0) every t and every refined point is multiplied by one factor that puts the camera of the first ok
+ *   pair without a link at distance 1 from the root. n_iters = 0: re-triangulation and the statistics alone.
+ * Outputs: d_views_out (n_frames records; d_views is not written), d_cloud_out (3 doubles per cloud entry), d_track_status (int32 per
+ *   cloud entry: 0 refined, 1 excluded: two keypoints of a frame, 2 excluded: fewer than two observations, 3 refined from its cloud
+ *   point: re-triangulation was refused) and one gms_sfm_ba_summary. A null pointer, n_iters < 0, n_cg < 1, a negative or non-finite
+ *   lambda0, cg_tol, ftol or huber_px, total_kp or cloud_cap >= 2^31 - 1, more than 2^24 frames, a workspace that is not 256-byte aligned or too small:
+ *   GMS_ERR_BAD_ARG, nothing run. Stream-ordered on the context's stream; no allocation, no synchronisation, no readback
+ *   (graph-capturable); 12 + n_iters (8 + 3 n_cg) launches.
+ * gms_sfm_ba: the same on host arrays, synchronous, on the current HIP device; n_tracks: the registration summary's. */
+typedef struct gms_sfm_ba_params {
+    double  lambda0, cg_tol, ftol, huber_px;   /* 1e-3, 1e-8, 1e-10, 2.0 */
+    int32_t n_iters, n_cg, retriangulate;      /* 10, 50, 1              */
+    int32_t reserved;
+} gms_sfm_ba_params;
+typedef struct gms_sfm_ba_summary {
+    double  cost0, cost;          /* Huber cost in px^2 before (after re-triangulation) and after                  */
+    double  rms0_px, rms_px;      /* unweighted, over the active observations                                      */
+    double  lambda;               /* the damping the last iteration left                                           */
+    int64_t n_obs, n_active;      /* observations of the used tracks; those active at the end                      */
+    int64_t n_tracks_used, n_tracks_multi;
+    int32_t n_frames_free;        /* registered frames other than the root                                         */
+    int32_t iters_run, iters_accepted, cg_iters;
+    int32_t status;               /* GMS_OK, or GMS_ERR_NO_MODEL when no observation is active                     */
+    int32_t reserved;
+} gms_sfm_ba_summary;
+size_t gms_sfm_ba_workspace_bytes(int n_frames, int n_pairs, int64_t total_kp, int64_t cloud_cap);
+int gms_sfm_ba_device(gms_ctx* ctx, const gms_camera* camera, const gms_sfm_ba_params* params, const gms_keypoint* d_kp,
+                      const int64_t* d_frame_off, int n_frames, int64_t total_kp, const gms_pair* d_pairs, int n_pairs,
+                      int64_t total_matches, const gms_dmatch* d_filtered, const uint8_t* d_mask, const gms_sfm_view* d_views,
+                      const gms_sfm_pair_reg* d_reg, const int32_t* d_track, int64_t cloud_cap, const double* d_cloud,
+                      const int32_t* d_cloud_id, const gms_sfm_summary* d_reg_summary, void* d_ws, size_t ws_bytes,
+                      gms_sfm_view* d_views_out, double* d_cloud_out, int32_t* d_track_status, gms_sfm_ba_summary* d_summary);
+int gms_sfm_ba(const gms_camera* camera, const gms_sfm_ba_params* params, const gms_keypoint* kp, const int64_t* frame_off, int n_frames,
+               const gms_pair* pairs, int n_pairs, const gms_dmatch* filtered, const uint8_t* mask, const gms_sfm_view* views,
+               const gms_sfm_pair_reg* reg, const int32_t* track, int64_t cloud_cap, const double* cloud, const int32_t* cloud_id,
+               int64_t n_tracks, gms_sfm_view* views_out, double* cloud_out, int32_t* track_status, gms_sfm_ba_summary* summary);
+
 /* ---- ingest format -----------------------------------------------------------------------------------------
  * The reference keeps detector and matcher output in process (std::vector<cv::KeyPoint>, cv::Mat descriptors,
  * std::vector<cv::DMatch>: FeatureMatchUtil.cpp:9-12,58-68; DisparityUtil.cpp:108,137-143) and has no on-disk form. One

@@ -20,6 +20,9 @@ from .api import findChessboardCorners, cornerSubPix, calibrateCamera, addChessb
 from .types import CHESS_CANDIDATE_DTYPE  # noqa: F401
 from .api import structureFromMotionMulti, registerViews, sfm_plan  # noqa: F401
 from .types import SFM_PLAN_DTYPE, SFM_VIEW_DTYPE, SFM_PAIR_REG_DTYPE, SFM_SUMMARY_DTYPE, GMS_SFM_SKIPPED  # noqa: F401
+from .api import bundleAdjust  # noqa: F401
+from .types import (SFM_BA_PARAMS_DTYPE, SFM_BA_SUMMARY_DTYPE, SFM_BA_REFINED, SFM_BA_MULTI, SFM_BA_FEW, SFM_BA_KEPT, SFM_BA_DEFAULTS,  # noqa: F401
+                    sfm_ba_params)
 from .sharding import all_pairs_count, pair_from_index, shard_range  # noqa: F401
 
 __all__ = [
@@ -30,6 +33,7 @@ __all__ = [
     "portraitMode", "medianBlur", "structureFromMotion", "resize", "warpAffine", "getRotationMatrix2D", "imgRotate", "PORTRAIT_PARAMS_DTYPE", "portrait_params",
     "findChessboardCorners", "cornerSubPix", "calibrateCamera", "addChessboardPoints", "chessboardObjectPoints", "CHESS_CANDIDATE_DTYPE",
     "structureFromMotionMulti", "registerViews", "sfm_plan", "SFM_PLAN_DTYPE", "SFM_VIEW_DTYPE", "SFM_PAIR_REG_DTYPE", "SFM_SUMMARY_DTYPE",
-    "GMS_SFM_SKIPPED",
+    "GMS_SFM_SKIPPED", "bundleAdjust", "SFM_BA_PARAMS_DTYPE", "SFM_BA_SUMMARY_DTYPE", "SFM_BA_REFINED", "SFM_BA_MULTI", "SFM_BA_FEW",
+    "SFM_BA_KEPT", "SFM_BA_DEFAULTS", "sfm_ba_params",
     "all_pairs_count", "pair_from_index", "shard_range", "GMS_DESC_HAMMING256", "GMS_DESC_L2_F32X128", "GMS_DETECT_BORDER",
 ]

@@ -263,6 +263,20 @@ class GmsContext:
                                                  int(ws_bytes), d_views, d_reg, d_points_world, d_track, int(cloud_cap), d_cloud, d_cloud_id,
                                                  d_cloud_obs, d_cloud_est, d_cloud_spread, d_summary), self._lib, "gms_sfm_register_device")
 
+    # -- bundle adjustment behind the registration (include/gms.h) --------------------------------------------------
+    def sfm_ba_workspace_bytes(self, n_frames, n_pairs, total_kp, cloud_cap):
+        return int(self._lib.gms_sfm_ba_workspace_bytes(int(n_frames), int(n_pairs), int(total_kp), int(cloud_cap)))
+
+    def sfm_ba_device(self, camera, params, d_kp, d_frame_off, n_frames, total_kp, d_pairs, n_pairs, total_matches, d_filtered, d_mask, d_views,
+                      d_reg, d_track, cloud_cap, d_cloud, d_cloud_id, d_reg_summary, d_ws, ws_bytes, d_views_out, d_cloud_out, d_track_status,
+                      d_summary):
+        """gms_sfm_ba_device on what gms_two_view_batch_device and gms_sfm_register_device left; camera: a CAMERA_DTYPE record, params: a
+        SFM_BA_PARAMS_DTYPE record (host values). Stream-ordered, capturable."""
+        _check(self._lib.gms_sfm_ba_device(self._h, None if camera is None else camera.ctypes.data, None if params is None else params.ctypes.data,
+                                           d_kp, d_frame_off, int(n_frames), int(total_kp), d_pairs, int(n_pairs), int(total_matches), d_filtered,
+                                           d_mask, d_views, d_reg, d_track, int(cloud_cap), d_cloud, d_cloud_id, d_reg_summary, d_ws, int(ws_bytes),
+                                           d_views_out, d_cloud_out, d_track_status, d_summary), self._lib, "gms_sfm_ba_device")
+
     def detect_workspace_bytes(self, width, height, n_images, max_keypoints):
         return int(self._lib.gms_detect_workspace_bytes(int(width), int(height), int(n_images), int(max_keypoints)))
 
@@ -668,7 +682,8 @@ def registerViews(frame_off, pairs, matches, mask, points3d, two_view, root=0, m
     frame_off int64 [n_frames + 1], pairs PAIR_DTYPE, and matches (DMATCH_DTYPE), mask (uint8), points3d ([.., 3] float64) laid out by
     the pairs' match_off, two_view TWO_VIEW_DTYPE per pair: pipeline.run_dataset's arrays -- joined into the frame of `root`. Returns
     dict(plan, views SFM_VIEW_DTYPE per frame, registration SFM_PAIR_REG_DTYPE per pair, points_world, track, cloud, cloud_id,
-    cloud_obs, cloud_est, cloud_spread, summary). Loop closure, bundle adjustment and re-triangulation are not done."""
+    cloud_obs, cloud_est, cloud_spread, summary). Loop closure is not done; re-triangulation over all views and
+    bundle adjustment are bundleAdjust's, on this call's result."""
     frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
     recs = _as(pairs, PAIR_DTYPE, "pairs")
     n_frames, n = len(frame_off) - 1, len(recs)
@@ -689,13 +704,45 @@ def registerViews(frame_off, pairs, matches, mask, points3d, two_view, root=0, m
     return sfm_trim(out)
 
 
-def structureFromMotionMulti(images, camera, dist=None, method="gms", pairs=None, root=0, min_links=8, ctx=None, **params):
+def bundleAdjust(keypoints, frame_off, pairs, matches, mask, registration, camera, dist=None, **ba):
+    """gms_sfm_ba, the one-shot on host arrays (synchronous, on the current device): bundle adjustment behind registerViews (DESIGN.md
+    4.10c). keypoints: KEYPOINT_DTYPE, all frames back to back; frame_off, pairs, matches, mask as registerViews took them;
+    registration: its dict (views, registration, track, cloud, cloud_id, summary); camera = (fx, fy, cx, cy), dist = (k1, k2, p1, p2, k3)
+    or None; ba: n_iters, n_cg, lambda0, cg_tol, ftol, huber_px, retriangulate. Returns dict(views_ba SFM_VIEW_DTYPE per frame,
+    cloud_ba [n, 3], track_status int32 [n], ba_summary SFM_BA_SUMMARY_DTYPE [1]), n the cloud's entries."""
+    from .types import SFM_BA_SUMMARY_DTYPE, make_camera, sfm_ba_params
+    frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
+    recs = _as(pairs, PAIR_DTYPE, "pairs")
+    kp, m = _as(keypoints, KEYPOINT_DTYPE, "keypoints"), _as(matches, DMATCH_DTYPE, "matches")
+    mk = np.ascontiguousarray(mask, dtype=np.uint8)
+    views, reg = _as(registration["views"], SFM_VIEW_DTYPE, "views"), _as(registration["registration"], SFM_PAIR_REG_DTYPE, "registration")
+    track = np.ascontiguousarray(registration["track"], dtype=np.int32)
+    cloud = np.ascontiguousarray(registration["cloud"], dtype=np.float64).reshape(-1, 3)
+    ids = np.ascontiguousarray(registration["cloud_id"], dtype=np.int32)
+    n_frames, n, cap = len(frame_off) - 1, len(recs), len(ids)
+    total = int((recs["match_off"] + np.maximum(recs["m"], 0)).max()) if n else 0
+    if min(len(m), len(mk), len(track)) < total or len(reg) != n or len(views) != n_frames or len(kp) < frame_off[-1] or len(cloud) != cap:
+        raise ValueError("keypoints cover every frame; matches, mask and track every pair's match range; one record per pair and per frame")
+    cam, prm = make_camera(camera, dist), sfm_ba_params(**ba)
+    out = dict(views_ba=np.zeros(n_frames, SFM_VIEW_DTYPE), cloud_ba=np.zeros((cap, 3)), track_status=np.zeros(cap, np.int32),
+               ba_summary=np.zeros(1, SFM_BA_SUMMARY_DTYPE))
+    lib = load_library()
+    _check(lib.gms_sfm_ba(cam.ctypes.data, prm.ctypes.data, kp.ctypes.data, frame_off.ctypes.data, n_frames, recs.ctypes.data, n, m.ctypes.data,
+                          mk.ctypes.data, views.ctypes.data, reg.ctypes.data, track.ctypes.data, cap, cloud.ctypes.data, ids.ctypes.data,
+                          int(registration["summary"]["n_tracks"][0]), out["views_ba"].ctypes.data, out["cloud_ba"].ctypes.data,
+                          out["track_status"].ctypes.data, out["ba_summary"].ctypes.data), lib, "gms_sfm_ba")
+    return out
+
+
+def structureFromMotionMulti(images, camera, dist=None, method="gms", pairs=None, root=0, min_links=8, ctx=None, bundle=False, **params):
     """structureFromMotion for a sequence: n photographs of one size (a list, or [n, H, W] / [n, H, W, 3]) -> every pair's two-view result
     and the registration that joins them into the frame of image `root` (pipeline.run_images(..., register=True)). pairs: (frame_a,
     frame_b) rows, default the chain (i, i + 1); they are walked in order, a pair registers frame_b when frame_a is registered.
     method, camera, dist and params as structureFromMotion (method="gms" runs matchGMS(true, true)). Returns run_images' dict:
     two_view, points3d, ... per pair, and views, registration, points_world, track, cloud, cloud_obs, cloud_est, cloud_spread, summary.
-    A pair without a pose does not raise here: its registration status says so, and the frames behind it stay unregistered."""
+    A pair without a pose does not raise here: its registration status says so, and the frames behind it stay unregistered.
+    bundle=True: bundle adjustment behind the registration (gms_sfm_ba_device; its keywords n_iters, n_cg, lambda0, cg_tol, ftol,
+    huber_px, retriangulate among params) adds views_ba, cloud_ba, track_status and ba_summary; bundle=False returns the dict without."""
     from . import pipeline
     if method not in pipeline.METHODS:
         raise ValueError(f"unknown method {method!r}")
@@ -710,7 +757,7 @@ def structureFromMotionMulti(images, camera, dist=None, method="gms", pairs=None
     if method == "logos" and opts.get("dictionary") is None:
         opts.setdefault("train_dictionary", True)
     return pipeline.run_images(ctx or default_context(), stack, camera, dist, method=method, pairs=pairs, register=True, root=root,
-                               min_links=min_links, **opts)
+                               min_links=min_links, bundle=bundle, **opts)
 
 
 def default_context():

@@ -1057,6 +1057,124 @@ class SfmRegister:
         return sfm_trim(out) if trim else out
 
 
+class SfmBundle:
+    """Device buffers of one gms_sfm_ba_device call (bundle adjustment behind the registration) over a fixed pair list
+    and cloud capacity: the workspace and the outputs, sized once, so that run() can be repeated or captured into a graph. The inputs
+    are either device tensors handed to run() -- a SfmRegister's own (`after`) and the keypoints, survivors and mask the two-view
+    stage read and left -- or the object's own, which load() fills from host arrays. camera = (fx, fy, cx, cy), dist = (k1, k2, p1,
+    p2, k3) or None; ba: n_iters, n_cg, lambda0, cg_tol, ftol, huber_px, retriangulate."""
+
+    def __init__(self, ctx, frame_off, pairs, cloud_cap, camera, dist=None, device=None, d_frame_off=None, d_pairs=None, **ba):
+        from .types import SFM_BA_SUMMARY_DTYPE, SFM_VIEW_DTYPE, make_camera, sfm_ba_params
+        self.ctx = ctx
+        self.frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
+        self.recs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
+        self.n_frames, self.n_pairs, self.total_kp = len(self.frame_off) - 1, len(self.recs), int(self.frame_off[-1])
+        n = self.n_pairs
+        self.total_m = int((self.recs["match_off"] + np.maximum(self.recs["m"], 0)).max()) if n else 0
+        self.cloud_cap = int(cloud_cap)
+        self.camera, self.params = make_camera(camera, dist), sfm_ba_params(**ba)
+        self.ws_bytes = ctx.sfm_ba_workspace_bytes(self.n_frames, n, self.total_kp, self.cloud_cap)
+        if self.ws_bytes == 0:
+            raise ValueError("SfmBundle: sizes rejected (include/gms.h)")
+        dev = _device(ctx, device)
+        self.device = dev
+        self.d_frame_off = d_frame_off if d_frame_off is not None else torch.from_numpy(self.frame_off).to(dev)
+        self.d_pairs = d_pairs if d_pairs is not None else (_to_dev(self.recs, dev) if n else torch.zeros(24, dtype=torch.uint8, device=dev))
+        self.d_ws = torch.zeros(self.ws_bytes, dtype=torch.uint8, device=dev)
+        cap = max(self.cloud_cap, 1)
+        self.d_views_out = torch.zeros(self.n_frames * SFM_VIEW_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.d_cloud_out = torch.zeros(cap * 3, dtype=torch.float64, device=dev)
+        self.d_status = torch.zeros(cap, dtype=torch.int32, device=dev)
+        self.d_summary = torch.zeros(SFM_BA_SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self._own = None
+        torch.cuda.synchronize(dev)
+
+    def _own_inputs(self):
+        from .types import SFM_PAIR_REG_DTYPE, SFM_SUMMARY_DTYPE, SFM_VIEW_DTYPE
+        if self._own is None:
+            m, n, cap, dev = max(self.total_m, 1), max(self.n_pairs, 1), max(self.cloud_cap, 1), self.device
+            u8 = dict(dtype=torch.uint8, device=dev)
+            self._own = dict(kp=torch.zeros(max(self.total_kp, 1) * 28, **u8), matches=torch.zeros(m * 16, **u8), mask=torch.zeros(m, **u8),
+                             views=torch.zeros(self.n_frames * SFM_VIEW_DTYPE.itemsize, **u8), reg=torch.zeros(n * SFM_PAIR_REG_DTYPE.itemsize, **u8),
+                             track=torch.zeros(m, dtype=torch.int32, device=dev), cloud=torch.zeros(cap * 3, dtype=torch.float64, device=dev),
+                             cloud_id=torch.zeros(cap, dtype=torch.int32, device=dev), summary=torch.zeros(SFM_SUMMARY_DTYPE.itemsize, **u8))
+        return self._own
+
+    def load(self, keypoints, matches, mask, registration):
+        """Host arrays into the object's own input tensors (the same tensors every time: a captured run() reads what the latest load()
+        left). registration: SfmRegister.results() / registerViews' dict, trimmed or not."""
+        from .types import SFM_PAIR_REG_DTYPE, SFM_SUMMARY_DTYPE, SFM_VIEW_DTYPE
+        own = self._own_inputs()
+        kp = np.ascontiguousarray(keypoints, dtype=KEYPOINT_DTYPE)
+        m, mk = np.ascontiguousarray(matches, dtype=DMATCH_DTYPE), np.ascontiguousarray(mask, dtype=np.uint8)
+        views = np.ascontiguousarray(registration["views"], dtype=SFM_VIEW_DTYPE)
+        reg = np.ascontiguousarray(registration["registration"], dtype=SFM_PAIR_REG_DTYPE)
+        track = np.ascontiguousarray(registration["track"], dtype=np.int32)
+        cloud = np.ascontiguousarray(registration["cloud"], dtype=np.float64).reshape(-1, 3)
+        ids = np.ascontiguousarray(registration["cloud_id"], dtype=np.int32)
+        summary = np.ascontiguousarray(registration["summary"], dtype=SFM_SUMMARY_DTYPE)
+        if (len(kp) < self.total_kp or min(len(m), len(mk), len(track)) < self.total_m or len(views) != self.n_frames or len(reg) != self.n_pairs
+                or len(cloud) != len(ids) or len(ids) > self.cloud_cap or len(ids) < min(int(summary["n_tracks"][0]), self.cloud_cap)):
+            raise ValueError("keypoints cover every frame; matches, mask and track every pair's match range; one record per pair and per "
+                             "frame; the cloud holds its first min(n_tracks, cloud_cap) entries")
+
+        def put(t, a, as_bytes=False):
+            a = np.ascontiguousarray(a).reshape(-1)
+            flat = torch.from_numpy(a.view(np.uint8) if as_bytes else a)
+            if len(flat):
+                t[:len(flat)].copy_(flat)
+        put(own["kp"], kp[:self.total_kp], 1)
+        put(own["matches"], m[:self.total_m], 1)
+        put(own["mask"], mk[:self.total_m])
+        put(own["views"], views, 1)
+        put(own["reg"], reg, 1)
+        put(own["track"], track[:self.total_m])
+        put(own["cloud"], cloud)
+        put(own["cloud_id"], ids)
+        put(own["summary"], summary, 1)
+
+    def run(self, after=None, d_kp=None, d_matches=None, d_mask=None):
+        """gms_sfm_ba_device, stream-ordered on the context's stream; no allocation, no synchronisation, no readback. after: the
+        SfmRegister whose outputs to refine, with the keypoints, survivors and mask on the device; none of them: the object's own."""
+        given = (after, d_kp, d_matches, d_mask)
+        if all(t is None for t in given):
+            o = self._own_inputs()
+            ptrs = [o[k].data_ptr() for k in ("kp", "matches", "mask", "views", "reg", "track")] + [o["cloud"].data_ptr(), o["cloud_id"].data_ptr(),
+                                                                                               o["summary"].data_ptr()]
+        elif any(t is None for t in given):
+            raise ValueError("run: a SfmRegister and the three input tensors, or none (the object's own)")
+        else:
+            if after.cloud_cap != self.cloud_cap or after.n_pairs != self.n_pairs or after.total_kp != self.total_kp:
+                raise ValueError("run: the SfmRegister has other sizes")
+            ptrs = [d_kp.data_ptr(), d_matches.data_ptr(), d_mask.data_ptr(), after.d_views.data_ptr(), after.d_reg.data_ptr(),
+                    after.d_track.data_ptr(), after.d_cloud.data_ptr(), after.d_cloud_id.data_ptr(), after.d_summary.data_ptr()]
+        kp, matches, mask, views, reg, track, cloud, cloud_id, summary = ptrs
+        self.ctx.sfm_ba_device(self.camera, self.params, kp, self.d_frame_off.data_ptr(), self.n_frames, self.total_kp, self.d_pairs.data_ptr(),
+                               self.n_pairs, self.total_m, matches, mask, views, reg, track, self.cloud_cap, cloud, cloud_id, summary,
+                               self.d_ws.data_ptr(), self.ws_bytes, self.d_views_out.data_ptr(), self.d_cloud_out.data_ptr(),
+                               self.d_status.data_ptr(), self.d_summary.data_ptr())
+
+    def results(self, n_tracks=None):
+        """Waits for the context's stream -> dict(views_ba, cloud_ba, track_status, ba_summary) on the host; the cloud arrays cut to
+        n_tracks entries when given."""
+        from .types import SFM_BA_SUMMARY_DTYPE, SFM_VIEW_DTYPE
+        self.ctx.synchronize()
+        n = self.cloud_cap if n_tracks is None else min(int(n_tracks), self.cloud_cap)
+        return dict(views_ba=self.d_views_out.cpu().numpy().view(SFM_VIEW_DTYPE).copy(), cloud_ba=self.d_cloud_out.cpu().numpy().reshape(-1, 3)[:n].copy(),
+                    track_status=self.d_status.cpu().numpy()[:n].copy(), ba_summary=self.d_summary.cpu().numpy().view(SFM_BA_SUMMARY_DTYPE).copy())
+
+
+def bundle_adjust(ctx, keypoints, frame_off, pairs, matches, mask, registration, camera, dist=None, device=None, **ba):
+    """The convenience call: host arrays (the keypoints, the two-view stage's pairs, survivors and mask, and a registration's dict) ->
+    SfmBundle.results() after one gms_sfm_ba_device run, cut to the cloud's entries."""
+    job = SfmBundle(ctx, frame_off, pairs, len(registration["cloud_id"]), camera, dist, device, **ba)
+    job.load(keypoints, matches, mask, registration)
+    torch.cuda.synchronize(job.device)
+    job.run()
+    return job.results()
+
+
 def register_pairs(ctx, frame_off, pairs, matches, mask, points3d, two_view, root=0, min_links=8, cloud_cap=None, device=None):
     """The convenience call: host arrays of many pairs' two-view results (run_dataset's pairs, out, mask, points3d, two_view and the
     frames' offsets) -> SfmRegister.results() after one gms_sfm_register_device run."""

@@ -26,6 +26,7 @@
 #include "logos_dict_core.h"
 #include "portrait_core.h"
 #include "stereo_bm_core.h"
+#include "sfm_ba_core.h"
 #include "sfm_register_core.h"
 #include "stereo_sgm_core.h"
 #include "twoview_core.h"
@@ -1832,6 +1833,104 @@ int gms_sfm_register(const int64_t* frame_off, int n_frames, const gms_pair* pai
         blk.out(cloud_spread, o_spread, 8 * Cc);
     }
     blk.out(summary, o_sum, sizeof(gms_sfm_summary));
+    return blk.finish();
+}
+
+// ---- bundle adjustment behind the registration (sfm_ba_kernels.hip; the arithmetic is sfm_ba_core.h) --------------------------------
+static bool sfm_ba_sizes_ok(int n_frames, int n_pairs, int64_t total_kp, int64_t cloud_cap)
+{
+    return n_frames >= 1 && n_frames <= (1 << 24) && n_pairs >= 0 && total_kp >= 0 && total_kp < INT32_MAX && cloud_cap >= 0 && cloud_cap < INT32_MAX;
+}
+
+size_t gms_sfm_ba_workspace_bytes(int n_frames, int n_pairs, int64_t total_kp, int64_t cloud_cap)
+{
+    if (!sfm_ba_sizes_ok(n_frames, n_pairs, total_kp, cloud_cap)) return 0;
+    return gms::sfm_ba_ws_bytes(n_frames, total_kp, cloud_cap);
+}
+
+int gms_sfm_ba_device(gms_ctx* c, const gms_camera* camera, const gms_sfm_ba_params* params, const gms_keypoint* d_kp,
+                      const int64_t* d_frame_off, int n_frames, int64_t total_kp, const gms_pair* d_pairs, int n_pairs,
+                      int64_t total_matches, const gms_dmatch* d_filtered, const uint8_t* d_mask, const gms_sfm_view* d_views,
+                      const gms_sfm_pair_reg* d_reg, const int32_t* d_track, int64_t cloud_cap, const double* d_cloud,
+                      const int32_t* d_cloud_id, const gms_sfm_summary* d_reg_summary, void* d_ws, size_t ws_bytes,
+                      gms_sfm_view* d_views_out, double* d_cloud_out, int32_t* d_track_status, gms_sfm_ba_summary* d_summary)
+{
+    if (!c || !camera || !params || !sfm_ba_sizes_ok(n_frames, n_pairs, total_kp, cloud_cap) || !sba::params_ok(*params)) return GMS_ERR_BAD_ARG;
+    if (total_matches < 0 || total_matches >= ((int64_t)1 << 40)) return GMS_ERR_BAD_ARG;
+    if (!d_frame_off || !d_views || !d_reg_summary || !d_ws || !d_views_out || !d_summary) return GMS_ERR_BAD_ARG;
+    if (total_kp > 0 && !d_kp) return GMS_ERR_BAD_ARG;
+    if (n_pairs > 0 && (!d_pairs || !d_reg)) return GMS_ERR_BAD_ARG;
+    if (total_matches > 0 && (!d_filtered || !d_mask || !d_track)) return GMS_ERR_BAD_ARG;
+    if (cloud_cap > 0 && (!d_cloud || !d_cloud_id || !d_cloud_out || !d_track_status)) return GMS_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_ws) & 255u) || ws_bytes < gms::sfm_ba_ws_bytes(n_frames, total_kp, cloud_cap)) return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] {
+        return gms::launch_sfm_ba(*camera, *params, d_kp, d_frame_off, n_frames, total_kp, d_pairs, n_pairs, total_matches, d_filtered, d_mask,
+                                  d_views, d_reg, d_track, cloud_cap, d_cloud, d_cloud_id, d_reg_summary, d_ws, d_views_out, d_cloud_out,
+                                  d_track_status, d_summary, c->stream);
+    });
+}
+
+int gms_sfm_ba(const gms_camera* camera, const gms_sfm_ba_params* params, const gms_keypoint* kp, const int64_t* frame_off, int n_frames,
+               const gms_pair* pairs, int n_pairs, const gms_dmatch* filtered, const uint8_t* mask, const gms_sfm_view* views,
+               const gms_sfm_pair_reg* reg, const int32_t* track, int64_t cloud_cap, const double* cloud, const int32_t* cloud_id,
+               int64_t n_tracks, gms_sfm_view* views_out, double* cloud_out, int32_t* track_status, gms_sfm_ba_summary* summary)
+{
+    if (!camera || !params || n_frames < 1 || n_pairs < 0 || !frame_off || !views || !views_out || !summary || cloud_cap < 0 || n_tracks < 0 ||
+        !sba::params_ok(*params))
+        return GMS_ERR_BAD_ARG;
+    if (n_pairs > 0 && (!pairs || !reg)) return GMS_ERR_BAD_ARG;
+    if (cloud_cap > 0 && (!cloud || !cloud_id || !cloud_out || !track_status)) return GMS_ERR_BAD_ARG;
+    for (int f = 0; f < n_frames; f++)
+        if (frame_off[f] < 0 || frame_off[f + 1] < frame_off[f]) return GMS_ERR_BAD_ARG;
+    int64_t total_m = 0;
+    for (int p = 0; p < n_pairs; p++) {
+        if (pairs[p].m < 0 || pairs[p].match_off < 0) return GMS_ERR_BAD_ARG;
+        total_m = std::max(total_m, pairs[p].match_off + (int64_t)pairs[p].m);
+    }
+    const int64_t total_kp = frame_off[n_frames];
+    if (!sfm_ba_sizes_ok(n_frames, n_pairs, total_kp, cloud_cap) || total_m >= ((int64_t)1 << 40)) return GMS_ERR_BAD_ARG;
+    if (total_kp > 0 && !kp) return GMS_ERR_BAD_ARG;
+    if (total_m > 0 && (!filtered || !mask || !track)) return GMS_ERR_BAD_ARG;
+    const size_t M = (size_t)total_m, P = (size_t)n_pairs, Cc = (size_t)cloud_cap, K = (size_t)total_kp, F = (size_t)n_frames;
+    gms_sfm_summary rs = {};
+    rs.n_tracks = n_tracks;
+    gms::BlockLayout lay;
+    const size_t o_kp = lay.add(sizeof(gms_keypoint) * K), o_off = lay.add(8 * (F + 1)), o_pairs = lay.add(sizeof(gms_pair) * P);
+    const size_t o_m = lay.add(sizeof(gms_dmatch) * M), o_mask = lay.add(M), o_views = lay.add(sizeof(gms_sfm_view) * F);
+    const size_t o_reg = lay.add(sizeof(gms_sfm_pair_reg) * P), o_track = lay.add(4 * M), o_cloud = lay.add(24 * Cc), o_id = lay.add(4 * Cc);
+    const size_t o_rs = lay.add(sizeof(gms_sfm_summary)), o_ws = lay.add(gms::sfm_ba_ws_bytes(n_frames, total_kp, cloud_cap));
+    const size_t o_vout = lay.add(sizeof(gms_sfm_view) * F), o_cout = lay.add(24 * Cc), o_st = lay.add(4 * Cc), o_sum = lay.add(sizeof(gms_sfm_ba_summary));
+    DevBlock blk(lay, nullptr);
+    blk.in(o_off, frame_off, 8 * (F + 1));
+    blk.in(o_views, views, sizeof(gms_sfm_view) * F);
+    blk.in(o_rs, &rs, sizeof(rs));
+    if (K) blk.in(o_kp, kp, sizeof(gms_keypoint) * K);
+    if (P) {
+        blk.in(o_pairs, pairs, sizeof(gms_pair) * P);
+        blk.in(o_reg, reg, sizeof(gms_sfm_pair_reg) * P);
+    }
+    if (M) {
+        blk.in(o_m, filtered, sizeof(gms_dmatch) * M);
+        blk.in(o_mask, mask, M);
+        blk.in(o_track, track, 4 * M);
+    }
+    if (Cc) {
+        blk.in(o_cloud, cloud, 24 * Cc);
+        blk.in(o_id, cloud_id, 4 * Cc);
+    }
+    blk.run([&](hipStream_t st) {
+        return gms::launch_sfm_ba(*camera, *params, blk.at<gms_keypoint>(o_kp), blk.at<int64_t>(o_off), n_frames, total_kp,
+                                  blk.at<gms_pair>(o_pairs), n_pairs, total_m, blk.at<gms_dmatch>(o_m), blk.at<uint8_t>(o_mask),
+                                  blk.at<gms_sfm_view>(o_views), blk.at<gms_sfm_pair_reg>(o_reg), blk.at<int32_t>(o_track), cloud_cap,
+                                  blk.at<double>(o_cloud), blk.at<int32_t>(o_id), blk.at<gms_sfm_summary>(o_rs), blk.at(o_ws),
+                                  blk.at<gms_sfm_view>(o_vout), blk.at<double>(o_cout), blk.at<int32_t>(o_st), blk.at<gms_sfm_ba_summary>(o_sum), st);
+    });
+    blk.out(views_out, o_vout, sizeof(gms_sfm_view) * F);
+    if (Cc) {
+        blk.out(cloud_out, o_cout, 24 * Cc);
+        blk.out(track_status, o_st, 4 * Cc);
+    }
+    blk.out(summary, o_sum, sizeof(gms_sfm_ba_summary));
     return blk.finish();
 }
 

@@ -205,6 +205,14 @@ hipError_t launch_sfm_register(const int64_t* d_frame_off, int n_frames, int64_t
                                void* d_ws, gms_sfm_view* d_views, gms_sfm_pair_reg* d_reg, double* d_world, int32_t* d_track,
                                int64_t cloud_cap, double* d_cloud, int32_t* d_cloud_id, int32_t* d_cloud_obs, int32_t* d_cloud_est,
                                double* d_cloud_spread, gms_sfm_summary* d_summary, hipStream_t stream);
+// bundle adjustment behind the registration (sfm_ba_kernels.hip; shared arithmetic in sfm_ba_core.h)
+size_t     sfm_ba_ws_bytes(int n_frames, int64_t total_kp, int64_t cloud_cap);
+hipError_t launch_sfm_ba(const gms_camera& camera, const gms_sfm_ba_params& prm, const gms_keypoint* d_kp, const int64_t* d_frame_off,
+                         int n_frames, int64_t total_kp, const gms_pair* d_pairs, int n_pairs, int64_t total_m, const gms_dmatch* d_filtered,
+                         const uint8_t* d_mask, const gms_sfm_view* d_views, const gms_sfm_pair_reg* d_reg, const int32_t* d_track,
+                         int64_t cloud_cap, const double* d_cloud, const int32_t* d_cloud_id, const gms_sfm_summary* d_reg_summary, void* d_ws,
+                         gms_sfm_view* d_views_out, double* d_cloud_out, int32_t* d_track_status, gms_sfm_ba_summary* d_summary,
+                         hipStream_t stream);
 // semi-global matching on StereoBM's costs (stereo_sgm_kernels.hip; shared arithmetic in stereo_sgm_core.h); 0 bytes: beyond size_t
 size_t     stereo_sgm_ws_bytes(const gms_stereo_sgm_params& p, int n, int W, int H);
 hipError_t launch_stereo_sgm(const gms_stereo_sgm_params& p, const uint8_t* d_left, const uint8_t* d_right, int n, int W, int H, int pitch,

@@ -337,4 +337,51 @@ inline SfmRegisterLayout sfm_register_layout(int n_pairs, int64_t total_kp, int6
             c.take(4 * P, 256), c.end};
 }
 
+// ---- bundle adjustment behind the registration (sfm_ba_kernels.hip) -----------------------------------------------------------------
+// K global keypoints, C cloud entries, F frames. Everything an observation owns sits at its keypoint's index: a keypoint is an
+// observation of at most one track, so no compaction is needed and the observations of a frame are a range. Every call writes every
+// word it later reads.
+constexpr int kSbaScanTile = 4096;  // cloud entries per workgroup of the prefix sum over the tracks' counts
+struct SfmBaLayout {
+    size_t kp_track;  // int32 [K]: the cloud entry the keypoint observes, -1: none
+    size_t kp_frame;  // int32 [K]: its frame
+    size_t list;      // int32 [K]: the tracks' keypoints, ascending within a track, track c at t_off[c]
+    size_t uv;        // double [K][2]: the undistorted measurement
+    size_t jc;        // double [K][12]: sqrt(w) Jc, zeros when inactive or the frame is not free
+    size_t jp;        // double [K][6]: sqrt(w) Jp
+    size_t res;       // double [K][2]: sqrt(w) r
+    size_t t_cnt;     // int32 [C]: observations of the track
+    size_t t_off;     // int32 [C]: their exclusive prefix
+    size_t t_fill;    // int32 [C]: the fill cursor
+    size_t t_used;    // int32 [C]: 1 when the track takes part
+    size_t tiles;     // int32 [ceil(C / kSbaScanTile) + 1]
+    size_t xc;        // double [C][3]: the candidate points
+    size_t vinv;      // double [C][9]: (V + lambda diag V)^-1
+    size_t gp;        // double [C][3]: -sum Jp^T r
+    size_t qt;        // double [C][3]: the per-track pass of S p
+    size_t cand;      // gms_sfm_view [F]: the candidate views
+    size_t U;         // double [F][36]: damped
+    size_t L;         // double [F][36]: the preconditioner's Cholesky factor
+    size_t lok;       // int32 [F]: 1 when it has one
+    size_t free_;     // int32 [F]: 1 when the frame is a parameter
+    size_t vec;       // double [6][F][6]: b, x, r, z, p, q
+    size_t part;      // double [F]: per-frame shares of a dot product
+    size_t costp;     // double [F][2]: per-frame Huber cost and sum of squares
+    size_t actp;      // int64 [F]: per-frame active observations
+    size_t scal;      // double [16]
+    size_t flags;     // int32 [16]
+    size_t total;
+};
+inline SfmBaLayout sfm_ba_layout(int n_frames, int64_t total_kp, int64_t cloud_cap)
+{
+    const size_t K = (size_t)total_kp, Cc = (size_t)cloud_cap, F = (size_t)n_frames;
+    WsCursor c;
+    return {c.take(4 * K, 256), c.take(4 * K, 256), c.take(4 * K, 256), c.take(16 * K, 256), c.take(96 * K, 256), c.take(48 * K, 256),
+            c.take(16 * K, 256), c.take(4 * Cc, 256), c.take(4 * Cc, 256), c.take(4 * Cc, 256), c.take(4 * Cc, 256),
+            c.take(4 * ((Cc + kSbaScanTile - 1) / kSbaScanTile + 1), 256), c.take(24 * Cc, 256), c.take(72 * Cc, 256), c.take(24 * Cc, 256),
+            c.take(24 * Cc, 256), c.take(sizeof(gms_sfm_view) * F, 256), c.take(288 * F, 256), c.take(288 * F, 256), c.take(4 * F, 256),
+            c.take(4 * F, 256), c.take(288 * F, 256), c.take(8 * F, 256), c.take(16 * F, 256), c.take(8 * F, 256), c.take(128, 256),
+            c.take(64, 256), c.end};
+}
+
 }  // namespace gms

@@ -435,7 +435,7 @@ inline void stereo_match_sgm(const std::vector<uint8_t>& left, const std::vector
 // Many two-view results into one frame (include/gms.h) -- the library's own step behind the batched two-view stage.
 // frame_off: n_frames + 1 keypoint offsets; pairs, matches, mask, points3d (3 doubles per match slot) and two_view as the stage leaves
 // them, laid out by the pairs' match_off. Runs synchronously on the current HIP device (gms_sfm_register). The cloud arrays are cut to
-// the tracks they hold. Loop closure, bundle adjustment and re-triangulation over more than two views are not done.
+// the tracks they hold. Loop closure is not done; re-triangulation over all views and bundle adjustment are bundleAdjust's, below.
 struct Registration {
     std::vector<gms_sfm_view> views;            // one per frame
     std::vector<gms_sfm_pair_reg> pairs;        // one per pair
@@ -478,6 +478,52 @@ inline Registration registerViews(const std::vector<int64_t>& frame_off, const s
     r.cloud_id.resize(n);
     r.cloud_obs.resize(n);
     r.cloud_est.resize(n);
+    return r;
+}
+
+// Bundle adjustment behind registerViews (include/gms.h): refines the views and the cloud over all the keypoints a
+// track chains together. keypoints: all frames back to back (frame_off); pairs, matches and mask as registerViews took them; reg: its
+// result. Runs synchronously on the current HIP device (gms_sfm_ba). The outputs have one entry per view and per cloud entry of reg.
+struct BundleAdjustment {
+    std::vector<gms_sfm_view> views;      // one per frame
+    std::vector<double> cloud;            // 3 per cloud entry
+    std::vector<int32_t> track_status;    // 0 refined, 1 two keypoints of a frame, 2 fewer than two observations, 3 kept its cloud point
+    gms_sfm_ba_summary summary;
+};
+
+inline gms_sfm_ba_params bundle_default_params()
+{
+    gms_sfm_ba_params p = {};
+    p.lambda0 = 1e-3;
+    p.cg_tol = 1e-8;
+    p.ftol = 1e-10;
+    p.huber_px = 2.0;
+    p.n_iters = 10;
+    p.n_cg = 50;
+    p.retriangulate = 1;
+    return p;
+}
+
+inline BundleAdjustment bundleAdjust(const std::vector<gms_keypoint>& keypoints, const std::vector<int64_t>& frame_off,
+                                     const std::vector<gms_pair>& pairs, const std::vector<gms_dmatch>& matches, const std::vector<uint8_t>& mask,
+                                     const Registration& reg, const gms_camera& camera, const gms_sfm_ba_params& params = bundle_default_params())
+{
+    size_t total = 0;
+    for (const gms_pair& p : pairs)
+        if (p.m > 0 && p.match_off >= 0) total = std::max(total, (size_t)p.match_off + (size_t)p.m);
+    const size_t cap = reg.cloud_id.size();
+    if (frame_off.size() < 2 || frame_off.back() < 0 || keypoints.size() < (size_t)frame_off.back() || reg.views.size() != frame_off.size() - 1 ||
+        reg.pairs.size() != pairs.size() || matches.size() < total || mask.size() < total || reg.track.size() < total || reg.cloud.size() != 3 * cap)
+        throw std::invalid_argument("mi355::bundleAdjust: keypoints that cover every frame, arrays that cover every pair's match range, and the registration of the same frames and pairs");
+    const int n_frames = (int)frame_off.size() - 1;
+    BundleAdjustment r;
+    r.views.resize((size_t)n_frames);
+    r.cloud.assign(3 * cap, 0.0);
+    r.track_status.assign(cap, 0);
+    const int rc = gms_sfm_ba(&camera, &params, keypoints.data(), frame_off.data(), n_frames, pairs.data(), (int)pairs.size(), matches.data(),
+                              mask.data(), reg.views.data(), reg.pairs.data(), reg.track.data(), (int64_t)cap, reg.cloud.data(), reg.cloud_id.data(),
+                              reg.summary.n_tracks, r.views.data(), r.cloud.data(), r.track_status.data(), &r.summary);
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::bundleAdjust: ") + gms_error_string(rc));
     return r;
 }
 

@@ -24,11 +24,11 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from .batch import (BfSelect, DescriptorTable, DetectPyramid, FrameTable, LogosDictionary, LogosFilter, LogosTable, SfmRegister, Warp, _device, _to_dev,
+from .batch import (BfSelect, DescriptorTable, DetectPyramid, FrameTable, LogosDictionary, LogosFilter, LogosTable, SfmBundle, SfmRegister, Warp, _device, _to_dev,
                     bf_select_table, bgr_to_gray, frame_counts, frame_pairs_of, logos_dictionary, pair_table, tables_from_detector)
 from .api import getRotationMatrix2D, logos_dict_args
 from .types import (DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128, GMS_ERR_CAPACITY, PAIR_DTYPE, RESULT_DTYPE, TWO_VIEW_DTYPE,
-                    desc_layout, make_camera)
+                    desc_layout, make_camera, sfm_ba_params)
 
 METHODS = ("gms", "bf", "logos")
 
@@ -53,9 +53,17 @@ def _two_view(ctx, frames, d_pairs, n_pairs, max_m, total_m, d_out, d_res, camer
     joined = {}
     if reg is not None:
         job = SfmRegister(ctx, frames.frame_off_host, pairs, reg[0], reg[1], device=dev, d_frame_off=frames.d_frame_off, d_pairs=d_pairs)
+        refine = None
+        if reg[2] is not None:   # bundle adjustment behind it, in stream order, on the registration's own tensors
+            refine = SfmBundle(ctx, frames.frame_off_host, pairs, job.cloud_cap, camera, dist, device=dev, d_frame_off=frames.d_frame_off,
+                               d_pairs=d_pairs, **reg[2])
         job.run(d_out, d_mask, d_p3, d_tv)
+        if refine is not None:
+            refine.run(job, frames.d_kp, d_out, d_mask)
         joined = job.results()
         joined["register_plan"] = joined.pop("plan")
+        if refine is not None:
+            joined.update(refine.results(len(joined["cloud_id"])))
     ctx.synchronize()
     return dict(joined, two_view=d_tv.cpu().numpy().view(TWO_VIEW_DTYPE)[:n_pairs], coords1=d_c1.cpu().numpy().reshape(-1, 2)[:total_m],
                 coords2=d_c2.cpu().numpy().reshape(-1, 2)[:total_m], mask=d_mask.cpu().numpy()[:total_m],
@@ -64,7 +72,8 @@ def _two_view(ctx, frames, d_pairs, n_pairs, max_m, total_m, d_out, d_res, camer
 
 def run_dataset(ctx, ds, withRotation=False, withScale=False, thresholdFactor=6.0, match=None, camera=None, dist=None, prob=0.7,
                 ransac_threshold=1.0, max_iters=1000, device="cuda:0", method="gms", dictionary=None, logos_capacity=None,
-                cross_check=True, distance_coef=4.0, max_size=500, train_dictionary=None, register=False, root=0, min_links=8):
+                cross_check=True, distance_coef=4.0, max_size=500, train_dictionary=None, register=False, root=0, min_links=8, bundle=False,
+                **ba):
     """(prob, ransac_threshold: findEssentialMat's confidence and threshold as the flow this function restates passes them -- SfMUtil.cpp:39:
     RANSAC, 0.7, 1.0 -- not OpenCV's own default of 0.999, which gms_find_essential_batch_device's Python mirror keeps.)
     ds: io.Dataset. match=None: brute-force match when the file carries descriptors and no matches. camera = (fx, fy, cx, cy)
@@ -82,8 +91,11 @@ def run_dataset(ctx, ds, withRotation=False, withScale=False, thresholdFactor=6.
     (gms_sfm_register_device): the pairs are walked in order, a pair registers frame_b when frame_a is registered, and a
     pair with fewer than min_links scene points shared with the pair it hangs on fails. Adds views, registration, points_world, track,
     cloud, cloud_id, cloud_obs, cloud_est, cloud_spread, summary and register_plan. register=False returns the dict without them.
+    bundle=True (needs register=True; ba: n_iters, n_cg, lambda0, cg_tol, ftol, huber_px, retriangulate): gms_sfm_ba_device then refines
+    views and cloud over all the keypoints of a track, in stream order behind the registration. Adds views_ba, cloud_ba,
+    track_status and ba_summary; the registration's own arrays stay as they are. bundle=False returns the dict without them.
     The stages themselves work on resident tables (_run_gms, _run_bf, _run_logos): run_images feeds them from pixels."""
-    tail = (camera, dist, prob, ransac_threshold, max_iters, _register_args(register, root, min_links, camera))
+    tail = (camera, dist, prob, ransac_threshold, max_iters, _register_args(register, root, min_links, camera, bundle, ba))
     if method == "bf":
         if ds.descriptors is None:
             raise ValueError("method='bf' needs the dataset's descriptors")
@@ -158,15 +170,22 @@ def _run_gms(ctx, frames, descs, src_pairs, matches, withRotation, withScale, th
     return out
 
 
-def _register_args(register, root, min_links, camera):
-    """run_dataset's register / root / min_links -> None or (root, min_links), checked before anything is launched."""
+def _register_args(register, root, min_links, camera, bundle=False, ba=None):
+    """run_dataset's register / root / min_links / bundle and the bundle adjustment's keywords -> None or (root, min_links, None or
+    those keywords), checked before anything is launched."""
+    if bundle and not register:
+        raise ValueError("bundle=True needs register=True: it refines the registration")
+    if ba and not bundle:
+        raise TypeError(f"unknown arguments {sorted(ba)} (the bundle adjustment's, without bundle=True)")
     if not register:
         return None
     if camera is None:
         raise ValueError("register=True needs a camera: it joins the two-view results")
     if int(min_links) < 1 or int(root) < 0:
         raise ValueError("root: a frame index; min_links: at least 1")
-    return int(root), int(min_links)
+    if bundle:
+        sfm_ba_params(**ba)   # (refuses an unknown keyword)
+    return int(root), int(min_links), (dict(ba) if bundle else None)
 
 
 def image_stack(images):
@@ -210,7 +229,7 @@ def _train_dictionary_device(ctx, descs, opts):
 def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, threshold=20, max_keypoints=10000, n_levels=8,
                descriptor="grad", withRotation=False, withScale=False, thresholdFactor=6.0, prob=0.7, ransac_threshold=1.0, max_iters=1000,
                device=None, dictionary=None, logos_capacity=None, cross_check=True, distance_coef=4.0, max_size=500, train_dictionary=None,
-               keep_tables=False, detector="fast", contrast=128, refine=False, register=False, root=0, min_links=8):
+               keep_tables=False, detector="fast", contrast=128, refine=False, register=False, root=0, min_links=8, bundle=False, **ba):
     """run_dataset from pixels. images: [n, H, W] grey or [n, H, W, 3] BGR, 8-bit, a host array or a device tensor (or a list of equally
     sized images). BGR goes through gms_bgr_to_gray_device; the pyramid keypoint source (threshold, max_keypoints, n_levels; detector
     "fast", or "dog" with `contrast` in the place of `threshold`: gms_detect_dog_batch_device, with refine=True
@@ -219,14 +238,14 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
     n + 1 frame offsets (and the status records the stages already read) come back. pairs: (frame_a, frame_b) rows or PAIR_DTYPE
     records; default every a < b. The other arguments and the returned records are run_dataset's (the matcher always runs: there are
     no matches to bring); keep_tables=True adds `tables` = (FrameTable, DescriptorTable), the resident keypoints and rows.
-    register, root, min_links: run_dataset's."""
+    register, root, min_links, bundle and the bundle adjustment's keywords: run_dataset's."""
     if method not in METHODS:
         raise ValueError(f"unknown method {method!r}")
     if descriptor not in ("brief", "grad", "both"):
         raise ValueError('descriptor: "brief", "grad" or "both"')
     images, is_bgr = image_stack(images)
     n, h, w = images.shape[:3]
-    reg = _register_args(register, root, min_links, camera)
+    reg = _register_args(register, root, min_links, camera, bundle, ba)
     if reg is not None and not 0 <= reg[0] < n:
         raise ValueError("root: a frame index")
     if pairs is None:

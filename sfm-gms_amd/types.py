@@ -146,6 +146,26 @@ SFM_SUMMARY_DTYPE = np.dtype([("n_tracks", "<i8"), ("n_points", "<i8"), ("n_mult
 assert SFM_PLAN_DTYPE.itemsize == 16 and SFM_VIEW_DTYPE.itemsize == 104 and SFM_PAIR_REG_DTYPE.itemsize == 40
 assert SFM_SUMMARY_DTYPE.itemsize == 32
 
+# gms_sfm_ba_params / gms_sfm_ba_summary (include/gms.h): bundle adjustment behind the registration; the track statuses
+SFM_BA_PARAMS_DTYPE = np.dtype([("lambda0", "<f8"), ("cg_tol", "<f8"), ("ftol", "<f8"), ("huber_px", "<f8"), ("n_iters", "<i4"), ("n_cg", "<i4"),
+                                ("retriangulate", "<i4"), ("reserved", "<i4")])
+SFM_BA_SUMMARY_DTYPE = np.dtype([("cost0", "<f8"), ("cost", "<f8"), ("rms0_px", "<f8"), ("rms_px", "<f8"), ("lambda", "<f8"), ("n_obs", "<i8"),
+                                 ("n_active", "<i8"), ("n_tracks_used", "<i8"), ("n_tracks_multi", "<i8"), ("n_frames_free", "<i4"),
+                                 ("iters_run", "<i4"), ("iters_accepted", "<i4"), ("cg_iters", "<i4"), ("status", "<i4"), ("reserved", "<i4")])
+assert SFM_BA_PARAMS_DTYPE.itemsize == 48 and SFM_BA_SUMMARY_DTYPE.itemsize == 96
+SFM_BA_REFINED, SFM_BA_MULTI, SFM_BA_FEW, SFM_BA_KEPT = 0, 1, 2, 3
+SFM_BA_DEFAULTS = dict(n_iters=10, n_cg=50, lambda0=1e-3, cg_tol=1e-8, ftol=1e-10, huber_px=2.0, retriangulate=1)
+
+
+def sfm_ba_params(**kw):
+    """A one-record SFM_BA_PARAMS_DTYPE array: the definition's defaults, updated from the keywords."""
+    rec = np.zeros(1, SFM_BA_PARAMS_DTYPE)
+    for k, v in dict(SFM_BA_DEFAULTS, **kw).items():
+        if k not in SFM_BA_DEFAULTS:
+            raise TypeError(f"unknown bundle adjustment parameter {k!r}")
+        rec[k] = v
+    return rec
+
 
 def make_camera(camera, dist=None):
     """(fx, fy, cx, cy) and (k1, k2, p1, p2, k3) or None -> a CAMERA_DTYPE record (cameraMatrix / distCoeffs of SfMUtil.cpp:4)."""

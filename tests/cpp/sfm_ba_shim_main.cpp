@@ -1,0 +1,62 @@
+// tests/test_cpp_sfm_ba_shim.py: mi355::registerViews, then mi355::bundleAdjust (sfm-gms_amd/include/mi355_gms.hpp) on the arrays of an
+// input file, printing an FNV-1a checksum of each output in the order views, cloud, track_status, summary. Input (little-endian): int32
+// n_frames, n_pairs, root, min_links; int64 total match slots; gms_camera; frame_off int64 [n_frames + 1]; gms_keypoint [frame_off
+// [n_frames]]; gms_pair [n_pairs]; gms_dmatch [total]; mask uint8 [total]; points3d double [total][3]; gms_two_view [n_pairs]. No
+// arguments: prints usage and exits 2 (the CPU test links this without a device).
+#include <cstdio>
+#include <vector>
+
+#include "mi355_gms.hpp"
+
+static unsigned long long fnv(const void* q, size_t n)
+{
+    const unsigned char* p = static_cast<const unsigned char*>(q);
+    unsigned long long s = 1469598103934665603ull;
+    for (size_t i = 0; i < n; ++i) s = (s ^ p[i]) * 1099511628211ull;
+    return s;
+}
+
+template <class T>
+static bool read_all(FILE* f, std::vector<T>& v)
+{
+    return v.empty() || std::fread(v.data(), sizeof(T), v.size(), f) == v.size();
+}
+
+template <class T>
+static void print_sum(const std::vector<T>& v)
+{
+    std::printf("%llu\n", fnv(v.data(), v.size() * sizeof(T)));
+}
+
+int main(int argc, char** argv)
+{
+    if (argc < 2) {
+        std::fprintf(stderr, "usage: sfm_ba_shim_main RECORDS.bin\n");
+        return 2;
+    }
+    FILE* f = std::fopen(argv[1], "rb");
+    if (!f) return 2;
+    int32_t head[4];
+    int64_t total;
+    gms_camera cam;
+    if (std::fread(head, 4, 4, f) != 4 || std::fread(&total, 8, 1, f) != 1 || std::fread(&cam, sizeof cam, 1, f) != 1 || head[0] < 1 || head[1] < 0 ||
+        total < 0)
+        return 2;
+    std::vector<int64_t> frame_off((size_t)head[0] + 1);
+    if (!read_all(f, frame_off) || frame_off.back() < 0) return 2;
+    std::vector<gms_keypoint> kp((size_t)frame_off.back());
+    std::vector<gms_pair> pairs((size_t)head[1]);
+    std::vector<gms_dmatch> matches((size_t)total);
+    std::vector<uint8_t> mask((size_t)total);
+    std::vector<double> points(3 * (size_t)total);
+    std::vector<gms_two_view> tv((size_t)head[1]);
+    if (!read_all(f, kp) || !read_all(f, pairs) || !read_all(f, matches) || !read_all(f, mask) || !read_all(f, points) || !read_all(f, tv)) return 2;
+    std::fclose(f);
+    const mi355::Registration r = mi355::registerViews(frame_off, pairs, matches, mask, points, tv, head[2], head[3]);
+    const mi355::BundleAdjustment b = mi355::bundleAdjust(kp, frame_off, pairs, matches, mask, r, cam);
+    print_sum(b.views);
+    print_sum(b.cloud);
+    print_sum(b.track_status);
+    std::printf("%llu\n", fnv(&b.summary, sizeof b.summary));
+    return 0;
+}

@@ -3,14 +3,16 @@
 pipeline.run_images(register=True): per pair the two-view stage, then gms_sfm_register_device joins the pairs).
 Prints one JSON line: per pair n_links, r, S and status; per view the camera centre; tracks by length; the median spread.
 
-    python tools/gms_sfm_sequence.py [images.npz] [--method gms|bf|logos] [--pairs chain|star|all] [--root 0] [--min-links 8] [--max-keypoints 2000] [--ply out.ply] [--check]
+    python tools/gms_sfm_sequence.py [images.npz] [--method gms|bf|logos] [--pairs chain|star|all] [--root 0] [--min-links 8] [--max-keypoints 2000] [--ply out.ply] [--bundle] [--check]
 
 images.npz: arrays images ([n, H, W] grey or [n, H, W, 3] BGR, uint8) and camera = (fx, fy, cx, cy), optionally dist. Default: views
 1, 2, 3, 4 of the reference's SourceImages scene from the two committed fixtures (tests/golden/image_sfm_pair_1008x756.npz holds views 1
 and 4, image_sfm_more_1008x756.npz views 2 and 3), with the pair's stated camera. --pairs: chain (i, i + 1); star (root, i); all:
 every a < b in order (the pairs that close a loop are skipped by the plan). --ply: the cloud as an ASCII PLY file (x, y, z, and the
 track's keypoint count as `obs`). --check: feeds the GPU's own two-view records to the numpy statement (tests/sfm_register_ref.py)
-and compares: integers exactly, doubles to 1e-9; test infrastructure."""
+and compares: integers exactly, doubles to 1e-9; test infrastructure. --bundle: bundle adjustment behind the registration
+(gms_sfm_ba_device): reprojection RMS before and after, accepted iterations, tracks used and excluded, the camera
+centres after; with --check also against tests/sfm_ba_ref.py under the tolerance measured on these records."""
 import argparse
 import importlib
 import json
@@ -55,6 +57,7 @@ def main():
     ap.add_argument("--max-keypoints", type=int, default=2000)
     ap.add_argument("--ply")
     ap.add_argument("--check", action="store_true")
+    ap.add_argument("--bundle", action="store_true")
     a = ap.parse_args()
     if a.images:
         z = np.load(a.images)
@@ -68,7 +71,7 @@ def main():
     pairs = pair_list(a.pairs, n, a.root)
     pkg = importlib.import_module("sfm-gms_amd")
     r = pkg.structureFromMotionMulti(images, camera, dist, method=a.method, pairs=pairs, root=a.root, min_links=a.min_links,
-                                     max_keypoints=a.max_keypoints, keep_tables=True)
+                                     max_keypoints=a.max_keypoints, keep_tables=True, bundle=a.bundle)
     reg, views, tv = r["registration"], r["views"], r["two_view"]
     centres = [None if not v["registered"] else [round(float(x), 5) for x in -v["R"].T @ v["t"]] for v in views]
     obs, spread, cloud = r["cloud_obs"], r["cloud_spread"], r["cloud"]
@@ -86,7 +89,39 @@ def main():
             "median_depth": None if not len(depth) else round(float(np.median(depth)), 5),
             "median_spread": None if not len(many) else round(float(np.median(many)), 6),
             "median_spread_over_median_depth": None if not len(many) or not len(depth) else round(float(np.median(many) / np.median(depth)), 6)}
+    if a.bundle:
+        s, st = r["ba_summary"][0], np.bincount(r["track_status"], minlength=4)
+        line["bundle"] = {"rms_px_before": round(float(s["rms0_px"]), 4), "rms_px_after": round(float(s["rms_px"]), 4),
+                          "cost_before": round(float(s["cost0"]), 3), "cost_after": round(float(s["cost"]), 3),
+                          "iterations_run": int(s["iters_run"]), "iterations_accepted": int(s["iters_accepted"]), "cg_iterations": int(s["cg_iters"]),
+                          "observations": int(s["n_obs"]), "active": int(s["n_active"]), "free_frames": int(s["n_frames_free"]),
+                          "tracks_used": int(s["n_tracks_used"]), "tracks_excluded_two_keypoints_of_a_frame": int(st[1]),
+                          "tracks_excluded_fewer_than_two": int(st[2]), "tracks_kept_cloud_point_at_retriangulation": int(st[3]),
+                          "camera_centres": [None if not v["registered"] else [round(float(x), 5) for x in -v["R"].T @ v["t"]] for v in r["views_ba"]]}
     ok = True
+    if a.check and a.bundle:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import sfm_ba_ref as ba_ref
+        frames = r["tables"][0]
+        kp = frames.d_kp.cpu().numpy().view(pkg.KEYPOINT_DTYPE)[:int(frames.frame_off_host[-1])]
+        cam9 = tuple(camera) + (tuple(dist) if dist is not None else (0.0,) * 5)
+        args = (np.stack([kp["x"], kp["y"]], 1), frames.frame_off_host, r["pairs"], r["out"], r["mask"], views, reg, r["track"], r["cloud"],
+                r["cloud_id"], cam9)
+        fwd, rev = ba_ref.bundle_adjust(*args), ba_ref.bundle_adjust(*args, order=-1)
+
+        def rel(x, y, floor):
+            x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+            return float((np.abs(x - y) / np.maximum(np.maximum(np.abs(x), np.abs(y)), floor)).max()) if x.size else 0.0
+
+        def apart(p, q):
+            return max(rel(p["views_ba"]["R"], q["views_ba"]["R"], 1.0), rel(p["views_ba"]["t"], q["views_ba"]["t"], 1.0),
+                       rel(p["cloud_ba"], q["cloud_ba"], 1.0), rel(p["ba_summary"]["cost"], q["ba_summary"]["cost"], 1e-300))
+        tol = max(16.0 * apart(fwd, rev), 1e-12)   # 16 times what the order of the sums is worth, DESIGN.md 4.10c
+        ints = ("n_obs", "n_active", "n_tracks_used", "n_tracks_multi", "n_frames_free", "iters_run", "iters_accepted", "status")
+        chk = {"ba_integers": bool(np.array_equal(r["track_status"], fwd["track_status"]) and all(s[k] == fwd["ba_summary"][0][k] for k in ints)),
+               "ba_doubles": apart(r, fwd) <= tol}
+        line["bundle"]["check_vs_statement"] = dict(chk, tolerance=tol, apart=apart(r, fwd))
+        ok = all(chk.values())
     if a.check:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import sfm_register_ref as ref
@@ -110,7 +145,7 @@ def main():
                              and near(spread, want["cloud_spread"], 1.0 + (np.abs(fin).max() if fin.size else 0.0))),
                "summary": r["summary"].tobytes() == want["summary"].tobytes()}
         line["check_vs_statement"] = {k: bool(v) for k, v in chk.items()}
-        ok = all(chk.values())
+        ok = ok and all(chk.values())
     if a.ply:
         write_ply(a.ply, cloud, obs)
     print(json.dumps(line))
