@@ -943,6 +943,97 @@ int gms_warp_affine(const uint8_t* src, int src_width, int src_height, int chann
                     int dst_height);
 int gms_img_rotate(const uint8_t* src, int width, int height, int channels, double angle, uint8_t* dst);
 
+/* ---- a dense cloud from a posed pair: rectify, match, reproject (the library's own step) --------------------------
+ * The two-view stage leaves a pose (R, t) with X2 = R X1 + t; the stereo matchers read rectified pairs. This stage joins them. It
+ * follows cv::stereoRectify, initUndistortRectifyMap, remap and reprojectImageTo3D in structure; the definition is this library's
+ * (parity with an OpenCV build is unpinned), stated in csrc/rectify_core.h and in numpy in tests/rectify_ref.py: fp64, only
+ * + - * / sqrt rint in one fixed order, so that the GPU, a host build of the header and numpy agree bit for bit.
+ *   The plan of a pair: Rh = R^(-1/2) from the half-angle quaternion; b = -Rh t; a quarter turn Z about the optical axis that brings
+ *     b nearest +x (turn 0: none, 1: half turn, 2 / 3: quarter turns for a baseline along +y / -y); the rotation A that takes
+ *     g = Z b onto +x; R2 = A Z Rh, R1 = R2 R. Then R2 R R1^T = I and R2 t = (-B, 0, 0): camera 1 is the left image and points in
+ *     front have positive disparity. The new camera: fx' = fy' = min(fx, fy); each camera's principal point puts the mean of its four
+ *     undistorted, rotated source corners at the centre of the output, and both use the mean of the two, so that a point at
+ *     infinity has disparity 0. Output size: as asked, or for out_width / out_height <= 0 the source's (swapped for turns 2 and 3).
+ *     Not rectifiable (status GMS_ERR_NO_MODEL, every other field 0): trace R <= 0; g_x <= 0 or g_x < |g_z| (a baseline more than 45
+ *     degrees out of the image plane); a source corner with z <= 0 after the rotation.
+ *   A rectified byte: the ray R_k^T ((u - cx') / fx', (v - cy') / fy', 1); z <= 0: the byte is 0. Else the distortion model on
+ *     (x / z, y / z), the source position with 5 fractional bits (rint), the integer part saturated to int16, and gms_warp_affine's
+ *     blend of the four taps; a tap outside the source is 0 and is never read. valid (optional): 1 where all four taps are inside.
+ *   A point: pixel (u, v) of the int16 map (4 fractional bits) is a point when d16 != filtered16, d16 >= min_disp16 and its valid
+ *     byte is set. Z = fx' B 16 / d16, X = (u - cx') Z / fx', Y = (v - cy') Z / fx', p = R1^T (X, Y, Z): camera 1's frame in the unit
+ *     of t, as the pair's sparse points3d. With a registration (d_pairs, d_reg, d_views all given) p_world = G_a.R^T (S p - G_a.t),
+ *     as gms_sfm_register_device's d_points_world, and a pair whose registration status is not GMS_OK, or whose frame_a is not below n_frames, has no points. fp64, stored
+ *     as float32.
+ * gms_rectify_plan: one pair on the host, pure arithmetic. gms_rectify_plan_device: n_pairs pairs, R, t and status read from
+ *   d_tv on the device (a pair whose two-view status is not GMS_OK gets the zeroed plan); camera is a HOST pointer.
+ * gms_rectify_q: reprojectImageTo3D's 4 x 4 Q (row-major) of a plan, for disparities in pixels; host arithmetic.
+ * gms_rectify_device: n images (layout and accepted arguments as gms_warp_affine_device's) through plan i, or through one plan
+ *   (n_plans 1); which: 1 or 2, the camera of the pair. The plans are read by the kernel, so a captured graph follows new poses; a
+ *   plan whose status is not GMS_OK gives zeros. d_valid (optional): dense [n][dst_height][dst_width]. No workspace, no allocation,
+ *   no synchronisation, no readback (graph-capturable).
+ * gms_rectify, gms_undistort: ONE image on host pointers (dense rows), synchronous, on the current HIP device. gms_rectify writes
+ *   plan->out_w x out_h pixels; gms_undistort is cv::undistort with the new camera equal to the camera: no rotation, same size.
+ * gms_dense_cloud_device: per pair, in raster order, the first `cap` points: d_xyz float32 [n][cap][3], d_color (optional) the
+ *   bytes of d_image's pixel [n][cap][channels], d_pixel int32 [n][cap] = v * width + u; d_count int32 [n] states all the points,
+ *   also beyond cap. Entries past the count are left as they were. d_disp16 and d_valid are dense [n][height][width]; d_image
+ *   (optional: camera 1's rectified image, 1 or 3 channels) has rows image_pitch bytes apart. The order is fixed: counts per block
+ *   of 1024 pixels, a scan, then the writes; no atomic. min_disp16 >= 1; cap >= 0; width and height 1..GMS_WARP_MAX_SIDE;
+ *   d_workspace 256-byte aligned, gms_dense_cloud_workspace_bytes (0 for arguments that are refused). Stream-ordered, capturable.
+ * gms_dense_pairs_device: the whole stage for n_pairs pairs in stream order, with no allocation, synchronisation or readback
+ *   (graph-capturable): the plan kernel on d_tv; for BGR input (channels 3) gms_bgr_to_gray_device of both images; the grey images
+ *   rectified into d_rect1 / d_rect2 with camera 1's valid plane in d_valid; for BGR input camera 1's colour image rectified into
+ *   d_color; gms_stereo_sgm_device on the rectified pair into d_disp16; gms_dense_cloud_device with filtered16 =
+ *   (min_disparity - 1) * 16 and colours from d_color (d_rect1 for grey input), in the world frame with a registration. Images
+ *   are dense: pair i's image of camera k at d_imgk + i * height * width * channels. out_width, out_height >= 1: the rectified
+ *   size of every pair (the plans are made for it). params NULL: GMS_STEREO_SGM_PARAMS_DENSE, the reference's record with
+ *   min_disparity 0 and num_disparities 128 (the shared principal point makes every true disparity positive). d_plans [n],
+ *   d_rect1, d_rect2, d_valid [n][out_height][out_width], d_color [n][out_height][out_width][3] (BGR input only), d_disp16 likewise
+ *   int16; the cloud outputs as gms_dense_cloud_device's, d_cloud_color with `channels` bytes per point. A pair whose two-view
+ *   status is not GMS_OK, or that is not rectifiable, has zero images, no valid pixel and count 0.
+ * gms_dense_pairs_workspace_bytes: its workspace (256-byte aligned pointer); 0 for arguments that are refused.
+ * gms_dense_pair: ONE pair on host pointers (dense rows; R [9] and t [3] on the host), synchronous, on the current HIP device. The
+ *   plan comes back in *plan; out_width / out_height <= 0: its default size, which the caller reads from gms_rectify_plan_host
+ *   beforehand to size rect1, rect2, valid [plan.out_h][plan.out_w], color (BGR input; optional) and disp16. Returns
+ *   GMS_ERR_NO_MODEL when the pair is not rectifiable (nothing but *plan is written). cap points at most; *count states all. */
+#define GMS_STEREO_SGM_PARAMS_DENSE {{5, 128, 0, GMS_STEREO_BM_PREFILTER_XSOBEL, 5, 61, 507, 0, 0, 8, 1}, 200, 800, 8}
+typedef struct gms_rectify_plan {
+    double  R1[9], R2[9];          /* x_rectified = R_k x_camera_k                                            */
+    double  fx, fy, cx, cy;        /* the new camera of both images (fx = fy from gms_rectify_plan)           */
+    double  B;                     /* the baseline |t|: R2 t = (-B, 0, 0)                                     */
+    int32_t out_w, out_h;          /* the size the principal point was made for                               */
+    int32_t turn;                  /* 0: none, 1: half turn, 2: quarter turn (baseline +y), 3: (baseline -y)  */
+    int32_t status;                /* GMS_OK or GMS_ERR_NO_MODEL                                              */
+} gms_rectify_plan;
+int gms_rectify_plan_host(const gms_camera* camera, const double* R, const double* t, int width, int height, int out_width,
+                          int out_height, gms_rectify_plan* plan);
+int gms_rectify_plan_device(gms_ctx* ctx, const gms_camera* camera, const gms_two_view* d_tv, int n_pairs, int width, int height,
+                            int out_width, int out_height, gms_rectify_plan* d_plans);
+int gms_rectify_q(const gms_rectify_plan* plan, double* Q);
+int gms_rectify_device(gms_ctx* ctx, const gms_camera* camera, const uint8_t* d_src, int n, int src_width, int src_height, int channels,
+                       int src_pitch, const gms_rectify_plan* d_plans, int n_plans, int which, uint8_t* d_dst, int dst_width,
+                       int dst_height, int dst_pitch, uint8_t* d_valid);
+int gms_rectify(const gms_camera* camera, const gms_rectify_plan* plan, int which, const uint8_t* src, int src_width, int src_height,
+                int channels, uint8_t* dst, uint8_t* valid);
+int gms_undistort(const gms_camera* camera, const uint8_t* src, int width, int height, int channels, uint8_t* dst);
+size_t gms_dense_cloud_workspace_bytes(int width, int height, int n_pairs);
+int gms_dense_cloud_device(gms_ctx* ctx, const int16_t* d_disp16, const uint8_t* d_valid, const uint8_t* d_image, int channels,
+                           int image_pitch, int n_pairs, int width, int height, const gms_rectify_plan* d_plans, int filtered16,
+                           int min_disp16, const gms_pair* d_pairs, const gms_sfm_pair_reg* d_reg, const gms_sfm_view* d_views,
+                           int n_frames, void* d_workspace, size_t workspace_bytes, int cap, float* d_xyz, uint8_t* d_color, int32_t* d_pixel,
+                           int32_t* d_count);
+size_t gms_dense_pairs_workspace_bytes(int src_width, int src_height, int channels, int out_width, int out_height, int n_pairs,
+                                       const gms_stereo_sgm_params* params);
+int gms_dense_pairs_device(gms_ctx* ctx, const gms_camera* camera, const gms_stereo_sgm_params* params, const uint8_t* d_img1,
+                           const uint8_t* d_img2, int n_pairs, int src_width, int src_height, int channels, const gms_two_view* d_tv,
+                           int out_width, int out_height, int min_disp16, const gms_pair* d_pairs, const gms_sfm_pair_reg* d_reg,
+                           const gms_sfm_view* d_views, int n_frames, void* d_workspace, size_t workspace_bytes, gms_rectify_plan* d_plans,
+                           uint8_t* d_rect1, uint8_t* d_rect2, uint8_t* d_valid, uint8_t* d_color, int16_t* d_disp16, int cap, float* d_xyz,
+                           uint8_t* d_cloud_color, int32_t* d_pixel, int32_t* d_count);
+int gms_dense_pair(const gms_camera* camera, const gms_stereo_sgm_params* params, const uint8_t* img1, const uint8_t* img2, int width,
+                   int height, int channels, const double* R, const double* t, int out_width, int out_height, int min_disp16,
+                   gms_rectify_plan* plan, uint8_t* rect1, uint8_t* rect2, uint8_t* valid, uint8_t* color, int16_t* disp16, int cap,
+                   float* xyz, uint8_t* cloud_color, int32_t* pixel, int32_t* count);
+
 /* ---- camera calibration from chessboard photographs (main.cpp:53-68, CalibrationUtil.cpp:3-53) ---------------------
  * The corner finder is THIS LIBRARY'S OWN definition, not OpenCV's quad-based findChessboardCorners; cornerSubPix restates OpenCV
  * 4.5.2's algorithm in fp64; calibrateCamera follows its structure. Parity with an OpenCV build is unpinned. tests/calib_ref.py states

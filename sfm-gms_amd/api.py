@@ -14,7 +14,8 @@ import numpy as np
 from .capi import load_library
 from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, LOGOS_DICT_RESULT_DTYPE, KEYPOINT_DTYPE, PAIR_DTYPE, RESULT_DTYPE, GMS_OK, GMS_ERR_CAPACITY,
                     GmsError, SFM_PAIR_REG_DTYPE, SFM_PLAN_DTYPE, SFM_SUMMARY_DTYPE, SFM_VIEW_DTYPE, TWO_VIEW_DTYPE, concat_frames, desc_layout,
-                    portrait_params, stereo_bm_params, stereo_sgm_params)
+                    portrait_params, stereo_bm_params, stereo_sgm_params, GMS_ERR_BAD_ARG, RECTIFY_PLAN_DTYPE, STEREO_SGM_DENSE, RectifyPlan,
+                    make_camera, rectify_plan_records)
 
 
 def _as(arr, dtype, name):
@@ -461,6 +462,48 @@ class GmsContext:
                                                 d_M, int(n_matrices), d_dst, int(dst_width), int(dst_height), int(dst_pitch)), self._lib,
                "gms_warp_affine_device")
 
+    # -- a dense cloud from a posed pair (batch.Rectify / batch.DensePairs drive these) ------------------------------
+    def rectify_plan_device(self, camera, d_tv, n_pairs, width, height, out_width, out_height, d_plans):
+        """gms_rectify_plan_device: camera a CAMERA_DTYPE record (host), d_tv TWO_VIEW_DTYPE records and d_plans RECTIFY_PLAN_DTYPE
+        records on the device. Stream-ordered."""
+        _check(self._lib.gms_rectify_plan_device(self._h, camera.ctypes.data, d_tv or None, int(n_pairs), int(width), int(height),
+                                                 int(out_width), int(out_height), d_plans or None), self._lib, "gms_rectify_plan_device")
+
+    def rectify_device(self, camera, d_src, n, src_width, src_height, channels, src_pitch, d_plans, n_plans, which, d_dst, dst_width,
+                       dst_height, dst_pitch, d_valid=None):
+        """gms_rectify_device on raw device pointers; the plans are read when the kernel runs. Stream-ordered."""
+        _check(self._lib.gms_rectify_device(self._h, camera.ctypes.data, d_src, int(n), int(src_width), int(src_height), int(channels),
+                                            int(src_pitch), d_plans or None, int(n_plans), int(which), d_dst, int(dst_width), int(dst_height),
+                                            int(dst_pitch), d_valid or None), self._lib, "gms_rectify_device")
+
+    def dense_cloud_workspace_bytes(self, width, height, n_pairs):
+        return int(self._lib.gms_dense_cloud_workspace_bytes(int(width), int(height), int(n_pairs)))
+
+    def dense_cloud_device(self, d_disp16, d_valid, d_image, channels, image_pitch, n_pairs, width, height, d_plans, filtered16, min_disp16,
+                           d_ws, ws_bytes, cap, d_xyz, d_color, d_pixel, d_count, d_pairs=None, d_reg=None, d_views=None, n_frames=0):
+        """gms_dense_cloud_device on raw device pointers. Stream-ordered."""
+        _check(self._lib.gms_dense_cloud_device(self._h, d_disp16 or None, d_valid or None, d_image or None, int(channels), int(image_pitch),
+                                                int(n_pairs), int(width), int(height), d_plans or None, int(filtered16), int(min_disp16),
+                                                d_pairs or None, d_reg or None, d_views or None, int(n_frames), d_ws or None, int(ws_bytes),
+                                                int(cap), d_xyz or None, d_color or None, d_pixel or None, d_count or None), self._lib,
+               "gms_dense_cloud_device")
+
+    def dense_pairs_workspace_bytes(self, src_width, src_height, channels, out_width, out_height, n_pairs, params=None):
+        return int(self._lib.gms_dense_pairs_workspace_bytes(int(src_width), int(src_height), int(channels), int(out_width), int(out_height),
+                                                             int(n_pairs), dense_sgm_params(params).ctypes.data))
+
+    def dense_pairs_device(self, camera, params, d_img1, d_img2, n_pairs, src_width, src_height, channels, d_tv, out_width, out_height,
+                           min_disp16, d_ws, ws_bytes, d_plans, d_rect1, d_rect2, d_valid, d_color, d_disp16, cap, d_xyz, d_cloud_color,
+                           d_pixel, d_count, d_pairs=None, d_reg=None, d_views=None, n_frames=0):
+        """gms_dense_pairs_device on raw device pointers; params: None (GMS_STEREO_SGM_PARAMS_DENSE), a dict or a record. Stream-ordered."""
+        rec = dense_sgm_params(params)
+        _check(self._lib.gms_dense_pairs_device(self._h, camera.ctypes.data, rec.ctypes.data, d_img1 or None, d_img2 or None, int(n_pairs),
+                                                int(src_width), int(src_height), int(channels), d_tv or None, int(out_width), int(out_height),
+                                                int(min_disp16), d_pairs or None, d_reg or None, d_views or None, int(n_frames), d_ws or None,
+                                                int(ws_bytes), d_plans or None, d_rect1 or None, d_rect2 or None, d_valid or None,
+                                                d_color or None, d_disp16 or None, int(cap), d_xyz or None, d_cloud_color or None,
+                                                d_pixel or None, d_count or None), self._lib, "gms_dense_pairs_device")
+
     # -- chessboard corner candidates and cornerSubPix (DESIGN.md 4.12; batch.ChessCorners drives these) ---------------------------------
     def chess_candidates_workspace_bytes(self, width, height, n_images):
         return int(self._lib.gms_chess_candidates_workspace_bytes(int(width), int(height), int(n_images)))
@@ -613,7 +656,9 @@ def structureFromMotion(img1, img2, camera, dist=None, method="logos", ctx=None,
     Returns a dict: points3D float64 [k, 3] (the inliers' points, in their order), R [3, 3], t [3], E [3, 3], matches (the method's
     surviving DMATCH_DTYPE records), mask (uint8 per surviving match: 0 = not an inlier of the pose), keypoints1, keypoints2
     (KEYPOINT_DTYPE), two_view (the pair's TWO_VIEW_DTYPE record: counts, iterations, reprojection sums) and detail (run_images'
-    record, with `tables`: the resident FrameTable and DescriptorTable). A pair without a pose raises GmsError with the two-view status."""
+    record, with `tables`: the resident FrameTable and DescriptorTable). A pair without a pose raises GmsError with the two-view status.
+    dense=True among params (run_images' min_disp16, dense_cap, dense_sgm): adds `dense`, the pair's dense cloud in
+    points3D's frame and unit -- a dict of points, colors, pixel, count and plan, or None when the pose is not rectifiable."""
     from . import pipeline
     if method not in pipeline.METHODS:
         raise ValueError(f"unknown method {method!r}")
@@ -635,9 +680,12 @@ def structureFromMotion(img1, img2, camera, dist=None, method="logos", ctx=None,
         raise GmsError(int(r["results"]["status"][0]) or int(tv["status"]), "structureFromMotion: no pose for this pair")
     kp = frames.d_kp.cpu().numpy()[: frames.total * KEYPOINT_DTYPE.itemsize].view(KEYPOINT_DTYPE)
     f = frames.frame_off_host
-    return dict(points3D=r["points3d"][off:off + int(tv["n_triangulated"])].copy(), R=tv["R"].copy(), t=tv["t"].copy(), E=tv["E"].copy(),
-                matches=r["out"][off:off + k].copy(), mask=r["mask"][off:off + k].copy(), keypoints1=kp[f[0]:f[1]].copy(),
-                keypoints2=kp[f[1]:f[2]].copy(), two_view=tv, detail=r)
+    out = dict(points3D=r["points3d"][off:off + int(tv["n_triangulated"])].copy(), R=tv["R"].copy(), t=tv["t"].copy(), E=tv["E"].copy(),
+               matches=r["out"][off:off + k].copy(), mask=r["mask"][off:off + k].copy(), keypoints1=kp[f[0]:f[1]].copy(),
+               keypoints2=kp[f[1]:f[2]].copy(), two_view=tv, detail=r)
+    if "dense" in r:
+        out["dense"] = r["dense"][0]
+    return out
 
 
 def sfm_plan(pairs, n_frames, root=0):
@@ -926,6 +974,153 @@ def imgRotate(image, angle):
     size. 180 degrees is NOT image[::-1, ::-1]: it is that flip moved by one pixel, behind a black first row and column."""
     h, w = image.shape[:2]
     return warpAffine(image, getRotationMatrix2D((w / 2., h / 2.), angle, 1.0), (w, h))
+
+
+def dense_sgm_params(params=None, **kw):
+    """The matcher's record of the dense stage: types.stereo_sgm_params with min_disparity 0 and num_disparities 128 unless given."""
+    vals = dict(STEREO_SGM_DENSE)
+    if params is not None:
+        if not isinstance(params, dict):
+            return stereo_sgm_params(params, **kw)
+        vals.update(params)
+    vals.update(kw)
+    return stereo_sgm_params(vals)
+
+
+def stereoRectify(camera, dist, R, t, image_size, out_size=None):
+    """The rectifying plan of a posed pair X2 = R X1 + t (gms_rectify_plan_host; host arithmetic, no GPU work; DESIGN.md 4.13;
+    tests/rectify_ref.py states it): a one-record RECTIFY_PLAN_DTYPE array with R1, R2 (x_rectified = R_k x_camera_k), the new camera
+    fx = fy, cx, cy of both images, the baseline B, the output size and the quarter turn chosen. camera = (fx, fy, cx, cy), dist =
+    (k1, k2, p1, p2, k3) or None, image_size = (W, H); out_size None: (W, H), or (H, W) for the quarter turns. A pair that is not
+    rectifiable has status GMS_ERR_NO_MODEL and zeros elsewhere. rectifyQ(plan) gives reprojectImageTo3D's Q."""
+    lib = load_library()
+    cam = make_camera(camera, dist)
+    R = np.ascontiguousarray(R, dtype=np.float64).reshape(9)
+    t = np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+    plan = np.zeros(1, RECTIFY_PLAN_DTYPE)
+    ow, oh = (0, 0) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    _check(lib.gms_rectify_plan_host(cam.ctypes.data, R.ctypes.data, t.ctypes.data, int(image_size[0]), int(image_size[1]), ow, oh,
+                                     plan.ctypes.data), lib, "gms_rectify_plan_host")
+    return RectifyPlan(plan, cam)
+
+
+def rectifyQ(plan):
+    """reprojectImageTo3D's 4 x 4 Q of a plan, for disparities in pixels (the int16 map / 16)."""
+    lib = load_library()
+    plan, Q = _plan_record(plan), np.zeros((4, 4))
+    _check(lib.gms_rectify_q(plan.ctypes.data, Q.ctypes.data), lib, "gms_rectify_q")
+    return Q
+
+
+def _plan_record(plan):
+    plan = rectify_plan_records(plan)
+    if len(plan) != 1:
+        raise ValueError("plan: one RECTIFY_PLAN_DTYPE record")
+    return plan
+
+
+def rectify(image, plan, which, camera=None, dist=None, return_valid=False):
+    """The rectified image of camera `which` (1 or 2) of a pair under stereoRectify's plan: uint8 [plan.out_h, plan.out_w(, 3)]; a
+    pixel whose ray leaves the source is 0. The source camera is the plan's own (a RectifyPlan); camera / dist state it for a bare
+    RECTIFY_PLAN_DTYPE record. Host array -> host array (gms_rectify), device tensor -> device tensor (batch.Rectify).
+    return_valid=True: also the uint8 plane that is 1 where all four taps lie inside the source."""
+    if camera is None and not isinstance(plan, RectifyPlan):
+        raise ValueError("rectify: a RectifyPlan, or a plan record with the source camera")
+    cam = plan.camera if camera is None else make_camera(camera, dist)
+    plan = _plan_record(plan)
+    if _is_tensor(image):
+        from .batch import Rectify
+        if image.dim() not in (2, 3) or (image.dim() == 3 and image.shape[2] != 3):
+            raise ValueError("rectify: [H, W] or [H, W, 3]")
+        ctx = default_context()
+        run = Rectify(ctx, 1, (image.shape[1], image.shape[0]), (int(plan["out_w"][0]), int(plan["out_h"][0])), cam,
+                      1 if image.dim() == 2 else 3, n_plans=1, device=image.device)
+        run.set_plans(plan)
+        out = run.run(image.contiguous()[None], which)[0]
+        ctx.synchronize()
+        return (out, run.d_valid[0]) if return_valid else out
+    lib = load_library()
+    img, w, h, c = _host_image(image, "rectify")
+    ow, oh = int(plan["out_w"][0]), int(plan["out_h"][0])
+    if ow < 1 or oh < 1:
+        raise ValueError("rectify: the plan has no output size (a pair that is not rectifiable?)")
+    out = np.zeros((oh, ow) + img.shape[2:], np.uint8)
+    valid = np.zeros((oh, ow), np.uint8) if return_valid else None
+    _check(lib.gms_rectify(cam.ctypes.data, plan.ctypes.data, int(which), img.ctypes.data, w, h, c, out.ctypes.data,
+                           None if valid is None else valid.ctypes.data), lib, "gms_rectify")
+    return (out, valid) if return_valid else out
+
+
+def undistort(image, camera, dist):
+    """cv::undistort(image, cameraMatrix, distCoeffs) with the new camera equal to the camera (gms_undistort): the identity plan of
+    the rectifying kernel. Host array -> host array, device tensor -> device tensor."""
+    cam = make_camera(camera, dist)
+    if _is_tensor(image):
+        plan = np.zeros(1, RECTIFY_PLAN_DTYPE)
+        plan["R1"][0] = plan["R2"][0] = np.eye(3)
+        plan["fx"], plan["fy"], plan["cx"], plan["cy"] = [float(v) for v in camera]
+        plan["out_w"], plan["out_h"] = int(image.shape[1]), int(image.shape[0])
+        return rectify(image, plan, 1, camera, dist if dist is not None else np.zeros(5))
+    lib = load_library()
+    img, w, h, c = _host_image(image, "undistort")
+    out = np.zeros_like(img)
+    _check(lib.gms_undistort(cam.ctypes.data, img.ctypes.data, w, h, c, out.ctypes.data), lib, "gms_undistort")
+    return out
+
+
+def denseStereo(img1, img2, camera, dist, R, t, min_disp16=16, out_size=None, cap=None, **sgm_params):
+    """A dense, coloured cloud from a posed pair X2 = R X1 + t: stereoRectify's plan, both images rectified, stereoSGM
+    on the rectified pair, every matched pixel reprojected into camera 1's frame in the unit of t -- the frame and unit of
+    structureFromMotion's points3D. img1 / img2: uint8 [H, W] or [H, W, 3] BGR of one size, host arrays (gms_dense_pair) or device
+    tensors (batch.DensePairs). sgm_params: stereoSGM's keywords; min_disparity 0 and num_disparities 128 unless given. cap: the most
+    points returned (default: every pixel). Returns a dict: points float32 [k, 3], colors uint8 [k] or [k, 3], pixel int32 [k]
+    (v * out_w + u of the rectified image, raster order), disp16 int16, rect1, rect2, valid (camera 1's), plan, count (all the points,
+    also beyond cap). A pair that is not rectifiable raises GmsError(GMS_ERR_NO_MODEL)."""
+    shapes = [tuple(im.shape) for im in (img1, img2)]
+    if len(shapes[0]) not in (2, 3) or (len(shapes[0]) == 3 and shapes[0][2] != 3) or shapes[0] != shapes[1]:
+        raise ValueError("img1 / img2: [H, W] grey or [H, W, 3] BGR, one size")
+    if int(min_disp16) < 1:
+        raise GmsError(GMS_ERR_BAD_ARG, "denseStereo: min_disp16 >= 1")
+    h, w = shapes[0][:2]
+    c = 1 if len(shapes[0]) == 2 else 3
+    plan = stereoRectify(camera, dist, R, t, (w, h), out_size)
+    if not plan.ok:
+        raise GmsError(int(plan["status"]), "denseStereo: the pair is not rectifiable")
+    ow, oh = plan.out_size
+    cap = ow * oh if cap is None else int(cap)
+    rec = dense_sgm_params(sgm_params)
+    if _is_tensor(img1):
+        from .batch import DensePairs
+        import torch
+        ctx = default_context()
+        run = DensePairs(ctx, 1, (w, h), (ow, oh), camera, dist, c, cap=cap, min_disp16=min_disp16, params=rec, device=img1.device)
+        tv = np.zeros(1, TWO_VIEW_DTYPE)
+        tv["R"][0], tv["t"][0] = np.asarray(R, dtype=np.float64).reshape(3, 3), np.asarray(t, dtype=np.float64).reshape(3)
+        run.set_two_view(tv)
+        torch.cuda.synchronize(img1.device)
+        run.run(img1.contiguous()[None], img2.contiguous()[None])
+        ctx.synchronize()
+        k = min(int(run.d_count[0]), cap)
+        return dict(points=run.d_xyz[0, :k], colors=run.d_cloud_color[0, :k] if c == 3 else run.d_cloud_color[0, :k, 0], pixel=run.d_pixel[0, :k],
+                    disp16=run.d_disp16[0], rect1=run.d_color[0] if c == 3 else run.d_rect1[0], rect2=run.d_rect2[0], valid=run.d_valid[0],
+                    plan=plan, count=int(run.d_count[0]))
+    lib = load_library()
+    cam = make_camera(camera, dist)
+    a, b = np.ascontiguousarray(img1, dtype=np.uint8), np.ascontiguousarray(img2, dtype=np.uint8)
+    Rv, tvec = np.ascontiguousarray(R, dtype=np.float64).reshape(9), np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+    rect1, rect2, valid = (np.zeros((oh, ow), np.uint8) for _ in range(3))
+    color = np.zeros((oh, ow, 3), np.uint8) if c == 3 else None
+    disp16 = np.zeros((oh, ow), np.int16)
+    xyz, cc, pixel = np.zeros((max(cap, 1), 3), np.float32), np.zeros((max(cap, 1), c), np.uint8), np.zeros(max(cap, 1), np.int32)
+    count = np.zeros(1, np.int32)
+    out_plan = np.zeros(1, RECTIFY_PLAN_DTYPE)
+    _check(lib.gms_dense_pair(cam.ctypes.data, rec.ctypes.data, a.ctypes.data, b.ctypes.data, w, h, c, Rv.ctypes.data, tvec.ctypes.data, ow, oh,
+                              int(min_disp16), out_plan.ctypes.data, rect1.ctypes.data, rect2.ctypes.data, valid.ctypes.data,
+                              None if color is None else color.ctypes.data, disp16.ctypes.data, cap, xyz.ctypes.data, cc.ctypes.data,
+                              pixel.ctypes.data, count.ctypes.data), lib, "gms_dense_pair")
+    k = min(int(count[0]), cap)
+    return dict(points=xyz[:k], colors=cc[:k] if c == 3 else cc[:k, 0], pixel=pixel[:k], disp16=disp16, rect1=color if c == 3 else rect1,
+                rect2=rect2, valid=valid, plan=RectifyPlan(out_plan, cam), count=int(count[0]))
 
 
 def _grey_host(image, who):

@@ -10,7 +10,8 @@ import torch
 
 from .api import GmsContext, logos_dict_args
 from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128, GMS_ERR_CAPACITY, KEYPOINT_DTYPE, LOGOS_DICT_RESULT_DTYPE, LOGOS_RESULT_DTYPE, PAIR_DTYPE,
-                    RESULT_DTYPE, concat_frames, desc_layout, portrait_params, stereo_bm_params, stereo_sgm_params)
+                    RESULT_DTYPE, concat_frames, desc_layout, portrait_params, stereo_bm_params, stereo_sgm_params, CAMERA_DTYPE, GMS_ERR_BAD_ARG, GmsError,
+                    RECTIFY_PLAN_DTYPE, TWO_VIEW_DTYPE, make_camera, rectify_plan_records)
 
 
 def _to_dev(arr, device):
@@ -907,6 +908,107 @@ def warp_affine_images(images, M, dsize, ctx=None):
     run.warp_affine(d)
     ctx.synchronize()
     return run.d_dst if on_dev else run.d_dst.cpu().numpy()
+
+
+class Rectify:
+    """Device buffers of gms_rectify_device for n images of one size and channel count (1: [n, H, W]; 3: [n, H, W, 3]): the rectified
+    images d_dst, the valid planes d_valid [n, H', W'] and the plans d_plans (RECTIFY_PLAN_DTYPE bytes; n_plans 1: one for all
+    images, or n), sized once, so that run() can be repeated or captured into a graph. The kernel reads d_plans when it runs: a
+    captured graph follows set_plans(). camera: a CAMERA_DTYPE record (types.make_camera), the source camera of every image."""
+
+    def __init__(self, ctx, n, src_size, dst_size, camera, channels=1, n_plans=1, device=None):
+        self.ctx, self.n, self.channels, self.n_plans = ctx, int(n), int(channels), int(n_plans)
+        (self.sw, self.sh), (self.dw, self.dh) = (int(v) for v in src_size), (int(v) for v in dst_size)
+        if self.channels not in (1, 3) or self.n < 1 or min(self.sw, self.sh, self.dw, self.dh) < 1 or self.n_plans not in (1, self.n):
+            raise ValueError("Rectify: channels 1 or 3, n >= 1, positive sizes, n_plans 1 or n")
+        self.camera = np.ascontiguousarray(camera, dtype=CAMERA_DTYPE).reshape(1)
+        dev = _device(ctx, device)
+        tail = () if self.channels == 1 else (3,)
+        self.src_shape = (self.n, self.sh, self.sw) + tail
+        self.d_dst = torch.zeros((self.n, self.dh, self.dw) + tail, dtype=torch.uint8, device=dev)
+        self.d_valid = torch.zeros((self.n, self.dh, self.dw), dtype=torch.uint8, device=dev)
+        self.d_plans = torch.zeros((self.n_plans, RECTIFY_PLAN_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+
+    def set_plans(self, plans):
+        """n_plans RECTIFY_PLAN_DTYPE records (or RectifyPlan objects) on the host -> d_plans (a copy on torch's current stream)."""
+        rec = rectify_plan_records(plans)
+        if len(rec) != self.n_plans:
+            raise ValueError(f"plans: {self.n_plans} records")
+        self.d_plans.copy_(torch.from_numpy(rec.view(np.uint8).reshape(self.n_plans, -1)))
+
+    def run(self, d_src, which):
+        """gms_rectify_device of camera `which` (1 or 2) by d_plans into d_dst and d_valid. Stream-ordered on the context's stream."""
+        if d_src.dtype != torch.uint8 or tuple(d_src.shape) != self.src_shape or not d_src.is_contiguous():
+            raise ValueError(f"images: a contiguous uint8 device tensor {self.src_shape}")
+        self.ctx.rectify_device(self.camera, d_src.data_ptr(), self.n, self.sw, self.sh, self.channels, self.sw * self.channels,
+                                self.d_plans.data_ptr(), self.n_plans, which, self.d_dst.data_ptr(), self.dw, self.dh,
+                                self.dw * self.channels, self.d_valid.data_ptr())
+        return self.d_dst
+
+
+class DensePairs:
+    """Device buffers of gms_dense_pairs_device for n pairs of one image size (channels 1: [n, H, W] grey; 3: [n, H, W, 3] BGR) and one
+    rectified size: the workspace, the two-view records d_tv (TWO_VIEW_DTYPE bytes; the stage reads R, t and status), the plans, the
+    rectified images d_rect1 / d_rect2 (grey), d_color (BGR input: camera 1's rectified colour image), d_valid, d_disp16 and the
+    cloud (d_xyz [n, cap, 3], d_cloud_color [n, cap, channels], d_pixel [n, cap], d_count [n]), sized once, so that run() can be
+    repeated or captured into a graph; it is one stream with no parallel branches. The kernels read d_tv when they run: a captured
+    graph follows set_two_view(). d_tv may also be the tensor a two-view stage writes (pass d_tv=). With a registration
+    (set_registration) the points are in the world frame."""
+
+    def __init__(self, ctx, n, src_size, out_size, camera, dist=None, channels=1, cap=None, min_disp16=16, params=None, device=None, d_tv=None):
+        from .api import dense_sgm_params
+        self.ctx, self.n, self.channels, self.min_disp16 = ctx, int(n), int(channels), int(min_disp16)
+        (self.sw, self.sh), (self.ow, self.oh) = (int(v) for v in src_size), (int(v) for v in out_size)
+        self.camera = make_camera(camera, dist) if not isinstance(camera, np.ndarray) or camera.dtype != CAMERA_DTYPE else camera
+        self.params = dense_sgm_params(params)
+        self.cap = self.ow * self.oh if cap is None else int(cap)
+        self.ws_bytes = ctx.dense_pairs_workspace_bytes(self.sw, self.sh, self.channels, self.ow, self.oh, self.n, self.params)
+        if self.ws_bytes == 0:
+            raise GmsError(GMS_ERR_BAD_ARG, "DensePairs: sizes, channels or matcher parameters outside what gms_dense_pairs_device accepts")
+        dev = _device(ctx, device)
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        self.src_shape = (self.n, self.sh, self.sw) + (() if self.channels == 1 else (3,))
+        self.d_ws = z((self.ws_bytes,), torch.uint8)
+        self.d_tv = d_tv if d_tv is not None else z((self.n, TWO_VIEW_DTYPE.itemsize), torch.uint8)
+        self.d_plans = z((self.n, RECTIFY_PLAN_DTYPE.itemsize), torch.uint8)
+        self.d_rect1, self.d_rect2, self.d_valid = (z((self.n, self.oh, self.ow), torch.uint8) for _ in range(3))
+        self.d_color = z((self.n, self.oh, self.ow, 3), torch.uint8) if self.channels == 3 else None
+        self.d_disp16 = z((self.n, self.oh, self.ow), torch.int16)
+        k = max(self.cap, 1)
+        self.d_xyz, self.d_cloud_color = z((self.n, k, 3), torch.float32), z((self.n, k, self.channels), torch.uint8)
+        self.d_pixel, self.d_count = z((self.n, k), torch.int32), z((self.n,), torch.int32)
+        self.reg = None
+        torch.cuda.synchronize(dev)
+
+    def set_two_view(self, two_view):
+        """n TWO_VIEW_DTYPE records on the host -> d_tv (a copy on torch's current stream)."""
+        rec = np.ascontiguousarray(two_view, dtype=TWO_VIEW_DTYPE).reshape(self.n)
+        self.d_tv.copy_(torch.from_numpy(rec.view(np.uint8).reshape(self.n, -1)))
+
+    def set_registration(self, d_pairs, d_reg, d_views, n_frames):
+        """The device tensors of the pairs (PAIR_DTYPE), their registration (SFM_PAIR_REG_DTYPE) and the views (SFM_VIEW_DTYPE) as
+        SfmRegister leaves them; None, None, None, 0 for camera 1's frame."""
+        self.reg = None if d_pairs is None else (d_pairs, d_reg, d_views, int(n_frames))
+
+    def plans(self):
+        """The plans of the last run, RECTIFY_PLAN_DTYPE [n] on the host (synchronises)."""
+        return self.d_plans.cpu().numpy().reshape(-1).view(RECTIFY_PLAN_DTYPE).copy()
+
+    def run(self, d_img1, d_img2):
+        """gms_dense_pairs_device. Stream-ordered on the context's stream; no allocation, no synchronisation."""
+        for d in (d_img1, d_img2):
+            if d.dtype != torch.uint8 or tuple(d.shape) != self.src_shape or not d.is_contiguous():
+                raise ValueError(f"images: contiguous uint8 device tensors {self.src_shape}")
+        reg = {} if self.reg is None else dict(d_pairs=self.reg[0].data_ptr(), d_reg=self.reg[1].data_ptr(), d_views=self.reg[2].data_ptr(),
+                                               n_frames=self.reg[3])
+        self.ctx.dense_pairs_device(self.camera, self.params, d_img1.data_ptr(), d_img2.data_ptr(), self.n, self.sw, self.sh, self.channels,
+                                    self.d_tv.data_ptr(), self.ow, self.oh, self.min_disp16, self.d_ws.data_ptr(), self.ws_bytes,
+                                    self.d_plans.data_ptr(), self.d_rect1.data_ptr(), self.d_rect2.data_ptr(), self.d_valid.data_ptr(),
+                                    None if self.d_color is None else self.d_color.data_ptr(), self.d_disp16.data_ptr(), self.cap,
+                                    self.d_xyz.data_ptr(), self.d_cloud_color.data_ptr(), self.d_pixel.data_ptr(), self.d_count.data_ptr(),
+                                    **reg)
+        return self.d_count
 
 
 class ChessCorners:

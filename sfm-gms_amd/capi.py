@@ -85,6 +85,18 @@ SIGNATURES = {
     "gms_resize": (i32, [vp, i32, i32, i32, vp, i32, i32]),
     "gms_warp_affine": (i32, [vp, i32, i32, i32, vp, vp, i32, i32]),
     "gms_img_rotate": (i32, [vp, i32, i32, i32, dbl, vp]),
+    "gms_rectify_plan_host": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
+    "gms_rectify_plan_device": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "gms_rectify_q": (i32, [vp, vp]),
+    "gms_rectify_device": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, i32, vp]),
+    "gms_rectify": (i32, [vp, vp, i32, vp, i32, i32, i32, vp, vp]),
+    "gms_undistort": (i32, [vp, vp, i32, i32, i32, vp]),
+    "gms_dense_cloud_workspace_bytes": (sz, [i32, i32, i32]),
+    "gms_dense_cloud_device": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, i32, vp, sz, i32, vp, vp, vp, vp]),
+    "gms_dense_pairs_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32, vp]),
+    "gms_dense_pairs_device": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, i32, vp, sz, vp, vp, vp, vp, vp, vp,
+                                     i32, vp, vp, vp, vp]),
+    "gms_dense_pair": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
     "gms_chess_candidates_workspace_bytes": (sz, [i32, i32, i32]),
     "gms_chess_candidates_device": (i32, [vp, vp, i32, i32, i32, i32, vp, sz, vp, vp]),
     "gms_corner_subpix_device": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, dbl, vp]),

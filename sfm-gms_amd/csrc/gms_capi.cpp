@@ -30,6 +30,7 @@
 #include "sfm_register_core.h"
 #include "stereo_sgm_core.h"
 #include "twoview_core.h"
+#include "rectify_core.h"
 #include "warp_core.h"
 #include "calib_core.h"
 
@@ -1451,6 +1452,226 @@ int gms_img_rotate(const uint8_t* src, int width, int height, int channels, doub
     double M[6];
     warp::rotation_matrix_2d(width / 2., height / 2., angle, 1.0, M);
     return gms_warp_affine(src, width, height, channels, M, dst, width, height);
+}
+
+// ---- a dense cloud from a posed pair (rectify_kernels.hip, rectify_core.h) ------------------------------------------
+static_assert(sizeof(gms_rectify_plan) == 200, "gms_rectify_plan: 23 doubles and four 32-bit words");
+
+int gms_rectify_plan_host(const gms_camera* camera, const double* R, const double* t, int width, int height, int out_w, int out_h,
+                          gms_rectify_plan* plan)
+{
+    if (!camera || !R || !t || !plan || !warp::side_ok(width) || !warp::side_ok(height) || out_w > warp::kMaxSide || out_h > warp::kMaxSide)
+        return GMS_ERR_BAD_ARG;
+    rect::make_plan(rect::camera_of(*camera), R, t, width, height, out_w, out_h, *plan);
+    return GMS_OK;
+}
+
+int gms_rectify_plan_device(gms_ctx* c, const gms_camera* camera, const gms_two_view* d_tv, int n_pairs, int width, int height, int out_w,
+                            int out_h, gms_rectify_plan* d_plans)
+{
+    if (!c || !camera || n_pairs < 0 || n_pairs > 65535 || !warp::side_ok(width) || !warp::side_ok(height) || out_w > warp::kMaxSide ||
+        out_h > warp::kMaxSide)
+        return GMS_ERR_BAD_ARG;
+    if (n_pairs == 0) return GMS_OK;
+    if (!d_tv || !d_plans) return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] { return gms::launch_rectify_plan(*camera, d_tv, n_pairs, width, height, out_w, out_h, d_plans, c->stream); });
+}
+
+int gms_rectify_q(const gms_rectify_plan* plan, double* Q)
+{
+    if (!plan || !Q) return GMS_ERR_BAD_ARG;
+    rect::plan_q(*plan, Q);
+    return GMS_OK;
+}
+
+int gms_rectify_device(gms_ctx* c, const gms_camera* camera, const uint8_t* d_src, int n, int sw, int sh, int channels, int src_pitch,
+                       const gms_rectify_plan* d_plans, int n_plans, int which, uint8_t* d_dst, int dw, int dh, int dst_pitch,
+                       uint8_t* d_valid)
+{
+    if (!c || !camera || !d_plans || (reinterpret_cast<uintptr_t>(d_plans) & 7u) || (n_plans != 1 && n_plans != n) || (which != 1 && which != 2) ||
+        !rect::image_args_ok(n, sw, sh, channels, src_pitch, dw, dh, dst_pitch) || !warp_ranges_ok(d_src, n, sh, src_pitch, d_dst, dh, dst_pitch))
+        return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] {
+        return gms::launch_rectify(*camera, d_src, n, sw, sh, channels, src_pitch, d_plans, n_plans, which, d_dst, dw, dh, dst_pitch, d_valid,
+                                   c->stream);
+    });
+}
+
+int gms_rectify(const gms_camera* camera, const gms_rectify_plan* plan, int which, const uint8_t* src, int sw, int sh, int channels,
+                uint8_t* dst, uint8_t* valid)
+{
+    if (!camera || !plan || !src || !dst || (which != 1 && which != 2)) return GMS_ERR_BAD_ARG;
+    const int dw = plan->out_w, dh = plan->out_h;
+    if (!rect::image_args_ok(1, sw, sh, channels, (long long)channels * sw, dw, dh, (long long)channels * dw)) return GMS_ERR_BAD_ARG;
+    const size_t s_bytes = (size_t)sw * (size_t)sh * (size_t)channels, d_px = (size_t)dw * (size_t)dh;
+    gms::BlockLayout lay;
+    const size_t o_src = lay.add(s_bytes), o_plan = lay.add(sizeof(gms_rectify_plan)), o_dst = lay.add(d_px * channels), o_valid = lay.add(d_px);
+    DevBlock blk(lay, nullptr);
+    blk.in(o_src, src, s_bytes);
+    blk.in(o_plan, plan, sizeof(gms_rectify_plan));
+    blk.run([&](hipStream_t st) {
+        return gms::launch_rectify(*camera, blk.at<uint8_t>(o_src), 1, sw, sh, channels, sw * channels, blk.at<gms_rectify_plan>(o_plan), 1, which,
+                                   blk.at<uint8_t>(o_dst), dw, dh, dw * channels, valid ? blk.at<uint8_t>(o_valid) : nullptr, st);
+    });
+    blk.out(dst, o_dst, d_px * channels);
+    if (valid) blk.out(valid, o_valid, d_px);
+    return blk.finish();
+}
+
+int gms_undistort(const gms_camera* camera, const uint8_t* src, int width, int height, int channels, uint8_t* dst)
+{
+    if (!camera || !warp::side_ok(width) || !warp::side_ok(height)) return GMS_ERR_BAD_ARG;
+    gms_rectify_plan plan;
+    rect::identity_plan(rect::camera_of(*camera), width, height, plan);
+    return gms_rectify(camera, &plan, 1, src, width, height, channels, dst, nullptr);
+}
+
+size_t gms_dense_cloud_workspace_bytes(int width, int height, int n_pairs)
+{
+    if (n_pairs < 1 || n_pairs > 65535 || !warp::side_ok(width) || !warp::side_ok(height)) return 0;
+    return gms::dense_cloud_ws_bytes(n_pairs, width, height);
+}
+
+int gms_dense_cloud_device(gms_ctx* c, const int16_t* d_disp16, const uint8_t* d_valid, const uint8_t* d_image, int channels,
+                           int image_pitch, int n_pairs, int width, int height, const gms_rectify_plan* d_plans, int filtered16,
+                           int min_disp16, const gms_pair* d_pairs, const gms_sfm_pair_reg* d_reg, const gms_sfm_view* d_views, int n_frames,
+                           void* d_ws, size_t ws_bytes, int cap, float* d_xyz, uint8_t* d_color, int32_t* d_pixel, int32_t* d_count)
+{
+    if (!c || n_pairs < 0 || n_pairs > 65535 || !warp::side_ok(width) || !warp::side_ok(height) || min_disp16 < 1 || cap < 0) return GMS_ERR_BAD_ARG;
+    if (n_pairs == 0) return GMS_OK;
+    const bool any_reg = d_pairs || d_reg || d_views, all_reg = d_pairs && d_reg && d_views;
+    if (!d_disp16 || !d_valid || !d_plans || !d_ws || !d_count || (cap > 0 && (!d_xyz || !d_pixel)) || any_reg != all_reg ||
+        (all_reg && n_frames < 1))
+        return GMS_ERR_BAD_ARG;
+    if (d_image && ((channels != 1 && channels != 3) || (long long)image_pitch < (long long)channels * width)) return GMS_ERR_BAD_ARG;
+    if (d_color && !d_image) return GMS_ERR_BAD_ARG;
+    const size_t need = gms::dense_cloud_ws_bytes(n_pairs, width, height);
+    if ((reinterpret_cast<uintptr_t>(d_ws) & 255u) || (reinterpret_cast<uintptr_t>(d_plans) & 7u) || (reinterpret_cast<uintptr_t>(d_disp16) & 1u) ||
+        (reinterpret_cast<uintptr_t>(d_xyz) & 3u) ||
+        (reinterpret_cast<uintptr_t>(d_pixel) & 3u) || (reinterpret_cast<uintptr_t>(d_count) & 3u) || ws_bytes < need)
+        return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] {
+        return gms::launch_dense_cloud(d_disp16, d_valid, d_image, channels, image_pitch, n_pairs, width, height, d_plans, filtered16, min_disp16,
+                                       d_pairs, d_reg, d_views, n_frames, d_ws, cap, d_xyz, d_color, d_pixel, d_count, c->stream);
+    });
+}
+
+static const gms_stereo_sgm_params& dense_sgm_params(const gms_stereo_sgm_params* p)
+{
+    static const gms_stereo_sgm_params ref = GMS_STEREO_SGM_PARAMS_DENSE;
+    return p ? *p : ref;
+}
+
+static bool dense_shape_ok(int sw, int sh, int channels, int ow, int oh, int n_pairs, const gms_stereo_sgm_params& p)
+{
+    return n_pairs >= 1 && n_pairs <= 65535 && (channels == 1 || channels == 3) && warp::side_ok(sw) && warp::side_ok(sh) && warp::side_ok(ow) &&
+           warp::side_ok(oh) && sgm::params_ok(p, ow, oh);
+}
+
+size_t gms_dense_pairs_workspace_bytes(int sw, int sh, int channels, int ow, int oh, int n_pairs, const gms_stereo_sgm_params* params)
+{
+    const gms_stereo_sgm_params& p = dense_sgm_params(params);
+    if (!dense_shape_ok(sw, sh, channels, ow, oh, n_pairs, p)) return 0;
+    const size_t sgm_bytes = gms::stereo_sgm_ws_bytes(p, n_pairs, ow, oh);
+    return sgm_bytes ? gms::dense_pairs_layout(n_pairs, sw, sh, channels, ow, oh, sgm_bytes).total : 0;
+}
+
+// everything behind the plans, in stream order: grey, the three rectified images, the matcher, the cloud
+static hipError_t dense_pairs_launch(const gms_camera& cam, const gms_stereo_sgm_params& p, const uint8_t* d_img1, const uint8_t* d_img2, int n,
+                                     int sw, int sh, int channels, int ow, int oh, int min_disp16, const gms_pair* d_pairs,
+                                     const gms_sfm_pair_reg* d_reg, const gms_sfm_view* d_views, int n_frames, void* d_ws,
+                                     const gms_rectify_plan* d_plans, uint8_t* d_rect1, uint8_t* d_rect2, uint8_t* d_valid, uint8_t* d_color,
+                                     int16_t* d_disp16, int cap, float* d_xyz, uint8_t* d_cloud_color, int32_t* d_pixel, int32_t* d_count,
+                                     hipStream_t st)
+{
+    const gms::DensePairsLayout L = gms::dense_pairs_layout(n, sw, sh, channels, ow, oh, gms::stereo_sgm_ws_bytes(p, n, ow, oh));
+    const uint8_t *g1 = d_img1, *g2 = d_img2;
+    hipError_t e;
+    if (channels == 3) {
+        uint8_t* grey = gms::ws_ptr<uint8_t>(d_ws, L.grey);
+        const size_t plane = (size_t)n * (size_t)sw * (size_t)sh;
+        if ((e = gms::launch_bgr_to_gray(d_img1, n, sw, sh, grey, st)) != hipSuccess) return e;
+        if ((e = gms::launch_bgr_to_gray(d_img2, n, sw, sh, grey + plane, st)) != hipSuccess) return e;
+        g1 = grey;
+        g2 = grey + plane;
+        if ((e = gms::launch_rectify(cam, d_img1, n, sw, sh, 3, 3 * sw, d_plans, n, 1, d_color, ow, oh, 3 * ow, nullptr, st)) != hipSuccess) return e;
+    }
+    if ((e = gms::launch_rectify(cam, g1, n, sw, sh, 1, sw, d_plans, n, 1, d_rect1, ow, oh, ow, d_valid, st)) != hipSuccess) return e;
+    if ((e = gms::launch_rectify(cam, g2, n, sw, sh, 1, sw, d_plans, n, 2, d_rect2, ow, oh, ow, nullptr, st)) != hipSuccess) return e;
+    if ((e = gms::launch_stereo_sgm(p, d_rect1, d_rect2, n, ow, oh, ow, gms::ws_ptr<void>(d_ws, L.sgm), d_disp16, nullptr, st)) != hipSuccess) return e;
+    return gms::launch_dense_cloud(d_disp16, d_valid, channels == 3 ? d_color : d_rect1, channels, channels * ow, n, ow, oh, d_plans,
+                                   (p.bm.min_disparity - 1) * 16, min_disp16, d_pairs, d_reg, d_views, n_frames, gms::ws_ptr<void>(d_ws, L.cloud), cap,
+                                   d_xyz, d_cloud_color, d_pixel, d_count, st);
+}
+
+int gms_dense_pairs_device(gms_ctx* c, const gms_camera* camera, const gms_stereo_sgm_params* params, const uint8_t* d_img1, const uint8_t* d_img2,
+                           int n_pairs, int sw, int sh, int channels, const gms_two_view* d_tv, int ow, int oh, int min_disp16,
+                           const gms_pair* d_pairs, const gms_sfm_pair_reg* d_reg, const gms_sfm_view* d_views, int n_frames, void* d_ws,
+                           size_t ws_bytes, gms_rectify_plan* d_plans, uint8_t* d_rect1, uint8_t* d_rect2, uint8_t* d_valid, uint8_t* d_color,
+                           int16_t* d_disp16, int cap, float* d_xyz, uint8_t* d_cloud_color, int32_t* d_pixel, int32_t* d_count)
+{
+    const gms_stereo_sgm_params& p = dense_sgm_params(params);
+    if (!c || !camera || !dense_shape_ok(sw, sh, channels, ow, oh, n_pairs, p) || min_disp16 < 1 || cap < 0) return GMS_ERR_BAD_ARG;
+    const bool any_reg = d_pairs || d_reg || d_views, all_reg = d_pairs && d_reg && d_views;
+    if (!d_img1 || !d_img2 || !d_tv || !d_ws || !d_plans || !d_rect1 || !d_rect2 || !d_valid || (channels == 3 && !d_color) || !d_disp16 ||
+        !d_count || (cap > 0 && (!d_xyz || !d_pixel)) || any_reg != all_reg || (all_reg && n_frames < 1))
+        return GMS_ERR_BAD_ARG;
+    const size_t need = gms_dense_pairs_workspace_bytes(sw, sh, channels, ow, oh, n_pairs, &p);
+    if ((reinterpret_cast<uintptr_t>(d_ws) & 255u) || (reinterpret_cast<uintptr_t>(d_plans) & 7u) || (reinterpret_cast<uintptr_t>(d_disp16) & 1u) ||
+        (reinterpret_cast<uintptr_t>(d_xyz) & 3u) || (reinterpret_cast<uintptr_t>(d_pixel) & 3u) || (reinterpret_cast<uintptr_t>(d_count) & 3u) ||
+        need == 0 || ws_bytes < need)
+        return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] {
+        const hipError_t e = gms::launch_rectify_plan(*camera, d_tv, n_pairs, sw, sh, ow, oh, d_plans, c->stream);
+        if (e != hipSuccess) return e;
+        return dense_pairs_launch(*camera, p, d_img1, d_img2, n_pairs, sw, sh, channels, ow, oh, min_disp16, d_pairs, d_reg, d_views, n_frames, d_ws,
+                                  d_plans, d_rect1, d_rect2, d_valid, d_color, d_disp16, cap, d_xyz, d_cloud_color, d_pixel, d_count, c->stream);
+    });
+}
+
+int gms_dense_pair(const gms_camera* camera, const gms_stereo_sgm_params* params, const uint8_t* img1, const uint8_t* img2, int width, int height,
+                   int channels, const double* R, const double* t, int out_w, int out_h, int min_disp16, gms_rectify_plan* plan, uint8_t* rect1,
+                   uint8_t* rect2, uint8_t* valid, uint8_t* color, int16_t* disp16, int cap, float* xyz, uint8_t* cloud_color, int32_t* pixel,
+                   int32_t* count)
+{
+    const gms_stereo_sgm_params& p = dense_sgm_params(params);
+    if (!camera || !img1 || !img2 || !R || !t || !plan || !count || min_disp16 < 1 || cap < 0 || (cap > 0 && (!xyz || !pixel))) return GMS_ERR_BAD_ARG;
+    const int rc = gms_rectify_plan_host(camera, R, t, width, height, out_w, out_h, plan);
+    if (rc != GMS_OK) return rc;
+    if (plan->status != GMS_OK) return GMS_ERR_NO_MODEL;
+    const int ow = plan->out_w, oh = plan->out_h;
+    const size_t ws = gms_dense_pairs_workspace_bytes(width, height, channels, ow, oh, 1, &p);
+    if (ws == 0) return GMS_ERR_BAD_ARG;
+    const size_t s_bytes = (size_t)width * (size_t)height * (size_t)channels, px = (size_t)ow * (size_t)oh, ucap = (size_t)cap;
+    gms::BlockLayout lay;
+    const size_t o_1 = lay.add(s_bytes), o_2 = lay.add(s_bytes), o_plan = lay.add(sizeof(gms_rectify_plan)), o_ws = lay.add(ws), o_r1 = lay.add(px),
+                 o_r2 = lay.add(px), o_v = lay.add(px), o_c = lay.add(3 * px), o_d = lay.add(2 * px), o_xyz = lay.add(12 * ucap + 4),
+                 o_cc = lay.add(3 * ucap + 4), o_pix = lay.add(4 * ucap + 4), o_n = lay.add(4);
+    DevBlock blk(lay, nullptr);
+    blk.in(o_1, img1, s_bytes);
+    blk.in(o_2, img2, s_bytes);
+    blk.in(o_plan, plan, sizeof(gms_rectify_plan));
+    blk.run([&](hipStream_t st) {
+        return dense_pairs_launch(*camera, p, blk.at<uint8_t>(o_1), blk.at<uint8_t>(o_2), 1, width, height, channels, ow, oh, min_disp16, nullptr, nullptr,
+                                  nullptr, 0, blk.at(o_ws), blk.at<gms_rectify_plan>(o_plan), blk.at<uint8_t>(o_r1), blk.at<uint8_t>(o_r2),
+                                  blk.at<uint8_t>(o_v), blk.at<uint8_t>(o_c), blk.at<int16_t>(o_d), cap, blk.at<float>(o_xyz),
+                                  cloud_color ? blk.at<uint8_t>(o_cc) : nullptr, blk.at<int32_t>(o_pix), blk.at<int32_t>(o_n), st);
+    });
+    int32_t n = 0;
+    blk.out_now(&n, o_n, 4);
+    *count = n;
+    const size_t k = (size_t)(n < cap ? n : cap);
+    if (rect1) blk.out(rect1, o_r1, px);
+    if (rect2) blk.out(rect2, o_r2, px);
+    if (valid) blk.out(valid, o_v, px);
+    if (color && channels == 3) blk.out(color, o_c, 3 * px);
+    if (disp16) blk.out(disp16, o_d, 2 * px);
+    if (k && blk.ok()) {
+        blk.out(xyz, o_xyz, 12 * k);
+        blk.out(pixel, o_pix, 4 * k);
+        if (cloud_color) blk.out(cloud_color, o_cc, (size_t)channels * k);
+    }
+    return blk.finish();
 }
 
 // ---- camera calibration from chessboard photographs (calib_kernels.hip, calib_core.h) -----------------------------

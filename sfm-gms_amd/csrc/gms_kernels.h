@@ -229,6 +229,17 @@ hipError_t launch_resize(const uint8_t* d_src, int n, int sw, int sh, int channe
                          int dst_pitch, hipStream_t stream);
 hipError_t launch_warp_affine(const uint8_t* d_src, int n, int sw, int sh, int channels, int src_pitch, const double* d_M, int n_matrices,
                               uint8_t* d_dst, int dw, int dh, int dst_pitch, hipStream_t stream);
+// a dense cloud from a posed pair (rectify_kernels.hip; arithmetic in rectify_core.h; workspace: ws_layout.h DenseCloudLayout)
+hipError_t launch_rectify_plan(const gms_camera& camera, const gms_two_view* d_tv, int n_pairs, int W, int H, int out_w, int out_h,
+                               gms_rectify_plan* d_plans, hipStream_t stream);
+hipError_t launch_rectify(const gms_camera& camera, const uint8_t* d_src, int n, int sw, int sh, int channels, int src_pitch,
+                          const gms_rectify_plan* d_plans, int n_plans, int which, uint8_t* d_dst, int dw, int dh, int dst_pitch,
+                          uint8_t* d_valid, hipStream_t stream);
+size_t     dense_cloud_ws_bytes(int n_pairs, int W, int H);
+hipError_t launch_dense_cloud(const int16_t* d_disp16, const uint8_t* d_valid, const uint8_t* d_image, int channels, int image_pitch,
+                              int n_pairs, int W, int H, const gms_rectify_plan* d_plans, int filtered16, int min_disp16,
+                              const gms_pair* d_pairs, const gms_sfm_pair_reg* d_reg, const gms_sfm_view* d_views, int n_frames, void* d_ws,
+                              int cap, float* d_xyz, uint8_t* d_color, int32_t* d_pixel, int32_t* d_count, hipStream_t stream);
 // chessboard corner candidates and cornerSubPix (calib_kernels.hip; arithmetic in calib_core.h; workspace: ws_layout.h ChessLayout)
 size_t     chess_candidates_ws_bytes(int n, int w, int h);
 hipError_t launch_chess_candidates(const uint8_t* d_images, int n, int w, int h, int max_candidates, void* d_ws,

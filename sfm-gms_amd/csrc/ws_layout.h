@@ -384,4 +384,34 @@ inline SfmBaLayout sfm_ba_layout(int n_frames, int64_t total_kp, int64_t cloud_c
             c.take(64, 256), c.end};
 }
 
+// ---- the points of disparity maps (rectify_kernels.hip) -----------------------------------------------------------------------------
+// Every call writes every word it later reads.
+constexpr int kDenseScanBlock = 1024;  // pixels per workgroup of the ordered compaction
+inline int dense_cloud_blocks(int W, int H) { return (int)(((size_t)W * (size_t)H + kDenseScanBlock - 1) / kDenseScanBlock); }
+struct DenseCloudLayout {
+    size_t blocks;  // int32 [n][dense_cloud_blocks]: points per block, then in place their exclusive prefix within the pair
+    size_t total;
+};
+inline DenseCloudLayout dense_cloud_layout(int n, int W, int H)
+{
+    WsCursor c;
+    return {c.take(4 * (size_t)n * (size_t)dense_cloud_blocks(W, H), 256), c.end};
+}
+
+
+// ---- the dense stage of a batch of posed pairs (gms_dense_pairs_device) -----------------------------------------------------------------
+// sgm_bytes: gms_stereo_sgm_workspace_bytes for the rectified size. Every call writes every word it later reads.
+struct DensePairsLayout {
+    size_t grey;   // uint8 [2][n][sh][sw]: the grey images of both cameras, for BGR input only
+    size_t sgm;    // the matcher's workspace
+    size_t cloud;  // DenseCloudLayout
+    size_t total;
+};
+inline DensePairsLayout dense_pairs_layout(int n, int sw, int sh, int channels, int ow, int oh, size_t sgm_bytes)
+{
+    WsCursor c;
+    return {c.take(channels == 3 ? 2 * (size_t)n * (size_t)sw * (size_t)sh : 0, 256), c.take(sgm_bytes, 256),
+            c.take(dense_cloud_layout(n, ow, oh).total, 256), c.end};
+}
+
 }  // namespace gms

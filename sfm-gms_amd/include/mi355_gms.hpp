@@ -607,6 +607,68 @@ inline void img_rotate(const std::vector<uint8_t>& src, int width, int height, i
     if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::img_rotate: ") + gms_error_string(rc));
 }
 
+// ---- a dense cloud from a posed pair ----------------------------------------------------------------------------------
+// stereoRectify: the plan of X2 = R X1 + t (R 9 doubles row-major, t 3), host arithmetic; out_width / out_height <= 0: the default
+// size. undistort: cv::undistort with the new camera equal to the camera. denseStereo: the plan, both images rectified, semi-global
+// matching (params NULL: GMS_STEREO_SGM_PARAMS_DENSE) and every matched pixel reprojected into camera 1's frame in the unit of t.
+// Images are flat row-major 8-bit, 1 or 3 interleaved channels; each call runs synchronously on the current HIP device.
+inline gms_rectify_plan stereoRectify(const gms_camera& camera, const std::array<double, 9>& R, const std::array<double, 3>& t, int width,
+                                      int height, int out_width = 0, int out_height = 0)
+{
+    gms_rectify_plan plan;
+    const int rc = gms_rectify_plan_host(&camera, R.data(), t.data(), width, height, out_width, out_height, &plan);
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::stereoRectify: ") + gms_error_string(rc));
+    return plan;
+}
+
+inline void undistort(const std::vector<uint8_t>& src, int width, int height, int channels, const gms_camera& camera, std::vector<uint8_t>& dst)
+{
+    warp_check_image("mi355::undistort", src, width, height, channels);
+    dst.assign(src.size(), 0);
+    const int rc = gms_undistort(&camera, src.data(), width, height, channels, dst.data());
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::undistort: ") + gms_error_string(rc));
+}
+
+struct DenseCloud {
+    gms_rectify_plan plan{};
+    std::vector<float> points;      // [k][3]
+    std::vector<uint8_t> colors;    // [k][channels]
+    std::vector<int32_t> pixel;     // [k]: v * plan.out_w + u, raster order
+    std::vector<int16_t> disp16;    // [plan.out_h][plan.out_w], 4 fractional bits
+    std::vector<uint8_t> rect1, rect2, valid;   // grey, [plan.out_h][plan.out_w]
+    int32_t count = 0;              // all the points, also beyond cap
+};
+
+// Throws std::runtime_error with "not rectifiable" when the plan's status is GMS_ERR_NO_MODEL. cap < 0: every pixel.
+inline DenseCloud denseStereo(const std::vector<uint8_t>& img1, const std::vector<uint8_t>& img2, int width, int height, int channels,
+                              const gms_camera& camera, const std::array<double, 9>& R, const std::array<double, 3>& t, int min_disp16 = 16,
+                              int cap = -1, const gms_stereo_sgm_params* params = nullptr)
+{
+    warp_check_image("mi355::denseStereo", img1, width, height, channels);
+    warp_check_image("mi355::denseStereo", img2, width, height, channels);
+    DenseCloud out;
+    out.plan = stereoRectify(camera, R, t, width, height);
+    if (out.plan.status != GMS_OK) throw std::runtime_error("mi355::denseStereo: the pair is not rectifiable");
+    const size_t px = (size_t)out.plan.out_w * (size_t)out.plan.out_h;
+    const int k = cap < 0 ? (int)px : cap;
+    out.points.assign(3 * (size_t)k, 0.f);
+    out.colors.assign((size_t)channels * (size_t)k, 0);
+    out.pixel.assign((size_t)k, 0);
+    out.disp16.assign(px, 0);
+    out.rect1.assign(px, 0);
+    out.rect2.assign(px, 0);
+    out.valid.assign(px, 0);
+    const int rc = gms_dense_pair(&camera, params, img1.data(), img2.data(), width, height, channels, R.data(), t.data(), out.plan.out_w,
+                                  out.plan.out_h, min_disp16, &out.plan, out.rect1.data(), out.rect2.data(), out.valid.data(), nullptr,
+                                  out.disp16.data(), k, out.points.data(), out.colors.data(), out.pixel.data(), &out.count);
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::denseStereo: ") + gms_error_string(rc));
+    const size_t n = (size_t)(out.count < k ? out.count : k);
+    out.points.resize(3 * n);
+    out.colors.resize((size_t)channels * n);
+    out.pixel.resize(n);
+    return out;
+}
+
 // ---- camera calibration from chessboard photographs (main.cpp:53-68, CalibrationUtil.cpp:3-53) --------------------------
 // The library's own corner finder (NOT OpenCV's quad-based one), OpenCV 4.5.2's cornerSubPix in fp64, and calibrateCamera with
 // flags = 0, on flat 8-bit grey images (dense rows). Points are doubles, so that nothing is rounded between the steps.

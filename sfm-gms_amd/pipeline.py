@@ -24,10 +24,10 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from .batch import (BfSelect, DescriptorTable, DetectPyramid, FrameTable, LogosDictionary, LogosFilter, LogosTable, SfmBundle, SfmRegister, Warp, _device, _to_dev,
+from .batch import (BfSelect, DescriptorTable, DetectPyramid, FrameTable, LogosDictionary, LogosFilter, LogosTable, DensePairs, SfmBundle, SfmRegister, Warp, _device, _to_dev,
                     bf_select_table, bgr_to_gray, frame_counts, frame_pairs_of, logos_dictionary, pair_table, tables_from_detector)
 from .api import getRotationMatrix2D, logos_dict_args
-from .types import (DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128, GMS_ERR_CAPACITY, PAIR_DTYPE, RESULT_DTYPE, TWO_VIEW_DTYPE,
+from .types import (DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128, GMS_ERR_CAPACITY, GMS_OK, PAIR_DTYPE, RESULT_DTYPE, TWO_VIEW_DTYPE,
                     desc_layout, make_camera, sfm_ba_params)
 
 METHODS = ("gms", "bf", "logos")
@@ -229,7 +229,8 @@ def _train_dictionary_device(ctx, descs, opts):
 def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, threshold=20, max_keypoints=10000, n_levels=8,
                descriptor="grad", withRotation=False, withScale=False, thresholdFactor=6.0, prob=0.7, ransac_threshold=1.0, max_iters=1000,
                device=None, dictionary=None, logos_capacity=None, cross_check=True, distance_coef=4.0, max_size=500, train_dictionary=None,
-               keep_tables=False, detector="fast", contrast=128, refine=False, register=False, root=0, min_links=8, bundle=False, **ba):
+               keep_tables=False, detector="fast", contrast=128, refine=False, register=False, root=0, min_links=8, bundle=False, dense=False,
+               min_disp16=16, dense_cap=None, dense_sgm=None, **ba):
     """run_dataset from pixels. images: [n, H, W] grey or [n, H, W, 3] BGR, 8-bit, a host array or a device tensor (or a list of equally
     sized images). BGR goes through gms_bgr_to_gray_device; the pyramid keypoint source (threshold, max_keypoints, n_levels; detector
     "fast", or "dog" with `contrast` in the place of `threshold`: gms_detect_dog_batch_device, with refine=True
@@ -238,9 +239,17 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
     n + 1 frame offsets (and the status records the stages already read) come back. pairs: (frame_a, frame_b) rows or PAIR_DTYPE
     records; default every a < b. The other arguments and the returned records are run_dataset's (the matcher always runs: there are
     no matches to bring); keep_tables=True adds `tables` = (FrameTable, DescriptorTable), the resident keypoints and rows.
-    register, root, min_links, bundle and the bundle adjustment's keywords: run_dataset's."""
+    register, root, min_links, bundle and the bundle adjustment's keywords: run_dataset's.
+    dense=True (needs a camera): adds `dense`, one entry per pair -- None for a pair without a pose or one that is not
+    rectifiable, else a dict of points float32 [k, 3], colors uint8 [k] or [k, 3], pixel int32 [k], count and plan
+    (gms_dense_pairs_device on the photographs themselves; min_disp16, dense_cap = the most points per pair, dense_sgm = the
+    matcher's keywords). The points are in frame_a's frame and the pair's unit, as points3d; with register=True in the world frame,
+    as points_world, and a pair the registration does not use has none. The clouds of different pairs are not fused or
+    de-duplicated. dense=False returns the dict without."""
     if method not in METHODS:
         raise ValueError(f"unknown method {method!r}")
+    if dense and camera is None:
+        raise ValueError("dense=True needs a camera: it rectifies by the recovered poses")
     if descriptor not in ("brief", "grad", "both"):
         raise ValueError('descriptor: "brief", "grad" or "both"')
     images, is_bgr = image_stack(images)
@@ -255,6 +264,7 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
     dev = _device(ctx, device)
     d_images = (images if torch.is_tensor(images) else torch.from_numpy(np.ascontiguousarray(images))).to(dev).contiguous()
     source = DetectPyramid(ctx, n, w, h, threshold, max_keypoints, n_levels, dev, descriptor, detector, contrast, refine)   # (refuses a bad size before any launch)
+    d_photos = d_images
     if is_bgr:
         d_images = bgr_to_gray(ctx, d_images)
     torch.cuda.synchronize(dev)
@@ -275,9 +285,47 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
             r.update(dictionary=dic_host, dictionary_result=trained)
     else:
         r = _run_gms(ctx, frames, descs, src, None, withRotation, withScale, thresholdFactor, *tail)
+    if dense:
+        r.update(dense=_dense_pairs(ctx, d_photos, r, camera, dist, min_disp16, dense_cap, dense_sgm, reg is not None))
     if keep_tables:
         r.update(tables=(frames, descs))
     return r
+
+
+def _dense_pairs(ctx, d_photos, r, camera, dist, min_disp16, cap, sgm, registered):
+    """run_images' dense=True: gms_dense_pairs_device for the pairs with a pose, one run per output size (the source's size, and its
+    transpose for the pairs whose baseline is nearer the vertical), on the two-view records and the registration that `r` holds."""
+    from .api import stereoRectify
+    n, h, w = d_photos.shape[:3]
+    channels = 3 if d_photos.dim() == 4 else 1
+    pairs, tv = r["pairs"], r["two_view"]
+    out = [None] * len(pairs)
+    groups = {}
+    for i in range(len(pairs)):
+        if int(tv["status"][i]) != GMS_OK:
+            continue
+        plan = stereoRectify(camera, dist, tv["R"][i], tv["t"][i], (w, h))
+        if plan.ok:
+            groups.setdefault(plan.out_size, []).append(i)
+    for size, idx in groups.items():
+        run = DensePairs(ctx, len(idx), (w, h), size, camera, dist, channels, cap=cap, min_disp16=min_disp16, params=sgm, device=d_photos.device)
+        run.set_two_view(tv[idx])
+        if registered:
+            sub = pairs[idx].copy()
+            run.set_registration(_to_dev(sub, d_photos.device), _to_dev(r["registration"][idx], d_photos.device),
+                                 _to_dev(r["views"], d_photos.device), len(r["views"]))
+        a = d_photos[torch.as_tensor(pairs["frame_a"][idx].astype(np.int64), device=d_photos.device)].contiguous()
+        b = d_photos[torch.as_tensor(pairs["frame_b"][idx].astype(np.int64), device=d_photos.device)].contiguous()
+        torch.cuda.synchronize(d_photos.device)
+        run.run(a, b)
+        ctx.synchronize()
+        counts, plans = run.d_count.cpu().numpy(), run.plans()
+        for j, i in enumerate(idx):
+            k = min(int(counts[j]), run.cap)
+            colors = run.d_cloud_color[j, :k].cpu().numpy()
+            out[i] = dict(points=run.d_xyz[j, :k].cpu().numpy(), colors=colors if channels == 3 else colors[:, 0],
+                          pixel=run.d_pixel[j, :k].cpu().numpy(), count=int(counts[j]), plan=plans[j:j + 1])
+    return out
 
 
 MAIN_SCENARIOS = ("normal", "rotated", "resized")   # frame 0 = the left image; frames 1, 2, 3 = the right image of each scenario

@@ -167,6 +167,47 @@ def sfm_ba_params(**kw):
     return rec
 
 
+# gms_rectify_plan (include/gms.h): the rectifying rotations and the new camera of a posed pair
+RECTIFY_PLAN_DTYPE = np.dtype([("R1", "<f8", (3, 3)), ("R2", "<f8", (3, 3)), ("fx", "<f8"), ("fy", "<f8"), ("cx", "<f8"), ("cy", "<f8"), ("B", "<f8"),
+                               ("out_w", "<i4"), ("out_h", "<i4"), ("turn", "<i4"), ("status", "<i4")])
+assert RECTIFY_PLAN_DTYPE.itemsize == 200
+
+
+def rectify_plan_records(plans):
+    """RECTIFY_PLAN_DTYPE records [n] from a RectifyPlan, an array of 200-byte plan records of any field layout (their bytes are
+    taken as they are: numpy's cast between record types would go field by field), or a list of those."""
+    if isinstance(plans, (list, tuple)):
+        return np.concatenate([rectify_plan_records(p) for p in plans])
+    a = np.ascontiguousarray(plans.record if isinstance(plans, RectifyPlan) else plans)
+    if a.dtype.itemsize != RECTIFY_PLAN_DTYPE.itemsize:
+        raise ValueError("plans: gms_rectify_plan records (200 bytes each)")
+    return a.reshape(-1).view(np.uint8).view(RECTIFY_PLAN_DTYPE).copy()
+
+
+class RectifyPlan:
+    """A gms_rectify_plan record (`record`, one RECTIFY_PLAN_DTYPE entry; plan["R1"] etc. read it) with the source camera it was
+    made for (`camera`, a CAMERA_DTYPE record), so that rectify(image, plan, which) needs nothing else."""
+
+    def __init__(self, record, camera):
+        self.record = rectify_plan_records(record).reshape(1)
+        self.camera = np.ascontiguousarray(camera, dtype=CAMERA_DTYPE).reshape(1)
+
+    def __getitem__(self, key):
+        return self.record[key][0]
+
+    @property
+    def ok(self):
+        return int(self.record["status"][0]) == GMS_OK
+
+    @property
+    def out_size(self):
+        return int(self.record["out_w"][0]), int(self.record["out_h"][0])
+
+
+# GMS_STEREO_SGM_PARAMS_DENSE: the matcher's record of the dense stage (the shared principal point makes true disparities positive)
+STEREO_SGM_DENSE = dict(min_disparity=0, num_disparities=128)
+
+
 def make_camera(camera, dist=None):
     """(fx, fy, cx, cy) and (k1, k2, p1, p2, k3) or None -> a CAMERA_DTYPE record (cameraMatrix / distCoeffs of SfMUtil.cpp:4)."""
     c = np.zeros(1, dtype=CAMERA_DTYPE)
