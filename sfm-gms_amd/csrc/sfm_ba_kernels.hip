@@ -156,8 +156,9 @@ sba_mark_kernel(SbaIn in, SbaWs ws)
     const gms_pair pr = in.pairs[i];
     // (uniform over the workgroup) a pair whose frames, offsets or match range do not fit the arrays has no observations
     if (in.reg[i].status != GMS_OK) return;
+    // (match_off against total_m - m: their sum need not fit 64 bits)
     if (pr.frame_a < 0 || pr.frame_a >= in.n_frames || pr.frame_b < 0 || pr.frame_b >= in.n_frames || pr.m < 0 || pr.match_off < 0 ||
-        pr.match_off + (int64_t)pr.m > in.total_m)
+        pr.match_off > in.total_m - (int64_t)pr.m)
         return;
     if (!in.views[pr.frame_a].registered || !in.views[pr.frame_b].registered) return;
     const int64_t oa = in.frame_off[pr.frame_a], ob = in.frame_off[pr.frame_b];

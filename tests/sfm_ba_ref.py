@@ -3,8 +3,8 @@ sfm_ba_kernels.hip compute on the device and tests/cpp/sfm_ba_host.cpp on the ho
 
 Inputs are what gms_two_view_batch_device and gms_sfm_register_device leave: the keypoints' pixel positions `xy` ([K, 2] float32, all
 frames back to back), frame_off, pairs, the survivors `matches`, `mask`, and the registration's views, registration records, track
-(per match slot), cloud and cloud_id (already cut to min(n_tracks, cloud_cap) entries), and the camera (fx, fy, cx, cy, k1, k2, p1, p2,
-k3). Every sum over observations runs in ascending global keypoint index (np.add.at and np.cumsum are sequential); order=-1 runs every
+(per match slot), cloud and cloud_id (cloud_cap entries, of which the first min(n_tracks, cloud_cap) count; n_tracks is the
+registration summary's and defaults to all of them), and the camera (fx, fy, cx, cy, k1, k2, p1, p2, k3). Every sum over observations runs in ascending global keypoint index (np.add.at and np.cumsum are sequential); order=-1 runs every
 one of them in descending index instead, which is how the tests measure what the order of a sum is worth."""
 import numpy as np
 
@@ -47,17 +47,28 @@ def rodrigues(w):
     return np.eye(3) + A * K + B * (K @ K)
 
 
-def observations(frame_off, pairs, matches, mask, views, reg, track, cloud_id):
-    """kp_track int32 [K]: the cloud entry a keypoint is an observation of, -1 otherwise."""
+def observations(frame_off, pairs, matches, mask, views, reg, track, cloud_id, n_tracks=None, total_m=None):
+    """kp_track int32 [K]: the cloud entry a keypoint is an observation of, -1 otherwise. Only the first min(n_tracks, len(cloud_id))
+    entries of cloud_id are searched (n_tracks: the registration summary's; what lies behind them need not be sorted). A pair whose
+    frames, frame offsets or match range (inside the total_m slots of matches, mask and track; len(mask) by default) do not fit the
+    arrays has no observations."""
     frame_off = np.asarray(frame_off, dtype=np.int64)
+    n_frames, total_kp = len(frame_off) - 1, int(frame_off[-1])
     counts = np.diff(frame_off)
-    kp_track = np.full(int(frame_off[-1]), -1, np.int32)
-    ids = np.asarray(cloud_id, dtype=np.int64)
+    kp_track = np.full(total_kp, -1, np.int32)
+    n_c = len(cloud_id) if n_tracks is None else max(0, min(int(n_tracks), len(cloud_id)))
+    ids = np.asarray(cloud_id, dtype=np.int64)[:n_c]
+    total_m = len(mask) if total_m is None else int(total_m)
     for i, p in enumerate(pairs):
-        a, b = int(p["frame_a"]), int(p["frame_b"])
-        if reg[i]["status"] != GMS_OK or not views[a]["registered"] or not views[b]["registered"]:
+        a, b, off, m = int(p["frame_a"]), int(p["frame_b"]), int(p["match_off"]), int(p["m"])
+        if reg[i]["status"] != GMS_OK:
             continue
-        off, m = int(p["match_off"]), int(p["m"])
+        if not (0 <= a < n_frames and 0 <= b < n_frames) or m < 0 or off < 0 or off + m > total_m:
+            continue
+        if not views[a]["registered"] or not views[b]["registered"]:
+            continue
+        if min(frame_off[a], frame_off[b], counts[a], counts[b]) < 0 or max(frame_off[a + 1], frame_off[b + 1]) > total_kp:
+            continue
         mk = mask[off:off + m] != 0
         rank = np.cumsum(mk) - mk
         q, t = matches["queryIdx"][off:off + m].astype(np.int64), matches["trainIdx"][off:off + m].astype(np.int64)
@@ -171,8 +182,13 @@ def huber(r, h):
         return np.where(far, h / np.where(far, n, 1.0), 1.0), np.where(far, 2.0 * h * n - h * h, n2)
 
 
-def bundle_adjust(xy, frame_off, pairs, matches, mask, views, reg, track, cloud, cloud_id, camera, order=1, trace=None, **params):
-    """-> dict(views_ba, cloud_ba, track_status int32 per cloud entry, ba_summary BA_SUMMARY_DTYPE [1], kp_track, lists)."""
+def bundle_adjust(xy, frame_off, pairs, matches, mask, views, reg, track, cloud, cloud_id, camera, order=1, trace=None, n_tracks=None,
+                  total_m=None, **params):
+    """-> dict(views_ba, cloud_ba, track_status int32 per cloud entry, ba_summary BA_SUMMARY_DTYPE [1], kp_track, lists, factors = per
+    outer iteration the free frames that had a Cholesky factor, kept_why = per KEPT entry what refused its re-triangulation).
+    n_tracks, total_m: as observations() takes them; the entries of cloud_id past min(n_tracks, len(cloud_id)) are neither searched
+    nor visited: status FEW, their rows of cloud unchanged. trace, when a list, gets per outer iteration (accepted, the cost before,
+    the candidate's cost, lambda, conjugate-gradient iterations, what ended them: "rz0", "n_cg", "pq" or "cg_tol")."""
     P = dict(PARAMS, **params)
     n_iters, n_cg, lam, cg_tol, ftol, h = int(P["n_iters"]), int(P["n_cg"]), float(P["lambda0"]), float(P["cg_tol"]), float(P["ftol"]), float(P["huber_px"])
     frame_off = np.asarray(frame_off, dtype=np.int64)
@@ -182,7 +198,7 @@ def bundle_adjust(xy, frame_off, pairs, matches, mask, views, reg, track, cloud,
     f = 0.5 * (cam[0] + cam[1])
     views_out = np.array(views, copy=True)
     X = np.array(cloud, dtype=np.float64, copy=True).reshape(-1, 3)[:n_c]
-    kp_track = observations(frame_off, pairs, matches, mask, views, reg, track, cloud_id)
+    kp_track = observations(frame_off, pairs, matches, mask, views, reg, track, cloud_id, n_tracks, total_m)
     g_all = np.nonzero(kp_track >= 0)[0]
     fr_all = np.searchsorted(frame_off, g_all, side="right") - 1
     c_all = kp_track[g_all]
@@ -202,6 +218,7 @@ def bundle_adjust(xy, frame_off, pairs, matches, mask, views, reg, track, cloud,
     R, t = views_out["R"].copy(), views_out["t"].copy()
     free = (views_out["registered"] != 0) & (views_out["pair"] >= 0)
     fidx = np.nonzero(free)[0]
+    kept_why = {}
     # re-triangulation over all views
     if P["retriangulate"] and len(g):
         Rt = np.transpose(R[fr], (0, 2, 1))
@@ -216,10 +233,12 @@ def bundle_adjust(xy, frame_off, pairs, matches, mask, views, reg, track, cloud,
         Pc, act, _ = project(R[fr], t[fr], Xn[tc], uv, f)
         bad = np.zeros(n_c, bool)
         np.logical_or.at(bad, tc, ~act)
-        bad |= ~np.isfinite(Xn).all(1) | ~Ai.any((1, 2))
+        singular = ~Ai.any((1, 2))
+        bad |= ~np.isfinite(Xn).all(1) | singular
         for c in np.nonzero(status == REFINED)[0]:
             if bad[c]:
                 status[c] = KEPT
+                kept_why[int(c)] = "singular" if singular[c] else "behind" if np.isfinite(Xn[c]).all() else "not finite"
             else:
                 X[c] = Xn[c]
 
@@ -235,6 +254,7 @@ def bundle_adjust(xy, frame_off, pairs, matches, mask, views, reg, track, cloud,
     cost, sq, n_act = cost_of(R, t, X)
     cost0, sq0, n_act0 = cost, sq, n_act
     iters_run = iters_acc = cg_total = 0
+    factors = []
     done = not (len(g) and len(fidx))
     for it in range(n_iters):
         if done:
@@ -259,6 +279,7 @@ def bundle_adjust(xy, frame_off, pairs, matches, mask, views, reg, track, cloud,
         E = _segsum(n_frames, fr, np.einsum("nik,njk->nij", WV, Wo))
         U[:, range(6), range(6)] *= 1.0 + lam
         Ls = {int(k): chol6(U[k] - E[k]) for k in fidx}
+        factors.append(np.array([k for k in fidx if Ls[int(k)] is not None], dtype=np.int64))
 
         def precond(v):
             out = np.zeros_like(v)
@@ -285,6 +306,7 @@ def bundle_adjust(xy, frame_off, pairs, matches, mask, views, reg, track, cloud,
         p = z.copy()
         rz = rz0 = dot(rr, z)
         cg_done = not (np.isfinite(rz0) and rz0 > 0)
+        cg_before, cg_end = cg_total, "rz0" if cg_done else "n_cg"   # how the solve ends: r0.z0 <= 0, n_cg used up, p.Sp, cg_tol
         for _ in range(n_cg):
             if cg_done:
                 break
@@ -292,12 +314,14 @@ def bundle_adjust(xy, frame_off, pairs, matches, mask, views, reg, track, cloud,
             pq = dot(p, q)
             cg_total += 1
             if not (np.isfinite(pq) and pq > 0):
+                cg_end = "pq"
                 break
             alpha = rz / pq
             x, rr = x + alpha * p, rr - alpha * q
             z = precond(rr)
             rz_new = dot(rr, z)
             if not np.isfinite(rz_new) or rz_new <= cg_tol * cg_tol * rz0:
+                cg_end = "cg_tol"
                 break
             p = z + (rz_new / rz) * p
             rz = rz_new
@@ -312,7 +336,7 @@ def bundle_adjust(xy, frame_off, pairs, matches, mask, views, reg, track, cloud,
         c_new, sq_new, act_new = cost_of(Rc, tcand, Xc)
         accept = bool(np.isfinite(c_new) and c_new < cost and act_new >= n_act)
         if trace is not None:
-            trace.append((accept, cost, c_new, lam))
+            trace.append((accept, cost, c_new, lam, cg_total - cg_before, cg_end))
         if accept:
             iters_acc += 1
             done = cost - c_new <= ftol * cost
@@ -340,4 +364,4 @@ def bundle_adjust(xy, frame_off, pairs, matches, mask, views, reg, track, cloud,
     s["n_obs"], s["n_active"], s["n_tracks_used"], s["n_tracks_multi"] = len(g), n_act, int(ref.sum()), int((status == MULTI).sum())
     s["n_frames_free"], s["iters_run"], s["iters_accepted"], s["cg_iters"] = len(fidx), iters_run, iters_acc, cg_total
     s["status"] = GMS_OK if n_act else GMS_ERR_NO_MODEL
-    return dict(views_ba=views_out, cloud_ba=cloud_out, track_status=status, ba_summary=s, kp_track=kp_track, lists=lists)
+    return dict(views_ba=views_out, cloud_ba=cloud_out, track_status=status, ba_summary=s, kp_track=kp_track, lists=lists, factors=factors, kept_why=kept_why)

@@ -1,7 +1,10 @@
 """CPU: the bundle adjustment statement (tests/sfm_ba_ref.py) -- its Jacobians against central differences of its own
 residual, the five-view scene with ground-truth poses through the CPU two-view chain and the registration statement (without noise and
 with half a pixel of it), what the order of the sums is worth on every hand-made case (tests/sfm_ba_cases.py) against the table the GPU
-test's tolerances come from, the host build of sfm_ba_core.h (tests/cpp/sfm_ba_host.cpp), and the C ABI's host-only parts."""
+test's tolerances come from, what each case is there for -- the structural ones too: a second scan tile, more than 256 frames, more
+frames than cloud entries, a cloud_cap past n_tracks, the sorted-neighbour test, KEPT for two reasons, dropped steps, both ends of
+conjugate gradients and of the outer loop, records that do not fit the arrays --, the host build of sfm_ba_core.h
+(tests/cpp/sfm_ba_host.cpp), and the C ABI's host-only parts."""
 import ctypes as C
 import os
 import subprocess
@@ -27,7 +30,10 @@ CASE_NAMES = sorted(cases.CASES)
 # another numpy build's rounding does not trip it; that headroom is the CPU test's alone.
 MEASURED_SPREAD = {"as_is": 0.0, "behind": 5.9e-16, "multi": 2.3e-14, "outlier_huber": 3.0e-14, "outlier_plain": 8.2e-14,
                    "retriangulate_only": 2.4e-14, "small_cap": 3.8e-14, "three_chain": 2.4e-14, "twelve_frames": 2.8e-14, "two_frames": 2.6e-14,
-                   "unregistered": 2.8e-14, "wide": 8.0e-15, "five_views_noisy": 9.5e-15}
+                   "unregistered": 2.8e-14, "wide": 8.0e-15, "five_views_noisy": 9.5e-15,
+                   "two_tiles": 4.2e-15, "many_frames": 2.0e-12, "frames_past_cap": 1.5e-12, "cap_past_tracks": 2.4e-14, "multi_sorted": 4.8e-15,
+                   "kept": 2.5e-13, "misfit_records": 2.4e-14, "rejected_step": 1.1e-13, "cg_short": 2.2e-14, "cg_converges": 2.2e-14,
+                   "ftol_stops": 7.3e-13, "iters_run_out": 7.3e-13}
 
 
 def tolerance(name):
@@ -42,9 +48,11 @@ def cpu_guard(name):
 
 
 def run_statement(c, **kw):
+    """The statement on a case: n_tracks is the registration summary's, total_m the case's own where it states one."""
     reg = c["reg"]
     return B.bundle_adjust(cases.xy_of(c["kp"]), c["frame_off"], c["pairs"], c["matches"], c["mask"], reg["views"], reg["registration"],
-                           reg["track"], reg["cloud"], reg["cloud_id"], c["camera"], **dict(c["params"], **kw))
+                           reg["track"], reg["cloud"], reg["cloud_id"], c["camera"], n_tracks=int(reg["summary"]["n_tracks"][0]),
+                           total_m=c.get("total_m"), **dict(c["params"], **kw))
 
 
 def spread(a, b):
@@ -80,7 +88,7 @@ def statement_of():
     def get(name):
         if name not in done:
             tr = []
-            done[name] = dict(run_statement(cases.case(name), trace=tr), accepts=[x[0] for x in tr])
+            done[name] = dict(run_statement(cases.case(name), trace=tr), accepts=[x[0] for x in tr], trace=tr)
         return done[name]
     return get
 
@@ -223,6 +231,85 @@ def test_what_the_cases_are_there_for(statement_of):
     a, c = statement_of("as_is"), cases.case("as_is")
     assert a["views_ba"].tobytes() == c["reg"]["views"].tobytes() and a["cloud_ba"].tobytes() == c["reg"]["cloud"].tobytes()
     assert s["retriangulate_only"]["iters_run"] == 0 and s["retriangulate_only"]["cost0"] < s["as_is"]["cost0"]
+    # -- the structural edges: a second scan tile, a second pass over the frames, frames past the cloud, a cap past the tracks
+    tt = statement_of("two_tiles")
+    assert len(tt["track_status"]) >= 4200 and s["two_tiles"]["n_tracks_used"] == len(tt["track_status"]) == 4300
+    assert (tt["track_status"][[0, 4095, 4096, 4299]] == B.REFINED).all() and min(len(x) for x in tt["lists"]) >= 2
+    mf, cm = statement_of("many_frames"), cases.case("many_frames")
+    assert s["many_frames"]["n_frames_free"] == cases.MANY_FRAMES - 1 > 256 and s["many_frames"]["n_active"] == s["many_frames"]["n_obs"] > 0
+    assert run_statement(cm, n_iters=0, retriangulate=0)["ba_summary"][0]["n_active"] == s["many_frames"]["n_obs"]   # and at the registration's points
+    assert max(len(x) for x in mf["lists"]) == 7 and (cm["params"]["n_iters"], cm["params"]["n_cg"]) == (3, 10)
+    assert all(len(x) == cases.MANY_FRAMES - 1 for x in mf["factors"]) and [x[5] for x in mf["trace"]] == ["n_cg"] * 3
+    fp, cf = statement_of("frames_past_cap"), cases.case("frames_past_cap")
+    n_frames = len(cf["frame_off"]) - 1
+    assert len(cf["reg"]["cloud_id"]) == cases.FRAMES_PAST_CAP < n_frames and cases.FRAMES_PAST_CAP <= 256 and s["frames_past_cap"]["n_frames_free"] == n_frames - 1
+    seen_by = np.unique(np.searchsorted(cf["frame_off"], np.nonzero(fp["kp_track"] >= 0)[0], side="right") - 1)
+    for has in fp["factors"]:   # chol6 gave None for every free frame without an observation, and a factor for the others
+        assert 0 < len(has) < n_frames - 1 and np.array_equal(has, seen_by[seen_by > 0])
+    assert B.chol6(np.zeros((6, 6))) is None and fp["views_ba"][n_frames - 1]["R"].tobytes() == cf["reg"]["views"][n_frames - 1]["R"].tobytes()
+    cp, cc, tc = statement_of("cap_past_tracks"), cases.case("cap_past_tracks"), statement_of("three_chain")
+    n_real = cc["n_real"]
+    assert n_real == int(cc["reg"]["summary"]["n_tracks"][0]) == 40 and len(cp["track_status"]) == 90
+    assert (cp["track_status"][n_real:] == B.FEW).all() and cp["cloud_ba"][n_real:].tobytes() == cc["reg"]["cloud"][n_real:].tobytes()
+    assert (cc["reg"]["cloud"][n_real:] == cases.CAP_FILL).all() and (np.diff(cc["reg"]["cloud_id"][n_real:]) < 0).any()
+    assert np.isin(cc["reg"]["cloud_id"][n_real:], cc["reg"]["cloud_id"][:n_real]).all()
+    assert cp["cloud_ba"][:n_real].tobytes() == tc["cloud_ba"].tobytes() and cp["views_ba"].tobytes() == tc["views_ba"].tobytes()
+    assert np.array_equal(cp["track_status"][:n_real], tc["track_status"]) and cp["ba_summary"].tobytes() == tc["ba_summary"].tobytes()
+    # (without n_tracks the padding is searched too, and the repeated ids send observations elsewhere)
+    loose = B.observations(cc["frame_off"], cc["pairs"], cc["matches"], cc["mask"], cc["reg"]["views"], cc["reg"]["registration"], cc["reg"]["track"],
+                           cc["reg"]["cloud_id"])
+    assert not np.array_equal(loose, cp["kp_track"])
+    # -- the sorted-neighbour test, KEPT, a dropped step
+    ms, cs = statement_of("multi_sorted"), cases.case("multi_sorted")
+    e = cs["entry"]
+    assert len(cs["frame_off"]) - 1 == 4 and s["multi_sorted"]["n_tracks_multi"] == 1 and np.nonzero(ms["track_status"] == B.MULTI)[0].tolist() == [e]
+    fr = np.searchsorted(cs["frame_off"], ms["lists"][e], side="right") - 1
+    assert fr.tolist() == [1, 1, 2] and ms["cloud_ba"][e].tobytes() == cs["reg"]["cloud"][e].tobytes()   # n = 3 <= n_frames = 4
+    for w in cs["whole"]:
+        assert (np.searchsorted(cs["frame_off"], ms["lists"][w], side="right") - 1).tolist() == [0, 1, 2, 3] and ms["track_status"][w] == B.REFINED
+    kt, ck = statement_of("kept"), cases.case("kept")
+    assert ck["params"].get("retriangulate", 1) == 1 and kt["kept_why"] == {ck["behind"]: "behind", ck["singular"]: "singular"}
+    assert np.nonzero(kt["track_status"] == B.KEPT)[0].tolist() == sorted([ck["behind"], ck["singular"]])
+    assert s["kept"]["n_tracks_used"] == len(kt["track_status"]) == 41 and s["kept"]["n_obs"] == 102
+    k0 = run_statement(ck, n_iters=0)   # the registration's point is where they start from
+    for e in (ck["behind"], ck["singular"]):
+        assert k0["cloud_ba"][e].tobytes() == ck["reg"]["cloud"][e].tobytes()
+    assert (k0["cloud_ba"][k0["track_status"] == B.REFINED] != ck["reg"]["cloud"][k0["track_status"] == B.REFINED]).any(1).all()
+    rs = statement_of("rejected_step")
+    assert rs["accepts"] == [False] * 7 + [True] * 3 and s["rejected_step"]["iters_accepted"] == 3
+    for accept, cost, c_new, lam, _, _ in rs["trace"][:7]:   # dropped for the cost alone, and by far
+        assert not accept and c_new > 1.5 * cost and cost == rs["trace"][0][1]
+    assert [x[3] for x in rs["trace"][:8]] == pytest.approx([1e-9 * 10.0 ** k for k in range(8)], rel=1e-12) and s["rejected_step"]["n_active"] == 100
+    # -- how conjugate gradients and the outer loop end (cg_iters by both orders of the sums: test_cg_iters_of_the_cg_cases_by_both_orders)
+    assert [x[4:] for x in statement_of("cg_short")["trace"]] == [(2, "n_cg")] * 10 and s["cg_short"]["cg_iters"] == 20
+    cv = statement_of("cg_converges")["trace"]
+    assert all(x[5] == "cg_tol" and 0 < x[4] < 40 for x in cv) and s["cg_converges"]["cg_iters"] == sum(x[4] for x in cv) == 160
+    assert all(x[5] == "cg_tol" for x in statement_of("twelve_frames")["trace"]) and s["twelve_frames"]["cg_iters"] == 257
+    assert s["ftol_stops"]["iters_run"] == 3 < B.PARAMS["n_iters"] and cases.case("ftol_stops")["params"] == dict(ftol=1e-3)
+    assert s["iters_run_out"]["iters_run"] == 3 == cases.case("iters_run_out")["params"]["n_iters"] and s["iters_run_out"]["iters_accepted"] == 3
+    last = statement_of("iters_run_out")["trace"][-1]
+    assert last[1] - last[2] > 0.0 and last[1] - last[2] <= 1e-3 * last[1]   # ftol = 0 did not stop it; ftol = 1e-3 stops at this very step
+    # -- records that do not fit
+    mr, cr = statement_of("misfit_records"), cases.case("misfit_records")
+    assert len(cr["pairs"]) == 7 and (cr["reg"]["registration"]["status"] == 0).all() and cr["total_m"] == len(cr["mask"])
+    for k in ("views_ba", "cloud_ba", "track_status", "ba_summary", "kp_track"):
+        assert np.asarray(mr[k]).tobytes() == np.asarray(tc[k]).tobytes(), k
+
+
+def cg_iters_by_both_orders(name):
+    """cg_iters of a case by the statement as written and with every sum reversed: what the device's count must lie between (and
+    equal, where the two agree)."""
+    c = cases.case(name)
+    return tuple(int(run_statement(c, order=o)["ba_summary"][0]["cg_iters"]) for o in (1, -1))
+
+
+def test_cg_iters_of_the_cg_cases_by_both_orders():
+    """cg_short: n_cg = 2 ends every one of the 10 solves, whatever the order. cg_converges: the threshold ends each; the order of the
+    sums may move a crossing by an iteration, here it does not."""
+    assert cg_iters_by_both_orders("cg_short") == (20, 20)
+    a, b = cg_iters_by_both_orders("cg_converges")
+    print("cg_converges: cg_iters", a, "and with the sums reversed", b)
+    assert a == 160 and abs(a - b) <= 6
 
 
 # ---- the host build -------------------------------------------------------------------------------------------------------------------
@@ -247,7 +334,8 @@ def test_host_build_of_the_core_equals_the_statement(host, name):
     track's re-triangulated point."""
     c = cases.case(name)
     reg = c["reg"]
-    kp_track = B.observations(c["frame_off"], c["pairs"], c["matches"], c["mask"], reg["views"], reg["registration"], reg["track"], reg["cloud_id"])
+    kp_track = B.observations(c["frame_off"], c["pairs"], c["matches"], c["mask"], reg["views"], reg["registration"], reg["track"], reg["cloud_id"],
+                              int(reg["summary"]["n_tracks"][0]), c.get("total_m"))
     g = np.nonzero(kp_track >= 0)[0]
     fr, tc = np.searchsorted(c["frame_off"], g, side="right") - 1, kp_track[g]
     uv = B.undistort(c["camera"], cases.xy_of(c["kp"])[g])
