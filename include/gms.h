@@ -415,7 +415,8 @@ int gms_disparity_batch_device(gms_ctx* ctx, const gms_keypoint* d_kp, const int
  *   synchronisation, no readback (graph-capturable).
  * gms_sfm_register_workspace_bytes: the workspace for n_pairs pairs over total_kp keypoints and total_matches match slots (0: refused).
  * gms_sfm_register: plan + the device call on host arrays, synchronous, on the current HIP device; the outputs cover every match
- *   slot below max(match_off + m) and cloud_cap entries (what the device call leaves untouched is 0). */
+ *   slot below max(match_off + m) and cloud_cap entries (what the device call leaves untouched is 0). A pair with m < 0,
+ *   match_off < 0 or match_off > 2^40 - m (held so, before the sum is formed): GMS_ERR_BAD_ARG, nothing run. */
 #define GMS_SFM_SKIPPED 1   /* gms_sfm_pair_reg.status of a pair the plan does not use */
 typedef struct gms_sfm_plan_entry {
     int32_t registers;  /* 1: the pair registers its frame_b                     */
@@ -480,7 +481,8 @@ int gms_sfm_register(const int64_t* frame_off, int n_frames, const gms_pair* pai
  *   lambda0, cg_tol, ftol or huber_px, total_kp or cloud_cap >= 2^31 - 1, more than 2^24 frames, a workspace that is not 256-byte aligned or too small:
  *   GMS_ERR_BAD_ARG, nothing run. Stream-ordered on the context's stream; no allocation, no synchronisation, no readback
  *   (graph-capturable); 12 + n_iters (8 + 3 n_cg) launches.
- * gms_sfm_ba: the same on host arrays, synchronous, on the current HIP device; n_tracks: the registration summary's. */
+ * gms_sfm_ba: the same on host arrays, synchronous, on the current HIP device; n_tracks: the registration summary's. A pair with
+ *   m < 0, match_off < 0 or match_off > 2^40 - m (held so, before the sum is formed): GMS_ERR_BAD_ARG, nothing run. */
 typedef struct gms_sfm_ba_params {
     double  lambda0, cg_tol, ftol, huber_px;   /* 1e-3, 1e-8, 1e-10, 2.0 */
     int32_t n_iters, n_cg, retriangulate;      /* 10, 50, 1              */

@@ -1960,6 +1960,13 @@ static bool sfm_register_sizes_ok(int n_frames, int n_pairs, int64_t total_kp, i
     return n_frames >= 1 && n_pairs >= 0 && total_kp >= 0 && total_kp < INT32_MAX && total_matches >= 0 && total_matches < ((int64_t)1 << 40);
 }
 
+// a pair's match range as the host one-shots take it: m >= 0, match_off >= 0 and an end within the 2^40 that sfm_register_sizes_ok
+// allows -- match_off is held against 2^40 - m, so that match_off + m is formed only where it fits
+static bool sfm_match_range_ok(const gms_pair& pr)
+{
+    return pr.m >= 0 && pr.match_off >= 0 && pr.match_off <= ((int64_t)1 << 40) - (int64_t)pr.m;
+}
+
 size_t gms_sfm_register_workspace_bytes(int n_frames, int n_pairs, int64_t total_kp, int64_t total_matches)
 {
     if (!sfm_register_sizes_ok(n_frames, n_pairs, total_kp, total_matches)) return 0;
@@ -2003,7 +2010,7 @@ int gms_sfm_register(const int64_t* frame_off, int n_frames, const gms_pair* pai
     int64_t total_m = 0;
     int max_m = 0;
     for (int p = 0; p < n_pairs; p++) {
-        if (pairs[p].m < 0 || pairs[p].match_off < 0) return GMS_ERR_BAD_ARG;
+        if (!sfm_match_range_ok(pairs[p])) return GMS_ERR_BAD_ARG;
         total_m = std::max(total_m, pairs[p].match_off + (int64_t)pairs[p].m);
         max_m = std::max(max_m, pairs[p].m);
     }
@@ -2105,7 +2112,7 @@ int gms_sfm_ba(const gms_camera* camera, const gms_sfm_ba_params* params, const 
         if (frame_off[f] < 0 || frame_off[f + 1] < frame_off[f]) return GMS_ERR_BAD_ARG;
     int64_t total_m = 0;
     for (int p = 0; p < n_pairs; p++) {
-        if (pairs[p].m < 0 || pairs[p].match_off < 0) return GMS_ERR_BAD_ARG;
+        if (!sfm_match_range_ok(pairs[p])) return GMS_ERR_BAD_ARG;
         total_m = std::max(total_m, pairs[p].match_off + (int64_t)pairs[p].m);
     }
     const int64_t total_kp = frame_off[n_frames];

@@ -48,6 +48,26 @@ inline bool plan(const gms_pair* pairs, int n_pairs, int n_frames, int root, int
     return true;
 }
 
+// Whether a pair's record fits the arrays it indexes: both frame indices in [0, n_frames), m >= 0, a match range inside
+// [0, total_m] and both frames' keypoint ranges inside [0, total_kp]. No sum is formed that need not fit 64 bits: match_off is held
+// against total_m - m (total_m >= 0 and m >= 0 by then), a frame's end against total_kp. frame_off is read only behind the frame
+// indices' check. A pair that does not fit has no matches and does not register. *r: the two frames' ranges, set when it fits.
+struct PairRanges {
+    int64_t oa, ob, na, nb;
+};
+SFR_HD bool pair_fits(const gms_pair& pr, const int64_t* frame_off, int n_frames, int64_t total_kp, int64_t total_m, PairRanges* r)
+{
+    if (pr.frame_a < 0 || pr.frame_a >= n_frames || pr.frame_b < 0 || pr.frame_b >= n_frames || pr.m < 0 || pr.match_off < 0 || total_m < 0 ||
+        pr.match_off > total_m - (int64_t)pr.m)
+        return false;
+    const int64_t oa = frame_off[pr.frame_a], ea = frame_off[pr.frame_a + 1], ob = frame_off[pr.frame_b], eb = frame_off[pr.frame_b + 1];
+    if (oa < 0 || ob < 0 || ea < oa || eb < ob || ea > total_kp || eb > total_kp) return false;
+    *r = PairRanges{oa, ob, ea - oa, eb - ob};
+    return true;
+}
+// A plan entry of pair i that the walk in pair order can follow: one that registers links to an earlier pair, or to none (-1).
+SFR_HD bool plan_entry_fits(const gms_sfm_plan_entry& pl, int i) { return !pl.registers || (pl.link >= -1 && pl.link < i); }
+
 // the matches of a pair that the stage reads: those the two-view stage gathered
 SFR_HD int pair_count(const gms_pair& pr, const gms_two_view& t)
 {

@@ -63,22 +63,17 @@ __device__ __forceinline__ PairInfo pair_info(const SfrIn& in, int i)
     const gms_pair pr = in.pairs[i];
     p.pl = in.plan[i];
     p.a = pr.frame_a;
-    bool fits = pr.frame_a >= 0 && pr.frame_a < in.n_frames && pr.frame_b >= 0 && pr.frame_b < in.n_frames && pr.m >= 0 &&
-                pr.match_off >= 0 && pr.match_off + (int64_t)pr.m <= in.total_m;
-    if (fits) {
-        p.oa = in.frame_off[pr.frame_a];
-        p.ob = in.frame_off[pr.frame_b];
-        const int64_t na = in.frame_off[pr.frame_a + 1] - p.oa, nb = in.frame_off[pr.frame_b + 1] - p.ob;
-        fits = p.oa >= 0 && p.ob >= 0 && na >= 0 && nb >= 0 && p.oa + na <= in.total_kp && p.ob + nb <= in.total_kp;
-        p.na = (int)na;
-        p.nb = (int)nb;
-    }
-    if (p.pl.registers && (p.pl.link < -1 || p.pl.link >= i)) fits = false;  // a link points back: the walk in pair order is the plan's
-    if (!fits) {
+    sfr::PairRanges fr = {};
+    // (a link points back: the walk in pair order is the plan's)
+    if (!sfr::pair_fits(pr, in.frame_off, in.n_frames, in.total_kp, in.total_m, &fr) || !sfr::plan_entry_fits(p.pl, i)) {
         p = PairInfo{};
         p.pl = gms_sfm_plan_entry{0, -1, 0, 0};
         return p;
     }
+    p.oa = fr.oa;
+    p.ob = fr.ob;
+    p.na = (int)fr.na;
+    p.nb = (int)fr.nb;
     p.off = pr.match_off;
     p.n = sfr::pair_count(pr, in.tv[i]);
     return p;

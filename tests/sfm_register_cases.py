@@ -5,7 +5,10 @@ of the pair without a link that starts i's chain), whatever the median picks amo
 
 Keypoint perm_f[s] of frame f shows scene point s (a different permutation per frame, and frame f has 3 f keypoints that show
 nothing), so that queryIdx and trainIdx cannot be mixed up unnoticed. case(name) -> dict(frame_off, pairs, matches, mask, points3d,
-tv, root, min_links, expect = {pair: (status, n_links or None, S or None)}, truth = (R [n, 3, 3], t [n, 3]))."""
+tv, root, min_links, expect = {pair: (status, n_links or None, S or None)}, truth = (R [n, 3, 3], t [n, 3])). A case may add
+cloud_cap (the capacity to run it with), and -- the cases named in UNFIT -- plan (the plan to walk instead of the pair list's own),
+host_pairs (the sane records the host sizes its buffers by, where `pairs` are what the device reads) and total_m (the arrays'
+length)."""
 import functools
 
 import numpy as np
@@ -21,18 +24,22 @@ TWO_VIEW_DTYPE = np.dtype([("E", "<f8", (3, 3)), ("R", "<f8", (3, 3)), ("t", "<f
 
 
 class Scene:
-    def __init__(self, seed, n_frames, n_points):
+    """gentle: 0.002 rad and (0.01, 0.002, 0.003) of motion per frame instead of 0.03 rad and 0.4 -- the scene stays in front of
+    hundreds of cameras, where the default motion puts it behind them after about 60. spare: per frame the number of keypoints that
+    show nothing (default 3 f)."""
+
+    def __init__(self, seed, n_frames, n_points, gentle=False, spare=None):
         rng = np.random.default_rng(seed)
         self.rng, self.n_frames, self.n_points = rng, n_frames, n_points
         self.X = np.stack([rng.uniform(-3, 3, n_points), rng.uniform(-2, 2, n_points), rng.uniform(5, 9, n_points)], 1)
         self.R, self.t = np.zeros((n_frames, 3, 3)), np.zeros((n_frames, 3))
         for f in range(n_frames):
-            a, b = 0.03 * f, -0.02 * f
+            a, b = (0.002 * f, -0.001 * f) if gentle else (0.03 * f, -0.02 * f)
             Ry = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
             Rx = np.array([[1, 0, 0], [0, np.cos(b), -np.sin(b)], [0, np.sin(b), np.cos(b)]])
             self.R[f] = Ry @ Rx
-            self.t[f] = -self.R[f] @ np.array([0.4 * f, 0.05 * f * f, 0.1 * f])
-        self.counts = np.array([n_points + 3 * f for f in range(n_frames)])
+            self.t[f] = -self.R[f] @ (np.array([0.01 * f, 0.002 * f, 0.003 * f]) if gentle else np.array([0.4 * f, 0.05 * f * f, 0.1 * f]))
+        self.counts = np.array([n_points + (3 * f if spare is None else int(spare[f])) for f in range(n_frames)])
         self.perm = [rng.permutation(self.counts[f])[:n_points] for f in range(n_frames)]
         self.frame_off = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int64)
 
@@ -181,8 +188,190 @@ def _many_links():
     return c
 
 
+def _unit(f):
+    return 1.0 + 0.25 * (f % 5)
+
+
+def _chain_300():
+    """301 frames, pair f = (f, f + 1): every link is the previous pair and every frame_a the frame it registered, so the walk of
+    sfr_compose_kernel takes all of it from its registers, across the boundary of its 256 staged pairs. 24 tracks of 301 keypoints."""
+    sc = Scene(31, 301, 24, gentle=True)
+    c = assemble(sc, [dict(a=f, b=f + 1, unit=_unit(f), pts=np.arange(24)) for f in range(300)])
+    c["expect"] = {f: (GMS_OK, 24 if f else 0, _unit(f)) for f in range(300)}
+    return c
+
+
+def _star_300():
+    """The same frames, pair f = (0, f + 1): every link is pair 0 in role 0, so from pair 2 on its outcome and scale are read from
+    global memory, and the view of frame_a is the root's."""
+    sc = Scene(32, 301, 24, gentle=True)
+    c = assemble(sc, [dict(a=0, b=f + 1, unit=_unit(f), pts=np.arange(24)) for f in range(300)])
+    c["expect"] = {f: (GMS_OK, 24 if f else 0, _unit(f)) for f in range(300)}
+    return c
+
+
+def _two_branches_300():
+    """Two chains out of frame 0, taken in turn: pairs (0, 1), (0, 2), then pair i = (i - 1, i + 1). The link of pair i is pair i - 2
+    and frame_a is never the frame registered last: outcome, scale and view all come from global memory. Pair 256 -- the first of
+    the second staging pass -- has no two-view model: its branch fails from there on, the other goes on."""
+    sc = Scene(33, 301, 24, gentle=True)
+    specs = [dict(a=0 if i < 2 else i - 1, b=i + 1, unit=_unit(i), pts=np.arange(24)) for i in range(300)]
+    specs[256]["status"] = NO_MODEL
+    c = assemble(sc, specs)
+    # (pairs 256 and 258 measure no link: one side has no two-view result; from 260 on both sides have one)
+    c["expect"] = {i: (GMS_OK, 24 if i else 0, _unit(i)) if i < 256 or i % 2 else (NO_MODEL, 0 if i < 260 else 24, 0.0) for i in range(300)}
+    return c
+
+
+def _tiles_past_256():
+    """Three frames, the root with 1,100,000 spare keypoints: 1,100,185 keypoints are 269 tiles of the ordered compaction, past one
+    pass of sfr_scan_kernel. The track ids are keypoints of frame 0, scattered over its tiles by the permutation, and -- for the
+    points only pair 1 shows -- of frame 1, in the last tile. cloud_cap: what the device call is given (the default would be half the
+    keypoints)."""
+    sc = Scene(34, 3, 60, spare=(1100000, 2, 3))
+
+    def half_other(blk):
+        _scale_points(blk, np.arange(20, len(blk["P"])), 1 / 1.5)
+    c = assemble(sc, [dict(a=0, b=1, unit=1.0, pts=np.arange(0, 50), junk=3), dict(a=1, b=2, unit=2.5, pts=np.arange(10, 60), junk=4, edit=half_other)])
+    c["expect"] = {0: (GMS_OK, 0, 1.0), 1: (GMS_OK, 40, 2.5)}
+    c["cloud_cap"] = 64
+    return c
+
+
+def _ratio_spread():
+    """Ratios that differ in every byte, so that each of the eight passes of the radix select has more than one bin to walk. Every
+    pair but the first hangs on pair 0 and nothing hangs on them, so their scaled points reach no other pair.
+    pair 1 (role 1): 41 links, its own point e scaled by 2^(-24 e), e = -20 .. 20 shuffled -- ratios 2^-480 .. 2^480 times the true one,
+    which is the median. pair 2 (role 0): 40 links, 19 ratios below the true one and 20 above in steps of 2^20: the lower median is
+    the true one, the upper is not. pair 3 (role 0): 257 links -- past one trip of the 256 lanes over the ratios --, 200 of them one
+    match repeated (one ratio, bit for bit: more than the target in one bin, in every pass), 28 within 2^-3 .. 2^-48 of it on either
+    side, four to a byte, and 29 whole powers of 2^16 away. pair 4 (role 0): 63 links, the true ratio and 31 on either side of it at
+    random factors within 2, so that the mantissas differ from the first byte on: from pass 5 down the median is alone behind its
+    prefix, and a ratio counted without the prefix compare falls into a lower bin."""
+    sc = Scene(35, 6, 300)
+    rng = np.random.default_rng(350)
+
+    def wide(blk):
+        blk["P"] *= np.exp2(-24.0 * rng.permutation(np.arange(-20, 21)))[:, None]
+
+    def even(blk):
+        blk["P"] *= np.exp2(-20.0 * rng.permutation(np.arange(-19, 21)))[:, None]
+
+    def bunch(blk):
+        f = [1.0]                                             # row 0: the match that is repeated
+        for s in (3, 8, 16, 24, 32, 40, 48):                  # a relative step of 2^-s lands in byte 6, 5, .. 0 of the ratio
+            f += [1 - 2.0 ** -s, 1 + 2.0 ** -s, 1 - 3 * 2.0 ** -s, 1 + 3 * 2.0 ** -s]
+        f += [2.0 ** (16 * e) for e in range(-14, 16) if e]
+        assert len(f) == len(blk["P"]) == 58
+        blk["P"] *= np.array(f)[:, None]
+        for k in ("q", "t", "mask"):
+            blk[k] = np.concatenate([blk[k], np.repeat(blk[k][:1], 199)])
+        blk["P"] = np.concatenate([blk["P"], np.repeat(blk["P"][:1], 199, 0)])
+
+    def scatter(blk):
+        blk["P"] *= rng.permutation(np.concatenate([rng.uniform(0.5, 1.0, 31), [1.0], rng.uniform(1.0, 2.0, 31)]))[:, None]
+    specs = [dict(a=0, b=1, unit=1.0, pts=np.arange(300), junk=7),
+             dict(a=1, b=2, unit=2.5, pts=np.arange(100, 141), edit=wide),
+             dict(a=0, b=3, unit=0.7, pts=np.arange(30, 70), junk=3, edit=even),
+             dict(a=0, b=4, unit=0.3, pts=np.arange(200, 258), edit=bunch),
+             dict(a=0, b=5, unit=1.7, pts=np.arange(120, 183), junk=5, edit=scatter)]
+    c = assemble(sc, specs)
+    c["expect"] = {0: (GMS_OK, 0, 1.0), 1: (GMS_OK, 41, 2.5), 2: (GMS_OK, 40, 0.7), 3: (GMS_OK, 257, 0.3), 4: (GMS_OK, 63, 1.7)}
+    return c
+
+
+def _first_root_pair_fails():
+    """upstream_failures' shape with the first registering pair out of the root without a two-view model: the two role-0 pairs behind
+    it have no link table to measure against (n_links 0, r 0) and fail, and so does everything further down; nothing registers but
+    the root. The reverse pair stays skipped."""
+    sc = Scene(36, 8, 30)
+    specs = [dict(a=2, b=0, unit=1.0, pts=np.arange(30), junk=4, status=NO_MODEL),
+             dict(a=0, b=1, unit=0.25, pts=np.arange(30), junk=7),
+             dict(a=1, b=3, unit=1.0, pts=np.arange(30)),      # both this pair and its link have a two-view result: 30 links, and no model
+             dict(a=2, b=5, unit=2.0, pts=np.arange(30)),      # role 0
+             dict(a=5, b=6, unit=1.0, pts=np.arange(5, 30)),
+             dict(a=1, b=0, unit=1.0, pts=np.arange(30)),      # both frames are registered by the plan: skipped
+             dict(a=2, b=7, unit=8.0, pts=np.arange(3, 30))]   # role 0
+    c = assemble(sc, specs, root=2)
+    c["expect"] = {0: (NO_MODEL, 0, 0.0), 1: (NO_MODEL, 0, 0.0), 2: (NO_MODEL, 30, 0.0), 3: (NO_MODEL, 0, 0.0), 4: (NO_MODEL, 25, 0.0),
+                   5: (SKIPPED, 0, 0.0), 6: (NO_MODEL, 0, 0.0)}
+    return c
+
+
+def _misfit_records():
+    """chain_roles plus seven pairs over seven more frames of 60 keypoints each. `host_pairs` -- what makes the plan, total_m and max_m --
+    holds sane records: pairs 7 .. 12 each register a frame of their own (7 .. 12) out of a registered one, with ten inlier matches
+    between keypoints that their link saw, real points and a pose, so that each would register if it were read; pair 13 = (11, 13)
+    hangs on pair 11. `pairs` -- what the device and the statement read -- differs in pairs 7 .. 12: frame_a = n_frames; frame_b = -1;
+    m = -3; match_off = -1; a range of 10 that ends 5 slots past total_m (its first 5 slots, the arrays' last, hold pair 13's inlier
+    matches and points); match_off = 2^63 - 2 with m = 5, whose sum does not fit 64 bits. Each of them ends skipped, pair 13 without
+    a model, and everything else is chain_roles' own."""
+    import sfm_register_ref
+    base, sc = _chain_roles(), Scene(11, 7, 60)
+    n0, f0, m0 = len(base["pairs"]), len(base["frame_off"]) - 1, len(base["mask"])
+    frame_off = np.concatenate([base["frame_off"], base["frame_off"][-1] + 60 * np.arange(1, 8)]).astype(np.int64)
+    from_frame = [1, 2, 3, 4, 1, 2, 11]
+    host = np.zeros(7, PAIR_DTYPE)
+    tv = np.zeros(7, TWO_VIEW_DTYPE)
+    total_m = m0 + 6 * 12 + 10                                # the arrays end with pair 13's last match
+    matches, mask, points = np.zeros(total_m, DMATCH_DTYPE), np.full(total_m, 255, np.uint8), np.full((total_m, 3), FILL)
+    matches[:m0], mask[:m0], points[:m0] = base["matches"], base["mask"], base["points3d"]
+    matches["queryIdx"][m0:], matches["trainIdx"][m0:] = -5, 10 ** 6
+    s = np.arange(10, 20)                                     # scene points that every registering pair of chain_roles shows
+    for k, a in enumerate(from_frame):
+        off = m0 + 12 * k
+        host[k] = (a, f0 + k, 10, 0, off)
+        matches["queryIdx"][off:off + 10], matches["trainIdx"][off:off + 10] = (sc.perm[a][s] if a < f0 else s), s
+        mask[off:off + 10] = 1
+        points[off:off + 10] = sc.cam(min(a, f0 - 1), s)
+        tv[k]["R"], tv[k]["t"], tv[k]["n_points"], tv[k]["n_triangulated"] = np.eye(3), (1.0, 0.0, 0.0), 10, 10
+    dev = host.copy()
+    dev["frame_a"][0] = f0 + 7
+    dev["frame_b"][1] = -1
+    dev["m"][2] = -3
+    dev["match_off"][3] = -1
+    dev["match_off"][4] = total_m - 5
+    dev["match_off"][5], dev["m"][5] = 2 ** 63 - 2, 5
+    host_pairs = np.concatenate([base["pairs"], host])
+    R, t = base["truth"]
+    c = dict(base, frame_off=frame_off, pairs=np.concatenate([base["pairs"], dev]), host_pairs=host_pairs, matches=matches, mask=mask,
+             points3d=points, tv=np.concatenate([base["tv"], tv]), total_m=total_m, n_base_pairs=n0, n_base_frames=f0,
+             plan=sfm_register_ref.plan(np.stack([host_pairs["frame_a"], host_pairs["frame_b"]], 1), f0 + 7, base["root"]),
+             truth=(np.concatenate([R, np.zeros((7, 3, 3))]), np.concatenate([t, np.zeros((7, 3))])))
+    c["expect"] = {**base["expect"], **{n0 + k: (SKIPPED, 0, 0.0) for k in range(6)}, n0 + 6: (NO_MODEL, 0, 0.0)}
+    return c
+
+
+def _bad_plan_links():
+    """chain_roles with plan entries that the walk cannot follow. `plan` (what the device and the statement are given in place of the
+    pair list's own): pair 1 links to itself and pair 2 forward, to pair 4 -- both are skipped, and pair 6, which hangs on pair 2,
+    has no model. `more_plans`: pair 1 with link -2 and pair 6 with link n_pairs + 5 (both skipped, the rest as planned); and pair 0
+    with link -2, which takes every registering pair with it. Each with the (status, n_links, S) it must end in."""
+    import sfm_register_ref
+    c = _chain_roles()
+    n = len(c["pairs"])
+    own = sfm_register_ref.plan(np.stack([c["pairs"]["frame_a"], c["pairs"]["frame_b"]], 1), len(c["frame_off"]) - 1, c["root"])
+
+    def with_links(links):
+        p = own.copy()
+        for i, link in links.items():
+            assert p[i]["registers"]
+            p[i]["link"] = link
+        return p
+    skipped, failed = (SKIPPED, 0, 0.0), (NO_MODEL, 0, 0.0)
+    c["plan"] = with_links({1: 1, 2: 4})
+    c["expect"] = {**c["expect"], 1: skipped, 2: skipped, 6: failed}
+    c["more_plans"] = [(with_links({1: -2, 6: n + 5}), {**c["expect"], 1: skipped, 2: (GMS_OK, 41, 0.7), 6: skipped}),
+                       # (pair 6 and its link, pair 2, both have a two-view result: their 35 links are measured)
+                       (with_links({0: -2}), {**c["expect"], 0: skipped, 1: failed, 2: failed, 6: (NO_MODEL, 35, 0.0)})]
+    return c
+
+
 CASES = {"chain_roles": _chain_roles, "lowest_k_wins": _lowest_k_wins, "invalid_links_and_min_links": _invalid_links_and_min_links,
-         "upstream_failures": _upstream_failures, "many_links": _many_links}
+         "upstream_failures": _upstream_failures, "many_links": _many_links, "chain_300": _chain_300, "star_300": _star_300,
+         "two_branches_300": _two_branches_300, "tiles_past_256": _tiles_past_256, "ratio_spread": _ratio_spread,
+         "first_root_pair_fails": _first_root_pair_fails, "misfit_records": _misfit_records, "bad_plan_links": _bad_plan_links}
+UNFIT = ("misfit_records", "bad_plan_links")   # cases whose records or plan differ from what the pair list alone gives
 
 
 @functools.lru_cache(maxsize=None)

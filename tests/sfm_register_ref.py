@@ -4,7 +4,8 @@ sfm_register_core.h / sfm_register_kernels.hip compute on the device and tests/c
 Inputs are what gms_two_view_batch_device leaves: frame_off [n_frames + 1], pairs (PAIR_DTYPE), the survivors `matches` (DMATCH_DTYPE),
 `mask` (uint8) and `points3d` ([.., 3] float64) laid out by the pairs' match_off, and `tv` (TWO_VIEW_DTYPE per pair). Pair i has
 n_i = clamp(tv.n_points, 0, m) matches when tv.status is GMS_OK, none otherwise; rank(k) = non-zero mask bytes before k; its points
-are points3d[match_off + rank]. A match whose queryIdx / trainIdx lies outside its frame is ignored everywhere."""
+are points3d[match_off + rank]. A match whose queryIdx / trainIdx lies outside its frame is ignored everywhere, and so is a pair
+whose record does not fit the arrays or whose plan entry the walk cannot follow (pair_fits, plan_entry_fits: the kernels' rule)."""
 import numpy as np
 
 GMS_OK, GMS_SFM_SKIPPED, GMS_ERR_NO_MODEL = 0, 1, -8
@@ -44,6 +45,9 @@ def plan(frame_pairs, n_frames, root=0):
     return out
 
 
+plan_of_pairs = plan   # (register() has an argument of the name)
+
+
 def rows_times(V, M):
     """V @ M for rows V [n, 3], as three products summed in order -- what the C code does, also on non-finite values."""
     return V[:, 0:1] * M[0] + V[:, 1:2] * M[1] + V[:, 2:3] * M[2]
@@ -67,15 +71,47 @@ def _pair_view(i, pairs, matches, mask, tv, counts):
     return k, q[k], t[k], rank[k], int(mk.sum())
 
 
-def register(frame_off, pairs, matches, mask, points3d, tv, root=0, min_links=8):
+def pair_fits(pair, frame_off, total_m):
+    """sfr::pair_fits of sfm_register_core.h in Python's integers: both frame indices in [0, n_frames), m >= 0, the match range inside
+    [0, total_m] and both frames' keypoint ranges inside [0, total_kp]."""
+    n_frames, total_kp = len(frame_off) - 1, int(frame_off[-1])
+    a, b, m, off = int(pair["frame_a"]), int(pair["frame_b"]), int(pair["m"]), int(pair["match_off"])
+    if not (0 <= a < n_frames and 0 <= b < n_frames) or m < 0 or off < 0 or off + m > total_m:
+        return False
+    return all(0 <= int(frame_off[f]) <= int(frame_off[f + 1]) <= total_kp for f in (a, b))
+
+
+def plan_entry_fits(entry, i):
+    """sfr::plan_entry_fits: an entry that registers links to an earlier pair or to none."""
+    return not entry["registers"] or -1 <= int(entry["link"]) < i
+
+
+_NO_MATCHES = (np.zeros(0, np.int64),) * 4 + (0,)
+
+
+def register(frame_off, pairs, matches, mask, points3d, tv, root=0, min_links=8, plan=None, total_m=None):
     """-> dict(plan, views VIEW_DTYPE [n_frames], registration PAIR_REG_DTYPE [n_pairs], points_world [len(points3d), 3], track int32
     [len(points3d)], cloud [n_tracks, 3], cloud_id, cloud_obs, cloud_est (int32), cloud_spread (float64), summary SUMMARY_DTYPE [1]).
-    points_world / track entries that belong to no point are 0 / -1."""
+    points_world / track entries that belong to no point are 0 / -1.
+
+    plan: PLAN_DTYPE entries to walk instead of the pair list's own (returned as given); total_m: the length of the match arrays
+    (default: the mask's). A pair that does not fit -- pair_fits, or a plan entry that is not plan_entry_fits -- has no matches and
+    the plan entry {0, -1, 0, 0}, as in the kernels: it ends GMS_SFM_SKIPPED with link -1 and zeros, and what hangs on it by the plan
+    fails by the ordinary rule. The pair list's own plan is made only where none is given: it refuses a frame index out of range."""
     frame_off = np.asarray(frame_off, dtype=np.int64)
     n_frames, n_pairs = len(frame_off) - 1, len(pairs)
     counts = np.diff(frame_off)
     P = np.asarray(points3d, dtype=np.float64).reshape(-1, 3)
-    pl = plan(np.stack([pairs["frame_a"], pairs["frame_b"]], 1) if n_pairs else np.zeros((0, 2)), n_frames, root)
+    given = plan
+    if given is None:
+        given = plan_of_pairs(np.stack([pairs["frame_a"], pairs["frame_b"]], 1) if n_pairs else np.zeros((0, 2)), n_frames, root)
+    given = np.asarray(given, dtype=PLAN_DTYPE)
+    total_m = len(mask) if total_m is None else int(total_m)
+    fits = [pair_fits(pairs[i], frame_off, total_m) and plan_entry_fits(given[i], i) for i in range(n_pairs)]
+    pl = given.copy()
+    for i in range(n_pairs):
+        if not fits[i]:
+            pl[i] = (0, -1, 0, 0)
     views = np.zeros(n_frames, VIEW_DTYPE)
     views["pair"] = -1
     views[root]["R"], views[root]["registered"] = np.eye(3), 1
@@ -83,7 +119,7 @@ def register(frame_off, pairs, matches, mask, points3d, tv, root=0, min_links=8)
     reg["link"], reg["status"] = -1, GMS_SFM_SKIPPED
     world = np.zeros_like(P)
     track = np.full(len(P), -1, np.int32)
-    pv = [_pair_view(i, pairs, matches, mask, tv, counts) for i in range(n_pairs)]
+    pv = [_pair_view(i, pairs, matches, mask, tv, counts) if fits[i] else _NO_MATCHES for i in range(n_pairs)]
     base_ok = [bool(pl[i]["registers"]) and tv[i]["status"] == GMS_OK and tv[i]["n_triangulated"] > 0 for i in range(n_pairs)]
     ok = np.zeros(n_pairs, bool)
     for i in range(n_pairs):
@@ -150,7 +186,9 @@ def register(frame_off, pairs, matches, mask, points3d, tv, root=0, min_links=8)
             if rx != ry:
                 parent[max(rx, ry)] = min(rx, ry)
         est += [(int(i), int(rk), int(x)) for rk, x in zip(rank, u)]
-    root_of = np.array([find(g) for g in range(total_kp)], dtype=np.int64)
+    root_of = np.arange(total_kp, dtype=np.int64)             # (a keypoint of no edge is its own root, and nothing below reads it)
+    for g in np.nonzero(member)[0].tolist():
+        root_of[g] = find(g)
     ids = np.unique(root_of[member])
     index_of = {int(g): c for c, g in enumerate(ids)}
     n_tracks = len(ids)
@@ -177,7 +215,7 @@ def register(frame_off, pairs, matches, mask, points3d, tv, root=0, min_links=8)
     summary = np.zeros(1, SUMMARY_DTYPE)
     summary["n_tracks"], summary["n_points"], summary["n_multi"] = n_tracks, len(est), int((frames_in < cloud_obs).sum())
     summary["n_registered"], summary["n_ok_pairs"] = int(views["registered"].sum()), int(ok.sum())
-    return dict(plan=pl, views=views, registration=reg, points_world=world, track=track, cloud=cloud, cloud_id=ids.astype(np.int32),
+    return dict(plan=given, views=views, registration=reg, points_world=world, track=track, cloud=cloud, cloud_id=ids.astype(np.int32),
                 cloud_obs=cloud_obs, cloud_est=cloud_est, cloud_spread=spread, summary=summary)
 
 

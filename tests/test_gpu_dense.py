@@ -1,5 +1,5 @@
 """GPU: gms_dense_cloud_device, gms_dense_pairs_device and their Python faces against tests/rectify_ref.py, byte for byte (DESIGN.md
-§4.13): the cloud kernels on hand-made int16 planes (no matcher involved), the whole stage on a rendered plane against the numpy
+§4.13): the cloud kernels on hand-made int16 planes (no matcher involved; also past the 256 blocks of one scan pass), the whole stage on a rendered plane against the numpy
 chain, a failed pair inside a batch, one graph capture replayed on new poses, the committed 450 x 375 pair, the interface and the
 refused arguments."""
 import importlib
@@ -106,6 +106,29 @@ def test_cloud_batch_of_three_on_hand_made_planes(ctx, w, h, channels):
                 assert np.array_equal(col[i, :k].reshape(wc[:k].shape), wc[:k])
                 assert (np.diff(pix[i, :k]) > 0).all()           # raster order
                 assert (xyz[i, k:] == -7.0).all() and (pix[i, k:] == -7).all() and (col[i, k:] == 0xA5).all()   # nothing past cap or count
+
+
+def test_cloud_past_256_scan_blocks(ctx):
+    """Two hand-made 512 x 520 maps: 260 blocks of 1024 pixels each, past one pass of cloud_scan_kernel, whose second pass adds the
+    carry of the first 256. A cap above both counts, and one that ends inside block 258 of the first map: the counts, the bytes in
+    raster order, and the fill behind the cap or the count."""
+    import torch
+    w, h = 512, 520
+    maps = [_hand_made_map(900 + i, h, w) for i in range(2)]
+    disp, valid = np.stack([m[0] for m in maps]), np.stack([m[1] for m in maps])
+    plans = [_plan((w, h), "rot10_x"), _plan((w, h), "rot10_z")]
+    want = [rr.cloud(disp[i], valid[i], None, plans[i], FILTERED, 16) for i in range(2)]
+    assert -(-w * h // 1024) == 260 and all((x[2] >= 257 * 1024).sum() > 1000 for x in want)     # points in the blocks behind the first pass
+    inside = int(np.searchsorted(want[0][2], 258 * 1024)) + 100
+    assert want[0][2][inside - 1] // 1024 == 258 == want[0][2][inside] // 1024
+    for cap in (max(len(x[0]) for x in want) + 3, inside):
+        xyz, _, pix, cnt = _run_cloud(ctx, torch, disp, valid, None, plans, 16, cap)
+        for i in range(2):
+            wx, _, wp = want[i]
+            k = min(len(wx), cap)
+            assert cnt[i] == len(wx), (cap, i)
+            assert xyz[i, :k].tobytes() == wx[:k].tobytes() and np.array_equal(pix[i, :k], wp[:k]) and (np.diff(pix[i, :k]) > 0).all()
+            assert (xyz[i, k:] == -7.0).all() and (pix[i, k:] == -7).all()
 
 
 def test_cloud_with_a_registration_failed_pairs_and_no_image(ctx, types):

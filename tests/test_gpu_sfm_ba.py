@@ -309,3 +309,22 @@ def test_refusals_through_the_c_abi(ctx, pkg, batch):
         assert bool((t.view(torch.uint8) == 0xA5).all())
     ctx.sfm_ba_device(*good)                                   # and the unchanged arguments run
     assert int(job.results()["ba_summary"]["n_tracks_used"][0]) == 40
+    # the one-shot: a match range that ends past 2^40 is refused before match_off + m is formed (2^63 - 2 with m = 5 does not fit 64
+    # bits); straight to the C call, every pointer good, and the unchanged records run
+    past, wraps = c["pairs"].copy(), c["pairs"].copy()
+    past["match_off"][1], past["m"][1] = 2 ** 40 - 4, 5
+    wraps["match_off"][1], wraps["m"][1] = 2 ** 63 - 2, 5
+    with pytest.raises(pkg.GmsError) as e:
+        pkg.bundleAdjust(c["kp"], c["frame_off"], wraps, c["matches"], c["mask"], c["reg"], c["camera"][:4], c["camera"][4:])
+    assert e.value.code == -1
+    lib, reg = pkg.load_library(), c["reg"]
+    ins = {k: np.ascontiguousarray(v) for k, v in dict(kp=c["kp"], off=c["frame_off"], m=c["matches"], mask=c["mask"], views=reg["views"],
+                                                       reg=reg["registration"], track=reg["track"], cloud=reg["cloud"], ids=reg["cloud_id"]).items()}
+    cap = len(ins["ids"])
+    for recs in (c["pairs"], past, wraps):
+        out = [np.zeros(job.n_frames, pkg.SFM_VIEW_DTYPE), np.zeros((cap, 3)), np.zeros(cap, np.int32), np.zeros(1, pkg.SFM_BA_SUMMARY_DTYPE)]
+        code = lib.gms_sfm_ba(job.camera.ctypes.data, job.params.ctypes.data, ins["kp"].ctypes.data, ins["off"].ctypes.data, job.n_frames,
+                              recs.ctypes.data, len(recs), ins["m"].ctypes.data, ins["mask"].ctypes.data, ins["views"].ctypes.data,
+                              ins["reg"].ctypes.data, ins["track"].ctypes.data, cap, ins["cloud"].ctypes.data, ins["ids"].ctypes.data,
+                              int(reg["summary"]["n_tracks"][0]), *(a.ctypes.data for a in out))
+        assert code == (0 if recs is c["pairs"] else -1) and bool(out[3]["n_tracks_used"][0]) == (recs is c["pairs"])

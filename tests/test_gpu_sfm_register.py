@@ -3,7 +3,20 @@ tests/sfm_register_cases.py against the numpy statement (tests/sfm_register_ref.
 against the device call, pipeline.run_dataset(register=True) on the five-view scene against the statement fed the GPU's own two-view
 records and against the ground truth, batch.SfmRegister in a captured graph, the four photographs, and the refusals of the C ABI.
 Integers are exact; doubles are held to 1e-9 (the tolerance of the two-view tests), relative to the value, or to the size of the vector
-for the entries of a rotation, a translation or a point."""
+for the entries of a rotation, a translation or a point.
+
+The structural edges among the hand-made cases (DESIGN.md §4.10b lists what each reaches and which wrong answers they catch): more
+than 256 pairs, walked from registers (chain_300), with every link's outcome read from global memory (star_300) and every view too,
+and a failure carried across the staging boundary (two_branches_300); more than 256 scan tiles (tiles_past_256, also with a capacity
+that ends below tile 256); link ratios that differ in every byte, an even count, more links than lanes with 200 equal ratios
+(ratio_spread); the first pair out of the root without a model (first_root_pair_fails); device records that do not fit the arrays
+(misfit_records) and plan entries the walk cannot follow (bad_plan_links), which must be ignored.
+
+Still untested: frame offsets on the device that descend or pass total_kp (sfr::pair_fits sees them only in the stand-alone host
+program); the probe sequence of sfr_flatten_kernel wrapping round the end of its hash table; total_kp near 2^31 - 1 and a
+match_off past 2^31 (the arrays would take tens of GB); a median wrong in its lowest three bytes alone, which is 3.7e-9 of its value
+at most and near the 1e-9 the doubles are held to; and a captured graph of more than one staging pass or scan pass (the replay test
+is chain_roles')."""
 import importlib
 import os
 
@@ -13,7 +26,7 @@ import torch
 
 import sfm_register_cases as cases
 import sfm_register_ref as R
-from test_sfm_register_ref import CASE_NAMES, check_against_truth, close, truth_scene
+from test_sfm_register_ref import CASE_NAMES, check_against_truth, check_expect, close, run_ref, truth_scene
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
@@ -52,8 +65,9 @@ def same_registration(got, want, what=""):
     assert close(got["cloud_spread"], want["cloud_spread"], TOL, size), what
 
 
-def want_of(c):
-    return R.register(c["frame_off"], c["pairs"], c["matches"], c["mask"], c["points3d"], c["tv"], c["root"], c["min_links"])
+def want_of(c, **kw):
+    """The statement fed the arrays the device is fed: for the cases of cases.UNFIT the device's records, its plan and the arrays' length."""
+    return run_ref(c, **kw)
 
 
 @pytest.fixture(scope="module")
@@ -67,7 +81,32 @@ def wanted():
     return get
 
 
+def job_of(ctx, batch, c, plan=None, cloud_cap=None):
+    """A loaded batch.SfmRegister on a case, with the cloud capacity the case states. The host's pair list makes the plan, total_m and
+    max_m; a case with `host_pairs` (misfit_records) puts other records on the device through d_pairs, and a case with `plan`
+    (bad_plan_links; or `plan` here) overwrites the device's plan after construction -- and the host's copy, which results() returns."""
+    cap = c.get("cloud_cap") if cloud_cap is None else cloud_cap
+    d_pairs = None
+    if "host_pairs" in c:
+        d_pairs = torch.from_numpy(np.ascontiguousarray(c["pairs"]).view(np.uint8).reshape(-1)).to(f"cuda:{ctx.device}")
+    job = batch.SfmRegister(ctx, c["frame_off"], c.get("host_pairs", c["pairs"]), c["root"], c["min_links"], cap, d_pairs=d_pairs)
+    assert job.total_m == c.get("total_m", job.total_m)
+    plan = c.get("plan") if plan is None else plan
+    if plan is not None:
+        assert plan.dtype == job.plan.dtype and len(plan) == job.n_pairs
+        job.plan = plan.copy()
+        job.d_plan.copy_(torch.from_numpy(np.ascontiguousarray(plan).view(np.uint8).reshape(-1)))
+    job.load(c["matches"], c["mask"], c["points3d"], c["tv"])
+    torch.cuda.synchronize(job.device)
+    return job
+
+
 def device_call(ctx, batch, c, **kw):
+    if "host_pairs" in c or "plan" in c or "plan" in kw:
+        job = job_of(ctx, batch, c, **kw)
+        job.run()
+        return job.results()
+    kw.setdefault("cloud_cap", c.get("cloud_cap"))
     return batch.register_pairs(ctx, c["frame_off"], c["pairs"], c["matches"], c["mask"], c["points3d"], c["tv"], c["root"], c["min_links"], **kw)
 
 
@@ -83,16 +122,63 @@ def test_hand_made_records_equal_the_statement(ctx, batch, wanted, name):
 
 
 def test_the_same_result_run_after_run(ctx, batch):
-    """Every atomic is an integer minimum, maximum or sum: three runs on one object give the same bytes."""
-    c = cases.case("many_links")
-    job = batch.SfmRegister(ctx, c["frame_off"], c["pairs"], c["root"], c["min_links"])
-    job.load(c["matches"], c["mask"], c["points3d"], c["tv"])
-    seen = set()
-    for _ in range(3):
-        job.run()
-        r = job.results()
-        seen.add(b"".join(r[k].tobytes() for k in sorted(r)))
-    assert len(seen) == 1
+    """Every atomic is an integer minimum, maximum or sum: three runs on one object give the same bytes -- also with a walk of two
+    staging passes that reads global memory at every step, and with a scan of two passes."""
+    for name in ("many_links", "two_branches_300", "tiles_past_256"):
+        job = job_of(ctx, batch, cases.case(name))
+        seen = set()
+        for _ in range(3):
+            job.run()
+            r = job.results()
+            seen.add(b"".join(r[k].tobytes() for k in sorted(r)))
+        assert len(seen) == 1, name
+
+
+def test_a_capacity_that_ends_below_tile_256_keeps_the_first_tracks_and_writes_nothing_behind(ctx, batch, wanted):
+    """tiles_past_256 with room for 20 tracks, fewer than its ids below tile 256: n_tracks still counts all 60 (the scan's second pass
+    and its carry), the 20 entries are the statement's first 20, and the cloud arrays -- 64 entries long here -- keep behind them the
+    fill they held before the call."""
+    c, want = cases.case("tiles_past_256"), wanted("tiles_past_256")
+    assert int((want["cloud_id"] // 4096 < 256).sum()) > 20
+    job = job_of(ctx, batch, c, cloud_cap=20)
+    dev = job.device
+    job.d_cloud = torch.full((64 * 3,), -7.0, dtype=torch.float64, device=dev)
+    job.d_cloud_id, job.d_cloud_obs, job.d_cloud_est = (torch.full((64,), -7, dtype=torch.int32, device=dev) for _ in range(3))
+    job.d_cloud_spread = torch.full((64,), -7.0, dtype=torch.float64, device=dev)
+    torch.cuda.synchronize(dev)
+    job.run()
+    got = job.results(trim=False)
+    assert got["summary"].tobytes() == want["summary"].tobytes() and got["summary"]["n_tracks"][0] == 60 and len(got["cloud_id"]) == 20
+    assert np.array_equal(got["cloud_id"], want["cloud_id"][:20]) and np.array_equal(got["cloud_obs"], want["cloud_obs"][:20])
+    assert np.array_equal(got["cloud_est"], want["cloud_est"][:20]) and close(got["cloud"], want["cloud"][:20], TOL, 1.0)
+    assert np.array_equal(got["track"], want["track"][:len(got["track"])])
+    for t in (job.d_cloud[60:], job.d_cloud_id[20:], job.d_cloud_obs[20:], job.d_cloud_est[20:], job.d_cloud_spread[20:]):
+        assert bool((t == -7).all())
+
+
+def test_misfit_records_leave_chain_roles_bytes(ctx, batch):
+    """Beside the comparison with the statement (test_hand_made_records_equal_the_statement): the device's own result on chain_roles
+    comes back byte for byte around the records that do not fit, each of which ends skipped with zeros."""
+    c, base = cases.case("misfit_records"), cases.case("chain_roles")
+    got, plain = device_call(ctx, batch, c), device_call(ctx, batch, base)
+    n0, f0, m0 = c["n_base_pairs"], c["n_base_frames"], len(plain["track"])
+    check_expect(c, got["registration"], c["expect"])
+    assert got["registration"][:n0].tobytes() == plain["registration"].tobytes() and got["views"][:f0].tobytes() == plain["views"].tobytes()
+    assert not got["views"]["registered"][f0:].any() and (got["views"]["pair"][f0:] == -1).all() and not got["views"]["R"][f0:].any()
+    for k in ("cloud", "cloud_id", "cloud_obs", "cloud_est", "cloud_spread", "summary"):
+        assert got[k].tobytes() == plain[k].tobytes(), k
+    assert got["track"][:m0].tobytes() == plain["track"].tobytes() and got["points_world"][:m0].tobytes() == plain["points_world"].tobytes()
+    assert (got["track"][m0:] == -1).all() and not got["points_world"][m0:].any()
+
+
+def test_plan_entries_the_walk_cannot_follow(ctx, batch):
+    """bad_plan_links' further plans (its first is among the hand-made cases): link -2, link n_pairs + 5, and the first pair out of the
+    root with link -2, each against the statement given the same plan and against the stated outcome."""
+    c = cases.case("bad_plan_links")
+    for given, expect in c["more_plans"]:
+        got = device_call(ctx, batch, c, plan=given)
+        same_registration(got, want_of(c, plan=given), "bad plan")
+        check_expect(c, got["registration"], expect)
 
 
 def test_a_small_cloud_capacity_keeps_the_first_tracks(ctx, batch, wanted):
@@ -258,10 +344,22 @@ def test_refusals_through_the_c_abi(ctx, pkg, batch):
     args = dict(frame_off=c["frame_off"], pairs=c["pairs"], matches=c["matches"], mask=c["mask"], points3d=c["points3d"], two_view=c["tv"])
     wrong = c["pairs"].copy()
     wrong["frame_b"][1] = 3
-    for change in (dict(pairs=wrong), dict(root=3), dict(root=-1), dict(min_links=0), dict(cloud_cap=-1)):
+    # ... and a match range that ends past 2^40, refused before match_off + m is formed: 2^63 - 2 with m = 5 does not fit 64 bits
+    past, wraps = c["pairs"].copy(), c["pairs"].copy()
+    past["match_off"][1], past["m"][1] = 2 ** 40 - 4, 5
+    wraps["match_off"][1], wraps["m"][1] = 2 ** 63 - 2, 5
+    for change in (dict(pairs=wrong), dict(root=3), dict(root=-1), dict(min_links=0), dict(cloud_cap=-1), dict(pairs=wraps)):
         with pytest.raises(pkg.GmsError) as e:
             pkg.registerViews(**dict(args, **change))
         assert e.value.code == -1, change
+    api = importlib.import_module("sfm-gms_amd.api")
+    ins = [np.ascontiguousarray(c[k]) for k in ("matches", "mask", "points3d", "tv")]
+    for recs in (c["pairs"], past, wraps):                     # (straight to the C call, every pointer good: the arrays end far before 2^40)
+        o = api.sfm_outputs(len(c["frame_off"]) - 1, len(recs), len(c["mask"]), 10)
+        code = lib.gms_sfm_register(c["frame_off"].ctypes.data, len(c["frame_off"]) - 1, recs.ctypes.data, len(recs), *(a.ctypes.data for a in ins),
+                                    c["root"], c["min_links"], *(o[k].ctypes.data for k in ("views", "registration", "points_world", "track")), 10,
+                                    *(o[k].ctypes.data for k in ("cloud", "cloud_id", "cloud_obs", "cloud_est", "cloud_spread", "summary")))
+        assert code == (0 if recs is c["pairs"] else -1) and bool(o["summary"]["n_ok_pairs"][0]) == (recs is c["pairs"])
     ctx.sfm_register_device(*good)                             # and the unchanged arguments run
     ctx.synchronize()
     assert int(job.results()["summary"]["n_ok_pairs"][0]) == 2

@@ -1,8 +1,11 @@
 """CPU: the registration statement (tests/sfm_register_ref.py) -- a five-view scene with ground-truth poses through the
 CPU two-view chain, hand-made records with analytically known scales (tests/sfm_register_cases.py), the tracks against
 scipy.sparse.csgraph.connected_components, the host build of sfm_register_core.h (tests/cpp/sfm_register_host.cpp) and the C ABI's
-gms_sfm_plan against the Python plan, and the workspace's layout (tests/cpp/sfm_register_layout_check.cpp)."""
+gms_sfm_plan against the Python plan, and the workspace's layout (tests/cpp/sfm_register_layout_check.cpp). The cases whose records
+or plan do not fit (cases.UNFIT) have tests of their own here, and the stand-alone host program hands their records to
+sfr::pair_fits under the sanitizers."""
 import ctypes as C
+import hashlib
 import os
 import subprocess
 
@@ -18,10 +21,20 @@ HOST_SRC = os.path.join(ROOT, "tests", "cpp", "sfm_register_host.cpp")
 LAYOUT_SRC = os.path.join(ROOT, "tests", "cpp", "sfm_register_layout_check.cpp")
 FLAGS = ["-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "sfm-gms_amd", "csrc"), "-I" + os.path.join(ROOT, "include")]
 CASE_NAMES = sorted(cases.CASES)
+SANE_NAMES = [name for name in CASE_NAMES if name not in cases.UNFIT]   # the pair list alone says what the device reads
+# sha256 over the statement's arrays (in the order of their names) on the five cases it was first written for, as it stood before it
+# learnt the kernels' rule for records that do not fit
+STATEMENT_BEFORE = {"chain_roles": "ec0f73ce93fd766d829a932efc01c597e13d1524478d3a488fe7a8023745c612",
+                    "invalid_links_and_min_links": "a17ee900a5c352f5c0292af44edd059efb7c0ae99acb9a34279ed86a25c34b0e",
+                    "lowest_k_wins": "00077c0d6c0cb1be9debacf09121ff6ec41390ffcc828f61ddde158988488db8",
+                    "many_links": "8316f24cc5ce2c7579e88dd32ca0f83351f72a8bb90bf54a608fa6b95dbc93c0",
+                    "upstream_failures": "1b9de0f5f9cb13d41c45eac481a5107628384eaaeeb1099d583e71156e2620fc"}
 
 
-def run_ref(c):
-    return R.register(c["frame_off"], c["pairs"], c["matches"], c["mask"], c["points3d"], c["tv"], c["root"], c["min_links"])
+def run_ref(c, **kw):
+    """The statement on a case: a case that states a plan or the arrays' length (cases.UNFIT) hands them on."""
+    kw = dict({k: c[k] for k in ("plan", "total_m") if k in c}, **kw)
+    return R.register(c["frame_off"], c["pairs"], c["matches"], c["mask"], c["points3d"], c["tv"], c["root"], c["min_links"], **kw)
 
 
 @pytest.fixture(scope="module")
@@ -110,7 +123,7 @@ def test_plan_by_hand():
 
 
 # ---- hand-made records ----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", CASE_NAMES)
+@pytest.mark.parametrize("name", SANE_NAMES)
 def test_hand_made_records_have_the_stated_scales(ref_of, name):
     c, out = cases.case(name), ref_of(name)
     reg = out["registration"]
@@ -155,8 +168,92 @@ def test_many_links_case_is_past_one_pass():
     assert c["tv"]["n_points"].min() > 5000 and c["frame_off"][-1] > 3 * 4096
 
 
+def test_the_statement_without_the_new_arguments_is_unchanged(ref_of):
+    """plan= and total_m= left out: the five cases the statement was written for give the bytes they gave before it had them."""
+    for name, before in STATEMENT_BEFORE.items():
+        out = ref_of(name)
+        assert "plan" not in cases.case(name) and "total_m" not in cases.case(name)
+        assert hashlib.sha256(b"".join(np.ascontiguousarray(out[k]).tobytes() for k in sorted(out))).hexdigest() == before, name
+
+
+def test_the_long_cases_reach_what_they_are_for(ref_of):
+    """Conditions on the inputs and on the statement's outcome that the device tests rely on (DESIGN.md 4.10b names the kernel paths)."""
+    for name in ("chain_300", "star_300", "two_branches_300"):
+        assert len(cases.case(name)["pairs"]) == 300 > 256              # past one staging pass of the walk
+    reg = ref_of("chain_300")["registration"]
+    assert (reg["status"] == 0).all() and reg["depth"].tolist() == list(range(300)) and reg["link"].tolist() == list(range(-1, 299))
+    out = ref_of("chain_300")
+    assert out["summary"]["n_tracks"][0] == 24 and (out["cloud_obs"] == 301).all() and (out["cloud_est"] == 300).all()
+    reg = ref_of("star_300")["registration"]
+    assert (reg["status"] == 0).all() and (reg["link"][1:] == 0).all() and (reg["role"] == 0).all() and reg["depth"].max() == 1
+    c, reg = cases.case("two_branches_300"), ref_of("two_branches_300")["registration"]
+    assert reg["link"].tolist() == [-1, 0] + list(range(298)) and (c["pairs"]["frame_a"][2:] != c["pairs"]["frame_b"][1:-1]).all()
+    assert int((reg["status"] == 0).sum()) == 278 and np.nonzero(reg["status"] == R.GMS_ERR_NO_MODEL)[0].tolist() == list(range(256, 300, 2))
+    # tiles_past_256: more than 256 tiles of 4096 keypoints, and track ids on both sides of tile 256
+    c, out = cases.case("tiles_past_256"), ref_of("tiles_past_256")
+    tile = out["cloud_id"] // 4096
+    assert int(c["frame_off"][-1]) == 1100185 and -(-1100185 // 4096) == 269 and out["summary"]["n_tracks"][0] == 60
+    print("tiles_past_256: ids below tile 256:", int((tile < 256).sum()), "at or past it:", int((tile >= 256).sum()))
+    assert (tile < 256).sum() >= 5 and (tile >= 256).sum() >= 5 and (tile < 256).sum() > 20   # (20: the small capacity of the device test)
+    # ratio_spread: the ratios of each pair differ in every byte above the lowest, and the medians are the true ones
+    reg = ref_of("ratio_spread")["registration"]
+    assert reg["n_links"].tolist() == [0, 41, 40, 257, 63] and np.allclose(reg["r"][1:], [2.5, 0.7, 0.3, 1.7], rtol=1e-12, atol=0)
+    reg = ref_of("first_root_pair_fails")["registration"]
+    assert reg["status"].tolist() == [-8, -8, -8, -8, -8, 1, -8] and reg["role"][[3, 6]].tolist() == [0, 0] and not reg["r"][[3, 6]].any()
+
+
+def check_expect(c, reg, expect):
+    for i, (status, n_links, S) in expect.items():
+        assert reg[i]["status"] == status and (n_links is None or reg[i]["n_links"] == n_links) and abs(reg[i]["S"] - S) <= 1e-12 * S, (i, reg[i])
+        if status == R.GMS_SFM_SKIPPED:                                  # link -1 and zeros
+            assert reg[i].tobytes() == np.array([(0.0, 0.0, 0, 0, -1, 0, R.GMS_SFM_SKIPPED, 0)], R.PAIR_REG_DTYPE).tobytes(), (i, reg[i])
+
+
+def test_misfit_records_are_skipped_and_the_rest_is_chain_roles(ref_of):
+    """The records that do not fit end skipped with zeros, the pair that hangs on one of them has no model, and every other output
+    byte is chain_roles' own. The statement is fed the device's records, the host's plan and the arrays' length."""
+    c, out, base, want = cases.case("misfit_records"), ref_of("misfit_records"), cases.case("chain_roles"), ref_of("chain_roles")
+    n0, f0, m0 = c["n_base_pairs"], c["n_base_frames"], len(base["mask"])
+    assert set(c["expect"]) == set(range(len(c["pairs"]))) and c["total_m"] == len(c["mask"]) and len(c["pairs"]) == n0 + 7
+    assert c["plan"]["registers"][n0:].all() and c["plan"]["link"][n0:].tolist() == [0, 1, 2, 6, 0, 1, n0 + 4]
+    assert [R.pair_fits(p, c["frame_off"], c["total_m"]) for p in c["pairs"]] == [True] * n0 + [False] * 6 + [True]
+    assert all(R.pair_fits(p, c["frame_off"], c["total_m"]) for p in c["host_pairs"])
+    p = c["pairs"][n0:]
+    assert (p["frame_a"][0], p["frame_b"][1], p["m"][2], p["match_off"][3]) == (f0 + 7, -1, -3, -1)
+    assert p["match_off"][4] + p["m"][4] == c["total_m"] + 5 and (c["mask"][-5:] != 0).all() and np.isfinite(c["points3d"][-5:]).all()
+    assert (int(p["match_off"][5]), int(p["m"][5])) == (2 ** 63 - 2, 5)
+    check_expect(c, out["registration"], c["expect"])
+    assert out["registration"][:n0].tobytes() == want["registration"].tobytes() and out["views"][:f0].tobytes() == want["views"].tobytes()
+    blank = np.zeros(7, R.VIEW_DTYPE)
+    blank["pair"] = -1
+    assert out["views"][f0:].tobytes() == blank.tobytes() and out["summary"].tobytes() == want["summary"].tobytes()
+    for k in ("cloud", "cloud_id", "cloud_obs", "cloud_est", "cloud_spread"):
+        assert out[k].tobytes() == want[k].tobytes(), k
+    assert out["track"][:m0].tobytes() == want["track"].tobytes() and out["points_world"][:m0].tobytes() == want["points_world"].tobytes()
+    assert (out["track"][m0:] == -1).all() and not out["points_world"][m0:].any()
+    with pytest.raises(ValueError):                                      # the pair list's own plan refuses these records: one must be given
+        run_ref(c, plan=None)
+
+
+def test_bad_plan_links_are_skipped_and_take_their_descendants(ref_of):
+    """A registering entry whose link is the pair itself, a later pair, below -1 or past the list: skipped with zeros; what hangs on
+    it has no model; what does not is chain_roles' own."""
+    c, want = cases.case("bad_plan_links"), ref_of("chain_roles")["registration"]
+    n = len(c["pairs"])
+    assert c["plan"]["link"][[1, 2]].tolist() == [1, 2 + 2] and c["more_plans"][0][0]["link"][[1, 6]].tolist() == [-2, n + 5]
+    for given, expect in [(c["plan"], c["expect"])] + c["more_plans"]:
+        assert set(expect) == set(range(n))
+        out = run_ref(c, plan=given)
+        assert out["plan"].tobytes() == given.tobytes()
+        check_expect(c, out["registration"], expect)
+        for i, (status, _, _) in expect.items():
+            if status == 0:
+                assert out["registration"][i].tobytes() == want[i].tobytes(), i
+        assert out["summary"]["n_ok_pairs"][0] == sum(1 for e in expect.values() if e[0] == 0)
+
+
 # ---- tracks ---------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", CASE_NAMES)
+@pytest.mark.parametrize("name", SANE_NAMES)
 def test_tracks_against_scipy(ref_of, name):
     from scipy.sparse import coo_matrix
     from scipy.sparse.csgraph import connected_components
@@ -174,7 +271,7 @@ def test_tracks_against_scipy(ref_of, name):
         us.append(c["frame_off"][p["frame_a"]] + q[mk])
         vs.append(c["frame_off"][p["frame_b"]] + t[mk])
         est_at.append(o + rank[mk])
-    u, v, at = np.concatenate(us), np.concatenate(vs), np.concatenate(est_at)
+    u, v, at = (np.concatenate(x) if x else np.zeros(0, np.int64) for x in (us, vs, est_at))   # (no ok pair: no edge)
     _, label = connected_components(coo_matrix((np.ones(len(u)), (u, v)), shape=(K, K)), directed=False)
     touched = np.zeros(K, bool)
     touched[u], touched[v] = True, True
@@ -206,8 +303,8 @@ def host(tmp_path_factory):
     subprocess.check_call(["g++", "-O2", *FLAGS, "-shared", "-fPIC", "-o", so, HOST_SRC])
     lib = C.CDLL(so)
     lib.sfr_host_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    lib.sfr_host_register.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                      C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sfr_host_register.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     return lib
 
 
@@ -224,12 +321,16 @@ def close(a, b, rel=1e-12, floor=0.0):
 
 @pytest.mark.parametrize("name", CASE_NAMES)
 def test_host_build_of_the_core_equals_the_statement(host, ref_of, name):
+    """Every case, those of cases.UNFIT with their records, their plan and the arrays' length: the host build applies sfr::pair_fits
+    and sfr::plan_entry_fits as the kernels do."""
     c, want = cases.case(name), ref_of(name)
     n_frames, n_pairs = len(c["frame_off"]) - 1, len(c["pairs"])
     views, reg = np.zeros(n_frames, R.VIEW_DTYPE), np.zeros(n_pairs, R.PAIR_REG_DTYPE)
     world = np.zeros_like(c["points3d"])
     arrs = [np.ascontiguousarray(c[k]) for k in ("frame_off", "pairs", "matches", "mask", "points3d", "tv")]
-    assert host.sfr_host_register(arrs[0].ctypes.data, n_frames, arrs[1].ctypes.data, n_pairs, arrs[2].ctypes.data, arrs[3].ctypes.data,
+    given = np.ascontiguousarray(c["plan"]) if "plan" in c else None
+    assert host.sfr_host_register(arrs[0].ctypes.data, n_frames, arrs[1].ctypes.data, n_pairs, c.get("total_m", len(c["mask"])),
+                                  None if given is None else given.ctypes.data, arrs[2].ctypes.data, arrs[3].ctypes.data,
                                   arrs[4].ctypes.data, arrs[5].ctypes.data, c["root"], c["min_links"], views.ctypes.data, reg.ctypes.data,
                                   world.ctypes.data) == 0
     for f in ("n_links", "depth", "link", "role", "status"):
@@ -280,6 +381,9 @@ def test_stand_alone_host_program_under_sanitizers(tmp_path):
         pytest.skip("this toolchain cannot build with -fsanitize=address,undefined: " + (build.stderr.strip().splitlines() or ["?"])[-1][:200])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and out.stdout.startswith("sfr_host: tiny 0 40 2.000000"), out.stdout + out.stderr
+    # sfr::pair_fits on the records of misfit_records, match_off = 2^63 - 2 with m = 5 among them: a sum of the two would stop the
+    # program here ("signed integer overflow", -fno-sanitize-recover)
+    assert "sfr_host: misfit records, 0 wrong" in out.stdout and "runtime error" not in out.stderr, out.stdout + out.stderr
 
 
 # ---- the workspace's layout -----------------------------------------------------------------------------------------------------------
