@@ -122,16 +122,22 @@ int  gms_ctx_reserve(gms_ctx* ctx, int n_pairs, int max_m, int with_rotation, in
                                          the pair its CU's next workgroup will filter, so that they wait in L2 (-1: never)        */
 #define GMS_QUERY_PREFETCH_AHEAD    7 /* ... how many pairs ahead that pair is (the number of CUs unless GMS_PREFETCH says otherwise) */
 #define GMS_QUERY_STAGGER_TICKS     8 /* first-round start spread of the most recent launch, in 10 ns ticks (0: none)             */
+#define GMS_QUERY_LAST_IDENT        9 /* 1: the byte-matrix kernel ran its identity-query instantiation (match k of a pair is query k, one
+                                         match per keypoint of frame A: what gms_bfmatch_device and cv::BFMatcher::match return)      */
+#define GMS_QUERY_IDENT_MISSES     10 /* pairs that instantiation has had to filter with the generic body so far (a device counter, read
+                                         without waiting: complete for the launches the caller has synchronised with)              */
 int  gms_ctx_query(gms_ctx* ctx, int what, int64_t* value);
 /* Forces one of those choices for the context's later launches (value 0 / 1), or hands it back to the library (-1, the default).
- * Speed only: every variant produces the same bytes. The environment switches GMS_DEAL / GMS_SCALE_PROBE do the same process-wide. */
+ * Speed only: every variant produces the same bytes. The environment switches GMS_DEAL / GMS_SCALE_PROBE / GMS_IDENT do the same process-wide. */
 #define GMS_OPTION_DEAL         1
 #define GMS_OPTION_SCALE_PROBE  2
+#define GMS_OPTION_IDENT        3 /* (GMS_IDENT): identity-query pairs under the default flags. Forced on, every pair is still checked and a
+                                     pair that is not one -- or whose table this context did not build last -- takes the generic body */
 int  gms_ctx_set_option(gms_ctx* ctx, int option, int value);
 
 /* ---- device-resident batch path (throughput API) ---------------------------------------------
  * All d_* pointers are device pointers on the context's device; calls are stream-ordered on the
- * context's stream. gms_normalize_device never synchronises. gms_filter_device does not synchronise or allocate
+ * context's stream. gms_normalize_device does not synchronise (but see the side records below). gms_filter_device does not synchronise or allocate
  * once the shape has been reserved (gms_ctx_reserve); without a reservation it grows its workspaces on first
  * use of a larger shape (one hipStreamSynchronize + hipMalloc then), and returns GMS_ERR_NOT_RESERVED instead
  * if that would have to happen inside a stream capture. Batches of pairs up to 16 384 matches under the
@@ -151,6 +157,19 @@ int  gms_ctx_set_option(gms_ctx* ctx, int option, int value);
 int64_t gms_frame_table_bytes(int64_t total_kp);
 int gms_normalize_device(gms_ctx* ctx, const gms_keypoint* d_kp, const int64_t* d_frame_off,
                          const int32_t* d_wh, int n_frames, int64_t total_kp, float* d_pts);
+/* Beside the table a build fills per-frame side records in a buffer of the CONTEXT (the half-cell histogram of each frame's keypoints
+ * as left points, GMS_SIDE_RECORD_BYTES each): what the filter's identity-query instantiation needs of a pair's frame A. They describe
+ * the context's LATEST build only; table and records carry a stamp (a 64-bit digest of what the records were built from, in the
+ * table's spare bytes: equal tables stay byte-identical), and a table whose stamp is not the records' -- built from other keypoints
+ * by this or another context, at the same address or not -- is filtered by the generic code. The buffer holds 2048 frames from the start; a build of more frames grows it, which
+ * synchronises the device once (a build inside a stream capture that would have to grow it leaves no records instead), and a table of
+ * more than 64 MiB of records gets none.
+ * gms_ctx_read_side_records: diagnostic. Waits for the context's stream and copies the records of the latest build to host memory:
+ * per frame int64 first keypoint, int32 keypoint count, uint32 flags (1: a keypoint outside the parity domain, 2: a half cell above 255
+ * keypoints), uint64 stamp, 8 spare bytes, then 400 dwords -- cell c of the 20 x 20 grid, byte (hx & 1) + 2 (hy & 1) of it the
+ * count of its half cell. *n_frames: how many records there are (0: the latest build left none); at most dst_bytes are written. */
+#define GMS_SIDE_RECORD_BYTES 1632
+int gms_ctx_read_side_records(gms_ctx* ctx, void* dst, size_t dst_bytes, int* n_frames);
 
 /* gms_filter_device: the GMS filter proper (GMSMatcher ctor..getInlierMask..copy-out, DLL@0x180046900,
  * 0x180047dc0, 0x180048630, 0x180048d10, 0x180048340) for n_pairs independent pairs.

@@ -33,8 +33,16 @@ def _check(rc, lib, what):
         raise GmsError(rc, f"{what}: {msg}")
 
 
+# one record of GmsContext.read_side_records (gms_ctx_read_side_records, GMS_SIDE_RECORD_BYTES)
+SIDE_RECORD_DTYPE = np.dtype([("off", "<i8"), ("n", "<i4"), ("flags", "<u4"), ("stamp", "<u8"), ("pad", "<u4", (2,)), ("hist", "<u4", (400,))])
+assert SIDE_RECORD_DTYPE.itemsize == 1632
+
+
 class GmsContext:
     """gms_ctx: one per (process, device). Thread-safe for the one-shot call; stream-ordered batch calls."""
+
+    OPTION_DEAL, OPTION_SCALE_PROBE, OPTION_IDENT = 1, 2, 3  # gms_ctx_set_option
+    QUERY_LAST_IDENT, QUERY_IDENT_MISSES = 9, 10            # gms_ctx_query (the earlier ids: see query)
 
     def __init__(self, device=0):
         self._lib = load_library()
@@ -72,11 +80,14 @@ class GmsContext:
         _check(self._lib.gms_ctx_synchronize(self._h), self._lib, "synchronize")
 
     def set_option(self, option, value):
-        """gms_ctx_set_option: option 1 = deal the matches to the lanes, 2 = probe scale hypotheses; value -1 (library's choice), 0, 1."""
+        """gms_ctx_set_option: option 1 = deal the matches to the lanes, 2 = probe scale hypotheses, 3 = the identity-query instantiation
+        (OPTION_IDENT); value -1 (library's choice), 0, 1."""
         _check(self._lib.gms_ctx_set_option(self._h, int(option), int(value)), self._lib, "gms_ctx_set_option")
 
     def query(self, what):
-        """gms_ctx_query: 1 = last launch dealt, 2 = its scale-probe mask, 3 = its matches per thread, 4 = launches, 5 = CUs, 6 / 7 = touch-ahead grid type / pairs ahead, 8 = last launch's first-round stagger (10 ns ticks)."""
+        """gms_ctx_query: 1 = last launch dealt, 2 = its scale-probe mask, 3 = its matches per thread, 4 = launches, 5 = CUs, 6 / 7 = touch-ahead grid type / pairs ahead, 8 = last launch's first-round stagger (10 ns ticks),
+        9 = last launch ran the identity-query instantiation (QUERY_LAST_IDENT), 10 = pairs that instantiation handed to the generic body so
+        far (QUERY_IDENT_MISSES)."""
         v = C.c_int64(0)
         _check(self._lib.gms_ctx_query(self._h, int(what), C.byref(v)), self._lib, "gms_ctx_query")
         return int(v.value)
@@ -151,6 +162,15 @@ class GmsContext:
     def normalize_device(self, d_kp, d_frame_off, d_wh, n_frames, total_kp, d_pts):
         _check(self._lib.gms_normalize_device(self._h, d_kp, d_frame_off, d_wh, int(n_frames), int(total_kp), d_pts),
                self._lib, "gms_normalize_device")
+
+    def read_side_records(self, max_frames):
+        """gms_ctx_read_side_records (diagnostic): the per-frame side records of the context's latest table build, after waiting for
+        its stream -- SIDE_RECORD_DTYPE, at most max_frames of them (none when that build left none)."""
+        buf = np.zeros(max(int(max_frames), 1), dtype=SIDE_RECORD_DTYPE)
+        n = C.c_int(0)
+        _check(self._lib.gms_ctx_read_side_records(self._h, buf.ctypes.data, int(max_frames) * SIDE_RECORD_DTYPE.itemsize, C.byref(n)),
+               self._lib, "gms_ctx_read_side_records")
+        return buf[: min(int(n.value), int(max_frames))]
 
     def filter_device(self, d_pts, d_frame_off, n_frames, d_pairs, n_pairs, max_m, d_matches, d_out, d_results,
                       d_mask=None, withRotation=False, withScale=False, thresholdFactor=6.0):

@@ -20,6 +20,7 @@ SIGNATURES = {
     "gms_ctx_set_option": (i32, [vp, i32, i32]),
     "gms_frame_table_bytes": (i64, [i64]),
     "gms_normalize_device": (i32, [vp, vp, vp, vp, i32, i64, vp]),
+    "gms_ctx_read_side_records": (i32, [vp, vp, sz, P(i32)]),
     "gms_filter_device": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, i32, i32, dbl, vp, vp, vp]),
     "gms_filter_host_batch": (i32, [vp, vp, vp, vp, i32, vp, i32, vp, i32, i32, dbl, vp, vp]),
     "gms_bf_prepared_bytes": (i64, [i32, i64, i32]),

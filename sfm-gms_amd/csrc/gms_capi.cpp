@@ -74,6 +74,7 @@ namespace {
 //   GMS_STAGGER_US=n     spread of the first dispatch round's start times at 10k matches per pair (0 = off)
 //   GMS_BAND_WS_BYTES=n  budget of the large-pair workspace (default 4 GiB); a batch is filtered in slices that fit it
 //   GMS_DEAL=0|1         never / always deal the matches to the lanes of the byte-matrix kernel (default: what the probe saw)
+//   GMS_IDENT=0|1        never / always try the byte-matrix kernel's identity-query instantiation under the default flags (default: what the probe saw)
 //   GMS_SCALE_PROBE=0|1  never / always bound the finer scale hypotheses' inlier counts first (default: while it pays, see below)
 //   GMS_CHECK_PAIRS=0|1  never / always validate the pair table behind a launch (default: the first launch and every sixteenth)
 //   GMS_PREFETCH=t[,a]   byte-matrix kernel: before grid type t (0..3, default 3; -1 = never) a workgroup touches the match records of
@@ -82,7 +83,7 @@ struct Knobs {
     bool dense_on = true, band_on = true, stream_on = true;
     int probe_nibble = 16;  // which fine right grids (bit 3: 28 x 28, bit 4: 40 x 40) a scale probe tries with four-bit entries first when the probe is forced on
     bool probe_nibble_set = false;  // GMS_PROBE_NIBBLE given: also a limit on what the library chooses by itself
-    int stagger_us = -1, deal = -1, scale_probe = -1, check_pairs = -1;
+    int stagger_us = -1, deal = -1, scale_probe = -1, check_pairs = -1, ident = -1;
     int prefetch_type = 3, prefetch_ahead = 0;
     size_t band_ws_budget = (size_t)4 << 30;
 };
@@ -96,6 +97,7 @@ const Knobs& knobs()
         if (const char* e = std::getenv("GMS_PROBE_NIBBLE")) { v.probe_nibble = (int)std::strtol(e, nullptr, 0) & 24; v.probe_nibble_set = true; }
         if (const char* e = std::getenv("GMS_STAGGER_US")) v.stagger_us = std::atoi(e);
         if (const char* e = std::getenv("GMS_DEAL")) v.deal = std::atoi(e) != 0 ? 1 : 0;
+        if (const char* e = std::getenv("GMS_IDENT")) v.ident = std::atoi(e) != 0 ? 1 : 0;
         if (const char* e = std::getenv("GMS_SCALE_PROBE")) v.scale_probe = std::atoi(e) != 0 ? 1 : 0;
         if (const char* e = std::getenv("GMS_CHECK_PAIRS")) v.check_pairs = std::atoi(e) != 0 ? 1 : 0;
         if (const char* e = std::getenv("GMS_PREFETCH")) {
@@ -191,7 +193,18 @@ struct gms_ctx {
     // moved since the last look, the next 64 launches of large pairs take the 16-bit band / tile kernels instead, then the streamed ones get another try
     uint32_t overflow_seen = 0;
     int stream_penalty = 0;
-    int opt_deal = -1, opt_probe = -1;  // gms_ctx_set_option: -1 = the library's own choice (and the environment switches), 0 / 1 = forced
+    int opt_deal = -1, opt_probe = -1, opt_ident = -1;  // gms_ctx_set_option: -1 = the library's own choice (and the environment switches), 0 / 1 = forced
+    // Identity-query pairs (match k of a pair is query k, one match per keypoint of frame A): the byte-matrix kernel's IDENT instantiation
+    // works from per-frame side records (gms_kernels.h) that every table build of this context fills in `side`; side_stamp says
+    // whether the latest build left any (the stamp that ties them to their table is worked out and compared on the device).
+    // verdict[3]: what the spatial-order probe saw of its sampled pairs (adopted with verdict[0]); verdict[4]: a counter of the pairs
+    // an IDENT launch had to filter with the generic body, read without waiting like verdict[2] -- when it has moved, IDENT is off
+    // until a later probe says otherwise.
+    DevBuf side;
+    int side_frames = 0;
+    uint64_t side_stamp = 0;
+    int use_ident = 0, last_ident = 0;
+    uint32_t ident_misses_seen = 0;
     // Scale hypotheses: the kernels can bound a scale's inlier count before evaluating it (gms_kernel_scales.hip, PROBE) and skip the
     // scale when it cannot win -- a gain when at least half of the probes let a scale skip, a loss otherwise. The kernels count
     // both in probe_stats (device); every sixteenth launch with scale hypotheses probes whatever the verdict and is followed by a
@@ -273,6 +286,34 @@ int grow_pose_ws(gms_ctx* c, size_t bytes, hipStream_t st)
     return GMS_OK;
 }
 
+// A frame table build on stream `st`: normalize_kernel and, behind it, the context's per-frame side records and the stamp that ties them to the table. The records' buffer grows like the filter's workspaces -- never inside a stream capture, and only after everything that may
+// still read the old block has finished; a build that cannot have records (a capture that would have to allocate, more frames than
+// kSideMaxBytes holds) stamps its table 0, and the filter then never takes the identity path on it. The caller holds c->mu.
+int build_frame_table(gms_ctx* c, hipStream_t st, const void* d_kp, int kp_stride_bytes, const int64_t* d_frame_off, const int32_t* d_wh,
+                      int n_frames, int64_t total_kp, float* d_pts)
+{
+    if (total_kp <= 0) return GMS_OK;
+    const size_t need = (size_t)(n_frames > 0 ? n_frames : 0) * sizeof(gms::SideRecord);
+    bool with_side = n_frames > 0 && need <= gms::kSideMaxBytes;
+    if (with_side && need > c->side.cap) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
+            with_side = false;
+        } else {
+            GMS_HIP(hipDeviceSynchronize());  // (earlier filter launches of any stream may still read the old records)
+            GMS_HIP(c->side.reserve(need));
+        }
+    }
+    const uint64_t stamp = with_side ? 1 : 0;  // (records wanted; the stamp itself is worked out on the device: table_stamp_kernel)
+    c->side_stamp = 0;  // (a failed launch leaves no records to use)
+    c->side_frames = 0;
+    GMS_HIP(gms::launch_normalize(d_kp, kp_stride_bytes, d_frame_off, d_wh, n_frames, total_kp, d_pts,
+                                  with_side ? (gms::SideRecord*)c->side.p : nullptr, stamp, st));
+    c->side_stamp = stamp;
+    c->side_frames = with_side ? n_frames : 0;
+    return GMS_OK;
+}
+
 // The filter launches of one call on stream `st`. The caller holds c->mu and has selected the device.
 int filter_launch(gms_ctx* c, hipStream_t st, const float* d_pts, const int64_t* d_frame_off, int n_frames,
                   const gms_pair* d_pairs, int n_pairs, int max_m, const gms_dmatch* d_matches,
@@ -331,8 +372,25 @@ int filter_launch(gms_ctx* c, hipStream_t st, const float* d_pts, const int64_t*
     if (c->verdict_pending && !capturing && hipEventQuery(c->verdict_event) == hipSuccess) {
         c->use_dealt = c->verdict[0] != 0u ? 1 : 0;
         c->use_probe = (int)c->verdict[1];
+        c->use_ident = c->verdict[3] != 0u ? 1 : 0;
         c->verdict_pending = false;
     }
+    if (!capturing) {
+        // pairs an IDENT launch had to hand to the generic body (read without waiting: it only steers which of two bit-identical
+        // instantiations runs): off until a later probe says otherwise
+        const uint32_t now = ((volatile uint32_t*)c->verdict)[4];
+        if (now != c->ident_misses_seen) {
+            c->ident_misses_seen = now;
+            c->use_ident = 0;
+        }
+    }
+    const int force_ident = c->opt_ident >= 0 ? c->opt_ident : knobs().ident;
+    // (only where the context's side records are current; the kernel checks table and records pair by pair whatever is asked for here)
+    p.side = (const gms::SideRecord*)c->side.p;
+    p.side_frames = c->side_frames;
+    p.side_stamp = c->side_stamp;
+    p.ident = (p.dense && kpt && !with_rotation && c->side.p != nullptr && c->side_frames >= 1 && c->side_stamp != 0 &&
+               (force_ident >= 0 ? force_ident != 0 : c->use_ident != 0)) ? 1 : 0;
     const int force_deal = c->opt_deal >= 0 ? c->opt_deal : knobs().deal, force_probe = c->opt_probe >= 0 ? c->opt_probe : knobs().scale_probe;
     const bool scales_matrix = kpt && with_scale && knobs().dense_on;  // (the byte-matrix kernel of the scale hypotheses deals too)
     p.dealt = ((p.dense || scales_matrix) && kpt && (force_deal >= 0 ? force_deal != 0 : c->use_dealt != 0)) ? 1 : 0;
@@ -354,6 +412,7 @@ int filter_launch(gms_ctx* c, hipStream_t st, const float* d_pts, const int64_t*
     {
         void* dflag = nullptr;
         p.overflow_events = hipHostGetDevicePointer(&dflag, c->verdict, 0) == hipSuccess ? (uint32_t*)dflag + 2 : nullptr;
+        p.ident_misses = p.overflow_events ? p.overflow_events + 2 : nullptr;
     }
     if (kpt && with_scale) {
         // the scales finer than 20 x 20 and the 14 x 14 one are probed (2, 3, 4); the measuring launches are left out of stream captures
@@ -373,7 +432,7 @@ int filter_launch(gms_ctx* c, hipStream_t st, const float* d_pts, const int64_t*
         if (!capturing && p.probe_stats == nullptr && (c->dense_launches++ & 15u) == 0u) {  // the spatial-order probe of this batch, for later launches (one verdict event: not beside a measuring launch)
             void* dflag = nullptr;
             GMS_HIP(hipHostGetDevicePointer(&dflag, c->verdict, 0));
-            GMS_HIP(gms::launch_order_probe(p, (uint32_t*)dflag, st));
+            GMS_HIP(gms::launch_order_probe(p, (uint32_t*)dflag, (uint32_t*)dflag + 3, st));
             GMS_HIP(hipEventRecord(c->verdict_event, st));
             c->verdict_pending = true;
         }
@@ -390,7 +449,7 @@ int filter_launch(gms_ctx* c, hipStream_t st, const float* d_pts, const int64_t*
         if (p.dense && !capturing && (c->dense_launches++ & 15u) == 0u) {
             void* dflag = nullptr;
             GMS_HIP(hipHostGetDevicePointer(&dflag, c->verdict, 0));
-            GMS_HIP(gms::launch_order_probe(p, (uint32_t*)dflag, st));
+            GMS_HIP(gms::launch_order_probe(p, (uint32_t*)dflag, (uint32_t*)dflag + 3, st));
             GMS_HIP(hipEventRecord(c->verdict_event, st));
             c->verdict_pending = true;
         }
@@ -421,6 +480,7 @@ int filter_launch(gms_ctx* c, hipStream_t st, const float* d_pts, const int64_t*
         GMS_HIP(gms::launch_filter_big(p, w.mcap, n_wg, (uint32_t*)c->big_ws.p, st));
     }
     c->last_dealt = p.dealt;
+    c->last_ident = p.ident;
     c->last_probe = p.probe_scales | (p.probe_scales ? p.probe_nibble << 8 : 0);
     c->last_kpt = kpt;
     c->last_stagger_ticks = p.stagger_ticks;
@@ -575,8 +635,11 @@ int gms_ctx_create(int device, gms_ctx** out_ctx)
         c->verdict[0] = 0;
         c->verdict[1] = 0x1D | (16 << 8);
         c->verdict[2] = 0;
+        c->verdict[3] = 0;
+        c->verdict[4] = 0;
         GMS_HIP(c->probe_stats.reserve(128));  // [0..13] probe counters (probe_verdict_kernel), [16..23] flag words of the pair-table check
         GMS_HIP(hipMemset(c->probe_stats.p, 0, 128));
+        GMS_HIP(c->side.reserve(2048 * sizeof(gms::SideRecord)));  // (tables of up to 2048 frames are built without growing it)
         GMS_HIP(gms::init_filter_kernels());
         GMS_HIP(gms::init_band_kernels());
         GMS_HIP(gms::init_stream_kernels());
@@ -595,6 +658,7 @@ int gms_ctx_create(int device, gms_ctx** out_ctx)
         if (c->verdict_event) (void)hipEventDestroy(c->verdict_event);
         if (c->verdict) (void)hipHostFree(c->verdict);
         c->probe_stats.release();
+        c->side.release();
         delete c;
         return rc;
     }
@@ -616,7 +680,7 @@ int gms_ctx_destroy(gms_ctx* c)
         (void)hipStreamSynchronize(c->lane[1].stream);
         (void)hipStreamSynchronize(c->lane[2].stream);
         if (c->ws_pending) (void)hipEventSynchronize(c->ws_event);
-        DevBuf* bufs[] = {&c->aux, &c->big_ws, &c->band_ws, &c->partial_ws, &c->pose_ws, &c->probe_stats, &c->tab_kp, &c->tab_pts, &c->tab_small};
+        DevBuf* bufs[] = {&c->aux, &c->big_ws, &c->band_ws, &c->partial_ws, &c->pose_ws, &c->probe_stats, &c->tab_kp, &c->tab_pts, &c->tab_small, &c->side};
         if (c->verdict) (void)hipHostFree(c->verdict);
         for (DevBuf* b : bufs) b->release();
         for (Lane& l : c->lane) {
@@ -656,6 +720,7 @@ int gms_ctx_synchronize(gms_ctx* c)
     if (c->verdict_pending && hipEventQuery(c->verdict_event) == hipSuccess) {  // (recorded on another stream: maybe not yet)
         c->use_dealt = c->verdict[0] != 0u ? 1 : 0;
         c->use_probe = (int)c->verdict[1];
+        c->use_ident = c->verdict[3] != 0u ? 1 : 0;
         c->verdict_pending = false;
     }
     return GMS_OK;
@@ -668,6 +733,7 @@ int gms_ctx_set_option(gms_ctx* c, int option, int value)
     switch (option) {
     case GMS_OPTION_DEAL: c->opt_deal = value; return GMS_OK;
     case GMS_OPTION_SCALE_PROBE: c->opt_probe = value; return GMS_OK;
+    case GMS_OPTION_IDENT: c->opt_ident = value; return GMS_OK;
     default: return GMS_ERR_BAD_ARG;
     }
 }
@@ -685,6 +751,8 @@ int gms_ctx_query(gms_ctx* c, int what, int64_t* value)
     case GMS_QUERY_PREFETCH_TYPE: *value = knobs().prefetch_type; return GMS_OK;
     case GMS_QUERY_PREFETCH_AHEAD: *value = knobs().prefetch_ahead > 0 ? knobs().prefetch_ahead : c->n_cus; return GMS_OK;
     case GMS_QUERY_STAGGER_TICKS: *value = c->last_stagger_ticks; return GMS_OK;
+    case GMS_QUERY_LAST_IDENT: *value = c->last_ident; return GMS_OK;
+    case GMS_QUERY_IDENT_MISSES: *value = (int64_t)((volatile uint32_t*)c->verdict)[4]; return GMS_OK;
     default: return GMS_ERR_BAD_ARG;
     }
 }
@@ -715,7 +783,22 @@ int gms_normalize_device(gms_ctx* c, const gms_keypoint* d_kp, const int64_t* d_
     if (!c || n_frames < 0 || total_kp < 0) return GMS_ERR_BAD_ARG;
     if (total_kp == 0 || n_frames == 0) return GMS_OK;
     if (!d_kp || !d_frame_off || !d_wh || !d_pts) return GMS_ERR_BAD_ARG;
-    return on_ctx(c, [&] { return gms::launch_normalize(d_kp, (int)sizeof(gms_keypoint), d_frame_off, d_wh, n_frames, total_kp, d_pts, c->stream); });
+    std::lock_guard<std::mutex> lock(c->mu);
+    GMS_HIP(hipSetDevice(c->device));
+    return build_frame_table(c, c->stream, d_kp, (int)sizeof(gms_keypoint), d_frame_off, d_wh, n_frames, total_kp, d_pts);
+}
+
+int gms_ctx_read_side_records(gms_ctx* c, void* dst, size_t dst_bytes, int* n_frames)
+{
+    static_assert(sizeof(gms::SideRecord) == GMS_SIDE_RECORD_BYTES, "the public size of a side record");
+    if (!c || !n_frames || (dst_bytes && !dst)) return GMS_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(c->mu);
+    GMS_HIP(hipSetDevice(c->device));
+    GMS_HIP(hipStreamSynchronize(c->stream));
+    *n_frames = c->side_stamp != 0 ? c->side_frames : 0;
+    const size_t bytes = std::min(dst_bytes, (size_t)*n_frames * sizeof(gms::SideRecord));
+    if (bytes) GMS_HIP(hipMemcpy(dst, c->side.p, bytes, hipMemcpyDeviceToHost));
+    return GMS_OK;
 }
 
 int gms_filter_device(gms_ctx* c, const float* d_pts, const int64_t* d_frame_off, int n_frames,
@@ -792,7 +875,7 @@ int gms_match_ctx(gms_ctx* c, const gms_keypoint* kp1, int n1, int w1, int h1,
     const gms_pair* d_pair = (const gms_pair*)(din + offsetof(CallHeader, pair));
     gms_pair_result* d_res = (gms_pair_result*)dout;
     gms_dmatch* d_out = (gms_dmatch*)(dout + sizeof(gms_pair_result));
-    if (nkp) GMS_HIP(gms::launch_normalize(din + off_xy, 8, d_foff, d_wh, 2, (int64_t)nkp, (float*)c->tab_pts.p, st));
+    if (nkp) GMS_TRY(build_frame_table(c, st, din + off_xy, 8, d_foff, d_wh, 2, (int64_t)nkp, (float*)c->tab_pts.p));
     GMS_TRY(filter_launch(c, st, (const float*)c->tab_pts.p, d_foff, 2, d_pair, 1, m, (const gms_dmatch*)(din + off_m),
                           with_rotation, with_scale, threshold_factor, d_out, d_res, nullptr));
     // Staged calls fetch the result record first and then exactly the survivors.
@@ -936,9 +1019,9 @@ int gms_filter_host_batch(gms_ctx* c, const gms_keypoint* kp, const int64_t* fra
             pool.run(jobs);
             jobs.clear();
             GMS_HIP(hipMemcpyAsync(c->tab_kp.p, c->lane[0].hin.p, (size_t)total_kp * 8, hipMemcpyHostToDevice, st));
-            GMS_HIP(gms::launch_normalize(c->tab_kp.p, 8, (const int64_t*)c->tab_small.p,
-                                          (const int32_t*)((char*)c->tab_small.p + align16((size_t)(n_frames + 1) * 8)),
-                                          n_frames, total_kp, (float*)c->tab_pts.p, st));
+            GMS_TRY(build_frame_table(c, st, c->tab_kp.p, 8, (const int64_t*)c->tab_small.p,
+                                      (const int32_t*)((char*)c->tab_small.p + align16((size_t)(n_frames + 1) * 8)),
+                                      n_frames, total_kp, (float*)c->tab_pts.p));
         }
         GMS_HIP(hipStreamSynchronize(st));  // (frame_off / wh are the caller's pageable memory; lane 0's pinned block is reused below)
     }

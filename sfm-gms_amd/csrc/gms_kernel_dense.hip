@@ -519,8 +519,23 @@ static_assert(kDenseLdsBytes < (1u << 18), "an entry offset is 18 bits");
 // byte 3 of a row header is zero at all times (arg-max keys end at bit 21, cellPairs words at bit 8)
 constexpr uint32_t kPZeroByte = 3u;
 
-template <int KPT, int NT, bool DEALT>
-__device__ __forceinline__ bool dense_pair_plain(const FilterParams& p, uint32_t* smem, const int pair_idx, const int tid)
+// What dense_pair_plain returns (workgroup-uniform; unless kPairDone nothing has been written to global memory and the LDS is free)
+constexpr int kPairGeneral = 0;   // the pair has to take the general path
+constexpr int kPairDone = 1;
+constexpr int kPairNotIdent = 2;  // IDENT only: not an identity-query pair of a frame whose side record is current
+
+// IDENT: the instantiation for identity-query pairs -- match k of the list is query k and the list has one match per keypoint of
+// frame A (what a brute-force matcher without cross-check returns; the host picks the instantiation from what order_probe_kernel
+// saw). For such a pair the left half of the binning phase does not depend on the pair: the left code of match k is lcode[k] of
+// frame A, a coalesced global load requested at the top beside the records instead of a staged copy and an LDS gather, and the
+// half-cell histogram is the frame's own, built once per frame by side_records_kernel (gms_kernels.hip) and copied in here
+// (1.6 KB) instead of one returning LDS atomic per match. Only frame B's right codes are staged. Everything is checked per
+// pair -- every thread its own matches' queryIdx, the workgroup m == nA, the table's stamp against the side record's,
+// the record's (off, n) against this call's frame_off: the workgroup's tests before anything is
+// touched, the threads' through a flag word read where the domain flag is read, behind the barriers that follow the staging. A pair
+// that fails returns kPairNotIdent and the kernel runs the generic body on it.
+template <int KPT, int NT, bool DEALT, bool IDENT>
+__device__ __forceinline__ int dense_pair_plain(const FilterParams& p, uint32_t* smem, const int pair_idx, const int tid)
 {
     constexpr int kMcap = KPT * NT;
     constexpr int kChunk = (KPT % 5 == 0) ? 5 : 4;
@@ -535,14 +550,14 @@ __device__ __forceinline__ bool dense_pair_plain(const FilterParams& p, uint32_t
     auto match_of = [&](int k) -> int { return m_base + k * m_stride; };
 
     // the absolute LDS offsets below assume the dynamic segment starts at 0 (no static LDS in the kernels that call this)
-    if ((uint32_t)(uintptr_t)((lds_u32_t*)smem) != 0u) return false;
+    if ((uint32_t)(uintptr_t)((lds_u32_t*)smem) != 0u) return kPairGeneral;
 
     int64_t total_kp;
     const gms_pair pr = load_pair(p.pairs, pair_idx, p, total_kp);  // (and the frame table's header word)
     const int m = pr.m;
     if (p.with_scale || p.with_rotation || p.right_w[0] != kDenseRightW || p.right_h[0] != kDenseRightW || m <= 0 || m > kMcap ||
         pr.frame_a < 0 || pr.frame_a >= p.n_frames || pr.frame_b < 0 || pr.frame_b >= p.n_frames)
-        return false;
+        return kPairGeneral;
     // the frame ranges and, right behind them, the pair's DMatch records: the records do not depend on the ranges, so they travel
     // beside them instead of a round trip later.
     // The records of a thread's first kKeep matches stay in registers from here to the copy-out (all of them up to ten matches per
@@ -550,6 +565,19 @@ __device__ __forceinline__ bool dense_pair_plain(const FilterParams& p, uint32_t
     // 6.67 M fourteen -- with 8 bytes of scratch --, 6.21 M all sixteen with 36); the others are loaded as (queryIdx, trainIdx) alone and
     // the survivors among them are read again at the end.
     const FrameRangeWords fr_words = request_frame_ranges(p.frame_off, pr.frame_a, pr.frame_b);
+    // IDENT: beside the ranges the head of frame A's side record, the table's stamp (in the spare bytes behind the code arrays;
+    // a block without header is left below before the word is looked at) and this thread's dword of the record's histogram. The
+    // addresses are selected, never branched on: all of them are readable whatever the pair turns out to be.
+    uint4 side_h0 = make_uint4(0, 0, 0, 0);
+    uint2 side_h1 = make_uint2(0, 0), tab_stamp = make_uint2(0, 0);
+    uint32_t side_hist = 0;
+    if constexpr (IDENT) {
+        const SideRecord* __restrict__ sr = p.side + min(pr.frame_a, p.side_frames - 1);
+        side_h0 = *reinterpret_cast<const uint4*>(sr);
+        side_h1 = *reinterpret_cast<const uint2*>(&sr->stamp);
+        tab_stamp = *reinterpret_cast<const uint2*>(total_kp >= 0 ? p.pts + 2 * total_kp : p.pts - 2);
+        side_hist = sr->hist[min(tid, kLeftN - 1)];
+    }
     const gms_dmatch* __restrict__ matches = p.matches + pr.match_off;
     constexpr int kKeep = KPT <= 10 ? KPT : (DEALT ? 10 : 12);  // (the dealt instantiation has two registers less to spare)
     uint4 rec[kKeep];
@@ -562,10 +590,23 @@ __device__ __forceinline__ bool dense_pair_plain(const FilterParams& p, uint32_t
     int64_t offA, offB;
     int nA, nB;
     take_frame_ranges(fr_words, offA, nA, offB, nB);
-    if (nA <= 0 || nB <= 0) return false;
-    if (total_kp < 0 || offA + nA > total_kp || offB + nB > total_kp) return false;  // (workgroup-uniform) no header, or frames beyond the table
+    if (nA <= 0 || nB <= 0) return kPairGeneral;
+    if (total_kp < 0 || offA + nA > total_kp || offB + nB > total_kp) return kPairGeneral;  // (workgroup-uniform) no header, or frames beyond the table
     const uint16_t* __restrict__ lcodeA = reinterpret_cast<const uint16_t*>(p.pts + total_kp) + offA;
     const uint16_t* __restrict__ rcodeB = reinterpret_cast<const uint16_t*>(p.pts + total_kp) + total_kp + offB;
+    uint32_t side_flags = 0;
+    if constexpr (IDENT) {
+        // what the workgroup can tell without looking at a match: the records belong to this build of this table, the frame is where it
+        // was, one match per keypoint. Nothing has been touched yet: the generic body starts from scratch.
+        asm volatile("" : "+v"(side_h0.x), "+v"(side_h0.y), "+v"(side_h0.z), "+v"(side_h0.w), "+v"(side_h1.x), "+v"(side_h1.y), "+v"(tab_stamp.x), "+v"(tab_stamp.y));
+        const int64_t side_off = (int64_t)(((uint64_t)(uint32_t)uniform((int)side_h0.y) << 32) | (uint32_t)uniform((int)side_h0.x));
+        const int side_n = uniform((int)side_h0.z);
+        side_flags = (uint32_t)uniform((int)side_h0.w);
+        const uint64_t s_side = ((uint64_t)(uint32_t)uniform((int)side_h1.y) << 32) | (uint32_t)uniform((int)side_h1.x);
+        const uint64_t s_tab = ((uint64_t)(uint32_t)uniform((int)tab_stamp.y) << 32) | (uint32_t)uniform((int)tab_stamp.x);
+        if (p.side_stamp == 0 || s_side == 0 || s_side != s_tab || side_off != offA || side_n != nA || m != nA)
+            return kPairNotIdent;
+    }
 
     uint32_t* nfine32 = smem + kDenseFineOff / 4;   // half-cell histogram: one dword per cell of grid type 1, a byte per half cell
     const uint8_t* nfine8 = reinterpret_cast<const uint8_t*>(nfine32);
@@ -578,21 +619,27 @@ __device__ __forceinline__ bool dense_pair_plain(const FilterParams& p, uint32_t
 #endif
     if (tid < 32) misc[tid] = 0;
     if (tid < 16) trash[tid] = 0;
-    if (tid < kFineN / 4) nfine32[tid] = 0;
+    if (IDENT ? tid < kLeftN : tid < kFineN / 4) nfine32[tid] = IDENT ? side_hist : 0u;  // (IDENT: the frame's own histogram, complete)
 
     // ---- staging: both frames' code words into the still unused matrix area, (twin of dense_pair_rot's; the pair's DMatch records were requested above)
+    //      IDENT: frame B's alone (qA = 0); a thread's left codes come straight from the table, requested behind the staging loads
     const uint32_t phA = (uint32_t)(reinterpret_cast<uintptr_t>(lcodeA) >> 1) & 7u, phB = (uint32_t)(reinterpret_cast<uintptr_t>(rcodeB) >> 1) & 7u;
-    const uint32_t qA = (phA + (uint32_t)nA + 7u) >> 3, qB = (phB + (uint32_t)nB + 7u) >> 3;
+    const uint32_t qA = IDENT ? 0u : (phA + (uint32_t)nA + 7u) >> 3, qB = (phB + (uint32_t)nB + 7u) >> 3;
     const bool staged = (qA + qB) * 16u <= kDenseBytes;
     const uint4* __restrict__ srcA = reinterpret_cast<const uint4*>(lcodeA - phA);
     const uint4* __restrict__ srcB = reinterpret_cast<const uint4*>(rcodeB - phB);
-    constexpr int kStageRegs = 3;
+    constexpr int kStageRegs = IDENT ? 2 : 3;  // (IDENT: 32 KB, 16 384 keypoints of frame B; larger frames finish in the plain loop)
     uint4 tb[kStageRegs];
 #pragma unroll
     for (int i = 0; i < kStageRegs; ++i) {
         const uint32_t j = min((uint32_t)(i * NT + tid), qA + qB - 1u);
         const uint4* src = j < qA ? srcA + j : srcB + (j - qA);
         tb[i] = *src;
+    }
+    uint32_t ca_id[IDENT ? KPT : 1];
+    if constexpr (IDENT) {
+#pragma unroll
+        for (int k = 0; k < KPT; ++k) ca_id[k] = lcodeA[min(match_of(k), nA - 1)];  // (m == nA: the clamp is the records')
     }
     auto query_of = [&](int k) -> uint32_t { return k < kKeep ? rec[k < kKeep ? k : 0].x : qt[k < kKeep ? 0 : k - kKeep].x; };
     auto train_of = [&](int k) -> uint32_t { return k < kKeep ? rec[k < kKeep ? k : 0].y : qt[k < kKeep ? 0 : k - kKeep].y; };
@@ -616,6 +663,22 @@ __device__ __forceinline__ bool dense_pair_plain(const FilterParams& p, uint32_t
         for (uint32_t j = kStageRegs * NT + tid; j < qA + qB; j += NT) d4[j] = *(j < qA ? srcA + j : srcB + (j - qA));
     }
     const uint32_t ldsA = 2u * phA, ldsB = 16u * qA + 2u * phB;  // byte offsets: left code of frame A's keypoint q at ldsA + 2 q
+    // IDENT: the left half of every code word -- [404 * cell : 18 | 0 : 9 | q and the edge bits : 5], kLeftNone for a match that is not
+    // binned whatever its right side says -- and the identity test, IN FRONT of the barrier: a wave whose loads have landed does this
+    // while the others' are still arriving and the vector ALUs are idle (behind the barrier all sixteen waves would share them for it)
+    constexpr uint32_t kLeftNone = 0xFFFFFFFFu;
+    uint32_t lw[IDENT ? KPT : 1];
+    bool moved = false;
+    if constexpr (IDENT) {
+#pragma unroll
+        for (int k = 0; k < KPT; ++k) {
+            const uint32_t c = ca_id[k], cell = c >> kLCellShift;
+            const bool live = match_of(k) < m;
+            const uint32_t qe = (c & 21u) | ((c >> 4) & kPEdgeX) | ((c >> 3) & kPEdgeY);
+            lw[k] = (live & (cell < kLCellNever)) ? ((__umul24(cell, kDenseRow) << kPAtShift) | qe) : kLeftNone;
+            moved |= live & (query_of(k) != (uint32_t)match_of(k));
+        }
+    }
     __syncthreads();
 #ifdef GMS_PHASE_TIMING
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -628,14 +691,22 @@ __device__ __forceinline__ bool dense_pair_plain(const FilterParams& p, uint32_t
     const uint32_t cw_sink = (kDenseTrashOff + 4u * (uint32_t)(lane & 15)) << kPAtShift;  // E = 0, q = 0, no edge bit
     {
         uint32_t ca[KPT], cb[KPT];
-        if (staged) {
+        if constexpr (IDENT) {
 #pragma unroll
-            for (int k = 0; k < KPT; ++k) ca[k] = ldsa_ld16(ldsA + 2u * min(query_of(k), (uint32_t)(nA - 1)));
+            for (int k = 0; k < KPT; ++k) ca[k] = 0;  // (not looked at: lw has what the left code said)
+        }
+        if (staged) {
+            if constexpr (!IDENT) {
+#pragma unroll
+                for (int k = 0; k < KPT; ++k) ca[k] = ldsa_ld16(ldsA + 2u * min(query_of(k), (uint32_t)(nA - 1)));
+            }
 #pragma unroll
             for (int k = 0; k < KPT; ++k) cb[k] = ldsa_ld16(ldsB + 2u * min(train_of(k), (uint32_t)(nB - 1)));
         } else {
+            if constexpr (!IDENT) {
 #pragma unroll
-            for (int k = 0; k < KPT; ++k) ca[k] = lcodeA[min(query_of(k), (uint32_t)(nA - 1))];
+                for (int k = 0; k < KPT; ++k) ca[k] = lcodeA[min(query_of(k), (uint32_t)(nA - 1))];
+            }
 #pragma unroll
             for (int k = 0; k < KPT; ++k) cb[k] = rcodeB[min(train_of(k), (uint32_t)(nB - 1))];
         }
@@ -643,17 +714,28 @@ __device__ __forceinline__ bool dense_pair_plain(const FilterParams& p, uint32_t
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         GMS_STAMP(12);
 #endif
-        bool any_bad = false, spill = false;
+        // IDENT: the left side of a match's test is the frame's (a bad left code anywhere in frame A is in side_flags: every keypoint
+        // is matched), the histogram is in place; what is left per match is the right side, and that the match is where it should be
+        bool any_bad = IDENT && (side_flags & kSideBadLeft) != 0u, spill = false;
 #pragma unroll
         for (int k = 0; k < KPT; ++k) {
             const bool live = match_of(k) < m;
             const uint32_t e0 = cb[k] & kDEMask;
             const uint32_t cell = ca[k] >> kLCellShift;
-            const bool ok = ((int)(query_of(k) < (uint32_t)nA) & (int)(train_of(k) < (uint32_t)nB) & (int)(cell != kLCellBad) & (int)((cb[k] & kRCodeBad) == 0u) & (int)(e0 != 0u)) != 0;
-            const bool binned = live & ok & (cell < kLCellNever);
-            const uint32_t sh = ((ca[k] & 1u) << 3) | ((ca[k] & 4u) << 2);  // (half-cell histogram: twin of dense_pair_rot's)
-            const uint32_t old = ldsa_add_rtn(binned ? kDenseFineOff + 4u * cell : kDenseTrashOff + 4u * (uint32_t)(lane & 7), 1u << sh);
-            spill |= binned & (((old >> sh) & 255u) == 255u);
+            bool ok, binned;
+            if constexpr (IDENT) {
+                ok = ((int)(train_of(k) < (uint32_t)nB) & (int)((cb[k] & kRCodeBad) == 0u) & (int)(e0 != 0u)) != 0;
+                any_bad |= live & !ok;
+                // E into both of its fields of the left word (disjoint bit fields: the sum is the generic body's code word)
+                code[k] = (ok & (lw[k] != kLeftNone)) ? lw[k] + __umul24(e0, (1u << kPAtShift) | (1u << kPEShift)) : cw_sink;
+                continue;
+            } else {
+                ok = ((int)(query_of(k) < (uint32_t)nA) & (int)(train_of(k) < (uint32_t)nB) & (int)(cell != kLCellBad) & (int)((cb[k] & kRCodeBad) == 0u) & (int)(e0 != 0u)) != 0;
+                binned = live & ok & (cell < kLCellNever);
+                const uint32_t sh = ((ca[k] & 1u) << 3) | ((ca[k] & 4u) << 2);  // (half-cell histogram: twin of dense_pair_rot's)
+                const uint32_t old = ldsa_add_rtn(binned ? kDenseFineOff + 4u * cell : kDenseTrashOff + 4u * (uint32_t)(lane & 7), 1u << sh);
+                spill |= binned & (((old >> sh) & 255u) == 255u);
+            }
             any_bad |= live & !ok;
             const uint32_t qe = (ca[k] & 21u) | ((ca[k] >> 4) & kPEdgeX) | ((ca[k] >> 3) & kPEdgeY);
             const uint32_t at1 = __umul24(cell, kDenseRow) + e0;
@@ -661,6 +743,7 @@ __device__ __forceinline__ bool dense_pair_plain(const FilterParams& p, uint32_t
         }
         if (any_bad) misc[8] = 1;
         if (spill) misc[13] = 1;
+        if (IDENT && moved) misc[10] = 1;  // (its own word: the generic body, not the general path, takes the pair)
     }
     GMS_STAMP(13);
     __syncthreads();
@@ -677,11 +760,15 @@ __device__ __forceinline__ bool dense_pair_plain(const FilterParams& p, uint32_t
     }
     __syncthreads();
     GMS_STAMP(2);
+    if (IDENT && misc[10] != 0) {  // a match that is not where the identity says (workgroup-uniform): the left codes were somebody else's
+        __syncthreads();
+        return kPairNotIdent;
+    }
     if (misc[8] != 0) {
         __syncthreads();
-        return false;
+        return kPairGeneral;
     }
-    const bool spilled = misc[13] != 0;
+    const bool spilled = IDENT ? (side_flags & kSideSpill) != 0u : misc[13] != 0;
 
     const bool thr_fast = threshold_fast_ok(p.threshold_factor);
     const uint32_t f2i = dense_factor_sq(p.threshold_factor);
@@ -724,8 +811,12 @@ __device__ __forceinline__ bool dense_pair_plain(const FilterParams& p, uint32_t
             // XCD's L2 when that workgroup asks for them. Late on purpose -- one grid type before the end -- so that only a few
             // CUs' worth of lines sit in the 4 MB at any time (touched at the start of a pair they are evicted before use).
             // (two independent loads, consumed only before the copy-out: nothing waits for them here)
-            if ((uint32_t)tid < pf_lines) pf_sink = pf_base[32u * (uint32_t)tid];
-            if ((uint32_t)tid + NT < pf_lines) pf_sink2 = pf_base[32u * ((uint32_t)tid + NT)];
+            // (sixteen matches per thread, IDENT: the two line addresses are worked out here, not once in front of the
+            //  grid types -- four registers that the loop does not have; 12 to 16 bytes of scratch otherwise)
+            uint32_t pt = (uint32_t)tid;
+            if constexpr (IDENT && KPT > 10) asm volatile("" : "+v"(pt));
+            if (pt < pf_lines) pf_sink = pf_base[32u * pt];
+            if (pt + NT < pf_lines) pf_sink2 = pf_base[32u * (pt + NT)];
         }
         if (!CROWDED && tid < kLeftN) {
             const uint32_t n = dense_nleft_cm(nfine8, tid % kLeftW, tid / kLeftW, gx, gy);
@@ -855,7 +946,7 @@ __device__ __forceinline__ bool dense_pair_plain(const FilterParams& p, uint32_t
     }
     if (status != 0) {
         __syncthreads();
-        return false;
+        return kPairGeneral;
     }
     GMS_STAMP(7);
     if (p.prefetch_type == 4 && pf_lines) {  // (diagnostic setting: as late as possible)
@@ -1014,18 +1105,31 @@ __device__ __forceinline__ bool dense_pair_plain(const FilterParams& p, uint32_t
         r.status = GMS_OK;
         p.results[pair_idx] = r;
     }
-    return true;
+    return kPairDone;
 }
 
-template <int KPT, bool ROT, int NT, bool DEALT>
+// IDENT (default flags only): the identity-query body first; a pair it turns down is counted (p.ident_misses: the host takes launches
+// that meet such pairs off this instantiation) and filtered by the generic body, same workgroup, same launch.
+template <int KPT, bool ROT, int NT, bool DEALT, bool IDENT>
 __global__ void __launch_bounds__(NT)
 filter_kernel_dense(FilterParams p)
 {
+    static_assert(!(ROT && IDENT), "the identity-query body is dense_pair_plain's");
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     first_round_stagger(p);
     bool done;
-    if constexpr (ROT) done = dense_pair_rot<KPT, NT, DEALT>(p, smem, (int)blockIdx.x, (int)threadIdx.x);
-    else done = dense_pair_plain<KPT, NT, DEALT>(p, smem, (int)blockIdx.x, (int)threadIdx.x);
+    if constexpr (ROT) {
+        done = dense_pair_rot<KPT, NT, DEALT>(p, smem, (int)blockIdx.x, (int)threadIdx.x);
+    } else {
+        int r = dense_pair_plain<KPT, NT, DEALT, IDENT>(p, smem, (int)blockIdx.x, (int)threadIdx.x);
+        if constexpr (IDENT) {
+            if (r == kPairNotIdent) {
+                if (threadIdx.x == 0 && p.ident_misses) atomicAdd(p.ident_misses, 1u);
+                r = dense_pair_plain<KPT, NT, DEALT, false>(p, smem, (int)blockIdx.x, (int)threadIdx.x);
+            }
+        }
+        done = r == kPairDone;
+    }
     if (!done) hash_pair<KPT, ROT, NT>(p, smem, (int)blockIdx.x, (int)threadIdx.x);
 }
 
@@ -1061,8 +1165,15 @@ hipError_t launch_filter_dense(const FilterParams& p, int kpt, int n_pairs, size
     return dispatch_kpt_rot(kpt, p.with_rotation != 0, [&](auto k, auto rot) {
         constexpr int KPT = decltype(k)::value;
         constexpr bool ROT = decltype(rot)::value;
-        if (p.dealt) hipLaunchKernelGGL((filter_kernel_dense<KPT, ROT, kThreads, true>), dim3((unsigned)n_pairs), dim3(kThreads), lds, stream, p);
-        else hipLaunchKernelGGL((filter_kernel_dense<KPT, ROT, kThreads, false>), dim3((unsigned)n_pairs), dim3(kThreads), lds, stream, p);
+        if constexpr (!ROT) {
+            if (p.ident && p.side != nullptr && p.side_frames >= 1 && p.side_stamp != 0) {
+                if (p.dealt) hipLaunchKernelGGL((filter_kernel_dense<KPT, false, kThreads, true, true>), dim3((unsigned)n_pairs), dim3(kThreads), lds, stream, p);
+                else hipLaunchKernelGGL((filter_kernel_dense<KPT, false, kThreads, false, true>), dim3((unsigned)n_pairs), dim3(kThreads), lds, stream, p);
+                return hipGetLastError();
+            }
+        }
+        if (p.dealt) hipLaunchKernelGGL((filter_kernel_dense<KPT, ROT, kThreads, true, false>), dim3((unsigned)n_pairs), dim3(kThreads), lds, stream, p);
+        else hipLaunchKernelGGL((filter_kernel_dense<KPT, ROT, kThreads, false, false>), dim3((unsigned)n_pairs), dim3(kThreads), lds, stream, p);
         return hipGetLastError();
     });
 }
@@ -1072,8 +1183,13 @@ hipError_t init_dense_kernels()
     return for_each_kpt_rot([](auto k, auto rot) {
         constexpr int KPT = decltype(k)::value;
         constexpr bool ROT = decltype(rot)::value;
-        const hipError_t e = allow_full_lds(filter_kernel_dense<KPT, ROT, kThreads, false>);
-        return e != hipSuccess ? e : allow_full_lds(filter_kernel_dense<KPT, ROT, kThreads, true>);
+        hipError_t e = allow_full_lds(filter_kernel_dense<KPT, ROT, kThreads, false, false>);
+        if (e == hipSuccess) e = allow_full_lds(filter_kernel_dense<KPT, ROT, kThreads, true, false>);
+        if constexpr (!ROT) {
+            if (e == hipSuccess) e = allow_full_lds(filter_kernel_dense<KPT, false, kThreads, false, true>);
+            if (e == hipSuccess) e = allow_full_lds(filter_kernel_dense<KPT, false, kThreads, true, true>);
+        }
+        return e;
     });
 }
 

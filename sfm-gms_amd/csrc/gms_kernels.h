@@ -23,6 +23,28 @@ constexpr uint32_t kPartialStrideDw = kPartialHeaderDw + 16 * 1024 / 32;
 constexpr uint32_t kTableMagic0 = 0x46534D47u, kTableMagic1 = 0x31424154u;  // "GMSF" "TAB1"
 constexpr int kTableHeaderBytes = 16;
 
+// Per-frame side records: what the byte-matrix kernel's identity-query path (dense_pair_plain<..., IDENT>) needs of frame A and
+// what does not depend on the pair -- the half-cell histogram of ALL the frame's keypoints and two flags. They live in a buffer
+// of the CONTEXT that built the table (side_records_kernel behind normalize_kernel), not in the table: its public size and
+// layout stay what they were. Table and records are tied by a stamp: a 64-bit digest of what the records were built from (every
+// frame's left codes, offset and count: table_stamp_kernel), never 0, which the build writes into the table's 16 spare bytes behind
+// the code arrays (which no kernel interprets) and into every record. Equal tables carry equal bytes whoever built them; a table
+// rebuilt from other keypoints -- by any context, at any address -- no longer matches the records of the build before. The kernel
+// takes the identity path for a pair only when the two stamps agree and the record's (off, n) is the pair's frame A as this
+// call's frame_off describes it.
+struct SideRecord {
+    int64_t off;              // the frame's first keypoint and ...
+    int32_t n;                // ... number of keypoints when the records were built
+    uint32_t flags;           // kSideBadLeft | kSideSpill
+    uint64_t stamp;
+    uint32_t pad[2];
+    uint32_t hist[400];       // the half-cell histogram exactly as dense_pair_plain builds it in LDS: a dword per cell of grid type 1, a byte per half cell
+};
+static_assert(sizeof(SideRecord) == 1632 && sizeof(SideRecord) % 16 == 0, "side records are read in uint4s");
+constexpr uint32_t kSideBadLeft = 1u;   // some left code is kLCellBad (a keypoint outside the parity domain)
+constexpr uint32_t kSideSpill = 2u;     // some half cell holds more than 255 keypoints (a byte of hist has wrapped: hist is void)
+constexpr size_t kSideMaxBytes = (size_t)64 << 20;  // a table of more frames than fit this gets no records (and no identity path)
+
 struct FilterParams {
     const float2* pts;          // normalised keypoints of all frames (the table's points: kTableHeaderBytes behind its start)
     const int64_t* frame_off;   // n_frames + 1
@@ -47,6 +69,11 @@ struct FilterParams {
     uint32_t* overflow_events;  // streamed byte-matrix kernels: a word (pinned host memory) that counts the pairs they had to hand on because an entry left its byte
     int prefetch_type, prefetch_ahead;  // byte-matrix kernel: before grid type prefetch_type a workgroup touches the records of pair + prefetch_ahead (0 = off)
     int dense;                  // try the byte-matrix path first (no scale hypotheses only); the general path is the fallback
+    int ident;                  // byte-matrix kernel, default flags: the identity-query instantiation (side != nullptr, side_frames >= 1, stamp != 0)
+    int side_frames;            // records behind side
+    const SideRecord* side;     // the context's per-frame side records, or nullptr
+    uint64_t side_stamp;        // non-zero: the context's latest table build left side records (the stamp itself is on the device)
+    uint32_t* ident_misses;     // a word (pinned host memory) that counts the pairs the identity instantiation had to filter with the generic body
     double threshold_factor;
     int right_w[5], right_h[5]; // setScale (DLL@0x180048c10): cvRound(20 * ratio[s])
 #ifdef GMS_PHASE_TIMING
@@ -62,8 +89,9 @@ uint32_t   filter_table_slots(int kpt);
 int        filter_region_shift(int kpt);
 size_t     filter_lds_bytes(int kpt, uint32_t table_slots);
 // kp_stride_bytes: 28 = cv::KeyPoint records, 8 = packed (pt.x, pt.y) pairs
+// d_side: n_frames side records to fill behind the table (stamp != 0), or nullptr (stamp 0: the table is marked as having none)
 hipError_t launch_normalize(const void* d_kp, int kp_stride_bytes, const int64_t* d_frame_off, const int32_t* d_wh,
-                            int n_frames, int64_t total_kp, float* d_pts, hipStream_t stream);
+                            int n_frames, int64_t total_kp, float* d_pts, SideRecord* d_side, uint64_t stamp, hipStream_t stream);
 hipError_t launch_filter(const FilterParams& p, int kpt, int n_pairs, hipStream_t stream);
 // what launch_filter and init_filter_kernels dispatch to: the hashed kernel (gms_kernel_hash.hip), the byte-matrix kernel that
 // falls back to it per pair (gms_kernel_dense.hip), and the limits of launch_filter_scales' first kernel (gms_kernel_scales.hip)
@@ -72,7 +100,7 @@ hipError_t launch_filter_dense(const FilterParams& p, int kpt, int n_pairs, size
 hipError_t init_hash_kernels();
 hipError_t init_dense_kernels();
 hipError_t init_scales_kernels();
-hipError_t launch_order_probe(const FilterParams& p, uint32_t* flag, hipStream_t stream);  // *flag: pinned host word
+hipError_t launch_order_probe(const FilterParams& p, uint32_t* flag, uint32_t* ident_flag, hipStream_t stream);  // *flag, *ident_flag: pinned host words
 hipError_t launch_probe_verdict(uint32_t* stats, uint32_t* flag, hipStream_t stream);      // FilterParams::probe_stats -> pinned host word
 // pair-table validation: ranges [match_off, match_off + m) must be disjoint; offenders get GMS_ERR_BAD_ARG in d_results (d_flag: a device word)
 hipError_t launch_check_pairs(const gms_pair* d_pairs, int n_pairs, gms_pair_result* d_results, uint32_t* d_flag, hipStream_t stream);

@@ -81,13 +81,18 @@ __device__ __forceinline__ void keypoint_codes(float2 n, uint16_t& lcode, uint16
 
 __global__ void __launch_bounds__(256)
 normalize_kernel(const char* __restrict__ kp, int kp_stride, const int64_t* __restrict__ frame_off,
-                 const int32_t* __restrict__ wh, int n_frames, int64_t total, float2* __restrict__ pts)
+                 const int32_t* __restrict__ wh, int n_frames, int64_t total, float2* __restrict__ pts, uint64_t stamp)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) {  // the table's header (gms_kernels.h): the kernels read the keypoint count from here
         uint32_t* h = reinterpret_cast<uint32_t*>(pts) - kTableHeaderBytes / 4;
         h[0] = kTableMagic0;
         h[1] = kTableMagic1;
         *reinterpret_cast<int64_t*>(h + 2) = total;
+        // the stamp of the side records that go with this build, in the spare bytes behind the code arrays: 0 = none, until
+        // table_stamp_kernel has worked it out from the finished table
+        uint64_t* tail = reinterpret_cast<uint64_t*>(pts + 2 * total);
+        tail[0] = stamp;
+        tail[1] = 0;
     }
     uint16_t* __restrict__ lcode = reinterpret_cast<uint16_t*>(pts + total);
     uint16_t* __restrict__ rcode = lcode + total;
@@ -115,17 +120,98 @@ normalize_kernel(const char* __restrict__ kp, int kp_stride, const int64_t* __re
     }
 }
 
+// The side record of one frame (gms_kernels.h), one workgroup per frame behind normalize_kernel: the half-cell histogram of the
+// frame's keypoints as LEFT points -- counted the way dense_pair_plain counts a pair's matches, a returning LDS atomic per
+// keypoint whose result catches a byte passing 255 -- and whether some keypoint lies outside the parity domain. What a pair
+// whose match k has queryIdx k for every keypoint of frame A would build for itself, once instead of once per pair.
+__device__ __forceinline__ uint64_t mix64(uint64_t x)  // (splitmix64's finaliser)
+{
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+__global__ void __launch_bounds__(1024)
+side_records_kernel(const int64_t* __restrict__ frame_off, int64_t total, const float2* __restrict__ pts, uint64_t stamp,
+                    SideRecord* __restrict__ side)
+{
+    __shared__ uint32_t s_hist[kLeftN];
+    __shared__ uint32_t s_flags;
+    __shared__ unsigned long long s_sum;
+    const int tid = (int)threadIdx.x, f = (int)blockIdx.x;
+    if (tid < kLeftN) s_hist[tid] = 0;
+    if (tid == 0) s_flags = 0;
+    if (tid == 0) s_sum = 0;
+    __syncthreads();
+    const int64_t off = frame_off[f], end = frame_off[f + 1];
+    const bool inside = off >= 0 && end >= off && end <= total && end - off <= (int64_t)0x7FFFFFFF;
+    const int n = inside ? (int)(end - off) : 0;
+    const uint16_t* __restrict__ lcode = reinterpret_cast<const uint16_t*>(pts + total) + (inside ? off : 0);
+    uint32_t flags = 0;
+    uint64_t sum = 0;  // of a 64-bit mix of every (position, left code) of the frame: whatever the order of the additions
+    for (int i = tid; i < n; i += 1024) {
+        const uint32_t c = lcode[i];
+        sum += mix64(((uint64_t)(uint32_t)i << 16) | c);
+        const uint32_t cell = c >> kLCellShift;
+        if (cell == kLCellBad) flags |= kSideBadLeft;
+        if (cell < (uint32_t)kLeftN) {  // (a cell below kLCellNever is a cell of the grid: keypoint_codes writes no other)
+            const uint32_t sh = ((c & 1u) << 3) | ((c & 4u) << 2);
+            const uint32_t old = atomicAdd(&s_hist[cell], 1u << sh);
+            if (((old >> sh) & 255u) == 255u) flags |= kSideSpill;
+        }
+    }
+    if (flags) atomicOr(&s_flags, flags);
+    if (sum) atomicAdd(&s_sum, (unsigned long long)sum);
+    __syncthreads();
+    SideRecord* __restrict__ r = side + f;
+    if (tid < kLeftN) r->hist[tid] = s_hist[tid];
+    if (tid == 0) {
+        r->off = off;
+        r->n = inside ? n : -1;  // (a frame outside the table equals no pair's frame A)
+        r->flags = s_flags;
+        r->stamp = stamp != 0 ? (uint64_t)s_sum : 0;  // the frame's share; table_stamp_kernel replaces it by the table's stamp
+        r->pad[0] = r->pad[1] = 0;
+    }
+}
+
+// The stamp that ties a table to its side records is a 64-bit digest of what the records were built from -- every frame's left codes,
+// first keypoint and count, and the table's keypoint count --, written behind the table's code arrays and into every record: equal
+// tables carry equal bytes whichever context built them and when, and a table rebuilt from other keypoints, at the same address or
+// not, no longer matches records of the build before (two different tables share a stamp with probability 2^-64). One workgroup.
+__global__ void __launch_bounds__(1024)
+table_stamp_kernel(SideRecord* __restrict__ side, int n_frames, int64_t total, float2* __restrict__ pts)
+{
+    __shared__ unsigned long long s_sum;
+    const int tid = (int)threadIdx.x;
+    if (tid == 0) s_sum = 0;
+    __syncthreads();
+    uint64_t sum = 0;
+    for (int f = tid; f < n_frames; f += 1024) {
+        const SideRecord& r = side[f];
+        sum += mix64(r.stamp ^ mix64(((uint64_t)(uint32_t)f << 32) ^ (uint64_t)r.off) ^ mix64(0x5157ull + (uint64_t)(uint32_t)r.n));
+    }
+    if (sum) atomicAdd(&s_sum, (unsigned long long)sum);
+    __syncthreads();  // (every frame's share has been read: the field is written below)
+    const uint64_t stamp = mix64((uint64_t)s_sum ^ (uint64_t)total) | 1ull;  // never 0
+    for (int f = tid; f < n_frames; f += 1024) side[f].stamp = stamp;
+    if (tid == 0) *reinterpret_cast<uint64_t*>(pts + 2 * total) = stamp;
+}
+
 // Are a batch's matches in spatial order? One small workgroup, launched now and then behind a byte-matrix launch (gms_capi.cpp):
 // sixteen waves look at 64 consecutive matches in the middle of sixteen pairs spread over the batch and count neighbours in the list
 // whose left points share the cell of grid type 1 (random order: 1 in 400; a row-scanning detector or a per-pixel grid: most of them).
 // More than a quarter -> *flag = 1 (a word in pinned host memory the host reads, without waiting, when it picks the DEALT
 // instantiation for later launches). Speed only: either mapping gives the same result.
+// The same samples answer a second question: are these identity-query pairs -- match k of the list is query k, and the list has one
+// match per keypoint of frame A (what a brute-force matcher without cross-check returns)? All of the sampled pairs -> *ident_flag = 1:
+// later launches take the IDENT instantiation, which checks every pair completely itself.
 __global__ void __launch_bounds__(1024)
-order_probe_kernel(FilterParams p, uint32_t* __restrict__ flag)
+order_probe_kernel(FilterParams p, uint32_t* __restrict__ flag, uint32_t* __restrict__ ident_flag)
 {
-    __shared__ uint32_t s_same, s_seen;
+    __shared__ uint32_t s_same, s_seen, s_not_ident;
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_same = s_seen = 0;
+    if (tid == 0) s_same = s_seen = s_not_ident = 0;
     __syncthreads();
     const int pi = (int)(((long long)wave * p.n_pairs) >> 4);
     const gms_pair pr = p.pairs[pi];
@@ -141,13 +227,18 @@ order_probe_kernel(FilterParams p, uint32_t* __restrict__ flag)
         const uint32_t cell = lc >= kLCellNever ? 0x10000u + (uint32_t)lane : lc;  // never binned: equals nobody
         const uint32_t next = (uint32_t)__shfl_down((int)cell, 1);
         const unsigned long long same = __ballot(lane < 63 && cell == next);
+        const unsigned long long moved = __ballot(q != (uint32_t)(start + lane));
         if (lane == 0) {
             atomicAdd(&s_same, (uint32_t)__popcll(same));
             atomicAdd(&s_seen, 63u);
+            if (moved != 0ull || pr.m != nA) atomicAdd(&s_not_ident, 1u);
         }
     }
     __syncthreads();
-    if (tid == 0 && s_seen != 0) *flag = 4u * s_same > s_seen ? 1u : 0u;
+    if (tid == 0 && s_seen != 0) {
+        *flag = 4u * s_same > s_seen ? 1u : 0u;
+        *ident_flag = s_not_ident == 0u ? 1u : 0u;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -303,22 +394,27 @@ hipError_t launch_probe_verdict(uint32_t* stats, uint32_t* flag, hipStream_t str
     return hipGetLastError();
 }
 
-hipError_t launch_order_probe(const FilterParams& p, uint32_t* flag, hipStream_t stream)
+hipError_t launch_order_probe(const FilterParams& p, uint32_t* flag, uint32_t* ident_flag, hipStream_t stream)
 {
     if (p.n_pairs <= 0) return hipSuccess;
-    hipLaunchKernelGGL(order_probe_kernel, dim3(1), dim3(1024), 0, stream, p, flag);
+    hipLaunchKernelGGL(order_probe_kernel, dim3(1), dim3(1024), 0, stream, p, flag, ident_flag);
     return hipGetLastError();
 }
 
 hipError_t launch_normalize(const void* d_kp, int kp_stride_bytes, const int64_t* d_frame_off, const int32_t* d_wh,
-                            int n_frames, int64_t total_kp, float* d_pts, hipStream_t stream)
+                            int n_frames, int64_t total_kp, float* d_pts, SideRecord* d_side, uint64_t stamp, hipStream_t stream)
 {
     if (total_kp <= 0) return hipSuccess;
     int64_t blocks = (total_kp + 255) / 256;
     if (blocks > 8192) blocks = 8192;
+    float2* pts = reinterpret_cast<float2*>(reinterpret_cast<char*>(d_pts) + kTableHeaderBytes);
+    if (d_side == nullptr || n_frames <= 0) stamp = 0;
     hipLaunchKernelGGL(normalize_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, reinterpret_cast<const char*>(d_kp),
-                       kp_stride_bytes, d_frame_off, d_wh, n_frames, total_kp,
-                       reinterpret_cast<float2*>(reinterpret_cast<char*>(d_pts) + kTableHeaderBytes));
+                       kp_stride_bytes, d_frame_off, d_wh, n_frames, total_kp, pts, (uint64_t)0);
+    if (stamp != 0) {
+        hipLaunchKernelGGL(side_records_kernel, dim3((unsigned)n_frames), dim3(1024), 0, stream, d_frame_off, total_kp, pts, stamp, d_side);
+        hipLaunchKernelGGL(table_stamp_kernel, dim3(1), dim3(1024), 0, stream, d_side, n_frames, total_kp, pts);
+    }
     return hipGetLastError();
 }
 
