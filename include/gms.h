@@ -1055,6 +1055,53 @@ int gms_dense_pair(const gms_camera* camera, const gms_stereo_sgm_params* params
                    gms_rectify_plan* plan, uint8_t* rect1, uint8_t* rect2, uint8_t* valid, uint8_t* color, int16_t* disp16, int cap,
                    float* xyz, uint8_t* cloud_color, int32_t* pixel, int32_t* count);
 
+/* ---- the clouds of several pairs fused into one by depth consistency (the library's own step) ----------------------
+ * Stated in csrc/dense_fuse_core.h and in numpy in tests/dense_fuse_ref.py: fp64, only + - * / rint, every sum in one order; the GPU,
+ * a host build of the header and numpy agree byte for byte.
+ *   A source is one pair's output of the dense stage: gms_dense_fuse_src, an array of them in DEVICE memory whose pointers are device
+ *   pointers (the kernels read everything through them when they run, so a captured graph follows new maps and poses). d_color, d_view
+ *   (NULL: identity) and d_reg (NULL: S = 1, ok) are optional. A source is live when its plan's status is GMS_OK, its registration's
+ *   is GMS_OK with S > 0 (or d_reg is NULL), its view is registered (or d_view is NULL), width and height are 1..GMS_WARP_MAX_SIDE and
+ *   0 <= cap <= max_cap. A source that is not live has no points and sees nothing; a live one has n_i = min(*d_count, cap) points.
+ *   look(P, j), P's three float32 widened: p = (G.R P + G.t) / S with source j's view and scale; r = R1 p; r.z <= 0: UNSEEN;
+ *   u = fx (r.x / r.z) + cx, v likewise; (ui, vi) = rint, clamped, NaN -> INT32_MIN; outside the map: UNSEEN (checked before an address
+ *   is formed); valid 0, d16 == filtered16 or d16 < min_disp16: UNSEEN; e = fx B 16 / r.z; |d16 - e| <= tol16: CONSISTENT, else CONFLICT.
+ *   d_neighbors int32 [n_src][n_nb]: entry j of source i is skipped when j < 0, j >= n_src, j == i or source j is not live.
+ *   Per point k < n_i of source i, over its neighbour slots in order: support = 1 + #CONSISTENT, conflict = #CONFLICT, duplicate = some
+ *   CONSISTENT j < i. Kept: not a duplicate and support >= min_support. A rule per point, not a clustering: the lower copy of a
+ *   dropped duplicate is not guaranteed to be kept itself.
+ *   Kept points in source order, then the source's own order; the first fused_cap of them get d_xyz (the source's bits), d_color
+ *   (optional; zeros for a source without colours), d_source, d_index (k), d_support, d_conflict. d_counts int32 [n_src + 1]: kept per
+ *   source, then the total, also beyond fused_cap. Nothing past min(total, fused_cap) is written. No atomic decides a position.
+ * gms_dense_fuse_device: stream-ordered on the context's stream; no allocation, no synchronisation, no readback; capturable (one
+ *   stream, no parallel branches). max_cap bounds every source's cap and sizes the grid (the caps themselves are on the device).
+ *   Refused (GMS_ERR_BAD_ARG, nothing run): n_src outside 1..65535, n_nb outside 1..32, channels not 1 or 3, tol16 < 0,
+ *   min_support < 1, max_cap outside 1..GMS_WARP_MAX_SIDE^2, n_src * max_cap >= 2^31, fused_cap < 0, a NULL or misaligned pointer
+ *   (d_workspace 256 bytes, d_src 8), a workspace below gms_dense_fuse_workspace_bytes (0 for arguments that are refused).
+ * gms_dense_fuse: the same on HOST pointers, synchronous, on the current HIP device: src is a host array whose pointers are host
+ *   pointers; also refuses a source whose width, height or cap is out of range. */
+typedef struct gms_dense_fuse_src {
+    const int16_t*          d_disp16;  /* [height][width]                                            */
+    const uint8_t*          d_valid;   /* [height][width]                                            */
+    const gms_rectify_plan* d_plan;
+    const float*            d_xyz;     /* [cap][3]                                                   */
+    const uint8_t*          d_color;   /* [cap][channels]; optional                                  */
+    const int32_t*          d_count;
+    const gms_sfm_view*     d_view;    /* the view of the pair's frame_a; NULL: identity             */
+    const gms_sfm_pair_reg* d_reg;     /* the pair's registration; NULL: S = 1, ok                   */
+    int32_t width, height;
+    int32_t filtered16, min_disp16;    /* as passed to gms_dense_cloud_device                        */
+    int32_t cap;
+    int32_t reserved;
+} gms_dense_fuse_src;
+size_t gms_dense_fuse_workspace_bytes(int n_src, int max_cap);
+int gms_dense_fuse_device(gms_ctx* ctx, const gms_dense_fuse_src* d_src, int n_src, int max_cap, const int32_t* d_neighbors, int n_nb,
+                          int channels, int tol16, int min_support, void* d_workspace, size_t workspace_bytes, int fused_cap, float* d_xyz,
+                          uint8_t* d_color, int32_t* d_source, int32_t* d_index, uint8_t* d_support, uint8_t* d_conflict, int32_t* d_counts);
+int gms_dense_fuse(const gms_dense_fuse_src* src, int n_src, const int32_t* neighbors, int n_nb, int channels, int tol16, int min_support,
+                   int fused_cap, float* xyz, uint8_t* color, int32_t* source, int32_t* index, uint8_t* support, uint8_t* conflict,
+                   int32_t* counts);
+
 /* ---- camera calibration from chessboard photographs (main.cpp:53-68, CalibrationUtil.cpp:3-53) ---------------------
  * The corner finder is THIS LIBRARY'S OWN definition, not OpenCV's quad-based findChessboardCorners; cornerSubPix restates OpenCV
  * 4.5.2's algorithm in fp64; calibrateCamera follows its structure. Parity with an OpenCV build is unpinned. tests/calib_ref.py states

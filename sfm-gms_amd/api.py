@@ -15,7 +15,7 @@ from .capi import load_library
 from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, LOGOS_DICT_RESULT_DTYPE, KEYPOINT_DTYPE, PAIR_DTYPE, RESULT_DTYPE, GMS_OK, GMS_ERR_CAPACITY,
                     GmsError, SFM_PAIR_REG_DTYPE, SFM_PLAN_DTYPE, SFM_SUMMARY_DTYPE, SFM_VIEW_DTYPE, TWO_VIEW_DTYPE, concat_frames, desc_layout,
                     portrait_params, stereo_bm_params, stereo_sgm_params, GMS_ERR_BAD_ARG, RECTIFY_PLAN_DTYPE, STEREO_SGM_DENSE, RectifyPlan,
-                    make_camera, rectify_plan_records)
+                    make_camera, rectify_plan_records, DENSE_FUSE_SRC_DTYPE, dense_fuse_neighbors, sfm_view_record, sfm_pair_reg_record)
 
 
 def _as(arr, dtype, name):
@@ -524,6 +524,18 @@ class GmsContext:
                                                 d_color or None, d_disp16 or None, int(cap), d_xyz or None, d_cloud_color or None,
                                                 d_pixel or None, d_count or None), self._lib, "gms_dense_pairs_device")
 
+    # -- the clouds of several pairs fused into one (batch.DenseFuse drives these) --------------------------------------
+    def dense_fuse_workspace_bytes(self, n_src, max_cap):
+        return int(self._lib.gms_dense_fuse_workspace_bytes(int(n_src), int(max_cap)))
+
+    def dense_fuse_device(self, d_src, n_src, max_cap, d_neighbors, n_nb, channels, tol16, min_support, d_ws, ws_bytes, fused_cap, d_xyz, d_color,
+                          d_source, d_index, d_support, d_conflict, d_counts):
+        """gms_dense_fuse_device on raw device pointers: d_src DENSE_FUSE_SRC_DTYPE records on the device. Stream-ordered."""
+        _check(self._lib.gms_dense_fuse_device(self._h, d_src or None, int(n_src), int(max_cap), d_neighbors or None, int(n_nb), int(channels),
+                                               int(tol16), int(min_support), d_ws or None, int(ws_bytes), int(fused_cap), d_xyz or None,
+                                               d_color or None, d_source or None, d_index or None, d_support or None, d_conflict or None,
+                                               d_counts or None), self._lib, "gms_dense_fuse_device")
+
     # -- chessboard corner candidates and cornerSubPix (DESIGN.md 4.12; batch.ChessCorners drives these) ---------------------------------
     def chess_candidates_workspace_bytes(self, width, height, n_images):
         return int(self._lib.gms_chess_candidates_workspace_bytes(int(width), int(height), int(n_images)))
@@ -810,10 +822,15 @@ def structureFromMotionMulti(images, camera, dist=None, method="gms", pairs=None
     two_view, points3d, ... per pair, and views, registration, points_world, track, cloud, cloud_obs, cloud_est, cloud_spread, summary.
     A pair without a pose does not raise here: its registration status says so, and the frames behind it stay unregistered.
     bundle=True: bundle adjustment behind the registration (gms_sfm_ba_device; its keywords n_iters, n_cg, lambda0, cg_tol, ftol,
-    huber_px, retriangulate among params) adds views_ba, cloud_ba, track_status and ba_summary; bundle=False returns the dict without."""
+    huber_px, retriangulate among params) adds views_ba, cloud_ba, track_status and ba_summary; bundle=False returns the dict without.
+    dense=True among params adds `dense`, one cloud per pair in the root's frame; fuse=True beside it (fuse_tol16, fuse_min_support,
+    fuse_cap: run_images') adds `dense_fused`, those clouds fused into one by depth consistency; fuse=True without
+    dense=True raises ValueError."""
     from . import pipeline
     if method not in pipeline.METHODS:
         raise ValueError(f"unknown method {method!r}")
+    if params.get("fuse") and not params.get("dense"):
+        raise ValueError("fuse=True needs dense=True: the fusion reads the pairs' dense clouds")
     stack, _ = pipeline.image_stack(images)
     n = stack.shape[0]
     if pairs is None:
@@ -1141,6 +1158,64 @@ def denseStereo(img1, img2, camera, dist, R, t, min_disp16=16, out_size=None, ca
     k = min(int(count[0]), cap)
     return dict(points=xyz[:k], colors=cc[:k] if c == 3 else cc[:k, 0], pixel=pixel[:k], disp16=disp16, rect1=color if c == 3 else rect1,
                 rect2=rect2, valid=valid, plan=RectifyPlan(out_plan, cam), count=int(count[0]))
+
+
+def denseFuse(sources, neighbors=None, tol16=16, min_support=1, fused_cap=None):
+    """The clouds of several posed pairs fused into one by depth consistency (gms_dense_fuse on host arrays). A point
+    of source i is looked up in each neighbour j: moved into j's rectified camera 1 and compared with the disparity j's own map
+    holds at the pixel it falls on (nearest pixel; within tol16 sixteenths of a pixel: CONSISTENT, else CONFLICT; no valid disparity
+    there, outside the map or behind the camera: UNSEEN). support = 1 + the consistent neighbours, conflict = the conflicting ones; a
+    point is dropped when a consistent neighbour has a lower index (that source owns it) or support < min_support. A rule per point,
+    not a clustering: the lower copy of a dropped point is not guaranteed to be kept. Positions are not averaged.
+    sources: dicts of disp16 int16 [H, W], valid uint8 [H, W], plan (a RectifyPlan or a 200-byte record), points float32 [cap, 3],
+    filtered16 (the matcher's FILTERED code, (min_disparity - 1) * 16; default -16), min_disp16 (default 16), and optionally colors
+    uint8 [cap] or [cap, 3], count (default cap), view ((R, t) of the pair's frame_a, x_camera = R x_world + t, or an SFM_VIEW_DTYPE
+    record; default identity) and reg ((S, status) or an SFM_PAIR_REG_DTYPE record; default S = 1, ok) -- what denseStereo returns
+    holds the first four. neighbors: types.dense_fuse_neighbors' table (default every other source; more than 33 sources need one).
+    Returns a dict: points float32 [k, 3], colors uint8 [k] or [k, 3], source, index int32 [k] (the source and the point's index in
+    it), support, conflict uint8 [k], counts int32 [n + 1] (kept per source, then the total, also beyond fused_cap)."""
+    n = len(sources)
+    if n < 1:
+        raise ValueError("denseFuse: at least one source")
+    nb = dense_fuse_neighbors(n, neighbors)
+    if int(min_support) < 1 or int(tol16) < 0:
+        raise GmsError(GMS_ERR_BAD_ARG, "denseFuse: min_support >= 1 and tol16 >= 0")
+    tab, keep = np.zeros(n, DENSE_FUSE_SRC_DTYPE), []
+    channels = None
+    for i, s in enumerate(sources):
+        disp, valid = np.ascontiguousarray(s["disp16"], dtype=np.int16), np.ascontiguousarray(s["valid"], dtype=np.uint8)
+        if disp.ndim != 2 or disp.shape != valid.shape:
+            raise ValueError("denseFuse: disp16 and valid [H, W]")
+        xyz = np.ascontiguousarray(s["points"], dtype=np.float32).reshape(-1, 3)
+        plan, count = rectify_plan_records(s["plan"])[:1], np.array([s.get("count", len(xyz))], np.int32)
+        row = [disp, valid, plan, xyz, None, count, None, None]
+        if s.get("colors") is not None:
+            col = np.ascontiguousarray(s["colors"], dtype=np.uint8).reshape(len(xyz), -1)
+            if col.shape[1] not in (1, 3) or channels not in (None, col.shape[1]):
+                raise ValueError("denseFuse: colors uint8 [cap] or [cap, 3], the same for every source that has them")
+            channels, row[4] = col.shape[1], col
+        if s.get("view") is not None:
+            row[6] = sfm_view_record(s["view"])
+        if s.get("reg") is not None:
+            row[7] = sfm_pair_reg_record(s["reg"])
+        keep.append(row)
+        for name, a in zip(DENSE_FUSE_SRC_DTYPE.names[:8], row):
+            tab[name][i] = 0 if a is None else a.ctypes.data
+        tab["width"][i], tab["height"][i], tab["cap"][i] = disp.shape[1], disp.shape[0], len(xyz)
+        tab["filtered16"][i], tab["min_disp16"][i] = int(s.get("filtered16", -16)), int(s.get("min_disp16", 16))
+    c = channels or 1
+    cap = int(tab["cap"].sum()) if fused_cap is None else int(fused_cap)
+    if cap < 0:
+        raise GmsError(GMS_ERR_BAD_ARG, "denseFuse: fused_cap >= 0")
+    k1 = max(cap, 1)
+    xyz, col, src, idx = np.zeros((k1, 3), np.float32), np.zeros((k1, c), np.uint8), np.zeros(k1, np.int32), np.zeros(k1, np.int32)
+    sup, con, counts = np.zeros(k1, np.uint8), np.zeros(k1, np.uint8), np.zeros(n + 1, np.int32)
+    lib = load_library()
+    _check(lib.gms_dense_fuse(tab.ctypes.data, n, nb.ctypes.data, nb.shape[1], c, int(tol16), int(min_support), cap, xyz.ctypes.data, col.ctypes.data,
+                              src.ctypes.data, idx.ctypes.data, sup.ctypes.data, con.ctypes.data, counts.ctypes.data), lib, "gms_dense_fuse")
+    k = min(int(counts[n]), cap)
+    return dict(points=xyz[:k], colors=col[:k] if c == 3 else col[:k, 0], source=src[:k], index=idx[:k], support=sup[:k], conflict=con[:k],
+                counts=counts)
 
 
 def _grey_host(image, who):

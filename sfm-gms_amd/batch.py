@@ -11,7 +11,8 @@ import torch
 from .api import GmsContext, logos_dict_args
 from .types import (BF_RESULT_DTYPE, DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128, GMS_ERR_CAPACITY, KEYPOINT_DTYPE, LOGOS_DICT_RESULT_DTYPE, LOGOS_RESULT_DTYPE, PAIR_DTYPE,
                     RESULT_DTYPE, concat_frames, desc_layout, portrait_params, stereo_bm_params, stereo_sgm_params, CAMERA_DTYPE, GMS_ERR_BAD_ARG, GmsError,
-                    RECTIFY_PLAN_DTYPE, TWO_VIEW_DTYPE, make_camera, rectify_plan_records)
+                    RECTIFY_PLAN_DTYPE, TWO_VIEW_DTYPE, make_camera, rectify_plan_records, DENSE_FUSE_SRC_DTYPE, dense_fuse_neighbors, SFM_VIEW_DTYPE,
+                    SFM_PAIR_REG_DTYPE)
 
 
 def _to_dev(arr, device):
@@ -1009,6 +1010,117 @@ class DensePairs:
                                     self.d_xyz.data_ptr(), self.d_cloud_color.data_ptr(), self.d_pixel.data_ptr(), self.d_count.data_ptr(),
                                     **reg)
         return self.d_count
+
+
+def dense_fuse_sources(run, frame_a=None):
+    """The n fusion sources of a DensePairs run, as dicts of views into its device tensors (nothing is copied): d_disp16, d_valid,
+    d_plan, d_xyz, d_color, d_count, filtered16, min_disp16, and with a registration d_view (the view of the pair's frame_a) and d_reg.
+    frame_a: the pairs' frame_a on the host; default: read from the run's pair table (one readback, when the table is built)."""
+    f16 = (int(np.asarray(run.params).reshape(-1)[0]["min_disparity"]) - 1) * 16
+    if run.reg is not None and frame_a is None:
+        frame_a = run.reg[0].cpu().numpy().reshape(-1).view(PAIR_DTYPE)["frame_a"]
+    out = []
+    for j in range(run.n):
+        s = dict(d_disp16=run.d_disp16[j], d_valid=run.d_valid[j], d_plan=run.d_plans[j], d_xyz=run.d_xyz[j], d_color=run.d_cloud_color[j],
+                 d_count=run.d_count[j:j + 1], filtered16=f16, min_disp16=run.min_disp16, cap=run.cap)
+        if run.reg is not None:
+            a = int(frame_a[j])
+            if not 0 <= a < run.reg[3]:
+                raise ValueError("dense_fuse_sources: a pair's frame_a is not a frame of the registration")
+            s.update(d_view=run.reg[2].reshape(run.reg[3], -1)[a], d_reg=run.reg[1].reshape(run.n, -1)[j])
+        out.append(s)
+    return out
+
+
+class DenseFuse:
+    """Device buffers of gms_dense_fuse_device: the source table and the neighbour table, built and uploaded once,
+    the workspace and the fused cloud (d_xyz [fused_cap, 3], d_color [fused_cap, channels], d_source, d_index, d_support, d_conflict,
+    d_counts [n_src + 1]), so that run() can be repeated or captured into a graph; it is one stream with no parallel branches. The
+    table holds pointers into the sources' tensors, which this object keeps alive: the kernels read maps, plans, points, counts, views
+    and scales when they run, so a run -- or a captured graph -- follows whatever the dense stage and the registration wrote there
+    since. sources: DensePairs objects (every pair of the run, in order) and / or dicts as dense_fuse_sources returns them -- device
+    tensors d_disp16 int16 [H, W], d_valid uint8 [H, W], d_plan (200 bytes), d_xyz float32 [cap, 3], d_count int32 [1]; optional
+    d_color uint8 [cap, channels], d_view (an SFM_VIEW_DTYPE record's bytes; default identity), d_reg (SFM_PAIR_REG_DTYPE; default
+    S = 1, ok), cap (default d_xyz's rows), filtered16 (default -16), min_disp16 (default 16).
+    neighbors: types.dense_fuse_neighbors' table; default every other source, which needs at most 33 sources (ValueError beyond). For
+    j > i the table should list i for j whenever it lists j for i: a one-sided entry lets duplicates survive."""
+
+    def __init__(self, ctx, sources, neighbors=None, channels=1, tol16=16, min_support=1, fused_cap=None, device=None):
+        self.ctx, self.channels, self.tol16, self.min_support = ctx, int(channels), int(tol16), int(min_support)
+        self.sources = []
+        for s in sources:
+            self.sources += dense_fuse_sources(s) if isinstance(s, DensePairs) else [s]
+        self.n = len(self.sources)
+        if self.n < 1:
+            raise ValueError("DenseFuse: at least one source")
+        nb = dense_fuse_neighbors(self.n, neighbors)
+        tab = np.zeros(self.n, DENSE_FUSE_SRC_DTYPE)
+        sizes = dict(d_plan=RECTIFY_PLAN_DTYPE.itemsize, d_view=SFM_VIEW_DTYPE.itemsize, d_reg=SFM_PAIR_REG_DTYPE.itemsize)
+        for i, s in enumerate(self.sources):
+            d, v, xyz = s["d_disp16"], s["d_valid"], s["d_xyz"]
+            if d.dtype != torch.int16 or d.dim() != 2 or v.dtype != torch.uint8 or v.shape != d.shape or xyz.dtype != torch.float32 or \
+                    xyz.dim() != 2 or xyz.shape[1] != 3 or s["d_count"].dtype != torch.int32 or not all(t.is_contiguous() for t in (d, v, xyz)):
+                raise ValueError("DenseFuse: d_disp16 int16 [H, W], d_valid uint8 [H, W], d_xyz float32 [cap, 3], d_count int32, contiguous")
+            col = s.get("d_color")
+            if col is not None and (col.dtype != torch.uint8 or not col.is_contiguous() or col.numel() < xyz.shape[0] * self.channels):
+                raise ValueError("DenseFuse: d_color uint8 [cap, channels], contiguous")
+            for name, size in sizes.items():
+                t = s.get(name)
+                if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() != size):
+                    raise ValueError(f"DenseFuse: {name}: the record's {size} bytes as a contiguous uint8 tensor")
+            if s.get("d_plan") is None:
+                raise ValueError("DenseFuse: d_plan")
+            for name in DENSE_FUSE_SRC_DTYPE.names[:8]:
+                tab[name][i] = 0 if s.get(name) is None else s[name].data_ptr()
+            tab["width"][i], tab["height"][i], tab["cap"][i] = d.shape[1], d.shape[0], int(s.get("cap", xyz.shape[0]))
+            if tab["cap"][i] > xyz.shape[0]:
+                raise ValueError("DenseFuse: cap exceeds d_xyz's rows")
+            tab["filtered16"][i], tab["min_disp16"][i] = int(s.get("filtered16", -16)), int(s.get("min_disp16", 16))
+        self.table = tab
+        self.max_cap = max(int(tab["cap"].max()), 1)
+        self.fused_cap = int(tab["cap"].astype(np.int64).sum()) if fused_cap is None else int(fused_cap)
+        self.ws_bytes = ctx.dense_fuse_workspace_bytes(self.n, self.max_cap)
+        if self.ws_bytes == 0 or self.fused_cap < 0 or self.fused_cap > 2 ** 31 - 1:
+            raise GmsError(GMS_ERR_BAD_ARG, "DenseFuse: the number of sources, their caps or fused_cap outside what gms_dense_fuse_device accepts")
+        dev = _device(ctx, device)
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        k = max(self.fused_cap, 1)
+        self.d_ws = z((self.ws_bytes,), torch.uint8)
+        self.d_src = _to_dev(tab, dev)
+        self.d_neighbors, self.n_nb = torch.from_numpy(nb).to(dev), nb.shape[1]
+        self.d_xyz, self.d_color = z((k, 3), torch.float32), z((k, self.channels), torch.uint8)
+        self.d_source, self.d_index = z((k,), torch.int32), z((k,), torch.int32)
+        self.d_support, self.d_conflict = z((k,), torch.uint8), z((k,), torch.uint8)
+        self.d_counts = z((self.n + 1,), torch.int32)
+        torch.cuda.synchronize(dev)
+
+    def run(self):
+        """gms_dense_fuse_device. Stream-ordered on the context's stream; no allocation, no synchronisation."""
+        self.ctx.dense_fuse_device(self.d_src.data_ptr(), self.n, self.max_cap, self.d_neighbors.data_ptr(), self.n_nb, self.channels, self.tol16,
+                                   self.min_support, self.d_ws.data_ptr(), self.ws_bytes, self.fused_cap, self.d_xyz.data_ptr(),
+                                   self.d_color.data_ptr(), self.d_source.data_ptr(), self.d_index.data_ptr(), self.d_support.data_ptr(),
+                                   self.d_conflict.data_ptr(), self.d_counts.data_ptr())
+        return self.d_counts
+
+    def result(self):
+        """Waits for the context's stream -> the fused cloud on the host: points float32 [k, 3], colors uint8 [k] or [k, 3], source,
+        index int32 [k], support, conflict uint8 [k] with k = min(total, fused_cap), and counts int32 [n_src + 1]."""
+        self.ctx.synchronize()
+        counts = self.d_counts.cpu().numpy()
+        k = min(int(counts[-1]), self.fused_cap)
+        colors = self.d_color[:k].cpu().numpy()
+        return dict(points=self.d_xyz[:k].cpu().numpy(), colors=colors if self.channels == 3 else colors[:, 0],
+                    source=self.d_source[:k].cpu().numpy(), index=self.d_index[:k].cpu().numpy(), support=self.d_support[:k].cpu().numpy(),
+                    conflict=self.d_conflict[:k].cpu().numpy(), counts=counts)
+
+
+def fuse_dense(ctx, runs, neighbors=None, channels=1, tol16=16, min_support=1, fused_cap=None, device=None):
+    """One fused cloud from the outputs of the dense stage: `runs` holds DensePairs objects that have run (all their pairs, run after
+    run, are the sources) or equivalent dicts (DenseFuse). Builds a DenseFuse, runs it once and returns its result()."""
+    job = DenseFuse(ctx, runs, neighbors, channels, tol16, min_support, fused_cap, device)
+    torch.cuda.synchronize(job.d_ws.device)
+    job.run()
+    return job.result()
 
 
 class ChessCorners:

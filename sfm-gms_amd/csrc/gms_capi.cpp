@@ -31,6 +31,7 @@
 #include "stereo_sgm_core.h"
 #include "twoview_core.h"
 #include "rectify_core.h"
+#include "dense_fuse_core.h"
 #include "warp_core.h"
 #include "calib_core.h"
 
@@ -1753,6 +1754,100 @@ int gms_dense_pair(const gms_camera* camera, const gms_stereo_sgm_params* params
         blk.out(xyz, o_xyz, 12 * k);
         blk.out(pixel, o_pix, 4 * k);
         if (cloud_color) blk.out(cloud_color, o_cc, (size_t)channels * k);
+    }
+    return blk.finish();
+}
+
+// ---- the clouds of several pairs fused into one (dense_fuse_kernels.hip, dense_fuse_core.h) ----------------------
+static_assert(sizeof(gms_dense_fuse_src) == 88, "gms_dense_fuse_src: eight pointers and six 32-bit words");
+
+size_t gms_dense_fuse_workspace_bytes(int n_src, int max_cap)
+{
+    if (!fuse::call_args_ok(n_src, max_cap, 1, 1, 0, 1, 0)) return 0;
+    return gms::dense_fuse_ws_bytes(n_src, max_cap);
+}
+
+int gms_dense_fuse_device(gms_ctx* c, const gms_dense_fuse_src* d_src, int n_src, int max_cap, const int32_t* d_neighbors, int n_nb, int channels,
+                          int tol16, int min_support, void* d_ws, size_t ws_bytes, int fused_cap, float* d_xyz, uint8_t* d_color, int32_t* d_source,
+                          int32_t* d_index, uint8_t* d_support, uint8_t* d_conflict, int32_t* d_counts)
+{
+    if (!c || !fuse::call_args_ok(n_src, max_cap, n_nb, channels, tol16, min_support, fused_cap)) return GMS_ERR_BAD_ARG;
+    if (!d_src || !d_neighbors || !d_ws || !d_counts || (fused_cap > 0 && (!d_xyz || !d_source || !d_index || !d_support || !d_conflict)))
+        return GMS_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_ws) & 255u) || (reinterpret_cast<uintptr_t>(d_src) & 7u) || (reinterpret_cast<uintptr_t>(d_neighbors) & 3u) ||
+        (reinterpret_cast<uintptr_t>(d_xyz) & 3u) || (reinterpret_cast<uintptr_t>(d_source) & 3u) || (reinterpret_cast<uintptr_t>(d_index) & 3u) ||
+        (reinterpret_cast<uintptr_t>(d_counts) & 3u) || ws_bytes < gms::dense_fuse_ws_bytes(n_src, max_cap))
+        return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] {
+        return gms::launch_dense_fuse(d_src, n_src, max_cap, d_neighbors, n_nb, channels, tol16, min_support, d_ws, fused_cap, d_xyz, d_color, d_source,
+                                      d_index, d_support, d_conflict, d_counts, c->stream);
+    });
+}
+
+int gms_dense_fuse(const gms_dense_fuse_src* src, int n_src, const int32_t* neighbors, int n_nb, int channels, int tol16, int min_support,
+                   int fused_cap, float* xyz, uint8_t* color, int32_t* source, int32_t* index, uint8_t* support, uint8_t* conflict, int32_t* counts)
+{
+    if (!src || n_src < 1 || n_src > 65535 || !neighbors || !counts || (fused_cap > 0 && (!xyz || !source || !index || !support || !conflict)))
+        return GMS_ERR_BAD_ARG;
+    long long max_cap = 1;
+    for (int i = 0; i < n_src; ++i) {
+        const gms_dense_fuse_src& s = src[i];
+        if (!fuse::shape_ok(s, fuse::kMaxCap) || !s.d_disp16 || !s.d_valid || !s.d_plan || !s.d_count || (s.cap > 0 && !s.d_xyz)) return GMS_ERR_BAD_ARG;
+        if (s.cap > max_cap) max_cap = s.cap;
+    }
+    if (!fuse::call_args_ok(n_src, max_cap, n_nb, channels, tol16, min_support, fused_cap)) return GMS_ERR_BAD_ARG;
+    const size_t ws = gms::dense_fuse_ws_bytes(n_src, (int)max_cap), ucap = (size_t)fused_cap, un = (size_t)n_src;
+    // one block: the table, the neighbours, the workspace, the outputs, then every source's arrays
+    struct Off { size_t disp, valid, plan, xyz, color, count, view, reg; };
+    std::vector<Off> off(un);
+    gms::BlockLayout lay;
+    const size_t o_tab = lay.add(sizeof(gms_dense_fuse_src) * un), o_nb = lay.add(4 * un * (size_t)n_nb), o_ws = lay.add(ws), o_xyz = lay.add(12 * ucap + 4),
+                 o_col = lay.add(3 * ucap + 4), o_src = lay.add(4 * ucap + 4), o_idx = lay.add(4 * ucap + 4), o_sup = lay.add(ucap + 4),
+                 o_con = lay.add(ucap + 4), o_cnt = lay.add(4 * (un + 1));
+    for (size_t i = 0; i < un; ++i) {
+        const gms_dense_fuse_src& s = src[i];
+        const size_t px = (size_t)s.width * (size_t)s.height, cap = (size_t)s.cap;
+        off[i] = {lay.add(2 * px), lay.add(px), lay.add(sizeof(gms_rectify_plan)), lay.add(12 * cap + 4), lay.add(s.d_color ? channels * cap + 4 : 4),
+                  lay.add(4), lay.add(sizeof(gms_sfm_view)), lay.add(sizeof(gms_sfm_pair_reg))};
+    }
+    DevBlock blk(lay, nullptr);
+    std::vector<gms_dense_fuse_src> tab(src, src + n_src);
+    for (size_t i = 0; i < un; ++i) {
+        const gms_dense_fuse_src& s = src[i];
+        const size_t px = (size_t)s.width * (size_t)s.height, cap = (size_t)s.cap;
+        blk.in(off[i].disp, s.d_disp16, 2 * px);
+        blk.in(off[i].valid, s.d_valid, px);
+        blk.in(off[i].plan, s.d_plan, sizeof(gms_rectify_plan));
+        blk.in(off[i].count, s.d_count, 4);
+        if (cap) blk.in(off[i].xyz, s.d_xyz, 12 * cap);
+        if (cap && s.d_color) blk.in(off[i].color, s.d_color, channels * cap);
+        if (s.d_view) blk.in(off[i].view, s.d_view, sizeof(gms_sfm_view));
+        if (s.d_reg) blk.in(off[i].reg, s.d_reg, sizeof(gms_sfm_pair_reg));
+        tab[i].d_disp16 = blk.at<int16_t>(off[i].disp);
+        tab[i].d_valid = blk.at<uint8_t>(off[i].valid);
+        tab[i].d_plan = blk.at<gms_rectify_plan>(off[i].plan);
+        tab[i].d_xyz = blk.at<float>(off[i].xyz);
+        tab[i].d_color = s.d_color ? blk.at<uint8_t>(off[i].color) : nullptr;
+        tab[i].d_count = blk.at<int32_t>(off[i].count);
+        tab[i].d_view = s.d_view ? blk.at<gms_sfm_view>(off[i].view) : nullptr;
+        tab[i].d_reg = s.d_reg ? blk.at<gms_sfm_pair_reg>(off[i].reg) : nullptr;
+    }
+    blk.in(o_tab, tab.data(), sizeof(gms_dense_fuse_src) * un);
+    blk.in(o_nb, neighbors, 4 * un * (size_t)n_nb);
+    blk.run([&](hipStream_t st) {
+        return gms::launch_dense_fuse(blk.at<gms_dense_fuse_src>(o_tab), n_src, (int)max_cap, blk.at<int32_t>(o_nb), n_nb, channels, tol16, min_support,
+                                      blk.at(o_ws), fused_cap, blk.at<float>(o_xyz), color ? blk.at<uint8_t>(o_col) : nullptr, blk.at<int32_t>(o_src),
+                                      blk.at<int32_t>(o_idx), blk.at<uint8_t>(o_sup), blk.at<uint8_t>(o_con), blk.at<int32_t>(o_cnt), st);
+    });
+    blk.out_now(counts, o_cnt, 4 * (un + 1));  // (also waits for the copies in: `tab` is read until then)
+    const size_t k = blk.ok() ? (size_t)(counts[n_src] < fused_cap ? counts[n_src] : fused_cap) : 0;
+    if (k) {
+        blk.out(xyz, o_xyz, 12 * k);
+        if (color) blk.out(color, o_col, (size_t)channels * k);
+        blk.out(source, o_src, 4 * k);
+        blk.out(index, o_idx, 4 * k);
+        blk.out(support, o_sup, k);
+        blk.out(conflict, o_con, k);
     }
     return blk.finish();
 }

@@ -268,6 +268,11 @@ hipError_t launch_dense_cloud(const int16_t* d_disp16, const uint8_t* d_valid, c
                               int n_pairs, int W, int H, const gms_rectify_plan* d_plans, int filtered16, int min_disp16,
                               const gms_pair* d_pairs, const gms_sfm_pair_reg* d_reg, const gms_sfm_view* d_views, int n_frames, void* d_ws,
                               int cap, float* d_xyz, uint8_t* d_color, int32_t* d_pixel, int32_t* d_count, hipStream_t stream);
+// the clouds of several pairs fused into one (dense_fuse_kernels.hip; arithmetic in dense_fuse_core.h; workspace: ws_layout.h DenseFuseLayout)
+size_t     dense_fuse_ws_bytes(int n_src, int max_cap);
+hipError_t launch_dense_fuse(const gms_dense_fuse_src* d_src, int n_src, int max_cap, const int32_t* d_neighbors, int n_nb, int channels, int tol16,
+                             int min_support, void* d_ws, int fused_cap, float* d_xyz, uint8_t* d_color, int32_t* d_source, int32_t* d_index,
+                             uint8_t* d_support, uint8_t* d_conflict, int32_t* d_counts, hipStream_t stream);
 // chessboard corner candidates and cornerSubPix (calib_kernels.hip; arithmetic in calib_core.h; workspace: ws_layout.h ChessLayout)
 size_t     chess_candidates_ws_bytes(int n, int w, int h);
 hipError_t launch_chess_candidates(const uint8_t* d_images, int n, int w, int h, int max_candidates, void* d_ws,

@@ -414,4 +414,21 @@ inline DensePairsLayout dense_pairs_layout(int n, int sw, int sh, int channels, 
             c.take(dense_cloud_layout(n, ow, oh).total, 256), c.end};
 }
 
+// ---- the clouds of several pairs fused into one (dense_fuse_kernels.hip) -------------------------------------------------------------------
+// Every source gets the blocks of max_cap points, source after source: block b of source i is word i * blocks_per_src + b. Every call
+// writes every word it later reads.
+constexpr int kFuseBlockPoints = 1024;  // points per workgroup of the mark and write kernels
+inline int dense_fuse_blocks(int max_cap) { return (int)(((size_t)max_cap + kFuseBlockPoints - 1) / kFuseBlockPoints); }
+struct DenseFuseLayout {
+    size_t blocks;  // int32 [n_src][blocks_per_src]: kept points per block, then in place their exclusive prefix over all blocks
+    size_t marks;   // uint8 [n_src][blocks_per_src * 1024][2]: per point its support byte (0x80: kept) and its conflict count
+    size_t total;
+};
+inline DenseFuseLayout dense_fuse_layout(int n_src, int max_cap)
+{
+    const size_t nb = (size_t)n_src * (size_t)dense_fuse_blocks(max_cap);
+    WsCursor c;
+    return {c.take(4 * nb, 256), c.take(2 * nb * kFuseBlockPoints, 256), c.end};
+}
+
 }  // namespace gms

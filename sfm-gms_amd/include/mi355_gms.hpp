@@ -669,6 +669,86 @@ inline DenseCloud denseStereo(const std::vector<uint8_t>& img1, const std::vecto
     return out;
 }
 
+// ---- the clouds of several posed pairs fused into one by depth consistency --------------------------------------------
+// A source is one pair's output of the dense stage (what denseStereo returns holds plan, points, colors, disp16 and valid), with the
+// view of the pair's frame_a (x_camera = R x_world + t) and the pair's registration when the clouds were made in a world frame.
+// fuseDense runs gms_dense_fuse on them, synchronously on the current HIP device: a point is kept once, by the lowest source whose own
+// map agrees with it, with the number of sources that agree (support) and disagree (conflict). neighbors: [n][n_nb] source indices
+// (-1: empty), empty: every other source, which needs at most 33 sources. fused_cap < 0: room for all.
+struct FuseSource {
+    gms_rectify_plan plan{};
+    int width = 0, height = 0;      // the maps' size; 0: plan.out_w, plan.out_h
+    std::vector<int16_t> disp16;    // [height][width]
+    std::vector<uint8_t> valid;     // [height][width]
+    std::vector<float> points;      // [cap][3]
+    std::vector<uint8_t> colors;    // [cap][channels], or empty
+    int32_t count = -1;             // < 0: every point of `points`
+    int filtered16 = -16, min_disp16 = 16;
+    bool has_view = false, has_reg = false;
+    gms_sfm_view view{};
+    gms_sfm_pair_reg reg{};
+};
+struct FusedCloud {
+    std::vector<float> points;      // [k][3]
+    std::vector<uint8_t> colors;    // [k][channels]
+    std::vector<int32_t> source, index;   // [k]: the source and the point's index in it
+    std::vector<uint8_t> support, conflict;
+    std::vector<int32_t> counts;    // [n + 1]: kept per source, then the total (also beyond fused_cap)
+};
+
+inline FusedCloud fuseDense(const std::vector<FuseSource>& sources, int channels = 1, int tol16 = 16, int min_support = 1, long long fused_cap = -1,
+                            const std::vector<int32_t>& neighbors = {}, int n_nb = 0)
+{
+    const size_t n = sources.size();
+    if (n == 0) throw std::runtime_error("mi355::fuseDense: at least one source");
+    std::vector<int32_t> nb = neighbors;
+    if (nb.empty()) {
+        if (n > 33) throw std::runtime_error("mi355::fuseDense: more than 33 sources need a neighbour table");
+        n_nb = n > 1 ? (int)n - 1 : 1;
+        nb.assign(n * (size_t)n_nb, -1);
+        for (size_t i = 0; i < n; ++i)
+            for (size_t j = 0, q = 0; j < n; ++j)
+                if (j != i) nb[i * (size_t)n_nb + q++] = (int32_t)j;
+    }
+    if (n_nb < 1 || nb.size() != n * (size_t)n_nb) throw std::runtime_error("mi355::fuseDense: neighbors: [n][n_nb]");
+    std::vector<gms_dense_fuse_src> tab(n);
+    std::vector<int32_t> counts_in(n);
+    long long total_cap = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const FuseSource& s = sources[i];
+        const int w = s.width > 0 ? s.width : s.plan.out_w, h = s.height > 0 ? s.height : s.plan.out_h;
+        const size_t px = (size_t)(w > 0 ? w : 0) * (size_t)(h > 0 ? h : 0), cap = s.points.size() / 3;
+        if (px == 0 || s.disp16.size() != px || s.valid.size() != px || s.points.size() != 3 * cap ||
+            (!s.colors.empty() && s.colors.size() != (size_t)channels * cap))
+            throw std::runtime_error("mi355::fuseDense: a source's arrays do not fit its size");
+        counts_in[i] = s.count < 0 ? (int32_t)cap : s.count;
+        tab[i] = {s.disp16.data(), s.valid.data(), &s.plan, s.points.data(), s.colors.empty() ? nullptr : s.colors.data(), &counts_in[i],
+                  s.has_view ? &s.view : nullptr, s.has_reg ? &s.reg : nullptr, w, h, s.filtered16, s.min_disp16, (int32_t)cap, 0};
+        total_cap += (long long)cap;
+    }
+    const long long k = fused_cap < 0 ? total_cap : fused_cap;
+    if (k > 2147483647LL) throw std::runtime_error("mi355::fuseDense: fused_cap");
+    FusedCloud out;
+    out.points.assign(3 * (size_t)k + 3, 0.f);
+    out.colors.assign((size_t)channels * (size_t)k + 3, 0);
+    out.source.assign((size_t)k + 1, 0);
+    out.index.assign((size_t)k + 1, 0);
+    out.support.assign((size_t)k + 1, 0);
+    out.conflict.assign((size_t)k + 1, 0);
+    out.counts.assign(n + 1, 0);
+    const int rc = gms_dense_fuse(tab.data(), (int)n, nb.data(), n_nb, channels, tol16, min_support, (int)k, out.points.data(), out.colors.data(),
+                                  out.source.data(), out.index.data(), out.support.data(), out.conflict.data(), out.counts.data());
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::fuseDense: ") + gms_error_string(rc));
+    const size_t kept = (size_t)(out.counts[n] < k ? out.counts[n] : k);
+    out.points.resize(3 * kept);
+    out.colors.resize((size_t)channels * kept);
+    out.source.resize(kept);
+    out.index.resize(kept);
+    out.support.resize(kept);
+    out.conflict.resize(kept);
+    return out;
+}
+
 // ---- camera calibration from chessboard photographs (main.cpp:53-68, CalibrationUtil.cpp:3-53) --------------------------
 // The library's own corner finder (NOT OpenCV's quad-based one), OpenCV 4.5.2's cornerSubPix in fp64, and calibrateCamera with
 // flags = 0, on flat 8-bit grey images (dense rows). Points are doubles, so that nothing is rounded between the steps.

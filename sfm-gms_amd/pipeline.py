@@ -24,7 +24,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from .batch import (BfSelect, DescriptorTable, DetectPyramid, FrameTable, LogosDictionary, LogosFilter, LogosTable, DensePairs, SfmBundle, SfmRegister, Warp, _device, _to_dev,
+from .batch import (BfSelect, DescriptorTable, DetectPyramid, FrameTable, LogosDictionary, LogosFilter, LogosTable, DensePairs, dense_fuse_sources, fuse_dense, SfmBundle, SfmRegister, Warp, _device, _to_dev,
                     bf_select_table, bgr_to_gray, frame_counts, frame_pairs_of, logos_dictionary, pair_table, tables_from_detector)
 from .api import getRotationMatrix2D, logos_dict_args
 from .types import (DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128, GMS_ERR_CAPACITY, GMS_OK, PAIR_DTYPE, RESULT_DTYPE, TWO_VIEW_DTYPE,
@@ -230,7 +230,7 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
                descriptor="grad", withRotation=False, withScale=False, thresholdFactor=6.0, prob=0.7, ransac_threshold=1.0, max_iters=1000,
                device=None, dictionary=None, logos_capacity=None, cross_check=True, distance_coef=4.0, max_size=500, train_dictionary=None,
                keep_tables=False, detector="fast", contrast=128, refine=False, register=False, root=0, min_links=8, bundle=False, dense=False,
-               min_disp16=16, dense_cap=None, dense_sgm=None, **ba):
+               min_disp16=16, dense_cap=None, dense_sgm=None, fuse=False, fuse_tol16=16, fuse_min_support=1, fuse_cap=None, **ba):
     """run_dataset from pixels. images: [n, H, W] grey or [n, H, W, 3] BGR, 8-bit, a host array or a device tensor (or a list of equally
     sized images). BGR goes through gms_bgr_to_gray_device; the pyramid keypoint source (threshold, max_keypoints, n_levels; detector
     "fast", or "dog" with `contrast` in the place of `threshold`: gms_detect_dog_batch_device, with refine=True
@@ -244,12 +244,21 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
     rectifiable, else a dict of points float32 [k, 3], colors uint8 [k] or [k, 3], pixel int32 [k], count and plan
     (gms_dense_pairs_device on the photographs themselves; min_disp16, dense_cap = the most points per pair, dense_sgm = the
     matcher's keywords). The points are in frame_a's frame and the pair's unit, as points3d; with register=True in the world frame,
-    as points_world, and a pair the registration does not use has none. The clouds of different pairs are not fused or
-    de-duplicated. dense=False returns the dict without."""
+    as points_world, and a pair the registration does not use has none. dense=False returns the dict without.
+    fuse=True (needs dense=True and register=True: without a registration the clouds share no frame) adds
+    `dense_fused`, the pairs' clouds fused into one by depth consistency (gms_dense_fuse_device on the maps, plans, views and scales
+    still resident on the device): a dict of points float32 [k, 3], colors, source int32 [k] (an index into `pairs`), index int32 [k]
+    (the point's index in that pair's `dense` entry), support and conflict uint8 [k] (the other pairs whose own disparity map agrees /
+    disagrees with the point within fuse_tol16 sixteenths of a pixel, support counting the point's own pair) and counts int32
+    [n_pairs + 1] (kept per pair, then the total). A point is kept once, by the lowest pair that sees it consistently, and only with
+    support >= fuse_min_support; fuse_cap: the most points returned (default: room for all). `dense` itself is what it is without
+    fuse; fuse=False returns the dict without `dense_fused`."""
     if method not in METHODS:
         raise ValueError(f"unknown method {method!r}")
     if dense and camera is None:
         raise ValueError("dense=True needs a camera: it rectifies by the recovered poses")
+    if fuse and not (dense and register):
+        raise ValueError("fuse=True needs dense=True and register=True: without a registration the clouds share no frame")
     if descriptor not in ("brief", "grad", "both"):
         raise ValueError('descriptor: "brief", "grad" or "both"')
     images, is_bgr = image_stack(images)
@@ -286,15 +295,19 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
     else:
         r = _run_gms(ctx, frames, descs, src, None, withRotation, withScale, thresholdFactor, *tail)
     if dense:
-        r.update(dense=_dense_pairs(ctx, d_photos, r, camera, dist, min_disp16, dense_cap, dense_sgm, reg is not None))
+        runs = [] if fuse else None       # (the runs' device buffers stay alive until the fusion has read them)
+        r.update(dense=_dense_pairs(ctx, d_photos, r, camera, dist, min_disp16, dense_cap, dense_sgm, reg is not None, runs))
+        if fuse:
+            r.update(dense_fused=_dense_fuse(ctx, runs, len(src), 3 if d_photos.dim() == 4 else 1, fuse_tol16, fuse_min_support, fuse_cap))
     if keep_tables:
         r.update(tables=(frames, descs))
     return r
 
 
-def _dense_pairs(ctx, d_photos, r, camera, dist, min_disp16, cap, sgm, registered):
+def _dense_pairs(ctx, d_photos, r, camera, dist, min_disp16, cap, sgm, registered, keep=None):
     """run_images' dense=True: gms_dense_pairs_device for the pairs with a pose, one run per output size (the source's size, and its
-    transpose for the pairs whose baseline is nearer the vertical), on the two-view records and the registration that `r` holds."""
+    transpose for the pairs whose baseline is nearer the vertical), on the two-view records and the registration that `r` holds.
+    keep: a list that gets (run, pair indices) of every run, for the fusion."""
     from .api import stereoRectify
     n, h, w = d_photos.shape[:3]
     channels = 3 if d_photos.dim() == 4 else 1
@@ -319,12 +332,29 @@ def _dense_pairs(ctx, d_photos, r, camera, dist, min_disp16, cap, sgm, registere
         torch.cuda.synchronize(d_photos.device)
         run.run(a, b)
         ctx.synchronize()
+        if keep is not None:
+            keep.append((run, idx))
         counts, plans = run.d_count.cpu().numpy(), run.plans()
         for j, i in enumerate(idx):
             k = min(int(counts[j]), run.cap)
             colors = run.d_cloud_color[j, :k].cpu().numpy()
             out[i] = dict(points=run.d_xyz[j, :k].cpu().numpy(), colors=colors if channels == 3 else colors[:, 0],
                           pixel=run.d_pixel[j, :k].cpu().numpy(), count=int(counts[j]), plan=plans[j:j + 1])
+    return out
+
+
+def _dense_fuse(ctx, runs, n_pairs, channels, tol16, min_support, cap):
+    """run_images' fuse=True: one gms_dense_fuse_device over the sources of every dense run, in the order of `pairs` (the pointer table
+    joins the two size groups without a copy); `source` comes back as an index into `pairs`. No source: an empty cloud."""
+    srcs = sorted(((i, s) for run, idx in runs for i, s in zip(idx, dense_fuse_sources(run))), key=lambda e: e[0])
+    counts = np.zeros(n_pairs + 1, np.int32)
+    if not srcs:
+        return dict(points=np.zeros((0, 3), np.float32), colors=np.zeros((0, 3) if channels == 3 else (0,), np.uint8), source=np.zeros(0, np.int32),
+                    index=np.zeros(0, np.int32), support=np.zeros(0, np.uint8), conflict=np.zeros(0, np.uint8), counts=counts)
+    pair_of = np.array([i for i, _ in srcs], np.int32)
+    out = fuse_dense(ctx, [s for _, s in srcs], None, channels, tol16, min_support, cap)
+    counts[pair_of], counts[-1] = out["counts"][:-1], out["counts"][-1]
+    out.update(source=pair_of[out["source"]], counts=counts)
     return out
 
 

@@ -204,6 +204,50 @@ class RectifyPlan:
         return int(self.record["out_w"][0]), int(self.record["out_h"][0])
 
 
+# gms_dense_fuse_src (include/gms.h): one pair's output of the dense stage as the fusion reads it; the first eight fields are pointers
+DENSE_FUSE_SRC_DTYPE = np.dtype([("d_disp16", "<u8"), ("d_valid", "<u8"), ("d_plan", "<u8"), ("d_xyz", "<u8"), ("d_color", "<u8"), ("d_count", "<u8"),
+                                 ("d_view", "<u8"), ("d_reg", "<u8"), ("width", "<i4"), ("height", "<i4"), ("filtered16", "<i4"),
+                                 ("min_disp16", "<i4"), ("cap", "<i4"), ("reserved", "<i4")])
+assert DENSE_FUSE_SRC_DTYPE.itemsize == 88
+DENSE_FUSE_MAX_NEIGHBORS = 32
+
+
+def dense_fuse_neighbors(n_src, neighbors=None):
+    """The fusion's neighbour table, int32 [n_src, n_nb] with 1 <= n_nb <= 32 (-1: an empty slot). None: every other source, which
+    needs n_src - 1 <= 32; beyond that the caller chooses (ValueError otherwise). For j > i the table should list i for j whenever it
+    lists j for i: source j drops its copy of a point only when it looks at source i, so a one-sided entry lets duplicates survive."""
+    if neighbors is None:
+        if n_src - 1 > DENSE_FUSE_MAX_NEIGHBORS:
+            raise ValueError(f"{n_src} sources: more than {DENSE_FUSE_MAX_NEIGHBORS} others each, pass neighbors=")
+        nb = np.full((n_src, max(n_src - 1, 1)), -1, np.int32)
+        for i in range(n_src):
+            nb[i, :n_src - 1] = [j for j in range(n_src) if j != i]
+        return nb
+    nb = np.ascontiguousarray(neighbors, dtype=np.int32)
+    if nb.ndim != 2 or nb.shape[0] != n_src or not 1 <= nb.shape[1] <= DENSE_FUSE_MAX_NEIGHBORS:
+        raise ValueError(f"neighbors: int32 [{n_src}, 1..{DENSE_FUSE_MAX_NEIGHBORS}]")
+    return nb
+
+
+def sfm_view_record(view):
+    """One SFM_VIEW_DTYPE record from a record, or from (R, t) / (R, t, registered)."""
+    if isinstance(view, np.ndarray) and view.dtype.itemsize == SFM_VIEW_DTYPE.itemsize and view.dtype.names:
+        return np.ascontiguousarray(view).reshape(-1)[:1].view(np.uint8).view(SFM_VIEW_DTYPE).copy()
+    G = np.zeros(1, SFM_VIEW_DTYPE)
+    G["R"][0], G["t"][0] = np.asarray(view[0], dtype=np.float64).reshape(3, 3), np.asarray(view[1], dtype=np.float64).reshape(3)
+    G["registered"], G["pair"] = (int(view[2]) if len(view) > 2 else 1), -1
+    return G
+
+
+def sfm_pair_reg_record(reg):
+    """One SFM_PAIR_REG_DTYPE record from a record, or from (S, status)."""
+    if isinstance(reg, np.ndarray) and reg.dtype.itemsize == SFM_PAIR_REG_DTYPE.itemsize and reg.dtype.names:
+        return np.ascontiguousarray(reg).reshape(-1)[:1].view(np.uint8).view(SFM_PAIR_REG_DTYPE).copy()
+    r = np.zeros(1, SFM_PAIR_REG_DTYPE)
+    r["S"], r["status"] = float(reg[0]), int(reg[1])
+    return r
+
+
 # GMS_STEREO_SGM_PARAMS_DENSE: the matcher's record of the dense stage (the shared principal point makes true disparities positive)
 STEREO_SGM_DENSE = dict(min_disparity=0, num_disparities=128)
 

@@ -3,7 +3,7 @@
 pipeline.run_images(register=True): per pair the two-view stage, then gms_sfm_register_device joins the pairs).
 Prints one JSON line: per pair n_links, r, S and status; per view the camera centre; tracks by length; the median spread.
 
-    python tools/gms_sfm_sequence.py [images.npz] [--method gms|bf|logos] [--pairs chain|star|all] [--root 0] [--min-links 8] [--max-keypoints 2000] [--ply out.ply] [--bundle] [--check]
+    python tools/gms_sfm_sequence.py [images.npz] [--method gms|bf|logos] [--pairs chain|star|all] [--root 0] [--min-links 8] [--max-keypoints 2000] [--ply out.ply] [--bundle] [--dense [--fuse [--fuse-tol16 16] [--fuse-min-support 1]]] [--check]
 
 images.npz: arrays images ([n, H, W] grey or [n, H, W, 3] BGR, uint8) and camera = (fx, fy, cx, cy), optionally dist. Default: views
 1, 2, 3, 4 of the reference's SourceImages scene from the two committed fixtures (tests/golden/image_sfm_pair_1008x756.npz holds views 1
@@ -12,7 +12,11 @@ every a < b in order (the pairs that close a loop are skipped by the plan). --pl
 track's keypoint count as `obs`). --check: feeds the GPU's own two-view records to the numpy statement (tests/sfm_register_ref.py)
 and compares: integers exactly, doubles to 1e-9; test infrastructure. --bundle: bundle adjustment behind the registration
 (gms_sfm_ba_device): reprojection RMS before and after, accepted iterations, tracks used and excluded, the camera
-centres after; with --check also against tests/sfm_ba_ref.py under the tolerance measured on these records."""
+centres after; with --check also against tests/sfm_ba_ref.py under the tolerance measured on these records. --dense: the dense
+cloud of every pair; --fuse: the clouds fused into one by depth consistency (gms_dense_fuse_device):
+the points per pair, the fused total and a histogram of `support`; --ply then writes the fused cloud (x, y, z, the colour, support);
+with --check the dense stage is run once more to read its maps back, the numpy statement (tests/dense_fuse_ref.py) fuses them, and
+every output byte is compared."""
 import argparse
 import importlib
 import json
@@ -47,6 +51,52 @@ def write_ply(path, cloud, obs):
             f.write(f"{p[0]:.9g} {p[1]:.9g} {p[2]:.9g} {int(o)}\n")
 
 
+def write_fused_ply(path, f):
+    col = f["colors"] if f["colors"].ndim == 2 else np.stack([f["colors"]] * 3, axis=1)   # BGR, or grey three times
+    with open(path, "w") as out:
+        out.write(f"ply\nformat ascii 1.0\nelement vertex {len(f['points'])}\nproperty float x\nproperty float y\nproperty float z\n"
+                  "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar support\nend_header\n")
+        for p, c, s in zip(f["points"], col, f["support"]):
+            out.write(f"{p[0]:.9g} {p[1]:.9g} {p[2]:.9g} {int(c[2])} {int(c[1])} {int(c[0])} {int(s)}\n")
+
+
+def check_fusion(pkg, r, images, camera, dist, a):
+    """The dense stage once more on the same records (it is deterministic), its maps read back, tests/dense_fuse_ref.py on them, and
+    the fused cloud the run returned compared byte for byte. Test infrastructure."""
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import dense_fuse_ref as fr
+    pipeline = importlib.import_module("sfm-gms_amd.pipeline")
+    api = importlib.import_module("sfm-gms_amd.api")
+    ctx = api.default_context()
+    d_photos = torch.from_numpy(np.ascontiguousarray(images)).to(f"cuda:{ctx.device}")
+    runs = []
+    dense = pipeline._dense_pairs(ctx, d_photos, r, camera, dist, 16, a.dense_cap, None, True, runs)
+    same_dense = all((x is None) == (y is None) and (x is None or x["points"].tobytes() == y["points"].tobytes()) for x, y in zip(dense, r["dense"]))
+    channels = 3 if images.ndim == 4 else 1
+    srcs, pair_of = {}, []
+    for run, idx in runs:
+        plans, counts = run.plans(), run.d_count.cpu().numpy()
+        for j, i in enumerate(idx):
+            v = r["views"][int(r["pairs"]["frame_a"][i])]
+            g = r["registration"][i]
+            srcs[i] = fr.source(run.d_disp16[j].cpu().numpy(), run.d_valid[j].cpu().numpy(), plans[j:j + 1], run.d_xyz[j].cpu().numpy()[:run.cap],
+                                count=int(counts[j]), color=run.d_cloud_color[j].cpu().numpy()[:run.cap], filtered16=-16, min_disp16=16,
+                                view=(v["R"], v["t"], int(v["registered"])), reg=(float(g["S"]), int(g["status"])))
+    pair_of = np.array(sorted(srcs), np.int32)
+    want = fr.fuse([srcs[i] for i in pair_of], None, channels, a.fuse_tol16, a.fuse_min_support) if len(pair_of) else None
+    f = r["dense_fused"]
+    if want is None:
+        return {"dense_repeats": bool(same_dense), "empty": len(f["points"]) == 0}
+    counts = np.zeros(len(r["pairs"]) + 1, np.int32)
+    counts[pair_of], counts[-1] = want["counts"][:-1], want["counts"][-1]
+    colors = want["colors"] if channels == 3 else want["colors"][:, 0]
+    return {"dense_repeats": bool(same_dense), "counts": bool(np.array_equal(f["counts"], counts)),
+            "points": f["points"].tobytes() == want["points"].tobytes(), "colors": f["colors"].tobytes() == np.ascontiguousarray(colors).tobytes(),
+            "source": bool(np.array_equal(f["source"], pair_of[want["source"]])), "index": bool(np.array_equal(f["index"], want["index"])),
+            "support": bool(np.array_equal(f["support"], want["support"])), "conflict": bool(np.array_equal(f["conflict"], want["conflict"]))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("images", nargs="?")
@@ -58,7 +108,14 @@ def main():
     ap.add_argument("--ply")
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--bundle", action="store_true")
+    ap.add_argument("--dense", action="store_true")
+    ap.add_argument("--fuse", action="store_true")
+    ap.add_argument("--fuse-tol16", type=int, default=16)
+    ap.add_argument("--fuse-min-support", type=int, default=1)
+    ap.add_argument("--dense-cap", type=int, default=None)
     a = ap.parse_args()
+    if a.fuse and not a.dense:
+        ap.error("--fuse needs --dense")
     if a.images:
         z = np.load(a.images)
         images, camera = np.ascontiguousarray(z["images"], dtype=np.uint8), tuple(float(v) for v in z["camera"])
@@ -71,7 +128,9 @@ def main():
     pairs = pair_list(a.pairs, n, a.root)
     pkg = importlib.import_module("sfm-gms_amd")
     r = pkg.structureFromMotionMulti(images, camera, dist, method=a.method, pairs=pairs, root=a.root, min_links=a.min_links,
-                                     max_keypoints=a.max_keypoints, keep_tables=True, bundle=a.bundle)
+                                     max_keypoints=a.max_keypoints, keep_tables=True, bundle=a.bundle,
+                                     **(dict(dense=True, dense_cap=a.dense_cap) if a.dense else {}),
+                                     **(dict(fuse=True, fuse_tol16=a.fuse_tol16, fuse_min_support=a.fuse_min_support) if a.fuse else {}))
     reg, views, tv = r["registration"], r["views"], r["two_view"]
     centres = [None if not v["registered"] else [round(float(x), 5) for x in -v["R"].T @ v["t"]] for v in views]
     obs, spread, cloud = r["cloud_obs"], r["cloud_spread"], r["cloud"]
@@ -99,6 +158,18 @@ def main():
                           "tracks_excluded_fewer_than_two": int(st[2]), "tracks_kept_cloud_point_at_retriangulation": int(st[3]),
                           "camera_centres": [None if not v["registered"] else [round(float(x), 5) for x in -v["R"].T @ v["t"]] for v in r["views_ba"]]}
     ok = True
+    if a.dense:
+        line["dense_points_per_pair"] = [0 if d is None else int(d["count"]) for d in r["dense"]]
+    if a.fuse:
+        f = r["dense_fused"]
+        line["fused"] = {"tol16": a.fuse_tol16, "min_support": a.fuse_min_support, "kept_per_pair": f["counts"][:-1].tolist(), "total": int(f["counts"][-1]),
+                         "sum_of_parts": int(sum(line["dense_points_per_pair"])),
+                         "support_histogram": {str(k): int(c) for k, c in enumerate(np.bincount(f["support"])) if c},
+                         "conflict_histogram": {str(k): int(c) for k, c in enumerate(np.bincount(f["conflict"])) if c}}
+        if a.check:
+            chk = check_fusion(pkg, r, images, camera, dist, a)
+            line["fused"]["check_vs_statement"] = chk
+            ok = ok and all(chk.values())
     if a.check and a.bundle:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import sfm_ba_ref as ba_ref
@@ -146,7 +217,9 @@ def main():
                "summary": r["summary"].tobytes() == want["summary"].tobytes()}
         line["check_vs_statement"] = {k: bool(v) for k, v in chk.items()}
         ok = ok and all(chk.values())
-    if a.ply:
+    if a.ply and a.fuse:
+        write_fused_ply(a.ply, r["dense_fused"])
+    elif a.ply:
         write_ply(a.ply, cloud, obs)
     print(json.dumps(line))
     return 0 if ok else 1

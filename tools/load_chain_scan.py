@@ -13,7 +13,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "sfm-gms_amd", "csrc")
 FILES = ["gms_kernels.hip", "gms_kernel_hash.hip", "gms_kernel_dense.hip", "gms_kernel_scales.hip", "gms_kernel_stream.hip", "gms_kernel_stream_plain.hip", "gms_kernel_band.hip", "gms_kernel_big.hip", "bf_kernels.hip", "consumer_kernels.hip",
-         "twoview_kernels.hip", "detect_kernels.hip"]
+         "twoview_kernels.hip", "detect_kernels.hip", "dense_fuse_kernels.hip"]
 
 
 def demangle(names):
