@@ -1102,6 +1102,45 @@ int gms_dense_fuse(const gms_dense_fuse_src* src, int n_src, const int32_t* neig
                    int fused_cap, float* xyz, uint8_t* color, int32_t* source, int32_t* index, uint8_t* support, uint8_t* conflict,
                    int32_t* counts);
 
+/* ---- the speckle filter behind the matchers (cv::filterSpeckles for CV_16S) ----------------------------------------
+ * Stated in csrc/speckle_core.h and twice in numpy in tests/speckle_ref.py; integer, free of any scan order, so the GPU, a host build
+ * of the header and numpy agree byte for byte. Written from the published algorithm: parity with an OpenCV build is unpinned.
+ *   On an int16 map [height][width] (dense rows): two pixels are linked when they are 4-neighbours, neither equals new_val and
+ *   |a - b| <= max_diff, the difference taken in 32 bits (32767 beside -32768 differ by 65535). Components are the transitive
+ *   closure of the links. Every pixel that is not new_val and whose component has at most max_speckle_size pixels becomes new_val;
+ *   nothing else changes. max_diff is in the map's own units -- sixteenths of a pixel for the matchers' maps; it is not scaled, and
+ *   neither of OpenCV's matcher conventions is claimed. max_speckle_size 0 leaves the maps as they are.
+ * gms_filter_speckles_device: n maps, image i at d_disp16 + i * height * width, in place; d_removed (optional) int32 [n]: the pixels
+ *   changed per map. Stream-ordered on the context's stream; no allocation, no synchronisation, no readback; capturable (one
+ *   stream, no parallel branches). Refused (GMS_ERR_BAD_ARG, nothing run): width or height outside 1..8192, n outside 1..65535,
+ *   new_val outside int16, max_speckle_size < 0, max_diff < 0, a NULL or misaligned pointer (d_workspace 256 bytes, d_disp16 2,
+ *   d_removed 4), a workspace below gms_filter_speckles_workspace_bytes (8 bytes per pixel; 0 for arguments that are refused).
+ * gms_filter_speckles: ONE map on host pointers, in place, synchronous, on the current HIP device; *removed (optional) the pixels
+ *   changed.
+ * gms_dense_pairs_filtered_device: gms_dense_pairs_device with the filter between the matcher and the cloud: on d_disp16 with
+ *   new_val = (min_disparity - 1) * 16, the matcher's FILTERED code, max_speckle_size = speckle_size and max_diff = speckle_diff16;
+ *   d_removed (optional) int32 [n_pairs]. The filter works in a region of its own behind gms_dense_pairs_device's workspace
+ *   (gms_dense_pairs_filtered_workspace_bytes). speckle_size 0 is gms_dense_pairs_device: the same bytes.
+ * gms_dense_pair_filtered: gms_dense_pair likewise; *removed (optional). */
+size_t gms_filter_speckles_workspace_bytes(int width, int height, int n);
+int gms_filter_speckles_device(gms_ctx* ctx, int16_t* d_disp16, int n, int width, int height, int new_val, int max_speckle_size,
+                               int max_diff, void* d_workspace, size_t workspace_bytes, int32_t* d_removed);
+int gms_filter_speckles(int16_t* disp16, int width, int height, int new_val, int max_speckle_size, int max_diff, int32_t* removed);
+size_t gms_dense_pairs_filtered_workspace_bytes(int src_width, int src_height, int channels, int out_width, int out_height, int n_pairs,
+                                                const gms_stereo_sgm_params* params);
+int gms_dense_pairs_filtered_device(gms_ctx* ctx, const gms_camera* camera, const gms_stereo_sgm_params* params, const uint8_t* d_img1,
+                                    const uint8_t* d_img2, int n_pairs, int src_width, int src_height, int channels,
+                                    const gms_two_view* d_tv, int out_width, int out_height, int min_disp16, const gms_pair* d_pairs,
+                                    const gms_sfm_pair_reg* d_reg, const gms_sfm_view* d_views, int n_frames, void* d_workspace,
+                                    size_t workspace_bytes, gms_rectify_plan* d_plans, uint8_t* d_rect1, uint8_t* d_rect2, uint8_t* d_valid,
+                                    uint8_t* d_color, int16_t* d_disp16, int cap, float* d_xyz, uint8_t* d_cloud_color, int32_t* d_pixel,
+                                    int32_t* d_count, int speckle_size, int speckle_diff16, int32_t* d_removed);
+int gms_dense_pair_filtered(const gms_camera* camera, const gms_stereo_sgm_params* params, const uint8_t* img1, const uint8_t* img2,
+                            int width, int height, int channels, const double* R, const double* t, int out_width, int out_height,
+                            int min_disp16, gms_rectify_plan* plan, uint8_t* rect1, uint8_t* rect2, uint8_t* valid, uint8_t* color,
+                            int16_t* disp16, int cap, float* xyz, uint8_t* cloud_color, int32_t* pixel, int32_t* count, int speckle_size,
+                            int speckle_diff16, int32_t* removed);
+
 /* ---- camera calibration from chessboard photographs (main.cpp:53-68, CalibrationUtil.cpp:3-53) ---------------------
  * The corner finder is THIS LIBRARY'S OWN definition, not OpenCV's quad-based findChessboardCorners; cornerSubPix restates OpenCV
  * 4.5.2's algorithm in fp64; calibrateCamera follows its structure. Parity with an OpenCV build is unpinned. tests/calib_ref.py states

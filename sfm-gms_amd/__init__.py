@@ -21,7 +21,7 @@ from .types import CHESS_CANDIDATE_DTYPE  # noqa: F401
 from .api import structureFromMotionMulti, registerViews, sfm_plan  # noqa: F401
 from .types import SFM_PLAN_DTYPE, SFM_VIEW_DTYPE, SFM_PAIR_REG_DTYPE, SFM_SUMMARY_DTYPE, GMS_SFM_SKIPPED  # noqa: F401
 from .api import bundleAdjust  # noqa: F401
-from .api import stereoRectify, rectifyQ, rectify, undistort, denseStereo, denseFuse  # noqa: F401
+from .api import stereoRectify, rectifyQ, rectify, undistort, denseStereo, denseFuse, filterSpeckles  # noqa: F401
 from .types import DENSE_FUSE_SRC_DTYPE, dense_fuse_neighbors  # noqa: F401
 from .types import RECTIFY_PLAN_DTYPE, RectifyPlan  # noqa: F401
 from .types import (SFM_BA_PARAMS_DTYPE, SFM_BA_SUMMARY_DTYPE, SFM_BA_REFINED, SFM_BA_MULTI, SFM_BA_FEW, SFM_BA_KEPT, SFM_BA_DEFAULTS,  # noqa: F401
@@ -38,6 +38,6 @@ __all__ = [
     "structureFromMotionMulti", "registerViews", "sfm_plan", "SFM_PLAN_DTYPE", "SFM_VIEW_DTYPE", "SFM_PAIR_REG_DTYPE", "SFM_SUMMARY_DTYPE",
     "GMS_SFM_SKIPPED", "bundleAdjust", "SFM_BA_PARAMS_DTYPE", "SFM_BA_SUMMARY_DTYPE", "SFM_BA_REFINED", "SFM_BA_MULTI", "SFM_BA_FEW",
     "SFM_BA_KEPT", "SFM_BA_DEFAULTS", "sfm_ba_params",
-    "stereoRectify", "rectifyQ", "rectify", "undistort", "denseStereo", "denseFuse", "DENSE_FUSE_SRC_DTYPE", "dense_fuse_neighbors", "RECTIFY_PLAN_DTYPE", "RectifyPlan",
+    "stereoRectify", "rectifyQ", "rectify", "undistort", "denseStereo", "denseFuse", "filterSpeckles", "DENSE_FUSE_SRC_DTYPE", "dense_fuse_neighbors", "RECTIFY_PLAN_DTYPE", "RectifyPlan",
     "all_pairs_count", "pair_from_index", "shard_range", "GMS_DESC_HAMMING256", "GMS_DESC_L2_F32X128", "GMS_DETECT_BORDER",
 ]

@@ -33,6 +33,14 @@ def _check(rc, lib, what):
         raise GmsError(rc, f"{what}: {msg}")
 
 
+def _c_int(v):
+    """An argument the C ABI takes as int: refused here when it does not fit, since ctypes would pass its low 32 bits."""
+    v = int(v)
+    if not -2 ** 31 <= v < 2 ** 31:
+        raise GmsError(GMS_ERR_BAD_ARG, f"{v} does not fit a C int")
+    return v
+
+
 # one record of GmsContext.read_side_records (gms_ctx_read_side_records, GMS_SIDE_RECORD_BYTES)
 SIDE_RECORD_DTYPE = np.dtype([("off", "<i8"), ("n", "<i4"), ("flags", "<u4"), ("stamp", "<u8"), ("pad", "<u4", (2,)), ("hist", "<u4", (400,))])
 assert SIDE_RECORD_DTYPE.itemsize == 1632
@@ -524,6 +532,36 @@ class GmsContext:
                                                 d_color or None, d_disp16 or None, int(cap), d_xyz or None, d_cloud_color or None,
                                                 d_pixel or None, d_count or None), self._lib, "gms_dense_pairs_device")
 
+    def dense_pairs_filtered_workspace_bytes(self, src_width, src_height, channels, out_width, out_height, n_pairs, params=None):
+        return int(self._lib.gms_dense_pairs_filtered_workspace_bytes(int(src_width), int(src_height), int(channels), int(out_width),
+                                                                      int(out_height), int(n_pairs), dense_sgm_params(params).ctypes.data))
+
+    def dense_pairs_filtered_device(self, camera, params, d_img1, d_img2, n_pairs, src_width, src_height, channels, d_tv, out_width, out_height,
+                                    min_disp16, d_ws, ws_bytes, d_plans, d_rect1, d_rect2, d_valid, d_color, d_disp16, cap, d_xyz, d_cloud_color,
+                                    d_pixel, d_count, speckle_size, speckle_diff16, d_removed=None, d_pairs=None, d_reg=None, d_views=None,
+                                    n_frames=0):
+        """gms_dense_pairs_filtered_device: dense_pairs_device with the speckle filter (speckle_size, speckle_diff16 in sixteenths of a
+        pixel) between the matcher and the cloud. Stream-ordered."""
+        rec = dense_sgm_params(params)
+        _check(self._lib.gms_dense_pairs_filtered_device(self._h, camera.ctypes.data, rec.ctypes.data, d_img1 or None, d_img2 or None, int(n_pairs),
+                                                         int(src_width), int(src_height), int(channels), d_tv or None, int(out_width),
+                                                         int(out_height), int(min_disp16), d_pairs or None, d_reg or None, d_views or None,
+                                                         int(n_frames), d_ws or None, int(ws_bytes), d_plans or None, d_rect1 or None,
+                                                         d_rect2 or None, d_valid or None, d_color or None, d_disp16 or None, int(cap),
+                                                         d_xyz or None, d_cloud_color or None, d_pixel or None, d_count or None,
+                                                         int(speckle_size), int(speckle_diff16), d_removed or None), self._lib,
+               "gms_dense_pairs_filtered_device")
+
+    # -- the speckle filter (DESIGN.md 4.13c; batch.SpeckleFilter drives these) ----------------------------------------------------------
+    def filter_speckles_workspace_bytes(self, width, height, n):
+        return int(self._lib.gms_filter_speckles_workspace_bytes(int(width), int(height), int(n)))
+
+    def filter_speckles_device(self, d_disp16, n, width, height, new_val, max_speckle_size, max_diff, d_ws, ws_bytes, d_removed=None):
+        """gms_filter_speckles_device on raw device pointers: n int16 maps filtered in place. Stream-ordered."""
+        _check(self._lib.gms_filter_speckles_device(self._h, d_disp16 or None, int(n), int(width), int(height), _c_int(new_val),
+                                                    _c_int(max_speckle_size), _c_int(max_diff), d_ws or None, int(ws_bytes),
+                                                    d_removed or None), self._lib, "gms_filter_speckles_device")
+
     # -- the clouds of several pairs fused into one (DESIGN.md 4.13b; batch.DenseFuse drives these) --------------------------------------
     def dense_fuse_workspace_bytes(self, n_src, max_cap):
         return int(self._lib.gms_dense_fuse_workspace_bytes(int(n_src), int(max_cap)))
@@ -690,7 +728,9 @@ def structureFromMotion(img1, img2, camera, dist=None, method="logos", ctx=None,
     (KEYPOINT_DTYPE), two_view (the pair's TWO_VIEW_DTYPE record: counts, iterations, reprojection sums) and detail (run_images'
     record, with `tables`: the resident FrameTable and DescriptorTable). A pair without a pose raises GmsError with the two-view status.
     dense=True among params (run_images' min_disp16, dense_cap, dense_sgm): adds `dense`, the pair's dense cloud in
-    points3D's frame and unit -- a dict of points, colors, pixel, count and plan, or None when the pose is not rectifiable."""
+    points3D's frame and unit -- a dict of points, colors, pixel, count and plan, or None when the pose is not rectifiable.
+    dense_speckle = (max_speckle_size, max_diff16) beside it: filterSpeckles on the matcher's map before the reprojection (DESIGN.md
+    4.13c); the entry then also holds removed. None, the default: no filter."""
     from . import pipeline
     if method not in pipeline.METHODS:
         raise ValueError(f"unknown method {method!r}")
@@ -825,7 +865,8 @@ def structureFromMotionMulti(images, camera, dist=None, method="gms", pairs=None
     huber_px, retriangulate among params) adds views_ba, cloud_ba, track_status and ba_summary; bundle=False returns the dict without.
     dense=True among params adds `dense`, one cloud per pair in the root's frame; fuse=True beside it (fuse_tol16, fuse_min_support,
     fuse_cap: run_images') adds `dense_fused`, those clouds fused into one by depth consistency; fuse=True without
-    dense=True raises ValueError."""
+    dense=True raises ValueError. dense_speckle = (max_speckle_size, max_diff16): filterSpeckles on every pair's map before the
+    reprojection; the fusion then reads the filtered maps. None, the default: no filter."""
     from . import pipeline
     if method not in pipeline.METHODS:
         raise ValueError(f"unknown method {method!r}")
@@ -878,7 +919,8 @@ def stereoBM(left, right, return_cost=False, **params):
     """StereoBM::compute(left, right, disparity) of OpenCV 4.5.2 on the GPU (integer path; tests/stereo_bm_ref.py states it): the int16
     map with 4 fractional bits, FILTERED = (min_disparity - 1) * 16. Parameters by keyword (block_size, num_disparities, min_disparity,
     pre_filter_cap, texture_threshold, uniqueness_ratio, disp12_max_diff, ...; types.STEREO_BM_PARAMS_DTYPE), the reference's values
-    (DisparityUtil.cpp:24-36) by default. return_cost=True: also the int32 cost map (sad of the winner, -1 where there is none)."""
+    (DisparityUtil.cpp:24-36) by default. return_cost=True: also the int32 cost map (sad of the winner, -1 where there is none).
+    speckle_window_size > 0 is refused: pass the map to filterSpeckles(disp16, FILTERED, size, range * 16 or any max_diff in sixteenths)."""
     d16, cost, _ = _stereo_bm(left, right, params, True, return_cost, False)
     return (d16, cost) if return_cost else d16
 
@@ -908,7 +950,8 @@ def stereoSGM(left, right, return_cost=False, p1=None, p2=None, n_paths=8, **bm_
     one; default 8 block_size^2) and p2 (a larger step; default 32 block_size^2), then StereoBM's decision rules on the sums. left /
     right: uint8 [H, W] host arrays or device tensors. Returns the int16 map with 4 fractional bits, FILTERED = (min_disparity - 1) * 16;
     return_cost=True: also the int32 cost map (the winner's sum, -1 where there is none). bm_params: StereoBM's parameters by keyword
-    (types.STEREO_SGM_PARAMS_DTYPE), the reference's values by default. p1 = p2 = 0 with uniqueness_ratio = 0 gives stereoBM's map."""
+    (types.STEREO_SGM_PARAMS_DTYPE), the reference's values by default. p1 = p2 = 0 with uniqueness_ratio = 0 gives stereoBM's map.
+    speckle_window_size > 0 is refused: pass the map to filterSpeckles (new_val = FILTERED, max_diff in sixteenths of a pixel)."""
     d16, cost, _ = _stereo_sgm(left, right, dict(bm_params, p1=p1, p2=p2, n_paths=n_paths), return_cost, False)
     return (d16, cost) if return_cost else d16
 
@@ -1105,14 +1148,51 @@ def undistort(image, camera, dist):
     return out
 
 
-def denseStereo(img1, img2, camera, dist, R, t, min_disp16=16, out_size=None, cap=None, **sgm_params):
+def _speckle_pair(speckle, who):
+    """speckle=None | (max_speckle_size, max_diff16) -> (size, diff16); None is (0, 0), the unfiltered stage."""
+    if speckle is None:
+        return 0, 0
+    size, diff = (_c_int(v) for v in speckle)
+    if size < 0 or diff < 0:
+        raise GmsError(GMS_ERR_BAD_ARG, f"{who}: speckle = (max_speckle_size >= 0, max_diff16 >= 0)")
+    return size, diff
+
+
+def filterSpeckles(disp16, new_val, max_speckle_size, max_diff, return_removed=False):
+    """cv::filterSpeckles(img, newVal, maxSpeckleSize, maxDiff) for an int16 map [H, W] on the GPU (DESIGN.md 4.13c;
+    tests/speckle_ref.py states it): pixels are linked when they are 4-neighbours, neither equals new_val and |a - b| <= max_diff
+    (taken in 32 bits); every pixel that is not new_val and whose component has at most max_speckle_size pixels becomes new_val.
+    max_diff is in the map's own units: sixteenths of a pixel for stereoBM's / stereoSGM's maps, whose new_val is their FILTERED code
+    (min_disparity - 1) * 16. A host array gives a new host array (gms_filter_speckles); a device tensor (int16, contiguous) is
+    filtered in place and returned (batch.SpeckleFilter). return_removed=True: also the number of pixels changed."""
+    if _is_tensor(disp16):
+        from .batch import filter_speckles_batch
+        if disp16.dim() != 2:
+            raise ValueError("filterSpeckles: an int16 map [H, W]")
+        _, removed = filter_speckles_batch(disp16[None], new_val, max_speckle_size, max_diff, return_removed=True)
+        return (disp16, int(removed[0])) if return_removed else disp16
+    src = np.asarray(disp16)
+    if src.dtype != np.int16 or src.ndim != 2 or src.size == 0:
+        raise ValueError("filterSpeckles: an int16 map [H, W]")
+    lib = load_library()
+    out = np.array(src, dtype=np.int16, order="C", copy=True)
+    removed = np.zeros(1, np.int32)
+    _check(lib.gms_filter_speckles(out.ctypes.data, out.shape[1], out.shape[0], _c_int(new_val), _c_int(max_speckle_size), _c_int(max_diff),
+                                   removed.ctypes.data), lib, "gms_filter_speckles")
+    return (out, int(removed[0])) if return_removed else out
+
+
+def denseStereo(img1, img2, camera, dist, R, t, min_disp16=16, out_size=None, cap=None, speckle=None, **sgm_params):
     """A dense, coloured cloud from a posed pair X2 = R X1 + t: stereoRectify's plan, both images rectified, stereoSGM
     on the rectified pair, every matched pixel reprojected into camera 1's frame in the unit of t -- the frame and unit of
     structureFromMotion's points3D. img1 / img2: uint8 [H, W] or [H, W, 3] BGR of one size, host arrays (gms_dense_pair) or device
     tensors (batch.DensePairs). sgm_params: stereoSGM's keywords; min_disparity 0 and num_disparities 128 unless given. cap: the most
     points returned (default: every pixel). Returns a dict: points float32 [k, 3], colors uint8 [k] or [k, 3], pixel int32 [k]
     (v * out_w + u of the rectified image, raster order), disp16 int16, rect1, rect2, valid (camera 1's), plan, count (all the points,
-    also beyond cap). A pair that is not rectifiable raises GmsError(GMS_ERR_NO_MODEL)."""
+    also beyond cap). speckle = (max_speckle_size, max_diff16): filterSpeckles on the matcher's map before the reprojection, max_diff16 in
+    sixteenths of a pixel; the dict then also holds removed. None: no filter. A pair that is not rectifiable raises
+    GmsError(GMS_ERR_NO_MODEL)."""
+    spk_size, spk_diff = _speckle_pair(speckle, "denseStereo")
     shapes = [tuple(im.shape) for im in (img1, img2)]
     if len(shapes[0]) not in (2, 3) or (len(shapes[0]) == 3 and shapes[0][2] != 3) or shapes[0] != shapes[1]:
         raise ValueError("img1 / img2: [H, W] grey or [H, W, 3] BGR, one size")
@@ -1130,7 +1210,8 @@ def denseStereo(img1, img2, camera, dist, R, t, min_disp16=16, out_size=None, ca
         from .batch import DensePairs
         import torch
         ctx = default_context()
-        run = DensePairs(ctx, 1, (w, h), (ow, oh), camera, dist, c, cap=cap, min_disp16=min_disp16, params=rec, device=img1.device)
+        run = DensePairs(ctx, 1, (w, h), (ow, oh), camera, dist, c, cap=cap, min_disp16=min_disp16, params=rec, device=img1.device,
+                         speckle=speckle)
         tv = np.zeros(1, TWO_VIEW_DTYPE)
         tv["R"][0], tv["t"][0] = np.asarray(R, dtype=np.float64).reshape(3, 3), np.asarray(t, dtype=np.float64).reshape(3)
         run.set_two_view(tv)
@@ -1138,9 +1219,10 @@ def denseStereo(img1, img2, camera, dist, R, t, min_disp16=16, out_size=None, ca
         run.run(img1.contiguous()[None], img2.contiguous()[None])
         ctx.synchronize()
         k = min(int(run.d_count[0]), cap)
+        more = {} if speckle is None else dict(removed=int(run.d_removed[0]))
         return dict(points=run.d_xyz[0, :k], colors=run.d_cloud_color[0, :k] if c == 3 else run.d_cloud_color[0, :k, 0], pixel=run.d_pixel[0, :k],
                     disp16=run.d_disp16[0], rect1=run.d_color[0] if c == 3 else run.d_rect1[0], rect2=run.d_rect2[0], valid=run.d_valid[0],
-                    plan=plan, count=int(run.d_count[0]))
+                    plan=plan, count=int(run.d_count[0]), **more)
     lib = load_library()
     cam = make_camera(camera, dist)
     a, b = np.ascontiguousarray(img1, dtype=np.uint8), np.ascontiguousarray(img2, dtype=np.uint8)
@@ -1151,13 +1233,19 @@ def denseStereo(img1, img2, camera, dist, R, t, min_disp16=16, out_size=None, ca
     xyz, cc, pixel = np.zeros((max(cap, 1), 3), np.float32), np.zeros((max(cap, 1), c), np.uint8), np.zeros(max(cap, 1), np.int32)
     count = np.zeros(1, np.int32)
     out_plan = np.zeros(1, RECTIFY_PLAN_DTYPE)
-    _check(lib.gms_dense_pair(cam.ctypes.data, rec.ctypes.data, a.ctypes.data, b.ctypes.data, w, h, c, Rv.ctypes.data, tvec.ctypes.data, ow, oh,
-                              int(min_disp16), out_plan.ctypes.data, rect1.ctypes.data, rect2.ctypes.data, valid.ctypes.data,
-                              None if color is None else color.ctypes.data, disp16.ctypes.data, cap, xyz.ctypes.data, cc.ctypes.data,
-                              pixel.ctypes.data, count.ctypes.data), lib, "gms_dense_pair")
+    args = (cam.ctypes.data, rec.ctypes.data, a.ctypes.data, b.ctypes.data, w, h, c, Rv.ctypes.data, tvec.ctypes.data, ow, oh, int(min_disp16),
+            out_plan.ctypes.data, rect1.ctypes.data, rect2.ctypes.data, valid.ctypes.data, None if color is None else color.ctypes.data,
+            disp16.ctypes.data, cap, xyz.ctypes.data, cc.ctypes.data, pixel.ctypes.data, count.ctypes.data)
+    more = {}
+    if speckle is None:
+        _check(lib.gms_dense_pair(*args), lib, "gms_dense_pair")
+    else:
+        removed = np.zeros(1, np.int32)
+        _check(lib.gms_dense_pair_filtered(*args, spk_size, spk_diff, removed.ctypes.data), lib, "gms_dense_pair_filtered")
+        more = dict(removed=int(removed[0]))
     k = min(int(count[0]), cap)
     return dict(points=xyz[:k], colors=cc[:k] if c == 3 else cc[:k, 0], pixel=pixel[:k], disp16=disp16, rect1=color if c == 3 else rect1,
-                rect2=rect2, valid=valid, plan=RectifyPlan(out_plan, cam), count=int(count[0]))
+                rect2=rect2, valid=valid, plan=RectifyPlan(out_plan, cam), count=int(count[0]), **more)
 
 
 def denseFuse(sources, neighbors=None, tol16=16, min_support=1, fused_cap=None):

@@ -955,16 +955,20 @@ class DensePairs:
     cloud (d_xyz [n, cap, 3], d_cloud_color [n, cap, channels], d_pixel [n, cap], d_count [n]), sized once, so that run() can be
     repeated or captured into a graph; it is one stream with no parallel branches. The kernels read d_tv when they run: a captured
     graph follows set_two_view(). d_tv may also be the tensor a two-view stage writes (pass d_tv=). With a registration
-    (set_registration) the points are in the world frame."""
+    (set_registration) the points are in the world frame. speckle = (max_speckle_size, max_diff16): gms_dense_pairs_filtered_device,
+    the speckle filter on d_disp16 between the matcher and the cloud, and d_removed int32 [n]; None: gms_dense_pairs_device."""
 
-    def __init__(self, ctx, n, src_size, out_size, camera, dist=None, channels=1, cap=None, min_disp16=16, params=None, device=None, d_tv=None):
-        from .api import dense_sgm_params
+    def __init__(self, ctx, n, src_size, out_size, camera, dist=None, channels=1, cap=None, min_disp16=16, params=None, device=None, d_tv=None,
+                 speckle=None):
+        from .api import dense_sgm_params, _speckle_pair
         self.ctx, self.n, self.channels, self.min_disp16 = ctx, int(n), int(channels), int(min_disp16)
+        self.speckle = None if speckle is None else _speckle_pair(speckle, "DensePairs")
         (self.sw, self.sh), (self.ow, self.oh) = (int(v) for v in src_size), (int(v) for v in out_size)
         self.camera = make_camera(camera, dist) if not isinstance(camera, np.ndarray) or camera.dtype != CAMERA_DTYPE else camera
         self.params = dense_sgm_params(params)
         self.cap = self.ow * self.oh if cap is None else int(cap)
-        self.ws_bytes = ctx.dense_pairs_workspace_bytes(self.sw, self.sh, self.channels, self.ow, self.oh, self.n, self.params)
+        ws_bytes = ctx.dense_pairs_workspace_bytes if self.speckle is None else ctx.dense_pairs_filtered_workspace_bytes
+        self.ws_bytes = ws_bytes(self.sw, self.sh, self.channels, self.ow, self.oh, self.n, self.params)
         if self.ws_bytes == 0:
             raise GmsError(GMS_ERR_BAD_ARG, "DensePairs: sizes, channels or matcher parameters outside what gms_dense_pairs_device accepts")
         dev = _device(ctx, device)
@@ -979,6 +983,7 @@ class DensePairs:
         k = max(self.cap, 1)
         self.d_xyz, self.d_cloud_color = z((self.n, k, 3), torch.float32), z((self.n, k, self.channels), torch.uint8)
         self.d_pixel, self.d_count = z((self.n, k), torch.int32), z((self.n,), torch.int32)
+        self.d_removed = None if self.speckle is None else z((self.n,), torch.int32)
         self.reg = None
         torch.cuda.synchronize(dev)
 
@@ -1003,13 +1008,65 @@ class DensePairs:
                 raise ValueError(f"images: contiguous uint8 device tensors {self.src_shape}")
         reg = {} if self.reg is None else dict(d_pairs=self.reg[0].data_ptr(), d_reg=self.reg[1].data_ptr(), d_views=self.reg[2].data_ptr(),
                                                n_frames=self.reg[3])
-        self.ctx.dense_pairs_device(self.camera, self.params, d_img1.data_ptr(), d_img2.data_ptr(), self.n, self.sw, self.sh, self.channels,
-                                    self.d_tv.data_ptr(), self.ow, self.oh, self.min_disp16, self.d_ws.data_ptr(), self.ws_bytes,
-                                    self.d_plans.data_ptr(), self.d_rect1.data_ptr(), self.d_rect2.data_ptr(), self.d_valid.data_ptr(),
-                                    None if self.d_color is None else self.d_color.data_ptr(), self.d_disp16.data_ptr(), self.cap,
-                                    self.d_xyz.data_ptr(), self.d_cloud_color.data_ptr(), self.d_pixel.data_ptr(), self.d_count.data_ptr(),
-                                    **reg)
+        args = (self.camera, self.params, d_img1.data_ptr(), d_img2.data_ptr(), self.n, self.sw, self.sh, self.channels, self.d_tv.data_ptr(),
+                self.ow, self.oh, self.min_disp16, self.d_ws.data_ptr(), self.ws_bytes, self.d_plans.data_ptr(), self.d_rect1.data_ptr(),
+                self.d_rect2.data_ptr(), self.d_valid.data_ptr(), None if self.d_color is None else self.d_color.data_ptr(),
+                self.d_disp16.data_ptr(), self.cap, self.d_xyz.data_ptr(), self.d_cloud_color.data_ptr(), self.d_pixel.data_ptr(),
+                self.d_count.data_ptr())
+        if self.speckle is None:
+            self.ctx.dense_pairs_device(*args, **reg)
+        else:
+            self.ctx.dense_pairs_filtered_device(*args, self.speckle[0], self.speckle[1], self.d_removed.data_ptr(), **reg)
         return self.d_count
+
+
+class SpeckleFilter:
+    """The workspace of gms_filter_speckles_device for n int16 maps of one size (w, h), and d_removed int32 [n], sized once, so that
+    run() can be repeated or captured into a graph; it is one stream with no parallel branches."""
+
+    def __init__(self, ctx, n, size, device=None):
+        self.ctx, self.n = ctx, int(n)
+        self.width, self.height = (int(v) for v in size)
+        self.ws_bytes = ctx.filter_speckles_workspace_bytes(self.width, self.height, self.n)
+        if self.ws_bytes == 0:
+            raise GmsError(GMS_ERR_BAD_ARG, "SpeckleFilter: width, height 1..8192 and n 1..65535")
+        dev = _device(ctx, device)
+        self.d_ws = torch.zeros((self.ws_bytes,), dtype=torch.uint8, device=dev)
+        self.d_removed = torch.zeros((self.n,), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+
+    def run(self, d_disp16, new_val, max_speckle_size, max_diff):
+        """filterSpeckles on d_disp16, a contiguous int16 device tensor [n, height, width], in place; the pixels changed per map in
+        d_removed. Stream-ordered on the context's stream; no allocation, no synchronisation."""
+        if d_disp16.dtype != torch.int16 or tuple(d_disp16.shape) != (self.n, self.height, self.width) or not d_disp16.is_contiguous():
+            raise ValueError(f"d_disp16: a contiguous int16 device tensor {(self.n, self.height, self.width)}")
+        self.ctx.filter_speckles_device(d_disp16.data_ptr(), self.n, self.width, self.height, new_val, max_speckle_size, max_diff,
+                                        self.d_ws.data_ptr(), self.ws_bytes, self.d_removed.data_ptr())
+        return d_disp16
+
+
+def filter_speckles_batch(maps, new_val, max_speckle_size, max_diff, ctx=None, return_removed=False):
+    """filterSpeckles for n maps in one gms_filter_speckles_device run. maps: int16 [n, H, W]; a host array gives new host arrays, a
+    contiguous device tensor is filtered in place and returned. return_removed=True: also the int32 [n] counts of pixels changed."""
+    from .api import default_context
+    ctx = ctx or default_context()
+    on_dev = isinstance(maps, torch.Tensor)
+    if on_dev:
+        d = maps
+        if d.dtype != torch.int16 or d.dim() != 3 or not d.is_contiguous():
+            raise ValueError("maps: a contiguous int16 device tensor [n, H, W]")
+    else:
+        m = np.asarray(maps)
+        if m.dtype != np.int16 or m.ndim != 3 or m.size == 0:
+            raise ValueError("maps: int16 [n, H, W]")
+        d = torch.from_numpy(np.ascontiguousarray(m)).cuda()
+    n, h, w = d.shape
+    run = SpeckleFilter(ctx, n, (w, h), d.device)
+    run.run(d, new_val, max_speckle_size, max_diff)
+    ctx.synchronize()
+    out = d if on_dev else d.cpu().numpy()
+    removed = run.d_removed if on_dev else run.d_removed.cpu().numpy()
+    return (out, removed) if return_removed else out
 
 
 def dense_fuse_sources(run, frame_a=None):

@@ -101,6 +101,14 @@ SIGNATURES = {
     "gms_dense_fuse_workspace_bytes": (sz, [i32, i32]),
     "gms_dense_fuse_device": (i32, [vp, vp, i32, i32, vp, i32, i32, i32, i32, vp, sz, i32, vp, vp, vp, vp, vp, vp, vp]),
     "gms_dense_fuse": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "gms_filter_speckles_workspace_bytes": (sz, [i32, i32, i32]),
+    "gms_filter_speckles_device": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+    "gms_filter_speckles": (i32, [vp, i32, i32, i32, i32, i32, vp]),
+    "gms_dense_pairs_filtered_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32, vp]),
+    "gms_dense_pairs_filtered_device": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, i32, vp, sz, vp, vp, vp, vp, vp,
+                                              vp, i32, vp, vp, vp, vp, i32, i32, vp]),
+    "gms_dense_pair_filtered": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32,
+                                      vp]),
     "gms_chess_candidates_workspace_bytes": (sz, [i32, i32, i32]),
     "gms_chess_candidates_device": (i32, [vp, vp, i32, i32, i32, i32, vp, sz, vp, vp]),
     "gms_corner_subpix_device": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, dbl, vp]),

@@ -32,6 +32,7 @@
 #include "twoview_core.h"
 #include "rectify_core.h"
 #include "dense_fuse_core.h"
+#include "speckle_core.h"
 #include "warp_core.h"
 #include "calib_core.h"
 
@@ -1666,9 +1667,11 @@ static hipError_t dense_pairs_launch(const gms_camera& cam, const gms_stereo_sgm
                                      const gms_sfm_pair_reg* d_reg, const gms_sfm_view* d_views, int n_frames, void* d_ws,
                                      const gms_rectify_plan* d_plans, uint8_t* d_rect1, uint8_t* d_rect2, uint8_t* d_valid, uint8_t* d_color,
                                      int16_t* d_disp16, int cap, float* d_xyz, uint8_t* d_cloud_color, int32_t* d_pixel, int32_t* d_count,
-                                     hipStream_t st)
+                                     int speckle_size, int speckle_diff16, int32_t* d_removed, hipStream_t st)
 {
-    const gms::DensePairsLayout L = gms::dense_pairs_layout(n, sw, sh, channels, ow, oh, gms::stereo_sgm_ws_bytes(p, n, ow, oh));
+    // speckle_size > 0: the workspace is DensePairsFilteredLayout's, whose first regions are DensePairsLayout's
+    const gms::DensePairsFilteredLayout F = gms::dense_pairs_filtered_layout(n, sw, sh, channels, ow, oh, gms::stereo_sgm_ws_bytes(p, n, ow, oh));
+    const gms::DensePairsLayout& L = F.pairs;
     const uint8_t *g1 = d_img1, *g2 = d_img2;
     hipError_t e;
     if (channels == 3) {
@@ -1683,24 +1686,42 @@ static hipError_t dense_pairs_launch(const gms_camera& cam, const gms_stereo_sgm
     if ((e = gms::launch_rectify(cam, g1, n, sw, sh, 1, sw, d_plans, n, 1, d_rect1, ow, oh, ow, d_valid, st)) != hipSuccess) return e;
     if ((e = gms::launch_rectify(cam, g2, n, sw, sh, 1, sw, d_plans, n, 2, d_rect2, ow, oh, ow, nullptr, st)) != hipSuccess) return e;
     if ((e = gms::launch_stereo_sgm(p, d_rect1, d_rect2, n, ow, oh, ow, gms::ws_ptr<void>(d_ws, L.sgm), d_disp16, nullptr, st)) != hipSuccess) return e;
+    if (speckle_size > 0)
+        e = gms::launch_filter_speckles(d_disp16, n, ow, oh, (p.bm.min_disparity - 1) * 16, speckle_size, speckle_diff16,
+                                        gms::ws_ptr<void>(d_ws, F.speckle), d_removed, st);
+    else if (d_removed)
+        e = hipMemsetAsync(d_removed, 0, sizeof(int32_t) * (size_t)n, st);
+    if (e != hipSuccess) return e;
     return gms::launch_dense_cloud(d_disp16, d_valid, channels == 3 ? d_color : d_rect1, channels, channels * ow, n, ow, oh, d_plans,
                                    (p.bm.min_disparity - 1) * 16, min_disp16, d_pairs, d_reg, d_views, n_frames, gms::ws_ptr<void>(d_ws, L.cloud), cap,
                                    d_xyz, d_cloud_color, d_pixel, d_count, st);
 }
 
-int gms_dense_pairs_device(gms_ctx* c, const gms_camera* camera, const gms_stereo_sgm_params* params, const uint8_t* d_img1, const uint8_t* d_img2,
-                           int n_pairs, int sw, int sh, int channels, const gms_two_view* d_tv, int ow, int oh, int min_disp16,
-                           const gms_pair* d_pairs, const gms_sfm_pair_reg* d_reg, const gms_sfm_view* d_views, int n_frames, void* d_ws,
-                           size_t ws_bytes, gms_rectify_plan* d_plans, uint8_t* d_rect1, uint8_t* d_rect2, uint8_t* d_valid, uint8_t* d_color,
-                           int16_t* d_disp16, int cap, float* d_xyz, uint8_t* d_cloud_color, int32_t* d_pixel, int32_t* d_count)
+size_t gms_dense_pairs_filtered_workspace_bytes(int sw, int sh, int channels, int ow, int oh, int n_pairs, const gms_stereo_sgm_params* params)
+{
+    const gms_stereo_sgm_params& p = dense_sgm_params(params);
+    if (!dense_shape_ok(sw, sh, channels, ow, oh, n_pairs, p)) return 0;
+    const size_t sgm_bytes = gms::stereo_sgm_ws_bytes(p, n_pairs, ow, oh);
+    return sgm_bytes ? gms::dense_pairs_filtered_layout(n_pairs, sw, sh, channels, ow, oh, sgm_bytes).total : 0;
+}
+
+// filtered: the workspace also holds the filter's region (also with speckle_size 0, so that one size serves every call)
+static int dense_pairs_device(gms_ctx* c, const gms_camera* camera, const gms_stereo_sgm_params* params, const uint8_t* d_img1, const uint8_t* d_img2,
+                              int n_pairs, int sw, int sh, int channels, const gms_two_view* d_tv, int ow, int oh, int min_disp16,
+                              const gms_pair* d_pairs, const gms_sfm_pair_reg* d_reg, const gms_sfm_view* d_views, int n_frames, void* d_ws,
+                              size_t ws_bytes, gms_rectify_plan* d_plans, uint8_t* d_rect1, uint8_t* d_rect2, uint8_t* d_valid, uint8_t* d_color,
+                              int16_t* d_disp16, int cap, float* d_xyz, uint8_t* d_cloud_color, int32_t* d_pixel, int32_t* d_count, bool filtered,
+                              int speckle_size, int speckle_diff16, int32_t* d_removed)
 {
     const gms_stereo_sgm_params& p = dense_sgm_params(params);
     if (!c || !camera || !dense_shape_ok(sw, sh, channels, ow, oh, n_pairs, p) || min_disp16 < 1 || cap < 0) return GMS_ERR_BAD_ARG;
+    if (speckle_size < 0 || speckle_diff16 < 0 || (reinterpret_cast<uintptr_t>(d_removed) & 3u)) return GMS_ERR_BAD_ARG;
     const bool any_reg = d_pairs || d_reg || d_views, all_reg = d_pairs && d_reg && d_views;
     if (!d_img1 || !d_img2 || !d_tv || !d_ws || !d_plans || !d_rect1 || !d_rect2 || !d_valid || (channels == 3 && !d_color) || !d_disp16 ||
         !d_count || (cap > 0 && (!d_xyz || !d_pixel)) || any_reg != all_reg || (all_reg && n_frames < 1))
         return GMS_ERR_BAD_ARG;
-    const size_t need = gms_dense_pairs_workspace_bytes(sw, sh, channels, ow, oh, n_pairs, &p);
+    const size_t need = filtered ? gms_dense_pairs_filtered_workspace_bytes(sw, sh, channels, ow, oh, n_pairs, &p)
+                                 : gms_dense_pairs_workspace_bytes(sw, sh, channels, ow, oh, n_pairs, &p);
     if ((reinterpret_cast<uintptr_t>(d_ws) & 255u) || (reinterpret_cast<uintptr_t>(d_plans) & 7u) || (reinterpret_cast<uintptr_t>(d_disp16) & 1u) ||
         (reinterpret_cast<uintptr_t>(d_xyz) & 3u) || (reinterpret_cast<uintptr_t>(d_pixel) & 3u) || (reinterpret_cast<uintptr_t>(d_count) & 3u) ||
         need == 0 || ws_bytes < need)
@@ -1709,28 +1730,54 @@ int gms_dense_pairs_device(gms_ctx* c, const gms_camera* camera, const gms_stere
         const hipError_t e = gms::launch_rectify_plan(*camera, d_tv, n_pairs, sw, sh, ow, oh, d_plans, c->stream);
         if (e != hipSuccess) return e;
         return dense_pairs_launch(*camera, p, d_img1, d_img2, n_pairs, sw, sh, channels, ow, oh, min_disp16, d_pairs, d_reg, d_views, n_frames, d_ws,
-                                  d_plans, d_rect1, d_rect2, d_valid, d_color, d_disp16, cap, d_xyz, d_cloud_color, d_pixel, d_count, c->stream);
+                                  d_plans, d_rect1, d_rect2, d_valid, d_color, d_disp16, cap, d_xyz, d_cloud_color, d_pixel, d_count, speckle_size,
+                                  speckle_diff16, d_removed, c->stream);
     });
 }
 
-int gms_dense_pair(const gms_camera* camera, const gms_stereo_sgm_params* params, const uint8_t* img1, const uint8_t* img2, int width, int height,
-                   int channels, const double* R, const double* t, int out_w, int out_h, int min_disp16, gms_rectify_plan* plan, uint8_t* rect1,
-                   uint8_t* rect2, uint8_t* valid, uint8_t* color, int16_t* disp16, int cap, float* xyz, uint8_t* cloud_color, int32_t* pixel,
-                   int32_t* count)
+int gms_dense_pairs_device(gms_ctx* c, const gms_camera* camera, const gms_stereo_sgm_params* params, const uint8_t* d_img1, const uint8_t* d_img2,
+                           int n_pairs, int sw, int sh, int channels, const gms_two_view* d_tv, int ow, int oh, int min_disp16,
+                           const gms_pair* d_pairs, const gms_sfm_pair_reg* d_reg, const gms_sfm_view* d_views, int n_frames, void* d_ws,
+                           size_t ws_bytes, gms_rectify_plan* d_plans, uint8_t* d_rect1, uint8_t* d_rect2, uint8_t* d_valid, uint8_t* d_color,
+                           int16_t* d_disp16, int cap, float* d_xyz, uint8_t* d_cloud_color, int32_t* d_pixel, int32_t* d_count)
+{
+    return dense_pairs_device(c, camera, params, d_img1, d_img2, n_pairs, sw, sh, channels, d_tv, ow, oh, min_disp16, d_pairs, d_reg, d_views, n_frames,
+                              d_ws, ws_bytes, d_plans, d_rect1, d_rect2, d_valid, d_color, d_disp16, cap, d_xyz, d_cloud_color, d_pixel, d_count, false,
+                              0, 0, nullptr);
+}
+
+int gms_dense_pairs_filtered_device(gms_ctx* c, const gms_camera* camera, const gms_stereo_sgm_params* params, const uint8_t* d_img1,
+                                    const uint8_t* d_img2, int n_pairs, int sw, int sh, int channels, const gms_two_view* d_tv, int ow, int oh,
+                                    int min_disp16, const gms_pair* d_pairs, const gms_sfm_pair_reg* d_reg, const gms_sfm_view* d_views, int n_frames,
+                                    void* d_ws, size_t ws_bytes, gms_rectify_plan* d_plans, uint8_t* d_rect1, uint8_t* d_rect2, uint8_t* d_valid,
+                                    uint8_t* d_color, int16_t* d_disp16, int cap, float* d_xyz, uint8_t* d_cloud_color, int32_t* d_pixel,
+                                    int32_t* d_count, int speckle_size, int speckle_diff16, int32_t* d_removed)
+{
+    return dense_pairs_device(c, camera, params, d_img1, d_img2, n_pairs, sw, sh, channels, d_tv, ow, oh, min_disp16, d_pairs, d_reg, d_views, n_frames,
+                              d_ws, ws_bytes, d_plans, d_rect1, d_rect2, d_valid, d_color, d_disp16, cap, d_xyz, d_cloud_color, d_pixel, d_count, true,
+                              speckle_size, speckle_diff16, d_removed);
+}
+
+int gms_dense_pair_filtered(const gms_camera* camera, const gms_stereo_sgm_params* params, const uint8_t* img1, const uint8_t* img2, int width,
+                            int height, int channels, const double* R, const double* t, int out_w, int out_h, int min_disp16, gms_rectify_plan* plan,
+                            uint8_t* rect1, uint8_t* rect2, uint8_t* valid, uint8_t* color, int16_t* disp16, int cap, float* xyz,
+                            uint8_t* cloud_color, int32_t* pixel, int32_t* count, int speckle_size, int speckle_diff16, int32_t* removed)
 {
     const gms_stereo_sgm_params& p = dense_sgm_params(params);
     if (!camera || !img1 || !img2 || !R || !t || !plan || !count || min_disp16 < 1 || cap < 0 || (cap > 0 && (!xyz || !pixel))) return GMS_ERR_BAD_ARG;
+    if (speckle_size < 0 || speckle_diff16 < 0) return GMS_ERR_BAD_ARG;
     const int rc = gms_rectify_plan_host(camera, R, t, width, height, out_w, out_h, plan);
     if (rc != GMS_OK) return rc;
     if (plan->status != GMS_OK) return GMS_ERR_NO_MODEL;
     const int ow = plan->out_w, oh = plan->out_h;
-    const size_t ws = gms_dense_pairs_workspace_bytes(width, height, channels, ow, oh, 1, &p);
+    const size_t ws = speckle_size > 0 ? gms_dense_pairs_filtered_workspace_bytes(width, height, channels, ow, oh, 1, &p)
+                                       : gms_dense_pairs_workspace_bytes(width, height, channels, ow, oh, 1, &p);
     if (ws == 0) return GMS_ERR_BAD_ARG;
     const size_t s_bytes = (size_t)width * (size_t)height * (size_t)channels, px = (size_t)ow * (size_t)oh, ucap = (size_t)cap;
     gms::BlockLayout lay;
     const size_t o_1 = lay.add(s_bytes), o_2 = lay.add(s_bytes), o_plan = lay.add(sizeof(gms_rectify_plan)), o_ws = lay.add(ws), o_r1 = lay.add(px),
                  o_r2 = lay.add(px), o_v = lay.add(px), o_c = lay.add(3 * px), o_d = lay.add(2 * px), o_xyz = lay.add(12 * ucap + 4),
-                 o_cc = lay.add(3 * ucap + 4), o_pix = lay.add(4 * ucap + 4), o_n = lay.add(4);
+                 o_cc = lay.add(3 * ucap + 4), o_pix = lay.add(4 * ucap + 4), o_n = lay.add(4), o_rm = lay.add(4);
     DevBlock blk(lay, nullptr);
     blk.in(o_1, img1, s_bytes);
     blk.in(o_2, img2, s_bytes);
@@ -1739,11 +1786,13 @@ int gms_dense_pair(const gms_camera* camera, const gms_stereo_sgm_params* params
         return dense_pairs_launch(*camera, p, blk.at<uint8_t>(o_1), blk.at<uint8_t>(o_2), 1, width, height, channels, ow, oh, min_disp16, nullptr, nullptr,
                                   nullptr, 0, blk.at(o_ws), blk.at<gms_rectify_plan>(o_plan), blk.at<uint8_t>(o_r1), blk.at<uint8_t>(o_r2),
                                   blk.at<uint8_t>(o_v), blk.at<uint8_t>(o_c), blk.at<int16_t>(o_d), cap, blk.at<float>(o_xyz),
-                                  cloud_color ? blk.at<uint8_t>(o_cc) : nullptr, blk.at<int32_t>(o_pix), blk.at<int32_t>(o_n), st);
+                                  cloud_color ? blk.at<uint8_t>(o_cc) : nullptr, blk.at<int32_t>(o_pix), blk.at<int32_t>(o_n), speckle_size,
+                                  speckle_diff16, removed ? blk.at<int32_t>(o_rm) : nullptr, st);
     });
     int32_t n = 0;
     blk.out_now(&n, o_n, 4);
     *count = n;
+    if (removed) blk.out(removed, o_rm, 4);
     const size_t k = (size_t)(n < cap ? n : cap);
     if (rect1) blk.out(rect1, o_r1, px);
     if (rect2) blk.out(rect2, o_r2, px);
@@ -1755,6 +1804,51 @@ int gms_dense_pair(const gms_camera* camera, const gms_stereo_sgm_params* params
         blk.out(pixel, o_pix, 4 * k);
         if (cloud_color) blk.out(cloud_color, o_cc, (size_t)channels * k);
     }
+    return blk.finish();
+}
+
+int gms_dense_pair(const gms_camera* camera, const gms_stereo_sgm_params* params, const uint8_t* img1, const uint8_t* img2, int width, int height,
+                   int channels, const double* R, const double* t, int out_w, int out_h, int min_disp16, gms_rectify_plan* plan, uint8_t* rect1,
+                   uint8_t* rect2, uint8_t* valid, uint8_t* color, int16_t* disp16, int cap, float* xyz, uint8_t* cloud_color, int32_t* pixel,
+                   int32_t* count)
+{
+    return gms_dense_pair_filtered(camera, params, img1, img2, width, height, channels, R, t, out_w, out_h, min_disp16, plan, rect1, rect2, valid, color,
+                                   disp16, cap, xyz, cloud_color, pixel, count, 0, 0, nullptr);
+}
+
+// ---- the speckle filter (speckle_kernels.hip, speckle_core.h) ------------------------------------------------------
+size_t gms_filter_speckles_workspace_bytes(int width, int height, int n)
+{
+    if (!spk::args_ok(width, height, n, 0, 0, 0)) return 0;
+    return gms::speckle_ws_bytes(n, width, height);
+}
+
+int gms_filter_speckles_device(gms_ctx* c, int16_t* d_disp16, int n, int width, int height, int new_val, int max_speckle_size, int max_diff,
+                               void* d_ws, size_t ws_bytes, int32_t* d_removed)
+{
+    if (!c || !spk::args_ok(width, height, n, new_val, max_speckle_size, max_diff) || !d_disp16 || !d_ws) return GMS_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_ws) & 255u) || (reinterpret_cast<uintptr_t>(d_disp16) & 1u) || (reinterpret_cast<uintptr_t>(d_removed) & 3u) ||
+        ws_bytes < gms::speckle_ws_bytes(n, width, height))
+        return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] {
+        return gms::launch_filter_speckles(d_disp16, n, width, height, new_val, max_speckle_size, max_diff, d_ws, d_removed, c->stream);
+    });
+}
+
+int gms_filter_speckles(int16_t* disp16, int width, int height, int new_val, int max_speckle_size, int max_diff, int32_t* removed)
+{
+    if (!spk::args_ok(width, height, 1, new_val, max_speckle_size, max_diff) || !disp16) return GMS_ERR_BAD_ARG;
+    const size_t bytes = 2 * (size_t)width * (size_t)height;
+    gms::BlockLayout lay;
+    const size_t o_d = lay.add(bytes), o_ws = lay.add(gms::speckle_ws_bytes(1, width, height)), o_rm = lay.add(4);
+    DevBlock blk(lay, nullptr);
+    blk.in(o_d, disp16, bytes);
+    blk.run([&](hipStream_t st) {
+        return gms::launch_filter_speckles(blk.at<int16_t>(o_d), 1, width, height, new_val, max_speckle_size, max_diff, blk.at(o_ws),
+                                           blk.at<int32_t>(o_rm), st);
+    });
+    blk.out(disp16, o_d, bytes);
+    if (removed) blk.out(removed, o_rm, 4);
     return blk.finish();
 }
 

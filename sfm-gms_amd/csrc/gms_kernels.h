@@ -273,6 +273,10 @@ size_t     dense_fuse_ws_bytes(int n_src, int max_cap);
 hipError_t launch_dense_fuse(const gms_dense_fuse_src* d_src, int n_src, int max_cap, const int32_t* d_neighbors, int n_nb, int channels, int tol16,
                              int min_support, void* d_ws, int fused_cap, float* d_xyz, uint8_t* d_color, int32_t* d_source, int32_t* d_index,
                              uint8_t* d_support, uint8_t* d_conflict, int32_t* d_counts, hipStream_t stream);
+// the speckle filter on int16 maps, in place (speckle_kernels.hip; shared parts in speckle_core.h; workspace: ws_layout.h SpeckleLayout)
+size_t     speckle_ws_bytes(int n, int W, int H);
+hipError_t launch_filter_speckles(int16_t* d_disp16, int n, int W, int H, int new_val, int max_speckle_size, int max_diff, void* d_ws,
+                                  int32_t* d_removed, hipStream_t stream);
 // chessboard corner candidates and cornerSubPix (calib_kernels.hip; arithmetic in calib_core.h; workspace: ws_layout.h ChessLayout)
 size_t     chess_candidates_ws_bytes(int n, int w, int h);
 hipError_t launch_chess_candidates(const uint8_t* d_images, int n, int w, int h, int max_candidates, void* d_ws,

@@ -431,4 +431,34 @@ inline DenseFuseLayout dense_fuse_layout(int n_src, int max_cap)
     return {c.take(4 * nb, 256), c.take(2 * nb * kFuseBlockPoints, 256), c.end};
 }
 
+// ---- the speckle filter (speckle_kernels.hip) ---------------------------------------------------------------------------------------
+// Every call writes every word it later reads: the tile kernel writes both planes whole.
+struct SpeckleLayout {
+    size_t label;  // int32 [n][H][W]: union-find over pixel indices within the image; -1 where the pixel is new_val
+    size_t size;   // int32 [n][H][W]: at a tile-local root the pixels of its tile-local component, at a global root the component's
+    size_t total;
+};
+inline SpeckleLayout speckle_layout(int n, int W, int H)
+{
+    const size_t px = (size_t)n * (size_t)W * (size_t)H;  // n <= 65535, W, H <= 8192: below 2^42
+    WsCursor c;
+    return {c.take(4 * px, 256), c.take(4 * px, 256), c.end};
+}
+
+// ---- the dense stage with the speckle filter behind the matcher (gms_dense_pairs_filtered_device) -------------------------------------
+// DensePairsLayout's regions unchanged, then the filter's own: it aliases none of the matcher's volumes.
+struct DensePairsFilteredLayout {
+    DensePairsLayout pairs;
+    size_t speckle;  // SpeckleLayout of the rectified size
+    size_t total;
+};
+inline DensePairsFilteredLayout dense_pairs_filtered_layout(int n, int sw, int sh, int channels, int ow, int oh, size_t sgm_bytes)
+{
+    const DensePairsLayout P = dense_pairs_layout(n, sw, sh, channels, ow, oh, sgm_bytes);
+    WsCursor c;
+    c.take(P.total, 256);
+    const size_t speckle = c.take(speckle_layout(n, ow, oh).total, 256);
+    return {P, speckle, c.end};
+}
+
 }  // namespace gms

@@ -669,6 +669,21 @@ inline DenseCloud denseStereo(const std::vector<uint8_t>& img1, const std::vecto
     return out;
 }
 
+// ---- the speckle filter -----------------------------------------------------------------------------------------------
+// cv::filterSpeckles(img, newVal, maxSpeckleSize, maxDiff) for a CV_16S map, in cv's argument order: disp is a flat row-major int16
+// map [height][width], filtered in place by gms_filter_speckles, synchronously on the current HIP device. maxDiff is in the map's
+// own units (sixteenths of a pixel for stereoBM's and stereoSGM's maps, whose newVal is (min_disparity - 1) * 16). Returns the number
+// of pixels changed.
+inline int filterSpeckles(std::vector<int16_t>& disp, int width, int height, int newVal, int maxSpeckleSize, int maxDiff)
+{
+    if (width <= 0 || height <= 0 || disp.size() != (size_t)width * (size_t)height)
+        throw std::invalid_argument("mi355::filterSpeckles: a width * height int16 map");
+    int32_t removed = 0;
+    const int rc = gms_filter_speckles(disp.data(), width, height, newVal, maxSpeckleSize, maxDiff, &removed);
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::filterSpeckles: ") + gms_error_string(rc));
+    return removed;
+}
+
 // ---- the clouds of several posed pairs fused into one by depth consistency --------------------------------------------
 // A source is one pair's output of the dense stage (what denseStereo returns holds plan, points, colors, disp16 and valid), with the
 // view of the pair's frame_a (x_camera = R x_world + t) and the pair's registration when the clouds were made in a world frame.

@@ -230,7 +230,8 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
                descriptor="grad", withRotation=False, withScale=False, thresholdFactor=6.0, prob=0.7, ransac_threshold=1.0, max_iters=1000,
                device=None, dictionary=None, logos_capacity=None, cross_check=True, distance_coef=4.0, max_size=500, train_dictionary=None,
                keep_tables=False, detector="fast", contrast=128, refine=False, register=False, root=0, min_links=8, bundle=False, dense=False,
-               min_disp16=16, dense_cap=None, dense_sgm=None, fuse=False, fuse_tol16=16, fuse_min_support=1, fuse_cap=None, **ba):
+               min_disp16=16, dense_cap=None, dense_sgm=None, fuse=False, fuse_tol16=16, fuse_min_support=1, fuse_cap=None, dense_speckle=None,
+               **ba):
     """run_dataset from pixels. images: [n, H, W] grey or [n, H, W, 3] BGR, 8-bit, a host array or a device tensor (or a list of equally
     sized images). BGR goes through gms_bgr_to_gray_device; the pyramid keypoint source (threshold, max_keypoints, n_levels; detector
     "fast", or "dog" with `contrast` in the place of `threshold`: gms_detect_dog_batch_device, with refine=True
@@ -245,6 +246,9 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
     (gms_dense_pairs_device on the photographs themselves; min_disp16, dense_cap = the most points per pair, dense_sgm = the
     matcher's keywords). The points are in frame_a's frame and the pair's unit, as points3d; with register=True in the world frame,
     as points_world, and a pair the registration does not use has none. dense=False returns the dict without.
+    dense_speckle = (max_speckle_size, max_diff16): the speckle filter on every pair's disparity map between the matcher and the
+    cloud (gms_dense_pairs_filtered_device; max_diff16 in sixteenths of a pixel); each `dense` entry then also holds `removed`, and
+    the fusion reads the filtered maps. None: no filter.
     fuse=True (needs dense=True and register=True: without a registration the clouds share no frame) adds
     `dense_fused`, the pairs' clouds fused into one by depth consistency (gms_dense_fuse_device on the maps, plans, views and scales
     still resident on the device): a dict of points float32 [k, 3], colors, source int32 [k] (an index into `pairs`), index int32 [k]
@@ -296,7 +300,7 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
         r = _run_gms(ctx, frames, descs, src, None, withRotation, withScale, thresholdFactor, *tail)
     if dense:
         runs = [] if fuse else None       # (the runs' device buffers stay alive until the fusion has read them)
-        r.update(dense=_dense_pairs(ctx, d_photos, r, camera, dist, min_disp16, dense_cap, dense_sgm, reg is not None, runs))
+        r.update(dense=_dense_pairs(ctx, d_photos, r, camera, dist, min_disp16, dense_cap, dense_sgm, reg is not None, runs, dense_speckle))
         if fuse:
             r.update(dense_fused=_dense_fuse(ctx, runs, len(src), 3 if d_photos.dim() == 4 else 1, fuse_tol16, fuse_min_support, fuse_cap))
     if keep_tables:
@@ -304,7 +308,7 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
     return r
 
 
-def _dense_pairs(ctx, d_photos, r, camera, dist, min_disp16, cap, sgm, registered, keep=None):
+def _dense_pairs(ctx, d_photos, r, camera, dist, min_disp16, cap, sgm, registered, keep=None, speckle=None):
     """run_images' dense=True: gms_dense_pairs_device for the pairs with a pose, one run per output size (the source's size, and its
     transpose for the pairs whose baseline is nearer the vertical), on the two-view records and the registration that `r` holds.
     keep: a list that gets (run, pair indices) of every run, for the fusion."""
@@ -321,7 +325,8 @@ def _dense_pairs(ctx, d_photos, r, camera, dist, min_disp16, cap, sgm, registere
         if plan.ok:
             groups.setdefault(plan.out_size, []).append(i)
     for size, idx in groups.items():
-        run = DensePairs(ctx, len(idx), (w, h), size, camera, dist, channels, cap=cap, min_disp16=min_disp16, params=sgm, device=d_photos.device)
+        run = DensePairs(ctx, len(idx), (w, h), size, camera, dist, channels, cap=cap, min_disp16=min_disp16, params=sgm, device=d_photos.device,
+                         speckle=speckle)
         run.set_two_view(tv[idx])
         if registered:
             sub = pairs[idx].copy()
@@ -335,11 +340,14 @@ def _dense_pairs(ctx, d_photos, r, camera, dist, min_disp16, cap, sgm, registere
         if keep is not None:
             keep.append((run, idx))
         counts, plans = run.d_count.cpu().numpy(), run.plans()
+        removed = None if speckle is None else run.d_removed.cpu().numpy()
         for j, i in enumerate(idx):
             k = min(int(counts[j]), run.cap)
             colors = run.d_cloud_color[j, :k].cpu().numpy()
             out[i] = dict(points=run.d_xyz[j, :k].cpu().numpy(), colors=colors if channels == 3 else colors[:, 0],
                           pixel=run.d_pixel[j, :k].cpu().numpy(), count=int(counts[j]), plan=plans[j:j + 1])
+            if removed is not None:
+                out[i].update(removed=int(removed[j]))
     return out
 
 

@@ -5,12 +5,15 @@ file on the host. Prints one JSON line: the turn chosen, the share of rectified 
 the sparse cloud's, and the median distance (in the pair's unit, |t| = 1) from each sparse triangulated point to the dense point at
 its rectified pixel.
 
-    python tools/gms_dense_pair.py [pair.npz] [--method gms|bf|logos] [--max-keypoints 10000] [--num-disparities 128] [--min-disp16 16] [--check] [--ply cloud.ply]
+    python tools/gms_dense_pair.py [pair.npz] [--method gms|bf|logos] [--max-keypoints 10000] [--num-disparities 128] [--min-disp16 16] [--speckle SIZE,DIFF16] [--check] [--ply cloud.ply]
 
 pair.npz: arrays left, right ([H, W] grey or [H, W, 3] BGR, uint8) and camera = (fx, fy, cx, cy), optionally dist; default: the
 committed pair of the reference's SourceImages, tests/golden/image_sfm_pair_1008x756.npz (its camera is stated, not calibrated).
 --check: the numpy statement (tests/rectify_ref.py) beside it: the plan, both rectified images, the valid plane and the cloud of the
-stage's own disparity map must be equal byte for byte (the matcher has its own check, tools/stereo_sgm_bench.py --check)."""
+stage's own disparity map must be equal byte for byte (the matcher has its own check, tools/stereo_sgm_bench.py --check).
+--speckle SIZE,DIFF16: filterSpeckles on the matcher's map before the reprojection (DIFF16 in sixteenths of a
+pixel); the line then states the pixels removed, and --check also runs the stage without the filter and compares the filtered map
+with the numpy statement (tests/speckle_ref.py) of the unfiltered one."""
 import argparse
 import importlib
 import json
@@ -41,6 +44,7 @@ def main():
     ap.add_argument("--max-keypoints", type=int, default=10000)
     ap.add_argument("--num-disparities", type=int, default=128)
     ap.add_argument("--min-disp16", type=int, default=16)
+    ap.add_argument("--speckle", help="SIZE,DIFF16")
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--ply")
     a = ap.parse_args()
@@ -57,9 +61,12 @@ def main():
     if not plan.ok:
         print(json.dumps(line))
         return 1
-    r = pkg.denseStereo(left, right, camera, dist, sfm["R"], sfm["t"], min_disp16=a.min_disp16, num_disparities=a.num_disparities)
+    speckle = tuple(int(v) for v in a.speckle.split(",")) if a.speckle else None
+    r = pkg.denseStereo(left, right, camera, dist, sfm["R"], sfm["t"], min_disp16=a.min_disp16, num_disparities=a.num_disparities, speckle=speckle)
     ow, oh = plan.out_size
     line.update(valid_share=round(float((r["valid"] != 0).mean()), 4), dense_points=int(r["count"]))
+    if speckle:
+        line.update(speckle=list(speckle), speckle_removed=int(r["removed"]))
     # every sparse point at its rectified pixel: the dense point there, when there is one
     X = np.asarray(sfm["points3D"], dtype=np.float64)
     p = X @ plan["R1"].T
@@ -86,6 +93,12 @@ def main():
         chk = {"plan": plan.record.tobytes() == ref.tobytes(), "rect1": grey1 is None or bool(np.array_equal(grey1, r1)),
                "rect2": left.ndim != 2 or bool(np.array_equal(r["rect2"], r2)), "valid": bool(np.array_equal(r["valid"], v1)),
                "cloud": r["points"].tobytes() == xyz.tobytes() and bool(np.array_equal(r["pixel"], pixel)) and bool(np.array_equal(r["colors"], colors))}
+        if speckle:
+            import speckle_ref
+            plain = pkg.denseStereo(left, right, camera, dist, sfm["R"], sfm["t"], min_disp16=a.min_disp16, num_disparities=a.num_disparities)
+            want, n_want = speckle_ref.components(plain["disp16"], -16, *speckle)
+            chk["speckle"] = r["disp16"].tobytes() == want.tobytes() and int(r["removed"]) == n_want
+            line["dense_points_unfiltered"] = int(plain["count"])
         line["check_vs_numpy"] = chk
         ok = all(chk.values())
     if a.ply:

@@ -3,7 +3,7 @@
 pipeline.run_images(register=True): per pair the two-view stage, then gms_sfm_register_device joins the pairs).
 Prints one JSON line: per pair n_links, r, S and status; per view the camera centre; tracks by length; the median spread.
 
-    python tools/gms_sfm_sequence.py [images.npz] [--method gms|bf|logos] [--pairs chain|star|all] [--root 0] [--min-links 8] [--max-keypoints 2000] [--ply out.ply] [--bundle] [--dense [--fuse [--fuse-tol16 16] [--fuse-min-support 1]]] [--check]
+    python tools/gms_sfm_sequence.py [images.npz] [--method gms|bf|logos] [--pairs chain|star|all] [--root 0] [--min-links 8] [--max-keypoints 2000] [--ply out.ply] [--bundle] [--dense [--speckle SIZE,DIFF16] [--fuse [--fuse-tol16 16] [--fuse-min-support 1]]] [--check]
 
 images.npz: arrays images ([n, H, W] grey or [n, H, W, 3] BGR, uint8) and camera = (fx, fy, cx, cy), optionally dist. Default: views
 1, 2, 3, 4 of the reference's SourceImages scene from the two committed fixtures (tests/golden/image_sfm_pair_1008x756.npz holds views 1
@@ -16,7 +16,9 @@ centres after; with --check also against tests/sfm_ba_ref.py under the tolerance
 cloud of every pair; --fuse: the clouds fused into one by depth consistency (gms_dense_fuse_device):
 the points per pair, the fused total and a histogram of `support`; --ply then writes the fused cloud (x, y, z, the colour, support);
 with --check the dense stage is run once more to read its maps back, the numpy statement (tests/dense_fuse_ref.py) fuses them, and
-every output byte is compared."""
+every output byte is compared. --speckle SIZE,DIFF16 (with --dense): the speckle filter on every pair's map before the reprojection
+(DIFF16 in sixteenths of a pixel): the pixels removed per pair; with --check the stage is run with and without the
+filter, and the filtered maps and clouds must equal the numpy statements (tests/speckle_ref.py, tests/rectify_ref.py)."""
 import argparse
 import importlib
 import json
@@ -60,6 +62,35 @@ def write_fused_ply(path, f):
             out.write(f"{p[0]:.9g} {p[1]:.9g} {p[2]:.9g} {int(c[2])} {int(c[1])} {int(c[0])} {int(s)}\n")
 
 
+def check_speckle(r, images, camera, dist, a):
+    """--dense --speckle --check: the dense stage once more with and without the filter, the maps read back: every filtered map must
+    equal the numpy statement (tests/speckle_ref.py) of the unfiltered one, and the cloud the numpy chain (tests/rectify_ref.py) on
+    the filtered map. Test infrastructure."""
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import rectify_ref
+    import speckle_ref
+    pipeline = importlib.import_module("sfm-gms_amd.pipeline")
+    ctx = importlib.import_module("sfm-gms_amd.api").default_context()
+    d_photos = torch.from_numpy(np.ascontiguousarray(images)).to(f"cuda:{ctx.device}")
+    plain, filt = [], []
+    pipeline._dense_pairs(ctx, d_photos, r, camera, dist, 16, a.dense_cap, None, False, plain)
+    pipeline._dense_pairs(ctx, d_photos, r, camera, dist, 16, a.dense_cap, None, False, filt, a.speckle)
+    maps = removed = clouds = True
+    for (p, idx), (f, _) in zip(plain, filt):
+        plans = f.plans()
+        for j in range(len(idx)):
+            want, n_want = speckle_ref.components(p.d_disp16[j].cpu().numpy(), -16, *a.speckle)
+            got = f.d_disp16[j].cpu().numpy()
+            maps &= got.tobytes() == want.tobytes()
+            removed &= int(f.d_removed[j]) == n_want
+            image = (f.d_color if f.d_color is not None else f.d_rect1)[j].cpu().numpy()
+            xyz = rectify_ref.cloud(got, f.d_valid[j].cpu().numpy(), image, plans[j:j + 1], -16, 16)[0]
+            k = min(int(f.d_count[j]), f.cap)
+            clouds &= int(f.d_count[j]) == len(xyz) and f.d_xyz[j, :k].cpu().numpy().tobytes() == xyz[:k].tobytes()
+    return {"maps": bool(maps), "removed": bool(removed), "clouds": bool(clouds)}
+
+
 def check_fusion(pkg, r, images, camera, dist, a):
     """The dense stage once more on the same records (it is deterministic), its maps read back, tests/dense_fuse_ref.py on them, and
     the fused cloud the run returned compared byte for byte. Test infrastructure."""
@@ -71,7 +102,7 @@ def check_fusion(pkg, r, images, camera, dist, a):
     ctx = api.default_context()
     d_photos = torch.from_numpy(np.ascontiguousarray(images)).to(f"cuda:{ctx.device}")
     runs = []
-    dense = pipeline._dense_pairs(ctx, d_photos, r, camera, dist, 16, a.dense_cap, None, True, runs)
+    dense = pipeline._dense_pairs(ctx, d_photos, r, camera, dist, 16, a.dense_cap, None, True, runs, a.speckle)
     same_dense = all((x is None) == (y is None) and (x is None or x["points"].tobytes() == y["points"].tobytes()) for x, y in zip(dense, r["dense"]))
     channels = 3 if images.ndim == 4 else 1
     srcs, pair_of = {}, []
@@ -113,9 +144,13 @@ def main():
     ap.add_argument("--fuse-tol16", type=int, default=16)
     ap.add_argument("--fuse-min-support", type=int, default=1)
     ap.add_argument("--dense-cap", type=int, default=None)
+    ap.add_argument("--speckle", help="SIZE,DIFF16: the speckle filter on every pair's map (DESIGN.md 4.13c)")
     a = ap.parse_args()
     if a.fuse and not a.dense:
         ap.error("--fuse needs --dense")
+    if a.speckle and not a.dense:
+        ap.error("--speckle needs --dense")
+    a.speckle = tuple(int(v) for v in a.speckle.split(",")) if a.speckle else None
     if a.images:
         z = np.load(a.images)
         images, camera = np.ascontiguousarray(z["images"], dtype=np.uint8), tuple(float(v) for v in z["camera"])
@@ -129,7 +164,7 @@ def main():
     pkg = importlib.import_module("sfm-gms_amd")
     r = pkg.structureFromMotionMulti(images, camera, dist, method=a.method, pairs=pairs, root=a.root, min_links=a.min_links,
                                      max_keypoints=a.max_keypoints, keep_tables=True, bundle=a.bundle,
-                                     **(dict(dense=True, dense_cap=a.dense_cap) if a.dense else {}),
+                                     **(dict(dense=True, dense_cap=a.dense_cap, dense_speckle=a.speckle) if a.dense else {}),
                                      **(dict(fuse=True, fuse_tol16=a.fuse_tol16, fuse_min_support=a.fuse_min_support) if a.fuse else {}))
     reg, views, tv = r["registration"], r["views"], r["two_view"]
     centres = [None if not v["registered"] else [round(float(x), 5) for x in -v["R"].T @ v["t"]] for v in views]
@@ -160,6 +195,11 @@ def main():
     ok = True
     if a.dense:
         line["dense_points_per_pair"] = [0 if d is None else int(d["count"]) for d in r["dense"]]
+        if a.speckle:
+            line["speckle"] = {"size": a.speckle[0], "diff16": a.speckle[1], "removed_per_pair": [0 if d is None else int(d["removed"]) for d in r["dense"]]}
+            if a.check:
+                line["speckle"]["check_vs_statement"] = check_speckle(r, images, camera, dist, a)
+                ok = ok and all(line["speckle"]["check_vs_statement"].values())
     if a.fuse:
         f = r["dense_fused"]
         line["fused"] = {"tol16": a.fuse_tol16, "min_support": a.fuse_min_support, "kept_per_pair": f["counts"][:-1].tolist(), "total": int(f["counts"][-1]),
