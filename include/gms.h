@@ -530,6 +530,28 @@ int gms_sfm_ba(const gms_camera* camera, const gms_sfm_ba_params* params, const 
                const gms_sfm_pair_reg* reg, const int32_t* track, int64_t cloud_cap, const double* cloud, const int32_t* cloud_id,
                int64_t n_tracks, gms_sfm_view* views_out, double* cloud_out, int32_t* track_status, gms_sfm_ba_summary* summary);
 
+/* ---- pair records from a view array (the library's own; tests/sfm_pair_pose_ref.py is the definition) -----------
+ * The dense stage (gms_dense_pairs_device) and the fusion (gms_dense_fuse_device) read a pair's pose from gms_two_view.R/t/status and
+ * its scale from gms_sfm_pair_reg.S/status when they run. This stage writes such records for ANY frame pairs of ANY view array --
+ * gms_sfm_register_device's d_views or gms_sfm_ba_device's d_views_out --, so that the dense stages run on those poses, also for
+ * pairs the sparse stage never matched. Stated in csrc/sfm_pair_pose_core.h: fp64, only + - * / sqrt, every sum in index order; the
+ * GPU, a host build of the header and numpy agree byte for byte.
+ *   For pair i with frames a = frame_a, b = frame_b (m and match_off are not read) and views x_cam = R x_world + t:
+ *     R_ab[r][c] = sum_k R_b[r][k] R_a[c][k], T = t_b - R_ab t_a, S = sqrt(T0^2 + T1^2 + T2^2), t = T / S per component.
+ *   GMS_OK when both indices are in 0..n_frames-1 (checked before a view's address is formed), a != b, both views are registered,
+ *   every entry of R_ab and T is finite and S is finite and > 0; otherwise GMS_ERR_NO_MODEL.
+ *   d_tv_out[i]: R = R_ab, t, status; d_reg_out[i]: S, status, link = -1; every other field of both records is 0, and a pair that
+ *   is not ok has R, t and S zero as well. Every byte of both records is written. Fed the registration's own views, an ok pair's
+ *   R, t and S come back up to rounding.
+ * gms_sfm_pair_poses_device: one kernel, one lane per pair; stream-ordered on the context's stream; no allocation, no
+ *   synchronisation, no readback (graph-capturable). n_pairs < 0 or above 2^30, n_frames < 1, or with n_pairs > 0 a NULL pointer or
+ *   one that is not 8-byte aligned: GMS_ERR_BAD_ARG, nothing run. n_pairs = 0 succeeds and writes nothing.
+ * gms_sfm_pair_poses: the same on host arrays, synchronous, on the current HIP device. */
+int gms_sfm_pair_poses_device(gms_ctx* ctx, const gms_sfm_view* d_views, int n_frames, const gms_pair* d_pairs, int n_pairs,
+                              gms_two_view* d_tv_out, gms_sfm_pair_reg* d_reg_out);
+int gms_sfm_pair_poses(const gms_sfm_view* views, int n_frames, const gms_pair* pairs, int n_pairs, gms_two_view* tv_out,
+                       gms_sfm_pair_reg* reg_out);
+
 /* ---- ingest format -----------------------------------------------------------------------------------------
  * The reference keeps detector and matcher output in process (std::vector<cv::KeyPoint>, cv::Mat descriptors,
  * std::vector<cv::DMatch>: FeatureMatchUtil.cpp:9-12,58-68; DisparityUtil.cpp:108,137-143) and has no on-disk form. One

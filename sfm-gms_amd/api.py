@@ -306,6 +306,13 @@ class GmsContext:
                                            d_mask, d_views, d_reg, d_track, int(cloud_cap), d_cloud, d_cloud_id, d_reg_summary, d_ws, int(ws_bytes),
                                            d_views_out, d_cloud_out, d_track_status, d_summary), self._lib, "gms_sfm_ba_device")
 
+    # -- pair records from a view array (include/gms.h; batch.SfmPairPoses drives this) -------------------------------
+    def sfm_pair_poses_device(self, d_views, n_frames, d_pairs, n_pairs, d_tv_out, d_reg_out):
+        """gms_sfm_pair_poses_device on raw device pointers: SFM_VIEW_DTYPE views and PAIR_DTYPE pairs in, TWO_VIEW_DTYPE and
+        SFM_PAIR_REG_DTYPE records out. Stream-ordered, capturable."""
+        _check(self._lib.gms_sfm_pair_poses_device(self._h, d_views or None, int(n_frames), d_pairs or None, int(n_pairs), d_tv_out or None,
+                                                   d_reg_out or None), self._lib, "gms_sfm_pair_poses_device")
+
     def detect_workspace_bytes(self, width, height, n_images, max_keypoints):
         return int(self._lib.gms_detect_workspace_bytes(int(width), int(height), int(n_images), int(max_keypoints)))
 
@@ -866,12 +873,18 @@ def structureFromMotionMulti(images, camera, dist=None, method="gms", pairs=None
     dense=True among params adds `dense`, one cloud per pair in the root's frame; fuse=True beside it (fuse_tol16, fuse_min_support,
     fuse_cap: run_images') adds `dense_fused`, those clouds fused into one by depth consistency; fuse=True without
     dense=True raises ValueError. dense_speckle = (max_speckle_size, max_diff16): filterSpeckles on every pair's map before the
-    reprojection; the fusion then reads the filtered maps. None, the default: no filter."""
+    reprojection; the fusion then reads the filtered maps. None, the default: no filter.
+    dense_poses = "pair" (the default: each pair's own two-view pose and the registration's scale), "registration" or "bundle" (needs
+    bundle=True; ValueError otherwise): the dense stage and the fusion on records derived from `views` / `views_ba`
+    (gms_sfm_pair_poses_device); the dict then also holds `dense_pose_records`. dense_pairs = [(a, b), ...] (needs
+    dense_poses other than "pair"): those frame pairs are matched densely in place of `pairs` -- any two registered frames, matched
+    sparsely or not --, and `dense`, `dense_fused["source"]` and the fusion's neighbour table index into dense_pairs."""
     from . import pipeline
     if method not in pipeline.METHODS:
         raise ValueError(f"unknown method {method!r}")
     if params.get("fuse") and not params.get("dense"):
         raise ValueError("fuse=True needs dense=True: the fusion reads the pairs' dense clouds")
+    pipeline.check_dense_poses(params.get("dense_poses", "pair"), params.get("dense_pairs"), params.get("dense", False), True, bundle)
     stack, _ = pipeline.image_stack(images)
     n = stack.shape[0]
     if pairs is None:

@@ -956,11 +956,25 @@ class DensePairs:
     repeated or captured into a graph; it is one stream with no parallel branches. The kernels read d_tv when they run: a captured
     graph follows set_two_view(). d_tv may also be the tensor a two-view stage writes (pass d_tv=). With a registration
     (set_registration) the points are in the world frame. speckle = (max_speckle_size, max_diff16): gms_dense_pairs_filtered_device,
-    the speckle filter on d_disp16 between the matcher and the cloud, and d_removed int32 [n]; None: gms_dense_pairs_device."""
+    the speckle filter on d_disp16 between the matcher and the cloud, and d_removed int32 [n]; None: gms_dense_pairs_device.
+    views= (a device view array: SfmRegister.d_views, SfmBundle.d_views_out or any SFM_VIEW_DTYPE bytes) with pose_records= (a
+    SfmPairPoses over the same n pairs, or its (d_tv, d_reg, d_pairs) tensors -- the cloud kernel reads each pair's frame_a from the
+    pair table): the stage rectifies by those records and puts its
+    clouds into the frame of those views -- the pose of pair i is whatever the records hold when run() runs, so a captured graph
+    follows SfmPairPoses.run(). Pair i is then the i-th pair of the SfmPairPoses, matched sparsely or not. Without the two, nothing
+    changes."""
 
     def __init__(self, ctx, n, src_size, out_size, camera, dist=None, channels=1, cap=None, min_disp16=16, params=None, device=None, d_tv=None,
-                 speckle=None):
+                 speckle=None, views=None, pose_records=None):
         from .api import dense_sgm_params, _speckle_pair
+        if (views is None) != (pose_records is None):
+            raise ValueError("DensePairs: views= and pose_records= go together")
+        posed = None
+        if pose_records is not None:
+            if d_tv is not None:
+                raise ValueError("DensePairs: pose_records= brings its own two-view records; d_tv= is the other route")
+            posed = _pose_records(pose_records, views, n)
+            d_tv = posed[0]
         self.ctx, self.n, self.channels, self.min_disp16 = ctx, int(n), int(channels), int(min_disp16)
         self.speckle = None if speckle is None else _speckle_pair(speckle, "DensePairs")
         (self.sw, self.sh), (self.ow, self.oh) = (int(v) for v in src_size), (int(v) for v in out_size)
@@ -985,6 +999,8 @@ class DensePairs:
         self.d_pixel, self.d_count = z((self.n, k), torch.int32), z((self.n,), torch.int32)
         self.d_removed = None if self.speckle is None else z((self.n,), torch.int32)
         self.reg = None
+        if posed is not None:
+            self.set_registration(posed[2], posed[1], views, posed[3])
         torch.cuda.synchronize(dev)
 
     def set_two_view(self, two_view):
@@ -1434,6 +1450,94 @@ class SfmBundle:
         n = self.cloud_cap if n_tracks is None else min(int(n_tracks), self.cloud_cap)
         return dict(views_ba=self.d_views_out.cpu().numpy().view(SFM_VIEW_DTYPE).copy(), cloud_ba=self.d_cloud_out.cpu().numpy().reshape(-1, 3)[:n].copy(),
                     track_status=self.d_status.cpu().numpy()[:n].copy(), ba_summary=self.d_summary.cpu().numpy().view(SFM_BA_SUMMARY_DTYPE).copy())
+
+
+def _pose_records(pose_records, views, n):
+    """DensePairs' pose_records= and views= -> (d_tv, d_reg, d_pairs, n_frames), checked against n pairs."""
+    from .types import SFM_PAIR_REG_DTYPE, SFM_VIEW_DTYPE, TWO_VIEW_DTYPE
+    rec = (pose_records.d_tv, pose_records.d_reg, pose_records.d_pairs) if isinstance(pose_records, SfmPairPoses) else tuple(pose_records)
+    if len(rec) != 3:
+        raise ValueError("pose_records: a SfmPairPoses, or its (d_tv, d_reg, d_pairs)")
+    d_tv, d_reg, d_pairs = rec
+    for t, size, name in ((d_tv, TWO_VIEW_DTYPE.itemsize, "d_tv"), (d_reg, SFM_PAIR_REG_DTYPE.itemsize, "d_reg"), (d_pairs, PAIR_DTYPE.itemsize, "d_pairs")):
+        if t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() != int(n) * size:
+            raise ValueError(f"pose_records: {name} holds {int(n)} records of {size} bytes as a contiguous uint8 tensor")
+    if views.dtype != torch.uint8 or not views.is_contiguous() or views.numel() == 0 or views.numel() % SFM_VIEW_DTYPE.itemsize:
+        raise ValueError(f"views: SFM_VIEW_DTYPE records ({SFM_VIEW_DTYPE.itemsize} bytes each) as a contiguous uint8 device tensor")
+    return d_tv, d_reg, d_pairs, views.numel() // SFM_VIEW_DTYPE.itemsize
+
+
+class SfmPairPoses:
+    """Device buffers of gms_sfm_pair_poses_device over a fixed list of frame pairs: the pair table d_pairs
+    (PAIR_DTYPE; m and match_off 0) and the records d_tv (TWO_VIEW_DTYPE) and d_reg (SFM_PAIR_REG_DTYPE) of every pair, sized once,
+    so that run() can be repeated or captured into a graph; it is one kernel on the context's stream. frame_pairs: (frame_a, frame_b)
+    rows -- any two frames of the view array, matched sparsely or not; a pair the views cannot pose (an index out of range, a == b,
+    a frame that is not registered, coincident centres, a value that is not finite) gets GMS_ERR_NO_MODEL records. The views are a
+    device tensor of n_frames SFM_VIEW_DTYPE records handed to run() (SfmRegister.d_views, SfmBundle.d_views_out), or the object's own,
+    which set_views() fills from the host."""
+
+    def __init__(self, ctx, n_frames, frame_pairs, device=None):
+        from .types import SFM_PAIR_REG_DTYPE, SFM_VIEW_DTYPE, TWO_VIEW_DTYPE
+        self.ctx, self.n_frames = ctx, int(n_frames)
+        fp = np.asarray(frame_pairs, dtype=np.int64).reshape(-1, 2)
+        if self.n_frames < 1 or (np.abs(fp) > 2 ** 31 - 1).any():
+            raise ValueError("SfmPairPoses: at least one frame; frame indices are 32-bit")
+        self.frame_pairs, self.n_pairs = fp, len(fp)
+        self.recs = np.zeros(self.n_pairs, PAIR_DTYPE)
+        self.recs["frame_a"], self.recs["frame_b"] = fp[:, 0], fp[:, 1]
+        dev = _device(ctx, device)
+        self.device = dev
+        n = max(self.n_pairs, 1)
+        self.d_pairs = _to_dev(self.recs, dev) if self.n_pairs else torch.zeros(PAIR_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.d_tv = torch.zeros(n * TWO_VIEW_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.d_reg = torch.zeros(n * SFM_PAIR_REG_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self._view_bytes = SFM_VIEW_DTYPE.itemsize
+        self.d_views = None
+        if self.n_pairs == 0:   # (DensePairs takes the tensors by their size)
+            self.d_pairs, self.d_tv, self.d_reg = self.d_pairs[:0], self.d_tv[:0], self.d_reg[:0]
+        torch.cuda.synchronize(dev)
+
+    def set_views(self, views):
+        """n_frames SFM_VIEW_DTYPE records on the host -> the object's own view tensor (the same tensor every time)."""
+        from .types import SFM_VIEW_DTYPE
+        rec = np.ascontiguousarray(views, dtype=SFM_VIEW_DTYPE).reshape(-1)
+        if len(rec) != self.n_frames:
+            raise ValueError("set_views: one record per frame")
+        if self.d_views is None:
+            self.d_views = torch.zeros(self.n_frames * self._view_bytes, dtype=torch.uint8, device=self.device)
+        self.d_views.copy_(torch.from_numpy(rec.view(np.uint8).reshape(-1)))
+        return self.d_views
+
+    def run(self, d_views=None):
+        """gms_sfm_pair_poses_device, stream-ordered on the context's stream; no allocation, no synchronisation, no readback."""
+        d_views = self.d_views if d_views is None else d_views
+        if d_views is None:
+            raise ValueError("run: a device view tensor, or set_views() first")
+        if d_views.dtype != torch.uint8 or not d_views.is_contiguous() or d_views.numel() != self.n_frames * self._view_bytes:
+            raise ValueError(f"views: {self.n_frames} SFM_VIEW_DTYPE records as a contiguous uint8 device tensor")
+        self.ctx.sfm_pair_poses_device(d_views.data_ptr(), self.n_frames, self.d_pairs.data_ptr(), self.n_pairs, self.d_tv.data_ptr(),
+                                       self.d_reg.data_ptr())
+        return self.d_tv, self.d_reg
+
+    def results(self):
+        """Waits for the context's stream -> (TWO_VIEW_DTYPE [n_pairs], SFM_PAIR_REG_DTYPE [n_pairs]) on the host."""
+        from .types import SFM_PAIR_REG_DTYPE, TWO_VIEW_DTYPE
+        self.ctx.synchronize()
+        return (self.d_tv.cpu().numpy().view(TWO_VIEW_DTYPE)[:self.n_pairs].copy(), self.d_reg.cpu().numpy().view(SFM_PAIR_REG_DTYPE)[:self.n_pairs].copy())
+
+
+def pair_poses(ctx, views, pairs, device=None):
+    """The convenience call: views (SFM_VIEW_DTYPE records on the host, or a device tensor of their bytes) and (frame_a, frame_b)
+    rows -> the SfmPairPoses after one run (its d_tv, d_reg and d_pairs stay on the device; results() brings the records back)."""
+    from .types import SFM_VIEW_DTYPE
+    on_dev = torch.is_tensor(views)
+    n_frames = views.numel() // SFM_VIEW_DTYPE.itemsize if on_dev else len(np.asarray(views).reshape(-1))
+    job = SfmPairPoses(ctx, n_frames, pairs, views.device if on_dev and device is None else device)
+    if not on_dev:
+        job.set_views(views)
+    torch.cuda.synchronize(job.device)
+    job.run(views if on_dev else None)
+    return job
 
 
 def bundle_adjust(ctx, keypoints, frame_off, pairs, matches, mask, registration, camera, dist=None, device=None, **ba):

@@ -44,6 +44,8 @@ SIGNATURES = {
     "gms_sfm_ba_workspace_bytes": (sz, [i32, i32, i64, i64]),
     "gms_sfm_ba_device": (i32, [vp, vp, vp, vp, vp, i32, i64, vp, i32, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, sz, vp, vp, vp, vp]),
     "gms_sfm_ba": (i32, [vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp]),
+    "gms_sfm_pair_poses_device": (i32, [vp, vp, i32, vp, i32, vp, vp]),
+    "gms_sfm_pair_poses": (i32, [vp, i32, vp, i32, vp, vp]),
     "gms_dataset_write": (i32, [cstr, vp]),
     "gms_dataset_read": (i32, [cstr, vp]),
     "gms_dataset_free": (None, [vp]),

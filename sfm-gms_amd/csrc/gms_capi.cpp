@@ -32,6 +32,7 @@
 #include "twoview_core.h"
 #include "rectify_core.h"
 #include "dense_fuse_core.h"
+#include "sfm_pair_pose_core.h"
 #include "speckle_core.h"
 #include "warp_core.h"
 #include "calib_core.h"
@@ -2431,6 +2432,40 @@ int gms_sfm_ba(const gms_camera* camera, const gms_sfm_ba_params* params, const 
         blk.out(track_status, o_st, 4 * Cc);
     }
     blk.out(summary, o_sum, sizeof(gms_sfm_ba_summary));
+    return blk.finish();
+}
+
+// ---- pair records from a view array (sfm_pair_pose_kernels.hip; the arithmetic is sfm_pair_pose_core.h) -------------
+int gms_sfm_pair_poses_device(gms_ctx* c, const gms_sfm_view* d_views, int n_frames, const gms_pair* d_pairs, int n_pairs, gms_two_view* d_tv_out,
+                              gms_sfm_pair_reg* d_reg_out)
+{
+    if (!c || !ppose::call_args_ok(n_frames, n_pairs)) return GMS_ERR_BAD_ARG;
+    if (n_pairs == 0) return GMS_OK;
+    if (!d_views || !d_pairs || !d_tv_out || !d_reg_out) return GMS_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_views) & 7u) || (reinterpret_cast<uintptr_t>(d_pairs) & 7u) || (reinterpret_cast<uintptr_t>(d_tv_out) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_reg_out) & 7u))
+        return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] { return gms::launch_sfm_pair_poses(d_views, n_frames, d_pairs, n_pairs, d_tv_out, d_reg_out, c->stream); });
+}
+
+int gms_sfm_pair_poses(const gms_sfm_view* views, int n_frames, const gms_pair* pairs, int n_pairs, gms_two_view* tv_out, gms_sfm_pair_reg* reg_out)
+{
+    if (!ppose::call_args_ok(n_frames, n_pairs)) return GMS_ERR_BAD_ARG;
+    if (n_pairs == 0) return GMS_OK;
+    if (!views || !pairs || !tv_out || !reg_out) return GMS_ERR_BAD_ARG;
+    const size_t F = (size_t)n_frames, P = (size_t)n_pairs;
+    gms::BlockLayout lay;
+    const size_t o_views = lay.add(sizeof(gms_sfm_view) * F), o_pairs = lay.add(sizeof(gms_pair) * P), o_tv = lay.add(sizeof(gms_two_view) * P),
+                 o_reg = lay.add(sizeof(gms_sfm_pair_reg) * P);
+    DevBlock blk(lay, nullptr);
+    blk.in(o_views, views, sizeof(gms_sfm_view) * F);
+    blk.in(o_pairs, pairs, sizeof(gms_pair) * P);
+    blk.run([&](hipStream_t st) {
+        return gms::launch_sfm_pair_poses(blk.at<gms_sfm_view>(o_views), n_frames, blk.at<gms_pair>(o_pairs), n_pairs, blk.at<gms_two_view>(o_tv),
+                                          blk.at<gms_sfm_pair_reg>(o_reg), st);
+    });
+    blk.out(tv_out, o_tv, sizeof(gms_two_view) * P);
+    blk.out(reg_out, o_reg, sizeof(gms_sfm_pair_reg) * P);
     return blk.finish();
 }
 

@@ -241,6 +241,9 @@ hipError_t launch_sfm_ba(const gms_camera& camera, const gms_sfm_ba_params& prm,
                          int64_t cloud_cap, const double* d_cloud, const int32_t* d_cloud_id, const gms_sfm_summary* d_reg_summary, void* d_ws,
                          gms_sfm_view* d_views_out, double* d_cloud_out, int32_t* d_track_status, gms_sfm_ba_summary* d_summary,
                          hipStream_t stream);
+// two-view and registration records of frame pairs from a view array (sfm_pair_pose_kernels.hip; arithmetic in sfm_pair_pose_core.h)
+hipError_t launch_sfm_pair_poses(const gms_sfm_view* d_views, int n_frames, const gms_pair* d_pairs, int n_pairs, gms_two_view* d_tv,
+                                 gms_sfm_pair_reg* d_reg, hipStream_t stream);
 // semi-global matching on StereoBM's costs (stereo_sgm_kernels.hip; shared arithmetic in stereo_sgm_core.h); 0 bytes: beyond size_t
 size_t     stereo_sgm_ws_bytes(const gms_stereo_sgm_params& p, int n, int W, int H);
 hipError_t launch_stereo_sgm(const gms_stereo_sgm_params& p, const uint8_t* d_left, const uint8_t* d_right, int n, int W, int H, int pitch,

@@ -527,6 +527,34 @@ inline BundleAdjustment bundleAdjust(const std::vector<gms_keypoint>& keypoints,
     return r;
 }
 
+// Pair records from views (include/gms.h): for any frame pairs (a, b) of a view array -- registerViews' views or
+// bundleAdjust's -- the two-view records (R, unit t, status) and registration records (S, status) that the dense stage and the fusion
+// read, so that they run on those poses, also for pairs the sparse stage never matched. A pair the views cannot pose (an index out of
+// range, a == b, a frame that is not registered, coincident centres) gets status GMS_ERR_NO_MODEL and zeros. Runs synchronously on the
+// current HIP device (gms_sfm_pair_poses).
+struct PairPoses {
+    std::vector<gms_pair> pairs;             // frame_a, frame_b; m and match_off 0
+    std::vector<gms_two_view> two_view;      // one per pair
+    std::vector<gms_sfm_pair_reg> reg;       // one per pair
+};
+
+inline PairPoses pairPosesFromViews(const std::vector<gms_sfm_view>& views, const std::vector<std::pair<int, int>>& frame_pairs)
+{
+    if (views.empty()) throw std::invalid_argument("mi355::pairPosesFromViews: at least one view");
+    PairPoses r;
+    r.pairs.resize(frame_pairs.size());
+    for (size_t i = 0; i < frame_pairs.size(); ++i) {
+        r.pairs[i] = gms_pair{};
+        r.pairs[i].frame_a = frame_pairs[i].first;
+        r.pairs[i].frame_b = frame_pairs[i].second;
+    }
+    r.two_view.resize(frame_pairs.size());
+    r.reg.resize(frame_pairs.size());
+    const int rc = gms_sfm_pair_poses(views.data(), (int)views.size(), r.pairs.data(), (int)r.pairs.size(), r.two_view.data(), r.reg.data());
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::pairPosesFromViews: ") + gms_error_string(rc));
+    return r;
+}
+
 // The image tail of the reference's createPortraitMode (DisparityUtil.cpp:317-412): img = the photograph as flat row-major BGR bytes
 // (3 * width * height, cv::Mat's layout after imread), disparity = an 8-bit map with 255 = no value (what gms_disparity_device and
 // stereo_match write); out receives the portrait image in img's layout. medianBlur is cv::medianBlur for 1 or 3 interleaved channels

@@ -231,7 +231,7 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
                device=None, dictionary=None, logos_capacity=None, cross_check=True, distance_coef=4.0, max_size=500, train_dictionary=None,
                keep_tables=False, detector="fast", contrast=128, refine=False, register=False, root=0, min_links=8, bundle=False, dense=False,
                min_disp16=16, dense_cap=None, dense_sgm=None, fuse=False, fuse_tol16=16, fuse_min_support=1, fuse_cap=None, dense_speckle=None,
-               **ba):
+               dense_poses="pair", dense_pairs=None, **ba):
     """run_dataset from pixels. images: [n, H, W] grey or [n, H, W, 3] BGR, 8-bit, a host array or a device tensor (or a list of equally
     sized images). BGR goes through gms_bgr_to_gray_device; the pyramid keypoint source (threshold, max_keypoints, n_levels; detector
     "fast", or "dog" with `contrast` in the place of `threshold`: gms_detect_dog_batch_device, with refine=True
@@ -256,13 +256,22 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
     disagrees with the point within fuse_tol16 sixteenths of a pixel, support counting the point's own pair) and counts int32
     [n_pairs + 1] (kept per pair, then the total). A point is kept once, by the lowest pair that sees it consistently, and only with
     support >= fuse_min_support; fuse_cap: the most points returned (default: room for all). `dense` itself is what it is without
-    fuse; fuse=False returns the dict without `dense_fused`."""
+    fuse; fuse=False returns the dict without `dense_fused`.
+    dense_poses: where the dense stage and the fusion take a pair's pose and scale from. "pair", the default: the
+    pair's own two-view record and the registration's scale, as ever. "registration" (needs register=True) / "bundle" (needs
+    bundle=True): gms_sfm_pair_poses_device derives every pair's records from `views` / `views_ba`, the dense stage rectifies by them
+    and its clouds and the fusion are in the frame of those views; the dict then also holds `dense_pose_records` = (two-view records,
+    registration records) of the dense pairs, TWO_VIEW_DTYPE and SFM_PAIR_REG_DTYPE. dense_pairs = [(a, b), ...] (needs dense_poses
+    other than "pair"): the frame pairs to match densely, in place of `pairs` -- any two registered frames, matched sparsely or not;
+    `dense`, `dense_pose_records`, `dense_fused["source"]`, its counts and the fusion's neighbour table then index into dense_pairs,
+    not into `pairs`. None: the sparse pair list."""
     if method not in METHODS:
         raise ValueError(f"unknown method {method!r}")
     if dense and camera is None:
         raise ValueError("dense=True needs a camera: it rectifies by the recovered poses")
     if fuse and not (dense and register):
         raise ValueError("fuse=True needs dense=True and register=True: without a registration the clouds share no frame")
+    dense_pairs = check_dense_poses(dense_poses, dense_pairs, dense, register, bundle)
     if descriptor not in ("brief", "grad", "both"):
         raise ValueError('descriptor: "brief", "grad" or "both"')
     images, is_bgr = image_stack(images)
@@ -300,12 +309,52 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
         r = _run_gms(ctx, frames, descs, src, None, withRotation, withScale, thresholdFactor, *tail)
     if dense:
         runs = [] if fuse else None       # (the runs' device buffers stay alive until the fusion has read them)
-        r.update(dense=_dense_pairs(ctx, d_photos, r, camera, dist, min_disp16, dense_cap, dense_sgm, reg is not None, runs, dense_speckle))
+        rd = r
+        if dense_poses != "pair":         # the dense stages' inputs from the chosen views instead of the pairs' own records
+            rd = _dense_pose_records(ctx, r, dense_poses, dense_pairs, dev)
+            r.update(dense_pose_records=(rd["two_view"], rd["registration"]))
+        r.update(dense=_dense_pairs(ctx, d_photos, rd, camera, dist, min_disp16, dense_cap, dense_sgm, reg is not None, runs, dense_speckle))
         if fuse:
-            r.update(dense_fused=_dense_fuse(ctx, runs, len(src), 3 if d_photos.dim() == 4 else 1, fuse_tol16, fuse_min_support, fuse_cap))
+            r.update(dense_fused=_dense_fuse(ctx, runs, len(rd["pairs"]), 3 if d_photos.dim() == 4 else 1, fuse_tol16, fuse_min_support, fuse_cap))
     if keep_tables:
         r.update(tables=(frames, descs))
     return r
+
+
+DENSE_POSES = ("pair", "registration", "bundle")
+
+
+def check_dense_poses(dense_poses, dense_pairs, dense, register, bundle):
+    """run_images' dense_poses / dense_pairs, refused before any device work -> dense_pairs as an int64 [n, 2] array, or None."""
+    if dense_poses not in DENSE_POSES:
+        raise ValueError(f"dense_poses: one of {DENSE_POSES}, not {dense_poses!r}")
+    if dense_poses == "pair":
+        if dense_pairs is not None:
+            raise ValueError('dense_pairs needs dense_poses="registration" or "bundle": a pair the sparse stage did not match has no pose of its own')
+        return None
+    if not dense:
+        raise ValueError(f"dense_poses={dense_poses!r} needs dense=True: it says where the dense stage takes its poses from")
+    if dense_poses == "bundle" and not bundle:
+        raise ValueError('dense_poses="bundle" needs bundle=True: it reads the bundle-adjusted views')
+    if not register:
+        raise ValueError(f"dense_poses={dense_poses!r} needs register=True: it reads the registration's views")
+    if dense_pairs is None:
+        return None
+    fp = np.asarray(dense_pairs, dtype=np.int64)
+    if fp.ndim != 2 or fp.shape[1] != 2 or len(fp) < 1 or (np.abs(fp) > 2 ** 31 - 1).any():
+        raise ValueError("dense_pairs: (frame_a, frame_b) rows")
+    return fp
+
+
+def _dense_pose_records(ctx, r, dense_poses, dense_pairs, dev):
+    """run_images' dense_poses other than "pair": gms_sfm_pair_poses_device on `views` or `views_ba` for the dense pairs (default: the
+    sparse pair list's frames) -> what _dense_pairs and _dense_fuse read of `r`, with those records in the place of the pairs' own."""
+    from .batch import pair_poses
+    views = r["views_ba" if dense_poses == "bundle" else "views"]
+    fp = np.stack([r["pairs"]["frame_a"], r["pairs"]["frame_b"]], 1).astype(np.int64) if dense_pairs is None else dense_pairs
+    job = pair_poses(ctx, views, fp, dev)
+    tv, reg = job.results()
+    return dict(pairs=job.recs, two_view=tv, registration=reg, views=views)
 
 
 def _dense_pairs(ctx, d_photos, r, camera, dist, min_disp16, cap, sgm, registered, keep=None, speckle=None):

@@ -3,7 +3,7 @@
 pipeline.run_images(register=True): per pair the two-view stage, then gms_sfm_register_device joins the pairs).
 Prints one JSON line: per pair n_links, r, S and status; per view the camera centre; tracks by length; the median spread.
 
-    python tools/gms_sfm_sequence.py [images.npz] [--method gms|bf|logos] [--pairs chain|star|all] [--root 0] [--min-links 8] [--max-keypoints 2000] [--ply out.ply] [--bundle] [--dense [--speckle SIZE,DIFF16] [--fuse [--fuse-tol16 16] [--fuse-min-support 1]]] [--check]
+    python tools/gms_sfm_sequence.py [images.npz] [--method gms|bf|logos] [--pairs chain|star|all] [--root 0] [--min-links 8] [--max-keypoints 2000] [--ply out.ply] [--bundle] [--dense [--speckle SIZE,DIFF16] [--dense-poses pair|registration|bundle] [--dense-pairs a-b,c-d] [--fuse [--fuse-tol16 16] [--fuse-min-support 1]]] [--check]
 
 images.npz: arrays images ([n, H, W] grey or [n, H, W, 3] BGR, uint8) and camera = (fx, fy, cx, cy), optionally dist. Default: views
 1, 2, 3, 4 of the reference's SourceImages scene from the two committed fixtures (tests/golden/image_sfm_pair_1008x756.npz holds views 1
@@ -18,7 +18,12 @@ the points per pair, the fused total and a histogram of `support`; --ply then wr
 with --check the dense stage is run once more to read its maps back, the numpy statement (tests/dense_fuse_ref.py) fuses them, and
 every output byte is compared. --speckle SIZE,DIFF16 (with --dense): the speckle filter on every pair's map before the reprojection
 (DIFF16 in sixteenths of a pixel): the pixels removed per pair; with --check the stage is run with and without the
-filter, and the filtered maps and clouds must equal the numpy statements (tests/speckle_ref.py, tests/rectify_ref.py)."""
+filter, and the filtered maps and clouds must equal the numpy statements (tests/speckle_ref.py, tests/rectify_ref.py).
+--dense-poses registration | bundle (the latter with --bundle): the dense stage and the fusion on pair records derived from the
+registration's / the bundle-adjusted views (gms_sfm_pair_poses_device; DESIGN.md 4.10d) instead of each pair's own two-view pose;
+--dense-pairs a-b,c-d: those frame pairs are matched densely in place of the sparse pair list (the per-pair figures of the dense
+stage and the fusion then follow that list). With --check the records must equal the numpy statement (tests/sfm_pair_pose_ref.py)
+on the GPU's own views and every plan tests/rectify_ref.py's on its record, byte for byte; the other checks run on those records."""
 import argparse
 import importlib
 import json
@@ -60,6 +65,37 @@ def write_fused_ply(path, f):
                   "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar support\nend_header\n")
         for p, c, s in zip(f["points"], col, f["support"]):
             out.write(f"{p[0]:.9g} {p[1]:.9g} {p[2]:.9g} {int(c[2])} {int(c[1])} {int(c[0])} {int(s)}\n")
+
+
+def dense_inputs(pkg, r, a):
+    """What the dense stage and the fusion read of the run: `r` itself, or with --dense-poses the records derived from the views."""
+    if a.dense_poses == "pair":
+        return r
+    tv, reg = r["dense_pose_records"]
+    fp = np.array(a.dense_pairs, np.int64).reshape(-1, 2) if a.dense_pairs else np.stack([r["pairs"]["frame_a"], r["pairs"]["frame_b"]], 1)
+    pairs = np.zeros(len(fp), pkg.PAIR_DTYPE)
+    pairs["frame_a"], pairs["frame_b"] = fp[:, 0], fp[:, 1]
+    return dict(r, pairs=pairs, two_view=tv, registration=reg, views=r["views_ba" if a.dense_poses == "bundle" else "views"])
+
+
+def check_pose_records(rd, images, camera, dist):
+    """--dense-poses --check: the records against tests/sfm_pair_pose_ref.py on the GPU's own views, and every returned plan against
+    tests/rectify_ref.py on its record, byte for byte. Test infrastructure."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import rectify_ref
+    import sfm_pair_pose_ref as pp
+    views = np.zeros(len(rd["views"]), pp.VIEW_DTYPE)
+    for k in views.dtype.names:
+        views[k] = np.asarray(rd["views"][k]).reshape(views[k].shape)
+    fp = np.stack([rd["pairs"]["frame_a"], rd["pairs"]["frame_b"]], 1)
+    tv, reg = pp.pair_poses(views, fp)
+    plans = True
+    for i, d in enumerate(rd["dense"]):
+        if d is not None:
+            p = d["plan"][0]
+            want = rectify_ref.make_plan(camera, dist, tv["R"][i], tv["t"][i], (images.shape[2], images.shape[1]), (int(p["out_w"]), int(p["out_h"])))
+            plans &= np.asarray(want).tobytes() == d["plan"].tobytes()
+    return {"two_view": rd["two_view"].tobytes() == tv.tobytes(), "registration": rd["registration"].tobytes() == reg.tobytes(), "plans": bool(plans)}
 
 
 def check_speckle(r, images, camera, dist, a):
@@ -145,12 +181,21 @@ def main():
     ap.add_argument("--fuse-min-support", type=int, default=1)
     ap.add_argument("--dense-cap", type=int, default=None)
     ap.add_argument("--speckle", help="SIZE,DIFF16: the speckle filter on every pair's map (DESIGN.md 4.13c)")
+    ap.add_argument("--dense-poses", choices=("pair", "registration", "bundle"), default="pair")
+    ap.add_argument("--dense-pairs", help="a-b,c-d: the frame pairs to match densely (needs --dense-poses registration or bundle)")
     a = ap.parse_args()
     if a.fuse and not a.dense:
         ap.error("--fuse needs --dense")
     if a.speckle and not a.dense:
         ap.error("--speckle needs --dense")
     a.speckle = tuple(int(v) for v in a.speckle.split(",")) if a.speckle else None
+    if a.dense_poses != "pair" and not a.dense:
+        ap.error("--dense-poses needs --dense")
+    if a.dense_poses == "bundle" and not a.bundle:
+        ap.error("--dense-poses bundle needs --bundle")
+    if a.dense_pairs and a.dense_poses == "pair":
+        ap.error("--dense-pairs needs --dense-poses registration or bundle")
+    a.dense_pairs = [tuple(int(v) for v in p.split("-")) for p in a.dense_pairs.split(",")] if a.dense_pairs else None
     if a.images:
         z = np.load(a.images)
         images, camera = np.ascontiguousarray(z["images"], dtype=np.uint8), tuple(float(v) for v in z["camera"])
@@ -165,6 +210,7 @@ def main():
     r = pkg.structureFromMotionMulti(images, camera, dist, method=a.method, pairs=pairs, root=a.root, min_links=a.min_links,
                                      max_keypoints=a.max_keypoints, keep_tables=True, bundle=a.bundle,
                                      **(dict(dense=True, dense_cap=a.dense_cap, dense_speckle=a.speckle) if a.dense else {}),
+                                     **(dict(dense_poses=a.dense_poses, dense_pairs=a.dense_pairs) if a.dense_poses != "pair" else {}),
                                      **(dict(fuse=True, fuse_tol16=a.fuse_tol16, fuse_min_support=a.fuse_min_support) if a.fuse else {}))
     reg, views, tv = r["registration"], r["views"], r["two_view"]
     centres = [None if not v["registered"] else [round(float(x), 5) for x in -v["R"].T @ v["t"]] for v in views]
@@ -193,12 +239,19 @@ def main():
                           "tracks_excluded_fewer_than_two": int(st[2]), "tracks_kept_cloud_point_at_retriangulation": int(st[3]),
                           "camera_centres": [None if not v["registered"] else [round(float(x), 5) for x in -v["R"].T @ v["t"]] for v in r["views_ba"]]}
     ok = True
+    rd = dense_inputs(pkg, r, a) if a.dense else r
     if a.dense:
         line["dense_points_per_pair"] = [0 if d is None else int(d["count"]) for d in r["dense"]]
+        if a.dense_poses != "pair":
+            line["dense_poses"] = {"from": a.dense_poses, "pairs": [[int(p["frame_a"]), int(p["frame_b"])] for p in rd["pairs"]],
+                                   "status": rd["two_view"]["status"].tolist(), "S": [round(float(v), 6) for v in rd["registration"]["S"]]}
+            if a.check:
+                line["dense_poses"]["check_vs_statement"] = check_pose_records(rd, images, camera, dist)
+                ok = ok and all(line["dense_poses"]["check_vs_statement"].values())
         if a.speckle:
             line["speckle"] = {"size": a.speckle[0], "diff16": a.speckle[1], "removed_per_pair": [0 if d is None else int(d["removed"]) for d in r["dense"]]}
             if a.check:
-                line["speckle"]["check_vs_statement"] = check_speckle(r, images, camera, dist, a)
+                line["speckle"]["check_vs_statement"] = check_speckle(rd, images, camera, dist, a)
                 ok = ok and all(line["speckle"]["check_vs_statement"].values())
     if a.fuse:
         f = r["dense_fused"]
@@ -207,7 +260,7 @@ def main():
                          "support_histogram": {str(k): int(c) for k, c in enumerate(np.bincount(f["support"])) if c},
                          "conflict_histogram": {str(k): int(c) for k, c in enumerate(np.bincount(f["conflict"])) if c}}
         if a.check:
-            chk = check_fusion(pkg, r, images, camera, dist, a)
+            chk = check_fusion(pkg, rd, images, camera, dist, a)
             line["fused"]["check_vs_statement"] = chk
             ok = ok and all(chk.values())
     if a.check and a.bundle:
@@ -232,7 +285,7 @@ def main():
         chk = {"ba_integers": bool(np.array_equal(r["track_status"], fwd["track_status"]) and all(s[k] == fwd["ba_summary"][0][k] for k in ints)),
                "ba_doubles": apart(r, fwd) <= tol}
         line["bundle"]["check_vs_statement"] = dict(chk, tolerance=tol, apart=apart(r, fwd))
-        ok = all(chk.values())
+        ok = ok and all(chk.values())
     if a.check:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import sfm_register_ref as ref
