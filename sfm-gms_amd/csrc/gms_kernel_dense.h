@@ -1,12 +1,23 @@
 // gms_kernel_dense.h -- what the byte-matrix forms of the GMS filter share (overview: gms_kernels.hip): the LDS layout of the
 // 400 x 400 byte matrix, the per-keypoint codes of the frame table and the dense code word, the threshold test on small integers
-// and nLeft from the half-cell histogram. Used by gms_kernel_dense.hip (no scale hypotheses), gms_kernel_scales.hip
-// (scale hypotheses) and gms_kernels.hip (normalize_kernel writes the codes). Internal; .hip files only.
+// and nLeft from the half-cell histogram with the half-cell rule of the mark table. Used by gms_kernel_dense.hip (no scale
+// hypotheses), gms_kernel_scales.hip (scale hypotheses) and gms_kernels.hip (normalize_kernel writes the codes). Internal.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ws_layout.h"
+// The layout constants and the half-cell geometry below are plain arithmetic that a host compiler builds alone
+// (tests/cpp/mark_table_check.cpp); everything that needs the device is behind __HIPCC__.
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+
 #include "gms_device_common.h"
+#define GMS_DENSE_HD __host__ __device__ __forceinline__
+#define GMS_DENSE_UNROLL _Pragma("unroll")
+#else
+#define GMS_DENSE_HD inline
+#define GMS_DENSE_UNROLL
+#endif
 
 namespace gms {
 
@@ -43,8 +54,10 @@ constexpr uint32_t kDenseMiscOff = kDenseNleftOff + kLeftN;     // [32] dwords: 
                                                                 //   at its limit, [13] a half cell above 255, [16..31] scan scratch
 constexpr uint32_t kDenseTrashOff = kDenseMiscOff + 4u * 32u;   // [16] dwords: sinks
 constexpr uint32_t kDenseLdsBytes = kDenseTrashOff + 4u * 16u;  // 163 792
-static_assert(kDenseLdsBytes <= kLdsBytes, "dense layout exceeds the LDS");
 static_assert(kDenseBytes % 16 == 0 && kDenseRow % 4 == 0, "rows are dword aligned, the matrix is cleared in uint4s");
+
+#if defined(__HIPCC__)
+static_assert(kDenseLdsBytes <= kLdsBytes, "dense layout exceeds the LDS");
 
 // The threshold test of the byte-matrix path: T <= 9 * 255, score <= 9 * 255, n <= 9. For an integer factor up to 1023
 // (the reference's default is 6) T * factor^2 and score^2 * n are exact 32-bit integers; when they differ, they differ by
@@ -63,23 +76,64 @@ __device__ __forceinline__ bool dense_threshold_rejects(uint32_t T, uint32_t n, 
     return threshold_rejects(T, n, score, factor, fast_ok);
 }
 
+// 8-byte LDS accesses at absolute byte offsets (a multiple of 8), beside gms_device_common.h's ldsa_*: the mark table's entries
+using lds_u64_t = __attribute__((address_space(3))) uint64_t;
+__device__ __forceinline__ uint64_t ldsa_ld64(uint32_t a) { return *reinterpret_cast<lds_u64_t*>((uintptr_t)a); }
+__device__ __forceinline__ void ldsa_st64(uint32_t a, uint64_t v) { *reinterpret_cast<lds_u64_t*>((uintptr_t)a) = v; }
+#endif
+
 // mNumberPointsInPerCellLeft of cell (x, y) under the grid type shifted by (gx, gy) half cells, from the half-cell histogram --
 // which is laid out by cell: one dword per cell of grid type 1, its four half cells in the
 // four bytes (byte index (hx & 1) + 2 (hy & 1)) -- the index a left code word yields without arithmetic.
-__device__ __forceinline__ uint32_t dense_nleft_cm(const uint8_t* nfine8, int x, int y, int gx, int gy)
+GMS_DENSE_HD uint32_t dense_nleft_cm(const uint8_t* nfine8, int x, int y, int gx, int gy)
 {
     const int hx0 = 2 * x - gx, hy0 = 2 * y - gy;
     uint32_t n = 0;
-#pragma unroll
+    GMS_DENSE_UNROLL
     for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
+        GMS_DENSE_UNROLL
         for (int dx = 0; dx < 2; ++dx) {
-            const int hx = max(hx0 + dx, 0), hy = max(hy0 + dy, 0);
+            const int hx = hx0 + dx < 0 ? 0 : hx0 + dx, hy = hy0 + dy < 0 ? 0 : hy0 + dy;
             const uint32_t v = nfine8[(((hy >> 1) * kLeftW + (hx >> 1)) << 2) + (hx & 1) + ((hy & 1) << 1)];
             n += (hx0 + dx >= 0 && hy0 + dy >= 0) ? v : 0u;
         }
     return n;
 }
+
+// The same geometry the other way round: the cell that owns half cell (hx, hy) under the grid type shifted by (gx, gy) half cells --
+// the cell whose dense_nleft_cm counts it --, or -1 where no cell does: the last half cell of a shifted axis (x >= 20 || y >= 20
+// -> -1 in the reference, the edge bits of a code word). It is l1 + (q & (gx + 20 gy)) of a match's code word.
+constexpr int dense_half_cell_owner(int hx, int hy, int gx, int gy)
+{
+    return ((hx + gx) >> 1) < kLeftW && ((hy + gy) >> 1) < kLeftH ? ((hy + gy) >> 1) * kLeftW + ((hx + gx) >> 1) : -1;
+}
+// where a half cell sits in the half-cell histogram (a byte) and in the mark table (an 8-byte entry): by cell of grid type 1
+constexpr uint32_t dense_half_cell_slot(int hx, int hy)
+{
+    return (uint32_t)((((hy >> 1) * kLeftW + (hx >> 1)) << 2) + (hx & 1) + ((hy & 1) << 1));
+}
+static_assert(dense_half_cell_owner(39, 38, 1, 0) == -1 && dense_half_cell_owner(39, 38, 0, 1) == 19 * kLeftW + 19 &&
+              dense_half_cell_owner(0, 0, 1, 1) == 0 && dense_half_cell_owner(1, 1, 1, 1) == kLeftW + 1, "half cells and shifted grids");
+
+// The mark table of dense_pair_plain: after the last grid type the matrix area is free, and the verdicts of all four grid types --
+// cellPairs[cell] as E(j*), kDenseMarkNone where the cell pair was rejected or the cell is empty -- go into it once per pair:
+//   verdicts  [400] x 4 16-bit fields: what the two verifying lanes of a cell decided under grid types 1..4 (they kept them in
+//             registers while the matrix lived);
+//   table     8-byte entries of 4 16-bit fields, entry dense_half_cell_slot(hx, hy): field g = the verdict of the cell that owns
+//             the half cell under grid type g, kDenseMarkNone where nobody does. A match is an inlier when one field of its left
+//             point's entry equals its E(r): one 8-byte read instead of a row header per grid type. A match that is not binned
+//             (code word = a sink's) computes "cell" kDenseMarkSinkSlot / 4 from its sink's offset: an entry of its own, none four times.
+// Both lie above everything the copy-out keeps in the area (its scan table: at most 8 KB from offset 0), and the table's offset fits
+// the 16-bit immediate of an LDS instruction.
+constexpr uint32_t kDenseMarkNone = 0xFFFFu;             // never an E(r): those are 4..403, a sink's is 0
+constexpr uint32_t kDenseMarkVerdictOff = 16384;
+constexpr uint32_t kDenseMarkTableOff = 32768;
+constexpr uint32_t kDenseMarkSinkSlot = 4u * ((kDenseTrashOff / 4u * 649u) >> 16);  // 1620: the sinks' "row / 404" is 405
+constexpr uint32_t kDenseMarkEntries = kDenseMarkSinkSlot + 1u;
+static_assert(((((kDenseTrashOff + 60u) >> 2) * 649u) >> 16) == kDenseMarkSinkSlot / 4u && kDenseMarkSinkSlot >= (uint32_t)kFineN,
+              "all sixteen sink dwords divide to one row above the grid");
+static_assert(kDenseMarkTableOff + 8u * kDenseMarkEntries <= kDenseBytes && kDenseMarkTableOff + 8u * kDenseMarkEntries < 65536u &&
+              kDenseMarkVerdictOff + 8u * kLeftN <= kDenseMarkTableOff, "verdicts and table inside the matrix area, apart");
 
 // dense code word
                                                      // bits 0..4   q = (hx & 1) + 20 * (hy & 1)

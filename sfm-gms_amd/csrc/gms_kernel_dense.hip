@@ -505,9 +505,9 @@ __device__ __forceinline__ bool dense_pair_rot(const FilterParams& p, uint32_t* 
 //     axis) swaps its code word for the lane's SINK word -- an entry in the 64 spare bytes behind the matrix -- and runs the same
 //     instructions as everybody else (no exec masks, no branches around the LDS atomics);
 //   * LDS is addressed by absolute byte offsets (the dynamic segment starts at 0 in these kernels): no "+ base" per access;
-//   * the inlier flag of a match is one bit of a wave-wide mask in scalar registers (v_cmp writes it; the copy-out wants the
-//     ballot anyway), the row header after verification is E(j*) when the cell pair passes and 0 when it does not: marking is
-//     one compare;
+//   * inliers are marked once per pair, not once per grid type: the verifying lanes keep cellPairs of all four grid types in a
+//     register, and behind the last one a table of the 1600 left half cells x 4 grid types is built in the free matrix area; a
+//     match reads the one entry of its half cell and compares four fields with its E (the mark table: gms_kernel_dense.h);
 //   * verification: the eight neighbour pairs of a cell are base + s * 403 * d for d in {-21, -20, -19, -1} and s = +-1 (the two
 //     lanes of a cell), their validity three compares per axis; an invalid pair reads a byte that is always zero.
 // ------------------------------------------------------------------------------------------------
@@ -755,7 +755,8 @@ __device__ __forceinline__ int dense_pair_plain(const FilterParams& p, uint32_t*
         uint4* d4 = reinterpret_cast<uint4*>(smem);
         for (uint32_t i = tid; i < staged16; i += NT) d4[i] = z4;
         // the sink dwords from here on: bit 31 set, and nothing below ever clears it (increments land in byte 0, arg-max keys end at
-        // bit 21, the undo stores a zero into byte 0) -- a sink is never equal to an E, so a sink word is nobody's inlier
+        // bit 21, the undo stores a zero into byte 0). (Nobody compares a sink dword any more: a sink word's E is 0, which no field of
+        // the mark table equals.)
         if (tid < 16) trash[tid] = 0x80000000u;
     }
     __syncthreads();
@@ -772,13 +773,12 @@ __device__ __forceinline__ int dense_pair_plain(const FilterParams& p, uint32_t*
 
     const bool thr_fast = threshold_fast_ok(p.threshold_factor);
     const uint32_t f2i = dense_factor_sq(p.threshold_factor);
-    uint32_t acc = 0;  // bit k: match k of this thread is an inlier under some grid type
+    // cellPairs of this thread's cell under two of the four grid types, 16 bits each: E(j*) or kDenseMarkNone. The even lane of a
+    // verifying pair decides and keeps grid types 1 and 2, the odd lane is handed 3 and 4 (one DPP move). They stay here until
+    // the last grid type is through -- the LDS has no room for them while the matrix lives -- and then go into the mark table
+    // (gms_kernel_dense.h), where every match looks its four verdicts up at once.
+    uint32_t vd = 0;
 
-    // verification: lane pair of cell i = tid >> 1; the even lane takes the neighbour pairs at d = -21, -20, -19, -1 (positions 0..3 of
-    // the 3 x 3 block), the odd lane the mirrored ones (positions 8..5): s = +-1
-    const uint32_t vi = (uint32_t)tid >> 1;
-    const uint32_t viy = (vi * 3277u) >> 16, vix = vi - 20u * viy;  // vi / 20, vi % 20 for vi < 400 (and harmless above)
-    const bool vodd = (tid & 1) != 0;
 
     // L2 prefetch for the workgroup that follows this one on the CU: workgroups are handed out in order, one per CU, so that is
     // pair_idx + (number of CUs) -- on the same XCD (256 = 8 x 32)
@@ -825,7 +825,7 @@ __device__ __forceinline__ int dense_pair_plain(const FilterParams& p, uint32_t*
         }
 
         // ---- assignMatchPairs
-        uint32_t ae[KPT];  // [E : 9 | entry : 18] of every match under this grid type (a sink's own for the matches it does not bin)
+        uint32_t ae[KPT];  // the entry of every match under this grid type (a sink's own for the matches it does not bin)
 #pragma unroll
         for (int k0 = 0; k0 < KPT; k0 += kChunk) {
             uint32_t old[kChunk], at[kChunk], cg[kChunk], sh[kChunk];
@@ -849,7 +849,7 @@ __device__ __forceinline__ int dense_pair_plain(const FilterParams& p, uint32_t*
                 const uint32_t before = __builtin_amdgcn_ubfe(old[c], sh[c], 8);  // <= 254, or ...
                 if (CROWDED && e != 0u && before == 255u) misc[12] = 1;                // ... the entry's byte has just wrapped
                 ldsa_max(at[c] - e, key_tag | (before << 11) | e);
-                asm("v_lshl_or_b32 %0, %1, 18, %2" : "=v"(ae[k0 + c]) : "v"(e), "v"(at[c]));  // (opaque: the compiler cannot know that an entry is 18 bits)
+                ae[k0 + c] = at[c];
             }
         }
         GMS_STAMP(3);
@@ -860,6 +860,15 @@ __device__ __forceinline__ int dense_pair_plain(const FilterParams& p, uint32_t*
 
         // ---- verifyCellPairs
         if (tid < 2 * kLeftN) {
+            // lane pair of cell i = tid >> 1; the even lane takes the neighbour pairs at d = -21, -20, -19, -1 (positions 0..3 of
+            // the 3 x 3 block), the odd lane the mirrored ones (positions 8..5): s = +-1
+            // (sixteen matches per thread: what follows from the lane alone is worked out here, per grid type, instead of a dozen
+            //  registers of signs, steps and limits held across the binning passes, which do not have them)
+            uint32_t vt = (uint32_t)tid;
+            if constexpr (KPT > 10) asm volatile("" : "+v"(vt));
+            const uint32_t vi = vt >> 1;
+            const uint32_t viy = (vi * 3277u) >> 16, vix = vi - 20u * viy;  // vi / 20, vi % 20 for vi < 400
+            const bool vodd = (vt & 1u) != 0;
             // (everything that does not depend on j* is read at once: the cell's nLeft, its header, the four neighbours' nLeft)
             const int s1 = vodd ? -1 : 1;
             const uint32_t nlb = (CROWDED ? nl_cur + 2u * vi : kDenseNleftOff + vi);
@@ -875,9 +884,11 @@ __device__ __forceinline__ int dense_pair_plain(const FilterParams& p, uint32_t*
                     nl4[c] = CROWDED ? ldsa_ld16(na) : ldsa_ld8(na);
                 }
             }
+            uint32_t ej = 0;
+            bool pass = false;  // the cell pair (i, j*) stands: decided by the even lane
             if (__ballot(ni != 0) != 0ull) {
                 const uint32_t best = hdr_word & ((1u << kDTagShift) - 1u);  // ((max count - 1) << 11) | E(j*), lowest j* among maxima
-                const uint32_t ej = ni ? (best & kDEMask) : (uint32_t)(kDenseRightN + 3);
+                ej = ni ? (best & kDEMask) : (uint32_t)(kDenseRightN + 3);
                 const uint32_t j = (uint32_t)(kDenseRightN + 3) - ej;
                 const uint32_t jy = (j * 3277u) >> 16, jx = j - 20u * jy;
                 const uint32_t lo = vodd ? 19u : 0u, hi = 19u - lo;
@@ -903,23 +914,23 @@ __device__ __forceinline__ int dense_pair_plain(const FilterParams& p, uint32_t*
                 if (ni != 0 && !vodd) {
                     const bool rej = CROWDED ? threshold_rejects(tn >> 4, tn & 15u, score, p.threshold_factor, thr_fast)
                                              : dense_threshold_rejects(tn >> 4, tn & 15u, score, p.threshold_factor, thr_fast, f2i);
-                    ldsa_st32(hdr, rej ? 0u : ej);  // cellPairs[i] as E(j*), 0 = none
+                    pass = !rej;
                 }
             }
+            // cellPairs[i] as E(j*); none: an empty cell, a rejected pair. Grid types 3 and 4 are kept by the odd lane.
+            uint32_t verdict = pass ? ej : kDenseMarkNone;
+            if (g >> 1) verdict = dpp_xor1(verdict);
+            // the lane's first grid type ends up in the low half, its second in the high half (a restart in crowded mode shifts
+            // two new ones in). The row header keeps its arg-max key: the next grid type's keys outrank it, nobody else reads it.
+            if ((uint32_t)(g >> 1) == (vt & 1u)) vd = (vd >> 16) | (verdict << 16);
         }
         __syncthreads();
         GMS_STAMP(5);
 
-        // ---- mark inliers (cellPairs[l] == r) and take this grid type's increments back (plain zero bytes: see dense_pair_rot)
-        uint32_t cur = 0;
+        // ---- take this grid type's increments back (plain zero bytes: see dense_pair_rot); every reader of the matrix is past the
+        //      barrier. After the last grid type as well: the loop has one body.
 #pragma unroll
-        for (int k = 0; k < KPT; ++k) {
-            const uint32_t at = ae[k] & 0x3FFFFu, e = ae[k] >> 18;
-            const uint32_t cr = ldsa_ld32(at - e);  // (a sink's own dword: never equal to its E = 0)
-            ldsa_st8(at, 0u);                       // (after the last grid type as well: the area is free then)
-            cur = shift_in_equal(cur, cr, e);       // match k ends up in bit KPT - 1 - k
-        }
-        acc |= cur;
+        for (int k = 0; k < KPT; ++k) ldsa_st8(ae[k], 0u);
         if (CROWDED && tid < kLeftN / 2) ldsa_st32(kDenseFineOff + (uint32_t)((g + 1) & 1) * (kLeftN * 2u) + 4u * (uint32_t)tid, 0u);
         __syncthreads();
         GMS_STAMP(6);
@@ -939,7 +950,6 @@ __device__ __forceinline__ int dense_pair_plain(const FilterParams& p, uint32_t*
             if (tid < kLeftN) nfine32[tid] = 0;
             if (tid == 0) misc[11] = 0;
         }
-        acc = 0;
         if (tid < 16) trash[tid] = 0x80000000u;
         __syncthreads();
         status = run_types(std::true_type{});
@@ -948,6 +958,45 @@ __device__ __forceinline__ int dense_pair_plain(const FilterParams& p, uint32_t*
         __syncthreads();
         return kPairGeneral;
     }
+
+    // ---- mark inliers (cellPairs[l] == r under some grid type), once per pair: the matrix area is free behind the last barrier
+    //      of the grid types. The verdicts leave the registers, the mark table is built from them -- all of it, for every pair: what
+    //      the previous workgroup left in the LDS is never read --, and a match reads the one entry of its left half cell.
+    if (tid < 2 * kLeftN) ldsa_st32(kDenseMarkVerdictOff + 4u * (uint32_t)tid, vd);  // (cell tid >> 1's four fields: the pair's two dwords)
+    __syncthreads();
+    for (uint32_t s = (uint32_t)tid; s < kDenseMarkEntries; s += NT) {
+        const uint32_t c1 = s >> 2, c1y = (c1 * 3277u) >> 16, c1x = c1 - 20u * c1y;  // (the slots behind the grid: no half cell, none)
+        const int hx = (int)(2u * c1x + (s & 1u)), hy = (int)(2u * c1y + ((s >> 1) & 1u));
+        uint32_t f[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int owner = s < (uint32_t)kFineN ? dense_half_cell_owner(hx, hy, g & 1, g >> 1) : -1;
+            const uint32_t v = ldsa_ld16(kDenseMarkVerdictOff + 8u * (uint32_t)max(owner, 0) + 2u * (uint32_t)g);
+            f[g] = owner >= 0 ? v : kDenseMarkNone;
+        }
+        ldsa_st64(kDenseMarkTableOff + 8u * s, ((uint64_t)(f[2] | (f[3] << 16)) << 32) | (f[0] | (f[1] << 16)));
+    }
+    __syncthreads();
+    uint32_t acc = 0;  // bit KPT - 1 - k: match k of this thread is an inlier under some grid type
+#pragma unroll
+    for (int k0 = 0; k0 < KPT; k0 += kChunk) {
+        uint64_t t[kChunk];
+#pragma unroll
+        for (int c = 0; c < kChunk; ++c) {
+            const uint32_t cw = code[k0 + c];
+            const uint32_t row = (cw >> kPAtShift) - ((cw >> kPEShift) & kDEMask);   // 404 * the cell under grid type 1; a sink's own dword
+            const uint32_t cell = ((row >> 2) * 649u) >> 16;                         // row / 404 (the sinks: kDenseMarkSinkSlot / 4)
+            t[c] = ldsa_ld64(kDenseMarkTableOff + (cell << 5) + ((cw & 1u) << 3) + ((cw & 4u) << 2));  // entry dense_half_cell_slot()
+        }
+#pragma unroll
+        for (int c = 0; c < kChunk; ++c) {
+            const uint32_t e = (code[k0 + c] >> kPEShift) & kDEMask;  // (a sink's 0 equals no field: none is not an E)
+            const uint32_t lo = (uint32_t)t[c], hi = (uint32_t)(t[c] >> 32);
+            const bool in = ((lo & 0xFFFFu) == e) | ((lo >> 16) == e) | ((hi & 0xFFFFu) == e) | ((hi >> 16) == e);
+            acc = 2u * acc + (in ? 1u : 0u);
+        }
+    }
+    GMS_STAMP(1);  // mark table: verdicts out, build, look-up
     GMS_STAMP(7);
     if (p.prefetch_type == 4 && pf_lines) {  // (diagnostic setting: as late as possible)
         if ((uint32_t)tid < pf_lines) pf_sink = pf_base[32u * (uint32_t)tid];
@@ -958,7 +1007,7 @@ __device__ __forceinline__ int dense_pair_plain(const FilterParams& p, uint32_t*
 
     // ---- copy-out: surviving DMatch verbatim, in input order (DLL@0x180048340), from the registers (see dense_pair_rot)
     constexpr int kWaves = NT / 64;
-    uint32_t* cnt_tab = smem;
+    uint32_t* cnt_tab = smem;  // (below the mark table, which slower waves may still be reading)
     unsigned long long keep[KPT];
 #pragma unroll
     for (int k = 0; k < KPT; ++k) keep[k] = __ballot((acc >> (KPT - 1 - k)) & 1u);

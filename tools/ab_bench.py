@@ -28,7 +28,7 @@ for rnd in range(rounds):
     for entry in entries:
         *settings, lib = entry.split(",")
         env = dict(os.environ, **dict(s.split("=", 1) for s in settings))
-        r = subprocess.run([sys.executable, "-c", code.format(root=ROOT, extra=extra, lib=os.path.abspath(lib))], capture_output=True, text=True, env=env)
+        r = subprocess.run([sys.executable, "-c", code.format(root=ROOT, extra=extra, lib=os.path.abspath(lib))], capture_output=True, text=True, env=env, timeout=600)
         label = " ".join(settings + [os.path.basename(lib)])
         try:
             d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -36,7 +36,8 @@ for rnd in range(rounds):
             print(label, round(d["roofline"]["kernel_ms_per_launch"], 4), "ms/launch", round(d["value"]), "pairs/s", d["parity"]["bit_exact"],
                   "frame_table_build_ms", round(d.get("frame_table_build_ms", float("nan")), 3), flush=True)
         except Exception:
-            print(label, "failed", r.stderr[-300:], flush=True)
+            print(label, "failed", r.returncode, r.stderr[-300:], flush=True)
+            sys.exit(1)  # (nothing more is started on a device behind a run that failed)
 for entry, t in times.items():
     if t:
         print("summary", entry, "n", len(t), "min", round(min(t), 4), "max", round(max(t), 4), "mean", round(sum(t) / len(t), 4), flush=True)

@@ -16,7 +16,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 
-PHASES = ["bin_barrier", "region_tables", "clear", "insert_first", "bin_qt_loads", "verify", "mark", "count_select", "out_scan", "copy_out", "insert_leftover", "insert_barrier", "bin_gathers", "bin_compute", "x14", "x15"]
+# (slot 1: the hashed kernels' region tables; in the byte-matrix kernel's default-flags body the once-per-pair mark table -- verdicts
+#  out of the registers, build, look-up --, whose "mark" is the undo of a grid type's increments alone. Slots 14 and 15 are not free:
+#  they carry the wall-clock stamps that --starts saves.)
+PHASES = ["bin_barrier", "region_tables/mark_table", "clear", "insert_first", "bin_qt_loads", "verify", "mark", "count_select", "out_scan", "copy_out", "insert_leftover", "insert_barrier", "bin_gathers", "bin_compute", "x14", "x15"]
 
 
 BY_SCALE = ["eval_s0", "eval_s1", "eval_s2", "eval_s3", "eval_s4", "probe_s0", "probe_s1", "probe_s2", "probe_s3", "probe_s4", "load", "record", "sort", "x13", "x14", "x15"]
