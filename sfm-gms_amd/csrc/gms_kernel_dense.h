@@ -1,7 +1,8 @@
 // gms_kernel_dense.h -- what the byte-matrix forms of the GMS filter share (overview: gms_kernels.hip): the LDS layout of the
 // 400 x 400 byte matrix, the per-keypoint codes of the frame table and the dense code word, the threshold test on small integers
-// and nLeft from the half-cell histogram with the half-cell rule of the mark table. Used by gms_kernel_dense.hip (no scale
-// hypotheses), gms_kernel_scales.hip (scale hypotheses) and gms_kernels.hip (normalize_kernel writes the codes). Internal.
+// and nLeft from the half-cell histogram with the half-cell rule of the mark table and the list of who writes which of its
+// fields. Used by gms_kernel_dense.hip (no scale hypotheses), gms_kernel_scales.hip (scale hypotheses) and gms_kernels.hip
+// (normalize_kernel writes the codes). Internal.
 #pragma once
 #include <stdint.h>
 
@@ -38,7 +39,7 @@ namespace gms {
 //     half-cell parities q = (hx & 1) + 20 (hy & 1) and three "not binned under ..." bits. The left cell under grid
 //     type g is l1 + (q & M_g), M_g = gx + 20 gy, so the row start is one multiply-add away;
 //   * the matrix is zeroed once per pair; after each grid type every match takes its own increment back
-//     (one non-returning atomic) instead of 160 KB being cleared again.
+//     (one store) instead of 160 KB being cleared again -- dense_pair_plain: not after the last, which nobody reads behind.
 // Everything else has to live in the remaining 2.2 KB: the half-cell histogram and the current grid type's nLeft as
 // bytes, the rotation counters and a few sink dwords. The DMatch records stay in registers from the first load to
 // copy-out, so the match array is read exactly once.
@@ -80,6 +81,7 @@ __device__ __forceinline__ bool dense_threshold_rejects(uint32_t T, uint32_t n, 
 using lds_u64_t = __attribute__((address_space(3))) uint64_t;
 __device__ __forceinline__ uint64_t ldsa_ld64(uint32_t a) { return *reinterpret_cast<lds_u64_t*>((uintptr_t)a); }
 __device__ __forceinline__ void ldsa_st64(uint32_t a, uint64_t v) { *reinterpret_cast<lds_u64_t*>((uintptr_t)a) = v; }
+__device__ __forceinline__ void ldsa_st16(uint32_t a, uint32_t v) { *reinterpret_cast<lds_u16_t*>((uintptr_t)a) = (uint16_t)v; }  // one field
 #endif
 
 // mNumberPointsInPerCellLeft of cell (x, y) under the grid type shifted by (gx, gy) half cells, from the half-cell histogram --
@@ -115,16 +117,16 @@ constexpr uint32_t dense_half_cell_slot(int hx, int hy)
 static_assert(dense_half_cell_owner(39, 38, 1, 0) == -1 && dense_half_cell_owner(39, 38, 0, 1) == 19 * kLeftW + 19 &&
               dense_half_cell_owner(0, 0, 1, 1) == 0 && dense_half_cell_owner(1, 1, 1, 1) == kLeftW + 1, "half cells and shifted grids");
 
-// The mark table of dense_pair_plain: after the last grid type the matrix area is free, and the verdicts of all four grid types --
-// cellPairs[cell] as E(j*), kDenseMarkNone where the cell pair was rejected or the cell is empty -- go into it once per pair:
-//   verdicts  [400] x 4 16-bit fields: what the two verifying lanes of a cell decided under grid types 1..4 (they kept them in
-//             registers while the matrix lived);
+// The mark table of dense_pair_plain: behind the last grid type's verification nobody reads the matrix any more (that grid type's
+// increments are still in it), and the verdicts of all four grid types -- cellPairs[cell] as E(j*), kDenseMarkNone where the cell
+// pair was rejected or the cell is empty, kept in the verifying lanes' registers while the matrix lived -- go into it once per pair:
 //   table     8-byte entries of 4 16-bit fields, entry dense_half_cell_slot(hx, hy): field g = the verdict of the cell that owns
 //             the half cell under grid type g, kDenseMarkNone where nobody does. A match is an inlier when one field of its left
 //             point's entry equals its E(r): one 8-byte read instead of a row header per grid type. A match that is not binned
 //             (code word = a sink's) computes "cell" kDenseMarkSinkSlot / 4 from its sink's offset: an entry of its own, none four times.
-// Both lie above everything the copy-out keeps in the area (its scan table: at most 8 KB from offset 0), and the table's offset fits
-// the 16-bit immediate of an LDS instruction.
+// The lanes store the fields directly (who writes which: below); kDenseMarkVerdictOff is where an earlier form of the kernel laid
+// the verdicts down first, [400] x 4 fields -- nothing is written there now. The table lies above everything the copy-out keeps in
+// the area (its scan table: at most 8 KB from offset 0), and its offset fits the 16-bit immediate of an LDS instruction.
 constexpr uint32_t kDenseMarkNone = 0xFFFFu;             // never an E(r): those are 4..403, a sink's is 0
 constexpr uint32_t kDenseMarkVerdictOff = 16384;
 constexpr uint32_t kDenseMarkTableOff = 32768;
@@ -134,6 +136,35 @@ static_assert(((((kDenseTrashOff + 60u) >> 2) * 649u) >> 16) == kDenseMarkSinkSl
               "all sixteen sink dwords divide to one row above the grid");
 static_assert(kDenseMarkTableOff + 8u * kDenseMarkEntries <= kDenseBytes && kDenseMarkTableOff + 8u * kDenseMarkEntries < 65536u &&
               kDenseMarkVerdictOff + 8u * kLeftN <= kDenseMarkTableOff, "verdicts and table inside the matrix area, apart");
+
+// Who writes the table (tests/cpp/mark_scatter_check.cpp replays both kinds of writer over all fields). A field is one 16-bit word:
+// field f = 4 * entry + grid type, at dense_mark_field_off(f).
+//   owned fields    the two verifying lanes of cell (x, y) store the cell's verdict under grid type g into field g of its (up to)
+//                   four half cells: dense_cell_half_slot(x, y, gx, gy, dx, dy), dx, dy in {0, 1} -- the inverse of
+//                   dense_half_cell_owner(). Where a shifted axis cuts the cell at the image's first half row or column the index is
+//                   clamped as dense_nleft_cm clamps it: that store repeats one of the cell's own (same field, same value), so
+//                   none of the four is predicated;
+//   the others      fields nobody owns -- hx == 39 under the x-shifted grid types, hy == 39 under the y-shifted ones,
+//                   kDenseMarkUnownedFields in all -- and the four fields of every entry behind the grid up to the sink's: field
+//                   dense_mark_none_field(u), u < kDenseMarkNoneFields, written with kDenseMarkNone by the lanes that do not verify.
+// Every field has exactly one writer, for every pair.
+constexpr uint32_t dense_mark_field_off(uint32_t field) { return kDenseMarkTableOff + 2u * field; }
+constexpr uint32_t dense_cell_half_slot(int x, int y, int gx, int gy, int dx, int dy)
+{
+    return dense_half_cell_slot(2 * x - gx + dx < 0 ? 0 : 2 * x - gx + dx, 2 * y - gy + dy < 0 ? 0 : 2 * y - gy + dy);
+}
+constexpr uint32_t kDenseMarkUnownedFields = 2u * kFineW + kFineW + (kFineW - 1u);  // 159: (39, 39) under grid type 4 counts once
+constexpr uint32_t kDenseMarkNoneFields = kDenseMarkUnownedFields + 4u * (kDenseMarkEntries - (uint32_t)kFineN);  // 243
+constexpr uint32_t dense_mark_none_field(uint32_t u)
+{
+    constexpr uint32_t w = (uint32_t)kFineW, last = w - 1u;
+    return u < 2u * w   ? 4u * dense_half_cell_slot((int)last, (int)(u < w ? u : u - w)) + (u < w ? 1u : 3u)            // hx == 39: grid types 2, 4
+           : u < 3u * w ? 4u * dense_half_cell_slot((int)(u - 2u * w), (int)last) + 2u                                  // hy == 39: grid type 3 ...
+           : u < kDenseMarkUnownedFields ? 4u * dense_half_cell_slot((int)(u - 3u * w), (int)last) + 3u                 // ... and 4, hx < 39
+                                         : 4u * (uint32_t)kFineN + (u - kDenseMarkUnownedFields);                       // behind the grid
+}
+static_assert(dense_mark_none_field(kDenseMarkNoneFields - 1u) == 4u * kDenseMarkEntries - 1u && dense_cell_half_slot(0, 0, 1, 1, 0, 0) == 0u &&
+              dense_cell_half_slot(3, 2, 1, 0, 0, 1) == dense_half_cell_slot(5, 5), "the table's last field; clamping; a cell's half cells");
 
 // dense code word
                                                      // bits 0..4   q = (hx & 1) + 20 * (hy & 1)

@@ -2,6 +2,9 @@
 // gms_kernels.hip; the matrix and its LDS layout: gms_kernel_dense.h). Two per-pair bodies -- dense_pair_plain() for the
 // reference's default flags (the headline workload) and dense_pair_rot() with rotation hypotheses --, the kernel that runs one of
 // them and hands the pairs it cannot take to hash_pair() (gms_kernel_hash.h), its launch and its dynamic-LDS limits.
+// The end of a pair in dense_pair_plain: the last grid type takes no increments back (nothing reads the matrix behind its
+// verification), the verifying lanes store their verdicts straight into the mark table over those bytes, one barrier, and every
+// match reads the one entry of its left half cell.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -926,14 +929,18 @@ __device__ __forceinline__ int dense_pair_plain(const FilterParams& p, uint32_t*
         }
         __syncthreads();
         GMS_STAMP(5);
-
-        // ---- take this grid type's increments back (plain zero bytes: see dense_pair_rot); every reader of the matrix is past the
-        //      barrier. After the last grid type as well: the loop has one body.
+        // Nothing reads the matrix behind the last grid type's verification: the mark table and the copy-out's count table, which
+        // reuse the area, write every word before they read it, and the next workgroup on the CU clears the LDS itself. So the last
+        // grid type leaves its increments (and the crowded counters) where they are: it ends here. (workgroup-uniform; one loop body)
+        if (g != 3) {
+            // ---- take this grid type's increments back (plain zero bytes: see dense_pair_rot); every reader of the matrix is past
+            //      the barrier.
 #pragma unroll
-        for (int k = 0; k < KPT; ++k) ldsa_st8(ae[k], 0u);
-        if (CROWDED && tid < kLeftN / 2) ldsa_st32(kDenseFineOff + (uint32_t)((g + 1) & 1) * (kLeftN * 2u) + 4u * (uint32_t)tid, 0u);
-        __syncthreads();
-        GMS_STAMP(6);
+            for (int k = 0; k < KPT; ++k) ldsa_st8(ae[k], 0u);
+            if (CROWDED && tid < kLeftN / 2) ldsa_st32(kDenseFineOff + (uint32_t)((g + 1) & 1) * (kLeftN * 2u) + 4u * (uint32_t)tid, 0u);
+            __syncthreads();
+            GMS_STAMP(6);
+        }
     }
     return 0;
     };
@@ -960,21 +967,25 @@ __device__ __forceinline__ int dense_pair_plain(const FilterParams& p, uint32_t*
     }
 
     // ---- mark inliers (cellPairs[l] == r under some grid type), once per pair: the matrix area is free behind the last barrier
-    //      of the grid types. The verdicts leave the registers, the mark table is built from them -- all of it, for every pair: what
-    //      the previous workgroup left in the LDS is never read --, and a match reads the one entry of its left half cell.
-    if (tid < 2 * kLeftN) ldsa_st32(kDenseMarkVerdictOff + 4u * (uint32_t)tid, vd);  // (cell tid >> 1's four fields: the pair's two dwords)
-    __syncthreads();
-    for (uint32_t s = (uint32_t)tid; s < kDenseMarkEntries; s += NT) {
-        const uint32_t c1 = s >> 2, c1y = (c1 * 3277u) >> 16, c1x = c1 - 20u * c1y;  // (the slots behind the grid: no half cell, none)
-        const int hx = (int)(2u * c1x + (s & 1u)), hy = (int)(2u * c1y + ((s >> 1) & 1u));
-        uint32_t f[4];
+    //      of the grid types' verification (the last grid type's increments still lie in it: every field below is written before it
+    //      is read). The verdicts go from the registers straight into the mark table -- all of it, for every pair: neither the
+    //      matrix's bytes nor what the previous workgroup left in the LDS is ever read --, and a match reads the one entry of its left
+    //      half cell. Who writes which field: gms_kernel_dense.h.
+    static_assert(NT > 2 * kLeftN, "the lanes that do not verify write the fields nobody owns");
+    if (tid < 2 * kLeftN) {
+        // a verifying lane: its cell's verdicts under its two grid types into field g of the cell's four half cells (unpredicated:
+        // a half cell cut off by the image's border is clamped onto one of the cell's own, same field, same value)
+        const uint32_t vi = (uint32_t)tid >> 1, viy = (vi * 3277u) >> 16, vix = vi - 20u * viy;
+        const int gy = tid & 1;
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int owner = s < (uint32_t)kFineN ? dense_half_cell_owner(hx, hy, g & 1, g >> 1) : -1;
-            const uint32_t v = ldsa_ld16(kDenseMarkVerdictOff + 8u * (uint32_t)max(owner, 0) + 2u * (uint32_t)g);
-            f[g] = owner >= 0 ? v : kDenseMarkNone;
-        }
-        ldsa_st64(kDenseMarkTableOff + 8u * s, ((uint64_t)(f[2] | (f[3] << 16)) << 32) | (f[0] | (f[1] << 16)));
+        for (int gx = 0; gx < 2; ++gx)
+#pragma unroll
+            for (int d = 0; d < 4; ++d)
+                ldsa_st16(dense_mark_field_off(4u * dense_cell_half_slot((int)vix, (int)viy, gx, gy, d & 1, d >> 1) + 2u * (uint32_t)gy + (uint32_t)gx),
+                          gx ? vd >> 16 : vd);
+    } else {
+        for (uint32_t u = (uint32_t)tid - 2u * kLeftN; u < kDenseMarkNoneFields; u += (uint32_t)NT - 2u * kLeftN)
+            ldsa_st16(dense_mark_field_off(dense_mark_none_field(u)), kDenseMarkNone);
     }
     __syncthreads();
     uint32_t acc = 0;  // bit KPT - 1 - k: match k of this thread is an inlier under some grid type
@@ -996,7 +1007,7 @@ __device__ __forceinline__ int dense_pair_plain(const FilterParams& p, uint32_t*
             acc = 2u * acc + (in ? 1u : 0u);
         }
     }
-    GMS_STAMP(1);  // mark table: verdicts out, build, look-up
+    GMS_STAMP(1);  // mark table: the verdicts' scatter, its barrier, look-up
     GMS_STAMP(7);
     if (p.prefetch_type == 4 && pf_lines) {  // (diagnostic setting: as late as possible)
         if ((uint32_t)tid < pf_lines) pf_sink = pf_base[32u * (uint32_t)tid];

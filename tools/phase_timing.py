@@ -16,8 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 
-# (slot 1: the hashed kernels' region tables; in the byte-matrix kernel's default-flags body the once-per-pair mark table -- verdicts
-#  out of the registers, build, look-up --, whose "mark" is the undo of a grid type's increments alone. Slots 14 and 15 are not free:
+# (slot 1: the hashed kernels' region tables; in the byte-matrix kernel's default-flags body the once-per-pair mark table -- the verdicts'
+#  scatter, its barrier, the look-up --, whose "mark" is the undo of the increments alone (grid types 1 to 3). Slots 14 and 15 are not free:
 #  they carry the wall-clock stamps that --starts saves.)
 PHASES = ["bin_barrier", "region_tables/mark_table", "clear", "insert_first", "bin_qt_loads", "verify", "mark", "count_select", "out_scan", "copy_out", "insert_leftover", "insert_barrier", "bin_gathers", "bin_compute", "x14", "x15"]
 
