@@ -475,6 +475,53 @@ int gms_sfm_register(const int64_t* frame_off, int n_frames, const gms_pair* pai
                      gms_sfm_pair_reg* reg, double* points_world, int32_t* track, int64_t cloud_cap, double* cloud, int32_t* cloud_id,
                      int32_t* cloud_obs, int32_t* cloud_est, double* cloud_spread, gms_sfm_summary* summary);
 
+/* ---- one-to-one matches per pair, and the registration on them (the library's own; tests/match_unique_ref.py is
+ * the definition in numpy) ---------------------------------------------------------------------------------------------------------
+ * A nearest-neighbour matcher gives every keypoint of frame_a a match, so several may name one keypoint of frame_b, and the tracks
+ * then chain two keypoints of one frame together. This stage keeps, per pair, a one-to-one subset of the matches.
+ *   Match k of pair i is live when k < n_i (n_i as in the registration: clamp(tv.n_points, 0, m) when tv.status is GMS_OK, else 0),
+ *   its mask byte is non-zero and both indices lie inside their frames. With null d_tv: n_i = m; with null d_mask: every byte counts
+ *   as set. key(k) = (ord(distance) << 32) | k, ord(d) = the bit pattern of a finite d > 0, 0 for +0 and -0, 0xFFFFFFFF for anything
+ *   else (negative, infinite, no number: last, ordered by k). A live match is kept when its key is the least among the live matches
+ *   of its pair that share its trainIdx and the least among those that share its queryIdx. Everything else -- the losers, the
+ *   matches that are not live, the slots in [n_i, m) -- gets 0. It is not a maximum matching: a match may lose on one side to a
+ *   match that loses on the other, and then neither is kept. Integer minima only: the same bytes run after run.
+ * gms_match_unique_device: writes d_keep (one uint8 per match slot) for [match_off, match_off + m) of every pair whose record fits
+ *   the arrays (as in the registration; a pair that does not fit has nothing read or written and counts {0, 0}; other slots are not
+ *   written), and d_counts (two int32 per pair: live, kept). Any pair list: a frame may be frame_a or frame_b of any number of pairs,
+ *   and a pair of frames may appear more than once; the match ranges of different pairs do not overlap. d_mask and d_tv may be null
+ *   (above). A null ctx, d_frame_off, d_ws, or (n_pairs > 0) d_pairs, d_counts, or (total_matches > 0) d_filtered, d_keep; max_m
+ *   outside [0, 2^24); total_kp >= 2^31 - 1; a workspace that is not 256-byte aligned or too small: GMS_ERR_BAD_ARG, nothing run.
+ *   Stream-ordered on the context's stream; no allocation, no synchronisation, no readback (graph-capturable); three launches.
+ * gms_match_unique_workspace_bytes: 32 bytes per match slot (two open-addressing tables of 2 m keys per pair, laid out by match_off),
+ *   rounded up to 256; at least 256. It does not grow with n_pairs or total_kp. 0: sizes refused.
+ * gms_match_unique: the same on host arrays, synchronous, on the current HIP device; keep covers every slot below max(match_off + m)
+ *   (what the device call leaves untouched is 0). mask and tv may be null. It refuses what gms_sfm_register refuses of the pair
+ *   records and offsets: a frame index out of range, m < 0, match_off < 0 or beyond 2^40 - m, decreasing frame_off.
+ * gms_sfm_register_keep_device / gms_sfm_register_keep: gms_sfm_register_device / gms_sfm_register with a keep plane (one uint8 per
+ *   match slot, as above). A null d_keep / keep: the same bytes as those calls. With a plane, a match of the registration whose byte
+ *   is 0 does not feed the tracks: it is no edge and no estimate, and d_track at its slot (match_off + rank) stays -1. d_track, the
+ *   cloud arrays and the summary's n_tracks, n_points, n_multi follow the kept matches (n_points and d_cloud_est count kept
+ *   estimates only). d_views, d_reg, d_points_world and the links do not read the plane: the same bytes as without it. When every ok
+ *   pair's kept matches are one-to-one and the ok pairs form a tree over the frames -- gms_sfm_plan's always do -- no track holds two
+ *   keypoints of a frame: n_multi = 0. With a caller's plan that is no tree, n_multi is still counted. */
+size_t gms_match_unique_workspace_bytes(int n_pairs, int64_t total_kp, int64_t total_matches);
+int gms_match_unique_device(gms_ctx* ctx, const int64_t* d_frame_off, int n_frames, int64_t total_kp, const gms_pair* d_pairs, int n_pairs,
+                            int max_m, int64_t total_matches, const gms_dmatch* d_filtered, const uint8_t* d_mask, const gms_two_view* d_tv,
+                            void* d_ws, size_t ws_bytes, uint8_t* d_keep, int32_t* d_counts);
+int gms_match_unique(const int64_t* frame_off, int n_frames, const gms_pair* pairs, int n_pairs, const gms_dmatch* filtered,
+                     const uint8_t* mask, const gms_two_view* tv, uint8_t* keep, int32_t* counts);
+int gms_sfm_register_keep_device(gms_ctx* ctx, const int64_t* d_frame_off, int n_frames, int64_t total_kp, const gms_pair* d_pairs,
+                                 const gms_sfm_plan_entry* d_plan, int n_pairs, int max_m, int64_t total_matches, const gms_dmatch* d_filtered,
+                                 const uint8_t* d_mask, const double* d_points3d, const gms_two_view* d_tv, int root, int min_links,
+                                 void* d_ws, size_t ws_bytes, gms_sfm_view* d_views, gms_sfm_pair_reg* d_reg, double* d_points_world,
+                                 int32_t* d_track, int64_t cloud_cap, double* d_cloud, int32_t* d_cloud_id, int32_t* d_cloud_obs,
+                                 int32_t* d_cloud_est, double* d_cloud_spread, gms_sfm_summary* d_summary, const uint8_t* d_keep);
+int gms_sfm_register_keep(const int64_t* frame_off, int n_frames, const gms_pair* pairs, int n_pairs, const gms_dmatch* filtered,
+                          const uint8_t* mask, const double* points3d, const gms_two_view* tv, int root, int min_links, gms_sfm_view* views,
+                          gms_sfm_pair_reg* reg, double* points_world, int32_t* track, int64_t cloud_cap, double* cloud, int32_t* cloud_id,
+                          int32_t* cloud_obs, int32_t* cloud_est, double* cloud_spread, gms_sfm_summary* summary, const uint8_t* keep);
+
 /* ---- bundle adjustment behind the registration (the library's own; tests/sfm_ba_ref.py is the definition) --------
  * Refines the registered views and the cloud over all the keypoints a track chains together. Inputs: the keypoints, d_frame_off,
  * d_pairs, the survivors d_filtered and d_mask as the two-view stage took and left them, and d_views, d_reg, d_track, d_cloud,

@@ -18,7 +18,7 @@ from .api import matchGMS, matchLOGOS, trainLogosDictionary, bruteForceMatch, st
 from .api import resize, warpAffine, getRotationMatrix2D, imgRotate  # noqa: F401
 from .api import findChessboardCorners, cornerSubPix, calibrateCamera, addChessboardPoints, chessboardObjectPoints  # noqa: F401
 from .types import CHESS_CANDIDATE_DTYPE  # noqa: F401
-from .api import structureFromMotionMulti, registerViews, sfm_plan  # noqa: F401
+from .api import structureFromMotionMulti, registerViews, sfm_plan, uniqueMatches  # noqa: F401
 from .types import SFM_PLAN_DTYPE, SFM_VIEW_DTYPE, SFM_PAIR_REG_DTYPE, SFM_SUMMARY_DTYPE, GMS_SFM_SKIPPED  # noqa: F401
 from .api import bundleAdjust  # noqa: F401
 from .api import stereoRectify, rectifyQ, rectify, undistort, denseStereo, denseFuse, filterSpeckles  # noqa: F401
@@ -35,7 +35,7 @@ __all__ = [
     "stereoSGM", "stereo_match_sgm", "STEREO_SGM_PARAMS_DTYPE", "stereo_sgm_params",
     "portraitMode", "medianBlur", "structureFromMotion", "resize", "warpAffine", "getRotationMatrix2D", "imgRotate", "PORTRAIT_PARAMS_DTYPE", "portrait_params",
     "findChessboardCorners", "cornerSubPix", "calibrateCamera", "addChessboardPoints", "chessboardObjectPoints", "CHESS_CANDIDATE_DTYPE",
-    "structureFromMotionMulti", "registerViews", "sfm_plan", "SFM_PLAN_DTYPE", "SFM_VIEW_DTYPE", "SFM_PAIR_REG_DTYPE", "SFM_SUMMARY_DTYPE",
+    "structureFromMotionMulti", "registerViews", "sfm_plan", "uniqueMatches", "SFM_PLAN_DTYPE", "SFM_VIEW_DTYPE", "SFM_PAIR_REG_DTYPE", "SFM_SUMMARY_DTYPE",
     "GMS_SFM_SKIPPED", "bundleAdjust", "SFM_BA_PARAMS_DTYPE", "SFM_BA_SUMMARY_DTYPE", "SFM_BA_REFINED", "SFM_BA_MULTI", "SFM_BA_FEW",
     "SFM_BA_KEPT", "SFM_BA_DEFAULTS", "sfm_ba_params",
     "stereoRectify", "rectifyQ", "rectify", "undistort", "denseStereo", "denseFuse", "filterSpeckles", "DENSE_FUSE_SRC_DTYPE", "dense_fuse_neighbors", "RECTIFY_PLAN_DTYPE", "RectifyPlan",

@@ -284,13 +284,32 @@ class GmsContext:
 
     def sfm_register_device(self, d_frame_off, n_frames, total_kp, d_pairs, d_plan, n_pairs, max_m, total_matches, d_filtered, d_mask,
                             d_points3d, d_tv, root, min_links, d_ws, ws_bytes, d_views, d_reg, d_points_world, d_track, cloud_cap, d_cloud,
-                            d_cloud_id, d_cloud_obs, d_cloud_est, d_cloud_spread, d_summary):
+                            d_cloud_id, d_cloud_obs, d_cloud_est, d_cloud_spread, d_summary, d_keep=None):
         """gms_sfm_register_device on the pairs, survivors, mask, points and records gms_two_view_batch_device left; d_plan: sfm_plan's
-        records in device memory. Stream-ordered, capturable."""
+        records in device memory. d_keep: a keep plane (match_unique_device's) -> gms_sfm_register_keep_device.
+        Stream-ordered, capturable."""
+        if d_keep:
+            _check(self._lib.gms_sfm_register_keep_device(self._h, d_frame_off, int(n_frames), int(total_kp), d_pairs, d_plan, int(n_pairs),
+                                                          int(max_m), int(total_matches), d_filtered, d_mask, d_points3d, d_tv, int(root),
+                                                          int(min_links), d_ws, int(ws_bytes), d_views, d_reg, d_points_world, d_track,
+                                                          int(cloud_cap), d_cloud, d_cloud_id, d_cloud_obs, d_cloud_est, d_cloud_spread, d_summary,
+                                                          d_keep), self._lib, "gms_sfm_register_keep_device")
+            return
         _check(self._lib.gms_sfm_register_device(self._h, d_frame_off, int(n_frames), int(total_kp), d_pairs, d_plan, int(n_pairs), int(max_m),
                                                  int(total_matches), d_filtered, d_mask, d_points3d, d_tv, int(root), int(min_links), d_ws,
                                                  int(ws_bytes), d_views, d_reg, d_points_world, d_track, int(cloud_cap), d_cloud, d_cloud_id,
                                                  d_cloud_obs, d_cloud_est, d_cloud_spread, d_summary), self._lib, "gms_sfm_register_device")
+
+    # -- one-to-one matches per pair (include/gms.h; DESIGN.md 4.10e; batch.MatchUnique drives this) ---------------------------------
+    def match_unique_workspace_bytes(self, n_pairs, total_kp, total_matches):
+        return int(self._lib.gms_match_unique_workspace_bytes(int(n_pairs), int(total_kp), int(total_matches)))
+
+    def match_unique_device(self, d_frame_off, n_frames, total_kp, d_pairs, n_pairs, max_m, total_matches, d_filtered, d_mask, d_tv, d_ws,
+                            ws_bytes, d_keep, d_counts):
+        """gms_match_unique_device on raw device pointers; d_mask / d_tv: None for every slot below m live. Stream-ordered, capturable."""
+        _check(self._lib.gms_match_unique_device(self._h, d_frame_off or None, int(n_frames), int(total_kp), d_pairs or None, int(n_pairs),
+                                                 int(max_m), int(total_matches), d_filtered or None, d_mask or None, d_tv or None, d_ws or None,
+                                                 int(ws_bytes), d_keep or None, d_counts or None), self._lib, "gms_match_unique_device")
 
     # -- bundle adjustment behind the registration (include/gms.h; DESIGN.md 4.10c) --------------------------------------------------
     def sfm_ba_workspace_bytes(self, n_frames, n_pairs, total_kp, cloud_cap):
@@ -804,13 +823,34 @@ def sfm_trim(out):
     return out
 
 
-def registerViews(frame_off, pairs, matches, mask, points3d, two_view, root=0, min_links=8, cloud_cap=None):
+def uniqueMatches(matches, n1, n2, mask=None):
+    """gms_match_unique on one match list (synchronous, on the current device): matches DMATCH_DTYPE between n1 query and n2 train
+    keypoints, mask uint8 per match or None -> (keep uint8 per match, (live, kept)). A match is live when its mask byte is non-zero
+    and both indices lie inside; it is kept when it is the best (distance, then position; negative, infinite and NaN distances last)
+    of the live matches on its train keypoint and of those on its query keypoint. One-to-one, not a maximum matching (DESIGN.md
+    4.10e)."""
+    m = _as(matches, DMATCH_DTYPE, "matches")
+    mk = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+    if mk is not None and len(mk) != len(m):
+        raise ValueError("mask: one byte per match")
+    frame_off = np.array([0, int(n1), int(n1) + int(n2)], np.int64)
+    recs = np.zeros(1, PAIR_DTYPE)
+    recs[0] = (0, 1, len(m), 0, 0)
+    keep, counts = np.zeros(len(m), np.uint8), np.zeros(2, np.int32)
+    lib = load_library()
+    _check(lib.gms_match_unique(frame_off.ctypes.data, 2, recs.ctypes.data, 1, m.ctypes.data, None if mk is None else mk.ctypes.data, None,
+                                keep.ctypes.data, counts.ctypes.data), lib, "gms_match_unique")
+    return keep, (int(counts[0]), int(counts[1]))
+
+
+def registerViews(frame_off, pairs, matches, mask, points3d, two_view, root=0, min_links=8, cloud_cap=None, keep=None):
     """gms_sfm_register, the one-shot on host arrays (synchronous, on the current device): the two-view results of many pairs --
     frame_off int64 [n_frames + 1], pairs PAIR_DTYPE, and matches (DMATCH_DTYPE), mask (uint8), points3d ([.., 3] float64) laid out by
     the pairs' match_off, two_view TWO_VIEW_DTYPE per pair: pipeline.run_dataset's arrays -- joined into the frame of `root`. Returns
     dict(plan, views SFM_VIEW_DTYPE per frame, registration SFM_PAIR_REG_DTYPE per pair, points_world, track, cloud, cloud_id,
     cloud_obs, cloud_est, cloud_spread, summary). Loop closure is not done; re-triangulation over all views and
-    bundle adjustment are bundleAdjust's, on this call's result."""
+    bundle adjustment are bundleAdjust's, on this call's result. keep: a keep plane, uint8 per match slot (batch.unique_matches';
+    DESIGN.md 4.10e) -> gms_sfm_register_keep: a match whose byte is 0 feeds no track; None: gms_sfm_register."""
     frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
     recs = _as(pairs, PAIR_DTYPE, "pairs")
     n_frames, n = len(frame_off) - 1, len(recs)
@@ -820,13 +860,19 @@ def registerViews(frame_off, pairs, matches, mask, points3d, two_view, root=0, m
     tv = _as(two_view, TWO_VIEW_DTYPE, "two_view")
     if min(len(m), len(mk), len(pts)) < total or len(tv) != n:
         raise ValueError("matches, mask and points3d cover every pair's match range; one two_view record per pair")
+    kp = None if keep is None else np.ascontiguousarray(keep, dtype=np.uint8)
+    if kp is not None and len(kp) < total:
+        raise ValueError("keep covers every pair's match range")
     cap = max(int(frame_off[-1]) // 2, 0) if cloud_cap is None else int(cloud_cap)
     out = sfm_outputs(n_frames, n, total, max(cap, 0))   # (a negative capacity is the C call's to refuse)
     lib = load_library()
-    _check(lib.gms_sfm_register(frame_off.ctypes.data, n_frames, recs.ctypes.data, n, m.ctypes.data, mk.ctypes.data, pts.ctypes.data,
-                                tv.ctypes.data, int(root), int(min_links), *(out[k].ctypes.data for k in ("views", "registration",
-                                "points_world", "track")), cap, *(out[k].ctypes.data for k in ("cloud", "cloud_id", "cloud_obs",
-                                "cloud_est", "cloud_spread", "summary"))), lib, "gms_sfm_register")
+    args = (frame_off.ctypes.data, n_frames, recs.ctypes.data, n, m.ctypes.data, mk.ctypes.data, pts.ctypes.data, tv.ctypes.data, int(root),
+            int(min_links), *(out[k].ctypes.data for k in ("views", "registration", "points_world", "track")), cap,
+            *(out[k].ctypes.data for k in ("cloud", "cloud_id", "cloud_obs", "cloud_est", "cloud_spread", "summary")))
+    if kp is None:
+        _check(lib.gms_sfm_register(*args), lib, "gms_sfm_register")
+    else:
+        _check(lib.gms_sfm_register_keep(*args, kp.ctypes.data), lib, "gms_sfm_register_keep")
     out["plan"] = sfm_plan(recs, n_frames, root)
     return sfm_trim(out)
 
@@ -861,7 +907,8 @@ def bundleAdjust(keypoints, frame_off, pairs, matches, mask, registration, camer
     return out
 
 
-def structureFromMotionMulti(images, camera, dist=None, method="gms", pairs=None, root=0, min_links=8, ctx=None, bundle=False, **params):
+def structureFromMotionMulti(images, camera, dist=None, method="gms", pairs=None, root=0, min_links=8, ctx=None, bundle=False, unique=False,
+                             **params):
     """structureFromMotion for a sequence: n photographs of one size (a list, or [n, H, W] / [n, H, W, 3]) -> every pair's two-view result
     and the registration that joins them into the frame of image `root` (pipeline.run_images(..., register=True)). pairs: (frame_a,
     frame_b) rows, default the chain (i, i + 1); they are walked in order, a pair registers frame_b when frame_a is registered.
@@ -870,6 +917,10 @@ def structureFromMotionMulti(images, camera, dist=None, method="gms", pairs=None
     A pair without a pose does not raise here: its registration status says so, and the frames behind it stay unregistered.
     bundle=True: bundle adjustment behind the registration (gms_sfm_ba_device; its keywords n_iters, n_cg, lambda0, cg_tol, ftol,
     huber_px, retriangulate among params) adds views_ba, cloud_ba, track_status and ba_summary; bundle=False returns the dict without.
+    unique=True: the tracks are built from one-to-one matches only (gms_match_unique_device in front of the registration; DESIGN.md
+    4.10e), so that no track holds two keypoints of a frame (summary n_multi = 0) and the bundle adjustment excludes none for it; adds
+    `keep` (uint8 per match slot) and `unique_counts` (live, kept per pair). The views are the same bytes either way. unique=False
+    returns the dict without.
     dense=True among params adds `dense`, one cloud per pair in the root's frame; fuse=True beside it (fuse_tol16, fuse_min_support,
     fuse_cap: run_images') adds `dense_fused`, those clouds fused into one by depth consistency; fuse=True without
     dense=True raises ValueError. dense_speckle = (max_speckle_size, max_diff16): filterSpeckles on every pair's map before the
@@ -896,7 +947,7 @@ def structureFromMotionMulti(images, camera, dist=None, method="gms", pairs=None
     if method == "logos" and opts.get("dictionary") is None:
         opts.setdefault("train_dictionary", True)
     return pipeline.run_images(ctx or default_context(), stack, camera, dist, method=method, pairs=pairs, register=True, root=root,
-                               min_links=min_links, bundle=bundle, **opts)
+                               min_links=min_links, bundle=bundle, unique=unique, **opts)
 
 
 def default_context():

@@ -1250,11 +1250,14 @@ class SfmRegister:
     (api.sfm_plan, computed here on the host from the pair list), the workspace and every output, sized once, so that run() can be
     repeated or captured into a graph. The inputs -- survivors, mask, points and two-view records, as gms_two_view_batch_device
     leaves them -- are either the caller's device tensors, handed to run(), or the object's own (load() copies host arrays into them;
-    run() without arguments reads them). frame_off: int64 [n_frames + 1] on the host; pairs: PAIR_DTYPE records."""
+    run() without arguments reads them). frame_off: int64 [n_frames + 1] on the host; pairs: PAIR_DTYPE records.
+    keep: None -- gms_sfm_register_device; a uint8 device tensor with one byte per match slot (a MatchUnique's d_keep)
+    -- every run() is gms_sfm_register_keep_device on it; True -- the same on the object's own plane, which load(..., keep=) fills."""
 
-    def __init__(self, ctx, frame_off, pairs, root=0, min_links=8, cloud_cap=None, device=None, d_frame_off=None, d_pairs=None):
+    def __init__(self, ctx, frame_off, pairs, root=0, min_links=8, cloud_cap=None, device=None, d_frame_off=None, d_pairs=None, keep=None):
         from .api import sfm_plan
         from .types import SFM_PAIR_REG_DTYPE, SFM_SUMMARY_DTYPE, SFM_VIEW_DTYPE, TWO_VIEW_DTYPE
+        self.d_keep = None if keep is None or keep is False or keep is True else keep   # (True: the object's own, made below)
         self.ctx, self.root, self.min_links = ctx, int(root), int(min_links)
         self.frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
         self.recs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
@@ -1286,6 +1289,10 @@ class SfmRegister:
         self.d_summary = torch.zeros(SFM_SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         self._own = None
         self._tv_bytes = TWO_VIEW_DTYPE.itemsize
+        if keep is True:
+            self.d_keep = torch.zeros(m, dtype=torch.uint8, device=dev)
+        elif self.d_keep is not None and (self.d_keep.dtype != torch.uint8 or self.d_keep.numel() < self.total_m):
+            raise ValueError("SfmRegister: keep is a uint8 tensor with one byte per match slot")
         torch.cuda.synchronize(dev)
 
     def _own_inputs(self):
@@ -1295,9 +1302,10 @@ class SfmRegister:
                          torch.zeros(m * 3, dtype=torch.float64, device=dev), torch.zeros(n * self._tv_bytes, dtype=torch.uint8, device=dev))
         return self._own
 
-    def load(self, matches, mask, points3d, two_view):
+    def load(self, matches, mask, points3d, two_view, keep=None):
         """Host arrays (run_dataset's out, mask, points3d, two_view) into the object's own input tensors (same tensors every time: a
-        captured run() reads what the latest load() left)."""
+        captured run() reads what the latest load() left). keep: a host keep plane into the object's plane (keep=True or a tensor at
+        construction)."""
         from .types import TWO_VIEW_DTYPE
         d_m, d_mask, d_pts, d_tv = self._own_inputs()
         m = np.ascontiguousarray(matches, dtype=DMATCH_DTYPE)
@@ -1312,9 +1320,16 @@ class SfmRegister:
             d_pts[:self.total_m * 3].copy_(torch.from_numpy(pts[:self.total_m].reshape(-1)))
         if self.n_pairs:
             d_tv[:self.n_pairs * self._tv_bytes].copy_(torch.from_numpy(tv.view(np.uint8).reshape(-1)))
+        if keep is not None:
+            kp = np.ascontiguousarray(keep, dtype=np.uint8)
+            if self.d_keep is None or len(kp) < self.total_m:
+                raise ValueError("load: a keep plane needs keep=True (or a tensor) at construction, and one byte per match slot")
+            if self.total_m:
+                self.d_keep[:self.total_m].copy_(torch.from_numpy(kp[:self.total_m]))
 
     def run(self, d_matches=None, d_mask=None, d_points3d=None, d_tv=None):
-        """gms_sfm_register_device, stream-ordered on the context's stream; no allocation, no synchronisation, no readback."""
+        """gms_sfm_register_device (with a keep plane: gms_sfm_register_keep_device), stream-ordered on the context's stream; no
+        allocation, no synchronisation, no readback."""
         given = (d_matches, d_mask, d_points3d, d_tv)
         if any(t is None for t in given):
             if not all(t is None for t in given):
@@ -1326,7 +1341,8 @@ class SfmRegister:
                                      d_tv.data_ptr(), self.root, self.min_links, self.d_ws.data_ptr(), self.ws_bytes, self.d_views.data_ptr(),
                                      self.d_reg.data_ptr(), self.d_world.data_ptr(), self.d_track.data_ptr(), self.cloud_cap,
                                      self.d_cloud.data_ptr(), self.d_cloud_id.data_ptr(), self.d_cloud_obs.data_ptr(),
-                                     self.d_cloud_est.data_ptr(), self.d_cloud_spread.data_ptr(), self.d_summary.data_ptr())
+                                     self.d_cloud_est.data_ptr(), self.d_cloud_spread.data_ptr(), self.d_summary.data_ptr(),
+                                     None if self.d_keep is None else self.d_keep.data_ptr())
 
     def results(self, trim=True):
         """Waits for the context's stream -> dict(plan, views, registration, points_world, track, cloud, cloud_id, cloud_obs, cloud_est,
@@ -1342,6 +1358,89 @@ class SfmRegister:
                    cloud_obs=self.d_cloud_obs.cpu().numpy()[:cap].copy(), cloud_est=self.d_cloud_est.cpu().numpy()[:cap].copy(),
                    cloud_spread=self.d_cloud_spread.cpu().numpy()[:cap].copy(), summary=self.d_summary.cpu().numpy().view(SFM_SUMMARY_DTYPE).copy())
         return sfm_trim(out) if trim else out
+
+
+class MatchUnique:
+    """Device buffers of one gms_match_unique_device call over a fixed pair list (one-to-one matches per pair): the
+    frame offsets, the pair table, the workspace, the keep plane d_keep (uint8 per match slot) and d_counts (int32 live, kept per
+    pair), sized once, so that run() can be repeated or captured into a graph. The inputs -- matches, and optionally the mask and the
+    two-view records as gms_two_view_batch_device leaves them -- are the caller's device tensors, handed to run(), or the object's
+    own (load() copies host arrays into them; run() without arguments reads them). Any pair list: no plan is made. total_m: the match
+    arrays' length, where it is more than the pairs' ranges need (the plane then has that many bytes)."""
+
+    def __init__(self, ctx, frame_off, pairs, device=None, d_frame_off=None, d_pairs=None, total_m=None):
+        from .types import TWO_VIEW_DTYPE
+        self.ctx = ctx
+        self.frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
+        self.recs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
+        self.n_frames, self.n_pairs, self.total_kp = len(self.frame_off) - 1, len(self.recs), int(self.frame_off[-1])
+        n = self.n_pairs
+        self.total_m = int((self.recs["match_off"] + np.maximum(self.recs["m"], 0)).max()) if n else 0
+        self.total_m = max(self.total_m, 0 if total_m is None else int(total_m))
+        self.max_m = int(self.recs["m"].max()) if n else 0
+        self.ws_bytes = ctx.match_unique_workspace_bytes(n, self.total_kp, self.total_m) if self.n_frames >= 1 else 0
+        if self.ws_bytes == 0:
+            raise ValueError("MatchUnique: sizes rejected (include/gms.h)")
+        dev = _device(ctx, device)
+        self.device = dev
+        self.d_frame_off = d_frame_off if d_frame_off is not None else torch.from_numpy(self.frame_off).to(dev)
+        self.d_pairs = d_pairs if d_pairs is not None else (_to_dev(self.recs, dev) if n else torch.zeros(24, dtype=torch.uint8, device=dev))
+        self.d_ws = torch.zeros(self.ws_bytes, dtype=torch.uint8, device=dev)
+        self.d_keep = torch.zeros(max(self.total_m, 1), dtype=torch.uint8, device=dev)
+        self.d_counts = torch.zeros(2 * max(n, 1), dtype=torch.int32, device=dev)
+        self._own = None
+        self._own_mask = self._own_tv = False
+        self._tv_bytes = TWO_VIEW_DTYPE.itemsize
+        torch.cuda.synchronize(dev)
+
+    def load(self, matches, mask=None, two_view=None):
+        """Host arrays into the object's own input tensors (same tensors every time: a captured run() reads what the latest load()
+        left). Whether a mask and two-view records take part is fixed by the first load()."""
+        from .types import TWO_VIEW_DTYPE
+        m = np.ascontiguousarray(matches, dtype=DMATCH_DTYPE)
+        if self._own is None:
+            mm, n, dev = max(self.total_m, 1), max(self.n_pairs, 1), self.device
+            self._own = (torch.zeros(mm * 16, dtype=torch.uint8, device=dev), torch.zeros(mm, dtype=torch.uint8, device=dev),
+                         torch.zeros(n * self._tv_bytes, dtype=torch.uint8, device=dev))
+            self._own_mask, self._own_tv = mask is not None, two_view is not None
+        if (mask is not None) != self._own_mask or (two_view is not None) != self._own_tv:
+            raise ValueError("load: with a mask / two-view records every time, or never")
+        if len(m) < self.total_m or (mask is not None and len(mask) < self.total_m) or (two_view is not None and len(two_view) != self.n_pairs):
+            raise ValueError("matches and mask cover every pair's match range; one two_view record per pair")
+        d_m, d_mask, d_tv = self._own
+        if self.total_m:
+            d_m[:self.total_m * 16].copy_(torch.from_numpy(m[:self.total_m].view(np.uint8).reshape(-1)))
+            if mask is not None:
+                d_mask[:self.total_m].copy_(torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8)[:self.total_m]))
+        if self.n_pairs and two_view is not None:
+            d_tv[:self.n_pairs * self._tv_bytes].copy_(torch.from_numpy(np.ascontiguousarray(two_view, dtype=TWO_VIEW_DTYPE).view(np.uint8).reshape(-1)))
+
+    def run(self, d_matches=None, d_mask=None, d_tv=None):
+        """gms_match_unique_device, stream-ordered on the context's stream; no allocation, no synchronisation, no readback. d_matches
+        None: the object's own inputs."""
+        if d_matches is None:
+            if self._own is None or d_mask is not None or d_tv is not None:
+                raise ValueError("run: the caller's tensors, or none after a load() (the object's own)")
+            d_matches, d_mask, d_tv = self._own[0], self._own[1] if self._own_mask else None, self._own[2] if self._own_tv else None
+        self.ctx.match_unique_device(self.d_frame_off.data_ptr(), self.n_frames, self.total_kp, self.d_pairs.data_ptr(), self.n_pairs, self.max_m,
+                                     self.total_m, d_matches.data_ptr(), None if d_mask is None else d_mask.data_ptr(),
+                                     None if d_tv is None else d_tv.data_ptr(), self.d_ws.data_ptr(), self.ws_bytes, self.d_keep.data_ptr(),
+                                     self.d_counts.data_ptr())
+
+    def results(self):
+        """Waits for the context's stream -> (keep uint8 [total_m], counts int32 [n_pairs, 2] = live, kept) on the host."""
+        self.ctx.synchronize()
+        return self.d_keep.cpu().numpy()[:self.total_m].copy(), self.d_counts.cpu().numpy().reshape(-1, 2)[:self.n_pairs].copy()
+
+
+def unique_matches(ctx, frame_off, pairs, matches, mask=None, two_view=None, device=None):
+    """The convenience call: host arrays of many pairs' matches (and optionally the two-view stage's mask and records) ->
+    MatchUnique.results() after one gms_match_unique_device run."""
+    job = MatchUnique(ctx, frame_off, pairs, device)
+    job.load(matches, mask, two_view)
+    torch.cuda.synchronize(job.device)
+    job.run()
+    return job.results()
 
 
 class SfmBundle:
@@ -1550,11 +1649,12 @@ def bundle_adjust(ctx, keypoints, frame_off, pairs, matches, mask, registration,
     return job.results()
 
 
-def register_pairs(ctx, frame_off, pairs, matches, mask, points3d, two_view, root=0, min_links=8, cloud_cap=None, device=None):
+def register_pairs(ctx, frame_off, pairs, matches, mask, points3d, two_view, root=0, min_links=8, cloud_cap=None, device=None, keep=None):
     """The convenience call: host arrays of many pairs' two-view results (run_dataset's pairs, out, mask, points3d, two_view and the
-    frames' offsets) -> SfmRegister.results() after one gms_sfm_register_device run."""
-    job = SfmRegister(ctx, frame_off, pairs, root, min_links, cloud_cap, device)
-    job.load(matches, mask, points3d, two_view)
+    frames' offsets) -> SfmRegister.results() after one gms_sfm_register_device run. keep: a host keep plane (unique_matches') -> one
+    gms_sfm_register_keep_device run on it."""
+    job = SfmRegister(ctx, frame_off, pairs, root, min_links, cloud_cap, device, keep=None if keep is None else True)
+    job.load(matches, mask, points3d, two_view, keep)
     torch.cuda.synchronize(job.device)
     job.run()
     return job.results()

@@ -41,6 +41,12 @@ SIGNATURES = {
     "gms_sfm_register_device": (i32, [vp, vp, i32, i64, vp, vp, i32, i32, i64, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp, vp, vp, i64, vp, vp, vp,
                                       vp, vp, vp]),
     "gms_sfm_register": (i32, [vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]),
+    "gms_match_unique_workspace_bytes": (sz, [i32, i64, i64]),
+    "gms_match_unique_device": (i32, [vp, vp, i32, i64, vp, i32, i32, i64, vp, vp, vp, vp, sz, vp, vp]),
+    "gms_match_unique": (i32, [vp, i32, vp, i32, vp, vp, vp, vp, vp]),
+    "gms_sfm_register_keep_device": (i32, [vp, vp, i32, i64, vp, vp, i32, i32, i64, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp, vp, vp, i64, vp, vp,
+                                           vp, vp, vp, vp, vp]),
+    "gms_sfm_register_keep": (i32, [vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
     "gms_sfm_ba_workspace_bytes": (sz, [i32, i32, i64, i64]),
     "gms_sfm_ba_device": (i32, [vp, vp, vp, vp, vp, i32, i64, vp, i32, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, sz, vp, vp, vp, vp]),
     "gms_sfm_ba": (i32, [vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp]),

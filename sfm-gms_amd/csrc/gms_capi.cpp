@@ -2246,12 +2246,12 @@ size_t gms_sfm_register_workspace_bytes(int n_frames, int n_pairs, int64_t total
     return gms::sfm_register_ws_bytes(n_pairs, total_kp, total_matches);
 }
 
-int gms_sfm_register_device(gms_ctx* c, const int64_t* d_frame_off, int n_frames, int64_t total_kp, const gms_pair* d_pairs,
+int gms_sfm_register_keep_device(gms_ctx* c, const int64_t* d_frame_off, int n_frames, int64_t total_kp, const gms_pair* d_pairs,
                             const gms_sfm_plan_entry* d_plan, int n_pairs, int max_m, int64_t total_matches, const gms_dmatch* d_filtered,
                             const uint8_t* d_mask, const double* d_points3d, const gms_two_view* d_tv, int root, int min_links, void* d_ws,
                             size_t ws_bytes, gms_sfm_view* d_views, gms_sfm_pair_reg* d_reg, double* d_points_world, int32_t* d_track,
                             int64_t cloud_cap, double* d_cloud, int32_t* d_cloud_id, int32_t* d_cloud_obs, int32_t* d_cloud_est,
-                            double* d_cloud_spread, gms_sfm_summary* d_summary)
+                            double* d_cloud_spread, gms_sfm_summary* d_summary, const uint8_t* d_keep)
 {
     if (!c || !sfm_register_sizes_ok(n_frames, n_pairs, total_kp, total_matches) || max_m < 0 || max_m >= (1 << 24)) return GMS_ERR_BAD_ARG;
     if (root < 0 || root >= n_frames || min_links < 1 || cloud_cap < 0) return GMS_ERR_BAD_ARG;
@@ -2263,14 +2263,14 @@ int gms_sfm_register_device(gms_ctx* c, const int64_t* d_frame_off, int n_frames
     return on_ctx(c, [&] {
         return gms::launch_sfm_register(d_frame_off, n_frames, total_kp, d_pairs, d_plan, n_pairs, max_m, total_matches, d_filtered, d_mask,
                                         d_points3d, d_tv, root, min_links, d_ws, d_views, d_reg, d_points_world, d_track, cloud_cap, d_cloud,
-                                        d_cloud_id, d_cloud_obs, d_cloud_est, d_cloud_spread, d_summary, c->stream);
+                                        d_cloud_id, d_cloud_obs, d_cloud_est, d_cloud_spread, d_summary, c->stream, d_keep);
     });
 }
 
-int gms_sfm_register(const int64_t* frame_off, int n_frames, const gms_pair* pairs, int n_pairs, const gms_dmatch* filtered,
+int gms_sfm_register_keep(const int64_t* frame_off, int n_frames, const gms_pair* pairs, int n_pairs, const gms_dmatch* filtered,
                      const uint8_t* mask, const double* points3d, const gms_two_view* tv, int root, int min_links, gms_sfm_view* views,
                      gms_sfm_pair_reg* reg, double* points_world, int32_t* track, int64_t cloud_cap, double* cloud, int32_t* cloud_id,
-                     int32_t* cloud_obs, int32_t* cloud_est, double* cloud_spread, gms_sfm_summary* summary)
+                     int32_t* cloud_obs, int32_t* cloud_est, double* cloud_spread, gms_sfm_summary* summary, const uint8_t* keep)
 {
     if (n_frames < 1 || n_pairs < 0 || !frame_off || !views || !summary || root < 0 || root >= n_frames || min_links < 1 || cloud_cap < 0)
         return GMS_ERR_BAD_ARG;
@@ -2294,7 +2294,7 @@ int gms_sfm_register(const int64_t* frame_off, int n_frames, const gms_pair* pai
     gms::BlockLayout lay;
     const size_t o_off = lay.add(8 * ((size_t)n_frames + 1)), o_pairs = lay.add(sizeof(gms_pair) * P), o_plan = lay.add(sizeof(gms_sfm_plan_entry) * P);
     const size_t o_m = lay.add(sizeof(gms_dmatch) * M), o_mask = lay.add(M), o_pts = lay.add(24 * M), o_tv = lay.add(sizeof(gms_two_view) * P);
-    const size_t o_ws = lay.add(gms::sfm_register_ws_bytes(n_pairs, total_kp, total_m));
+    const size_t o_ws = lay.add(gms::sfm_register_ws_bytes(n_pairs, total_kp, total_m)), o_keep = lay.add(keep ? M : 0);
     // the outputs, back to back: cleared as one span
     const size_t o_views = lay.add(sizeof(gms_sfm_view) * (size_t)n_frames), o_reg = lay.add(sizeof(gms_sfm_pair_reg) * P), o_world = lay.add(24 * M);
     const size_t o_track = lay.add(4 * M), o_cloud = lay.add(24 * Cc), o_id = lay.add(4 * Cc), o_obs = lay.add(4 * Cc), o_est = lay.add(4 * Cc);
@@ -2310,6 +2310,7 @@ int gms_sfm_register(const int64_t* frame_off, int n_frames, const gms_pair* pai
         blk.in(o_m, filtered, sizeof(gms_dmatch) * M);
         blk.in(o_mask, mask, M);
         blk.in(o_pts, points3d, 24 * M);
+        if (keep) blk.in(o_keep, keep, M);
     }
     blk.run([&](hipStream_t st) { return hipMemsetAsync(blk.at(o_views), 0, lay.total() - o_views, st); });
     blk.run([&](hipStream_t st) {
@@ -2318,7 +2319,7 @@ int gms_sfm_register(const int64_t* frame_off, int n_frames, const gms_pair* pai
                                         blk.at<gms_two_view>(o_tv), root, min_links, blk.at(o_ws), blk.at<gms_sfm_view>(o_views),
                                         blk.at<gms_sfm_pair_reg>(o_reg), blk.at<double>(o_world), blk.at<int32_t>(o_track), cloud_cap,
                                         blk.at<double>(o_cloud), blk.at<int32_t>(o_id), blk.at<int32_t>(o_obs), blk.at<int32_t>(o_est),
-                                        blk.at<double>(o_spread), blk.at<gms_sfm_summary>(o_sum), st);
+                                        blk.at<double>(o_spread), blk.at<gms_sfm_summary>(o_sum), st, keep && M ? blk.at<uint8_t>(o_keep) : nullptr);
     });
     blk.out(views, o_views, sizeof(gms_sfm_view) * (size_t)n_frames);
     if (P) blk.out(reg, o_reg, sizeof(gms_sfm_pair_reg) * P);
@@ -2334,6 +2335,95 @@ int gms_sfm_register(const int64_t* frame_off, int n_frames, const gms_pair* pai
         blk.out(cloud_spread, o_spread, 8 * Cc);
     }
     blk.out(summary, o_sum, sizeof(gms_sfm_summary));
+    return blk.finish();
+}
+
+// the calls without a keep plane: the same launches with a null plane
+int gms_sfm_register_device(gms_ctx* c, const int64_t* d_frame_off, int n_frames, int64_t total_kp, const gms_pair* d_pairs,
+                            const gms_sfm_plan_entry* d_plan, int n_pairs, int max_m, int64_t total_matches, const gms_dmatch* d_filtered,
+                            const uint8_t* d_mask, const double* d_points3d, const gms_two_view* d_tv, int root, int min_links, void* d_ws,
+                            size_t ws_bytes, gms_sfm_view* d_views, gms_sfm_pair_reg* d_reg, double* d_points_world, int32_t* d_track,
+                            int64_t cloud_cap, double* d_cloud, int32_t* d_cloud_id, int32_t* d_cloud_obs, int32_t* d_cloud_est,
+                            double* d_cloud_spread, gms_sfm_summary* d_summary)
+{
+    return gms_sfm_register_keep_device(c, d_frame_off, n_frames, total_kp, d_pairs, d_plan, n_pairs, max_m, total_matches, d_filtered, d_mask,
+                                        d_points3d, d_tv, root, min_links, d_ws, ws_bytes, d_views, d_reg, d_points_world, d_track, cloud_cap,
+                                        d_cloud, d_cloud_id, d_cloud_obs, d_cloud_est, d_cloud_spread, d_summary, nullptr);
+}
+
+int gms_sfm_register(const int64_t* frame_off, int n_frames, const gms_pair* pairs, int n_pairs, const gms_dmatch* filtered,
+                     const uint8_t* mask, const double* points3d, const gms_two_view* tv, int root, int min_links, gms_sfm_view* views,
+                     gms_sfm_pair_reg* reg, double* points_world, int32_t* track, int64_t cloud_cap, double* cloud, int32_t* cloud_id,
+                     int32_t* cloud_obs, int32_t* cloud_est, double* cloud_spread, gms_sfm_summary* summary)
+{
+    return gms_sfm_register_keep(frame_off, n_frames, pairs, n_pairs, filtered, mask, points3d, tv, root, min_links, views, reg, points_world,
+                                 track, cloud_cap, cloud, cloud_id, cloud_obs, cloud_est, cloud_spread, summary, nullptr);
+}
+
+// ---- one-to-one matches per pair (match_unique_kernels.hip; the rule is match_unique_core.h) ----------------------------------------
+size_t gms_match_unique_workspace_bytes(int n_pairs, int64_t total_kp, int64_t total_matches)
+{
+    if (!sfm_register_sizes_ok(1, n_pairs, total_kp, total_matches)) return 0;
+    return gms::match_unique_ws_bytes(total_matches);
+}
+
+int gms_match_unique_device(gms_ctx* c, const int64_t* d_frame_off, int n_frames, int64_t total_kp, const gms_pair* d_pairs, int n_pairs,
+                            int max_m, int64_t total_matches, const gms_dmatch* d_filtered, const uint8_t* d_mask, const gms_two_view* d_tv,
+                            void* d_ws, size_t ws_bytes, uint8_t* d_keep, int32_t* d_counts)
+{
+    if (!c || !sfm_register_sizes_ok(n_frames, n_pairs, total_kp, total_matches) || max_m < 0 || max_m >= (1 << 24)) return GMS_ERR_BAD_ARG;
+    if (!d_frame_off || !d_ws) return GMS_ERR_BAD_ARG;
+    if (n_pairs > 0 && (!d_pairs || !d_counts)) return GMS_ERR_BAD_ARG;
+    if (total_matches > 0 && (!d_filtered || !d_keep)) return GMS_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_ws) & 255u) || ws_bytes < gms::match_unique_ws_bytes(total_matches)) return GMS_ERR_BAD_ARG;
+    return on_ctx(c, [&] {
+        return gms::launch_match_unique(d_frame_off, n_frames, total_kp, d_pairs, n_pairs, max_m, total_matches, d_filtered, d_mask, d_tv, d_ws,
+                                        d_keep, d_counts, c->stream);
+    });
+}
+
+int gms_match_unique(const int64_t* frame_off, int n_frames, const gms_pair* pairs, int n_pairs, const gms_dmatch* filtered,
+                     const uint8_t* mask, const gms_two_view* tv, uint8_t* keep, int32_t* counts)
+{
+    if (n_frames < 1 || n_pairs < 0 || !frame_off) return GMS_ERR_BAD_ARG;
+    if (n_pairs > 0 && (!pairs || !counts)) return GMS_ERR_BAD_ARG;
+    for (int f = 0; f < n_frames; f++)
+        if (frame_off[f] < 0 || frame_off[f + 1] < frame_off[f]) return GMS_ERR_BAD_ARG;
+    int64_t total_m = 0;
+    int max_m = 0;
+    for (int p = 0; p < n_pairs; p++) {
+        if (pairs[p].frame_a < 0 || pairs[p].frame_a >= n_frames || pairs[p].frame_b < 0 || pairs[p].frame_b >= n_frames) return GMS_ERR_BAD_ARG;
+        if (!sfm_match_range_ok(pairs[p])) return GMS_ERR_BAD_ARG;
+        total_m = std::max(total_m, pairs[p].match_off + (int64_t)pairs[p].m);
+        max_m = std::max(max_m, pairs[p].m);
+    }
+    const int64_t total_kp = frame_off[n_frames];
+    if (!sfm_register_sizes_ok(n_frames, n_pairs, total_kp, total_m) || max_m >= (1 << 24)) return GMS_ERR_BAD_ARG;
+    if (total_m > 0 && (!filtered || !keep)) return GMS_ERR_BAD_ARG;
+    const size_t M = (size_t)total_m, P = (size_t)n_pairs;
+    gms::BlockLayout lay;
+    const size_t o_off = lay.add(8 * ((size_t)n_frames + 1)), o_pairs = lay.add(sizeof(gms_pair) * P), o_m = lay.add(sizeof(gms_dmatch) * M);
+    const size_t o_mask = lay.add(mask ? M : 0), o_tv = lay.add(tv ? sizeof(gms_two_view) * P : 0), o_ws = lay.add(gms::match_unique_ws_bytes(total_m));
+    const size_t o_keep = lay.add(M), o_counts = lay.add(8 * P);  // the outputs, back to back: cleared as one span
+    DevBlock blk(lay, nullptr);
+    blk.in(o_off, frame_off, 8 * ((size_t)n_frames + 1));
+    if (P) {
+        blk.in(o_pairs, pairs, sizeof(gms_pair) * P);
+        if (tv) blk.in(o_tv, tv, sizeof(gms_two_view) * P);
+    }
+    if (M) {
+        blk.in(o_m, filtered, sizeof(gms_dmatch) * M);
+        if (mask) blk.in(o_mask, mask, M);
+    }
+    if (lay.total() > o_keep) blk.run([&](hipStream_t st) { return hipMemsetAsync(blk.at(o_keep), 0, lay.total() - o_keep, st); });
+    blk.run([&](hipStream_t st) {
+        return gms::launch_match_unique(blk.at<int64_t>(o_off), n_frames, total_kp, blk.at<gms_pair>(o_pairs), n_pairs, max_m, total_m,
+                                        blk.at<gms_dmatch>(o_m), mask && M ? blk.at<uint8_t>(o_mask) : nullptr,
+                                        tv && P ? blk.at<gms_two_view>(o_tv) : nullptr, blk.at(o_ws), blk.at<uint8_t>(o_keep),
+                                        blk.at<int32_t>(o_counts), st);
+    });
+    if (M) blk.out(keep, o_keep, M);
+    if (P) blk.out(counts, o_counts, 8 * P);
     return blk.finish();
 }
 

@@ -232,7 +232,12 @@ hipError_t launch_sfm_register(const int64_t* d_frame_off, int n_frames, int64_t
                                const uint8_t* d_mask, const double* d_points3d, const gms_two_view* d_tv, int root, int min_links,
                                void* d_ws, gms_sfm_view* d_views, gms_sfm_pair_reg* d_reg, double* d_world, int32_t* d_track,
                                int64_t cloud_cap, double* d_cloud, int32_t* d_cloud_id, int32_t* d_cloud_obs, int32_t* d_cloud_est,
-                               double* d_cloud_spread, gms_sfm_summary* d_summary, hipStream_t stream);
+                               double* d_cloud_spread, gms_sfm_summary* d_summary, hipStream_t stream, const uint8_t* d_keep = nullptr);
+// one-to-one matches per pair (match_unique_kernels.hip; the rule is match_unique_core.h); d_mask, d_tv: null for every slot live
+size_t     match_unique_ws_bytes(int64_t total_m);
+hipError_t launch_match_unique(const int64_t* d_frame_off, int n_frames, int64_t total_kp, const gms_pair* d_pairs, int n_pairs, int max_m,
+                               int64_t total_m, const gms_dmatch* d_filtered, const uint8_t* d_mask, const gms_two_view* d_tv, void* d_ws,
+                               uint8_t* d_keep, int32_t* d_counts, hipStream_t stream);
 // bundle adjustment behind the registration (sfm_ba_kernels.hip; shared arithmetic in sfm_ba_core.h)
 size_t     sfm_ba_ws_bytes(int n_frames, int64_t total_kp, int64_t cloud_cap);
 hipError_t launch_sfm_ba(const gms_camera& camera, const gms_sfm_ba_params& prm, const gms_keypoint* d_kp, const int64_t* d_frame_off,

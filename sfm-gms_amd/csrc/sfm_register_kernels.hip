@@ -13,6 +13,7 @@
 //   sfr_world_kernel     W = G_a.R^T (S p - G_a.t)
 //   sfr_merge_kernel / sfr_flatten_kernel   union-find over the global keypoints with atomicMin on the roots (as portrait mode's), then
 //                        per root its keypoints, and through a table of (root, frame) keys whether two of them share a frame
+//   (merge, estimate and spread take an optional keep plane, DESIGN.md §4.10e: a match whose byte is 0 is no edge and no estimate)
 //   sfr_estimate_kernel  per point its track; per root the least (pair, rank) key (64-bit atomicMin) and the estimates
 //   sfr_spread_kernel    per root the largest distance to the representative (atomicMax on the bit pattern)
 //   sfr_tile_kernel / sfr_scan_kernel / sfr_cloud_kernel   the roots compacted in ascending order by a prefix sum over the keypoints
@@ -85,6 +86,9 @@ __device__ __forceinline__ bool kept(const SfrIn& in, const PairInfo& p, int k, 
     m = in.matches[p.off + k];
     return (uint32_t)m.queryIdx < (uint32_t)p.na && (uint32_t)m.trainIdx < (uint32_t)p.nb;
 }
+
+// with a keep plane, whether match k of the pair feeds the tracks; the links and the points do not ask
+__device__ __forceinline__ bool on_plane(const uint8_t* keep, const PairInfo& p, int k) { return !keep || keep[p.off + k] != 0; }
 
 __device__ __forceinline__ int uf_find(const int32_t* L, int a)
 {
@@ -386,14 +390,14 @@ sfr_world_kernel(SfrIn in, SfrWs ws, const gms_sfm_view* __restrict__ views, con
 }
 
 __global__ void __launch_bounds__(kB)
-sfr_merge_kernel(SfrIn in, SfrWs ws)
+sfr_merge_kernel(SfrIn in, SfrWs ws, const uint8_t* __restrict__ keep)
 {
     const int i = (int)blockIdx.x;
     if (!ws.ok[i]) return;
     const PairInfo p = pair_info(in, i);
     const int k = (int)(blockIdx.y * kB + threadIdx.x);
     gms_dmatch m;
-    if (!kept(in, p, k, m)) return;
+    if (!kept(in, p, k, m) || !on_plane(keep, p, k)) return;
     const int u = (int)(p.oa + m.queryIdx), v = (int)(p.ob + m.trainIdx);
     ws.member[u] = 1;  // (benign races: every writer stores 1)
     ws.member[v] = 1;
@@ -429,14 +433,14 @@ sfr_flatten_kernel(SfrIn in, SfrWs ws)
 }
 
 __global__ void __launch_bounds__(kB)
-sfr_estimate_kernel(SfrIn in, SfrWs ws, int32_t* __restrict__ track)
+sfr_estimate_kernel(SfrIn in, SfrWs ws, const uint8_t* __restrict__ keep, int32_t* __restrict__ track)
 {
     const int i = (int)blockIdx.x;
     if (!ws.ok[i]) return;
     const PairInfo p = pair_info(in, i);
     const int k = (int)(blockIdx.y * kB + threadIdx.x);
     gms_dmatch m;
-    if (!kept(in, p, k, m)) return;
+    if (!kept(in, p, k, m) || !on_plane(keep, p, k)) return;
     const int root = ws.parent[p.oa + m.queryIdx];
     const int rank = ws.rank[p.off + k];
     track[p.off + rank] = root;
@@ -450,14 +454,14 @@ __device__ __forceinline__ const double* rep_point(const SfrIn& in, const double
 }
 
 __global__ void __launch_bounds__(kB)
-sfr_spread_kernel(SfrIn in, SfrWs ws, const double* __restrict__ world)
+sfr_spread_kernel(SfrIn in, SfrWs ws, const uint8_t* __restrict__ keep, const double* __restrict__ world)
 {
     const int i = (int)blockIdx.x;
     if (!ws.ok[i]) return;
     const PairInfo p = pair_info(in, i);
     const int k = (int)(blockIdx.y * kB + threadIdx.x);
     gms_dmatch m;
-    if (!kept(in, p, k, m)) return;
+    if (!kept(in, p, k, m) || !on_plane(keep, p, k)) return;
     const int root = ws.parent[p.oa + m.queryIdx];
     const double* w = world + 3 * (p.off + ws.rank[p.off + k]);
     const double* c = rep_point(in, world, ws.repkey[root]);
@@ -566,7 +570,7 @@ hipError_t launch_sfm_register(const int64_t* d_frame_off, int n_frames, int64_t
                                const uint8_t* d_mask, const double* d_points3d, const gms_two_view* d_tv, int root, int min_links,
                                void* d_ws, gms_sfm_view* d_views, gms_sfm_pair_reg* d_reg, double* d_world, int32_t* d_track,
                                int64_t cloud_cap, double* d_cloud, int32_t* d_cloud_id, int32_t* d_cloud_obs, int32_t* d_cloud_est,
-                               double* d_cloud_spread, gms_sfm_summary* d_summary, hipStream_t stream)
+                               double* d_cloud_spread, gms_sfm_summary* d_summary, hipStream_t stream, const uint8_t* d_keep)
 {
     const SfmRegisterLayout L = sfm_register_layout(n_pairs, total_kp, total_m);
     const int64_t hash_slots = (int64_t)sfr_hash_slots((size_t)total_kp);
@@ -595,14 +599,14 @@ hipError_t launch_sfm_register(const int64_t* d_frame_off, int n_frames, int64_t
     SFR_STAGE(sfr_compose_kernel, dim3(1), dim3(kB), 0, stream, in, ws, min_links, d_views, d_reg, d_summary);
     if (work) {
         SFR_STAGE(sfr_world_kernel, per_match, dim3(kB), 0, stream, in, ws, d_views, d_reg, d_world);
-        SFR_STAGE(sfr_merge_kernel, per_match, dim3(kB), 0, stream, in, ws);
+        SFR_STAGE(sfr_merge_kernel, per_match, dim3(kB), 0, stream, in, ws, d_keep);
     }
     if (total_kp > 0) {
         const int n_tiles = (int)((total_kp + kSfrScanTile - 1) / kSfrScanTile);
         SFR_STAGE(sfr_flatten_kernel, dim3((uint32_t)((total_kp + kB - 1) / kB)), dim3(kB), 0, stream, in, ws);
         if (work) {
-            SFR_STAGE(sfr_estimate_kernel, per_match, dim3(kB), 0, stream, in, ws, d_track);
-            SFR_STAGE(sfr_spread_kernel, per_match, dim3(kB), 0, stream, in, ws, d_world);
+            SFR_STAGE(sfr_estimate_kernel, per_match, dim3(kB), 0, stream, in, ws, d_keep, d_track);
+            SFR_STAGE(sfr_spread_kernel, per_match, dim3(kB), 0, stream, in, ws, d_keep, d_world);
         }
         SFR_STAGE(sfr_tile_kernel, dim3((uint32_t)n_tiles), dim3(kB), 0, stream, ws, total_kp);
         SFR_STAGE(sfr_scan_kernel, dim3(1), dim3(kB), 0, stream, ws, n_tiles, d_summary);

@@ -337,6 +337,23 @@ inline SfmRegisterLayout sfm_register_layout(int n_pairs, int64_t total_kp, int6
             c.take(4 * P, 256), c.end};
 }
 
+// ---- one-to-one matches per pair (match_unique_kernels.hip) --------------------------------------------------------------------------
+// M match slots. A pair of m slots at match_off owns slots [2 match_off, 2 match_off + 2 m) of each table: open addressing over the
+// keypoints its live matches name, at most m of them in 2 m slots, so a probe always meets an empty slot. A slot holds the least key
+// (match_unique_core.h) of one keypoint; which keypoint, the key's match says. 32 bytes per match slot, whatever the frames' sizes
+// and however often a frame appears in the pair list. Every call writes every word it later reads.
+struct MatchUniqueLayout {
+    size_t by_query;  // uint64 [2 M]
+    size_t by_train;  // uint64 [2 M]
+    size_t total;
+};
+inline MatchUniqueLayout match_unique_layout(int64_t total_matches)
+{
+    const size_t M = (size_t)total_matches;
+    WsCursor c;
+    return {c.take(16 * M, 256), c.take(16 * M, 256), c.take(0) + (M == 0 ? 256 : 0)};
+}
+
 // ---- bundle adjustment behind the registration (sfm_ba_kernels.hip) -----------------------------------------------------------------
 // K global keypoints, C cloud entries, F frames. Everything an observation owns sits at its keypoint's index: a keypoint is an
 // observation of at most one track, so no compaction is needed and the observations of a frame are a range. Every call writes every

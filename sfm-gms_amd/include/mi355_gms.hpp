@@ -446,15 +446,18 @@ struct Registration {
     gms_sfm_summary summary;
 };
 
-inline Registration registerViews(const std::vector<int64_t>& frame_off, const std::vector<gms_pair>& pairs, const std::vector<gms_dmatch>& matches,
-                                  const std::vector<uint8_t>& mask, const std::vector<double>& points3d, const std::vector<gms_two_view>& two_view,
-                                  int root = 0, int min_links = 8)
+namespace detail {
+// registerViews with (gms_sfm_register_keep) or without (gms_sfm_register) a keep plane
+inline Registration register_views(const std::vector<int64_t>& frame_off, const std::vector<gms_pair>& pairs, const std::vector<gms_dmatch>& matches,
+                                   const std::vector<uint8_t>& mask, const std::vector<double>& points3d, const std::vector<gms_two_view>& two_view,
+                                   const std::vector<uint8_t>* keep, int root, int min_links)
 {
     size_t total = 0;
     for (const gms_pair& p : pairs)
         if (p.m > 0 && p.match_off >= 0) total = std::max(total, (size_t)p.match_off + (size_t)p.m);
     if (frame_off.size() < 2 || two_view.size() != pairs.size() || matches.size() < total || mask.size() < total || points3d.size() < 3 * total)
         throw std::invalid_argument("mi355::registerViews: offsets of at least one frame, one two-view record per pair, arrays that cover every pair's match range");
+    if (keep && keep->size() < total) throw std::invalid_argument("mi355::registerViews: a keep plane that covers every pair's match range");
     const int n_frames = (int)frame_off.size() - 1;
     const size_t cap = frame_off.back() > 0 ? (size_t)frame_off.back() / 2 : 0;
     Registration r;
@@ -467,10 +470,14 @@ inline Registration registerViews(const std::vector<int64_t>& frame_off, const s
     r.cloud_id.assign(cap, 0);
     r.cloud_obs.assign(cap, 0);
     r.cloud_est.assign(cap, 0);
-    const int rc = gms_sfm_register(frame_off.data(), n_frames, pairs.data(), (int)pairs.size(), matches.data(), mask.data(), points3d.data(),
-                                    two_view.data(), root, min_links, r.views.data(), r.pairs.data(), r.points_world.data(), r.track.data(),
-                                    (int64_t)cap, r.cloud.data(), r.cloud_id.data(), r.cloud_obs.data(), r.cloud_est.data(),
-                                    r.cloud_spread.data(), &r.summary);
+    const int rc = keep ? gms_sfm_register_keep(frame_off.data(), n_frames, pairs.data(), (int)pairs.size(), matches.data(), mask.data(),
+                                                points3d.data(), two_view.data(), root, min_links, r.views.data(), r.pairs.data(),
+                                                r.points_world.data(), r.track.data(), (int64_t)cap, r.cloud.data(), r.cloud_id.data(),
+                                                r.cloud_obs.data(), r.cloud_est.data(), r.cloud_spread.data(), &r.summary, keep->data())
+                        : gms_sfm_register(frame_off.data(), n_frames, pairs.data(), (int)pairs.size(), matches.data(), mask.data(), points3d.data(),
+                                           two_view.data(), root, min_links, r.views.data(), r.pairs.data(), r.points_world.data(), r.track.data(),
+                                           (int64_t)cap, r.cloud.data(), r.cloud_id.data(), r.cloud_obs.data(), r.cloud_est.data(),
+                                           r.cloud_spread.data(), &r.summary);
     if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::registerViews: ") + gms_error_string(rc));
     const size_t n = std::min(cap, (size_t)r.summary.n_tracks);
     r.cloud.resize(3 * n);
@@ -479,6 +486,45 @@ inline Registration registerViews(const std::vector<int64_t>& frame_off, const s
     r.cloud_obs.resize(n);
     r.cloud_est.resize(n);
     return r;
+}
+}  // namespace detail
+
+inline Registration registerViews(const std::vector<int64_t>& frame_off, const std::vector<gms_pair>& pairs, const std::vector<gms_dmatch>& matches,
+                                  const std::vector<uint8_t>& mask, const std::vector<double>& points3d, const std::vector<gms_two_view>& two_view,
+                                  int root = 0, int min_links = 8)
+{
+    return detail::register_views(frame_off, pairs, matches, mask, points3d, two_view, nullptr, root, min_links);
+}
+
+// One-to-one matches per pair (include/gms.h): per match slot one byte, 1 where the match is live (inside the pair's
+// count, a non-zero mask byte, both indices inside their frames) and the best of the live matches on its train keypoint and of those
+// on its query keypoint (distance, then position). mask and two_view may be empty: then every slot below a pair's m is live. counts,
+// when given, gets {live, kept} per pair. Runs synchronously on the current HIP device (gms_match_unique). Not a maximum matching.
+inline std::vector<uint8_t> uniqueMatches(const std::vector<int64_t>& frame_off, const std::vector<gms_pair>& pairs,
+                                          const std::vector<gms_dmatch>& matches, const std::vector<uint8_t>& mask = {},
+                                          const std::vector<gms_two_view>& two_view = {}, std::vector<int32_t>* counts = nullptr)
+{
+    size_t total = 0;
+    for (const gms_pair& p : pairs)
+        if (p.m > 0 && p.match_off >= 0) total = std::max(total, (size_t)p.match_off + (size_t)p.m);
+    if (frame_off.size() < 2 || matches.size() < total || (!mask.empty() && mask.size() < total) || (!two_view.empty() && two_view.size() != pairs.size()))
+        throw std::invalid_argument("mi355::uniqueMatches: offsets of at least one frame, arrays that cover every pair's match range, one two-view record per pair or none");
+    std::vector<uint8_t> keep(total, 0);
+    std::vector<int32_t> cnt(2 * pairs.size(), 0);
+    const int rc = gms_match_unique(frame_off.data(), (int)frame_off.size() - 1, pairs.data(), (int)pairs.size(), matches.data(),
+                                    mask.empty() ? nullptr : mask.data(), two_view.empty() ? nullptr : two_view.data(), keep.data(), cnt.data());
+    if (rc != GMS_OK) throw std::runtime_error(std::string("mi355::uniqueMatches: ") + gms_error_string(rc));
+    if (counts) *counts = cnt;
+    return keep;
+}
+
+// registerViews on a keep plane (uniqueMatches'): a match whose byte is 0 feeds no track; views, pairs and points_world are the bytes
+// of the call without the plane (gms_sfm_register_keep).
+inline Registration registerViews(const std::vector<int64_t>& frame_off, const std::vector<gms_pair>& pairs, const std::vector<gms_dmatch>& matches,
+                                  const std::vector<uint8_t>& mask, const std::vector<double>& points3d, const std::vector<gms_two_view>& two_view,
+                                  const std::vector<uint8_t>& keep, int root = 0, int min_links = 8)
+{
+    return detail::register_views(frame_off, pairs, matches, mask, points3d, two_view, &keep, root, min_links);
 }
 
 // Bundle adjustment behind registerViews (include/gms.h): refines the views and the cloud over all the keypoints a

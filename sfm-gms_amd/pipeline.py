@@ -24,7 +24,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from .batch import (BfSelect, DescriptorTable, DetectPyramid, FrameTable, LogosDictionary, LogosFilter, LogosTable, DensePairs, dense_fuse_sources, fuse_dense, SfmBundle, SfmRegister, Warp, _device, _to_dev,
+from .batch import (BfSelect, DescriptorTable, DetectPyramid, FrameTable, LogosDictionary, LogosFilter, LogosTable, DensePairs, dense_fuse_sources, fuse_dense, MatchUnique, SfmBundle, SfmRegister, Warp, _device, _to_dev,
                     bf_select_table, bgr_to_gray, frame_counts, frame_pairs_of, logos_dictionary, pair_table, tables_from_detector)
 from .api import getRotationMatrix2D, logos_dict_args
 from .types import (DMATCH_DTYPE, GMS_DESC_HAMMING256, GMS_DESC_L2_F32X128, GMS_ERR_CAPACITY, GMS_OK, PAIR_DTYPE, RESULT_DTYPE, TWO_VIEW_DTYPE,
@@ -38,7 +38,8 @@ def _two_view(ctx, frames, d_pairs, n_pairs, max_m, total_m, d_out, d_res, camer
     """gms_two_view_batch_device on the survivors d_out and their gms_pair_result records d_res, laid out by the pair table d_pairs ->
     the two-view part of run_dataset's result: two_view, coords1, coords2, mask, points3d as host arrays. reg = (root, min_links)
     (with `pairs`, the host copy of the pair table): gms_sfm_register_device then joins the pairs on the tensors the stage left, in
-    stream order behind it -> also SfmRegister.results()'s arrays (the plan as `register_plan`)."""
+    stream order behind it -> also SfmRegister.results()'s arrays (the plan as `register_plan`). reg[3] (unique): gms_match_unique_device
+    in between, the registration on its keep plane -> also `keep` and `unique_counts`."""
     dev = frames.device
     cam = make_camera(camera, dist)
     d_c1 = torch.zeros(max(total_m, 1) * 2, dtype=torch.float32, device=dev)
@@ -52,16 +53,24 @@ def _two_view(ctx, frames, d_pairs, n_pairs, max_m, total_m, d_out, d_res, camer
                               d_p3.data_ptr(), d_tv.data_ptr(), prob, ransac_threshold, max_iters)
     joined = {}
     if reg is not None:
-        job = SfmRegister(ctx, frames.frame_off_host, pairs, reg[0], reg[1], device=dev, d_frame_off=frames.d_frame_off, d_pairs=d_pairs)
+        uq = None
+        if reg[3]:   # one-to-one matches per pair in front, in stream order, on the tensors the two-view stage left
+            uq = MatchUnique(ctx, frames.frame_off_host, pairs, device=dev, d_frame_off=frames.d_frame_off, d_pairs=d_pairs)
+        job = SfmRegister(ctx, frames.frame_off_host, pairs, reg[0], reg[1], device=dev, d_frame_off=frames.d_frame_off, d_pairs=d_pairs,
+                          keep=None if uq is None else uq.d_keep)
         refine = None
         if reg[2] is not None:   # bundle adjustment behind it, in stream order, on the registration's own tensors
             refine = SfmBundle(ctx, frames.frame_off_host, pairs, job.cloud_cap, camera, dist, device=dev, d_frame_off=frames.d_frame_off,
                                d_pairs=d_pairs, **reg[2])
+        if uq is not None:
+            uq.run(d_out, d_mask, d_tv)
         job.run(d_out, d_mask, d_p3, d_tv)
         if refine is not None:
             refine.run(job, frames.d_kp, d_out, d_mask)
         joined = job.results()
         joined["register_plan"] = joined.pop("plan")
+        if uq is not None:
+            joined["keep"], joined["unique_counts"] = uq.results()
         if refine is not None:
             joined.update(refine.results(len(joined["cloud_id"])))
     ctx.synchronize()
@@ -73,7 +82,7 @@ def _two_view(ctx, frames, d_pairs, n_pairs, max_m, total_m, d_out, d_res, camer
 def run_dataset(ctx, ds, withRotation=False, withScale=False, thresholdFactor=6.0, match=None, camera=None, dist=None, prob=0.7,
                 ransac_threshold=1.0, max_iters=1000, device="cuda:0", method="gms", dictionary=None, logos_capacity=None,
                 cross_check=True, distance_coef=4.0, max_size=500, train_dictionary=None, register=False, root=0, min_links=8, bundle=False,
-                **ba):
+                unique=False, **ba):
     """(prob, ransac_threshold: findEssentialMat's confidence and threshold as the flow this function restates passes them -- SfMUtil.cpp:39:
     RANSAC, 0.7, 1.0 -- not OpenCV's own default of 0.999, which gms_find_essential_batch_device's Python mirror keeps.)
     ds: io.Dataset. match=None: brute-force match when the file carries descriptors and no matches. camera = (fx, fy, cx, cy)
@@ -94,8 +103,12 @@ def run_dataset(ctx, ds, withRotation=False, withScale=False, thresholdFactor=6.
     bundle=True (needs register=True; ba: n_iters, n_cg, lambda0, cg_tol, ftol, huber_px, retriangulate): gms_sfm_ba_device then refines
     views and cloud over all the keypoints of a track, in stream order behind the registration. Adds views_ba, cloud_ba,
     track_status and ba_summary; the registration's own arrays stay as they are. bundle=False returns the dict without them.
+    unique=True (needs register=True; ValueError otherwise): gms_match_unique_device in front of the registration, which then builds
+    its tracks from the one-to-one matches only: with the plan the library makes no track holds two keypoints of a
+    frame, and the bundle adjustment reads the tracks as they are. Adds keep (uint8 per match slot) and unique_counts (int32 live, kept
+    per pair); views, registration and points_world are the bytes of unique=False, which returns the dict without the two.
     The stages themselves work on resident tables (_run_gms, _run_bf, _run_logos): run_images feeds them from pixels."""
-    tail = (camera, dist, prob, ransac_threshold, max_iters, _register_args(register, root, min_links, camera, bundle, ba))
+    tail = (camera, dist, prob, ransac_threshold, max_iters, _register_args(register, root, min_links, camera, bundle, ba, unique))
     if method == "bf":
         if ds.descriptors is None:
             raise ValueError("method='bf' needs the dataset's descriptors")
@@ -170,11 +183,13 @@ def _run_gms(ctx, frames, descs, src_pairs, matches, withRotation, withScale, th
     return out
 
 
-def _register_args(register, root, min_links, camera, bundle=False, ba=None):
-    """run_dataset's register / root / min_links / bundle and the bundle adjustment's keywords -> None or (root, min_links, None or
-    those keywords), checked before anything is launched."""
+def _register_args(register, root, min_links, camera, bundle=False, ba=None, unique=False):
+    """run_dataset's register / root / min_links / bundle / unique and the bundle adjustment's keywords -> None or (root, min_links,
+    None or those keywords, unique), checked before anything is launched."""
     if bundle and not register:
         raise ValueError("bundle=True needs register=True: it refines the registration")
+    if unique and not register:
+        raise ValueError("unique=True needs register=True: it chooses the matches the registration builds its tracks from")
     if ba and not bundle:
         raise TypeError(f"unknown arguments {sorted(ba)} (the bundle adjustment's, without bundle=True)")
     if not register:
@@ -185,7 +200,7 @@ def _register_args(register, root, min_links, camera, bundle=False, ba=None):
         raise ValueError("root: a frame index; min_links: at least 1")
     if bundle:
         sfm_ba_params(**ba)   # (refuses an unknown keyword)
-    return int(root), int(min_links), (dict(ba) if bundle else None)
+    return int(root), int(min_links), (dict(ba) if bundle else None), bool(unique)
 
 
 def image_stack(images):
@@ -231,7 +246,7 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
                device=None, dictionary=None, logos_capacity=None, cross_check=True, distance_coef=4.0, max_size=500, train_dictionary=None,
                keep_tables=False, detector="fast", contrast=128, refine=False, register=False, root=0, min_links=8, bundle=False, dense=False,
                min_disp16=16, dense_cap=None, dense_sgm=None, fuse=False, fuse_tol16=16, fuse_min_support=1, fuse_cap=None, dense_speckle=None,
-               dense_poses="pair", dense_pairs=None, **ba):
+               dense_poses="pair", dense_pairs=None, unique=False, **ba):
     """run_dataset from pixels. images: [n, H, W] grey or [n, H, W, 3] BGR, 8-bit, a host array or a device tensor (or a list of equally
     sized images). BGR goes through gms_bgr_to_gray_device; the pyramid keypoint source (threshold, max_keypoints, n_levels; detector
     "fast", or "dog" with `contrast` in the place of `threshold`: gms_detect_dog_batch_device, with refine=True
@@ -240,7 +255,7 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
     n + 1 frame offsets (and the status records the stages already read) come back. pairs: (frame_a, frame_b) rows or PAIR_DTYPE
     records; default every a < b. The other arguments and the returned records are run_dataset's (the matcher always runs: there are
     no matches to bring); keep_tables=True adds `tables` = (FrameTable, DescriptorTable), the resident keypoints and rows.
-    register, root, min_links, bundle and the bundle adjustment's keywords: run_dataset's.
+    register, root, min_links, bundle, unique and the bundle adjustment's keywords: run_dataset's.
     dense=True (needs a camera): adds `dense`, one entry per pair -- None for a pair without a pose or one that is not
     rectifiable, else a dict of points float32 [k, 3], colors uint8 [k] or [k, 3], pixel int32 [k], count and plan
     (gms_dense_pairs_device on the photographs themselves; min_disp16, dense_cap = the most points per pair, dense_sgm = the
@@ -276,7 +291,7 @@ def run_images(ctx, images, camera=None, dist=None, method="gms", pairs=None, th
         raise ValueError('descriptor: "brief", "grad" or "both"')
     images, is_bgr = image_stack(images)
     n, h, w = images.shape[:3]
-    reg = _register_args(register, root, min_links, camera, bundle, ba)
+    reg = _register_args(register, root, min_links, camera, bundle, ba, unique)
     if reg is not None and not 0 <= reg[0] < n:
         raise ValueError("root: a frame index")
     if pairs is None:

@@ -1,0 +1,65 @@
+// tests/test_cpp_match_unique_shim.py: mi355::uniqueMatches, then mi355::registerViews on its keep plane (sfm-gms_amd/include/mi355_gms.hpp)
+// on the arrays of an input file, printing an FNV-1a checksum of keep, of the counts and of each output of the registration in the order
+// views, pairs, points_world, track, cloud, cloud_id, cloud_obs, cloud_est, cloud_spread, summary. Input: sfm_register_shim_main's. No
+// arguments: prints usage and exits 2 (the CPU test links this without a device).
+#include <cstdio>
+#include <vector>
+
+#include "mi355_gms.hpp"
+
+static unsigned long long fnv(const void* q, size_t n)
+{
+    const unsigned char* p = static_cast<const unsigned char*>(q);
+    unsigned long long s = 1469598103934665603ull;
+    for (size_t i = 0; i < n; ++i) s = (s ^ p[i]) * 1099511628211ull;
+    return s;
+}
+
+template <class T>
+static bool read_all(FILE* f, std::vector<T>& v)
+{
+    return v.empty() || std::fread(v.data(), sizeof(T), v.size(), f) == v.size();
+}
+
+template <class T>
+static void print_sum(const std::vector<T>& v)
+{
+    std::printf("%llu\n", fnv(v.data(), v.size() * sizeof(T)));
+}
+
+int main(int argc, char** argv)
+{
+    if (argc < 2) {
+        std::fprintf(stderr, "usage: match_unique_shim_main RECORDS.bin\n");
+        return 2;
+    }
+    FILE* f = std::fopen(argv[1], "rb");
+    if (!f) return 2;
+    int32_t head[4];
+    int64_t total;
+    if (std::fread(head, 4, 4, f) != 4 || std::fread(&total, 8, 1, f) != 1 || head[0] < 1 || head[1] < 0 || total < 0) return 2;
+    std::vector<int64_t> frame_off((size_t)head[0] + 1);
+    std::vector<gms_pair> pairs((size_t)head[1]);
+    std::vector<gms_dmatch> matches((size_t)total);
+    std::vector<uint8_t> mask((size_t)total);
+    std::vector<double> points(3 * (size_t)total);
+    std::vector<gms_two_view> tv((size_t)head[1]);
+    if (!read_all(f, frame_off) || !read_all(f, pairs) || !read_all(f, matches) || !read_all(f, mask) || !read_all(f, points) || !read_all(f, tv)) return 2;
+    std::fclose(f);
+    std::vector<int32_t> counts;
+    const std::vector<uint8_t> keep = mi355::uniqueMatches(frame_off, pairs, matches, mask, tv, &counts);
+    print_sum(keep);
+    print_sum(counts);
+    const mi355::Registration r = mi355::registerViews(frame_off, pairs, matches, mask, points, tv, keep, head[2], head[3]);
+    print_sum(r.views);
+    print_sum(r.pairs);
+    print_sum(r.points_world);
+    print_sum(r.track);
+    print_sum(r.cloud);
+    print_sum(r.cloud_id);
+    print_sum(r.cloud_obs);
+    print_sum(r.cloud_est);
+    print_sum(r.cloud_spread);
+    std::printf("%llu\n", fnv(&r.summary, sizeof r.summary));
+    return 0;
+}

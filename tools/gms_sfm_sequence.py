@@ -3,7 +3,7 @@
 pipeline.run_images(register=True): per pair the two-view stage, then gms_sfm_register_device joins the pairs).
 Prints one JSON line: per pair n_links, r, S and status; per view the camera centre; tracks by length; the median spread.
 
-    python tools/gms_sfm_sequence.py [images.npz] [--method gms|bf|logos] [--pairs chain|star|all] [--root 0] [--min-links 8] [--max-keypoints 2000] [--ply out.ply] [--bundle] [--dense [--speckle SIZE,DIFF16] [--dense-poses pair|registration|bundle] [--dense-pairs a-b,c-d] [--fuse [--fuse-tol16 16] [--fuse-min-support 1]]] [--check]
+    python tools/gms_sfm_sequence.py [images.npz] [--method gms|bf|logos] [--pairs chain|star|all] [--root 0] [--min-links 8] [--max-keypoints 2000] [--ply out.ply] [--unique] [--bundle] [--dense [--speckle SIZE,DIFF16] [--dense-poses pair|registration|bundle] [--dense-pairs a-b,c-d] [--fuse [--fuse-tol16 16] [--fuse-min-support 1]]] [--check]
 
 images.npz: arrays images ([n, H, W] grey or [n, H, W, 3] BGR, uint8) and camera = (fx, fy, cx, cy), optionally dist. Default: views
 1, 2, 3, 4 of the reference's SourceImages scene from the two committed fixtures (tests/golden/image_sfm_pair_1008x756.npz holds views 1
@@ -23,7 +23,11 @@ filter, and the filtered maps and clouds must equal the numpy statements (tests/
 registration's / the bundle-adjusted views (gms_sfm_pair_poses_device; DESIGN.md 4.10d) instead of each pair's own two-view pose;
 --dense-pairs a-b,c-d: those frame pairs are matched densely in place of the sparse pair list (the per-pair figures of the dense
 stage and the fusion then follow that list). With --check the records must equal the numpy statement (tests/sfm_pair_pose_ref.py)
-on the GPU's own views and every plan tests/rectify_ref.py's on its record, byte for byte; the other checks run on those records."""
+on the GPU's own views and every plan tests/rectify_ref.py's on its record, byte for byte; the other checks run on those records.
+--unique: one-to-one matches per pair in front of the registration (gms_match_unique_device): per pair the live and
+the kept matches; the tracks, and with --bundle the observations, are then built from the kept matches only. With --check the keep
+plane and the counts must equal the numpy statement (tests/match_unique_ref.py) on the GPU's own records byte for byte, and the
+registration is compared with that statement's register_keep."""
 import argparse
 import importlib
 import json
@@ -175,6 +179,7 @@ def main():
     ap.add_argument("--ply")
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--bundle", action="store_true")
+    ap.add_argument("--unique", action="store_true", help="one-to-one matches per pair in front of the registration (DESIGN.md 4.10e)")
     ap.add_argument("--dense", action="store_true")
     ap.add_argument("--fuse", action="store_true")
     ap.add_argument("--fuse-tol16", type=int, default=16)
@@ -208,7 +213,7 @@ def main():
     pairs = pair_list(a.pairs, n, a.root)
     pkg = importlib.import_module("sfm-gms_amd")
     r = pkg.structureFromMotionMulti(images, camera, dist, method=a.method, pairs=pairs, root=a.root, min_links=a.min_links,
-                                     max_keypoints=a.max_keypoints, keep_tables=True, bundle=a.bundle,
+                                     max_keypoints=a.max_keypoints, keep_tables=True, bundle=a.bundle, unique=a.unique,
                                      **(dict(dense=True, dense_cap=a.dense_cap, dense_speckle=a.speckle) if a.dense else {}),
                                      **(dict(dense_poses=a.dense_poses, dense_pairs=a.dense_pairs) if a.dense_poses != "pair" else {}),
                                      **(dict(fuse=True, fuse_tol16=a.fuse_tol16, fuse_min_support=a.fuse_min_support) if a.fuse else {}))
@@ -229,6 +234,8 @@ def main():
             "median_depth": None if not len(depth) else round(float(np.median(depth)), 5),
             "median_spread": None if not len(many) else round(float(np.median(many)), 6),
             "median_spread_over_median_depth": None if not len(many) or not len(depth) else round(float(np.median(many) / np.median(depth)), 6)}
+    if a.unique:
+        line["unique"] = {"live_per_pair": r["unique_counts"][:, 0].tolist(), "kept_per_pair": r["unique_counts"][:, 1].tolist()}
     if a.bundle:
         s, st = r["ba_summary"][0], np.bincount(r["track_status"], minlength=4)
         line["bundle"] = {"rms_px_before": round(float(s["rms0_px"]), 4), "rms_px_after": round(float(s["rms_px"]), 4),
@@ -289,7 +296,16 @@ def main():
     if a.check:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import sfm_register_ref as ref
-        want = ref.register(r["tables"][0].frame_off_host, r["pairs"], r["out"], r["mask"], r["points3d"], tv, a.root, a.min_links)
+        keep = None
+        if a.unique:
+            import match_unique_ref as unique_ref
+            keep, counts = unique_ref.unique(r["tables"][0].frame_off_host, r["pairs"], r["out"], r["mask"], tv)
+            line["unique"]["check_vs_statement"] = {"keep": r["keep"].tobytes() == keep.tobytes(), "counts": r["unique_counts"].tobytes() == counts.tobytes()}
+            ok = ok and all(line["unique"]["check_vs_statement"].values())
+            want = unique_ref.register_keep(r["tables"][0].frame_off_host, r["pairs"], r["out"], r["mask"], r["points3d"], tv, a.root, a.min_links,
+                                            keep=keep)
+        else:
+            want = ref.register(r["tables"][0].frame_off_host, r["pairs"], r["out"], r["mask"], r["points3d"], tv, a.root, a.min_links)
 
         def near(x, y, size=0.0):
             x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
