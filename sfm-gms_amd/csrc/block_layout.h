@@ -1,6 +1,6 @@
 // block_layout.h -- where the regions of one device block start.
 //
-// The one-shot host entry points of gms_capi.cpp (gms_bf_match_select, gms_stereo_bm, gms_portrait, ...) keep everything a call needs --
+// The one-shot host entry points of the capi_*.cpp (gms_bf_match_select, gms_stereo_bm, gms_portrait, ...) keep everything a call needs --
 // inputs, tables, workspace, outputs -- in ONE device allocation. This is the arithmetic of that block, and nothing else: no HIP
 // header, so that a host compiler builds it alone (tests/cpp/block_layout_check.cpp does).
 #pragma once

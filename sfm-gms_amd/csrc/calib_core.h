@@ -1,5 +1,5 @@
 // calib_core.h -- camera calibration from chessboard photographs: what the kernels (calib_kernels.hip), the C ABI
-// (gms_capi.cpp) and the host test build (tests/cpp/calib_host.cpp) share. tests/calib_ref.py states the same in numpy.
+// (capi_calib.cpp) and the host test build (tests/cpp/calib_host.cpp) share. tests/calib_ref.py states the same in numpy.
 //   corner candidates   an integer saddle response, its 17 x 17 peaks, the strongest of them: this library's own definition
 //   order_board         the candidates onto the nx x ny grid, host only, fp64
 //   subpix_refine       cv::cornerSubPix (OpenCV 4.5.2, read from its source) for one corner, fp64, host and device

@@ -164,7 +164,7 @@ triangulate_kernel(CameraModel cam, const float2* __restrict__ coords1, const fl
 }
 
 // ---- cv::recoverPose (SfMUtil.cpp:45) -----------------------------------------------------------------------------------------------
-// The four (R, t) an essential matrix decomposes into (the host does the 3 x 3 decomposition: gms_capi.cpp) are tried on every
+// The four (R, t) an essential matrix decomposes into (the host does the 3 x 3 decomposition: capi_twoview.cpp) are tried on every
 // correspondence as OpenCV 4.5.2 does: triangulate with P0 = [I|0] and P = [R|t] in normalised coordinates ((x - cx) / fx, no
 // distortion model), keep the point if its depth is positive and below the distance threshold in both cameras. One byte of four
 // vote bits per correspondence, four counters; pose_pick_kernel then takes the first hypothesis with the most votes in the order

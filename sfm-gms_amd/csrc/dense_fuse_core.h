@@ -1,6 +1,6 @@
 // dense_fuse_core.h -- the clouds of several posed pairs fused into one by depth consistency: whether a source (one
 // pair's disparity map, valid plane, plan, view and scale) sees a point where its own map says it is, and the rule that keeps a point
-// once. The library's own definition. What the kernels (dense_fuse_kernels.hip), the C ABI (gms_capi.cpp) and the host test build
+// once. The library's own definition. What the kernels (dense_fuse_kernels.hip), the C ABI (capi_dense.cpp) and the host test build
 // (tests/cpp/dense_fuse_host.cpp) share; tests/dense_fuse_ref.py states the same in numpy. fp64, only + - * / rint, every sum in the
 // order written here, built with -ffp-contract=off: the GPU, the host and numpy agree bit for bit.
 #pragma once

@@ -1,4 +1,4 @@
-// logos_batch.h -- layouts shared by the batched LOGOS path (logos_batch_kernels.hip) and its C ABI (gms_capi.cpp): the per-frame
+// logos_batch.h -- layouts shared by the batched LOGOS path (logos_batch_kernels.hip) and its C ABI (capi_logos.cpp): the per-frame
 // table gms_logos_prepare_device builds and the workspace of gms_logos_prepare_device / gms_logos_filter_device. Both are opaque to
 // callers, who only size them (gms_logos_table_bytes, gms_logos_workspace_bytes).
 #pragma once

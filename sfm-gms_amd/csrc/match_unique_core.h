@@ -1,5 +1,5 @@
 // match_unique_core.h -- one-to-one matches per pair: the order key of a match, when a match is live, and the keep
-// rule as a sequential statement. What the kernels (match_unique_kernels.hip), the C ABI (gms_capi.cpp) and the host build
+// rule as a sequential statement. What the kernels (match_unique_kernels.hip), the C ABI (capi_sfm.cpp) and the host build
 // (tests/cpp/match_unique_host.cpp) share; tests/match_unique_ref.py states the same in numpy. The library's own definition.
 #pragma once
 #include <stdint.h>

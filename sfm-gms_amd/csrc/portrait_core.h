@@ -1,5 +1,5 @@
 // portrait_core.h -- portrait mode's parameter check, neighbour numbering and border walk: what the C ABI
-// (gms_capi.cpp), the kernels (portrait_kernels.hip) and host tests share. tests/portrait_ref.py states the same in numpy.
+// (capi_image.cpp), the kernels (portrait_kernels.hip) and host tests share. tests/portrait_ref.py states the same in numpy.
 #pragma once
 #include <stdint.h>
 

@@ -2,7 +2,7 @@
 // rectifying plan of a pair (two rotations and one new camera), the map from a rectified pixel to a source position with the
 // distortion model applied, and the reprojection of a disparity into the frame of the pair's sparse points. The library's own
 // definition; it follows cv::stereoRectify, initUndistortRectifyMap, remap and reprojectImageTo3D in structure only. What the kernels
-// (rectify_kernels.hip), the C ABI (gms_capi.cpp) and the host test build (tests/cpp/rectify_host.cpp) share; tests/rectify_ref.py
+// (rectify_kernels.hip), the C ABI (capi_image.cpp) and the host test build (tests/cpp/rectify_host.cpp) share; tests/rectify_ref.py
 // states the same in numpy. fp64, only + - * / sqrt rint, every sum in the order written here, built with -ffp-contract=off: the GPU,
 // the host and numpy agree bit for bit. No sin / cos / acos: the device's are not the host's.
 #pragma once

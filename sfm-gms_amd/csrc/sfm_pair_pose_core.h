@@ -1,7 +1,7 @@
 // sfm_pair_pose_core.h -- the two-view and registration records of a frame pair, derived from two views of one view array (DESIGN.md
 // §4.10d): the relative pose R_ab, the unit baseline t and its length S, as the dense stage (gms_dense_pairs_device) and the fusion
 // (gms_dense_fuse_device) read them from gms_two_view.R/t/status and gms_sfm_pair_reg.S/status. The library's own definition. What the
-// kernel (sfm_pair_pose_kernels.hip), the C ABI (gms_capi.cpp) and the host test build (tests/cpp/sfm_pair_pose_host.cpp) share;
+// kernel (sfm_pair_pose_kernels.hip), the C ABI (capi_sfm.cpp) and the host test build (tests/cpp/sfm_pair_pose_host.cpp) share;
 // tests/sfm_pair_pose_ref.py states the same in numpy. fp64, only + - * / sqrt, every sum in index order 0, 1, 2, built with
 // -ffp-contract=off: the GPU, the host and numpy agree bit for bit.
 #pragma once

@@ -1,5 +1,5 @@
 // sfm_register_core.h -- registering many two-view results into one frame: the plan over the pair list, when a
-// link between two pairs' points counts and its scale ratio, and the pose and point transforms. What the C ABI (gms_capi.cpp), the
+// link between two pairs' points counts and its scale ratio, and the pose and point transforms. What the C ABI (capi_sfm.cpp), the
 // kernels (sfm_register_kernels.hip) and the host build (tests/cpp/sfm_register_host.cpp) share; tests/sfm_register_ref.py states the
 // same in numpy. This is the library's own definition: the reference stops at one pair (SfMUtil.cpp:4-83).
 #pragma once

@@ -1,4 +1,4 @@
-// stereo_bm_core.h -- StereoBM's geometry, parameter check and subpixel step: what the C ABI (gms_capi.cpp) and the
+// stereo_bm_core.h -- StereoBM's geometry, parameter check and subpixel step: what the C ABI (capi_stereo.cpp) and the
 // kernels (stereo_bm_kernels.hip) share. tests/stereo_bm_ref.py states the same in numpy.
 #pragma once
 #include <stdint.h>

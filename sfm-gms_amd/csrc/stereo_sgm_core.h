@@ -1,5 +1,5 @@
 // stereo_sgm_core.h -- semi-global matching on StereoBM's costs: the parameter check, the eight path directions, the
-// lines a direction cuts the computed region into, and one step of the path recurrence. What the C ABI (gms_capi.cpp), the kernels
+// lines a direction cuts the computed region into, and one step of the path recurrence. What the C ABI (capi_stereo.cpp, capi_dense.cpp), the kernels
 // (stereo_sgm_kernels.hip) and the host build (tests/cpp/stereo_sgm_host.cpp) share; tests/stereo_sgm_ref.py states the same in numpy.
 // This is the library's own definition, not cv::StereoSGBM: the matching cost is StereoBM's window SAD, not Birchfield-Tomasi.
 #pragma once

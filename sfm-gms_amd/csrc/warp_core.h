@@ -1,6 +1,6 @@
 // warp_core.h -- cv::resize (INTER_LINEAR, 8-bit) and cv::warpAffine (INTER_LINEAR, BORDER_CONSTANT 0, 8-bit) as integer arithmetic
 // on taps that come from a few IEEE fp32 / fp64 operations: what the kernels (warp_kernels.hip), the C ABI
-// (gms_capi.cpp) and the host test build (tests/cpp/warp_host.cpp) share. tests/warp_ref.py states the same in numpy. Built with
+// (capi_image.cpp) and the host test build (tests/cpp/warp_host.cpp) share. tests/warp_ref.py states the same in numpy. Built with
 // -ffp-contract=off: no product below may be fused into a sum.
 #pragma once
 #include <math.h>

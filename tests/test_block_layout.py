@@ -1,6 +1,6 @@
 """CPU: the offset arithmetic of the one-shot host entry points' device block (gms::BlockLayout, sfm-gms_amd/csrc/block_layout.h),
 compiled for the host by g++ into tests/cpp/block_layout_check.cpp -- a test build, the product includes the same header in
-gms_capi.cpp. Over a few thousand seeded sequences of add(bytes, slack), with sizes 0, 1, 255, 256, 257 and above 4 GiB among them:
+capi_common.h, for the one-shot entry points of the capi_*.cpp. Over a few thousand seeded sequences of add(bytes, slack), with sizes 0, 1, 255, 256, 257 and above 4 GiB among them:
 every offset is a multiple of 256, regions follow each other in call order without overlap, each is at least bytes + slack long, and
 the block is less than 256 * (regions + 1) bytes larger than what it holds."""
 import os
