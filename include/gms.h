@@ -781,13 +781,17 @@ int gms_detect_pack_device(gms_ctx* ctx, const gms_keypoint* d_keypoint_blocks, 
  * Host pointers; synchronous; uses the current HIP device. out_cap: room in `out`. *n_out: the number of survivors -- also when
  * that exceeds out_cap, in which case nothing is written and GMS_ERR_CAPACITY is returned. result may be NULL.
  * Neighbours at equal distances are taken in the order the reference's (unstable) std::sort leaves them in, restated in
- * logos_core.h. Frames of 1..5 keypoints use the neighbours there are (the reference reads past its list there). */
+ * logos_core.h. Frames of 1..5 keypoints use the neighbours there are (the reference reads past its list there).
+ * Keypoint domain (every LOGOS entry point): pt.x, pt.y and angle finite, |angle| <= 3600 degrees; size is not restricted (0,
+ * negative, NaN and inf give a log scale that fails every comparison, as in the reference). Outside the domain the reference's
+ * orientation wrap does not terminate. gms_logos_match checks both frames on the host before any allocation or copy: it returns
+ * GMS_ERR_DOMAIN with *n_out = 0 and result->status = GMS_ERR_DOMAIN, and writes nothing to `out`. */
 typedef struct gms_logos_result {
     int64_t n_candidates; /* pairs with equal labels                                   */
     int64_t n_supported;  /* candidates with local support                             */
     int64_t n_out;        /* survivors (the needed count on overflow)                  */
     int32_t peak_bin;     /* 0..188, -1 when no candidate had support                  */
-    int32_t status;       /* GMS_OK or GMS_ERR_CAPACITY (batched path also: _DOMAIN, _BAD_ARG) */
+    int32_t status;       /* GMS_OK, GMS_ERR_CAPACITY or GMS_ERR_DOMAIN (batched path also: _BAD_ARG) */
 } gms_logos_result;
 
 int gms_logos_match(const gms_keypoint* kp1, int n1, const gms_keypoint* kp2, int n2, const int32_t* nn1, const int32_t* nn2,
@@ -802,7 +806,8 @@ int gms_logos_match(const gms_keypoint* kp1, int n1, const gms_keypoint* kp2, in
  *   opaque) for the keypoints d_kp of n_frames frames (d_frame_off: n_frames + 1 offsets) and one word per keypoint, d_words,
  *   in [0, n_words): the LOGOS point of each keypoint, its five nearest neighbours in its frame (ties at the fifth place in the
  *   order of the reference's sort, as gms_logos_match), and per frame its keypoints sorted by word (stable) with bucket offsets.
- *   A word outside [0, n_words) marks its frame: pairs that touch it get GMS_ERR_DOMAIN. The workspace holds the slices of the tie
+ *   A word outside [0, n_words), or a keypoint outside the keypoint domain stated at gms_logos_match, marks its frame: pairs that
+ *   touch it, in either role, get GMS_ERR_DOMAIN and none of their queries is run. The workspace holds the slices of the tie
  *   pass: with fewer than gms_logos_workspace_bytes(largest frame, 0, 0) bytes, a frame whose ties do not fit is marked and its
  *   pairs get GMS_ERR_BAD_ARG.
  * gms_logos_filter_device: n_pairs pairs of the table's frames. For a gms_pair here, m is the pair's OUTPUT CAPACITY and match_off
@@ -821,7 +826,8 @@ int gms_logos_match(const gms_keypoint* kp1, int n1, const gms_keypoint* kp2, in
  *                          distance counts as +inf.
  *     GMS_DESC_HAMMING256  rows of 32 bytes; popcount of the xor.
  * gms_logos_host_batch: prepare + filter on host arrays, synchronous (the C++ shim's batch form); pairs / out / results as for
- *   gms_logos_filter_device, in host memory. */
+ *   gms_logos_filter_device, in host memory. The keypoint domain is checked per frame by its prepare step, on the device: the
+ *   call returns GMS_OK and the pairs of a frame outside the domain carry GMS_ERR_DOMAIN in their records. */
 int64_t gms_logos_table_bytes(int64_t total_kp, int n_frames, int n_words);
 size_t  gms_logos_workspace_bytes(int64_t max_frame_kp, int n_pairs, int64_t max_query_kp);
 int gms_logos_prepare_device(gms_ctx* ctx, const gms_keypoint* d_kp, const int64_t* d_frame_off, int n_frames, int64_t total_kp,

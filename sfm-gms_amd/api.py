@@ -655,7 +655,10 @@ def matchLOGOS(keypoints1, keypoints2, nn1, nn2):
     """cv::xfeatures2d::matchLOGOS(keypoints1, keypoints2, nn1, nn2, matches1to2) (FeatureMatchUtil.cpp:86-131) on the GPU.
 
     keypoints*: KEYPOINT_DTYPE arrays (pt, size and angle are read); nn*: the visual word of each keypoint (int32). Returns the
-    surviving DMATCH_DTYPE records (queryIdx, trainIdx, imgIdx -1, distance 0) in the reference's order."""
+    surviving DMATCH_DTYPE records (queryIdx, trainIdx, imgIdx -1, distance 0) in the reference's order.
+
+    Keypoint domain: pt.x, pt.y and angle finite, |angle| <= 3600 degrees (-1, OpenCV's "no orientation", is inside); size is not
+    restricted. Outside it the reference does not terminate; here GmsError with code GMS_ERR_DOMAIN is raised before any device work."""
     lib = load_library()
     kp1 = _as(keypoints1, KEYPOINT_DTYPE, "keypoints1")
     kp2 = _as(keypoints2, KEYPOINT_DTYPE, "keypoints2")

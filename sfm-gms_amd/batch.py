@@ -493,7 +493,8 @@ class LogosTable:
 
     keypoints_per_frame: a list of KEYPOINT_DTYPE arrays, or a FrameTable whose resident keypoints are used. words_per_frame: one word
     per keypoint in [0, n_words) -- a list of per-frame int arrays, or an int32 device tensor of all keypoints back to back (as
-    gms_logos_words_device leaves it). A frame with a word out of range is marked: its pairs come back with GMS_ERR_DOMAIN."""
+    gms_logos_words_device leaves it). A frame with a word out of range, or with a keypoint outside the domain (pt.x, pt.y and angle
+    finite, |angle| <= 3600 degrees; size is not restricted), is marked: its pairs come back with GMS_ERR_DOMAIN."""
 
     def __init__(self, ctx, keypoints_per_frame, words_per_frame, n_words, device="cuda:0"):
         self.ctx, self.n_words = ctx, int(n_words)

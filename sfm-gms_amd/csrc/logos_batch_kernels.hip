@@ -140,10 +140,13 @@ __global__ void __launch_bounds__(kBlock) prep_points_kernel(const gms_keypoint*
     const int n_words = t.h->n_words;
     for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < n; k += (int64_t)gridDim.x * kBlock) {
         const gms_keypoint p = kp[k];
-        t.pts[k] = Pt{p.x, p.y, gms::logos::orientation(p.angle), gms::logos::logf_(p.size)};
+        // a keypoint outside the domain (logos_core.h kp_ok) marks its frame as a word out of range does, and is stored as zeros, so
+        // that no later prepare kernel sorts or compares a non-finite coordinate; the filter runs none of the frame's queries
+        const bool ok = gms::logos::kp_ok(p.x, p.y, p.angle);
+        t.pts[k] = ok ? Pt{p.x, p.y, gms::logos::orientation(p.angle), gms::logos::logf_(p.size)} : Pt{0.0f, 0.0f, 0.0f, 0.0f};
         const int32_t w = words[k];
         t.word[k] = w;
-        if (w < 0 || w >= n_words) atomicMin(&t.status[last_le(t.frame_off, t.h->n_frames, k)], GMS_ERR_DOMAIN);
+        if (!ok || w < 0 || w >= n_words) atomicMin(&t.status[last_le(t.frame_off, t.h->n_frames, k)], GMS_ERR_DOMAIN);
     }
 }
 
@@ -353,7 +356,9 @@ __device__ __forceinline__ FilterWs filter_ws(void* ws, int n_pairs)
     return f;
 }
 
-// pair checks and the batch's query numbering; zeroes the pairs' accumulators
+// pair checks and the batch's query numbering; zeroes the pairs' accumulators. A pair of a marked frame (a word out of range, a
+// keypoint outside the domain, ties that did not fit the prepare workspace) takes the frame's status in either role and gets n1 = 0:
+// it has no queries in the numbering, so passes 1-3 never read the frame's points, neighbours or buckets.
 __global__ void __launch_bounds__(kScanBlock) filter_plan_kernel(const void* table, const gms_pair* __restrict__ pairs, int n_pairs,
                                                                   void* ws, int64_t keep_cap)
 {

@@ -101,11 +101,23 @@ GMS_HD float acosf_(float xf)
 // Point::Point: orientation = (float)(angle * pi / 180.0) in fp64
 GMS_HD float orientation(float angle_deg) { return (float)(((double)angle_deg * kPi) / 180.0); }
 
-// PointPair::PointPair: relOri = o1 - o2, brought into [-pi, pi] through fp64 the way the DLL loops
+// The keypoint domain of every LOGOS entry point (include/gms.h): x, y and angle finite, |angle| <= kMaxAngleDeg. Ten turns is far
+// beyond any detector's output (-1, OpenCV's "no orientation", and 360 lie inside), and it is what bounds the loops of rel_ori:
+// beyond 2^27 rad a float no longer changes when 2 pi is taken off it, so the DLL's loop -- and this one -- would never end.
+// size is not restricted: logf_ is total and a NaN fails every comparison, as in the DLL.
+constexpr float kMaxAngleDeg = 3600.0f;
+GMS_HD bool kp_ok(float x, float y, float angle)
+{
+    return x - x == 0.0f && y - y == 0.0f && angle - angle == 0.0f && fabsf(angle) <= kMaxAngleDeg;
+}
+
+// PointPair::PointPair: relOri = o1 - o2, brought into [-pi, pi] through fp64 the way the DLL loops. The entry points admit only
+// keypoints that pass kp_ok, so |d| <= 2 * 3600 deg = 40 pi (+ rounding) and either loop runs at most 21 times; the inf / NaN test
+// only keeps a direct caller (the host build) from looping, it is not reached from the kernels.
 GMS_HD float rel_ori(float o1, float o2)
 {
     float d = o1 - o2;
-    if (!(d - d == 0.0f)) return d;  // inf / NaN: the DLL's loops would not end; left as they are
+    if (!(d - d == 0.0f)) return d;  // inf / NaN: outside the domain; left as they are
     while ((double)d > kPi) d = (float)((double)d - kTwoPi);
     while (-kPi > (double)d) d = (float)((double)d + kTwoPi);
     return d;

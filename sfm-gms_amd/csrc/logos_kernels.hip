@@ -276,6 +276,15 @@ extern "C" int gms_logos_match(const gms_keypoint* kp1, int n1, const gms_keypoi
     if (result) *result = gms_logos_result{0, 0, 0, -1, GMS_OK};
     if (n1 < 0 || n2 < 0 || out_cap < 0 || !n_out) return GMS_ERR_BAD_ARG;
     if ((n1 > 0 && (!kp1 || !nn1)) || (n2 > 0 && (!kp2 || !nn2)) || (out_cap > 0 && !out)) return GMS_ERR_BAD_ARG;
+    // the keypoint domain (logos_core.h kp_ok), before any allocation or copy: outside it the wrap loops of rel_ori would not end
+    for (int f = 0; f < 2; f++) {
+        const gms_keypoint* k = f ? kp2 : kp1;
+        for (int i = 0, m = f ? n2 : n1; i < m; i++) {
+            if (gms::logos::kp_ok(k[i].x, k[i].y, k[i].angle)) continue;
+            if (result) result->status = GMS_ERR_DOMAIN;
+            return GMS_ERR_DOMAIN;
+        }
+    }
     if (n1 == 0 || n2 == 0) return GMS_OK;
 
     DevBuf kp, lab, pts, nb, cnt, bins, peak, keep, koff, dout, ties, work;

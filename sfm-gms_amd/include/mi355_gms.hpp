@@ -165,7 +165,7 @@ inline void matchLOGOS(const std::vector<KeyPoint>& keypoints1, const std::vecto
 // The LOGOS filter for a whole sequence in one call, on a context (gms_logos_host_batch): keypoints[f] / words[f] describe frame f
 // (words in [0, n_words)), pair p filters frames pairs[p].first (query side) and pairs[p].second; matches1to2[p] receives what
 // matchLOGOS would. Each frame's neighbours and word buckets are worked out once for all its pairs. Pairs the library refuses (a word
-// out of range: GMS_ERR_DOMAIN) come back empty with ok[p] = false (if given).
+// out of range, or a keypoint whose x, y or angle is not finite or whose |angle| exceeds 3600 degrees: GMS_ERR_DOMAIN) come back empty with ok[p] = false (if given).
 inline void matchLOGOSBatch(const std::vector<std::vector<KeyPoint>>& keypoints, const std::vector<std::vector<int>>& words, int n_words,
                             const std::vector<std::pair<int, int>>& pairs, std::vector<std::vector<DMatch>>& matches1to2,
                             std::vector<bool>* ok = nullptr)

@@ -16,6 +16,13 @@ void logos_host_acosf(const float* x, int n, float* y)
     for (int i = 0; i < n; i++) y[i] = acosf_(x[i]);
 }
 
+// the keypoint domain of the entry points, and the wrapped difference of two orientations (radians)
+int logos_host_kp_ok(float x, float y, float angle) { return kp_ok(x, y, angle) ? 1 : 0; }
+
+float logos_host_orientation(float angle_deg) { return orientation(angle_deg); }
+
+float logos_host_rel_ori(float o1, float o2) { return rel_ori(o1, o2); }
+
 // the first k places of the DLL's std::sort over n (d, ix) records, in place
 void logos_host_sort_head(float* d, int* ix, long n, long k) { msvc_sort_head(d, ix, n, k); }
 

@@ -211,10 +211,22 @@ def neighbours(x, y, k=NUM, chunk=1024):
     return out
 
 
+MAX_ANGLE_DEG = F(3600.0)
+
+
+def kp_ok(x, y, angle):
+    """The keypoint domain of every LOGOS entry point (include/gms.h; logos_core.h kp_ok): x, y and angle finite and
+    |angle| <= 3600. Elementwise on float32 arrays."""
+    x, y, angle = (np.asarray(v, F) for v in (x, y, angle))
+    return np.isfinite(x) & np.isfinite(y) & np.isfinite(angle) & (np.abs(angle) <= MAX_ANGLE_DEG)
+
+
 def _wrap_pair(d):
-    """relOri of a pair: d = o1 - o2 in float, brought into [-pi, pi] through double the way the DLL does."""
+    """relOri of a pair: d = o1 - o2 in float, brought into [-pi, pi] through double the way the DLL does. match() admits only
+    keypoints inside kp_ok, which bounds either loop to 21 rounds: beyond 2^27 rad a float no longer changes when 2 pi is taken
+    off it, and the DLL's loop -- and this one -- would never end."""
     d = d.astype(F)
-    fin = np.isfinite(d)           # inf / NaN: the DLL's loops would not end; left as they are
+    fin = np.isfinite(d)           # inf / NaN: outside the domain; left as they are
     while True:
         m = (d.astype(np.float64) > PI) & fin
         if not m.any():
@@ -312,9 +324,13 @@ def candidates(l1, l2):
 
 
 def match(kp1, kp2, nn1, nn2, detail=False):
-    """matchLOGOS: (m, 2) int32 (queryIdx, trainIdx). With detail, also (n candidates, n supported, peak bin)."""
+    """matchLOGOS: (m, 2) int32 (queryIdx, trainIdx). With detail, also (n candidates, n supported, peak bin). ValueError for a
+    keypoint outside the domain (kp_ok), where the DLL does not terminate."""
     kp1 = np.asarray(kp1, np.float32).reshape(-1, 4)
     kp2 = np.asarray(kp2, np.float32).reshape(-1, 4)
+    for kp in (kp1, kp2):
+        if not kp_ok(kp[:, 0], kp[:, 1], kp[:, 3]).all():
+            raise ValueError("matchLOGOS: a keypoint outside the domain (x, y, angle finite, |angle| <= 3600)")
     empty = np.zeros((0, 2), np.int32)
     if len(kp1) == 0 or len(kp2) == 0:
         return (empty, (0, 0, -1)) if detail else empty

@@ -8,25 +8,12 @@ import numpy as np
 import pytest
 
 import logos_ref
+from logos_gpu import kp_records as _kp, want_dmatch as _want_dmatch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pkg = importlib.import_module("sfm-gms_amd")
 Z = np.load(os.path.join(ROOT, "tests", "golden", "refdll_logos.npz"))
 NAMES = sorted(k[: -len("_matches")] for k in Z.files if k.endswith("_matches"))
-
-
-def _kp(a4):
-    a4 = np.asarray(a4, np.float32).reshape(-1, 4)
-    k = np.zeros(len(a4), pkg.KEYPOINT_DTYPE)
-    k["x"], k["y"], k["size"], k["angle"] = a4[:, 0], a4[:, 1], a4[:, 2], a4[:, 3]
-    k["class_id"] = -1
-    return k
-
-
-def _want_dmatch(pairs):
-    out = np.zeros(len(pairs), pkg.DMATCH_DTYPE)
-    out["queryIdx"], out["trainIdx"], out["imgIdx"] = pairs[:, 0], pairs[:, 1], -1
-    return out
 
 
 @pytest.mark.gpu

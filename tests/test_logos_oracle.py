@@ -59,6 +59,11 @@ def host(tmp_path_factory):
     lib.logos_host_acosf.argtypes = [vp, C.c_int, vp]
     lib.logos_host_support.argtypes = [vp] * 8 + [C.c_longlong, vp, vp]
     lib.logos_host_sort_head.argtypes = [vp, vp, C.c_long, C.c_long]
+    lib.logos_host_kp_ok.argtypes = [C.c_float] * 3
+    lib.logos_host_orientation.argtypes = [C.c_float]
+    lib.logos_host_orientation.restype = C.c_float
+    lib.logos_host_rel_ori.argtypes = [C.c_float, C.c_float]
+    lib.logos_host_rel_ori.restype = C.c_float
     return lib
 
 
@@ -86,6 +91,22 @@ def test_elementary_functions_close_to_libm(host):
     y = np.zeros_like(z)
     host.logos_host_logf(z.ctypes.data, 2, y.ctypes.data)
     assert y[0] == -np.inf and np.isnan(y[1])
+
+
+def test_fixture_lies_inside_the_keypoint_domain(host):
+    """Every keypoint of the DLL's fixture passes kp_ok, in the statement and in the host build: the domain refuses nothing the
+    fixture pins. rel_ori of the host build is the statement's wrap on every pair of the fixture's extreme orientations."""
+    for name in NAMES:
+        for side in ("_kp1", "_kp2"):
+            kp = Z[name + side].astype(np.float32).reshape(-1, 4)
+            assert logos_ref.kp_ok(kp[:, 0], kp[:, 1], kp[:, 3]).all(), name
+            for k in kp[:: max(1, len(kp) // 50)]:
+                assert host.logos_host_kp_ok(float(k[0]), float(k[1]), float(k[3])) == 1
+    o = np.float32([host.logos_host_orientation(a) for a in (0.0, 359.9999, -1.0, 180.0, 360.0)])
+    for o1 in o:
+        for o2 in o:
+            got = np.float32(host.logos_host_rel_ori(float(o1), float(o2)))
+            assert got.tobytes() == logos_ref._wrap_pair(np.float32([o1]) - np.float32([o2]))[0].tobytes()
 
 
 @pytest.mark.parametrize("name", [n for n in NAMES if not n.startswith("empty")])
