@@ -17,7 +17,8 @@ arrays. Two calls of the reference have no effect on the result and are left out
 The reference indexes five contours whether or not five exist (an OpenCV assertion otherwise); here fewer than num_contours borders
 means all of them. Where the reference's order could show -- equal area between the last chosen border and the first one left out --
 this statement ranks by the raster order of the border's start pixel, outer border before hole border. That is NOT the reference's
-rule (MSVC's std::sort on OpenCV's contour order), and the GPU tests avoid such inputs.
+rule (MSVC's std::sort on OpenCV's contour order): the GPU tests' seeded and photographic inputs avoid such ties, and the named
+cases of tests/portrait_cases.py that are tied on purpose test this rule as the project's own.
 """
 import numpy as np
 

@@ -1,16 +1,23 @@
 """-m gpu: portrait mode (gms_portrait_device, gms_median_blur_device, gms_portrait) -- the dilated mask, the selection,
 the blurred image and the portrait byte for byte against the CPU statement tests/portrait_ref.py: on the reference's photograph with
-the project's own stereo_match map, over a seeded sweep of blob masks, sizes and parameters, the median alone (with a pitch), a batch
-against single calls, workspace reuse, graph replay, rejected arguments and the one-shot call.
+the project's own stereo_match map, over a seeded sweep of blob masks, sizes and parameters, over the named cases of
+tests/portrait_cases.py, the median alone (with a pitch), a batch against single calls, workspace reuse, graph replay, rejected
+arguments and the one-shot call.
 
-The sweep's inputs obey one condition, asserted on the CPU for every case: the last chosen border and the first one left out never
-have equal area, because that tie is broken by the statement's own rule and not by the reference's. No case is left out at run time."""
+Two kinds of input, two rules about ties. The photograph, the seeded sweep and the other seeded inputs obey one condition, asserted
+on the CPU for every case: the last chosen border and the first one left out never have equal area, because there the reference's
+own order could show and that tie is broken by the statement's rule, not by the reference's. The named cases are constructed, and
+nine of them are tied at the cut on purpose: they test the project's own stated rule (equal areas rank by the raster index of the
+border's start pixel), which the key's low word has to order and not merely to carry. tests/test_portrait_cases.py holds, on the
+CPU, what each named case contains (tied or not as declared, more than 1024 borders, 64 chosen, chains past 30 000 steps, dilations
+5 to 8, sides of 1 and 8192). No case is left out at run time."""
 import importlib
 import os
 
 import numpy as np
 import pytest
 
+import portrait_cases as C
 import portrait_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -133,6 +140,61 @@ def test_sweep_contains_every_kind_of_shape():
 def test_sweep_equals_statement(pkg, case):
     img, disparity, kw, want = _sweep_want(case)
     _assert_equal(pkg.portraitMode(img, disparity, detail=True, **kw), want, SWEEP[case])
+
+
+@pytest.mark.parametrize("name", C.NAMES)
+def test_named_case_equals_statement(pkg, name):
+    c = C.case(name)
+    _assert_equal(pkg.portraitMode(c["image"], c["disparity"], detail=True, **c["params"]), C.expected(name), name)
+
+
+def test_named_cases_as_one_batch(ctx, pkg):
+    """Five 131 x 259 maps in one run at num_contours 64: one image with more than 1024 keys and 64 chosen, two with a single key
+    each (chains past 30 000 steps), one with 65 equal keys of which the tie rule leaves out the last, one with none -- each equals
+    the statement on that image alone, so nothing of one image's key list, count or chosen roots shows in another's."""
+    names = ("noise_64", "serpentine", "serpentine_inverse", "comb")
+    over = dict(threshold=C.NOISE_THRESHOLD, num_contours=64)      # the constructed maps' 200 is above this threshold too
+    kw = dict(C.case("noise_64")["params"], **over)
+    imgs = [C.case(n)["image"] for n in names] + [C.case("comb")["image"]]
+    disps = [C.case(n)["disparity"] for n in names] + [np.full((131, 259), 255, np.uint8)]
+    wants = [C.expected(n, **over) for n in names] + [R.portrait(imgs[-1], disps[-1], **kw)]
+    counts = [len(w["info"]["contours"]) for w in wants]
+    assert counts[0] > 1024 and counts[1:] == [1, 65, 1, 0] and [len(w["info"]["chosen"]) for w in wants] == [64, 1, 64, 1, 0]
+    for n, w in zip(names[1:], wants[1:]):
+        assert np.array_equal(w["mask"], C.expected(n)["mask"])
+    got = _batch().portrait_batch(np.stack(imgs), np.stack(disps), kw, ctx, detail=True)
+    for i, w in enumerate(wants):
+        _assert_equal([g[i] for g in got], w, ("batch", i))
+    assert not got[2][4].any() and got[0][4].tobytes() == got[3][4].tobytes()     # no border: nothing selected, all blurred
+
+
+def test_tied_cut_follows_the_stated_rule(pkg):
+    """Equal areas at the cut rank by the raster index of the start pixel. Beside the bytes, the visible fact is
+    asserted from the construction alone, so that a statement and a kernel that were wrong together would still fail."""
+    for name, blob_selected in (("ring_then_blob", False), ("blob_then_ring", True)):
+        c = C.case(name)
+        got = pkg.portraitMode(c["image"], c["disparity"], detail=True, **c["params"])
+        _assert_equal(got, C.expected(name), name)
+        sel = got[2] != 0
+        y0, y1, x0, x1 = c["facts"]["blob"]
+        ring_x = c["facts"]["chosen_starts"][0][0]
+        assert sel[y0:y1, x0:x1].all() if blob_selected else not sel[y0:y1, x0:x1].any(), name
+        assert sel[5:14, ring_x:ring_x + 9].all() and int(sel.sum()) == 81 + (96 if blob_selected else 0), name
+    for num, squares in ((5, {3, 1, 6, 4, 2}), (1, {3})):             # the squares with the highest top rows, whatever their column
+        name = f"equal_squares_staggered_{num}"
+        c = C.case(name)
+        got = pkg.portraitMode(c["image"], c["disparity"], detail=True, **c["params"])
+        _assert_equal(got, C.expected(name), name)
+        sel = got[2] != 0
+        for i, top in enumerate(C.SQUARE_TOPS):
+            square = sel[top:top + 7, 4 + 16 * i:11 + 16 * i]
+            assert square.all() if i in squares else not square.any(), (name, i)
+        assert int(sel.sum()) == 49 * num
+    for name in ("dots_lattice_64", "dots_lattice_5", "serpentine_inverse", "row_8192_2", "column_8192_2"):
+        c = C.case(name)                                              # and the first ones in raster order where everything is tied
+        sel = pkg.portraitMode(c["image"], c["disparity"], detail=True, **c["params"])[2] != 0
+        assert int(sel.sum()) == c["facts"]["selected"], name
+        assert all(sel[y, x] for x, y in c["facts"]["chosen_starts"]), name
 
 
 def test_no_value_anywhere_is_blurred_everywhere(pkg):
