@@ -4,19 +4,10 @@
 // and its rows, int32 n_pairs, int32 (a, b) per pair. No arguments: prints usage and exits 2 (the CPU test links this without a
 // device).
 #include <cstdio>
-#include <cstring>
 #include <vector>
 
 #include "mi355_gms.hpp"
-
-static unsigned long long fnv(const std::vector<mi355::DMatch>& m)
-{
-    unsigned long long s = 1469598103934665603ull;
-    std::vector<uint32_t> w(m.size() * 4);
-    if (!m.empty()) std::memcpy(w.data(), m.data(), w.size() * 4);
-    for (uint32_t v : w) s = (s ^ v) * 1099511628211ull;
-    return s;
-}
+#include "test_main_util.h"
 
 template <typename T>
 static int run(FILE* f, size_t width)
@@ -41,22 +32,18 @@ static int run(FILE* f, size_t width)
     for (const auto& p : pairs) {
         std::vector<mi355::DMatch> m;
         mi355::bruteForceMatch(rows[(size_t)p.first], rows[(size_t)p.second], m);
-        std::printf("%zu %llu\n", m.size(), fnv(m));
+        std::printf("%zu %llu\n", m.size(), fnv_words(m));
     }
     std::vector<std::vector<mi355::DMatch>> all;
     std::vector<bool> ok;
     mi355::bruteForceMatchBatch(rows, pairs, all, true, 4.0, 500, &ok);
-    for (size_t p = 0; p < pairs.size(); ++p) std::printf("%zu %llu %d\n", all[p].size(), fnv(all[p]), ok[p] ? 1 : 0);
+    for (size_t p = 0; p < pairs.size(); ++p) std::printf("%zu %llu %d\n", all[p].size(), fnv_words(all[p]), ok[p] ? 1 : 0);
     return 0;
 }
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) {
-        std::fprintf(stderr, "usage: bf_shim_main CASES.bin\n");
-        return 2;
-    }
-    FILE* f = std::fopen(argv[1], "rb");
+    FILE* f = open_input(argc, argv, "bf_shim_main CASES.bin");
     if (!f) return 2;
     int32_t kind = -1;
     if (std::fread(&kind, 4, 1, f) != 1) return 2;

@@ -7,14 +7,11 @@
 #include <vector>
 
 #include "mi355_gms.hpp"
+#include "test_main_util.h"
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) {
-        std::fprintf(stderr, "usage: calib_shim_main IMAGES.bin\n");
-        return 2;
-    }
-    FILE* f = std::fopen(argv[1], "rb");
+    FILE* f = open_input(argc, argv, "calib_shim_main IMAGES.bin");
     if (!f) return 2;
     int32_t hd[5];
     if (std::fread(hd, 4, 5, f) != 5) return 2;

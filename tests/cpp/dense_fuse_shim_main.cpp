@@ -6,25 +6,14 @@
 #include <vector>
 
 #include "mi355_gms.hpp"
-
-static unsigned long long fnv(const void* p, size_t bytes)
-{
-    const uint8_t* v = static_cast<const uint8_t*>(p);
-    unsigned long long s = 1469598103934665603ull;
-    for (size_t i = 0; i < bytes; ++i) s = (s ^ v[i]) * 1099511628211ull;
-    return s;
-}
+#include "test_main_util.h"
 
 template <class T>
 static bool get(FILE* f, T* p, size_t n) { return n == 0 || std::fread(p, sizeof(T), n, f) == n; }
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) {
-        std::fprintf(stderr, "usage: dense_fuse_shim_main CASE.bin\n");
-        return 2;
-    }
-    FILE* f = std::fopen(argv[1], "rb");
+    FILE* f = open_input(argc, argv, "dense_fuse_shim_main CASE.bin");
     if (!f) return 2;
     int32_t h[6];
     if (!get(f, h, 6) || h[0] < 1 || h[0] > 4096 || h[1] < 1 || h[1] > 32 || (h[2] != 1 && h[2] != 3)) return 2;

@@ -8,22 +8,11 @@
 #include <vector>
 
 #include "mi355_gms.hpp"
-
-static unsigned long long fnv(const void* p, size_t bytes)
-{
-    const uint8_t* v = static_cast<const uint8_t*>(p);
-    unsigned long long s = 1469598103934665603ull;
-    for (size_t i = 0; i < bytes; ++i) s = (s ^ v[i]) * 1099511628211ull;
-    return s;
-}
+#include "test_main_util.h"
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) {
-        std::fprintf(stderr, "usage: dense_shim_main PAIR.bin\n");
-        return 2;
-    }
-    FILE* f = std::fopen(argv[1], "rb");
+    FILE* f = open_input(argc, argv, "dense_shim_main PAIR.bin");
     if (!f) return 2;
     int32_t wh[2];
     double num[21];

@@ -7,14 +7,7 @@
 #include <vector>
 
 #include "mi355_gms.hpp"
-
-static unsigned long long fnv(const void* p, size_t bytes)
-{
-    unsigned long long s = 1469598103934665603ull;
-    const unsigned char* b = static_cast<const unsigned char*>(p);
-    for (size_t i = 0; i < bytes; ++i) s = (s ^ b[i]) * 1099511628211ull;
-    return s;
-}
+#include "test_main_util.h"
 
 template <typename T>
 static int run(FILE* f, size_t width, const int32_t* head, uint64_t seed)
@@ -38,11 +31,7 @@ static int run(FILE* f, size_t width, const int32_t* head, uint64_t seed)
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) {
-        std::fprintf(stderr, "usage: logos_dict_shim_main CASE.bin\n");
-        return 2;
-    }
-    FILE* f = std::fopen(argv[1], "rb");
+    FILE* f = open_input(argc, argv, "logos_dict_shim_main CASE.bin");
     if (!f) return 2;
     int32_t kind = -1, head[4];
     uint64_t seed = 0;

@@ -3,27 +3,14 @@
 // Input (little-endian): int32 n_cases, then per case int32 n1, n2, float x, y, size, angle per keypoint of frame 1 then frame 2,
 // int32 words of frame 1 then frame 2. No arguments: prints usage and exits 2 (the CPU test links this without a device).
 #include <cstdio>
-#include <cstring>
 #include <vector>
 
 #include "mi355_gms.hpp"
-
-static unsigned long long fnv(const std::vector<mi355::DMatch>& m)
-{
-    unsigned long long s = 1469598103934665603ull;
-    std::vector<uint32_t> w(m.size() * 4);
-    if (!m.empty()) std::memcpy(w.data(), m.data(), w.size() * 4);
-    for (uint32_t v : w) s = (s ^ v) * 1099511628211ull;
-    return s;
-}
+#include "test_main_util.h"
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) {
-        std::fprintf(stderr, "usage: logos_shim_main CASES.bin\n");
-        return 2;
-    }
-    FILE* f = std::fopen(argv[1], "rb");
+    FILE* f = open_input(argc, argv, "logos_shim_main CASES.bin");
     if (!f) return 2;
     int32_t n_cases = 0;
     if (std::fread(&n_cases, 4, 1, f) != 1) return 2;
@@ -56,13 +43,13 @@ int main(int argc, char** argv)
         for (int c = 0; c < n_cases; ++c) {
             std::vector<mi355::DMatch> m;
             mi355::matchLOGOS(kps[2 * c], kps[2 * c + 1], words[2 * c], words[2 * c + 1], m);
-            std::printf("%zu %llu\n", m.size(), fnv(m));
+            std::printf("%zu %llu\n", m.size(), fnv_words(m));
             pairs.push_back({2 * c, 2 * c + 1});
         }
         std::vector<std::vector<mi355::DMatch>> out;
         std::vector<bool> ok;
         mi355::matchLOGOSBatch(kps, words, 50, pairs, out, &ok);
-        for (int c = 0; c < n_cases; ++c) std::printf("%zu %llu %d\n", out[c].size(), fnv(out[c]), ok[c] ? 1 : 0);
+        for (int c = 0; c < n_cases; ++c) std::printf("%zu %llu %d\n", out[c].size(), fnv_words(out[c]), ok[c] ? 1 : 0);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "%s\n", e.what());
         return 3;

@@ -6,34 +6,11 @@
 #include <vector>
 
 #include "mi355_gms.hpp"
-
-static unsigned long long fnv(const void* q, size_t n)
-{
-    const unsigned char* p = static_cast<const unsigned char*>(q);
-    unsigned long long s = 1469598103934665603ull;
-    for (size_t i = 0; i < n; ++i) s = (s ^ p[i]) * 1099511628211ull;
-    return s;
-}
-
-template <class T>
-static bool read_all(FILE* f, std::vector<T>& v)
-{
-    return v.empty() || std::fread(v.data(), sizeof(T), v.size(), f) == v.size();
-}
-
-template <class T>
-static void print_sum(const std::vector<T>& v)
-{
-    std::printf("%llu\n", fnv(v.data(), v.size() * sizeof(T)));
-}
+#include "test_main_util.h"
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) {
-        std::fprintf(stderr, "usage: match_unique_shim_main RECORDS.bin\n");
-        return 2;
-    }
-    FILE* f = std::fopen(argv[1], "rb");
+    FILE* f = open_input(argc, argv, "match_unique_shim_main RECORDS.bin");
     if (!f) return 2;
     int32_t head[4];
     int64_t total;

@@ -6,21 +6,11 @@
 #include <vector>
 
 #include "mi355_gms.hpp"
-
-static unsigned long long fnv(const std::vector<uint8_t>& v)
-{
-    unsigned long long s = 1469598103934665603ull;
-    for (size_t i = 0; i < v.size(); ++i) s = (s ^ v[i]) * 1099511628211ull;
-    return s;
-}
+#include "test_main_util.h"
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) {
-        std::fprintf(stderr, "usage: portrait_shim_main IMAGE_AND_MAP.bin\n");
-        return 2;
-    }
-    FILE* f = std::fopen(argv[1], "rb");
+    FILE* f = open_input(argc, argv, "portrait_shim_main IMAGE_AND_MAP.bin");
     if (!f) return 2;
     int32_t wh[2];
     if (std::fread(wh, 4, 2, f) != 2) return 2;

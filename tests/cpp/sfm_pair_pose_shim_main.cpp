@@ -5,14 +5,11 @@
 #include <vector>
 
 #include "mi355_gms.hpp"
+#include "test_main_util.h"
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) {
-        std::fprintf(stderr, "usage: sfm_pair_pose_shim_main CASE.bin RESULT.bin\n");
-        return 2;
-    }
-    FILE* f = std::fopen(argv[1], "rb");
+    FILE* f = open_input(argc, argv, "sfm_pair_pose_shim_main CASE.bin RESULT.bin", 2);
     if (!f) return 2;
     int32_t head[2];
     if (std::fread(head, 4, 2, f) != 2 || head[0] < 1 || head[1] < 1) return 2;

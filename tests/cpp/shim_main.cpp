@@ -7,6 +7,7 @@
 #include <utility>
 
 #include "mi355_gms.hpp"
+#include "test_main_util.h"
 
 static uint32_t lcg(uint32_t& s) { s = s * 1664525u + 1013904223u; return s >> 8; }
 
@@ -30,14 +31,7 @@ int main()
     try {
         for (int flags = 0; flags < 2; ++flags) {
             mi355::matchGMS(mi355::Size(w, h), mi355::Size(w, h), kp1, kp2, matches, out, flags != 0, flags != 0);
-            uint64_t sum = 1469598103934665603ull;
-            for (const auto& m : out) {
-                uint32_t bits;
-                __builtin_memcpy(&bits, &m.distance, 4);
-                for (uint32_t v : {(uint32_t)m.queryIdx, (uint32_t)m.trainIdx, (uint32_t)m.imgIdx, bits})
-                    sum = (sum ^ v) * 1099511628211ull;
-            }
-            std::printf("%zu %llu\n", out.size(), (unsigned long long)sum);
+            std::printf("%zu %llu\n", out.size(), fnv_words(out));
         }
         // the batch form: the same pair three times (forwards, with the roles of the frames swapped is another input, so: twice
         // forwards with different flags would need two calls -- one call, one flag set) plus an empty pair in the middle
@@ -49,14 +43,7 @@ int main()
         std::vector<bool> ok;
         mi355::matchGMSBatch(sizes, frames, prs, in, outs, true, true, 6.0, &ok);
         for (size_t p = 0; p < outs.size(); ++p) {
-            uint64_t sum = 1469598103934665603ull;
-            for (const auto& m : outs[p]) {
-                uint32_t bits;
-                __builtin_memcpy(&bits, &m.distance, 4);
-                for (uint32_t v : {(uint32_t)m.queryIdx, (uint32_t)m.trainIdx, (uint32_t)m.imgIdx, bits})
-                    sum = (sum ^ v) * 1099511628211ull;
-            }
-            std::printf("%zu %llu %d\n", outs[p].size(), (unsigned long long)sum, (int)ok[p]);
+            std::printf("%zu %llu %d\n", outs[p].size(), fnv_words(outs[p]), (int)ok[p]);
         }
     } catch (const std::exception& e) {
         std::fprintf(stderr, "error: %s\n", e.what());

@@ -6,25 +6,21 @@ instance (predicate a.d < b.d on a float alone -- the shape of DMatch::operator<
 own instance of the template cannot be run; the cross-check rule is restated from OpenCV's published batchDistance."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bf_select_ref
 import logos_ref
+import hostbuild as hb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-Z = np.load(os.path.join(ROOT, "tests", "golden", "refdll_logos.npz"))
+Z = np.load(os.path.join(hb.ROOT, "tests", "golden", "refdll_logos.npz"))
 SORTS = sorted(int(k.split("_")[1]) for k in Z.files if k.startswith("sort_") and k.endswith("_order"))
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("bfsel") / "libbf_select_host.so")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wextra", "-Werror",
-                           "-I" + os.path.join(ROOT, "sfm-gms_amd", "csrc"), "-o", so, os.path.join(ROOT, "tests", "cpp", "bf_select_host.cpp")])
-    lib = C.CDLL(so)
+def host():
+    lib = C.CDLL(hb.host_lib("bf_select_host.cpp"))
     lib.bf_host_sort_prefix.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_long]
     return lib
 

@@ -7,28 +7,23 @@ Tolerances between two fp64 implementations are not taken from anywhere: the sta
 order of summation changed (points permuted within each view; the sub-pixel window summed backwards), and 100 x the largest difference
 that makes is allowed. The measured values stand next to the assertions."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import calib_cases as CC
 import calib_ref as R
+import hostbuild as hb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "sfm-gms_amd", "csrc")
-SRC = os.path.join(ROOT, "tests", "cpp", "calib_host.cpp")
-FLAGS = ["-O2", "-ffp-contract=off", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + CSRC]
+SRC = "calib_host.cpp"
 NX, NY, N = CC.NX, CC.NY, CC.NX * CC.NY
 FACTOR = CC.FACTOR
 first_points, calib_vector, fixture_images, subpix_tolerance = CC.first_points, CC.calib_vector, CC.fixture_images, CC.subpix_tolerance
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("calib") / "libcalib_host.so")
-    subprocess.check_call(["g++", *FLAGS, "-shared", "-fPIC", "-o", so, SRC])
+def host():
+    so = hb.host_lib(SRC)
     lib = C.CDLL(so)
     lib.calib_host_candidates.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     lib.calib_host_peak_capacity.restype = C.c_longlong
@@ -334,9 +329,8 @@ def test_host_equals_the_statement_on_the_photographs(host, fixture_run, calib_t
     assert measured > 0 and err <= FACTOR * measured
 
 
-def test_stand_alone_program_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "calib_host_asan")
-    subprocess.check_call(["g++", *FLAGS, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DCALIB_HOST_MAIN", "-o", exe, SRC])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+def test_stand_alone_program_under_sanitizers():
+    exe = hb.host_exe_sanitized(SRC, defines=("CALIB_HOST_MAIN",))
+    out = hb.run(exe)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "worst error" in out.stdout and "rms" in out.stdout

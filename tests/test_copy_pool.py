@@ -4,19 +4,14 @@ the pool's hand-off points (a worker "descheduled" between taking a generation a
 caller between publishing a run and working along), with more workers than cores, over thousands of runs whose part counts grow and
 shrink. A worker of one run that reached into the next one left that run waiting forever or returning before every byte had landed
 (the watchdog's "HANG after N runs" / the byte check), and under ThreadSanitizer it is a data race on the run's offsets."""
-import os
-import subprocess
+import hostbuild as hb
 
-import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "copy_pool_stress.cpp")
-INC = ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "sfm-gms_amd", "csrc")]
+SRC = "copy_pool_stress.cpp"
 
 
 def _run(exe, args, env=None):
-    res = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=120,
-                         env=dict(os.environ, **(env or {})))
+    res = hb.run(exe, *args, env=env)
     report = (res.stdout + res.stderr)[-4000:]
     assert "HANG" not in res.stdout, report
     assert "ThreadSanitizer" not in res.stderr, report
@@ -24,21 +19,16 @@ def _run(exe, args, env=None):
     return res.stdout
 
 
-def test_copy_pool_stress(tmp_path):
+def test_copy_pool_stress():
     """2000 runs, 15 workers, hooks sleeping up to 3 ms."""
-    exe = str(tmp_path / "copy_pool_stress")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-pthread", "-Wall", "-Wextra", "-Werror", *INC, "-o", exe, SRC])
+    exe = hb.host_exe(SRC, extra=("-pthread",))          # the pool's workers are std::threads
     out = _run(exe, [2000, 1, 15])
     assert "2000 runs" in out
 
 
-def test_copy_pool_stress_under_thread_sanitizer(tmp_path):
+def test_copy_pool_stress_under_thread_sanitizer():
     """The same under ThreadSanitizer: every copy and check is several times slower there, so the lists are shorter (4-8 parts) and
     the hooks sleep up to 100 ms -- a sleeping worker still outlasts the rest of its run, as it does in the plain build."""
-    exe = str(tmp_path / "copy_pool_stress_tsan")
-    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-pthread", *INC, "-o", exe, SRC],
-                           capture_output=True, text=True)
-    if build.returncode != 0:
-        pytest.skip("this toolchain cannot build with -fsanitize=thread: " + (build.stderr.strip().splitlines() or ["?"])[-1][:200])
+    exe = hb.host_exe_sanitized(SRC, "thread", extra=("-pthread",))         # a race shows under ThreadSanitizer, not under the default set
     out = _run(exe, [120, 2, 15, 8, 100000], env={"TSAN_OPTIONS": "halt_on_error=1"})
     assert "120 runs" in out

@@ -1,44 +1,24 @@
 """The header-only C++ shim's bruteForceMatch entry points (sfm-gms_amd/include/mi355_gms.hpp): mi355::bruteForceMatch on flat
 128-float and 32-byte rows, and mi355::bruteForceMatchBatch. CPU: they compile and link against libgms_hip.so. GPU: both give the
 survivors of tests/bf_select_ref.py."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bf_select_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "sfm-gms_amd", "csrc")
+import hostbuild as hb
 
 
-def _build(tmp_path):
-    exe = str(tmp_path / "bf_shim_main")
-    cmd = ["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "sfm-gms_amd", "include"),
-           os.path.join(ROOT, "tests", "cpp", "bf_shim_main.cpp"), "-L", CSRC, "-lgms_hip", "-Wl,-rpath," + CSRC,
-           "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
-    subprocess.check_call(cmd)
-    return exe
-
-
-def _fnv(m):
-    s = 1469598103934665603
-    for v in np.ascontiguousarray(m).view(np.uint32).reshape(-1):
-        s = ((s ^ int(v)) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-    return s
-
-
-def test_bf_shim_compiles_and_links(tmp_path):
-    exe = _build(tmp_path)
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+def test_bf_shim_compiles_and_links():
+    exe = hb.shim_exe("bf_shim_main.cpp")
+    res = hb.run(exe)
     assert res.returncode == 2 and "usage" in res.stderr
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind", [0, 1])
 def test_bf_shim_matches_restatement(tmp_path, kind):
-    exe = _build(tmp_path)
+    exe = hb.shim_exe("bf_shim_main.cpp")
     rng = np.random.default_rng(71 + kind)
     if kind == 0:
         rows = [rng.integers(0, 256, (n, 32), dtype=np.uint8) for n in (400, 65, 1025)]
@@ -52,11 +32,11 @@ def test_bf_shim_matches_restatement(tmp_path, kind):
         for r in rows:
             f.write(np.int32(len(r)).tobytes() + r.tobytes())
         f.write(np.int32(len(pairs)).tobytes() + np.asarray(pairs, np.int32).tobytes())
-    res = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=600)
+    res = hb.run(exe, path, timeout=600)
     assert res.returncode == 0, res.stderr
     lines = res.stdout.splitlines()
     assert len(lines) == 2 * len(pairs)
     for k, (a, b) in enumerate(pairs):
         want, _, _, _ = bf_select_ref.bf_match_select(rows[a], rows[b], kind == 0)
-        assert lines[k].split() == [str(len(want)), str(_fnv(want))]
-        assert lines[len(pairs) + k].split() == [str(len(want)), str(_fnv(want)), "1"]
+        assert lines[k].split() == [str(len(want)), str(hb.fnv1a(want.tobytes(), words=True))]
+        assert lines[len(pairs) + k].split() == [str(len(want)), str(hb.fnv1a(want.tobytes(), words=True)), "1"]

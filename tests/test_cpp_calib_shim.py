@@ -1,41 +1,28 @@
 """The header-only C++ shim's calibration calls (sfm-gms_amd/include/mi355_gms.hpp): mi355::findChessboardCorners, cornerSubPix,
 calibrateCamera and addChessboardPoints on flat grey images. CPU: they compile and link without a device. GPU: on three named boards
 and one image without a board (tests/calib_cases.py) they give what the Python calls give, to the last digit printed."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import calib_cases as CC
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "sfm-gms_amd", "csrc")
+import hostbuild as hb
 
 
-def _build(tmp_path):
-    exe = str(tmp_path / "calib_shim_main")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), "-I",
-           os.path.join(ROOT, "sfm-gms_amd", "include"), os.path.join(ROOT, "tests", "cpp", "calib_shim_main.cpp"), "-L", CSRC, "-lgms_hip",
-           "-Wl,-rpath," + CSRC, "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
-    subprocess.check_call(cmd)
-    return exe
-
-
-def test_calib_shim_compiles_and_links(tmp_path):
-    res = subprocess.run([_build(tmp_path)], capture_output=True, text=True, timeout=120)
+def test_calib_shim_compiles_and_links():
+    res = hb.run(hb.shim_exe("calib_shim_main.cpp"))
     assert res.returncode == 2 and "usage" in res.stderr
 
 
 @pytest.mark.gpu
 def test_calib_shim_matches_python(tmp_path, pkg):
-    exe = _build(tmp_path)
+    exe = hb.shim_exe("calib_shim_main.cpp")
     names = ("rot0", "covered", "perspective", "edges")          # one size; the second has no board
     imgs = np.stack([CC.case(n).image for n in names])
     n, h, w = imgs.shape
     path = tmp_path / "images.bin"
     path.write_bytes(np.array([n, w, h, CC.NX, CC.NY], np.int32).tobytes() + imgs.tobytes())
-    res = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=600)
+    res = hb.run(exe, path, timeout=600)
     assert res.returncode == 0, res.stderr
     lines = [[float(v) for v in ln.split()] for ln in res.stdout.strip().splitlines()]
     ok, obj, img = pkg.addChessboardPoints(list(imgs), (CC.NX, CC.NY))

@@ -1,48 +1,29 @@
 """The header-only C++ shim's dense fusion (sfm-gms_amd/include/mi355_gms.hpp): mi355::fuseDense. CPU: the shim compiles and links
 without a device. GPU: on the hand-made cases of tests/dense_fuse_cases.py the shim's results equal the statement's
 (tests/dense_fuse_ref.py), compared by digest."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import dense_fuse_cases as fc
 import dense_fuse_ref as fr
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "sfm-gms_amd", "csrc")
-INCLUDES = ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "sfm-gms_amd", "include")]
+import hostbuild as hb
 
 
-def _build(tmp_path):
-    exe = str(tmp_path / "dense_fuse_shim_main")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", *INCLUDES, os.path.join(ROOT, "tests", "cpp", "dense_fuse_shim_main.cpp"), "-L", CSRC,
-                           "-lgms_hip", "-Wl,-rpath," + CSRC, "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
-    return exe
-
-
-def _fnv(a):
-    s = 1469598103934665603
-    for v in np.frombuffer(np.ascontiguousarray(a).tobytes(), np.uint8):
-        s = ((s ^ int(v)) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-    return s
-
-
-def test_dense_fuse_shim_compiles_and_links(tmp_path):
-    res = subprocess.run([_build(tmp_path)], capture_output=True, text=True, timeout=120)
+def test_dense_fuse_shim_compiles_and_links():
+    res = hb.run(hb.shim_exe("dense_fuse_shim_main.cpp"))
     assert res.returncode == 2 and "usage" in res.stderr
 
 
 @pytest.mark.gpu
 def test_dense_fuse_shim_matches_the_statement(tmp_path):
-    exe = _build(tmp_path)
+    exe = hb.shim_exe("dense_fuse_shim_main.cpp")
     for case in fc.hand_cases():
         want = fr.fuse(case["sources"], case["neighbors"], case["channels"], case["tol16"], case["min_support"], case["fused_cap"])
         path = tmp_path / (case["name"] + ".bin")
         path.write_bytes(fc.case_bytes(case, sum(len(s["xyz"]) for s in case["sources"])))
-        res = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=600)
+        res = hb.run(exe, path, timeout=600)
         assert res.returncode == 0, (case["name"], res.stderr)
         lines = res.stdout.split("\n")
         assert lines[0].split() == [str(int(v)) for v in want["counts"]], case["name"]
-        assert lines[1:7] == [str(_fnv(want[k])) for k in ("points", "colors", "source", "index", "support", "conflict")], case["name"]
+        assert lines[1:7] == [str(hb.fnv1a(want[k].tobytes())) for k in ("points", "colors", "source", "index", "support", "conflict")], case["name"]

@@ -1,44 +1,24 @@
 """The header-only C++ shim's dictionary trainer (sfm-gms_amd/include/mi355_gms.hpp): mi355::trainLogosDictionary on flat 128-float
 and 32-byte rows. CPU: it compiles and links against libgms_hip.so. GPU: it gives the dictionary, labels and record of
 tests/logos_dict_ref.py."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import logos_dict_ref as ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "sfm-gms_amd", "csrc")
+import hostbuild as hb
 
 
-def _build(tmp_path):
-    exe = str(tmp_path / "logos_dict_shim_main")
-    cmd = ["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "sfm-gms_amd", "include"),
-           os.path.join(ROOT, "tests", "cpp", "logos_dict_shim_main.cpp"), "-L", CSRC, "-lgms_hip", "-Wl,-rpath," + CSRC,
-           "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
-    subprocess.check_call(cmd)
-    return exe
-
-
-def _fnv(a):
-    s = 1469598103934665603
-    for v in np.ascontiguousarray(a).view(np.uint8).reshape(-1):
-        s = ((s ^ int(v)) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-    return s
-
-
-def test_logos_dict_shim_compiles_and_links(tmp_path):
-    exe = _build(tmp_path)
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+def test_logos_dict_shim_compiles_and_links():
+    exe = hb.shim_exe("logos_dict_shim_main.cpp")
+    res = hb.run(exe)
     assert res.returncode == 2 and "usage" in res.stderr
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind", [0, 1])
 def test_logos_dict_shim_equals_the_statement(tmp_path, kind):
-    exe = _build(tmp_path)
+    exe = hb.shim_exe("logos_dict_shim_main.cpp")
     rng = np.random.default_rng(5 + kind)
     n, n_words, attempts, max_iters, seed = 700, 20, 2, 25, 2**63 + 5
     if kind == 0:
@@ -48,10 +28,10 @@ def test_logos_dict_shim_equals_the_statement(tmp_path, kind):
     path = tmp_path / "case.bin"
     with open(path, "wb") as f:
         f.write(np.array([kind, n, n_words, attempts, max_iters], np.int32).tobytes() + np.uint64(seed).tobytes() + rows.tobytes())
-    res = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=600)
+    res = hb.run(exe, path, timeout=600)
     assert res.returncode == 0, res.stderr
     dic, rec, labels = ref.train_set(rows, kind, n_words, attempts, max_iters, seed)
     lines = res.stdout.splitlines()
-    assert lines[0].split() == [str(_fnv(dic)), str(_fnv(labels)), str(rec["attempt"]), str(rec["iterations"]),
+    assert lines[0].split() == [str(hb.fnv1a(dic.tobytes())), str(hb.fnv1a(labels.tobytes())), str(rec["attempt"]), str(rec["iterations"]),
                                 str(rec["empty_clusters"]), str(rec["compactness"])]
     assert lines[1].split() == ["1"]

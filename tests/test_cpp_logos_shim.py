@@ -2,45 +2,32 @@
 signature and mi355::matchLOGOSBatch. CPU: they compile and link against libgms_hip.so. GPU: the fixture cases of
 tests/golden/refdll_logos.npz through both give the fixture's matches."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "sfm-gms_amd", "csrc")
-Z = np.load(os.path.join(ROOT, "tests", "golden", "refdll_logos.npz"))
+import hostbuild as hb
+
+Z = np.load(os.path.join(hb.ROOT, "tests", "golden", "refdll_logos.npz"))
 NAMES = sorted(k[: -len("_matches")] for k in Z.files if k.endswith("_matches"))
 
-
-def _build(tmp_path):
-    exe = str(tmp_path / "logos_shim_main")
-    cmd = ["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "sfm-gms_amd", "include"),
-           os.path.join(ROOT, "tests", "cpp", "logos_shim_main.cpp"), "-L", CSRC, "-lgms_hip", "-Wl,-rpath," + CSRC,
-           "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
-    subprocess.check_call(cmd)
-    return exe
-
-
-def _fnv(pairs):
+def _records(pairs):
+    """The gms_dmatch records of (query, train) pairs: imgIdx -1, distance 0."""
     rec = np.zeros((len(pairs), 4), np.int32)
     rec[:, :2] = np.asarray(pairs, np.int32).reshape(-1, 2)
     rec[:, 2] = -1
-    s = 1469598103934665603
-    for v in rec.view(np.uint32).reshape(-1):
-        s = ((s ^ int(v)) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-    return s
+    return rec
 
 
-def test_logos_shim_compiles_and_links(tmp_path):
-    exe = _build(tmp_path)
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+def test_logos_shim_compiles_and_links():
+    exe = hb.shim_exe("logos_shim_main.cpp")
+    res = hb.run(exe)
     assert res.returncode == 2 and "usage" in res.stderr
 
 
 @pytest.mark.gpu
 def test_logos_shim_matches_fixture(tmp_path):
-    exe = _build(tmp_path)
+    exe = hb.shim_exe("logos_shim_main.cpp")
     path = tmp_path / "cases.bin"
     with open(path, "wb") as f:
         f.write(np.int32(len(NAMES)).tobytes())
@@ -49,11 +36,11 @@ def test_logos_shim_matches_fixture(tmp_path):
             f.write(np.array([len(k1), len(k2)], np.int32).tobytes())
             f.write(k1.tobytes() + k2.tobytes())
             f.write(Z[name + "_nn1"].astype(np.int32).tobytes() + Z[name + "_nn2"].astype(np.int32).tobytes())
-    res = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=600)
+    res = hb.run(exe, path, timeout=600)
     assert res.returncode == 0, res.stderr
     lines = res.stdout.splitlines()
     assert len(lines) == 2 * len(NAMES)
     for c, name in enumerate(NAMES):
         want = Z[name + "_matches"]
-        assert lines[c].split() == [str(len(want)), str(_fnv(want))], name
-        assert lines[len(NAMES) + c].split() == [str(len(want)), str(_fnv(want)), "1"], name
+        assert lines[c].split() == [str(len(want)), str(hb.fnv1a(_records(want), words=True))], name
+        assert lines[len(NAMES) + c].split() == [str(len(want)), str(hb.fnv1a(_records(want), words=True)), "1"], name

@@ -2,41 +2,24 @@
 on flat 8-bit vectors. CPU: they compile and link against libgms_hip.so. GPU: on the reference's photograph (reduced, with a synthetic
 disparity map) they equal the Python results."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "sfm-gms_amd", "csrc")
-GOLDEN = os.path.join(ROOT, "tests", "golden", "image_portrait_robot.npz")
+import hostbuild as hb
+
+GOLDEN = os.path.join(hb.ROOT, "tests", "golden", "image_portrait_robot.npz")
 
 
-def _build(tmp_path):
-    exe = str(tmp_path / "portrait_shim_main")
-    cmd = ["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "sfm-gms_amd", "include"),
-           os.path.join(ROOT, "tests", "cpp", "portrait_shim_main.cpp"), "-L", CSRC, "-lgms_hip", "-Wl,-rpath," + CSRC,
-           "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
-    subprocess.check_call(cmd)
-    return exe
-
-
-def _fnv(b):
-    s = 1469598103934665603
-    for v in np.frombuffer(b, np.uint8):
-        s = ((s ^ int(v)) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-    return s
-
-
-def test_portrait_shim_compiles_and_links(tmp_path):
-    exe = _build(tmp_path)
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+def test_portrait_shim_compiles_and_links():
+    exe = hb.shim_exe("portrait_shim_main.cpp")
+    res = hb.run(exe)
     assert res.returncode == 2 and "usage" in res.stderr
 
 
 @pytest.mark.gpu
 def test_portrait_shim_matches_python(tmp_path, pkg):
-    exe = _build(tmp_path)
+    exe = hb.shim_exe("portrait_shim_main.cpp")
     bgr = np.ascontiguousarray(np.load(GOLDEN)["left_bgr"][:120, :200])
     h, w = bgr.shape[:2]
     yy, xx = np.mgrid[:h, :w]
@@ -44,7 +27,7 @@ def test_portrait_shim_matches_python(tmp_path, pkg):
     disparity[::7, ::5] = 255
     path = tmp_path / "image.bin"
     path.write_bytes(np.array([w, h], np.int32).tobytes() + bgr.tobytes() + disparity.tobytes())
-    res = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=600)
+    res = hb.run(exe, path, timeout=600)
     assert res.returncode == 0, res.stderr
     want = [pkg.portraitMode(bgr, disparity), pkg.medianBlur(bgr, 5), pkg.medianBlur(np.ascontiguousarray(bgr[:, :, 0]), 7)]
-    assert res.stdout.split() == [str(_fnv(a.tobytes())) for a in want]
+    assert res.stdout.split() == [str(hb.fnv1a(a.tobytes())) for a in want]

@@ -2,22 +2,11 @@
 CPU: it compiles and links against libgms_hip.so and fails loudly without a device. GPU: same data
 through the oracle, same survivors."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "sfm-gms_amd", "csrc")
-
-
-def _build(tmp_path):
-    exe = str(tmp_path / "shim_main")
-    cmd = ["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "sfm-gms_amd", "include"),
-           os.path.join(ROOT, "tests", "cpp", "shim_main.cpp"), "-L", CSRC, "-lgms_hip", "-Wl,-rpath," + CSRC,
-           "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
-    subprocess.check_call(cmd)
-    return exe
+import hostbuild as hb
 
 
 def _lcg_data():
@@ -44,16 +33,16 @@ def _lcg_data():
 
 
 @pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="this box has a GPU")
-def test_shim_compiles_links_and_fails_loudly_without_gpu(tmp_path):
-    exe = _build(tmp_path)
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+def test_shim_compiles_links_and_fails_loudly_without_gpu():
+    exe = hb.shim_exe("shim_main.cpp")
+    res = hb.run(exe)
     assert res.returncode == 3 and "no usable HIP device" in res.stderr
 
 
 @pytest.mark.gpu
-def test_shim_matches_oracle(tmp_path, oracle, pkg, synth):
-    exe = _build(tmp_path)
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+def test_shim_matches_oracle(oracle, pkg, synth):
+    exe = hb.shim_exe("shim_main.cpp")
+    res = hb.run(exe, timeout=300)
     assert res.returncode == 0, res.stderr
     lines = res.stdout.split()
     size, xy1, xy2, q, t, img, dist = _lcg_data()
@@ -62,18 +51,10 @@ def test_shim_matches_oracle(tmp_path, oracle, pkg, synth):
     for k, flags in enumerate(((False, False), (True, True))):
         rc, want, _, _ = oracle.match(size, size, synth.make_keypoints(xy1), synth.make_keypoints(xy2), m, *flags, 6.0)
         assert rc == 0 and len(want) > 500
-        s = 1469598103934665603
-        for v in want.view(np.uint32).reshape(-1):
-            s = ((s ^ int(v)) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-        assert (int(lines[2 * k]), int(lines[2 * k + 1])) == (len(want), s)
+        assert (int(lines[2 * k]), int(lines[2 * k + 1])) == (len(want), hb.fnv1a(want.tobytes(), words=True))
     # the batch form (matchGMSBatch -> gms_filter_host_batch): the pair, an empty pair, the first half of the pair's matches
-    def checksum(arr):
-        s = 1469598103934665603
-        for v in arr.view(np.uint32).reshape(-1):
-            s = ((s ^ int(v)) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-        return s
     kp1, kp2 = synth.make_keypoints(xy1), synth.make_keypoints(xy2)
     for p, mm in enumerate((m, m[:0], m[: len(m) // 2])):
         rc, want, _, _ = oracle.match(size, size, kp1, kp2, mm, True, True, 6.0)
         assert rc == 0
-        assert [int(x) for x in lines[4 + 3 * p: 7 + 3 * p]] == [len(want), checksum(want), 1]
+        assert [int(x) for x in lines[4 + 3 * p: 7 + 3 * p]] == [len(want), hb.fnv1a(want.tobytes(), words=True), 1]

@@ -2,19 +2,15 @@
 (sfm-gms_amd/csrc/dense_fuse_core.h through the stand-alone program tests/cpp/dense_fuse_host.cpp), byte for byte, plain and under
 sanitizers; that each case of tests/dense_fuse_cases.py holds what it is named for; the workspace's layout; and the rule's effect on
 the rendered plane seen by three cameras. The host program never runs inside Python: cases go to it as files."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import dense_fuse_cases as fc
 import dense_fuse_ref as fr
+import hostbuild as hb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "sfm-gms_amd", "csrc")
-SRC = os.path.join(ROOT, "tests", "cpp", "dense_fuse_host.cpp")
-FLAGS = ["-O2", "-ffp-contract=off", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + CSRC, "-I" + os.path.join(ROOT, "include")]
+SRC = "dense_fuse_host.cpp"
 
 def statement(case):
     return fr.fuse(case["sources"], case["neighbors"], case["channels"], case["tol16"], case["min_support"], case["fused_cap"])
@@ -24,7 +20,7 @@ def run_host(exe, case, tmp_path):
     total_cap = sum(len(s["xyz"]) for s in case["sources"])
     src, dst = tmp_path / (case["name"] + ".in"), tmp_path / (case["name"] + ".out")
     src.write_bytes(fc.case_bytes(case, total_cap))
-    res = subprocess.run([exe, str(src), str(dst)], capture_output=True, text=True, timeout=120)
+    res = hb.run(exe, src, dst)
     assert res.returncode == 0, (case["name"], res.returncode, res.stderr)
     return dst.read_bytes()
 
@@ -35,9 +31,8 @@ def cases():
 
 
 @pytest.fixture(scope="module")
-def host_exe(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("dense_fuse") / "dense_fuse_host")
-    subprocess.check_call(["g++", *FLAGS, "-o", exe, SRC])
+def host_exe():
+    exe = hb.host_exe(SRC)
     return exe
 
 
@@ -123,17 +118,13 @@ def test_host_build_equals_statement_on_scene(scene_sources, host_exe, tmp_path)
 
 
 def test_stand_alone_program_under_sanitizers(cases, tmp_path):
-    exe = str(tmp_path / "dense_fuse_host_asan")
-    subprocess.check_call(["g++", *FLAGS, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, SRC])
+    exe = hb.host_exe_sanitized(SRC)
     for case in cases:
         assert run_host(exe, case, tmp_path) == fc.result_bytes(statement(case), case["channels"]), case["name"]
 
 
-def test_layout(tmp_path):
-    exe = str(tmp_path / "dense_fuse_layout_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-                           os.path.join(ROOT, "tests", "cpp", "dense_fuse_layout_check.cpp"), "-o", exe])
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+def test_layout():
+    res = hb.run(hb.host_exe("dense_fuse_layout_check.cpp"))
     assert res.returncode == 0 and res.stdout.strip() == "dense_fuse_layout: ok", res.stdout
 
 

@@ -2,24 +2,20 @@
 (sfm-gms_amd/csrc/dog_core.h through tests/cpp/dog_host.cpp), on every pixel, and the properties the definition implies
 (DESIGN.md §4.7d)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import dog_ref
 import pyramid_ref
+import hostbuild as hb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "dog_host.cpp")
-FLAGS = ["-O2", "-ffp-contract=off", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "sfm-gms_amd", "csrc")]
+SRC = "dog_host.cpp"
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("dog") / "libdog_host.so")
-    subprocess.check_call(["g++", *FLAGS, "-shared", "-fPIC", "-o", so, SRC])
+def host():
+    so = hb.host_lib(SRC)
     lib = C.CDLL(so)
     lib.dog_host_table.argtypes = [C.c_int, C.c_void_p]
     lib.dog_host_blur.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -162,9 +158,8 @@ def test_select_takes_the_strongest_in_raster_order():
     assert len(dog_ref.select(cand, 0)[0]) == 0
 
 
-def test_sanitizer_run_of_the_stand_alone_program(tmp_path):
-    exe = str(tmp_path / "dog_host_asan")
-    subprocess.check_call(["g++", *FLAGS, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DDOG_HOST_MAIN", "-o", exe, SRC])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+def test_sanitizer_run_of_the_stand_alone_program():
+    exe = hb.host_exe_sanitized(SRC, defines=("DOG_HOST_MAIN",))
+    out = hb.run(exe)
     assert out.returncode == 0, out.stdout + out.stderr
     assert out.stdout.startswith("dog_host: tiny ")

@@ -4,7 +4,6 @@ the refinement is for: more RANSAC inliers from the same matches on the committe
 import ctypes as C
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,19 +11,17 @@ import pytest
 import dog_ref
 import dog_refine_ref as ref
 from test_dog_ref import small_images
+import hostbuild as hb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "dog_refine_host.cpp")
-FLAGS = ["-O2", "-ffp-contract=off", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "sfm-gms_amd", "csrc")]
+SRC = "dog_refine_host.cpp"
 SIZES = [(33, 33), (97, 65), (64, 48), (130, 200), (641, 479), (1030, 50)]     # (width, height): those of tests/test_gpu_dog.py
 CONTRASTS = (0, 128)
-SFM_PAIR = os.path.join(ROOT, "tests", "golden", "image_sfm_pair_1008x756.npz")
+SFM_PAIR = os.path.join(hb.ROOT, "tests", "golden", "image_sfm_pair_1008x756.npz")
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("dog_refine") / "libdog_refine_host.so")
-    subprocess.check_call(["g++", *FLAGS, "-shared", "-fPIC", "-o", so, SRC])
+def host():
+    so = hb.host_lib(SRC)
     lib = C.CDLL(so)
     lib.dog_refine_host_scale.restype = lib.dog_refine_host_coord.restype = lib.dog_refine_host_size.restype = C.c_float
     lib.dog_refine_host_scale.argtypes = [C.c_int]
@@ -201,9 +198,8 @@ def test_more_inliers_on_the_sfm_pair(oracle):
     assert n[(True, 1.0)][0] >= n[(False, 1.0)][0]
 
 
-def test_sanitizer_run_of_the_stand_alone_program(tmp_path):
-    exe = str(tmp_path / "dog_refine_host_asan")
-    subprocess.check_call(["g++", *FLAGS, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DDOG_REFINE_HOST_MAIN", "-o", exe, SRC])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+def test_sanitizer_run_of_the_stand_alone_program():
+    exe = hb.host_exe_sanitized(SRC, defines=("DOG_REFINE_HOST_MAIN",))
+    out = hb.run(exe)
     assert out.returncode == 0, out.stdout + out.stderr
     assert out.stdout.startswith("dog_refine_host: tiny ")

@@ -4,24 +4,21 @@
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import grad_desc_ref as gd
 import pyramid_ref
+import hostbuild as hb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STEREO = os.path.join(ROOT, "tests", "golden", "image_stereo_pair_450x375.npz")
-SRC = os.path.join(ROOT, "tests", "cpp", "grad_desc_host.cpp")
-FLAGS = ["-O2", "-ffp-contract=off", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "sfm-gms_amd", "csrc")]
+STEREO = os.path.join(hb.ROOT, "tests", "golden", "image_stereo_pair_450x375.npz")
+SRC = "grad_desc_host.cpp"
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("graddesc") / "libgrad_desc_host.so")
-    subprocess.check_call(["g++", *FLAGS, "-shared", "-fPIC", "-o", so, SRC])
+def host():
+    so = hb.host_lib(SRC)
     lib = C.CDLL(so)
     lib.gd_host_window_table.argtypes = [C.c_void_p]
     lib.gd_host_dir_table.argtypes = [C.c_void_p, C.c_void_p]
@@ -186,9 +183,8 @@ def test_rot90_with_eight_bins_more_is_the_same_row():
     assert a.any()
 
 
-def test_sanitizer_run_of_the_stand_alone_program(tmp_path):
-    exe = str(tmp_path / "grad_desc_host_asan")
-    subprocess.check_call(["g++", *FLAGS, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DGRAD_DESC_MAIN", "-o", exe, SRC])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+def test_sanitizer_run_of_the_stand_alone_program():
+    exe = hb.host_exe_sanitized(SRC, defines=("GRAD_DESC_MAIN",))
+    out = hb.run(exe)
     assert out.returncode == 0, out.stdout + out.stderr
     assert out.stdout.startswith("grad_desc_host: noise ")

@@ -2,8 +2,6 @@
 numpy; sfm-gms_amd/csrc/logos_dict_core.h is what the kernels run, compiled here for the host (tests/cpp/logos_dict_host.cpp). The
 GPU is held to the statement's bytes in tests/test_gpu_logos_dict.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,8 +9,8 @@ import pytest
 import logos_dict_cases as cases
 import logos_dict_ref as ref
 import logos_words_ref
+import hostbuild as hb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HAMMING, L2 = ref.HAMMING, ref.L2
 
 
@@ -188,12 +186,8 @@ def test_quantised_mean_by_hand():
 
 # ---- logos_dict_core.h, built for the host, against the statement -----------------------------------------------------------------
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("logos_dict") / "liblogos_dict_host.so")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wextra", "-Werror",
-                           "-I" + os.path.join(ROOT, "sfm-gms_amd", "csrc"), "-o", so,
-                           os.path.join(ROOT, "tests", "cpp", "logos_dict_host.cpp")])
-    lib = C.CDLL(so)
+def host():
+    lib = C.CDLL(hb.host_lib("logos_dict_host.cpp"))
     vp, u64, i64 = C.c_void_p, C.c_ulonglong, C.c_longlong
     lib.dict_host_draw.argtypes = [u64] * 5
     lib.dict_host_draw.restype = u64

@@ -6,15 +6,14 @@ it in numpy; sfm-gms_amd/csrc/logos_core.h is what the kernels run per lane, com
 """
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import logos_ref
+import hostbuild as hb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIXTURE = os.path.join(ROOT, "tests", "golden", "refdll_logos.npz")
+FIXTURE = os.path.join(hb.ROOT, "tests", "golden", "refdll_logos.npz")
 
 
 def fixture_cases():
@@ -49,11 +48,8 @@ def test_fixture_has_real_peaks():
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("logos") / "liblogos_host.so")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wextra", "-Werror",
-                           "-I" + os.path.join(ROOT, "sfm-gms_amd", "csrc"), "-o", so, os.path.join(ROOT, "tests", "cpp", "logos_host.cpp")])
-    lib = C.CDLL(so)
+def host():
+    lib = C.CDLL(hb.host_lib("logos_host.cpp"))
     vp = C.c_void_p
     lib.logos_host_logf.argtypes = [vp, C.c_int, vp]
     lib.logos_host_acosf.argtypes = [vp, C.c_int, vp]

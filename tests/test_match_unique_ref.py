@@ -4,7 +4,6 @@ plain and under the address / undefined-behaviour sanitizers) against the statem
 indices (n_multi > 0 without the plane, 0 with it, the views untouched), inputs that are one-to-one already, the five-view scene with
 ground truth through the bundle adjustment's statement, and what of the C ABI is host arithmetic."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,10 +14,9 @@ import sfm_ba_ref as B
 import sfm_ref
 import sfm_register_cases as rcases
 import sfm_register_ref as R
+import hostbuild as hb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST_SRC = os.path.join(ROOT, "tests", "cpp", "match_unique_host.cpp")
-FLAGS = ["-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "sfm-gms_amd", "csrc"), "-I" + os.path.join(ROOT, "include")]
+HOST_SRC = "match_unique_host.cpp"
 NAMES = sorted(ucases.CASES)
 REGISTER_ARRAYS = ("plan", "views", "registration", "points_world", "track", "cloud", "cloud_id", "cloud_obs", "cloud_est", "cloud_spread", "summary")
 UNTOUCHED = ("views", "registration", "points_world")
@@ -50,7 +48,7 @@ def write_input(c, path):
 def run_host(exe, c, tmp):
     src, dst = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
     write_input(c, src)
-    res = subprocess.run([exe, src, dst], capture_output=True, text=True, timeout=120)
+    res = hb.run(exe, src, dst)
     assert res.returncode == 0, res.stdout + res.stderr
     raw = np.fromfile(dst, np.uint8)
     m = c["total_m"]
@@ -98,9 +96,8 @@ def test_the_shape_cases_reach_what_they_are_for():
 
 
 @pytest.fixture(scope="module")
-def host_exe(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("match_unique_host") / "match_unique_host")
-    subprocess.check_call(["g++", "-O2", *FLAGS, "-o", exe, HOST_SRC])
+def host_exe():
+    exe = hb.host_exe(HOST_SRC)
     return exe
 
 
@@ -112,11 +109,7 @@ def test_host_build_of_the_core_equals_the_statement(host_exe, tmp_path, name, c
 
 
 def test_stand_alone_host_program_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "match_unique_host_san")
-    build = subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", *FLAGS, "-o", exe, HOST_SRC],
-                           capture_output=True, text=True)
-    if build.returncode != 0:
-        pytest.skip("this toolchain cannot build with -fsanitize=address,undefined: " + (build.stderr.strip().splitlines() or ["?"])[-1][:200])
+    exe = hb.host_exe_sanitized(HOST_SRC)
     for name, c in all_cases():
         if name.startswith("tiles_past_256"):
             continue                                            # (a million keypoints: the plain build covers it)

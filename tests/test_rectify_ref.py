@@ -3,19 +3,15 @@ kernels compile (sfm-gms_amd/csrc/rectify_core.h through tests/cpp/rectify_host.
 and cloud records; the plan's properties; the cases of tests/rectify_cases.py; and the accuracy of the whole chain on a rendered
 plane."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import rectify_cases as rc
 import rectify_ref as rr
+import hostbuild as hb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "sfm-gms_amd", "csrc")
-SRC = os.path.join(ROOT, "tests", "cpp", "rectify_host.cpp")
-FLAGS = ["-O2", "-ffp-contract=off", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + CSRC, "-I" + os.path.join(ROOT, "include")]
+SRC = "rectify_host.cpp"
 ll = C.c_longlong
 VIEW_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("registered", "<i4"), ("pair", "<i4")])
 
@@ -25,9 +21,8 @@ def _camera(camera, dist):
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("rectify") / "librectify_host.so")
-    subprocess.check_call(["g++", *FLAGS, "-shared", "-fPIC", "-o", so, SRC])
+def host():
+    so = hb.host_lib(SRC)
     lib = C.CDLL(so)
     lib.rectify_host_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     lib.rectify_host_identity_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -242,9 +237,8 @@ def test_scene_chain_accuracy(scene_chain):
     assert np.array_equal(colors, r1.reshape(-1)[pixel])
 
 
-def test_stand_alone_program_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "rectify_host_asan")
-    subprocess.check_call(["g++", *FLAGS, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DRECTIFY_HOST_MAIN", "-o", exe, SRC])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+def test_stand_alone_program_under_sanitizers():
+    exe = hb.host_exe_sanitized(SRC, defines=("RECTIFY_HOST_MAIN",))
+    out = hb.run(exe)
     assert out.returncode == 0, out.stderr
     assert out.stdout.startswith("rectify_host: checksum ")

@@ -6,8 +6,6 @@ frames than cloud entries, a cloud_cap past n_tracks, the sorted-neighbour test,
 conjugate gradients and of the outer loop, records that do not fit the arrays --, the host build of sfm_ba_core.h
 (tests/cpp/sfm_ba_host.cpp), and the C ABI's host-only parts."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,10 +15,9 @@ import sfm_ba_ref as B
 import sfm_ref
 import sfm_register_ref as R
 from test_sfm_register_ref import check_against_truth, close, truth_scene
+import hostbuild as hb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST_SRC = os.path.join(ROOT, "tests", "cpp", "sfm_ba_host.cpp")
-FLAGS = ["-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "sfm-gms_amd", "csrc"), "-I" + os.path.join(ROOT, "include")]
+HOST_SRC = "sfm_ba_host.cpp"
 CASE_NAMES = sorted(cases.CASES)
 
 # What the order of the observations inside every sum is worth (DESIGN.md §4.10c has the measured values): per case the largest
@@ -314,9 +311,8 @@ def test_cg_iters_of_the_cg_cases_by_both_orders():
 
 # ---- the host build -------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("sba") / "libsba_host.so")
-    subprocess.check_call(["g++", "-O2", *FLAGS, "-shared", "-fPIC", "-o", so, HOST_SRC])
+def host():
+    so = hb.host_lib(HOST_SRC)
     lib = C.CDLL(so)
     vp, dbl = C.c_void_p, C.c_double
     lib.sba_host_observation.argtypes = [vp, vp, vp, dbl, dbl, dbl, dbl, vp, vp, vp, vp, vp, vp]
@@ -385,13 +381,8 @@ def test_host_small_solves_and_rodrigues(host):
     assert np.array_equal(E, np.eye(3))
 
 
-def test_stand_alone_host_program_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "sba_host_asan")
-    build = subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", *FLAGS, "-DSBA_HOST_MAIN", "-o", exe,
-                            HOST_SRC], capture_output=True, text=True)
-    if build.returncode != 0:
-        pytest.skip("this toolchain cannot build with -fsanitize=address,undefined: " + (build.stderr.strip().splitlines() or ["?"])[-1][:200])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+def test_stand_alone_host_program_under_sanitizers():
+    out = hb.run(hb.host_exe_sanitized(HOST_SRC, defines=("SBA_HOST_MAIN",)))
     assert out.returncode == 0 and out.stdout.startswith("sba_host: tiny 1 0.000000 0.000000 1 0.500000 0.250000 4.000000 1 3.000000 layout 0 bad"), \
         out.stdout + out.stderr
 

@@ -2,8 +2,6 @@
 (tests/cpp/sfm_pair_pose_host.cpp, a stand-alone program that reads a case file) against the numpy statement byte for byte, plain and
 under sanitizers; the registration's own views giving back each ok pair's two-view pose and scale; what the records are worth on the
 rendered plane of tests/dense_fuse_cases.py when a view is wrong; and the argument checks of the public calls."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,11 +9,9 @@ import pytest
 import dense_fuse_cases as fc
 import sfm_pair_pose_cases as pc
 import sfm_pair_pose_ref as pp
+import hostbuild as hb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "sfm_pair_pose_host.cpp")
-FLAGS = ["-O2", "-ffp-contract=off", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "sfm-gms_amd", "csrc"),
-         "-I" + os.path.join(ROOT, "include")]
+SRC = "sfm_pair_pose_host.cpp"
 
 # Measured here (numpy 2.x, x86-64) on the five-view scene, records from the registration's own views against the two-view records and
 # the registration's S: the largest |difference| of R 7.8e-16, of t 3.3e-16, of S relative 1.2e-15; the statement against itself
@@ -43,7 +39,7 @@ def run_host(exe, case, tmp_path):
     name, views, frame_pairs = case
     src, dst = tmp_path / (name + ".in"), tmp_path / (name + ".out")
     src.write_bytes(pp.case_bytes(views, pp.pair_table(frame_pairs)))
-    res = subprocess.run([exe, str(src), str(dst)], capture_output=True, text=True, timeout=120)
+    res = hb.run(exe, src, dst)
     assert res.returncode == 0, (name, res.returncode, res.stderr)
     return dst.read_bytes()
 
@@ -72,15 +68,13 @@ def test_cases_hold_what_they_are_named_for(cases):
 
 
 def test_host_build_equals_statement(cases, tmp_path):
-    exe = str(tmp_path / "sfm_pair_pose_host")
-    subprocess.check_call(["g++", *FLAGS, "-o", exe, SRC])
+    exe = hb.host_exe(SRC)
     for case in cases:
         assert run_host(exe, case, tmp_path) == pp.result_bytes(*pc.statement(case)), case[0]
 
 
 def test_stand_alone_program_under_sanitizers(cases, tmp_path):
-    exe = str(tmp_path / "sfm_pair_pose_host_asan")
-    subprocess.check_call(["g++", *FLAGS, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, SRC])
+    exe = hb.host_exe_sanitized(SRC)
     for case in cases:
         assert run_host(exe, case, tmp_path) == pp.result_bytes(*pc.statement(case)), case[0]
 

@@ -6,8 +6,6 @@ or plan do not fit (cases.UNFIT) have tests of their own here, and the stand-alo
 sfr::pair_fits under the sanitizers."""
 import ctypes as C
 import hashlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,11 +13,10 @@ import pytest
 import sfm_ref
 import sfm_register_cases as cases
 import sfm_register_ref as R
+import hostbuild as hb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST_SRC = os.path.join(ROOT, "tests", "cpp", "sfm_register_host.cpp")
-LAYOUT_SRC = os.path.join(ROOT, "tests", "cpp", "sfm_register_layout_check.cpp")
-FLAGS = ["-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "sfm-gms_amd", "csrc"), "-I" + os.path.join(ROOT, "include")]
+HOST_SRC = "sfm_register_host.cpp"
+LAYOUT_SRC = "sfm_register_layout_check.cpp"
 CASE_NAMES = sorted(cases.CASES)
 SANE_NAMES = [name for name in CASE_NAMES if name not in cases.UNFIT]   # the pair list alone says what the device reads
 # sha256 over the statement's arrays (in the order of their names) on the five cases it was first written for, as it stood before it
@@ -298,9 +295,8 @@ def test_tracks_against_scipy(ref_of, name):
 
 # ---- host builds ----------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("sfr") / "libsfr_host.so")
-    subprocess.check_call(["g++", "-O2", *FLAGS, "-shared", "-fPIC", "-o", so, HOST_SRC])
+def host():
+    so = hb.host_lib(HOST_SRC)
     lib = C.CDLL(so)
     lib.sfr_host_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     lib.sfr_host_register.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -373,13 +369,8 @@ def test_dtypes_match_the_statement(pkg):
     assert lib.gms_sfm_register_workspace_bytes(8, 7, 16000, 21000) % 256 == 0 and lib.gms_sfm_register_workspace_bytes(1, 0, 0, 0) > 0
 
 
-def test_stand_alone_host_program_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "sfr_host_asan")
-    build = subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", *FLAGS, "-DSFR_HOST_MAIN", "-o", exe,
-                            HOST_SRC], capture_output=True, text=True)
-    if build.returncode != 0:
-        pytest.skip("this toolchain cannot build with -fsanitize=address,undefined: " + (build.stderr.strip().splitlines() or ["?"])[-1][:200])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+def test_stand_alone_host_program_under_sanitizers():
+    out = hb.run(hb.host_exe_sanitized(HOST_SRC, defines=("SFR_HOST_MAIN",)))
     assert out.returncode == 0 and out.stdout.startswith("sfr_host: tiny 0 40 2.000000"), out.stdout + out.stderr
     # sfr::pair_fits on the records of misfit_records, match_off = 2^63 - 2 with m = 5 among them: a sum of the two would stop the
     # program here ("signed integer overflow", -fno-sanitize-recover)
@@ -388,22 +379,16 @@ def test_stand_alone_host_program_under_sanitizers(tmp_path):
 
 # ---- the workspace's layout -----------------------------------------------------------------------------------------------------------
 def _run_layout(exe):
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    res = hb.run_clean(exe)
     report = (res.stdout + res.stderr)[-4000:]
-    assert "runtime error" not in res.stderr and "AddressSanitizer" not in res.stderr, report
     assert res.returncode == 0 and "cases: 0 bad" in res.stdout, report
 
 
-def test_layout(tmp_path, pkg):
-    exe = str(tmp_path / "sfm_register_layout_check")
-    subprocess.check_call(["g++", "-O2", *FLAGS, "-o", exe, LAYOUT_SRC])
+def test_layout(pkg):
+    exe = hb.host_exe(LAYOUT_SRC)
     _run_layout(exe)
 
 
-def test_layout_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "sfm_register_layout_check_san")
-    build = subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", *FLAGS, "-o", exe, LAYOUT_SRC],
-                           capture_output=True, text=True)
-    if build.returncode != 0:
-        pytest.skip("this toolchain cannot build with -fsanitize=address,undefined: " + (build.stderr.strip().splitlines() or ["?"])[-1][:200])
+def test_layout_under_sanitizers():
+    exe = hb.host_exe_sanitized(LAYOUT_SRC)
     _run_layout(exe)

@@ -2,19 +2,15 @@
 kernels compile (sfm-gms_amd/csrc/speckle_core.h through the stand-alone program tests/cpp/speckle_host.cpp), byte for byte, plain and
 under sanitizers; that each case of tests/speckle_cases.py holds what it is named for; idempotence; the workspace's layout; and the
 arguments that are refused. The host program never runs inside Python: cases go to it as files."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import speckle_cases as sc
 import speckle_ref as sr
+import hostbuild as hb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "sfm-gms_amd", "csrc")
-SRC = os.path.join(ROOT, "tests", "cpp", "speckle_host.cpp")
-FLAGS = ["-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + CSRC, "-I" + os.path.join(ROOT, "include")]
+SRC = "speckle_host.cpp"
 NAMES = {"plus_on_lattice_131x67", "plus_on_lattice_135x71", "serpentine_70x40", "serpentine_259x131", "constant", "singletons", "ramp_exact",
          "ramp_one_more", "extremes", "diagonal_only", "new_val_inside", "thin_1x1", "thin_1x300", "thin_300x1", "thin_8192x1",
          "random_blobs_131x67", "random_blobs_259x131"}
@@ -27,14 +23,13 @@ def runs():
 def run_host(exe, disp, new_val, size, diff, tmp_path, tag):
     src, dst = tmp_path / (tag + ".in"), tmp_path / (tag + ".out")
     src.write_bytes(sc.case_bytes(disp, new_val, size, diff))
-    res = subprocess.run([exe, str(src), str(dst)], capture_output=True, text=True, timeout=120)
+    res = hb.run(exe, src, dst)
     return res.returncode, (dst.read_bytes() if res.returncode == 0 else res.stderr)
 
 
 @pytest.fixture(scope="module")
-def host_exe(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("speckle") / "speckle_host")
-    subprocess.check_call(["g++", *FLAGS, "-o", exe, SRC])
+def host_exe():
+    exe = hb.host_exe(SRC)
     return exe
 
 
@@ -103,19 +98,15 @@ def test_host_build_equals_statement(host_exe, tmp_path):
 
 
 def test_stand_alone_program_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "speckle_host_asan")
-    subprocess.check_call(["g++", *FLAGS, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, SRC])
+    exe = hb.host_exe_sanitized(SRC)
     for c, k in runs():
         size, diff, _ = c["runs"][k]
         rc, got = run_host(exe, c["disp"], c["new_val"], size, diff, tmp_path, f"{c['name']}_{k}")
         assert rc == 0 and got == sc.result_bytes(*sc.expected(c["name"], k)), (c["name"], k, got if rc else "")
 
 
-def test_layout(tmp_path):
-    exe = str(tmp_path / "speckle_layout_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-                           os.path.join(ROOT, "tests", "cpp", "speckle_layout_check.cpp"), "-o", exe])
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+def test_layout():
+    res = hb.run(hb.host_exe("speckle_layout_check.cpp"))
     assert res.returncode == 0 and res.stdout.strip() == "speckle_layout: ok", res.stdout
 
 

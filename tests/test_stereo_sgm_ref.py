@@ -3,8 +3,6 @@ the vectorised form over a parameter sweep, the host build of stereo_sgm_core.h 
 0 against StereoBM, the bound 0 <= L <= C + p2 and the parameter rule at 65535, the committed 450 x 375 pair against its ground truth
 beside StereoBM, and the named cases of tests/stereo_sgm_cases.py: each contains what it is named for, by the statement's own census."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,16 +10,14 @@ import pytest
 import stereo_bm_ref as B
 import stereo_sgm_cases as cases
 import stereo_sgm_ref as R
+import hostbuild as hb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "stereo_sgm_host.cpp")
-FLAGS = ["-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "sfm-gms_amd", "csrc"), "-I" + os.path.join(ROOT, "include")]
+SRC = "stereo_sgm_host.cpp"
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("sgm") / "libsgm_host.so")
-    subprocess.check_call(["g++", *FLAGS, "-shared", "-fPIC", "-o", so, SRC])
+def host():
+    so = hb.host_lib(SRC)
     lib = C.CDLL(so)
     lib.sgm_host_params_ok.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.sgm_host_aggregate.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
@@ -128,10 +124,9 @@ def test_host_build_on_named_cases(host, name):
     assert (got[0] == want[0]).all() and (got[1] == want[1]).all()
 
 
-def test_sanitizer_run_of_the_stand_alone_program(tmp_path):
-    exe = str(tmp_path / "sgm_host_asan")
-    subprocess.check_call(["g++", *FLAGS, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DSGM_HOST_MAIN", "-o", exe, SRC])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+def test_sanitizer_run_of_the_stand_alone_program():
+    exe = hb.host_exe_sanitized(SRC, defines=("SGM_HOST_MAIN",))
+    out = hb.run(exe)
     assert out.returncode == 0, out.stdout + out.stderr
     assert out.stdout.startswith("sgm_host: tiny ")
 

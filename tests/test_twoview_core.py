@@ -4,24 +4,18 @@ on the GPU only) against the numpy restatement oracle/sfm_ref.py, which goes abo
 LU solve, companion-matrix roots, SVD null vector). findEssentialMat lives in opencv_world452 (an import library in the reference):
 parity unpinned; these tests pin the two implementations to each other."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import sfm_ref
 import twoview_scenes as scenes
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import hostbuild as hb
 
 
 @pytest.fixture(scope="module")
-def tvh(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("tvh") / "libtvh.so")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wextra", "-Werror",
-                           "-I" + os.path.join(ROOT, "sfm-gms_amd", "csrc"), "-o", so, os.path.join(ROOT, "tests", "cpp", "twoview_host.cpp")])
-    lib = C.CDLL(so)
+def tvh():
+    lib = C.CDLL(hb.host_lib("twoview_host.cpp"))
     vp = C.c_void_p
     lib.tvh_five_point.argtypes = [vp] * 5
     lib.tvh_rng.argtypes = [C.c_uint64, C.c_int, C.c_int, vp]

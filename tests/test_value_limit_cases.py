@@ -4,8 +4,6 @@ something: FAST score 255 and a quota inside its tie, the gradient descriptor's 
 |D_1|, refinement terms beyond those of the noise and block images. The host builds of the kernels' headers equal the statements on
 these inputs byte for byte. Every property is asserted and its number printed."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,36 +15,28 @@ import grad_desc_ref as gd
 import pyramid_ref
 import value_limit_cases as vc
 from test_dog_ref import small_images
+import hostbuild as hb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ["-O2", "-ffp-contract=off", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "sfm-gms_amd", "csrc")]
 SMALL_SIZES = [(33, 33), (97, 65), (64, 48), (130, 200), (641, 479), (1030, 50)]     # those of tests/test_dog_refine_ref.py
 
 
-def _build(tmp_path_factory, name):
-    """The host build of tests/cpp/<name>.cpp, as tests/test_grad_desc_ref.py, test_dog_ref.py and test_dog_refine_ref.py compile it."""
-    so = str(tmp_path_factory.mktemp(name) / f"lib{name}.so")
-    subprocess.check_call(["g++", *FLAGS, "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "cpp", name + ".cpp")])
-    return C.CDLL(so)
-
-
 @pytest.fixture(scope="module")
-def grad_host(tmp_path_factory):
-    lib = _build(tmp_path_factory, "grad_desc_host")
+def grad_host():
+    lib = C.CDLL(hb.host_lib("grad_desc_host.cpp"))
     lib.gd_host_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     return lib
 
 
 @pytest.fixture(scope="module")
-def dog_host(tmp_path_factory):
-    lib = _build(tmp_path_factory, "dog_host")
+def dog_host():
+    lib = C.CDLL(hb.host_lib("dog_host.cpp"))
     lib.dog_host_candidates.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     return lib
 
 
 @pytest.fixture(scope="module")
-def refine_host(tmp_path_factory):
-    lib = _build(tmp_path_factory, "dog_refine_host")
+def refine_host():
+    lib = C.CDLL(hb.host_lib("dog_refine_host.cpp"))
     lib.dog_refine_host_offsets.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     return lib
 

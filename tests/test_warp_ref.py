@@ -2,25 +2,20 @@
 header the kernels compile (sfm-gms_amd/csrc/warp_core.h through tests/cpp/warp_host.cpp), byte for byte, and the properties that do
 not depend on the statement."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import warp_ref
+import hostbuild as hb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "sfm-gms_amd", "csrc")
-SRC = os.path.join(ROOT, "tests", "cpp", "warp_host.cpp")
-FLAGS = ["-O2", "-ffp-contract=off", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + CSRC]
+SRC = "warp_host.cpp"
 ll = C.c_longlong
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("warp") / "libwarp_host.so")
-    subprocess.check_call(["g++", *FLAGS, "-shared", "-fPIC", "-o", so, SRC])
+def host():
+    so = hb.host_lib(SRC)
     lib = C.CDLL(so)
     lib.warp_host_resize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, ll, C.c_void_p, C.c_int, C.c_int, ll]
     lib.warp_host_warp_affine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, ll, C.c_void_p, C.c_void_p, C.c_int, C.c_int, ll]
@@ -161,18 +156,13 @@ def test_accepted_arguments(host):
     assert not ok(1, 4, 4, 3, 11, 4, 4, 12) and not ok(1, 4, 4, 3, 12, 4, 4, 11)
 
 
-def test_stand_alone_program_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "warp_host_asan")
-    subprocess.check_call(["g++", *FLAGS, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DWARP_HOST_MAIN", "-o", exe, SRC])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+def test_stand_alone_program_under_sanitizers():
+    exe = hb.host_exe_sanitized(SRC, defines=("WARP_HOST_MAIN",))
+    out = hb.run(exe)
     assert out.returncode == 0, out.stderr
     assert out.stdout.startswith("warp_host: checksum ")
 
 
-def test_warp_shim_compiles_and_links(tmp_path):
-    exe = str(tmp_path / "warp_shim_main")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "sfm-gms_amd", "include"),
-                           os.path.join(ROOT, "tests", "cpp", "warp_shim_main.cpp"), "-L", CSRC, "-lgms_hip", "-Wl,-rpath," + CSRC,
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
-    res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+def test_warp_shim_compiles_and_links():
+    res = hb.run(hb.shim_exe("warp_shim_main.cpp"))
     assert res.returncode == 2 and "usage" in res.stderr

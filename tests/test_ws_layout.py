@@ -8,40 +8,31 @@ the library before the layouts existed (tests/golden/ws_layout_sizes.txt, made b
 do the public gms_*_workspace_bytes functions of the built library, refusals included."""
 import ctypes as C
 import os
-import subprocess
 
-import pytest
+import hostbuild as hb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "ws_layout_check.cpp")
-FIXTURE = os.path.join(ROOT, "tests", "golden", "ws_layout_sizes.txt")
-FLAGS = ["-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "sfm-gms_amd", "csrc"), "-I" + os.path.join(ROOT, "include")]
+
+SRC = "ws_layout_check.cpp"
+FIXTURE = os.path.join(hb.ROOT, "tests", "golden", "ws_layout_sizes.txt")
 
 
 def _run(exe, seed):
-    res = subprocess.run([exe, FIXTURE, str(seed)], capture_output=True, text=True, timeout=120)
+    res = hb.run_clean(exe, FIXTURE, seed)
     report = (res.stdout + res.stderr)[-4000:]
-    assert "runtime error" not in res.stderr and "AddressSanitizer" not in res.stderr, report
     with open(FIXTURE) as f:
         lines = sum(1 for _ in f)
     assert res.returncode == 0 and f"{lines} fixture lines: 0 bad" in res.stdout, report
 
 
-def test_ws_layout(tmp_path):
-    exe = str(tmp_path / "ws_layout_check")
-    subprocess.check_call(["g++", "-O2", *FLAGS, "-o", exe, SRC])
+def test_ws_layout():
+    exe = hb.host_exe(SRC)
     _run(exe, 1)
     _run(exe, 2)
 
 
-def test_ws_layout_under_sanitizers(tmp_path):
+def test_ws_layout_under_sanitizers():
     """The same under AddressSanitizer and UndefinedBehaviorSanitizer (host code, a CPU build)."""
-    exe = str(tmp_path / "ws_layout_check_san")
-    build = subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", *FLAGS, "-o", exe, SRC],
-                           capture_output=True, text=True)
-    if build.returncode != 0:
-        pytest.skip("this toolchain cannot build with -fsanitize=address,undefined: " +
-                    (build.stderr.strip().splitlines() or ["?"])[-1][:200])
+    exe = hb.host_exe_sanitized(SRC)
     _run(exe, 1)
 
 
